@@ -6,20 +6,28 @@ One "step" = one pass of the hot path over one batch of synthetic u8 frames ALRE
   -> detections in HBM.
 `value` is quoted in the precision mode whose -m gpu test asserts BASELINE.json's tolerance (scores / coords within 1e-3 of the fp32
 path, identical detection sets): `--precision f16x2`, the default.  The plain fp16-storage mode (5e-3 worst case, tests/test_gpu_e2e.py)
-is measured in the same run and reported under `secondary`.
+is measured in a `--full` run and reported under `secondary`.
 `--streams` (default 4) independent batches are kept in flight (step i on stream i mod 4, own plan and decode scratch; the part has four
 compute pipes: 3 -> 79 k, 4 -> 82 k, 5 -> 68 k, 6 -> 72 k, 8 -> 75 k images/s whoever creates the streams, profiles/r05_diag_batch_streams.txt);
-the one-batch-in-flight rate is measured in the same run and reported beside it.
+the one-batch-in-flight rate is measured in a `--full` run and reported beside it.
 N>1: one process per GPU (torch.distributed / RCCL used only for the barrier + max-over-ranks of the
 timing); images are sharded across ranks, weights replicated, NO data-path collective ("weak" scaling).  `python bench.py --gpus N`
 starts the N ranks itself (re-executes under torch.distributed.run on 127.0.0.1) when it is not already running under a launcher, and
 refuses loudly when the box has fewer than N devices.  `--stub` replaces the GPU step by a fixed sleep and RCCL by gloo: the launcher,
 rendezvous, barrier and max-over-ranks path of the bench can then be exercised on a CPU-only box (tests/test_bench_launcher.py).
 
-Timing: W warm-up steps, then regions of EXACTLY K steps each, bracketed by barrier + synchronize on both sides; when one region
-is shorter than 0.25 s (K small) the region is repeated and the MEDIAN region time is used (`timed_regions` says how many).
+Timing: W warm-up steps (at least 3), then ONE region of EXACTLY K steps (`--steps`), bracketed by barrier + synchronize on both sides;
+`ms_per_step` = the region's time / K.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with
+`--dump-outputs DIR` writes what the last timed step computed, as a caller of the step receives it, to DIR/<name>.npy (float32):
+detections + counts (or, with --from-host, the host rows + offsets) and the network's output tensors behind them.  Frames and
+weights are seeded, so two builds run with the same arguments can be compared output for output.
+
+A plain run (no `--full`) sets up, warms up, times the K steps, dumps if asked and prints the headline line.  `--full` adds
+everything else this file measures: the one-batch rate, per-launch profiles and the roofline, the from-host rate, the secondary
+variants, the training step and the CPU baseline.
+
+Prints ONE JSON line on rank 0 (contract in the task statement); with `--full` it also holds
   roofline        the dominant kernel, HIP-event timing on the launch stream, algorithmic bytes = SURVEY 8(d) in+out fp16
   cpu_baseline    the CPU path timed on this box's host cores on a bounded sample (oracle port + torch-CPU/oneDNN graph)
   value_from_host the same step fed from pinned host memory (H2D copy in front of the replayed graph, detections written straight into pinned
@@ -396,8 +404,8 @@ def main():
     ap.add_argument('--steps', type=int, default=200)
     ap.add_argument('--warmup', type=int, default=20)
     ap.add_argument('--batch', type=int, default=32, help='images per GPU per step (BASELINE: 32)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-secondary', action='store_true', help='skip the secondary measurements (variants, f16x2 mode, training step)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without the CPU baseline')
+    ap.add_argument('--no-secondary', action='store_true', help='--full without the secondary measurements (variants, f16x2 mode, training step)')
     ap.add_argument('--streams', type=int, default=4, help='independent batches in flight: step i runs on stream i %% S with its own plan, '
                     'outputs and decode scratch (consecutive steps are independent batches)')
     ap.add_argument('--letterbox', action='store_true', help='SURVEY 8(d) variant (ii) as the timed step: 240x320 camera frames, letterboxed '
@@ -413,6 +421,9 @@ def main():
     ap.add_argument('--cpu-baseline-only', action='store_true', help='print the cpu_baseline object alone (no GPU needed)')
     ap.add_argument('--mode', choices=['inference', 'train'], default='inference',
                     help="'train': BASELINE configs[3] (yolo_mobilev2 1.0 training step, 16 images/GPU, RCCL gradient all-reduce)")
+    ap.add_argument('--full', action='store_true', help='besides the headline: one-batch rate, per-launch profiles and roofline, from-host '
+                    'rate, secondary variants, training step, CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help="write the last timed step's results to DIR/<name>.npy (float32)")
     args = ap.parse_args()
     if args.cpu_worker:
         return _cpu_worker_main(json.loads(args.cpu_worker))
@@ -480,12 +491,32 @@ def main():
                     self.pipe.host_input(i).copy_(h)              # the frames of every slot wait in pinned host memory
 
         def step(self):
+            self.last_slot = self.pipe.next_slot()
             if self.from_host:
                 # every slot's frames wait in pinned memory: the copy of the NEXT submit's batch is started before this one is launched
                 # (Pipeline.stage_host: what a producer thread does when it has filled a slot) - each batch still crosses PCIe inside the timed region
                 self.pipe.stage_host(self.pipe.next_slot() + 1)
-                return self.pipe.submit_host(None)
-            return self.pipe.submit(self.src, sync_input=False)   # resident frames: nothing to order them behind
+                self.last = self.pipe.submit_host(None)
+            else:
+                self.last = self.pipe.submit(self.src, sync_input=False)   # resident frames: nothing to order them behind
+            return self.last
+
+        def dump(self, d):
+            """The last step's results as its caller receives them (+ the network outputs they were decoded from) -> d/<name>.npy, float32."""
+            d.mkdir(parents=True, exist_ok=True)
+            torch.cuda.synchronize()
+            if self.from_host:
+                rows, off = self.last.result()
+                arrs = {'detections': rows, 'detection_offsets': off}
+            else:
+                dets, counts = self.last[0].cpu().numpy().copy(), self.last[1].cpu().numpy()
+                for b, n in enumerate(counts):
+                    dets[b, n:] = 0.0                             # rows past an image's count are scratch, not results
+                arrs = {'detections': dets, 'detection_counts': counts}
+            for o in self.pipe.outs[self.last_slot]:
+                arrs[f'network_output_{o.shape[1]}x{o.shape[2]}'] = o[:B].cpu().numpy()
+            for k, v in arrs.items():
+                np.save(d / f'{k}.npy', np.ascontiguousarray(v, dtype=np.float32))
 
         def measure(self, steps, warmup, min_s=MIN_REGION_S, max_regions=64):
             for _ in range(max(warmup, 3)):
@@ -524,11 +555,47 @@ def main():
     S = max(1, args.streams)
     use_graph = not args.eager
     head = Harness(S, args.precision, letterbox=args.letterbox, from_host=args.from_host, graph=use_graph)
-    elapsed, regions = head.measure(args.steps, args.warmup)
+    elapsed, regions = head.measure(args.steps, args.warmup, max_regions=1)
     ms_per_step = elapsed / args.steps * 1e3
     value = world * B * args.steps / elapsed
     host_us = head.host_s * 1e6
     graph_nodes = max((g.nodes for sl in head.pipe.slots for g in sl.graphs.values()), default=0)
+    if args.dump_outputs and rank == 0:
+        head.dump(Path(args.dump_outputs))
+    inflight = f'{S} batches in flight' if S > 1 else 'one batch in flight'
+    out = {
+        'metric': f'images/sec end-to-end, yolo_mobilev1-0.75 320x240 b32 (`value_from_host`: SURVEY 8(d) end to end - u8 frames in pinned host '
+                  f'memory -> H2D -> normalise -> backbone + heads -> decode -> NMS -> detections in host memory; `value`: the same step with the '
+                  f'frames already resident in HBM, which is what the bench contract fixes `value` to be; {inflight})',
+        'value': round(value, 1), 'unit': 'images/sec', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
+        'ms_per_step': round(ms_per_step, 4), 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
+        'dtype': 'f16 storage / f32 accumulate' if args.precision == 'f16' else 'f16x2 (compensated fp16 MFMA operands: x = hi + lo, fp32 accumulate)',
+        'data': 'synthetic u8 frames resident in HBM, seeded random-init weights',
+        'timed_regions': regions,
+        'full': args.full,
+        'config': {'workload': 'configs[1]: yolo_mobilev1 alpha=0.75, network tensor 224x320x3 (320x240 frame, SURVEY F1), '
+                               f'20-class VOC head, u8 normalise + backbone/head + python-mode decode + per-class NMS; {inflight} '
+                               '(independent batches on separate HIP streams, one plan each)',
+                   'batch_per_gpu': B, 'global_batch': B * world,
+                   'launch_mode': 'graph' if use_graph else 'eager', 'graph_nodes_per_step': graph_nodes,
+                   'streams': 'created by the library back to back (yk_stream_create): one hardware queue each; more than four lose (4 compute pipes)',
+                   'schedule': getattr(head.pipe, 'schedule', None),
+                   'host_us_per_step': round(host_us, 1), 'batches_in_flight': S, 'precision': args.precision,
+                   'tolerance_carried': ('BASELINE north_star: identical detection sets, scores / coords within 1e-3 max '
+                                         '(tests/test_gpu_e2e.py::test_north_star_*)' if args.precision == 'f16x2' else
+                                         'fp16-storage budget: scores within 5e-3 max, >= 97 % of detections reproduced (tests/test_gpu_e2e.py)'),
+                   'frames': ('240x320 letterboxed on GPU' if args.letterbox else '224x320 native') +
+                             (', from pinned host memory, detections copied back' if args.from_host else ', resident in HBM'),
+                   'parallelism': f'image-sharded x{world}, no collective'},
+    }
+    if not args.full:                                                # a plain run: the headline and nothing else
+        head.close()
+        if rank == 0:
+            print(json.dumps(out))
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     single = Harness(1, args.precision, letterbox=args.letterbox, from_host=args.from_host, graph=use_graph)
     el1, _ = single.measure(min(args.steps, 100), 5)
     single_ms = el1 / min(args.steps, 100) * 1e3
@@ -648,27 +715,16 @@ def main():
         alg_gb = spec.act_elems_per_image() * 2 * B / 1e9                     # in + out of every conv layer once, fp16
         alg_gflop = 2.0 * spec.macs_per_image() * B / 1e9
         roof_step_us = alg_gb / HBM_PEAK_GBS * 1e6                            # the whole step is HBM-bound under this model
-        inflight = f'{S} batches in flight' if S > 1 else 'one batch in flight'
-        out = {
-            'metric': f'images/sec end-to-end, yolo_mobilev1-0.75 320x240 b32 (`value_from_host`: SURVEY 8(d) end to end - u8 frames in pinned host '
-                      f'memory -> H2D -> normalise -> backbone + heads -> decode -> NMS -> detections in host memory; `value`: the same step with the '
-                      f'frames already resident in HBM, which is what the bench contract fixes `value` to be; {inflight})',
-            'value': round(value, 1), 'value_from_host': None if value_from_host is None else round(value_from_host, 1),
+        out.update({
+            'value_from_host': None if value_from_host is None else round(value_from_host, 1),
             'from_host_frac_of_value': None if value_from_host is None else round(value_from_host / value, 3),
             'from_host_h2d_GBps': None if value_from_host is None else round(value_from_host / world * 224 * 320 * 3 / 1e9, 2),
             'from_host_per_rank': None if per_rank_fh is None else {'images_per_sec': per_rank_fh, 'min': min(per_rank_fh), 'max': max(per_rank_fh)},
             'host_placement': {'numa_node_of_gpu': numa.get('node'), 'cpus_bound': numa.get('cpus'), 'pci': numa.get('pci')},
-            'unit': 'images/sec', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
-            'ms_per_step': round(ms_per_step, 4), 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
-            'dtype': 'f16 storage / f32 accumulate' if args.precision == 'f16' else 'f16x2 (compensated fp16 MFMA operands: x = hi + lo, fp32 accumulate)',
-            'data': 'synthetic u8 frames resident in HBM, seeded random-init weights',
-            'timed_regions': regions,
-            'config': {'workload': 'configs[1]: yolo_mobilev1 alpha=0.75, network tensor 224x320x3 (320x240 frame, SURVEY F1), '
-                                   f'20-class VOC head, u8 normalise + backbone/head + python-mode decode + per-class NMS; {inflight} '
-                                   '(independent batches on separate HIP streams, one plan each)',
-                       'batch_per_gpu': B, 'global_batch': B * world, 'launches_per_step': len(launches) + 3,
-                       'launch_mode': 'graph' if use_graph else 'eager', 'graph_nodes_per_step': graph_nodes,
-                       'streams': 'created by the library back to back (yk_stream_create): one hardware queue each; more than four lose (4 compute pipes)',
+            'roofline': roof,
+        })
+        out['config'].update({
+                       'launches_per_step': len(launches) + 3,
                        'schedule': sched_head,
                        'latency_schedule': {'what': 'the plan of one_batch_in_flight_*: engine.Pipeline(depth=1) -> YK_SCHEDULE_LATENCY (late backbone and heads as '
                                                     'two launches of per-image workgroup clusters)',
@@ -676,24 +732,16 @@ def main():
                                             'sum_kernels_us': round(float(lat_ms.sum()) * 1e3, 1),
                                             'step_frac_time_weighted': round(lat_roof_sum / (float(lat_ms.sum()) * 1e3), 4), 'families': lat_fam,
                                             'per_kernel_us': {f'{i}:{lat_launches[i][0][:72]}': round(float(lat_ms[i]) * 1e3, 2) for i in range(len(lat_ms))}},
-                       'host_us_per_step': round(host_us, 1),
                        'from_host_host_us_per_step': None if fh_host_us is None else round(fh_host_us, 1),
                        'from_host_host_blocked_us_per_step': None if fh_wait_us is None else round(fh_wait_us, 1),
-                       'from_host_host_busy_us_per_step': None if fh_wait_us is None else round(fh_host_us - fh_wait_us, 1), 'batches_in_flight': S, 'precision': args.precision,
-                       'tolerance_carried': ('BASELINE north_star: identical detection sets, scores / coords within 1e-3 max '
-                                             '(tests/test_gpu_e2e.py::test_north_star_*)' if args.precision == 'f16x2' else
-                                             'fp16-storage budget: scores within 5e-3 max, >= 97 % of detections reproduced (tests/test_gpu_e2e.py)'),
-                       'frames': ('240x320 letterboxed on GPU' if args.letterbox else '224x320 native') +
-                                 (', from pinned host memory, detections copied back' if args.from_host else ', resident in HBM'),
+                       'from_host_host_busy_us_per_step': None if fh_wait_us is None else round(fh_host_us - fh_wait_us, 1),
                        'one_batch_in_flight_ms_per_step': round(single_ms, 4),
                        'one_batch_in_flight_images_per_sec': round(world * B / (single_ms * 1e-3), 1),
                        'algorithmic_GB_per_step': round(alg_gb, 4), 'algorithmic_GFLOP_per_step': round(alg_gflop, 2),
                        'step_roofline_us': round(roof_step_us, 1),
                        'step_frac_of_roofline': round(roof_step_us / (ms_per_step * 1e3), 4),
-                       'one_batch_step_frac_of_roofline': round(roof_step_us / (single_ms * 1e3), 4),
-                       'parallelism': f'image-sharded x{world}, no collective'},
-            'roofline': roof,
-        }
+                       'one_batch_step_frac_of_roofline': round(roof_step_us / (single_ms * 1e3), 4)})
+
     def rate(S_, prec, lb, fh, steps=60, graph=None):
         hs = Harness(S_, prec, letterbox=lb, from_host=fh, graph=use_graph if graph is None else graph)
         el, _ = hs.measure(steps, 30, min_s=0.25, max_regions=16)

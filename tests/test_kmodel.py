@@ -32,11 +32,30 @@ def gold():
     return np.load(GOLD / 'kmodel_dog_golden.npz')
 
 
-def test_fixture_is_the_references_file():
-    ref = Path('/root/reference/yolo3_frame_test_public/kfpkg/kpu_yolov3.kfpkg')
-    if not ref.exists():
-        pytest.skip('reference tree not present (GPU box)')
-    assert kmodel.read_kfpkg(ref) == (GOLD / 'yolo.kmodel').read_bytes()
+def test_fixture_is_the_references_file(tmp_path):
+    """tests/golden/yolo.kmodel is the `.kmodel` member of the reference's kpu_yolov3.kfpkg, byte for byte: its size, CRC-32 and SHA-256
+    are the ones recorded from that package (tests/golden/make_kfpkg_manifest.py), and read_kfpkg extracts it from a package laid out
+    the same way."""
+    import hashlib
+    import json
+    import zipfile
+    man = json.loads((GOLD / 'kfpkg_manifest.json').read_text())
+    data = (GOLD / 'yolo.kmodel').read_bytes()
+    member = [m for m in man['members'] if m['name'].endswith('.kmodel')]
+    assert len(member) == 1 and member[0]['size'] == man['kmodel_size'] == len(data)
+    assert member[0]['crc32'] == zipfile.crc32(data)
+    assert man['kmodel_sha256'] == hashlib.sha256(data).hexdigest()
+    pkg = tmp_path / man['package']
+    with zipfile.ZipFile(pkg, 'w', zipfile.ZIP_DEFLATED) as z:
+        for m in man['members']:
+            if m['name'] == 'flash-list.json':
+                z.writestr(m['name'], man['flash_list_json'])
+            elif m['name'].endswith('.kmodel'):
+                z.writestr(m['name'], data)
+            else:
+                z.writestr(m['name'], b'\0' * m['size'])                 # the firmware image: not part of the fixture
+    assert [i.filename for i in zipfile.ZipFile(pkg).infolist()] == [m['name'] for m in man['members']]
+    assert kmodel.read_kfpkg(pkg) == data
 
 
 def test_container_parses_into_the_yolo_mobilev1_graph(km):

@@ -1,7 +1,8 @@
 """Pin oracle/region_layer_ref.c against the reference's own region_layer.c.
 
 (a) committed golden vectors produced by the compiled reference (tests/golden/make_region_golden.py)
-(b) the live oracle/_ref build, when present, on fresh seeded inputs (incl. hypothesis shapes)
+(b) stored outputs of the compiled reference on seeded inputs of several shapes (tests/golden/make_region_live_golden.py),
+    re-checked against the live oracle/_ref build when it is present
 """
 import numpy as np
 import pytest
@@ -30,18 +31,24 @@ def test_golden_cases_bit_exact(golden_dir):
         np.testing.assert_array_equal(dets, g[n + '/dets'], err_msg=n)
 
 
-@pytest.mark.skipif(not oracle.have_ref(), reason='oracle/_ref not built (needs /root/reference)')
 @pytest.mark.parametrize('W,H,A,C,thr,nms,net', [
     (10, 7, 3, 20, 0.6, 0.3, (320, 224)), (20, 14, 3, 20, 0.1, 0.3, (320, 224)),
     (13, 13, 3, 20, 0.2, 0.5, (416, 416)), (5, 3, 5, 2, 0.05, 0.2, (160, 224)), (1, 1, 1, 1, 0.0, 0.5, (320, 224)),
     (20, 14, 3, 1, 0.3, 0.3, (320, 224)),
 ])
-def test_live_reference_bit_exact(W, H, A, C, thr, nms, net):
-    rng = np.random.default_rng(W * 1000 + H * 10 + C)
-    anchor = rng.uniform(0.05, 0.9, 2 * A).astype(np.float32)
+def test_live_reference_bit_exact(W, H, A, C, thr, nms, net, golden_dir):
+    """The reference's outputs on these seeded inputs are stored (tests/golden/make_region_live_golden.py); where oracle/_ref is built,
+    the live reference must still produce them."""
+    g = np.load(golden_dir / 'region_live_golden.npz')
+    key = f'{W}x{H}x{A}x{C}_{thr}_{nms}_{net[0]}x{net[1]}'
+    anchor = g[key + '/anchor']
     for scale in (6.0, 2.0):
-        x = rng.uniform(-scale, scale, (A, 5 + C, H, W)).astype(np.float32)
-        ro, rb, rp, rd = oracle.ref_region_run(x, anchor, W, H, A, C, thr, nms, net)
+        k = f'{key}/s{scale:g}'
+        x = g[k + '/input']
+        ro, rb, rp, rd = g[k + '/output'], g[k + '/boxes'], g[k + '/probs'], g[k + '/dets']
+        if oracle.have_ref():
+            for live, stored in zip(oracle.ref_region_run(x, anchor, W, H, A, C, thr, nms, net), (ro, rb, rp, rd)):
+                np.testing.assert_array_equal(live, stored)
         out, boxes, probs = oracle.region_run(x, anchor, W, H, A, C, thr, nms, net)
         np.testing.assert_array_equal(out, ro)
         np.testing.assert_array_equal(boxes, rb)

@@ -5,7 +5,7 @@ cd "$GRAFT_REPO_ROOT" || exit 1
 R=$PWD; CALL=$1; O=$R/gpurun_out/$CALL; mkdir -p "$O"
 CS=$R/k210_yolo_framework_amd/csrc
 # bench <tag> [ENV=..]...: one bench.py line (no CPU leg, no secondaries) -> $O/bench_<tag>.json + a one-line summary
-bench() { local tag=$1; shift; ( env "$@" timeout 400 python bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-secondary ) > $O/bench_$tag.json 2> $O/bench_$tag.err
+bench() { local tag=$1; shift; ( env "$@" timeout 400 python bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --no-secondary ) > $O/bench_$tag.json 2> $O/bench_$tag.err
   python - <<PY
 import json
 try:

@@ -14,5 +14,5 @@ timeout -k 5 120 python tests/diag_drift.py yolo_mobilev1 0.75 > $O/drift_v1.txt
 timeout -k 5 200 python tools/pipebench.py tiny_yolo 1.0 416 416 64 > $O/pipe_tiny.txt 2>&1
 timeout -k 5 200 python tools/pipebench.py yolo_mobilev2 1.0 224 320 32 > $O/pipe_v2.txt 2>&1
 timeout -k 5 200 python tools/pipebench.py yolo 1.0 416 416 16 > $O/pipe_yolo.txt 2>&1
-timeout -k 5 400 python bench.py > $O/bench_line.json 2> $O/bench.err; echo bench rc=$?; tail -c 300 $O/bench_line.json
+timeout -k 5 400 python bench.py --full > $O/bench_line.json 2> $O/bench.err; echo bench rc=$?; tail -c 300 $O/bench_line.json
 ls $O/stats $O/fetch $O/write $O/train

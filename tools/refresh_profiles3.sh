@@ -12,6 +12,6 @@ fi
 cd $R
 timeout -k 5 120 python tools/xbench.py > $O/x2_per_launch.txt 2>&1
 if [ "$1" = "full" ]; then
-  timeout -k 5 500 python bench.py > $O/bench_line.json 2> $O/bench.err; echo bench rc=$?; tail -c 300 $O/bench_line.json
+  timeout -k 5 500 python bench.py --full > $O/bench_line.json 2> $O/bench.err; echo bench rc=$?; tail -c 300 $O/bench_line.json
 fi
 ls $O/stats $O/fetch $O/write

@@ -14,13 +14,13 @@ for s in throughput latency; do
 done
 if [ "$1" = "full" ]; then
   timeout -k 5 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/train -o p -- python $R/bench.py --mode train --steps 5 --warmup 2 > $O/train.log 2>&1; echo train rc=$?
-  timeout -k 5 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench -o p -- python $R/bench.py --steps 50 --warmup 10 --no-cpu-baseline --no-secondary > $O/bench_under_rocprof.json 2> $O/bench_under_rocprof.err; echo bench-rocprof rc=$?
+  timeout -k 5 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench -o p -- python $R/bench.py --full --steps 50 --warmup 10 --no-cpu-baseline --no-secondary > $O/bench_under_rocprof.json 2> $O/bench_under_rocprof.err; echo bench-rocprof rc=$?
 fi
 cd $R
 timeout -k 5 120 python tools/xbench.py > $O/x2_per_launch.txt 2>&1
 YK_LIB_PATH=$R/k210_yolo_framework_amd/csrc/libyolo_hip_dev.so timeout -k 5 120 python tools/xpersist_phase.py > $O/persist_phases.txt 2>&1
 YK_LIB_PATH=$R/k210_yolo_framework_amd/csrc/libyolo_hip_dev.so timeout -k 5 120 python tools/xheads_phase.py > $O/heads_phases.txt 2>&1
 if [ "$1" = "full" ]; then
-  timeout -k 5 700 python bench.py > $O/bench_line.json 2> $O/bench.err; echo bench rc=$?; tail -c 300 $O/bench_line.json
+  timeout -k 5 700 python bench.py --full > $O/bench_line.json 2> $O/bench.err; echo bench rc=$?; tail -c 300 $O/bench_line.json
 fi
 ls $O/throughput/stats $O/latency/stats | head

@@ -23,7 +23,7 @@ YK_NET=yolo timeout -k 5 300 rocprofv3 --kernel-trace --stats --output-format cs
 cd $R
 ( ROCP_TOOL_LIBRARIES=$R/tools/devcount/libdevcount.so timeout 400 python tools/inflight_counters.py 4 400 $O/inflight_d4.json ) > $O/inflight_d4.log 2>&1; echo inflight d4 rc=$?
 ( ROCP_TOOL_LIBRARIES=$R/tools/devcount/libdevcount.so timeout 400 python tools/inflight_counters.py 1 400 $O/inflight_d1.json ) > $O/inflight_d1.log 2>&1; echo inflight d1 rc=$?
-( timeout 900 python bench.py ) > $O/bench_line.json 2> $O/bench_line.err; echo bench rc=$?; cut -c1-400 $O/bench_line.json
+( timeout 900 python bench.py --full ) > $O/bench_line.json 2> $O/bench_line.err; echo bench rc=$?; cut -c1-400 $O/bench_line.json
 ( timeout 600 python tools/netbench.py tiny_yolo yolo_mobilev2 yolo ) > $O/other_configs.txt 2>&1; tail -8 $O/other_configs.txt
 cp gpurun_out/launch_names_throughput.json gpurun_out/launch_names_latency.json $O/ 2>/dev/null
 find $O -name "*.db" -delete 2>/dev/null
