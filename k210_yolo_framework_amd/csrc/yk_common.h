@@ -10,8 +10,8 @@
 
 #define YK_WAVE 64
 
-// Tuning switches (YK_IGEMM_FORCE, YK_SPLIT_FORCE, YK_PIPE, ...) exist only in development builds (`make DEV=1`, -DYK_DEV): the
-// shipped library never reads the environment on its launch path.
+// Tuning switches (YK_IGEMM_FORCE, YK_SPLIT_FORCE, YK_NS, YK_PIPE, ...) exist only in development builds (`make dev` or `make DEV=1`,
+// -DYK_DEV): the shipped library never reads the environment on its launch path.  Rejected kernel variants are not kept here (git history).
 #include <stdlib.h>
 #ifdef YK_DEV
 static inline const char *yk_dev_env(const char *name) { return getenv(name); }

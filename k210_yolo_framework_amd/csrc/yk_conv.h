@@ -43,8 +43,7 @@ struct igemm_args {
     int ks, stride, pad_t, pad_l;
     int M, N, K;                // M = B*Ho*Wo, N = Cout, K = ks*ks*(c0p+c1p)
     const yk_half *w;           // [N][K]
-    // the same weights in MFMA-fragment order [K/64 steps][ceil(N/16) blocks][2 half-steps][64 lanes][8] (null unless the plan was built
-    // for the register-fragment ring kernel, yk_igemm_br.h): a wave's load of one block and half-step is 1 KB of contiguous memory
+    // unused (a removed kernel's weight copy); kept so that the kernel-argument offsets of every igemm kernel stay as they are
     const yk_half *wfrag;
     uint32_t wfrag_bytes;
     int nb16;
@@ -78,8 +77,9 @@ struct igemm_args {
     unsigned fp_lds;
 };
 void yk_fdma_fill(igemm_args &a);   // computes the fp_* fields (a.M = max_batch * Ho * Wo)
-enum { IGEMM_128x64 = 0, IGEMM_128x48, IGEMM_128x96, IGEMM_128x192, IGEMM_64x64, IGEMM_128x128, IGEMM_F32_64x80,
-       IGEMM_F32_128x64, IGEMM_128x64K64, IGEMM_64x128, IGEMM_64x192, IGEMM_256x128 /* developer build only */, IGEMM_256x128W4, IGEMM_128x256, IGEMM_128x128R, IGEMM_256x256, IGEMM_LC_256x128, IGEMM_LC_128x128, IGEMM_LC_128x256, IGEMM_NUM };
+// the configurations yk_igemm_pick returns (developer builds: YK_IGEMM_FORCE=<number> forces one of them)
+enum { IGEMM_128x64 = 0, IGEMM_128x48, IGEMM_128x96, IGEMM_128x192, IGEMM_64x64, IGEMM_F32_64x80, IGEMM_F32_128x64, IGEMM_64x128,
+       IGEMM_128x128R, IGEMM_NUM };
 int yk_launch_igemm(int cfg, const igemm_args &a, hipStream_t st);
 int yk_fused_pad();
 int yk_igemm_pick(const igemm_args &a, bool out_f32);

@@ -726,9 +726,6 @@ __global__ void __launch_bounds__(64 * WM * WN) igemm_lin_kernel(const igemm_arg
 }
 
 #include "yk_igemm_pipe.h"
-#ifdef YK_DEV
-#include "yk_igemm_lc.h"                                           // loader / consumer waves: measured slower in the whole networks, developer builds only
-#endif
 
 int yk_launch_splitk_reduce(const igemm_args &a, bool out_f32, hipStream_t st) {
     const size_t total = (size_t)a.M * (a.ldn >> 2);
@@ -810,13 +807,8 @@ struct igemm_cfg_info {
 };
 static const igemm_cfg_info g_cfg[IGEMM_NUM] = {
     {128, 64, 32, "igemm_128x64"}, {128, 48, 32, "igemm_128x48"}, {128, 96, 32, "igemm_128x96"},
-    {128, 192, 64, "igemm_128x192k64"}, {64, 64, 64, "igemm_64x64k64"}, {128, 128, 64, "igemm_128x128k64"},
-    {64, 80, 64, "igemm_f32_64x80k64"}, {128, 64, 32, "igemm_f32_128x64"}, {128, 64, 64, "igemm_128x64k64"},
-    {64, 128, 64, "igemm_64x128k64"}, {64, 192, 64, "igemm_64x192k64"}, {256, 128, 64, "igemm_256x128k64"},
-    {256, 128, 64, "igemm_256x128k64w4"}, {128, 256, 64, "igemm_128x256k64"}, {128, 128, 64, "igemm_128x128k64r"}, {256, 256, 64, "igemm_256x256k64"},
-    {256, 128, 64, "igemm_lc_256x128"}, {128, 128, 64, "igemm_lc_128x128"}, {128, 256, 64, "igemm_lc_128x256"}};
-
-static int yk_big_ring_depth(int cfg) { return cfg == IGEMM_256x128 ? 3 : 2; }
+    {128, 192, 64, "igemm_128x192k64"}, {64, 64, 64, "igemm_64x64k64"}, {64, 80, 64, "igemm_f32_64x80k64"},
+    {128, 64, 32, "igemm_f32_128x64"}, {64, 128, 64, "igemm_64x128k64"}, {128, 128, 64, "igemm_128x128k64r"}};
 
 int yk_launch_igemm(int cfg, const igemm_args &a, hipStream_t st) {
     switch (cfg) {
@@ -825,39 +817,15 @@ int yk_launch_igemm(int cfg, const igemm_args &a, hipStream_t st) {
     case IGEMM_128x96: return launch_cfg<128, 96, 4, 1, 32, false>(a, st);
     case IGEMM_128x192: return launch_cfg<128, 192, 2, 2, 64, false, true>(a, st);
     case IGEMM_64x64: return launch_cfg<64, 64, 2, 2, 64, false, true>(a, st);
-    case IGEMM_128x128: return launch_cfg<128, 128, 2, 2, 64, false, true>(a, st);
     case IGEMM_F32_64x80: return launch_cfg<64, 80, 4, 1, 64, true, true>(a, st);
     case IGEMM_F32_128x64: return launch_cfg<128, 64, 2, 2, 32, true>(a, st);
-    case IGEMM_128x64K64: return launch_cfg<128, 64, 2, 2, 64, false, true>(a, st);
     case IGEMM_64x128: return launch_cfg<64, 128, 2, 2, 64, false, true>(a, st);
-    case IGEMM_64x192: return launch_cfg<64, 192, 2, 2, 64, false, true>(a, st);
-    // large ring tiles (MFMA-bound layers at large M: Darknet-53 / tiny-YOLO 3x3 convs); LDS-DMA preconditions only, no register-staged fallback
-    case IGEMM_256x128:
-    case IGEMM_256x128W4:
-    case IGEMM_128x256:
-    case IGEMM_128x128R:
-    case IGEMM_256x256:
-    case IGEMM_LC_256x128:
-    case IGEMM_LC_128x128:
-    case IGEMM_LC_128x256: {
+    // the large ring tile (MFMA-bound layers at large M: Darknet-53 / tiny-YOLO 3x3 convs); LDS-DMA preconditions only, no register-staged fallback
+    case IGEMM_128x128R: {
         const uint64_t margin = (uint64_t)(a.Wi + 2) * (uint64_t)std::max(a.c0p, a.c1p) * 2u + (uint64_t)a.c0p * 2u;
         if ((a.c0p + a.c1p) % 64 || a.c0p % 64 || (uint64_t)a.in0_bytes + margin >= YK_OOB || (uint64_t)a.in1_bytes + margin >= YK_OOB) break;
-        const int ns_env = yk_dev_env("YK_NS") ? atoi(yk_dev_env("YK_NS")) : 0;     // (developer build: read per launch, tools/r05_igemm_sweep.py)
-        const int ns = ns_env ? ns_env : yk_big_ring_depth(cfg);
-        if (cfg == IGEMM_256x128) return ns >= 3 ? launch_pipe<256, 128, 4, 2, 3>(a, st) : launch_pipe<256, 128, 4, 2, 2>(a, st);
-        if (cfg == IGEMM_256x128W4) return ns >= 3 ? launch_pipe<256, 128, 2, 2, 3>(a, st) : launch_pipe<256, 128, 2, 2, 2>(a, st);
-        if (cfg >= IGEMM_LC_256x128) {                             // loader / consumer form (yk_igemm_lc.h, developer builds): no upsampled source
-#ifdef YK_DEV
-            if (a.up0) break;
-            if (cfg == IGEMM_LC_256x128) return launch_lc<256, 128, 2, 2, 4, 3>(a, st);
-            if (cfg == IGEMM_LC_128x256) return launch_lc<128, 256, 2, 2, 4, 3>(a, st);
-            return ns >= 4 ? launch_lc<128, 128, 2, 2, 4, 4>(a, st) : launch_lc<128, 128, 2, 2, 4, 3>(a, st);
-#else
-            break;
-#endif
-        }
-        if (cfg == IGEMM_256x256) return launch_pipe<256, 256, 4, 2, 2>(a, st);
-        if (cfg == IGEMM_128x256) return ns >= 3 ? launch_pipe<128, 256, 2, 2, 3>(a, st) : launch_pipe<128, 256, 2, 2, 2>(a, st);
+        const int ns_env = yk_dev_env("YK_NS") ? atoi(yk_dev_env("YK_NS")) : 0;     // (developer build: read per launch)
+        const int ns = ns_env ? ns_env : 2;
         return ns >= 4 ? launch_pipe<128, 128, 2, 2, 4>(a, st) : (ns == 3 ? launch_pipe<128, 128, 2, 2, 3>(a, st) : launch_pipe<128, 128, 2, 2, 2>(a, st));
     }
     }
@@ -878,7 +846,7 @@ int yk_igemm_pick(const igemm_args &a, bool out_f32) {
         const char *f = yk_dev_env("YK_IGEMM_FORCE");
         if (f && f[0]) {
             const int c = atoi(f);
-            const bool ring_only = c >= IGEMM_256x128;                 // no register-staged fallback: only where the LDS-DMA ring applies
+            const bool ring_only = c == IGEMM_128x128R;                // no register-staged fallback: only where the LDS-DMA ring applies
             const bool ring_ok = ((a.c0p + a.c1p) % 64 == 0) && (a.c0p % 64 == 0);
             if (c >= 0 && c < IGEMM_NUM && c != IGEMM_F32_64x80 && c != IGEMM_F32_128x64 && a.N % g_cfg[c].bn == 0 && (!ring_only || ring_ok))
                 return c;
@@ -902,11 +870,6 @@ int yk_igemm_pick(const igemm_args &a, bool out_f32) {
     {
         const uint64_t margin = (uint64_t)(a.Wi + 2) * (uint64_t)std::max(a.c0p, a.c1p) * 2u + (uint64_t)a.c0p * 2u;
         const bool ring_fits = (uint64_t)a.in0_bytes + margin < YK_OOB && (uint64_t)a.in1_bytes + margin < YK_OOB;   // (the ring kernel has no fallback form)
-        // loader + consumer waves (yk_igemm_lc.h), 128x256 tile.  Alone, on a layer without residual and without split-K, it is ahead on the
-        // long-K wide-N 3x3 layers (tools/r05_igemm_sweep.py, TFLOP/s at 32 / 64 images: 26x26 256->512 686 / 878 vs 658 / 745, 13x13 512->1024
-        // 780 / 800 vs 665 / 708); picked for the whole of Darknet-53 it LOSES (6644 vs 7552 images/s at 32 images, 8328 vs 8708 at 64: its
-        // 128x256 tiles need split-K slabs + a finishing pass where the 64x128 tile fills the chip without) - developer builds only, YK_IGEMM_LC=1
-        if (yk_dev_env("YK_IGEMM_LC") && yk_dev_env("YK_IGEMM_LC")[0] == '1' && dma_ok && ring_fits && !a.up0 && !a.in1 && a.N % 256 == 0 && a.K >= 1024 && a.M >= 4096) return IGEMM_LC_128x256;
         if (dma_ok && ring_fits && !a.up0 && a.N % 128 == 0 && a.M >= 150000 && a.K >= 256) return IGEMM_128x128R;
     }
     if (a.K >= 512) return (a.N % 128 == 0 && dma_ok) ? IGEMM_64x128 : IGEMM_64x64;

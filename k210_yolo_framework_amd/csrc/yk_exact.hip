@@ -312,8 +312,7 @@ __device__ __forceinline__ void x_wait_vm() {
     asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory");
 }
 
-// IL (round 5): the prefetch step's DMA pieces go out BETWEEN the MFMAs of the step being computed (yk_igemm_pipe.h has the measurement)
-template <int BM, int BN, int WM, int WN, int NS, bool PART, bool IL = false>
+template <int BM, int BN, int WM, int WN, int NS, bool PART>
 __global__ void __launch_bounds__(64 * WM * WN) xg_kernel(const xg_args a) {
     typedef xg_cfg<BM, BN, WM, WN> C;
     constexpr int NW = C::NW, TM = C::TM, TN = C::TN;
@@ -492,45 +491,6 @@ __global__ void __launch_bounds__(64 * WM * WN) xg_kernel(const xg_args a) {
 #pragma unroll
             for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[j], xh[i], acc[i][j], 0, 0, 0);
     };
-    // the same step with the prefetch step's pieces spread over its 3 * TM * TN MFMAs
-    auto compute_il = [&](int stage, int wstage) {
-        constexpr int NM = 3 * TM * TN;
-        const unsigned char *As = xsm + stage * C::STAGE, *Bs = As + BM * 128;
-        dma_prepare();
-        half8 xh[TM], xl[TM], wh[TN], wl[TN];
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-            xh[i] = *reinterpret_cast<const half8 *>(As + ((wm * TM + i) * 2) * 1024 + foff);
-            xl[i] = *reinterpret_cast<const half8 *>(As + ((wm * TM + i) * 2 + 1) * 1024 + foff);
-        }
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            wh[j] = *reinterpret_cast<const half8 *>(Bs + ((wn * TN + j) * 2) * 1024 + foff);
-            wl[j] = *reinterpret_cast<const half8 *>(Bs + ((wn * TN + j) * 2 + 1) * 1024 + foff);
-        }
-#pragma unroll
-        for (int sw = 0; sw < 3; ++sw)
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j) {
-                    if (sw == 0) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl[j], xh[i], acc[i][j], 0, 0, 0);
-                    else if (sw == 1) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[j], xl[i], acc[i][j], 0, 0, 0);
-                    else acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[j], xh[i], acc[i][j], 0, 0, 0);
-                    const int idx = (sw * TM + i) * TN + j;
-                    const int p0 = idx * L / NM, p1 = (idx + 1) * L / NM;          // pieces [p0, p1) go out behind this MFMA
-                    if (p1 > p0) {
-                        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                        for (int pp = 0; pp < (L + NM - 1) / NM + 1; ++pp)
-                            if (p0 + pp < p1) {
-                                dma_piece(wstage, p0 + pp);
-                            }
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-                }
-        dma_advance();
-    };
     // image of each accumulator row (relative to b0)
     int rowb[TM];
 #pragma unroll
@@ -557,12 +517,8 @@ __global__ void __launch_bounds__(64 * WM * WN) xg_kernel(const xg_args a) {
             rescale();
             in0 = false;
         }
-        if constexpr (IL) {
-            compute_il(rd, wr);
-        } else {
-            dma(wr);
-            if (!X_DBG(a, 16)) compute(rd);
-        }
+        dma(wr);
+        if (!X_DBG(a, 16)) compute(rd);
         rd = (rd + 1 == NS) ? 0 : rd + 1;
         wr = (wr + 1 == NS) ? 0 : wr + 1;
     }
@@ -794,9 +750,6 @@ void xdw_geometry(xdw_args &d, int max_batch) {
 #include "yk_xpersist.h"
 #include "yk_xheads.h"
 #include "yk_xfin.h"
-#ifdef YK_DEV
-#include "yk_xwblock.h"                                            // two-role fused block: faster alone, slower with four batches in flight - developer builds
-#endif
 
 // =====================================================================================================================
 // stem conv (Cin = 3), fp32 VALU; u8 frames are normalised as float(v)/float(max) = numpy's `img / np.max(img)` rounded once.
@@ -1036,7 +989,6 @@ struct xlaunch {
     xadd_args ad;
     xb_args b;
     int tm = 0, tn = 0;                // xb_kernel<tm, tn>
-    int ws = 0;                        // ... as xw_kernel<tm, tn> (wave-specialised, yk_xwblock.h)
     int Ho = 0, Wo = 0;
     int cfg = 0, ns = 2;               // xg_kernel tile configuration and ring depth
     unsigned lds = 0;
@@ -1046,22 +998,12 @@ struct xlaunch {
     xh_args ha;                        // XK_HEADS
     unsigned h_lds = 0;
     xf_args f;                         // XK_FIN: conv + BN + act -> 1x1 output conv in one launch (yk_xfin.h)
-    int fin_bm = 64, fin_bn = 0, fin_nw = 4;
+    int fin_bn = 0;                    // ... its output channels (64-row tiles on four waves)
     int p_cw = 0;
     std::string name;
     double flops = 0, bytes = 0;
 };
 
-// interleaved DMA issue (IL): measured no faster (K2 step 646.6 vs 637.4 us of kernels, Darknet-53 f16x2 3119 vs 3089 images/s; gpurun_out/r5c3):
-// a wave blocks on the vector-memory issue of a piece wherever the piece sits in its stream - developer builds only (YK_X_IL=1)
-static bool x_interleave() {
-#ifdef YK_DEV
-    const char *e = getenv("YK_X_IL");
-    return e && e[0] == '1';
-#else
-    return false;
-#endif
-}
 template <int BM, int BN, int WM, int WN, int NS>
 int x_launch_g(const xg_args &g, hipStream_t st) {
     typedef xg_cfg<BM, BN, WM, WN> C;
@@ -1072,33 +1014,17 @@ int x_launch_g(const xg_args &g, hipStream_t st) {
     };
     static bool once = false;
     if (!once) {
-        allow(reinterpret_cast<const void *>(xg_kernel<BM, BN, WM, WN, NS, true, false>), lds);
-        allow(reinterpret_cast<const void *>(xg_kernel<BM, BN, WM, WN, NS, false, false>), lds);
+        allow(reinterpret_cast<const void *>(xg_kernel<BM, BN, WM, WN, NS, true>), lds);
+        allow(reinterpret_cast<const void *>(xg_kernel<BM, BN, WM, WN, NS, false>), lds);
         allow(reinterpret_cast<const void *>(xg_reduce_kernel<BM, BN, WM, WN>), rlds);
-#ifdef YK_DEV
-        allow(reinterpret_cast<const void *>(xg_kernel<BM, BN, WM, WN, NS, true, true>), lds);
-        allow(reinterpret_cast<const void *>(xg_kernel<BM, BN, WM, WN, NS, false, true>), lds);
-#endif
         once = true;
     }
-#ifdef YK_DEV
-    if (x_interleave()) {
-        if (g.splitk > 1) {
-            hipLaunchKernelGGL((xg_kernel<BM, BN, WM, WN, NS, true, true>), grid, dim3(C::NT), lds, st, g);
-            grid.z = 1;
-            hipLaunchKernelGGL((xg_reduce_kernel<BM, BN, WM, WN>), grid, dim3(C::NT), rlds, st, g);
-        } else {
-            hipLaunchKernelGGL((xg_kernel<BM, BN, WM, WN, NS, false, true>), grid, dim3(C::NT), lds, st, g);
-        }
-        return YK_OK;
-    }
-#endif
     if (g.splitk > 1) {
-        hipLaunchKernelGGL((xg_kernel<BM, BN, WM, WN, NS, true, false>), grid, dim3(C::NT), lds, st, g);
+        hipLaunchKernelGGL((xg_kernel<BM, BN, WM, WN, NS, true>), grid, dim3(C::NT), lds, st, g);
         grid.z = 1;
         hipLaunchKernelGGL((xg_reduce_kernel<BM, BN, WM, WN>), grid, dim3(C::NT), rlds, st, g);
     } else {
-        hipLaunchKernelGGL((xg_kernel<BM, BN, WM, WN, NS, false, false>), grid, dim3(C::NT), lds, st, g);
+        hipLaunchKernelGGL((xg_kernel<BM, BN, WM, WN, NS, false>), grid, dim3(C::NT), lds, st, g);
     }
     return YK_OK;
 }
@@ -1134,16 +1060,10 @@ int x_launch_fin_bn(const xf_args &f, int ns, hipStream_t st) {
     else hipLaunchKernelGGL((xf_kernel<BM, BN, 2, NW>), grid, dim3(C::NT), (unsigned)C::lds(2), st, f);
     return YK_OK;
 }
-int x_launch_fin(int bm, int bn, int nw, int ns, const xf_args &f, hipStream_t st) {
-    if (bm == 64 && bn == 128 && nw == 4) return x_launch_fin_bn<64, 128, 4>(f, ns, st);
-    if (bm == 64 && bn == 192 && nw == 4) return x_launch_fin_bn<64, 192, 4>(f, ns, st);
-#ifdef YK_DEV                                                           // measured equal (8 waves on a 64-row tile) or slower (128-row tiles): developer builds
-    if (bm == 64 && bn == 128 && nw == 8) return x_launch_fin_bn<64, 128, 8>(f, ns, st);
-    if (bm == 64 && bn == 192 && nw == 8) return x_launch_fin_bn<64, 192, 8>(f, ns, st);
-    if (bm == 128 && bn == 128) return x_launch_fin_bn<128, 128, 8>(f, ns, st);
-    if (bm == 128 && bn == 192) return x_launch_fin_bn<128, 192, 8>(f, ns, st);
-#endif
-    yk_set_error("f16x2: no fused head kernel for a %d x %d tile on %d waves", bm, bn, nw);
+int x_launch_fin(int bn, int ns, const xf_args &f, hipStream_t st) {
+    if (bn == 128) return x_launch_fin_bn<64, 128, 4>(f, ns, st);
+    if (bn == 192) return x_launch_fin_bn<64, 192, 4>(f, ns, st);
+    yk_set_error("f16x2: no fused head kernel for a 64 x %d tile on 4 waves", bn);
     return YK_ERR_ARG;
 }
 
@@ -1181,28 +1101,7 @@ bool xb_has(int tm, int tn) {
     for (int v : g_xb_tn) b |= v == tn;
     return a && b;
 }
-#ifdef YK_DEV
-// the wave-specialised form (yk_xwblock.h): producers run the depthwise pass of step k while consumers multiply step k-1
-template <int TM, int TN>
-int x_launch_w(const xb_args &g, int batch, hipStream_t st) {
-    static bool once = false;
-    if (!once) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(xw_kernel<TM, TN>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        once = true;
-    }
-    dim3 grid((unsigned)(batch * g.tiles_x * g.tiles_y), (unsigned)((g.N + 64 * TN - 1) / (64 * TN)));
-    hipLaunchKernelGGL((xw_kernel<TM, TN>), grid, dim3(512), (unsigned)g.lds_bytes, st, g);
-    return YK_OK;
-}
-#endif
-int x_launch_block(int tm, int tn, const xb_args &g, int batch, unsigned lds, hipStream_t st, int ws = 0) {
-#ifdef YK_DEV
-    if (ws && tm == 4 && tn == 6) return x_launch_w<4, 6>(g, batch, st);
-    if (ws && tm == 4 && tn == 3) return x_launch_w<4, 3>(g, batch, st);
-    if (ws && tm == 2 && tn == 3) return x_launch_w<2, 3>(g, batch, st);
-#else
-    (void)ws;
-#endif
+int x_launch_block(int tm, int tn, const xb_args &g, int batch, unsigned lds, hipStream_t st) {
 #define XB_CASE(M, N) \
     if (tm == M && tn == N) return x_launch_b<M, N>(g, batch, lds, st);
     XB_CASE(2, 1) XB_CASE(2, 2) XB_CASE(2, 3) XB_CASE(2, 6)
@@ -2151,8 +2050,7 @@ int yk_xplan_create(yk_xplan **out, const int32_t *ops, int n_ops, const int32_t
                 // that each re-read their operands from L2)
                 // The slice count follows the IMAGE size (priced for the 32-image batch of the benchmark), never max_batch: an image's
                 // arithmetic must not depend on how many images the plan was built for.
-                int bm = 64;
-                if (const char *e = yk_dev_env("YK_XF_BM")) bm = atoi(e) == 128 ? 128 : 64;
+                const int bm = 64;
                 const long tiles = (Mmax + bm - 1) / bm, tiles32 = (32L * Y.h * Y.w + bm - 1) / bm;
                 // measured with four batches in flight (tools/calls r6c5, developer build, one box; three-launch form 93.0 k images/s):
                 // slices (192-ch head, 128-ch head) = (8, 2) 94.0 k, (4, 4) 94.3 k, (6, 3) 94.8 k, (8, 4) 93.6 k; 128-row tiles 91.0 - 93.5 k
@@ -2163,10 +2061,7 @@ int yk_xplan_create(yk_xplan **out, const int32_t *ops, int n_ops, const int32_t
                 g.splitk = (int)sk;
                 l.ns = 2;
                 if (const char *e = yk_dev_env("YK_XF_NS")) l.ns = std::max(2, std::min(3, atoi(e)));
-                l.fin_bm = bm;
                 l.fin_bn = co;
-                l.fin_nw = bm == 128 ? 8 : 4;
-                if (const char *e = yk_dev_env("YK_XF_NW")) l.fin_nw = (atoi(e) == 8 || bm == 128) ? 8 : 4;
                 l.f.slab_bytes = 0;
                 if (g.splitk > 1) {
                     void *sl;
@@ -2262,7 +2157,7 @@ int yk_xplan_create(yk_xplan **out, const int32_t *ops, int n_ops, const int32_t
                 l.Wo = Y.w;
                 f.c = g;
                 char tl[64];
-                snprintf(tl, sizeof tl, "[%dx%d,%dwaves,ring%d%s]", l.fin_bm, co, l.fin_nw, l.ns, g.splitk > 1 ? ",splitk" : "");
+                snprintf(tl, sizeof tl, "[64x%d,4waves,ring%d%s]", co, l.ns, g.splitk > 1 ? ",splitk" : "");
                 snprintf(nm, sizeof nm, "x:conv%dx%ds%d_%dto%d%s+conv1x1_%dto%d%s", ks, ks, g.stride, cin, co, S1 ? "+upcat" : (up0 ? "+up" : ""), co, f.N2, tl);
                 l.flops = 2.0 * Y.h * Y.w * ks * ks * (double)cin * co + 2.0 * Y.h * Y.w * (double)co * f.N2;
                 l.bytes = ((double)S0.h * S0.w * c0 + (S1 ? (double)S1->h * S1->w * c1 : 0.0) + 2.0 * Y.h * Y.w * co + (double)Y.h * Y.w * f.N2) * 4;
@@ -2401,26 +2296,6 @@ int yk_xplan_create(yk_xplan **out, const int32_t *ops, int n_ops, const int32_t
             if (cons->kind == XK_BLOCK) cons->b.src_f32 = 1; else cons->d.in_f32 = 1;
             T.f32 = true;
         }
-    // Developer builds, YK_XB_WS=1: the long-walk blocks (12 channel steps to 384 outputs: the five 14x20x384 blocks of yolo_mobilev1-0.75) run
-    // wave-specialised (yk_xwblock.h): depthwise pass of step k on four waves while four others multiply step k-1.  Bit-identical outputs;
-    // measured (tools/calls r6c9, one box): the launch alone 36.5 -> 29.1 us (sum of kernels 598 -> 561 us), but `value` 99.1 -> 95.8 k images/s:
-    // its eight waves x 217 registers take the whole CU, where the one-role kernel leaves half of it to the other batches' workgroups.
-    if (yk_dev_env("YK_XB_WS") && yk_dev_env("YK_XB_WS")[0] == '1')
-        for (xlaunch &l : p->L) {
-            if (l.kind != XK_BLOCK || l.b.stem || l.b.GL != 4) continue;
-            const bool pick = (l.tm == 4 && l.tn == 6) || (yk_dev_env("YK_XB_WS_ALL") && ((l.tm == 4 && l.tn == 3) || (l.tm == 2 && l.tn == 3)));
-            if (!pick) continue;
-            const int bm = 16 * l.tm, bn = 64 * l.tn, ipp = (l.tn >= 3 && l.tm >= 2) ? (l.tm + 1) / 2 : l.tm;
-            const bool staged = !(l.b.dst_f32 && !l.b.res.p);
-            const int ring = 2 * (l.b.n16p * 32 + 2048) + 2 * bm * 128, ct = staged ? ipp * 16 * (bn * 4 + 16) : 0;
-            const int lds = std::max(ring, ct) + 64;
-            if (lds > 160 * 1024) continue;
-            l.ws = 1;
-            l.lds = (unsigned)lds;
-            l.b.lds_bytes = lds;
-            const size_t at = l.name.rfind(']');
-            if (at != std::string::npos) l.name.insert(at, ",2roles");
-        }
     // The two cluster launches hold every CU for their whole duration: the shortest time of ONE batch (one-batch latency 669 -> 542 us of
     // kernels), but with several batches in flight on several streams the launch-per-layer form overlaps better (78 k vs 68 k images/s, four in
     // flight; profiles/r04_schedules.txt).  YK_SCHEDULE_LATENCY selects them; YK_PERSIST / YK_HEADS = 0|1 override either way.
@@ -2481,7 +2356,7 @@ int yk_xplan_run(yk_xplan *p, const void *d_in, int in_f32, int batch, hipStream
             xf_args f = l.f;
             f.c.B = batch;
             f.c.M = batch * l.Ho * l.Wo;
-            int rc = x_launch_fin(l.fin_bm, l.fin_bn, l.fin_nw, l.ns, f, st);
+            int rc = x_launch_fin(l.fin_bn, l.ns, f, st);
             if (rc) return rc;
         } break;
         case XK_BLOCK: {
@@ -2494,7 +2369,7 @@ int yk_xplan_run(yk_xplan *p, const void *d_in, int in_f32, int batch, hipStream
             }
             if (const char *e = yk_dev_env("YK_XB_DBG")) g.dbg = atoi(e);
             g.stamps = (li == p->dbg_launch) ? p->d_dbg : nullptr;
-            int rc = x_launch_block(l.tm, l.tn, g, batch, l.lds, st, l.ws);
+            int rc = x_launch_block(l.tm, l.tn, g, batch, l.lds, st);
             if (rc) return rc;
         } break;
         case XK_DW: {

@@ -28,20 +28,8 @@ template <int N>
 __device__ __forceinline__ void yk_wait_vm_lgkm0() {
     asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory");
 }
-#ifdef YK_DEV
-#include "yk_igemm_br.h"                                           // (developer builds: the variant with the weight fragments in registers)
-#endif
 
-// IL (round 5): the DMA pieces of the step being prefetched are issued BETWEEN the MFMAs of the step being computed, one piece per few MFMAs
-// (an LDS-DMA instruction costs its wave ~150 cycles of issue when a whole step's pieces go out in one block ahead of the fragment reads,
-// ~60 in the shadow of the matrix pipe - MI355X_MICROARCH.md "LDS-DMA piece issue cost"; tools/r05_igemm_sweep.py: without it every tile
-// shape from 64x128 to 256x128 sits at 550-700 TFLOP/s at B=32, i.e. the loop is bound by DMA issue, not by the tile).
-// PS (round 5, phase split): half of the waves of a SIMD issue the step's DMA pieces BEFORE their MFMAs, the other half AFTER (needs NS >= 3:
-// a piece issued at the end of step k is waited for at the start of step k + 2).  A barrier releases every wave at once; unsplit, all of them
-// then sit in the vector-memory issue queue together (~100 cycles per 1 KB piece, the matrix pipe idle) and afterwards compete for the matrix
-// pipe together (tools/r05_igemm_phase.py: 870 cycles of DMA issue + 1450 of MFMAs + 1200 at the barrier per k-step for 1024 cycles of MFMA).
-// PS 1: by wave index (8-wave workgroups: waves w and w + 4 share a SIMD); PS 2: by the hardware wave slot's parity (two 4-wave workgroups per CU).
-template <int BM, int BN, int WM, int WN, int NS, int OUT, bool UP, bool IL = false, int PS = 0>
+template <int BM, int BN, int WM, int WN, int NS, int OUT, bool UP>
 __global__ void __launch_bounds__(64 * WM * WN) igemm_pipe_kernel(const igemm_args a) {
     constexpr int NW = WM * WN, BK = 64;
     constexpr int TM = BM / WM / 16, TN = BN / WN / 16;
@@ -192,41 +180,6 @@ __global__ void __launch_bounds__(64 * WM * WN) igemm_pipe_kernel(const igemm_ar
                 for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[j], xf[i], acc[i][j], 0, 0, 0);
         }
     };
-    // IL: the software-pipelined step (round 5).  Counters of the plain loop on a Darknet 52x52 128->256 3x3 at 32 images (profiles/r05_igemm_pmc.txt):
-    // matrix pipe busy 0.28, waves 34-40 % parked at s_waitcnt / s_barrier, 2600 cycles per wave and k-step for 512 cycles of MFMA - a wave's
-    // step was a serial chain  barrier -> 8 fragment reads (~250 cycles exposed) -> 16 MFMAs -> 8 reads -> 16 MFMAs, with the step's DMA pieces
-    // issued in one block in front.  Here the two half-steps' fragments live in two register sets: the reads of the second half go out before
-    // the first half's MFMAs, the reads of the NEXT step's first half right behind the barrier that ends this step (under the tail of its
-    // MFMAs), and the prefetch step's DMA pieces are spread between the MFMAs, one per NM / L of them.
-    half8 wf0[TN], xf0[TM], wf1[TN], xf1[TM];
-    auto read_frags = [&](int stage, int ks, half8 (&wf)[TN], half8 (&xf)[TM]) {
-        const yk_half *As = lds + stage * STAGE, *Bs = As + BM * BK;
-        const int ch = ((ks * 4 + fq) ^ sw) * 8;
-#pragma unroll
-        for (int j = 0; j < TN; ++j) wf[j] = *reinterpret_cast<const half8 *>(Bs + ((wn * TN + j) * 16 + fr) * BK + ch);
-#pragma unroll
-        for (int i = 0; i < TM; ++i) xf[i] = *reinterpret_cast<const half8 *>(As + ((wm * TM + i) * 16 + fr) * BK + ch);
-    };
-    auto mma_half = [&](int ks, const half8 (&wf)[TN], const half8 (&xf)[TM], int wstage) {
-        constexpr int NM = 2 * TM * TN;
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j) {
-                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[j], xf[i], acc[i][j], 0, 0, 0);
-                const int idx = (ks * TM + i) * TN + j;                           // MFMA number inside the step
-                const int p0 = idx * L / NM, p1 = (idx + 1) * L / NM;             // pieces [p0, p1) go out here
-                if (p1 > p0) {
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int pp = 0; pp < (L + NM - 1) / NM + 1; ++pp)
-                        if (p0 + pp < p1) {
-                            dma_piece(wstage, p0 + pp);
-                        }
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-    };
 #ifdef YK_DEV
     // developer build: where a wave's loop time goes (cycles of wave 0, summed over the k-steps) -> a.dbg[workgroup][8] (tools/r05_igemm_phase.py)
     long long c_wait = 0, c_bar = 0, c_dma = 0, c_mma = 0, c_t = 0;
@@ -237,65 +190,27 @@ __global__ void __launch_bounds__(64 * WM * WN) igemm_pipe_kernel(const igemm_ar
 #define PIPE_CLK(v)
 #define PIPE_CLK0()
 #endif
-    static_assert(PS == 0 || NS >= 3, "a late DMA needs a step of slack");
-    bool late_dma = false;
-    if constexpr (PS == 1) late_dma = wid >= NW / 2;
-    if constexpr (PS == 2) late_dma = (__builtin_amdgcn_s_getreg((3 << 11) | 4) & 1) != 0;    // hwreg(HW_REG_HW_ID, 0, 4): wave slot inside its SIMD
     if (nk > 0) {
 #pragma unroll
         for (int s = 0; s < NS - 1; ++s) dma(s);                   // steps past `lim` deposit zeros and keep the vmcnt arithmetic uniform
         int rd = 0, wr = NS - 1;                                   // stage read this step / stage refilled this step
         PIPE_CLK0()
-        if constexpr (IL) {
+        for (int kt = 0; kt < nk; ++kt) {
             yk_wait_vm_lgkm0<(NS - 2) * L>();
+            PIPE_CLK(c_wait)
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
-            read_frags(0, 0, wf0, xf0);
-            for (int kt = 0; kt < nk; ++kt) {
-                dma_prepare();
-                read_frags(rd, 1, wf1, xf1);
-                __builtin_amdgcn_sched_barrier(0);
-                mma_half(0, wf0, xf0, wr);
-                mma_half(1, wf1, xf1, wr);
-                dma_advance();
-                rd = (rd + 1 == NS) ? 0 : rd + 1;
-                wr = (wr + 1 == NS) ? 0 : wr + 1;
-                PIPE_CLK(c_mma)
-                yk_wait_vm_lgkm0<(NS - 2) * L>();                  // the next step's pieces have landed (this wave's) ...
-                PIPE_CLK(c_wait)
-                __builtin_amdgcn_s_barrier();                      // ... everybody's have, and everybody has read the stage refilled next
-                asm volatile("" ::: "memory");
-                PIPE_CLK(c_bar)
-                read_frags(rd, 0, wf0, xf0);                       // under the tail of this step's MFMAs (after the last step: a dead stage)
-            }
-            yk_wait_vm_lgkm0<0>();
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-        } else {
-            for (int kt = 0; kt < nk; ++kt) {
-                yk_wait_vm_lgkm0<(NS - 2) * L>();
-                PIPE_CLK(c_wait)
-                __builtin_amdgcn_s_barrier();
-                asm volatile("" ::: "memory");
-                PIPE_CLK(c_bar)
-                if (PS != 0 && late_dma) {
-                    compute(rd);
-                    PIPE_CLK(c_mma)
-                    dma(wr);
-                    PIPE_CLK(c_dma)
-                } else {
-                    dma(wr);
-                    PIPE_CLK(c_dma)
-                    compute(rd);
-                }
-                rd = (rd + 1 == NS) ? 0 : rd + 1;
-                wr = (wr + 1 == NS) ? 0 : wr + 1;
-                PIPE_CLK(c_mma)
-            }
-            yk_wait_vm_lgkm0<0>();                                 // drain the dead prefetches before LDS is reused by the epilogue
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
+            PIPE_CLK(c_bar)
+            dma(wr);
+            PIPE_CLK(c_dma)
+            compute(rd);
+            rd = (rd + 1 == NS) ? 0 : rd + 1;
+            wr = (wr + 1 == NS) ? 0 : wr + 1;
+            PIPE_CLK(c_mma)
         }
+        yk_wait_vm_lgkm0<0>();                                     // drain the dead prefetches before LDS is reused by the epilogue
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
     }
 #ifdef YK_DEV
     const long long wall1 = a.dbg ? (long long)wall_clock64() : 0;
@@ -311,19 +226,6 @@ __global__ void __launch_bounds__(64 * WM * WN) igemm_pipe_kernel(const igemm_ar
 #undef PIPE_CLK0
 }
 
-// The round-5 loop forms (IL: DMA pieces between the MFMAs; PS: phase-split waves; BR: weight fragments in registers, yk_igemm_br.h) were all
-// measured equal or slower in the whole networks ("measured and rejected"): they exist in developer builds only (-DYK_DEV).
-#ifdef YK_DEV
-static bool yk_pipe_interleave() {
-    const char *e = getenv("YK_PIPE_IL");
-    return e && e[0] == '1';
-}
-static int yk_pipe_phase_split() {
-    const char *e = getenv("YK_PIPE_PS");
-    return (e && e[0] != '0') ? 1 : 0;
-}
-#endif
-
 // more than 64 KB of dynamic LDS needs the attribute on EVERY kernel (instantiation) that is launched with it, on every device
 static inline void yk_allow_lds(const void *kern, size_t bytes) {
     if (bytes <= 64 * 1024) return;
@@ -337,10 +239,6 @@ static inline void yk_allow_lds(const void *kern, size_t bytes) {
 
 template <int BM, int BN, int WM, int WN, int NS>
 static int launch_pipe(const igemm_args &a, hipStream_t st) {
-#ifdef YK_DEV
-    if constexpr (NS == 2 && BM * BN <= 128 * 128)
-        if (!a.up0 && a.wfrag && yk_pipe_br()) return launch_br<BM, BN, WM, WN, NS>(a, st);     // weight fragments in registers (yk_igemm_br.h)
-#endif
     constexpr size_t ring = (size_t)NS * (BM + BN) * 64 * 2, ct = (size_t)BM * (BN + 8) * 2;
     constexpr size_t ldsd = ring > ct ? ring : ct;
     dim3 g2((a.M + BM - 1) / BM, (a.N + BN - 1) / BN, a.split_k > 1 ? a.split_k : 1);
@@ -353,27 +251,6 @@ static int launch_pipe(const igemm_args &a, hipStream_t st) {
         else go(igemm_pipe_kernel<BM, BN, WM, WN, NS, 0, true>);
         return YK_OK;
     }
-#ifdef YK_DEV
-    const bool il = yk_pipe_interleave();
-    const int ps = NS >= 3 ? yk_pipe_phase_split() : 0;
-    if (ps && NS >= 3) {
-        if constexpr (NS >= 3) {
-            if (WM * WN >= 8) {
-                if (a.split_k > 1) go(igemm_pipe_kernel<BM, BN, WM, WN, NS, 2, false, false, 1>);
-                else go(igemm_pipe_kernel<BM, BN, WM, WN, NS, 0, false, false, 1>);
-            } else {
-                if (a.split_k > 1) go(igemm_pipe_kernel<BM, BN, WM, WN, NS, 2, false, false, 2>);
-                else go(igemm_pipe_kernel<BM, BN, WM, WN, NS, 0, false, false, 2>);
-            }
-        }
-        return YK_OK;
-    }
-    if (il) {
-        if (a.split_k > 1) go(igemm_pipe_kernel<BM, BN, WM, WN, NS, 2, false, true>);
-        else go(igemm_pipe_kernel<BM, BN, WM, WN, NS, 0, false, true>);
-        return YK_OK;
-    }
-#endif
     if (a.split_k > 1) go(igemm_pipe_kernel<BM, BN, WM, WN, NS, 2, false>);
     else go(igemm_pipe_kernel<BM, BN, WM, WN, NS, 0, false>);
     return YK_OK;

@@ -1,5 +1,5 @@
 """Developer build: where a wave's k-loop time goes in igemm_pipe_kernel (cycles of wave 0 of every workgroup, summed over the k-steps).
-    YK_LIB_PATH=.../libyolo_hip_dev.so python tools/r05_igemm_phase.py H W C1 C2 B   (env: YK_IGEMM_FORCE, YK_NS, YK_PIPE_IL, YK_SPLIT_FORCE, KS)"""
+    YK_LIB_PATH=.../libyolo_hip_dev.so python tools/r05_igemm_phase.py H W C1 C2 B   (env: YK_IGEMM_FORCE, YK_NS, YK_SPLIT_FORCE, KS)"""
 import ctypes as C
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -32,7 +32,7 @@ rc = L.yk_debug_phase_stamps(plan._h, C.c_int(li), C.c_void_p(f.data_ptr()), C.c
 assert rc == 0, rc
 v = out[out[:, 0] > 0]
 nk = v[:, 7].astype(float)
-tag = f"cfg={os.environ.get('YK_IGEMM_FORCE', 'A')} ns={os.environ.get('YK_NS', '-')} il={os.environ.get('YK_PIPE_IL', '1')}"
+tag = f"cfg={os.environ.get('YK_IGEMM_FORCE', 'A')} ns={os.environ.get('YK_NS', '-')}"
 print(f'{name} {tag}: {ms[li] * 1e3:.1f} us ({fl * B / ms[li] / 1e9:.0f} TF/s; with stamps on the kernel is slower), {len(v)} workgroups, {nk.mean():.0f} k-steps')
 span = (v[:, 6].max() - v[:, 0].min()) / 100.0
 print(f'   stamped span {span:.1f} us; per workgroup: prologue+loop {np.median(v[:, 5] - v[:, 0]) / 100.0:.2f} us, epilogue {np.median(v[:, 6] - v[:, 5]) / 100.0:.2f} us')
