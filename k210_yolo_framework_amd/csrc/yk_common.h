@@ -42,6 +42,16 @@ void yk_set_error(const char *fmt, ...);
 void *yk_scratch(int device, void *stream, int slot, size_t bytes);
 void yk_scratch_release_stream(void *stream);
 
+// More than 64 KB of dynamic LDS needs the maximum-dynamic-LDS attribute on every kernel (instantiation) launched with it, on every
+// device.  yk_allow_lds raises it for (current device, kern) when `bytes` exceeds what was set there; every launch whose dynamic LDS
+// can exceed 64 KB goes through yk_launch_lds, which calls it.
+void yk_allow_lds(const void *kern, size_t bytes);
+template <typename... P, typename... A>
+static inline void yk_launch_lds(void (*kern)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t st, const A &...args) {
+    yk_allow_lds(reinterpret_cast<const void *>(kern), lds);
+    hipLaunchKernelGGL(kern, grid, block, lds, st, args...);
+}
+
 static inline int yk_current_device() {
     int d = -1;
     if (hipGetDevice(&d) != hipSuccess) return -1;

@@ -746,16 +746,7 @@ static int launch_cfg(const igemm_args &a, hipStream_t st) {
                      (uint64_t)a.in1_bytes + margin < YK_OOB;
     constexpr size_t stages = (size_t)2 * (BM + BN) * (BK + YK_LDPAD) * 2, ctile = F32 ? 0 : (size_t)BM * (BN + 8) * 2;
     constexpr size_t lds = stages > ctile ? stages : ctile;
-    auto go = [&](auto kern) {
-        if (lds > 64 * 1024) {
-            static bool done = false;
-            if (!done) {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                done = true;
-            }
-        }
-        hipLaunchKernelGGL(kern, grid, dim3(64 * WM * WN), lds, st, a);
-    };
+    auto go = [&](auto kern) { yk_launch_lds(kern, grid, dim3(64 * WM * WN), lds, st, a); };
     static const bool dma_on = yk_dev_env("YK_DMA") ? yk_dev_env("YK_DMA")[0] != '0' : true;      // LDS-DMA operand tiles (YK_DMA=0: register staging)
     if constexpr (UNI_OK && BK == 64 && !F32 && (BM / 8) % (WM * WN) == 0 && (BN / 8) % (WM * WN) == 0) {
         static const bool pipe_on = yk_dev_env("YK_PIPE") ? yk_dev_env("YK_PIPE")[0] != '0' : true;       // multi-stage LDS-DMA ring (yk_igemm_pipe.h)
@@ -1703,14 +1694,7 @@ static int launch_lr(const igemm_args &a, hipStream_t st) {
     // the results of every pass and the pixel fragments of every k-step stay in registers: instantiating for the real counts (1, 2 or
     // up to 4 each) keeps them at 12+8 / 24+16 / 48+32 registers per 16 rows instead of always the maximum, which spilled at the
     // 5-waves-per-SIMD budget (24->48: 30.9 -> 28.9 us).  Six waves per SIMD (80 registers, one spill) measured slower: 29.5 us.
-    auto go = [&](auto kern) {
-        static size_t attr_lds = 64 * 1024;
-        if (lds > attr_lds) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            attr_lds = lds;
-        }
-        hipLaunchKernelGGL(kern, dim3((a.M + BM - 1) / BM), dim3(256), lds, st, a);
-    };
+    auto go = [&](auto kern) { yk_launch_lds(kern, dim3((a.M + BM - 1) / BM), dim3(256), lds, st, a); };
     const int nk = Kp / 32;
     if (npass <= 1 && nk <= 1) go(fused_lr_kernel<TM, 1, 1>);
     else if (npass <= 2 && nk <= 2) go(fused_lr_kernel<TM, 2, 2>);
@@ -1724,14 +1708,8 @@ static int launch_wide(const igemm_args &a, hipStream_t st) {
     const int Kp = (a.c0p + 31) & ~31;
     size_t lds = (size_t)BM * (Kp + a.lda_pad) * 2 + (size_t)9 * a.c0p * 2, cs = (size_t)BM * (BN + 8) * 2;
     if (cs > lds) lds = cs;
-    static size_t attr_lds = 64 * 1024;
-    if (lds > attr_lds) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&fused_wide_kernel<WM, WN, TM, WPF>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_lds = lds;
-    }
     dim3 grid((a.M + BM - 1) / BM, (a.N + BN - 1) / BN);
-    hipLaunchKernelGGL((fused_wide_kernel<WM, WN, TM, WPF>), grid, dim3(768), lds, st, a);
+    yk_launch_lds(fused_wide_kernel<WM, WN, TM, WPF>, grid, dim3(768), lds, st, a);
     return YK_OK;
 }
 
@@ -1740,14 +1718,8 @@ static int launch_fused(const igemm_args &a, hipStream_t st) {
     const int Kp = (a.c0p + 31) & ~31;
     size_t lds = (size_t)BM * (Kp + a.lda_pad) * 2, cs = (size_t)BM * (BN + 8) * 2;
     if (cs > lds) lds = cs;
-    static size_t attr_lds = 64 * 1024;   // opt in to > 64 KiB dynamic LDS only when a layer needs it
-    if (lds > attr_lds) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&fused_dwpw_kernel<BM, BN, WM, WN, IT>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_lds = lds;
-    }
     dim3 grid((a.M + BM - 1) / BM, (a.N + BN - 1) / BN);
-    hipLaunchKernelGGL((fused_dwpw_kernel<BM, BN, WM, WN, IT>), grid, dim3(64 * WM * WN), lds, st, a);
+    yk_launch_lds(fused_dwpw_kernel<BM, BN, WM, WN, IT>, grid, dim3(64 * WM * WN), lds, st, a);
     return YK_OK;
 }
 

@@ -1009,23 +1009,8 @@ int x_launch_g(const xg_args &g, hipStream_t st) {
     typedef xg_cfg<BM, BN, WM, WN> C;
     constexpr unsigned lds = (unsigned)C::lds(NS), rlds = (unsigned)(C::CT + C::SMALL);
     dim3 grid((unsigned)((g.M + BM - 1) / BM), (unsigned)((g.N + BN - 1) / BN), (unsigned)g.splitk);
-    auto allow = [&](const void *k, unsigned bytes) {
-        if (bytes > 64 * 1024) (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    };
-    static bool once = false;
-    if (!once) {
-        allow(reinterpret_cast<const void *>(xg_kernel<BM, BN, WM, WN, NS, true>), lds);
-        allow(reinterpret_cast<const void *>(xg_kernel<BM, BN, WM, WN, NS, false>), lds);
-        allow(reinterpret_cast<const void *>(xg_reduce_kernel<BM, BN, WM, WN>), rlds);
-        once = true;
-    }
-    if (g.splitk > 1) {
-        hipLaunchKernelGGL((xg_kernel<BM, BN, WM, WN, NS, true>), grid, dim3(C::NT), lds, st, g);
-        grid.z = 1;
-        hipLaunchKernelGGL((xg_reduce_kernel<BM, BN, WM, WN>), grid, dim3(C::NT), rlds, st, g);
-    } else {
-        hipLaunchKernelGGL((xg_kernel<BM, BN, WM, WN, NS, false>), grid, dim3(C::NT), lds, st, g);
-    }
+    yk_launch_lds(g.splitk > 1 ? xg_kernel<BM, BN, WM, WN, NS, true> : xg_kernel<BM, BN, WM, WN, NS, false>, grid, dim3(C::NT), lds, st, g);
+    if (g.splitk > 1) yk_launch_lds(xg_reduce_kernel<BM, BN, WM, WN>, dim3(grid.x, grid.y), dim3(C::NT), rlds, st, g);
     return YK_OK;
 }
 template <int BM, int BN, int WM, int WN>
@@ -1050,14 +1035,8 @@ template <int BM, int BN, int NW>
 int x_launch_fin_bn(const xf_args &f, int ns, hipStream_t st) {
     typedef xf_cfg<BM, BN, NW> C;
     const dim3 grid((unsigned)((f.c.M + BM - 1) / BM), 1u, (unsigned)f.c.splitk);
-    static bool once = false;
-    if (!once) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(xf_kernel<BM, BN, 2, NW>), hipFuncAttributeMaxDynamicSharedMemorySize, C::lds(2));
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(xf_kernel<BM, BN, 3, NW>), hipFuncAttributeMaxDynamicSharedMemorySize, C::lds(3));
-        once = true;
-    }
-    if (ns >= 3) hipLaunchKernelGGL((xf_kernel<BM, BN, 3, NW>), grid, dim3(C::NT), (unsigned)C::lds(3), st, f);
-    else hipLaunchKernelGGL((xf_kernel<BM, BN, 2, NW>), grid, dim3(C::NT), (unsigned)C::lds(2), st, f);
+    if (ns < 3) yk_launch_lds(xf_kernel<BM, BN, 2, NW>, grid, dim3(C::NT), C::lds(2), st, f);
+    else yk_launch_lds(xf_kernel<BM, BN, 3, NW>, grid, dim3(C::NT), C::lds(3), st, f);
     return YK_OK;
 }
 int x_launch_fin(int bn, int ns, const xf_args &f, hipStream_t st) {
@@ -1071,13 +1050,8 @@ template <int TM, int TN, int SG, bool F32IN = false>
 int x_launch_b2(const xb_args &g, int batch, unsigned lds, hipStream_t st) {
     if constexpr (SG > 0 && !F32IN)
         if (g.in_f32) return x_launch_b2<TM, TN, SG, true>(g, batch, lds, st);
-    static unsigned allowed = 64 * 1024;
-    if (lds > allowed) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(xb_kernel<TM, TN, SG, F32IN>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024));
-        allowed = 160 * 1024;
-    }
     dim3 grid((unsigned)(batch * g.tiles_x * g.tiles_y), (unsigned)((g.N + 64 * TN - 1) / (64 * TN)));
-    hipLaunchKernelGGL((xb_kernel<TM, TN, SG, F32IN>), grid, dim3(256), lds, st, g);
+    yk_launch_lds(xb_kernel<TM, TN, SG, F32IN>, grid, dim3(256), lds, st, g);
     return YK_OK;
 }
 template <int TM, int TN>
@@ -2382,29 +2356,19 @@ int yk_xplan_run(yk_xplan *p, const void *d_in, int in_f32, int batch, hipStream
             xp_args pa = l.pa;
             pa.B = batch;
             pa.n_cluster = 8 * std::min(4, (batch + 7) / 8);           // <= 32 clusters of p_cw workgroups: one workgroup per CU
-            static bool once = false;
-            if (!once) {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void *>(xp_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(XP_NS * 8 * 6 * 1024 + XP_MISC));
-                once = true;
-            }
             pa.stamps = (li == p->dbg_launch) ? p->d_dbg : nullptr;
             pa.write_through = yk_env_flag("YK_CLUSTER_WT", false) ? 1 : 0;
             if (const char *e = yk_dev_env("YK_XP_DBG")) pa.dbg = atoi(e);
-            hipLaunchKernelGGL(xp_kernel, dim3((unsigned)(pa.n_cluster * l.p_cw)), dim3(XP_NT), XP_NS * 8 * 6 * 1024 + XP_MISC, st, pa);
+            yk_launch_lds(xp_kernel, dim3((unsigned)(pa.n_cluster * l.p_cw)), dim3(XP_NT), XP_NS * 8 * 6 * 1024 + XP_MISC, st, pa);
         } break;
         case XK_HEADS: {
             xh_args ha = l.ha;
             ha.B = batch;
             ha.n_cluster = 8 * std::min(4, (batch + 7) / 8);
-            static bool once = false;
-            if (!once) {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void *>(xh_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                once = true;
-            }
             ha.stamps = (li == p->dbg_launch) ? p->d_dbg : nullptr;
             ha.write_through = yk_env_flag("YK_CLUSTER_WT", false) ? 1 : 0;
             if (const char *e = yk_dev_env("YK_XH_DBG")) ha.dbg = atoi(e);
-            hipLaunchKernelGGL(xh_kernel, dim3((unsigned)(ha.n_cluster * XH_CW)), dim3(XH_NT), l.h_lds, st, ha);
+            yk_launch_lds(xh_kernel, dim3((unsigned)(ha.n_cluster * XH_CW)), dim3(XH_NT), l.h_lds, st, ha);
         } break;
         case XK_POOL: {
             xpool_args q = l.p;

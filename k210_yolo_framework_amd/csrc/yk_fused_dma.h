@@ -268,12 +268,7 @@ static int launch_fdma_t(const igemm_args &a, const fdma_plan &pl, hipStream_t s
     t.fd_rowu = yk_make_fastdiv((uint32_t)(t.in_cols * G));
     t.fd_g = yk_make_fastdiv((uint32_t)G);
     const int B = a.M / (a.Ho * a.Wo);
-    static size_t attr_lds = 64 * 1024;
-    if (pl.lds > attr_lds) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&fused_dma_kernel<NPW, KS, MT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024));
-        attr_lds = 160 * 1024;
-    }
-    hipLaunchKernelGGL((fused_dma_kernel<NPW, KS, MT>), dim3((unsigned)(B * t.tiles_x * t.tiles_y), pl.nsplit), dim3(768), pl.lds, st, a, t);
+    yk_launch_lds(fused_dma_kernel<NPW, KS, MT>, dim3((unsigned)(B * t.tiles_x * t.tiles_y), pl.nsplit), dim3(768), pl.lds, st, a, t);
     return YK_OK;
 }
 

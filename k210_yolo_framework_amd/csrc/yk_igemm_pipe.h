@@ -20,10 +20,6 @@
 // the row keeps (y0, x0) instead of a precomputed pointer.
 #pragma once
 
-#include <mutex>
-#include <set>
-#include <utility>
-
 template <int N>
 __device__ __forceinline__ void yk_wait_vm_lgkm0() {
     asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory");
@@ -226,26 +222,12 @@ __global__ void __launch_bounds__(64 * WM * WN) igemm_pipe_kernel(const igemm_ar
 #undef PIPE_CLK0
 }
 
-// more than 64 KB of dynamic LDS needs the attribute on EVERY kernel (instantiation) that is launched with it, on every device
-static inline void yk_allow_lds(const void *kern, size_t bytes) {
-    if (bytes <= 64 * 1024) return;
-    static std::mutex mu;
-    static std::set<std::pair<int, const void *>> done;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    std::lock_guard<std::mutex> lk(mu);
-    if (done.insert({dev, kern}).second) (void)hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-}
-
 template <int BM, int BN, int WM, int WN, int NS>
 static int launch_pipe(const igemm_args &a, hipStream_t st) {
     constexpr size_t ring = (size_t)NS * (BM + BN) * 64 * 2, ct = (size_t)BM * (BN + 8) * 2;
     constexpr size_t ldsd = ring > ct ? ring : ct;
     dim3 g2((a.M + BM - 1) / BM, (a.N + BN - 1) / BN, a.split_k > 1 ? a.split_k : 1);
-    auto go = [&](auto kern) {
-        yk_allow_lds(reinterpret_cast<const void *>(kern), ldsd);
-        hipLaunchKernelGGL(kern, g2, dim3(64 * WM * WN), ldsd, st, a);
-    };
+    auto go = [&](auto kern) { yk_launch_lds(kern, g2, dim3(64 * WM * WN), ldsd, st, a); };
     if (a.up0) {
         if (a.split_k > 1) go(igemm_pipe_kernel<BM, BN, WM, WN, NS, 2, true>);
         else go(igemm_pipe_kernel<BM, BN, WM, WN, NS, 0, true>);

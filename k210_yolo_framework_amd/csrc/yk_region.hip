@@ -34,6 +34,19 @@ extern "C" int yk_device_count(void) {
     return n;
 }
 
+// (device, kernel) -> the largest dynamic-LDS attribute set there.  A failed call records nothing: the next launch tries again, and the
+// launch itself reports the error.
+static std::mutex g_lds_mu;
+static std::map<std::pair<int, const void *>, size_t> g_lds_set;
+void yk_allow_lds(const void *kern, size_t bytes) {
+    if (bytes <= 64 * 1024) return;
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    std::lock_guard<std::mutex> lk(g_lds_mu);
+    size_t &set = g_lds_set[{dev, kern}];
+    if (bytes > set && hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess) set = bytes;
+}
+
 struct scratch_key {
     int dev;
     void *stream;
