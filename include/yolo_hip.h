@@ -275,6 +275,14 @@ int yk_region_batched(const yk_region_cfg_t *cfg, const float *d_input, int batc
  * (The `img / np.max(img)` that follows, utils.py:405, is fused into yk_run_u8.) */
 int yk_letterbox_u8(const uint8_t *d_src, int batch, int src_h, int src_w, uint8_t *d_dst, int dst_h, int dst_w,
                     void *stream);
+/* The same letterbox, then the training augmentation (the imgaug OneOf of tools/utils.py:84-88; semantics in
+ * k210_yolo_framework_amd/augment.py) in one launch for a batch of equally sized u8 frames.  d_inv: device float64 [batch][6],
+ * each image's inverse map M (row-major 2x3, pixel-index coordinates of the dst_h x dst_w tensor, src_idx = M . (x, y, 1)), built on
+ * the host.  The letterboxed image is warped bilinearly through M (taps outside the tensor read 0, round half up, capped at 255);
+ * no intermediate frame is written, and the result is bit-identical to yk_letterbox_u8 followed by that warp.  Integer M (identity,
+ * mirror) gives an exact pixel copy.  Bad arguments, a NULL d_inv included: YK_ERR_ARG.  Can be recorded in a graph. */
+int yk_letterbox_augment_u8(const uint8_t *d_src, int batch, int src_h, int src_w, const double *d_inv /* [batch][6] */,
+                            uint8_t *d_dst, int dst_h, int dst_w, void *stream);
 /* `img / np.max(img)` (tools/utils.py:405) for a batch of u8 frames of per_image bytes each -> fp32 (one correctly rounded quotient
  * per element, numpy's float64 division then the pipeline's float32 cast).  Used by the training input pipeline (N3); the inference
  * path fuses the normalisation into the stem conv (yk_run_u8). */

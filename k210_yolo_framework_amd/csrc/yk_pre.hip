@@ -14,19 +14,14 @@
 // The per-image max normalisation that follows (utils.py:405) is fused into the stem conv (yk_run_u8).
 #include "yk_common.h"
 
-__global__ void __launch_bounds__(256) letterbox_u8_kernel(const uint8_t *__restrict__ src, int batch, int sh, int sw,
-                                                           uint8_t *__restrict__ dst, int dh, int dw, double scale, int tx, int ty) {
-    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
-    const size_t total = (size_t)batch * dh * dw;
-    if (idx >= total) return;
-    const int x = (int)(idx % dw), y = (int)((idx / dw) % dh), b = (int)(idx / ((size_t)dw * dh));
+// One letterboxed pixel (x, y) of the network tensor from source frame `im` [sh][sw][3]: the arithmetic above, truncating cast.
+__device__ __forceinline__ void letterbox_px(const uint8_t *__restrict__ im, int sh, int sw, double scale, int tx, int ty, int x, int y,
+                                             uint8_t out[3]) {
     const double inv = 1.0 / scale;
     const double c = inv * (double)x + (-((double)tx * inv)), r = inv * (double)y + (-((double)ty * inv));
     const double minc_f = floor(c), minr_f = floor(r);
     const int minc = (int)minc_f, minr = (int)minr_f, maxc = (int)ceil(c), maxr = (int)ceil(r);
     const double dc = c - minc_f, dr = r - minr_f;
-    uint8_t *o = dst + idx * 3;
-    const uint8_t *im = src + (size_t)b * sh * sw * 3;
     auto px = [&](int yy, int xx, int ch) -> double {
         return (yy >= 0 && yy < sh && xx >= 0 && xx < sw) ? (double)im[((size_t)yy * sw + xx) * 3 + ch] : 0.0;
     };
@@ -34,8 +29,29 @@ __global__ void __launch_bounds__(256) letterbox_u8_kernel(const uint8_t *__rest
     for (int ch = 0; ch < 3; ++ch) {
         const double top = (1.0 - dc) * px(minr, minc, ch) + dc * px(minr, maxc, ch);
         const double bottom = (1.0 - dc) * px(maxr, minc, ch) + dc * px(maxr, maxc, ch);
-        o[ch] = (uint8_t)((1.0 - dr) * top + dr * bottom);    // astype('uint8'): truncation
+        out[ch] = (uint8_t)((1.0 - dr) * top + dr * bottom);    // astype('uint8'): truncation
     }
+}
+
+__global__ void __launch_bounds__(256) letterbox_u8_kernel(const uint8_t *__restrict__ src, int batch, int sh, int sw,
+                                                           uint8_t *__restrict__ dst, int dh, int dw, double scale, int tx, int ty) {
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t total = (size_t)batch * dh * dw;
+    if (idx >= total) return;
+    const int x = (int)(idx % dw), y = (int)((idx / dw) % dh), b = (int)(idx / ((size_t)dw * dh));
+    uint8_t v[3];
+    letterbox_px(src + (size_t)b * sh * sw * 3, sh, sw, scale, tx, ty, x, y, v);
+    uint8_t *o = dst + idx * 3;
+    o[0] = v[0];
+    o[1] = v[1];
+    o[2] = v[2];
+}
+
+static void letterbox_params(int src_h, int src_w, int dst_h, int dst_w, double *scale, int *tx, int *ty) {
+    const double sx = (double)dst_w / (double)src_w, sy = (double)dst_h / (double)src_h;
+    *scale = sx < sy ? sx : sy;                                                // utils.py:381-382
+    *tx = (int)(((double)dst_w - (double)src_w * *scale) / 2.0);               // .astype(int): truncation, utils.py:385
+    *ty = (int)(((double)dst_h - (double)src_h * *scale) / 2.0);
 }
 
 extern "C" int yk_letterbox_u8(const uint8_t *d_src, int batch, int src_h, int src_w, uint8_t *d_dst, int dst_h, int dst_w,
@@ -48,13 +64,71 @@ extern "C" int yk_letterbox_u8(const uint8_t *d_src, int batch, int src_h, int s
         yk_set_error("yk_letterbox_u8: no HIP device");
         return YK_ERR_NO_DEVICE;
     }
-    const double sx = (double)dst_w / (double)src_w, sy = (double)dst_h / (double)src_h;
-    const double scale = sx < sy ? sx : sy;                                    // utils.py:381-382
-    const int tx = (int)(((double)dst_w - (double)src_w * scale) / 2.0);       // .astype(int): truncation, utils.py:385
-    const int ty = (int)(((double)dst_h - (double)src_h * scale) / 2.0);
+    double scale;
+    int tx, ty;
+    letterbox_params(src_h, src_w, dst_h, dst_w, &scale, &tx, &ty);
     const size_t total = (size_t)batch * dst_h * dst_w;
     hipLaunchKernelGGL(letterbox_u8_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_src, batch,
                        src_h, src_w, d_dst, dst_h, dst_w, scale, tx, ty);
+    YK_HIP(hipGetLastError());
+    return YK_OK;
+}
+
+// ---- letterbox + training augmentation (k210_yolo_framework_amd/augment.py; the imgaug OneOf of tools/utils.py:84-88): the u8
+// letterboxed frame L above, then warped by the image's inverse map inv[b] = M (2x3, float64, pixel-index coordinates, computed on
+// the host; no transcendental here):
+//   c = M00*x + M01*y + M02, r = M10*x + M11*y + M12; taps floor/ceil as above, taps outside [0,dh)x[0,dw) read 0;
+//   out = min(255, floor((1-dr)*top + dr*bottom + 0.5)).
+// Each tap's L value is computed on the fly (letterbox_px), so no intermediate frame goes to HBM and the result is bit-identical
+// to yk_letterbox_u8 followed by the warp.  Identity and mirror matrices have integer entries: an exact pixel copy.
+__global__ void __launch_bounds__(256) letterbox_augment_u8_kernel(const uint8_t *__restrict__ src, int batch, int sh, int sw,
+                                                                   const double *__restrict__ inv, uint8_t *__restrict__ dst, int dh,
+                                                                   int dw, double scale, int tx, int ty) {
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t total = (size_t)batch * dh * dw;
+    if (idx >= total) return;
+    const int x = (int)(idx % dw), y = (int)((idx / dw) % dh), b = (int)(idx / ((size_t)dw * dh));
+    const double *m = inv + (size_t)b * 6;
+    const double c = m[0] * (double)x + m[1] * (double)y + m[2], r = m[3] * (double)x + m[4] * (double)y + m[5];
+    const double minc_f = floor(c), minr_f = floor(r), maxc_f = ceil(c), maxr_f = ceil(r);
+    const double dc = c - minc_f, dr = r - minr_f;
+    const uint8_t *im = src + (size_t)b * sh * sw * 3;
+    const double tr[4] = {minr_f, minr_f, maxr_f, maxr_f}, tc[4] = {minc_f, maxc_f, minc_f, maxc_f};
+    double t[4][3];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        uint8_t v[3] = {0, 0, 0};
+        if (tr[k] >= 0.0 && tr[k] < (double)dh && tc[k] >= 0.0 && tc[k] < (double)dw)      // compared as doubles: any M is safe
+            letterbox_px(im, sh, sw, scale, tx, ty, (int)tc[k], (int)tr[k], v);
+        t[k][0] = v[0];
+        t[k][1] = v[1];
+        t[k][2] = v[2];
+    }
+    uint8_t *o = dst + idx * 3;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+        const double top = (1.0 - dc) * t[0][ch] + dc * t[1][ch];
+        const double bottom = (1.0 - dc) * t[2][ch] + dc * t[3][ch];
+        o[ch] = (uint8_t)fmin(255.0, floor((1.0 - dr) * top + dr * bottom + 0.5));
+    }
+}
+
+extern "C" int yk_letterbox_augment_u8(const uint8_t *d_src, int batch, int src_h, int src_w, const double *d_inv, uint8_t *d_dst,
+                                       int dst_h, int dst_w, void *stream) {
+    if (!d_src || !d_inv || !d_dst || batch <= 0 || src_h <= 0 || src_w <= 0 || dst_h <= 0 || dst_w <= 0) {
+        yk_set_error("yk_letterbox_augment_u8: bad argument");
+        return YK_ERR_ARG;
+    }
+    if (yk_current_device() < 0) {
+        yk_set_error("yk_letterbox_augment_u8: no HIP device");
+        return YK_ERR_NO_DEVICE;
+    }
+    double scale;
+    int tx, ty;
+    letterbox_params(src_h, src_w, dst_h, dst_w, &scale, &tx, &ty);
+    const size_t total = (size_t)batch * dst_h * dst_w;
+    hipLaunchKernelGGL(letterbox_augment_u8_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_src,
+                       batch, src_h, src_w, d_inv, d_dst, dst_h, dst_w, scale, tx, ty);
     YK_HIP(hipGetLastError());
     return YK_OK;
 }

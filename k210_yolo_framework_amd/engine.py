@@ -71,7 +71,7 @@ def lib() -> C.CDLL:
         L.yk_device_count.restype = C.c_int
         for fn in ('yk_plan_create', 'yk_plan_create_ex', 'yk_run_u8', 'yk_run_f32', 'yk_get_output', 'yk_debug_read_tensor',
                    'yk_plan_launch_count', 'yk_plan_launch_info', 'yk_plan_check', 'yk_plan_peek_error', 'yk_plan_debug_set_error', 'yk_plan_profile', 'yk_decode_py', 'yk_decode_py_ex', 'yk_decode_py_packed',
-                   'yk_graph_begin', 'yk_graph_end', 'yk_graph_launch', 'yk_graph_node_count', 'yk_graph_kernel_node_count', 'yk_memcpy_async', 'yk_host_device_ptr', 'yk_stream_create', 'yk_stream_destroy', 'yk_stream_query_priority', 'yk_normalise_u8', 'yk_region_batched', 'yk_yolo_loss', 'yk_letterbox_u8',
+                   'yk_graph_begin', 'yk_graph_end', 'yk_graph_launch', 'yk_graph_node_count', 'yk_graph_kernel_node_count', 'yk_memcpy_async', 'yk_host_device_ptr', 'yk_stream_create', 'yk_stream_destroy', 'yk_stream_query_priority', 'yk_normalise_u8', 'yk_region_batched', 'yk_yolo_loss', 'yk_letterbox_u8', 'yk_letterbox_augment_u8',
                    'region_layer_init', 'yk_gemm_f32', 'yk_gemm_f32_grouped', 'yk_im2col3x3_f32', 'yk_col2im3x3_f32', 'yk_conv3x3_bn_fwd_f32', 'yk_conv3x3_bwd_weight_f32', 'yk_conv3x3_bwd_data_f32', 'yk_dw3x3_fwd_f32',
                    'yk_dw3x3_bwd_data_f32', 'yk_dw3x3_bwd_weight_f32', 'yk_dw3x3_bwd_weight_grouped_f32', 'yk_bn_train_fwd_f32', 'yk_bn_train_fwd_res_f32', 'yk_gemm_bn_fwd_f32', 'yk_dw3x3_bn_fwd_f32', 'yk_l2_segments_f32', 'yk_bn_train_bwd_f32',
                    'yk_bias_add_f32', 'yk_colsum_f32', 'yk_upsample2x_bwd_f32', 'yk_maxpool2_fwd_f32',
@@ -348,6 +348,22 @@ def letterbox_u8(frames, dst_hw, stream=None, out=None):
     assert out.is_cuda and out.is_contiguous() and tuple(out.shape) == (B, int(dst_hw[0]), int(dst_hw[1]), 3)
     _check(lib().yk_letterbox_u8(_ptr(frames), C.c_int(B), C.c_int(sh), C.c_int(sw), _ptr(out), C.c_int(out.shape[1]),
                                  C.c_int(out.shape[2]), _stream(stream)), 'yk_letterbox_u8')
+    return out
+
+
+def letterbox_augment_u8(frames, dst_hw, inv, stream=None, out=None):
+    """Letterbox + training augmentation in one launch (yk_letterbox_augment_u8, semantics in augment.py): cuda uint8 [B,h,w,3] and
+    each image's inverse map `inv` (cuda float64 [B,2,3] or [B,6]) -> cuda uint8 [B,H,W,3]."""
+    import torch
+    require_gpu()
+    assert frames.is_cuda and frames.dtype == torch.uint8 and frames.is_contiguous() and frames.shape[-1] == 3
+    B, sh, sw, _ = frames.shape
+    assert inv.is_cuda and inv.dtype == torch.float64 and inv.is_contiguous() and inv.numel() == 6 * B and inv.device == frames.device
+    if out is None:
+        out = torch.empty((B, int(dst_hw[0]), int(dst_hw[1]), 3), dtype=torch.uint8, device=frames.device)
+    assert out.is_cuda and out.is_contiguous() and tuple(out.shape) == (B, int(dst_hw[0]), int(dst_hw[1]), 3)
+    _check(lib().yk_letterbox_augment_u8(_ptr(frames), C.c_int(B), C.c_int(sh), C.c_int(sw), _ptr(inv), _ptr(out), C.c_int(out.shape[1]),
+                                         C.c_int(out.shape[2]), _stream(stream)), 'yk_letterbox_augment_u8')
     return out
 
 

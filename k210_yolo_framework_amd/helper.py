@@ -6,10 +6,12 @@ code base (vectorised numpy, tables built with broadcasting); each docstring nam
 reproduces, and tests/test_helper.py pins every one of them with hand-derived known answers.  The heavy arithmetic (model
 forward, decode, NMS, loss) is NOT here — it runs in libyolo_hip.so.
 
-Out of scope: imgaug augmentation, matplotlib drawing.
+Training augmentation (the imgaug OneOf of utils.py:84-88) is `augment.py`'s, parameters keyed by (seed, pass, row); see
+`data_augmenter`.  Out of scope: matplotlib drawing.
 """
 from __future__ import annotations
 
+import itertools
 import os
 from typing import Iterator, List, Optional, Sequence, Tuple, Union
 
@@ -181,7 +183,19 @@ class Helper(object):
         hot = np.concatenate([lab[lab[..., 4] > thersh] for lab in labels], axis=0)
         return np.column_stack([hot[:, 5:].argmax(axis=1), hot[:, :4]])
 
-    # ---- image side (behaviour of tools/utils.py:339-406) -----------------------------------------
+    # ---- image side (behaviour of tools/utils.py:309-406) -----------------------------------------
+    def data_augmenter(self, img: np.ndarray, true_box, aug):
+        """utils.py:309-337: the imgaug OneOf (flip / rotate / translate) of one letterboxed u8 image and its boxes, drawn from `aug`,
+        the row's five uniforms of `augment.param_table`.  Semantics and the deviations from the reference: augment.py; each class
+        stays with its own box.  -> (u8 image, surviving boxes)."""
+        from . import augment
+        hw = img.shape[:2]
+        A, t, M = augment.matrices(np.asarray(aug, np.float64).reshape(1, 5), hw)
+        img = augment.warp_u8(np.asarray(img, np.uint8), M[0])
+        if isinstance(true_box, np.ndarray):
+            true_box = augment.augment_boxes(true_box, A[0], t[0], hw)
+        return img, true_box
+
     def _read_img(self, img_path: str) -> np.ndarray:
         """RGB [H,W,3] like skimage.io.imread + gray2rgb / alpha drop (utils.py:339-355); pinned against the real skimage for every PIL
         mode by tests/golden/imread_golden.npz."""
@@ -204,8 +218,9 @@ class Helper(object):
         scale = np.full(2, (in_wh / img_wh).min())
         return scale, ((in_wh - img_wh * scale) / 2).astype(int)
 
-    def _process_img(self, img: np.ndarray, true_box, is_training: bool, is_resize: bool):
-        """utils.py:357-406 without augmentation: letterbox (bilinear, zero fill, truncating uint8 cast) then `img / np.max(img)`.
+    def _process_img(self, img: np.ndarray, true_box, is_training: bool, is_resize: bool, aug=None):
+        """utils.py:357-406: letterbox (bilinear, zero fill, truncating uint8 cast), with is_training the augmentation drawn from `aug`
+        (`data_augmenter`; the training pipeline runs the same two resamples fused on the GPU), then `img / np.max(img)`.
         The warp is skimage.transform.warp(order=1, mode='constant', cval=0, preserve_range=True) restated; pinned against the
         real skimage by tests/golden/letterbox_golden.npz."""
         if is_resize:
@@ -219,24 +234,29 @@ class Helper(object):
                 true_box[:, 1:5] = moved / net_wh
             img = letterbox_bilinear(img, tuple(self.in_hw[0]), float(scale[0]), translation)
         if is_training:
-            raise NotImplementedError('imgaug augmentation is out of scope (SURVEY.md §2 #6)')
+            if aug is None:
+                raise NotImplementedError('is_training=True augments: pass `aug`, the row of augment.param_table(seed, pass, rows)')
+            img, true_box = self.data_augmenter(img, true_box, aug)
         img = img / np.max(img)
         return img, true_box
 
     # ---- dataset iteration (behaviour of tools/utils.py:408-450) ----------------------------------
-    def generator(self, is_training=True, is_resize=True, is_make_lable=True, train_list=None):
-        """utils.py:408-415: (image, labels | boxes) one sample at a time."""
+    def generator(self, is_training=True, is_resize=True, is_make_lable=True, train_list=None, augs=None):
+        """utils.py:408-415: (image, labels | boxes) one sample at a time; with is_training, `augs` holds each row's augmentation
+        parameters (rows of augment.param_table)."""
         rows = self.train_list if train_list is None or train_list is True else train_list
-        for row in rows:
+        for k, row in enumerate(rows):
             src, boxes = row[0], np.array(row[1], float, copy=True)
             img = self._read_img(str(src)) if isinstance(src, (str, os.PathLike)) else src
-            img, boxes = self._process_img(img, boxes, is_training, is_resize)
+            img, boxes = self._process_img(img, boxes, is_training, is_resize, None if augs is None else augs[k])
             yield img, (self.box_to_label(boxes) if is_make_lable else boxes)
 
     def _create_dataset(self, image_ann_list, batch_size: int, rand_seed: int, is_training: bool, is_resize: bool,
                         repeat: bool = True) -> Iterator[Tuple[np.ndarray, List[np.ndarray]]]:
         """What the tf.data pipeline of utils.py:417-441 yields: (images [B,H,W,3] float32, one label tensor [B,h,w,A,5+C]
-        per layer), reshuffled every pass, incomplete batches dropped (`batch(batch_size, True)`), repeating for ever."""
+        per layer), reshuffled every pass, incomplete batches dropped (`batch(batch_size, True)`), repeating for ever.  With
+        is_training every sample is augmented, its parameters keyed by (rand_seed, pass, row): augment.param_table."""
+        from . import augment
         print(INFO, 'data augment is ', str(is_training))
         rng = np.random.default_rng(rand_seed)
         rows = list(image_ann_list)
@@ -244,9 +264,19 @@ class Helper(object):
             if repeat:                                     # the reference's infinite generator over an empty list never yields either;
                 raise ValueError('empty image list: nothing to batch')   # say so instead of spinning
             return
+        tables = {}
 
         def batch_of(picked):
-            samples = list(self.generator(is_training, is_resize, True, picked))
+            """picked: [(pass, row)]"""
+            augs = None
+            if is_training:
+                for p, _ in picked:
+                    if p not in tables:                    # passes only grow; a batch spans at most two
+                        for q in [q for q in tables if q < p - 1]:
+                            del tables[q]
+                        tables[p] = augment.param_table(rand_seed, p, len(rows))
+                augs = [tables[p][i] for p, i in picked]
+            samples = list(self.generator(is_training, is_resize, True, [rows[i] for _, i in picked], augs))
             imgs = np.stack([im.astype(np.float32) for im, _ in samples])
             labs = [np.stack([lab[l] for _, lab in samples]).astype(np.float32) for l in range(self.output_number)]
             return imgs, labs
@@ -254,20 +284,20 @@ class Helper(object):
             # fewer rows than one batch (a small validation split): the reference repeats BEFORE it batches (utils.py:438-441), so its
             # batches run across passes; a per-pass loop would never complete one
             pending: List = []
-            while True:
-                pending += [rows[i] for i in rng.permutation(len(rows))]
+            for p in itertools.count():
+                pending += [(p, int(i)) for i in rng.permutation(len(rows))]
                 while len(pending) >= batch_size:
                     yield batch_of(pending[:batch_size])
                     pending = pending[batch_size:]
-        while True:
+        for p in itertools.count():
             order = rng.permutation(len(rows)) if is_training or repeat else np.arange(len(rows))
             for s in range(0, len(order) - batch_size + 1, batch_size):
-                yield batch_of([rows[i] for i in order[s:s + batch_size]])
+                yield batch_of([(p, int(i)) for i in order[s:s + batch_size]])
             if not repeat:
                 return
 
     def set_dataset(self, batch_size, rand_seed, is_training=True, is_resize=True):
-        """utils.py:443-450."""
+        """utils.py:443-450; with is_training the training split is augmented, parameters keyed by (rand_seed, pass, row)."""
         self.batch_size = batch_size
         for split, lst, train in (('train', self.train_list, is_training), ('test', self.test_list, False)):
             setattr(self, split + '_dataset', self._create_dataset(lst, batch_size, rand_seed, train, is_resize))

@@ -14,8 +14,13 @@
   * a producer thread keeps `prefetch` batches ahead of the consumer (`.prefetch`); the consumer gets device tensors whose producing
     stream it must wait on (`batch.ready` is a recorded event; `__iter__` does the wait for the current stream).
 
-Images of one batch may have different sizes (VOC): they are letterboxed in groups of equal size.  Augmentation (imgaug,
-utils.py:357-376) is out of scope as everywhere in this build.
+Images of one batch may have different sizes (VOC): they are letterboxed in groups of equal size.
+
+augment=True adds the training augmentation (the imgaug OneOf of utils.py:84-88; semantics in augment.py): each row's parameters
+come from the epoch's table (seed, epoch, row), the letterboxed boxes are augmented before `batch_box_to_label`, the per-image
+inverse maps [n, 6] travel through a pinned slot like the labels, and each size group is letterboxed AND warped by one
+`yk_letterbox_augment_u8` launch (no intermediate frame).  `yk_normalise_u8` then divides by the augmented image's own maximum, as
+utils.py:405 does.
 """
 from __future__ import annotations
 
@@ -28,6 +33,7 @@ from typing import List, Optional, Sequence
 
 import numpy as np
 
+from . import augment as aug_mod
 from . import engine
 from .helper import Helper
 
@@ -121,10 +127,11 @@ class InputPipeline:
     """Iterable over one epoch: yields (x [per_rank,H,W,3] float32 cuda, [labels per layer, float32 cuda])."""
 
     def __init__(self, h: Helper, items: Sequence, global_batch: int, rank: int = 0, world: int = 1, seed: int = 0, epoch: int = 0,
-                 shuffle: bool = True, workers: int = 8, prefetch: int = 2, device: Optional[int] = None):
+                 shuffle: bool = True, workers: int = 8, prefetch: int = 2, device: Optional[int] = None, augment: bool = False):
         import torch
         engine.require_gpu()
         self.h, self.items = h, items
+        self.table = aug_mod.param_table(seed, epoch, len(items)) if augment else None       # per (seed, epoch, row): rank-independent
         self.rows = rank_rows(epoch_order(len(items), seed, epoch, shuffle), global_batch, rank, world)
         self.per = global_batch // world
         self.dev = torch.device('cuda', torch.cuda.current_device() if device is None else device)
@@ -187,16 +194,28 @@ class InputPipeline:
                 self._tick += 1
                 # labels of the whole batch in a handful of array operations (utils.py:207-230 on the letterboxed boxes), then ONE copy per
                 # layer into the pinned staging buffer (pinned memory is slow to write piecemeal from the CPU)
-                labs = self.h.batch_box_to_label(letterbox_boxes_batch(self.h, [im.shape[:2] for im in imgs],
-                                                                       [self.items[int(i)][1] for i in rows]))
+                boxes = letterbox_boxes_batch(self.h, [im.shape[:2] for im in imgs], [self.items[int(i)][1] for i in rows])
+                by_size = {}
+                for k, img in enumerate(imgs):
+                    by_size.setdefault(img.shape[:2], []).append(k)
+                inv_slot = None
+                if self.table is not None:
+                    A, t, M = aug_mod.matrices(self.table[rows], (H, W))
+                    boxes = aug_mod.augment_boxes_batch(boxes, A, t, (H, W))
+                    # the inverse maps in size-group order: group g reads a contiguous run of rows
+                    inv_slot = self._slot('inv', (n, 6), torch.float64)
+                    inv_slot[0].numpy()[...] = M.reshape(n, 6)[np.concatenate(list(by_size.values()))]
+                labs = self.h.batch_box_to_label(boxes)
                 lab_slots = [self._slot(('lab', l), labs[l].shape, torch.float32) for l in range(len(labs))]
                 for (view, _), lab in zip(lab_slots, labs):
                     view.numpy()[...] = lab
                 with torch.cuda.stream(self.stream):
                     frames = torch.empty((n, H, W, 3), dtype=torch.uint8, device=self.dev)
-                    by_size = {}
-                    for k, img in enumerate(imgs):
-                        by_size.setdefault(img.shape[:2], []).append(k)
+                    if inv_slot is not None:
+                        inv = inv_slot[0].to(self.dev, non_blocking=True)
+                        inv_slot[1][1] = torch.cuda.Event()
+                        inv_slot[1][1].record(self.stream)
+                    first = 0
                     for (sh, sw), idx in by_size.items():                   # equal-sized images are letterboxed in one launch
                         view, slot = self._slot('img', (len(idx), sh, sw, 3), torch.uint8)
                         hv = view.numpy()
@@ -205,7 +224,11 @@ class InputPipeline:
                         src = view.to(self.dev, non_blocking=True)
                         slot[1] = torch.cuda.Event()
                         slot[1].record(self.stream)
-                        out = engine.letterbox_u8(src, (H, W), stream=self.stream)
+                        if inv_slot is None:
+                            out = engine.letterbox_u8(src, (H, W), stream=self.stream)
+                        else:
+                            out = engine.letterbox_augment_u8(src, (H, W), inv[first:first + len(idx)], stream=self.stream)
+                        first += len(idx)
                         if len(by_size) == 1:
                             frames = out
                         else:

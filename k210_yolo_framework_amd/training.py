@@ -3,13 +3,15 @@
 Same CLI and the same `main(...)` parameter list as the reference script.  What `train_model.fit` did inside TensorFlow
 is `train.Trainer.step` here; the tf.data pipeline (tools/utils.py:417-450 `_create_dataset`: shuffle, read, letterbox,
 `box_to_label`, batch) is `pipeline.InputPipeline` (row N3: per-rank shards, thread-pool decode, GPU letterbox / normalise, two batches of prefetch); the
-plain-python `batches()` generator below is its host-only twin (tests compare the two bit for bit).  Validation runs the fp16 inference
+plain-python `batches()` generator below is its host-only twin (tests compare the two bit for bit).  `--augmenter True` (`make train
+IAA=True`) turns on the imgaug OneOf of tools/utils.py:84-88 for the training split: `augment.py`, fused into the GPU letterbox
+(`InputPipeline(augment=True)`), parameters keyed by (rand_seed, epoch, row); validation is never augmented.  Validation runs the fp16 inference
 engine on the exported weights (BatchNorm with moving statistics, like Keras' test phase).
 
 Checkpoints: `log/<time>/yolo_model.h5` in Keras' WEIGHTS-ONLY HDF5 layout (`model.save_weights` format: readable by the reference's
 `load_weights`, keras_inference.py:80; it is not a `save_model` file - no `model_config` - so `keras_freeze.py`'s `load_model` cannot
-open it; keras_io / h5lite, no h5py needed) plus the same arrays as `yolo_model.npz`; `--pre_ckpt` takes either.  Differences, reported at run time: imgaug augmentation and tfmot pruning are out of
-scope (SURVEY.md section 2 #6/#9) and raise instead of silently doing nothing."""
+open it; keras_io / h5lite, no h5py needed) plus the same arrays as `yolo_model.npz`; `--pre_ckpt` takes either.  Difference, reported at run time: tfmot pruning is out of
+scope (SURVEY.md section 2 #9) and raises instead of silently doing nothing."""
 from __future__ import annotations
 
 import argparse
@@ -45,8 +47,11 @@ def synthetic_list(n: int, in_hw, class_num: int, seed: int):
     return out
 
 
-def batches(h: Helper, items, batch_size: int, rng, shuffle: bool):
-    """tools/utils.py:417-450: (normalised image [B,H,W,3] float32, labels per layer [B,h,w,A,5+C] float32)."""
+def batches(h: Helper, items, batch_size: int, rng, shuffle: bool, augment=None):
+    """tools/utils.py:417-450: (normalised image [B,H,W,3] float32, labels per layer [B,h,w,A,5+C] float32).  augment=(seed, epoch):
+    every sample augmented with its row of augment.param_table(seed, epoch, len(items)), like InputPipeline(augment=True)."""
+    from . import augment as aug_mod
+    table = None if augment is None else aug_mod.param_table(augment[0], augment[1], len(items))
     order = rng.permutation(len(items)) if shuffle else np.arange(len(items))
     for s in range(0, len(order) - batch_size + 1, batch_size):             # drop_remainder=True (utils.py:447)
         xs, ys = [], [[] for _ in range(len(h.anchors))]
@@ -55,7 +60,8 @@ def batches(h: Helper, items, batch_size: int, rng, shuffle: bool):
             if isinstance(img, (str, os.PathLike)):
                 img = h._read_img(str(img))
             boxes = np.array(boxes, np.float64, copy=True)
-            img, boxes = h._process_img(img, boxes, is_training=False, is_resize=True)
+            img, boxes = h._process_img(img, boxes, is_training=table is not None, is_resize=True,
+                                        aug=None if table is None else table[i])
             xs.append(img.astype(np.float32))
             for l, lab in enumerate(h.box_to_label(boxes)):
                 ys[l].append(lab)
@@ -70,11 +76,15 @@ def main(args, train_set, class_num, pre_ckpt, model_def, depth_multiplier, is_a
     from .train import Trainer
     if is_prune == 'True':
         raise engine.YkError('tfmot magnitude pruning (keras_train.py:60-71) is out of scope of this build')
-    if is_augmenter == 'True':
-        raise engine.YkError('imgaug augmentation (tools/utils.py:357-376) is out of scope; run with IAA=False')
+    augment = is_augmenter == 'True'
     rank, world = int(os.environ.get('RANK', '0')), int(os.environ.get('WORLD_SIZE', '1'))
     local = int(os.environ.get('LOCAL_RANK', '0'))
-    engine.require_gpu()
+    try:
+        engine.require_gpu()
+    except engine.YkError as e:
+        if augment:
+            raise engine.YkError('--augmenter True (imgaug OneOf, tools/utils.py:84-88) runs in the GPU input pipeline: no HIP device') from e
+        raise
     torch.cuda.set_device(local)
     dist = None
     if world > 1:
@@ -120,12 +130,15 @@ def main(args, train_set, class_num, pre_ckpt, model_def, depth_multiplier, is_a
                  noobj_weight=noobj_weight, wh_weight=wh_weight, lr=init_learning_rate, decay=learning_rate_decay_factor, device=local,
                  world_size=world)
     from .pipeline import InputPipeline
+    if rank == 0:
+        print(INFO, 'data augment is ', str(augment))                            # utils.py:418
     steps = 0
     for epoch in range(max_nrof_epochs):
         t0, seen, run = time.time(), 0, 0.0
         # tools/utils.py:417-450: each rank decodes only its rows of the global batch, on a thread pool, two batches ahead;
         # letterbox + normalise on the GPU (pipeline.py)
-        pipe = InputPipeline(h, h.train_list, batch_size, rank, world, seed=rand_seed, epoch=epoch, shuffle=True, device=local)
+        pipe = InputPipeline(h, h.train_list, batch_size, rank, world, seed=rand_seed, epoch=epoch, shuffle=True, device=local,
+                             augment=augment)
         try:                                                                    # an exception in the step must not leave the producer running
             for x, ys in pipe:
                 out = tr.step(x, ys)
