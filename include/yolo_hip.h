@@ -390,6 +390,36 @@ int yk_axpy_f32(long long n, float a, const float *x, float *y, void *stream);  
 int yk_adam_f32(long long n, float *p, const float *g, float *m, float *v, float lr, float decay, long long iterations,
                 float beta1, float beta2, float eps, float grad_scale, void *stream);
 
+/* ---- KPU-exact mode: a kmodel v3 on the K210 KPU's integer arithmetic (kpu_load_kmodel / kpu_run_kmodel / kpu_get_output of
+ *      main.c:274,303,310, batched).  Outputs are bit-identical to oracle/kpu_ref.py (the restated KPU pipeline); DESIGN.md 3.7.
+ * The program is packed by k210_yolo_framework_amd/kmodel.py:pack_kpu from the parsed file (one parser):
+ *   values  int32 [n_values][4] = (C, H, W, dtype 0 = uint8 / 1 = fp32), every tensor of the run, each in its own buffer
+ *           ([max_batch][H][W][C], NHWC);
+ *   ops     int64 [n_ops][YK_KPU_FIELDS], issued in order: op code, input value (-1 = the frame), output value, then per op
+ *           (conv: kernel, pool type, pad value, shr_x, arg_x, blob offsets of the packed weights / per-channel constants / activation
+ *           segments, kmodel layer index, frame shape; gather: channel offset, 256-byte table offset or -1; dequantize: scale, bias bits);
+ *   outputs int32 [n_outputs] fp32 value ids;  blob: the bytes the ops address (16-byte aligned offsets).
+ * Every op, pool type and kernel size the kernels do not implement is refused here (YK_ERR_UNSUPPORTED), as is any inconsistent
+ * row (YK_ERR_ARG), and any tensor whose max_batch x C x H x W exceeds 2^30 elements (YK_ERR_UNSUPPORTED: the kernels index in 32 bits);
+ * yk_kpu_run_u8 never fails on the program's content. */
+#define YK_KPU_FIELDS 24
+#define YK_KPU_NHWC 0 /* frames uint8 [batch][H][W][C] (engine.letterbox_u8 / yk_run_u8) */
+#define YK_KPU_CHW 1  /* frames uint8 [batch][C][H][W] (what main.c feeds kpu_run_kmodel) */
+typedef struct yk_kpu_plan yk_kpu_plan_t; /* opaque */
+int yk_kpu_plan_create(yk_kpu_plan_t **out, const int64_t *ops, int n_ops, const int32_t *values, int n_values, const int32_t *outputs,
+                       int n_outputs, const void *blob, size_t blob_len, int max_batch, int device);
+void yk_kpu_plan_destroy(yk_kpu_plan_t *p);
+/* asynchronous on `stream`; one launch per op, no other stream touched (capturable with yk_graph_*) */
+int yk_kpu_run_u8(yk_kpu_plan_t *p, const uint8_t *d_frames, int batch, int layout, void *stream);
+/* borrowed device pointer to output idx, fp32 [max_batch][h][w][c] (the layout of yk_get_output: yk_decode_py consumes it) */
+int yk_kpu_get_output(yk_kpu_plan_t *p, int idx, float **d_ptr, size_t *bytes, int *h, int *w, int *c);
+int yk_kpu_output_count(const yk_kpu_plan_t *p);
+/* conv layer `layer_index` (kmodel layer index) of image `image` of the last run, uint8 CHW (n = C*H*W bytes); synchronises */
+int yk_kpu_debug_read(yk_kpu_plan_t *p, int layer_index, int image, uint8_t *h_dst, size_t n);
+/* launches one yk_kpu_run_u8 issues, and their median durations over `iters` runs (HIP events around every launch) */
+int yk_kpu_launch_count(const yk_kpu_plan_t *p);
+int yk_kpu_profile(yk_kpu_plan_t *p, const uint8_t *d_frames, int batch, int layout, int iters, void *stream, float *ms_out);
+
 #ifdef __cplusplus
 }
 #endif

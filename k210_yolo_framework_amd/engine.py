@@ -75,9 +75,12 @@ def lib() -> C.CDLL:
                    'region_layer_init', 'yk_gemm_f32', 'yk_gemm_f32_grouped', 'yk_im2col3x3_f32', 'yk_col2im3x3_f32', 'yk_conv3x3_bn_fwd_f32', 'yk_conv3x3_bwd_weight_f32', 'yk_conv3x3_bwd_data_f32', 'yk_dw3x3_fwd_f32',
                    'yk_dw3x3_bwd_data_f32', 'yk_dw3x3_bwd_weight_f32', 'yk_dw3x3_bwd_weight_grouped_f32', 'yk_bn_train_fwd_f32', 'yk_bn_train_fwd_res_f32', 'yk_gemm_bn_fwd_f32', 'yk_dw3x3_bn_fwd_f32', 'yk_l2_segments_f32', 'yk_bn_train_bwd_f32',
                    'yk_bias_add_f32', 'yk_colsum_f32', 'yk_upsample2x_bwd_f32', 'yk_maxpool2_fwd_f32',
-                   'yk_maxpool2_bwd_f32', 'yk_axpy_f32', 'yk_adam_f32', 'yk_dot_f32'):
+                   'yk_maxpool2_bwd_f32', 'yk_axpy_f32', 'yk_adam_f32', 'yk_dot_f32',
+                   'yk_kpu_plan_create', 'yk_kpu_run_u8', 'yk_kpu_get_output', 'yk_kpu_output_count', 'yk_kpu_debug_read',
+                   'yk_kpu_launch_count', 'yk_kpu_profile'):
             getattr(L, fn).restype = C.c_int
         L.yk_plan_destroy.restype = None
+        L.yk_kpu_plan_destroy.restype = None
         L.yk_graph_destroy.restype = None
         L.yk_scratch_generation.restype = C.c_ulonglong
         _lib = L
@@ -240,6 +243,121 @@ class Plan:
             fl, by = C.c_double(), C.c_double()
             lib().yk_plan_launch_info(self._h, C.c_int(i), name, C.c_size_t(128), C.byref(fl), C.byref(by))
             res.append((name.value.decode(), fl.value, by.value))
+        return res
+
+
+KPU_LAYOUTS = {'nhwc': 0, 'chw': 1}          # YK_KPU_NHWC / YK_KPU_CHW
+
+
+class KpuPlan:
+    """The K210 KPU's integer pipeline for a parsed kmodel v3 on the GPU (yk_kpu_*, include/yolo_hip.h): outputs
+    bit-identical to oracle/kpu_ref.run for every image.  The KPU takes the raw 0..255 pixels (no `img / np.max(img)`).  Duck-types Plan
+    where inference.detect and yolonet use it: `max_batch`, `run_u8`, `outputs`."""
+
+    def __init__(self, km, max_batch: int = 32, device: Optional[int] = None):
+        """km: a parsed kmodel.Kmodel (packed here) or a kmodel.KpuProgram that kmodel.pack_kpu already made."""
+        import torch
+        from . import kmodel
+        require_gpu()
+        # CPU: pack_kpu raises KmodelError for what the kernels do not implement
+        prog = km if isinstance(km, kmodel.KpuProgram) else kmodel.pack_kpu(km)
+        self.program = prog
+        self.max_batch = int(max_batch)
+        self.device = torch.cuda.current_device() if device is None else int(device)
+        self.input_chw = prog.input_chw
+        self._ops = np.ascontiguousarray(prog.ops, np.int64)
+        self._vals = np.ascontiguousarray(prog.values, np.int32)
+        self._outs = np.ascontiguousarray(prog.outputs, np.int32)
+        self._blob = np.ascontiguousarray(prog.blob, np.uint8)
+        self._h = C.c_void_p()
+        _check(lib().yk_kpu_plan_create(C.byref(self._h), self._ops.ctypes.data_as(C.POINTER(C.c_int64)), C.c_int(len(self._ops)),
+                                        self._vals.ctypes.data_as(i32p), C.c_int(len(self._vals)), self._outs.ctypes.data_as(i32p),
+                                        C.c_int(len(self._outs)), self._blob.ctypes.data_as(C.c_void_p), C.c_size_t(self._blob.size),
+                                        C.c_int(self.max_batch), C.c_int(self.device)), 'yk_kpu_plan_create')
+        self._out_views = None
+
+    def close(self):
+        self._out_views = None
+        if getattr(self, '_h', None) and self._h.value:
+            lib().yk_kpu_plan_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _frame_shape(self, layout: str):
+        c, h, w = self.input_chw
+        return (c, h, w) if layout == 'chw' else (h, w, c)
+
+    def run_u8(self, frames, layout: str = 'nhwc', stream=None) -> None:
+        """frames: torch.uint8 cuda tensor [B,H,W,C] ('nhwc', what letterbox_u8 / Plan.run_u8 use) or [B,C,H,W] ('chw', what main.c
+        feeds kpu_run_kmodel), raw 0..255 pixels.  Asynchronous (kpu_run_kmodel analogue)."""
+        import torch
+        if layout not in KPU_LAYOUTS:
+            raise YkError(f'layout {layout!r}: expected one of {sorted(KPU_LAYOUTS)}')
+        if not (frames.is_cuda and frames.dtype == torch.uint8 and frames.is_contiguous()):
+            raise YkError('KpuPlan.run_u8: frames must be a contiguous cuda uint8 tensor')
+        if tuple(frames.shape[1:]) != self._frame_shape(layout) or not 0 < frames.shape[0] <= self.max_batch:
+            raise YkError(f'KpuPlan.run_u8: frames {tuple(frames.shape)}, expected [<= {self.max_batch}, {", ".join(map(str, self._frame_shape(layout)))}]')
+        _check(lib().yk_kpu_run_u8(self._h, _ptr(frames), C.c_int(frames.shape[0]), C.c_int(KPU_LAYOUTS[layout]), _stream(stream)),
+               'yk_kpu_run_u8')
+
+    def output_ptrs(self) -> List[Tuple[int, Tuple[int, int, int]]]:
+        res = []
+        for i in range(len(self._outs)):
+            p = f32p()
+            nb = C.c_size_t()
+            h, w, c = C.c_int(), C.c_int(), C.c_int()
+            _check(lib().yk_kpu_get_output(self._h, C.c_int(i), C.byref(p), C.byref(nb), C.byref(h), C.byref(w), C.byref(c)),
+                   'yk_kpu_get_output')
+            res.append((C.cast(p, C.c_void_p).value, (h.value, w.value, c.value)))
+        return res
+
+    def outputs(self):
+        """Borrowed torch views [max_batch,h,w,c] fp32 of the network outputs (kpu_get_output; the layout of Plan.outputs)."""
+        import torch
+        if self._out_views is None:
+            self._out_views = [torch.as_tensor(_DevView(p, (self.max_batch, *s), '<f4', self), device=f'cuda:{self.device}')
+                               for p, s in self.output_ptrs()]
+        return self._out_views
+
+    def read_layer(self, index: int, image: int) -> np.ndarray:
+        """uint8 [C][H][W] output of the conv at kmodel layer `index` for image `image` of the last run (waits for the device)."""
+        v = self.program.conv_values.get(int(index))
+        if v is None:
+            raise YkError(f'layer {index} is not a KPU conv layer of this kmodel')
+        c, h, w = (int(x) for x in self.program.values[v, :3])
+        out = np.empty((c, h, w), np.uint8)
+        _check(lib().yk_kpu_debug_read(self._h, C.c_int(int(index)), C.c_int(int(image)), out.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                       C.c_size_t(out.size)), 'yk_kpu_debug_read')
+        return out
+
+    def profile(self, frames, layout: str = 'nhwc', iters: int = 10, stream=None) -> np.ndarray:
+        """Median duration (ms) of every launch of one run, HIP events around each (yk_kpu_profile)."""
+        n = lib().yk_kpu_launch_count(self._h)
+        ms = np.zeros(n, np.float32)
+        _check(lib().yk_kpu_profile(self._h, _ptr(frames), C.c_int(frames.shape[0]), C.c_int(KPU_LAYOUTS[layout]), C.c_int(iters),
+                                    _stream(stream), ms.ctypes.data_as(f32p)), 'yk_kpu_profile')
+        return ms
+
+    def launches(self) -> List[str]:
+        """Name of every launch of one run (op and kmodel layer), in issue order."""
+        from . import kmodel as km_
+        names = {km_.KPU_OP_CONV: 'conv', km_.KPU_OP_DWCONV: 'dwconv', km_.KPU_OP_GATHER: 'gather', km_.KPU_OP_DEQUANT: 'dequantize'}
+        res = []
+        for r in self.program.ops:
+            n = names[int(r[km_.KF_OP])]
+            res.append(f'{n}{int(r[km_.KF_K])}x{int(r[km_.KF_K])} layer {int(r[km_.KF_LAYER])}' if n.endswith('conv') else n)
         return res
 
 

@@ -94,8 +94,9 @@ def cli(argv=None):
     parser.add_argument('--output_size', type=int, help='net work output image size', default=(7, 10, 14, 20), nargs='+')
     parser.add_argument('--obj_thresh', type=float, help='obj mask thresh', default=0.7)
     parser.add_argument('--iou_thresh', type=float, help='iou mask thresh', default=0.3)
-    parser.add_argument('--precision', type=str, choices=['f16', 'f16x2'], default='f16x2',
-                        help="arithmetic of the conv stack (not in the reference): 'f16x2' = fp32-class results (default), 'f16' = fastest")
+    parser.add_argument('--precision', type=str, choices=['f16', 'f16x2', 'kpu'], default='f16x2',
+                        help="arithmetic of the conv stack (not in the reference): 'f16x2' = fp32-class results (default), 'f16' = fastest, "
+                             "'kpu' = a .kmodel/.kfpkg on the K210 KPU's integer arithmetic (raw 0..255 pixels, the board's outputs)")
     parser.add_argument('pre_ckpt', type=str, help='pre-train weights path')
     parser.add_argument('test_image', type=str, help='test image path')
     args = parser.parse_args(sys.argv[1:] if argv is None else argv)

@@ -216,6 +216,217 @@ def _parse_conv(index: int, data: bytes, body: bytes) -> ConvLayer:
                      bn_mul, bn_add, bn_shift, a_start, a_mul, a_shift, a_bias)
 
 
+# ---- the KPU-exact program (include/yolo_hip.h yk_kpu_plan_create) ------------------------------------------------------------------
+KPU_FIELDS = 24                                       # YK_KPU_FIELDS
+KPU_OP_CONV, KPU_OP_DWCONV, KPU_OP_GATHER, KPU_OP_DEQUANT = 1, 2, 3, 4
+(KF_OP, KF_IN, KF_OUT, KF_K, KF_POOL, KF_PAD, KF_SHR_X, KF_ARG_X, KF_W_OFF, KF_W_BYTES, KF_CH_OFF, KF_SEG_OFF, KF_LAYER, KF_C_OFF,
+ KF_TABLE_OFF, KF_SCALE_BITS, KF_BIAS_BITS, KF_IN_C, KF_IN_H, KF_IN_W) = range(20)
+KPU_U8, KPU_F32 = 0, 1
+
+
+@dataclass
+class KpuProgram:
+    """What yk_kpu_plan_create takes: op rows (int64 [n][KPU_FIELDS]), value shapes (int32 [n][4] = C, H, W, dtype), the fp32 output
+    value ids and the byte blob the rows address.  `input_chw` is the frame's shape, `conv_values` maps a conv's kmodel layer index to
+    its output value."""
+    ops: np.ndarray
+    values: np.ndarray
+    outputs: np.ndarray
+    blob: np.ndarray
+    input_chw: Tuple[int, int, int]
+    conv_values: Dict[int, int]
+
+    def output_shapes(self) -> List[Tuple[int, int, int]]:
+        """(C, H, W) of every output, in kmodel order."""
+        return [tuple(int(v) for v in self.values[i, :3]) for i in self.outputs]
+
+
+def _check_width(c: ConvLayer, name: str, v, bits: int, signed: bool) -> None:
+    """A register field must fit the width the KPU gives it (kpu_layer_argument_t; bn / act tables)."""
+    lo, hi = (-(1 << (bits - 1)), (1 << (bits - 1)) - 1) if signed else (0, (1 << bits) - 1)
+    if any(int(x) < lo or int(x) > hi for x in np.ravel(np.asarray(v, dtype=object))):
+        raise KmodelError(f'kmodel: conv layer {c.index}: {name} outside its {bits}-bit field')
+
+
+def pack_kpu(km: Kmodel) -> KpuProgram:
+    """Lower a parsed kmodel v3 to the KPU-exact program, resolving the KPU-RAM and main-memory addresses exactly as oracle/kpu_ref.run
+    does with its two dicts (a later write to an address replaces the tensor there).  Every tensor becomes a value with its own device
+    buffer; KPU convs, REQUANTIZE / RESIZE_NEAREST / CONCAT (gathers) and DEQUANTIZE become ops, K210_UPLOAD only renames.  Raises
+    KmodelError for anything the kernels do not implement or the oracle would not run.  CPU only."""
+    values: List[Tuple[int, int, int, int]] = []
+    rows: List[np.ndarray] = []
+    blob = bytearray()
+    conv_values: Dict[int, int] = {}
+
+    def new_value(c_, h_, w_, dt):
+        values.append((int(c_), int(h_), int(w_), dt))
+        return len(values) - 1
+
+    def put(b: bytes) -> int:
+        while len(blob) % 64:
+            blob.append(0)
+        off = len(blob)
+        blob.extend(b)
+        return off
+
+    def row(**kv):
+        r = np.zeros(KPU_FIELDS, np.int64)
+        r[KF_TABLE_OFF] = -1
+        for k, v in kv.items():
+            r[globals()['KF_' + k.upper()]] = int(v)
+        rows.append(r)
+
+    def shape(v):
+        return values[v][:3]
+
+    kpu: Dict[int, int] = {}
+    mem: Dict[int, int] = {}
+    first = True
+    input_chw = None
+    for l in km.layers:
+        if isinstance(l, ConvLayer):
+            c = l
+            if c.ksize not in (1, 3):
+                raise KmodelError(f'kmodel: conv layer {c.index}: kernel size {c.ksize} (the KPU has 1x1 and 3x3)')
+            if c.pool_type not in (POOL_BYPASS, POOL_LEFT_TOP_2_S2):
+                raise KmodelError(f'kmodel: conv layer {c.index}: KPU pool type {c.pool_type} is not implemented (bypass and left_top_2_s2 are)')
+            for name, v, bits, signed in (('pad_value', c.pad_value, 8, False), ('shr_x', c.shr_x, 4, False), ('shr_w', c.shr_w, 4, False),
+                                          ('arg_x', c.arg_x, 24, True), ('arg_w', c.arg_w, 24, True), ('arg_add', c.arg_add, 40, True),
+                                          ('bn_mul', c.bn_mul, 24, True), ('bn_add', c.bn_add, 32, True), ('bn_shift', c.bn_shift, 4, False),
+                                          ('act_shift', c.act_shift, 8, False), ('act_mul', c.act_mul, 16, True),
+                                          ('act_start', c.act_start, 36, True), ('act_bias', c.act_bias, 8, True)):
+                _check_width(c, name, v, bits, signed)
+            kk = c.ksize * c.ksize
+            w = np.asarray(c.weights)
+            if w.dtype != np.uint8 or w.shape != (c.out_ch, 1 if c.depthwise else c.in_ch, kk):
+                raise KmodelError(f'kmodel: conv layer {c.index}: weights {w.dtype} {w.shape}')
+            for name in ('bn_mul', 'bn_add', 'bn_shift'):
+                if np.shape(getattr(c, name)) != (c.out_ch,):
+                    raise KmodelError(f'kmodel: conv layer {c.index}: {name} has {np.shape(getattr(c, name))} entries, {c.out_ch} expected')
+            for name in ('act_start', 'act_mul', 'act_shift', 'act_bias'):
+                if np.shape(getattr(c, name)) != (16,):
+                    raise KmodelError(f'kmodel: conv layer {c.index}: {name} has {np.shape(getattr(c, name))} entries, 16 expected')
+            if first:
+                src = -1
+                input_chw = (c.in_ch, c.in_h, c.in_w)
+            else:
+                if c.src_addr not in kpu:
+                    raise KmodelError(f'kmodel: conv layer {c.index} reads KPU address {c.src_addr}, which no earlier layer wrote')
+                src = kpu[c.src_addr]
+                if values[src][3] != KPU_U8 or shape(src) != (c.in_ch, c.in_h, c.in_w):
+                    raise KmodelError(f'kmodel: conv layer {c.index}: input {shape(src)} != ({c.in_ch}, {c.in_h}, {c.in_w})')
+            first = False
+            H, W = c.in_h, c.in_w
+            oh, ow = ((H + 1) // 2, (W + 1) // 2) if c.pool_type == POOL_LEFT_TOP_2_S2 else (H, W)
+            if (c.out_h, c.out_w) != (oh, ow) or (c.depthwise and c.out_ch != c.in_ch):
+                raise KmodelError(f'kmodel: conv layer {c.index}: output ({c.out_ch}, {c.out_h}, {c.out_w}) does not follow from the input '
+                                  f'({c.in_ch}, {H}, {W}) and pool type {c.pool_type}')
+            w64 = w.astype(np.int64)
+            sum_w = w64.reshape(c.out_ch, -1).sum(1)
+            g_ic = 1 if c.depthwise else c.in_ch
+            K = kk * g_ic
+            ch = np.zeros((c.out_ch, 8), np.int64)
+            ch[:, 0] = ((np.int64(c.arg_w) * sum_w) >> np.int64(c.shr_w)) + np.int64(c.arg_add * g_ic)
+            if c.depthwise:
+                wb = w.reshape(c.out_ch, kk).tobytes()
+            else:
+                ch[:, 1] = 128 * sum_w                                          # 128 sum(w') + 16384 K, with sum(w') = sum(w) - 128 K
+                cp = (c.in_ch + 15) // 16 * 16
+                nq = kk * cp // 16
+                kw = (nq + 3) // 4 * 64
+                ocp = (c.out_ch + 31) // 32 * 32
+                wp = np.zeros((ocp, kw), np.int8)
+                t = np.zeros((c.out_ch, kk, cp), np.int16)
+                t[:, :, :c.in_ch] = w64.transpose(0, 2, 1) - 128                 # [oc][tap][c] of w' = w - 128
+                wp[:c.out_ch, :kk * cp] = t.reshape(c.out_ch, kk * cp).astype(np.int8)
+                wb = wp.tobytes()
+            ch[:, 2], ch[:, 3], ch[:, 4] = c.bn_mul, c.bn_add, c.bn_shift
+            seg = np.stack([np.asarray(c.act_start, np.int64), np.asarray(c.act_mul, np.int64), np.asarray(c.act_shift, np.int64),
+                            np.asarray(c.act_bias, np.int64)], 1)
+            w_off = put(wb)
+            ch_off = put(ch.tobytes())
+            seg_off = put(np.ascontiguousarray(seg).tobytes())
+            dst = new_value(c.out_ch, c.out_h, c.out_w, KPU_U8)
+            row(op=KPU_OP_DWCONV if c.depthwise else KPU_OP_CONV, **{'in': src}, out=dst, k=c.ksize, pool=c.pool_type, pad=c.pad_value,
+                shr_x=c.shr_x, arg_x=c.arg_x, w_off=w_off, w_bytes=len(wb), ch_off=ch_off, seg_off=seg_off, layer=c.index,
+                in_c=c.in_ch, in_h=c.in_h, in_w=c.in_w)
+            conv_values[c.index] = dst
+            kpu[c.dst_addr] = dst
+            if c.flags & KLF_MAIN_MEM_OUT:
+                mem[c.main_mem_out] = dst
+            continue
+        f = l.fields
+
+        def src_of(addr, what):
+            if addr not in mem:
+                raise KmodelError(f'kmodel: layer {l.index} ({what}) reads main-memory address {addr}, which no earlier layer wrote')
+            v = mem[addr]
+            if values[v][3] != KPU_U8:
+                raise KmodelError(f'kmodel: layer {l.index} ({what}) reads a dequantised (fp32) tensor; only uint8 inputs are implemented')
+            return v
+
+        def size(v):
+            C_, H_, W_ = shape(v)
+            return C_ * H_ * W_
+
+        if l.type == KL_DEQUANTIZE:
+            s = src_of(f['src'], 'DEQUANTIZE')
+            if size(s) != f['count']:
+                raise KmodelError(f'kmodel: layer {l.index}: DEQUANTIZE of {f["count"]} elements, the source has {size(s)}')
+            d = new_value(*shape(s), KPU_F32)
+            row(op=KPU_OP_DEQUANT, **{'in': s}, out=d, scale_bits=int(np.float32(f['scale']).view(np.uint32)),
+                bias_bits=int(np.float32(f['bias']).view(np.uint32)))
+            mem[f['dst']] = d
+        elif l.type == KL_REQUANTIZE:
+            s = src_of(f['src'], 'REQUANTIZE')
+            tab = np.asarray(f['table'])
+            if size(s) != f['count'] or tab.dtype != np.uint8 or tab.shape != (256,):
+                raise KmodelError(f'kmodel: layer {l.index}: REQUANTIZE of {f["count"]} elements through a {tab.dtype} {tab.shape} table')
+            d = new_value(*shape(s), KPU_U8)
+            row(op=KPU_OP_GATHER, **{'in': s}, out=d, c_off=0, table_off=put(tab.tobytes()))
+            mem[f['dst']] = d
+        elif l.type == KL_QUANTIZED_RESIZE_NN:
+            s = src_of(f['src'], 'RESIZE_NEAREST')
+            if shape(s) != (f['channels'], f['in_h'], f['in_w']) or f['out_h'] <= 0 or f['out_w'] <= 0:
+                raise KmodelError(f'kmodel: layer {l.index}: RESIZE_NEAREST of {shape(s)} as ({f["channels"]}, {f["in_h"]}, {f["in_w"]})')
+            d = new_value(f['channels'], f['out_h'], f['out_w'], KPU_U8)
+            row(op=KPU_OP_GATHER, **{'in': s}, out=d, c_off=0)
+            mem[f['dst']] = d
+        elif l.type == KL_QUANTIZED_CONCAT:
+            parts = [src_of(a, 'CONCAT') for a, _ in f['inputs']]
+            if not parts:
+                raise KmodelError(f'kmodel: layer {l.index}: CONCAT of nothing')
+            for p_, (_, sz) in zip(parts, f['inputs']):
+                if size(p_) != sz or shape(p_)[1:] != shape(parts[0])[1:]:
+                    raise KmodelError(f'kmodel: layer {l.index}: CONCAT parts {[shape(p) for p in parts]} (sizes {[s for _, s in f["inputs"]]})')
+            d = new_value(sum(shape(p_)[0] for p_ in parts), *shape(parts[0])[1:], KPU_U8)
+            off = 0
+            for p_ in parts:
+                row(op=KPU_OP_GATHER, **{'in': p_}, out=d, c_off=off)
+                off += shape(p_)[0]
+            mem[f['dst']] = d
+        elif l.type == KL_K210_UPLOAD:
+            s = src_of(f['src'], 'K210_UPLOAD')
+            if shape(s) != (f['channels'], f['height'], f['width']):
+                raise KmodelError(f'kmodel: layer {l.index}: K210_UPLOAD of {shape(s)} as ({f["channels"]}, {f["height"]}, {f["width"]})')
+            kpu[f['kpu_addr']] = s
+        else:
+            raise KmodelError(f'kmodel: layer {l.index} has type {l.type}, which the KPU-exact mode does not implement')
+    if input_chw is None:
+        raise KmodelError('kmodel: no KPU conv layer reads the frame')
+    outs = []
+    for a, _ in km.outputs:
+        if a not in mem:
+            raise KmodelError(f'kmodel: output at main-memory address {a} is written by no layer')
+        if values[mem[a]][3] != KPU_F32:
+            raise KmodelError(f'kmodel: output at main-memory address {a} is not dequantised (uint8 outputs are not implemented)')
+        outs.append(mem[a])
+    if not outs:
+        raise KmodelError('kmodel: no outputs')
+    return KpuProgram(np.stack(rows), np.asarray(values, np.int32).reshape(-1, 4), np.asarray(outs, np.int32),
+                      np.frombuffer(bytes(blob), np.uint8).copy(), input_chw, conv_values)
+
+
 # ---- dequantisation into Keras-named float weights ---------------------------------------------------------------------------------
 def _act_fit(c: ConvLayer) -> Tuple[float, float, float, float]:
     """The activation table as  y = y0 + s_pos * (z - z0)  for z >= z0,  y0 + s_neg * (z - z0)  below: returns (z0, y0, s_pos, s_neg).

@@ -10,6 +10,9 @@ numpy out and the reference's shapes and (h, w, anchor, entry) order.
 All arithmetic happens in libyolo_hip.so (engine.Plan); without a GPU `predict` raises.  The models default to the 'f16x2'
 precision mode (fp16 MFMA with compensated operands: the fp32-class results a Keras user expects, scores within 1e-3 and the same
 boxes); pass precision='f16' (or set `model.precision`) for the throughput mode used by bench.py.
+precision='kpu' runs a loaded `.kmodel` / `.kfpkg` on the K210 KPU's own integer arithmetic (engine.KpuPlan): the outputs the board
+computes, bit for bit as oracle/kpu_ref.py restates them.  The KPU takes the raw 0..255 pixels of uint8 frames; the float modes divide
+each image by its own maximum first (tools/utils.py:405), so for images whose maximum is below 255 the two modes see different inputs.
 
 Weights: Keras HDF5 files (`.h5`, read and written by keras_io / h5lite without h5py: the reference's checkpoint format,
 including the 255->A*(5+C) head cut of yolonet.py:146-156,182-189) or a flat `.npz` with Keras-layout arrays
@@ -67,6 +70,8 @@ class YoloModel:
             if tuple(weights[k].shape) != tuple(v.shape):
                 raise ValueError(f'{k}: shape {weights[k].shape} != {v.shape}')
         self._s['weights'] = {k: np.asarray(weights[k], np.float32) for k in want}
+        self._s.pop('kmodel', None)              # the integer model no longer describes these weights
+        self._s.pop('kpu_program', None)
         self._drop_plan()
 
     def load_weights(self, path: str, by_name: bool = False) -> None:
@@ -83,8 +88,10 @@ class YoloModel:
             # the K210 demo's 8-bit model (yolo3_frame_test_public/kfpkg/kpu_yolov3.kfpkg -> yolo.kmodel, main.c:57,213,274), dequantised
             from . import kmodel
             data = kmodel.read_kfpkg(path) if path.endswith('.kfpkg') else open(path, 'rb').read()
-            w, self.last_load_report = kmodel.to_float_weights(kmodel.parse(data))
+            km = kmodel.parse(data)
+            w, self.last_load_report = kmodel.to_float_weights(km)
             self.set_weights(w)
+            self._s['kmodel'] = km                   # kept beside its float weights: precision='kpu' runs it as the board does
             return
         with np.load(path) as z:
             have = {k: z[k] for k in z.files}
@@ -118,18 +125,46 @@ class YoloModel:
         p = self._s.get('plan')
         if p is None or p.max_batch < batch:
             self._drop_plan()
-            p = engine.Plan(self.spec, self._s['weights'], max_batch=max(batch, 1), precision=self.precision)
+            if self.precision == 'kpu':
+                p = engine.KpuPlan(self._kmodel(), max_batch=max(batch, 1))
+            else:
+                p = engine.Plan(self.spec, self._s['weights'], max_batch=max(batch, 1), precision=self.precision)
             self._s['plan'] = p
         return p
 
+    def _kmodel(self):
+        """The loaded kmodel packed once for the KPU-exact mode (kept beside it) and checked against this network's input and output
+        shapes (precision='kpu')."""
+        from . import engine, kmodel
+        km = self._s.get('kmodel')
+        if km is None:
+            raise engine.YkError("precision='kpu' runs a K210 kmodel: load_weights a .kmodel or .kfpkg first")
+        prog = self._s.get('kpu_program')
+        if prog is None:
+            try:
+                prog = kmodel.pack_kpu(km)
+            except kmodel.KmodelError as e:
+                raise engine.YkError(f"precision='kpu': {e}") from e
+            self._s['kpu_program'] = prog
+        want_in = (3, *self.spec.in_hw)
+        e = 5 + self.spec.class_num
+        want_out = [(self.spec.anchor_num * e, h, w) for (h, w) in self.spec.out_hw()]
+        if tuple(prog.input_chw) != want_in or prog.output_shapes() != want_out:
+            raise engine.YkError(f'kmodel takes {tuple(prog.input_chw)} and gives {prog.output_shapes()} (C, H, W); this network takes '
+                                 f'{want_in} and gives {want_out}')
+        return prog
+
     def predict(self, x: np.ndarray) -> List[np.ndarray]:
         """keras_inference.py:88.  x: [N,H,W,3] float (already `img / np.max(img)`) or uint8 frames
-        (then the normalisation of tools/utils.py:405 is done on the GPU)."""
+        (then the normalisation of tools/utils.py:405 is done on the GPU).  precision='kpu': uint8 frames only, raw 0..255 pixels."""
         import torch
         x = np.asarray(x)
         if x.ndim == 3:
             x = x[None]
         n = x.shape[0]
+        if self.precision == 'kpu' and x.dtype != np.uint8:
+            from . import engine
+            raise engine.YkError("precision='kpu' takes uint8 frames (the KPU's raw 0..255 pixels), not normalised floats")
         plan = self._plan(n)
         if x.dtype == np.uint8:
             plan.run_u8(torch.from_numpy(np.ascontiguousarray(x)).cuda())
