@@ -319,13 +319,15 @@ int yk_gemm_f32(int transA, int transB, int M, int N, int K, float alpha, const 
  * summation-order differences). */
 int yk_gemm_f32_grouped(int count, int transA, int transB, const int *M, const int *N, const int *K, float alpha, const float *const *A,
                         const int *lda, const float *const *B, const int *ldb, float beta, float *const *C, const int *ldc, void *stream);
-/* 3x3 Conv2D through GEMM: col [B*Ho*Wo][9*C], k = (ky*3+kx)*C + c; col2im is the adjoint (sums overlaps). */
+/* 3x3 Conv2D through a column matrix and GEMM, for what the implicit GEMM below does not cover (the 3-channel stem, the strided data
+ * gradient): col [B*Ho*Wo][9*C], k = (ky*3+kx)*C + c; col2im is the adjoint (sums overlaps). */
 int yk_im2col3x3_f32(const float *x, int B, int Hi, int Wi, int C, int Ho, int Wo, int stride, int pad_t, int pad_l,
                      float *col, void *stream);
 int yk_col2im3x3_f32(const float *col, int B, int Hi, int Wi, int C, int Ho, int Wo, int stride, int pad_t, int pad_l,
                      float *dx, void *stream);
-/* 3x3 Conv2D as an implicit GEMM (no column matrix); weights [Co][9 * Ci] (k = (ky*3+kx)*Ci + c).  Needs Ci % 4 == 0 (Co % 4 == 0 too for the
- * gradients; stride 1 for the data gradient) and 16-byte aligned tensors - YK_ERR_UNSUPPORTED otherwise (the im2col path above covers those).
+/* 3x3 Conv2D as an implicit GEMM (no column matrix); weights [Co][9 * Ci] (k = (ky*3+kx)*Ci + c).  A NULL tensor or a non-positive size:
+ * YK_ERR_ARG.  Needs Ci % 4 == 0 (Co % 4 == 0 too for the gradients; stride 1 for the data gradient) and 16-byte aligned tensors -
+ * YK_ERR_UNSUPPORTED otherwise (yk_im2col3x3_f32 / yk_col2im3x3_f32 + yk_gemm_f32 cover those).
  * yk_conv3x3_bn_fwd_f32: z = conv(x); with gamma != NULL also BatchNormalization(training) + activation (+ residual) -> y, as yk_gemm_bn_fwd_f32.
  * Forward and weight gradient add in the order of im2col + yk_gemm_f32: bitwise the same result. */
 int yk_conv3x3_bn_fwd_f32(const float *x, const float *w, int B, int Hi, int Wi, int Ci, int Ho, int Wo, int stride, int pad_t, int pad_l, int Co,
@@ -357,7 +359,8 @@ int yk_bn_train_fwd_res_f32(const float *z, long long M, int C, const float *gam
                             float alpha, float *y, float *save_mean, float *save_invstd, float *moving_mean,
                             float *moving_var, float momentum, const float *res, void *stream);
 /* Conv2D / DepthwiseConv2D + BatchNormalization(training=True) + activation (+ residual) forward in ONE call: z = the convolution
- * (X [M][K] row-major with leading dimension ldx, W [N][K]: 1x1 convs directly, 3x3 through yk_im2col3x3_f32), y as yk_bn_train_fwd_res_f32.
+ * (X [M][K] row-major with leading dimension ldx, W [N][K]: a 1x1 conv's input, or the column matrix of a 3x3 conv that
+ * yk_conv3x3_bn_fwd_f32 does not take), y as yk_bn_train_fwd_res_f32.
  * The producer of z leaves the partial sums of the batch statistics, so z is not read again for them.  Same arithmetic per element as the
  * separate calls; the statistics are added in another (fixed) order in double. */
 int yk_gemm_bn_fwd_f32(int M, int N, int K, const float *X, int ldx, const float *W, int ldw, float *z, const float *gamma, const float *beta,
@@ -377,7 +380,6 @@ int yk_maxpool2_fwd_f32(const float *x, int B, int Hi, int Wi, int C, int Ho, in
                         void *stream);
 int yk_maxpool2_bwd_f32(const float *dy, const uint8_t *argmax, int B, int Hi, int Wi, int C, int Ho, int Wo, int stride, float *dx,
                         void *stream);
-int yk_dot_f32(long long n, const float *x, const float *y, float alpha, float beta, float *out, void *stream); /* *out = alpha*<x,y> + beta*(*out) */
 /* keras.regularizers.l2(weight) of yolonet.py:245-250 over `nseg` segments of one flat parameter buffer in one pass: *out = weight * sum w^2
  * (want_value) and / or grads[j] += 2 * weight * params[j] (want_grad).  d_prefix [nseg + 1] = running sum of the segment lengths (device,
  * int64), d_offset [nseg] = start of every segment in the flat buffer, total = d_prefix[nseg]. */

@@ -5,16 +5,23 @@
 // fp32 FMA chains) — at 16 images per GPU the step is far from any roofline and parity with an fp32 autograd
 // oracle is what matters first.
 //
-//   yk_gemm_f32            C = alpha * op(A) * op(B) + beta * C  (row-major, any shape; optional split-K)
-//                          -> 1x1 conv forward / data gradient / weight gradient, and 3x3 convs through
-//   yk_im2col3x3_f32 / yk_col2im3x3_f32
-//   yk_dw3x3_{fwd,bwd_data,bwd_weight}_f32      DepthwiseConv2D
-//   yk_bn_train_fwd_f32 / yk_bn_train_bwd_f32   BatchNormalization in training mode fused with the activation
-//   yk_upsample2x_bwd_f32, yk_axpy_f32, yk_adam_f32 (Keras Adam incl. `decay`, keras_train.py:74-76)
-// Round 6 (what train.py calls now; the entry points above stay):
-//   yk_gemm_bn_fwd_f32 / yk_dw3x3_bn_fwd_f32     conv + BatchNorm forward in one call, the producer of z leaves the statistics' partial sums
-//   yk_gemm_f32_grouped / yk_dw3x3_bwd_weight_grouped_f32   all weight gradients of a backward pass in four launches
-//   yk_conv3x3_bn_fwd_f32 / _bwd_weight_f32 / _bwd_data_f32  3x3 convs as implicit GEMMs (no column matrix)
+// Forward, conv + BatchNormalization(training) + activation (+ residual) in one call; the producer of z leaves the statistics' partial sums:
+//   yk_gemm_bn_fwd_f32                 1x1 convs, and the 3-channel stem on its column matrix
+//   yk_conv3x3_bn_fwd_f32              3x3 convs as implicit GEMMs (no column matrix; Cin % 4 == 0)
+//   yk_dw3x3_bn_fwd_f32                DepthwiseConv2D
+//   yk_gemm_f32 + yk_bias_add_f32      the biased output convs (no BatchNorm); yk_gemm_f32: C = alpha * op(A) * op(B) + beta * C,
+//                                      row-major, any shape, optional split-K
+// Backward:
+//   yk_bn_train_bwd_f32                BatchNormalization + activation
+//   yk_gemm_f32                        1x1 data gradients; the column-matrix products of the stem and of the strided 3x3 data gradients
+//   yk_conv3x3_bwd_weight_f32 / _bwd_data_f32   3x3 weight gradient and stride-1 data gradient as implicit GEMMs (Cin, Cout % 4 == 0)
+//   yk_im2col3x3_f32 / yk_col2im3x3_f32         the column matrix and its adjoint, where the implicit kernels do not apply
+//   yk_dw3x3_bwd_data_f32              DepthwiseConv2D data gradient
+//   yk_gemm_f32_grouped / yk_dw3x3_bwd_weight_grouped_f32   the 1x1 and depthwise weight gradients of a backward pass in four launches
+//   yk_colsum_f32, yk_maxpool2_{fwd,bwd}_f32, yk_upsample2x_bwd_f32, yk_axpy_f32   bias gradient and the other layers
+// Step: yk_l2_segments_f32 (the l2 kernel regulariser), yk_adam_f32 (Keras Adam incl. `decay`, keras_train.py:74-76).
+// Per-layer forms, public ops of their own and the references the fused and grouped calls are tested against:
+//   yk_bn_train_fwd_f32 / yk_bn_train_fwd_res_f32, yk_dw3x3_fwd_f32, yk_dw3x3_bwd_weight_f32, yk_gemm_f32 as a weight gradient
 #include "yk_common.h"
 #include <algorithm>
 #include <cmath>
@@ -346,36 +353,13 @@ extern "C" int yk_gemm_f32_grouped(int count, int transA, int transB, const int 
     return YK_OK;
 }
 
-// <x, y> in two fixed-order stages (the l2 regulariser's value): out = alpha * dot + beta * out
-__global__ void __launch_bounds__(256) dot_partial_kernel(size_t n, const float *__restrict__ x, const float *__restrict__ y, double *__restrict__ part) {
-    __shared__ double red[256];
-    double s = 0;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) s += (double)x[i] * (double)y[i];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) part[blockIdx.x] = red[0];
-}
+// second, fixed-order stage of a sum of per-block partials (the l2 regulariser's value below): out = alpha * sum + beta * out
 __global__ void __launch_bounds__(64) dot_finish_kernel(const double *__restrict__ part, int blocks, float alpha, float beta, float *__restrict__ out) {
     double s = 0;
     for (int k = threadIdx.x; k < blocks; k += 64) s += part[k];
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
     if (threadIdx.x == 0) *out = alpha * (float)s + (beta != 0.f ? beta * *out : 0.f);
-}
-extern "C" int yk_dot_f32(long long n, const float *x, const float *y, float alpha, float beta, float *out, void *stream) {
-    int dev = yk_current_device();
-    if (dev < 0) return YK_ERR_NO_DEVICE;
-    const int blocks = (int)std::min<long long>(512, (n + 255) / 256);
-    double *part = (double *)yk_scratch(dev, stream, 15, sizeof(double) * 512);
-    if (!part) return YK_ERR_NOMEM;
-    hipLaunchKernelGGL(dot_partial_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (size_t)n, x, y, part);
-    hipLaunchKernelGGL(dot_finish_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const double *)part, blocks, alpha, beta, out);
-    YK_HIP(hipGetLastError());
-    return YK_OK;
 }
 
 // keras.regularizers.l2(weight) over SEGMENTS of one flat parameter buffer (yolonet.py:245-250: every DarknetConv2D kernel): the value
@@ -1520,9 +1504,9 @@ extern "C" int yk_dw3x3_bn_fwd_f32(const float *x, const float *w, int B, int Hi
 }
 
 // --------------------------------------------------------------------------------------------------------
-// 3x3 convolutions as IMPLICIT GEMMs (round 6; yk_gemm_f32.h CONV = 1 / 2 / 3): no column matrix - rounds 2-5 wrote it (113 MB for the 14x20x704
-// head conv), multiplied it, and for the data gradient wrote a column matrix of gradients and folded it (col2im).  Needs Cin % 4 == 0 (and
-// Cout % 4 == 0, stride 1 for the data gradient); the 3-channel stem keeps im2col.
+// 3x3 convolutions as IMPLICIT GEMMs (yk_gemm_f32.h CONV = 1 / 2 / 3): no column matrix - the im2col path writes it (113 MB for the 14x20x704
+// head conv), multiplies it, and for the data gradient writes a column matrix of gradients and folds it (col2im).  Needs Cin % 4 == 0 (and
+// Cout % 4 == 0, stride 1 for the data gradient); the 3-channel stem and the strided data gradients keep the column matrix.
 // --------------------------------------------------------------------------------------------------------
 static int conv_gemm(gemm_args g, const conv_args &cv, int mode, double *stats_partial, int *chunks_out, int *rpc_out, int *cwl_out, int dev, void *stream) {
     hipStream_t st = (hipStream_t)stream;
@@ -1558,22 +1542,23 @@ static int conv_gemm(gemm_args g, const conv_args &cv, int mode, double *stats_p
     YK_HIP(hipGetLastError());
     return YK_OK;
 }
-static bool conv3x3_ok(const char *who, const void *a, const void *b, const void *c, int B, int Ci, int Co, bool need_co4) {
+// YK_ERR_ARG for a null tensor or a non-positive size, YK_ERR_UNSUPPORTED for what the kernels do not cover (channel counts, alignment)
+static int conv3x3_check(const char *who, const void *a, const void *b, const void *c, int B, int Ci, int Co, bool need_co4) {
     if (!a || !b || !c || B <= 0 || Ci <= 0 || Co <= 0) {
         yk_set_error("%s: bad argument", who);
-        return false;
+        return YK_ERR_ARG;
     }
     if (Ci % 4 || (need_co4 && Co % 4) || (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15)) {
         yk_set_error("%s: needs Cin %% 4 == 0%s and 16-byte aligned tensors (use yk_im2col3x3_f32 + yk_gemm_f32 otherwise)", who, need_co4 ? ", Cout % 4 == 0" : "");
-        return false;
+        return YK_ERR_UNSUPPORTED;
     }
-    return true;
+    return YK_OK;
 }
 // z = conv3x3(x, w) [+ BatchNormalization(training) + activation (+ residual) -> y when gamma is given, as yk_gemm_bn_fwd_f32]; w: [Co][9 * Ci]
 extern "C" int yk_conv3x3_bn_fwd_f32(const float *x, const float *w, int B, int Hi, int Wi, int Ci, int Ho, int Wo, int stride, int pad_t, int pad_l, int Co,
                                      float *z, const float *gamma, const float *beta, float eps, int act, float alpha, float *y, float *save_mean,
                                      float *save_invstd, float *moving_mean, float *moving_var, float momentum, const float *res, void *stream) {
-    if (!conv3x3_ok("yk_conv3x3_bn_fwd_f32", x, w, z, B, Ci, Co, false)) return (Ci % 4) ? YK_ERR_UNSUPPORTED : YK_ERR_ARG;
+    if (const int rc = conv3x3_check("yk_conv3x3_bn_fwd_f32", x, w, z, B, Ci, Co, false)) return rc;
     if (gamma && (!beta || !y || !save_mean || !save_invstd)) {
         yk_set_error("yk_conv3x3_bn_fwd_f32: bad BatchNormalization argument");
         return YK_ERR_ARG;
@@ -1604,7 +1589,7 @@ extern "C" int yk_conv3x3_bn_fwd_f32(const float *x, const float *w, int B, int 
 // dw [Co][9 * Ci] = dz^T * col(x)      (tf Conv2DBackpropFilter)
 extern "C" int yk_conv3x3_bwd_weight_f32(const float *x, const float *dz, int B, int Hi, int Wi, int Ci, int Ho, int Wo, int stride, int pad_t, int pad_l,
                                          int Co, float *dw, void *stream) {
-    if (!conv3x3_ok("yk_conv3x3_bwd_weight_f32", x, dz, dw, B, Ci, Co, true)) return (Ci % 4 || Co % 4) ? YK_ERR_UNSUPPORTED : YK_ERR_ARG;
+    if (const int rc = conv3x3_check("yk_conv3x3_bwd_weight_f32", x, dz, dw, B, Ci, Co, true)) return rc;
     int dev = yk_current_device();
     if (dev < 0) return YK_ERR_NO_DEVICE;
     gemm_args g;
@@ -1616,7 +1601,7 @@ extern "C" int yk_conv3x3_bwd_weight_f32(const float *x, const float *dz, int B,
 // dx = the transposed convolution of dz (stride 1)      (tf Conv2DBackpropInput)
 extern "C" int yk_conv3x3_bwd_data_f32(const float *dz, const float *w, int B, int Hi, int Wi, int Ci, int Ho, int Wo, int stride, int pad_t, int pad_l, int Co,
                                        float *dx, void *stream) {
-    if (!conv3x3_ok("yk_conv3x3_bwd_data_f32", dz, w, dx, B, Ci, Co, true)) return (Ci % 4 || Co % 4) ? YK_ERR_UNSUPPORTED : YK_ERR_ARG;
+    if (const int rc = conv3x3_check("yk_conv3x3_bwd_data_f32", dz, w, dx, B, Ci, Co, true)) return rc;
     if (stride != 1) {
         yk_set_error("yk_conv3x3_bwd_data_f32: stride %d (only stride 1; use yk_gemm_f32 + yk_col2im3x3_f32)", stride);
         return YK_ERR_UNSUPPORTED;

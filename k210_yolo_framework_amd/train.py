@@ -32,6 +32,20 @@ def _is_darknet_conv(name: str) -> bool:
     return name.startswith('head_conv') or name.startswith('conv2d_')
 
 
+def conv_route(op: dict, layer: ns.Layer) -> str:
+    """How the training step computes a Conv2D op of the NetSpec; forward and backward take the same route:
+      'gemm'      1x1 stride 1: GEMMs on the activations themselves;
+      'implicit'  3x3 as implicit GEMMs, no column matrix (yk_conv3x3_*; a strided data gradient still goes through a column matrix
+                  folded by yk_col2im3x3_f32).  Needs Cin % 4 == 0 and Cout % 4 == 0, and BatchNorm: the step calls the forward kernel
+                  fused with it;
+      'im2col'    3x3 through a column matrix (yk_im2col3x3_f32 + GEMM; yk_col2im3x3_f32): every other 3x3 conv - in the networks
+                  netspec builds, only the 3-channel stem."""
+    if op['k'] == 1 and op['stride'] == 1:
+        return 'gemm'
+    assert op['k'] == 3, op
+    return 'implicit' if op['cin'] % 4 == 0 and op['cout'] % 4 == 0 and layer.bn_name else 'im2col'
+
+
 class Trainer:
     def __init__(self, spec: ns.NetSpec, weights: Dict[str, np.ndarray], anchors: np.ndarray, per_rank_batch: int,
                  obj_thresh: float = 0.7, iou_thresh: float = 0.5, obj_weight: float = 1.0, noobj_weight: float = 1.0,
@@ -80,21 +94,6 @@ class Trainer:
         # captured as a HIP graph and replayed (same kernels, same order, same buffers -> bitwise the same results; measured 7.8 ->
         # 6.7 ms per step for yolo_mobilev2-1.0 at 16 images).  Adam stays outside: its step counter is a launch argument.
         self.use_graph = bool(use_graph)
-        # weight gradients (and the regulariser's dot products) depend on nothing the backward chain waits for: they can run on a second
-        # stream - inside a captured step a parallel branch of the graph - joined before the exchange / update (~170 of the step's ~700 launches
-        # off the critical path).  A cross-stream edge inside a replayed hipGraph is expensive on this runtime: one fork per layer (~120 edges)
-        # measured 5.59 -> 10.37 ms per step (gpurun_out/r5c3), so the deferred launches are flushed to the side stream in
-        # YK_TRAIN_WSTREAM = N chunks (N forks + one join; 0 = everything on one stream, round 4's form).
-        import os as _os
-        self.wgrad_chunks = max(0, int(_os.environ.get('YK_TRAIN_WSTREAM', '0') or 0))
-        self.wgrad_stream = self.wgrad_chunks > 0
-        # ... what does pay (round 6): the 1x1 convs' weight gradients are independent GEMMs of 1-30 tiles each; collected during the backward
-        # walk and issued as ONE grouped launch at its end (yk_gemm_f32_grouped: bitwise the same results), their tiles fill the chip
-        # together - 35 GEMMs + 35 slice-adding launches become 2, the depthwise weight gradients (17 + 17) 2 more.  YK_TRAIN_GROUP_WGRAD=0: one launch
-        # per layer as before.
-        self.group_wgrad = (_os.environ.get('YK_TRAIN_GROUP_WGRAD', '1') or '1') != '0' and not self.wgrad_stream
-        self.implicit3x3 = (_os.environ.get('YK_TRAIN_IMPLICIT3X3', '1') or '1') != '0'     # 3x3 convs as implicit GEMMs (0: im2col + GEMM + col2im, rounds 2-5)
-        self._ws = None
         self._l2_seg = None
         self._fa = None
         self._graph = None
@@ -225,18 +224,11 @@ class Trainer:
                 l = self.lay[op['layer']]
                 w = self.view(self.P, l.name + '/kernel')
                 z = self._new(self.B, ho, wo, co)
-                a = kk = None
-                implicit = False                                   # 3x3 conv as an implicit GEMM: no column matrix (needs Cin % 4 == 0: not the 3-channel stem)
-                if t == ns.OP_CONV:
-                    ci, k = op['cin'], op['k']
-                    if k == 1 and op['stride'] == 1:
-                        a, kk = x, ci
-                    else:
-                        assert k == 3
-                        implicit = self.implicit3x3 and ci % 4 == 0 and bool(l.bn_name)
-                        if not implicit:
-                            a, kk = self._new(M, 9 * ci), 9 * ci
-                            self._ck(self.L.yk_im2col3x3_f32(engine._ptr(x), *self._geom(op), engine._ptr(a), self._s()), 'yk_im2col3x3_f32')
+                route = conv_route(op, l) if t == ns.OP_CONV else None
+                a, kk = x, op['cin']                                 # the GEMM's operand: a 1x1 conv's input, or the column matrix below
+                if route == 'im2col':
+                    a, kk = self._new(M, 9 * op['cin']), 9 * op['cin']
+                    self._ck(self.L.yk_im2col3x3_f32(engine._ptr(x), *self._geom(op), engine._ptr(a), self._s()), 'yk_im2col3x3_f32')
                 if l.bn_name:
                     # convolution + batch statistics + apply in one library call: the producer of z leaves the partial sums of the
                     # statistics (yk_gemm_bn_fwd_f32 / yk_dw3x3_bn_fwd_f32), z is not read a second time for them
@@ -250,7 +242,7 @@ class Trainer:
                           engine._ptr(self.moving[l.bn_name + '/moving_mean']), engine._ptr(self.moving[l.bn_name + '/moving_variance']),
                           C.c_float(BN_MOMENTUM_V2 if self.spec.name == 'yolo_mobilev2' and not _is_darknet_conv(l.name) else BN_MOMENTUM),
                           engine._ptr(res) if res is not None else None, self._s())
-                    if implicit:
+                    if route == 'implicit':
                         self._ck(self.L.yk_conv3x3_bn_fwd_f32(engine._ptr(x), engine._ptr(w), *self._geom(op), C.c_int(co), *bn), 'yk_conv3x3_bn_fwd_f32')
                     elif t == ns.OP_CONV:
                         self._ck(self.L.yk_gemm_bn_fwd_f32(C.c_int(M), C.c_int(co), C.c_int(kk), engine._ptr(a), C.c_int(kk), engine._ptr(w),
@@ -295,49 +287,17 @@ class Trainer:
         return [T[o].view(self.B, *self.spec.tensors[o][:2], self.spec.anchor_num, e) for o in self.spec.outputs]
 
     # ------------------------------------------------------------------ backward
-    def _wstream(self):
-        """The weight-gradient stream (created once; its split-K / reduction scratch is keyed by the stream, so it never collides with the
-        main chain's)."""
-        if self._ws is None:
-            self._ws = self.torch.cuda.Stream(device=self.dev)
-        return self._ws
-
     def backward(self, out_grads: Sequence["torch.Tensor"]) -> None:
         """out_grads[i] = dL/d(output i).  Fills self.G (kernel/bias/gamma/beta gradients; regulariser added by step())."""
-        torch = self.torch
         self.G.zero_()
         D: Dict[int, "torch.Tensor"] = {}
-        main = torch.cuda.current_stream()
-        ws = self._wstream() if self.wgrad_stream else None
-        keep = []                                                   # operands the side stream reads: alive until the join below
-        if ws is not None:
-            ws.wait_stream(main)                                    # G is zero, the forward tape is complete
-
-        grouped = []                                                # (dz, x, gw, co, ci, M) of the 1x1 convs: one grouped launch at the end
-        grouped_dw = []                                             # (x, dz, gw, geometry) of the depthwise convs: likewise
-        pending = []                                                # deferred weight-gradient launches of the current chunk
-        n_conv = sum(1 for o in self.spec.ops if o['type'] in (ns.OP_CONV, ns.OP_DWCONV))
-        per_chunk = max(1, -(-n_conv // max(1, self.wgrad_chunks)))
-        seen = [0]
-
-        def flush():
-            """Issue the chunk's deferred launches on the side stream, behind everything the main stream has been given so far."""
-            if ws is None or not pending:
-                return
-            ev = torch.cuda.Event()
-            ev.record(main)
-            ws.wait_event(ev)
-            with torch.cuda.stream(ws):
-                for fn in pending:
-                    fn()
-            pending.clear()
-
-        def on_side(fn, *tensors):
-            """fn() only WRITES weight gradients: run it now (no side stream) or defer it to the chunk's flush."""
-            if ws is None:
-                return fn()
-            pending.append(fn)
-            keep.extend(tensors)
+        # The weight gradients of the 1x1 and depthwise convs depend on nothing the backward chain waits for: they are collected during
+        # the walk and issued as grouped launches at its end, whose tiles fill the chip together (35 GEMMs + 35 slice-adding launches
+        # become 2, the 17 + 17 depthwise launches 2 more).  yk_gemm_f32_grouped sizes its K slices for the group: equal to per-layer
+        # yk_gemm_f32 calls within fp32 summation order, and reproducible from run to run.  yk_dw3x3_bwd_weight_grouped_f32 computes
+        # every problem as yk_dw3x3_bwd_weight_f32 does.
+        grouped = []                                                # (dz, x, gw, co, ci, M) of the 1x1 convs
+        grouped_dw = []                                             # (x, dz, gw, geometry) of the depthwise convs
 
         def acc(tid, g, own):
             if tid == 0:
@@ -360,9 +320,6 @@ class Trainer:
             hi, wi, ci = self.spec.tensors[op['in0']]
             M = self.B * ho * wo
             if t in (ns.OP_CONV, ns.OP_DWCONV):
-                seen[0] += 1
-                if seen[0] % per_chunk == 0:
-                    flush()
                 l = self.lay[op['layer']]
                 w = self.view(self.P, l.name + '/kernel')
                 gw = self.view(self.G, l.name + '/kernel')
@@ -378,17 +335,13 @@ class Trainer:
                 else:
                     dz = dy
                     if l.use_bias:
-                        gb = self.view(self.G, l.name + '/bias')
-                        on_side(lambda dz=dz, gb=gb, M=M, co=co: self._ck(self.L.yk_colsum_f32(engine._ptr(dz), C.c_longlong(M), C.c_int(co), engine._ptr(gb),
-                                                                                                self._s()), 'yk_colsum_f32'), dz)
+                        self._ck(self.L.yk_colsum_f32(engine._ptr(dz), C.c_longlong(M), C.c_int(co), engine._ptr(self.view(self.G, l.name + '/bias')),
+                                                      self._s()), 'yk_colsum_f32')
                 need_dx = op['in0'] != 0
                 if t == ns.OP_CONV:
-                    k = op['k']
-                    if k == 1 and op['stride'] == 1:
-                        if self.group_wgrad:
-                            grouped.append((dz, x, gw, co, ci, M))                       # dW = dZ^T * X, with all the others below
-                        else:
-                            on_side(lambda dz=dz, x=x, gw=gw, co=co, ci=ci, M=M: self.gemm(1, 0, co, ci, M, dz, co, x, ci, gw, ci), dz)     # dW = dZ^T * X
+                    route = conv_route(op, l)
+                    if route == 'gemm':
+                        grouped.append((dz, x, gw, co, ci, M))                           # dW = dZ^T * X, with all the others below
                         if need_dx:
                             if op['in0'] in D:                                          # a second reader of the input: dX += dZ * W straight into the
                                 self.gemm(0, 0, M, ci, co, dz, co, w, ci, D[op['in0']], ci, beta=1.0)   # accumulated gradient (no temporary, no axpy)
@@ -396,10 +349,10 @@ class Trainer:
                                 dx = self._new(self.B, hi, wi, ci)
                                 self.gemm(0, 0, M, ci, co, dz, co, w, ci, dx, ci)       # dX = dZ * W
                                 acc(op['in0'], dx, True)
-                    elif self.implicit3x3 and ci % 4 == 0 and co % 4 == 0:
+                    elif route == 'implicit':
                         geom = self._geom(op)
-                        on_side(lambda x=x, dz=dz, gw=gw, geom=geom, co=co: self._ck(self.L.yk_conv3x3_bwd_weight_f32(
-                            engine._ptr(x), engine._ptr(dz), *geom, C.c_int(co), engine._ptr(gw), self._s()), 'yk_conv3x3_bwd_weight_f32'), dz)
+                        self._ck(self.L.yk_conv3x3_bwd_weight_f32(engine._ptr(x), engine._ptr(dz), *geom, C.c_int(co), engine._ptr(gw), self._s()),
+                                 'yk_conv3x3_bwd_weight_f32')
                         if need_dx:
                             dx = self._new(self.B, hi, wi, ci)
                             if op['stride'] == 1:
@@ -416,7 +369,7 @@ class Trainer:
                         kk = 9 * ci
                         col = self._new(M, kk)
                         self._ck(self.L.yk_im2col3x3_f32(engine._ptr(x), *self._geom(op), engine._ptr(col), self._s()), 'yk_im2col3x3_f32')
-                        self.gemm(1, 0, co, kk, M, dz, co, col, kk, gw, kk)            # (main stream: `col` is overwritten right below)
+                        self.gemm(1, 0, co, kk, M, dz, co, col, kk, gw, kk)
                         if need_dx:
                             self.gemm(0, 0, M, kk, co, dz, co, w, kk, col, kk)          # dcol (reuses the buffer)
                             dx = self._new(self.B, hi, wi, ci)
@@ -425,12 +378,7 @@ class Trainer:
                             acc(op['in0'], dx, True)
                         del col
                 else:
-                    geom = self._geom(op)
-                    if self.group_wgrad:
-                        grouped_dw.append((x, dz, gw, [g.value for g in geom]))
-                    else:
-                        on_side(lambda x=x, dz=dz, gw=gw, geom=geom: self._ck(self.L.yk_dw3x3_bwd_weight_f32(engine._ptr(x), engine._ptr(dz), *geom, engine._ptr(gw),
-                                                                                                              self._s()), 'yk_dw3x3_bwd_weight_f32'), dz)
+                    grouped_dw.append((x, dz, gw, [g.value for g in self._geom(op)]))
                     if need_dx:
                         dx = self._new(self.B, hi, wi, ci)
                         self._ck(self.L.yk_dw3x3_bwd_data_f32(engine._ptr(dz), engine._ptr(w), *self._geom(op), engine._ptr(dx), self._s()),
@@ -463,8 +411,8 @@ class Trainer:
                 others = [j for j, q in enumerate(self.spec.ops) if j != i and (q.get('in0') == second or q.get('in1') == second)]
                 lone = not [j for j, q in enumerate(self.spec.ops) if j != i and (q.get('in0') == first or q.get('in1') == first)] and first not in self.spec.outputs
                 # ... and `first`'s producer must be a conv WITH BatchNorm: its backward only READS dy and writes a fresh dz.  Another Add would store
-                # dy again by reference, a conv without BN hands dy on as dz (and, with a weight-gradient stream, reads it later) - then a later
-                # accumulation into D[second] would corrupt a buffer somebody else still holds: clone.
+                # dy again by reference; a conv without BN hands dy on as its dz, and a 1x1 conv's dz is read again by the grouped weight-gradient
+                # launch at the end of backward() - then a later accumulation into D[second] would corrupt a buffer somebody else still holds: clone.
                 pq = self.spec.ops[pf] if pf >= 0 else None
                 fresh = pq is not None and pq['type'] in (ns.OP_CONV, ns.OP_DWCONV) and bool(self.lay[pq['layer']].bn_name)
                 share = a_ != b_ and lone and fresh and first not in D and second not in D and all(j < pf for j in others) and second != 0
@@ -484,15 +432,10 @@ class Trainer:
             geo = (C.c_int * (9 * n))(*[v for g in grouped_dw for v in g[3]])
             self._ck(self.L.yk_dw3x3_bwd_weight_grouped_f32(C.c_int(n), pa([g[0] for g in grouped_dw]), pa([g[1] for g in grouped_dw]), geo,
                                                             pa([g[2] for g in grouped_dw]), self._s()), 'yk_dw3x3_bwd_weight_grouped_f32')
-        del grouped, grouped_dw
-        flush()
-        if ws is not None:
-            main.wait_stream(ws)                                    # every weight gradient is in G
-        del keep
 
     # ------------------------------------------------------------------ one optimisation step
-    def regulariser(self, add_grad: bool, value: bool = True) -> "torch.Tensor":
-        """sum over DarknetConv2D kernels of 5e-4 * sum(w^2) (device scalar; value=False skips it); optionally G += 2*5e-4*W.
+    def regulariser(self, add_grad: bool) -> "torch.Tensor":
+        """sum over DarknetConv2D kernels of 5e-4 * sum(w^2) (device scalar); optionally G += 2*5e-4*W.
         One pass over all of those kernels (yk_l2_segments_f32: they are segments of the flat parameter buffer) - two launches instead of
         a dot product and an axpy per layer."""
         torch = self.torch
@@ -503,24 +446,16 @@ class Trainer:
             self._l2_seg = (torch.from_numpy(pre).to(self.dev), torch.from_numpy(np.asarray([o for o, _ in segs], np.int64)).to(self.dev), len(segs),
                             int(pre[-1]))
         pre, off, nseg, total = self._l2_seg
-        tot = torch.zeros(1, dtype=torch.float32, device=self.dev) if value else None
-        if nseg and (value or add_grad):
+        tot = torch.zeros(1, dtype=torch.float32, device=self.dev)
+        if nseg:
             self._ck(self.L.yk_l2_segments_f32(engine._ptr(self.P), engine._ptr(self.G), engine._ptr(pre), engine._ptr(off), C.c_int(nseg),
-                                               C.c_longlong(total), C.c_float(L2_WEIGHT), C.c_int(1 if value else 0), C.c_int(1 if add_grad else 0),
-                                               engine._ptr(tot) if value else None, self._s()), 'yk_l2_segments_f32')
+                                               C.c_longlong(total), C.c_float(L2_WEIGHT), C.c_int(1), C.c_int(1 if add_grad else 0),
+                                               engine._ptr(tot), self._s()), 'yk_l2_segments_f32')
         return tot
 
     def loss_and_grads(self, x_nhwc, y_true: Sequence["torch.Tensor"]):
         """forward + loss + backward (no all-reduce, no update).  -> dict of device scalars."""
-        torch = self.torch
         global_batch = self.B * self.world
-        reg = None
-        if self.wgrad_stream:
-            # the regulariser's value reads the weights only: its ~35 small launches run beside the forward pass (joined by backward())
-            main, ws = torch.cuda.current_stream(), self._wstream()
-            ws.wait_stream(main)
-            with torch.cuda.stream(ws):
-                reg = self.regulariser(add_grad=False)
         preds = self.forward(x_nhwc)
         parts, grads = [], []
         for li, (yp, yt) in enumerate(zip(preds, y_true)):
@@ -529,11 +464,7 @@ class Trainer:
             parts.append(loss6)
             grads.append(g)
         self.backward(grads)
-        if reg is None:
-            reg = self.regulariser(add_grad=self.world == 1)
-        elif self.world == 1:
-            self.regulariser(add_grad=True, value=False)
-        return dict(layers=parts, reg=reg)
+        return dict(layers=parts, reg=self.regulariser(add_grad=self.world == 1))
 
     def invalidate_graph(self) -> None:
         """Forget the captured step (the next two steps run eagerly / re-capture).  Called automatically when something a capture

@@ -12,6 +12,7 @@ import torch.nn.functional as F
 from k210_yolo_framework_amd import netspec as ns
 from k210_yolo_framework_amd.helper import Helper, VOC_ANCHORS
 from oracle import train_ref
+from tests.mini_net import residual_zoo_spec
 
 pytestmark = pytest.mark.gpu
 
@@ -191,8 +192,11 @@ def test_conv3x3_implicit_gemm_forward_and_gradients(stride, pad, B, Hi, Wi, Ci,
     for u, v in zip(a[2:], b[2:]):
         _close(v, u, 1e-6)
     assert np.abs(a[1] - b[1]).max() <= 1e-5 * np.abs(a[1]).max()
-    # a 3-channel input is refused (the im2col path covers it)
-    assert L.yk_conv3x3_bn_fwd_f32(engine._ptr(xd), engine._ptr(wd), B, Hi, Wi, 3, Ho, Wo, stride, pt, pl, Co, engine._ptr(z), *nobn, _st()) != 0
+    # a 3-channel input and a tensor off the 16-byte grid are refused as unsupported (the im2col path covers them); host checks, no launch
+    YK_ERR_UNSUPPORTED = -12                                                  # include/yolo_hip.h
+    assert L.yk_conv3x3_bn_fwd_f32(engine._ptr(xd), engine._ptr(wd), B, Hi, Wi, 3, Ho, Wo, stride, pt, pl, Co, engine._ptr(z), *nobn,
+                                   _st()) == YK_ERR_UNSUPPORTED
+    assert L.yk_conv3x3_bn_fwd_f32(C.c_void_p(xd.data_ptr() + 4), engine._ptr(wd), *geom, Co, engine._ptr(z), *nobn, _st()) == YK_ERR_UNSUPPORTED
 
 
 @pytest.mark.parametrize('stride', [1, 2])
@@ -487,35 +491,12 @@ def test_training_step_loss_and_all_gradients_vs_autograd(name, hw, B, alpha):
     assert compared >= 1, 'no flip-free seed found'
 
 
-def _residual_zoo_spec():
-    """Residual wiring the reference networks do NOT use (NetSpec is a general builder): Add(conv_out, shortcut) with the operands swapped,
-    an Add whose input is another Add's output, a shortcut read by three consumers, and a linear (no-BN) conv feeding an Add."""
-    s = ns.NetSpec('zoo', (32, 48), anchor_num=3, class_num=20)
-    x = s._new_tensor(32, 48, 3)
-    x = s.conv(x, 16, 3, 2, ns.K210_S2_PAD, act=ns.LEAKY03, name='conv1')
-    a = s.conv(x, 16, 1, act=ns.RELU6, name='conv_a')
-    r1 = s.add(a, x)                                       # operands swapped: (conv output, shortcut)
-    b = s.conv(r1, 16, 1, act=ns.LEAKY03, name='conv_b')
-    r2 = s.add(r1, b)                                      # the usual order
-    r3 = s.add(r2, r1)                                     # nested: r2 is itself an Add; r1 now has three readers
-    c = s.conv(r3, 16, 1, bn=False, bias=True, name='conv_c')   # no BatchNorm: its backward hands dy on as dz
-    r4 = s.add(r3, c)
-    x1 = s.conv(r4, 16, 1, act=ns.LEAKY03, name='conv_pw_1')
-    t = s.dwconv(x1, 2, ns.K210_S2_PAD, act=ns.RELU, name='conv_dw_2')
-    x2 = s.conv(t, 32, 1, act=ns.LEAKY03, name='conv_pw_2')
-    ns._head(s, x1, x2, 24, 16, 8, 75, [0])
-    return s
-
-
-@pytest.mark.parametrize('wstream', [0, 2])
-def test_nested_and_swapped_adds_gradients_vs_autograd(wstream, monkeypatch):
+def test_nested_and_swapped_adds_gradients_vs_autograd():
     """the Add backward may share dy between its two inputs only when the later producer is a BatchNorm conv (a fresh dz); and a
-    folded Add must work whichever operand is the conv's output.  Gradients of every parameter against float64 autograd, with and without
-    the weight-gradient side stream."""
+    folded Add must work whichever operand is the conv's output.  Gradients of every parameter against float64 autograd."""
     from k210_yolo_framework_amd.train import Trainer
-    monkeypatch.setenv('YK_TRAIN_WSTREAM', str(wstream))
     hyper = dict(obj_thresh=0.7, iou_thresh=0.5, obj_weight=1.0, noobj_weight=1.0, wh_weight=1.0)
-    spec = _residual_zoo_spec()
+    spec = residual_zoo_spec()
     h = Helper(None, 20, VOC_ANCHORS, [[32, 48]], [list(v) for v in spec.out_hw()])
     compared = 0
     for seed in range(3, 15):
