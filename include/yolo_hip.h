@@ -177,6 +177,10 @@ int yk_plan_debug_set_error(yk_plan_t *plan, unsigned value); /* test hook: what
 /* Debug/parity access to any intermediate activation (fp16, channel pitch padded
  * to a multiple of 8): copies tensor `tid` of the last run to host as fp32 NHWC. */
 int yk_debug_read_tensor(yk_plan_t *p, int tid, int batch, float *h_dst, size_t dst_elems);
+/* The per-image storage exponents of tensor `tid` in an f16x2 plan after the last run: the stored halves hold x * 2^-h_e[b] = hi + lo
+ * (fp32-plane tensors: 0).  YK_ERR_UNSUPPORTED for an f16 plan and for a tensor that is not stored split (a view, folded or fused
+ * away, an fp32 network output).  Debug / parity access only: synchronises the device. */
+int yk_debug_read_exponents(yk_plan_t *p, int tid, int batch, int32_t *h_e);
 /* Number of kernel launches one yk_run_* issues (after fusion). */
 int yk_plan_launch_count(const yk_plan_t *p);
 /* Name/shape of the i-th launch for bench/roofline bookkeeping. */

@@ -150,6 +150,7 @@ void yk_xplan_destroy(yk_xplan *p);
 int yk_xplan_run(yk_xplan *p, const void *d_in, int in_f32, int batch, hipStream_t st, hipEvent_t *ev);
 int yk_xplan_output(yk_xplan *p, int idx, float **d_ptr, size_t *bytes, int *h, int *w, int *c);
 int yk_xplan_read_tensor(yk_xplan *p, int tid, int batch, float *h_dst, size_t dst_elems);
+int yk_xplan_read_exponents(yk_xplan *p, int tid, int batch, int32_t *h_e);
 int yk_xplan_launch_count(const yk_xplan *p);
 int yk_xplan_check(yk_xplan *p);
 unsigned yk_xplan_peek_error(yk_xplan *p, int clear);

@@ -723,6 +723,19 @@ extern "C" int yk_debug_read_tensor(yk_plan_t *p, int tid, int batch, float *h_d
     return YK_OK;
 }
 
+extern "C" int yk_debug_read_exponents(yk_plan_t *p, int tid, int batch, int32_t *h_e) {
+    if (!p || tid <= 0 || tid >= (int)p->T.size() || batch <= 0 || batch > p->max_batch || !h_e) {
+        yk_set_error("yk_debug_read_exponents: bad argument");
+        return YK_ERR_ARG;
+    }
+    if (!p->x) {
+        yk_set_error("yk_debug_read_exponents: an f16 plan stores no exponents");
+        return YK_ERR_UNSUPPORTED;
+    }
+    YK_HIP(hipSetDevice(p->device));
+    return yk_xplan_read_exponents(p->x, tid, batch, h_e);
+}
+
 // dev instrumentation: arm phase timestamps for launch `li`, run once (u8 path), copy out [n_wg][8] ticks (100 MHz)
 extern "C" int yk_debug_phase_stamps(yk_plan_t *p, int li, const uint8_t *d_frames, int batch, void *stream,
                                      long long *h_out, int max_wg) {

@@ -2433,6 +2433,18 @@ int yk_xplan_read_tensor(yk_xplan *p, int tid, int batch, float *h_dst, size_t d
     return YK_OK;
 }
 
+// the storage exponents of a stored tensor (split halves: x * 2^-e = hi + lo; fp32 planes: 0), one per image of the last run
+int yk_xplan_read_exponents(yk_xplan *p, int tid, int batch, int32_t *h_e) {
+    if (tid <= 0 || tid >= (int)p->T.size()) return YK_ERR_ARG;
+    if (!p->T[tid].d) {
+        yk_set_error("yk_debug_read_exponents: tensor %d has no stored exponent (a view, folded away, or an fp32 network output)", tid);
+        return YK_ERR_UNSUPPORTED;
+    }
+    YK_HIP(hipDeviceSynchronize());
+    YK_HIP(hipMemcpy(h_e, p->d_eexp + (size_t)tid * p->max_batch, sizeof(int32_t) * batch, hipMemcpyDeviceToHost));
+    return YK_OK;
+}
+
 // dev instrumentation: arm phase timestamps for launch `li` (a fused block), run once, copy out [n_wg][16] ticks (100 MHz)
 int yk_xplan_phase_stamps(yk_xplan *p, int li, const void *d_in, int batch, hipStream_t st, long long *h_out, int max_wg) {
     if (li < 0 || li >= (int)p->L.size() || (p->L[li].kind != XK_BLOCK && p->L[li].kind != XK_PERSIST && p->L[li].kind != XK_HEADS)) return YK_ERR_ARG;

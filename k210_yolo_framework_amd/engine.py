@@ -69,7 +69,7 @@ def lib() -> C.CDLL:
         L = C.CDLL(str(LIB_PATH))
         L.yk_last_error.restype = C.c_char_p
         L.yk_device_count.restype = C.c_int
-        for fn in ('yk_plan_create', 'yk_plan_create_ex', 'yk_run_u8', 'yk_run_f32', 'yk_get_output', 'yk_debug_read_tensor',
+        for fn in ('yk_plan_create', 'yk_plan_create_ex', 'yk_run_u8', 'yk_run_f32', 'yk_get_output', 'yk_debug_read_tensor', 'yk_debug_read_exponents',
                    'yk_plan_launch_count', 'yk_plan_launch_info', 'yk_plan_check', 'yk_plan_peek_error', 'yk_plan_debug_set_error', 'yk_plan_profile', 'yk_decode_py', 'yk_decode_py_ex', 'yk_decode_py_packed',
                    'yk_graph_begin', 'yk_graph_end', 'yk_graph_launch', 'yk_graph_node_count', 'yk_graph_kernel_node_count', 'yk_memcpy_async', 'yk_host_device_ptr', 'yk_stream_create', 'yk_stream_destroy', 'yk_stream_query_priority', 'yk_normalise_u8', 'yk_region_batched', 'yk_yolo_loss', 'yk_letterbox_u8', 'yk_letterbox_augment_u8',
                    'region_layer_init', 'yk_gemm_f32', 'yk_gemm_f32_grouped', 'yk_im2col3x3_f32', 'yk_col2im3x3_f32', 'yk_conv3x3_bn_fwd_f32', 'yk_conv3x3_bwd_weight_f32', 'yk_conv3x3_bwd_data_f32', 'yk_dw3x3_fwd_f32',
@@ -226,6 +226,13 @@ class Plan:
         _check(lib().yk_debug_read_tensor(self._h, C.c_int(tid), C.c_int(batch), out.ctypes.data_as(f32p),
                                           C.c_size_t(out.size)), 'yk_debug_read_tensor')
         return out
+
+    def read_exponents(self, tid: int, batch: int) -> np.ndarray:
+        """int32 [batch]: the per-image storage exponents of an f16x2 plan's stored tensor `tid` (the halves hold x * 2^-e = hi + lo; fp32
+        planes: 0).  Raises for an f16 plan and for a tensor that is not stored split (yk_debug_read_exponents)."""
+        e = np.empty((batch,), np.int32)
+        _check(lib().yk_debug_read_exponents(self._h, C.c_int(tid), C.c_int(batch), e.ctypes.data_as(i32p)), 'yk_debug_read_exponents')
+        return e
 
     def profile(self, frames, iters: int = 10, stream=None) -> np.ndarray:
         """Average per-launch duration (ms) measured with HIP events on the launch stream."""

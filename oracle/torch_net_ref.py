@@ -13,13 +13,14 @@ import torch.nn.functional as F
 from k210_yolo_framework_amd import netspec as ns
 
 
-def forward(spec: ns.NetSpec, weights, x_nhwc: np.ndarray, want=None, dtype=torch.float64, store_hook=None):
-    """-> dict tensor_id -> NHWC fp32 numpy for ids in `want` (default: spec.outputs).
+def forward(spec: ns.NetSpec, weights, x_nhwc: np.ndarray, want=None, dtype=torch.float64, store_hook=None, keep_dtype=False):
+    """-> dict tensor_id -> NHWC fp32 numpy for ids in `want` (default: spec.outputs); keep_dtype: in `dtype` instead, from an input taken
+    in `dtype` (a float64 arbiter for oracle/x2_bound.py).
     store_hook(tensor_id, y_nchw) -> y_nchw: applied to every op's result before it is stored - a storage-format model (e.g. rounding to
     p significant bits) for pricing inter-layer formats (tools/r05_format_pricing.py); None = exact."""
     want = list(spec.outputs if want is None else want)
     lay = {l.name: l for l in spec.layers}
-    T = {0: torch.from_numpy(np.ascontiguousarray(x_nhwc, np.float32)).permute(0, 3, 1, 2).to(dtype)}
+    T = {0: torch.from_numpy(np.ascontiguousarray(x_nhwc, np.float64 if keep_dtype else np.float32)).permute(0, 3, 1, 2).to(dtype)}
     with torch.no_grad():
         for op in spec.ops:
             x = T[op['in0']]
@@ -69,6 +70,8 @@ def forward(spec: ns.NetSpec, weights, x_nhwc: np.ndarray, want=None, dtype=torc
             if store_hook is not None:
                 y = store_hook(op['out'], y)
             T[op['out']] = y
+    if keep_dtype:
+        return {i: T[i].permute(0, 2, 3, 1).contiguous().numpy() for i in want}
     return {i: T[i].permute(0, 2, 3, 1).float().numpy() for i in want}
 
 

@@ -1,4 +1,5 @@
-"""GPU parity, one launch at a time: every materialised tensor of a plan is recomputed by the CPU oracle FROM THE
+"""GPU parity of the opt-in `precision='f16'` mode ONLY (the f16x2 default and its `x:` kernels: tests/test_gpu_layers_x2.py),
+one launch at a time: every materialised tensor of a plan is recomputed by the CPU oracle FROM THE
 GPU'S OWN INPUT TENSORS of that launch (read back bit-exactly), so the comparison isolates each kernel from the
 accumulated fp16 drift of the layers before it.  What is left is fp32 accumulation order, i.e. at most a 1-ulp
 fp16 flip on a small fraction of elements:
