@@ -6,6 +6,7 @@
 #   make bench       images/sec, yolo_mobilev1-0.75, 32 frames per step (GPUS=N runs one rank per GPU through torchrun)
 #   make inference   MODEL=... DEPTHMUL=... CKPT=weights.h5|.npz IMG=picture.jpg
 #   make train       MODEL=... DEPTHMUL=... BATCH=16 MAXEP=10 [SYNTHETIC=256]
+#                    [PRUNE=True INITSPARSITY=0.5 FINALSPARSITY=0.9 END_EPOCH=5 FREQUENCY=100]: magnitude pruning, saves yolo_prune_model.h5
 #   make anchors     DATASET=voc ANCNUM=3 [LOW='0.0 0.0' HIGH='1.0 1.0']   (reference Makefile:78-87: k-means anchors from data/<set>_img_ann.npy)
 
 PY            ?= python3
@@ -30,6 +31,10 @@ WHWEIGHT      ?= 1
 SPLITFACTOR   ?= 0.05
 IAA           ?= False
 PRUNE         ?= False
+INITSPARSITY  ?= 0.5
+FINALSPARSITY ?= 0.9
+END_EPOCH     ?= 5
+FREQUENCY     ?= 100
 SYNTHETIC     ?= 0
 GPUS          ?= 1
 # anchors only (reference Makefile:27-29)
@@ -42,7 +47,8 @@ NET_ARGS   = --train_set $(DATASET) --class_num $(CLSNUM) --model_def $(MODEL) -
 TRAIN_ARGS = --pre_ckpt $(CKPT) --augmenter $(IAA) --batch_size $(BATCH) --rand_seed 3 --max_nrof_epochs $(MAXEP) \
              --init_learning_rate $(ILR) --learning_rate_decay_factor $(LRDECAYFACTOR) --obj_weight $(OBJWEIGHT) \
              --noobj_weight $(NOOBJWEIGHT) --wh_weight $(WHWEIGHT) --vaildation_split $(SPLITFACTOR) --log_dir log \
-             --is_prune $(PRUNE) --synthetic $(SYNTHETIC)
+             --is_prune $(PRUNE) --prune_initial_sparsity $(INITSPARSITY) --prune_final_sparsity $(FINALSPARSITY) \
+             --prune_end_epoch $(END_EPOCH) --prune_frequency $(FREQUENCY) --synthetic $(SYNTHETIC)
 ifeq ($(GPUS),1)
 LAUNCH = $(PY)
 else

@@ -395,6 +395,19 @@ int yk_axpy_f32(long long n, float a, const float *x, float *y, void *stream);  
  * g is multiplied by grad_scale first (1/world_size after a sum all-reduce). */
 int yk_adam_f32(long long n, float *p, const float *g, float *m, float *v, float lr, float decay, long long iterations,
                 float beta1, float beta2, float eps, float grad_scale, void *stream);
+/* Magnitude pruning (tfmot prune_low_magnitude of keras_train.py:59-71) over `nseg` segments of one flat parameter buffer
+ * in one call.  Segment s = params[d_offset[s] .. + d_size[s]) (device, int64; d_size >= 1); d_keep[s] = k, clamped to [1, d_size[s]].
+ * Outputs per segment: d_threshold[s] = the exact k-th largest |w| (a radix select on the uint32 pattern of |w|: equal to a sort),
+ * mask[d_offset[s] + e] = |w| >= threshold (1 / 0; ties at the threshold are all kept; bytes outside the segments are not written),
+ * d_kept[s] = number of mask bytes set.  Workgroups own tiles of YK_PRUNE_TILE elements of one segment: d_tile_first [nseg + 1] (device,
+ * int32) = running sum of ceil(d_size / YK_PRUNE_TILE), ntiles = d_tile_first[nseg].  Integer atomics only: bitwise reproducible.
+ * The call itself does not synchronise with the host; capturable once the stream's scratch has its size (one eager call). */
+#define YK_PRUNE_TILE 4096
+int yk_prune_tile(void); /* YK_PRUNE_TILE of the loaded library: callers that build d_tile_first without this header ask here */
+int yk_prune_masks_f32(const float *params, const long long *d_offset, const long long *d_size, const long long *d_keep,
+                       const int *d_tile_first, int nseg, int ntiles, uint8_t *mask, float *d_threshold, long long *d_kept, void *stream);
+/* params[i] = mask[i] ? params[i] : +0.0f over n elements */
+int yk_mask_apply_f32(float *params, const uint8_t *mask, long long n, void *stream);
 
 /* ---- KPU-exact mode: a kmodel v3 on the K210 KPU's integer arithmetic (kpu_load_kmodel / kpu_run_kmodel / kpu_get_output of
  *      main.c:274,303,310, batched).  Outputs are bit-identical to oracle/kpu_ref.py (the restated KPU pipeline); DESIGN.md 3.7.

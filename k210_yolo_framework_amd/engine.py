@@ -75,7 +75,7 @@ def lib() -> C.CDLL:
                    'region_layer_init', 'yk_gemm_f32', 'yk_gemm_f32_grouped', 'yk_im2col3x3_f32', 'yk_col2im3x3_f32', 'yk_conv3x3_bn_fwd_f32', 'yk_conv3x3_bwd_weight_f32', 'yk_conv3x3_bwd_data_f32', 'yk_dw3x3_fwd_f32',
                    'yk_dw3x3_bwd_data_f32', 'yk_dw3x3_bwd_weight_f32', 'yk_dw3x3_bwd_weight_grouped_f32', 'yk_bn_train_fwd_f32', 'yk_bn_train_fwd_res_f32', 'yk_gemm_bn_fwd_f32', 'yk_dw3x3_bn_fwd_f32', 'yk_l2_segments_f32', 'yk_bn_train_bwd_f32',
                    'yk_bias_add_f32', 'yk_colsum_f32', 'yk_upsample2x_bwd_f32', 'yk_maxpool2_fwd_f32',
-                   'yk_maxpool2_bwd_f32', 'yk_axpy_f32', 'yk_adam_f32',
+                   'yk_maxpool2_bwd_f32', 'yk_axpy_f32', 'yk_adam_f32', 'yk_prune_masks_f32', 'yk_mask_apply_f32', 'yk_prune_tile',
                    'yk_kpu_plan_create', 'yk_kpu_run_u8', 'yk_kpu_get_output', 'yk_kpu_output_count', 'yk_kpu_debug_read',
                    'yk_kpu_launch_count', 'yk_kpu_profile'):
             getattr(L, fn).restype = C.c_int

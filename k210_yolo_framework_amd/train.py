@@ -11,6 +11,10 @@ Data-parallel: one process per GPU, each with `per_rank_batch` images.  The loss
 Helper.batch_size is in the single-process reference), gradients are SUM-all-reduced in one flat bucket, BatchNorm
 statistics stay per replica.  With world_size 1 this is exactly the reference's step.
 
+Magnitude pruning (keras_train.py:59-71, tfmot prune_low_magnitude restated in prune.py): `Trainer(prune=PruneSchedule(...))` computes the
+masks of the Conv2D kernels on the schedule's update steps and zeroes the masked weights at the start of every step (csrc/yk_prune.hip),
+outside the captured graph like Adam.  With prune=None the step issues exactly the launches it issued before.
+
 fp32 storage and fp32 MFMA throughout (TF1.14's default for this model)."""
 from __future__ import annotations
 
@@ -50,7 +54,7 @@ class Trainer:
     def __init__(self, spec: ns.NetSpec, weights: Dict[str, np.ndarray], anchors: np.ndarray, per_rank_batch: int,
                  obj_thresh: float = 0.7, iou_thresh: float = 0.5, obj_weight: float = 1.0, noobj_weight: float = 1.0,
                  wh_weight: float = 1.0, lr: float = 5e-4, decay: float = 0.0, device: int = 0, process_group=None,
-                 world_size: int = 1, use_graph: bool = True):
+                 world_size: int = 1, use_graph: bool = True, prune=None):
         import torch
         engine.require_gpu()
         self.torch = torch
@@ -100,6 +104,10 @@ class Trainer:
         self._gx = self._gy = self._gres = self._side = None
         self._eager_steps = 0
         self._captured_key = None
+        # magnitude pruning (prune.PruneSchedule; keras_train.py:59-71).  None: nothing is allocated and nothing is launched.
+        self.prune = prune
+        if prune is not None:
+            self._prune_init()
 
     # ------------------------------------------------------------------ parameters
     def view(self, buf, name):
@@ -540,9 +548,89 @@ class Trainer:
                                     C.c_float(0.9), C.c_float(0.999), C.c_float(1e-7), C.c_float(1.0), self._s()), 'yk_adam_f32')
         self.iterations += 1
 
+    # ------------------------------------------------------------------ magnitude pruning
+    def _prune_init(self) -> None:
+        """Segment tables of the prunable kernels in the flat buffer, the flat uint8 mask (1 everywhere outside them) and the outputs."""
+        from .prune import prunable_layers
+        torch = self.torch
+        self._pr_names = [n + '/kernel' for n in prunable_layers(self.spec)]
+        offs = [self.slots[n][0] for n in self._pr_names]
+        self._pr_sizes = [int(np.prod(self.slots[n][1])) for n in self._pr_names]
+        if not self._pr_names:
+            raise engine.YkError('pruning: the network has no Conv2D kernel')
+        self.prune.check(self._pr_sizes)
+        tile = int(self.L.yk_prune_tile())                                      # YK_PRUNE_TILE of the loaded library
+        first = np.concatenate([[0], np.cumsum([(n + tile - 1) // tile for n in self._pr_sizes])])
+        assert all(o >= 0 and o + n <= self.n_params for o, n in zip(offs, self._pr_sizes)) and first[-1] < 2 ** 31
+        dev = lambda a, dt: torch.from_numpy(np.asarray(a, dt)).to(self.dev)
+        self._pr_off, self._pr_size, self._pr_first = dev(offs, np.int64), dev(self._pr_sizes, np.int64), dev(first, np.int32)
+        self._pr_ntiles = int(first[-1])
+        self._pr_keep = dev(self._pr_sizes, np.int64)
+        self._pr_keep_host = torch.zeros(len(offs), dtype=torch.int64).pin_memory()      # staging of the counts: the copy does not block the host
+        self._pr_keep_sent = None
+        self._pr_mask = torch.ones(self.n_params, dtype=torch.uint8, device=self.dev)
+        self._pr_thr = torch.zeros(len(offs), dtype=torch.float32, device=self.dev)     # before the first update every mask is all ones
+        self._pr_kept = dev(self._pr_sizes, np.int64)
+
+    def _need_prune(self):
+        if self.prune is None:
+            raise engine.YkError('this Trainer was built without a pruning schedule (prune=None)')
+
+    def update_masks(self, s: Optional[int] = None) -> None:
+        """Masks of step s (default: the current iteration) from the CURRENT weights: per kernel the k-th largest |w| and |w| >= it.
+        One library call for all kernels; the mask, the thresholds and the kept counts are written in place.
+        The copy of the keep counts and the kernels that read them are ordered by torch's CURRENT stream: call it (and step()) under the same
+        current stream for the whole life of the Trainer - the rule the captured step already sets (one Trainer per stream)."""
+        self._need_prune()
+        k = self.prune.keep_counts(self._pr_sizes, self.iterations if s is None else s)
+        # n and s are host values: the counts travel as a small array, through pinned memory so that the host does not wait for the stream;
+        # it only waits, before it overwrites the staging buffer, for the PREVIOUS update's copy (an update step ago: long done)
+        if self._pr_keep_sent is not None:
+            self._pr_keep_sent.synchronize()
+        self._pr_keep_host.copy_(self.torch.from_numpy(k))
+        self._pr_keep.copy_(self._pr_keep_host, non_blocking=True)
+        self._pr_keep_sent = self.torch.cuda.Event()
+        self._pr_keep_sent.record()
+        self._ck(self.L.yk_prune_masks_f32(engine._ptr(self.P), engine._ptr(self._pr_off), engine._ptr(self._pr_size),
+                                           engine._ptr(self._pr_keep), engine._ptr(self._pr_first), C.c_int(len(self._pr_sizes)),
+                                           C.c_int(self._pr_ntiles), engine._ptr(self._pr_mask), engine._ptr(self._pr_thr),
+                                           engine._ptr(self._pr_kept), self._s()), 'yk_prune_masks_f32')
+
+    def apply_masks(self) -> None:
+        """P *= mask, in place (tfmot's weight assignment at the start of a step and its on_epoch_end)."""
+        self._need_prune()
+        self._ck(self.L.yk_mask_apply_f32(engine._ptr(self.P), engine._ptr(self._pr_mask), C.c_longlong(self.n_params), self._s()),
+                 'yk_mask_apply_f32')
+
+    def prune_step(self) -> None:
+        """What pruning does at the start of step `iterations`: new masks on an update step, then P *= mask.  Outside the captured
+        step, like Adam; P and the mask are only written in place, so the capture stays valid."""
+        if self.prune.is_update(self.iterations):
+            self.update_masks()
+        self.apply_masks()
+
+    def prune_masks(self) -> Dict[str, np.ndarray]:
+        """Current mask of every pruned kernel, Keras layout (HWIO) bool arrays."""
+        self._need_prune()
+        out = {}
+        for nm in self._pr_names:
+            kh, kw, ci, co = self.lay[nm[:-7]].kernel_shape
+            m = self.view(self._pr_mask, nm).cpu().numpy()
+            out[nm] = np.transpose(m.reshape(co, kh, kw, ci), (1, 2, 3, 0)).astype(bool)
+        return out
+
+    def prune_report(self) -> Dict[str, dict]:
+        """Per pruned kernel: n, kept (mask bytes set), threshold (the k-th largest |w| at the last update) and the achieved sparsity."""
+        self._need_prune()
+        kept, thr = self._pr_kept.cpu().numpy(), self._pr_thr.cpu().numpy()
+        return {nm: dict(n=n, kept=int(k), threshold=float(t), sparsity=1.0 - int(k) / n)
+                for nm, n, k, t in zip(self._pr_names, self._pr_sizes, kept, thr)}
+
     def step(self, x_nhwc, y_true: Sequence["torch.Tensor"], reduce=None, reduce_scalar=None) -> Dict[str, float]:
         """model.fit's inner step (keras_train.py:94).  Returns python floats (one device->host sync)."""
         torch = self.torch
+        if self.prune is not None:
+            self.prune_step()
         r = self._loss_and_grads_replayed(x_nhwc, y_true)
         if self.world > 1:
             self.exchange(reduce)

@@ -10,8 +10,13 @@ engine on the exported weights (BatchNorm with moving statistics, like Keras' te
 
 Checkpoints: `log/<time>/yolo_model.h5` in Keras' WEIGHTS-ONLY HDF5 layout (`model.save_weights` format: readable by the reference's
 `load_weights`, keras_inference.py:80; it is not a `save_model` file - no `model_config` - so `keras_freeze.py`'s `load_model` cannot
-open it; keras_io / h5lite, no h5py needed) plus the same arrays as `yolo_model.npz`; `--pre_ckpt` takes either.  Difference, reported at run time: tfmot pruning is out of
-scope (SURVEY.md section 2 #9) and raises instead of silently doing nothing."""
+open it; keras_io / h5lite, no h5py needed) plus the same arrays as `yolo_model.npz`; `--pre_ckpt` takes either.
+
+`--is_prune True` (`make train PRUNE=True`, keras_train.py:59-71,87-90,102-107): magnitude pruning of every Conv2D kernel on a
+PolynomialDecay schedule built from the four `--prune_*` flags (`prune.PruneSchedule`, end_step = prune_end_epoch x steps per epoch);
+the masks are computed and applied by HIP kernels at the start of a step (`Trainer.prune_step`), once more at the end of every epoch,
+the overall and per-head sparsity is printed per epoch (the stand-in for PruningSummaries), and the checkpoint is
+`yolo_prune_model.h5` / `.npz` with the masked weights.  The rule is restated from tfmot's public source; parity with it is unpinned."""
 from __future__ import annotations
 
 import argparse
@@ -74,14 +79,16 @@ def main(args, train_set, class_num, pre_ckpt, model_def, depth_multiplier, is_a
          frequency=100, synthetic=0, max_steps=0):
     import torch
     from .train import Trainer
-    if is_prune == 'True':
-        raise engine.YkError('tfmot magnitude pruning (keras_train.py:60-71) is out of scope of this build')
+    prune = is_prune == 'True'
     augment = is_augmenter == 'True'
     rank, world = int(os.environ.get('RANK', '0')), int(os.environ.get('WORLD_SIZE', '1'))
     local = int(os.environ.get('LOCAL_RANK', '0'))
     try:
         engine.require_gpu()
     except engine.YkError as e:
+        if prune:
+            raise engine.YkError('--is_prune True (magnitude pruning, keras_train.py:59-71) runs in HIP kernels on the training step: '
+                                 'no HIP device') from e
         if augment:
             raise engine.YkError('--augmenter True (imgaug OneOf, tools/utils.py:84-88) runs in the GPU input pipeline: no HIP device') from e
         raise
@@ -126,9 +133,13 @@ def main(args, train_set, class_num, pre_ckpt, model_def, depth_multiplier, is_a
             print(INFO, f' Load CKPT {str(pre_ckpt)}')
         else:
             print(ERROR, ' Pre CKPT path is unvalid')
+    schedule = None
+    if prune:                                                                    # keras_train.py:60-66: end_step = train_epoch_step * end_epoch
+        from .prune import PruneSchedule
+        schedule = PruneSchedule(initial_sparsity, final_sparsity, end_epoch * (len(h.train_list) // batch_size), frequency)
     tr = Trainer(spec, weights, h.anchors, per_rank, obj_thresh=obj_thresh, iou_thresh=iou_thresh, obj_weight=obj_weight,
                  noobj_weight=noobj_weight, wh_weight=wh_weight, lr=init_learning_rate, decay=learning_rate_decay_factor, device=local,
-                 world_size=world)
+                 world_size=world, prune=schedule)
     from .pipeline import InputPipeline
     if rank == 0:
         print(INFO, 'data augment is ', str(augment))                            # utils.py:418
@@ -152,6 +163,10 @@ def main(args, train_set, class_num, pre_ckpt, model_def, depth_multiplier, is_a
             pipe_rate = pipe.producer_images_per_sec()
         finally:
             pipe.close()
+        if prune:
+            tr.apply_masks()                                                    # tfmot on_epoch_end: validation sees masked weights
+            if rank == 0:
+                print(sparsity_line(tr, spec, epoch), flush=True)
         val = validate(tr, h, spec, per_rank, rank) if rank == 0 and len(h.test_list) >= per_rank else None
         if rank == 0:
             print(f'epoch {epoch + 1}: {seen} steps, mean loss {run / max(seen, 1):.4f}, ' +
@@ -163,16 +178,30 @@ def main(args, train_set, class_num, pre_ckpt, model_def, depth_multiplier, is_a
             break
     if rank == 0:
         from . import keras_io
-        ckpt = log_dir / 'yolo_model.h5'                                        # keras_train.py:105-109
+        stem = 'yolo_prune_model' if prune else 'yolo_model'                    # keras_train.py:102-111
+        ckpt = log_dir / f'{stem}.h5'
+        if prune:
+            tr.apply_masks()                                                    # (a run cut short by --max_steps ends inside an epoch)
         final = tr.export_weights()
         keras_io.save_keras_model(spec, final, str(ckpt))                      # save_model layout: /model_weights + model_config
-        np.savez(log_dir / 'yolo_model.npz', **final)
+        np.savez(log_dir / f'{stem}.npz', **final)
         print()
-        print(INFO, f' Save Model as {str(ckpt)}')
+        print(INFO, f' Save Pruned Model as {str(ckpt)}' if prune else f' Save Model as {str(ckpt)}')
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
     return tr
+
+
+def sparsity_line(tr, spec, epoch: int) -> str:
+    """Achieved sparsity of the masks, overall and per scale head (the biased output convs): what PruningSummaries logs, as one line."""
+    rep = tr.prune_report()
+    n, kept = sum(r['n'] for r in rep.values()), sum(r['kept'] for r in rep.values())
+    heads = [l.name for l in spec.layers if l.kind == 'conv' and l.use_bias]
+    last = min(max(tr.iterations - 1, 0), tr.prune.end_step) // tr.prune.frequency * tr.prune.frequency      # the last update step so far
+    return (f'epoch {epoch + 1}: masks of step {last}, target sparsity {float(tr.prune.sparsity(last)):.4f}, '
+            f'achieved {1.0 - kept / n:.4f} over {len(rep)} kernels ({n - kept} of {n} weights masked); heads ' +
+            ' '.join(f'{nm} {rep[nm + "/kernel"]["sparsity"]:.4f}' for nm in heads))
 
 
 def validate(tr, h: Helper, spec, batch: int, rank: int) -> float:
