@@ -7,6 +7,7 @@
 #   make inference   MODEL=... DEPTHMUL=... CKPT=weights.h5|.npz IMG=picture.jpg
 #   make train       MODEL=... DEPTHMUL=... BATCH=16 MAXEP=10 [SYNTHETIC=256]
 #                    [PRUNE=True INITSPARSITY=0.5 FINALSPARSITY=0.9 END_EPOCH=5 FREQUENCY=100]: magnitude pruning, saves yolo_prune_model.h5
+#   make kmodel      CKPT=yolo_model.h5 OUT=yolo.kmodel|.kfpkg [SYNTHETIC=256 | CALIB=data/voc_img_ann.npy]: 8-bit K210 model, calibrated on the GPU
 #   make anchors     DATASET=voc ANCNUM=3 [LOW='0.0 0.0' HIGH='1.0 1.0']   (reference Makefile:78-87: k-means anchors from data/<set>_img_ann.npy)
 
 PY            ?= python3
@@ -36,6 +37,9 @@ FINALSPARSITY ?= 0.9
 END_EPOCH     ?= 5
 FREQUENCY     ?= 100
 SYNTHETIC     ?= 0
+# kmodel only
+OUT           ?= yolo.kmodel
+CALIB         ?= data/$(DATASET)_img_ann.npy
 GPUS          ?= 1
 # anchors only (reference Makefile:27-29)
 ANCNUM        ?= 3
@@ -55,9 +59,9 @@ else
 LAUNCH = $(PY) -m torch.distributed.run --nnodes=1 --nproc-per-node $(GPUS) --master-addr 127.0.0.1 --master-port 29533
 endif
 
-.PHONY: all build test bench inference train anchors
+.PHONY: all build test bench inference train anchors kmodel
 all:
-	@echo 'targets: build | test | bench | inference | train   (see the header of this Makefile)'
+	@echo 'targets: build | test | bench | inference | train | kmodel   (see the header of this Makefile)'
 
 build:
 	$(PY) -c "import __graft_entry__ as g; g.build()"
@@ -73,6 +77,11 @@ inference:
 
 train:
 	$(LAUNCH) keras_train.py $(NET_ARGS) $(TRAIN_ARGS)
+
+# the step the reference leaves to keras_freeze.py + nncase: CKPT -> 8-bit kmodel; SYNTHETIC=N calibrates on generated images
+kmodel:
+	$(PY) make_kmodel.py $(CKPT) $(OUT) --train_set $(DATASET) --class_num $(CLSNUM) --model_def $(MODEL) --depth_multiplier $(DEPTHMUL) \
+		--image_size $(IMGSIZE) --output_size $(OUTSIZE) $(if $(filter-out 0,$(SYNTHETIC)),--synthetic $(SYNTHETIC),--calib $(CALIB))
 
 # reference Makefile:78-87 (same flags; --is_random True as there)
 anchors:

@@ -439,6 +439,25 @@ int yk_kpu_debug_read(yk_kpu_plan_t *p, int layer_index, int image, uint8_t *h_d
 int yk_kpu_launch_count(const yk_kpu_plan_t *p);
 int yk_kpu_profile(yk_kpu_plan_t *p, const uint8_t *d_frames, int batch, int layout, int iters, void *stream, float *ms_out);
 
+/* ---- calibration for 8-bit quantisation (quantize.py): tensor ranges of an fp32 forward pass, reduced on the device.
+ * d_range holds YK_RANGE_WORDS uint32 per slot: {smallest key, largest key, flag, 0}.  The key of a float is its bit pattern made
+ * order-preserving for unsigned comparison (-max < ... < -0 < +0 < ... < +max), so the reduction is integer min / max: bitwise independent
+ * of scheduling, launch geometry and stream, and denormals are kept.  Infinities and NaNs do not enter a range; they set the slot's sticky
+ * flag.  Launches are asynchronous on `stream`: one atomicMin / atomicMax pair per workgroup.  Bad arguments: YK_ERR_ARG.
+ * yk_range_reset          every slot to "nothing seen" (min key all ones, max key 0, flag 0);
+ * yk_range_f32            folds min / max of x[0..n) into `slot` (accumulates over calls);
+ * yk_scale_act_range_f32  y[m][c] = act(z[m][c] * scale[c] + bias[c]) (act: YK_ACT_*, one rounding per operation: no FMA contraction),
+ *                         M x C row-major, any M, C >= 1 (16-byte accesses when C % 4 == 0 and the pointers allow), and folds min / max
+ *                         of y into `slot`;
+ * yk_range_read           ONE device-to-host copy (synchronises), decoded on the host: h_min / h_max [n_slots] (+inf / -inf for a slot that
+ *                         has seen nothing finite), h_flags [n_slots]. */
+#define YK_RANGE_WORDS 4
+int yk_range_reset(uint32_t *d_range, int n_slots, void *stream);
+int yk_range_f32(const float *x, long long n, uint32_t *d_range, int slot, void *stream);
+int yk_scale_act_range_f32(const float *z, long long M, int C, const float *scale, const float *bias, int act, float alpha, float *y,
+                           uint32_t *d_range, int slot, void *stream);
+int yk_range_read(const uint32_t *d_range, int n_slots, float *h_min, float *h_max, int *h_flags);
+
 #ifdef __cplusplus
 }
 #endif

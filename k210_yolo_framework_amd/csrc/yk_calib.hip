@@ -1,0 +1,222 @@
+// yk_calib.hip — calibration for 8-bit quantisation (quantize.py): the range of every tensor of an fp32 forward pass.
+//
+// The minimum and the maximum of a tensor are folded on the device into a slot of YK_RANGE_WORDS uint32 words: the smallest and the largest
+// ORDER-PRESERVING KEY seen so far and a sticky flag.  The key of a float is its bit pattern with the sign bit flipped (positive values)
+// or all bits flipped (negative values): unsigned comparison of keys is the total order -max < ... < -0 < +0 < ... < +max, so the whole
+// reduction is integer min / max - associative and commutative, hence bitwise independent of how workgroups are scheduled, of the launch
+// geometry and of the stream; denormals are never flushed because no floating-point comparison touches them.  A NaN or an infinity does
+// not enter the range: it sets the flag, which the host turns into an error naming the layer.
+//
+// Per launch: grid-stride loop with 16-byte loads (and stores), wave reduction in registers (__shfl_xor), block reduction through 2 x 4
+// words of LDS, then ONE atomicMin and ONE atomicMax per workgroup (vector atomics on global memory), and an atomicOr only from a
+// workgroup that met a non-finite value.
+#include "yk_common.h"
+
+namespace {
+
+constexpr int CAL_BLOCK = 256;
+constexpr int CAL_WAVES = CAL_BLOCK / YK_WAVE;
+constexpr unsigned CAL_MAX_GRID = 2048;                  // 8 workgroups per CU: enough in flight to stream from HBM
+
+__device__ __forceinline__ uint32_t key_of(uint32_t b) { return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u); }
+
+struct Acc {
+    uint32_t lo = 0xFFFFFFFFu, hi = 0u, bad = 0u;
+    __device__ __forceinline__ void add(float v) {
+        const uint32_t b = __float_as_uint(v);
+        if ((b & 0x7F800000u) == 0x7F800000u) {          // inf or NaN
+            bad = 1u;
+            return;
+        }
+        const uint32_t k = key_of(b);
+        lo = k < lo ? k : lo;
+        hi = k > hi ? k : hi;
+    }
+};
+
+// the workgroup's result into the slot: one atomicMin + one atomicMax
+__device__ __forceinline__ void fold(Acc a, uint32_t *slot) {
+    __shared__ uint32_t s_lo[CAL_WAVES], s_hi[CAL_WAVES], s_bad[CAL_WAVES];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const uint32_t l = __shfl_xor(a.lo, o, 64), h = __shfl_xor(a.hi, o, 64), f = __shfl_xor(a.bad, o, 64);
+        a.lo = l < a.lo ? l : a.lo;
+        a.hi = h > a.hi ? h : a.hi;
+        a.bad |= f;
+    }
+    const int wave = threadIdx.x / YK_WAVE;
+    if ((threadIdx.x & (YK_WAVE - 1)) == 0) {
+        s_lo[wave] = a.lo;
+        s_hi[wave] = a.hi;
+        s_bad[wave] = a.bad;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t lo = s_lo[0], hi = s_hi[0], bad = s_bad[0];
+#pragma unroll
+        for (int w = 1; w < CAL_WAVES; ++w) {
+            lo = s_lo[w] < lo ? s_lo[w] : lo;
+            hi = s_hi[w] > hi ? s_hi[w] : hi;
+            bad |= s_bad[w];
+        }
+        atomicMin(slot + 0, lo);
+        atomicMax(slot + 1, hi);
+        if (bad) atomicOr(slot + 2, 1u);
+    }
+}
+
+__device__ __forceinline__ float c_act(float v, int act, float alpha) {      // as t_act of yk_train.hip
+    if (act == YK_ACT_RELU) return v > 0.f ? v : 0.f;
+    if (act == YK_ACT_RELU6) return v < 0.f ? 0.f : (v > 6.f ? 6.f : v);
+    if (act == YK_ACT_LEAKY) return v >= 0.f ? v : v * alpha;
+    return v;
+}
+
+// n4 float4 + the scalar tail [4 * n4, n)
+__global__ __launch_bounds__(CAL_BLOCK) void range_kernel(const float *__restrict__ x, size_t n4, size_t n, uint32_t *slot) {
+    Acc a;
+    const size_t step = (size_t)gridDim.x * CAL_BLOCK;
+    const float4 *x4 = reinterpret_cast<const float4 *>(x);
+    for (size_t i = (size_t)blockIdx.x * CAL_BLOCK + threadIdx.x; i < n4; i += step) {
+        const float4 v = x4[i];
+        a.add(v.x);
+        a.add(v.y);
+        a.add(v.z);
+        a.add(v.w);
+    }
+    for (size_t i = 4 * n4 + (size_t)blockIdx.x * CAL_BLOCK + threadIdx.x; i < n; i += step) a.add(x[i]);
+    fold(a, slot);
+}
+
+// C % 4 == 0, all pointers 16-byte aligned: element 4 * i starts at channel (4 * i) % C and the four share one row
+__global__ __launch_bounds__(CAL_BLOCK) void scale_act_range_vec_kernel(const float *__restrict__ z, size_t n4, int C, const float *__restrict__ scale,
+                                                                         const float *__restrict__ bias, int act, float alpha, float *__restrict__ y,
+                                                                         uint32_t *slot) {
+    Acc a;
+    const size_t step = (size_t)gridDim.x * CAL_BLOCK;
+    const float4 *z4 = reinterpret_cast<const float4 *>(z);
+    float4 *y4 = reinterpret_cast<float4 *>(y);
+    const size_t c4 = (size_t)(C / 4);
+    for (size_t i = (size_t)blockIdx.x * CAL_BLOCK + threadIdx.x; i < n4; i += step) {
+        const size_t c = (i % c4) * 4;
+        const float4 v = z4[i];
+        const float4 s = *reinterpret_cast<const float4 *>(scale + c);
+        const float4 b = *reinterpret_cast<const float4 *>(bias + c);
+        float4 r;
+        r.x = c_act(v.x * s.x + b.x, act, alpha);
+        r.y = c_act(v.y * s.y + b.y, act, alpha);
+        r.z = c_act(v.z * s.z + b.z, act, alpha);
+        r.w = c_act(v.w * s.w + b.w, act, alpha);
+        y4[i] = r;
+        a.add(r.x);
+        a.add(r.y);
+        a.add(r.z);
+        a.add(r.w);
+    }
+    fold(a, slot);
+}
+
+__global__ __launch_bounds__(CAL_BLOCK) void scale_act_range_kernel(const float *__restrict__ z, size_t n, int C, const float *__restrict__ scale,
+                                                                     const float *__restrict__ bias, int act, float alpha, float *__restrict__ y,
+                                                                     uint32_t *slot) {
+    Acc a;
+    const size_t step = (size_t)gridDim.x * CAL_BLOCK;
+    for (size_t i = (size_t)blockIdx.x * CAL_BLOCK + threadIdx.x; i < n; i += step) {
+        const int c = (int)(i % (size_t)C);
+        const float r = c_act(z[i] * scale[c] + bias[c], act, alpha);
+        y[i] = r;
+        a.add(r);
+    }
+    fold(a, slot);
+}
+
+__global__ void range_reset_kernel(uint32_t *r, int n_slots) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n_slots) {
+        r[YK_RANGE_WORDS * i + 0] = 0xFFFFFFFFu;
+        r[YK_RANGE_WORDS * i + 1] = 0u;
+        r[YK_RANGE_WORDS * i + 2] = 0u;
+        r[YK_RANGE_WORDS * i + 3] = 0u;
+    }
+}
+
+inline unsigned grid_for(size_t items) {
+    const size_t g = (items + CAL_BLOCK - 1) / CAL_BLOCK;
+    return (unsigned)(g < 1 ? 1 : (g > CAL_MAX_GRID ? CAL_MAX_GRID : g));
+}
+inline bool aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
+inline float unkey(uint32_t k) {
+    const uint32_t b = (k & 0x80000000u) ? (k ^ 0x80000000u) : ~k;
+    float f;
+    memcpy(&f, &b, 4);
+    return f;
+}
+
+}  // namespace
+
+extern "C" int yk_range_reset(uint32_t *d_range, int n_slots, void *stream) {
+    if (!d_range || n_slots <= 0) {
+        yk_set_error("yk_range_reset: bad argument");
+        return YK_ERR_ARG;
+    }
+    hipLaunchKernelGGL(range_reset_kernel, dim3((unsigned)((n_slots + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_range, n_slots);
+    YK_HIP(hipGetLastError());
+    return YK_OK;
+}
+
+extern "C" int yk_range_f32(const float *x, long long n, uint32_t *d_range, int slot, void *stream) {
+    if (!x || n <= 0 || !d_range || slot < 0) {
+        yk_set_error("yk_range_f32: bad argument");
+        return YK_ERR_ARG;
+    }
+    const size_t n4 = aligned16(x) ? (size_t)n / 4 : 0;
+    const size_t items = n4 > (size_t)n - 4 * n4 ? n4 : (size_t)n - 4 * n4;
+    hipLaunchKernelGGL(range_kernel, dim3(grid_for(items)), dim3(CAL_BLOCK), 0, (hipStream_t)stream, x, n4, (size_t)n,
+                       d_range + (size_t)YK_RANGE_WORDS * slot);
+    YK_HIP(hipGetLastError());
+    return YK_OK;
+}
+
+extern "C" int yk_scale_act_range_f32(const float *z, long long M, int C, const float *scale, const float *bias, int act, float alpha, float *y,
+                                      uint32_t *d_range, int slot, void *stream) {
+    if (!z || !scale || !bias || !y || !d_range || M <= 0 || C <= 0 || slot < 0 || act < YK_ACT_NONE || act > YK_ACT_LEAKY) {
+        yk_set_error("yk_scale_act_range_f32: bad argument");
+        return YK_ERR_ARG;
+    }
+    const size_t n = (size_t)M * (size_t)C;
+    uint32_t *s = d_range + (size_t)YK_RANGE_WORDS * slot;
+    if (C % 4 == 0 && aligned16(z) && aligned16(y) && aligned16(scale) && aligned16(bias))
+        hipLaunchKernelGGL(scale_act_range_vec_kernel, dim3(grid_for(n / 4)), dim3(CAL_BLOCK), 0, (hipStream_t)stream, z, n / 4, C, scale, bias, act,
+                           alpha, y, s);
+    else
+        hipLaunchKernelGGL(scale_act_range_kernel, dim3(grid_for(n)), dim3(CAL_BLOCK), 0, (hipStream_t)stream, z, n, C, scale, bias, act, alpha, y, s);
+    YK_HIP(hipGetLastError());
+    return YK_OK;
+}
+
+extern "C" int yk_range_read(const uint32_t *d_range, int n_slots, float *h_min, float *h_max, int *h_flags) {
+    if (!d_range || n_slots <= 0 || !h_min || !h_max || !h_flags) {
+        yk_set_error("yk_range_read: bad argument");
+        return YK_ERR_ARG;
+    }
+    uint32_t *h = (uint32_t *)malloc((size_t)n_slots * YK_RANGE_WORDS * sizeof(uint32_t));
+    if (!h) {
+        yk_set_error("yk_range_read: out of host memory");
+        return YK_ERR_NOMEM;
+    }
+    const hipError_t e = hipMemcpy(h, d_range, (size_t)n_slots * YK_RANGE_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost);   // one copy; synchronises
+    if (e != hipSuccess) {
+        free(h);
+        yk_set_error("yk_range_read: hipMemcpy -> %s", hipGetErrorString(e));
+        return YK_ERR_HIP;
+    }
+    for (int i = 0; i < n_slots; ++i) {
+        const uint32_t lo = h[YK_RANGE_WORDS * i], hi = h[YK_RANGE_WORDS * i + 1];
+        const bool empty = lo > hi;                                    // nothing finite folded in yet
+        h_min[i] = empty ? __builtin_huge_valf() : unkey(lo);
+        h_max[i] = empty ? -__builtin_huge_valf() : unkey(hi);
+        h_flags[i] = (int)h[YK_RANGE_WORDS * i + 2];
+    }
+    free(h);
+    return YK_OK;
+}

@@ -1,4 +1,4 @@
-"""K210 kmodel (v3) reader: recover the trained, 8-bit quantised yolo_mobilev1-0.75 of the reference's K210 demo as Keras-named
+"""K210 kmodel (v3) reader and writer (`parse` / `serialise`, `write`; the quantiser that fills a model is quantize.py).  Reader: recover the trained, 8-bit quantised yolo_mobilev1-0.75 of the reference's K210 demo as Keras-named
 float weights this framework can run.
 
 The only trained weights in the reference tree are inside `yolo3_frame_test_public/kfpkg/kpu_yolov3.kfpkg` (a zip): `yolo.kmodel`,
@@ -478,8 +478,9 @@ YOLO_MOBILEV1_ORDER = (['conv1'] + [n for i in range(1, 14) for n in (f'conv_dw_
                        ['head_conv_1', 'head_conv_2', 'head_conv_3', 'head_conv_4', 'head_conv_5'])
 
 
-def to_float_weights(km: Kmodel) -> Tuple[Dict[str, np.ndarray], dict]:
-    """Float parameters of `yolonet.yolo_mobilev1(alpha=0.75)` under this framework's (Keras layer) names + a report (activation slopes found, zero points, the
+def to_float_weights(km: Kmodel, spec=None) -> Tuple[Dict[str, np.ndarray], dict]:
+    """Float parameters of `yolonet.yolo_mobilev1` - `spec`, a netspec.yolo_mobilev1 of any depth multiplier and class count; by default the
+    demo's (alpha=0.75, 20 classes) - under this framework's (Keras layer) names + a report (activation slopes found, zero points, the
     requantisation factors).  Conv kernels HWIO, depthwise [3,3,C,1], BatchNorm as gamma / beta / moving_mean 0 / moving_variance 1-eps
     so that Keras' inference formula reproduces (scale, bias) exactly; the two output convs carry a bias."""
     convs = km.convs
@@ -488,15 +489,18 @@ def to_float_weights(km: Kmodel) -> Tuple[Dict[str, np.ndarray], dict]:
     # every conv against the layer of yolo_mobilev1-0.75 it is mapped onto (kernel size, depthwise, channels, no KPU pooling): a kmodel
     # of another network with the same NUMBER of convs must not be dequantised into this one's names
     from . import netspec as ns
-    spec = ns.yolo_mobilev1((224, 320, 3), 3, 20, alpha=0.75)
+    if spec is None:
+        spec = ns.yolo_mobilev1((224, 320, 3), 3, 20, alpha=0.75)
     want = {l.name: l for l in spec.layers}
+    if sorted(want) != sorted(YOLO_MOBILEV1_ORDER):
+        raise KmodelError(f'kmodel: dequantisation maps onto the yolo_mobilev1 graph; {spec.name} has other layers')
     for name, c in zip(YOLO_MOBILEV1_ORDER, convs):
         kh, _, ci, co = want[name].kernel_shape
         dw = want[name].kind == 'dwconv'
         exp = (kh, dw, ci, ci if dw else co)
         got = (c.ksize, bool(c.depthwise), c.in_ch, c.out_ch)
         if got != exp:
-            raise KmodelError(f'kmodel: conv {c.index} is (k, depthwise, in, out) = {got}; yolo_mobilev1-0.75 layer {name} is {exp}')
+            raise KmodelError(f'kmodel: conv {c.index} is (k, depthwise, in, out) = {got}; layer {name} of the yolo_mobilev1 it is loaded into is {exp}')
         if c.pool_type not in (0, 5):          # 5 = keep the top-left sample of every 2x2 window: how the KPU runs a stride-2 conv
             raise KmodelError(f'kmodel: conv {c.index} ({name}) uses KPU pooling type {c.pool_type}; the graph has no pooling layers')
     mem = [l for l in km.layers if isinstance(l, MemLayer)]
@@ -562,3 +566,242 @@ def to_float_weights(km: Kmodel) -> Tuple[Dict[str, np.ndarray], dict]:
             out[f'{bn}/moving_variance'] = np.full(c.out_ch, 1.0 - eps, np.float32)   # gamma / sqrt(var + eps) = gamma
         report['layers'][name] = dict(alpha=alpha, zp_x=c.zp_x, zp_w=c.zp_w, z0=z0, y0=y0, slope=s_pos, pool=c.pool_type, pad_value=c.pad_value)
     return out, report
+
+
+# ---- writer: the inverse of parse -----------------------------------------------------------------------------------------------------
+# Everything below restates the published Kendryte standalone SDK (`kpu.h`: kpu_layer_argument_t, kpu_model_header_t and the kpu_model_*
+# layer bodies of `kpu.c`) and the rules nncase v0.1 applies when it emits a K210 conv; the demo file is the same network, so every rule
+# is held against its 32 convs bit for bit (tests/test_kmodel_write.py).
+KPU_RAM_BYTES = 2 * 1024 * 1024
+KPU_RAM_UNITS = KPU_RAM_BYTES // 64                   # image_src_addr / image_dst_addr count 64-byte lines
+KPU_PARAM_LOAD_BYTES = 30 * 1024                      # one weight load: nncase fills at most 30 KB of the parameter RAM at a time
+KFPKG_MODEL_ADDRESS = 0x00A00000                      # where the demo flashes yolo.kmodel (flash-list.json; main.c reads it from there)
+HEADER_FLAGS_8BIT = 1                                 # kpu_model_header_t.flags bit 0: eight-bit weights (the only kind read or written here)
+
+# Register fields that could NOT be derived from the public definitions and are therefore excluded from the register check, as
+# {name: (register, low bit, bits, reason)}.  Empty: every field of the demo's 32 x 12 registers is regenerated.
+UNDERIVED_REGISTER_FIELDS: Dict[str, Tuple[int, int, int, str]] = {}
+# The KPU-RAM addresses: allocator output, not a function of the layer (an own allocator need not place tensors where nncase did).
+KPU_ADDRESS_FIELDS = {'image_src_addr': (1, 0, 15), 'image_dst_addr': (1, 32, 15)}
+
+
+def kpu_row_layout(width: int) -> Tuple[int, int]:
+    """How the KPU lays one image row into its 64-byte RAM lines: (channels sharing a line, lines per row).  Rows up to 16 pixels pack
+    four channels into a line, up to 32 two; wider rows take ceil(width / 64) lines of their own."""
+    if width <= 16:
+        return 4, 1
+    if width <= 32:
+        return 2, 1
+    return 1, (width + 63) // 64
+
+
+def kpu_tensor_units(channels: int, height: int, width: int) -> int:
+    """64-byte lines a [C][H][W] uint8 tensor occupies in KPU RAM."""
+    groups, row_len = kpu_row_layout(width)
+    return row_len * height * ((channels + groups - 1) // groups)
+
+
+def _field(c: ConvLayer, regs: List[int], reg: int, lo: int, bits: int, name: str, v, signed: bool = False) -> None:
+    _check_width(c, name, [v], bits, signed)
+    regs[reg] |= (int(v) & ((1 << bits) - 1)) << lo
+
+
+def conv_registers(c: ConvLayer) -> List[int]:
+    """The twelve 64-bit registers (kpu_layer_argument_t) of a KPU conv, regenerated from its geometry and quantisation parameters.
+    Pointer fields the loader fills at run time (bwsx_base_addr, para_start_addr, active_addr) and send_data_out / int_en / full_add,
+    which kpu_run_kmodel sets per run, are zero in the file, as the demo has them.  KmodelError when a value does not fit its field."""
+    if c.ksize not in (1, 3):
+        raise KmodelError(f'kmodel: conv layer {c.index}: kernel size {c.ksize} (the KPU has 1x1 and 3x3)')
+    r = [0] * 12
+    f = lambda *a, **k: _field(c, r, *a, **k)                                                  # noqa: E731
+    in_groups, in_row_len = kpu_row_layout(c.in_w)
+    out_groups, out_row_len = kpu_row_layout(c.out_w)
+    one_channel = c.ksize * c.ksize * (1 if c.depthwise else c.in_ch)                          # weight bytes of one output channel
+    per_load = min(c.out_ch, KPU_PARAM_LOAD_BYTES // one_channel)
+    if per_load < 1:
+        raise KmodelError(f'kmodel: conv layer {c.index}: one output channel has {one_channel} weight bytes, more than one parameter load '
+                          f'({KPU_PARAM_LOAD_BYTES})')
+    # 0 interrupt_enabe
+    f(0, 0, 1, 'int_en', 0); f(0, 1, 1, 'ram_flag', 0); f(0, 2, 1, 'full_add', 0); f(0, 3, 1, 'depth_wise_layer', int(bool(c.depthwise)))
+    # 1 image_addr
+    f(1, 0, 15, 'image_src_addr', c.src_addr); f(1, 32, 15, 'image_dst_addr', c.dst_addr)
+    # 2 image_channel_num
+    f(2, 0, 10, 'i_ch_num', c.in_ch - 1); f(2, 32, 10, 'o_ch_num', c.out_ch - 1); f(2, 48, 10, 'o_ch_num_coef', per_load - 1)
+    # 3 image_size
+    f(3, 0, 10, 'i_row_wid', c.in_w - 1); f(3, 10, 9, 'i_col_high', c.in_h - 1)
+    f(3, 32, 10, 'o_row_wid', c.out_w - 1); f(3, 42, 9, 'o_col_high', c.out_h - 1)
+    # 4 kernel_pool_type_cfg
+    f(4, 0, 3, 'kernel_type', 1 if c.ksize == 3 else 0); f(4, 3, 1, 'pad_type', 0); f(4, 4, 4, 'pool_type', c.pool_type)
+    f(4, 8, 1, 'first_stride', 0 if c.in_h < 256 else 1); f(4, 9, 1, 'bypass_conv', 0); f(4, 10, 1, 'load_para', 1)
+    f(4, 16, 8, 'dma_burst_size', 15); f(4, 24, 8, 'pad_value', c.pad_value); f(4, 32, 32, 'bwsx_base_addr', 0)
+    # 5 kernel_load_cfg
+    f(5, 0, 1, 'load_coor', 1); f(5, 1, 6, 'load_time', (c.out_ch + per_load - 1) // per_load - 1)
+    f(5, 15, 17, 'para_size', per_load * one_channel); f(5, 32, 32, 'para_start_addr', 0)
+    # 6 kernel_offset
+    f(6, 0, 4, 'coef_column_offset', 0); f(6, 4, 12, 'coef_row_offset', 0)
+    # 7 kernel_calc_type_cfg
+    f(7, 0, 15, 'channel_switch_addr', in_row_len * c.in_h); f(7, 16, 4, 'row_switch_addr', in_row_len); f(7, 20, 8, 'coef_size', 0)
+    f(7, 28, 3, 'coef_group', in_groups); f(7, 31, 1, 'load_act', 1); f(7, 32, 32, 'active_addr', 0)
+    # 8 write_back_cfg
+    f(8, 0, 15, 'wb_channel_switch_addr', out_row_len * c.out_h); f(8, 16, 4, 'wb_row_switch_addr', out_row_len); f(8, 20, 3, 'wb_group', out_groups)
+    # 9 conv_value, 10 conv_value2
+    f(9, 0, 4, 'shr_w', c.shr_w); f(9, 4, 4, 'shr_x', c.shr_x); f(9, 8, 24, 'arg_w', c.arg_w, signed=True); f(9, 32, 24, 'arg_x', c.arg_x, signed=True)
+    f(10, 0, 40, 'arg_add', c.arg_add, signed=True)
+    # 11 dma_parameter
+    f(11, 0, 1, 'send_data_out', 0); f(11, 16, 16, 'channel_byte_num', c.out_w * c.out_h - 1)
+    f(11, 32, 32, 'dma_total_byte', c.out_w * c.out_h * c.out_ch - 1)
+    return r
+
+
+def register_field_mask(fields) -> List[int]:
+    """Twelve masks with the bits of the given {name: (register, low bit, bits, ...)} fields set."""
+    m = [0] * 12
+    for reg, lo, bits, *_ in fields.values():
+        m[reg] |= ((1 << bits) - 1) << lo
+    return m
+
+
+def main_mem_usage(km: Kmodel) -> int:
+    """Bytes of main memory the layers touch: the end of the highest tensor any layer writes (kpu_model_header_t.main_mem_usage)."""
+    end = 0
+    for l in km.layers:
+        if isinstance(l, ConvLayer):
+            if l.flags & KLF_MAIN_MEM_OUT:
+                end = max(end, l.main_mem_out + l.out_ch * l.out_h * l.out_w)
+            continue
+        f = l.fields
+        if l.type == KL_DEQUANTIZE:
+            end = max(end, f['dst'] + 4 * f['count'])
+        elif l.type == KL_REQUANTIZE:
+            end = max(end, f['dst'] + f['count'])
+        elif l.type == KL_QUANTIZED_RESIZE_NN:
+            end = max(end, f['dst'] + f['channels'] * f['out_h'] * f['out_w'])
+        elif l.type == KL_QUANTIZED_CONCAT:
+            end = max(end, f['dst'] + sum(s for _, s in f['inputs']))
+    return end
+
+
+def _pad_to(buf: bytearray, align: int) -> None:
+    while len(buf) % align:
+        buf.append(0)
+
+
+def serialise(km: Kmodel) -> bytes:
+    """The inverse of `parse`: a kmodel v3 file from the parsed model.  The header is rebuilt from the layers (eight-bit flag, layer count,
+    main_mem_usage = `main_mem_usage(km)`, the output table; max_start_address is 0 as nncase v0.1 leaves it), every conv's registers
+    by `conv_registers`, and the bodies are laid out as nncase does: registers 8-byte aligned, weights and BatchNorm table 128-byte
+    aligned, activation table 256-byte aligned (file offsets, which is what the body stores), main-memory bodies padded to 8 bytes.
+    For a parsed file whose addresses are kept this reproduces the demo byte for byte."""
+    if km.version != 3:
+        raise KmodelError(f'kmodel: version {km.version} (only v3 is written)')
+    n_out, n_l = len(km.outputs), len(km.layers)
+    buf = bytearray(struct.pack('<7I', 3, HEADER_FLAGS_8BIT, 0, n_l, 0, main_mem_usage(km), n_out))
+    for a, s in km.outputs:
+        buf += struct.pack('<2I', a, s)
+    table_at = len(buf)
+    buf += bytes(8 * n_l)
+    for i, l in enumerate(km.layers):
+        start = len(buf)
+        if isinstance(l, ConvLayer):
+            c = l
+            regs = conv_registers(c)
+            for name, v, bits, signed in (('bn_mul', c.bn_mul, 24, True), ('bn_add', c.bn_add, 32, True), ('bn_shift', c.bn_shift, 4, False),
+                                          ('act_shift', c.act_shift, 8, False), ('act_mul', c.act_mul, 16, True),
+                                          ('act_start', c.act_start, 36, True), ('act_bias', c.act_bias, 8, True)):
+                _check_width(c, name, v, bits, signed)
+            w = np.asarray(c.weights)
+            if w.dtype != np.uint8 or w.shape != (c.out_ch, 1 if c.depthwise else c.in_ch, c.ksize * c.ksize):
+                raise KmodelError(f'kmodel: conv layer {c.index}: weights {w.dtype} {w.shape}')
+            if len(c.bn_mul) != c.out_ch or len(c.bn_add) != c.out_ch or len(c.bn_shift) != c.out_ch or any(
+                    len(t) != 16 for t in (c.act_start, c.act_mul, c.act_shift, c.act_bias)):
+                raise KmodelError(f'kmodel: conv layer {c.index}: BatchNorm / activation tables of the wrong length')
+            buf += bytes(24)
+            _pad_to(buf, 8)
+            lo = len(buf)
+            buf += struct.pack('<12Q', *regs)
+            _pad_to(buf, 128)
+            wo = len(buf)
+            buf += w.tobytes()
+            _pad_to(buf, 128)
+            bo = len(buf)
+            for m, a, s in zip(c.bn_mul, c.bn_add, c.bn_shift):
+                buf += struct.pack('<Q', (int(m) & 0xFFFFFF) | ((int(a) & 0xFFFFFFFF) << 24) | ((int(s) & 0xF) << 56))
+            _pad_to(buf, 256)
+            ao = len(buf)
+            for st, m, s in zip(c.act_start, c.act_mul, c.act_shift):
+                buf += struct.pack('<Q', (int(s) & 0xFF) | ((int(m) & 0xFFFF) << 8) | ((int(st) & 0xFFFFFFFFF) << 24))
+            buf += np.asarray(c.act_bias, np.int64).astype(np.int8).tobytes()
+            struct.pack_into('<6I', buf, start, c.flags, c.main_mem_out, lo, wo, bo, ao)
+            ty = KL_K210_CONV
+        else:
+            f, ty = l.fields, l.type
+            if ty == KL_DEQUANTIZE:
+                buf += struct.pack('<4I2f', f['flags'], f['src'], f['dst'], f['count'], f['scale'], f['bias'])
+            elif ty == KL_REQUANTIZE:
+                tab = np.asarray(f['table'])
+                if tab.dtype != np.uint8 or tab.shape != (256,):
+                    raise KmodelError(f'kmodel: layer {l.index}: REQUANTIZE table {tab.dtype} {tab.shape}')
+                buf += struct.pack('<4I', f['flags'], f['src'], f['dst'], f['count']) + tab.tobytes()
+            elif ty == KL_QUANTIZED_CONCAT:
+                buf += struct.pack('<3I', f['flags'], f['dst'], len(f['inputs']))
+                for a, s in f['inputs']:
+                    buf += struct.pack('<2I', a, s)
+            elif ty == KL_QUANTIZED_RESIZE_NN:
+                buf += struct.pack('<9I', f['flags'], f['src'], f['dst'], f['in_w'], f['in_h'], f['channels'], f['out_w'], f['out_h'],
+                                   f['align'])
+            elif ty == KL_K210_UPLOAD:
+                buf += struct.pack('<6I', f['flags'], f['src'], f['kpu_addr'], f['width'], f['height'], f['channels'])
+            else:
+                raise KmodelError(f'kmodel: layer {l.index} has type {ty}, which this writer does not know')
+            buf += bytes(-(len(buf) - start) % 8)                      # every body is a multiple of 8 bytes long
+        struct.pack_into('<2I', buf, table_at + 8 * i, ty, len(buf) - start)
+    return bytes(buf)
+
+
+def write(path, km: Kmodel) -> int:
+    """Write `km` as a `.kmodel`, or - when the suffix is `.kfpkg` - as the flash package kflash takes: a zip of `yolo.kmodel` and a
+    `flash-list.json` with the model at the demo's address 0x00A00000.  The package carries NO firmware binary (the demo's has one beside
+    the model): flash the firmware separately.  Returns the kmodel's size in bytes."""
+    import json
+    data = serialise(km)
+    path = str(path)
+    if path.endswith('.kfpkg'):
+        manifest = {'version': '0.1.0', 'files': [{'address': KFPKG_MODEL_ADDRESS, 'bin': 'yolo.kmodel', 'sha256Prefix': False}]}
+        with zipfile.ZipFile(path, 'w', zipfile.ZIP_DEFLATED) as z:
+            z.writestr('flash-list.json', json.dumps(manifest, indent=2))
+            z.writestr('yolo.kmodel', data)
+    else:
+        with open(path, 'wb') as fh:
+            fh.write(data)
+    return len(data)
+
+
+def allocate_kpu_ram(sizes: List[int], births: List[int], deaths: List[int]) -> List[int]:
+    """KPU-RAM addresses (64-byte units) for tensors of `sizes` units, each alive from step births[i] to step deaths[i] inclusive (the
+    step that writes it .. the last step that reads it; a conv's input and output are both alive at the conv's step, so they never
+    overlap, and nothing still to be read is overwritten).  In order of birth, each tensor takes address 0 if it is free for its lifetime and
+    otherwise the highest free place; not nncase's allocator, and the addresses need not equal its.  KmodelError when a tensor does not fit below 2 MB."""
+    addr = [-1] * len(sizes)
+    for i in sorted(range(len(sizes)), key=lambda k: (births[k], k)):
+        if sizes[i] > KPU_RAM_UNITS:
+            raise KmodelError(f'kmodel: a tensor of {sizes[i] * 64} bytes exceeds the KPU RAM ({KPU_RAM_BYTES} bytes)')
+        busy = sorted((addr[j], addr[j] + sizes[j]) for j in range(len(sizes))
+                      if addr[j] >= 0 and not (deaths[j] < births[i] or births[j] > deaths[i]))
+        at = 0                                                          # lowest fit
+        for lo, hi in busy:
+            if at + sizes[i] <= lo:
+                break
+            at = max(at, hi)
+        if at != 0:                                                     # the bottom is taken: highest fit instead (input and output ping-pong
+            top = KPU_RAM_UNITS                                         # between the two ends, so neither fragments the other's room)
+            for lo, hi in reversed(busy):
+                if hi + sizes[i] <= top:
+                    break
+                top = min(top, lo)
+            if top - sizes[i] >= 0 and not any(lo < top and top - sizes[i] < hi for lo, hi in busy):
+                at = top - sizes[i]
+        if at + sizes[i] > KPU_RAM_UNITS:
+            raise KmodelError(f'kmodel: KPU RAM exhausted: a tensor of {sizes[i] * 64} bytes does not fit beside the '
+                              f'{sum(h - l for l, h in busy) * 64} bytes alive with it ({KPU_RAM_BYTES} bytes in all)')
+        addr[i] = at
+    return addr

@@ -1,0 +1,81 @@
+"""`make kmodel` - quantise a trained checkpoint to a K210 kmodel (the reference leaves this step to keras_freeze.py + nncase).
+
+    python make_kmodel.py CKPT OUT [network flags of keras_inference.py] (--calib LIST.npy | --synthetic N) [--calib_seed S]
+
+CKPT: a Keras `.h5` or `.npz` checkpoint; OUT: `.kmodel` or `.kfpkg`.  The calibration images are a list file as make_voc_list.py writes
+(data/<set>_img_ann.npy) or N generated images as `make train SYNTHETIC=N` trains on; they are decoded as the input pipeline decodes them
+(Helper._read_img) and letterboxed on the GPU (yk_letterbox_u8), then measured by quantize.Calibrator.  Prints the per-layer report and
+the file size."""
+from __future__ import annotations
+
+import argparse
+import sys
+import time
+
+import numpy as np
+
+from .helper import INFO, Helper, VOC_ANCHORS
+from .yolonet import MODEL_DEFS
+
+
+def calibration_frames(h: Helper, calib, synthetic: int, seed: int, class_num: int, limit: int = 0):
+    """Device uint8 [N, H, W, 3] at the network's input size."""
+    import torch
+    from . import engine
+    from .training import synthetic_list
+    in_hw = tuple(int(v) for v in h.in_hw[0])
+    if synthetic:
+        imgs = [it[0] for it in synthetic_list(int(synthetic), in_hw, class_num, seed)]
+    else:
+        rows = np.load(calib, allow_pickle=True)
+        order = np.random.default_rng(seed).permutation(len(rows))
+        if limit:
+            order = order[:limit]
+        imgs = [h._read_img(str(rows[i][0])) for i in order]
+    if not imgs:
+        raise engine.YkError('make_kmodel: no calibration images')
+    return torch.cat([engine.letterbox_u8(torch.from_numpy(np.ascontiguousarray(im[None, ..., :3], np.uint8)).cuda(), in_hw) for im in imgs])
+
+
+def main(ckpt, out, image_size, output_size, model_def, class_num, depth_multiplier, train_set, calib, synthetic, calib_seed, batch, limit=0):
+    from pathlib import Path
+    from . import quantize
+    anchor_file = Path(f'data/{train_set}_anchor.npy')
+    h = Helper(None, class_num, str(anchor_file) if anchor_file.exists() else VOC_ANCHORS, np.reshape(np.array(image_size), (-1, 2)),
+               np.reshape(np.array(output_size), (-1, 2)))
+    model, _ = MODEL_DEFS[model_def]([image_size[0], image_size[1], 3], len(h.anchors[0]), class_num, alpha=depth_multiplier)
+    model.load_weights(str(ckpt))
+    print(INFO, f' Load CKPT {ckpt}')
+    t0 = time.time()
+    frames = calibration_frames(h, calib, synthetic, calib_seed, class_num, limit)
+    report = model.save_kmodel(str(out), frames, batch=batch)
+    print(quantize.format_report(report))
+    print(INFO, f' {len(frames)} calibration images, {time.time() - t0:.2f} s')
+    print(INFO, f' wrote {out}: kmodel of {report["file_bytes"]} bytes')
+    return report
+
+
+def cli(argv=None):
+    p = argparse.ArgumentParser(description='quantise a checkpoint to a K210 kmodel, calibrated on the GPU')
+    p.add_argument('--train_set', type=str, help='trian file lists', default='voc')
+    p.add_argument('--class_num', type=int, help='trian class num', default=20)
+    p.add_argument('--model_def', type=str, help='Model definition.', default='yolo_mobilev1')
+    p.add_argument('--depth_multiplier', type=float, help='mobilenet depth_multiplier', choices=[0.5, 0.75, 1.0], default=0.75)
+    p.add_argument('--image_size', type=int, help='net work input image size', default=(224, 320), nargs='+')
+    p.add_argument('--output_size', type=int, help='net work output image size', default=(7, 10, 14, 20), nargs='+')
+    p.add_argument('--calib', type=str, default=None, help='calibration list file as make_voc_list.py writes (data/<set>_img_ann.npy)')
+    p.add_argument('--calib_limit', type=int, default=0, help='use at most this many images of --calib (0 = all)')
+    p.add_argument('--synthetic', type=int, default=0, help='calibrate on N generated images instead of --calib')
+    p.add_argument('--calib_seed', type=int, default=3, help='seed of the generated images / of the order --calib_limit samples in')
+    p.add_argument('--calib_batch', type=int, default=32, help='images per calibration forward pass')
+    p.add_argument('pre_ckpt', type=str, help='trained weights (.h5 / .npz)')
+    p.add_argument('output', type=str, help='.kmodel or .kfpkg to write')
+    a = p.parse_args(sys.argv[1:] if argv is None else argv)
+    if not a.calib and not a.synthetic:
+        p.error('give --calib LIST.npy or --synthetic N')
+    return main(a.pre_ckpt, a.output, a.image_size, a.output_size, a.model_def, a.class_num, a.depth_multiplier, a.train_set, a.calib,
+                a.synthetic, a.calib_seed, a.calib_batch, a.calib_limit)
+
+
+if __name__ == '__main__':
+    cli()

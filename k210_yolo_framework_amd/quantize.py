@@ -1,0 +1,495 @@
+"""Quantise a float checkpoint to a K210 kmodel (v3): the step the reference leaves to `keras_freeze.py` + nncase.
+
+    ranges = Calibrator(spec, weights, max_batch).feed(frames) ... .ranges()      GPU: the range of every tensor over the calibration set
+    km, report = quantize(spec, weights, ranges)                                   CPU, deterministic: KPU registers and tables
+    kmodel.write('yolo.kmodel', km)
+
+Conventions - exactly the ones `kmodel.to_float_weights` inverts and `oracle/kpu_ref.py` executes:
+  * one asymmetric uint8 (scale, zero point) per weight tensor and per activation tensor, real = scale * (q - zp);
+  * INTEGER zero points: a range is widened to contain 0 and zp = round(-min / scale), so real zero is exactly q = zp - zero padding is
+    pad_value = zp_x, and a pruned (exactly zero) weight is exactly zp_w;
+  * the input tensor is the raw pixel: scale 1/255, zero point 0;
+  * the zero-point terms are exact: arg_x = -zp_w << 15 with shr_x = 15, arg_w = -zp_x << 15 with shr_w = 15, arg_add = zp_x zp_w k^2, so
+    acc = sum((x - zp_x)(w - zp_w));
+  * BatchNorm per channel: the pre-activation in units of 2^-p output steps is  z = (acc * bn_mul >> bn_shift) + bn_add  with
+    bn_mul / 2^bn_shift = scale_c s_x s_w 2^p / s_y and bn_add = round(bias_c 2^p / s_y); every channel takes the largest shift (<= 15) that
+    keeps bn_mul inside its 24 bits, p = 10 unless a channel's multiplier needs fewer;
+  * the activation is a segment table over z with the kink at real zero (z = 0): slope 2^-p above it, alpha 2^-p below (LeakyReLU), 0 below
+    (ReLU), or one line (linear).  Below the calibrated minimum the table is flat at q = 0; above the calibrated maximum the KPU's own
+    clamp to 255 is the flat end (a segment bias is a signed byte and cannot hold 255; for the same reason a LeakyReLU tensor whose zero
+    point would exceed 127 has its range widened upward until it is 127);
+  * the two linear output convs carry their bias in bn_add; their DEQUANTIZE (scale s_y, bias -zp_y s_y) gives real logits.
+A range of zero width ([0, 0] after widening: a tensor that is constantly zero) gets scale 1/255 and zero point 0 - no division by zero, and
+the constant is represented exactly.
+
+The layer sequence is the demo's: KPU convs (a stride-2 depthwise conv runs at stride 1 and its 1x1 successor carries the
+`left_top_2_s2` pooling, as nncase emits it; a stride-2 full conv pools itself), KLF_MAIN_MEM_OUT where a tensor leaves the KPU,
+QUANTIZED_RESIZE_NN for `upsample`, one REQUANTIZE per `concat` input onto the union range, QUANTIZED_CONCAT + K210_UPLOAD, DEQUANTIZE
+for every network output.  What the KPU path cannot express raises `KmodelError` naming the op.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Dict, List, Optional, Tuple
+
+import numpy as np
+
+from . import kmodel as km_
+from . import netspec as ns
+from .kmodel import KmodelError
+
+FINE_BITS = 10                   # z counts 2^-10 output steps (what the demo's tables use: y_mul 1024 >> 20)
+ACT_MUL_BITS = 14                # the table's slope 2^-p is written as 2^14 >> (p + 14): alpha keeps 14 bits
+INPUT_SCALE = 1.0 / 255.0
+
+_OP_NAMES = {ns.OP_MAXPOOL: 'maxpool', ns.OP_UPSAMPLE: 'upsample', ns.OP_CONCAT: 'concat', ns.OP_ADD: 'add'}
+
+
+def tensor_names(spec: ns.NetSpec) -> List[str]:
+    """A name for every tensor of the spec: 'input', the layer name for a conv's output, '<op>_<n>' (n counts from 1 per op type) for
+    the others."""
+    names = ['?'] * len(spec.tensors)
+    names[0] = 'input'
+    seen: Dict[str, int] = {}
+    for op in spec.ops:
+        if op['type'] in (ns.OP_CONV, ns.OP_DWCONV):
+            names[op['out']] = op['layer']
+        else:
+            kind = _OP_NAMES[op['type']]
+            seen[kind] = seen.get(kind, 0) + 1
+            names[op['out']] = f'{kind}_{seen[kind]}'
+    return names
+
+
+def qparams(lo: float, hi: float) -> Tuple[float, int]:
+    """(scale, integer zero point) of the uint8 code for the range [lo, hi] widened to contain 0."""
+    lo, hi = float(lo), float(hi)
+    if not (np.isfinite(lo) and np.isfinite(hi)) or lo > hi:
+        raise KmodelError(f'quantize: range ({lo}, {hi}) is not a finite interval')
+    lo, hi = min(lo, 0.0), max(hi, 0.0)
+    if hi == lo:
+        return INPUT_SCALE, 0
+    scale = (hi - lo) / 255.0
+    return scale, int(min(255, max(0, round(-lo / scale))))
+
+
+def fold_bn(layer: ns.Layer, weights) -> Tuple[np.ndarray, np.ndarray]:
+    """Inference BatchNorm as float64 (scale, bias) per channel; a conv with bias and no BatchNorm: scale = 1."""
+    c = layer.kernel_shape[3] if layer.kind == 'conv' else layer.kernel_shape[2]
+    if layer.bn_name:
+        g, bt, mu, var = (np.asarray(weights[layer.bn_name + s], np.float64) for s in ('/gamma', '/beta', '/moving_mean', '/moving_variance'))
+        scale = g / np.sqrt(var + ns.BN_EPS)
+        return scale, bt - mu * scale
+    return np.ones(c), (np.asarray(weights[layer.name + '/bias'], np.float64) if layer.use_bias else np.zeros(c))
+
+
+def _consumers(spec: ns.NetSpec) -> Dict[int, List[int]]:
+    r: Dict[int, List[int]] = {}
+    for k, op in enumerate(spec.ops):
+        for key in ('in0', 'in1'):
+            if op.get(key, -1) is not None and op.get(key, -1) >= 0:
+                r.setdefault(op[key], []).append(k)
+    return r
+
+
+def plan_convs(spec: ns.NetSpec) -> Dict[int, dict]:
+    """The geometry of every conv op as the KPU runs it, {op index: dict(in_h, in_w, out_h, out_w, pool)}, and every refusal that needs
+    no weights.  KmodelError names the op the KPU path here cannot express."""
+    if not spec.ops or spec.ops[0]['type'] != ns.OP_CONV or spec.ops[0]['in0'] != 0 or spec.tensors[0][2] != 3:
+        raise KmodelError('quantize: the first layer must be a conv of the 3-channel frame')
+    readers = _consumers(spec)
+    hw: Dict[int, Tuple[int, int]] = {0: spec.tensors[0][:2]}                   # what the KPU holds for a tensor (full size when the pooling is deferred)
+    deferred = set()
+    plan: Dict[int, dict] = {}
+    for k, op in enumerate(spec.ops):
+        t = op['type']
+        if t in (ns.OP_ADD, ns.OP_MAXPOOL):
+            raise KmodelError(f"quantize: op {k} of {spec.name} is `{_OP_NAMES[t]}` on tensor {tensor_names(spec)[op['in0']]!r}: "
+                              f'the KPU path has no {_OP_NAMES[t]}')
+        if t in (ns.OP_UPSAMPLE, ns.OP_CONCAT):
+            hw[op['out']] = spec.tensors[op['out']][:2]
+            continue
+        name = op['layer']
+        if op['k'] not in (1, 3):
+            raise KmodelError(f"quantize: conv {name!r} has a {op['k']}x{op['k']} kernel (the KPU has 1x1 and 3x3)")
+        H, W = hw[op['in0']]
+        ci = spec.tensors[op['in0']][2]
+        pads = (op['pad_t'], op.get('pad_b', op['pad_t']), op['pad_l'], op.get('pad_r', op['pad_l']))
+        same = (op['k'] - 1) // 2
+        pool, oh, ow = km_.POOL_BYPASS, H, W
+        if op['in0'] in deferred:                                              # the 1x1 conv after a stride-2 depthwise conv
+            pool, oh, ow = km_.POOL_LEFT_TOP_2_S2, H // 2, W // 2
+        if op['stride'] == 2:
+            if op['k'] != 3 or pads != (1, 1, 1, 1) or H % 2 or W % 2:
+                raise KmodelError(f"quantize: conv {name!r} has stride 2 with kernel {op['k']}, padding {pads} on {H}x{W}: the KPU runs a "
+                                  f'stride-2 conv as a pad-1 3x3 conv + left_top_2_s2 pooling, i.e. padding (1, 1, 1, 1) on an even size')
+            nxt = [spec.ops[j] for j in readers.get(op['out'], [])]
+            if (t == ns.OP_DWCONV and len(nxt) == 1 and nxt[0]['type'] == ns.OP_CONV and nxt[0]['k'] == 1 and nxt[0]['stride'] == 1
+                    and op['out'] not in spec.outputs):
+                deferred.add(op['out'])                                        # full size here; the successor pools
+            else:
+                pool, oh, ow = km_.POOL_LEFT_TOP_2_S2, H // 2, W // 2
+        elif op['stride'] != 1 or pads != (same,) * 4:
+            raise KmodelError(f"quantize: conv {name!r} has stride {op['stride']} and padding {pads}: the KPU pads a {op['k']}x{op['k']} "
+                              f'conv by {same} on every side')
+        hw[op['out']] = (oh, ow) if op['out'] not in deferred else (H, W)
+        kh, kw = hw[op['out']]
+        co = spec.tensors[op['out']][2]
+        need = km_.kpu_tensor_units(ci, H, W) + km_.kpu_tensor_units(co, kh, kw)
+        if need > km_.KPU_RAM_UNITS:
+            raise KmodelError(f'quantize: conv {name!r} reads {ci}x{H}x{W} and writes {co}x{kh}x{kw}: {need * 64} bytes of KPU RAM, '
+                              f'{km_.KPU_RAM_BYTES} exist')
+        plan[k] = dict(in_h=H, in_w=W, out_h=kh, out_w=kw, pool=pool)
+    return plan
+
+
+def _act_table(act: int, alpha: float, zp_y: int, p: int):
+    """(start, mul, shift, bias) x 16 over z in 2^-p output steps, kink at z = 0."""
+    one, sh = 1 << ACT_MUL_BITS, p + ACT_MUL_BITS
+    far = -(1 << 35)
+    if act == ns.ACT_RELU:
+        segs = [(far, 0, 0, zp_y), (0, one, sh, zp_y)]
+    elif act == ns.ACT_LEAKY:
+        if not 0.0 < alpha <= 1.0:
+            raise KmodelError(f'quantize: LeakyReLU slope {alpha} outside (0, 1]')
+        a_mul = int(round(alpha * one))
+        z_lo = -int(round(zp_y * (1 << p) / (a_mul / one))) if a_mul else 0     # where the lower line reaches q = 0: the calibrated minimum
+        segs = [(far, 0, 0, 0), (z_lo, a_mul, sh, 0), (0, one, sh, zp_y)] if zp_y and a_mul else [(far, 0, 0, zp_y), (0, one, sh, zp_y)]
+    elif act == ns.ACT_NONE:
+        segs = [(far, 0, 0, 0), (-(zp_y << p), one, sh, 0)]                     # one line through (0, zp_y), started where it reaches q = 0
+    else:
+        raise KmodelError(f'quantize: activation code {act} (ReLU6) has no KPU table here')
+    top = (1 << 35) - 16
+    segs += [(top + k, 0, 0, 0) for k in range(16 - len(segs))]                 # unreachable, ascending, as nncase fills the rest
+    return tuple(np.array(col, np.int64) for col in zip(*segs))
+
+
+def quantize(spec: ns.NetSpec, weights: Dict[str, np.ndarray], ranges: Dict[str, Tuple[float, float]]):
+    """-> (kmodel.Kmodel, report).  `ranges`: {tensor name (tensor_names): (min, max)} of the calibration set, at least for the input-side
+    of every conv ('input' is fixed to the raw pixel and need not be given; upsample / concat outputs take their producers' ranges).
+    report['layers'][name] = scales, zero points, FINE_BITS used, the BatchNorm shifts chosen and the share of weights equal to the zero
+    point.  CPU only, deterministic."""
+    plan = plan_convs(spec)
+    names = tensor_names(spec)
+    lay = {l.name: l for l in spec.layers}
+    readers = _consumers(spec)
+    leaves = {t for t in range(len(spec.tensors))
+              if t in spec.outputs or any(spec.ops[j]['type'] in (ns.OP_UPSAMPLE, ns.OP_CONCAT) for j in readers.get(t, []))}
+    layers: List[object] = []
+    q: Dict[int, Tuple[float, int]] = {0: (INPUT_SCALE, 0)}
+    rng: Dict[int, Tuple[float, float]] = {0: (0.0, 1.0)}
+    kpu_of: Dict[int, int] = {}                                                # tensor -> KPU buffer
+    bufs: List[dict] = []                                                      # KPU buffers: units, birth, death (layer indices)
+    mem_of: Dict[int, int] = {}
+    mem_top = 0
+    out_entries: Dict[int, Tuple[int, int]] = {}
+    report = {'layers': {}, 'requant': []}
+
+    def mem_alloc(nbytes: int) -> int:
+        nonlocal mem_top
+        at = mem_top
+        mem_top += (nbytes + 7) // 8 * 8
+        return at
+
+    def new_buf(c, h, w, born):
+        bufs.append(dict(units=km_.kpu_tensor_units(c, h, w), birth=born, death=born))
+        return len(bufs) - 1
+
+    h0, w0, c0 = spec.tensors[0]
+    kpu_of[0] = new_buf(c0, plan[0]['in_h'], plan[0]['in_w'], 0)
+    for k, op in enumerate(spec.ops):
+        t = op['type']
+        idx = len(layers)
+        if t in (ns.OP_CONV, ns.OP_DWCONV):
+            l, g = lay[op['layer']], plan[k]
+            tin, tout = op['in0'], op['out']
+            if tin not in kpu_of:
+                raise KmodelError(f"quantize: conv {l.name!r} reads tensor {names[tin]!r}, which is not in KPU RAM")
+            if l.name not in ranges:
+                raise KmodelError(f'quantize: no calibrated range for tensor {l.name!r}')
+            dw = t == ns.OP_DWCONV
+            ci, co, kk = op['cin'], op['cout'], op['k'] * op['k']
+            s_x, zp_x = q[tin]
+            kern = np.asarray(weights[l.name + '/kernel'], np.float64)
+            s_w, zp_w = qparams(kern.min(), kern.max())
+            wq = np.clip(np.rint(kern / s_w) + zp_w, 0, 255).astype(np.uint8)
+            wq = (wq[..., 0].transpose(2, 0, 1).reshape(co, 1, kk) if dw else wq.transpose(3, 2, 0, 1).reshape(co, ci, kk))
+            lo, hi = (float(v) for v in ranges[l.name])
+            s_y, zp_y = qparams(lo, hi)
+            if op['act'] == ns.ACT_LEAKY and zp_y > 127:                        # the table holds the zero point in a signed byte (the kink's
+                s_y, zp_y = qparams(lo, -lo * 128.0 / 127.0)                    # result bias): widen the range upward until it fits
+            scale, bias = fold_bn(l, weights)
+            m = scale * (s_x * s_w / s_y)                                       # acc -> output steps
+            top = float(np.abs(m).max())
+            p = FINE_BITS if top == 0.0 else int(min(FINE_BITS, np.floor(np.log2(((1 << 23) - 1) / top))))
+            if p < 0:
+                raise KmodelError(f'quantize: conv {l.name!r}: a channel multiplies the accumulator by {top:.3g}, beyond the 24-bit bn_mul')
+            mf = m * float(1 << p)
+            with np.errstate(divide='ignore'):
+                shift = np.where(mf == 0.0, 15, np.floor(np.log2(((1 << 23) - 1) / np.maximum(np.abs(mf), 1e-300)))).clip(0, 15).astype(np.int64)
+            bn_mul = np.rint(mf * np.exp2(shift)).astype(np.int64)
+            over = np.abs(bn_mul) > (1 << 23) - 1                               # rounding pushed it past the field: one bit less
+            shift = np.where(over & (shift > 0), shift - 1, shift)
+            bn_mul = np.rint(mf * np.exp2(shift)).astype(np.int64)
+            bn_add = np.rint(bias / s_y * float(1 << p)).astype(np.int64)
+            a_start, a_mul, a_shift, a_bias = _act_table(op['act'], float(op['alpha']), zp_y, p)
+            dst = new_buf(co, g['out_h'], g['out_w'], idx)
+            bufs[kpu_of[tin]]['death'] = idx
+            flags, mm_out = 0, 0
+            if tout in leaves:
+                flags, mm_out = km_.KLF_MAIN_MEM_OUT, mem_alloc(co * g['out_h'] * g['out_w'])
+                mem_of[tout] = mm_out
+            c = km_.ConvLayer(idx, flags, mm_out, kpu_of[tin], dst, ci, co, g['in_w'], g['in_h'], g['out_w'], g['out_h'], op['k'], g['pool'], zp_x, dw,
+                              15 if zp_x else 0, 15, -(zp_x << 15), -(zp_w << 15), zp_x * zp_w * kk, wq, bn_mul, bn_add, shift,
+                              a_start, a_mul, a_shift, a_bias)
+            layers.append(c)
+            kpu_of[tout], q[tout], rng[tout] = dst, (s_y, zp_y), (-zp_y * s_y, (255 - zp_y) * s_y)
+            report['layers'][l.name] = dict(index=idx, s_x=s_x, zp_x=zp_x, s_w=s_w, zp_w=zp_w, s_y=s_y, zp_y=zp_y, fine_bits=p, pool=g['pool'],
+                                            bn_shift=(int(shift.min()), int(shift.max())), zero_share=float((wq == zp_w).mean()),
+                                            range=(lo, hi))
+            if tout in spec.outputs:
+                n = co * g['out_h'] * g['out_w']
+                d = mem_alloc(4 * n)
+                layers.append(km_.MemLayer(len(layers), km_.KL_DEQUANTIZE, dict(flags=1, src=mm_out, dst=d, count=n,
+                                                                                scale=float(np.float32(s_y)), bias=float(np.float32(-zp_y * s_y)))))
+                out_entries[tout] = (d, 4 * n)
+        elif t == ns.OP_UPSAMPLE:
+            tin, tout = op['in0'], op['out']
+            if tin not in mem_of:
+                raise KmodelError(f'quantize: upsample reads tensor {names[tin]!r}, which is not in main memory')
+            h, w, c = spec.tensors[tin]
+            oh, ow, _ = spec.tensors[tout]
+            d = mem_alloc(c * oh * ow)
+            layers.append(km_.MemLayer(idx, km_.KL_QUANTIZED_RESIZE_NN, dict(flags=0, src=mem_of[tin], dst=d, in_w=w, in_h=h, channels=c, out_w=ow,
+                                                                             out_h=oh, align=0)))
+            mem_of[tout], q[tout], rng[tout] = d, q[tin], rng[tin]
+        else:                                                                  # concat
+            parts, tout = (op['in0'], op['in1']), op['out']
+            for tin in parts:
+                if tin not in mem_of:
+                    raise KmodelError(f'quantize: concat reads tensor {names[tin]!r}, which is not in main memory')
+            lo, hi = min(rng[tin][0] for tin in parts), max(rng[tin][1] for tin in parts)
+            s_u, zp_u = qparams(lo, hi)
+            ins = []
+            for tin in parts:
+                h, w, c = spec.tensors[tin]
+                s_i, zp_i = q[tin]
+                table = np.clip(np.rint((np.arange(256) - zp_i) * (s_i / s_u)) + zp_u, 0, 255).astype(np.uint8)
+                d = mem_alloc(c * h * w)
+                layers.append(km_.MemLayer(len(layers), km_.KL_REQUANTIZE, dict(flags=1, src=mem_of[tin], dst=d, count=c * h * w, table=table)))
+                ins.append((d, c * h * w))
+                report['requant'].append(dict(tensor=names[tin], factor=s_i / s_u, zp_in=zp_i, zp_out=zp_u))
+            h, w, c = spec.tensors[tout]
+            d = mem_alloc(c * h * w)
+            layers.append(km_.MemLayer(len(layers), km_.KL_QUANTIZED_CONCAT, dict(flags=1, dst=d, inputs=ins)))
+            up = new_buf(c, h, w, len(layers))
+            layers.append(km_.MemLayer(len(layers), km_.KL_K210_UPLOAD, dict(flags=0, src=d, kpu_addr=up, width=w, height=h, channels=c)))
+            kpu_of[tout], mem_of[tout], q[tout], rng[tout] = up, d, (s_u, zp_u), (-zp_u * s_u, (255 - zp_u) * s_u)
+    addr = km_.allocate_kpu_ram([b['units'] for b in bufs], [b['birth'] for b in bufs], [b['death'] for b in bufs])
+    for l in layers:
+        if isinstance(l, km_.ConvLayer):
+            l.src_addr, l.dst_addr = addr[l.src_addr], addr[l.dst_addr]
+            km_.conv_registers(l)                                              # every field inside its width, or KmodelError
+        elif l.type == km_.KL_K210_UPLOAD:
+            l.fields['kpu_addr'] = addr[l.fields['kpu_addr']]
+    missing = [names[o] for o in spec.outputs if o not in out_entries]
+    if missing:
+        raise KmodelError(f'quantize: network outputs {missing} are not conv outputs')
+    model = km_.Kmodel(3, 0, [out_entries[o] for o in spec.outputs], layers)
+    model.main_mem_usage = km_.main_mem_usage(model)
+    km_.serialise(model)                                                       # the table fields too
+    report['main_mem_usage'] = model.main_mem_usage
+    report['kpu_ram_peak'] = max(a + b['units'] for a, b in zip(addr, bufs)) * 64
+    return model, report
+
+
+def format_report(report: dict) -> str:
+    rows = [f"{'layer':<14}{'s_x':>11}{'zp_x':>5}{'s_w':>11}{'zp_w':>5}{'s_y':>11}{'zp_y':>5}{'p':>3}{'shift':>7}{'pool':>5}{'w==zp':>8}"]
+    for name, r in report['layers'].items():
+        rows.append(f"{name:<14}{r['s_x']:>11.4g}{r['zp_x']:>5}{r['s_w']:>11.4g}{r['zp_w']:>5}{r['s_y']:>11.4g}{r['zp_y']:>5}{r['fine_bits']:>3}"
+                    f"{r['bn_shift'][0]:>4}-{r['bn_shift'][1]:<2}{r['pool']:>5}{100.0 * r['zero_share']:>7.2f}%")
+    for r in report['requant']:
+        rows.append(f"requantize {r['tensor']}: x{r['factor']:.4f}, zero point {r['zp_in']} -> {r['zp_out']}")
+    rows.append(f"main memory {report['main_mem_usage']} bytes, KPU RAM peak {report['kpu_ram_peak']} bytes")
+    return '\n'.join(rows)
+
+
+# ---- calibration on the GPU -------------------------------------------------------------------------------------------------------------
+class Calibrator:
+    """The range of every tensor of `spec` over a calibration set, measured by an fp32 forward pass on the GPU.
+
+    The pass walks the spec as train.Trainer.forward does, one device tensor per spec tensor.  Convolutions are the fp32 forward kernels of
+    the training step (yk_gemm_f32 for 1x1, yk_conv3x3_bn_fwd_f32 without BatchNorm / yk_im2col3x3_f32 + yk_gemm_f32 for 3x3,
+    yk_dw3x3_fwd_f32 for depthwise); inference BatchNorm (folded to scale / bias on the host) + activation + the min / max reduction are
+    ONE launch of yk_scale_act_range_f32 (csrc/yk_calib.hip), so no tensor is read a second time for its range and none crosses to the host:
+    `ranges()` copies 2 floats + a flag per tensor.
+
+    `feed` normalises the uint8 frames by 255 - what the KPU sees (raw pixels, scale 1/255) - NOT by each image's own maximum as the float
+    inference modes do (tools/utils.py:405).  `feed` may be called any number of times; ranges accumulate (min / max are exact and
+    order-free, so the result does not depend on how the set is split into batches)."""
+
+    def __init__(self, spec: ns.NetSpec, weights: Dict[str, np.ndarray], max_batch: int = 32, device: int = 0):
+        import torch
+        from . import engine
+        engine.require_gpu()
+        self.torch, self.engine, self.L = torch, engine, engine.lib()
+        self.spec, self.max_batch = spec, int(max_batch)
+        self.dev = torch.device('cuda', device)
+        self.names = tensor_names(spec)
+        self.lay = {l.name: l for l in spec.layers}
+        for k, op in enumerate(spec.ops):
+            if op['type'] in (ns.OP_ADD, ns.OP_MAXPOOL):
+                raise engine.YkError(f"Calibrator: op {k} of {spec.name} is `{_OP_NAMES[op['type']]}`, which the quantiser does not take")
+            if op['type'] == ns.OP_CONV and not ((op['k'] == 1 and op['stride'] == 1) or op['k'] == 3):
+                raise engine.YkError(f"Calibrator: conv {op['layer']!r}: kernel {op['k']} stride {op['stride']} has no fp32 forward kernel")
+        dev = self.dev
+        self.P: Dict[str, "torch.Tensor"] = {}
+        for l in spec.layers:
+            k = np.asarray(weights[l.name + '/kernel'], np.float32)
+            k = np.transpose(k, (3, 0, 1, 2)).reshape(l.kernel_shape[3], -1) if l.kind == 'conv' else k[..., 0].reshape(9, -1)
+            scale, bias = fold_bn(l, weights)
+            self.P[l.name + '/w'] = torch.from_numpy(np.ascontiguousarray(k)).to(dev)
+            self.P[l.name + '/scale'] = torch.from_numpy(scale.astype(np.float32)).to(dev)
+            self.P[l.name + '/bias'] = torch.from_numpy(bias.astype(np.float32)).to(dev)
+        self.P['input/scale'] = torch.full((3,), np.float32(INPUT_SCALE), dtype=torch.float32, device=dev)
+        self.P['input/bias'] = torch.zeros(3, dtype=torch.float32, device=dev)
+        self.n_slots = len(spec.tensors)
+        self.d_range = torch.zeros(self.n_slots * 4, dtype=torch.int32, device=dev)                      # YK_RANGE_WORDS per slot
+        self._last_use = {}
+        for k, op in enumerate(spec.ops):
+            for key in ('in0', 'in1'):
+                if op.get(key, -1) is not None and op.get(key, -1) >= 0:
+                    self._last_use[op[key]] = k
+        self.images = 0
+        self.reset()
+
+    def _s(self):
+        return C.c_void_p(self.torch.cuda.current_stream().cuda_stream)
+
+    def reset(self) -> None:
+        self.engine._check(self.L.yk_range_reset(self.engine._ptr(self.d_range), C.c_int(self.n_slots), self._s()), 'yk_range_reset')
+        self.images = 0
+
+    def _epilogue(self, z, M, Cn, scale, bias, act, alpha, y, slot):
+        p = self.engine._ptr
+        self.engine._check(self.L.yk_scale_act_range_f32(p(z), C.c_longlong(M), C.c_int(Cn), p(scale), p(bias), C.c_int(act), C.c_float(alpha), p(y),
+                                                         p(self.d_range), C.c_int(slot), self._s()), 'yk_scale_act_range_f32')
+
+    def _range(self, x, slot):
+        self.engine._check(self.L.yk_range_f32(self.engine._ptr(x), C.c_longlong(x.numel()), self.engine._ptr(self.d_range), C.c_int(slot), self._s()),
+                           'yk_range_f32')
+
+    def feed(self, frames_u8, keep=None) -> "Calibrator":
+        """frames_u8: device uint8 [B, H, W, 3], B <= max_batch, H x W = the spec's input size.  `keep`: a dict that receives every tensor
+        {name: device fp32 NHWC} of this batch (tests)."""
+        torch, eng, L, p = self.torch, self.engine, self.L, self.engine._ptr
+        H, W = self.spec.in_hw
+        if not (frames_u8.is_cuda and frames_u8.dtype == torch.uint8 and frames_u8.dim() == 4 and tuple(frames_u8.shape[1:]) == (H, W, 3)):
+            raise eng.YkError(f'Calibrator.feed takes device uint8 frames [B, {H}, {W}, 3]')
+        B = int(frames_u8.shape[0])
+        if not 1 <= B <= self.max_batch:
+            raise eng.YkError(f'Calibrator.feed: {B} frames, max_batch is {self.max_batch}')
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=self.dev)            # noqa: E731
+        raw = frames_u8.contiguous().to(torch.float32)                                           # 0..255, exact
+        x = new(B, H, W, 3)
+        self._epilogue(raw, B * H * W, 3, self.P['input/scale'], self.P['input/bias'], ns.ACT_NONE, 0.0, x, 0)
+        T = {0: x}
+        for i, op in enumerate(self.spec.ops):
+            x, t = T[op['in0']], op['type']
+            ho, wo, co = self.spec.tensors[op['out']]
+            hi, wi, ci = self.spec.tensors[op['in0']]
+            M = B * ho * wo
+            if t in (ns.OP_CONV, ns.OP_DWCONV):
+                name = op['layer']
+                w = self.P[name + '/w']
+                geom = [C.c_int(v) for v in (B, hi, wi, ci, ho, wo, op['stride'], op['pad_t'], op['pad_l'])]
+                z = new(B, ho, wo, co)
+                if t == ns.OP_DWCONV:
+                    eng._check(L.yk_dw3x3_fwd_f32(p(x), p(w), *geom, p(z), self._s()), 'yk_dw3x3_fwd_f32')
+                elif op['k'] == 1:
+                    eng._check(L.yk_gemm_f32(C.c_int(0), C.c_int(1), C.c_int(M), C.c_int(co), C.c_int(ci), C.c_float(1.0), p(x), C.c_int(ci), p(w),
+                                             C.c_int(ci), C.c_float(0.0), p(z), C.c_int(co), self._s()), 'yk_gemm_f32')
+                elif ci % 4 == 0:
+                    eng._check(L.yk_conv3x3_bn_fwd_f32(p(x), p(w), *geom, C.c_int(co), p(z), None, None, C.c_float(0.0), C.c_int(0), C.c_float(0.0),
+                                                       None, None, None, None, None, C.c_float(0.0), None, self._s()), 'yk_conv3x3_bn_fwd_f32')
+                else:
+                    col = new(M, 9 * ci)
+                    eng._check(L.yk_im2col3x3_f32(p(x), *geom, p(col), self._s()), 'yk_im2col3x3_f32')
+                    eng._check(L.yk_gemm_f32(C.c_int(0), C.c_int(1), C.c_int(M), C.c_int(co), C.c_int(9 * ci), C.c_float(1.0), p(col), C.c_int(9 * ci),
+                                             p(w), C.c_int(9 * ci), C.c_float(0.0), p(z), C.c_int(co), self._s()), 'yk_gemm_f32')
+                    del col
+                y = new(B, ho, wo, co)
+                self._epilogue(z, M, co, self.P[name + '/scale'], self.P[name + '/bias'], op['act'], float(op['alpha']), y, op['out'])
+            else:
+                if t == ns.OP_UPSAMPLE:                                                          # nearest x2: pure data movement
+                    y = x.repeat_interleave(2, dim=1).repeat_interleave(2, dim=2).contiguous()
+                else:
+                    y = torch.cat([x, T[op['in1']]], dim=3)
+                self._range(y, op['out'])
+            T[op['out']] = y
+            if keep is None:
+                for key in ('in0', 'in1'):
+                    tid = op.get(key, -1)
+                    if tid is not None and tid >= 0 and self._last_use.get(tid) == i and tid not in self.spec.outputs:
+                        T.pop(tid, None)
+        if keep is not None:
+            keep.update({self.names[tid]: v for tid, v in T.items()})
+        self.images += B
+        return self
+
+    def read(self):
+        """(min, max, flags) as numpy arrays over the spec's tensors: one device-to-host copy."""
+        lo = np.empty(self.n_slots, np.float32)
+        hi = np.empty(self.n_slots, np.float32)
+        fl = np.empty(self.n_slots, np.int32)
+        self.torch.cuda.current_stream().synchronize()
+        self.engine._check(self.L.yk_range_read(self.engine._ptr(self.d_range), C.c_int(self.n_slots), lo.ctypes.data_as(C.c_void_p),
+                                                hi.ctypes.data_as(C.c_void_p), fl.ctypes.data_as(C.c_void_p)), 'yk_range_read')
+        return lo, hi, fl
+
+    def ranges(self) -> Dict[str, Tuple[float, float]]:
+        """{tensor name: (min, max)} over everything fed so far.  YkError naming the layer when a tensor held a NaN or an infinity."""
+        if not self.images:
+            raise self.engine.YkError('Calibrator.ranges: nothing has been fed')
+        lo, hi, fl = self.read()
+        bad = [self.names[i] for i in range(self.n_slots) if fl[i]]
+        if bad:
+            raise self.engine.YkError(f'Calibrator: non-finite values (NaN or infinity) in tensor(s) {", ".join(bad)}: the weights or the frames '
+                                      f'are broken; no range is defined')
+        return {self.names[i]: (float(lo[i]), float(hi[i])) for i in range(self.n_slots)}
+
+
+def synthetic_frames(n: int, in_hw, seed: int) -> np.ndarray:
+    """`n` generated calibration frames, uint8 [n, H, W, 3], every one with maximum 255 (so the float modes, which divide by the image's
+    maximum, and the KPU see the same input): smooth random colour fields with rectangles, the kind of picture `make train SYNTHETIC=`
+    trains on."""
+    H, W = in_hw
+    rng = np.random.default_rng(seed)
+    out = np.empty((n, H, W, 3), np.uint8)
+    yy, xx = np.mgrid[0:H, 0:W].astype(np.float32)
+    for i in range(n):
+        img = np.zeros((H, W, 3), np.float32)
+        for c in range(3):
+            fx, fy, ph = rng.uniform(0.5, 6.0), rng.uniform(0.5, 6.0), rng.uniform(0, 2 * np.pi)
+            img[..., c] = 0.5 + 0.5 * np.sin(2 * np.pi * (fx * xx / W + fy * yy / H) + ph)
+        img *= rng.uniform(0.3, 1.0, 3).astype(np.float32)
+        for _ in range(int(rng.integers(1, 6))):
+            h, w = int(rng.integers(H // 8, H // 2)), int(rng.integers(W // 8, W // 2))
+            y0, x0 = int(rng.integers(0, H - h)), int(rng.integers(0, W - w))
+            img[y0:y0 + h, x0:x0 + w] = rng.uniform(0, 1, 3).astype(np.float32)
+        img += rng.normal(0, 0.03, img.shape).astype(np.float32)
+        img = np.clip(img, 0, 1)
+        img /= max(float(img.max()), 1e-6)
+        u8 = np.rint(img * 255).astype(np.uint8)
+        u8[tuple(int(v) for v in np.unravel_index(int(np.argmax(u8)), u8.shape))] = 255
+        out[i] = u8
+    return out
+
+
+def calibrate(spec: ns.NetSpec, weights, frames_u8: np.ndarray, batch: int = 32) -> Dict[str, Tuple[float, float]]:
+    """Ranges of `frames_u8` (host uint8 [N, H, W, 3]) in batches of `batch`."""
+    import torch
+    cal = Calibrator(spec, weights, max_batch=batch)
+    for i in range(0, len(frames_u8), batch):
+        cal.feed(torch.from_numpy(np.ascontiguousarray(frames_u8[i:i + batch])).cuda())
+    return cal.ranges()

@@ -75,8 +75,8 @@ class YoloModel:
         self._drop_plan()
 
     def load_weights(self, path: str, by_name: bool = False) -> None:
-        """keras_inference.py:80 / keras_train.py:52-57.  `.h5`/`.hdf5`: a Keras weight or full-model file; `.kmodel`/`.kfpkg`: the
-        K210 demo's quantised yolo_mobilev1-0.75 (kmodel.py); otherwise `.npz`.
+        """keras_inference.py:80 / keras_train.py:52-57.  `.h5`/`.hdf5`: a Keras weight or full-model file; `.kmodel`/`.kfpkg`: a
+        quantised yolo_mobilev1 - the K210 demo's, or one `save_kmodel` / `make kmodel` wrote for this network (kmodel.py); otherwise `.npz`.
         by_name=True accepts a file that covers only part of the network (backbone pre-train files, yolonet.py:16-21)."""
         path = str(path)
         if path.endswith(('.h5', '.hdf5', '.keras')):
@@ -89,7 +89,7 @@ class YoloModel:
             from . import kmodel
             data = kmodel.read_kfpkg(path) if path.endswith('.kfpkg') else open(path, 'rb').read()
             km = kmodel.parse(data)
-            w, self.last_load_report = kmodel.to_float_weights(km)
+            w, self.last_load_report = kmodel.to_float_weights(km, self.spec if self.spec.name == 'yolo_mobilev1' else None)
             self.set_weights(w)
             self._s['kmodel'] = km                   # kept beside its float weights: precision='kpu' runs it as the board does
             return
@@ -114,6 +114,36 @@ class YoloModel:
             keras_io.save_keras_weights(self.spec, self._s['weights'], path)
         else:
             np.savez(path, **self._s['weights'])
+
+    def save_kmodel(self, path: str, calibration_frames, batch: int = 32):
+        """Quantise these weights to a K210 kmodel (quantize.py) and write it: `.kmodel`, or `.kfpkg` (model + flash list, no
+        firmware).  calibration_frames: uint8 [N, H, W, 3] at the network's input size (host numpy or a device tensor); their tensor ranges
+        are measured on the GPU in batches of `batch`, from the raw pixels / 255 as the KPU sees them.  The new Kmodel is kept beside the
+        float weights, so precision='kpu' runs it on this object without reloading.  Returns the quantiser's report (also
+        `last_quantize_report`).  A network the KPU path cannot express raises YkError with the quantiser's reason."""
+        import torch
+        from . import engine, kmodel, quantize
+        try:
+            quantize.plan_convs(self.spec)                       # refuse before any GPU work
+        except kmodel.KmodelError as e:
+            raise engine.YkError(f'save_kmodel: {e}') from e
+        frames = calibration_frames if torch.is_tensor(calibration_frames) else torch.from_numpy(np.ascontiguousarray(calibration_frames))
+        if frames.dtype != torch.uint8 or frames.dim() != 4 or len(frames) == 0:
+            raise engine.YkError('save_kmodel: calibration_frames must be uint8 [N, H, W, 3], N >= 1')
+        cal = quantize.Calibrator(self.spec, self._s['weights'], max_batch=max(1, min(int(batch), len(frames))))
+        for i in range(0, len(frames), cal.max_batch):
+            cal.feed(frames[i:i + cal.max_batch].cuda())
+        try:
+            km, report = quantize.quantize(self.spec, self._s['weights'], cal.ranges())
+            report['file_bytes'] = kmodel.write(path, km)
+        except kmodel.KmodelError as e:
+            raise engine.YkError(f'save_kmodel: {e}') from e
+        self._s['kmodel'] = km
+        self._s.pop('kpu_program', None)
+        if self.precision == 'kpu':
+            self._drop_plan()
+        self.last_quantize_report = report
+        return report
 
     def _drop_plan(self):
         p = self._s.pop('plan', None)
