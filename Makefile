@@ -7,7 +7,9 @@
 #   make inference   MODEL=... DEPTHMUL=... CKPT=weights.h5|.npz IMG=picture.jpg
 #   make train       MODEL=... DEPTHMUL=... BATCH=16 MAXEP=10 [SYNTHETIC=256]
 #                    [PRUNE=True INITSPARSITY=0.5 FINALSPARSITY=0.9 END_EPOCH=5 FREQUENCY=100]: magnitude pruning, saves yolo_prune_model.h5
+#                    [QAT=True QATMOMENTUM=0.99 QATOBSERVE=8]: quantisation-aware fine-tuning, saves yolo_qat_model.h5 + yolo_qat_ranges.npz
 #   make kmodel      CKPT=yolo_model.h5 OUT=yolo.kmodel|.kfpkg [SYNTHETIC=256 | CALIB=data/voc_img_ann.npy]: 8-bit K210 model, calibrated on the GPU
+#                    [RANGES=yolo_qat_ranges.npz]: the ranges a QAT run learned instead of a calibration
 #   make anchors     DATASET=voc ANCNUM=3 [LOW='0.0 0.0' HIGH='1.0 1.0']   (reference Makefile:78-87: k-means anchors from data/<set>_img_ann.npy)
 
 PY            ?= python3
@@ -37,9 +39,13 @@ FINALSPARSITY ?= 0.9
 END_EPOCH     ?= 5
 FREQUENCY     ?= 100
 SYNTHETIC     ?= 0
+QAT           ?= False
+QATMOMENTUM   ?= 0.99
+QATOBSERVE    ?= 8
 # kmodel only
 OUT           ?= yolo.kmodel
 CALIB         ?= data/$(DATASET)_img_ann.npy
+RANGES        ?=
 GPUS          ?= 1
 # anchors only (reference Makefile:27-29)
 ANCNUM        ?= 3
@@ -52,7 +58,8 @@ TRAIN_ARGS = --pre_ckpt $(CKPT) --augmenter $(IAA) --batch_size $(BATCH) --rand_
              --init_learning_rate $(ILR) --learning_rate_decay_factor $(LRDECAYFACTOR) --obj_weight $(OBJWEIGHT) \
              --noobj_weight $(NOOBJWEIGHT) --wh_weight $(WHWEIGHT) --vaildation_split $(SPLITFACTOR) --log_dir log \
              --is_prune $(PRUNE) --prune_initial_sparsity $(INITSPARSITY) --prune_final_sparsity $(FINALSPARSITY) \
-             --prune_end_epoch $(END_EPOCH) --prune_frequency $(FREQUENCY) --synthetic $(SYNTHETIC)
+             --prune_end_epoch $(END_EPOCH) --prune_frequency $(FREQUENCY) --synthetic $(SYNTHETIC) \
+             --qat $(QAT) --qat_momentum $(QATMOMENTUM) --qat_observe $(QATOBSERVE)
 ifeq ($(GPUS),1)
 LAUNCH = $(PY)
 else
@@ -81,7 +88,7 @@ train:
 # the step the reference leaves to keras_freeze.py + nncase: CKPT -> 8-bit kmodel; SYNTHETIC=N calibrates on generated images
 kmodel:
 	$(PY) make_kmodel.py $(CKPT) $(OUT) --train_set $(DATASET) --class_num $(CLSNUM) --model_def $(MODEL) --depth_multiplier $(DEPTHMUL) \
-		--image_size $(IMGSIZE) --output_size $(OUTSIZE) $(if $(filter-out 0,$(SYNTHETIC)),--synthetic $(SYNTHETIC),--calib $(CALIB))
+		--image_size $(IMGSIZE) --output_size $(OUTSIZE) $(if $(RANGES),--ranges $(RANGES),$(if $(filter-out 0,$(SYNTHETIC)),--synthetic $(SYNTHETIC),--calib $(CALIB)))
 
 # reference Makefile:78-87 (same flags; --is_random True as there)
 anchors:

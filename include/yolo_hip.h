@@ -458,6 +458,38 @@ int yk_scale_act_range_f32(const float *z, long long M, int C, const float *scal
                            uint32_t *d_range, int slot, void *stream);
 int yk_range_read(const uint32_t *d_range, int n_slots, float *h_min, float *h_max, int *h_flags);
 
+/* ---- quantisation-aware training (train.Trainer(qat=...)): the kmodel's uint8 codes simulated in fp32 inside the step.
+ * The rule, quantize.qparams in fp32 with one rounding per operation (no FMA contraction), for a range (lo, hi):
+ *   lo' = lo < 0 ? lo : +0, hi' = hi > 0 ? hi : +0;  hi' == lo': s = 1.0f / 255.0f, zp = 0;  else s = (hi' - lo') / 255.0f,
+ *   zp = clamp(rintf((0 - lo') / s), 0, 255);  u = rintf(x / s) + zp, q = clamp(u, 0, 255), fq(x) = s * (q - zp).
+ * fq(+-0) is +0.0 for every range; a NaN stays a NaN.  Straight-through gradient: 1 where 0 <= u <= 255, else 0.
+ * All calls are asynchronous on `stream` and capturable (no allocation, no host synchronisation); bad arguments: YK_ERR_ARG.  16-byte
+ * accesses where the pointers of a call share their position inside 16 bytes, scalar heads and tails; any n >= 1.
+ * Tables: d_ranges = float [n_slots][2] (lo, hi; "nothing seen yet" is (+inf, -inf)); d_batch / d_wrange = uint32 [.][YK_RANGE_WORDS] in the
+ * layout of yk_range_f32 (ordered keys + sticky non-finite flag).
+ * yk_qat_weights_f32  segments s = params[d_offset[s] .. + d_size[s]) (device int64, d_size >= 1, inside [0, n)), tiles of YK_QAT_TILE
+ *                     elements as yk_prune_masks_f32 takes them (d_tile_first [nseg + 1] = running sum of ceil(d_size / YK_QAT_TILE), ntiles
+ *                     = its last entry).  params_q = params over all n elements, then every segment replaced by fq over ITS OWN exact
+ *                     [min, max] (left in d_wrange[s]; no weight is ever clamped).  params is only read.  Three launches.
+ * yk_qat_act_fwd_f32  yq = fq(y) over d_ranges[slot]; min / max of the UNQUANTISED finite y folded into d_batch[slot], a NaN or an infinity
+ *                     sets that slot's flag instead.
+ * yk_qat_act_bwd_f32  dy = dyq where 0 <= u(y) <= 255 over d_ranges[slot], else +0.0.  dy may be dyq (in place).
+ * yk_qat_update_f32   one launch for all slots.  d_kind[i] == YK_QAT_SLOT_OWNER and the batch saw something finite:
+ *                     r = momentum * r + one_minus_momentum * b for lo and hi (b = the decoded batch extreme), or with `observe`
+ *                     r = (min(r_lo, b_lo), max(r_hi, b_hi)).  Every slot's batch extremes are reset afterwards (flags stay).  Then, in
+ *                     ascending order, d_kind[i] == YK_QAT_SLOT_UNION: r = (min of lo, max of hi) of slots d_part0[i], d_part1[i] (< i). */
+#define YK_QAT_TILE 4096
+#define YK_QAT_SLOT_NONE 0
+#define YK_QAT_SLOT_OWNER 1
+#define YK_QAT_SLOT_UNION 2
+int yk_qat_tile(void); /* YK_QAT_TILE of the loaded library */
+int yk_qat_weights_f32(const float *params, long long n, const long long *d_offset, const long long *d_size, const int *d_tile_first, int nseg,
+                       int ntiles, float *params_q, uint32_t *d_wrange, void *stream);
+int yk_qat_act_fwd_f32(const float *y, long long n, const float *d_ranges, int slot, float *yq, uint32_t *d_batch, void *stream);
+int yk_qat_act_bwd_f32(const float *dyq, const float *y, long long n, const float *d_ranges, int slot, float *dy, void *stream);
+int yk_qat_update_f32(float *d_ranges, uint32_t *d_batch, const int *d_kind, const int *d_part0, const int *d_part1, int n_slots, float momentum,
+                      float one_minus_momentum, int observe, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

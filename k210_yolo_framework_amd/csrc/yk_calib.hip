@@ -9,61 +9,11 @@
 //
 // Per launch: grid-stride loop with 16-byte loads (and stores), wave reduction in registers (__shfl_xor), block reduction through 2 x 4
 // words of LDS, then ONE atomicMin and ONE atomicMax per workgroup (vector atomics on global memory), and an atomicOr only from a
-// workgroup that met a non-finite value.
-#include "yk_common.h"
+// workgroup that met a non-finite value.  The key, the accumulator and the workgroup fold live in yk_range.h (yk_qat.hip shares them).
+#include "yk_range.h"
 
 namespace {
-
-constexpr int CAL_BLOCK = 256;
-constexpr int CAL_WAVES = CAL_BLOCK / YK_WAVE;
-constexpr unsigned CAL_MAX_GRID = 2048;                  // 8 workgroups per CU: enough in flight to stream from HBM
-
-__device__ __forceinline__ uint32_t key_of(uint32_t b) { return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u); }
-
-struct Acc {
-    uint32_t lo = 0xFFFFFFFFu, hi = 0u, bad = 0u;
-    __device__ __forceinline__ void add(float v) {
-        const uint32_t b = __float_as_uint(v);
-        if ((b & 0x7F800000u) == 0x7F800000u) {          // inf or NaN
-            bad = 1u;
-            return;
-        }
-        const uint32_t k = key_of(b);
-        lo = k < lo ? k : lo;
-        hi = k > hi ? k : hi;
-    }
-};
-
-// the workgroup's result into the slot: one atomicMin + one atomicMax
-__device__ __forceinline__ void fold(Acc a, uint32_t *slot) {
-    __shared__ uint32_t s_lo[CAL_WAVES], s_hi[CAL_WAVES], s_bad[CAL_WAVES];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const uint32_t l = __shfl_xor(a.lo, o, 64), h = __shfl_xor(a.hi, o, 64), f = __shfl_xor(a.bad, o, 64);
-        a.lo = l < a.lo ? l : a.lo;
-        a.hi = h > a.hi ? h : a.hi;
-        a.bad |= f;
-    }
-    const int wave = threadIdx.x / YK_WAVE;
-    if ((threadIdx.x & (YK_WAVE - 1)) == 0) {
-        s_lo[wave] = a.lo;
-        s_hi[wave] = a.hi;
-        s_bad[wave] = a.bad;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t lo = s_lo[0], hi = s_hi[0], bad = s_bad[0];
-#pragma unroll
-        for (int w = 1; w < CAL_WAVES; ++w) {
-            lo = s_lo[w] < lo ? s_lo[w] : lo;
-            hi = s_hi[w] > hi ? s_hi[w] : hi;
-            bad |= s_bad[w];
-        }
-        atomicMin(slot + 0, lo);
-        atomicMax(slot + 1, hi);
-        if (bad) atomicOr(slot + 2, 1u);
-    }
-}
+using namespace yk_range;
 
 __device__ __forceinline__ float c_act(float v, int act, float alpha) {      // as t_act of yk_train.hip
     if (act == YK_ACT_RELU) return v > 0.f ? v : 0.f;
@@ -140,13 +90,8 @@ __global__ void range_reset_kernel(uint32_t *r, int n_slots) {
     }
 }
 
-inline unsigned grid_for(size_t items) {
-    const size_t g = (items + CAL_BLOCK - 1) / CAL_BLOCK;
-    return (unsigned)(g < 1 ? 1 : (g > CAL_MAX_GRID ? CAL_MAX_GRID : g));
-}
-inline bool aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
 inline float unkey(uint32_t k) {
-    const uint32_t b = (k & 0x80000000u) ? (k ^ 0x80000000u) : ~k;
+    const uint32_t b = unkey_bits(k);
     float f;
     memcpy(&f, &b, 4);
     return f;

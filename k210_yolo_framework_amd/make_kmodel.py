@@ -1,11 +1,12 @@
 """`make kmodel` - quantise a trained checkpoint to a K210 kmodel (the reference leaves this step to keras_freeze.py + nncase).
 
-    python make_kmodel.py CKPT OUT [network flags of keras_inference.py] (--calib LIST.npy | --synthetic N) [--calib_seed S]
+    python make_kmodel.py CKPT OUT [network flags of keras_inference.py] (--calib LIST.npy | --synthetic N | --ranges FILE.npz) [--calib_seed S]
 
 CKPT: a Keras `.h5` or `.npz` checkpoint; OUT: `.kmodel` or `.kfpkg`.  The calibration images are a list file as make_voc_list.py writes
 (data/<set>_img_ann.npy) or N generated images as `make train SYNTHETIC=N` trains on; they are decoded as the input pipeline decodes them
 (Helper._read_img) and letterboxed on the GPU (yk_letterbox_u8), then measured by quantize.Calibrator.  Prints the per-layer report and
-the file size."""
+the file size.  `--ranges FILE` (`make kmodel RANGES=`) quantises with the ranges a `make train QAT=True` run learned
+(`yolo_qat_ranges.npz`: tensor name -> [lo, hi]) instead of calibrating; no image is read and no GPU is needed."""
 from __future__ import annotations
 
 import argparse
@@ -37,7 +38,19 @@ def calibration_frames(h: Helper, calib, synthetic: int, seed: int, class_num: i
     return torch.cat([engine.letterbox_u8(torch.from_numpy(np.ascontiguousarray(im[None, ..., :3], np.uint8)).cuda(), in_hw) for im in imgs])
 
 
-def main(ckpt, out, image_size, output_size, model_def, class_num, depth_multiplier, train_set, calib, synthetic, calib_seed, batch, limit=0):
+def load_ranges(path, spec):
+    """{tensor name: (lo, hi)} of a `yolo_qat_ranges.npz`; YkError naming every conv output of `spec` the file lacks."""
+    from . import engine
+    with np.load(str(path)) as z:
+        ranges = {k: tuple(float(v) for v in np.asarray(z[k]).reshape(-1)[:2]) for k in z.files}
+    missing = [l.name for l in spec.layers if l.name not in ranges]
+    if missing:
+        raise engine.YkError(f'make_kmodel: --ranges {path} has no range for tensor(s) {", ".join(missing)} of {spec.name}')
+    return ranges
+
+
+def main(ckpt, out, image_size, output_size, model_def, class_num, depth_multiplier, train_set, calib, synthetic, calib_seed, batch, limit=0,
+         ranges=None):
     from pathlib import Path
     from . import quantize
     anchor_file = Path(f'data/{train_set}_anchor.npy')
@@ -47,10 +60,20 @@ def main(ckpt, out, image_size, output_size, model_def, class_num, depth_multipl
     model.load_weights(str(ckpt))
     print(INFO, f' Load CKPT {ckpt}')
     t0 = time.time()
-    frames = calibration_frames(h, calib, synthetic, calib_seed, class_num, limit)
-    report = model.save_kmodel(str(out), frames, batch=batch)
-    print(quantize.format_report(report))
-    print(INFO, f' {len(frames)} calibration images, {time.time() - t0:.2f} s')
+    if ranges:
+        from . import engine, kmodel
+        try:
+            km, report = quantize.quantize(model.spec, model.get_weights(), load_ranges(ranges, model.spec))
+            report['file_bytes'] = kmodel.write(str(out), km)
+        except kmodel.KmodelError as e:
+            raise engine.YkError(f'make_kmodel: {e}') from e
+        print(quantize.format_report(report))
+        print(INFO, f' ranges of {ranges}, no calibration, {time.time() - t0:.2f} s')
+    else:
+        frames = calibration_frames(h, calib, synthetic, calib_seed, class_num, limit)
+        report = model.save_kmodel(str(out), frames, batch=batch)
+        print(quantize.format_report(report))
+        print(INFO, f' {len(frames)} calibration images, {time.time() - t0:.2f} s')
     print(INFO, f' wrote {out}: kmodel of {report["file_bytes"]} bytes')
     return report
 
@@ -68,13 +91,16 @@ def cli(argv=None):
     p.add_argument('--synthetic', type=int, default=0, help='calibrate on N generated images instead of --calib')
     p.add_argument('--calib_seed', type=int, default=3, help='seed of the generated images / of the order --calib_limit samples in')
     p.add_argument('--calib_batch', type=int, default=32, help='images per calibration forward pass')
+    p.add_argument('--ranges', type=str, default=None, help='quantise with the ranges of a QAT run (yolo_qat_ranges.npz) instead of calibrating')
     p.add_argument('pre_ckpt', type=str, help='trained weights (.h5 / .npz)')
     p.add_argument('output', type=str, help='.kmodel or .kfpkg to write')
     a = p.parse_args(sys.argv[1:] if argv is None else argv)
-    if not a.calib and not a.synthetic:
-        p.error('give --calib LIST.npy or --synthetic N')
+    if a.ranges and (a.calib or a.synthetic):
+        p.error('--ranges replaces calibration: it cannot be combined with --calib or --synthetic')
+    if not a.calib and not a.synthetic and not a.ranges:
+        p.error('give --calib LIST.npy, --synthetic N or --ranges FILE.npz')
     return main(a.pre_ckpt, a.output, a.image_size, a.output_size, a.model_def, a.class_num, a.depth_multiplier, a.train_set, a.calib,
-                a.synthetic, a.calib_seed, a.calib_batch, a.calib_limit)
+                a.synthetic, a.calib_seed, a.calib_batch, a.calib_limit, a.ranges)
 
 
 if __name__ == '__main__':

@@ -15,6 +15,11 @@ Magnitude pruning (keras_train.py:59-71, tfmot prune_low_magnitude restated in p
 masks of the Conv2D kernels on the schedule's update steps and zeroes the masked weights at the start of every step (csrc/yk_prune.hip),
 outside the captured graph like Adam.  With prune=None the step issues exactly the launches it issued before.
 
+Quantisation-aware fine-tuning (qat.py): `Trainer(qat=QatConfig(...))` simulates the kmodel's 8-bit codes inside the step
+(csrc/yk_qat.hip): every conv / depthwise kernel is read from the shadow buffer Pq = fq(P), every conv output and every concat is
+fake-quantised over a range that follows the batches, the backward pass takes the straight-through gradient, and L2 and Adam act on the
+latent P.  All of it is inside the captured graph.  With qat=None nothing is allocated and nothing is launched.
+
 fp32 storage and fp32 MFMA throughout (TF1.14's default for this model)."""
 from __future__ import annotations
 
@@ -54,7 +59,7 @@ class Trainer:
     def __init__(self, spec: ns.NetSpec, weights: Dict[str, np.ndarray], anchors: np.ndarray, per_rank_batch: int,
                  obj_thresh: float = 0.7, iou_thresh: float = 0.5, obj_weight: float = 1.0, noobj_weight: float = 1.0,
                  wh_weight: float = 1.0, lr: float = 5e-4, decay: float = 0.0, device: int = 0, process_group=None,
-                 world_size: int = 1, use_graph: bool = True, prune=None):
+                 world_size: int = 1, use_graph: bool = True, prune=None, qat=None):
         import torch
         engine.require_gpu()
         self.torch = torch
@@ -108,6 +113,10 @@ class Trainer:
         self.prune = prune
         if prune is not None:
             self._prune_init()
+        # quantisation-aware training (qat.QatConfig).  None: nothing is allocated and nothing is launched.
+        self.qat = qat
+        if qat is not None:
+            self._qat_init()
 
     # ------------------------------------------------------------------ parameters
     def view(self, buf, name):
@@ -139,12 +148,18 @@ class Trainer:
                         # export_weights / validate read a tensor nobody updates
                         cur.copy_(src)
 
-    def export_weights(self) -> Dict[str, np.ndarray]:
-        """Keras-layout arrays again (what keras.models.save_model would hold, keras_train.py:107)."""
+    def export_weights(self, quantized: bool = False) -> Dict[str, np.ndarray]:
+        """Keras-layout arrays again (what keras.models.save_model would hold, keras_train.py:107).  quantized=True (a QAT Trainer): the
+        kernels as the step reads them, fq of the current P over each kernel's own range; everything else as in P."""
         out = {}
+        src = self.P
+        if quantized:
+            self._need_qat()
+            self._qat_weights()
+            src = self.Pq
         for l in self.spec.layers:
             kh, kw, ci, co = l.kernel_shape
-            k = self.view(self.P, l.name + '/kernel').cpu().numpy()
+            k = self.view(src, l.name + '/kernel').cpu().numpy()
             out[l.name + '/kernel'] = (np.transpose(k.reshape(co, kh, kw, ci), (1, 2, 3, 0)) if l.kind == 'conv'
                                        else k.reshape(3, 3, ci)[..., None]).copy()
             if l.use_bias:
@@ -215,11 +230,17 @@ class Trainer:
         return self._fa
 
     # ------------------------------------------------------------------ forward (training mode)
-    def forward(self, x_nhwc) -> List["torch.Tensor"]:
-        """x_nhwc: cuda fp32 [B,H,W,3] already normalised (Helper._process_img output).  Saves the tape."""
+    def forward(self, x_nhwc, observe: bool = False) -> List["torch.Tensor"]:
+        """x_nhwc: cuda fp32 [B,H,W,3] already normalised (Helper._process_img output).  Saves the tape.
+        A QAT Trainer reads the kernels from Pq and fake-quantises every conv output and concat (the unquantised tensor stays on the tape as
+        saved[i]['qy']); observe=True quantises nothing and only folds the batch extremes (qat_observe)."""
         torch = self.torch
         assert x_nhwc.is_cuda and x_nhwc.dtype == torch.float32 and tuple(x_nhwc.shape[:1]) == (self.B,)
         T, S = {0: x_nhwc.contiguous()}, {}
+        fq = self.qat is not None and not observe
+        if fq:
+            self._qat_weights()                                      # Pq = fq(P): the first launches of the captured region
+        W = self.Pq if fq else self.P
         fused_add = self._fused_adds()                               # conv op index -> (Add op index, the Add's other input)
         done = set()
         for i, op in enumerate(self.spec.ops):
@@ -230,7 +251,7 @@ class Trainer:
             M = self.B * ho * wo
             if t in (ns.OP_CONV, ns.OP_DWCONV):
                 l = self.lay[op['layer']]
-                w = self.view(self.P, l.name + '/kernel')
+                w = self.view(W, l.name + '/kernel')
                 z = self._new(self.B, ho, wo, co)
                 route = conv_route(op, l) if t == ns.OP_CONV else None
                 a, kk = x, op['cin']                                 # the GEMM's operand: a 1x1 conv's input, or the column matrix below
@@ -272,6 +293,8 @@ class Trainer:
                         self._ck(self.L.yk_bias_add_f32(engine._ptr(z), C.c_longlong(M), C.c_int(co),
                                                         engine._ptr(self.view(self.P, l.name + '/bias')), self._s()), 'yk_bias_add_f32')
                     y = z
+                if self.qat is not None:
+                    y = self._qat_out(i, op['out'], y, S, observe)
             elif t == ns.OP_MAXPOOL:
                 hi, wi, ci = self.spec.tensors[op['in0']]
                 y = self._new(self.B, ho, wo, co)
@@ -284,6 +307,8 @@ class Trainer:
                 y = x.repeat_interleave(2, dim=1).repeat_interleave(2, dim=2).contiguous()
             elif t == ns.OP_CONCAT:
                 y = torch.cat([x, T[op['in1']]], dim=3)
+                if fq:                                               # the kmodel's REQUANTIZE onto the union of the parts' ranges
+                    y = self._qat_out(i, op['out'], y, S, False)
             elif t == ns.OP_ADD:
                 y = x.clone()
                 self._axpy(1.0, T[op['in1']], y)
@@ -323,13 +348,18 @@ class Trainer:
             dy = D.pop(op['out'], None)
             if dy is None:
                 continue
+            if self.qat is not None and 'qy' in self.saved.get(i, ()):
+                # straight-through: dy is the gradient of the fake-quantised output and nobody else holds it, masked in place
+                self._ck(self.L.yk_qat_act_bwd_f32(engine._ptr(dy), engine._ptr(self.saved[i]['qy']), C.c_longlong(dy.numel()),
+                                                   engine._ptr(self._qa_ranges), C.c_int(op['out']), engine._ptr(dy), self._s()),
+                         'yk_qat_act_bwd_f32')
             x = self.T.get(op['in0'])                               # (None for an Add whose conv input was folded into the producer: never stored, never read here)
             ho, wo, co = self.spec.tensors[op['out']]
             hi, wi, ci = self.spec.tensors[op['in0']]
             M = self.B * ho * wo
             if t in (ns.OP_CONV, ns.OP_DWCONV):
                 l = self.lay[op['layer']]
-                w = self.view(self.P, l.name + '/kernel')
+                w = self.view(self.P if self.qat is None else self.Pq, l.name + '/kernel')     # dL/dPq is taken as dL/dP
                 gw = self.view(self.G, l.name + '/kernel')
                 if l.bn_name:
                     sv = self.saved[i]
@@ -472,7 +502,10 @@ class Trainer:
             parts.append(loss6)
             grads.append(g)
         self.backward(grads)
-        return dict(layers=parts, reg=self.regulariser(add_grad=self.world == 1))
+        res = dict(layers=parts, reg=self.regulariser(add_grad=self.world == 1))
+        if self.qat is not None:
+            self._qat_update(False)                                  # after the backward pass: forward and backward saw the same ranges
+        return res
 
     def invalidate_graph(self) -> None:
         """Forget the captured step (the next two steps run eagerly / re-capture).  Called automatically when something a capture
@@ -483,7 +516,8 @@ class Trainer:
         self._eager_steps = 0
 
     def _graph_key(self, x_nhwc, y_true):
-        return (tuple(sorted(self.hyper.items())), tuple(x_nhwc.shape), tuple(tuple(y.shape) for y in y_true), self.world)
+        return (tuple(sorted(self.hyper.items())), tuple(x_nhwc.shape), tuple(tuple(y.shape) for y in y_true), self.world,
+                None if self.qat is None else self.qat.momentum)           # (a launch scalar of yk_qat_update_f32 inside the capture)
 
     def _loss_and_grads_replayed(self, x_nhwc, y_true):
         """loss_and_grads through a captured HIP graph (after one eager step that also warms allocator and scratch buffers).
@@ -626,9 +660,126 @@ class Trainer:
         return {nm: dict(n=n, kept=int(k), threshold=float(t), sparsity=1.0 - int(k) / n)
                 for nm, n, k, t in zip(self._pr_names, self._pr_sizes, kept, thr)}
 
+    # ------------------------------------------------------------------ quantisation-aware training
+    def _qat_init(self) -> None:
+        """The slot table (one slot per spec tensor), the range and batch-extreme tables, the shadow parameter buffer Pq and the segment
+        tables of all conv / depthwise kernels.  Allocated once: the captured step holds their pointers."""
+        from . import quantize
+        from .qat import slot_table
+        torch = self.torch
+        kind, p0, p1 = slot_table(self.spec)                        # KmodelError naming the op the KPU path cannot express
+        self._qa_kind, self._qa_parts = kind, list(zip(p0, p1))
+        self._qa_names = quantize.tensor_names(self.spec)
+        self._qa_n = n = len(kind)
+        dev = lambda a, dt: torch.from_numpy(np.asarray(a, dt)).to(self.dev)
+        self._qa_kind_d, self._qa_p0_d, self._qa_p1_d = dev(kind, np.int32), dev(p0, np.int32), dev(p1, np.int32)
+        self._qa_ranges = dev(np.tile(np.array([np.inf, -np.inf], np.float32), n), np.float32)       # nothing seen yet
+        self._qa_batch = torch.zeros(4 * n, dtype=torch.int32, device=self.dev)                      # YK_RANGE_WORDS per slot
+        self._ck(self.L.yk_range_reset(engine._ptr(self._qa_batch), C.c_int(n), self._s()), 'yk_range_reset')
+        self.Pq = torch.zeros_like(self.P)
+        names = [l.name + '/kernel' for l in self.spec.layers]
+        offs = [self.slots[nm][0] for nm in names]
+        sizes = [int(np.prod(self.slots[nm][1])) for nm in names]
+        tile = int(self.L.yk_qat_tile())
+        first = np.concatenate([[0], np.cumsum([(s + tile - 1) // tile for s in sizes])])
+        assert all(o >= 0 and s >= 1 and o + s <= self.n_params for o, s in zip(offs, sizes)) and first[-1] < 2 ** 31
+        self._qa_off, self._qa_size, self._qa_first = dev(offs, np.int64), dev(sizes, np.int64), dev(first, np.int32)
+        self._qa_nseg, self._qa_ntiles = len(offs), int(first[-1])
+        self._qa_wrange = torch.zeros(4 * len(offs), dtype=torch.int32, device=self.dev)
+        self._qa_ready = False                                       # ranges come from qat_observe or qat_set_ranges
+
+    def _need_qat(self):
+        if self.qat is None:
+            raise engine.YkError('this Trainer was built without quantisation-aware training (qat=None)')
+
+    def _qat_weights(self) -> None:
+        """Pq = P with every conv / depthwise kernel replaced by fq over its own [min, max]: one library call, three launches."""
+        self._ck(self.L.yk_qat_weights_f32(engine._ptr(self.P), C.c_longlong(self.n_params), engine._ptr(self._qa_off), engine._ptr(self._qa_size),
+                                           engine._ptr(self._qa_first), C.c_int(self._qa_nseg), C.c_int(self._qa_ntiles), engine._ptr(self.Pq),
+                                           engine._ptr(self._qa_wrange), self._s()), 'yk_qat_weights_f32')
+
+    def _qat_out(self, i, slot, y, S, observe):
+        """Tensor `slot`, the output of op i: folded into the batch extremes only (observe), or fake-quantised over the slot's range into a
+        new tensor while y stays on the tape for the backward kernel."""
+        if observe:
+            self._ck(self.L.yk_range_f32(engine._ptr(y), C.c_longlong(y.numel()), engine._ptr(self._qa_batch), C.c_int(slot), self._s()),
+                     'yk_range_f32')
+            return y
+        yq = self.torch.empty_like(y)
+        self._ck(self.L.yk_qat_act_fwd_f32(engine._ptr(y), C.c_longlong(y.numel()), engine._ptr(self._qa_ranges), C.c_int(slot), engine._ptr(yq),
+                                           engine._ptr(self._qa_batch), self._s()), 'yk_qat_act_fwd_f32')
+        S.setdefault(i, {})['qy'] = y
+        return yq
+
+    def _qat_update(self, observe: bool) -> None:
+        m = np.float32(self.qat.momentum)
+        self._ck(self.L.yk_qat_update_f32(engine._ptr(self._qa_ranges), engine._ptr(self._qa_batch), engine._ptr(self._qa_kind_d),
+                                          engine._ptr(self._qa_p0_d), engine._ptr(self._qa_p1_d), C.c_int(self._qa_n), C.c_float(m),
+                                          C.c_float(np.float32(1) - m), C.c_int(1 if observe else 0), self._s()), 'yk_qat_update_f32')
+
+    def qat_observe(self, x_nhwc) -> None:
+        """One training-mode forward with no quantisation at all (BatchNorm moving statistics move as in a step); every range is widened
+        to the batch's extremes, starting from "nothing seen yet"."""
+        self._need_qat()
+        self.forward(x_nhwc, observe=True)
+        self._qat_update(True)
+        self._qa_ready = True
+
+    def qat_flagged(self) -> List[str]:
+        """Names of what has held a NaN or an infinity since construction or the last qat_clear_flags: tensors (conv outputs, concats) by
+        their name, kernels as '<layer>/kernel' (as of the last step).  Such values enter no range; the flags are sticky."""
+        self._need_qat()
+        flags = self._qa_batch.cpu().numpy().reshape(-1, 4)[:, 2]
+        wflags = self._qa_wrange.cpu().numpy().reshape(-1, 4)[:, 2]
+        return ([self._qa_names[i] for i in range(self._qa_n) if self._qa_kind[i] and flags[i]] +
+                [l.name + '/kernel' for l, f in zip(self.spec.layers, wflags) if f])
+
+    def qat_clear_flags(self) -> None:
+        """Forget the non-finite flags (in place; the ranges and the batch extremes stay)."""
+        self._need_qat()
+        self._qa_batch.view(-1, 4)[:, 2].zero_()
+
+    def qat_ranges(self, check: bool = True) -> Dict[str, tuple]:
+        """{tensor name (quantize.tensor_names): (lo, hi)} of every conv output and concat.  YkError naming the tensors that have no range
+        yet, and (check=True) whatever qat_flagged() names: a tensor or a kernel that held a NaN or an infinity."""
+        self._need_qat()
+        r = self._qa_ranges.cpu().numpy().reshape(-1, 2)
+        own = [i for i in range(self._qa_n) if self._qa_kind[i]]
+        bad = self.qat_flagged() if check else []
+        if bad:
+            raise engine.YkError(f'qat: non-finite values (NaN or infinity) in {", ".join(bad)}: the weights or the frames are broken '
+                                 f'(qat_clear_flags() forgets them; qat_ranges(check=False) reads the ranges of the finite values)')
+        empty = [self._qa_names[i] for i in own if not r[i, 0] <= r[i, 1]]
+        if empty:
+            raise engine.YkError(f'qat: no range yet for tensor(s) {", ".join(empty)}: call qat_observe or qat_set_ranges first')
+        return {self._qa_names[i]: (float(r[i, 0]), float(r[i, 1])) for i in own}
+
+    def qat_set_ranges(self, ranges: Dict[str, tuple]) -> None:
+        """Ranges of the conv outputs from {name: (lo, hi)}; a concat's range is derived (the union of its parts), whatever the dict holds
+        for it.  Written in place: a captured step keeps reading the same table."""
+        self._need_qat()
+        from .qat import SLOT_OWNER, SLOT_UNION
+        missing = [self._qa_names[i] for i in range(self._qa_n) if self._qa_kind[i] == SLOT_OWNER and self._qa_names[i] not in ranges]
+        if missing:
+            raise engine.YkError(f'qat_set_ranges: no range for tensor(s) {", ".join(missing)}')
+        r = np.tile(np.array([np.inf, -np.inf], np.float32), (self._qa_n, 1))
+        for i in range(self._qa_n):
+            if self._qa_kind[i] == SLOT_OWNER:
+                lo, hi = (np.float32(v) for v in ranges[self._qa_names[i]])
+                if not (np.isfinite(lo) and np.isfinite(hi) and lo <= hi):
+                    raise engine.YkError(f'qat_set_ranges: range ({lo}, {hi}) of {self._qa_names[i]!r} is not a finite interval')
+                r[i] = lo, hi
+            elif self._qa_kind[i] == SLOT_UNION:
+                a, b = self._qa_parts[i]
+                r[i] = min(r[a, 0], r[b, 0]), max(r[a, 1], r[b, 1])
+        self._qa_ranges.copy_(self.torch.from_numpy(r.reshape(-1)))
+        self._qa_ready = True
+
     def step(self, x_nhwc, y_true: Sequence["torch.Tensor"], reduce=None, reduce_scalar=None) -> Dict[str, float]:
         """model.fit's inner step (keras_train.py:94).  Returns python floats (one device->host sync)."""
         torch = self.torch
+        if self.qat is not None and not self._qa_ready:
+            raise engine.YkError('qat: the activation ranges are not set: call qat_observe(x) on a few batches (or qat_set_ranges) before the first step')
         if self.prune is not None:
             self.prune_step()
         r = self._loss_and_grads_replayed(x_nhwc, y_true)

@@ -16,7 +16,12 @@ open it; keras_io / h5lite, no h5py needed) plus the same arrays as `yolo_model.
 PolynomialDecay schedule built from the four `--prune_*` flags (`prune.PruneSchedule`, end_step = prune_end_epoch x steps per epoch);
 the masks are computed and applied by HIP kernels at the start of a step (`Trainer.prune_step`), once more at the end of every epoch,
 the overall and per-head sparsity is printed per epoch (the stand-in for PruningSummaries), and the checkpoint is
-`yolo_prune_model.h5` / `.npz` with the masked weights.  The rule is restated from tfmot's public source; parity with it is unpinned."""
+`yolo_prune_model.h5` / `.npz` with the masked weights.  The rule is restated from tfmot's public source; parity with it is unpinned.
+
+`--qat True` (`make train QAT=True`; qat.py): the kmodel's 8-bit quantisation simulated in the forward pass, straight-through
+gradients in the backward pass.  The first `--qat_observe` (>= 1) batches of epoch 0 only set the activation ranges (no update; an epoch 0
+with fewer batches is observed whole and training starts with epoch 1); afterwards the ranges follow the batches with `--qat_momentum`.  The checkpoint is `yolo_qat_model.h5` / `.npz` (the latent float weights; with
+`--is_prune True` masked) plus `yolo_qat_ranges.npz` (tensor name -> [lo, hi]), which `make kmodel RANGES=` quantises with."""
 from __future__ import annotations
 
 import argparse
@@ -76,10 +81,13 @@ def batches(h: Helper, items, batch_size: int, rng, shuffle: bool, augment=None)
 def main(args, train_set, class_num, pre_ckpt, model_def, depth_multiplier, is_augmenter, image_size, output_size, batch_size,
          rand_seed, max_nrof_epochs, init_learning_rate, learning_rate_decay_factor, obj_weight, noobj_weight, wh_weight,
          obj_thresh, iou_thresh, vaildation_split, log_dir, is_prune, initial_sparsity=0.5, final_sparsity=0.9, end_epoch=5,
-         frequency=100, synthetic=0, max_steps=0):
+         frequency=100, synthetic=0, max_steps=0, is_qat='False', qat_momentum=0.99, qat_observe=8):
     import torch
     from .train import Trainer
     prune = is_prune == 'True'
+    qat = is_qat == 'True'
+    if qat and int(qat_observe) < 1:
+        raise engine.YkError(f'--qat_observe {qat_observe}: at least one batch must set the activation ranges before the first step')
     augment = is_augmenter == 'True'
     rank, world = int(os.environ.get('RANK', '0')), int(os.environ.get('WORLD_SIZE', '1'))
     local = int(os.environ.get('LOCAL_RANK', '0'))
@@ -89,6 +97,8 @@ def main(args, train_set, class_num, pre_ckpt, model_def, depth_multiplier, is_a
         if prune:
             raise engine.YkError('--is_prune True (magnitude pruning, keras_train.py:59-71) runs in HIP kernels on the training step: '
                                  'no HIP device') from e
+        if qat:
+            raise engine.YkError('--qat True (quantisation-aware fine-tuning) runs in HIP kernels on the training step: no HIP device') from e
         if augment:
             raise engine.YkError('--augmenter True (imgaug OneOf, tools/utils.py:84-88) runs in the GPU input pipeline: no HIP device') from e
         raise
@@ -137,13 +147,17 @@ def main(args, train_set, class_num, pre_ckpt, model_def, depth_multiplier, is_a
     if prune:                                                                    # keras_train.py:60-66: end_step = train_epoch_step * end_epoch
         from .prune import PruneSchedule
         schedule = PruneSchedule(initial_sparsity, final_sparsity, end_epoch * (len(h.train_list) // batch_size), frequency)
+    qat_cfg = None
+    if qat:
+        from .qat import QatConfig
+        qat_cfg = QatConfig(qat_momentum)
     tr = Trainer(spec, weights, h.anchors, per_rank, obj_thresh=obj_thresh, iou_thresh=iou_thresh, obj_weight=obj_weight,
                  noobj_weight=noobj_weight, wh_weight=wh_weight, lr=init_learning_rate, decay=learning_rate_decay_factor, device=local,
-                 world_size=world, prune=schedule)
+                 world_size=world, prune=schedule, qat=qat_cfg)
     from .pipeline import InputPipeline
     if rank == 0:
         print(INFO, 'data augment is ', str(augment))                            # utils.py:418
-    steps = 0
+    steps, observed = 0, 0
     for epoch in range(max_nrof_epochs):
         t0, seen, run = time.time(), 0, 0.0
         # tools/utils.py:417-450: each rank decodes only its rows of the global batch, on a thread pool, two batches ahead;
@@ -152,6 +166,10 @@ def main(args, train_set, class_num, pre_ckpt, model_def, depth_multiplier, is_a
                              augment=augment)
         try:                                                                    # an exception in the step must not leave the producer running
             for x, ys in pipe:
+                if qat and epoch == 0 and observed < int(qat_observe):           # the first batches of epoch 0 only set the activation ranges
+                    tr.qat_observe(x)
+                    observed += 1
+                    continue
                 out = tr.step(x, ys)
                 seen, run, steps = seen + 1, run + out['loss'], steps + 1
                 if rank == 0 and (seen % 10 == 0 or seen == 1):
@@ -178,15 +196,21 @@ def main(args, train_set, class_num, pre_ckpt, model_def, depth_multiplier, is_a
             break
     if rank == 0:
         from . import keras_io
-        stem = 'yolo_prune_model' if prune else 'yolo_model'                    # keras_train.py:102-111
+        stem = 'yolo_qat_model' if qat else 'yolo_prune_model' if prune else 'yolo_model'      # keras_train.py:102-111
         ckpt = log_dir / f'{stem}.h5'
         if prune:
             tr.apply_masks()                                                    # (a run cut short by --max_steps ends inside an epoch)
         final = tr.export_weights()
         keras_io.save_keras_model(spec, final, str(ckpt))                      # save_model layout: /model_weights + model_config
         np.savez(log_dir / f'{stem}.npz', **final)
+        if qat:                                                                 # this rank's ranges (per replica, like BatchNorm statistics)
+            flagged = tr.qat_flagged()                                          # non-finite values never enter a range: the file is written anyway
+            if flagged:
+                print(ERROR, f' QAT met non-finite values (NaN or infinity) in {", ".join(flagged)}; yolo_qat_ranges.npz holds the ranges of the finite ones')
+            np.savez(log_dir / 'yolo_qat_ranges.npz', **{k: np.asarray(v, np.float32) for k, v in tr.qat_ranges(check=False).items()})
         print()
-        print(INFO, f' Save Pruned Model as {str(ckpt)}' if prune else f' Save Model as {str(ckpt)}')
+        print(INFO, f' Save QAT Model as {str(ckpt)} (ranges: yolo_qat_ranges.npz)' if qat else
+              f' Save Pruned Model as {str(ckpt)}' if prune else f' Save Model as {str(ckpt)}')
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
@@ -247,13 +271,17 @@ def cli(argv=None):
     p.add_argument('--prune_final_sparsity', type=float, default=0.9)
     p.add_argument('--prune_end_epoch', type=int, default=5)
     p.add_argument('--prune_frequency', type=int, default=100)
+    p.add_argument('--qat', type=str, choices=['True', 'False'], default='False', help='quantisation-aware fine-tuning (DESIGN.md 3.10)')
+    p.add_argument('--qat_momentum', type=float, default=0.99, help='moving average of the activation ranges')
+    p.add_argument('--qat_observe', type=int, default=8, help='batches of epoch 0 that only set the activation ranges')
     p.add_argument('--synthetic', type=int, default=0, help='train on N generated images instead of data/<set>_img_ann.npy')
     p.add_argument('--max_steps', type=int, default=0)
     a = p.parse_args(sys.argv[1:] if argv is None else argv)
     return main(a, a.train_set, a.class_num, a.pre_ckpt, a.model_def, a.depth_multiplier, a.augmenter, a.image_size, a.output_size,
                 a.batch_size, a.rand_seed, a.max_nrof_epochs, a.init_learning_rate, a.learning_rate_decay_factor, a.obj_weight,
                 a.noobj_weight, a.wh_weight, a.obj_thresh, a.iou_thresh, a.vaildation_split, a.log_dir, a.is_prune,
-                a.prune_initial_sparsity, a.prune_final_sparsity, a.prune_end_epoch, a.prune_frequency, a.synthetic, a.max_steps)
+                a.prune_initial_sparsity, a.prune_final_sparsity, a.prune_end_epoch, a.prune_frequency, a.synthetic, a.max_steps,
+                a.qat, a.qat_momentum, a.qat_observe)
 
 
 if __name__ == '__main__':

@@ -2,12 +2,12 @@
 """VOC mAP of a checkpoint on an annotation list, through the HIP engine (BASELINE.json: "VOC mAP within 0.1 pt of the Keras reference").
 
     python tools/map_eval.py CKPT [--ann data/voc_img_ann.npy] [--model_def yolo_mobilev1 --depth_multiplier 0.75]
-                             [--precision f16x2] [--compare f16] [--obj_thresh 0.05] [--iou_thresh 0.5] [--limit N] [--voc07]
+                             [--precision f16x2|f16|kpu] [--compare f16] [--obj_thresh 0.05] [--iou_thresh 0.5] [--limit N] [--voc07]
 
 `--ann`: the list `make_voc_list.py` writes (rows [image path, boxes [n,5] = (class, cx, cy, w, h) relative to the image, ...]); the
 validation head of it (Helper's validation_split) is evaluated unless --all.  The reference has no evaluator: the metric is the VOC
 devkit's (k210_yolo_framework_amd/voc_eval.py).  With --compare the second precision mode is evaluated on the same images and the mAP
-difference is printed in points.
+difference is printed in points.  `--precision kpu`: CKPT is a `.kmodel` / `.kfpkg`, run with the KPU's exact integer arithmetic.
 """
 import argparse
 import sys
@@ -51,7 +51,7 @@ def main(argv=None):
     p.add_argument('--depth_multiplier', type=float, default=0.75)
     p.add_argument('--image_size', type=int, default=(224, 320), nargs='+')
     p.add_argument('--output_size', type=int, default=(7, 10, 14, 20), nargs='+')
-    p.add_argument('--precision', choices=['f16', 'f16x2'], default='f16x2')
+    p.add_argument('--precision', choices=['f16', 'f16x2', 'kpu'], default='f16x2')
     p.add_argument('--compare', choices=['f16', 'f16x2'], default=None)
     p.add_argument('--obj_thresh', type=float, default=0.05)
     p.add_argument('--nms_iou', type=float, default=0.5, help='IoU of the per-class NMS (keras_inference.py --iou_thresh)')
@@ -60,6 +60,8 @@ def main(argv=None):
     p.add_argument('--all', action='store_true', help='evaluate the whole list, not its validation head')
     p.add_argument('--limit', type=int, default=0)
     a = p.parse_args(sys.argv[1:] if argv is None else argv)
+    if (a.precision == 'kpu') != a.ckpt.endswith(('.kmodel', '.kfpkg')):
+        p.error("--precision kpu runs a .kmodel / .kfpkg checkpoint, and only it does (the float modes take .h5 / .npz)")
     anchor_file = Path(f'data/{a.train_set}_anchor.npy')
     h = Helper(a.ann, a.class_num, str(anchor_file) if anchor_file.exists() else VOC_ANCHORS, np.reshape(np.array(a.image_size), (-1, 2)),
                np.reshape(np.array(a.output_size), (-1, 2)))
