@@ -10,6 +10,9 @@
 #                    [QAT=True QATMOMENTUM=0.99 QATOBSERVE=8]: quantisation-aware fine-tuning, saves yolo_qat_model.h5 + yolo_qat_ranges.npz
 #   make kmodel      CKPT=yolo_model.h5 OUT=yolo.kmodel|.kfpkg [SYNTHETIC=256 | CALIB=data/voc_img_ann.npy]: 8-bit K210 model, calibrated on the GPU
 #                    [RANGES=yolo_qat_ranges.npz]: the ranges a QAT run learned instead of a calibration
+#   make eval        CKPT=yolo_model.h5|yolo.kmodel [PRECISION=f16x2|f16|kpu] [ANN=data/voc_img_ann.npy | SYNTHETIC=256] [EVALOBJ=0.05] [VOC07=True]:
+#                    VOC mAP of the checkpoint, network and metric on the GPU; prints the per-class AP table, writes eval.json beside CKPT
+#                    (make train VALMAP=True appends val_mAP to every epoch line)
 #   make anchors     DATASET=voc ANCNUM=3 [LOW='0.0 0.0' HIGH='1.0 1.0']   (reference Makefile:78-87: k-means anchors from data/<set>_img_ann.npy)
 
 PY            ?= python3
@@ -42,6 +45,12 @@ SYNTHETIC     ?= 0
 QAT           ?= False
 QATMOMENTUM   ?= 0.99
 QATOBSERVE    ?= 8
+VALMAP        ?= False
+# eval only
+PRECISION     ?= f16x2
+ANN           ?= data/$(DATASET)_img_ann.npy
+EVALOBJ       ?= 0.05
+VOC07         ?= False
 # kmodel only
 OUT           ?= yolo.kmodel
 CALIB         ?= data/$(DATASET)_img_ann.npy
@@ -59,16 +68,16 @@ TRAIN_ARGS = --pre_ckpt $(CKPT) --augmenter $(IAA) --batch_size $(BATCH) --rand_
              --noobj_weight $(NOOBJWEIGHT) --wh_weight $(WHWEIGHT) --vaildation_split $(SPLITFACTOR) --log_dir log \
              --is_prune $(PRUNE) --prune_initial_sparsity $(INITSPARSITY) --prune_final_sparsity $(FINALSPARSITY) \
              --prune_end_epoch $(END_EPOCH) --prune_frequency $(FREQUENCY) --synthetic $(SYNTHETIC) \
-             --qat $(QAT) --qat_momentum $(QATMOMENTUM) --qat_observe $(QATOBSERVE)
+             --qat $(QAT) --qat_momentum $(QATMOMENTUM) --qat_observe $(QATOBSERVE) --val_map $(VALMAP)
 ifeq ($(GPUS),1)
 LAUNCH = $(PY)
 else
 LAUNCH = $(PY) -m torch.distributed.run --nnodes=1 --nproc-per-node $(GPUS) --master-addr 127.0.0.1 --master-port 29533
 endif
 
-.PHONY: all build test bench inference train anchors kmodel
+.PHONY: all build test bench inference train anchors kmodel eval
 all:
-	@echo 'targets: build | test | bench | inference | train | kmodel   (see the header of this Makefile)'
+	@echo 'targets: build | test | bench | inference | train | kmodel | eval   (see the header of this Makefile)'
 
 build:
 	$(PY) -c "import __graft_entry__ as g; g.build()"
@@ -89,6 +98,12 @@ train:
 kmodel:
 	$(PY) make_kmodel.py $(CKPT) $(OUT) --train_set $(DATASET) --class_num $(CLSNUM) --model_def $(MODEL) --depth_multiplier $(DEPTHMUL) \
 		--image_size $(IMGSIZE) --output_size $(OUTSIZE) $(if $(RANGES),--ranges $(RANGES),$(if $(filter-out 0,$(SYNTHETIC)),--synthetic $(SYNTHETIC),--calib $(CALIB)))
+
+# VOC mAP of CKPT (.h5 / .npz, or .kmodel / .kfpkg with PRECISION=kpu) on the validation head of ANN, or on SYNTHETIC=N generated images
+eval:
+	$(PY) keras_eval.py $(CKPT) --train_set $(DATASET) --class_num $(CLSNUM) --model_def $(MODEL) --depth_multiplier $(DEPTHMUL) \
+		--image_size $(IMGSIZE) --output_size $(OUTSIZE) --iou_thresh $(IOUTHRESH) --precision $(PRECISION) --obj_thresh $(EVALOBJ) \
+		--voc07 $(VOC07) $(if $(filter-out 0,$(SYNTHETIC)),--synthetic $(SYNTHETIC),--ann $(ANN))
 
 # reference Makefile:78-87 (same flags; --is_random True as there)
 anchors:

@@ -490,6 +490,39 @@ int yk_qat_act_bwd_f32(const float *dyq, const float *y, long long n, const floa
 int yk_qat_update_f32(float *d_ranges, uint32_t *d_batch, const int *d_kind, const int *d_part0, const int *d_part1, int n_slots, float momentum,
                       float one_minus_momentum, int observe, void *stream);
 
+/* ---- the PASCAL-VOC detection metric on the device (map_gpu.MapEvaluator): per-class AP and mAP of detection rows that
+ * are already in device memory, by the rule of voc_eval.evaluate, integer for integer.  All buffers are the caller's; every launch is on
+ * `stream`; nothing is allocated and nothing synchronises.  Rows are (top, left, bottom, right, score, class) fp32; ground truth is the
+ * same six columns in FLOAT64 (score ignored) so that every threshold decision is the one the float64 reference makes.  Scores and box
+ * coordinates are assumed finite (a NaN has no place in the sort order).  A class column is read as numpy's `astype(int)` reads it
+ * (truncation toward zero); a row whose class is outside [0, class_num) belongs to no class: flag 0, counted nowhere.
+ * yk_map_append_packed   rows d_src[d_offsets[0] .. d_offsets[n_img]) of n_img images (d_offsets [n_img + 1], device) are copied behind the
+ *                        `have` rows of d_rows [capacity][6]; d_img [capacity] receives img_base + the image of every row.  n_new is the
+ *                        number of rows (the caller has read it back or knows it).
+ * yk_map_append_padded   the same for the padded form yk_decode_py leaves in device memory: d_dets [batch][cap][6] + d_counts [batch]
+ *                        (counts are clamped to [0, cap]; n_new = their sum; rows past n_new are not written).
+ *                        Both refuse by name instead of overrunning: have + n_new > capacity or > 2^31-1 rows: YK_ERR_ARG.
+ * yk_map_workspace_bytes bytes of d_work that yk_map_eval needs for these sizes (sort keys, permutations, scans, rocPRIM's scratch).
+ * yk_map_eval            d_img [n_rows] ascending image index of every row (as the append calls write it); d_gt [n_gt_rows][6] float64 with
+ *                        d_gt_off [n_img + 1] and d_difficult [n_gt_rows].  Per (image, class) group, detections in descending score
+ *                        (-0.0 == +0.0; ties in row order) take the ground-truth box of their image and class with the largest IoU (float64,
+ *                        box_iou's operation order, `plus_one` adds 1 to every extent; first index on ties): IoU >= iou_thresh on a
+ *                        difficult box: ignored; on a free box: true positive, the box is taken; on a taken box or below: false positive.
+ *                        -> d_flags [n_rows] (0 ignored, 1 tp, 2 fp, in row order); per class d_n_gt (non-difficult), d_n_det, d_tp, d_fp
+ *                        (int32 [class_num]) and d_ap (float64 [class_num]; NaN where n_gt == 0): the area under the monotone precision
+ *                        envelope, or with use_07_metric the 11-point mean (t = k * 0.1, recall >= t - 1e-12); d_map [1] = the mean of the
+ *                        non-NaN APs in class order (NaN if there are none).  Deterministic: two runs give the same bits.
+ *                        More than 2^31-1 rows, or n_img * (class_num + 1) >= 2^32, or a workspace that is too small: YK_ERR_ARG. */
+int yk_map_append_packed(const float *d_src, const int32_t *d_offsets, int n_img, int img_base, long long n_new, float *d_rows, int32_t *d_img,
+                         long long have, long long capacity, void *stream);
+int yk_map_append_padded(const float *d_dets, const int32_t *d_counts, int batch, int cap, int img_base, long long n_new, float *d_rows,
+                         int32_t *d_img, long long have, long long capacity, void *stream);
+int yk_map_workspace_bytes(long long n_rows, long long n_gt_rows, int n_img, int class_num, size_t *bytes);
+int yk_map_eval(const float *d_rows, const int32_t *d_img, long long n_rows, int n_img, const double *d_gt, const int32_t *d_gt_off,
+                const uint8_t *d_difficult, long long n_gt_rows, int class_num, double iou_thresh, int use_07_metric, int plus_one, void *d_work,
+                size_t work_bytes, uint8_t *d_flags, int32_t *d_n_gt, int32_t *d_n_det, int32_t *d_tp, int32_t *d_fp, double *d_ap, double *d_map,
+                void *stream);
+
 #ifdef __cplusplus
 }
 #endif

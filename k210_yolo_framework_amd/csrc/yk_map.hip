@@ -1,0 +1,493 @@
+// yk_map.hip — the PASCAL-VOC detection metric (per-class AP, mAP) on the device, where the detections already are.
+//
+// The rule is voc_eval.evaluate's (k210_yolo_framework_amd/voc_eval.py), held to it integer for integer:
+//
+//   keys      one pass over the rows: class = the float's truncation (`astype(int)`), score -> an order-preserving 32-bit key, complemented
+//             (descending), -0.0 folded onto +0.0 first.  Two 64-bit keys per row:  A = class | score  and  B = image, class | score.
+//   sort      rocPRIM's stable LSD radix sort, twice, values = row indices.  Order A is the per-class curve order (score descending, row
+//             ascending); order B makes every (image, class) group contiguous in the order the devkit visits it.
+//   match     one wave per (image, class) group.  The detections of a group are sequential (a taken box changes the next answer); the IoUs
+//             of one detection with ALL ground-truth boxes of its image and class are parallel over the lanes, in float64, in box_iou's
+//             operation order; argmax with the first index on ties; then `>= iou_thresh`, difficult -> ignored, taken -> false positive.
+//   curve     one workgroup per class over order A: integer inclusive scan of tp / fp, precision and recall in float64, the monotone
+//             envelope as a reverse max-scan, AP as the sum over the rows where recall steps (the true positives), or the 11-point form.
+//
+// Everything is integer or order-independent (max) except the AP sum, which is added in a fixed order: two runs give the same bits.
+// This translation unit is compiled with -ffp-contract=off: one rounding per reference operation.
+#include "yk_common.h"
+
+#include <rocprim/rocprim.hpp>   // device radix sort (the ordering step only)
+
+namespace {
+
+constexpr int MAP_BLOCK = 256;
+constexpr int MAP_WAVES = MAP_BLOCK / YK_WAVE;
+constexpr long long MAP_MAX_ROWS = 0x7fffffffLL;
+
+inline unsigned grid_for(long long n, int per_block) {
+    long long g = (n + per_block - 1) / per_block;
+    if (g < 1) g = 1;
+    if (g > 65536) g = 65536;            // grid-stride loops
+    return (unsigned)g;
+}
+
+inline unsigned bits_for(unsigned long long v) {      // bits needed to hold values 0 .. v
+    unsigned b = 1;
+    while (b < 64 && (v >> b)) ++b;
+    return b;
+}
+
+// `a[:, 5].astype(int) == c` for c in [0, class_num): the truncation toward zero; everything else (NaN too) -> class_num, which no class owns
+__device__ __forceinline__ int class_of(double c, int class_num) {
+    if (!(c > -1.0 && c < (double)class_num)) return class_num;
+    return (int)c;
+}
+
+// descending score, +-0 equal: a smaller key = visited earlier
+__device__ __forceinline__ uint32_t desc_key(float s) {
+    uint32_t b = __float_as_uint(s);
+    if ((b << 1) == 0u) b = 0u;
+    b ^= (b & 0x80000000u) ? 0xFFFFFFFFu : 0x80000000u;
+    return ~b;
+}
+
+// first index k in [0, n) with a[k] >= v
+__device__ __forceinline__ long long lower_bound_u64(const uint64_t *__restrict__ a, long long n, uint64_t v) {
+    long long lo = 0, hi = n;
+    while (lo < hi) {
+        const long long mid = lo + ((hi - lo) >> 1);
+        if (a[mid] < v) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// ---- accumulation ---------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(MAP_BLOCK) void append_packed_kernel(const float *__restrict__ src, const int32_t *__restrict__ offsets, int n_img,
+                                                                  int img_base, long long n_new, float *__restrict__ rows, int32_t *__restrict__ img) {
+    const long long off0 = offsets[0];
+    for (long long r = (long long)blockIdx.x * MAP_BLOCK + threadIdx.x; r < n_new; r += (long long)gridDim.x * MAP_BLOCK) {
+        int lo = 0, hi = n_img;                                  // the last image b with offsets[b] - offsets[0] <= r
+        while (hi - lo > 1) {
+            const int mid = lo + ((hi - lo) >> 1);
+            if ((long long)offsets[mid] - off0 <= r) lo = mid; else hi = mid;
+        }
+        const float *s = src + (size_t)(off0 + r) * 6;
+        float *d = rows + (size_t)r * 6;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) d[k] = s[k];
+        img[r] = img_base + lo;
+    }
+}
+
+// one workgroup per image: its first row = the sum of the counts before it
+__global__ __launch_bounds__(MAP_BLOCK) void append_padded_kernel(const float *__restrict__ dets, const int32_t *__restrict__ counts, int batch, int cap,
+                                                                  int img_base, long long n_new, float *__restrict__ rows, int32_t *__restrict__ img) {
+    __shared__ unsigned long long before;
+    for (int b = blockIdx.x; b < batch; b += gridDim.x) {
+        if (threadIdx.x == 0) before = 0ull;
+        __syncthreads();
+        unsigned long long part = 0;
+        for (int j = threadIdx.x; j < b; j += MAP_BLOCK) part += (unsigned long long)min(max(counts[j], 0), cap);
+        if (part) atomicAdd(&before, part);
+        __syncthreads();
+        const long long first = (long long)before;
+        const int n = min(max(counts[b], 0), cap);
+        for (int k = threadIdx.x; k < n; k += MAP_BLOCK) {
+            const long long r = first + k;
+            if (r < n_new) {                                      // never past what the caller made room for
+                const float *s = dets + ((size_t)b * cap + k) * 6;
+                float *d = rows + (size_t)r * 6;
+#pragma unroll
+                for (int e = 0; e < 6; ++e) d[e] = s[e];
+                img[r] = img_base + b;
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// ---- keys -----------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(MAP_BLOCK) void keys_kernel(const float *__restrict__ rows, const int32_t *__restrict__ img, long long n, int class_num,
+                                                         uint64_t *__restrict__ key_a, uint64_t *__restrict__ key_b, uint32_t *__restrict__ iota) {
+    for (long long r = (long long)blockIdx.x * MAP_BLOCK + threadIdx.x; r < n; r += (long long)gridDim.x * MAP_BLOCK) {
+        const uint64_t c = (uint64_t)class_of((double)rows[(size_t)r * 6 + 5], class_num);
+        const uint64_t k = desc_key(rows[(size_t)r * 6 + 4]);
+        key_a[r] = (c << 32) | k;
+        key_b[r] = (((uint64_t)img[r] * (uint64_t)(class_num + 1) + c) << 32) | k;
+        iota[r] = (uint32_t)r;
+    }
+}
+
+__global__ void class_offsets_kernel(const uint64_t *__restrict__ key_a, long long n, int class_num, int32_t *__restrict__ cls_off) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c <= class_num) cls_off[c] = (int32_t)lower_bound_u64(key_a, n, (uint64_t)c << 32);
+}
+
+__global__ __launch_bounds__(MAP_BLOCK) void gt_count_kernel(const double *__restrict__ gt, const uint8_t *__restrict__ difficult, long long n_gt_rows,
+                                                             int class_num, int32_t *__restrict__ n_gt) {
+    for (long long g = (long long)blockIdx.x * MAP_BLOCK + threadIdx.x; g < n_gt_rows; g += (long long)gridDim.x * MAP_BLOCK) {
+        const int c = class_of(gt[(size_t)g * 6 + 5], class_num);
+        if (c < class_num && !difficult[g]) atomicAdd(&n_gt[c], 1);
+    }
+}
+
+// ---- matching: one wave per (image, class) group --------------------------------------------------------------------------------------
+__global__ __launch_bounds__(MAP_BLOCK) void match_kernel(const float *__restrict__ rows, const uint64_t *__restrict__ key_b, const uint32_t *__restrict__ row_b,
+                                                          long long n, int n_img, int class_num, const double *__restrict__ gt,
+                                                          const int32_t *__restrict__ gt_off, const uint8_t *__restrict__ difficult, uint8_t *taken,
+                                                          double iou_thresh, double o, uint8_t *__restrict__ flags) {
+    const int lane = threadIdx.x & (YK_WAVE - 1);
+    const long long n_groups = (long long)n_img * class_num;
+    for (long long q = (long long)blockIdx.x * MAP_WAVES + (threadIdx.x / YK_WAVE); q < n_groups; q += (long long)gridDim.x * MAP_WAVES) {
+        const int i = (int)(q / class_num), c = (int)(q % class_num);
+        const uint64_t gkey = (uint64_t)i * (uint64_t)(class_num + 1) + (uint64_t)c;
+        const long long lo = lower_bound_u64(key_b, n, gkey << 32);
+        const long long hi = lower_bound_u64(key_b, n, (gkey + 1) << 32);
+        const int g0 = gt_off[i], g1 = gt_off[i + 1];
+        for (long long k = lo; k < hi; ++k) {
+            const uint32_t r = row_b[k];
+            const float *d = rows + (size_t)r * 6;
+            const double b0 = (double)d[0], b1 = (double)d[1], b2 = (double)d[2], b3 = (double)d[3];
+            const double area = (b2 - b0 + o) * (b3 - b1 + o);
+            double best = -1.0;
+            int j = 0x7fffffff;
+            for (int g = g0 + lane; g < g1; g += YK_WAVE) {
+                const double *t = gt + (size_t)g * 6;
+                if (class_of(t[5], class_num) != c) continue;
+                const double t0 = t[0], t1 = t[1], t2 = t[2], t3 = t[3];
+                const double ih = fmin(b2, t2) - fmax(b0, t0) + o;
+                const double iw = fmin(b3, t3) - fmax(b1, t1) + o;
+                const double inter = fmax(ih, 0.0) * fmax(iw, 0.0);
+                const double areas = (t2 - t0 + o) * (t3 - t1 + o);
+                const double uni = area + areas - inter;
+                const double iou = uni > 0.0 ? inter / uni : 0.0;
+                if (iou > best) {                                 // a lane's indices ascend: the first of equal values stays
+                    best = iou;
+                    j = g;
+                }
+            }
+#pragma unroll
+            for (int s = YK_WAVE / 2; s > 0; s >>= 1) {
+                const double ob = __shfl_xor(best, s, YK_WAVE);
+                const int oj = __shfl_xor(j, s, YK_WAVE);
+                if (ob > best || (ob == best && oj < j)) {
+                    best = ob;
+                    j = oj;
+                }
+            }
+            if (lane == 0) {                                      // one lane reads and writes `taken`: program order is the devkit's order
+                uint8_t f = 2;
+                if (best >= iou_thresh && j != 0x7fffffff) {
+                    if (difficult[j]) f = 0;
+                    else if (!taken[j]) {
+                        f = 1;
+                        taken[j] = 1;
+                    }
+                }
+                flags[r] = f;
+            }
+        }
+    }
+}
+
+// ---- curve and AP: one workgroup per class --------------------------------------------------------------------------------------------
+struct AddU64 {
+    __device__ uint64_t operator()(uint64_t a, uint64_t b) const { return a + b; }
+};
+struct MaxF64 {
+    __device__ double operator()(double a, double b) const { return fmax(a, b); }
+};
+
+// inclusive scan over the workgroup (Hillis-Steele through LDS); sh is free again after the call
+template <typename T, typename Op>
+__device__ __forceinline__ T block_scan(T v, T *sh, Op op) {
+    const int t = threadIdx.x;
+    sh[t] = v;
+    __syncthreads();
+    for (int s = 1; s < MAP_BLOCK; s <<= 1) {
+        const T x = t >= s ? op(sh[t - s], sh[t]) : sh[t];
+        __syncthreads();
+        sh[t] = x;
+        __syncthreads();
+    }
+    const T out = sh[t];
+    __syncthreads();
+    return out;
+}
+
+__global__ __launch_bounds__(MAP_BLOCK) void ap_kernel(const uint32_t *__restrict__ row_a, const int32_t *__restrict__ cls_off, const uint8_t *__restrict__ flags,
+                                                       const int32_t *__restrict__ n_gt, int use_07, uint64_t *__restrict__ cum,
+                                                       int32_t *__restrict__ n_det, int32_t *__restrict__ tp, int32_t *__restrict__ fp, double *__restrict__ ap) {
+    __shared__ uint64_t sh_u[MAP_BLOCK];
+    __shared__ double sh_d[MAP_BLOCK];
+    __shared__ uint64_t carry_u;
+    __shared__ double carry_d;
+    const int c = blockIdx.x, t = threadIdx.x;
+    const long long lo = cls_off[c], n = (long long)cls_off[c + 1] - lo;
+    const long long tiles = (n + MAP_BLOCK - 1) / MAP_BLOCK;
+    // forward: cumulative tp (high word) and fp (low word), both < 2^31
+    if (t == 0) carry_u = 0ull;
+    __syncthreads();
+    for (long long base = 0; base < n; base += MAP_BLOCK) {
+        const long long k = base + t;
+        uint64_t v = 0;
+        if (k < n) {
+            const uint8_t f = flags[row_a[lo + k]];
+            v = f == 1 ? (1ull << 32) : (f == 2 ? 1ull : 0ull);
+        }
+        const uint64_t inc = block_scan(v, sh_u, AddU64()) + carry_u;
+        if (k < n) cum[lo + k] = inc;
+        __syncthreads();
+        if (t == MAP_BLOCK - 1) carry_u = inc;
+        __syncthreads();
+    }
+    const int ngt = n_gt[c];
+    if (t == 0) {
+        n_det[c] = (int32_t)n;
+        tp[c] = (int32_t)(carry_u >> 32);
+        fp[c] = (int32_t)(carry_u & 0xffffffffull);
+        if (ngt == 0) ap[c] = __builtin_nan("");
+    }
+    if (ngt == 0) return;
+    // backward: thread 0 holds the LAST row of a tile, so an inclusive max-scan over the threads is the reverse max-scan over the rows
+    const double dgt = (double)ngt;
+    double sum = 0.0, m11[11];
+#pragma unroll
+    for (int q = 0; q < 11; ++q) m11[q] = 0.0;
+    if (t == 0) carry_d = 0.0;
+    __syncthreads();
+    for (long long tile = tiles - 1; tile >= 0; --tile) {
+        const long long k = tile * MAP_BLOCK + (MAP_BLOCK - 1 - t);
+        double prec = 0.0, ctp = 0.0;
+        uint64_t cu = 0;
+        if (k < n) {
+            cu = cum[lo + k];
+            ctp = (double)(uint32_t)(cu >> 32);
+            const double cfp = (double)(uint32_t)(cu & 0xffffffffull);
+            prec = ctp / fmax(ctp + cfp, 2.220446049250313e-16);
+        }
+        const double env = fmax(block_scan(prec, sh_d, MaxF64()), carry_d);
+        if (k < n) {
+            const double rec = ctp / dgt;
+            if (use_07) {
+#pragma unroll
+                for (int q = 0; q < 11; ++q)
+                    if (rec >= (0.0 + (double)q * 0.1) - 1e-12) m11[q] = fmax(m11[q], prec);
+            } else {
+                const uint64_t before = k > 0 ? cum[lo + k - 1] : 0ull;
+                if ((before >> 32) != (cu >> 32)) sum += (rec - (ctp - 1.0) / dgt) * env;      // recall steps at a true positive only
+            }
+        }
+        __syncthreads();
+        if (t == MAP_BLOCK - 1) carry_d = env;
+        __syncthreads();
+    }
+    if (use_07) {
+        double out = 0.0;
+        for (int q = 0; q < 11; ++q) {
+            const double m = block_scan(m11[q], sh_d, MaxF64());
+            if (t == MAP_BLOCK - 1) out += m / 11.0;              // the eleven terms in order, in one thread
+        }
+        if (t == MAP_BLOCK - 1) ap[c] = out;
+    } else {
+        sh_d[t] = sum;
+        __syncthreads();
+        for (int s = MAP_BLOCK / 2; s > 0; s >>= 1) {             // a fixed tree: the same bits every run
+            if (t < s) sh_d[t] += sh_d[t + s];
+            __syncthreads();
+        }
+        if (t == 0) ap[c] = sh_d[0];
+    }
+}
+
+__global__ void map_mean_kernel(const double *__restrict__ ap, int class_num, double *__restrict__ map) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        double s = 0.0;
+        int n = 0;
+        for (int c = 0; c < class_num; ++c)
+            if (ap[c] == ap[c]) {
+                s += ap[c];
+                ++n;
+            }
+        map[0] = n ? s / (double)n : __builtin_nan("");
+    }
+}
+
+// ---- workspace ------------------------------------------------------------------------------------------------------------------------
+struct Work {
+    size_t key_a_in, key_a, key_b_in, key_b, iota, row_a, row_b, cum, taken, cls_off, sort_tmp, sort_bytes, total;
+    unsigned bits_a, bits_b;
+};
+
+inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+int layout(long long n_rows, long long n_gt_rows, int n_img, int class_num, Work *w) {
+    const size_t R = (size_t)(n_rows > 0 ? n_rows : 1), G = (size_t)(n_gt_rows > 0 ? n_gt_rows : 1);
+    size_t at = 0;
+    auto take = [&](size_t bytes) {
+        const size_t o = at;
+        at += up256(bytes);
+        return o;
+    };
+    w->key_a_in = take(R * 8);
+    w->key_a = take(R * 8);
+    w->key_b_in = take(R * 8);
+    w->key_b = take(R * 8);
+    w->iota = take(R * 4);
+    w->row_a = take(R * 4);
+    w->row_b = take(R * 4);
+    w->cum = take(R * 8);
+    w->taken = take(G);
+    w->cls_off = take((size_t)(class_num + 1) * 4);
+    w->bits_a = 32 + bits_for((unsigned long long)class_num);
+    w->bits_b = 32 + bits_for((unsigned long long)(n_img > 0 ? n_img : 1) * (unsigned long long)(class_num + 1));
+    if (w->bits_b > 64) w->bits_b = 64;
+    size_t bytes = 0;
+    if (n_rows > 0) {                                             // size queries only: nothing is launched
+        uint64_t *k = nullptr;
+        uint32_t *v = nullptr;
+        size_t a = 0, b = 0;
+        if (rocprim::radix_sort_pairs(nullptr, a, k, k, v, v, (size_t)n_rows, 0u, w->bits_a) != hipSuccess) return YK_ERR_HIP;
+        if (rocprim::radix_sort_pairs(nullptr, b, k, k, v, v, (size_t)n_rows, 0u, w->bits_b) != hipSuccess) return YK_ERR_HIP;
+        bytes = a > b ? a : b;
+    }
+    w->sort_bytes = bytes;
+    w->sort_tmp = take(bytes ? bytes : 1);
+    w->total = at;
+    return YK_OK;
+}
+
+int check_sizes(const char *who, long long n_rows, long long n_gt_rows, int n_img, int class_num) {
+    if (n_rows < 0 || n_gt_rows < 0 || n_img < 0 || class_num <= 0) {
+        yk_set_error("%s: bad argument", who);
+        return YK_ERR_ARG;
+    }
+    if (n_rows > MAP_MAX_ROWS || n_gt_rows > MAP_MAX_ROWS) {
+        yk_set_error("%s: %lld detection rows / %lld ground-truth rows: more than 2^31-1", who, n_rows, n_gt_rows);
+        return YK_ERR_ARG;
+    }
+    if ((unsigned long long)n_img * (unsigned long long)(class_num + 1) > 0xffffffffull) {
+        yk_set_error("%s: %d images x %d classes do not fit the 32-bit group key", who, n_img, class_num);
+        return YK_ERR_ARG;
+    }
+    return YK_OK;
+}
+
+int check_append(const char *who, const void *src, const void *cnt, long long n_new, const void *rows, const void *img, long long have, long long capacity) {
+    if (!src || !cnt || !rows || !img || n_new < 0 || have < 0 || capacity < 0) {
+        yk_set_error("%s: bad argument", who);
+        return YK_ERR_ARG;
+    }
+    if (have + n_new > MAP_MAX_ROWS) {
+        yk_set_error("%s: %lld + %lld rows: more than 2^31-1", who, have, n_new);
+        return YK_ERR_ARG;
+    }
+    if (have + n_new > capacity) {
+        yk_set_error("%s: %lld + %lld rows do not fit the buffer of %lld", who, have, n_new, capacity);
+        return YK_ERR_ARG;
+    }
+    return YK_OK;
+}
+
+}  // namespace
+
+extern "C" int yk_map_append_packed(const float *d_src, const int32_t *d_offsets, int n_img, int img_base, long long n_new, float *d_rows,
+                                    int32_t *d_img, long long have, long long capacity, void *stream) {
+    const int rc = check_append("yk_map_append_packed", d_src, d_offsets, n_new, d_rows, d_img, have, capacity);
+    if (rc != YK_OK) return rc;
+    if (n_img <= 0 || img_base < 0) {
+        yk_set_error("yk_map_append_packed: bad argument");
+        return YK_ERR_ARG;
+    }
+    if (n_new == 0) return YK_OK;
+    hipLaunchKernelGGL(append_packed_kernel, dim3(grid_for(n_new, MAP_BLOCK)), dim3(MAP_BLOCK), 0, (hipStream_t)stream, d_src, d_offsets, n_img, img_base,
+                       n_new, d_rows + (size_t)have * 6, d_img + have);
+    YK_HIP(hipGetLastError());
+    return YK_OK;
+}
+
+extern "C" int yk_map_append_padded(const float *d_dets, const int32_t *d_counts, int batch, int cap, int img_base, long long n_new, float *d_rows,
+                                    int32_t *d_img, long long have, long long capacity, void *stream) {
+    const int rc = check_append("yk_map_append_padded", d_dets, d_counts, n_new, d_rows, d_img, have, capacity);
+    if (rc != YK_OK) return rc;
+    if (batch <= 0 || cap <= 0 || img_base < 0) {
+        yk_set_error("yk_map_append_padded: bad argument");
+        return YK_ERR_ARG;
+    }
+    if (n_new == 0) return YK_OK;
+    hipLaunchKernelGGL(append_padded_kernel, dim3(grid_for(batch, 1)), dim3(MAP_BLOCK), 0, (hipStream_t)stream, d_dets, d_counts, batch, cap, img_base,
+                       n_new, d_rows + (size_t)have * 6, d_img + have);
+    YK_HIP(hipGetLastError());
+    return YK_OK;
+}
+
+extern "C" int yk_map_workspace_bytes(long long n_rows, long long n_gt_rows, int n_img, int class_num, size_t *bytes) {
+    const int rc = check_sizes("yk_map_workspace_bytes", n_rows, n_gt_rows, n_img, class_num);
+    if (rc != YK_OK) return rc;
+    if (!bytes) {
+        yk_set_error("yk_map_workspace_bytes: bad argument");
+        return YK_ERR_ARG;
+    }
+    Work w;
+    if (layout(n_rows, n_gt_rows, n_img, class_num, &w) != YK_OK) {
+        yk_set_error("yk_map_workspace_bytes: radix sort size query failed");
+        return YK_ERR_HIP;
+    }
+    *bytes = w.total;
+    return YK_OK;
+}
+
+extern "C" int yk_map_eval(const float *d_rows, const int32_t *d_img, long long n_rows, int n_img, const double *d_gt, const int32_t *d_gt_off,
+                           const uint8_t *d_difficult, long long n_gt_rows, int class_num, double iou_thresh, int use_07_metric, int plus_one,
+                           void *d_work, size_t work_bytes, uint8_t *d_flags, int32_t *d_n_gt, int32_t *d_n_det, int32_t *d_tp, int32_t *d_fp,
+                           double *d_ap, double *d_map, void *stream) {
+    const int rc = check_sizes("yk_map_eval", n_rows, n_gt_rows, n_img, class_num);
+    if (rc != YK_OK) return rc;
+    if (!d_gt_off || !d_work || !d_n_gt || !d_n_det || !d_tp || !d_fp || !d_ap || !d_map || (n_rows > 0 && (!d_rows || !d_img || !d_flags)) ||
+        (n_gt_rows > 0 && (!d_gt || !d_difficult)) || !(iou_thresh == iou_thresh)) {
+        yk_set_error("yk_map_eval: bad argument");
+        return YK_ERR_ARG;
+    }
+    Work w;
+    if (layout(n_rows, n_gt_rows, n_img, class_num, &w) != YK_OK) {
+        yk_set_error("yk_map_eval: radix sort size query failed");
+        return YK_ERR_HIP;
+    }
+    if (work_bytes < w.total) {
+        yk_set_error("yk_map_eval: workspace of %zu bytes, %zu needed (yk_map_workspace_bytes)", work_bytes, w.total);
+        return YK_ERR_ARG;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    char *base = (char *)d_work;
+    uint64_t *key_a_in = (uint64_t *)(base + w.key_a_in), *key_a = (uint64_t *)(base + w.key_a);
+    uint64_t *key_b_in = (uint64_t *)(base + w.key_b_in), *key_b = (uint64_t *)(base + w.key_b);
+    uint32_t *iota = (uint32_t *)(base + w.iota), *row_a = (uint32_t *)(base + w.row_a), *row_b = (uint32_t *)(base + w.row_b);
+    uint64_t *cum = (uint64_t *)(base + w.cum);
+    uint8_t *taken = (uint8_t *)(base + w.taken);
+    int32_t *cls_off = (int32_t *)(base + w.cls_off);
+
+    YK_HIP(hipMemsetAsync(d_n_gt, 0, (size_t)class_num * 4, st));
+    YK_HIP(hipMemsetAsync(cls_off, 0, (size_t)(class_num + 1) * 4, st));
+    if (n_gt_rows > 0) {
+        YK_HIP(hipMemsetAsync(taken, 0, (size_t)n_gt_rows, st));
+        hipLaunchKernelGGL(gt_count_kernel, dim3(grid_for(n_gt_rows, MAP_BLOCK)), dim3(MAP_BLOCK), 0, st, d_gt, d_difficult, n_gt_rows, class_num, d_n_gt);
+    }
+    if (n_rows > 0) {
+        YK_HIP(hipMemsetAsync(d_flags, 0, (size_t)n_rows, st));   // rows of no class in [0, class_num) stay 0
+        hipLaunchKernelGGL(keys_kernel, dim3(grid_for(n_rows, MAP_BLOCK)), dim3(MAP_BLOCK), 0, st, d_rows, d_img, n_rows, class_num, key_a_in, key_b_in, iota);
+        YK_HIP(hipGetLastError());
+        size_t tmp = w.sort_bytes;
+        YK_HIP(rocprim::radix_sort_pairs(base + w.sort_tmp, tmp, key_a_in, key_a, iota, row_a, (size_t)n_rows, 0u, w.bits_a, st));
+        tmp = w.sort_bytes;
+        YK_HIP(rocprim::radix_sort_pairs(base + w.sort_tmp, tmp, key_b_in, key_b, iota, row_b, (size_t)n_rows, 0u, w.bits_b, st));
+        hipLaunchKernelGGL(class_offsets_kernel, dim3((unsigned)(class_num + 1 + 63) / 64), dim3(64), 0, st, key_a, n_rows, class_num, cls_off);
+        if (n_img > 0)
+            hipLaunchKernelGGL(match_kernel, dim3(grid_for((long long)n_img * class_num, MAP_WAVES)), dim3(MAP_BLOCK), 0, st, d_rows, key_b, row_b, n_rows, n_img,
+                               class_num, d_gt, d_gt_off, d_difficult, taken, iou_thresh, plus_one ? 1.0 : 0.0, d_flags);
+    }
+    hipLaunchKernelGGL(ap_kernel, dim3((unsigned)class_num), dim3(MAP_BLOCK), 0, st, row_a, cls_off, d_flags, d_n_gt, use_07_metric ? 1 : 0, cum, d_n_det,
+                       d_tp, d_fp, d_ap);
+    hipLaunchKernelGGL(map_mean_kernel, dim3(1), dim3(1), 0, st, d_ap, class_num, d_map);
+    YK_HIP(hipGetLastError());
+    return YK_OK;
+}

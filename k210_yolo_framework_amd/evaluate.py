@@ -1,0 +1,178 @@
+"""`make eval` - VOC mAP of a checkpoint, network and metric both on the GPU.
+
+    python keras_eval.py CKPT [network flags of keras_inference.py] (--ann LIST.npy [--all] [--limit N] | --synthetic N)
+                              [--precision f16x2|f16|kpu] [--obj_thresh 0.05] [--nms_iou 0.5] [--iou_thresh 0.5] [--voc07 True]
+                              [--out eval.json] [--dump_rows rows.npz]
+
+CKPT: a Keras `.h5` / `.npz` checkpoint (float modes, through engine.Pipeline with several batches in flight) or a `.kmodel` / `.kfpkg`
+(`--precision kpu`, the K210 KPU's exact integer arithmetic through engine.KpuPlan).  The images are the validation head of the list
+make_voc_list.py writes (the whole list with --all), or N generated images with known boxes as `make train SYNTHETIC=N` trains on,
+drawn from a seed of their own.  Every batch's detections go from the decode straight into map_gpu.MapEvaluator, in device memory; the
+metric is voc_eval.evaluate's.  Prints the per-class AP table and the mAP, writes them to `eval.json` next to the checkpoint (or --out).
+The reference ships no evaluator; tools/map_eval.py is the host-side developer script this replaces as the product's entry point."""
+from __future__ import annotations
+
+import argparse
+import json
+import sys
+from collections import deque
+from pathlib import Path
+
+import numpy as np
+
+from .helper import INFO, Helper, VOC_ANCHORS
+from .yolonet import MODEL_DEFS
+
+SYNTHETIC_SEED = 7919        # `make train` draws its generated images from --rand_seed (3 in the Makefile, 6 by default)
+CAP_NOTE = 'at most 30 detections per class and image as keras_inference.py:125'
+
+
+def ground_truth_rows(boxes, img_hw) -> np.ndarray:
+    """[n,5] (class, cx, cy, w, h) relative to the image -> [n,6] float64 (top, left, bottom, right, 1, class) in its pixels."""
+    boxes = np.asarray(boxes, np.float64).reshape(-1, 5)
+    ih, iw = float(img_hw[0]), float(img_hw[1])
+    cx, cy, w, h = boxes[:, 1] * iw, boxes[:, 2] * ih, boxes[:, 3] * iw, boxes[:, 4] * ih
+    return np.stack([cy - h / 2, cx - w / 2, cy + h / 2, cx + w / 2, np.ones(len(boxes)), boxes[:, 0]], 1)
+
+
+def parse(argv=None):
+    p = argparse.ArgumentParser(description='VOC mAP of a checkpoint, evaluated on the GPU')
+    p.add_argument('pre_ckpt', type=str, help='.h5 / .npz weights, or a .kmodel / .kfpkg with --precision kpu')
+    p.add_argument('--ann', type=str, default=None, help='list file as make_voc_list.py writes (default data/<train_set>_img_ann.npy)')
+    p.add_argument('--synthetic', type=int, default=0, help='evaluate on N generated images with known boxes instead of --ann')
+    p.add_argument('--synthetic_seed', type=int, default=SYNTHETIC_SEED, help='seed of the generated images (not the training seed)')
+    p.add_argument('--train_set', type=str, default='voc')
+    p.add_argument('--class_num', type=int, default=20)
+    p.add_argument('--model_def', type=str, default='yolo_mobilev1')
+    p.add_argument('--depth_multiplier', type=float, choices=[0.5, 0.75, 1.0], default=0.75)
+    p.add_argument('--image_size', type=int, default=(224, 320), nargs='+')
+    p.add_argument('--output_size', type=int, default=(7, 10, 14, 20), nargs='+')
+    p.add_argument('--precision', type=str, choices=['f16', 'f16x2', 'kpu'], default='f16x2')
+    p.add_argument('--obj_thresh', type=float, default=0.05)
+    p.add_argument('--nms_iou', type=float, default=0.5, help='IoU of the per-class NMS (keras_inference.py --iou_thresh)')
+    p.add_argument('--iou_thresh', type=float, default=0.5, help='IoU a detection needs with a ground-truth box')
+    p.add_argument('--voc07', type=str, choices=['True', 'False'], default='False', help='11-point AP')
+    p.add_argument('--all', action='store_true', help='evaluate the whole list, not its validation head')
+    p.add_argument('--limit', type=int, default=0)
+    p.add_argument('--batch', type=int, default=32)
+    p.add_argument('--depth', type=int, default=3, help='batches in flight (float modes)')
+    p.add_argument('--out', type=str, default=None, help='result file (default: eval.json next to the checkpoint)')
+    p.add_argument('--dump_rows', type=str, default=None, help='also write the detections and the ground truth that were scored (.npz)')
+    a = p.parse_args(sys.argv[1:] if argv is None else argv)
+    if (a.precision == 'kpu') != a.pre_ckpt.endswith(('.kmodel', '.kfpkg')):
+        p.error('--precision kpu runs a .kmodel / .kfpkg checkpoint, and only it does (the float modes take .h5 / .npz)')
+    if a.synthetic and a.ann:
+        p.error('--synthetic N replaces --ann')
+    return a
+
+
+def _items(a, h: Helper):
+    """[(uint8 image or path, boxes [n,5])] to evaluate."""
+    from . import engine
+    if a.synthetic:
+        from .training import synthetic_list
+        return synthetic_list(int(a.synthetic), tuple(int(v) for v in h.in_hw[0]), a.class_num, a.synthetic_seed)
+    ann = Path(a.ann or f'data/{a.train_set}_img_ann.npy')
+    if not ann.exists():
+        raise engine.YkError(f'{ann} not found (make_voc_list.py output); pass --synthetic N for generated data')
+    rows = np.load(str(ann), allow_pickle=True)
+    n_val = int(len(rows) * h.validation_split)
+    rows = rows if a.all else rows[:n_val]
+    return [(r[0], r[1]) for r in (rows[:a.limit] if a.limit else rows)]
+
+
+def _load(h: Helper, item):
+    img, boxes = item
+    if not isinstance(img, np.ndarray):
+        img = h._read_img(str(img))
+    return np.ascontiguousarray(img[..., :3], np.uint8), np.asarray(boxes, np.float64)
+
+
+def run(a, h: Helper, model, items, ev) -> None:
+    """Every image of `items` through the network and the decode; detections and ground truth into `ev`."""
+    import torch
+    from . import engine
+    in_hw = tuple(int(v) for v in h.in_hw[0])
+    B = max(1, min(int(a.batch), len(items)))
+    if a.precision == 'kpu':
+        plan = model._plan(B)
+        cfg = engine.make_decode_cfg(h.anchors, h.class_num, h.in_hw[0], h.out_hw)
+        for k in range(0, len(items), B):
+            loaded = [_load(h, it) for it in items[k:k + B]]
+            frames = torch.cat([engine.letterbox_u8(torch.from_numpy(im[None]).cuda(), in_hw) for im, _ in loaded])
+            plan.run_u8(frames)
+            shapes = np.asarray([im.shape[:2] for im, _ in loaded], np.float32)
+            dets, counts = engine.decode_py(cfg, plan.outputs(), len(loaded), shapes, a.obj_thresh, a.nms_iou)
+            ev.add(dets, counts, [ground_truth_rows(b, im.shape[:2]) for im, b in loaded])
+        return
+    pipe = engine.Pipeline(model.spec, model.get_weights(), h.anchors, max_batch=B, depth=max(1, int(a.depth)), precision=a.precision)
+    pending = deque()                                       # (dets, counts, stream, ground truth) of the batches in flight
+
+    def drain():
+        dets, counts, stream, gts = pending.popleft()
+        ev.add(dets, counts, gts, stream=stream)           # on the slot's stream: the rows never leave device memory
+
+    try:
+        for k in range(0, len(items), B):
+            if len(pending) == pipe.depth:                  # the slot about to be reused still holds an unread result
+                drain()
+            loaded = [_load(h, it) for it in items[k:k + B]]
+            slot = pipe.next_slot()
+            buf, st = pipe.input(slot), pipe.streams[slot]
+            with torch.cuda.stream(st):
+                for j, (im, _) in enumerate(loaded):
+                    engine.letterbox_u8(torch.from_numpy(im[None]).to(buf.device, non_blocking=False), in_hw, stream=st, out=buf[j:j + 1])
+            shapes = np.asarray([im.shape[:2] for im, _ in loaded], np.float32)
+            dets, counts, stream = pipe.submit(None, image_hw=shapes, obj_thresh=a.obj_thresh, iou_thresh=a.nms_iou, batch=len(loaded))
+            pending.append((dets, counts, stream, [ground_truth_rows(b, im.shape[:2]) for im, b in loaded]))
+        while pending:
+            drain()
+        pipe.wait()
+        ev.synchronize()                                    # the appends ran on the slots' streams, which close() destroys
+    finally:
+        pipe.close()
+
+
+def main(argv=None):
+    a = parse(argv)
+    from . import engine
+    from .map_gpu import MapEvaluator
+    engine.require_gpu()
+    anchor_file = Path(f'data/{a.train_set}_anchor.npy')
+    h = Helper(None, a.class_num, str(anchor_file) if anchor_file.exists() else VOC_ANCHORS, np.reshape(np.array(a.image_size), (-1, 2)),
+               np.reshape(np.array(a.output_size), (-1, 2)))
+    model, _ = MODEL_DEFS[a.model_def]([a.image_size[0], a.image_size[1], 3], len(h.anchors[0]), a.class_num, alpha=a.depth_multiplier,
+                                       precision=a.precision)
+    model.load_weights(a.pre_ckpt)
+    print(INFO, f' Load CKPT {a.pre_ckpt}')
+    items = _items(a, h)
+    if not items:
+        raise engine.YkError('evaluate: no images to evaluate')
+    voc07 = a.voc07 == 'True'
+    ev = MapEvaluator(a.class_num, a.iou_thresh, voc07)
+    run(a, h, model, items, ev)
+    r = ev.result()
+    print(f'{a.precision}: mAP {100 * r["map"]:.2f} over {len(items)} images ({"VOC07 11-point" if voc07 else "area"} AP, IoU {a.iou_thresh}; '
+          f'obj_thresh {a.obj_thresh}, {CAP_NOTE})')
+    for c in range(a.class_num):
+        if r['n_gt'][c]:
+            print(f'   class {c:2d}: AP {100 * r["ap"][c]:6.2f}   gt {r["n_gt"][c]:5d}  det {r["n_det"][c]:6d}  tp {r["tp"][c]:5d}')
+    num = lambda v: None if v != v else float(v)
+    report = {'ckpt': str(a.pre_ckpt), 'precision': a.precision, 'images': len(items), 'rows': int(ev.n_rows), 'obj_thresh': a.obj_thresh,
+              'nms_iou': a.nms_iou, 'iou_thresh': a.iou_thresh, 'voc07': voc07, 'note': CAP_NOTE, 'map': num(r['map']),
+              'ap': [num(v) for v in r['ap']], 'n_gt': r['n_gt'].tolist(), 'n_det': r['n_det'].tolist(), 'tp': r['tp'].tolist(),
+              'fp': r['fp'].tolist()}
+    out = Path(a.out) if a.out else Path(a.pre_ckpt).resolve().parent / 'eval.json'
+    out.write_text(json.dumps(report, indent=1))
+    print(INFO, f' wrote {out}')
+    if a.dump_rows:
+        rows, img = ev.rows()
+        gt, gt_off, diff = ev.ground_truth()
+        np.savez(a.dump_rows, rows=rows, image=img, gt=gt, gt_offsets=gt_off, difficult=diff, flags=r['flags'])
+    return report
+
+
+cli = main
+
+if __name__ == '__main__':
+    main()

@@ -57,14 +57,15 @@ def synthetic_list(n: int, in_hw, class_num: int, seed: int):
     return out
 
 
-def batches(h: Helper, items, batch_size: int, rng, shuffle: bool, augment=None):
+def batches(h: Helper, items, batch_size: int, rng, shuffle: bool, augment=None, with_boxes: bool = False):
     """tools/utils.py:417-450: (normalised image [B,H,W,3] float32, labels per layer [B,h,w,A,5+C] float32).  augment=(seed, epoch):
-    every sample augmented with its row of augment.param_table(seed, epoch, len(items)), like InputPipeline(augment=True)."""
+    every sample augmented with its row of augment.param_table(seed, epoch, len(items)), like InputPipeline(augment=True).
+    with_boxes: a third element, each sample's boxes [n,5] (class, cx, cy, w, h) relative to the letterboxed frame."""
     from . import augment as aug_mod
     table = None if augment is None else aug_mod.param_table(augment[0], augment[1], len(items))
     order = rng.permutation(len(items)) if shuffle else np.arange(len(items))
     for s in range(0, len(order) - batch_size + 1, batch_size):             # drop_remainder=True (utils.py:447)
-        xs, ys = [], [[] for _ in range(len(h.anchors))]
+        xs, ys, bs = [], [[] for _ in range(len(h.anchors))], []
         for i in order[s:s + batch_size]:
             img, boxes = items[i]
             if isinstance(img, (str, os.PathLike)):
@@ -73,15 +74,19 @@ def batches(h: Helper, items, batch_size: int, rng, shuffle: bool, augment=None)
             img, boxes = h._process_img(img, boxes, is_training=table is not None, is_resize=True,
                                         aug=None if table is None else table[i])
             xs.append(img.astype(np.float32))
+            bs.append(boxes)
             for l, lab in enumerate(h.box_to_label(boxes)):
                 ys[l].append(lab)
-        yield np.stack(xs), [np.stack(y).astype(np.float32) for y in ys]
+        if with_boxes:
+            yield np.stack(xs), [np.stack(y).astype(np.float32) for y in ys], bs
+        else:
+            yield np.stack(xs), [np.stack(y).astype(np.float32) for y in ys]
 
 
 def main(args, train_set, class_num, pre_ckpt, model_def, depth_multiplier, is_augmenter, image_size, output_size, batch_size,
          rand_seed, max_nrof_epochs, init_learning_rate, learning_rate_decay_factor, obj_weight, noobj_weight, wh_weight,
          obj_thresh, iou_thresh, vaildation_split, log_dir, is_prune, initial_sparsity=0.5, final_sparsity=0.9, end_epoch=5,
-         frequency=100, synthetic=0, max_steps=0, is_qat='False', qat_momentum=0.99, qat_observe=8):
+         frequency=100, synthetic=0, max_steps=0, is_qat='False', qat_momentum=0.99, qat_observe=8, val_map='False', val_map_obj=0.05):
     import torch
     from .train import Trainer
     prune = is_prune == 'True'
@@ -185,11 +190,16 @@ def main(args, train_set, class_num, pre_ckpt, model_def, depth_multiplier, is_a
             tr.apply_masks()                                                    # tfmot on_epoch_end: validation sees masked weights
             if rank == 0:
                 print(sparsity_line(tr, spec, epoch), flush=True)
-        val = validate(tr, h, spec, per_rank, rank) if rank == 0 and len(h.test_list) >= per_rank else None
+        val = vmap = None
+        if rank == 0 and len(h.test_list) >= per_rank:
+            if val_map == 'True':                                               # opt-in: the pass also scores its detections
+                val, vmap = validate(tr, h, spec, per_rank, rank, map_obj=val_map_obj)
+            else:
+                val = validate(tr, h, spec, per_rank, rank)
         if rank == 0:
             print(f'epoch {epoch + 1}: {seen} steps, mean loss {run / max(seen, 1):.4f}, ' +
-                  (f'val_loss {val:.4f}, ' if val is not None else '') + f'{time.time() - t0:.1f}s, input pipeline {pipe_rate:.0f} images/s/rank',
-                  flush=True)
+                  (f'val_loss {val:.4f}, ' if val is not None else '') + f'{time.time() - t0:.1f}s, input pipeline {pipe_rate:.0f} images/s/rank' +
+                  (f', val_mAP {vmap:.4f}' if vmap is not None else ''), flush=True)
         for c in tr.counts:
             c.zero_()                                                           # Keras resets metrics every epoch
         if max_steps and steps >= max_steps:
@@ -228,19 +238,33 @@ def sparsity_line(tr, spec, epoch: int) -> str:
             ' '.join(f'{nm} {rep[nm + "/kernel"]["sparsity"]:.4f}' for nm in heads))
 
 
-def validate(tr, h: Helper, spec, batch: int, rank: int) -> float:
-    """validation_data pass (keras_train.py:96-98): inference-mode forward on the engine (the f16x2 mode, the boundary default) + the same loss."""
+def validate(tr, h: Helper, spec, batch: int, rank: int, map_obj=None):
+    """validation_data pass (keras_train.py:96-98): inference-mode forward on the engine (the f16x2 mode, the boundary default) + the same loss.
+    map_obj (`--val_map True`): the plan's outputs are also decoded on the GPU at this objectness threshold (NMS and match IoU = the run's
+    iou_thresh) and scored in device memory by map_gpu.MapEvaluator against the validation boxes in network-input pixels - the letterboxed
+    frame is the image; -> (val_loss, val_mAP) instead of val_loss."""
     import torch
     tot, n = 0.0, 0
     e = 5 + spec.class_num
+    ev = cfg = None
+    if map_obj is not None:
+        from .evaluate import ground_truth_rows
+        from .map_gpu import MapEvaluator
+        ev = MapEvaluator(spec.class_num, tr.hyper['iou_thresh'], device=tr.dev.index or 0)
+        cfg = engine.make_decode_cfg(h.anchors, spec.class_num, spec.in_hw, spec.out_hw())
     with engine.Plan(spec, tr.export_weights(), max_batch=batch, device=tr.dev.index or 0) as plan:   # freed on exit, every epoch
-        for x, ys in batches(h, h.test_list, batch, np.random.default_rng(0), shuffle=False):
+        for x, ys, *boxes in batches(h, h.test_list, batch, np.random.default_rng(0), shuffle=False, with_boxes=ev is not None):
             plan.run_f32(torch.from_numpy(x).cuda())
+            if ev is not None:
+                dets, counts = engine.decode_py(cfg, plan.outputs(), batch, None, float(map_obj), tr.hyper['iou_thresh'])
+                ev.add(dets, counts, [ground_truth_rows(b, spec.in_hw) for b in boxes[0]])
             for li, (o, yt) in enumerate(zip(plan.outputs(), ys)):
                 yp = o[:batch].reshape(batch, *spec.tensors[spec.outputs[li]][:2], spec.anchor_num, e).contiguous()
                 loss6, _, _ = engine.yolo_loss(torch.from_numpy(yt).cuda(), yp, tr.anchors[li], batch_size=batch, want_grad=False, **tr.hyper)
                 tot += float(loss6[0])
             n += 1
+    if ev is not None:
+        return tot / max(n, 1), ev.result()['map']
     return tot / max(n, 1)
 
 
@@ -276,12 +300,14 @@ def cli(argv=None):
     p.add_argument('--qat_observe', type=int, default=8, help='batches of epoch 0 that only set the activation ranges')
     p.add_argument('--synthetic', type=int, default=0, help='train on N generated images instead of data/<set>_img_ann.npy')
     p.add_argument('--max_steps', type=int, default=0)
+    p.add_argument('--val_map', type=str, choices=['True', 'False'], default='False', help='append val_mAP (VOC, on the GPU) to the epoch line')
+    p.add_argument('--val_map_obj', type=float, default=0.05, help='objectness threshold of the detections val_mAP scores')
     a = p.parse_args(sys.argv[1:] if argv is None else argv)
     return main(a, a.train_set, a.class_num, a.pre_ckpt, a.model_def, a.depth_multiplier, a.augmenter, a.image_size, a.output_size,
                 a.batch_size, a.rand_seed, a.max_nrof_epochs, a.init_learning_rate, a.learning_rate_decay_factor, a.obj_weight,
                 a.noobj_weight, a.wh_weight, a.obj_thresh, a.iou_thresh, a.vaildation_split, a.log_dir, a.is_prune,
                 a.prune_initial_sparsity, a.prune_final_sparsity, a.prune_end_epoch, a.prune_frequency, a.synthetic, a.max_steps,
-                a.qat, a.qat_momentum, a.qat_observe)
+                a.qat, a.qat_momentum, a.qat_observe, a.val_map, a.val_map_obj)
 
 
 if __name__ == '__main__':
