@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "yk_conv.h"
+#include "yk_plan_graph.h"
 
 namespace {
 
@@ -60,15 +61,10 @@ float h2f_bits(uint16_t h) {
 }
 
 enum { K_FIRST = 1, K_DW, K_IGEMM, K_POOL, K_ADD, K_U8MAX, K_REDUCE, K_REDUCE_PW };
-enum { T_REAL = 0, T_UP = 1, T_CAT = 2 };
 
-struct tinfo {
-    int h = 0, w = 0, c = 0, cp = 0;
-    int kind = T_REAL, src0 = -1, src1 = -1;
-    bool net_out = false, is_input = false;
+struct tinfo : yk_gtens {
     yk_half *d = nullptr;
     float *d32 = nullptr;
-    int uses = 0;
 };
 
 struct launch {
@@ -171,15 +167,7 @@ extern "C" int yk_plan_create_ex(yk_plan_t **out, const int32_t *ops, int n_ops,
         return code;
     };
 
-    p->T.resize(n_tensors);
-    for (int i = 0; i < n_tensors; ++i) {
-        tinfo &t = p->T[i];
-        t.h = tensors[4 * i];
-        t.w = tensors[4 * i + 1];
-        t.c = tensors[4 * i + 2];
-        t.cp = yk_pad8(t.c);
-        t.is_input = tensors[4 * i + 3] != 0;
-    }
+    yk_graph_tensors(p->T, tensors, n_tensors);
     if (!p->T[0].is_input || p->T[0].c != 3) {
         yk_set_error("yk_plan_create: tensor 0 must be the 3-channel network input");
         return fail(YK_ERR_UNSUPPORTED);
@@ -205,48 +193,10 @@ extern "C" int yk_plan_create_ex(yk_plan_t **out, const int32_t *ops, int n_ops,
         yk_set_error("yk_plan_create_ex: unknown precision %d", precision);
         return fail(YK_ERR_ARG);
     }
-    // pass 1: views, use counts, output flags
-    for (int i = 0; i < n_ops; ++i) {
-        const int32_t *o = ops + (size_t)i * YK_OP_FIELDS;
-        const int ty = o[YK_F_TYPE], in0 = o[YK_F_IN0], in1 = o[YK_F_IN1], ot = o[YK_F_OUT];
-        if (in0 < 0 || in0 >= n_tensors || ot <= 0 || ot >= n_tensors || in1 >= n_tensors) {
-            yk_set_error("yk_plan_create: op %d has a bad tensor id", i);
-            return fail(YK_ERR_ARG);
-        }
-        p->T[in0].uses++;
-        if (in1 >= 0) p->T[in1].uses++;
-        if (ty == YK_OP_UPSAMPLE) {
-            p->T[ot].kind = T_UP;
-            p->T[ot].src0 = in0;
-        } else if (ty == YK_OP_CONCAT) {
-            p->T[ot].kind = T_CAT;
-            p->T[ot].src0 = in0;
-            p->T[ot].src1 = in1;
-        }
-        if ((ty == YK_OP_CONV) && (o[YK_F_FLAGS] & YK_FLAG_NET_OUTPUT)) p->T[ot].net_out = true;
-        if ((ty == YK_OP_CONV || ty == YK_OP_DWCONV) &&
-            ((size_t)std::max(o[YK_F_W_OFF], std::max(o[YK_F_SCALE_OFF], o[YK_F_BIAS_OFF])) >= blob_len ||
-             o[YK_F_W_OFF] < 0)) {
-            yk_set_error("yk_plan_create: op %d weight offset outside the blob", i);
-            return fail(YK_ERR_ARG);
-        }
-    }
-    for (int t : p->outputs) p->T[t].uses++;
-
-    // fusion decisions need the op list; decide ADD-folding first
-    std::vector<int> add_of(n_ops, -1);   // conv op i -> index of the ADD folded into it
-    std::vector<char> skip(n_ops, 0);
-    for (int i = 0; i + 1 < n_ops; ++i) {
-        const int32_t *o = ops + (size_t)i * YK_OP_FIELDS, *q = o + YK_OP_FIELDS;
-        if (o[YK_F_TYPE] == YK_OP_CONV && q[YK_F_TYPE] == YK_OP_ADD && !(o[YK_F_FLAGS] & YK_FLAG_NET_OUTPUT)) {
-            const int y = o[YK_F_OUT];
-            const int other = (q[YK_F_IN0] == y) ? q[YK_F_IN1] : (q[YK_F_IN1] == y ? q[YK_F_IN0] : -1);
-            if (other >= 0 && other != y && p->T[y].uses == 1 && p->T[other].kind == T_REAL && !p->T[other].is_input) {
-                add_of[i] = i + 1;
-                skip[i + 1] = 1;
-            }
-        }
-    }
+    // pass 1: views, use counts, output flags; fusion decisions need the op list, ADD-folding is decided first
+    std::vector<int> add_of;              // conv op i -> index of the ADD folded into it
+    std::vector<char> skip;
+    if ((rc = yk_graph_analyse(p->T, ops, n_ops, blob_len, p->outputs, add_of, skip))) return fail(rc);
     // depthwise -> pointwise fusion (decided here, realised below)
     const bool fuse_dwpw = env_flag("YK_FUSE_DWPW", true);
     std::vector<int> dw_of(n_ops, -1);    // 1x1 conv op i -> index of the DWCONV fused in front of it

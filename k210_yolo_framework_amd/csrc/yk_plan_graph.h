@@ -1,0 +1,79 @@
+// yk_plan_graph.h — the op-graph analysis both plan builders start from (host only): yk_plan_create_ex's f16 path (yk_engine.hip) and
+// yk_xplan_create (yk_xplan_build.h).  Tensor table, op validation, use counts, UpSampling2D / Concatenate views, network-output flags
+// and the residual Adds that fold into their producing conv.
+#pragma once
+#include <algorithm>
+#include <vector>
+
+#include "yk_conv.h"
+
+enum { T_REAL = 0, T_UP = 1, T_CAT = 2 };
+
+// what the analysis knows of a tensor; each plan's tensor struct derives from it and adds its device pointers
+struct yk_gtens {
+    int h = 0, w = 0, c = 0, cp = 0;
+    int kind = T_REAL, src0 = -1, src1 = -1;
+    bool net_out = false, is_input = false;
+    int uses = 0;
+};
+
+template <class TENS>
+static void yk_graph_tensors(std::vector<TENS> &T, const int32_t *tensors, int n_tensors) {
+    T.resize(n_tensors);
+    for (int i = 0; i < n_tensors; ++i) {
+        TENS &t = T[i];
+        t.h = tensors[4 * i];
+        t.w = tensors[4 * i + 1];
+        t.c = tensors[4 * i + 2];
+        t.cp = yk_pad8(t.c);
+        t.is_input = tensors[4 * i + 3] != 0;
+    }
+}
+
+// views, use counts (the network outputs count as a use), output flags; then add_of[i] = index of the Add folded into conv op i's
+// epilogue and skip[that Add] = 1.  YK_ERR_ARG (with the error text set) for a bad tensor id or a weight offset outside the blob.
+template <class TENS>
+static int yk_graph_analyse(std::vector<TENS> &T, const int32_t *ops, int n_ops, size_t blob_len, const std::vector<int> &outputs,
+                            std::vector<int> &add_of, std::vector<char> &skip) {
+    const int n_tensors = (int)T.size();
+    for (int i = 0; i < n_ops; ++i) {
+        const int32_t *o = ops + (size_t)i * YK_OP_FIELDS;
+        const int ty = o[YK_F_TYPE], in0 = o[YK_F_IN0], in1 = o[YK_F_IN1], ot = o[YK_F_OUT];
+        if (in0 < 0 || in0 >= n_tensors || ot <= 0 || ot >= n_tensors || in1 >= n_tensors) {
+            yk_set_error("yk_plan_create: op %d has a bad tensor id", i);
+            return YK_ERR_ARG;
+        }
+        T[in0].uses++;
+        if (in1 >= 0) T[in1].uses++;
+        if (ty == YK_OP_UPSAMPLE) {
+            T[ot].kind = T_UP;
+            T[ot].src0 = in0;
+        } else if (ty == YK_OP_CONCAT) {
+            T[ot].kind = T_CAT;
+            T[ot].src0 = in0;
+            T[ot].src1 = in1;
+        }
+        if ((ty == YK_OP_CONV) && (o[YK_F_FLAGS] & YK_FLAG_NET_OUTPUT)) T[ot].net_out = true;
+        if ((ty == YK_OP_CONV || ty == YK_OP_DWCONV) &&
+            ((size_t)std::max(o[YK_F_W_OFF], std::max(o[YK_F_SCALE_OFF], o[YK_F_BIAS_OFF])) >= blob_len ||
+             o[YK_F_W_OFF] < 0)) {
+            yk_set_error("yk_plan_create: op %d weight offset outside the blob", i);
+            return YK_ERR_ARG;
+        }
+    }
+    for (int t : outputs) T[t].uses++;
+    add_of.assign(n_ops, -1);
+    skip.assign(n_ops, 0);
+    for (int i = 0; i + 1 < n_ops; ++i) {      // residual Add folded into the producing conv's epilogue
+        const int32_t *o = ops + (size_t)i * YK_OP_FIELDS, *q = o + YK_OP_FIELDS;
+        if (o[YK_F_TYPE] == YK_OP_CONV && q[YK_F_TYPE] == YK_OP_ADD && !(o[YK_F_FLAGS] & YK_FLAG_NET_OUTPUT)) {
+            const int y = o[YK_F_OUT];
+            const int other = (q[YK_F_IN0] == y) ? q[YK_F_IN1] : (q[YK_F_IN1] == y ? q[YK_F_IN0] : -1);
+            if (other >= 0 && other != y && T[y].uses == 1 && T[other].kind == T_REAL && !T[other].is_input) {
+                add_of[i] = i + 1;
+                skip[i + 1] = 1;
+            }
+        }
+    }
+    return YK_OK;
+}
