@@ -13,6 +13,8 @@
 #   make eval        CKPT=yolo_model.h5|yolo.kmodel [PRECISION=f16x2|f16|kpu] [ANN=data/voc_img_ann.npy | SYNTHETIC=256] [EVALOBJ=0.05] [VOC07=True]:
 #                    VOC mAP of the checkpoint, network and metric on the GPU; prints the per-class AP table, writes eval.json beside CKPT
 #                    (make train VALMAP=True appends val_mAP to every epoch line)
+#   make detect      CKPT=yolo_model.h5|yolo.kmodel SRC=folder|list.txt [OUTDIR=out] [DRAW=True|False] [PRECISION=...]: every picture of SRC through
+#                    the pipeline; writes OUTDIR/detections.json and, with DRAW=True, OUTDIR/<stem>_res.jpg (boxes and labels drawn on the GPU)
 #   make anchors     DATASET=voc ANCNUM=3 [LOW='0.0 0.0' HIGH='1.0 1.0']   (reference Makefile:78-87: k-means anchors from data/<set>_img_ann.npy)
 
 PY            ?= python3
@@ -51,6 +53,10 @@ PRECISION     ?= f16x2
 ANN           ?= data/$(DATASET)_img_ann.npy
 EVALOBJ       ?= 0.05
 VOC07         ?= False
+# detect only
+SRC           ?= data
+OUTDIR        ?= out
+DRAW          ?= True
 # kmodel only
 OUT           ?= yolo.kmodel
 CALIB         ?= data/$(DATASET)_img_ann.npy
@@ -75,9 +81,9 @@ else
 LAUNCH = $(PY) -m torch.distributed.run --nnodes=1 --nproc-per-node $(GPUS) --master-addr 127.0.0.1 --master-port 29533
 endif
 
-.PHONY: all build test bench inference train anchors kmodel eval
+.PHONY: all build test bench inference train anchors kmodel eval detect
 all:
-	@echo 'targets: build | test | bench | inference | train | kmodel | eval   (see the header of this Makefile)'
+	@echo 'targets: build | test | bench | inference | train | kmodel | eval | detect   (see the header of this Makefile)'
 
 build:
 	$(PY) -c "import __graft_entry__ as g; g.build()"
@@ -104,6 +110,10 @@ eval:
 	$(PY) keras_eval.py $(CKPT) --train_set $(DATASET) --class_num $(CLSNUM) --model_def $(MODEL) --depth_multiplier $(DEPTHMUL) \
 		--image_size $(IMGSIZE) --output_size $(OUTSIZE) --iou_thresh $(IOUTHRESH) --precision $(PRECISION) --obj_thresh $(EVALOBJ) \
 		--voc07 $(VOC07) $(if $(filter-out 0,$(SYNTHETIC)),--synthetic $(SYNTHETIC),--ann $(ANN))
+
+# every picture of SRC (a folder or a text list) -> OUTDIR/detections.json + OUTDIR/<stem>_res.jpg; batches of BATCH pictures of any sizes
+detect:
+	$(PY) keras_detect.py $(CKPT) $(SRC) --out_dir $(OUTDIR) --draw $(DRAW) --batch $(BATCH) --precision $(PRECISION) $(NET_ARGS)
 
 # reference Makefile:78-87 (same flags; --is_random True as there)
 anchors:

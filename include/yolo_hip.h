@@ -292,6 +292,51 @@ int yk_letterbox_augment_u8(const uint8_t *d_src, int batch, int src_h, int src_
  * path fuses the normalisation into the stem conv (yk_run_u8). */
 int yk_normalise_u8(const uint8_t *d_frames, int batch, size_t per_image, float *d_out, void *stream);
 
+/* ---- pictures of different sizes in one buffer (`make detect`) ------------------------------
+ * A ragged batch is one packed device buffer of `n` pictures, picture i = [h][w][3] u8 at byte `offset` (any value: pixels are 3 bytes,
+ * no alignment is assumed; gaps between pictures are allowed), and a device table of one row per picture. */
+typedef struct yk_ragged_row {
+    uint64_t offset;    /* byte offset of the picture in the packed buffer */
+    int32_t h, w;       /* its size */
+    double scale;       /* letterbox of this picture into dst_h x dst_w: yk_letterbox_ragged_params fills these three */
+    int32_t tx, ty;
+    int32_t thickness;  /* yk_draw_dets_u8: rings of box outline, and the integer magnification of the glyphs (values < 1 draw as 1, mag > 1024 as 1024) */
+    int32_t mag;
+} yk_ragged_row_t;      /* 40 bytes, no padding */
+/* HOST helper: fills scale, tx, ty of n rows in host memory with the arithmetic yk_letterbox_u8 uses for (h, w) -> (dst_h, dst_w).
+ * A row with h <= 0 or w <= 0, a NULL table, n <= 0 or a non-positive dst size: YK_ERR_ARG.  Needs no device. */
+int yk_letterbox_ragged_params(yk_ragged_row_t *h_table, int n, int dst_h, int dst_w);
+/* One launch for the whole ragged batch: d_dst [n][dst_h][dst_w][3]; image i of the result equals yk_letterbox_u8 on picture i alone,
+ * bit for bit (the same per-pixel arithmetic with the row's scale, tx, ty).  d_table is DEVICE memory, so this call cannot read it:
+ * NULL pointers, n <= 0, src_bytes == 0 and non-positive dst sizes are YK_ERR_ARG here, while refusing a row whose h or w is not positive,
+ * or whose picture does not lie inside the buffer, is the caller's job (engine.letterbox_ragged_u8 does it on the host table).
+ * The kernel does not trust the table either: the image of a row with h <= 0, w <= 0 or offset + 3*h*w > src_bytes is written as
+ * zeros and nothing of d_src is read for it.  Can be recorded in a graph. */
+int yk_letterbox_ragged_u8(const uint8_t *d_src, size_t src_bytes, const yk_ragged_row_t *d_table, int n, uint8_t *d_dst, int dst_h,
+                           int dst_w, void *stream);
+/* Draws detections INTO the pictures of a ragged batch, in place (inference.py's PIL loop plus keras_inference.py:137-174's label with
+ * its filled background), by the painter's rule: for picture i and its rows k = 0 .. count_i - 1 in order, later paint over earlier:
+ *   corners   t = max(0, floorf(top + 0.5f)), l likewise from left; b = min(h, floorf(bottom + 0.5f)), r = min(w, floorf(right + 0.5f))
+ *             (fp32 arithmetic, as NumPy evaluates inference.py's expression on a float32 row); b <= t or r <= l: the row draws nothing;
+ *   outline   for j = 0 .. thickness - 1 while r - j > l + j and b - j > t + j: the one-pixel outline of the inclusive rectangle
+ *             [l+j, t+j, r-j, b-j] in the class colour d_colors[class mod n_colors] (ImageDraw.rectangle(outline=)); clipped to the
+ *             picture, so row h and column w are simply not painted;
+ *   label     the rectangle at (l, t + 1) of 7*gw*mag by gh*mag pixels filled with the class colour, clipped; on it the 7 glyphs of
+ *             '{:2d} {:.2f}'.format(class, score), a glyph pixel of value 1 painted black as a mag x mag block.  The score digits are
+ *             rint((double)score * 100.0), half to even: exact, so they are Python's digits for every fp32 score in [0, 1].
+ *             A class >= 100 draws its low two digits, a score >= 10 the low three digits of that rint; a negative class draws as 0,
+ *             a negative or non-finite score as 0.00: every input has a defined picture.  gh == 0 switches the label off.
+ * Pixels that no primitive covers are not written.  d_dets [n][cap][6] fp32 rows (top, left, bottom, right, score, class) and d_counts [n]
+ * (clamped to [0, cap]) as yk_decode_py leaves them; d_colors [n_colors][3] u8; d_atlas [12][gh][gw] u8 of 0 / 1 for the glyphs
+ * "0123456789. " (may be NULL when gh == 0).  max_pixels >= the largest h*w of the table: it sizes the launch, and a picture with more
+ * pixels is drawn only in its first max_pixels.  One thread per pixel gathers: it walks the picture's rows from the last to the first and
+ * writes the first primitive that covers it, once - no atomics, no ordering between workgroups, the same bytes on every run.  Rows whose
+ * picture does not lie inside src_bytes are skipped.  NULL pointers, n <= 0, cap <= 0, n_colors <= 0, gh < 0, gw <= 0, src_bytes == 0,
+ * max_pixels == 0: YK_ERR_ARG.  Can be recorded in a graph. */
+int yk_draw_dets_u8(uint8_t *d_buf, size_t src_bytes, const yk_ragged_row_t *d_table, int n, const float *d_dets, int cap,
+                    const int32_t *d_counts, const uint8_t *d_colors, int n_colors, const uint8_t *d_atlas, int gh, int gw,
+                    size_t max_pixels, void *stream);
+
 /* ---- training step, loss level (tools/utils.py:708-793 create_loss_fn, :662-705 calc_ignore_mask,
  *      tools/custom.py:13-75 Yolo_Precision/Yolo_Recall) for ONE output layer.
  * d_y_true / d_y_pred: device fp32 [batch][out_h][out_w][A][5+C] (labels from Helper.box_to_label / raw outputs).

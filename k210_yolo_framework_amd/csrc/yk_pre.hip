@@ -74,6 +74,67 @@ extern "C" int yk_letterbox_u8(const uint8_t *d_src, int batch, int src_h, int s
     return YK_OK;
 }
 
+// ---- the same letterbox for a RAGGED batch: pictures of different sizes packed into one buffer, one table row each (yolo_hip.h), one
+// launch.  blockIdx.y is the picture, so a workgroup reads one row (uniform loads) and every pixel goes through letterbox_px with that
+// row's (scale, tx, ty) - the values letterbox_params gives yk_letterbox_u8 for the same sizes, hence the same bytes.  Picture offsets carry
+// no alignment (3-byte pixels): sources are read a byte at a time, as above.
+__global__ void __launch_bounds__(256) letterbox_ragged_u8_kernel(const uint8_t *__restrict__ src, size_t src_bytes,
+                                                                  const yk_ragged_row_t *__restrict__ table, uint8_t *__restrict__ dst, int dh,
+                                                                  int dw) {
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t per = (size_t)dh * dw;
+    if (idx >= per) return;
+    const yk_ragged_row_t row = table[blockIdx.y];
+    const int x = (int)(idx % dw), y = (int)(idx / dw);
+    uint8_t v[3] = {0, 0, 0};
+    // a row the host should have refused: nothing of src is read for it
+    const bool ok = row.h > 0 && row.w > 0 && row.offset <= src_bytes && (size_t)row.h * row.w * 3 <= src_bytes - row.offset;
+    if (ok) letterbox_px(src + row.offset, row.h, row.w, row.scale, row.tx, row.ty, x, y, v);
+    uint8_t *o = dst + ((size_t)blockIdx.y * per + idx) * 3;
+    o[0] = v[0];
+    o[1] = v[1];
+    o[2] = v[2];
+}
+
+extern "C" int yk_letterbox_ragged_params(yk_ragged_row_t *h_table, int n, int dst_h, int dst_w) {
+    if (!h_table || n <= 0 || dst_h <= 0 || dst_w <= 0) {
+        yk_set_error("yk_letterbox_ragged_params: bad argument");
+        return YK_ERR_ARG;
+    }
+    for (int i = 0; i < n; ++i)
+        if (h_table[i].h <= 0 || h_table[i].w <= 0) {
+            yk_set_error("yk_letterbox_ragged_params: row %d is %d x %d", i, (int)h_table[i].h, (int)h_table[i].w);
+            return YK_ERR_ARG;
+        }
+    for (int i = 0; i < n; ++i) {
+        int tx, ty;
+        letterbox_params(h_table[i].h, h_table[i].w, dst_h, dst_w, &h_table[i].scale, &tx, &ty);
+        h_table[i].tx = tx;
+        h_table[i].ty = ty;
+    }
+    return YK_OK;
+}
+
+extern "C" int yk_letterbox_ragged_u8(const uint8_t *d_src, size_t src_bytes, const yk_ragged_row_t *d_table, int n, uint8_t *d_dst,
+                                      int dst_h, int dst_w, void *stream) {
+    if (!d_src || !d_table || !d_dst || n <= 0 || src_bytes == 0 || dst_h <= 0 || dst_w <= 0) {
+        yk_set_error("yk_letterbox_ragged_u8: bad argument");
+        return YK_ERR_ARG;
+    }
+    if (yk_current_device() < 0) {
+        yk_set_error("yk_letterbox_ragged_u8: no HIP device");
+        return YK_ERR_NO_DEVICE;
+    }
+    const size_t per = (size_t)dst_h * dst_w;
+    for (int base = 0; base < n; base += 65535) {                                 // grid.y holds at most 65535 pictures
+        const int m = n - base < 65535 ? n - base : 65535;
+        hipLaunchKernelGGL(letterbox_ragged_u8_kernel, dim3((unsigned)((per + 255) / 256), (unsigned)m), dim3(256), 0, (hipStream_t)stream,
+                           d_src, src_bytes, d_table + base, d_dst + (size_t)base * per * 3, dst_h, dst_w);
+    }
+    YK_HIP(hipGetLastError());
+    return YK_OK;
+}
+
 // ---- letterbox + training augmentation (k210_yolo_framework_amd/augment.py; the imgaug OneOf of tools/utils.py:84-88): the u8
 // letterboxed frame L above, then warped by the image's inverse map inv[b] = M (2x3, float64, pixel-index coordinates, computed on
 // the host; no transcendental here):

@@ -1,0 +1,275 @@
+"""`make detect` - a folder of pictures through the pipeline: detections and annotated pictures out.
+
+    python keras_detect.py CKPT SRC --out_dir D [--draw True|False] [--batch 32] [--depth 4] [network and threshold flags of keras_inference.py]
+
+SRC: a folder (its .jpg / .jpeg / .png / .bmp files, in sorted order), a text file with one picture path per line, or one picture.
+What the reference's keras_inference.py:137-174 does for one picture, for all of them at the pipeline's rate: the pictures are decoded on
+a thread pool, each batch is packed into ONE pinned buffer (pictures of different sizes back to back), crosses PCIe in one copy, is
+letterboxed by one launch (yk_letterbox_ragged_u8) into a Pipeline slot and submitted; with --draw True the boxes and labels are painted
+into the still-resident originals on the slot's stream (yk_draw_dets_u8), and only finished pictures come back, to be written as
+<out_dir>/<stem>_res.jpg on the pool.  Always writes <out_dir>/detections.json ([{path, detections: [[top, left, bottom, right, score,
+class], ...]}, ...]) and prints the reference's table per picture.  `--precision kpu` runs a .kmodel / .kfpkg through engine.KpuPlan."""
+from __future__ import annotations
+
+import argparse
+import ctypes as C
+import json
+import sys
+from collections import deque
+from concurrent.futures import ThreadPoolExecutor
+from pathlib import Path
+from typing import List, Optional, Sequence
+
+import numpy as np
+
+from . import draw as dr
+from .helper import INFO, NOTE, Helper, VOC_ANCHORS
+from .yolonet import MODEL_DEFS
+
+EXTENSIONS = ('.jpg', '.jpeg', '.png', '.bmp')
+MAX_WORKERS = 16                    # decode / encode pool: a fixed ceiling, never the machine's CPU count
+
+
+def parse(argv=None):
+    p = argparse.ArgumentParser(description='detections and annotated pictures for a folder or a list of pictures')
+    p.add_argument('pre_ckpt', type=str, help='.h5 / .npz weights ("" = seeded random weights), or a .kmodel / .kfpkg with --precision kpu')
+    p.add_argument('src', type=str, help='a folder of pictures, a text file of picture paths, or one picture')
+    p.add_argument('--out_dir', type=str, default='out')
+    p.add_argument('--draw', type=str, choices=['True', 'False'], default='True', help='write <stem>_res.jpg with boxes and labels')
+    p.add_argument('--batch', type=int, default=32)
+    p.add_argument('--depth', type=int, default=4, help='batches in flight (float modes)')
+    p.add_argument('--workers', type=int, default=8, help=f'decode / encode threads (at most {MAX_WORKERS})')
+    p.add_argument('--train_set', type=str, default='voc')
+    p.add_argument('--class_num', type=int, default=20)
+    p.add_argument('--model_def', type=str, default='yolo_mobilev2')
+    p.add_argument('--depth_multiplier', type=float, choices=[0.5, 0.75, 1.0], default=1.0)
+    p.add_argument('--image_size', type=int, default=(224, 320), nargs='+')
+    p.add_argument('--output_size', type=int, default=(7, 10, 14, 20), nargs='+')
+    p.add_argument('--obj_thresh', type=float, default=0.7)
+    p.add_argument('--iou_thresh', type=float, default=0.3)
+    p.add_argument('--precision', type=str, choices=['f16', 'f16x2', 'kpu'], default='f16x2')
+    a = p.parse_args(sys.argv[1:] if argv is None else argv)
+    if (a.precision == 'kpu') != a.pre_ckpt.endswith(('.kmodel', '.kfpkg')):
+        p.error('--precision kpu runs a .kmodel / .kfpkg checkpoint, and only it does (the float modes take .h5 / .npz)')
+    if a.batch < 1 or a.depth < 1 or a.workers < 1:
+        p.error('--batch, --depth and --workers are at least 1')
+    a.draw = a.draw == 'True'
+    return a
+
+
+def expand_sources(src) -> List[str]:
+    """A folder -> its pictures (EXTENSIONS, any letter case) in sorted order; a picture -> itself; any other file -> the paths it lists, one
+    per line (blank lines and lines starting with # skipped; a relative path that does not exist as written is taken relative to the list)."""
+    p = Path(src)
+    if p.is_dir():
+        return [str(f) for f in sorted(p.iterdir()) if f.is_file() and f.suffix.lower() in EXTENSIONS]
+    if not p.is_file():
+        raise FileNotFoundError(f'{src}: neither a folder nor a file')
+    if p.suffix.lower() in EXTENSIONS:
+        return [str(p)]
+    out = []
+    for line in p.read_text().splitlines():
+        line = line.strip()
+        if not line or line.startswith('#'):
+            continue
+        q = Path(line)
+        out.append(str(q if q.is_absolute() or q.exists() else p.parent / q))
+    return out
+
+
+def output_names(names: Sequence[str], out_dir) -> List[str]:
+    """<out_dir>/<stem>_res.jpg per picture; a stem that occurred before (two folders in one list) gets _2, _3, ... appended."""
+    seen, out = {}, []
+    for n in names:
+        stem = Path(n).stem
+        seen[stem] = seen.get(stem, 0) + 1
+        out.append(str(Path(out_dir) / (f'{stem}_res.jpg' if seen[stem] == 1 else f'{stem}_{seen[stem]}_res.jpg')))
+    return out
+
+
+def print_table(name: str, rows: np.ndarray) -> None:
+    """keras_inference.py:146,154 for one picture, its path above."""
+    print(name)
+    if len(rows):
+        print('[top\tleft\tbottom\tright\tscore\tclass]')
+        for top, left, bottom, right, score, c in rows:
+            print(f'[{top:.1f}\t{left:.1f}\t{bottom:.1f}\t{right:.1f}\t{score:.2f}\t{int(c):2d}]')
+    else:
+        print(NOTE, ' no boxes detected')
+
+
+def _save_jpg(arr: np.ndarray, path: str) -> str:
+    from PIL import Image
+    Image.fromarray(arr).save(path)
+    return path
+
+
+class _Stage:
+    """What one batch in flight owns besides its Pipeline slot."""
+
+    def __init__(self):
+        self.pinned = self.d_packed = self.h_dets = self.h_counts = None
+
+
+def run(h: Helper, model, sources, out_dir=None, draw: bool = True, batch: int = 32, depth: int = 4, precision: str = 'f16x2',
+        obj_thresh: float = 0.7, iou_thresh: float = 0.3, workers: int = 8, names: Optional[Sequence[str]] = None,
+        return_arrays: bool = False, verbose: bool = True, max_out: int = 30):
+    """sources: picture paths, or [h, w, 3] uint8 arrays already in memory (then `names` names them).  -> {'names', 'detections': one
+    [k, 6] float32 array per picture, 'files': the pictures written, 'arrays': the annotated pictures as they leave the GPU, before any JPEG
+    encoding (return_arrays=True with draw=True)}.  With out_dir also writes detections.json and, when drawing, the _res.jpg files."""
+    import torch
+    from . import engine
+    engine.require_gpu()
+    n_all = len(sources)
+    if n_all == 0:
+        raise engine.YkError('detect: no pictures')
+    in_memory = isinstance(sources[0], np.ndarray)
+    names = list(names) if names is not None else ([f'img{i:05d}' for i in range(n_all)] if in_memory else [str(s) for s in sources])
+    in_hw = tuple(int(v) for v in h.in_hw[0])
+    B = max(1, min(int(batch), n_all))
+    dev = torch.device('cuda', torch.cuda.current_device())
+    if out_dir is not None:
+        Path(out_dir).mkdir(parents=True, exist_ok=True)
+    files = output_names(names, out_dir) if (draw and out_dir is not None) else [None] * n_all
+    want_pixels = draw and (out_dir is not None or return_arrays)
+    cap = h.class_num * max_out
+    colormap = torch.from_numpy(np.asarray(h.colormap, np.uint8).reshape(-1, 3)).to(dev)
+    atlas = torch.from_numpy(dr.glyph_atlas()).to(dev)
+
+    pipe = plan = None
+    if precision == 'kpu':                                  # one batch at a time through the KPU's integer arithmetic, on the current stream
+        plan = model._plan(B)
+        cfg = engine.make_decode_cfg(h.anchors, h.class_num, h.in_hw[0], h.out_hw)
+        frames = torch.empty((B, *in_hw, 3), dtype=torch.uint8, device=dev)
+        depth = 1
+    else:
+        depth = max(1, int(depth))
+        pipe = engine.Pipeline(model.spec, model.get_weights(), h.anchors, max_batch=B, depth=depth, precision=precision, max_out=max_out)
+    stages = [_Stage() for _ in range(depth)]
+    pool = ThreadPoolExecutor(max_workers=max(1, min(MAX_WORKERS, int(workers))))
+    load = (lambda s: np.ascontiguousarray(s[..., :3], np.uint8)) if in_memory else \
+        (lambda s: np.ascontiguousarray(h._read_img(str(s))[..., :3]).astype(np.uint8, copy=False))
+    starts = list(range(0, n_all, B))
+    ahead = depth + 1                                       # batches whose pictures are being decoded while the GPU works
+    loading = deque()
+    pending = deque()                                       # batches on the GPU: (first picture, count, stage, table, device table, event, slot)
+    results = [None] * n_all
+    arrays = [None] * n_all if (return_arrays and draw) else None
+    saves = []
+
+    def copy(dst, src, nbytes, stream):
+        """Pinned <-> device on a slot's stream through the library, as Pipeline copies: torch's pinned-memory allocator must never learn of
+        the pipeline's own streams - it records an event on every stream a pinned block was copied on when the block is FREED, and by then
+        Pipeline.close() has destroyed them."""
+        engine._check(engine.lib().yk_memcpy_async(C.c_void_p(dst.data_ptr()), C.c_void_p(src.data_ptr()), C.c_size_t(int(nbytes)),
+                                                   C.c_void_p(stream.cuda_stream)), 'yk_memcpy_async')
+
+    def start_load(k):
+        loading.append([pool.submit(load, s) for s in sources[starts[k]:starts[k] + B]])
+
+    def drain():
+        first, n, st, table, _, ev, slot = pending.popleft()
+        ev.synchronize()
+        if pipe is not None:
+            pipe.plans[slot].raise_if_failed()
+        counts = st.h_counts[:n].numpy()
+        for i in range(n):
+            results[first + i] = st.h_dets[i, :int(counts[i])].numpy().copy()
+        if want_pixels:
+            flat = st.pinned.numpy()
+            for i, view in enumerate(dr.unpack_ragged(flat, table)):
+                arr = view.copy()                           # the slot's buffer is packed again while the pool encodes
+                if arrays is not None:
+                    arrays[first + i] = arr
+                if files[first + i] is not None:
+                    saves.append(pool.submit(_save_jpg, arr, files[first + i]))
+        if verbose:
+            for i in range(n):
+                print_table(names[first + i], results[first + i])
+
+    try:
+        for k in range(min(ahead, len(starts))):
+            start_load(k)
+        for k, first in enumerate(starts):
+            imgs = [f.result() for f in loading.popleft()]
+            if k + ahead < len(starts):
+                start_load(k + ahead)
+            if len(pending) == depth:                       # the slot about to be reused still holds an unread batch
+                drain()
+            n = len(imgs)
+            slot = pipe.next_slot() if pipe is not None else 0
+            st = stages[slot]
+            need = sum(im.size for im in imgs)
+            if st.pinned is None or st.pinned.numel() < need:
+                size = need + need // 4                     # grown rarely: pinning is slow
+                st.pinned = torch.empty(size, dtype=torch.uint8).pin_memory()
+                st.d_packed = torch.empty(size, dtype=torch.uint8, device=dev)
+                st.h_dets = torch.empty((B, cap, 6), dtype=torch.float32).pin_memory()
+                st.h_counts = torch.empty((B,), dtype=torch.int32).pin_memory()
+            _, table, shapes = dr.pack_ragged(imgs, out=st.pinned)
+            total = dr.packed_bytes(table)
+            stream = pipe.streams[slot] if pipe is not None else torch.cuda.current_stream()
+            d_packed = st.d_packed[:total]
+            table_d = engine.ragged_table_to_device(table, in_hw, total, dev)              # (a blocking copy of 40 bytes per picture)
+            copy(d_packed, st.pinned, total, stream)                                        # the batch's one copy to the device
+            dst = pipe.input(slot)[:n] if pipe is not None else frames[:n]
+            engine.letterbox_ragged_u8(d_packed, table_d, in_hw, stream=stream, out=dst)
+            hw = np.asarray(shapes, np.float32)
+            if pipe is not None:
+                dets, counts, _ = pipe.submit(None, image_hw=hw, obj_thresh=obj_thresh, iou_thresh=iou_thresh, max_out=max_out, batch=n)
+            else:
+                plan.run_u8(frames[:n])
+                dets, counts = engine.decode_py(cfg, plan.outputs(), n, hw, obj_thresh, iou_thresh, max_out=max_out)
+            if want_pixels:
+                max_px = int(max(s[0] * s[1] for s in shapes))
+                engine.draw_detections_u8(d_packed, table_d, dets, counts, colormap, atlas, stream=stream, max_pixels=max_px)
+                copy(st.pinned, d_packed, total, stream)                                    # only finished pictures come back
+            copy(st.h_dets, dets, n * cap * 6 * 4, stream)
+            copy(st.h_counts, counts, n * 4, stream)
+            ev = torch.cuda.Event()
+            ev.record(stream)
+            pending.append((first, n, st, table, table_d, ev, slot))                        # (table_d: alive until the batch has run)
+        while pending:
+            drain()
+        written = [f.result() for f in saves]
+    finally:
+        pool.shutdown(wait=True)
+        if pipe is not None:
+            pipe.close()
+    if out_dir is not None:
+        doc = [{'path': names[i], 'detections': [[float(v) for v in row] for row in results[i]]} for i in range(n_all)]
+        (Path(out_dir) / 'detections.json').write_text(json.dumps(doc, indent=1))
+    out = {'names': names, 'detections': results, 'files': written}
+    if arrays is not None:
+        out['arrays'] = arrays
+    return out
+
+
+def main(argv=None):
+    a = parse(argv)
+    from . import engine
+    engine.require_gpu()
+    anchor_file = Path(f'data/{a.train_set}_anchor.npy')
+    h = Helper(None, a.class_num, str(anchor_file) if anchor_file.exists() else VOC_ANCHORS, np.reshape(np.array(a.image_size), (-1, 2)),
+               np.reshape(np.array(a.output_size), (-1, 2)))
+    model, _ = MODEL_DEFS[a.model_def]([a.image_size[0], a.image_size[1], 3], len(h.anchors[0]), a.class_num, alpha=a.depth_multiplier,
+                                       precision=a.precision)
+    if a.pre_ckpt and a.pre_ckpt not in ('None', '""'):
+        model.load_weights(a.pre_ckpt)
+        print(INFO, f' Load CKPT {a.pre_ckpt}')
+    else:
+        print(NOTE, ' no checkpoint given: seeded random weights')
+    paths = expand_sources(a.src)
+    if not paths:
+        raise engine.YkError(f'detect: no pictures ({", ".join(EXTENSIONS)}) in {a.src}')
+    res = run(h, model, paths, out_dir=a.out_dir, draw=a.draw, batch=a.batch, depth=a.depth, precision=a.precision,
+              obj_thresh=a.obj_thresh, iou_thresh=a.iou_thresh, workers=a.workers)
+    print(INFO, f' {len(paths)} pictures, {sum(len(d) for d in res["detections"])} detections -> {Path(a.out_dir) / "detections.json"}'
+          + (f', {len(res["files"])} annotated pictures' if a.draw else ''))
+    return res
+
+
+cli = main
+
+if __name__ == '__main__':
+    main()

@@ -72,6 +72,7 @@ def lib() -> C.CDLL:
         for fn in ('yk_plan_create', 'yk_plan_create_ex', 'yk_run_u8', 'yk_run_f32', 'yk_get_output', 'yk_debug_read_tensor', 'yk_debug_read_exponents',
                    'yk_plan_launch_count', 'yk_plan_launch_info', 'yk_plan_check', 'yk_plan_peek_error', 'yk_plan_debug_set_error', 'yk_plan_profile', 'yk_decode_py', 'yk_decode_py_ex', 'yk_decode_py_packed',
                    'yk_graph_begin', 'yk_graph_end', 'yk_graph_launch', 'yk_graph_node_count', 'yk_graph_kernel_node_count', 'yk_memcpy_async', 'yk_host_device_ptr', 'yk_stream_create', 'yk_stream_destroy', 'yk_stream_query_priority', 'yk_normalise_u8', 'yk_region_batched', 'yk_yolo_loss', 'yk_letterbox_u8', 'yk_letterbox_augment_u8',
+                   'yk_letterbox_ragged_params', 'yk_letterbox_ragged_u8', 'yk_draw_dets_u8',
                    'region_layer_init', 'yk_gemm_f32', 'yk_gemm_f32_grouped', 'yk_im2col3x3_f32', 'yk_col2im3x3_f32', 'yk_conv3x3_bn_fwd_f32', 'yk_conv3x3_bwd_weight_f32', 'yk_conv3x3_bwd_data_f32', 'yk_dw3x3_fwd_f32',
                    'yk_dw3x3_bwd_data_f32', 'yk_dw3x3_bwd_weight_f32', 'yk_dw3x3_bwd_weight_grouped_f32', 'yk_bn_train_fwd_f32', 'yk_bn_train_fwd_res_f32', 'yk_gemm_bn_fwd_f32', 'yk_dw3x3_bn_fwd_f32', 'yk_l2_segments_f32', 'yk_bn_train_bwd_f32',
                    'yk_bias_add_f32', 'yk_colsum_f32', 'yk_upsample2x_bwd_f32', 'yk_maxpool2_fwd_f32',
@@ -491,6 +492,82 @@ def letterbox_augment_u8(frames, dst_hw, inv, stream=None, out=None):
     _check(lib().yk_letterbox_augment_u8(_ptr(frames), C.c_int(B), C.c_int(sh), C.c_int(sw), _ptr(inv), _ptr(out), C.c_int(out.shape[1]),
                                          C.c_int(out.shape[2]), _stream(stream)), 'yk_letterbox_augment_u8')
     return out
+
+
+def ragged_table_to_device(table, dst_hw, packed_bytes: int, device, stream=None):
+    """A host table of a ragged batch (draw.RAGGED_DTYPE = yk_ragged_row_t; draw.pack_ragged writes it) checked, completed and uploaded:
+    every row must be a non-empty picture inside the `packed_bytes` of its buffer; scale / tx / ty are filled for the network size dst_hw
+    (None: left as they are - drawing does not read them).  -> cuda uint8 [n, 40], what the ragged calls take as their table."""
+    import torch
+    from .draw import RAGGED_DTYPE
+    t = np.array(table, dtype=RAGGED_DTYPE, copy=True).reshape(-1)
+    if len(t) == 0:
+        raise YkError('ragged table: no rows')
+    bad = (t['h'] <= 0) | (t['w'] <= 0)
+    if bad.any():
+        i = int(np.nonzero(bad)[0][0])
+        raise YkError(f'ragged table: row {i} is {int(t["h"][i])} x {int(t["w"][i])}')
+    end = t['offset'].astype(object) + 3 * t['h'].astype(object) * t['w'].astype(object)
+    if max(end) > int(packed_bytes):
+        raise YkError(f'ragged table: row {int(np.argmax(end))} ends at byte {max(end)} of a {int(packed_bytes)}-byte buffer')
+    if dst_hw is not None:
+        _check(lib().yk_letterbox_ragged_params(t.ctypes.data_as(C.c_void_p), C.c_int(len(t)), C.c_int(int(dst_hw[0])), C.c_int(int(dst_hw[1]))),
+               'yk_letterbox_ragged_params')
+    host = torch.from_numpy(t.view(np.uint8).reshape(len(t), RAGGED_DTYPE.itemsize))
+    with torch.cuda.stream(torch.cuda.current_stream() if stream is None else stream):
+        return host.to(device, non_blocking=False)
+
+
+def _ragged_args(packed, table, dst_hw, stream):
+    import torch
+    from .draw import RAGGED_DTYPE
+    assert packed.is_cuda and packed.dtype == torch.uint8 and packed.is_contiguous() and packed.numel() > 0
+    if not torch.is_tensor(table):
+        table = ragged_table_to_device(table, dst_hw, packed.numel(), packed.device, stream)
+    assert table.is_cuda and table.dtype == torch.uint8 and table.is_contiguous() and table.dim() == 2 and table.device == packed.device
+    assert table.shape[1] == RAGGED_DTYPE.itemsize and table.shape[0] > 0, tuple(table.shape)
+    return table
+
+
+def letterbox_ragged_u8(packed, table, dst_hw, stream=None, out=None):
+    """The letterbox of letterbox_u8 for pictures of DIFFERENT sizes in one launch (yk_letterbox_ragged_u8): `packed` cuda uint8 [bytes], the
+    pictures of draw.pack_ragged; `table` its host table (checked here: a row without pixels, or one that leaves the buffer, is refused) or
+    the device table ragged_table_to_device returned for this dst_hw.  -> cuda uint8 [n, H, W, 3]; image i is bit for bit
+    letterbox_u8 of picture i alone."""
+    import torch
+    require_gpu()
+    table = _ragged_args(packed, table, dst_hw, stream)
+    n = int(table.shape[0])
+    if out is None:
+        out = torch.empty((n, int(dst_hw[0]), int(dst_hw[1]), 3), dtype=torch.uint8, device=packed.device)
+    assert out.is_cuda and out.is_contiguous() and tuple(out.shape) == (n, int(dst_hw[0]), int(dst_hw[1]), 3), tuple(out.shape)
+    _check(lib().yk_letterbox_ragged_u8(_ptr(packed), C.c_size_t(packed.numel()), _ptr(table), C.c_int(n), _ptr(out), C.c_int(out.shape[1]),
+                                        C.c_int(out.shape[2]), _stream(stream)), 'yk_letterbox_ragged_u8')
+    return out
+
+
+def draw_detections_u8(packed, table, dets, counts, colormap, atlas, stream=None, max_pixels: Optional[int] = None):
+    """Paint detections into the pictures of a ragged batch, in place and on the device (yk_draw_dets_u8; the rule is in include/yolo_hip.h):
+    dets cuda fp32 [n, cap, 6] and counts cuda int32 [n] as decode_py / Pipeline.submit leave them, colormap cuda uint8 [n_colors, 3],
+    atlas cuda uint8 [12, gh, gw] of 0 / 1 (draw.glyph_atlas; gh == 0 draws no label).  `table` as for letterbox_ragged_u8; with a device
+    table pass max_pixels, the largest h * w of the batch."""
+    import torch
+    require_gpu()
+    if not torch.is_tensor(table):
+        t = np.asarray(table)
+        max_pixels = int((t['h'].astype(np.int64) * t['w'].astype(np.int64)).max()) if len(t) else 0
+    elif max_pixels is None:
+        raise YkError('draw_detections_u8: a device table needs max_pixels')
+    table = _ragged_args(packed, table, None, stream)
+    n = int(table.shape[0])
+    assert dets.is_cuda and dets.dtype == torch.float32 and dets.is_contiguous() and dets.dim() == 3 and dets.shape[0] == n and dets.shape[2] == 6
+    assert counts.is_cuda and counts.dtype == torch.int32 and counts.is_contiguous() and tuple(counts.shape) == (n,)
+    assert colormap.is_cuda and colormap.dtype == torch.uint8 and colormap.is_contiguous() and colormap.dim() == 2 and colormap.shape[1] == 3
+    assert atlas.is_cuda and atlas.dtype == torch.uint8 and atlas.is_contiguous() and atlas.dim() == 3 and atlas.shape[0] == 12
+    _check(lib().yk_draw_dets_u8(_ptr(packed), C.c_size_t(packed.numel()), _ptr(table), C.c_int(n), _ptr(dets), C.c_int(dets.shape[1]),
+                                 _ptr(counts), _ptr(colormap), C.c_int(colormap.shape[0]), _ptr(atlas) if atlas.numel() else None,
+                                 C.c_int(atlas.shape[1]), C.c_int(atlas.shape[2]), C.c_size_t(int(max_pixels)), _stream(stream)), 'yk_draw_dets_u8')
+    return packed
 
 
 class Graph:
