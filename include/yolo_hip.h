@@ -337,6 +337,39 @@ int yk_draw_dets_u8(uint8_t *d_buf, size_t src_bytes, const yk_ragged_row_t *d_t
                     const int32_t *d_counts, const uint8_t *d_colors, int n_colors, const uint8_t *d_atlas, int gh, int gw,
                     size_t max_pixels, void *stream);
 
+/* ---- JPEG encoding of a ragged batch on the device (`make detect ENCODE=gpu`) ----------------
+ * Baseline sequential JFIF as PIL's default save() writes it structurally: 8 bit, YCbCr, 4:2:0 (16x16 MCUs: Y00 Y01 Y10 Y11 Cb Cr), one
+ * interleaved scan, the four Huffman tables of ITU-T T.81 Annex K.3, no restart markers.  The device produces the entropy-coded scan;
+ * the headers and EOI are the host's (k210_yolo_framework_amd/jpeg.py).  Integer arithmetic only, so that a restatement gives the same bytes:
+ *   colour    Y  = (19595 R + 38470 G + 7471 B + 32768) >> 16
+ *             Cb = ((-11059 R - 21709 G + 32768 B + 32768) >> 16) + 128,  Cr = ((32768 R - 27439 G - 5329 B + 32768) >> 16) + 128
+ *             (arithmetic shifts, results clamped to [0, 255]); a picture is extended to multiples of 16 by replicating its last column
+ *             and row on the RGB indices (min(x, w-1), min(y, h-1)); chroma = (a + b + c + d + 2) >> 2 over each 2x2 group;
+ *   DCT       s = p - 128, T[u][x] = rint(2^13 a(u) cos((2x+1) u pi / 16)), a(0) = sqrt(1/8), a(u>0) = 1/2 (float64, tabulated);
+ *             rows r1 = (sum_x T[u][x] s[x] + 512) >> 10, columns c = sum_y T[v][y] r1[y] (the coefficient times 2^16, |c| < 1.3e8);
+ *   quantise  q = sign(c) * ((|c| + d * 2^15) / (d * 2^16)), d the table entry; AC clamped to +-1023, DC differences to +-2047;
+ *   coding    T.81: zigzag, DC difference to the previous block of the component (0 at the start of a picture), (run, size) symbols with
+ *             ZRL and EOB, bits MSB first, the last byte padded with 1-bits, 0x00 after every 0xFF byte (a padded last byte included). */
+/* HOST helper: the Annex K.1 luminance and chrominance tables scaled by the IJG rule (scale = 5000 / q for q < 50, else 200 - 2q;
+ * t = clamp((base * scale + 50) / 100, 1, 255)) into h_qtab [2][64], natural order.  quality outside 1 .. 100, NULL: YK_ERR_ARG. */
+int yk_jpeg_tables(int quality, uint8_t *h_qtab);
+/* HOST helper: the workspace and the output capacity yk_jpeg_encode_ragged_u8 needs for the n rows of a HOST table, from the proved
+ * worst case of 1660 bits per 8x8 block (1248 bytes per MCU before stuffing, twice that after).  Rows with h <= 0 or w <= 0 count
+ * nothing; a row with h or w > 65535, NULL pointers, n <= 0: YK_ERR_ARG.  Needs no device. */
+int yk_jpeg_workspace_bytes(const yk_ragged_row_t *h_table, int n, size_t *work_bytes, size_t *out_capacity);
+/* Encodes the n pictures of a ragged batch (the buffer and table of yk_letterbox_ragged_u8 / yk_draw_dets_u8) with the quantisation
+ * tables d_qtab (DEVICE, [2][64] natural order).  d_out receives the scan data of picture i at [d_out_off[i], d_out_off[i + 1]), packed
+ * back to back; nothing at or beyond d_out_off[n] is written, d_buf is only read.  d_work: 16-byte aligned device scratch of work_bytes,
+ * contents undefined before and after.  d_table is DEVICE memory, so this call cannot read it: NULL pointers, n <= 0, src_bytes == 0, a
+ * misaligned d_work and capacities that hold not even one MCU are YK_ERR_ARG here, and checking them against yk_jpeg_workspace_bytes
+ * is the caller's job (engine.jpeg_encode_ragged_u8 does it on the host table).  The kernels do not trust the table either: a row with
+ * h <= 0, w <= 0, h or w > 65535 or offset + 3*h*w > src_bytes gives a zero-length stream and nothing of d_buf is read for it, and a
+ * table that needs more than work_bytes or out_capacity hold gives n zero-length streams - no input writes outside the buffers.
+ * The same bytes on every run.  Never synchronises; can be recorded in a graph. */
+int yk_jpeg_encode_ragged_u8(const uint8_t *d_buf, size_t src_bytes, const yk_ragged_row_t *d_table, int n, const uint8_t *d_qtab,
+                             void *d_work, size_t work_bytes, uint8_t *d_out, size_t out_capacity, uint64_t *d_out_off /* [n + 1] */,
+                             void *stream);
+
 /* ---- training step, loss level (tools/utils.py:708-793 create_loss_fn, :662-705 calc_ignore_mask,
  *      tools/custom.py:13-75 Yolo_Precision/Yolo_Recall) for ONE output layer.
  * d_y_true / d_y_pred: device fp32 [batch][out_h][out_w][A][5+C] (labels from Helper.box_to_label / raw outputs).

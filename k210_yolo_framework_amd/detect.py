@@ -1,13 +1,15 @@
 """`make detect` - a folder of pictures through the pipeline: detections and annotated pictures out.
 
-    python keras_detect.py CKPT SRC --out_dir D [--draw True|False] [--batch 32] [--depth 4] [network and threshold flags of keras_inference.py]
+    python keras_detect.py CKPT SRC --out_dir D [--draw True|False] [--encode pil|gpu] [--quality 75] [--batch 32] [--depth 4]
+                           [network and threshold flags of keras_inference.py]
 
 SRC: a folder (its .jpg / .jpeg / .png / .bmp files, in sorted order), a text file with one picture path per line, or one picture.
 What the reference's keras_inference.py:137-174 does for one picture, for all of them at the pipeline's rate: the pictures are decoded on
 a thread pool, each batch is packed into ONE pinned buffer (pictures of different sizes back to back), crosses PCIe in one copy, is
 letterboxed by one launch (yk_letterbox_ragged_u8) into a Pipeline slot and submitted; with --draw True the boxes and labels are painted
 into the still-resident originals on the slot's stream (yk_draw_dets_u8), and only finished pictures come back, to be written as
-<out_dir>/<stem>_res.jpg on the pool.  Always writes <out_dir>/detections.json ([{path, detections: [[top, left, bottom, right, score,
+<out_dir>/<stem>_res.jpg on the pool (--encode pil, the default), or are JPEG-encoded on the device right after the draw (--encode gpu,
+yk_jpeg_encode_ragged_u8: only the compressed scans come back and are written between jpeg.py's headers and EOI).  Always writes <out_dir>/detections.json ([{path, detections: [[top, left, bottom, right, score,
 class], ...]}, ...]) and prints the reference's table per picture.  `--precision kpu` runs a .kmodel / .kfpkg through engine.KpuPlan."""
 from __future__ import annotations
 
@@ -23,6 +25,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import draw as dr
+from . import jpeg
 from .helper import INFO, NOTE, Helper, VOC_ANCHORS
 from .yolonet import MODEL_DEFS
 
@@ -36,6 +39,9 @@ def parse(argv=None):
     p.add_argument('src', type=str, help='a folder of pictures, a text file of picture paths, or one picture')
     p.add_argument('--out_dir', type=str, default='out')
     p.add_argument('--draw', type=str, choices=['True', 'False'], default='True', help='write <stem>_res.jpg with boxes and labels')
+    p.add_argument('--encode', type=str, choices=['pil', 'gpu'], default='pil',
+                   help='who writes the JPEG of an annotated picture: PIL on the thread pool, or the GPU right after the draw')
+    p.add_argument('--quality', type=int, default=75, help='JPEG quality 1 .. 100 of --encode gpu')
     p.add_argument('--batch', type=int, default=32)
     p.add_argument('--depth', type=int, default=4, help='batches in flight (float modes)')
     p.add_argument('--workers', type=int, default=8, help=f'decode / encode threads (at most {MAX_WORKERS})')
@@ -53,6 +59,8 @@ def parse(argv=None):
         p.error('--precision kpu runs a .kmodel / .kfpkg checkpoint, and only it does (the float modes take .h5 / .npz)')
     if a.batch < 1 or a.depth < 1 or a.workers < 1:
         p.error('--batch, --depth and --workers are at least 1')
+    if not 1 <= a.quality <= 100:
+        p.error('--quality is 1 .. 100')
     a.draw = a.draw == 'True'
     return a
 
@@ -109,20 +117,25 @@ class _Stage:
 
     def __init__(self):
         self.pinned = self.d_packed = self.h_dets = self.h_counts = None
+        self.d_work = self.d_scan = self.h_scan = self.d_off = self.h_off = None       # encode='gpu'
 
 
 def run(h: Helper, model, sources, out_dir=None, draw: bool = True, batch: int = 32, depth: int = 4, precision: str = 'f16x2',
         obj_thresh: float = 0.7, iou_thresh: float = 0.3, workers: int = 8, names: Optional[Sequence[str]] = None,
-        return_arrays: bool = False, verbose: bool = True, max_out: int = 30):
+        return_arrays: bool = False, verbose: bool = True, max_out: int = 30, encode: str = 'pil', quality: int = 75):
     """sources: picture paths, or [h, w, 3] uint8 arrays already in memory (then `names` names them).  -> {'names', 'detections': one
     [k, 6] float32 array per picture, 'files': the pictures written, 'arrays': the annotated pictures as they leave the GPU, before any JPEG
-    encoding (return_arrays=True with draw=True)}.  With out_dir also writes detections.json and, when drawing, the _res.jpg files."""
+    encoding (return_arrays=True with draw=True)}.  With out_dir also writes detections.json and, when drawing, the _res.jpg files:
+    encode='pil' through PIL's save() on the pool; encode='gpu' encodes them on the slot's stream right after the draw at `quality`
+     - then the uncompressed pictures come back only for return_arrays, and the files are headers + scan + EOI."""
     import torch
     from . import engine
     engine.require_gpu()
     n_all = len(sources)
     if n_all == 0:
         raise engine.YkError('detect: no pictures')
+    if encode not in ('pil', 'gpu'):
+        raise engine.YkError(f'detect: encode {encode!r}: expected pil or gpu')
     in_memory = isinstance(sources[0], np.ndarray)
     names = list(names) if names is not None else ([f'img{i:05d}' for i in range(n_all)] if in_memory else [str(s) for s in sources])
     in_hw = tuple(int(v) for v in h.in_hw[0])
@@ -132,9 +145,14 @@ def run(h: Helper, model, sources, out_dir=None, draw: bool = True, batch: int =
         Path(out_dir).mkdir(parents=True, exist_ok=True)
     files = output_names(names, out_dir) if (draw and out_dir is not None) else [None] * n_all
     want_pixels = draw and (out_dir is not None or return_arrays)
+    gpu_jpeg = encode == 'gpu' and draw and out_dir is not None
+    copy_pixels = want_pixels and (return_arrays or not gpu_jpeg)       # the uncompressed pictures cross PCIe only when someone reads them
     cap = h.class_num * max_out
     colormap = torch.from_numpy(np.asarray(h.colormap, np.uint8).reshape(-1, 3)).to(dev)
     atlas = torch.from_numpy(dr.glyph_atlas()).to(dev)
+    if gpu_jpeg:
+        qtabs = engine.jpeg_tables(quality)
+        d_qtab = torch.from_numpy(qtabs).to(dev)
 
     pipe = plan = None
     if precision == 'kpu':                                  # one batch at a time through the KPU's integer arithmetic, on the current stream
@@ -152,10 +170,11 @@ def run(h: Helper, model, sources, out_dir=None, draw: bool = True, batch: int =
     starts = list(range(0, n_all, B))
     ahead = depth + 1                                       # batches whose pictures are being decoded while the GPU works
     loading = deque()
-    pending = deque()                                       # batches on the GPU: (first picture, count, stage, table, device table, event, slot)
+    pending = deque()                                       # batches on the GPU: (first picture, count, stage, table, device table, event, slot, stream)
     results = [None] * n_all
     arrays = [None] * n_all if (return_arrays and draw) else None
     saves = []
+    written = []
 
     def copy(dst, src, nbytes, stream):
         """Pinned <-> device on a slot's stream through the library, as Pipeline copies: torch's pinned-memory allocator must never learn of
@@ -168,21 +187,32 @@ def run(h: Helper, model, sources, out_dir=None, draw: bool = True, batch: int =
         loading.append([pool.submit(load, s) for s in sources[starts[k]:starts[k] + B]])
 
     def drain():
-        first, n, st, table, _, ev, slot = pending.popleft()
+        first, n, st, table, _, ev, slot, stream = pending.popleft()
         ev.synchronize()
         if pipe is not None:
             pipe.plans[slot].raise_if_failed()
         counts = st.h_counts[:n].numpy()
         for i in range(n):
             results[first + i] = st.h_dets[i, :int(counts[i])].numpy().copy()
-        if want_pixels:
+        if copy_pixels:
             flat = st.pinned.numpy()
             for i, view in enumerate(dr.unpack_ragged(flat, table)):
                 arr = view.copy()                           # the slot's buffer is packed again while the pool encodes
                 if arrays is not None:
                     arrays[first + i] = arr
-                if files[first + i] is not None:
+                if files[first + i] is not None and not gpu_jpeg:
                     saves.append(pool.submit(_save_jpg, arr, files[first + i]))
+        if gpu_jpeg:
+            off = st.h_off[:n + 1].numpy()                  # came back with the batch; now the second copy knows its size
+            total = int(off[n])
+            if total:
+                copy(st.h_scan, st.d_scan, total, stream)
+                stream.synchronize()
+            scan = st.h_scan.numpy()
+            for i in range(n):
+                with open(files[first + i], 'wb') as f:
+                    f.write(jpeg.assemble(int(table['h'][i]), int(table['w'][i]), qtabs, scan[int(off[i]):int(off[i + 1])].tobytes()))
+                written.append(files[first + i])
         if verbose:
             for i in range(n):
                 print_table(names[first + i], results[first + i])
@@ -223,15 +253,28 @@ def run(h: Helper, model, sources, out_dir=None, draw: bool = True, batch: int =
             if want_pixels:
                 max_px = int(max(s[0] * s[1] for s in shapes))
                 engine.draw_detections_u8(d_packed, table_d, dets, counts, colormap, atlas, stream=stream, max_pixels=max_px)
-                copy(st.pinned, d_packed, total, stream)                                    # only finished pictures come back
+                if copy_pixels:
+                    copy(st.pinned, d_packed, total, stream)                                # only finished pictures come back
+                if gpu_jpeg:
+                    sizes = engine.jpeg_workspace_bytes(table)
+                    if st.d_work is None or st.d_work.numel() < sizes[0] or st.d_scan.numel() < sizes[1]:
+                        torch.cuda.synchronize()                                            # grown rarely; nothing in flight reads the old ones
+                        st.d_work = torch.empty(sizes[0] + sizes[0] // 4, dtype=torch.uint8, device=dev)
+                        st.d_scan = torch.empty(sizes[1] + sizes[1] // 4, dtype=torch.uint8, device=dev)
+                        st.h_scan = torch.empty(st.d_scan.numel(), dtype=torch.uint8).pin_memory()
+                        st.d_off = torch.empty(B + 1, dtype=torch.int64, device=dev)
+                        st.h_off = torch.empty(B + 1, dtype=torch.int64).pin_memory()
+                    engine.jpeg_encode_ragged_u8(d_packed, table_d, d_qtab, stream=stream, sizes=sizes, work=st.d_work, out=st.d_scan,
+                                                 out_off=st.d_off[:n + 1])
+                    copy(st.h_off, st.d_off, (n + 1) * 8, stream)
             copy(st.h_dets, dets, n * cap * 6 * 4, stream)
             copy(st.h_counts, counts, n * 4, stream)
             ev = torch.cuda.Event()
             ev.record(stream)
-            pending.append((first, n, st, table, table_d, ev, slot))                        # (table_d: alive until the batch has run)
+            pending.append((first, n, st, table, table_d, ev, slot, stream))                # (table_d: alive until the batch has run)
         while pending:
             drain()
-        written = [f.result() for f in saves]
+        written += [f.result() for f in saves]
     finally:
         pool.shutdown(wait=True)
         if pipe is not None:
@@ -263,7 +306,7 @@ def main(argv=None):
     if not paths:
         raise engine.YkError(f'detect: no pictures ({", ".join(EXTENSIONS)}) in {a.src}')
     res = run(h, model, paths, out_dir=a.out_dir, draw=a.draw, batch=a.batch, depth=a.depth, precision=a.precision,
-              obj_thresh=a.obj_thresh, iou_thresh=a.iou_thresh, workers=a.workers)
+              obj_thresh=a.obj_thresh, iou_thresh=a.iou_thresh, workers=a.workers, encode=a.encode, quality=a.quality)
     print(INFO, f' {len(paths)} pictures, {sum(len(d) for d in res["detections"])} detections -> {Path(a.out_dir) / "detections.json"}'
           + (f', {len(res["files"])} annotated pictures' if a.draw else ''))
     return res

@@ -73,6 +73,7 @@ def lib() -> C.CDLL:
                    'yk_plan_launch_count', 'yk_plan_launch_info', 'yk_plan_check', 'yk_plan_peek_error', 'yk_plan_debug_set_error', 'yk_plan_profile', 'yk_decode_py', 'yk_decode_py_ex', 'yk_decode_py_packed',
                    'yk_graph_begin', 'yk_graph_end', 'yk_graph_launch', 'yk_graph_node_count', 'yk_graph_kernel_node_count', 'yk_memcpy_async', 'yk_host_device_ptr', 'yk_stream_create', 'yk_stream_destroy', 'yk_stream_query_priority', 'yk_normalise_u8', 'yk_region_batched', 'yk_yolo_loss', 'yk_letterbox_u8', 'yk_letterbox_augment_u8',
                    'yk_letterbox_ragged_params', 'yk_letterbox_ragged_u8', 'yk_draw_dets_u8',
+                   'yk_jpeg_tables', 'yk_jpeg_workspace_bytes', 'yk_jpeg_encode_ragged_u8',
                    'region_layer_init', 'yk_gemm_f32', 'yk_gemm_f32_grouped', 'yk_im2col3x3_f32', 'yk_col2im3x3_f32', 'yk_conv3x3_bn_fwd_f32', 'yk_conv3x3_bwd_weight_f32', 'yk_conv3x3_bwd_data_f32', 'yk_dw3x3_fwd_f32',
                    'yk_dw3x3_bwd_data_f32', 'yk_dw3x3_bwd_weight_f32', 'yk_dw3x3_bwd_weight_grouped_f32', 'yk_bn_train_fwd_f32', 'yk_bn_train_fwd_res_f32', 'yk_gemm_bn_fwd_f32', 'yk_dw3x3_bn_fwd_f32', 'yk_l2_segments_f32', 'yk_bn_train_bwd_f32',
                    'yk_bias_add_f32', 'yk_colsum_f32', 'yk_upsample2x_bwd_f32', 'yk_maxpool2_fwd_f32',
@@ -568,6 +569,54 @@ def draw_detections_u8(packed, table, dets, counts, colormap, atlas, stream=None
                                  _ptr(counts), _ptr(colormap), C.c_int(colormap.shape[0]), _ptr(atlas) if atlas.numel() else None,
                                  C.c_int(atlas.shape[1]), C.c_int(atlas.shape[2]), C.c_size_t(int(max_pixels)), _stream(stream)), 'yk_draw_dets_u8')
     return packed
+
+
+def jpeg_tables(quality: int = 75) -> np.ndarray:
+    """yk_jpeg_tables: the Annex K.1 tables scaled by the IJG rule -> uint8 [2, 64], natural order (what jpeg.quant_tables states in numpy)."""
+    q = np.zeros((2, 64), np.uint8)
+    _check(lib().yk_jpeg_tables(C.c_int(int(quality)), q.ctypes.data_as(C.c_void_p)), 'yk_jpeg_tables')
+    return q
+
+
+def jpeg_workspace_bytes(table) -> Tuple[int, int]:
+    """yk_jpeg_workspace_bytes for a host table: (bytes of scratch, capacity of the output) from the worst case per 8x8 block."""
+    from .draw import RAGGED_DTYPE
+    t = np.ascontiguousarray(np.asarray(table, dtype=RAGGED_DTYPE).reshape(-1))
+    work, cap = C.c_size_t(0), C.c_size_t(0)
+    _check(lib().yk_jpeg_workspace_bytes(t.ctypes.data_as(C.c_void_p), C.c_int(len(t)), C.byref(work), C.byref(cap)), 'yk_jpeg_workspace_bytes')
+    return int(work.value), int(cap.value)
+
+
+def jpeg_encode_ragged_u8(packed, table, qtab, stream=None, sizes=None, work=None, out=None, out_off=None):
+    """JPEG-encode the pictures of a ragged batch on the device (yk_jpeg_encode_ragged_u8; the rule is in include/yolo_hip.h): `packed` and
+    `table` as for letterbox_ragged_u8 (a host table is checked here: a row without pixels, or one that leaves the buffer, is refused),
+    qtab cuda uint8 [2, 64] (jpeg_tables).  With a device table pass sizes = jpeg_workspace_bytes(host table).  work / out / out_off: cuda
+    buffers to reuse (uint8 [>= sizes[0]], uint8 [>= sizes[1]], int64 [n + 1]); allocated when None.  -> (out, out_off): the scan data of
+    picture i is out[out_off[i]:out_off[i + 1]]; jpeg.assemble puts the file around it.  Does not synchronise."""
+    import torch
+    require_gpu()
+    if not torch.is_tensor(table):
+        sizes = jpeg_workspace_bytes(table)
+    elif sizes is None:
+        raise YkError('jpeg_encode_ragged_u8: a device table needs sizes = jpeg_workspace_bytes(host table)')
+    table = _ragged_args(packed, table, None, stream)
+    n = int(table.shape[0])
+    dev = packed.device
+    if work is None:
+        work = torch.empty(sizes[0], dtype=torch.uint8, device=dev)
+    if out is None:
+        out = torch.empty(sizes[1], dtype=torch.uint8, device=dev)
+    if out_off is None:
+        out_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    assert qtab.is_cuda and qtab.dtype == torch.uint8 and qtab.is_contiguous() and tuple(qtab.shape) == (2, 64)
+    assert work.is_cuda and work.dtype == torch.uint8 and work.is_contiguous() and out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous()
+    assert out_off.is_cuda and out_off.dtype == torch.int64 and out_off.is_contiguous() and out_off.numel() == n + 1
+    if work.numel() < sizes[0] or out.numel() < sizes[1]:
+        raise YkError(f'jpeg_encode_ragged_u8: work {work.numel()} / out {out.numel()} bytes, the batch needs {sizes[0]} / {sizes[1]}')
+    _check(lib().yk_jpeg_encode_ragged_u8(_ptr(packed), C.c_size_t(packed.numel()), _ptr(table), C.c_int(n), _ptr(qtab), _ptr(work),
+                                          C.c_size_t(work.numel()), _ptr(out), C.c_size_t(out.numel()), _ptr(out_off), _stream(stream)),
+           'yk_jpeg_encode_ragged_u8')
+    return out, out_off
 
 
 class Graph:

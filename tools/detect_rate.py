@@ -3,7 +3,9 @@
         one letterbox launch and one blocking copy per picture, torch.cat) on the same pictures in lists of 32;
   (ii)  the ragged letterbox of one 32-picture batch against 32 yk_letterbox_u8 launches + torch.cat, inputs resident;
   (iii) the draw launch alone, at the default obj_thresh and at 0.05 (many boxes);
-  (iv)  draw=True end to end, with and without the JPEG files, and PIL's encode time for one picture.
+  (iv)  draw=True end to end, with and without the JPEG files, and PIL's encode time for one picture;
+  (v)   draw=True end to end with encode='gpu' against encode='pil' (files written by both), and the encode launches of one 32-picture
+        batch alone (yk_jpeg_encode_ragged_u8, quality 75, inputs resident).
 Both sides warmed up, synchronised on both ends, three alternated repeats; medians with min / max."""
 import shutil
 import statistics
@@ -135,6 +137,28 @@ def main():
         say(f'    drawn, copied back, no files        {med(ta)}   -> {256 / statistics.median(ta):.0f} pictures/s')
         say(f'    + <stem>_res.jpg on 16 pool threads {med(tj)}   -> {256 / statistics.median(tj):.0f} pictures/s')
         say(f'    PIL JPEG encode of one picture on one thread: {enc * 1e3:.1f} ms (256 of them over 16 threads: {256 * enc / 16:.3f} s if they scaled perfectly)')
+        # (v) who encodes: the GPU right after the draw, or PIL on 16 pool threads
+        run_as = lambda enc_: lambda: detect.run(h, model, pics, out_dir=str(tmp / enc_), draw=True, batch=32, depth=4, obj_thresh=OBJ,
+                                                 iou_thresh=IOU, verbose=False, workers=16, encode=enc_, quality=75)
+        gpu, pil = run_as('gpu'), run_as('pil')
+        gpu(); pil()
+        tg, tl = [], []
+        for _ in range(3):
+            tg.append(timed(gpu)); tl.append(timed(pil))
+        size = lambda enc_: sum(f.stat().st_size for f in (tmp / enc_).glob('*_res.jpg')) / 1e6
+        say('(v) 256 pictures, draw=True, files written, seconds per call:')
+        say(f"    encode='gpu' (quality 75)     {med(tg)}   -> {256 / statistics.median(tg):.0f} pictures/s, {size('gpu'):.1f} MB of files")
+        say(f"    encode='pil' (16 pool threads) {med(tl)}   -> {256 / statistics.median(tl):.0f} pictures/s, {size('pil'):.1f} MB of files")
+        qtab = torch.from_numpy(engine.jpeg_tables(75)).cuda()
+        jsizes = engine.jpeg_workspace_bytes(table)
+        work = torch.empty(jsizes[0], dtype=torch.uint8, device='cuda')
+        scan = torch.empty(jsizes[1], dtype=torch.uint8, device='cuda')
+        off = torch.empty(33, dtype=torch.int64, device='cuda')
+        enc_gpu = lambda: [engine.jpeg_encode_ragged_u8(d_packed, d_table, qtab, sizes=jsizes, work=work, out=scan, out_off=off) for _ in range(50)]
+        enc_gpu()
+        te = [timed(enc_gpu) / 50 * 1e6 for _ in range(3)]
+        say(f'    yk_jpeg_encode_ragged_u8 alone, 32 pictures ({d_packed.numel() / 1e6:.1f} MB -> {int(off[32].item()) / 1e6:.2f} MB of scans, workspace '
+            f'{jsizes[0] / 1e6:.0f} MB): microseconds per call (9 launches, 50 calls in a row, host included) {med(te)}')
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
 
