@@ -13,9 +13,10 @@
 #   make eval        CKPT=yolo_model.h5|yolo.kmodel [PRECISION=f16x2|f16|kpu] [ANN=data/voc_img_ann.npy | SYNTHETIC=256] [EVALOBJ=0.05] [VOC07=True]:
 #                    VOC mAP of the checkpoint, network and metric on the GPU; prints the per-class AP table, writes eval.json beside CKPT
 #                    (make train VALMAP=True appends val_mAP to every epoch line)
-#   make detect      CKPT=yolo_model.h5|yolo.kmodel SRC=folder|list.txt [OUTDIR=out] [DRAW=True|False] [PRECISION=...] [ENCODE=pil|gpu QUALITY=75]: every
+#   make detect      CKPT=yolo_model.h5|yolo.kmodel SRC=folder|list.txt [OUTDIR=out] [DRAW=True|False] [PRECISION=...] [DECODE=pil|gpu] [ENCODE=pil|gpu QUALITY=75]: every
 #                    picture of SRC through the pipeline; writes OUTDIR/detections.json and, with DRAW=True, OUTDIR/<stem>_res.jpg (boxes and
-#                    labels drawn on the GPU; ENCODE=gpu also JPEG-encodes them there at QUALITY, ENCODE=pil leaves that to PIL on the host)
+#                    labels drawn on the GPU; ENCODE=gpu also JPEG-encodes them there at QUALITY, ENCODE=pil leaves that to PIL on the host;
+#                    DECODE=gpu decodes baseline JPEG files there too, by the project's own integer rule, every other file by PIL)
 #   make anchors     DATASET=voc ANCNUM=3 [LOW='0.0 0.0' HIGH='1.0 1.0']   (reference Makefile:78-87: k-means anchors from data/<set>_img_ann.npy)
 
 PY            ?= python3
@@ -59,6 +60,7 @@ SRC           ?= data
 OUTDIR        ?= out
 DRAW          ?= True
 ENCODE        ?= pil
+DECODE        ?= pil
 QUALITY       ?= 75
 # kmodel only
 OUT           ?= yolo.kmodel
@@ -116,7 +118,7 @@ eval:
 
 # every picture of SRC (a folder or a text list) -> OUTDIR/detections.json + OUTDIR/<stem>_res.jpg; batches of BATCH pictures of any sizes
 detect:
-	$(PY) keras_detect.py $(CKPT) $(SRC) --out_dir $(OUTDIR) --draw $(DRAW) --encode $(ENCODE) --quality $(QUALITY) --batch $(BATCH) --precision $(PRECISION) $(NET_ARGS)
+	$(PY) keras_detect.py $(CKPT) $(SRC) --out_dir $(OUTDIR) --draw $(DRAW) --decode $(DECODE) --encode $(ENCODE) --quality $(QUALITY) --batch $(BATCH) --precision $(PRECISION) $(NET_ARGS)
 
 # reference Makefile:78-87 (same flags; --is_random True as there)
 anchors:

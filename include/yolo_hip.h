@@ -370,6 +370,68 @@ int yk_jpeg_encode_ragged_u8(const uint8_t *d_buf, size_t src_bytes, const yk_ra
                              void *d_work, size_t work_bytes, uint8_t *d_out, size_t out_capacity, uint64_t *d_out_off /* [n + 1] */,
                              void *stream);
 
+/* ---- JPEG decoding of a batch into a ragged buffer on the device (`make detect DECODE=gpu`) -----------
+ * Baseline sequential files (SOF0, 8 bit; grey, or YCbCr 4:4:4 / 4:2:2 / 4:2:0; one interleaved scan; any restart interval), parsed on
+ * the host (k210_yolo_framework_amd/jpeg.py: parse_baseline refuses everything else by name, plan_decode builds what this call takes):
+ *   d_scan    the entropy-coded segments packed in one buffer: the bytes after the SOS header up to, not including, EOI - stuffed zeros
+ *             and RSTn markers left in place - each segment 4-byte aligned and followed by at least 8 zero bytes;
+ *   d_pics    one yk_jpeg_pic_t per picture (below);
+ *   d_tables  per picture, at table_offset (a multiple of 4): 3840 bytes = q u8 [4][64], the quantisation tables by id in natural order,
+ *             then the Huffman tables DC 0, DC 1, AC 0, AC 1 of 896 bytes each: look u16 [256] (for the 8 bits c: length << 8 | symbol of
+ *             the code of at most 8 bits that c begins with, 0 = none), maxcode i32 [16] (largest code of length l at [l - 1], -1 = none),
+ *             delta i32 [16] (index of the length's first value - its first code), vals u8 [256] (HUFFVAL);
+ *   d_rows    the yk_ragged_row_t table of the destination: picture i is written as [h][w][3] u8 at d_dst + d_rows[i].offset - the layout
+ *             yk_letterbox_ragged_u8, yk_draw_dets_u8 and yk_jpeg_encode_ragged_u8 read - and only these h * w * 3 bytes are written.
+ * The rule, integer only, so that a restatement (tests/jpeg_dec_ref.py) gives the same bytes:
+ *   entropy   T.81 F.2.2: Huffman codes MSB first, the 0x00 after an 0xFF skipped, EXTEND as in the standard, the DC a difference to the
+ *             previous block of its component (0 at the start and after every restart marker), AC (run, size) with ZRL and EOB; the
+ *             position behind the k-th RSTn is block k * Ri * (blocks per MCU);
+ *   dequant   c = clamp(q * Q, -32767, 32767) in int32, q the coefficient, Q the table entry;
+ *   IDCT      T[u][x] = rint(2^13 a(u) cos((2x+1) u pi / 16)), a(0) = sqrt(1/8), a(u>0) = 1/2 (float64, tabulated; sum_u |T[u][x]| <= 21641);
+ *             columns t[y][u] = clamp((sum_v T[v][y] c[v][u] + 512) >> 10, -65535, 65535)   (|sum| <= 32767 * 21641 < 2^30),
+ *             rows    p[y][x] = clamp(((sum_u T[u][x] t[y][u] + 32768) >> 16) + 128, 0, 255) (|sum| <= 65535 * 21641 < 2^31 - 2^15);
+ *             (the clamp of t is out of reach of any coefficients an encoder derives from 8-bit samples: there |t| < 2^16 / 1.7);
+ *   upsample  chroma of 4:2:2: out[2i] = (3 C[i] + C[i-1] + 1) >> 2, out[2i+1] = (3 C[i] + C[i+1] + 2) >> 2; of 4:2:0: per column
+ *             v = 3 near + far (the rows y >> 1 and, for even y, the one above it, for odd y the one below), then
+ *             out[2i] = (3 v[i] + v[i-1] + 8) >> 4, out[2i+1] = (3 v[i] + v[i+1] + 7) >> 4; neighbour indices clamped to the component's
+ *             real size ceil(w / 2) x ceil(h / 2), not to the MCU padding;
+ *   colour    R = Y + ((91881 (Cr-128) + 32768) >> 16), G = Y + ((-22554 (Cb-128) - 46802 (Cr-128) + 32768) >> 16),
+ *             B = Y + ((116130 (Cb-128) + 32768) >> 16): rint(c 2^16) of 1.40200, 0.34414, 0.71414, 1.77200, arithmetic shifts, clamped to
+ *             [0, 255]; a grey picture writes Y to all three bytes.
+ * Corrupt input has a defined result as well: every read is clamped to the picture's segment (bytes beyond it read 0), a code no table
+ * entry matches consumes one bit, a run that passes index 63 ends its block, any 0xFF followed by a non-zero byte is a marker: once the
+ * bits in front of it are used up (1-bits that fill the last byte in front of a marker or of the end are padding) decoding goes on behind
+ * it at the first block of an MCU.  Such input changes coefficients and the status, never an address. */
+#define YK_JPEG_DECODE_CHUNK 128    /* the default chunk_bytes */
+typedef struct yk_jpeg_pic {
+    uint64_t scan_offset;   /* of the picture's segment in d_scan, a multiple of 4 */
+    uint32_t scan_bytes;    /* its length, 1 .. 2^28 - 1 */
+    uint32_t table_offset;  /* of the picture's 3840 bytes in d_tables, a multiple of 4 */
+    int32_t h, w;           /* 1 .. 65535 */
+    int32_t ncomp;          /* 1 or 3 */
+    int32_t hs, vs;         /* luma sampling: 1x1, 2x1 or 2x2 (chroma is 1x1; grey: 1x1) */
+    int32_t restart;        /* MCUs per restart interval, 0 = none */
+    uint8_t tq[4], td[4], ta[4];    /* per component: quantisation table 0 .. 3, DC and AC Huffman table 0 .. 1 */
+    uint32_t reserved;
+} yk_jpeg_pic_t;            /* 56 bytes, no padding */
+/* HOST helper: the workspace yk_jpeg_decode_ragged_u8 needs for the n rows of a HOST table: 192 bytes per 8x8 block of the MCU-padded
+ * pictures (coefficients, component planes) and a header.  A row that is not a picture the decoder takes (sizes, component count,
+ * sampling, selectors), NULL pointers, n <= 0: YK_ERR_ARG.  Needs no device. */
+int yk_jpeg_decode_workspace_bytes(const yk_jpeg_pic_t *h_pics, int n, size_t *work_bytes);
+/* Decodes n pictures.  d_status[i] = 0 when exactly the picture's MCUs were decoded and the stream ended inside its last byte; otherwise
+ * bits say why: 1 the row leaves scan_bytes / table_bytes / dst_bytes, is no picture this decoder takes or disagrees with d_rows[i] on
+ * h, w (nothing is written for it); 2 too few MCUs in the stream; 4 data behind the last MCU; 8 a marker that is not the expected RSTn at
+ * the end of its interval; 16 the DEVICE table needs more blocks than work_bytes hold (then every status has this bit and nothing is
+ * written).  chunk_bytes: how much of the stuffed stream one thread decodes speculatively, a multiple of 4 in 4 .. 1024, 0 = the default;
+ * the result does not depend on it.  d_scan and d_tables 4-byte, d_pics 8-byte, d_work 16-byte aligned; these, NULL pointers, n <= 0,
+ * zero sizes and a workspace that holds not one block are YK_ERR_ARG here; checking the tables is the kernels' job, since they are DEVICE
+ * memory.  d_work: contents undefined before and after, but for uint32 [n] at byte ((4 (n + 1) + 15) & ~15): the rounds the fixed-point
+ * iteration of the Huffman stage took per picture, summed over its tiles of 256 chunks (a figure for tools, no part of the result).
+ * The same bytes on every run.  Never synchronises; can be recorded in a graph. */
+int yk_jpeg_decode_ragged_u8(const uint8_t *d_scan, size_t scan_bytes, const yk_jpeg_pic_t *d_pics, const uint8_t *d_tables,
+                             size_t table_bytes, const yk_ragged_row_t *d_rows, int n, uint8_t *d_dst, size_t dst_bytes, void *d_work,
+                             size_t work_bytes, int32_t *d_status, int chunk_bytes, void *stream);
+
 /* ---- training step, loss level (tools/utils.py:708-793 create_loss_fn, :662-705 calc_ignore_mask,
  *      tools/custom.py:13-75 Yolo_Precision/Yolo_Recall) for ONE output layer.
  * d_y_true / d_y_pred: device fp32 [batch][out_h][out_w][A][5+C] (labels from Helper.box_to_label / raw outputs).

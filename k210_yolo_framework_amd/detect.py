@@ -1,6 +1,6 @@
 """`make detect` - a folder of pictures through the pipeline: detections and annotated pictures out.
 
-    python keras_detect.py CKPT SRC --out_dir D [--draw True|False] [--encode pil|gpu] [--quality 75] [--batch 32] [--depth 4]
+    python keras_detect.py CKPT SRC --out_dir D [--draw True|False] [--decode pil|gpu] [--encode pil|gpu] [--quality 75] [--batch 32] [--depth 4]
                            [network and threshold flags of keras_inference.py]
 
 SRC: a folder (its .jpg / .jpeg / .png / .bmp files, in sorted order), a text file with one picture path per line, or one picture.
@@ -9,12 +9,16 @@ a thread pool, each batch is packed into ONE pinned buffer (pictures of differen
 letterboxed by one launch (yk_letterbox_ragged_u8) into a Pipeline slot and submitted; with --draw True the boxes and labels are painted
 into the still-resident originals on the slot's stream (yk_draw_dets_u8), and only finished pictures come back, to be written as
 <out_dir>/<stem>_res.jpg on the pool (--encode pil, the default), or are JPEG-encoded on the device right after the draw (--encode gpu,
-yk_jpeg_encode_ragged_u8: only the compressed scans come back and are written between jpeg.py's headers and EOI).  Always writes <out_dir>/detections.json ([{path, detections: [[top, left, bottom, right, score,
+yk_jpeg_encode_ragged_u8: only the compressed scans come back and are written between jpeg.py's headers and EOI).  With --decode gpu the pool
+only reads and parses the files: the entropy-coded scans cross PCIe instead of the pixels and yk_jpeg_decode_ragged_u8 decodes them on the
+slot's stream in front of the letterbox; a picture the parser refuses (progressive, CMYK, a PNG ...) is decoded by PIL as before and
+travels in the same buffer.  Always writes <out_dir>/detections.json ([{path, detections: [[top, left, bottom, right, score,
 class], ...]}, ...]) and prints the reference's table per picture.  `--precision kpu` runs a .kmodel / .kfpkg through engine.KpuPlan."""
 from __future__ import annotations
 
 import argparse
 import ctypes as C
+import io
 import json
 import sys
 from collections import deque
@@ -39,6 +43,8 @@ def parse(argv=None):
     p.add_argument('src', type=str, help='a folder of pictures, a text file of picture paths, or one picture')
     p.add_argument('--out_dir', type=str, default='out')
     p.add_argument('--draw', type=str, choices=['True', 'False'], default='True', help='write <stem>_res.jpg with boxes and labels')
+    p.add_argument('--decode', type=str, choices=['pil', 'gpu'], default='pil',
+                   help='who decodes the pictures: PIL on the thread pool, or (baseline JPEG files) the GPU in front of the letterbox')
     p.add_argument('--encode', type=str, choices=['pil', 'gpu'], default='pil',
                    help='who writes the JPEG of an annotated picture: PIL on the thread pool, or the GPU right after the draw')
     p.add_argument('--quality', type=int, default=75, help='JPEG quality 1 .. 100 of --encode gpu')
@@ -118,12 +124,15 @@ class _Stage:
     def __init__(self):
         self.pinned = self.d_packed = self.h_dets = self.h_counts = None
         self.d_work = self.d_scan = self.h_scan = self.d_off = self.h_off = None       # encode='gpu'
+        self.d_stage = self.d_jwork = self.d_jstatus = self.h_jstatus = None           # decode='gpu'
 
 
 def run(h: Helper, model, sources, out_dir=None, draw: bool = True, batch: int = 32, depth: int = 4, precision: str = 'f16x2',
         obj_thresh: float = 0.7, iou_thresh: float = 0.3, workers: int = 8, names: Optional[Sequence[str]] = None,
-        return_arrays: bool = False, verbose: bool = True, max_out: int = 30, encode: str = 'pil', quality: int = 75):
-    """sources: picture paths, or [h, w, 3] uint8 arrays already in memory (then `names` names them).  -> {'names', 'detections': one
+        return_arrays: bool = False, verbose: bool = True, max_out: int = 30, encode: str = 'pil', quality: int = 75, decode: str = 'pil'):
+    """sources: picture paths, or [h, w, 3] uint8 arrays already in memory (then `names` names them); with decode='gpu' paths or the bytes of
+    picture files: baseline JPEGs are decoded on the device by the rule of include/yolo_hip.h (not PIL's bytes: DESIGN.md 3.12), every other
+    file by PIL on the pool as with decode='pil'; a stream the device cannot finish raises YkError naming the file.  -> {'names', 'detections': one
     [k, 6] float32 array per picture, 'files': the pictures written, 'arrays': the annotated pictures as they leave the GPU, before any JPEG
     encoding (return_arrays=True with draw=True)}.  With out_dir also writes detections.json and, when drawing, the _res.jpg files:
     encode='pil' through PIL's save() on the pool; encode='gpu' encodes them on the slot's stream right after the draw at `quality`
@@ -136,7 +145,12 @@ def run(h: Helper, model, sources, out_dir=None, draw: bool = True, batch: int =
         raise engine.YkError('detect: no pictures')
     if encode not in ('pil', 'gpu'):
         raise engine.YkError(f'detect: encode {encode!r}: expected pil or gpu')
-    in_memory = isinstance(sources[0], np.ndarray)
+    if decode not in ('pil', 'gpu'):
+        raise engine.YkError(f'detect: decode {decode!r}: expected pil or gpu')
+    gpu_decode = decode == 'gpu'
+    in_memory = isinstance(sources[0], (np.ndarray, bytes))
+    if gpu_decode and any(isinstance(s, np.ndarray) for s in sources):
+        raise engine.YkError("detect: decode='gpu' takes paths or the bytes of picture files, not arrays")
     names = list(names) if names is not None else ([f'img{i:05d}' for i in range(n_all)] if in_memory else [str(s) for s in sources])
     in_hw = tuple(int(v) for v in h.in_hw[0])
     B = max(1, min(int(batch), n_all))
@@ -167,6 +181,17 @@ def run(h: Helper, model, sources, out_dir=None, draw: bool = True, batch: int =
     pool = ThreadPoolExecutor(max_workers=max(1, min(MAX_WORKERS, int(workers))))
     load = (lambda s: np.ascontiguousarray(s[..., :3], np.uint8)) if in_memory else \
         (lambda s: np.ascontiguousarray(h._read_img(str(s))[..., :3]).astype(np.uint8, copy=False))
+
+    def load_file(s):
+        """decode='gpu': -> a jpeg.Baseline, or (pixels, the parser's reason for refusing the file)."""
+        data = s if isinstance(s, bytes) else Path(s).read_bytes()
+        try:
+            return jpeg.parse_baseline(data)
+        except jpeg.Unsupported as e:
+            return np.ascontiguousarray(h._read_img(io.BytesIO(data))[..., :3]).astype(np.uint8, copy=False), e.reason
+
+    if gpu_decode:
+        load = load_file
     starts = list(range(0, n_all, B))
     ahead = depth + 1                                       # batches whose pictures are being decoded while the GPU works
     loading = deque()
@@ -187,10 +212,14 @@ def run(h: Helper, model, sources, out_dir=None, draw: bool = True, batch: int =
         loading.append([pool.submit(load, s) for s in sources[starts[k]:starts[k] + B]])
 
     def drain():
-        first, n, st, table, _, ev, slot, stream = pending.popleft()
+        first, n, st, table, keep, ev, slot, stream = pending.popleft()
         ev.synchronize()
         if pipe is not None:
             pipe.plans[slot].raise_if_failed()
+        if gpu_decode and keep[1]:
+            for j, code in zip(keep[1], st.h_jstatus[:len(keep[1])].numpy().tolist()):
+                if code:
+                    raise engine.YkError(f'detect: {names[first + j]}: the JPEG stream does not decode (status {code}: yk_jpeg_decode_ragged_u8)')
         counts = st.h_counts[:n].numpy()
         for i in range(n):
             results[first + i] = st.h_dets[i, :int(counts[i])].numpy().copy()
@@ -229,19 +258,74 @@ def run(h: Helper, model, sources, out_dir=None, draw: bool = True, batch: int =
             n = len(imgs)
             slot = pipe.next_slot() if pipe is not None else 0
             st = stages[slot]
-            need = sum(im.size for im in imgs)
+            if gpu_decode:
+                # the pinned buffer carries, 16-byte aligned: the pixels of the refused pictures, the scans and tables of the others,
+                # their yk_jpeg_pic_t rows and their rows of the destination's table
+                a16 = lambda v: (v + 15) & ~15
+                jp = [j for j, it in enumerate(imgs) if isinstance(it, jpeg.Baseline)]
+                parsed = [imgs[j] for j in jp]
+                raw = [(j, it[0]) for j, it in enumerate(imgs) if not isinstance(it, jpeg.Baseline)]
+                if verbose:
+                    for j, it in enumerate(imgs):
+                        if not isinstance(it, jpeg.Baseline):
+                            print(NOTE, f' {names[first + j]}: {it[1]}: decoded by PIL')
+                shapes = [(it.h, it.w) if isinstance(it, jpeg.Baseline) else it[0].shape[:2] for it in imgs]
+                table = dr.ragged_table(shapes)
+                total = dr.packed_bytes(table)
+                raw_bytes = sum(a16(im.size) for _, im in raw)
+                jbytes = a16(sum((len(q.scan) + jpeg.SCAN_PAD + 3) // 4 * 4 for q in parsed)) + len(jp) * jpeg.PIC_TABLE_BYTES
+                stage_bytes = raw_bytes + a16(jbytes) + a16(len(jp) * jpeg.PIC_DTYPE.itemsize) + len(jp) * dr.RAGGED_DTYPE.itemsize
+                need = max(stage_bytes, total)
+            else:
+                need = sum(im.size for im in imgs)
             if st.pinned is None or st.pinned.numel() < need:
                 size = need + need // 4                     # grown rarely: pinning is slow
                 st.pinned = torch.empty(size, dtype=torch.uint8).pin_memory()
                 st.d_packed = torch.empty(size, dtype=torch.uint8, device=dev)
                 st.h_dets = torch.empty((B, cap, 6), dtype=torch.float32).pin_memory()
                 st.h_counts = torch.empty((B,), dtype=torch.int32).pin_memory()
-            _, table, shapes = dr.pack_ragged(imgs, out=st.pinned)
-            total = dr.packed_bytes(table)
             stream = pipe.streams[slot] if pipe is not None else torch.cuda.current_stream()
-            d_packed = st.d_packed[:total]
-            table_d = engine.ragged_table_to_device(table, in_hw, total, dev)              # (a blocking copy of 40 bytes per picture)
-            copy(d_packed, st.pinned, total, stream)                                        # the batch's one copy to the device
+            keep = None
+            if gpu_decode:
+                if st.d_stage is None or st.d_stage.numel() < stage_bytes:
+                    st.d_stage = torch.empty(stage_bytes + stage_bytes // 4, dtype=torch.uint8, device=dev)
+                    st.d_jstatus = torch.empty(B, dtype=torch.int32, device=dev)
+                    st.h_jstatus = torch.empty(B, dtype=torch.int32).pin_memory()
+                flat = st.pinned.numpy()
+                at, raw_at = 0, []
+                for j, im in raw:
+                    flat[at:at + im.size] = im.reshape(-1)
+                    raw_at.append(at)
+                    at += a16(im.size)
+                d_packed = st.d_packed[:total]
+                if jp:
+                    _, pics, scan_bytes, table_bytes = jpeg.plan_decode(parsed, out=flat[at:at + jbytes])
+                    pics_at = at + a16(jbytes)
+                    rows_at = pics_at + a16(len(jp) * jpeg.PIC_DTYPE.itemsize)
+                    flat[pics_at:rows_at][:pics.nbytes] = pics.view(np.uint8)
+                    flat[rows_at:rows_at + len(jp) * dr.RAGGED_DTYPE.itemsize] = np.ascontiguousarray(table[jp]).view(np.uint8)
+                    work_bytes = engine.jpeg_decode_workspace_bytes(pics)
+                    if st.d_jwork is None or st.d_jwork.numel() < work_bytes:
+                        torch.cuda.synchronize()                                            # grown rarely; nothing in flight reads the old one
+                        st.d_jwork = torch.empty(work_bytes + work_bytes // 4, dtype=torch.uint8, device=dev)
+                copy(st.d_stage, st.pinned, stage_bytes, stream)                            # the batch's one copy to the device
+                for (j, im), o in zip(raw, raw_at):                                         # refused pictures: device to device, to their offsets
+                    copy(d_packed[int(table['offset'][j]):], st.d_stage[o:], im.size, stream)
+                if jp:
+                    engine.jpeg_decode_ragged_u8(st.d_stage[at:at + scan_bytes], st.d_stage[pics_at:pics_at + pics.nbytes].view(len(jp), -1),
+                                                 st.d_stage[at + scan_bytes:at + scan_bytes + table_bytes],
+                                                 st.d_stage[rows_at:rows_at + len(jp) * dr.RAGGED_DTYPE.itemsize].view(len(jp), -1), d_packed,
+                                                 stream=stream, work_bytes=work_bytes, work=st.d_jwork, status=st.d_jstatus[:len(jp)])
+                    copy(st.h_jstatus, st.d_jstatus, len(jp) * 4, stream)
+                table_d = engine.ragged_table_to_device(table, in_hw, total, dev)
+                keep = (table_d, jp)
+            else:
+                _, table, shapes = dr.pack_ragged(imgs, out=st.pinned)
+                total = dr.packed_bytes(table)
+                d_packed = st.d_packed[:total]
+                table_d = engine.ragged_table_to_device(table, in_hw, total, dev)          # (a blocking copy of 40 bytes per picture)
+                copy(d_packed, st.pinned, total, stream)                                    # the batch's one copy to the device
+                keep = (table_d, None)
             dst = pipe.input(slot)[:n] if pipe is not None else frames[:n]
             engine.letterbox_ragged_u8(d_packed, table_d, in_hw, stream=stream, out=dst)
             hw = np.asarray(shapes, np.float32)
@@ -271,7 +355,7 @@ def run(h: Helper, model, sources, out_dir=None, draw: bool = True, batch: int =
             copy(st.h_counts, counts, n * 4, stream)
             ev = torch.cuda.Event()
             ev.record(stream)
-            pending.append((first, n, st, table, table_d, ev, slot, stream))                # (table_d: alive until the batch has run)
+            pending.append((first, n, st, table, keep, ev, slot, stream))                   # (keep: the device table, alive until the batch has run)
         while pending:
             drain()
         written += [f.result() for f in saves]
@@ -306,7 +390,7 @@ def main(argv=None):
     if not paths:
         raise engine.YkError(f'detect: no pictures ({", ".join(EXTENSIONS)}) in {a.src}')
     res = run(h, model, paths, out_dir=a.out_dir, draw=a.draw, batch=a.batch, depth=a.depth, precision=a.precision,
-              obj_thresh=a.obj_thresh, iou_thresh=a.iou_thresh, workers=a.workers, encode=a.encode, quality=a.quality)
+              obj_thresh=a.obj_thresh, iou_thresh=a.iou_thresh, workers=a.workers, encode=a.encode, quality=a.quality, decode=a.decode)
     print(INFO, f' {len(paths)} pictures, {sum(len(d) for d in res["detections"])} detections -> {Path(a.out_dir) / "detections.json"}'
           + (f', {len(res["files"])} annotated pictures' if a.draw else ''))
     return res

@@ -73,7 +73,7 @@ def lib() -> C.CDLL:
                    'yk_plan_launch_count', 'yk_plan_launch_info', 'yk_plan_check', 'yk_plan_peek_error', 'yk_plan_debug_set_error', 'yk_plan_profile', 'yk_decode_py', 'yk_decode_py_ex', 'yk_decode_py_packed',
                    'yk_graph_begin', 'yk_graph_end', 'yk_graph_launch', 'yk_graph_node_count', 'yk_graph_kernel_node_count', 'yk_memcpy_async', 'yk_host_device_ptr', 'yk_stream_create', 'yk_stream_destroy', 'yk_stream_query_priority', 'yk_normalise_u8', 'yk_region_batched', 'yk_yolo_loss', 'yk_letterbox_u8', 'yk_letterbox_augment_u8',
                    'yk_letterbox_ragged_params', 'yk_letterbox_ragged_u8', 'yk_draw_dets_u8',
-                   'yk_jpeg_tables', 'yk_jpeg_workspace_bytes', 'yk_jpeg_encode_ragged_u8',
+                   'yk_jpeg_tables', 'yk_jpeg_workspace_bytes', 'yk_jpeg_encode_ragged_u8', 'yk_jpeg_decode_workspace_bytes', 'yk_jpeg_decode_ragged_u8',
                    'region_layer_init', 'yk_gemm_f32', 'yk_gemm_f32_grouped', 'yk_im2col3x3_f32', 'yk_col2im3x3_f32', 'yk_conv3x3_bn_fwd_f32', 'yk_conv3x3_bwd_weight_f32', 'yk_conv3x3_bwd_data_f32', 'yk_dw3x3_fwd_f32',
                    'yk_dw3x3_bwd_data_f32', 'yk_dw3x3_bwd_weight_f32', 'yk_dw3x3_bwd_weight_grouped_f32', 'yk_bn_train_fwd_f32', 'yk_bn_train_fwd_res_f32', 'yk_gemm_bn_fwd_f32', 'yk_dw3x3_bn_fwd_f32', 'yk_l2_segments_f32', 'yk_bn_train_bwd_f32',
                    'yk_bias_add_f32', 'yk_colsum_f32', 'yk_upsample2x_bwd_f32', 'yk_maxpool2_fwd_f32',
@@ -617,6 +617,71 @@ def jpeg_encode_ragged_u8(packed, table, qtab, stream=None, sizes=None, work=Non
                                           C.c_size_t(work.numel()), _ptr(out), C.c_size_t(out.numel()), _ptr(out_off), _stream(stream)),
            'yk_jpeg_encode_ragged_u8')
     return out, out_off
+
+
+class JpegPic(C.Structure):
+    """yk_jpeg_pic_t (numpy: jpeg.PIC_DTYPE)"""
+    _fields_ = [('scan_offset', C.c_uint64), ('scan_bytes', C.c_uint32), ('table_offset', C.c_uint32), ('h', C.c_int32), ('w', C.c_int32),
+                ('ncomp', C.c_int32), ('hs', C.c_int32), ('vs', C.c_int32), ('restart', C.c_int32), ('tq', C.c_uint8 * 4),
+                ('td', C.c_uint8 * 4), ('ta', C.c_uint8 * 4), ('reserved', C.c_uint32)]
+
+
+class RaggedRow(C.Structure):
+    """yk_ragged_row_t (numpy: draw.RAGGED_DTYPE)"""
+    _fields_ = [('offset', C.c_uint64), ('h', C.c_int32), ('w', C.c_int32), ('scale', C.c_double), ('tx', C.c_int32), ('ty', C.c_int32),
+                ('thickness', C.c_int32), ('mag', C.c_int32)]
+
+
+assert C.sizeof(JpegPic) == 56 and C.sizeof(RaggedRow) == 40
+
+
+def jpeg_decode_workspace_bytes(pics) -> int:
+    """yk_jpeg_decode_workspace_bytes for a host table of jpeg.PIC_DTYPE rows (jpeg.plan_decode): bytes of scratch."""
+    from .jpeg import PIC_DTYPE
+    t = np.ascontiguousarray(np.asarray(pics, dtype=PIC_DTYPE).reshape(-1))
+    work = C.c_size_t(0)
+    _check(lib().yk_jpeg_decode_workspace_bytes(t.ctypes.data_as(C.POINTER(JpegPic)), C.c_int(len(t)), C.byref(work)),
+           'yk_jpeg_decode_workspace_bytes')
+    return int(work.value)
+
+
+def jpeg_decode_ragged_u8(scan, pics, tables, rows, dst, stream=None, work_bytes=None, work=None, status=None, chunk_bytes: int = 0):
+    """Decode baseline JPEGs into a ragged packed buffer on the device (yk_jpeg_decode_ragged_u8; the rule is in include/yolo_hip.h): scan
+    and tables cuda uint8 (jpeg.plan_decode's buffer, split at its scan_bytes), pics its host table of jpeg.PIC_DTYPE or that table on the
+    device as cuda uint8 [n, 56] (then pass work_bytes = jpeg_decode_workspace_bytes(host table)), rows the destination's ragged table
+    (host, or cuda uint8 [n, 40]), dst cuda uint8: picture i is written as [h, w, 3] at dst[rows[i].offset:].  work / status: cuda buffers to
+    reuse (uint8 [>= work_bytes], int32 [n]).  -> status, 0 per decoded picture.  Does not synchronise."""
+    import torch
+    from .draw import RAGGED_DTYPE
+    from .jpeg import PIC_DTYPE
+    require_gpu()
+    dev = dst.device
+    if not torch.is_tensor(pics):
+        t = np.ascontiguousarray(np.asarray(pics, dtype=PIC_DTYPE).reshape(-1))
+        work_bytes = jpeg_decode_workspace_bytes(t)
+        pics = torch.from_numpy(t.view(np.uint8).reshape(len(t), PIC_DTYPE.itemsize)).to(dev)
+    elif work_bytes is None:
+        raise YkError('jpeg_decode_ragged_u8: a device table needs work_bytes = jpeg_decode_workspace_bytes(host table)')
+    if not torch.is_tensor(rows):
+        t = np.ascontiguousarray(np.asarray(rows, dtype=RAGGED_DTYPE).reshape(-1))
+        rows = torch.from_numpy(t.view(np.uint8).reshape(len(t), RAGGED_DTYPE.itemsize)).to(dev)
+    n = int(pics.shape[0])
+    for t_, width in ((pics, PIC_DTYPE.itemsize), (rows, RAGGED_DTYPE.itemsize)):
+        assert t_.is_cuda and t_.dtype == torch.uint8 and t_.is_contiguous() and tuple(t_.shape) == (n, width), tuple(t_.shape)
+    for t_ in (scan, tables, dst):
+        assert t_.is_cuda and t_.dtype == torch.uint8 and t_.is_contiguous() and t_.numel() > 0
+    if work is None:
+        work = torch.empty(int(work_bytes), dtype=torch.uint8, device=dev)
+    if status is None:
+        status = torch.empty(n, dtype=torch.int32, device=dev)
+    assert work.is_cuda and work.dtype == torch.uint8 and work.is_contiguous()
+    assert status.is_cuda and status.dtype == torch.int32 and status.is_contiguous() and status.numel() == n
+    if work.numel() < int(work_bytes):
+        raise YkError(f'jpeg_decode_ragged_u8: work {work.numel()} bytes, the batch needs {int(work_bytes)}')
+    _check(lib().yk_jpeg_decode_ragged_u8(_ptr(scan), C.c_size_t(scan.numel()), _ptr(pics), _ptr(tables), C.c_size_t(tables.numel()), _ptr(rows),
+                                          C.c_int(n), _ptr(dst), C.c_size_t(dst.numel()), _ptr(work), C.c_size_t(work.numel()), _ptr(status),
+                                          C.c_int(int(chunk_bytes)), _stream(stream)), 'yk_jpeg_decode_ragged_u8')
+    return status
 
 
 class Graph:

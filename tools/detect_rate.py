@@ -5,7 +5,11 @@
   (iii) the draw launch alone, at the default obj_thresh and at 0.05 (many boxes);
   (iv)  draw=True end to end, with and without the JPEG files, and PIL's encode time for one picture;
   (v)   draw=True end to end with encode='gpu' against encode='pil' (files written by both), and the encode launches of one 32-picture
-        batch alone (yk_jpeg_encode_ragged_u8, quality 75, inputs resident).
+        batch alone (yk_jpeg_encode_ragged_u8, quality 75, inputs resident);
+  (vi)  decode='gpu' against decode='pil' end to end on the same 256 pictures as JPEG files (PIL, quality 90, 4:2:0), draw=False, and the
+        decode launches of one 32-picture batch alone (yk_jpeg_decode_ragged_u8, inputs resident) with the rounds the fixed-point
+        iteration took per picture at the default chunk size.  Written to profiles/jpeg_decode_rate.txt when run as
+        `python tools/detect_rate.py profiles/detect_rate.txt profiles/jpeg_decode_rate.txt`.
 Both sides warmed up, synchronised on both ends, three alternated repeats; medians with min / max."""
 import shutil
 import statistics
@@ -18,11 +22,12 @@ import numpy as np
 import torch
 
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
-from k210_yolo_framework_amd import detect, draw, engine, inference  # noqa: E402
+from k210_yolo_framework_amd import detect, draw, engine, inference, jpeg  # noqa: E402
 from k210_yolo_framework_amd.helper import Helper, VOC_ANCHORS  # noqa: E402
 from k210_yolo_framework_amd.yolonet import MODEL_DEFS  # noqa: E402
 
 OUT = Path(sys.argv[1]) if len(sys.argv) > 1 else None
+OUT_DECODE = Path(sys.argv[2]) if len(sys.argv) > 2 else None
 lines = []
 
 
@@ -159,6 +164,45 @@ def main():
         te = [timed(enc_gpu) / 50 * 1e6 for _ in range(3)]
         say(f'    yk_jpeg_encode_ragged_u8 alone, 32 pictures ({d_packed.numel() / 1e6:.1f} MB -> {int(off[32].item()) / 1e6:.2f} MB of scans, workspace '
             f'{jsizes[0] / 1e6:.0f} MB): microseconds per call (9 launches, 50 calls in a row, host included) {med(te)}')
+        # (vi) who decodes: the GPU in front of the letterbox, or PIL on 16 pool threads
+        mark = len(lines)
+        from PIL import Image
+        (tmp / 'src').mkdir()
+        paths = []
+        for i, p in enumerate(pics):
+            paths.append(str(tmp / 'src' / f'p{i:03d}.jpg'))
+            Image.fromarray(p).save(paths[-1], quality=90)
+        dec_as = lambda d_: lambda: detect.run(h, model, paths, out_dir=None, draw=False, batch=32, depth=4, obj_thresh=OBJ, iou_thresh=IOU,
+                                               verbose=False, workers=16, decode=d_)
+        dgpu, dpil = dec_as('gpu'), dec_as('pil')
+        dgpu(); dpil()
+        tg, tl = [], []
+        for _ in range(3):
+            tg.append(timed(dgpu)); tl.append(timed(dpil))
+        mb = sum(Path(f).stat().st_size for f in paths) / 1e6
+        say(f'(vi) 256 JPEG files ({mb:.1f} MB, PIL quality 90, 4:2:0), draw=False, seconds per call:')
+        say(f"    decode='gpu'                   {med(tg)}   -> {256 / statistics.median(tg):.0f} pictures/s")
+        say(f"    decode='pil' (16 pool threads) {med(tl)}   -> {256 / statistics.median(tl):.0f} pictures/s")
+        parsed = [jpeg.parse_baseline(Path(f).read_bytes()) for f in paths[:32]]
+        buf, jpics, scan_bytes, table_bytes = jpeg.plan_decode(parsed)
+        d_buf = torch.from_numpy(buf).cuda()
+        d_jpics = torch.from_numpy(jpics.view(np.uint8).reshape(32, -1).copy()).cuda()
+        need = engine.jpeg_decode_workspace_bytes(jpics)
+        jwork = torch.empty(need, dtype=torch.uint8, device='cuda')
+        status = torch.empty(32, dtype=torch.int32, device='cuda')
+        dec_gpu = lambda: [engine.jpeg_decode_ragged_u8(d_buf[:scan_bytes], d_jpics, d_buf[scan_bytes:], d_table, d_packed, work_bytes=need, work=jwork,
+                                                        status=status) for _ in range(50)]
+        dec_gpu()
+        tdec = [timed(dec_gpu) / 50 * 1e6 for _ in range(3)]
+        at = (4 * 33 + 15) & ~15
+        rounds = jwork[at:at + 4 * 32].cpu().numpy().view(np.uint32)
+        tiles = [-(-(-(-len(q.scan) // 128)) // 256) for q in parsed]
+        say(f'    yk_jpeg_decode_ragged_u8 alone, 32 pictures ({scan_bytes / 1e6:.2f} MB of scans -> {d_packed.numel() / 1e6:.1f} MB, workspace {need / 1e6:.0f} MB, '
+            f'statuses all 0: {not status.any().item()}): microseconds per call (6 launches, 50 calls in a row, host included) {med(tdec)}')
+        say(f'    fixed-point rounds per picture at chunk_bytes {128} (summed over its tiles of 256 chunks; tiles per picture {min(tiles)} .. {max(tiles)}): '
+            f'min {int(rounds.min())}, median {int(np.median(rounds))}, max {int(rounds.max())}')
+        if OUT_DECODE is not None:
+            OUT_DECODE.write_text('\n'.join(lines[:1] + lines[mark:]) + '\n')
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
 
