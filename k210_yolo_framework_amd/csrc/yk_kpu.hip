@@ -8,7 +8,7 @@
 // The host (k210_yolo_framework_amd/kmodel.py:pack_kpu) folds the per-channel constants: wconst = (arg_w*sum(w) >> shr_w) + arg_add*g_ic.
 //
 // Dense convs are an implicit GEMM on the int8 MFMA (v_mfma_i32_16x16x64_i8): operands x' = x ^ 0x80, w' = w ^ 0x80 (x - 128, w - 128 as
-// int8) and  sum(x*w) = sum(x'w') + 128 sum(x') + 128 sum(w') + 16384 K,  exact in int32 for K <= 6912.  The K axis is (ky, kx, c) with
+// int8) and  sum(x*w) = sum(x'w') + 128 sum(x') + 128 sum(w') + 16384 K,  exact in int32 for K <= 27648.  The K axis is (ky, kx, c) with
 // the channels of one tap padded to a multiple of 16 (x' = w' = 0 there: they add nothing to any sum).  Depthwise convs run on the VALU.
 // Activations are uint8 NHWC per image, each tensor in its own buffer; main-memory layers are gathers, DEQUANTIZE writes the fp32 output.
 #include "yk_common.h"
