@@ -82,8 +82,9 @@ __global__ void __launch_bounds__(256) yolo_loss_kernel(loss_args a, const float
         if (ignore_out) ignore_out[(size_t)b * P + p] = ign;
         const bool ob = tc > a.obj_thresh;
         const float obj = tc;
-        // targets in grid scale
-        const float gx = tx * (float)a.w - (float)col, gy = ty * (float)a.h - (float)row;
+        // targets in grid scale.  One rounding (fma): rounding tx * w first costs the position inside the cell log2(w) bits, and with them
+        // the xy gradient on a wide grid (257 columns: 5e-6 off, found by tests/test_gpu_loss.py against the float64-pinned oracle)
+        const float gx = fmaf(tx, (float)a.w, -(float)col), gy = fmaf(ty, (float)a.h, -(float)row);
         const float gw = ob ? logf(tw / a.anchors[an][0]) : 0.f, gh = ob ? logf(th / a.anchors[an][1]) : 0.f;
         const float cw = 2.f - tw * th;
         s_xy += (double)(obj * cw * (l_bce(gx, px) + l_bce(gy, py)));

@@ -72,7 +72,9 @@ def yolo_loss(y_true: np.ndarray, y_pred: np.ndarray, anchors_l: np.ndarray, obj
             ignore[b] = (best < F(iou_thresh)).astype(F)
 
     # ---- targets in grid scale (utils.py:550-572,762-764)
-    g_txy = (txy * wh_hw - offset).astype(F)
+    # product and difference rounded ONCE (an fma): rounding the fp32 product first costs the position inside the cell log2(w) bits,
+    # which at w = 257 is more than tests/test_oracle_loss.py allows the gradient
+    g_txy = (txy.astype(np.float64) * wh_hw - offset).astype(F)
     with np.errstate(divide='ignore', invalid='ignore'):
         g_twh = np.log(twh / anc, dtype=F)
     g_twh = np.where(obj_bool[..., None], g_twh, F(0)).astype(F)

@@ -115,6 +115,54 @@ def test_augmented_pipeline_equals_the_host_generator_for_every_rank(tmp_path):
         assert pipe.producer_images_per_sec() > 0
 
 
+def test_augmented_pipeline_divides_by_the_augmented_images_own_maximum(tmp_path):
+    """Dark and sub-255 images, and dim ones whose only 255 is a corner pixel: the warp moves it out of the frame or blends it, so the
+    divisor is the maximum of the augmented image, not of its source."""
+    from PIL import Image
+    from k210_yolo_framework_amd import pipeline, training
+    from tests.test_gpu_pipeline import divisors
+    h = _h()
+    rng = np.random.default_rng(16)
+    items, corner = [], []
+    for k in range(12):
+        hw = [(240, 320), (375, 500), (333, 500), (224, 320)][k % 4]
+        if k % 3 == 2:
+            img = rng.integers(0, 256, (*HW, 3), dtype=np.uint8) // 16
+            img[[0, 0, -1, -1][k % 4], [0, -1, 0, -1][k % 4]] = 255
+            corner.append(k)
+        else:
+            img = rng.integers(0, 256, (*hw, 3), dtype=np.uint8) // 16 if k % 3 == 0 else rng.integers(0, 200, (*hw, 3), dtype=np.uint8)
+        n = int(rng.integers(1, 4))
+        boxes = np.concatenate([rng.integers(0, 20, (n, 1)).astype(float), rng.uniform(0.05, 0.95, (n, 2)), rng.uniform(0.05, 0.3, (n, 2))], 1)
+        if k % 5 == 0:
+            p = tmp_path / f'{k}.png'
+            Image.fromarray(img).save(p)
+            items.append((str(p), boxes))
+        else:
+            items.append((img, boxes))
+    GB, seed, epoch = 4, 3, 1
+    order = pipeline.epoch_order(len(items), seed=seed, epoch=epoch, shuffle=True)
+
+    class _Fixed:
+        def permutation(self, n):
+            return order
+    want = list(training.batches(h, items, GB, _Fixed(), shuffle=True, augment=(seed, epoch)))
+    plain = list(training.batches(h, items, GB, _Fixed(), shuffle=True))
+    assert len(want) == 3
+    div, div_plain = np.array([divisors(wx) for wx, _ in want]), np.array([divisors(px) for px, _ in plain])
+    assert all(len(set(d)) > 1 for d in div), div
+    is_corner = np.isin(order[:12].reshape(3, GB), corner)
+    assert (div_plain[is_corner] == 255).all() and (div[is_corner] != 255).any(), (div, div_plain)
+    pipe = pipeline.InputPipeline(h, items, GB, 0, 1, seed=seed, epoch=epoch, shuffle=True, workers=4, prefetch=2, augment=True)
+    got = [(x.cpu().numpy(), [y.cpu().numpy() for y in ys]) for x, ys in pipe]
+    pipe.close()
+    assert len(got) == len(want)
+    for (gx, gys), (wx, wys) in zip(got, want):
+        np.testing.assert_array_equal(gx, wx)
+        for gy, wy in zip(gys, wys):
+            np.testing.assert_array_equal(gy, wy)
+
+
 def test_make_train_with_the_augmenter(tmp_path, capsys):
     from k210_yolo_framework_amd import training
     training.cli(['--synthetic', '64', '--augmenter', 'True', '--max_steps', '3', '--model_def', 'yolo_mobilev1', '--depth_multiplier',

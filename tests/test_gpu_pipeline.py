@@ -46,6 +46,51 @@ def test_pipeline_equals_the_host_generator_for_every_rank(tmp_path):
         assert pipe.producer_images_per_sec() > 0
 
 
+def divisors(x):
+    """The maximum each image of a normalised batch [B,H,W,3] was divided by: its levels are k / max, and two neighbouring k occur."""
+    return [int(round(1.0 / float(np.diff(np.unique(img)).min()))) for img in x]
+
+
+def test_pipeline_equals_the_host_generator_when_the_maxima_differ(tmp_path):
+    """Dark images and images that stop short of 255 next to full-range ones: each is divided by its own maximum."""
+    from PIL import Image
+    from k210_yolo_framework_amd import pipeline, training
+    from k210_yolo_framework_amd.helper import Helper, VOC_ANCHORS
+    h = Helper(None, 20, VOC_ANCHORS, [[224, 320]], [[7, 10], [14, 20]])
+    rng = np.random.default_rng(15)
+    items = []
+    for k in range(12):
+        hw = [(240, 320), (375, 500), (333, 500), (224, 320)][k % 4]
+        img = [lambda: rng.integers(0, 256, (*hw, 3), dtype=np.uint8) // 16, lambda: rng.integers(0, 200, (*hw, 3), dtype=np.uint8),
+               lambda: rng.integers(0, 256, (*hw, 3), dtype=np.uint8)][k % 3]()
+        n = int(rng.integers(1, 4))
+        boxes = np.concatenate([rng.integers(0, 20, (n, 1)).astype(float), rng.uniform(0.2, 0.8, (n, 2)), rng.uniform(0.05, 0.3, (n, 2))], 1)
+        if k % 5 == 0:
+            p = tmp_path / f'{k}.png'
+            Image.fromarray(img).save(p)
+            items.append((str(p), boxes))
+        else:
+            items.append((img, boxes))
+    GB = 4
+    order = pipeline.epoch_order(len(items), seed=3, epoch=1, shuffle=True)
+
+    class _Fixed:
+        def permutation(self, n):
+            return order
+    want = list(training.batches(h, items, GB, _Fixed(), shuffle=True))
+    assert len(want) == 3
+    div = [divisors(wx) for wx, _ in want]
+    assert all(len(set(d)) > 1 for d in div) and min(map(min, div)) == 15 and max(map(max, div)) == 255, div
+    pipe = pipeline.InputPipeline(h, items, GB, 0, 1, seed=3, epoch=1, shuffle=True, workers=4, prefetch=2)
+    got = [(x.cpu().numpy(), [y.cpu().numpy() for y in ys]) for x, ys in pipe]
+    pipe.close()
+    assert len(got) == len(want)
+    for (gx, gys), (wx, wys) in zip(got, want):
+        np.testing.assert_array_equal(gx, wx)
+        for gy, wy in zip(gys, wys):
+            np.testing.assert_array_equal(gy, wy)
+
+
 def test_worker_errors_reach_the_consumer():
     from k210_yolo_framework_amd import pipeline
     from k210_yolo_framework_amd.helper import Helper, VOC_ANCHORS

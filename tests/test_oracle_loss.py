@@ -6,7 +6,7 @@ import torch
 import torch.nn.functional as TF
 
 from oracle import loss_ref
-from k210_yolo_framework_amd.helper import Helper, VOC_ANCHORS
+from k210_yolo_framework_amd.helper import Helper, VOC_ANCHORS, tf_iou, tf_xywh_to_all
 
 
 def make_case(seed, B=4, layer=1, n_boxes=(1, 6)):
@@ -21,6 +21,61 @@ def make_case(seed, B=4, layer=1, n_boxes=(1, 6)):
     y_true = np.stack(ys).astype(np.float32)
     y_pred = rng.normal(0, 1.5, y_true.shape).astype(np.float32)
     return h, y_true, y_pred
+
+
+SHAPES = [(3, 5, 1, 1), (3, 5, 8, 2), (8, 8, 4, 3), (1, 257, 1, 2)]        # (h, w, A, C): h*w*A = 15, 120, 256 (one chunk), 257 (one + 1)
+
+
+def make_shape_case(seed, hh, ww, A, C, B=3, n_boxes=(1, 7)):
+    """`make_case` for one layer of any grid, anchor count and class count: random anchors, 1 to 6 boxes per image."""
+    rng = np.random.default_rng(seed)
+    anc = rng.uniform(0.05, 0.5, (1, A, 2)).astype(np.float32)
+    h = Helper(None, C, anc, [[32 * hh, 32 * ww]], [[hh, ww]])
+    ys = []
+    for b in range(B):
+        n = int(rng.integers(*n_boxes))
+        boxes = np.stack([rng.integers(0, C, n), rng.uniform(0.05, 0.95, n), rng.uniform(0.05, 0.95, n),
+                          rng.uniform(0.05, 0.9, n), rng.uniform(0.05, 0.9, n)], 1)
+        ys.append(h.box_to_label(boxes)[0])
+    y_true = np.stack(ys).astype(np.float32)
+    y_pred = rng.normal(0, 1.5, y_true.shape).astype(np.float32)
+    return h, y_true, y_pred
+
+
+SWITCH_SEED = 0
+
+
+def make_switch_case(seed=SWITCH_SEED):
+    """26x26x3 grid, 2 classes: image 0 has exactly 1024 labelled cells (the most the loss kernel lists), image 1 has 1025 (it scans the
+    label tensor).  Small boxes centred in their own cell, at random slots."""
+    rng = np.random.default_rng(seed)
+    B, hh, ww, A, C = 2, 26, 26, 3, 2
+    anc = rng.uniform(0.05, 0.5, (1, A, 2)).astype(np.float32)
+    h = Helper(None, C, anc, [[32 * hh, 32 * ww]], [[hh, ww]])
+    P = hh * ww * A
+    y_true = np.zeros((B, P, 5 + C), np.float32)
+    for b, n in enumerate((1024, 1025)):
+        slot = np.sort(rng.choice(P, n, replace=False))
+        cell = slot // A
+        y_true[b, slot, 0] = (cell % ww + rng.uniform(0.05, 0.95, n)) / ww
+        y_true[b, slot, 1] = (cell // ww + rng.uniform(0.05, 0.95, n)) / hh
+        y_true[b, slot, 2:4] = rng.uniform(0.02, 0.2, (n, 2))
+        y_true[b, slot, 4] = 1
+        y_true[b, slot, 5 + rng.integers(0, C, n)] = 1
+    y_true = y_true.reshape(B, hh, ww, A, 5 + C)
+    y_pred = rng.normal(0, 1, y_true.shape).astype(np.float32)
+    return h, y_true, y_pred
+
+
+def best_iou_f64(h, y_true, y_pred, obj_thresh=0.7):
+    """Every prediction's best IoU with its image's labelled boxes, in float64 (helper.tf_xywh_to_all / tf_iou) -> [B,h,w,A]."""
+    a_xy, a_wh = tf_xywh_to_all(y_pred[..., 0:2].astype(np.float64), y_pred[..., 2:4].astype(np.float64), 0, h)
+    best = np.full(y_pred.shape[:4], -np.inf)
+    for b in range(len(y_pred)):
+        m = y_true[b, ..., 4] > obj_thresh
+        if m.any():
+            best[b] = tf_iou(a_xy[b], a_wh[b], y_true[b, ..., 0:2][m].astype(np.float64), y_true[b, ..., 2:4][m].astype(np.float64)).max(-1)
+    return best
 
 
 def torch_loss(y_true, y_pred, anchors, obj_thresh, iou_thresh, ow, nw, ww):
@@ -86,3 +141,32 @@ def test_empty_image_ignore_mask_is_one_and_metrics_threshold_logits():
     p = y_pred[..., 4] > 0.7
     assert (tp, fp, fn) == (int((t & p).sum()), int((~t & p).sum()), int((t & ~p).sum()))
     assert fp > 0
+
+
+@pytest.mark.parametrize('hh,ww,A,C', SHAPES)
+def test_loss_value_and_gradient_vs_torch_autograd_at_other_grids_anchor_and_class_counts(hh, ww, A, C):
+    """The shapes tests/test_gpu_loss.py holds the kernel to: one and YK_MAX_ANCHORS anchors, one class, 256 and 257 predictions."""
+    h, y_true, y_pred = make_shape_case(hh * ww * A + C, hh, ww, A, C)
+    assert y_true.shape == (3, hh, ww, A, 5 + C) and (y_true[..., 4].reshape(3, -1).sum(1) >= 1).all()
+    losses, grad, ign, cnt = loss_ref.yolo_loss(y_true, y_pred, h.anchors[0], 0.7, 0.5, 5, 0.5, 0.5)
+    tl, tg, ti = torch_loss(y_true, y_pred, h.anchors[0], 0.7, 0.5, 5, 0.5, 0.5)
+    for k in tl:
+        assert abs(losses[k] - tl[k]) <= 2e-5 * max(1.0, abs(tl[k])), (k, losses[k], tl[k])
+    assert np.array_equal(ign, ti.astype(np.float32))
+    assert np.abs(grad - tg).max() <= 2e-6 * max(1.0, np.abs(tg).max())
+    t, p = y_true[..., 4] > 0.7, y_pred[..., 4] > 0.7
+    assert cnt == (int((t & p).sum()), int((~t & p).sum()), int((t & ~p).sum()))
+
+
+def test_loss_at_1024_and_1025_boxes_vs_torch_autograd_and_float64_iou():
+    h, y_true, y_pred = make_switch_case()
+    assert (y_true[..., 4] > 0.7).reshape(2, -1).sum(1).tolist() == [1024, 1025]
+    best = best_iou_f64(h, y_true, y_pred)
+    assert np.abs(best - 0.5).min() > 1e-5                    # the seed's property: no prediction sits on the threshold
+    losses, grad, ign, cnt = loss_ref.yolo_loss(y_true, y_pred, h.anchors[0], 0.7, 0.5, 1, 1, 1)
+    tl, tg, ti = torch_loss(y_true, y_pred, h.anchors[0], 0.7, 0.5, 1, 1, 1)
+    for k in tl:
+        assert abs(losses[k] - tl[k]) <= 2e-5 * max(1.0, abs(tl[k])), (k, losses[k], tl[k])
+    assert np.array_equal(ign, (best < 0.5).astype(np.float32)) and np.array_equal(ign, ti.astype(np.float32))
+    assert 0.05 < 1 - ign[0].mean() < 0.5 and 0.05 < 1 - ign[1].mean() < 0.5        # both values of the mask are well represented
+    assert np.abs(grad - tg).max() <= 2e-6 * max(1.0, np.abs(tg).max())
