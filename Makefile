@@ -10,6 +10,8 @@
 #                    [QAT=True QATMOMENTUM=0.99 QATOBSERVE=8]: quantisation-aware fine-tuning, saves yolo_qat_model.h5 + yolo_qat_ranges.npz
 #   make kmodel      CKPT=yolo_model.h5 OUT=yolo.kmodel|.kfpkg [SYNTHETIC=256 | CALIB=data/voc_img_ann.npy]: 8-bit K210 model, calibrated on the GPU
 #                    [RANGES=yolo_qat_ranges.npz]: the ranges a QAT run learned instead of a calibration
+#                    [CALIBMETHOD=minmax|percentile|mse CALIBPCT=99.99 CALIBBINS=2048]: minmax (default) takes each tensor's exact range; percentile
+#                    and mse clip it from a histogram taken on the GPU in a second pass over the calibration images (not with RANGES=)
 #   make eval        CKPT=yolo_model.h5|yolo.kmodel [PRECISION=f16x2|f16|kpu] [ANN=data/voc_img_ann.npy | SYNTHETIC=256] [EVALOBJ=0.05] [VOC07=True]:
 #                    VOC mAP of the checkpoint, network and metric on the GPU; prints the per-class AP table, writes eval.json beside CKPT
 #                    (make train VALMAP=True appends val_mAP to every epoch line)
@@ -66,6 +68,9 @@ QUALITY       ?= 75
 OUT           ?= yolo.kmodel
 CALIB         ?= data/$(DATASET)_img_ann.npy
 RANGES        ?=
+CALIBMETHOD   ?=
+CALIBPCT      ?= 99.99
+CALIBBINS     ?= 2048
 GPUS          ?= 1
 # anchors only (reference Makefile:27-29)
 ANCNUM        ?= 3
@@ -108,7 +113,8 @@ train:
 # the step the reference leaves to keras_freeze.py + nncase: CKPT -> 8-bit kmodel; SYNTHETIC=N calibrates on generated images
 kmodel:
 	$(PY) make_kmodel.py $(CKPT) $(OUT) --train_set $(DATASET) --class_num $(CLSNUM) --model_def $(MODEL) --depth_multiplier $(DEPTHMUL) \
-		--image_size $(IMGSIZE) --output_size $(OUTSIZE) $(if $(RANGES),--ranges $(RANGES),$(if $(filter-out 0,$(SYNTHETIC)),--synthetic $(SYNTHETIC),--calib $(CALIB)))
+		--image_size $(IMGSIZE) --output_size $(OUTSIZE) $(if $(RANGES),--ranges $(RANGES),$(if $(filter-out 0,$(SYNTHETIC)),--synthetic $(SYNTHETIC),--calib $(CALIB))) \
+		$(if $(CALIBMETHOD),--calib_method $(CALIBMETHOD) --calib_percentile $(CALIBPCT) --calib_bins $(CALIBBINS))
 
 # VOC mAP of CKPT (.h5 / .npz, or .kmodel / .kfpkg with PRECISION=kpu) on the validation head of ANN, or on SYNTHETIC=N generated images
 eval:

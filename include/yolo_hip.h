@@ -598,6 +598,24 @@ int yk_scale_act_range_f32(const float *z, long long M, int C, const float *scal
                            uint32_t *d_range, int slot, void *stream);
 int yk_range_read(const uint32_t *d_range, int n_slots, float *h_min, float *h_max, int *h_flags);
 
+/* ---- histograms for the clipped calibrations (quantize.clip_range): a second pass over the calibration set, after the ranges.
+ * d_hist holds uint64 counts [n_slots][nbins], 16 <= nbins <= 4096; d_flags one uint32 per slot.  A slot's bins are equal parts of [lo, hi],
+ * the range of its tensor widened to contain 0; the caller passes lo and inv = (float)(nbins / ((double)hi - lo)), rounded once (0 for
+ * hi == lo).  The bin of v:  t = (v - lo) * inv  in fp32, one rounding per operation (no FMA);  t >= nbins -> nbins - 1,  t > 0 -> (int)t
+ * (truncated),  otherwise 0.  So values outside [lo, hi] land in the end bins, denormals are kept, and a zero-width range puts everything in
+ * bin 0.  A NaN or an infinity is not counted: it sets the slot's sticky flag.  Each workgroup counts in LDS (uint32) and adds its non-zero
+ * bins with 64-bit atomics: integer adds only, so the counts are bitwise independent of scheduling, launch geometry and stream.  Launches are
+ * asynchronous on `stream`.  Bad arguments, and an n so large that one workgroup could count 2^32 elements: YK_ERR_ARG.
+ * yk_hist_reset          the counts of slots [0, n_slots) to 0 (the flags are the caller's to clear);
+ * yk_hist_f32            counts x[0..n) into `slot` (accumulates over calls);
+ * yk_scale_act_hist_f32  the twin of yk_scale_act_range_f32: the same y, bit for bit, stored by the same launch that counts it into `slot`;
+ * yk_hist_read           the counts [n_slots][nbins] in one device-to-host copy (synchronises) and the n_slots flag words in a second. */
+int yk_hist_reset(uint64_t *d_hist, int n_slots, int nbins, void *stream);
+int yk_hist_f32(const float *x, long long n, float lo, float inv, int nbins, uint64_t *d_hist, uint32_t *d_flags, int slot, void *stream);
+int yk_scale_act_hist_f32(const float *z, long long M, int C, const float *scale, const float *bias, int act, float alpha, float *y, float lo,
+                          float inv, int nbins, uint64_t *d_hist, uint32_t *d_flags, int slot, void *stream);
+int yk_hist_read(const uint64_t *d_hist, const uint32_t *d_flags, int n_slots, int nbins, uint64_t *h_counts, int *h_flags);
+
 /* ---- quantisation-aware training (train.Trainer(qat=...)): the kmodel's uint8 codes simulated in fp32 inside the step.
  * The rule, quantize.qparams in fp32 with one rounding per operation (no FMA contraction), for a range (lo, hi):
  *   lo' = lo < 0 ? lo : +0, hi' = hi > 0 ? hi : +0;  hi' == lo': s = 1.0f / 255.0f, zp = 0;  else s = (hi' - lo') / 255.0f,

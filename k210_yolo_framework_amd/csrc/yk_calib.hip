@@ -10,6 +10,13 @@
 // Per launch: grid-stride loop with 16-byte loads (and stores), wave reduction in registers (__shfl_xor), block reduction through 2 x 4
 // words of LDS, then ONE atomicMin and ONE atomicMax per workgroup (vector atomics on global memory), and an atomicOr only from a
 // workgroup that met a non-finite value.  The key, the accumulator and the workgroup fold live in yk_range.h (yk_qat.hip shares them).
+//
+// Second pass, for the clipped calibrations (quantize.clip_range): a histogram of NB equal bins per tensor over the range the first pass
+// found, uint64 counts [n_slots][NB].  The bin of v is  t = (v - lo) * inv  (one rounding per operation), truncated and clamped to
+// [0, NB - 1]: values outside [lo, hi] land in the end bins, a NaN or an infinity is not counted and sets the slot's flag.  Same launch shape
+// as the range kernels.  Each workgroup counts into a private uint32 [NB] in LDS (LDS atomics; the bin that holds real zero - most of a
+// post-ReLU tensor - is first summed over the wave with a ballot, one LDS add per wave) and at the end adds its non-zero bins to global
+// memory with 64-bit vector atomics.  Integer adds only: the counts do not depend on scheduling, launch geometry or stream.
 #include "yk_range.h"
 
 namespace {
@@ -78,6 +85,127 @@ __global__ __launch_bounds__(CAL_BLOCK) void scale_act_range_kernel(const float 
         a.add(r);
     }
     fold(a, slot);
+}
+
+// ---- histograms ---------------------------------------------------------------------------------------------------------------------
+constexpr int HIST_MIN_BINS = 16, HIST_MAX_BINS = 4096;
+constexpr bool HIST_WAVE_ZERO = true;                     // the zero bin per wave (ballot + popcount) before the per-lane LDS atomics
+
+// truncation and clamp written as comparisons on t, so that an overflowing or NaN t (zero-width and sub-normal-width ranges) is defined:
+// t >= NB -> NB - 1, t > 0 -> (int)t, anything else (t <= 0, NaN) -> 0
+__device__ __forceinline__ int bin_of(float v, float lo, float inv, int nb) {
+    const float t = __fmul_rn(__fsub_rn(v, lo), inv);
+    return t >= (float)nb ? nb - 1 : (t > 0.f ? (int)t : 0);
+}
+
+struct Hist {
+    uint32_t *s_h;                                       // LDS, [nb]
+    float lo, inv;
+    int nb, zbin;
+    uint32_t bad = 0u;
+    __device__ __forceinline__ Hist(uint32_t *lds, float lo_, float inv_, int nb_) : s_h(lds), lo(lo_), inv(inv_), nb(nb_) {
+        zbin = bin_of(0.f, lo, inv, nb);
+        for (int b = threadIdx.x; b < nb; b += CAL_BLOCK) s_h[b] = 0u;
+        __syncthreads();
+    }
+    __device__ __forceinline__ void add(float v) {
+        const bool ok = (__float_as_uint(v) & 0x7F800000u) != 0x7F800000u;
+        if (!ok) bad = 1u;
+        const int b = bin_of(v, lo, inv, nb);
+        if (HIST_WAVE_ZERO) {
+            const bool z = ok && b == zbin;
+            const unsigned long long m = __ballot(z);                          // over the lanes active here
+            if (z) {
+                if ((int)(threadIdx.x & (YK_WAVE - 1)) == __ffsll((long long)m) - 1) atomicAdd(s_h + zbin, (uint32_t)__popcll(m));
+            } else if (ok) {
+                atomicAdd(s_h + b, 1u);
+            }
+        } else if (ok) {
+            atomicAdd(s_h + b, 1u);
+        }
+    }
+    // the workgroup's non-zero bins into the slot's row; the flag only from a workgroup that met a non-finite value
+    __device__ __forceinline__ void flush(unsigned long long *row, uint32_t *flag) {
+        __shared__ uint32_t s_bad;
+        if (threadIdx.x == 0) s_bad = 0u;
+        __syncthreads();                                                       // also: every LDS count is in
+        if (bad) atomicOr(&s_bad, 1u);
+        for (int b = threadIdx.x; b < nb; b += CAL_BLOCK) {
+            const uint32_t c = s_h[b];
+            if (c) atomicAdd(row + b, (unsigned long long)c);
+        }
+        __syncthreads();
+        if (threadIdx.x == 0 && s_bad) atomicOr(flag, 1u);
+    }
+};
+
+__global__ __launch_bounds__(CAL_BLOCK) void hist_kernel(const float *__restrict__ x, size_t n4, size_t n, float lo, float inv, int nb,
+                                                          unsigned long long *row, uint32_t *flag) {
+    extern __shared__ uint32_t s_hist[];
+    Hist h(s_hist, lo, inv, nb);
+    const size_t step = (size_t)gridDim.x * CAL_BLOCK;
+    const float4 *x4 = reinterpret_cast<const float4 *>(x);
+    for (size_t i = (size_t)blockIdx.x * CAL_BLOCK + threadIdx.x; i < n4; i += step) {
+        const float4 v = x4[i];
+        h.add(v.x);
+        h.add(v.y);
+        h.add(v.z);
+        h.add(v.w);
+    }
+    for (size_t i = 4 * n4 + (size_t)blockIdx.x * CAL_BLOCK + threadIdx.x; i < n; i += step) h.add(x[i]);
+    h.flush(row, flag);
+}
+
+// the twins of scale_act_range_vec_kernel / scale_act_range_kernel: the same expression for y (this unit compiles with -ffp-contract=off, so
+// it rounds the same way in both), the histogram in place of the min / max
+__global__ __launch_bounds__(CAL_BLOCK) void scale_act_hist_vec_kernel(const float *__restrict__ z, size_t n4, int C, const float *__restrict__ scale,
+                                                                        const float *__restrict__ bias, int act, float alpha, float *__restrict__ y,
+                                                                        float lo, float inv, int nb, unsigned long long *row, uint32_t *flag) {
+    extern __shared__ uint32_t s_hist[];
+    Hist h(s_hist, lo, inv, nb);
+    const size_t step = (size_t)gridDim.x * CAL_BLOCK;
+    const float4 *z4 = reinterpret_cast<const float4 *>(z);
+    float4 *y4 = reinterpret_cast<float4 *>(y);
+    const size_t c4 = (size_t)(C / 4);
+    for (size_t i = (size_t)blockIdx.x * CAL_BLOCK + threadIdx.x; i < n4; i += step) {
+        const size_t c = (i % c4) * 4;
+        const float4 v = z4[i];
+        const float4 s = *reinterpret_cast<const float4 *>(scale + c);
+        const float4 b = *reinterpret_cast<const float4 *>(bias + c);
+        float4 r;
+        r.x = c_act(v.x * s.x + b.x, act, alpha);
+        r.y = c_act(v.y * s.y + b.y, act, alpha);
+        r.z = c_act(v.z * s.z + b.z, act, alpha);
+        r.w = c_act(v.w * s.w + b.w, act, alpha);
+        y4[i] = r;
+        h.add(r.x);
+        h.add(r.y);
+        h.add(r.z);
+        h.add(r.w);
+    }
+    h.flush(row, flag);
+}
+
+__global__ __launch_bounds__(CAL_BLOCK) void scale_act_hist_kernel(const float *__restrict__ z, size_t n, int C, const float *__restrict__ scale,
+                                                                    const float *__restrict__ bias, int act, float alpha, float *__restrict__ y,
+                                                                    float lo, float inv, int nb, unsigned long long *row, uint32_t *flag) {
+    extern __shared__ uint32_t s_hist[];
+    Hist h(s_hist, lo, inv, nb);
+    const size_t step = (size_t)gridDim.x * CAL_BLOCK;
+    for (size_t i = (size_t)blockIdx.x * CAL_BLOCK + threadIdx.x; i < n; i += step) {
+        const int c = (int)(i % (size_t)C);
+        const float r = c_act(z[i] * scale[c] + bias[c], act, alpha);
+        y[i] = r;
+        h.add(r);
+    }
+    h.flush(row, flag);
+}
+
+// what a call may histogram: NB in range, a finite lo, inv >= 0 (+inf allowed: a range narrower than NB / FLT_MAX), and no workgroup of
+// `grid` that could count 2^32 elements into one uint32 bin (a workgroup takes at most n / grid + 4 * CAL_BLOCK + 3 of them)
+inline bool hist_args_ok(long long n, float lo, float inv, int nbins, int slot, unsigned grid) {
+    return n > 0 && nbins >= HIST_MIN_BINS && nbins <= HIST_MAX_BINS && slot >= 0 && lo - lo == 0.f && inv >= 0.f &&
+           (unsigned long long)n / grid + 4ull * CAL_BLOCK + 3ull < (1ull << 32);
 }
 
 __global__ void range_reset_kernel(uint32_t *r, int n_slots) {
@@ -163,5 +291,74 @@ extern "C" int yk_range_read(const uint32_t *d_range, int n_slots, float *h_min,
         h_flags[i] = (int)h[YK_RANGE_WORDS * i + 2];
     }
     free(h);
+    return YK_OK;
+}
+
+extern "C" int yk_hist_reset(uint64_t *d_hist, int n_slots, int nbins, void *stream) {
+    if (!d_hist || n_slots <= 0 || nbins < HIST_MIN_BINS || nbins > HIST_MAX_BINS) {
+        yk_set_error("yk_hist_reset: bad argument");
+        return YK_ERR_ARG;
+    }
+    YK_HIP(hipMemsetAsync(d_hist, 0, (size_t)n_slots * (size_t)nbins * sizeof(uint64_t), (hipStream_t)stream));
+    return YK_OK;
+}
+
+extern "C" int yk_hist_f32(const float *x, long long n, float lo, float inv, int nbins, uint64_t *d_hist, uint32_t *d_flags, int slot,
+                           void *stream) {
+    if (!x || !d_hist || !d_flags || n <= 0) {
+        yk_set_error("yk_hist_f32: bad argument");
+        return YK_ERR_ARG;
+    }
+    const size_t n4 = aligned16(x) ? (size_t)n / 4 : 0;
+    const size_t items = n4 > (size_t)n - 4 * n4 ? n4 : (size_t)n - 4 * n4;
+    const unsigned grid = grid_for(items);
+    if (!hist_args_ok(n, lo, inv, nbins, slot, grid)) {
+        yk_set_error("yk_hist_f32: bad argument (16 <= nbins <= 4096, finite lo, inv >= 0, n / workgroups < 2^32)");
+        return YK_ERR_ARG;
+    }
+    hipLaunchKernelGGL(hist_kernel, dim3(grid), dim3(CAL_BLOCK), (size_t)nbins * sizeof(uint32_t), (hipStream_t)stream, x, n4, (size_t)n, lo, inv,
+                       nbins, reinterpret_cast<unsigned long long *>(d_hist) + (size_t)slot * nbins, d_flags + slot);
+    YK_HIP(hipGetLastError());
+    return YK_OK;
+}
+
+extern "C" int yk_scale_act_hist_f32(const float *z, long long M, int C, const float *scale, const float *bias, int act, float alpha, float *y,
+                                     float lo, float inv, int nbins, uint64_t *d_hist, uint32_t *d_flags, int slot, void *stream) {
+    if (!z || !scale || !bias || !y || !d_hist || !d_flags || M <= 0 || C <= 0 || act < YK_ACT_NONE || act > YK_ACT_LEAKY ||
+        M > (long long)(~0ull >> 1) / C) {
+        yk_set_error("yk_scale_act_hist_f32: bad argument");
+        return YK_ERR_ARG;
+    }
+    const size_t n = (size_t)M * (size_t)C;
+    const bool vec = C % 4 == 0 && aligned16(z) && aligned16(y) && aligned16(scale) && aligned16(bias);
+    const unsigned grid = grid_for(vec ? n / 4 : n);
+    if (!hist_args_ok((long long)n, lo, inv, nbins, slot, grid)) {
+        yk_set_error("yk_scale_act_hist_f32: bad argument (16 <= nbins <= 4096, finite lo, inv >= 0, M * C / workgroups < 2^32)");
+        return YK_ERR_ARG;
+    }
+    unsigned long long *row = reinterpret_cast<unsigned long long *>(d_hist) + (size_t)slot * nbins;
+    const size_t lds = (size_t)nbins * sizeof(uint32_t);
+    if (vec)
+        hipLaunchKernelGGL(scale_act_hist_vec_kernel, dim3(grid), dim3(CAL_BLOCK), lds, (hipStream_t)stream, z, n / 4, C, scale, bias, act, alpha, y, lo,
+                           inv, nbins, row, d_flags + slot);
+    else
+        hipLaunchKernelGGL(scale_act_hist_kernel, dim3(grid), dim3(CAL_BLOCK), lds, (hipStream_t)stream, z, n, C, scale, bias, act, alpha, y, lo, inv,
+                           nbins, row, d_flags + slot);
+    YK_HIP(hipGetLastError());
+    return YK_OK;
+}
+
+extern "C" int yk_hist_read(const uint64_t *d_hist, const uint32_t *d_flags, int n_slots, int nbins, uint64_t *h_counts,
+                            int *h_flags) {
+    if (!d_hist || !d_flags || n_slots <= 0 || nbins < HIST_MIN_BINS || nbins > HIST_MAX_BINS || !h_counts || !h_flags) {
+        yk_set_error("yk_hist_read: bad argument");
+        return YK_ERR_ARG;
+    }
+    hipError_t e = hipMemcpy(h_counts, d_hist, (size_t)n_slots * (size_t)nbins * sizeof(uint64_t), hipMemcpyDeviceToHost);   // synchronises
+    if (e == hipSuccess) e = hipMemcpy(h_flags, d_flags, (size_t)n_slots * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) {
+        yk_set_error("yk_hist_read: hipMemcpy -> %s", hipGetErrorString(e));
+        return YK_ERR_HIP;
+    }
     return YK_OK;
 }

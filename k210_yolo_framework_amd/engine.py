@@ -80,6 +80,7 @@ def lib() -> C.CDLL:
                    'yk_maxpool2_bwd_f32', 'yk_axpy_f32', 'yk_adam_f32', 'yk_prune_masks_f32', 'yk_mask_apply_f32', 'yk_prune_tile',
                    'yk_kpu_plan_create', 'yk_kpu_run_u8', 'yk_kpu_get_output', 'yk_kpu_output_count', 'yk_kpu_debug_read',
                    'yk_kpu_launch_count', 'yk_kpu_profile', 'yk_range_reset', 'yk_range_f32', 'yk_scale_act_range_f32', 'yk_range_read',
+                   'yk_hist_reset', 'yk_hist_f32', 'yk_scale_act_hist_f32', 'yk_hist_read',
                    'yk_qat_tile', 'yk_qat_weights_f32', 'yk_qat_act_fwd_f32', 'yk_qat_act_bwd_f32', 'yk_qat_update_f32'):
             getattr(L, fn).restype = C.c_int
         L.yk_plan_destroy.restype = None

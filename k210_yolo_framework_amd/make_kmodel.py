@@ -1,12 +1,16 @@
 """`make kmodel` - quantise a trained checkpoint to a K210 kmodel (the reference leaves this step to keras_freeze.py + nncase).
 
     python make_kmodel.py CKPT OUT [network flags of keras_inference.py] (--calib LIST.npy | --synthetic N | --ranges FILE.npz) [--calib_seed S]
+                          [--calib_method minmax|percentile|mse] [--calib_percentile P] [--calib_bins NB]
 
 CKPT: a Keras `.h5` or `.npz` checkpoint; OUT: `.kmodel` or `.kfpkg`.  The calibration images are a list file as make_voc_list.py writes
 (data/<set>_img_ann.npy) or N generated images as `make train SYNTHETIC=N` trains on; they are decoded as the input pipeline decodes them
 (Helper._read_img) and letterboxed on the GPU (yk_letterbox_u8), then measured by quantize.Calibrator.  Prints the per-layer report and
 the file size.  `--ranges FILE` (`make kmodel RANGES=`) quantises with the ranges a `make train QAT=True` run learned
-(`yolo_qat_ranges.npz`: tensor name -> [lo, hi]) instead of calibrating; no image is read and no GPU is needed."""
+(`yolo_qat_ranges.npz`: tensor name -> [lo, hi]) instead of calibrating; no image is read and no GPU is needed.
+`--calib_method` (`make kmodel CALIBMETHOD=`): `minmax`, the default, spreads the 256 codes over each tensor's exact range; `percentile`
+(`--calib_percentile`, default 99.99) and `mse` clip the range from a histogram of `--calib_bins` bins per tensor, taken on the GPU in a second
+pass over the same images (quantize.clip_range).  The report then lists every clipped tensor."""
 from __future__ import annotations
 
 import argparse
@@ -50,7 +54,7 @@ def load_ranges(path, spec):
 
 
 def main(ckpt, out, image_size, output_size, model_def, class_num, depth_multiplier, train_set, calib, synthetic, calib_seed, batch, limit=0,
-         ranges=None):
+         ranges=None, method='minmax', percentile=99.99, bins=2048):
     from pathlib import Path
     from . import quantize
     anchor_file = Path(f'data/{train_set}_anchor.npy')
@@ -71,9 +75,10 @@ def main(ckpt, out, image_size, output_size, model_def, class_num, depth_multipl
         print(INFO, f' ranges of {ranges}, no calibration, {time.time() - t0:.2f} s')
     else:
         frames = calibration_frames(h, calib, synthetic, calib_seed, class_num, limit)
-        report = model.save_kmodel(str(out), frames, batch=batch)
+        report = model.save_kmodel(str(out), frames, batch=batch, method=method, percentile=percentile, bins=bins)
         print(quantize.format_report(report))
-        print(INFO, f' {len(frames)} calibration images, {time.time() - t0:.2f} s')
+        print(INFO, f' {len(frames)} calibration images{"" if method == "minmax" else f", {method} ranges from {bins}-bin histograms"}, '
+                    f'{time.time() - t0:.2f} s')
     print(INFO, f' wrote {out}: kmodel of {report["file_bytes"]} bytes')
     return report
 
@@ -92,15 +97,29 @@ def cli(argv=None):
     p.add_argument('--calib_seed', type=int, default=3, help='seed of the generated images / of the order --calib_limit samples in')
     p.add_argument('--calib_batch', type=int, default=32, help='images per calibration forward pass')
     p.add_argument('--ranges', type=str, default=None, help='quantise with the ranges of a QAT run (yolo_qat_ranges.npz) instead of calibrating')
+    p.add_argument('--calib_method', type=str, default=None, help='minmax (default): exact ranges; percentile | mse: ranges clipped from GPU '
+                                                                  'histograms (a second pass over the images)')
+    p.add_argument('--calib_percentile', type=float, default=99.99, help='share of the values --calib_method percentile keeps at each end, '
+                                                                         'in (50, 100]')
+    p.add_argument('--calib_bins', type=int, default=2048, help='histogram bins per tensor, 16..4096')
     p.add_argument('pre_ckpt', type=str, help='trained weights (.h5 / .npz)')
     p.add_argument('output', type=str, help='.kmodel or .kfpkg to write')
     a = p.parse_args(sys.argv[1:] if argv is None else argv)
     if a.ranges and (a.calib or a.synthetic):
         p.error('--ranges replaces calibration: it cannot be combined with --calib or --synthetic')
+    if a.ranges and a.calib_method is not None:
+        p.error('--ranges replaces calibration: it cannot be combined with --calib_method')
     if not a.calib and not a.synthetic and not a.ranges:
         p.error('give --calib LIST.npy, --synthetic N or --ranges FILE.npz')
+    method = a.calib_method or 'minmax'
+    if method not in ('minmax', 'percentile', 'mse'):
+        p.error(f'--calib_method {method}: one of minmax, percentile, mse')
+    if not 50.0 < a.calib_percentile <= 100.0:
+        p.error(f'--calib_percentile {a.calib_percentile} outside (50, 100]')
+    if not 16 <= a.calib_bins <= 4096:
+        p.error(f'--calib_bins {a.calib_bins} outside 16..4096')
     return main(a.pre_ckpt, a.output, a.image_size, a.output_size, a.model_def, a.class_num, a.depth_multiplier, a.train_set, a.calib,
-                a.synthetic, a.calib_seed, a.calib_batch, a.calib_limit, a.ranges)
+                a.synthetic, a.calib_seed, a.calib_batch, a.calib_limit, a.ranges, method, a.calib_percentile, a.calib_bins)
 
 
 if __name__ == '__main__':

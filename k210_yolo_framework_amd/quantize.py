@@ -1,6 +1,7 @@
 """Quantise a float checkpoint to a K210 kmodel (v3): the step the reference leaves to `keras_freeze.py` + nncase.
 
     ranges = Calibrator(spec, weights, max_batch).feed(frames) ... .ranges()      GPU: the range of every tensor over the calibration set
+    ... .feed_hist(frames) ... .ranges('mse' | 'percentile', percentile)           GPU, optional second pass: histograms -> clipped ranges
     km, report = quantize(spec, weights, ranges)                                   CPU, deterministic: KPU registers and tables
     kmodel.write('yolo.kmodel', km)
 
@@ -310,8 +311,114 @@ def format_report(report: dict) -> str:
                     f"{r['bn_shift'][0]:>4}-{r['bn_shift'][1]:<2}{r['pool']:>5}{100.0 * r['zero_share']:>7.2f}%")
     for r in report['requant']:
         rows.append(f"requantize {r['tensor']}: x{r['factor']:.4f}, zero point {r['zp_in']} -> {r['zp_out']}")
+    for r in report.get('clipped', []):
+        rows.append(f"clipped {r['tensor']} ({r['method']}): ({r['lo']:.6g}, {r['hi']:.6g}) -> ({r['new_lo']:.6g}, {r['new_hi']:.6g}), "
+                    f"{100.0 * r['outside']:.4f}% of the calibration values outside")
     rows.append(f"main memory {report['main_mem_usage']} bytes, KPU RAM peak {report['kpu_ram_peak']} bytes")
     return '\n'.join(rows)
+
+
+# ---- clipped calibration: a range from a histogram (host, float64, deterministic) ---------------------------------------------------------
+CALIB_METHODS = ('minmax', 'percentile', 'mse')
+DEFAULT_BINS = 2048
+MIN_BINS, MAX_BINS = 16, 4096
+
+
+def hist_inv(lo: float, hi: float, bins: int) -> np.float32:
+    """The factor of the bin rule, bin(v) = trunc((v - lo) * inv) clamped to [0, bins - 1] in fp32: bins / (hi - lo) in float64, rounded to
+    fp32 once; 0 for a zero-width range (everything in bin 0); +inf where the quotient exceeds fp32."""
+    width = float(hi) - float(lo)
+    with np.errstate(over='ignore'):
+        return np.float32(bins / width) if width > 0.0 else np.float32(0.0)
+
+
+def _edges(lo: float, hi: float, nb: int) -> np.ndarray:
+    e = lo + np.arange(nb + 1, dtype=np.float64) * ((hi - lo) / nb)
+    e[0], e[nb] = lo, hi                                                       # exactly
+    return e
+
+
+def _check_hist(counts, lo, hi):
+    counts = np.asarray(counts)
+    lo, hi = float(lo), float(hi)
+    if counts.ndim != 1 or not MIN_BINS <= len(counts) <= MAX_BINS or (counts < 0).any():
+        raise KmodelError(f'clip_range: a histogram is {MIN_BINS}..{MAX_BINS} non-negative counts')
+    if not (np.isfinite(lo) and np.isfinite(hi)) or not lo <= 0.0 <= hi:
+        raise KmodelError(f'clip_range: the histogram range ({lo}, {hi}) must be finite and contain 0')
+    return counts.astype(np.float64), lo, hi
+
+
+def _errors(counts: np.ndarray, mid: np.ndarray, a: np.ndarray, d: np.ndarray) -> np.ndarray:
+    """err(a[k], d[k]) for every candidate k: the squared error of the uint8 code of qparams(a, d) over the bin centres, weighted by the
+    counts.  Every row is reduced by the same numpy sum, so equal candidates give equal errors."""
+    keep = counts > 0
+    counts, mid = counts[keep], mid[keep]
+    out = np.empty(len(a), np.float64)
+    sz = [qparams(x, y) for x, y in zip(a, d)]
+    for k0 in range(0, len(a), 256):
+        s = np.array([v[0] for v in sz[k0:k0 + 256]], np.float64)[:, None]
+        zp = np.array([v[1] for v in sz[k0:k0 + 256]], np.float64)[:, None]
+        xq = s * (np.clip(np.rint(mid[None, :] / s) + zp, 0.0, 255.0) - zp)
+        out[k0:k0 + 256] = (counts[None, :] * (mid[None, :] - xq) ** 2).sum(axis=1)
+    return out
+
+
+def clip_error(counts, lo: float, hi: float, a: float, d: float) -> float:
+    """err(a, d) of the `mse` rule of clip_range for the histogram `counts` over [lo, hi]."""
+    counts, lo, hi = _check_hist(counts, lo, hi)
+    nb = len(counts)
+    mid = lo + (np.arange(nb, dtype=np.float64) + 0.5) * ((hi - lo) / nb)
+    return float(_errors(counts, mid, np.array([float(a)]), np.array([float(d)]))[0])
+
+
+def clip_range(counts, lo: float, hi: float, method: str, percentile: float = 99.99) -> Tuple[float, float]:
+    """(lo', hi') inside [lo, hi] for a tensor whose values have the histogram `counts` (NB equal bins of [lo, hi], lo <= 0 <= hi; the bin
+    rule of yk_hist_f32).  Host, float64, deterministic; no GPU.  With w = (hi - lo) / NB the bin edges are e_b = lo + b w (e_0 = lo and
+    e_NB = hi exactly), the centres m_b = lo + (b + 0.5) w, N the total count.
+
+    'minmax'      (lo, hi).
+    'percentile'  k = floor((1 - percentile / 100) N) values may be cut at either end: hi' = e_(j+1) for the smallest j with at most k values
+                  in the bins above j, lo' = e_i for the largest i with at most k values in the bins below i; then lo' = min(lo', 0),
+                  hi' = max(hi', 0).  50 < percentile <= 100; percentile = 100 is (lo, hi).
+    'mse'         err(a, d) = sum_b counts[b] (m_b - x^(m_b))^2 with x^ the uint8 code of qparams(a, d) (the range widened to contain 0).
+                  First d* = argmin over j = 1..NB of err(lo, e_j), the larger d on a tie; then a* = argmin over the i with e_i <= 0 of
+                  err(e_i, d*), the smaller a on a tie.  err(a*, d*) <= err(lo, hi) by construction.  The search models qparams alone: the
+                  upward widening quantize() applies afterwards to a LeakyReLU tensor whose zero point would exceed 127 is not in it.
+
+    Both rules are restated from the general literature (percentile and minimum-squared-error calibrators); they are not pinned against
+    nncase's or TensorRT's calibrators.  A zero-width range and an empty histogram return (lo, hi)."""
+    if method not in CALIB_METHODS:
+        raise KmodelError(f'clip_range: unknown method {method!r} (one of {", ".join(CALIB_METHODS)})')
+    if method == 'minmax':
+        return float(lo), float(hi)
+    counts, lo, hi = _check_hist(counts, lo, hi)
+    nb = len(counts)
+    if method == 'percentile' and not 50.0 < float(percentile) <= 100.0:
+        raise KmodelError(f'clip_range: percentile {percentile} outside (50, 100]')
+    total = counts.sum()
+    if hi == lo or total == 0 or (method == 'percentile' and float(percentile) == 100.0):
+        return lo, hi
+    e = _edges(lo, hi, nb)
+    if method == 'percentile':
+        k = np.floor((1.0 - float(percentile) / 100.0) * total)
+        csum = np.concatenate([[0.0], np.cumsum(counts)])                      # csum[i] = values in the bins below i (exact: integers < 2^53)
+        j = int(np.argmax(total - csum[1:] <= k))                              # values in the bins above j
+        i = int(np.nonzero(csum[:nb] <= k)[0][-1])
+        return min(float(e[i]), 0.0), max(float(e[j + 1]), 0.0)
+    mid = lo + (np.arange(nb, dtype=np.float64) + 0.5) * ((hi - lo) / nb)
+    err = _errors(counts, mid, np.full(nb, lo), e[1:])
+    d = float(e[1:][nb - 1 - int(np.argmin(err[::-1]))])                       # the last of the minima: the larger d
+    cand = e[:nb][e[:nb] <= 0.0]
+    a = float(cand[int(np.argmin(_errors(counts, mid, cand, np.full(len(cand), d))))])    # the first of the minima: the smaller a
+    return a, d
+
+
+def outside_share(counts, lo: float, hi: float, new_lo: float, new_hi: float) -> float:
+    """The share of a histogram's values in bins that lie wholly outside [new_lo, new_hi]."""
+    counts, lo, hi = _check_hist(counts, lo, hi)
+    e = _edges(lo, hi, len(counts))
+    total = counts.sum()
+    return float(counts[(e[1:] <= new_lo) | (e[:-1] >= new_hi)].sum() / total) if total else 0.0
 
 
 # ---- calibration on the GPU -------------------------------------------------------------------------------------------------------------
@@ -326,9 +433,14 @@ class Calibrator:
 
     `feed` normalises the uint8 frames by 255 - what the KPU sees (raw pixels, scale 1/255) - NOT by each image's own maximum as the float
     inference modes do (tools/utils.py:405).  `feed` may be called any number of times; ranges accumulate (min / max are exact and
-    order-free, so the result does not depend on how the set is split into batches)."""
+    order-free, so the result does not depend on how the set is split into batches).
 
-    def __init__(self, spec: ns.NetSpec, weights: Dict[str, np.ndarray], max_batch: int = 32, device: int = 0):
+    The clipped calibrations (`ranges('percentile' | 'mse')`, clip_range) need a second pass over the same frames, `feed_hist`: the same walk
+    with yk_scale_act_hist_f32 / yk_hist_f32 in place of the range launches, which count every tensor into `bins` equal bins of the range
+    the first pass found (widened to contain 0, as qparams widens it).  The first `feed_hist` freezes those ranges; the counts are uint64,
+    integer adds, order-free like the ranges."""
+
+    def __init__(self, spec: ns.NetSpec, weights: Dict[str, np.ndarray], max_batch: int = 32, device: int = 0, bins: int = DEFAULT_BINS):
         import torch
         from . import engine
         engine.require_gpu()
@@ -355,6 +467,10 @@ class Calibrator:
         self.P['input/bias'] = torch.zeros(3, dtype=torch.float32, device=dev)
         self.n_slots = len(spec.tensors)
         self.d_range = torch.zeros(self.n_slots * 4, dtype=torch.int32, device=dev)                      # YK_RANGE_WORDS per slot
+        self.bins = int(bins)
+        if not MIN_BINS <= self.bins <= MAX_BINS:
+            raise engine.YkError(f'Calibrator: bins = {bins} outside {MIN_BINS}..{MAX_BINS}')
+        self.d_hist = self.d_hflags = None                                                               # allocated by the first feed_hist
         self._last_use = {}
         for k, op in enumerate(spec.ops):
             for key in ('in0', 'in1'):
@@ -368,7 +484,9 @@ class Calibrator:
 
     def reset(self) -> None:
         self.engine._check(self.L.yk_range_reset(self.engine._ptr(self.d_range), C.c_int(self.n_slots), self._s()), 'yk_range_reset')
-        self.images = 0
+        self.images = self.hist_images = 0
+        self.h_lo = self.h_hi = self.h_inv = None                                                        # frozen by the first feed_hist
+        self.last_clip: List[dict] = []
 
     def _epilogue(self, z, M, Cn, scale, bias, act, alpha, y, slot):
         p = self.engine._ptr
@@ -379,20 +497,60 @@ class Calibrator:
         self.engine._check(self.L.yk_range_f32(self.engine._ptr(x), C.c_longlong(x.numel()), self.engine._ptr(self.d_range), C.c_int(slot), self._s()),
                            'yk_range_f32')
 
+    def _epilogue_hist(self, z, M, Cn, scale, bias, act, alpha, y, slot):
+        p = self.engine._ptr
+        self.engine._check(self.L.yk_scale_act_hist_f32(p(z), C.c_longlong(M), C.c_int(Cn), p(scale), p(bias), C.c_int(act), C.c_float(alpha), p(y),
+                                                        C.c_float(self.h_lo[slot]), C.c_float(self.h_inv[slot]), C.c_int(self.bins), p(self.d_hist),
+                                                        p(self.d_hflags), C.c_int(slot), self._s()), 'yk_scale_act_hist_f32')
+
+    def _hist(self, x, slot):
+        p = self.engine._ptr
+        self.engine._check(self.L.yk_hist_f32(p(x), C.c_longlong(x.numel()), C.c_float(self.h_lo[slot]), C.c_float(self.h_inv[slot]),
+                                              C.c_int(self.bins), p(self.d_hist), p(self.d_hflags), C.c_int(slot), self._s()), 'yk_hist_f32')
+
     def feed(self, frames_u8, keep=None) -> "Calibrator":
         """frames_u8: device uint8 [B, H, W, 3], B <= max_batch, H x W = the spec's input size.  `keep`: a dict that receives every tensor
         {name: device fp32 NHWC} of this batch (tests)."""
+        if self.h_lo is not None:
+            raise self.engine.YkError('Calibrator.feed: the ranges are frozen by feed_hist; reset() starts a new calibration')
+        self._walk(frames_u8, keep, self._epilogue, self._range, 'feed')
+        self.images += int(frames_u8.shape[0])
+        return self
+
+    def feed_hist(self, frames_u8, keep=None) -> "Calibrator":
+        """The second pass: `frames_u8` (as `feed` takes them - the frames the ranges came from) counted into the histogram of every tensor.
+        The first call freezes the ranges fed so far, widened to contain 0, as the span of the bins.  YkError unless ranges have been fed."""
+        if not self.images:
+            raise self.engine.YkError('Calibrator.feed_hist: feed the ranges first (the bins span them)')
+        if self.h_lo is None:
+            self.ranges()                                                                            # raises on a non-finite tensor
+            lo, hi, _ = self.read()
+            lo, hi = np.minimum(lo, np.float32(0)), np.maximum(hi, np.float32(0))
+            inv = np.array([hist_inv(a, b, self.bins) for a, b in zip(lo, hi)], np.float32)
+            if self.d_hist is None:
+                self.d_hist = self.torch.zeros(self.n_slots * self.bins, dtype=self.torch.int64, device=self.dev)
+                self.d_hflags = self.torch.zeros(self.n_slots, dtype=self.torch.int32, device=self.dev)
+            self.engine._check(self.L.yk_hist_reset(self.engine._ptr(self.d_hist), C.c_int(self.n_slots), C.c_int(self.bins), self._s()),
+                               'yk_hist_reset')
+            self.d_hflags.zero_()
+            self.h_lo, self.h_hi, self.h_inv = lo, hi, inv
+        self._walk(frames_u8, keep, self._epilogue_hist, self._hist, 'feed_hist')
+        self.hist_images += int(frames_u8.shape[0])
+        return self
+
+    def _walk(self, frames_u8, keep, epilogue, plain, who) -> None:
+        """One fp32 forward pass of the spec; `epilogue` finishes a conv (and the input) and measures it, `plain` measures a moved tensor."""
         torch, eng, L, p = self.torch, self.engine, self.L, self.engine._ptr
         H, W = self.spec.in_hw
         if not (frames_u8.is_cuda and frames_u8.dtype == torch.uint8 and frames_u8.dim() == 4 and tuple(frames_u8.shape[1:]) == (H, W, 3)):
-            raise eng.YkError(f'Calibrator.feed takes device uint8 frames [B, {H}, {W}, 3]')
+            raise eng.YkError(f'Calibrator.{who} takes device uint8 frames [B, {H}, {W}, 3]')
         B = int(frames_u8.shape[0])
         if not 1 <= B <= self.max_batch:
-            raise eng.YkError(f'Calibrator.feed: {B} frames, max_batch is {self.max_batch}')
+            raise eng.YkError(f'Calibrator.{who}: {B} frames, max_batch is {self.max_batch}')
         new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=self.dev)            # noqa: E731
         raw = frames_u8.contiguous().to(torch.float32)                                           # 0..255, exact
         x = new(B, H, W, 3)
-        self._epilogue(raw, B * H * W, 3, self.P['input/scale'], self.P['input/bias'], ns.ACT_NONE, 0.0, x, 0)
+        epilogue(raw, B * H * W, 3, self.P['input/scale'], self.P['input/bias'], ns.ACT_NONE, 0.0, x, 0)
         T = {0: x}
         for i, op in enumerate(self.spec.ops):
             x, t = T[op['in0']], op['type']
@@ -419,13 +577,13 @@ class Calibrator:
                                              p(w), C.c_int(9 * ci), C.c_float(0.0), p(z), C.c_int(co), self._s()), 'yk_gemm_f32')
                     del col
                 y = new(B, ho, wo, co)
-                self._epilogue(z, M, co, self.P[name + '/scale'], self.P[name + '/bias'], op['act'], float(op['alpha']), y, op['out'])
+                epilogue(z, M, co, self.P[name + '/scale'], self.P[name + '/bias'], op['act'], float(op['alpha']), y, op['out'])
             else:
                 if t == ns.OP_UPSAMPLE:                                                          # nearest x2: pure data movement
                     y = x.repeat_interleave(2, dim=1).repeat_interleave(2, dim=2).contiguous()
                 else:
                     y = torch.cat([x, T[op['in1']]], dim=3)
-                self._range(y, op['out'])
+                plain(y, op['out'])
             T[op['out']] = y
             if keep is None:
                 for key in ('in0', 'in1'):
@@ -434,8 +592,6 @@ class Calibrator:
                         T.pop(tid, None)
         if keep is not None:
             keep.update({self.names[tid]: v for tid, v in T.items()})
-        self.images += B
-        return self
 
     def read(self):
         """(min, max, flags) as numpy arrays over the spec's tensors: one device-to-host copy."""
@@ -447,16 +603,59 @@ class Calibrator:
                                                 hi.ctypes.data_as(C.c_void_p), fl.ctypes.data_as(C.c_void_p)), 'yk_range_read')
         return lo, hi, fl
 
-    def ranges(self) -> Dict[str, Tuple[float, float]]:
-        """{tensor name: (min, max)} over everything fed so far.  YkError naming the layer when a tensor held a NaN or an infinity."""
-        if not self.images:
-            raise self.engine.YkError('Calibrator.ranges: nothing has been fed')
-        lo, hi, fl = self.read()
-        bad = [self.names[i] for i in range(self.n_slots) if fl[i]]
+    def _raise_non_finite(self, flags) -> None:
+        bad = [self.names[i] for i in range(self.n_slots) if flags[i]]
         if bad:
             raise self.engine.YkError(f'Calibrator: non-finite values (NaN or infinity) in tensor(s) {", ".join(bad)}: the weights or the frames '
                                       f'are broken; no range is defined')
-        return {self.names[i]: (float(lo[i]), float(hi[i])) for i in range(self.n_slots)}
+
+    def histograms(self):
+        """(counts uint64 [n_slots, bins], lo, hi): the histogram of every tensor over everything fed to feed_hist, and the float32 ends of
+        its bins per slot (the tensor's range widened to contain 0).  One device-to-host copy of the counts.  YkError naming the layer when
+        a tensor held a NaN or an infinity."""
+        if not self.hist_images:
+            raise self.engine.YkError('Calibrator.histograms: nothing has been fed to feed_hist')
+        counts = np.empty((self.n_slots, self.bins), np.uint64)
+        fl = np.empty(self.n_slots, np.int32)
+        self.torch.cuda.current_stream().synchronize()
+        self.engine._check(self.L.yk_hist_read(self.engine._ptr(self.d_hist), self.engine._ptr(self.d_hflags), C.c_int(self.n_slots),
+                                               C.c_int(self.bins), counts.ctypes.data_as(C.c_void_p), fl.ctypes.data_as(C.c_void_p)), 'yk_hist_read')
+        self._raise_non_finite(fl)
+        return counts, self.h_lo.copy(), self.h_hi.copy()
+
+    def ranges(self, method: str = 'minmax', percentile: float = 99.99) -> Dict[str, Tuple[float, float]]:
+        """{tensor name: (min, max)} over everything fed so far.  YkError naming the layer when a tensor held a NaN or an infinity.
+        method 'percentile' / 'mse': every tensor but the input (always the raw pixel) clipped by clip_range from its histogram, which
+        feed_hist must have been given the same frames; an end the rule leaves where it was keeps its measured value.  `last_clip` then
+        lists every conv output the rule moved (format_report prints it)."""
+        if not self.images:
+            raise self.engine.YkError('Calibrator.ranges: nothing has been fed')
+        if method not in CALIB_METHODS:
+            raise self.engine.YkError(f'Calibrator.ranges: unknown method {method!r} (one of {", ".join(CALIB_METHODS)})')
+        lo, hi, fl = self.read()
+        self._raise_non_finite(fl)
+        out = {self.names[i]: (float(lo[i]), float(hi[i])) for i in range(self.n_slots)}
+        self.last_clip = []
+        if method == 'minmax':
+            return out
+        if self.hist_images != self.images:
+            raise self.engine.YkError(f'Calibrator.ranges({method!r}): feed_hist has seen {self.hist_images} of the {self.images} frames the '
+                                      f'ranges came from')
+        counts, blo, bhi = self.histograms()
+        for i in range(1, self.n_slots):
+            try:
+                a, d = clip_range(counts[i], blo[i], bhi[i], method, percentile)
+            except KmodelError as e:
+                raise self.engine.YkError(f'Calibrator.ranges: {e}') from e
+            if (a, d) == (float(blo[i]), float(bhi[i])):
+                continue
+            name = self.names[i]
+            new = (out[name][0] if a == float(blo[i]) else a, out[name][1] if d == float(bhi[i]) else d)
+            if name in self.lay:
+                self.last_clip.append(dict(tensor=name, method=method, lo=out[name][0], hi=out[name][1], new_lo=new[0], new_hi=new[1],
+                                           outside=outside_share(counts[i], blo[i], bhi[i], a, d)))
+            out[name] = new
+        return out
 
 
 def synthetic_frames(n: int, in_hw, seed: int) -> np.ndarray:
@@ -486,10 +685,36 @@ def synthetic_frames(n: int, in_hw, seed: int) -> np.ndarray:
     return out
 
 
-def calibrate(spec: ns.NetSpec, weights, frames_u8: np.ndarray, batch: int = 32) -> Dict[str, Tuple[float, float]]:
-    """Ranges of `frames_u8` (host uint8 [N, H, W, 3]) in batches of `batch`."""
+def check_method(method: str, percentile: float, bins: int) -> None:
+    """KmodelError for a calibration method, percentile or bin count the quantiser does not take."""
+    if method not in CALIB_METHODS:
+        raise KmodelError(f'unknown calibration method {method!r} (one of {", ".join(CALIB_METHODS)})')
+    if not 50.0 < float(percentile) <= 100.0:
+        raise KmodelError(f'calibration percentile {percentile} outside (50, 100]')
+    if not MIN_BINS <= int(bins) <= MAX_BINS:
+        raise KmodelError(f'calibration bins {bins} outside {MIN_BINS}..{MAX_BINS}')
+
+
+def calibrate(spec: ns.NetSpec, weights, frames_u8, batch: int = 32, method: str = 'minmax', percentile: float = 99.99,
+              bins: int = DEFAULT_BINS, clipped: Optional[List[dict]] = None) -> Dict[str, Tuple[float, float]]:
+    """Ranges of `frames_u8` (uint8 [N, H, W, 3], host numpy or a device tensor) in batches of `batch`.  A method other than 'minmax' walks
+    the frames a second time for the histograms (`bins` bins per tensor) and clips every range by clip_range; `clipped`, a list, receives
+    Calibrator.last_clip.  The input tensor's range is the raw pixel's whatever the method."""
     import torch
-    cal = Calibrator(spec, weights, max_batch=batch)
-    for i in range(0, len(frames_u8), batch):
-        cal.feed(torch.from_numpy(np.ascontiguousarray(frames_u8[i:i + batch])).cuda())
-    return cal.ranges()
+    from . import engine
+    try:
+        check_method(method, percentile, bins)
+    except KmodelError as e:
+        raise engine.YkError(f'calibrate: {e}') from e
+    frames = frames_u8 if torch.is_tensor(frames_u8) else torch.from_numpy(np.ascontiguousarray(frames_u8))
+    batch = max(1, min(int(batch), len(frames)))
+    cal = Calibrator(spec, weights, max_batch=batch, bins=bins)
+    for i in range(0, len(frames), batch):
+        cal.feed(frames[i:i + batch].cuda())
+    if method != 'minmax':
+        for i in range(0, len(frames), batch):
+            cal.feed_hist(frames[i:i + batch].cuda())
+    out = cal.ranges(method, percentile)
+    if clipped is not None:
+        clipped.extend(cal.last_clip)
+    return out

@@ -115,12 +115,14 @@ class YoloModel:
         else:
             np.savez(path, **self._s['weights'])
 
-    def save_kmodel(self, path: str, calibration_frames, batch: int = 32):
+    def save_kmodel(self, path: str, calibration_frames, batch: int = 32, method: str = 'minmax', percentile: float = 99.99, bins: int = 2048):
         """Quantise these weights to a K210 kmodel (quantize.py) and write it: `.kmodel`, or `.kfpkg` (model + flash list, no
         firmware).  calibration_frames: uint8 [N, H, W, 3] at the network's input size (host numpy or a device tensor); their tensor ranges
         are measured on the GPU in batches of `batch`, from the raw pixels / 255 as the KPU sees them.  The new Kmodel is kept beside the
         float weights, so precision='kpu' runs it on this object without reloading.  Returns the quantiser's report (also
-        `last_quantize_report`).  A network the KPU path cannot express raises YkError with the quantiser's reason."""
+        `last_quantize_report`).  A network the KPU path cannot express raises YkError with the quantiser's reason.
+        method 'percentile' / 'mse' (quantize.clip_range) clips every range from a histogram of `bins` bins, taken on the GPU in a second
+        pass over the frames; report['clipped'] lists the tensors it moved.  The default, 'minmax', is the exact range and one pass."""
         import torch
         from . import engine, kmodel, quantize
         try:
@@ -130,11 +132,12 @@ class YoloModel:
         frames = calibration_frames if torch.is_tensor(calibration_frames) else torch.from_numpy(np.ascontiguousarray(calibration_frames))
         if frames.dtype != torch.uint8 or frames.dim() != 4 or len(frames) == 0:
             raise engine.YkError('save_kmodel: calibration_frames must be uint8 [N, H, W, 3], N >= 1')
-        cal = quantize.Calibrator(self.spec, self._s['weights'], max_batch=max(1, min(int(batch), len(frames))))
-        for i in range(0, len(frames), cal.max_batch):
-            cal.feed(frames[i:i + cal.max_batch].cuda())
+        clipped = []
+        ranges = quantize.calibrate(self.spec, self._s['weights'], frames, batch, method, percentile, bins, clipped)
         try:
-            km, report = quantize.quantize(self.spec, self._s['weights'], cal.ranges())
+            km, report = quantize.quantize(self.spec, self._s['weights'], ranges)
+            if method != 'minmax':
+                report['clipped'] = clipped
             report['file_bytes'] = kmodel.write(path, km)
         except kmodel.KmodelError as e:
             raise engine.YkError(f'save_kmodel: {e}') from e
