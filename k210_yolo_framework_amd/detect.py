@@ -17,7 +17,6 @@ class], ...]}, ...]) and prints the reference's table per picture.  `--precision
 from __future__ import annotations
 
 import argparse
-import ctypes as C
 import io
 import json
 import sys
@@ -205,8 +204,7 @@ def run(h: Helper, model, sources, out_dir=None, draw: bool = True, batch: int =
         """Pinned <-> device on a slot's stream through the library, as Pipeline copies: torch's pinned-memory allocator must never learn of
         the pipeline's own streams - it records an event on every stream a pinned block was copied on when the block is FREED, and by then
         Pipeline.close() has destroyed them."""
-        engine._check(engine.lib().yk_memcpy_async(C.c_void_p(dst.data_ptr()), C.c_void_p(src.data_ptr()), C.c_size_t(int(nbytes)),
-                                                   C.c_void_p(stream.cuda_stream)), 'yk_memcpy_async')
+        engine.call('yk_memcpy_async', dst, src, int(nbytes), stream.cuda_stream)
 
     def start_load(k):
         loading.append([pool.submit(load, s) for s in sources[starts[k]:starts[k] + B]])

@@ -3,20 +3,27 @@
 There is no CPU fallback: if the library is missing, or no HIP device is visible, every entry point
 raises.  PyTorch-ROCm is used for plumbing only (device buffers, streams, torch.distributed); it is
 imported before the library so that both share one HIP runtime instance (libamdhip64.so.7).
+
+The header is the one statement of the ABI: lib() reads its prototypes (abi.signatures) and sets argtypes / restype on every declared function.
+Calls go through `call(name, *args)` with plain Python ints and floats, tensors and numpy arrays (abi.DevPtr takes their address and refuses a
+non-contiguous one) and byref(...) for out-parameters; a value of the wrong kind or width raises ctypes.ArgumentError before the call.
 """
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import os
 from pathlib import Path
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from . import abi
 from . import netspec as ns
 
 # YK_LIB_PATH: the developer build of the same library (`make -C csrc dev`: tuning switches compiled in), for tools/ only
 LIB_PATH = Path(os.environ.get('YK_LIB_PATH') or Path(__file__).resolve().parent / 'csrc' / 'libyolo_hip.so')
+HEADER_PATH = Path(__file__).resolve().parents[1] / 'include' / 'yolo_hip.h'
 YK_MAX_LAYERS, YK_MAX_ANCHORS = 4, 8
 PRECISIONS = {'f16': 0, 'f16x2': 1}          # YK_PRECISION_F16 / YK_PRECISION_F16X2
 SCHEDULES = {'throughput': 0x000, 'latency': 0x100}      # YK_SCHEDULE_* (include/yolo_hip.h): per-layer launches | per-image cluster launches
@@ -65,28 +72,15 @@ def lib() -> C.CDLL:
         if not LIB_PATH.exists():
             raise YkError(f'{LIB_PATH} not built: run `python -c "import __graft_entry__ as g; g.build()"` '
                           f'(hipcc --offload-arch=gfx950).  There is no CPU fallback.')
+        if not HEADER_PATH.exists():
+            raise YkError(f'{HEADER_PATH} is missing: the ctypes signatures of {LIB_PATH.name} are read from it')
         import torch  # noqa: F401  (binds libamdhip64.so.7 first)
         L = C.CDLL(str(LIB_PATH))
-        L.yk_last_error.restype = C.c_char_p
-        L.yk_device_count.restype = C.c_int
-        for fn in ('yk_plan_create', 'yk_plan_create_ex', 'yk_run_u8', 'yk_run_f32', 'yk_get_output', 'yk_debug_read_tensor', 'yk_debug_read_exponents',
-                   'yk_plan_launch_count', 'yk_plan_launch_info', 'yk_plan_check', 'yk_plan_peek_error', 'yk_plan_debug_set_error', 'yk_plan_profile', 'yk_decode_py', 'yk_decode_py_ex', 'yk_decode_py_packed',
-                   'yk_graph_begin', 'yk_graph_end', 'yk_graph_launch', 'yk_graph_node_count', 'yk_graph_kernel_node_count', 'yk_memcpy_async', 'yk_host_device_ptr', 'yk_stream_create', 'yk_stream_destroy', 'yk_stream_query_priority', 'yk_normalise_u8', 'yk_region_batched', 'yk_yolo_loss', 'yk_letterbox_u8', 'yk_letterbox_augment_u8',
-                   'yk_letterbox_ragged_params', 'yk_letterbox_ragged_u8', 'yk_draw_dets_u8',
-                   'yk_jpeg_tables', 'yk_jpeg_workspace_bytes', 'yk_jpeg_encode_ragged_u8', 'yk_jpeg_decode_workspace_bytes', 'yk_jpeg_decode_ragged_u8',
-                   'region_layer_init', 'yk_gemm_f32', 'yk_gemm_f32_grouped', 'yk_im2col3x3_f32', 'yk_col2im3x3_f32', 'yk_conv3x3_bn_fwd_f32', 'yk_conv3x3_bwd_weight_f32', 'yk_conv3x3_bwd_data_f32', 'yk_dw3x3_fwd_f32',
-                   'yk_dw3x3_bwd_data_f32', 'yk_dw3x3_bwd_weight_f32', 'yk_dw3x3_bwd_weight_grouped_f32', 'yk_bn_train_fwd_f32', 'yk_bn_train_fwd_res_f32', 'yk_gemm_bn_fwd_f32', 'yk_dw3x3_bn_fwd_f32', 'yk_l2_segments_f32', 'yk_bn_train_bwd_f32',
-                   'yk_bias_add_f32', 'yk_colsum_f32', 'yk_upsample2x_bwd_f32', 'yk_maxpool2_fwd_f32',
-                   'yk_maxpool2_bwd_f32', 'yk_axpy_f32', 'yk_adam_f32', 'yk_prune_masks_f32', 'yk_mask_apply_f32', 'yk_prune_tile',
-                   'yk_kpu_plan_create', 'yk_kpu_run_u8', 'yk_kpu_get_output', 'yk_kpu_output_count', 'yk_kpu_debug_read',
-                   'yk_kpu_launch_count', 'yk_kpu_profile', 'yk_range_reset', 'yk_range_f32', 'yk_scale_act_range_f32', 'yk_range_read',
-                   'yk_hist_reset', 'yk_hist_f32', 'yk_scale_act_hist_f32', 'yk_hist_read',
-                   'yk_qat_tile', 'yk_qat_weights_f32', 'yk_qat_act_fwd_f32', 'yk_qat_act_bwd_f32', 'yk_qat_update_f32'):
-            getattr(L, fn).restype = C.c_int
-        L.yk_plan_destroy.restype = None
-        L.yk_kpu_plan_destroy.restype = None
-        L.yk_graph_destroy.restype = None
-        L.yk_scratch_generation.restype = C.c_ulonglong
+        for name, (restype, argtypes) in abi.signatures(HEADER_PATH.read_text()).items():
+            fn = getattr(L, name, None)        # (a function the library exports but the header does not declare keeps ctypes' defaults)
+            if fn is None:
+                raise YkError(f'{LIB_PATH} does not export {name}, which {HEADER_PATH.name} declares: the library is stale, build it again')
+            fn.restype, fn.argtypes = restype, argtypes
         _lib = L
     return _lib
 
@@ -94,6 +88,21 @@ def lib() -> C.CDLL:
 def _check(rc: int, what: str) -> None:
     if rc != 0:
         raise YkError(f'{what} failed ({rc}): {lib().yk_last_error().decode()}')
+
+
+def call(name: str, *args) -> None:
+    """Call the library function `name` (an int-returning one) and raise YkError if it fails.  Arguments are converted by the signature
+    lib() read from the header: plain ints and floats, tensors and numpy arrays (abi.DevPtr), byref(...) for out-parameters."""
+    _check(getattr(lib(), name)(*args), name)
+
+
+@functools.lru_cache(maxsize=None)
+def _handles_only(name: str):
+    """A second binding of `name` whose pointer parameters are plain c_void_p, converted in C: for the calls of a replayed step, the
+    timed path, which pass prebuilt c_void_p handles (and byref) and nothing abi.DevPtr (a from_param written in Python) would have to look at."""
+    decl, fn = getattr(lib(), name), lib()[name]
+    fn.restype, fn.argtypes = decl.restype, [C.c_void_p if a is abi.DevPtr else a for a in decl.argtypes]
+    return fn
 
 
 def require_gpu() -> None:
@@ -125,8 +134,52 @@ class _DevView:
         self._owner = weakref.ref(owner)
 
 
-class Plan:
+class _PlanBase:
+    """What Plan and KpuPlan share: the handle's life and the borrowed views of the outputs.  A subclass names its destroy and get-output
+    functions and sets _h, _n_outputs, max_batch and device."""
+    _destroy = _get_output = None
+
+    def close(self):
+        self._out_views = None
+        if getattr(self, '_h', None) and self._h.value:
+            getattr(lib(), self._destroy)(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def output_ptrs(self) -> List[Tuple[int, Tuple[int, int, int]]]:
+        res = []
+        for i in range(self._n_outputs):
+            p = f32p()
+            nb = C.c_size_t()
+            h, w, c = C.c_int(), C.c_int(), C.c_int()
+            call(self._get_output, self._h, i, C.byref(p), C.byref(nb), C.byref(h), C.byref(w), C.byref(c))
+            res.append((C.cast(p, C.c_void_p).value, (h.value, w.value, c.value)))
+        return res
+
+    def outputs(self):
+        """Borrowed torch views [max_batch,h,w,c] fp32 of the network outputs (kpu_get_output; Plan: c = A*(5+C))."""
+        import torch
+        if self._out_views is None:
+            self._out_views = [torch.as_tensor(_DevView(p, (self.max_batch, *s), '<f4', self), device=f'cuda:{self.device}')
+                               for p, s in self.output_ptrs()]
+        return self._out_views
+
+
+class Plan(_PlanBase):
     """kpu_load_kmodel analogue (main.c:274): a compiled, device-resident network."""
+    _destroy, _get_output = 'yk_plan_destroy', 'yk_get_output'
 
     def __init__(self, spec: ns.NetSpec, weights, max_batch: int = 32, device: Optional[int] = None, precision: str = 'f16x2',
                  schedule: str = 'latency'):
@@ -152,98 +205,54 @@ class Plan:
         self._tens = np.ascontiguousarray(tens, np.int32)
         blob = np.ascontiguousarray(blob, np.float32)
         outs = np.ascontiguousarray(spec.outputs, np.int32)
-        self._h = C.c_void_p()
-        L = lib()
-        _check(L.yk_plan_create_ex(C.byref(self._h), self._ops.ctypes.data_as(i32p), C.c_int(len(ops)),
-                                   self._tens.ctypes.data_as(i32p), C.c_int(len(tens)), blob.ctypes.data_as(f32p),
-                                   C.c_size_t(blob.size), outs.ctypes.data_as(i32p), C.c_int(len(outs)),
-                                   C.c_int(self.max_batch), C.c_int(self.device), C.c_int(PRECISIONS[precision] | SCHEDULES[schedule])), 'yk_plan_create_ex')
-        self._out_views = None
-
-    def close(self):
-        self._out_views = None
-        if getattr(self, '_h', None) and self._h.value:
-            lib().yk_plan_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._h, self._n_outputs, self._out_views = C.c_void_p(), len(outs), None
+        call('yk_plan_create_ex', C.byref(self._h), self._ops, len(ops), self._tens, len(tens), blob, blob.size, outs, len(outs),
+             self.max_batch, self.device, PRECISIONS[precision] | SCHEDULES[schedule])
 
     # -- run ---------------------------------------------------------------
     def run_u8(self, frames, stream=None) -> None:
         """frames: torch.uint8 cuda tensor [B,H,W,3] (kpu_run_kmodel analogue, async)."""
         assert frames.is_cuda and frames.dtype.__str__() == 'torch.uint8' and frames.is_contiguous()
         assert tuple(frames.shape[1:]) == (*self.spec.in_hw, 3), frames.shape
-        _check(lib().yk_run_u8(self._h, _ptr(frames), C.c_int(frames.shape[0]), _stream(stream)), 'yk_run_u8')
+        call('yk_run_u8', self._h, frames, frames.shape[0], _stream(stream))
 
     def run_f32(self, x, stream=None) -> None:
         assert x.is_cuda and x.dtype.__str__() == 'torch.float32' and x.is_contiguous()
         assert tuple(x.shape[1:]) == (*self.spec.in_hw, 3), x.shape
-        _check(lib().yk_run_f32(self._h, _ptr(x), C.c_int(x.shape[0]), _stream(stream)), 'yk_run_f32')
+        call('yk_run_f32', self._h, x, x.shape[0], _stream(stream))
 
     def check(self) -> None:
         """Wait for the device; raise if an earlier asynchronous run of this plan failed on the device (yk_plan_check)."""
-        _check(lib().yk_plan_check(self._h), 'yk_plan_check')
+        call('yk_plan_check', self._h)
 
     def raise_if_failed(self) -> None:
         """Raise if a run of this plan that has ALREADY finished failed on the device (yk_plan_peek_error: a read of mapped host memory,
         no synchronisation - call it after waiting for the run's stream or event).  The flag is cleared by the report."""
         e = C.c_uint()
-        _check(lib().yk_plan_peek_error(self._h, C.c_int(1), C.byref(e)), 'yk_plan_peek_error')
+        _check(_handles_only('yk_plan_peek_error')(self._h, 1, C.byref(e)), 'yk_plan_peek_error')      # (Ticket.result: once per timed step)
         if e.value:
             raise YkError('f16x2 cluster launch: a workgroup cluster did not assemble (its workgroups were not co-resident, e.g. another '
                           'kernel held CUs for the whole launch); the results of that run are invalid.  Use schedule=\'throughput\' when the '
                           'GPU is shared.')
 
-    def output_ptrs(self) -> List[Tuple[int, Tuple[int, int, int]]]:
-        res = []
-        for i in range(len(self.spec.outputs)):
-            p = f32p()
-            nb = C.c_size_t()
-            h, w, c = C.c_int(), C.c_int(), C.c_int()
-            _check(lib().yk_get_output(self._h, C.c_int(i), C.byref(p), C.byref(nb), C.byref(h), C.byref(w), C.byref(c)),
-                   'yk_get_output')
-            res.append((C.cast(p, C.c_void_p).value, (h.value, w.value, c.value)))
-        return res
-
-    def outputs(self):
-        """Borrowed torch views [max_batch,h,w,A*(5+C)] fp32 of the network outputs (kpu_get_output)."""
-        import torch
-        if self._out_views is None:
-            self._out_views = [torch.as_tensor(_DevView(p, (self.max_batch, *s), '<f4', self), device=f'cuda:{self.device}')
-                               for p, s in self.output_ptrs()]
-        return self._out_views
-
     def read_tensor(self, tid: int, batch: int) -> np.ndarray:
         h, w, c = self.spec.tensors[tid]
         out = np.empty((batch, h, w, c), np.float32)
-        _check(lib().yk_debug_read_tensor(self._h, C.c_int(tid), C.c_int(batch), out.ctypes.data_as(f32p),
-                                          C.c_size_t(out.size)), 'yk_debug_read_tensor')
+        call('yk_debug_read_tensor', self._h, tid, batch, out, out.size)
         return out
 
     def read_exponents(self, tid: int, batch: int) -> np.ndarray:
         """int32 [batch]: the per-image storage exponents of an f16x2 plan's stored tensor `tid` (the halves hold x * 2^-e = hi + lo; fp32
         planes: 0).  Raises for an f16 plan and for a tensor that is not stored split (yk_debug_read_exponents)."""
         e = np.empty((batch,), np.int32)
-        _check(lib().yk_debug_read_exponents(self._h, C.c_int(tid), C.c_int(batch), e.ctypes.data_as(i32p)), 'yk_debug_read_exponents')
+        call('yk_debug_read_exponents', self._h, tid, batch, e)
         return e
 
     def profile(self, frames, iters: int = 10, stream=None) -> np.ndarray:
         """Average per-launch duration (ms) measured with HIP events on the launch stream."""
         n = lib().yk_plan_launch_count(self._h)
         ms = np.zeros(n, np.float32)
-        _check(lib().yk_plan_profile(self._h, _ptr(frames), C.c_int(frames.shape[0]), C.c_int(iters), _stream(stream),
-                                     ms.ctypes.data_as(f32p)), 'yk_plan_profile')
+        call('yk_plan_profile', self._h, frames, frames.shape[0], iters, _stream(stream), ms)
         return ms
 
     def launches(self):
@@ -252,7 +261,7 @@ class Plan:
         for i in range(n):
             name = C.create_string_buffer(128)
             fl, by = C.c_double(), C.c_double()
-            lib().yk_plan_launch_info(self._h, C.c_int(i), name, C.c_size_t(128), C.byref(fl), C.byref(by))
+            lib().yk_plan_launch_info(self._h, i, name, 128, C.byref(fl), C.byref(by))
             res.append((name.value.decode(), fl.value, by.value))
         return res
 
@@ -260,10 +269,11 @@ class Plan:
 KPU_LAYOUTS = {'nhwc': 0, 'chw': 1}          # YK_KPU_NHWC / YK_KPU_CHW
 
 
-class KpuPlan:
+class KpuPlan(_PlanBase):
     """The K210 KPU's integer pipeline for a parsed kmodel v3 on the GPU (yk_kpu_*, include/yolo_hip.h): outputs
     bit-identical to oracle/kpu_ref.run for every image.  The KPU takes the raw 0..255 pixels (no `img / np.max(img)`).  Duck-types Plan
     where inference.detect and yolonet use it: `max_batch`, `run_u8`, `outputs`."""
+    _destroy, _get_output = 'yk_kpu_plan_destroy', 'yk_kpu_get_output'
 
     def __init__(self, km, max_batch: int = 32, device: Optional[int] = None):
         """km: a parsed kmodel.Kmodel (packed here) or a kmodel.KpuProgram that kmodel.pack_kpu already made."""
@@ -280,31 +290,9 @@ class KpuPlan:
         self._vals = np.ascontiguousarray(prog.values, np.int32)
         self._outs = np.ascontiguousarray(prog.outputs, np.int32)
         self._blob = np.ascontiguousarray(prog.blob, np.uint8)
-        self._h = C.c_void_p()
-        _check(lib().yk_kpu_plan_create(C.byref(self._h), self._ops.ctypes.data_as(C.POINTER(C.c_int64)), C.c_int(len(self._ops)),
-                                        self._vals.ctypes.data_as(i32p), C.c_int(len(self._vals)), self._outs.ctypes.data_as(i32p),
-                                        C.c_int(len(self._outs)), self._blob.ctypes.data_as(C.c_void_p), C.c_size_t(self._blob.size),
-                                        C.c_int(self.max_batch), C.c_int(self.device)), 'yk_kpu_plan_create')
-        self._out_views = None
-
-    def close(self):
-        self._out_views = None
-        if getattr(self, '_h', None) and self._h.value:
-            lib().yk_kpu_plan_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._h, self._n_outputs, self._out_views = C.c_void_p(), len(self._outs), None
+        call('yk_kpu_plan_create', C.byref(self._h), self._ops, len(self._ops), self._vals, len(self._vals), self._outs, len(self._outs),
+             self._blob, self._blob.size, self.max_batch, self.device)
 
     def _frame_shape(self, layout: str):
         c, h, w = self.input_chw
@@ -320,27 +308,7 @@ class KpuPlan:
             raise YkError('KpuPlan.run_u8: frames must be a contiguous cuda uint8 tensor')
         if tuple(frames.shape[1:]) != self._frame_shape(layout) or not 0 < frames.shape[0] <= self.max_batch:
             raise YkError(f'KpuPlan.run_u8: frames {tuple(frames.shape)}, expected [<= {self.max_batch}, {", ".join(map(str, self._frame_shape(layout)))}]')
-        _check(lib().yk_kpu_run_u8(self._h, _ptr(frames), C.c_int(frames.shape[0]), C.c_int(KPU_LAYOUTS[layout]), _stream(stream)),
-               'yk_kpu_run_u8')
-
-    def output_ptrs(self) -> List[Tuple[int, Tuple[int, int, int]]]:
-        res = []
-        for i in range(len(self._outs)):
-            p = f32p()
-            nb = C.c_size_t()
-            h, w, c = C.c_int(), C.c_int(), C.c_int()
-            _check(lib().yk_kpu_get_output(self._h, C.c_int(i), C.byref(p), C.byref(nb), C.byref(h), C.byref(w), C.byref(c)),
-                   'yk_kpu_get_output')
-            res.append((C.cast(p, C.c_void_p).value, (h.value, w.value, c.value)))
-        return res
-
-    def outputs(self):
-        """Borrowed torch views [max_batch,h,w,c] fp32 of the network outputs (kpu_get_output; the layout of Plan.outputs)."""
-        import torch
-        if self._out_views is None:
-            self._out_views = [torch.as_tensor(_DevView(p, (self.max_batch, *s), '<f4', self), device=f'cuda:{self.device}')
-                               for p, s in self.output_ptrs()]
-        return self._out_views
+        call('yk_kpu_run_u8', self._h, frames, frames.shape[0], KPU_LAYOUTS[layout], _stream(stream))
 
     def read_layer(self, index: int, image: int) -> np.ndarray:
         """uint8 [C][H][W] output of the conv at kmodel layer `index` for image `image` of the last run (waits for the device)."""
@@ -349,16 +317,14 @@ class KpuPlan:
             raise YkError(f'layer {index} is not a KPU conv layer of this kmodel')
         c, h, w = (int(x) for x in self.program.values[v, :3])
         out = np.empty((c, h, w), np.uint8)
-        _check(lib().yk_kpu_debug_read(self._h, C.c_int(int(index)), C.c_int(int(image)), out.ctypes.data_as(C.POINTER(C.c_uint8)),
-                                       C.c_size_t(out.size)), 'yk_kpu_debug_read')
+        call('yk_kpu_debug_read', self._h, int(index), int(image), out, out.size)
         return out
 
     def profile(self, frames, layout: str = 'nhwc', iters: int = 10, stream=None) -> np.ndarray:
         """Median duration (ms) of every launch of one run, HIP events around each (yk_kpu_profile)."""
         n = lib().yk_kpu_launch_count(self._h)
         ms = np.zeros(n, np.float32)
-        _check(lib().yk_kpu_profile(self._h, _ptr(frames), C.c_int(frames.shape[0]), C.c_int(KPU_LAYOUTS[layout]), C.c_int(iters),
-                                    _stream(stream), ms.ctypes.data_as(f32p)), 'yk_kpu_profile')
+        call('yk_kpu_profile', self._h, frames, frames.shape[0], KPU_LAYOUTS[layout], iters, _stream(stream), ms)
         return ms
 
     def launches(self) -> List[str]:
@@ -398,19 +364,15 @@ def decode_py(cfg: DecodeCfg, preds: Sequence, batch: int, image_hw=None, obj_th
     dev = preds[0].device
     dets = torch.empty((batch, cfg.class_num * max_out, 6), dtype=torch.float32, device=dev)
     counts = torch.empty((batch,), dtype=torch.int32, device=dev)
-    arr = (C.c_void_p * len(preds))(*[C.c_void_p(p.data_ptr()) for p in preds])
+    arr = (C.c_void_p * len(preds))(*[p.data_ptr() for p in preds])
     ihw = None
     if image_hw is not None:
         ihw = torch.as_tensor(np.broadcast_to(np.asarray(image_hw, np.float32), (batch, 2)).copy(), device=dev)
     if return_index:
         index = torch.full((batch, cfg.class_num * max_out), -1, dtype=torch.int32, device=dev)
-        _check(lib().yk_decode_py_ex(C.byref(cfg), arr, C.c_int(batch), _ptr(ihw) if ihw is not None else None,
-                                     C.c_float(obj_thresh), C.c_float(iou_thresh), C.c_int(max_out), _ptr(dets), _ptr(counts),
-                                     _ptr(index), _stream(stream)), 'yk_decode_py_ex')
+        call('yk_decode_py_ex', C.byref(cfg), arr, batch, ihw, obj_thresh, iou_thresh, max_out, dets, counts, index, _stream(stream))
         return dets, counts, index
-    _check(lib().yk_decode_py(C.byref(cfg), arr, C.c_int(batch), _ptr(ihw) if ihw is not None else None,
-                              C.c_float(obj_thresh), C.c_float(iou_thresh), C.c_int(max_out), _ptr(dets), _ptr(counts),
-                              _stream(stream)), 'yk_decode_py')
+    call('yk_decode_py', C.byref(cfg), arr, batch, ihw, obj_thresh, iou_thresh, max_out, dets, counts, _stream(stream))
     return dets, counts
 
 
@@ -435,8 +397,7 @@ def region_batched(inp, W: int, H: int, A: int, Cn: int, anchor, threshold: floa
     out = torch.empty((B, A * E, H, W), dtype=torch.float32, device=inp.device) if want_output else None
     boxes = torch.empty((B, nb, 4), dtype=torch.float32, device=inp.device)
     probs = torch.empty((B, nb, Cn + 1), dtype=torch.float32, device=inp.device)
-    _check(lib().yk_region_batched(C.byref(cfg), _ptr(inp), C.c_int(B), _ptr(out) if out is not None else None,
-                                   _ptr(boxes), _ptr(probs), _stream(stream)), 'yk_region_batched')
+    call('yk_region_batched', C.byref(cfg), inp, B, out, boxes, probs, _stream(stream))
     return out, boxes, probs
 
 
@@ -460,9 +421,7 @@ def yolo_loss(y_true, y_pred, anchors_l, obj_thresh, iou_thresh, obj_weight, noo
     loss = torch.empty(6, dtype=torch.float32, device=y_pred.device)
     grad = torch.empty_like(y_pred) if want_grad else None
     ign = torch.empty((B, h, w, A), dtype=torch.float32, device=y_pred.device) if want_ignore else None
-    _check(lib().yk_yolo_loss(C.byref(cfg), _ptr(y_true), _ptr(y_pred), C.c_int(B), _ptr(loss),
-                              _ptr(grad) if grad is not None else None, _ptr(ign) if ign is not None else None,
-                              _ptr(counts) if counts is not None else None, _stream(stream)), 'yk_yolo_loss')
+    call('yk_yolo_loss', C.byref(cfg), y_true, y_pred, B, loss, grad, ign, counts, _stream(stream))
     return loss, grad, ign
 
 
@@ -475,8 +434,7 @@ def letterbox_u8(frames, dst_hw, stream=None, out=None):
     if out is None:
         out = torch.empty((B, int(dst_hw[0]), int(dst_hw[1]), 3), dtype=torch.uint8, device=frames.device)
     assert out.is_cuda and out.is_contiguous() and tuple(out.shape) == (B, int(dst_hw[0]), int(dst_hw[1]), 3)
-    _check(lib().yk_letterbox_u8(_ptr(frames), C.c_int(B), C.c_int(sh), C.c_int(sw), _ptr(out), C.c_int(out.shape[1]),
-                                 C.c_int(out.shape[2]), _stream(stream)), 'yk_letterbox_u8')
+    call('yk_letterbox_u8', frames, B, sh, sw, out, out.shape[1], out.shape[2], _stream(stream))
     return out
 
 
@@ -491,8 +449,7 @@ def letterbox_augment_u8(frames, dst_hw, inv, stream=None, out=None):
     if out is None:
         out = torch.empty((B, int(dst_hw[0]), int(dst_hw[1]), 3), dtype=torch.uint8, device=frames.device)
     assert out.is_cuda and out.is_contiguous() and tuple(out.shape) == (B, int(dst_hw[0]), int(dst_hw[1]), 3)
-    _check(lib().yk_letterbox_augment_u8(_ptr(frames), C.c_int(B), C.c_int(sh), C.c_int(sw), _ptr(inv), _ptr(out), C.c_int(out.shape[1]),
-                                         C.c_int(out.shape[2]), _stream(stream)), 'yk_letterbox_augment_u8')
+    call('yk_letterbox_augment_u8', frames, B, sh, sw, inv, out, out.shape[1], out.shape[2], _stream(stream))
     return out
 
 
@@ -513,8 +470,7 @@ def ragged_table_to_device(table, dst_hw, packed_bytes: int, device, stream=None
     if max(end) > int(packed_bytes):
         raise YkError(f'ragged table: row {int(np.argmax(end))} ends at byte {max(end)} of a {int(packed_bytes)}-byte buffer')
     if dst_hw is not None:
-        _check(lib().yk_letterbox_ragged_params(t.ctypes.data_as(C.c_void_p), C.c_int(len(t)), C.c_int(int(dst_hw[0])), C.c_int(int(dst_hw[1]))),
-               'yk_letterbox_ragged_params')
+        call('yk_letterbox_ragged_params', t, len(t), int(dst_hw[0]), int(dst_hw[1]))
     host = torch.from_numpy(t.view(np.uint8).reshape(len(t), RAGGED_DTYPE.itemsize))
     with torch.cuda.stream(torch.cuda.current_stream() if stream is None else stream):
         return host.to(device, non_blocking=False)
@@ -543,8 +499,7 @@ def letterbox_ragged_u8(packed, table, dst_hw, stream=None, out=None):
     if out is None:
         out = torch.empty((n, int(dst_hw[0]), int(dst_hw[1]), 3), dtype=torch.uint8, device=packed.device)
     assert out.is_cuda and out.is_contiguous() and tuple(out.shape) == (n, int(dst_hw[0]), int(dst_hw[1]), 3), tuple(out.shape)
-    _check(lib().yk_letterbox_ragged_u8(_ptr(packed), C.c_size_t(packed.numel()), _ptr(table), C.c_int(n), _ptr(out), C.c_int(out.shape[1]),
-                                        C.c_int(out.shape[2]), _stream(stream)), 'yk_letterbox_ragged_u8')
+    call('yk_letterbox_ragged_u8', packed, packed.numel(), table, n, out, out.shape[1], out.shape[2], _stream(stream))
     return out
 
 
@@ -566,16 +521,15 @@ def draw_detections_u8(packed, table, dets, counts, colormap, atlas, stream=None
     assert counts.is_cuda and counts.dtype == torch.int32 and counts.is_contiguous() and tuple(counts.shape) == (n,)
     assert colormap.is_cuda and colormap.dtype == torch.uint8 and colormap.is_contiguous() and colormap.dim() == 2 and colormap.shape[1] == 3
     assert atlas.is_cuda and atlas.dtype == torch.uint8 and atlas.is_contiguous() and atlas.dim() == 3 and atlas.shape[0] == 12
-    _check(lib().yk_draw_dets_u8(_ptr(packed), C.c_size_t(packed.numel()), _ptr(table), C.c_int(n), _ptr(dets), C.c_int(dets.shape[1]),
-                                 _ptr(counts), _ptr(colormap), C.c_int(colormap.shape[0]), _ptr(atlas) if atlas.numel() else None,
-                                 C.c_int(atlas.shape[1]), C.c_int(atlas.shape[2]), C.c_size_t(int(max_pixels)), _stream(stream)), 'yk_draw_dets_u8')
+    call('yk_draw_dets_u8', packed, packed.numel(), table, n, dets, dets.shape[1], counts, colormap, colormap.shape[0],
+         atlas if atlas.numel() else None, atlas.shape[1], atlas.shape[2], int(max_pixels), _stream(stream))
     return packed
 
 
 def jpeg_tables(quality: int = 75) -> np.ndarray:
     """yk_jpeg_tables: the Annex K.1 tables scaled by the IJG rule -> uint8 [2, 64], natural order (what jpeg.quant_tables states in numpy)."""
     q = np.zeros((2, 64), np.uint8)
-    _check(lib().yk_jpeg_tables(C.c_int(int(quality)), q.ctypes.data_as(C.c_void_p)), 'yk_jpeg_tables')
+    call('yk_jpeg_tables', int(quality), q)
     return q
 
 
@@ -584,7 +538,7 @@ def jpeg_workspace_bytes(table) -> Tuple[int, int]:
     from .draw import RAGGED_DTYPE
     t = np.ascontiguousarray(np.asarray(table, dtype=RAGGED_DTYPE).reshape(-1))
     work, cap = C.c_size_t(0), C.c_size_t(0)
-    _check(lib().yk_jpeg_workspace_bytes(t.ctypes.data_as(C.c_void_p), C.c_int(len(t)), C.byref(work), C.byref(cap)), 'yk_jpeg_workspace_bytes')
+    call('yk_jpeg_workspace_bytes', t, len(t), C.byref(work), C.byref(cap))
     return int(work.value), int(cap.value)
 
 
@@ -614,9 +568,7 @@ def jpeg_encode_ragged_u8(packed, table, qtab, stream=None, sizes=None, work=Non
     assert out_off.is_cuda and out_off.dtype == torch.int64 and out_off.is_contiguous() and out_off.numel() == n + 1
     if work.numel() < sizes[0] or out.numel() < sizes[1]:
         raise YkError(f'jpeg_encode_ragged_u8: work {work.numel()} / out {out.numel()} bytes, the batch needs {sizes[0]} / {sizes[1]}')
-    _check(lib().yk_jpeg_encode_ragged_u8(_ptr(packed), C.c_size_t(packed.numel()), _ptr(table), C.c_int(n), _ptr(qtab), _ptr(work),
-                                          C.c_size_t(work.numel()), _ptr(out), C.c_size_t(out.numel()), _ptr(out_off), _stream(stream)),
-           'yk_jpeg_encode_ragged_u8')
+    call('yk_jpeg_encode_ragged_u8', packed, packed.numel(), table, n, qtab, work, work.numel(), out, out.numel(), out_off, _stream(stream))
     return out, out_off
 
 
@@ -641,8 +593,7 @@ def jpeg_decode_workspace_bytes(pics) -> int:
     from .jpeg import PIC_DTYPE
     t = np.ascontiguousarray(np.asarray(pics, dtype=PIC_DTYPE).reshape(-1))
     work = C.c_size_t(0)
-    _check(lib().yk_jpeg_decode_workspace_bytes(t.ctypes.data_as(C.POINTER(JpegPic)), C.c_int(len(t)), C.byref(work)),
-           'yk_jpeg_decode_workspace_bytes')
+    call('yk_jpeg_decode_workspace_bytes', t, len(t), C.byref(work))
     return int(work.value)
 
 
@@ -679,9 +630,8 @@ def jpeg_decode_ragged_u8(scan, pics, tables, rows, dst, stream=None, work_bytes
     assert status.is_cuda and status.dtype == torch.int32 and status.is_contiguous() and status.numel() == n
     if work.numel() < int(work_bytes):
         raise YkError(f'jpeg_decode_ragged_u8: work {work.numel()} bytes, the batch needs {int(work_bytes)}')
-    _check(lib().yk_jpeg_decode_ragged_u8(_ptr(scan), C.c_size_t(scan.numel()), _ptr(pics), _ptr(tables), C.c_size_t(tables.numel()), _ptr(rows),
-                                          C.c_int(n), _ptr(dst), C.c_size_t(dst.numel()), _ptr(work), C.c_size_t(work.numel()), _ptr(status),
-                                          C.c_int(int(chunk_bytes)), _stream(stream)), 'yk_jpeg_decode_ragged_u8')
+    call('yk_jpeg_decode_ragged_u8', scan, scan.numel(), pics, tables, tables.numel(), rows, n, dst, dst.numel(), work, work.numel(), status,
+         int(chunk_bytes), _stream(stream))
     return status
 
 
@@ -700,7 +650,7 @@ class Graph:
         return int(lib().yk_graph_kernel_node_count(self._h)) if self._h else 0
 
     def launch(self, stream_handle: C.c_void_p) -> None:
-        _check(lib().yk_graph_launch(self._h, stream_handle), 'yk_graph_launch')
+        _check(_handles_only('yk_graph_launch')(self._h, stream_handle), 'yk_graph_launch')
 
     def close(self) -> None:
         if self._h is not None and self._h.value:
@@ -717,7 +667,7 @@ class Graph:
 def capture(stream_handle: C.c_void_p, issue) -> Graph:
     """Record what `issue()` submits to the stream as a Graph.  The stream must have run the same step eagerly before."""
     L = lib()
-    _check(L.yk_graph_begin(stream_handle), 'yk_graph_begin')
+    call('yk_graph_begin', stream_handle)
     try:
         issue()
     except Exception:
@@ -727,7 +677,7 @@ def capture(stream_handle: C.c_void_p, issue) -> Graph:
             L.yk_graph_destroy(h)
         raise
     h = C.c_void_p()
-    _check(L.yk_graph_end(stream_handle, C.byref(h)), 'yk_graph_end')
+    call('yk_graph_end', stream_handle, C.byref(h))
     return Graph(h)
 
 
@@ -736,7 +686,7 @@ def _pinned(shape, dtype):
     import torch
     t = torch.empty(shape, dtype=dtype).pin_memory()
     d = C.c_void_p()
-    _check(lib().yk_host_device_ptr(C.c_void_p(t.data_ptr()), C.byref(d)), 'yk_host_device_ptr')
+    call('yk_host_device_ptr', t, C.byref(d))
     return t, d
 
 
@@ -806,7 +756,7 @@ class Pipeline:
             with torch.cuda.device(dev):
                 for _ in range(self.depth):
                     h = C.c_void_p()
-                    _check(lib().yk_stream_create(C.byref(h), C.c_int(0)), 'yk_stream_create')
+                    call('yk_stream_create', C.byref(h), 0)
                     self._own_streams.append(h)
             self.streams = [torch.cuda.ExternalStream(h.value, device=dev) for h in self._own_streams]
         else:
@@ -820,7 +770,7 @@ class Pipeline:
         for i in range(self.depth):
             s = _Slot()
             s.plan, s.stream, s.st = self.plans[i], self.streams[i], C.c_void_p(self.streams[i].cuda_stream)
-            s.preds = (C.c_void_p * len(self.outs[i]))(*[C.c_void_p(o.data_ptr()) for o in self.outs[i]])
+            s.preds = (C.c_void_p * len(self.outs[i]))(*[o.data_ptr() for o in self.outs[i]])
             s.frames = torch.full((B, H, W, 3), 127, dtype=torch.uint8, device=dev)      # (defined bytes: the warm-up step reads them)
             s.src = torch.full((B, *self.src_hw, 3), 127, dtype=torch.uint8, device=dev) if self.src_hw else s.frames
             s.image_hw = torch.empty((B, 2), dtype=torch.float32, device=dev)
@@ -836,6 +786,7 @@ class Pipeline:
         self.host_us = 0.0
         self.host_wait_us = 0.0                                                         # submit_host: time the submit thread spent BLOCKED on a slot's input buffer (cumulative)
         self._copy_stream = None                                                        # submit_host: the H2D leg's own stream (created on first use)
+        self._copy_st = None                                                            # ... and its handle, as the library takes it
 
     # -- buffers ------------------------------------------------------------------------------------
     def input(self, i: int):
@@ -864,6 +815,8 @@ class Pipeline:
             # next batch runs under its current batch's kernels instead of in front of them on the same stream (round 5: the copy leg is
             # 125 us of a 330 us step, and a stream that copies is a stream that does not compute - from host 0.87 of resident before)
             s.h2d_bufs = [s.src, torch.full_like(s.src, 127)]
+            # the copy's arguments prebuilt, like s.st: submit_host is timed, and its host thread is the busy one
+            s.h2d_ptrs, s.h_src_ptr, s.frame_bytes = [C.c_void_p(t.data_ptr()) for t in s.h2d_bufs], C.c_void_p(s.h_src.data_ptr()), s.src[0].numel()
             s.h2d_next = 0
             s.h2d_copied = [torch.cuda.Event(), torch.cuda.Event()]
             s.staged = None                                         # (buffer index, batch) of a copy stage_host() has started
@@ -872,11 +825,12 @@ class Pipeline:
                 if self._own_streams:                                   # library-created, like the slots' streams
                     h = C.c_void_p()
                     with torch.cuda.device(s.src.device):
-                        _check(lib().yk_stream_create(C.byref(h), C.c_int(0)), 'yk_stream_create')
+                        call('yk_stream_create', C.byref(h), 0)
                     self._own_streams.append(h)
                     self._copy_stream = torch.cuda.ExternalStream(h.value, device=s.src.device)
                 else:
                     self._copy_stream = torch.cuda.Stream(device=s.src.device)
+                self._copy_st = C.c_void_p(self._copy_stream.cuda_stream)
 
     # -- the step, as the library calls it is made of (eager, or recorded by capture()) ---------------------------------
     def _h2d_start(self, s, B):
@@ -885,7 +839,7 @@ class Pipeline:
         import time
         b = s.h2d_next
         s.h2d_next ^= 1
-        dst, cs = s.h2d_bufs[b], self._copy_stream
+        cs = self._copy_stream
         if s.h2d_free[b] is not None and not s.h2d_free[b].query():
             # the batch that last read this buffer (two submits of this slot ago) - waited for on the HOST, where it is over long ago in steady
             # state: a wait inside the copy stream would put barrier packets into a fifth hardware queue, and a fifth active queue costs the
@@ -893,8 +847,7 @@ class Pipeline:
             t0 = time.perf_counter()
             s.h2d_free[b].synchronize()
             self.host_wait_us += (time.perf_counter() - t0) * 1e6      # blocked, not busy: bench.py reports the two apart
-        _check(lib().yk_memcpy_async(C.c_void_p(dst.data_ptr()), C.c_void_p(s.h_src.data_ptr()), C.c_size_t(B * s.src[0].numel()),
-                                     C.c_void_p(cs.cuda_stream)), 'yk_memcpy_async')
+        _check(_handles_only('yk_memcpy_async')(s.h2d_ptrs[b], s.h_src_ptr, B * s.frame_bytes, self._copy_st), 'yk_memcpy_async')
         s.h2d_copied[b].record(cs)
         return b
 
@@ -934,21 +887,19 @@ class Pipeline:
         s.h2d_free[s.h2d_last] = ev
 
     def _issue(self, s, B, src_ptr, host, use_hw, obj, iou, max_out, want_index):
-        L = lib()
         H, W = self.spec.in_hw
         x = src_ptr
         if self.src_hw:
-            _check(L.yk_letterbox_u8(C.c_void_p(x), C.c_int(B), C.c_int(self.src_hw[0]), C.c_int(self.src_hw[1]), _ptr(s.frames),
-                                     C.c_int(H), C.c_int(W), s.st), 'yk_letterbox_u8')
-            x = s.frames.data_ptr()
-        _check(L.yk_run_u8(s.plan._h, C.c_void_p(x), C.c_int(B), s.st), 'yk_run_u8')
-        ihw = _ptr(s.image_hw) if use_hw else None
+            call('yk_letterbox_u8', x, B, self.src_hw[0], self.src_hw[1], s.frames, H, W, s.st)
+            x = s.frames
+        call('yk_run_u8', s.plan._h, x, B, s.st)
+        ihw = s.image_hw if use_hw else None
         if host:
-            _check(L.yk_decode_py_packed(C.byref(self.cfg), s.preds, C.c_int(B), ihw, C.c_float(obj), C.c_float(iou), C.c_int(max_out),
-                                         s.d_rows, s.d_offsets, s.d_index if want_index else None, None, None, s.st), 'yk_decode_py_packed')
+            call('yk_decode_py_packed', C.byref(self.cfg), s.preds, B, ihw, obj, iou, max_out, s.d_rows, s.d_offsets,
+                 s.d_index if want_index else None, None, None, s.st)
         else:
-            _check(L.yk_decode_py_ex(C.byref(self.cfg), s.preds, C.c_int(B), ihw, C.c_float(obj), C.c_float(iou), C.c_int(max_out),
-                                     _ptr(s.dets), _ptr(s.counts), _ptr(s.index) if want_index else None, s.st), 'yk_decode_py_ex')
+            call('yk_decode_py_ex', C.byref(self.cfg), s.preds, B, ihw, obj, iou, max_out, s.dets, s.counts,
+                 s.index if want_index else None, s.st)
 
     GRAPH_CACHE = 8                     # captured steps kept per slot (one per distinct (batch, source, thresholds, ...) combination)
 
@@ -970,7 +921,7 @@ class Pipeline:
             return
         # a captured step holds the address of the stream's decode scratch: if that buffer has moved since (it cannot once the slot is
         # warm - __init__ sizes it for max_batch x max_out - but another user of the same stream could grow it), every capture is stale
-        gen = int(lib().yk_scratch_generation(s.st))
+        gen = _handles_only('yk_scratch_generation')(s.st)
         if gen != s.scratch_gen:
             s.stream.synchronize()
             self._drop_graphs(s)

@@ -119,17 +119,12 @@ class MapEvaluator:
                 if n_new and B:
                     d = d.to(self.dev).contiguous()
                     c = c.to(self.dev).contiguous()
-                    L = engine.lib()
                     if padded:
-                        engine._check(L.yk_map_append_padded(engine._ptr(d), engine._ptr(c), C.c_int(B), C.c_int(cap), C.c_int(self.n_img),
-                                                             C.c_longlong(n_new), engine._ptr(self._rows), engine._ptr(self._img),
-                                                             C.c_longlong(self.n_rows), C.c_longlong(self._cap), engine._stream(st)),
-                                      'yk_map_append_padded')
+                        engine.call('yk_map_append_padded', d, c, B, cap, self.n_img, n_new, self._rows, self._img, self.n_rows, self._cap,
+                                    engine._stream(st))
                     else:
-                        engine._check(L.yk_map_append_packed(engine._ptr(d), engine._ptr(c), C.c_int(B), C.c_int(self.n_img),
-                                                             C.c_longlong(n_new), engine._ptr(self._rows), engine._ptr(self._img),
-                                                             C.c_longlong(self.n_rows), C.c_longlong(self._cap), engine._stream(st)),
-                                      'yk_map_append_packed')
+                        engine.call('yk_map_append_packed', d, c, B, self.n_img, n_new, self._rows, self._img, self.n_rows, self._cap,
+                                    engine._stream(st))
                     self._last = st
         for i in range(B):
             g = _gt_rows(gts[i])
@@ -177,10 +172,8 @@ class MapEvaluator:
         G = int(off[-1])
         if G > MAX_ROWS:
             raise engine.YkError(f'MapEvaluator: {G} ground-truth rows: more than 2^31-1')
-        L = engine.lib()
-        L.yk_map_workspace_bytes.argtypes = [C.c_longlong, C.c_longlong, C.c_int, C.c_int, C.POINTER(C.c_size_t)]
         nbytes = C.c_size_t()
-        engine._check(L.yk_map_workspace_bytes(R, G, N, Cn, C.byref(nbytes)), 'yk_map_workspace_bytes')
+        engine.call('yk_map_workspace_bytes', R, G, N, Cn, C.byref(nbytes))
         with torch.cuda.device(self.dev):
             st = torch.cuda.current_stream() if stream is None else stream
             with torch.cuda.stream(st):
@@ -194,12 +187,9 @@ class MapEvaluator:
                 flags = torch.empty((max(R, 1),), dtype=torch.uint8, device=self.dev)
                 ints = torch.empty((4, Cn), dtype=torch.int32, device=self.dev)
                 ap = torch.empty((Cn + 1,), dtype=torch.float64, device=self.dev)           # [class_num] + the mean
-                vp = lambda t: None if t is None else engine._ptr(t)
-                engine._check(L.yk_map_eval(vp(self._rows) if R else None, vp(self._img) if R else None, C.c_longlong(R), C.c_int(N), vp(d_gt),
-                                            vp(d_off), vp(d_diff), C.c_longlong(G), C.c_int(Cn), C.c_double(self.iou_thresh),
-                                            C.c_int(int(self.use_07_metric)), C.c_int(int(self.plus_one)), vp(work), C.c_size_t(nbytes.value),
-                                            vp(flags), vp(ints[0]), vp(ints[1]), vp(ints[2]), vp(ints[3]), vp(ap),
-                                            C.c_void_p(ap.data_ptr() + 8 * Cn), engine._stream(st)), 'yk_map_eval')
+                engine.call('yk_map_eval', self._rows if R else None, self._img if R else None, R, N, d_gt, d_off, d_diff, G, Cn, self.iou_thresh,
+                            int(self.use_07_metric), int(self.plus_one), work, nbytes.value, flags, ints[0], ints[1], ints[2], ints[3], ap,
+                            ap[Cn:], engine._stream(st))
                 st.synchronize()
                 self._last = None                                             # everything added so far is complete
                 h_ints, h_ap, h_flags = ints.cpu().numpy().astype(int), ap.cpu().numpy(), flags[:R].cpu().numpy()

@@ -179,7 +179,6 @@ class InputPipeline:
     def _produce(self):
         import torch
         H, W = int(self.h.in_hw[0][0]), int(self.h.in_hw[0][1])
-        L = engine.lib()
         self._tick = 0
         try:
             for rows in self.rows:
@@ -234,8 +233,7 @@ class InputPipeline:
                         else:
                             frames[torch.as_tensor(idx, device=self.dev)] = out
                     x = torch.empty((n, H, W, 3), dtype=torch.float32, device=self.dev)
-                    engine._check(L.yk_normalise_u8(engine._ptr(frames), n, engine.C.c_size_t(H * W * 3), engine._ptr(x),
-                                                    engine._stream(self.stream)), 'yk_normalise_u8')
+                    engine.call('yk_normalise_u8', frames, n, H * W * 3, x, engine._stream(self.stream))
                     labels = []
                     for view, slot in lab_slots:
                         labels.append(view.to(self.dev, non_blocking=True))

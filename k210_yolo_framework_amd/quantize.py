@@ -30,7 +30,6 @@ for every network output.  What the KPU path cannot express raises `KmodelError`
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Dict, List, Optional, Tuple
 
 import numpy as np
@@ -444,7 +443,7 @@ class Calibrator:
         import torch
         from . import engine
         engine.require_gpu()
-        self.torch, self.engine, self.L = torch, engine, engine.lib()
+        self.torch, self.engine = torch, engine
         self.spec, self.max_batch = spec, int(max_batch)
         self.dev = torch.device('cuda', device)
         self.names = tensor_names(spec)
@@ -479,34 +478,28 @@ class Calibrator:
         self.images = 0
         self.reset()
 
-    def _s(self):
-        return C.c_void_p(self.torch.cuda.current_stream().cuda_stream)
+    def _ck(self, name, *args):
+        """engine.call of a library function whose last parameter is the stream: torch's current one."""
+        self.engine.call(name, *args, self.torch.cuda.current_stream().cuda_stream)
 
     def reset(self) -> None:
-        self.engine._check(self.L.yk_range_reset(self.engine._ptr(self.d_range), C.c_int(self.n_slots), self._s()), 'yk_range_reset')
+        self._ck('yk_range_reset', self.d_range, self.n_slots)
         self.images = self.hist_images = 0
         self.h_lo = self.h_hi = self.h_inv = None                                                        # frozen by the first feed_hist
         self.last_clip: List[dict] = []
 
     def _epilogue(self, z, M, Cn, scale, bias, act, alpha, y, slot):
-        p = self.engine._ptr
-        self.engine._check(self.L.yk_scale_act_range_f32(p(z), C.c_longlong(M), C.c_int(Cn), p(scale), p(bias), C.c_int(act), C.c_float(alpha), p(y),
-                                                         p(self.d_range), C.c_int(slot), self._s()), 'yk_scale_act_range_f32')
+        self._ck('yk_scale_act_range_f32', z, M, Cn, scale, bias, act, alpha, y, self.d_range, slot)
 
     def _range(self, x, slot):
-        self.engine._check(self.L.yk_range_f32(self.engine._ptr(x), C.c_longlong(x.numel()), self.engine._ptr(self.d_range), C.c_int(slot), self._s()),
-                           'yk_range_f32')
+        self._ck('yk_range_f32', x, x.numel(), self.d_range, slot)
 
     def _epilogue_hist(self, z, M, Cn, scale, bias, act, alpha, y, slot):
-        p = self.engine._ptr
-        self.engine._check(self.L.yk_scale_act_hist_f32(p(z), C.c_longlong(M), C.c_int(Cn), p(scale), p(bias), C.c_int(act), C.c_float(alpha), p(y),
-                                                        C.c_float(self.h_lo[slot]), C.c_float(self.h_inv[slot]), C.c_int(self.bins), p(self.d_hist),
-                                                        p(self.d_hflags), C.c_int(slot), self._s()), 'yk_scale_act_hist_f32')
+        self._ck('yk_scale_act_hist_f32', z, M, Cn, scale, bias, act, alpha, y, float(self.h_lo[slot]), float(self.h_inv[slot]), self.bins,
+                 self.d_hist, self.d_hflags, slot)
 
     def _hist(self, x, slot):
-        p = self.engine._ptr
-        self.engine._check(self.L.yk_hist_f32(p(x), C.c_longlong(x.numel()), C.c_float(self.h_lo[slot]), C.c_float(self.h_inv[slot]),
-                                              C.c_int(self.bins), p(self.d_hist), p(self.d_hflags), C.c_int(slot), self._s()), 'yk_hist_f32')
+        self._ck('yk_hist_f32', x, x.numel(), float(self.h_lo[slot]), float(self.h_inv[slot]), self.bins, self.d_hist, self.d_hflags, slot)
 
     def feed(self, frames_u8, keep=None) -> "Calibrator":
         """frames_u8: device uint8 [B, H, W, 3], B <= max_batch, H x W = the spec's input size.  `keep`: a dict that receives every tensor
@@ -530,8 +523,7 @@ class Calibrator:
             if self.d_hist is None:
                 self.d_hist = self.torch.zeros(self.n_slots * self.bins, dtype=self.torch.int64, device=self.dev)
                 self.d_hflags = self.torch.zeros(self.n_slots, dtype=self.torch.int32, device=self.dev)
-            self.engine._check(self.L.yk_hist_reset(self.engine._ptr(self.d_hist), C.c_int(self.n_slots), C.c_int(self.bins), self._s()),
-                               'yk_hist_reset')
+            self._ck('yk_hist_reset', self.d_hist, self.n_slots, self.bins)
             self.d_hflags.zero_()
             self.h_lo, self.h_hi, self.h_inv = lo, hi, inv
         self._walk(frames_u8, keep, self._epilogue_hist, self._hist, 'feed_hist')
@@ -540,7 +532,7 @@ class Calibrator:
 
     def _walk(self, frames_u8, keep, epilogue, plain, who) -> None:
         """One fp32 forward pass of the spec; `epilogue` finishes a conv (and the input) and measures it, `plain` measures a moved tensor."""
-        torch, eng, L, p = self.torch, self.engine, self.L, self.engine._ptr
+        torch, eng = self.torch, self.engine
         H, W = self.spec.in_hw
         if not (frames_u8.is_cuda and frames_u8.dtype == torch.uint8 and frames_u8.dim() == 4 and tuple(frames_u8.shape[1:]) == (H, W, 3)):
             raise eng.YkError(f'Calibrator.{who} takes device uint8 frames [B, {H}, {W}, 3]')
@@ -560,21 +552,18 @@ class Calibrator:
             if t in (ns.OP_CONV, ns.OP_DWCONV):
                 name = op['layer']
                 w = self.P[name + '/w']
-                geom = [C.c_int(v) for v in (B, hi, wi, ci, ho, wo, op['stride'], op['pad_t'], op['pad_l'])]
+                geom = [B, hi, wi, ci, ho, wo, op['stride'], op['pad_t'], op['pad_l']]
                 z = new(B, ho, wo, co)
                 if t == ns.OP_DWCONV:
-                    eng._check(L.yk_dw3x3_fwd_f32(p(x), p(w), *geom, p(z), self._s()), 'yk_dw3x3_fwd_f32')
+                    self._ck('yk_dw3x3_fwd_f32', x, w, *geom, z)
                 elif op['k'] == 1:
-                    eng._check(L.yk_gemm_f32(C.c_int(0), C.c_int(1), C.c_int(M), C.c_int(co), C.c_int(ci), C.c_float(1.0), p(x), C.c_int(ci), p(w),
-                                             C.c_int(ci), C.c_float(0.0), p(z), C.c_int(co), self._s()), 'yk_gemm_f32')
+                    self._ck('yk_gemm_f32', 0, 1, M, co, ci, 1.0, x, ci, w, ci, 0.0, z, co)
                 elif ci % 4 == 0:
-                    eng._check(L.yk_conv3x3_bn_fwd_f32(p(x), p(w), *geom, C.c_int(co), p(z), None, None, C.c_float(0.0), C.c_int(0), C.c_float(0.0),
-                                                       None, None, None, None, None, C.c_float(0.0), None, self._s()), 'yk_conv3x3_bn_fwd_f32')
+                    self._ck('yk_conv3x3_bn_fwd_f32', x, w, *geom, co, z, None, None, 0.0, 0, 0.0, None, None, None, None, None, 0.0, None)
                 else:
                     col = new(M, 9 * ci)
-                    eng._check(L.yk_im2col3x3_f32(p(x), *geom, p(col), self._s()), 'yk_im2col3x3_f32')
-                    eng._check(L.yk_gemm_f32(C.c_int(0), C.c_int(1), C.c_int(M), C.c_int(co), C.c_int(9 * ci), C.c_float(1.0), p(col), C.c_int(9 * ci),
-                                             p(w), C.c_int(9 * ci), C.c_float(0.0), p(z), C.c_int(co), self._s()), 'yk_gemm_f32')
+                    self._ck('yk_im2col3x3_f32', x, *geom, col)
+                    self._ck('yk_gemm_f32', 0, 1, M, co, 9 * ci, 1.0, col, 9 * ci, w, 9 * ci, 0.0, z, co)
                     del col
                 y = new(B, ho, wo, co)
                 epilogue(z, M, co, self.P[name + '/scale'], self.P[name + '/bias'], op['act'], float(op['alpha']), y, op['out'])
@@ -599,8 +588,7 @@ class Calibrator:
         hi = np.empty(self.n_slots, np.float32)
         fl = np.empty(self.n_slots, np.int32)
         self.torch.cuda.current_stream().synchronize()
-        self.engine._check(self.L.yk_range_read(self.engine._ptr(self.d_range), C.c_int(self.n_slots), lo.ctypes.data_as(C.c_void_p),
-                                                hi.ctypes.data_as(C.c_void_p), fl.ctypes.data_as(C.c_void_p)), 'yk_range_read')
+        self.engine.call('yk_range_read', self.d_range, self.n_slots, lo, hi, fl)
         return lo, hi, fl
 
     def _raise_non_finite(self, flags) -> None:
@@ -618,8 +606,7 @@ class Calibrator:
         counts = np.empty((self.n_slots, self.bins), np.uint64)
         fl = np.empty(self.n_slots, np.int32)
         self.torch.cuda.current_stream().synchronize()
-        self.engine._check(self.L.yk_hist_read(self.engine._ptr(self.d_hist), self.engine._ptr(self.d_hflags), C.c_int(self.n_slots),
-                                               C.c_int(self.bins), counts.ctypes.data_as(C.c_void_p), fl.ctypes.data_as(C.c_void_p)), 'yk_hist_read')
+        self.engine.call('yk_hist_read', self.d_hist, self.d_hflags, self.n_slots, self.bins, counts, fl)
         self._raise_non_finite(fl)
         return counts, self.h_lo.copy(), self.h_hi.copy()
 

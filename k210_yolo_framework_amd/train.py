@@ -71,7 +71,6 @@ class Trainer:
         self.lr, self.decay, self.iterations = float(lr), float(decay), 0
         self.pg, self.world = process_group, int(world_size)
         self.lay = {l.name: l for l in spec.layers}
-        self.L = engine.lib()
 
         # ---- flat parameter / gradient / Adam buffers; conv kernels as [Cout][kh*kw*Cin], depthwise as [9][C]
         self.slots: Dict[str, tuple] = {}
@@ -184,27 +183,23 @@ class Trainer:
         return out
 
     # ------------------------------------------------------------------ kernel calls
-    def _s(self):
-        return C.c_void_p(self.torch.cuda.current_stream().cuda_stream)
-
-    def _ck(self, rc, what):
-        engine._check(rc, what)
+    def _ck(self, name, *args):
+        """engine.call of a library function whose last parameter is the stream: torch's current one."""
+        engine.call(name, *args, self.torch.cuda.current_stream().cuda_stream)
 
     def _new(self, *shape):
         return self.torch.empty(shape, dtype=self.torch.float32, device=self.dev)
 
     def gemm(self, tA, tB, M, N, K, A, lda, Bm, ldb, Cm, ldc, alpha=1.0, beta=0.0):
-        self._ck(self.L.yk_gemm_f32(C.c_int(tA), C.c_int(tB), C.c_int(M), C.c_int(N), C.c_int(K), C.c_float(alpha), engine._ptr(A),
-                                    C.c_int(lda), engine._ptr(Bm), C.c_int(ldb), C.c_float(beta), engine._ptr(Cm), C.c_int(ldc),
-                                    self._s()), 'yk_gemm_f32')
+        self._ck('yk_gemm_f32', tA, tB, M, N, K, alpha, A, lda, Bm, ldb, beta, Cm, ldc)
 
     def _geom(self, op):
         hi, wi, ci = self.spec.tensors[op['in0']]
         ho, wo, _ = self.spec.tensors[op['out']]
-        return [C.c_int(v) for v in (self.B, hi, wi, ci, ho, wo, op['stride'], op['pad_t'], op['pad_l'])]
+        return [self.B, hi, wi, ci, ho, wo, op['stride'], op['pad_t'], op['pad_l']]
 
     def _axpy(self, a, x, y):
-        self._ck(self.L.yk_axpy_f32(C.c_longlong(x.numel()), C.c_float(a), engine._ptr(x), engine._ptr(y), self._s()), 'yk_axpy_f32')
+        self._ck('yk_axpy_f32', x.numel(), a, x, y)
 
     def _fused_adds(self):
         """conv op index -> (index of the Add that consumes ONLY-there its output, the Add's other input).  The Add is folded into that
@@ -257,7 +252,7 @@ class Trainer:
                 a, kk = x, op['cin']                                 # the GEMM's operand: a 1x1 conv's input, or the column matrix below
                 if route == 'im2col':
                     a, kk = self._new(M, 9 * op['cin']), 9 * op['cin']
-                    self._ck(self.L.yk_im2col3x3_f32(engine._ptr(x), *self._geom(op), engine._ptr(a), self._s()), 'yk_im2col3x3_f32')
+                    self._ck('yk_im2col3x3_f32', x, *self._geom(op), a)
                 if l.bn_name:
                     # convolution + batch statistics + apply in one library call: the producer of z leaves the partial sums of the
                     # statistics (yk_gemm_bn_fwd_f32 / yk_dw3x3_bn_fwd_f32), z is not read a second time for them
@@ -265,19 +260,15 @@ class Trainer:
                     mean, invstd = self._new(co), self._new(co)
                     fa = fused_add.get(i)
                     res = T[fa[1]] if fa is not None else None       # keras Add()([res, this output]) folded into the apply pass
-                    bn = (engine._ptr(z), engine._ptr(self.view(self.P, l.bn_name + '/gamma')),
-                          engine._ptr(self.view(self.P, l.bn_name + '/beta')), C.c_float(ns.BN_EPS), C.c_int(op['act']),
-                          C.c_float(op['alpha']), engine._ptr(y), engine._ptr(mean), engine._ptr(invstd),
-                          engine._ptr(self.moving[l.bn_name + '/moving_mean']), engine._ptr(self.moving[l.bn_name + '/moving_variance']),
-                          C.c_float(BN_MOMENTUM_V2 if self.spec.name == 'yolo_mobilev2' and not _is_darknet_conv(l.name) else BN_MOMENTUM),
-                          engine._ptr(res) if res is not None else None, self._s())
+                    bn = (z, self.view(self.P, l.bn_name + '/gamma'), self.view(self.P, l.bn_name + '/beta'), ns.BN_EPS, op['act'], op['alpha'],
+                          y, mean, invstd, self.moving[l.bn_name + '/moving_mean'], self.moving[l.bn_name + '/moving_variance'],
+                          BN_MOMENTUM_V2 if self.spec.name == 'yolo_mobilev2' and not _is_darknet_conv(l.name) else BN_MOMENTUM, res)
                     if route == 'implicit':
-                        self._ck(self.L.yk_conv3x3_bn_fwd_f32(engine._ptr(x), engine._ptr(w), *self._geom(op), C.c_int(co), *bn), 'yk_conv3x3_bn_fwd_f32')
+                        self._ck('yk_conv3x3_bn_fwd_f32', x, w, *self._geom(op), co, *bn)
                     elif t == ns.OP_CONV:
-                        self._ck(self.L.yk_gemm_bn_fwd_f32(C.c_int(M), C.c_int(co), C.c_int(kk), engine._ptr(a), C.c_int(kk), engine._ptr(w),
-                                                           C.c_int(kk), *bn), 'yk_gemm_bn_fwd_f32')           # Z = X * W^T
+                        self._ck('yk_gemm_bn_fwd_f32', M, co, kk, a, kk, w, kk, *bn)           # Z = X * W^T
                     else:
-                        self._ck(self.L.yk_dw3x3_bn_fwd_f32(engine._ptr(x), engine._ptr(w), *self._geom(op), *bn), 'yk_dw3x3_bn_fwd_f32')
+                        self._ck('yk_dw3x3_bn_fwd_f32', x, w, *self._geom(op), *bn)
                     S[i] = dict(z=z, mean=mean, invstd=invstd)
                     if fa is not None:                               # y IS the Add's output; the conv's own output tensor is never needed again
                         T[self.spec.ops[fa[0]]['out']] = y
@@ -287,11 +278,9 @@ class Trainer:
                     if t == ns.OP_CONV:
                         self.gemm(0, 1, M, co, kk, a, kk, w, kk, z, co)                  # Z = X * W^T
                     else:
-                        self._ck(self.L.yk_dw3x3_fwd_f32(engine._ptr(x), engine._ptr(w), *self._geom(op), engine._ptr(z), self._s()),
-                                 'yk_dw3x3_fwd_f32')
+                        self._ck('yk_dw3x3_fwd_f32', x, w, *self._geom(op), z)
                     if l.use_bias:
-                        self._ck(self.L.yk_bias_add_f32(engine._ptr(z), C.c_longlong(M), C.c_int(co),
-                                                        engine._ptr(self.view(self.P, l.name + '/bias')), self._s()), 'yk_bias_add_f32')
+                        self._ck('yk_bias_add_f32', z, M, co, self.view(self.P, l.name + '/bias'))
                     y = z
                 if self.qat is not None:
                     y = self._qat_out(i, op['out'], y, S, observe)
@@ -299,9 +288,7 @@ class Trainer:
                 hi, wi, ci = self.spec.tensors[op['in0']]
                 y = self._new(self.B, ho, wo, co)
                 arg = torch.empty((self.B, ho, wo, co), dtype=torch.uint8, device=self.dev)
-                self._ck(self.L.yk_maxpool2_fwd_f32(engine._ptr(x), C.c_int(self.B), C.c_int(hi), C.c_int(wi), C.c_int(ci), C.c_int(ho),
-                                                    C.c_int(wo), C.c_int(op['stride']), engine._ptr(y), engine._ptr(arg), self._s()),
-                         'yk_maxpool2_fwd_f32')
+                self._ck('yk_maxpool2_fwd_f32', x, self.B, hi, wi, ci, ho, wo, op['stride'], y, arg)
                 S[i] = dict(arg=arg)
             elif t == ns.OP_UPSAMPLE:                                                   # nearest x2: pure data movement
                 y = x.repeat_interleave(2, dim=1).repeat_interleave(2, dim=2).contiguous()
@@ -350,9 +337,7 @@ class Trainer:
                 continue
             if self.qat is not None and 'qy' in self.saved.get(i, ()):
                 # straight-through: dy is the gradient of the fake-quantised output and nobody else holds it, masked in place
-                self._ck(self.L.yk_qat_act_bwd_f32(engine._ptr(dy), engine._ptr(self.saved[i]['qy']), C.c_longlong(dy.numel()),
-                                                   engine._ptr(self._qa_ranges), C.c_int(op['out']), engine._ptr(dy), self._s()),
-                         'yk_qat_act_bwd_f32')
+                self._ck('yk_qat_act_bwd_f32', dy, self.saved[i]['qy'], dy.numel(), self._qa_ranges, op['out'], dy)
             x = self.T.get(op['in0'])                               # (None for an Add whose conv input was folded into the producer: never stored, never read here)
             ho, wo, co = self.spec.tensors[op['out']]
             hi, wi, ci = self.spec.tensors[op['in0']]
@@ -364,17 +349,13 @@ class Trainer:
                 if l.bn_name:
                     sv = self.saved[i]
                     dz = self._new(self.B, ho, wo, co)
-                    self._ck(self.L.yk_bn_train_bwd_f32(
-                        engine._ptr(sv['z']), engine._ptr(dy), C.c_longlong(M), C.c_int(co),
-                        engine._ptr(self.view(self.P, l.bn_name + '/gamma')), engine._ptr(self.view(self.P, l.bn_name + '/beta')),
-                        engine._ptr(sv['mean']), engine._ptr(sv['invstd']), C.c_int(op['act']), C.c_float(op['alpha']), engine._ptr(dz),
-                        engine._ptr(self.view(self.G, l.bn_name + '/gamma')), engine._ptr(self.view(self.G, l.bn_name + '/beta')),
-                        self._s()), 'yk_bn_train_bwd_f32')
+                    self._ck('yk_bn_train_bwd_f32', sv['z'], dy, M, co, self.view(self.P, l.bn_name + '/gamma'), self.view(self.P, l.bn_name + '/beta'),
+                             sv['mean'], sv['invstd'], op['act'], op['alpha'], dz, self.view(self.G, l.bn_name + '/gamma'),
+                             self.view(self.G, l.bn_name + '/beta'))
                 else:
                     dz = dy
                     if l.use_bias:
-                        self._ck(self.L.yk_colsum_f32(engine._ptr(dz), C.c_longlong(M), C.c_int(co), engine._ptr(self.view(self.G, l.name + '/bias')),
-                                                      self._s()), 'yk_colsum_f32')
+                        self._ck('yk_colsum_f32', dz, M, co, self.view(self.G, l.name + '/bias'))
                 need_dx = op['in0'] != 0
                 if t == ns.OP_CONV:
                     route = conv_route(op, l)
@@ -389,49 +370,42 @@ class Trainer:
                                 acc(op['in0'], dx, True)
                     elif route == 'implicit':
                         geom = self._geom(op)
-                        self._ck(self.L.yk_conv3x3_bwd_weight_f32(engine._ptr(x), engine._ptr(dz), *geom, C.c_int(co), engine._ptr(gw), self._s()),
-                                 'yk_conv3x3_bwd_weight_f32')
+                        self._ck('yk_conv3x3_bwd_weight_f32', x, dz, *geom, co, gw)
                         if need_dx:
                             dx = self._new(self.B, hi, wi, ci)
                             if op['stride'] == 1:
-                                self._ck(self.L.yk_conv3x3_bwd_data_f32(engine._ptr(dz), engine._ptr(w), *geom, C.c_int(co), engine._ptr(dx), self._s()),
-                                         'yk_conv3x3_bwd_data_f32')
+                                self._ck('yk_conv3x3_bwd_data_f32', dz, w, *geom, co, dx)
                             else:                                           # strided: column matrix of gradients, folded by col2im
                                 kk = 9 * ci
                                 col = self._new(M, kk)
                                 self.gemm(0, 0, M, kk, co, dz, co, w, kk, col, kk)
-                                self._ck(self.L.yk_col2im3x3_f32(engine._ptr(col), *geom, engine._ptr(dx), self._s()), 'yk_col2im3x3_f32')
+                                self._ck('yk_col2im3x3_f32', col, *geom, dx)
                                 del col
                             acc(op['in0'], dx, True)
                     else:
                         kk = 9 * ci
                         col = self._new(M, kk)
-                        self._ck(self.L.yk_im2col3x3_f32(engine._ptr(x), *self._geom(op), engine._ptr(col), self._s()), 'yk_im2col3x3_f32')
+                        self._ck('yk_im2col3x3_f32', x, *self._geom(op), col)
                         self.gemm(1, 0, co, kk, M, dz, co, col, kk, gw, kk)
                         if need_dx:
                             self.gemm(0, 0, M, kk, co, dz, co, w, kk, col, kk)          # dcol (reuses the buffer)
                             dx = self._new(self.B, hi, wi, ci)
-                            self._ck(self.L.yk_col2im3x3_f32(engine._ptr(col), *self._geom(op), engine._ptr(dx), self._s()),
-                                     'yk_col2im3x3_f32')
+                            self._ck('yk_col2im3x3_f32', col, *self._geom(op), dx)
                             acc(op['in0'], dx, True)
                         del col
                 else:
-                    grouped_dw.append((x, dz, gw, [g.value for g in self._geom(op)]))
+                    grouped_dw.append((x, dz, gw, self._geom(op)))
                     if need_dx:
                         dx = self._new(self.B, hi, wi, ci)
-                        self._ck(self.L.yk_dw3x3_bwd_data_f32(engine._ptr(dz), engine._ptr(w), *self._geom(op), engine._ptr(dx), self._s()),
-                                 'yk_dw3x3_bwd_data_f32')
+                        self._ck('yk_dw3x3_bwd_data_f32', dz, w, *self._geom(op), dx)
                         acc(op['in0'], dx, True)
             elif t == ns.OP_MAXPOOL:
                 dx = self._new(self.B, hi, wi, ci)
-                self._ck(self.L.yk_maxpool2_bwd_f32(engine._ptr(dy), engine._ptr(self.saved[i]['arg']), C.c_int(self.B), C.c_int(hi),
-                                                    C.c_int(wi), C.c_int(ci), C.c_int(ho), C.c_int(wo), C.c_int(op['stride']),
-                                                    engine._ptr(dx), self._s()), 'yk_maxpool2_bwd_f32')
+                self._ck('yk_maxpool2_bwd_f32', dy, self.saved[i]['arg'], self.B, hi, wi, ci, ho, wo, op['stride'], dx)
                 acc(op['in0'], dx, True)
             elif t == ns.OP_UPSAMPLE:
                 dx = self._new(self.B, hi, wi, ci)
-                self._ck(self.L.yk_upsample2x_bwd_f32(engine._ptr(dy), C.c_int(self.B), C.c_int(hi), C.c_int(wi), C.c_int(ci),
-                                                      engine._ptr(dx), self._s()), 'yk_upsample2x_bwd_f32')
+                self._ck('yk_upsample2x_bwd_f32', dy, self.B, hi, wi, ci, dx)
                 acc(op['in0'], dx, True)
             elif t == ns.OP_CONCAT:
                 c0 = self.spec.tensors[op['in0']][2]
@@ -460,16 +434,15 @@ class Trainer:
             n = len(grouped)
             ia = lambda v: (C.c_int * n)(*v)
             pa = lambda ts: (C.c_void_p * n)(*[t.data_ptr() for t in ts])
-            self._ck(self.L.yk_gemm_f32_grouped(C.c_int(n), C.c_int(1), C.c_int(0), ia([g[3] for g in grouped]), ia([g[4] for g in grouped]),
-                                                ia([g[5] for g in grouped]), C.c_float(1.0), pa([g[0] for g in grouped]), ia([g[3] for g in grouped]),
-                                                pa([g[1] for g in grouped]), ia([g[4] for g in grouped]), C.c_float(0.0), pa([g[2] for g in grouped]),
-                                                ia([g[4] for g in grouped]), self._s()), 'yk_gemm_f32_grouped')
+            self._ck('yk_gemm_f32_grouped', n, 1, 0, ia([g[3] for g in grouped]), ia([g[4] for g in grouped]), ia([g[5] for g in grouped]), 1.0,
+                     pa([g[0] for g in grouped]), ia([g[3] for g in grouped]), pa([g[1] for g in grouped]), ia([g[4] for g in grouped]), 0.0,
+                     pa([g[2] for g in grouped]), ia([g[4] for g in grouped]))
         if grouped_dw:
             n = len(grouped_dw)
             pa = lambda ts: (C.c_void_p * n)(*[t.data_ptr() for t in ts])
             geo = (C.c_int * (9 * n))(*[v for g in grouped_dw for v in g[3]])
-            self._ck(self.L.yk_dw3x3_bwd_weight_grouped_f32(C.c_int(n), pa([g[0] for g in grouped_dw]), pa([g[1] for g in grouped_dw]), geo,
-                                                            pa([g[2] for g in grouped_dw]), self._s()), 'yk_dw3x3_bwd_weight_grouped_f32')
+            self._ck('yk_dw3x3_bwd_weight_grouped_f32', n, pa([g[0] for g in grouped_dw]), pa([g[1] for g in grouped_dw]), geo,
+                     pa([g[2] for g in grouped_dw]))
 
     # ------------------------------------------------------------------ one optimisation step
     def regulariser(self, add_grad: bool) -> "torch.Tensor":
@@ -486,9 +459,7 @@ class Trainer:
         pre, off, nseg, total = self._l2_seg
         tot = torch.zeros(1, dtype=torch.float32, device=self.dev)
         if nseg:
-            self._ck(self.L.yk_l2_segments_f32(engine._ptr(self.P), engine._ptr(self.G), engine._ptr(pre), engine._ptr(off), C.c_int(nseg),
-                                               C.c_longlong(total), C.c_float(L2_WEIGHT), C.c_int(1), C.c_int(1 if add_grad else 0),
-                                               engine._ptr(tot), self._s()), 'yk_l2_segments_f32')
+            self._ck('yk_l2_segments_f32', self.P, self.G, pre, off, nseg, total, L2_WEIGHT, 1, int(add_grad), tot)
         return tot
 
     def loss_and_grads(self, x_nhwc, y_true: Sequence["torch.Tensor"]):
@@ -577,9 +548,7 @@ class Trainer:
 
     def apply_update(self) -> None:
         """keras Adam(lr, decay) on the flat buffers (keras_train.py:73-76); one launch."""
-        self._ck(self.L.yk_adam_f32(C.c_longlong(self.n_params), engine._ptr(self.P), engine._ptr(self.G), engine._ptr(self.m),
-                                    engine._ptr(self.v), C.c_float(self.lr), C.c_float(self.decay), C.c_longlong(self.iterations),
-                                    C.c_float(0.9), C.c_float(0.999), C.c_float(1e-7), C.c_float(1.0), self._s()), 'yk_adam_f32')
+        self._ck('yk_adam_f32', self.n_params, self.P, self.G, self.m, self.v, self.lr, self.decay, self.iterations, 0.9, 0.999, 1e-7, 1.0)
         self.iterations += 1
 
     # ------------------------------------------------------------------ magnitude pruning (DESIGN.md 3.8)
@@ -593,7 +562,7 @@ class Trainer:
         if not self._pr_names:
             raise engine.YkError('pruning: the network has no Conv2D kernel')
         self.prune.check(self._pr_sizes)
-        tile = int(self.L.yk_prune_tile())                                      # YK_PRUNE_TILE of the loaded library
+        tile = engine.lib().yk_prune_tile()                                      # YK_PRUNE_TILE of the loaded library
         first = np.concatenate([[0], np.cumsum([(n + tile - 1) // tile for n in self._pr_sizes])])
         assert all(o >= 0 and o + n <= self.n_params for o, n in zip(offs, self._pr_sizes)) and first[-1] < 2 ** 31
         dev = lambda a, dt: torch.from_numpy(np.asarray(a, dt)).to(self.dev)
@@ -625,16 +594,13 @@ class Trainer:
         self._pr_keep.copy_(self._pr_keep_host, non_blocking=True)
         self._pr_keep_sent = self.torch.cuda.Event()
         self._pr_keep_sent.record()
-        self._ck(self.L.yk_prune_masks_f32(engine._ptr(self.P), engine._ptr(self._pr_off), engine._ptr(self._pr_size),
-                                           engine._ptr(self._pr_keep), engine._ptr(self._pr_first), C.c_int(len(self._pr_sizes)),
-                                           C.c_int(self._pr_ntiles), engine._ptr(self._pr_mask), engine._ptr(self._pr_thr),
-                                           engine._ptr(self._pr_kept), self._s()), 'yk_prune_masks_f32')
+        self._ck('yk_prune_masks_f32', self.P, self._pr_off, self._pr_size, self._pr_keep, self._pr_first, len(self._pr_sizes), self._pr_ntiles,
+                 self._pr_mask, self._pr_thr, self._pr_kept)
 
     def apply_masks(self) -> None:
         """P *= mask, in place (tfmot's weight assignment at the start of a step and its on_epoch_end)."""
         self._need_prune()
-        self._ck(self.L.yk_mask_apply_f32(engine._ptr(self.P), engine._ptr(self._pr_mask), C.c_longlong(self.n_params), self._s()),
-                 'yk_mask_apply_f32')
+        self._ck('yk_mask_apply_f32', self.P, self._pr_mask, self.n_params)
 
     def prune_step(self) -> None:
         """What pruning does at the start of step `iterations`: new masks on an update step, then P *= mask.  Outside the captured
@@ -675,12 +641,12 @@ class Trainer:
         self._qa_kind_d, self._qa_p0_d, self._qa_p1_d = dev(kind, np.int32), dev(p0, np.int32), dev(p1, np.int32)
         self._qa_ranges = dev(np.tile(np.array([np.inf, -np.inf], np.float32), n), np.float32)       # nothing seen yet
         self._qa_batch = torch.zeros(4 * n, dtype=torch.int32, device=self.dev)                      # YK_RANGE_WORDS per slot
-        self._ck(self.L.yk_range_reset(engine._ptr(self._qa_batch), C.c_int(n), self._s()), 'yk_range_reset')
+        self._ck('yk_range_reset', self._qa_batch, n)
         self.Pq = torch.zeros_like(self.P)
         names = [l.name + '/kernel' for l in self.spec.layers]
         offs = [self.slots[nm][0] for nm in names]
         sizes = [int(np.prod(self.slots[nm][1])) for nm in names]
-        tile = int(self.L.yk_qat_tile())
+        tile = engine.lib().yk_qat_tile()
         first = np.concatenate([[0], np.cumsum([(s + tile - 1) // tile for s in sizes])])
         assert all(o >= 0 and s >= 1 and o + s <= self.n_params for o, s in zip(offs, sizes)) and first[-1] < 2 ** 31
         self._qa_off, self._qa_size, self._qa_first = dev(offs, np.int64), dev(sizes, np.int64), dev(first, np.int32)
@@ -694,28 +660,24 @@ class Trainer:
 
     def _qat_weights(self) -> None:
         """Pq = P with every conv / depthwise kernel replaced by fq over its own [min, max]: one library call, three launches."""
-        self._ck(self.L.yk_qat_weights_f32(engine._ptr(self.P), C.c_longlong(self.n_params), engine._ptr(self._qa_off), engine._ptr(self._qa_size),
-                                           engine._ptr(self._qa_first), C.c_int(self._qa_nseg), C.c_int(self._qa_ntiles), engine._ptr(self.Pq),
-                                           engine._ptr(self._qa_wrange), self._s()), 'yk_qat_weights_f32')
+        self._ck('yk_qat_weights_f32', self.P, self.n_params, self._qa_off, self._qa_size, self._qa_first, self._qa_nseg, self._qa_ntiles, self.Pq,
+                 self._qa_wrange)
 
     def _qat_out(self, i, slot, y, S, observe):
         """Tensor `slot`, the output of op i: folded into the batch extremes only (observe), or fake-quantised over the slot's range into a
         new tensor while y stays on the tape for the backward kernel."""
         if observe:
-            self._ck(self.L.yk_range_f32(engine._ptr(y), C.c_longlong(y.numel()), engine._ptr(self._qa_batch), C.c_int(slot), self._s()),
-                     'yk_range_f32')
+            self._ck('yk_range_f32', y, y.numel(), self._qa_batch, slot)
             return y
         yq = self.torch.empty_like(y)
-        self._ck(self.L.yk_qat_act_fwd_f32(engine._ptr(y), C.c_longlong(y.numel()), engine._ptr(self._qa_ranges), C.c_int(slot), engine._ptr(yq),
-                                           engine._ptr(self._qa_batch), self._s()), 'yk_qat_act_fwd_f32')
+        self._ck('yk_qat_act_fwd_f32', y, y.numel(), self._qa_ranges, slot, yq, self._qa_batch)
         S.setdefault(i, {})['qy'] = y
         return yq
 
     def _qat_update(self, observe: bool) -> None:
         m = np.float32(self.qat.momentum)
-        self._ck(self.L.yk_qat_update_f32(engine._ptr(self._qa_ranges), engine._ptr(self._qa_batch), engine._ptr(self._qa_kind_d),
-                                          engine._ptr(self._qa_p0_d), engine._ptr(self._qa_p1_d), C.c_int(self._qa_n), C.c_float(m),
-                                          C.c_float(np.float32(1) - m), C.c_int(1 if observe else 0), self._s()), 'yk_qat_update_f32')
+        self._ck('yk_qat_update_f32', self._qa_ranges, self._qa_batch, self._qa_kind_d, self._qa_p0_d, self._qa_p1_d, self._qa_n, float(m),
+                 float(np.float32(1) - m), int(observe))
 
     def qat_observe(self, x_nhwc) -> None:
         """One training-mode forward with no quantisation at all (BatchNorm moving statistics move as in a step); every range is widened

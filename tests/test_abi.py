@@ -14,7 +14,7 @@ LIB = ROOT / 'k210_yolo_framework_amd' / 'csrc' / 'libyolo_hip.so'
 def declared_functions():
     txt = re.sub(r'/\*.*?\*/', '', HEADER.read_text(), flags=re.S)
     txt = re.sub(r'typedef\s+void\s*\(\*\w+\)\s*\([^;]*?\);', '', txt, flags=re.S)   # callback typedef is not an export
-    names = re.findall(r'^\s*(?:const\s+)?(?:int|void|char|size_t)\s*\*?\s*(\w+)\s*\(', txt, flags=re.M)
+    names = re.findall(r'^\s*(?:const\s+)?(?:int|void|char|size_t|unsigned\s+long\s+long)\s*\*?\s*(\w+)\s*\(', txt, flags=re.M)
     return sorted(set(names))
 
 
@@ -139,3 +139,82 @@ def test_schedule_and_precision_constants_match_the_header():
     assert engine.SCHEDULES == {'throughput': val('YK_SCHEDULE_THROUGHPUT'), 'latency': val('YK_SCHEDULE_LATENCY')}
     assert all((v & val('YK_SCHEDULE_MASK')) == v for v in engine.SCHEDULES.values())
     assert all((v & val('YK_SCHEDULE_MASK')) == 0 for v in engine.PRECISIONS.values())
+
+
+# ---- the ctypes signatures are derived from the header (k210_yolo_framework_amd/abi.py) ------------------------------------------------
+
+def test_signatures_cover_exactly_the_declared_functions():
+    from k210_yolo_framework_amd import abi
+    sigs = abi.signatures(HEADER.read_text())
+    assert sorted(sigs) == declared_functions()
+
+
+def test_signatures_spot_checks():
+    from k210_yolo_framework_amd import abi
+    sigs = abi.signatures(HEADER.read_text())
+    ptr, f, ll = abi.DevPtr, C.c_float, C.c_longlong
+    assert sigs['yk_adam_f32'] == (C.c_int, [ll, ptr, ptr, ptr, ptr, f, f, ll, f, f, f, f, ptr])
+    assert sigs['yk_memcpy_async'] == (C.c_int, [ptr, ptr, C.c_size_t, ptr])
+    assert sigs['yk_last_error'] == (C.c_char_p, [])
+    assert sigs['yk_scratch_generation'] == (C.c_ulonglong, [ptr])
+    assert sigs['yk_plan_destroy'] == (None, [ptr])
+    assert sigs['region_layer_draw_boxes'] == (None, [ptr, ptr])
+    assert sigs['yk_plan_peek_error'] == (C.c_int, [ptr, C.c_int, ptr])
+    assert sigs['yk_map_eval'][1][9] is C.c_double
+
+
+def test_signatures_refuse_an_unknown_type():
+    from k210_yolo_framework_amd import abi
+    with pytest.raises(ValueError, match='yk_thing'):
+        abi.signatures('int yk_fine(int a, float *b /* may be NULL */);\nint yk_thing(const float *x, short n);')
+    with pytest.raises(ValueError, match='yk_other'):
+        abi.signatures('short yk_other(int a);')
+    with pytest.raises(ValueError, match='yk_dims'):
+        abi.signatures('int yk_dims(int dims[3]);')                 # an array is a pointer the table does not spell
+    assert abi.signatures('int yk_none();') == abi.signatures('int yk_none(void);') == {'yk_none': (C.c_int, [])}
+    assert abi.signatures('int yk_fine(int a, float *b /* may be NULL */);') == {'yk_fine': (C.c_int, [C.c_int, abi.DevPtr])}
+
+
+def test_engine_lib_sets_every_declared_signature(dll):
+    from k210_yolo_framework_amd import abi, engine
+    L = engine.lib()
+    for name, (restype, argtypes) in abi.signatures(HEADER.read_text()).items():
+        fn = getattr(L, name)
+        assert fn.restype is restype and list(fn.argtypes) == argtypes, name
+
+
+def test_devptr_from_param():
+    import numpy as np
+    import torch
+    from k210_yolo_framework_amd.abi import DevPtr
+    value = lambda v: DevPtr.from_param(v).value or 0              # (c_void_p reads NULL back as None)
+    assert value(None) == 0
+    assert value(0x7f0012345678) == 0x7f0012345678
+    a = np.arange(12, dtype=np.float32).reshape(3, 4)
+    assert value(a) == a.ctypes.data
+    t = torch.arange(12, dtype=torch.float32).reshape(3, 4)
+    assert value(t) == t.data_ptr() and value(t[1:]) == t.data_ptr() + 16
+    ref = C.byref(C.c_int())
+    assert DevPtr.from_param(ref) is ref
+    buf = C.create_string_buffer(8)
+    assert C.cast(DevPtr.from_param(buf), C.c_void_p).value == C.addressof(buf)
+    assert value(C.c_void_p(24)) == 24
+    for bad in (a[:, ::2], a.T, t[:, ::2], t.t()):
+        with pytest.raises(TypeError):
+            DevPtr.from_param(bad)
+    for bad in (1.5, True, np.int64(4096), np.float32(1)):
+        with pytest.raises(TypeError):
+            DevPtr.from_param(bad)
+
+
+def test_a_wrapper_of_the_wrong_width_is_refused_before_the_call(dll):
+    from k210_yolo_framework_amd import engine
+    L = engine.lib()
+    with pytest.raises(C.ArgumentError):
+        L.yk_axpy_f32(C.c_int(4), 1.0, None, None, None)            # n is long long
+    with pytest.raises(C.ArgumentError):
+        L.yk_memcpy_async(None, None, C.c_int(4), None)             # bytes is size_t
+    with pytest.raises(C.ArgumentError):
+        L.yk_run_u8(None, None, 1.5, None)                          # batch is int
+    assert str(2 ** 40) in repr(C.c_longlong.from_param(2 ** 40))   # <cparam 'q' (1099511627776)>: all 64 bits
+    assert L.yk_axpy_f32.argtypes[0] is C.c_longlong

@@ -12,13 +12,9 @@ for _ in range(10):
     tr.step(x, y)
 torch.cuda.synchronize()
 print('eager ms/step', (time.perf_counter() - t0) / 10 * 1e3)
-import ctypes as C
-from k210_yolo_framework_amd import engine
 def body():
     r = tr.loss_and_grads(x, y)
-    tr._ck(tr.L.yk_adam_f32(C.c_longlong(tr.n_params), engine._ptr(tr.P), engine._ptr(tr.G), engine._ptr(tr.m), engine._ptr(tr.v),
-                            C.c_float(tr.lr), C.c_float(tr.decay), C.c_longlong(tr.iterations), C.c_float(0.9), C.c_float(0.999),
-                            C.c_float(1e-7), C.c_float(1.0), tr._s()), 'adam')
+    tr._ck('yk_adam_f32', tr.n_params, tr.P, tr.G, tr.m, tr.v, tr.lr, tr.decay, tr.iterations, 0.9, 0.999, 1e-7, 1.0)
     return r
 s = torch.cuda.Stream()
 s.wait_stream(torch.cuda.current_stream())
