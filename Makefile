@@ -20,6 +20,8 @@
 #                    labels drawn on the GPU; ENCODE=gpu also JPEG-encodes them there at QUALITY, ENCODE=pil leaves that to PIL on the host;
 #                    DECODE=gpu decodes baseline JPEG files there too, by the project's own integer rule, every other file by PIL)
 #   make anchors     DATASET=voc ANCNUM=3 [LOW='0.0 0.0' HIGH='1.0 1.0']   (reference Makefile:78-87: k-means anchors from data/<set>_img_ann.npy)
+#                    [ANCDEVICE=gpu RESTARTS=256 ANCSEED=0]: RESTARTS random starts in one GPU call; the set with the highest mean IoU is
+#                    kept and that IoU printed (ANCDEVICE=cpu RESTARTS=N loops the same rule in numpy)
 
 PY            ?= python3
 MODEL         ?= yolo_mobilev1
@@ -76,6 +78,9 @@ GPUS          ?= 1
 ANCNUM        ?= 3
 LOW           ?= 0.0 0.0
 HIGH          ?= 1.0 1.0
+ANCDEVICE     ?= cpu
+RESTARTS      ?= 1
+ANCSEED       ?=
 
 NET_ARGS   = --train_set $(DATASET) --class_num $(CLSNUM) --model_def $(MODEL) --depth_multiplier $(DEPTHMUL) \
              --image_size $(IMGSIZE) --output_size $(OUTSIZE) --obj_thresh $(OBJTHRESH) --iou_thresh $(IOUTHRESH)
@@ -129,4 +134,4 @@ detect:
 # reference Makefile:78-87 (same flags; --is_random True as there)
 anchors:
 	$(PY) ./make_anchor_list.py $(DATASET) --max_iters 10 --is_random True --in_hw $(IMGSIZE) --out_hw $(OUTSIZE) --anchor_num $(ANCNUM) \
-		--low $(LOW) --high $(HIGH)
+		--low $(LOW) --high $(HIGH) --device $(ANCDEVICE) --restarts $(RESTARTS) $(if $(ANCSEED),--seed $(ANCSEED))

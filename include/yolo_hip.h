@@ -681,6 +681,24 @@ int yk_map_eval(const float *d_rows, const int32_t *d_img, long long n_rows, int
                 size_t work_bytes, uint8_t *d_flags, int32_t *d_n_gt, int32_t *d_n_det, int32_t *d_tp, int32_t *d_fp, double *d_ap, double *d_map,
                 void *stream);
 
+/* ---- anchor k-means with many restarts in one call (datatools.run_kmeans_gpu): datatools.run_kmeans for each of
+ * `restarts` initial centroid sets, independently, on boxes d_wh [n][2] (w, h; finite and > 0, which the caller has checked).  Distance
+ * 1 - IoU of boxes centred at the origin, float64 in datatools.fake_iou_distance's operation order without contraction; assignment = argmin,
+ * the lowest index on a tie; update = sum / count per cluster, summed in an order that (n, k) alone fix (no floating-point atomics), so two
+ * calls on the same inputs give the same bits.
+ * d_init [restarts][k][2] -> d_centroids [restarts][k][2] (may be the same buffer), d_counts [restarts][k] and d_idx [restarts][n] (or
+ * NULL): the assignment of the last iteration, the one the returned centroids are the means of; d_score [restarts]: the mean over the boxes
+ * of the best IoU against the returned centroids.  A restart in which a cluster has no member at iteration i (from 0) gets d_empty = i + 1
+ * (else 0), NaN in that centroid row and a NaN score, and stops there: its other rows, counts and idx are those of iteration i (numpy
+ * would go on and assign every box to the NaN column; that is not reproduced).
+ * d_work: 16-byte aligned device scratch of yk_anchor_kmeans_workspace_bytes (needs no device), contents undefined before and after.
+ * Every launch is on `stream`; nothing is allocated and nothing synchronises.  k outside 1 .. 32, n outside 1 .. 2^24, restarts outside
+ * 1 .. 4096, iters outside 1 .. 1000, a NULL pointer, a d_wh or d_work that is not 16-byte aligned, a workspace that is too small:
+ * YK_ERR_ARG, with the argument named in yk_last_error. */
+int yk_anchor_kmeans_workspace_bytes(long long n, int k, int restarts, size_t *bytes);
+int yk_anchor_kmeans_f64(const double *d_wh, long long n, const double *d_init, int k, int restarts, int iters, double *d_centroids,
+                         int32_t *d_counts, double *d_score, int32_t *d_empty, uint8_t *d_idx, void *d_work, size_t work_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
