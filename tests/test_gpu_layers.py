@@ -7,71 +7,13 @@ fp16 flip on a small fraction of elements:
     and fewer than 2 % of the elements differ at all; fp32 network outputs: <= 1e-4*|ref| + 1e-4*rms(ref).
 Covers: stem (u8 + normalise LUT), fused dw3x3+pw1x1 (all four tile configs), standalone dw, implicit-GEMM
 1x1/3x3 incl. split-K, upsample+concat loader, residual Add epilogue, stride-2 top/left pad, max pools, fp32 heads."""
-import os
-
 import numpy as np
 import pytest
 
-import oracle
 from k210_yolo_framework_amd import netspec as ns
+from tests.layerwise import _layerwise_f16 as _layerwise             # shared with tests/test_gpu_plan_zoo.py
 
 pytestmark = pytest.mark.gpu
-
-
-def _layerwise(spec, w, B, fuse=True, splitk=True, seed=0):
-    import torch
-    from k210_yolo_framework_amd import engine
-    os.environ['YK_FUSE_DWPW'] = '1' if fuse else '0'
-    os.environ['YK_SPLITK'] = '1' if splitk else '0'
-    frames = np.random.default_rng(seed).integers(0, 256, (B, *spec.in_hw, 3), dtype=np.uint8)
-    plan = engine.Plan(spec, w, max_batch=B, precision='f16')
-    plan.run_u8(torch.from_numpy(frames).cuda())
-    torch.cuda.synchronize()
-    gpu = {0: oracle.normalise_u8(frames)}
-    for op in spec.ops:
-        if op['type'] in (ns.OP_UPSAMPLE, ns.OP_CONCAT):
-            continue
-        try:
-            gpu[op['out']] = plan.read_tensor(op['out'], B)
-        except engine.YkError:
-            pass                                   # fused away: lives only in LDS / registers
-    names = [l[0] for l in plan.launches()]
-    plan.close()
-    cp = spec.compile_plan(w)
-    producer = {op['out']: i for i, op in enumerate(spec.ops)}
-    checked, worst = 0, 0.0
-    for i, op in enumerate(spec.ops):
-        t = op['out']
-        if t not in gpu or op['type'] in (ns.OP_UPSAMPLE, ns.OP_CONCAT):
-            continue
-        rows, inputs = [], {}
-
-        def need(tid):
-            if tid in gpu and tid != t:
-                inputs[tid] = gpu[tid]
-                return
-            j = producer[tid]
-            o = spec.ops[j]
-            need(o['in0'])
-            if o['in1'] >= 0:
-                need(o['in1'])
-            if j not in rows:
-                rows.append(j)
-        need(t)
-        ref = oracle.net_forward_ex(cp, inputs, sorted(rows), [t], emulate_f16=True)[0]
-        got = gpu[t]
-        rms = float(np.sqrt((ref.astype(np.float64) ** 2).mean()))
-        err = np.abs(got - ref)
-        is_out = t in spec.outputs                  # network outputs are fp32: no fp16 rounding to flip
-        bound = (1e-4 * np.abs(ref) + 1e-4 * rms) if is_out else (2.0 ** -9 * np.abs(ref) + 1e-3 * rms)
-        bad = err > bound
-        frac = 0.0 if is_out else float((got != ref).mean())
-        assert not bad.any(), (f'op {i} {op.get("layer")} tensor {t} ({len(rows)} ops): {int(bad.sum())} elements beyond 1 ulp; '
-                               f'max err {float(err.max()):.4g}, rms {rms:.4g}')
-        assert frac < 0.02, f'op {i} {op.get("layer")}: {frac:.3%} of elements differ'
-        worst = max(worst, float((err / np.maximum(bound, 1e-30)).max()))
-        checked += 1
-    return checked, names
 
 
 @pytest.mark.parametrize('fuse,splitk', [(True, True), (False, False)])

@@ -19,132 +19,14 @@ the 2^16 of DESIGN section 2.
 Oracle time (float64, 16 host threads; measured): the whole file 35 s; Darknet-53 at 416x416, one image, all 75 tensors 3.8 s, the
 B = 32 plans 9 s each - so every tensor of every plan is checked, none sampled.  Measured worst error / E per plan (one MI355X):
 yolo_mobilev1 0.12 - 0.15 (cluster launches 0.03), yolo_mobilev2 0.29, tiny_yolo 0.09, Darknet-53 0.15 / 0.17."""
-import os
-import re
 import time
 
-import numpy as np
 import pytest
 
 from k210_yolo_framework_amd import netspec as ns
-from oracle import x2_bound as xb
+from tests.layerwise import _layerwise, _report                      # shared with tests/test_gpu_plan_zoo.py
 
 pytestmark = pytest.mark.gpu
-
-SWITCHES = ('YK_FUSE_DWPW', 'YK_SPLITK', 'YK_FUSE_HEAD', 'YK_CLUSTER_WT')
-
-
-def _frames(spec, B, seed):
-    """Random u8 frames; per batch one dark image (// 20), one whose maximum is below 255, one with a saturated block over a dim rest:
-    the per-image exponents differ inside a batch."""
-    H, W = spec.in_hw
-    f = np.random.default_rng(seed).integers(0, 256, (B, H, W, 3), dtype=np.uint8)
-    f[0] //= 20
-    k = 1 % B
-    f[k] = np.minimum(f[k], 200)
-    k = 2 % B
-    top = int(f[k].max())
-    f[k] //= 3
-    f[k, H // 4:H // 2, W // 4:W // 2] = top
-    return f
-
-
-def _stored_outputs(name):
-    """How many tensors a launch leaves in memory, from its name in the launch list."""
-    if name == 'u8_max':
-        return 0
-    if name.startswith('x:heads['):
-        return name.count(' | ') + 1                                  # every phase stores its tensor or the output of its 1x1 tail
-    m = re.match(r'x:persist\[(\d+) blocks.*?,(\d+) phases', name)
-    if m:
-        return int(m.group(2)) - 1 - 2 * int(m.group(1))              # phases = load + (dw, pw) per block + stores
-    return 1
-
-
-def _layerwise(spec, w, B, schedule='throughput', env=None, f32_entry=False, seed=0):
-    """-> (launch names, [(launch name, tensor, op index, error / E)], worst over-estimate)."""
-    import torch
-    from k210_yolo_framework_amd import engine
-    saved = {k: os.environ.get(k) for k in SWITCHES}
-    for k in SWITCHES:
-        os.environ.pop(k, None)
-    os.environ.update(env or {})
-    try:
-        frames = _frames(spec, B, seed)
-        plan = engine.Plan(spec, w, max_batch=B, precision='f16x2', schedule=schedule)
-        x0 = frames.astype(np.float64) / frames.reshape(B, -1).max(1).astype(np.float64).reshape(B, 1, 1, 1)
-        if f32_entry:
-            x32 = x0.astype(np.float32)
-            x0 = x32.astype(np.float64)
-            plan.run_f32(torch.from_numpy(x32).cuda())
-        else:
-            plan.run_u8(torch.from_numpy(frames).cuda())
-        plan.check()
-        gpu, fmt = {0: x0}, {}
-        readers = {}
-        for op in spec.ops:
-            for t in (op['in0'], op['in1']):
-                if t >= 0:
-                    readers.setdefault(t, []).append(op['type'])
-        over = 0.0
-        for op in spec.ops:
-            t = op['out']
-            if op['type'] in (ns.OP_UPSAMPLE, ns.OP_CONCAT):
-                continue                                               # views: a consumer reads their sources
-            try:
-                v = plan.read_tensor(t, B)
-            except engine.YkError as e:
-                if 'fused away' in str(e) or 'folded away' in str(e):
-                    continue                                           # lives only in LDS / registers
-                raise
-            assert np.isfinite(v).all(), f'tensor {t} ({op.get("layer")}): non-finite read-back'
-            gpu[t] = v
-            if t in spec.outputs:
-                fmt[t] = ('f32',)
-                continue
-            e = plan.read_exponents(t, B)
-            if readers.get(t) == [ns.OP_DWCONV] and not e.any() and not xb.is_split(v, e).all():
-                fmt[t] = ('f32',)                                      # fp32 planes: exponent 0 and values no (hi, lo) pair can hold
-                continue
-            ok, o, msg = xb.split_health(v, e)
-            assert ok, f'tensor {t} ({op.get("layer")}): {msg}; exponents {e.tolist()}'
-            assert xb.is_split(v, e).all(), f'tensor {t} ({op.get("layer")}): a read-back value is not hi + lo at its exponent'
-            over = max(over, o)
-            fmt[t] = ('split', e)
-        names = [l[0] for l in plan.launches()]
-        plan.close()
-    finally:
-        for k, v in saved.items():
-            os.environ.pop(k, None)
-            if v is not None:
-                os.environ[k] = v
-    expect = sum(_stored_outputs(n) for n in names)
-    stored = [op['out'] for op in spec.ops if op['out'] in fmt]
-    assert len(stored) == expect, (f'{expect} stored tensors according to the launch list, {len(stored)} could be read', names)
-    owner = [n for n in names for _ in range(_stored_outputs(n))]       # launches and stored tensors both come in issue order
-    producer = {op['out']: i for i, op in enumerate(spec.ops)}
-    rows = []
-    for name, t in zip(owner, stored):
-        idx, ins = xb.launch_chain(spec, set(gpu), t)
-        f = {t: fmt[t]}
-        for i in idx[:-1]:                                             # inner tensors an in-chain conv reads: split at an unstored exponent
-            o = spec.ops[i]
-            if o['type'] in (ns.OP_CONV, ns.OP_DWCONV) and any(spec.ops[j]['type'] in (ns.OP_CONV, ns.OP_DWCONV) and
-                                                               o['out'] in (spec.ops[j]['in0'], spec.ops[j]['in1']) for j in idx):
-                f[o['out']] = ('inner',)
-        Y, E = xb.run_chain(spec, w, {i: gpu[i] for i in ins}, idx, f)
-        r, at = xb.compare(gpu[t], Y[t], E[t])
-        rows.append((name, t, producer[t], r))
-        assert r <= 1.0, (f'launch {name!r}: op {producer[t]} ({[spec.ops[i].get("layer") or spec.ops[i]["type"] for i in idx]}) tensor {t}: '
-                          f'error / E = {r:.3g} at element [b, y, x, c] = {at}: gpu {gpu[t][at]!r}, ref {Y[t][at]!r}, E {E[t][at]:.3g}')
-    return names, rows, over
-
-
-def _report(title, names, rows, over, t0):
-    print(f'\n{title}: {len(names)} launches, {len(rows)} tensors checked, worst error / E = {max(r[3] for r in rows):.3f}, '
-          f'worst over-estimate 2^{np.log2(max(over, 1)):.1f}, {time.time() - t0:.1f} s')
-    for name, t, i, r in rows:
-        print(f'    {r:6.3f}  op {i:3d} tensor {t:3d}  {name}')
 
 
 def _mobilev1():
