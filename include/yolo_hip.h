@@ -494,7 +494,8 @@ int yk_dw3x3_bwd_weight_grouped_f32(int count, const float *const *x, const floa
 /* BatchNormalization(training=True) fused with the activation that follows it (act: YK_ACT_*).
  * fwd: batch mean / biased variance over M, y = act(gamma*(z-mean)*invstd + beta); saves mean and invstd and,
  *      when moving_mean/moving_var are given, updates them with `momentum` (Keras: 0.99).
- * bwd: dy is the gradient w.r.t. y; writes dz, dgamma, dbeta. */
+ * bwd: dy is the gradient w.r.t. y; writes dz, dgamma, dbeta (all three are required).  A NULL pointer, M <= 0 or C <= 0: YK_ERR_ARG,
+ *      checked on the host before anything is launched. */
 int yk_bn_train_fwd_f32(const float *z, long long M, int C, const float *gamma, const float *beta, float eps, int act,
                         float alpha, float *y, float *save_mean, float *save_invstd, float *moving_mean,
                         float *moving_var, float momentum, void *stream);

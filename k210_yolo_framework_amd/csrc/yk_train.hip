@@ -943,7 +943,7 @@ __global__ void __launch_bounds__(256) bn_bwd_finish_kernel(const float *__restr
     b = wave_sum(b);
     if (lane == 0) {
         dbeta[c] = a;
-        if (dgamma) dgamma[c] = b;
+        dgamma[c] = b;
     }
 }
 template <int V>
@@ -1144,7 +1144,7 @@ __global__ void __launch_bounds__(1024) bn_bwd_cols_kernel(const float *__restri
     }
     if (rl == 0) {
         stv<4>(dbeta + c, db);
-        if (dgamma) stv<4>(dgamma + c, dg);
+        stv<4>(dgamma + c, dg);
     }
 #pragma unroll
     for (int r = 0; r < R; ++r) {
@@ -1266,9 +1266,13 @@ static int bn_train_fwd(const float *z, long long M, int C, const float *gamma, 
 extern "C" int yk_bn_train_bwd_f32(const float *z, const float *dy, long long M, int C, const float *gamma, const float *beta,
                                    const float *save_mean, const float *save_invstd, int act, float alpha, float *dz, float *dgamma,
                                    float *dbeta, void *stream) {
+    if (!z || !dy || !gamma || !beta || !save_mean || !save_invstd || !dz || !dgamma || !dbeta || M <= 0 || C <= 0) {
+        yk_set_error("yk_bn_train_bwd_f32: bad argument");
+        return YK_ERR_ARG;
+    }
     int dev = yk_current_device();
     if (dev < 0) return YK_ERR_NO_DEVICE;
-    if (bn_cols_ok(M, C, z, dy, dz) && dgamma && (((uintptr_t)dgamma | (uintptr_t)dbeta | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)save_mean | (uintptr_t)save_invstd) & 15) == 0) {
+    if (bn_cols_ok(M, C, z, dy, dz) && (((uintptr_t)dgamma | (uintptr_t)dbeta | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)save_mean | (uintptr_t)save_invstd) & 15) == 0) {
         hipLaunchKernelGGL(bn_bwd_cols_kernel<3>, dim3((C + 7) / 8), dim3(1024), 0, (hipStream_t)stream, z, dy, (int)M, C, 1.f / (float)M, save_mean,
                            save_invstd, gamma, beta, act, alpha, dz, dgamma, dbeta);
         YK_HIP(hipGetLastError());
