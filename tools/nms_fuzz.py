@@ -3,6 +3,7 @@ score quantisation (ties), thresholds and max_out on both sides of every path sw
 max_out 64).  Development tool - the cases that found something go into tests/test_gpu_decode.py.  Round 6: 135 k cases, no logic mismatch;
 what differs is decided by the last bit of a score (two near-tied boxes swap: counted apart) or by an IoU AT the threshold (one in ~70 k cases:
 the box coordinates differ from numpy's in the last bit, which the 1e-3 tolerance of the boxes allows).
+The path-by-path suite on exact inputs, where none of that luck is left, is tests/nms_cases.py + tests/test_gpu_nms_paths.py.
     python tools/nms_fuzz.py [seconds=120] [seed=0]"""
 import os, sys, time
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
