@@ -447,6 +447,22 @@ typedef struct {
 } yk_loss_cfg_t;
 int yk_yolo_loss(const yk_loss_cfg_t *cfg, const float *d_y_true, const float *d_y_pred, int batch, float *d_loss,
                  float *d_grad, float *d_ignore, float *d_counts, void *stream);
+/* The same loss with a choice of box term.  YK_BOX_LOSS_MSE: the xy / wh terms above, the same bits as yk_yolo_loss.
+ * _GIOU / _DIOU / _CIOU: for every object cell (y_true conf > obj_thresh) the IoU-family loss l between the decoded prediction and the
+ * label box, weighted conf * (2 - tw * th) * box_weight; xy, wh and their gradients are then not computed: both report 0 and
+ * total = obj + noobj + cls + box.  Cells without an object add exactly 0 to the box term and to gradient entries 0..3.
+ * d_loss[7] = {total, xy, wh, obj, noobj, cls, box}; the other pointers as for yk_yolo_loss.  An unknown box_loss: YK_ERR_ARG. */
+enum { YK_BOX_LOSS_MSE = 0, YK_BOX_LOSS_GIOU = 1, YK_BOX_LOSS_DIOU = 2, YK_BOX_LOSS_CIOU = 3 };
+typedef struct {
+    int32_t out_h, out_w, anchor_num, class_num;       /* yk_loss_cfg_t's fields, in its order ... */
+    float anchors[YK_MAX_ANCHORS][2];
+    float obj_thresh, iou_thresh, obj_weight, noobj_weight, wh_weight;
+    int32_t batch_size;
+    int32_t box_loss;                                   /* ... then YK_BOX_LOSS_* */
+    float box_weight;                                   /* weight of the box term (wh_weight is not used by the IoU losses) */
+} yk_loss_cfg_ex_t;
+int yk_yolo_loss_ex(const yk_loss_cfg_ex_t *cfg, const float *d_y_true, const float *d_y_pred, int batch, float *d_loss,
+                    float *d_grad, float *d_ignore, float *d_counts, void *stream);
 
 /* ---- training step, network level (keras_train.py:73-98: model.fit = forward in training mode + TF autodiff +
  *      Adam; the reference gets every one of these ops from TensorFlow 1.14).  All tensors are device fp32, NHWC,

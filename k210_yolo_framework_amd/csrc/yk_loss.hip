@@ -11,25 +11,99 @@
 // compacted into LDS, (2) every prediction is decoded, matched against them (best IoU), contributes its five
 // loss terms and writes its 5+C gradient entries, (3) a block reduction in fp64 produces per-image partials;
 // a second tiny kernel adds the partials in image order (deterministic).
+//
+// Box term: the reference's xy / wh terms (YK_BOX_LOSS_MSE, the default) or, opt-in, one of the IoU-family losses between
+// the decoded prediction and the label box: GIoU (Rezatofighi et al. 2019), DIoU / CIoU (Zheng et al. 2020).  The mode is a template
+// parameter of the kernel: the MSE instance is the kernel as it was, the others replace the xy / wh arithmetic of an object cell.
 #include "yk_common.h"
 
 #define YK_LOSS_MAXGT 1024
+#define YK_LOSS_COLS 9   // float64 columns of a partial: xy, wh, obj, noobj, cls, tp, fp, fn, box
 
 struct loss_args {
     int h, w, A, C, E, batch_size;
     float anchors[YK_MAX_ANCHORS][2];
     float obj_thresh, iou_thresh, obj_w, noobj_w, wh_w;
+    int box_loss;
+    float box_w;
 };
 
 __device__ __forceinline__ float l_sigmoid(float v) { return 1.f / (1.f + expf(-v)); }
 __device__ __forceinline__ float l_bce(float z, float x) { return fmaxf(x, 0.f) - x * z + log1pf(expf(-fabsf(x))); }
 
+// 0.5 at a tie: where two edges coincide the loss has a kink, and the even split is the one sub-gradient that is zero for equal boxes
+__device__ __forceinline__ float l_less(float u, float v) { return u < v ? 1.f : (u == v ? 0.5f : 0.f); }
+
+// One axis of two boxes given as centre c / size s (prediction b, label t): the clamped overlap ov and the enclosing extent en, with
+// their derivatives by the prediction's centre (.._c) and size (.._s).
+struct l_axis {
+    float ov, ov_c, ov_s, en, en_c, en_s;
+};
+__device__ __forceinline__ l_axis l_box_axis(float bc, float bs, float tc, float ts) {
+    const float b1 = bc - bs / 2.f, b2 = bc + bs / 2.f, t1 = tc - ts / 2.f, t2 = tc + ts / 2.f;
+    const float raw = fminf(b2, t2) - fmaxf(b1, t1);
+    const float on = raw > 0.f ? 1.f : 0.f;
+    const float i2 = on * l_less(b2, t2), i1 = on * l_less(t1, b1);      // d ov / d b2, -d ov / d b1
+    const float e2 = l_less(t2, b2), e1 = l_less(b1, t1);                // d en / d b2, -d en / d b1
+    l_axis r;
+    r.ov = fmaxf(raw, 0.f);
+    r.ov_c = i2 - i1;
+    r.ov_s = (i2 + i1) / 2.f;
+    r.en = fmaxf(b2, t2) - fminf(b1, t1);
+    r.en_c = e2 - e1;
+    r.en_s = (e2 + e1) / 2.f;
+    return r;
+}
+
+// IoU-family loss of one object cell and its gradient g = d loss / d (bx, by, bw, bh); alpha of CIoU is a constant.
+template <int MODE>
+__device__ __forceinline__ float l_box_loss(float bx, float by, float bw, float bh, float tx, float ty, float tw, float th, float g[4]) {
+    const float eps = 1e-7f;
+    const l_axis X = l_box_axis(bx, bw, tx, tw), Y = l_box_axis(by, bh, ty, th);
+    const float I = X.ov * Y.ov;
+    const float U = bw * bh + tw * th - I + eps;
+    const float iou = I / U;
+    const float dI[4] = {Y.ov * X.ov_c, X.ov * Y.ov_c, Y.ov * X.ov_s, X.ov * Y.ov_s};
+    const float dU[4] = {-dI[0], -dI[1], bh - dI[2], bw - dI[3]};
+    float l = 1.f - iou;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) g[k] = -(dI[k] - iou * dU[k]) / U;
+    if (MODE == YK_BOX_LOSS_GIOU) {
+        const float Cc = X.en * Y.en + eps, r = U / Cc;
+        const float dC[4] = {Y.en * X.en_c, X.en * Y.en_c, Y.en * X.en_s, X.en * Y.en_s};
+        l += (Cc - U) / Cc;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) g[k] -= (dU[k] - r * dC[k]) / Cc;
+    } else {
+        const float c2 = X.en * X.en + Y.en * Y.en + eps;
+        const float dx = bx - tx, dy = by - ty, r = (dx * dx + dy * dy) / c2;
+        const float dc2[4] = {2.f * X.en * X.en_c, 2.f * Y.en * Y.en_c, 2.f * X.en * X.en_s, 2.f * Y.en * Y.en_s};
+        l += r;
+        g[0] += (2.f * dx - r * dc2[0]) / c2;
+        g[1] += (2.f * dy - r * dc2[1]) / c2;
+        g[2] -= r * dc2[2] / c2;
+        g[3] -= r * dc2[3] / c2;
+        if (MODE == YK_BOX_LOSS_CIOU) {
+            const float k4 = 0.40528473456935109f;                       // 4 / pi^2
+            const float d = atanf(tw / th) - atanf(bw / bh);
+            const float v = k4 * d * d;
+            const float alpha = v / (1.f - iou + v + eps);
+            const float q = alpha * 2.f * k4 * d / (bw * bw + bh * bh);
+            l += alpha * v;
+            g[2] -= q * bh;
+            g[3] += q * bw;
+        }
+    }
+    return l;
+}
+
+template <int MODE>
 __global__ void __launch_bounds__(256) yolo_loss_kernel(loss_args a, const float *__restrict__ y_true,
                                                         const float *__restrict__ y_pred, float *__restrict__ grad,
                                                         float *__restrict__ ignore_out, double *__restrict__ partial) {
     __shared__ float4 gt[YK_LOSS_MAXGT];
     __shared__ int ngt;
-    __shared__ double red[9][4];
+    __shared__ double red[YK_LOSS_COLS][4];
     // grid (batch, chunks of 256 boxes): one workgroup per image left 16 workgroups on the chip for 41 us; every chunk gathers the image's
     // ground truth itself (a strided scan of P objectness values) and handles one box per thread
     const int b = blockIdx.x, tid = threadIdx.x;
@@ -47,7 +121,7 @@ __global__ void __launch_bounds__(256) yolo_loss_kernel(loss_args a, const float
     __syncthreads();
     const int n = ngt;
     const float inv_bs = 1.f / (float)a.batch_size;
-    double s_xy = 0, s_wh = 0, s_obj = 0, s_noobj = 0, s_cls = 0;
+    double s_xy = 0, s_wh = 0, s_obj = 0, s_noobj = 0, s_cls = 0, s_box = 0;
     int tp = 0, fp = 0, fn = 0;
     for (int p = blockIdx.y * 256 + tid; p < min(P, (int)(blockIdx.y + 1) * 256); p += 256) {
         const float *t = yt + (size_t)p * a.E, *q = yp + (size_t)p * a.E;
@@ -87,8 +161,19 @@ __global__ void __launch_bounds__(256) yolo_loss_kernel(loss_args a, const float
         const float gx = fmaf(tx, (float)a.w, -(float)col), gy = fmaf(ty, (float)a.h, -(float)row);
         const float gw = ob ? logf(tw / a.anchors[an][0]) : 0.f, gh = ob ? logf(th / a.anchors[an][1]) : 0.f;
         const float cw = 2.f - tw * th;
-        s_xy += (double)(obj * cw * (l_bce(gx, px) + l_bce(gy, py)));
-        s_wh += (double)(obj * cw * a.wh_w * ((gw - pw) * (gw - pw) + (gh - ph) * (gh - ph)));
+        float gb[4] = {0.f, 0.f, 0.f, 0.f};     // the IoU modes' gradient entries 0..3
+        if (MODE == YK_BOX_LOSS_MSE) {
+            s_xy += (double)(obj * cw * (l_bce(gx, px) + l_bce(gy, py)));
+            s_wh += (double)(obj * cw * a.wh_w * ((gw - pw) * (gw - pw) + (gh - ph) * (gh - ph)));
+        } else if (ob) {
+            // skipped, not multiplied away, elsewhere: the label box of a cell without an object is all zeros (atan(0 / 0), 0 * NaN)
+            const float k = obj * cw * a.box_w;
+            s_box += (double)(k * l_box_loss<MODE>(ax, ay, aw, ah, tx, ty, tw, th, gb));
+            gb[0] = k * gb[0] * (sx * (1.f - sx) / (float)a.w) * inv_bs;
+            gb[1] = k * gb[1] * (sy * (1.f - sy) / (float)a.h) * inv_bs;
+            gb[2] = k * gb[2] * aw * inv_bs;
+            gb[3] = k * gb[3] * ah * inv_bs;
+        }
         const float bc = l_bce(tc, pc);
         s_obj += (double)(obj * bc);
         s_noobj += (double)((1.f - obj) * ign * bc);
@@ -101,10 +186,15 @@ __global__ void __launch_bounds__(256) yolo_loss_kernel(loss_args a, const float
         }
         s_cls += (double)(obj * cls);
         if (gr) {
-            gr[0] = obj * cw * (sx - gx) * inv_bs;
-            gr[1] = obj * cw * (sy - gy) * inv_bs;
-            gr[2] = obj * cw * a.wh_w * 2.f * (pw - gw) * inv_bs;
-            gr[3] = obj * cw * a.wh_w * 2.f * (ph - gh) * inv_bs;
+            if (MODE == YK_BOX_LOSS_MSE) {
+                gr[0] = obj * cw * (sx - gx) * inv_bs;
+                gr[1] = obj * cw * (sy - gy) * inv_bs;
+                gr[2] = obj * cw * a.wh_w * 2.f * (pw - gw) * inv_bs;
+                gr[3] = obj * cw * a.wh_w * 2.f * (ph - gh) * inv_bs;
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) gr[k] = gb[k];
+            }
             gr[4] = (a.obj_w * obj + a.noobj_w * (1.f - obj) * ign) * (l_sigmoid(pc) - tc) * inv_bs;
         }
         const bool pp = pc > a.obj_thresh;     // custom.py:33: raw logit
@@ -112,32 +202,35 @@ __global__ void __launch_bounds__(256) yolo_loss_kernel(loss_args a, const float
         fp += (!ob && pp);
         fn += (ob && !pp);
     }
-    double v[9] = {s_xy, s_wh, s_obj, s_noobj, s_cls, (double)tp, (double)fp, (double)fn, 0.0};
+    double v[YK_LOSS_COLS] = {s_xy, s_wh, s_obj, s_noobj, s_cls, (double)tp, (double)fp, (double)fn, s_box};
 #pragma unroll
-    for (int k = 0; k < 8; ++k) {
+    for (int k = 0; k < YK_LOSS_COLS; ++k) {
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o, 64);
         if ((tid & 63) == 0) red[k][tid >> 6] = v[k];
     }
     __syncthreads();
-    if (tid < 8) partial[((size_t)b * gridDim.y + blockIdx.y) * 8 + tid] = red[tid][0] + red[tid][1] + red[tid][2] + red[tid][3];
+    if (tid < YK_LOSS_COLS)
+        partial[((size_t)b * gridDim.y + blockIdx.y) * YK_LOSS_COLS + tid] = red[tid][0] + red[tid][1] + red[tid][2] + red[tid][3];
 }
 
-// out_loss = {total, xy, wh, obj, noobj, cls}; counts += {tp, fp, fn}
+// out_loss = {total, xy, wh, obj, noobj, cls} and, for yk_yolo_loss_ex (n_out = 7), box; counts += {tp, fp, fn}
 __global__ void yolo_loss_finish_kernel(loss_args a, int batch, const double *__restrict__ partial, float *__restrict__ out_loss,
-                                        float *__restrict__ counts) {
+                                        float *__restrict__ counts, int n_out) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    double s[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    double s[YK_LOSS_COLS] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     for (int b = 0; b < batch; ++b)
-        for (int k = 0; k < 8; ++k) s[k] += partial[(size_t)b * 8 + k];
+        for (int k = 0; k < YK_LOSS_COLS; ++k) s[k] += partial[(size_t)b * YK_LOSS_COLS + k];
     const double bs = (double)a.batch_size;
-    const double xy = s[0] / bs, wh = s[1] / bs, ob = a.obj_w * s[2] / bs, no = a.noobj_w * s[3] / bs, cl = s[4] / bs;
-    out_loss[0] = (float)(ob + no + cl + xy + wh);   // utils.py:789
+    const double xy = s[0] / bs, wh = s[1] / bs, ob = a.obj_w * s[2] / bs, no = a.noobj_w * s[3] / bs, cl = s[4] / bs, bx = s[8] / bs;
+    out_loss[0] = a.box_loss == YK_BOX_LOSS_MSE ? (float)(ob + no + cl + xy + wh)   // utils.py:789
+                                                : (float)(ob + no + cl + bx);        // xy and wh are not computed: both are 0
     out_loss[1] = (float)xy;
     out_loss[2] = (float)wh;
     out_loss[3] = (float)ob;
     out_loss[4] = (float)no;
     out_loss[5] = (float)cl;
+    if (n_out > 6) out_loss[6] = (float)bx;
     if (counts) {
         counts[0] += (float)s[5];
         counts[1] += (float)s[6];
@@ -145,16 +238,22 @@ __global__ void yolo_loss_finish_kernel(loss_args a, int batch, const double *__
     }
 }
 
-extern "C" int yk_yolo_loss(const yk_loss_cfg_t *cfg, const float *d_y_true, const float *d_y_pred, int batch, float *d_loss,
-                            float *d_grad, float *d_ignore, float *d_counts, void *stream) {
+// both entry points: `who` names the caller in the messages, n_out is the length of d_loss
+static int loss_launch(const char *who, const yk_loss_cfg_ex_t *cfg, int n_out, const float *d_y_true, const float *d_y_pred, int batch,
+                       float *d_loss, float *d_grad, float *d_ignore, float *d_counts, void *stream) {
     if (!cfg || !d_y_true || !d_y_pred || !d_loss || batch <= 0 || cfg->out_h <= 0 || cfg->out_w <= 0 || cfg->anchor_num <= 0 ||
         cfg->anchor_num > YK_MAX_ANCHORS || cfg->class_num <= 0 || cfg->batch_size <= 0) {
-        yk_set_error("yk_yolo_loss: bad argument");
+        yk_set_error("%s: bad argument", who);
+        return YK_ERR_ARG;
+    }
+    const int box_loss = cfg->box_loss;
+    if (box_loss != YK_BOX_LOSS_MSE && box_loss != YK_BOX_LOSS_GIOU && box_loss != YK_BOX_LOSS_DIOU && box_loss != YK_BOX_LOSS_CIOU) {
+        yk_set_error("%s: box_loss %d is none of YK_BOX_LOSS_MSE (0), _GIOU (1), _DIOU (2), _CIOU (3)", who, box_loss);
         return YK_ERR_ARG;
     }
     int dev = yk_current_device();
     if (dev < 0) {
-        yk_set_error("yk_yolo_loss: no HIP device");
+        yk_set_error("%s: no HIP device", who);
         return YK_ERR_NO_DEVICE;
     }
     loss_args a;
@@ -173,12 +272,53 @@ extern "C" int yk_yolo_loss(const yk_loss_cfg_t *cfg, const float *d_y_true, con
     a.obj_w = cfg->obj_weight;
     a.noobj_w = cfg->noobj_weight;
     a.wh_w = cfg->wh_weight;
+    a.box_loss = box_loss;
+    a.box_w = cfg->box_weight;
     const int chunks = (a.h * a.w * a.A + 255) / 256;
-    double *partial = (double *)yk_scratch(dev, stream, 1, sizeof(double) * 8 * batch * chunks);
+    double *partial = (double *)yk_scratch(dev, stream, 1, sizeof(double) * YK_LOSS_COLS * batch * chunks);
     if (!partial) return YK_ERR_NOMEM;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(yolo_loss_kernel, dim3(batch, chunks), dim3(256), 0, st, a, d_y_true, d_y_pred, d_grad, d_ignore, partial);
-    hipLaunchKernelGGL(yolo_loss_finish_kernel, dim3(1), dim3(64), 0, st, a, batch * chunks, partial, d_loss, d_counts);   // (image, chunk) in order
+    const dim3 grid(batch, chunks);
+    switch (box_loss) {
+    case YK_BOX_LOSS_GIOU:
+        hipLaunchKernelGGL(yolo_loss_kernel<YK_BOX_LOSS_GIOU>, grid, dim3(256), 0, st, a, d_y_true, d_y_pred, d_grad, d_ignore, partial);
+        break;
+    case YK_BOX_LOSS_DIOU:
+        hipLaunchKernelGGL(yolo_loss_kernel<YK_BOX_LOSS_DIOU>, grid, dim3(256), 0, st, a, d_y_true, d_y_pred, d_grad, d_ignore, partial);
+        break;
+    case YK_BOX_LOSS_CIOU:
+        hipLaunchKernelGGL(yolo_loss_kernel<YK_BOX_LOSS_CIOU>, grid, dim3(256), 0, st, a, d_y_true, d_y_pred, d_grad, d_ignore, partial);
+        break;
+    default:
+        hipLaunchKernelGGL(yolo_loss_kernel<YK_BOX_LOSS_MSE>, grid, dim3(256), 0, st, a, d_y_true, d_y_pred, d_grad, d_ignore, partial);
+    }
+    hipLaunchKernelGGL(yolo_loss_finish_kernel, dim3(1), dim3(64), 0, st, a, batch * chunks, partial, d_loss, d_counts, n_out);   // (image, chunk) in order
     YK_HIP(hipGetLastError());
     return YK_OK;
+}
+
+extern "C" int yk_yolo_loss(const yk_loss_cfg_t *cfg, const float *d_y_true, const float *d_y_pred, int batch, float *d_loss,
+                            float *d_grad, float *d_ignore, float *d_counts, void *stream) {
+    yk_loss_cfg_ex_t ex;
+    if (cfg) {
+        ex.out_h = cfg->out_h;
+        ex.out_w = cfg->out_w;
+        ex.anchor_num = cfg->anchor_num;
+        ex.class_num = cfg->class_num;
+        memcpy(ex.anchors, cfg->anchors, sizeof(ex.anchors));
+        ex.obj_thresh = cfg->obj_thresh;
+        ex.iou_thresh = cfg->iou_thresh;
+        ex.obj_weight = cfg->obj_weight;
+        ex.noobj_weight = cfg->noobj_weight;
+        ex.wh_weight = cfg->wh_weight;
+        ex.batch_size = cfg->batch_size;
+        ex.box_loss = YK_BOX_LOSS_MSE;
+        ex.box_weight = 0.f;
+    }
+    return loss_launch("yk_yolo_loss", cfg ? &ex : nullptr, 6, d_y_true, d_y_pred, batch, d_loss, d_grad, d_ignore, d_counts, stream);
+}
+
+extern "C" int yk_yolo_loss_ex(const yk_loss_cfg_ex_t *cfg, const float *d_y_true, const float *d_y_pred, int batch, float *d_loss,
+                               float *d_grad, float *d_ignore, float *d_counts, void *stream) {
+    return loss_launch("yk_yolo_loss_ex", cfg, 7, d_y_true, d_y_pred, batch, d_loss, d_grad, d_ignore, d_counts, stream);
 }

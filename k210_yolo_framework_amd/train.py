@@ -20,6 +20,10 @@ Quantisation-aware fine-tuning (qat.py): `Trainer(qat=QatConfig(
 fake-quantised over a range that follows the batches, the backward pass takes the straight-through gradient, and L2 and Adam act on the
 latent P.  All of it is inside the captured graph.  With qat=None nothing is allocated and nothing is launched.
 
+IoU box losses: `Trainer(box_loss='giou' | 'diou' | 'ciou', box_weight=...)` replaces the xy / wh terms of every layer's loss
+by the IoU-family term of csrc/yk_loss.hip (yk_yolo_loss_ex).  Both live in `tr.hyper`, so they are part of the captured step and of its key,
+and the validation pass uses the same loss.  With box_loss='mse' the step calls yk_yolo_loss as before.
+
 fp32 storage and fp32 MFMA throughout (TF1.14's default for this model)."""
 from __future__ import annotations
 
@@ -59,15 +63,17 @@ class Trainer:
     def __init__(self, spec: ns.NetSpec, weights: Dict[str, np.ndarray], anchors: np.ndarray, per_rank_batch: int,
                  obj_thresh: float = 0.7, iou_thresh: float = 0.5, obj_weight: float = 1.0, noobj_weight: float = 1.0,
                  wh_weight: float = 1.0, lr: float = 5e-4, decay: float = 0.0, device: int = 0, process_group=None,
-                 world_size: int = 1, use_graph: bool = True, prune=None, qat=None):
+                 world_size: int = 1, use_graph: bool = True, prune=None, qat=None, box_loss: str = 'mse', box_weight: float = 1.0):
         import torch
+        if box_loss not in engine.BOX_LOSSES:
+            raise ValueError(f'box_loss {box_loss!r}: choose one of ' + ', '.join(repr(k) for k in engine.BOX_LOSSES))
         engine.require_gpu()
         self.torch = torch
         self.spec, self.B = spec, int(per_rank_batch)
         self.dev = torch.device('cuda', device)
         self.anchors = np.asarray(anchors, np.float32)
         self.hyper = dict(obj_thresh=obj_thresh, iou_thresh=iou_thresh, obj_weight=obj_weight, noobj_weight=noobj_weight,
-                          wh_weight=wh_weight)
+                          wh_weight=wh_weight, box_loss=box_loss, box_weight=box_weight)
         self.lr, self.decay, self.iterations = float(lr), float(decay), 0
         self.pg, self.world = process_group, int(world_size)
         self.lay = {l.name: l for l in spec.layers}
@@ -748,15 +754,19 @@ class Trainer:
         if self.world > 1:
             self.exchange(reduce)
         self.apply_update()
-        data = torch.stack([p[0] for p in r['layers']]).sum()
+        iou_box = self.hyper['box_loss'] != 'mse'                     # then the layers' loss[6] is the box term (yk_yolo_loss_ex)
+        data = torch.stack([p[0::6] for p in r['layers']]).sum(0)     # [total] or, of 7 entries, [total, box]
         if self.world > 1:
             if reduce_scalar is not None:
                 reduce_scalar(data)
             else:
                 import torch.distributed as dist
                 dist.all_reduce(data, op=dist.ReduceOp.SUM, group=self.pg)
-        vals = torch.cat([data.view(1), r['reg'].view(1)]).cpu().numpy()
-        return dict(loss=float(vals[0] + vals[1]), data_loss=float(vals[0]), reg_loss=float(vals[1]))
+        vals = torch.cat([data, r['reg'].view(1)]).cpu().numpy()
+        out = dict(loss=float(vals[0] + vals[-1]), data_loss=float(vals[0]), reg_loss=float(vals[-1]))
+        if iou_box:
+            out['box'] = float(vals[1])
+        return out
 
     def precision_recall(self):
         """Yolo_Precision / Yolo_Recall running values per output layer (tools/custom.py:42-44,74-75)."""

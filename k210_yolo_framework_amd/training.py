@@ -21,7 +21,11 @@ the overall and per-head sparsity is printed per epoch (the stand-in for Pruning
 `--qat True` (`make train QAT=True`; qat.py): the kmodel's 8-bit quantisation simulated in the forward pass, straight-through
 gradients in the backward pass.  The first `--qat_observe` (>= 1) batches of epoch 0 only set the activation ranges (no update; an epoch 0
 with fewer batches is observed whole and training starts with epoch 1); afterwards the ranges follow the batches with `--qat_momentum`.  The checkpoint is `yolo_qat_model.h5` / `.npz` (the latent float weights; with
-`--is_prune True` masked) plus `yolo_qat_ranges.npz` (tensor name -> [lo, hi]), which `make kmodel RANGES=` quantises with."""
+`--is_prune True` masked) plus `yolo_qat_ranges.npz` (tensor name -> [lo, hi]), which `make kmodel RANGES=` quantises with.
+
+`--box_loss giou | diou | ciou` (`make train BOXLOSS=ciou`; not in the reference): the IoU-family box term, weighted by
+`--box_weight`, in place of the xy and wh terms, in the training step and in the validation loss alike; the step line and the epoch line
+then name the box term.  The default `mse` is the reference's loss."""
 from __future__ import annotations
 
 import argparse
@@ -86,7 +90,8 @@ def batches(h: Helper, items, batch_size: int, rng, shuffle: bool, augment=None,
 def main(args, train_set, class_num, pre_ckpt, model_def, depth_multiplier, is_augmenter, image_size, output_size, batch_size,
          rand_seed, max_nrof_epochs, init_learning_rate, learning_rate_decay_factor, obj_weight, noobj_weight, wh_weight,
          obj_thresh, iou_thresh, vaildation_split, log_dir, is_prune, initial_sparsity=0.5, final_sparsity=0.9, end_epoch=5,
-         frequency=100, synthetic=0, max_steps=0, is_qat='False', qat_momentum=0.99, qat_observe=8, val_map='False', val_map_obj=0.05):
+         frequency=100, synthetic=0, max_steps=0, is_qat='False', qat_momentum=0.99, qat_observe=8, val_map='False', val_map_obj=0.05,
+         box_loss='mse', box_weight=1.0):
     import torch
     from .train import Trainer
     prune = is_prune == 'True'
@@ -158,13 +163,14 @@ def main(args, train_set, class_num, pre_ckpt, model_def, depth_multiplier, is_a
         qat_cfg = QatConfig(qat_momentum)
     tr = Trainer(spec, weights, h.anchors, per_rank, obj_thresh=obj_thresh, iou_thresh=iou_thresh, obj_weight=obj_weight,
                  noobj_weight=noobj_weight, wh_weight=wh_weight, lr=init_learning_rate, decay=learning_rate_decay_factor, device=local,
-                 world_size=world, prune=schedule, qat=qat_cfg)
+                 world_size=world, prune=schedule, qat=qat_cfg, box_loss=box_loss, box_weight=box_weight)
     from .pipeline import InputPipeline
     if rank == 0:
         print(INFO, 'data augment is ', str(augment))                            # utils.py:418
     steps, observed = 0, 0
+    iou_box = box_loss != 'mse'
     for epoch in range(max_nrof_epochs):
-        t0, seen, run = time.time(), 0, 0.0
+        t0, seen, run, run_box = time.time(), 0, 0.0, 0.0
         # tools/utils.py:417-450: each rank decodes only its rows of the global batch, on a thread pool, two batches ahead;
         # letterbox + normalise on the GPU (pipeline.py)
         pipe = InputPipeline(h, h.train_list, batch_size, rank, world, seed=rand_seed, epoch=epoch, shuffle=True, device=local,
@@ -177,9 +183,10 @@ def main(args, train_set, class_num, pre_ckpt, model_def, depth_multiplier, is_a
                     continue
                 out = tr.step(x, ys)
                 seen, run, steps = seen + 1, run + out['loss'], steps + 1
+                run_box += out.get('box', 0.0)
                 if rank == 0 and (seen % 10 == 0 or seen == 1):
                     pr = tr.precision_recall()
-                    print(f'epoch {epoch + 1} step {seen}: loss {out["loss"]:.4f} ' +
+                    print(f'epoch {epoch + 1} step {seen}: loss {out["loss"]:.4f} ' + (f'{box_loss} {out["box"]:.4f} ' if iou_box else '') +
                           ' '.join(f'l{i + 1}_p {p:.3f} l{i + 1}_r {r:.3f}' for i, (p, r) in enumerate(pr)), flush=True)
                 if max_steps and steps >= max_steps:
                     break
@@ -198,6 +205,7 @@ def main(args, train_set, class_num, pre_ckpt, model_def, depth_multiplier, is_a
                 val = validate(tr, h, spec, per_rank, rank)
         if rank == 0:
             print(f'epoch {epoch + 1}: {seen} steps, mean loss {run / max(seen, 1):.4f}, ' +
+                  (f'mean {box_loss} {run_box / max(seen, 1):.4f}, ' if iou_box else '') +
                   (f'val_loss {val:.4f}, ' if val is not None else '') + f'{time.time() - t0:.1f}s, input pipeline {pipe_rate:.0f} images/s/rank' +
                   (f', val_mAP {vmap:.4f}' if vmap is not None else ''), flush=True)
         for c in tr.counts:
@@ -268,7 +276,7 @@ def validate(tr, h: Helper, spec, batch: int, rank: int, map_obj=None):
     return tot / max(n, 1)
 
 
-def cli(argv=None):
+def parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser()
     p.add_argument('--train_set', type=str, default='voc')
     p.add_argument('--class_num', type=int, default=20)
@@ -302,12 +310,19 @@ def cli(argv=None):
     p.add_argument('--max_steps', type=int, default=0)
     p.add_argument('--val_map', type=str, choices=['True', 'False'], default='False', help='append val_mAP (VOC, on the GPU) to the epoch line')
     p.add_argument('--val_map_obj', type=float, default=0.05, help='objectness threshold of the detections val_mAP scores')
-    a = p.parse_args(sys.argv[1:] if argv is None else argv)
+    p.add_argument('--box_loss', type=str, choices=['mse', 'giou', 'diou', 'ciou'], default='mse',
+                   help='box regression term: the xy / wh terms of the reference, or an IoU-family loss (DESIGN.md 3.14)')
+    p.add_argument('--box_weight', type=float, default=1.0, help='weight of the IoU box term (not used with --box_loss mse)')
+    return p
+
+
+def cli(argv=None):
+    a = parser().parse_args(sys.argv[1:] if argv is None else argv)
     return main(a, a.train_set, a.class_num, a.pre_ckpt, a.model_def, a.depth_multiplier, a.augmenter, a.image_size, a.output_size,
                 a.batch_size, a.rand_seed, a.max_nrof_epochs, a.init_learning_rate, a.learning_rate_decay_factor, a.obj_weight,
                 a.noobj_weight, a.wh_weight, a.obj_thresh, a.iou_thresh, a.vaildation_split, a.log_dir, a.is_prune,
                 a.prune_initial_sparsity, a.prune_final_sparsity, a.prune_end_epoch, a.prune_frequency, a.synthetic, a.max_steps,
-                a.qat, a.qat_momentum, a.qat_observe, a.val_map, a.val_map_obj)
+                a.qat, a.qat_momentum, a.qat_observe, a.val_map, a.val_map_obj, a.box_loss, a.box_weight)
 
 
 if __name__ == '__main__':
