@@ -1578,7 +1578,7 @@ __global__ void __launch_bounds__(256, (TM == 2 && NP == 4) ? 4 : 5) fused_lr_ke
     }
     for (int v = tid; v < 9 * (Cp >> 3); v += NT)
         *reinterpret_cast<half8 *>(Ws + v * 8) = *reinterpret_cast<const half8 *>(a.dw_w + (size_t)v * 8);
-    for (int v = tid; v < npass * 48; v += NT) {                     // arrays are zero-padded past N (yk_engine.hip upload_sb)
+    for (int v = tid; v < npass * 48; v += NT) {                     // arrays are zero-padded past N (yk_dev_mem::upload_f)
         Sb[v] = a.scale[v];
         Sb[npass * 48 + v] = a.bias[v];
     }

@@ -8,7 +8,8 @@
 //     where profitable (the depthwise tile lives only in LDS) — see YK_FUSE_DWPW;
 //   * every weight tensor is converted to fp16 with its reduction axis padded to the activation
 //     channel pitch, BatchNorm stays an fp32 (scale, bias) epilogue.
-// Running a plan replays the launch list on the caller's stream; nothing is allocated at run time.
+// The compiler itself - its passes and weight packers - is yk_plan_build.h; this file holds the plan, yk_plan_create_ex's pass list
+// and the executor.  Running a plan replays the launch list on the caller's stream; nothing is allocated at run time.
 #include <algorithm>
 #include <string>
 #include <vector>
@@ -17,48 +18,6 @@
 #include "yk_plan_graph.h"
 
 namespace {
-
-uint16_t f2h_bits(float f) {   // round-to-nearest-even fp32 -> fp16 bits
-    uint32_t x;
-    memcpy(&x, &f, 4);
-    const uint32_t sign = (x >> 16) & 0x8000u;
-    uint32_t ax = x & 0x7fffffffu;
-    if (ax >= 0x7f800000u) return (uint16_t)(sign | 0x7c00u | ((ax > 0x7f800000u) ? 0x200u : 0));
-    if (ax >= 0x477ff000u) return (uint16_t)(sign | 0x7c00u);
-    if (ax < 0x38800000u) {   // subnormal half
-        if (ax < 0x33000000u) return (uint16_t)sign;   // < 2^-25 -> 0 (ties-to-even at exactly 2^-25 -> 0)
-        const int e = (int)(ax >> 23);
-        uint32_t man = (ax & 0x7fffffu) | 0x800000u;
-        const int shift = 126 - e;                     // 14..24
-        const uint32_t lsb = 1u << shift, half = lsb >> 1;
-        uint32_t r = man >> shift;
-        const uint32_t rem = man & (lsb - 1);
-        if (rem > half || (rem == half && (r & 1))) ++r;
-        return (uint16_t)(sign | r);
-    }
-    const uint32_t lsb = (ax >> 13) & 1u;
-    ax += 0xfffu + lsb;
-    return (uint16_t)(sign | ((ax - 0x38000000u) >> 13));
-}
-float h2f_bits(uint16_t h) {
-    const uint32_t sign = (uint32_t)(h & 0x8000u) << 16;
-    uint32_t e = (h >> 10) & 0x1f, m = h & 0x3ffu, x;
-    if (e == 0) {
-        if (m == 0) x = sign;
-        else {
-            int sh = 0;
-            while (!(m & 0x400u)) {
-                m <<= 1;
-                ++sh;
-            }
-            x = sign | ((uint32_t)(113 - sh) << 23) | ((m & 0x3ffu) << 13);
-        }
-    } else if (e == 31) x = sign | 0x7f800000u | (m << 13);
-    else x = sign | ((e + 112) << 23) | (m << 13);
-    float f;
-    memcpy(&f, &x, 4);
-    return f;
-}
 
 enum { K_FIRST = 1, K_DW, K_IGEMM, K_POOL, K_ADD, K_U8MAX, K_REDUCE, K_REDUCE_PW };
 
@@ -90,7 +49,7 @@ struct yk_plan {
     int device = 0, max_batch = 0;
     std::vector<tinfo> T;
     std::vector<launch> L;
-    std::vector<void *> allocs;
+    yk_dev_mem mem;
     std::vector<int> outputs;
     unsigned *d_imgmax = nullptr;
     float *d_slab = nullptr;
@@ -102,34 +61,12 @@ struct yk_plan {
     yk_xplan *x = nullptr;       // precision 1 ("f16x2"): the plan lives in yk_exact.hip, everything below forwards to it
 };
 
-static int dev_alloc(yk_plan *p, void **ptr, size_t bytes, bool zero) {
-    YK_HIP(hipMalloc(ptr, bytes));
-    p->allocs.push_back(*ptr);
-    if (zero) YK_HIP(hipMemset(*ptr, 0, bytes));
-    return YK_OK;
-}
-static int upload(yk_plan *p, void **ptr, const void *src, size_t bytes) {
-    int rc = dev_alloc(p, ptr, bytes, false);
-    if (rc) return rc;
-    YK_HIP(hipMemcpy(*ptr, src, bytes, hipMemcpyHostToDevice));
-    return YK_OK;
-}
-// scale/bias padded with zeros so the epilogue may read past N unguarded
-static int upload_sb(yk_plan *p, const float *blob, int off, int n, const float **d) {
-    std::vector<float> v((size_t)n + 256, 0.f);
-    memcpy(v.data(), blob + off, sizeof(float) * n);
-    void *q;
-    int rc = upload(p, &q, v.data(), v.size() * sizeof(float));
-    *d = (const float *)q;
-    return rc;
-}
-
-static bool env_flag(const char *name, bool dflt) { return yk_env_flag(name, dflt); }
+#include "yk_plan_build.h"
 
 extern "C" void yk_plan_destroy(yk_plan_t *p) {
     if (!p) return;
     (void)hipSetDevice(p->device);
-    for (void *q : p->allocs) (void)hipFree(q);
+    p->mem.free_all();
     yk_xplan_destroy(p->x);
     delete p;
 }
@@ -161,360 +98,32 @@ extern "C" int yk_plan_create_ex(yk_plan_t **out, const int32_t *ops, int n_ops,
     yk_plan *p = new yk_plan();
     p->device = device;
     p->max_batch = max_batch;
-    int rc = YK_OK;
-    auto fail = [&](int code) {
-        yk_plan_destroy(p);
-        return code;
-    };
-
-    yk_graph_tensors(p->T, tensors, n_tensors);
-    if (!p->T[0].is_input || p->T[0].c != 3) {
-        yk_set_error("yk_plan_create: tensor 0 must be the 3-channel network input");
-        return fail(YK_ERR_UNSUPPORTED);
-    }
-    p->in_h = p->T[0].h;
-    p->in_w = p->T[0].w;
-    for (int i = 0; i < n_outputs; ++i) {
-        if (outputs[i] < 0 || outputs[i] >= n_tensors) {
-            yk_set_error("yk_plan_create: bad output id");
-            return fail(YK_ERR_ARG);
-        }
-        p->outputs.push_back(outputs[i]);
-    }
     const int schedule = precision & YK_SCHEDULE_MASK;
     precision &= ~YK_SCHEDULE_MASK;
-    if (precision == YK_PRECISION_F16X2) {
+    int rc = plan_read_tensors(p, tensors, n_tensors, outputs, n_outputs);
+    if (!rc && precision == YK_PRECISION_F16X2) {
         rc = yk_xplan_create(&p->x, ops, n_ops, tensors, n_tensors, blob, blob_len, outputs, n_outputs, max_batch, schedule == YK_SCHEDULE_LATENCY);
-        if (rc) return fail(rc);
-        *out = p;
-        return YK_OK;
-    }
-    if (precision != YK_PRECISION_F16) {
+    } else if (!rc && precision != YK_PRECISION_F16) {
         yk_set_error("yk_plan_create_ex: unknown precision %d", precision);
-        return fail(YK_ERR_ARG);
-    }
-    // pass 1: views, use counts, output flags; fusion decisions need the op list, ADD-folding is decided first
-    std::vector<int> add_of;              // conv op i -> index of the ADD folded into it
-    std::vector<char> skip;
-    if ((rc = yk_graph_analyse(p->T, ops, n_ops, blob_len, p->outputs, add_of, skip))) return fail(rc);
-    // depthwise -> pointwise fusion (decided here, realised below)
-    const bool fuse_dwpw = env_flag("YK_FUSE_DWPW", true);
-    std::vector<int> dw_of(n_ops, -1);    // 1x1 conv op i -> index of the DWCONV fused in front of it
-    if (fuse_dwpw) {
-        for (int i = 0; i + 1 < n_ops; ++i) {
-            const int32_t *o = ops + (size_t)i * YK_OP_FIELDS, *q = o + YK_OP_FIELDS;
-            if (o[YK_F_TYPE] == YK_OP_DWCONV && q[YK_F_TYPE] == YK_OP_CONV && q[YK_F_K] == 1 &&
-                q[YK_F_IN0] == o[YK_F_OUT] && p->T[o[YK_F_OUT]].uses == 1 && !(q[YK_F_FLAGS] & YK_FLAG_NET_OUTPUT) &&
-                p->T[o[YK_F_IN0]].kind == T_REAL && !p->T[o[YK_F_IN0]].is_input && o[YK_F_ACT] != YK_ACT_LEAKY &&
-                yk_igemm_fused_ok(yk_pad8(o[YK_F_CIN]), q[YK_F_COUT])) {
-                dw_of[i + 1] = i;
-                skip[i] = 1;
-            }
+        rc = YK_ERR_ARG;
+    } else if (!rc) {                                        // f16: the passes of yk_plan_build.h
+        builder b{p, ops, n_ops, blob, max_batch, read_plan_opts()};
+        rc = b.analyse(blob_len);
+        if (!rc) {
+            b.decide_dwpw();
+            rc = b.allocate();
+        }
+        if (!rc) b.emit_u8max();
+        for (int i = 0; i < n_ops && !rc; ++i) rc = b.emit(i);
+        if (!rc) {
+            b.merge_reduce_pw();
+            rc = b.finish();
         }
     }
-
-    // allocate real tensors
-    for (int i = 1; i < n_tensors; ++i) {
-        tinfo &t = p->T[i];
-        if (t.kind != T_REAL) continue;
-        bool produced_fused_away = false;
-        for (int k = 0; k < n_ops; ++k) {
-            const int32_t *o = ops + (size_t)k * YK_OP_FIELDS;
-            if (o[YK_F_OUT] == i && ((skip[k] && o[YK_F_TYPE] == YK_OP_DWCONV) || add_of[k] >= 0)) produced_fused_away = true;
-        }
-        if (produced_fused_away) continue;   // lives only in LDS / registers
-        if (t.net_out) {
-            rc = dev_alloc(p, (void **)&t.d32, (size_t)max_batch * t.h * t.w * t.c * sizeof(float), true);
-        } else {
-            rc = dev_alloc(p, (void **)&t.d, ((size_t)max_batch * t.h * t.w * t.cp + 64) * sizeof(yk_half), true);
-        }
-        if (rc) return fail(rc);
+    if (rc) {
+        yk_plan_destroy(p);
+        return rc;
     }
-    rc = dev_alloc(p, (void **)&p->d_imgmax, sizeof(unsigned) * max_batch * 32, true);   // YK_MAXP partials per image
-    if (rc) return fail(rc);
-
-    // pass 2: launches
-    {
-        launch l;
-        l.kind = K_U8MAX;   // only issued by yk_run_u8: Helper._process_img's np.max(img)
-        l.name = "u8_max";
-        l.bytes = (double)p->in_h * p->in_w * 3;
-        p->L.push_back(l);
-    }
-    for (int i = 0; i < n_ops; ++i) {
-        if (skip[i]) continue;
-        const int32_t *o = ops + (size_t)i * YK_OP_FIELDS;
-        const int ty = o[YK_F_TYPE];
-        if (ty == YK_OP_UPSAMPLE || ty == YK_OP_CONCAT) continue;
-        const tinfo &X = p->T[o[YK_F_IN0]];
-        tinfo &Y = p->T[o[YK_F_OUT]];
-        float alpha;
-        memcpy(&alpha, &o[YK_F_ALPHA], 4);
-        launch l;
-        l.Ho = Y.h;
-        l.Wo = Y.w;
-        char nm[96];
-        if (ty == YK_OP_CONV && X.is_input) {
-            // ---- stem conv
-            if (o[YK_F_K] != 3 || add_of[i] >= 0 || Y.net_out) {
-                yk_set_error("op %d: stem conv must be 3x3", i);
-                return fail(YK_ERR_UNSUPPORTED);
-            }
-            const int co = o[YK_F_COUT];
-            std::vector<float> w((size_t)27 * co);
-            for (int c = 0; c < co; ++c)
-                for (int t = 0; t < 27; ++t) w[(size_t)t * co + c] = h2f_bits(f2h_bits(blob[o[YK_F_W_OFF] + (size_t)c * 27 + t]));
-            void *dw_;
-            if ((rc = upload(p, &dw_, w.data(), w.size() * sizeof(float)))) return fail(rc);
-            l.kind = K_FIRST;
-            first_args &f = l.f;
-            memset(&f, 0, sizeof(f));
-            f.Hi = X.h; f.Wi = X.w; f.Ho = Y.h; f.Wo = Y.w;
-            f.stride = o[YK_F_STRIDE]; f.pad_t = o[YK_F_PAD_T]; f.pad_l = o[YK_F_PAD_L];
-            f.Cout = co; f.outp = Y.cp; f.w = (const float *)dw_;
-            if (co <= 32) {                                    // weights again, in the MFMA stem's k order
-                std::vector<uint16_t> wm(32 * 32, 0);
-                for (int n = 0; n < co; ++n)
-                    for (int ky = 0; ky < 3; ++ky)
-                        for (int j = 0; j < 9; ++j)
-                            wm[(size_t)n * 32 + (j < 8 ? ky * 8 + j : 24 + ky)] = f2h_bits(blob[o[YK_F_W_OFF] + (size_t)n * 27 + ky * 9 + j]);
-                void *dm;
-                if ((rc = upload(p, &dm, wm.data(), wm.size() * 2))) return fail(rc);
-                f.wm = (const yk_half *)dm;
-            }
-            if ((rc = upload_sb(p, blob, o[YK_F_SCALE_OFF], co, &f.scale))) return fail(rc);
-            if ((rc = upload_sb(p, blob, o[YK_F_BIAS_OFF], co, &f.bias))) return fail(rc);
-            f.act = o[YK_F_ACT]; f.alpha = alpha; f.out = Y.d;
-            yk_act_params(f.act, f.alpha, &f.slope, &f.cap);
-            if (Y.cp != co) {
-                yk_set_error("op %d: stem conv Cout must be a multiple of 8", i);
-                return fail(YK_ERR_UNSUPPORTED);
-            }
-            snprintf(nm, sizeof nm, "stem3x3s%d_%d", f.stride, co);
-            l.flops = 2.0 * Y.h * Y.w * 27 * co;
-            l.bytes = (double)X.h * X.w * 3 * 2 + (double)Y.h * Y.w * co * 2;
-        } else if (ty == YK_OP_CONV) {
-            // ---- implicit GEMM conv (+ folded Add, + fused depthwise producer)
-            l.kind = K_IGEMM;
-            igemm_args &g = l.g;
-            memset(&g, 0, sizeof(g));
-            g.lda_pad = yk_fused_pad();
-            const tinfo *s0 = &X, *s1 = nullptr;
-            int up0 = 0;
-            if (X.kind == T_CAT) {
-                s0 = &p->T[X.src0];
-                s1 = &p->T[X.src1];
-            }
-            if (s0->kind == T_UP) {
-                up0 = 1;
-                s0 = &p->T[s0->src0];
-            }
-            const int dwi = dw_of[i];
-            const int32_t *dwo = dwi >= 0 ? ops + (size_t)dwi * YK_OP_FIELDS : nullptr;
-            const tinfo *dwX = dwo ? &p->T[dwo[YK_F_IN0]] : nullptr;
-            if (dwo) s0 = dwX;
-            if (s0->kind != T_REAL || (s1 && s1->kind != T_REAL) || s0->is_input || (s1 && s1->is_input) || !s0->d ||
-                (s1 && !s1->d)) {
-                yk_set_error("op %d: unsupported input view nesting", i);
-                return fail(YK_ERR_UNSUPPORTED);
-            }
-            const int ks = o[YK_F_K], co = o[YK_F_COUT];
-            const int c0 = dwo ? X.c : s0->c, c0p = yk_pad8(c0), c1 = s1 ? s1->c : 0, c1p = s1 ? s1->cp : 0;
-            if (c0 + c1 != o[YK_F_CIN] || (ks != 1 && ks != 3)) {
-                yk_set_error("op %d: conv shape mismatch (cin %d vs %d+%d, k=%d)", i, o[YK_F_CIN], c0, c1, ks);
-                return fail(YK_ERR_UNSUPPORTED);
-            }
-            g.in0 = s0->d; g.in1 = s1 ? s1->d : nullptr;
-            g.c0p = c0p; g.c1p = c1p; g.up0 = up0;
-            g.Hi = X.h; g.Wi = X.w; g.Ho = Y.h; g.Wo = Y.w;
-            g.ks = ks; g.stride = o[YK_F_STRIDE]; g.pad_t = o[YK_F_PAD_T]; g.pad_l = o[YK_F_PAD_L];
-            g.N = co; g.K = ks * ks * (c0p + c1p);
-            std::vector<uint16_t> w((size_t)co * g.K, 0);
-            const int cin = o[YK_F_CIN];
-            for (int n = 0; n < co; ++n)
-                for (int t = 0; t < ks * ks; ++t)
-                    for (int c = 0; c < cin; ++c) {
-                        const int pos = c < c0 ? c : c0p + (c - c0);
-                        w[(size_t)n * g.K + (size_t)t * (c0p + c1p) + pos] =
-                            f2h_bits(blob[o[YK_F_W_OFF] + ((size_t)n * ks * ks + t) * cin + c]);
-                    }
-            void *dwt;
-            if ((rc = upload(p, &dwt, w.data(), w.size() * 2))) return fail(rc);
-            g.w = (const yk_half *)dwt;
-            g.w_bytes = (uint32_t)(w.size() * 2);
-            if ((rc = upload_sb(p, blob, o[YK_F_SCALE_OFF], co, &g.scale))) return fail(rc);
-            if ((rc = upload_sb(p, blob, o[YK_F_BIAS_OFF], co, &g.bias))) return fail(rc);
-            g.act = o[YK_F_ACT]; g.alpha = alpha;
-            yk_act_params(g.act, g.alpha, &g.slope, &g.cap);
-            g.fd_hw = yk_make_fastdiv((uint32_t)(Y.h * Y.w));
-            g.fd_wo = yk_make_fastdiv((uint32_t)Y.w);
-            g.fd_ctp = yk_make_fastdiv((uint32_t)(c0p + c1p));
-            g.split_k = 1;
-            g.in0_bytes = (uint32_t)std::min<size_t>((size_t)max_batch * s0->h * s0->w * s0->cp * 2, 0xffffffffu);
-            g.in1_bytes = s1 ? (uint32_t)std::min<size_t>((size_t)max_batch * s1->h * s1->w * s1->cp * 2, 0xffffffffu) : 0u;
-            if (g.in0_bytes >= 0x40000000u || g.in1_bytes >= 0x40000000u) {
-                yk_set_error("op %d: activation tensor >= 1 GiB; lower max_batch", i);
-                return fail(YK_ERR_UNSUPPORTED);
-            }
-            tinfo *dst = &Y;
-            if (add_of[i] >= 0) {
-                const int32_t *q = ops + (size_t)add_of[i] * YK_OP_FIELDS;
-                const int other = (q[YK_F_IN0] == o[YK_F_OUT]) ? q[YK_F_IN1] : q[YK_F_IN0];
-                g.res = p->T[other].d;
-                g.resp = p->T[other].cp;
-                dst = &p->T[q[YK_F_OUT]];
-            }
-            const bool f32 = dst->net_out;
-            g.out = f32 ? (void *)dst->d32 : (void *)dst->d;
-            g.outp = f32 ? dst->c : dst->cp;
-            g.fd_vpr = yk_make_fastdiv((uint32_t)std::max(1, g.outp >> 3));
-            if (!g.out) {
-                yk_set_error("op %d: output tensor not allocated", i);
-                return fail(YK_ERR_UNSUPPORTED);
-            }
-            double dw_flops = 0, dw_bytes = 0;
-            if (dwo) {
-                float dalpha;
-                memcpy(&dalpha, &dwo[YK_F_ALPHA], 4);
-                (void)dalpha;
-                std::vector<uint16_t> dww((size_t)9 * c0p, 0);
-                for (int t = 0; t < 9; ++t)
-                    for (int c = 0; c < c0; ++c) dww[(size_t)t * c0p + c] = f2h_bits(blob[dwo[YK_F_W_OFF] + (size_t)t * c0 + c]);
-                void *dd;
-                if ((rc = upload(p, &dd, dww.data(), dww.size() * 2))) return fail(rc);
-                g.dw_w = (const yk_half *)dd;
-                if ((rc = upload_sb(p, blob, dwo[YK_F_SCALE_OFF], c0, &g.dw_scale))) return fail(rc);
-                if ((rc = upload_sb(p, blob, dwo[YK_F_BIAS_OFF], c0, &g.dw_bias))) return fail(rc);
-                g.dw_act = dwo[YK_F_ACT]; g.dw_stride = dwo[YK_F_STRIDE];
-                g.dw_pad_t = dwo[YK_F_PAD_T]; g.dw_pad_l = dwo[YK_F_PAD_L];
-                g.dw_Hi = dwX->h; g.dw_Wi = dwX->w;
-                yk_act_params(g.dw_act, 0.f, &g.dw_slope, &g.dw_cap);
-                g.fd_g = yk_make_fastdiv((uint32_t)(c0p >> 3));
-                dw_flops = 2.0 * X.h * X.w * 9 * c0;
-                dw_bytes = ((double)dwX->h * dwX->w * c0 + (double)X.h * X.w * c0) * 2;
-            }
-            g.M = max_batch * Y.h * Y.w;   // for config choice; patched per run
-            l.cfg = dwo ? yk_igemm_fused_pick(g) : yk_igemm_pick(g, f32);
-            l.out_f32 = f32;
-            if (dwo && (l.cfg == FUSED_DMA || l.cfg == LR_T1 || l.cfg == LR_T2)) {
-                if (l.cfg == FUSED_DMA) yk_fdma_fill(g);
-                // the LDS-DMA staged kernel and the LR kernels read their pointwise panel in MFMA fragment order: [16-channel slice][k-step of 32][lane][8],
-                // element = W[slice*16 + (lane & 15)][kstep*32 + (lane >> 4)*8 + e]; one wave-load = 1 KB contiguous
-                const int Kp = (c0p + 31) & ~31, nkf = Kp / 32, nsl = (co + 15) / 16;
-                std::vector<uint16_t> wf((size_t)nsl * nkf * 512, 0);
-                for (int sl = 0; sl < nsl; ++sl)
-                    for (int ks2 = 0; ks2 < nkf; ++ks2)
-                        for (int ln = 0; ln < 64; ++ln)
-                            for (int e = 0; e < 8; ++e) {
-                                const int n = sl * 16 + (ln & 15), k = ks2 * 32 + (ln >> 4) * 8 + e;
-                                if (n < co && k < g.K) wf[(((size_t)sl * nkf + ks2) * 64 + ln) * 8 + e] = w[(size_t)n * g.K + k];
-                            }
-                void *dwf;
-                if ((rc = upload(p, &dwf, wf.data(), wf.size() * 2))) return fail(rc);
-                g.w = (const yk_half *)dwf;
-                g.w_bytes = (uint32_t)(wf.size() * 2);
-            }
-            if (!dwo && env_flag("YK_SPLITK", true)) {
-                g.split_k = yk_igemm_split(l.cfg, g);
-                if (g.split_k > 1) {
-                    g.ldn = (co + 15) & ~15;
-                    p->slab_bytes = std::max(p->slab_bytes, (size_t)g.split_k * g.M * g.ldn * sizeof(float));
-                }
-            }
-            snprintf(nm, sizeof nm, "%sconv%dx%ds%d_%dto%d%s%s[%s]", dwo ? "dw3x3+" : "", ks, ks, g.stride, o[YK_F_CIN], co,
-                     g.res ? "+add" : "", s1 ? "+upcat" : (up0 ? "+up" : ""),
-                     dwo ? yk_igemm_fused_name(l.cfg) : yk_igemm_name(l.cfg));
-            if (g.split_k > 1) snprintf(nm + strlen(nm), sizeof nm - strlen(nm), "/splitk%d", g.split_k);
-            l.flops = 2.0 * Y.h * Y.w * ks * ks * (double)o[YK_F_CIN] * co + dw_flops;
-            l.bytes = ((double)X.h * X.w * o[YK_F_CIN] + (double)Y.h * Y.w * co) * 2 + dw_bytes;
-        } else if (ty == YK_OP_DWCONV) {
-            if (X.kind != T_REAL || X.is_input) {
-                yk_set_error("op %d: depthwise conv on a view/input", i);
-                return fail(YK_ERR_UNSUPPORTED);
-            }
-            l.kind = K_DW;
-            dw_args &d = l.d;
-            memset(&d, 0, sizeof(d));
-            const int c = X.c, cp = X.cp;
-            std::vector<uint16_t> w((size_t)9 * cp, 0);
-            for (int t = 0; t < 9; ++t)
-                for (int k = 0; k < c; ++k) w[(size_t)t * cp + k] = f2h_bits(blob[o[YK_F_W_OFF] + (size_t)t * c + k]);
-            void *dd;
-            if ((rc = upload(p, &dd, w.data(), w.size() * 2))) return fail(rc);
-            d.in = X.d; d.Hi = X.h; d.Wi = X.w; d.Ho = Y.h; d.Wo = Y.w; d.Cp = cp;
-            d.stride = o[YK_F_STRIDE]; d.pad_t = o[YK_F_PAD_T]; d.pad_l = o[YK_F_PAD_L];
-            d.w = (const yk_half *)dd;
-            if ((rc = upload_sb(p, blob, o[YK_F_SCALE_OFF], c, &d.scale))) return fail(rc);
-            if ((rc = upload_sb(p, blob, o[YK_F_BIAS_OFF], c, &d.bias))) return fail(rc);
-            d.act = o[YK_F_ACT]; d.alpha = alpha; d.out = Y.d;
-            yk_act_params(d.act, d.alpha, &d.slope, &d.cap);
-            snprintf(nm, sizeof nm, "dw3x3s%d_%d", d.stride, c);
-            l.flops = 2.0 * Y.h * Y.w * 9 * c;
-            l.bytes = ((double)X.h * X.w * c + (double)Y.h * Y.w * c) * 2;
-        } else if (ty == YK_OP_MAXPOOL) {
-            if (X.kind != T_REAL || X.is_input) {
-                yk_set_error("op %d: max pool on a view/input", i);
-                return fail(YK_ERR_UNSUPPORTED);
-            }
-            l.kind = K_POOL;
-            pool_args &q = l.p;
-            memset(&q, 0, sizeof(q));
-            q.in = X.d; q.Hi = X.h; q.Wi = X.w; q.Ho = Y.h; q.Wo = Y.w; q.Cp = X.cp; q.stride = o[YK_F_STRIDE]; q.out = Y.d;
-            snprintf(nm, sizeof nm, "maxpool2x2s%d_%d", q.stride, X.c);
-            l.bytes = ((double)X.h * X.w * X.c + (double)Y.h * Y.w * Y.c) * 2;
-        } else if (ty == YK_OP_ADD) {
-            const tinfo &Z = p->T[o[YK_F_IN1]];
-            if (X.kind != T_REAL || Z.kind != T_REAL || !X.d || !Z.d || !Y.d) {
-                yk_set_error("op %d: standalone Add on views", i);
-                return fail(YK_ERR_UNSUPPORTED);
-            }
-            l.kind = K_ADD;
-            l.add_a = X.d; l.add_b = Z.d; l.add_o = Y.d;
-            l.add_n8_per_image = (size_t)Y.h * Y.w * Y.cp / 8;
-            snprintf(nm, sizeof nm, "add_%d", Y.c);
-            l.bytes = 3.0 * Y.h * Y.w * Y.c * 2;
-        } else {
-            yk_set_error("op %d: unknown op type %d", i, ty);
-            return fail(YK_ERR_UNSUPPORTED);
-        }
-        l.name = nm;
-        p->L.push_back(l);
-        if (l.kind == K_IGEMM && l.g.split_k > 1) {   // deterministic finishing pass of split-K, its own launch
-            launch r = l;
-            r.kind = K_REDUCE;
-            r.name = std::string("splitk_reduce") + std::to_string(l.g.split_k) + "_" + std::to_string(l.g.N);
-            r.flops = 0;
-            r.bytes = ((double)l.g.split_k * 4 + 2) * l.Ho * l.Wo * l.g.ldn;   // slabs read (fp32) + tile written (fp16)
-            p->L.push_back(r);
-        }
-    }
-    // split-K finishing pass followed by the 1x1 fp32 head conv that reads it -> one launch (reduce_pw_kernel)
-    if (env_flag("YK_REDUCE_PW", true)) {
-        for (size_t i = 0; i + 1 < p->L.size(); ++i) {
-            launch &r = p->L[i];
-            launch &c = p->L[i + 1];
-            if (r.kind != K_REDUCE || r.out_f32 || c.kind != K_IGEMM) continue;
-            igemm_args cg = c.g;
-            cg.M = r.g.M;
-            if (!yk_reduce_pw_ok(r.g, cg, c.out_f32)) continue;
-            r.kind = K_REDUCE_PW;
-            r.g2 = c.g;
-            r.Ho2 = c.Ho; r.Wo2 = c.Wo;
-            r.name += "+" + c.name.substr(0, c.name.find('['));
-            r.flops += c.flops;
-            r.bytes += c.bytes;
-            p->L.erase(p->L.begin() + i + 1);
-        }
-    }
-    if (p->slab_bytes) {
-        if ((rc = dev_alloc(p, (void **)&p->d_slab, p->slab_bytes, true))) return fail(rc);
-    }
-    for (int t : p->outputs)
-        if (!p->T[t].d32) {
-            yk_set_error("yk_plan_create: output tensor %d is not produced by a NET_OUTPUT conv", t);
-            return fail(YK_ERR_UNSUPPORTED);
-        }
-    YK_HIP(hipDeviceSynchronize());
     *out = p;
     return YK_OK;
 }
@@ -669,7 +278,7 @@ extern "C" int yk_debug_read_tensor(yk_plan_t *p, int tid, int batch, float *h_d
     YK_HIP(hipMemcpy(h.data(), t.d, h.size() * 2, hipMemcpyDeviceToHost));
     const size_t pix = (size_t)batch * t.h * t.w;
     for (size_t q = 0; q < pix; ++q)
-        for (int c = 0; c < t.c; ++c) h_dst[q * t.c + c] = h2f_bits(h[q * t.cp + c]);
+        for (int c = 0; c < t.c; ++c) h_dst[q * t.c + c] = yk_h2f(h[q * t.cp + c]);
     return YK_OK;
 }
 
@@ -696,7 +305,7 @@ extern "C" int yk_debug_phase_stamps(yk_plan_t *p, int li, const uint8_t *d_fram
     if (!p || li < 0 || li >= (int)p->L.size()) return YK_ERR_ARG;
     YK_HIP(hipSetDevice(p->device));
     if (!p->d_dbg) {
-        int rc = dev_alloc(p, (void **)&p->d_dbg, sizeof(long long) * 8 * 65536, true);
+        int rc = p->mem.alloc((void **)&p->d_dbg, sizeof(long long) * 8 * 65536);
         if (rc) return rc;
     }
     YK_HIP(hipMemset(p->d_dbg, 0, sizeof(long long) * 8 * 65536));

@@ -951,18 +951,6 @@ __global__ void __launch_bounds__(256) xadd_kernel(const xadd_args a) {
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------
-uint16_t x_f2h(float f) {   // round-to-nearest-even fp32 -> fp16 bits (normal / subnormal / overflow to inf)
-    _Float16 h = (_Float16)f;
-    uint16_t u;
-    memcpy(&u, &h, 2);
-    return u;
-}
-float x_h2f(uint16_t u) {
-    _Float16 h;
-    memcpy(&h, &u, 2);
-    return (float)h;
-}
-
 enum { XK_STEM = 1, XK_CONV, XK_DW, XK_POOL, XK_ADD, XK_U8MAX, XK_BLOCK, XK_PERSIST, XK_HEADS, XK_FIN };
 // tile configurations of xg_kernel
 enum { XC_64x64 = 0, XC_64x128, XC_128x64, XC_128x128, XC_NUM };
@@ -1168,7 +1156,7 @@ struct yk_xplan {
     int max_batch = 0, in_h = 0, in_w = 0;
     std::vector<xtens> T;
     std::vector<xlaunch> L;
-    std::vector<void *> allocs;
+    yk_dev_mem mem;
     std::vector<int> outputs;
     unsigned *d_imgmax = nullptr;
     uint32_t *d_amax = nullptr;        // [n_tensors][max_batch][XS], then [max_batch] cluster arrival counters: cleared by every step's first launch
@@ -1181,30 +1169,9 @@ struct yk_xplan {
     int cluster_wt = 0;                // YK_CLUSTER_WT as it stood when the plan was created -> xp_args / xh_args::write_through
 };
 
-static int x_alloc(yk_xplan *p, void **ptr, size_t bytes) {
-    YK_HIP(hipMalloc(ptr, bytes));
-    p->allocs.push_back(*ptr);
-    YK_HIP(hipMemset(*ptr, 0, bytes));
-    return YK_OK;
-}
-static int x_upload(yk_xplan *p, void **ptr, const void *src, size_t bytes) {
-    int rc = x_alloc(p, ptr, bytes);
-    if (rc) return rc;
-    YK_HIP(hipMemcpy(*ptr, src, bytes, hipMemcpyHostToDevice));
-    return YK_OK;
-}
-static int x_upload_f(yk_xplan *p, const float *src, int n, float mul, const float **d) {
-    std::vector<float> v((size_t)n + 256, 0.f);
-    for (int i = 0; i < n; ++i) v[i] = src[i] * mul;
-    void *q;
-    int rc = x_upload(p, &q, v.data(), v.size() * sizeof(float));
-    *d = (const float *)q;
-    return rc;
-}
-
 void yk_xplan_destroy(yk_xplan *p) {
     if (!p) return;
-    for (void *q : p->allocs) (void)hipFree(q);
+    p->mem.free_all();
     if (p->h_err) (void)hipHostFree(p->h_err);
     delete p;
 }
@@ -1376,17 +1343,17 @@ static int x_build_persist(yk_xplan *p, int max_batch) {
     const size_t total = (size_t)arena + 2 * (size_t)dmax * max_batch;
     if (total + 65536 >= X_OOB) return YK_OK;
     void *ar = nullptr, *dph = nullptr, *px = nullptr;
-    int rc = x_alloc(p, &ar, total + 65536);
+    int rc = p->mem.alloc(&ar, total + 65536);
     if (rc) return rc;
     for (auto &wc : wcopy) YK_HIP(hipMemcpy((uint8_t *)ar + wc.first, wc.second->c.w, wc.second->c.w_bytes, hipMemcpyDeviceToDevice));
-    if ((rc = x_upload(p, &dph, ph.data(), ph.size() * sizeof(xp_phase)))) return rc;
+    if ((rc = p->mem.upload(&dph, ph.data(), ph.size() * sizeof(xp_phase)))) return rc;
     a.ph = (const xp_phase *)dph;
     a.n_phase = (int)ph.size();
     a.CW = CW;
     a.arena = (const uint8_t *)ar;
     a.arena_bytes = (uint32_t)total;
     a.gran = reinterpret_cast<unsigned long long *>(p->d_amax + (p->zero_words - 2 * (size_t)max_batch * 2 * CW * 2));
-    if ((rc = x_alloc(p, &px, sizeof(uint32_t) * (size_t)max_batch * CW))) return rc;
+    if ((rc = p->mem.alloc(&px, sizeof(uint32_t) * (size_t)max_batch * CW))) return rc;
     a.pxcc = (uint32_t *)px;
     a.err = p->d_err;
     char nm[160];
@@ -1514,9 +1481,9 @@ static int x_build_heads_from(yk_xplan *p, int max_batch, int first, bool *built
     for (auto &it : ph) dev.push_back(it.q);
     void *dpart = nullptr, *dph = nullptr, *px = nullptr;
     int rc;
-    if ((rc = x_alloc(p, &dpart, total + 65536))) return rc;
-    if ((rc = x_upload(p, &dph, dev.data(), dev.size() * sizeof(xh_phase)))) return rc;
-    if ((rc = x_alloc(p, &px, sizeof(uint32_t) * (size_t)max_batch * XH_CW))) return rc;
+    if ((rc = p->mem.alloc(&dpart, total + 65536))) return rc;
+    if ((rc = p->mem.upload(&dph, dev.data(), dev.size() * sizeof(xh_phase)))) return rc;
+    if ((rc = p->mem.alloc(&px, sizeof(uint32_t) * (size_t)max_batch * XH_CW))) return rc;
     xlaunch l;
     l.kind = XK_HEADS;
     xh_args &a = l.ha;
@@ -1690,7 +1657,7 @@ int yk_xplan_read_tensor(yk_xplan *p, int tid, int batch, float *h_dst, size_t d
                 continue;
             }
             for (int c = 0; c < t.c; ++c)
-                dst[c] = ldexpf(x_h2f(src[(c >> 3) * 16 + (c & 7)]) + x_h2f(src[(c >> 3) * 16 + 8 + (c & 7)]), ee[b]);
+                dst[c] = ldexpf(yk_h2f(src[(c >> 3) * 16 + (c & 7)]) + yk_h2f(src[(c >> 3) * 16 + 8 + (c & 7)]), ee[b]);
         }
     return YK_OK;
 }
@@ -1712,7 +1679,7 @@ int yk_xplan_phase_stamps(yk_xplan *p, int li, const void *d_in, int batch, hipS
     if (li < 0 || li >= (int)p->L.size() || (p->L[li].kind != XK_BLOCK && p->L[li].kind != XK_PERSIST && p->L[li].kind != XK_HEADS)) return YK_ERR_ARG;
     const size_t cap = 65536;
     if (!p->d_dbg) {
-        int rc = x_alloc(p, (void **)&p->d_dbg, sizeof(long long) * 16 * cap);
+        int rc = p->mem.alloc((void **)&p->d_dbg, sizeof(long long) * 16 * cap);
         if (rc) return rc;
     }
     YK_HIP(hipMemset(p->d_dbg, 0, sizeof(long long) * 16 * cap));

@@ -1,11 +1,65 @@
-// yk_plan_graph.h — the op-graph analysis both plan builders start from (host only): yk_plan_create_ex's f16 path (yk_engine.hip) and
-// yk_xplan_create (yk_xplan_build.h).  Tensor table, op validation, use counts, UpSampling2D / Concatenate views, network-output flags
-// and the residual Adds that fold into their producing conv.
+// yk_plan_graph.h — what both plan builders start from (host only): the f16 one (yk_plan_build.h) and the f16x2 one
+// (yk_xplan_build.h).  The host plumbing - fp32 <-> fp16 conversion, a plan's device allocations - and the op-graph analysis: tensor
+// table, op validation, use counts, UpSampling2D / Concatenate views, network-output flags and the residual Adds that fold into their
+// producing conv.
 #pragma once
 #include <algorithm>
 #include <vector>
 
 #include "yk_conv.h"
+
+static inline uint16_t yk_f2h(float f) {   // round-to-nearest-even fp32 -> fp16 bits (normal / subnormal / overflow to inf)
+    _Float16 h = (_Float16)f;
+    uint16_t u;
+    memcpy(&u, &h, 2);
+    return u;
+}
+static inline float yk_h2f(uint16_t u) {
+    _Float16 h;
+    memcpy(&h, &u, 2);
+    return (float)h;
+}
+
+static inline float yk_op_alpha(const int32_t *o) {   // an op row's LeakyReLU slope: a float stored in an int32 field
+    float a;
+    memcpy(&a, &o[YK_F_ALPHA], 4);
+    return a;
+}
+
+// the device allocations of a plan, freed together by its destroy function
+struct yk_dev_mem {
+    std::vector<void *> ptrs;
+
+    int alloc(void **ptr, size_t bytes, bool zero = true) {
+        YK_HIP(hipMalloc(ptr, bytes));
+        ptrs.push_back(*ptr);
+        if (zero) YK_HIP(hipMemset(*ptr, 0, bytes));
+        return YK_OK;
+    }
+    int upload(void **ptr, const void *src, size_t bytes) {
+        int rc = alloc(ptr, bytes, false);
+        if (rc) return rc;
+        YK_HIP(hipMemcpy(*ptr, src, bytes, hipMemcpyHostToDevice));
+        return YK_OK;
+    }
+    template <class E, class D>
+    int upload(const std::vector<E> &v, const D **d) {   // a packed host panel, to the pointer type its kernel reads it through
+        void *q;
+        int rc = upload(&q, v.data(), v.size() * sizeof(E));
+        *d = (const D *)q;
+        return rc;
+    }
+    // n floats times `mul` (BatchNorm scale / bias), padded with 256 zeros so an epilogue may read past n unguarded
+    int upload_f(const float *src, int n, const float **d, float mul = 1.f) {
+        std::vector<float> v((size_t)n + 256, 0.f);
+        for (int i = 0; i < n; ++i) v[i] = src[i] * mul;
+        return upload(v, d);
+    }
+    void free_all() {
+        for (void *q : ptrs) (void)hipFree(q);
+        ptrs.clear();
+    }
+};
 
 enum { T_REAL = 0, T_UP = 1, T_CAT = 2 };
 

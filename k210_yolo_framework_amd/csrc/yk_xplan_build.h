@@ -112,11 +112,6 @@ struct xbuilder {
     size_t ticket_base = 0, ticket_used = 0;
 
     const int32_t *op(int i) const { return ops + (size_t)i * YK_OP_FIELDS; }
-    static float alpha_of(const int32_t *o) {
-        float a;
-        memcpy(&a, &o[YK_F_ALPHA], 4);
-        return a;
-    }
     uint32_t *amax_of(int tid) const { return p->d_amax + (size_t)tid * max_batch * XS; }
     int *eexp_of(int tid) const { return p->d_eexp + (size_t)tid * max_batch; }
     xview view_of(int tid) const {
@@ -245,14 +240,14 @@ struct xbuilder {
                 if (op(k)[YK_F_OUT] == i && add_of[k] >= 0) folded = true;
             if (folded) continue;
             if (t.net_out) {
-                if ((rc = x_alloc(p, (void **)&t.d32, ((size_t)max_batch * t.h * t.w * t.c + 64) * sizeof(float)))) return rc;
+                if ((rc = p->mem.alloc((void **)&t.d32, ((size_t)max_batch * t.h * t.w * t.c + 64) * sizeof(float)))) return rc;
             } else {
                 const size_t bytes = (size_t)max_batch * t.h * t.w * t.cp * 4;
                 if (bytes >= X_OOB) {
                     yk_set_error("tensor %d: %zu bytes >= 1 GiB; lower max_batch", i, bytes);
                     return YK_ERR_UNSUPPORTED;
                 }
-                if ((rc = x_alloc(p, (void **)&t.d, bytes + 256))) return rc;
+                if ((rc = p->mem.alloc((void **)&t.d, bytes + 256))) return rc;
             }
         }
         return YK_OK;
@@ -262,10 +257,10 @@ struct xbuilder {
     int alloc_step_state() {
         const size_t n_tensors = p->T.size();
         int rc;
-        if ((rc = x_alloc(p, (void **)&p->d_imgmax, sizeof(unsigned) * max_batch * 32))) return rc;
+        if ((rc = p->mem.alloc((void **)&p->d_imgmax, sizeof(unsigned) * max_batch * 32))) return rc;
         ticket_base = n_tensors * max_batch * XS;
         p->zero_words = ticket_base + XF_TICKETS + 2 * (size_t)max_batch * 2 * 8 * 2;
-        if ((rc = x_alloc(p, (void **)&p->d_amax, sizeof(uint32_t) * p->zero_words))) return rc;
+        if ((rc = p->mem.alloc((void **)&p->d_amax, sizeof(uint32_t) * p->zero_words))) return rc;
         {   // the error word lives in mapped host memory: a failing cluster writes it over the link once, the host polls it for free
             void *h = nullptr, *d = nullptr;
             if (hipHostMalloc(&h, 256, hipHostMallocMapped) != hipSuccess || hipHostGetDevicePointer(&d, h, 0) != hipSuccess) {
@@ -277,7 +272,7 @@ struct xbuilder {
             p->h_err = (uint32_t *)h;
             p->d_err = (uint32_t *)d;
         }
-        return x_alloc(p, (void **)&p->d_eexp, sizeof(int) * n_tensors * max_batch);
+        return p->mem.alloc((void **)&p->d_eexp, sizeof(int) * n_tensors * max_batch);
     }
 
     // conv weights -> device, split and tile-ordered: w * 2^s = hi + lo with max |w * 2^s| in [2^13, 2^14); [step][16-row block][hi|lo][16][32],
@@ -302,16 +297,14 @@ struct xbuilder {
                     const int step = second ? taps * nc0 + (cc / 32) * taps + t : (cc / 32) * taps + t;      // channel step outer, tap inner
                     const int k32 = cc % 32, chunk = k32 >> 3, e = k32 & 7, r = n & 15, pos = chunk ^ ((r >> 1) & 3);
                     const float v = ldexpf(wv, sexp);
-                    const uint16_t hi = x_f2h(v);
+                    const uint16_t hi = yk_f2h(v);
                     const size_t at = ((size_t)step * nslab + (n >> 4)) * 1024 + (size_t)r * 32 + pos * 8 + e;
                     wt[at] = hi;
-                    wt[at + 512] = x_f2h(v - x_h2f(hi));
+                    wt[at + 512] = yk_f2h(v - yk_h2f(hi));
                     (second ? sum1 : sum0)[n] += fabs((double)wv);
                 }
-        void *d1;
-        int rc2 = x_upload(p, &d1, wt.data(), wt.size() * 2);
+        int rc2 = p->mem.upload(wt, dw);
         if (rc2) return rc2;
-        *dw = (const uint8_t *)d1;
         *dbytes = (uint32_t)(wt.size() * 2);
         *gain0 = *gain1 = *off = 0.f;
         for (int n = 0; n < co; ++n) {
@@ -323,8 +316,8 @@ struct xbuilder {
         *gain0 *= 1.0001f;
         *gain1 *= 1.0001f;
         *off *= 1.0001f;
-        if ((rc2 = x_upload_f(p, blob + o[YK_F_SCALE_OFF], co, ldexpf(1.f, -sexp), dscale))) return rc2;
-        return x_upload_f(p, blob + o[YK_F_BIAS_OFF], co, 1.f, dbias);
+        if ((rc2 = p->mem.upload_f(blob + o[YK_F_SCALE_OFF], co, dscale, ldexpf(1.f, -sexp)))) return rc2;
+        return p->mem.upload_f(blob + o[YK_F_BIAS_OFF], co, dbias);
     }
     // [11][cp] depthwise parameters (nine taps, BN scale, BN bias) -> device; bound of the output from the input's max
     int pack_dw(const int32_t *o, int c, int cp, const float **dpar, float *gain, float *off) {
@@ -345,10 +338,7 @@ struct xbuilder {
         }
         *gain *= 1.0001f;
         *off *= 1.0001f;
-        void *dp;
-        int rc2 = x_upload(p, &dp, par.data(), par.size() * sizeof(float));
-        *dpar = (const float *)dp;
-        return rc2;
+        return p->mem.upload(par, dpar);
     }
     // the stem conv's output bound from its weights (the normalised image is in [0, 1]: the bound needs no measurement):
     // gain = max_c |scale_c| * sum_t |w_ct|, off = max |bias|, wmax = max |w|
@@ -420,17 +410,16 @@ struct xbuilder {
             for (int t = 0; t < 27; ++t) w[(size_t)t * co + c] = blob[o[YK_F_W_OFF] + (size_t)c * 27 + t];
         float gain, off, wmax;
         stem_gain(o, &gain, &off, &wmax);
-        void *dw_;
-        if ((rc = x_upload(p, &dw_, w.data(), w.size() * sizeof(float)))) return rc;
         l.kind = XK_STEM;
         xstem_args &s = l.s;
         memset(&s, 0, sizeof(s));
+        if ((rc = p->mem.upload(w, &s.w))) return rc;
         s.Hi = X.h; s.Wi = X.w; s.Ho = Y.h; s.Wo = Y.w;
         s.stride = o[YK_F_STRIDE]; s.pad_t = o[YK_F_PAD_T]; s.pad_l = o[YK_F_PAD_L];
-        s.Cout = co; s.outG = Y.cp >> 3; s.w = (const float *)dw_;
-        if ((rc = x_upload_f(p, blob + o[YK_F_SCALE_OFF], co, 1.f, &s.scale))) return rc;
-        if ((rc = x_upload_f(p, blob + o[YK_F_BIAS_OFF], co, 1.f, &s.bias))) return rc;
-        yk_act_params(o[YK_F_ACT], alpha_of(o), &s.slope, &s.cap);
+        s.Cout = co; s.outG = Y.cp >> 3;
+        if ((rc = p->mem.upload_f(blob + o[YK_F_SCALE_OFF], co, &s.scale))) return rc;
+        if ((rc = p->mem.upload_f(blob + o[YK_F_BIAS_OFF], co, &s.bias))) return rc;
+        yk_act_params(o[YK_F_ACT], yk_op_alpha(o), &s.slope, &s.cap);
         const float bound = std::min(s.cap, (gain + off) * 1.0001f);
         s.eo = (bound > 0.f && std::isfinite(bound)) ? ilogbf(bound) - 13 : 0;
         s.out = Y.d;
@@ -464,17 +453,15 @@ struct xbuilder {
                     else if (k < 27) t = (k - 24) * 9 + 8;
                     if (n >= sco || t < 0) continue;
                     const float v = ldexpf(blob[so[YK_F_W_OFF] + (size_t)n * 27 + t], sexp);
-                    const uint16_t hi = x_f2h(v);
+                    const uint16_t hi = yk_f2h(v);
                     wf[((size_t)(nf * 2 + 0) * 64 + ln) * 8 + e] = hi;
-                    wf[((size_t)(nf * 2 + 1) * 64 + ln) * 8 + e] = x_f2h(v - x_h2f(hi));
+                    wf[((size_t)(nf * 2 + 1) * 64 + ln) * 8 + e] = yk_f2h(v - yk_h2f(hi));
                 }
-        void *dw_;
-        if ((rc = x_upload(p, &dw_, wf.data(), wf.size() * 2))) return rc;
+        if ((rc = p->mem.upload(wf, &g.st_wf))) return rc;
         g.stem = 1;
-        g.st_wf = (const yk_half *)dw_;
-        if ((rc = x_upload_f(p, blob + so[YK_F_SCALE_OFF], sco, ldexpf(1.f, -sexp), &g.st_scale))) return rc;
-        if ((rc = x_upload_f(p, blob + so[YK_F_BIAS_OFF], sco, 1.f, &g.st_bias))) return rc;
-        yk_act_params(so[YK_F_ACT], alpha_of(so), &g.st_slope, &g.st_cap);
+        if ((rc = p->mem.upload_f(blob + so[YK_F_SCALE_OFF], sco, &g.st_scale, ldexpf(1.f, -sexp)))) return rc;
+        if ((rc = p->mem.upload_f(blob + so[YK_F_BIAS_OFF], sco, &g.st_bias))) return rc;
+        yk_act_params(so[YK_F_ACT], yk_op_alpha(so), &g.st_slope, &g.st_cap);
         g.st_stride = so[YK_F_STRIDE]; g.st_pad_t = so[YK_F_PAD_T]; g.st_pad_l = so[YK_F_PAD_L]; g.st_cout = sco;
         g.fH = F.h; g.fW = F.w;
         g.fd_wrow = yk_make_fastdiv((uint32_t)(((g.PW - 1) * g.st_stride + 3) * 3));
@@ -510,13 +497,13 @@ struct xbuilder {
         char stn[40] = "";
         if (stem_of[i] >= 0 && (rc = fuse_stem_into(g, op(stem_of[i]), S, stn, sizeof stn, &st_flops, &st_bytes))) return rc;
         if ((rc = pack_dw(dwo, S.c, S.cp, &g.par, &dwgain, &dwoff))) return rc;
-        yk_act_params(dwo[YK_F_ACT], alpha_of(dwo), &g.dw_slope, &g.dw_cap);
+        yk_act_params(dwo[YK_F_ACT], yk_op_alpha(dwo), &g.dw_slope, &g.dw_cap);
         g.dw_gain = dwgain;
         g.dw_off = dwoff;
         const int BN = 64 * l.tn;
         g.nslab = ((co + BN - 1) / BN) * (BN / 16);
         if ((rc = pack_w(o, cin, g.nk, 0, 1, g.nslab, &g.w, &g.w_bytes, &g.scale, &g.bias, &g.gain, &g1, &g.off))) return rc;
-        yk_act_params(o[YK_F_ACT], alpha_of(o), &g.slope, &g.cap);
+        yk_act_params(o[YK_F_ACT], yk_op_alpha(o), &g.slope, &g.cap);
         const int dst_id = residual_dst(i, &g.res);
         const xtens *dst = &p->T[dst_id];
         g.out = dst->d;
@@ -550,7 +537,7 @@ struct xbuilder {
         if (g.splitk > 1) {
             void *sl;
             const size_t sb = (size_t)g.splitk * tiles * bm * co * 4;
-            if ((rc = x_alloc(p, &sl, sb))) return rc;
+            if ((rc = p->mem.alloc(&sl, sb))) return rc;
             g.slab = (float *)sl;
             l.f.slab_bytes = (uint32_t)sb;
         }
@@ -575,7 +562,7 @@ struct xbuilder {
             void *sl;
             const int tm = g_xc[t.cfg].bm * g_xc[t.cfg].bn / 16 / (g_xc[t.cfg].threads / 64) / 16;   // floatx4 registers per thread
             int rc;
-            if ((rc = x_alloc(p, &sl, (size_t)g.splitk * t.tiles * tm * g_xc[t.cfg].threads * 16))) return rc;
+            if ((rc = p->mem.alloc(&sl, (size_t)g.splitk * t.tiles * tm * g_xc[t.cfg].threads * 16))) return rc;
             g.slab = (float *)sl;
         }
         return YK_OK;
@@ -632,7 +619,7 @@ struct xbuilder {
         const int BN = fin ? co : g_xc[l.cfg].bn;
         g.nslab = ((co + BN - 1) / BN) * (BN / 16);
         if ((rc = pack_w(o, c0, g.nc0, g.nc1, g.taps, g.nslab, &g.w, &g.w_bytes, &g.scale, &g.bias, &g.gain0, &g.gain1, &g.off))) return rc;
-        yk_act_params(o[YK_F_ACT], alpha_of(o), &g.slope, &g.cap);
+        yk_act_params(o[YK_F_ACT], yk_op_alpha(o), &g.slope, &g.cap);
         g.fd_hw = yk_make_fastdiv((uint32_t)(Y.h * Y.w));
         g.fd_wo = yk_make_fastdiv((uint32_t)Y.w);
         l.in_tid = (S1 || up0) ? -1 : s0;
@@ -675,7 +662,7 @@ struct xbuilder {
         float ga, gb, go;
         int rc;
         if ((rc = pack_w(q, co, co / 32, 0, 1, f.nslab2, &f.w2, &wb2, &f.scale2, &f.bias2, &ga, &gb, &go))) return rc;
-        yk_act_params(q[YK_F_ACT], alpha_of(q), &f.slope2, &f.cap2);
+        yk_act_params(q[YK_F_ACT], yk_op_alpha(q), &f.slope2, &f.cap2);
         f.out32 = Z.d32;
         if (!f.out32) {
             yk_set_error("op %d: network output not allocated", fin_of[i]);
@@ -710,7 +697,7 @@ struct xbuilder {
         d.in = view_of(xid);
         d.Ho = Y.h; d.Wo = Y.w;
         d.stride = o[YK_F_STRIDE]; d.pad_t = o[YK_F_PAD_T]; d.pad_l = o[YK_F_PAD_L];
-        yk_act_params(o[YK_F_ACT], alpha_of(o), &d.slope, &d.cap);
+        yk_act_params(o[YK_F_ACT], yk_op_alpha(o), &d.slope, &d.cap);
         d.gain = gain;
         d.off = off;
         d.out = Y.d;
