@@ -9,6 +9,7 @@
 #                    [PRUNE=True INITSPARSITY=0.5 FINALSPARSITY=0.9 END_EPOCH=5 FREQUENCY=100]: magnitude pruning, saves yolo_prune_model.h5
 #                    [QAT=True QATMOMENTUM=0.99 QATOBSERVE=8]: quantisation-aware fine-tuning, saves yolo_qat_model.h5 + yolo_qat_ranges.npz
 #                    [BOXLOSS=giou|diou|ciou BOXWEIGHT=1.0]: an IoU-family box loss in place of the xy / wh terms (default mse: the reference's loss)
+#                    [MOSAIC=True MOSAICPROB=1.0 MOSAICOFF=0]: four pictures per training sample, composed on the GPU; the last MOSAICOFF epochs without
 #   make kmodel      CKPT=yolo_model.h5 OUT=yolo.kmodel|.kfpkg [SYNTHETIC=256 | CALIB=data/voc_img_ann.npy]: 8-bit K210 model, calibrated on the GPU
 #                    [RANGES=yolo_qat_ranges.npz]: the ranges a QAT run learned instead of a calibration
 #                    [CALIBMETHOD=minmax|percentile|mse CALIBPCT=99.99 CALIBBINS=2048]: minmax (default) takes each tensor's exact range; percentile
@@ -57,6 +58,9 @@ QATOBSERVE    ?= 8
 VALMAP        ?= False
 BOXLOSS       ?= mse
 BOXWEIGHT     ?= 1.0
+MOSAIC        ?= False
+MOSAICPROB    ?= 1.0
+MOSAICOFF     ?= 0
 # eval only
 PRECISION     ?= f16x2
 ANN           ?= data/$(DATASET)_img_ann.npy
@@ -93,7 +97,7 @@ TRAIN_ARGS = --pre_ckpt $(CKPT) --augmenter $(IAA) --batch_size $(BATCH) --rand_
              --is_prune $(PRUNE) --prune_initial_sparsity $(INITSPARSITY) --prune_final_sparsity $(FINALSPARSITY) \
              --prune_end_epoch $(END_EPOCH) --prune_frequency $(FREQUENCY) --synthetic $(SYNTHETIC) \
              --qat $(QAT) --qat_momentum $(QATMOMENTUM) --qat_observe $(QATOBSERVE) --val_map $(VALMAP) \
-             --box_loss $(BOXLOSS) --box_weight $(BOXWEIGHT)
+             --box_loss $(BOXLOSS) --box_weight $(BOXWEIGHT) --mosaic $(MOSAIC) --mosaic_prob $(MOSAICPROB) --mosaic_off_epochs $(MOSAICOFF)
 ifeq ($(GPUS),1)
 LAUNCH = $(PY)
 else

@@ -314,6 +314,25 @@ int yk_letterbox_ragged_params(yk_ragged_row_t *h_table, int n, int dst_h, int d
  * zeros and nothing of d_src is read for it.  Can be recorded in a graph. */
 int yk_letterbox_ragged_u8(const uint8_t *d_src, size_t src_bytes, const yk_ragged_row_t *d_table, int n, uint8_t *d_dst, int dst_h,
                            int dst_w, void *stream);
+/* ---- mosaic: one training frame from four pictures (k210_yolo_framework_amd/mosaic.py) ------
+ * A sample is four table rows in quadrant order - 0 top left [0,cx) x [0,cy), 1 top right [cx,W) x [0,cy), 2 bottom left, 3 bottom right -
+ * and a seam (cx, cy).  Output pixel (x, y) is the letterbox pixel (yk_letterbox_u8's arithmetic, unchanged: truncating cast, taps outside
+ * the picture read 0) of the picture of the quadrant it falls in, with that row's scale, tx, ty; tx and ty may be negative.  Four equal rows
+ * holding a picture's plain letterbox give yk_letterbox_u8's frame, bit for bit, wherever the seam is.
+ * HOST helper: fills scale, tx, ty of the four rows of one sample from their (h, w), the seam and the gains: scale = gain_k * (the letterbox
+ * scale of (h, w) -> (dst_h, dst_w)); left quadrants tx = cx - (int)ceil(w * scale), right quadrants tx = cx; top quadrants
+ * ty = cy - (int)ceil(h * scale), bottom quadrants ty = cy - the corner of the scaled picture nearest the seam sits at the seam.  A NULL
+ * pointer, a row with h <= 0 or w <= 0, a gain that is not positive and finite, or a non-positive dst size: YK_ERR_ARG.  Needs no device. */
+int yk_mosaic_params(yk_ragged_row_t *h_rows4, int cx, int cy, const double *gain4, int dst_h, int dst_w);
+/* One launch for the whole batch (blockIdx.y is the sample, chunked at 65535; one thread per output pixel): d_table [n][4] rows (quadrant
+ * order), d_centre [n][2] = (cx, cy), d_inv [n][6] float64 or NULL (no warp), d_dst [n][dst_h][dst_w][3].  With d_inv the frame is warped
+ * by each sample's inverse map as yk_letterbox_augment_u8 warps the letterbox: the four bilinear taps each evaluate the mosaic pixel on the
+ * fly, no intermediate frame, bit-identical to the mosaic followed by that warp.  The kernel does not trust the table: a row with h <= 0,
+ * w <= 0 or offset + 3*h*w > src_bytes makes its quadrant zeros and nothing of d_src is read for it; cx and cy are clamped to [0, dst_w] and
+ * [0, dst_h] (an empty quadrant is legal).  NULL pointers other than d_inv, n <= 0, src_bytes == 0 and non-positive dst sizes:
+ * YK_ERR_ARG; no device: YK_ERR_NO_DEVICE.  Can be recorded in a graph. */
+int yk_mosaic_ragged_u8(const uint8_t *d_src, size_t src_bytes, const yk_ragged_row_t *d_table, const int32_t *d_centre,
+                        const double *d_inv, int n, uint8_t *d_dst, int dst_h, int dst_w, void *stream);
 /* Draws detections INTO the pictures of a ragged batch, in place (inference.py's PIL loop plus keras_inference.py:137-174's label with
  * its filled background), by the painter's rule: for picture i and its rows k = 0 .. count_i - 1 in order, later paint over earlier:
  *   corners   t = max(0, floorf(top + 0.5f)), l likewise from left; b = min(h, floorf(bottom + 0.5f)), r = min(w, floorf(right + 0.5f))

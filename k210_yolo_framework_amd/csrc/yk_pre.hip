@@ -194,6 +194,106 @@ extern "C" int yk_letterbox_augment_u8(const uint8_t *d_src, int batch, int src_
     return YK_OK;
 }
 
+// ---- mosaic (k210_yolo_framework_amd/mosaic.py): one frame from four pictures of any sizes, a whole ragged training batch
+// in one launch.  Sample b has four table rows in quadrant order (0 TL, 1 TR, 2 BL, 3 BR) and a seam (cx, cy): output pixel (x, y) belongs
+// to quadrant (x >= cx) + 2*(y >= cy) and is letterbox_px of that row's picture with that row's (scale, tx, ty) - the arithmetic above,
+// unchanged, so a quadrant equals the letterbox of its picture restricted to it, and four equal rows give the plain letterbox wherever
+// the seam is.  The table is not trusted: a row without pixels or one that leaves the buffer gives zeros and reads nothing.
+__device__ __forceinline__ void mosaic_px(const uint8_t *__restrict__ src, size_t src_bytes, const yk_ragged_row_t *__restrict__ rows4, int cx,
+                                          int cy, int x, int y, uint8_t out[3]) {
+    const yk_ragged_row_t row = rows4[(x >= cx ? 1 : 0) + (y >= cy ? 2 : 0)];
+    out[0] = out[1] = out[2] = 0;
+    const bool ok = row.h > 0 && row.w > 0 && row.offset <= src_bytes && (size_t)row.h * row.w * 3 <= src_bytes - row.offset;
+    if (ok) letterbox_px(src + row.offset, row.h, row.w, row.scale, row.tx, row.ty, x, y, out);
+}
+
+// inv == NULL: the mosaic frame itself.  Otherwise the frame warped by the sample's inverse map exactly as letterbox_augment_u8_kernel warps
+// the letterbox: each of the four taps evaluates the mosaic pixel on the fly, no intermediate frame.
+__global__ void __launch_bounds__(256) mosaic_ragged_u8_kernel(const uint8_t *__restrict__ src, size_t src_bytes,
+                                                               const yk_ragged_row_t *__restrict__ table, const int32_t *__restrict__ centre,
+                                                               const double *__restrict__ inv, uint8_t *__restrict__ dst, int dh, int dw) {
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t per = (size_t)dh * dw;
+    if (idx >= per) return;
+    const yk_ragged_row_t *rows4 = table + (size_t)blockIdx.y * 4;
+    const int cx = min(max(centre[(size_t)blockIdx.y * 2], 0), dw), cy = min(max(centre[(size_t)blockIdx.y * 2 + 1], 0), dh);
+    const int x = (int)(idx % dw), y = (int)(idx / dw);
+    uint8_t *o = dst + ((size_t)blockIdx.y * per + idx) * 3;
+    if (!inv) {
+        uint8_t v[3];
+        mosaic_px(src, src_bytes, rows4, cx, cy, x, y, v);
+        o[0] = v[0];
+        o[1] = v[1];
+        o[2] = v[2];
+        return;
+    }
+    const double *m = inv + (size_t)blockIdx.y * 6;
+    const double c = m[0] * (double)x + m[1] * (double)y + m[2], r = m[3] * (double)x + m[4] * (double)y + m[5];
+    const double minc_f = floor(c), minr_f = floor(r), maxc_f = ceil(c), maxr_f = ceil(r);
+    const double dc = c - minc_f, dr = r - minr_f;
+    const double tr[4] = {minr_f, minr_f, maxr_f, maxr_f}, tc[4] = {minc_f, maxc_f, minc_f, maxc_f};
+    double t[4][3];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        uint8_t v[3] = {0, 0, 0};
+        if (tr[k] >= 0.0 && tr[k] < (double)dh && tc[k] >= 0.0 && tc[k] < (double)dw)      // compared as doubles: any M is safe
+            mosaic_px(src, src_bytes, rows4, cx, cy, (int)tc[k], (int)tr[k], v);
+        t[k][0] = v[0];
+        t[k][1] = v[1];
+        t[k][2] = v[2];
+    }
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+        const double top = (1.0 - dc) * t[0][ch] + dc * t[1][ch];
+        const double bottom = (1.0 - dc) * t[2][ch] + dc * t[3][ch];
+        o[ch] = (uint8_t)fmin(255.0, floor((1.0 - dr) * top + dr * bottom + 0.5));
+    }
+}
+
+extern "C" int yk_mosaic_params(yk_ragged_row_t *h_rows4, int cx, int cy, const double *gain4, int dst_h, int dst_w) {
+    if (!h_rows4 || !gain4 || dst_h <= 0 || dst_w <= 0) {
+        yk_set_error("yk_mosaic_params: bad argument");
+        return YK_ERR_ARG;
+    }
+    for (int k = 0; k < 4; ++k)
+        if (h_rows4[k].h <= 0 || h_rows4[k].w <= 0 || !(gain4[k] > 0.0) || !(gain4[k] <= 1.0e300)) {
+            yk_set_error("yk_mosaic_params: row %d is %d x %d, gain %g", k, (int)h_rows4[k].h, (int)h_rows4[k].w, gain4[k]);
+            return YK_ERR_ARG;
+        }
+    for (int k = 0; k < 4; ++k) {
+        double s;
+        int tx, ty;
+        letterbox_params(h_rows4[k].h, h_rows4[k].w, dst_h, dst_w, &s, &tx, &ty);
+        const double scale = gain4[k] * s;
+        const double pw = (double)h_rows4[k].w * scale, ph = (double)h_rows4[k].h * scale;
+        h_rows4[k].scale = scale;
+        h_rows4[k].tx = (k & 1) ? cx : cx - (int)ceil(pw);            // the corner nearest the seam sits at the seam
+        h_rows4[k].ty = (k & 2) ? cy : cy - (int)ceil(ph);
+    }
+    return YK_OK;
+}
+
+extern "C" int yk_mosaic_ragged_u8(const uint8_t *d_src, size_t src_bytes, const yk_ragged_row_t *d_table, const int32_t *d_centre,
+                                   const double *d_inv, int n, uint8_t *d_dst, int dst_h, int dst_w, void *stream) {
+    if (!d_src || !d_table || !d_centre || !d_dst || n <= 0 || src_bytes == 0 || dst_h <= 0 || dst_w <= 0) {
+        yk_set_error("yk_mosaic_ragged_u8: bad argument");
+        return YK_ERR_ARG;
+    }
+    if (yk_current_device() < 0) {
+        yk_set_error("yk_mosaic_ragged_u8: no HIP device");
+        return YK_ERR_NO_DEVICE;
+    }
+    const size_t per = (size_t)dst_h * dst_w;
+    for (int base = 0; base < n; base += 65535) {                                 // grid.y holds at most 65535 samples
+        const int m = n - base < 65535 ? n - base : 65535;
+        hipLaunchKernelGGL(mosaic_ragged_u8_kernel, dim3((unsigned)((per + 255) / 256), (unsigned)m), dim3(256), 0, (hipStream_t)stream, d_src,
+                           src_bytes, d_table + (size_t)base * 4, d_centre + (size_t)base * 2, d_inv ? d_inv + (size_t)base * 6 : nullptr,
+                           d_dst + (size_t)base * per * 3, dst_h, dst_w);
+    }
+    YK_HIP(hipGetLastError());
+    return YK_OK;
+}
+
 // ---- `img / np.max(img)` (tools/utils.py:405) for a batch of u8 frames -> fp32, for the TRAINING input pipeline (the inference
 // path fuses it into the stem conv).  numpy divides in float64 and the pipeline then casts to float32 (utils.py:436 py_function
 // output type): one correctly rounded quotient per element.

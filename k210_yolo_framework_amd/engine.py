@@ -518,6 +518,52 @@ def letterbox_ragged_u8(packed, table, dst_hw, stream=None, out=None):
     return out
 
 
+def check_ragged_rows(table, packed_bytes: int) -> np.ndarray:
+    """The rows of a host table (draw.RAGGED_DTYPE) as one flat copy, refused with YkError unless every row is a non-empty picture inside
+    the `packed_bytes` of its buffer: what the kernels would otherwise answer with zeros."""
+    from .draw import RAGGED_DTYPE
+    t = np.array(table, dtype=RAGGED_DTYPE, copy=True).reshape(-1)
+    bad = (t['h'] <= 0) | (t['w'] <= 0)
+    if bad.any():
+        i = int(np.nonzero(bad)[0][0])
+        raise YkError(f'ragged table: row {i} is {int(t["h"][i])} x {int(t["w"][i])}')
+    end = t['offset'].astype(object) + 3 * t['h'].astype(object) * t['w'].astype(object)
+    if len(t) and max(end) > int(packed_bytes):
+        raise YkError(f'ragged table: row {int(np.argmax(end))} ends at byte {max(end)} of a {int(packed_bytes)}-byte buffer')
+    return t
+
+
+def mosaic_ragged_u8(packed, table, centres, dst_hw, inv=None, stream=None, out=None):
+    """One training frame from four pictures per sample, the whole batch in one launch (yk_mosaic_ragged_u8; the rule is in mosaic.py):
+    `packed` cuda uint8 [bytes], the pictures of draw.pack_ragged; `table` the samples' rows in quadrant order with scale / tx / ty filled
+    (mosaic.ragged_rows), either a host array of draw.RAGGED_DTYPE [n, 4] or [4n] - checked here: a row without pixels, or one that leaves
+    the buffer, is refused - or cuda uint8 [4n, 40]; `centres` the seams (cx, cy), a host array or cuda int32 [n, 2]; `inv` each sample's
+    inverse map of augment.py, cuda float64 [n, 6] or [n, 2, 3], or None for no warp.  -> cuda uint8 [n, H, W, 3]."""
+    import torch
+    from .draw import RAGGED_DTYPE
+    require_gpu()
+    assert packed.is_cuda and packed.dtype == torch.uint8 and packed.is_contiguous() and packed.numel() > 0
+    with torch.cuda.stream(torch.cuda.current_stream() if stream is None else stream):
+        if not torch.is_tensor(table):
+            t = check_ragged_rows(table, packed.numel())
+            if len(t) == 0 or len(t) % 4:
+                raise YkError(f'mosaic table: {len(t)} rows, a sample has four')
+            table = torch.from_numpy(t.view(np.uint8).reshape(len(t), RAGGED_DTYPE.itemsize)).to(packed.device)
+        if not torch.is_tensor(centres):
+            centres = torch.from_numpy(np.ascontiguousarray(centres, np.int32)).to(packed.device)
+    assert table.is_cuda and table.dtype == torch.uint8 and table.is_contiguous() and table.dim() == 2 and table.device == packed.device
+    assert table.shape[1] == RAGGED_DTYPE.itemsize and table.shape[0] > 0 and table.shape[0] % 4 == 0, tuple(table.shape)
+    n = int(table.shape[0]) // 4
+    assert centres.is_cuda and centres.dtype == torch.int32 and centres.is_contiguous() and centres.numel() == 2 * n and centres.device == packed.device
+    if inv is not None:
+        assert inv.is_cuda and inv.dtype == torch.float64 and inv.is_contiguous() and inv.numel() == 6 * n and inv.device == packed.device
+    if out is None:
+        out = torch.empty((n, int(dst_hw[0]), int(dst_hw[1]), 3), dtype=torch.uint8, device=packed.device)
+    assert out.is_cuda and out.is_contiguous() and tuple(out.shape) == (n, int(dst_hw[0]), int(dst_hw[1]), 3), tuple(out.shape)
+    call('yk_mosaic_ragged_u8', packed, packed.numel(), table, centres, inv, n, out, out.shape[1], out.shape[2], _stream(stream))
+    return out
+
+
 def draw_detections_u8(packed, table, dets, counts, colormap, atlas, stream=None, max_pixels: Optional[int] = None):
     """Paint detections into the pictures of a ragged batch, in place and on the device (yk_draw_dets_u8; the rule is in include/yolo_hip.h):
     dets cuda fp32 [n, cap, 6] and counts cuda int32 [n] as decode_py / Pipeline.submit leave them, colormap cuda uint8 [n_colors, 3],

@@ -25,7 +25,12 @@ with fewer batches is observed whole and training starts with epoch 1); afterwar
 
 `--box_loss giou | diou | ciou` (`make train BOXLOSS=ciou`; not in the reference): the IoU-family box term, weighted by
 `--box_weight`, in place of the xy and wh terms, in the training step and in the validation loss alike; the step line and the epoch line
-then name the box term.  The default `mse` is the reference's loss."""
+then name the box term.  The default `mse` is the reference's loss.
+
+`--mosaic True` (`make train MOSAIC=True MOSAICPROB=1.0 MOSAICOFF=0`; not in the reference, mosaic.py): a share `--mosaic_prob`
+of the training samples is composed of four pictures of the training list by one HIP launch per batch (`InputPipeline(mosaic=...)`), draws keyed
+by (rand_seed, epoch, row); with `--augmenter True` the augmentation acts on the mosaic.  The last `--mosaic_off_epochs` epochs train on plain
+samples; validation is never mosaicked."""
 from __future__ import annotations
 
 import argparse
@@ -61,21 +66,41 @@ def synthetic_list(n: int, in_hw, class_num: int, seed: int):
     return out
 
 
-def batches(h: Helper, items, batch_size: int, rng, shuffle: bool, augment=None, with_boxes: bool = False):
+def batches(h: Helper, items, batch_size: int, rng, shuffle: bool, augment=None, with_boxes: bool = False, mosaic=None):
     """tools/utils.py:417-450: (normalised image [B,H,W,3] float32, labels per layer [B,h,w,A,5+C] float32).  augment=(seed, epoch):
     every sample augmented with its row of augment.param_table(seed, epoch, len(items)), like InputPipeline(augment=True).
-    with_boxes: a third element, each sample's boxes [n,5] (class, cx, cy, w, h) relative to the letterboxed frame."""
+    with_boxes: a third element, each sample's boxes [n,5] (class, cx, cy, w, h) relative to the letterboxed frame.
+    mosaic=(seed, epoch, prob): every sample composed by mosaic.py from its row of mosaic.param_table(seed, epoch, len(items)) on the host
+    (mosaic.compose_u8), like InputPipeline(mosaic=MosaicConfig(prob)); the augmentation, if any, then acts on the mosaic."""
     from . import augment as aug_mod
+    from . import mosaic as mosaic_mod
     table = None if augment is None else aug_mod.param_table(augment[0], augment[1], len(items))
+    mtable = None if mosaic is None else mosaic_mod.param_table(mosaic[0], mosaic[1], len(items))
+    hw = (int(h.in_hw[0][0]), int(h.in_hw[0][1]))
     order = rng.permutation(len(items)) if shuffle else np.arange(len(items))
+
+    def picture(i, cache):
+        if i not in cache:
+            img = items[i][0]
+            cache[i] = np.asarray(h._read_img(str(img)) if isinstance(img, (str, os.PathLike)) else img)[..., :3]
+        return cache[i]
     for s in range(0, len(order) - batch_size + 1, batch_size):             # drop_remainder=True (utils.py:447)
         xs, ys, bs = [], [[] for _ in range(len(h.anchors))], []
-        for i in order[s:s + batch_size]:
-            img, boxes = items[i]
-            if isinstance(img, (str, os.PathLike)):
-                img = h._read_img(str(img))
-            boxes = np.array(boxes, np.float64, copy=True)
-            img, boxes = h._process_img(img, boxes, is_training=table is not None, is_resize=True,
+        rows = order[s:s + batch_size]
+        if mtable is not None:
+            cache = {}
+            quads, centres, box_lists = mosaic_mod.plan(rows, mtable, lambda i: picture(i, cache).shape[:2], hw,
+                                                        boxes_of=lambda i: items[i][1], prob=mosaic[2])
+        for k, i in enumerate(rows):
+            if mtable is not None:
+                img = mosaic_mod.compose_u8([picture(int(j), cache) for j in quads[k]['item']], quads[k], centres[k], hw)
+                boxes = box_lists[k]
+            else:
+                img, boxes = items[i]
+                if isinstance(img, (str, os.PathLike)):
+                    img = h._read_img(str(img))
+                boxes = np.array(boxes, np.float64, copy=True)
+            img, boxes = h._process_img(img, boxes, is_training=table is not None, is_resize=mtable is None,
                                         aug=None if table is None else table[i])
             xs.append(img.astype(np.float32))
             bs.append(boxes)
@@ -91,7 +116,7 @@ def main(args, train_set, class_num, pre_ckpt, model_def, depth_multiplier, is_a
          rand_seed, max_nrof_epochs, init_learning_rate, learning_rate_decay_factor, obj_weight, noobj_weight, wh_weight,
          obj_thresh, iou_thresh, vaildation_split, log_dir, is_prune, initial_sparsity=0.5, final_sparsity=0.9, end_epoch=5,
          frequency=100, synthetic=0, max_steps=0, is_qat='False', qat_momentum=0.99, qat_observe=8, val_map='False', val_map_obj=0.05,
-         box_loss='mse', box_weight=1.0):
+         box_loss='mse', box_weight=1.0, is_mosaic='False', mosaic_prob=1.0, mosaic_off_epochs=0):
     import torch
     from .train import Trainer
     prune = is_prune == 'True'
@@ -99,6 +124,11 @@ def main(args, train_set, class_num, pre_ckpt, model_def, depth_multiplier, is_a
     if qat and int(qat_observe) < 1:
         raise engine.YkError(f'--qat_observe {qat_observe}: at least one batch must set the activation ranges before the first step')
     augment = is_augmenter == 'True'
+    mosaic = is_mosaic == 'True'
+    if mosaic and not 0.0 <= float(mosaic_prob) <= 1.0:
+        raise engine.YkError(f'--mosaic_prob {mosaic_prob}: a probability')
+    if mosaic and int(mosaic_off_epochs) < 0:
+        raise engine.YkError(f'--mosaic_off_epochs {mosaic_off_epochs}: a number of epochs')
     rank, world = int(os.environ.get('RANK', '0')), int(os.environ.get('WORLD_SIZE', '1'))
     local = int(os.environ.get('LOCAL_RANK', '0'))
     try:
@@ -111,6 +141,8 @@ def main(args, train_set, class_num, pre_ckpt, model_def, depth_multiplier, is_a
             raise engine.YkError('--qat True (quantisation-aware fine-tuning) runs in HIP kernels on the training step: no HIP device') from e
         if augment:
             raise engine.YkError('--augmenter True (imgaug OneOf, tools/utils.py:84-88) runs in the GPU input pipeline: no HIP device') from e
+        if mosaic:
+            raise engine.YkError('--mosaic True (four pictures per sample, mosaic.py) runs in the GPU input pipeline: no HIP device') from e
         raise
     torch.cuda.set_device(local)
     dist = None
@@ -164,17 +196,22 @@ def main(args, train_set, class_num, pre_ckpt, model_def, depth_multiplier, is_a
     tr = Trainer(spec, weights, h.anchors, per_rank, obj_thresh=obj_thresh, iou_thresh=iou_thresh, obj_weight=obj_weight,
                  noobj_weight=noobj_weight, wh_weight=wh_weight, lr=init_learning_rate, decay=learning_rate_decay_factor, device=local,
                  world_size=world, prune=schedule, qat=qat_cfg, box_loss=box_loss, box_weight=box_weight)
+    from .mosaic import MosaicConfig
     from .pipeline import InputPipeline
     if rank == 0:
         print(INFO, 'data augment is ', str(augment))                            # utils.py:418
+        print(INFO, f'mosaic is {mosaic}, mosaic_prob {float(mosaic_prob)}, mosaic_off_epochs {int(mosaic_off_epochs)}')
     steps, observed = 0, 0
     iou_box = box_loss != 'mse'
     for epoch in range(max_nrof_epochs):
         t0, seen, run, run_box = time.time(), 0, 0.0, 0.0
+        if rank == 0 and mosaic and int(mosaic_off_epochs) > 0 and epoch == max(max_nrof_epochs - int(mosaic_off_epochs), 0):
+            print(f'epoch {epoch + 1}: mosaic off from here on', flush=True)
         # tools/utils.py:417-450: each rank decodes only its rows of the global batch, on a thread pool, two batches ahead;
         # letterbox + normalise on the GPU (pipeline.py)
         pipe = InputPipeline(h, h.train_list, batch_size, rank, world, seed=rand_seed, epoch=epoch, shuffle=True, device=local,
-                             augment=augment)
+                             augment=augment,                                    # the last mosaic_off_epochs epochs train on plain samples
+                             mosaic=MosaicConfig(float(mosaic_prob)) if mosaic and epoch < max_nrof_epochs - int(mosaic_off_epochs) else None)
         try:                                                                    # an exception in the step must not leave the producer running
             for x, ys in pipe:
                 if qat and epoch == 0 and observed < int(qat_observe):           # the first batches of epoch 0 only set the activation ranges
@@ -313,6 +350,10 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument('--box_loss', type=str, choices=['mse', 'giou', 'diou', 'ciou'], default='mse',
                    help='box regression term: the xy / wh terms of the reference, or an IoU-family loss (DESIGN.md 3.14)')
     p.add_argument('--box_weight', type=float, default=1.0, help='weight of the IoU box term (not used with --box_loss mse)')
+    p.add_argument('--mosaic', type=str, choices=['True', 'False'], default='False',
+                   help='compose every training sample of four pictures (DESIGN.md 3.15); validation is never mosaicked')
+    p.add_argument('--mosaic_prob', type=float, default=1.0, help='share of the training samples that are mosaics')
+    p.add_argument('--mosaic_off_epochs', type=int, default=0, help='the last N epochs train without mosaic')
     return p
 
 
@@ -322,7 +363,8 @@ def cli(argv=None):
                 a.batch_size, a.rand_seed, a.max_nrof_epochs, a.init_learning_rate, a.learning_rate_decay_factor, a.obj_weight,
                 a.noobj_weight, a.wh_weight, a.obj_thresh, a.iou_thresh, a.vaildation_split, a.log_dir, a.is_prune,
                 a.prune_initial_sparsity, a.prune_final_sparsity, a.prune_end_epoch, a.prune_frequency, a.synthetic, a.max_steps,
-                a.qat, a.qat_momentum, a.qat_observe, a.val_map, a.val_map_obj, a.box_loss, a.box_weight)
+                a.qat, a.qat_momentum, a.qat_observe, a.val_map, a.val_map_obj, a.box_loss, a.box_weight, a.mosaic, a.mosaic_prob,
+                a.mosaic_off_epochs)
 
 
 if __name__ == '__main__':
