@@ -1624,7 +1624,29 @@ __global__ void __launch_bounds__(256) bias_add_kernel(float *y, size_t total, i
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i < total) y[i] += bias[i % C];
 }
+// The host checks of the small calls below: YK_ERR_ARG for a null tensor or a non-positive size, before the device is asked for and before
+// any launch.  A valid call launches what it always did.
+static int small_check(const char *who, bool ok) {
+    if (ok) return YK_OK;
+    yk_set_error("%s: bad argument", who);
+    return YK_ERR_ARG;
+}
+// MaxPool2D 2x2 'same': stride 1 or 2 and Ho x Wo = ceil(Hi / stride) x ceil(Wi / stride), the only geometry the kernels index correctly
+static int pool_check(const char *who, const void *a, const void *b, const void *c, int B, int Hi, int Wi, int C, int Ho, int Wo, int stride) {
+    if (const int rc = small_check(who, a && b && c && B > 0 && Hi > 0 && Wi > 0 && C > 0 && Ho > 0 && Wo > 0)) return rc;
+    if (stride != 1 && stride != 2) {
+        yk_set_error("%s: stride %d (1 or 2)", who, stride);
+        return YK_ERR_ARG;
+    }
+    if (Ho != (Hi + stride - 1) / stride || Wo != (Wi + stride - 1) / stride) {
+        yk_set_error("%s: output %d x %d of a %d x %d input at stride %d (padding 'same': %d x %d)", who, Ho, Wo, Hi, Wi, stride,
+                     (Hi + stride - 1) / stride, (Wi + stride - 1) / stride);
+        return YK_ERR_ARG;
+    }
+    return YK_OK;
+}
 extern "C" int yk_bias_add_f32(float *y, long long M, int C, const float *bias, void *stream) {
+    if (const int rc = small_check("yk_bias_add_f32", y && bias && M > 0 && C > 0)) return rc;
     const size_t total = (size_t)M * C;
     hipLaunchKernelGGL(bias_add_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, y, total, C, bias);
     YK_HIP(hipGetLastError());
@@ -1639,6 +1661,7 @@ __global__ void __launch_bounds__(256) colsum_from_stats_kernel(const double *__
     if (lane == 0) out[c] = (float)a;
 }
 extern "C" int yk_colsum_f32(const float *x, long long M, int C, float *out, void *stream) {
+    if (const int rc = small_check("yk_colsum_f32", x && out && M > 0 && C > 0)) return rc;
     int dev = yk_current_device();
     if (dev < 0) return YK_ERR_NO_DEVICE;
     int rpc, cwl;
@@ -1668,6 +1691,7 @@ __global__ void __launch_bounds__(256) upsample_bwd_kernel(const float *__restri
     dx[i] = dy[r0] + dy[r0 + C] + dy[r0 + rs] + dy[r0 + rs + C];
 }
 extern "C" int yk_upsample2x_bwd_f32(const float *dy, int B, int H, int W, int C, float *dx, void *stream) {
+    if (const int rc = small_check("yk_upsample2x_bwd_f32", dy && dx && B > 0 && H > 0 && W > 0 && C > 0)) return rc;
     const size_t total = (size_t)B * H * W * C;
     hipLaunchKernelGGL(upsample_bwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, dy, B, H, W, C, dx);
     YK_HIP(hipGetLastError());
@@ -1678,6 +1702,7 @@ __global__ void __launch_bounds__(256) axpy_kernel(size_t n, float a, const floa
     if (i < n) y[i] += a * x[i];
 }
 extern "C" int yk_axpy_f32(long long n, float a, const float *x, float *y, void *stream) {
+    if (const int rc = small_check("yk_axpy_f32", x && y && n > 0)) return rc;
     hipLaunchKernelGGL(axpy_kernel, dim3((unsigned)(((size_t)n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (size_t)n, a, x, y);
     YK_HIP(hipGetLastError());
     return YK_OK;
@@ -1697,6 +1722,7 @@ __global__ void __launch_bounds__(256) adam_kernel(size_t n, float *p, const flo
 }
 extern "C" int yk_adam_f32(long long n, float *p, const float *g, float *m, float *v, float lr, float decay, long long iterations,
                            float beta1, float beta2, float eps, float grad_scale, void *stream) {
+    if (const int rc = small_check("yk_adam_f32", p && g && m && v && n > 0 && iterations >= 0)) return rc;
     const double t = (double)iterations + 1.0;
     const double lr_t = (double)lr / (1.0 + (double)decay * (double)iterations) * sqrt(1.0 - pow((double)beta2, t)) / (1.0 - pow((double)beta1, t));
     hipLaunchKernelGGL(adam_kernel, dim3((unsigned)(((size_t)n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (size_t)n, p, g, m, v,
@@ -1752,6 +1778,7 @@ __global__ void __launch_bounds__(256) maxpool_bwd_kernel(const float *__restric
 }
 extern "C" int yk_maxpool2_fwd_f32(const float *x, int B, int Hi, int Wi, int C, int Ho, int Wo, int stride, float *y, uint8_t *argmax,
                                    void *stream) {
+    if (const int rc = pool_check("yk_maxpool2_fwd_f32", x, y, argmax, B, Hi, Wi, C, Ho, Wo, stride)) return rc;
     const size_t total = (size_t)B * Ho * Wo * C;
     hipLaunchKernelGGL(maxpool_fwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, B, Hi, Wi, C, Ho, Wo,
                        stride, y, argmax);
@@ -1760,6 +1787,7 @@ extern "C" int yk_maxpool2_fwd_f32(const float *x, int B, int Hi, int Wi, int C,
 }
 extern "C" int yk_maxpool2_bwd_f32(const float *dy, const uint8_t *argmax, int B, int Hi, int Wi, int C, int Ho, int Wo, int stride, float *dx,
                                    void *stream) {
+    if (const int rc = pool_check("yk_maxpool2_bwd_f32", dy, argmax, dx, B, Hi, Wi, C, Ho, Wo, stride)) return rc;
     const size_t total = (size_t)B * Hi * Wi * C;
     hipLaunchKernelGGL(maxpool_bwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, dy, argmax, B, Hi, Wi, C,
                        Ho, Wo, stride, dx);

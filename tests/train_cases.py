@@ -1,6 +1,6 @@
-"""Cases, float64 references and tolerances for the depthwise and BatchNorm training kernels of csrc/yk_train.hip, shared by
-tests/test_train_cases.py (CPU: the references and the case tables checked on their own) and tests/test_gpu_train_edges.py (the kernels).
-Nothing here touches a GPU.
+"""Cases, float64 references and tolerances for the depthwise and BatchNorm training kernels of csrc/yk_train.hip and for its small calls
+(max pool, upsample adjoint, bias add, column sum, axpy, Adam), shared by tests/test_train_cases.py (CPU: the references and the case
+tables checked on their own), tests/test_gpu_train_edges.py and tests/test_gpu_train_small.py (the kernels).  Nothing here touches a GPU.
 
 The host wrappers of yk_train.hip choose among several kernels by shape.  The planners below are Python copies of those choices, used
 ONLY to label the cases (which path, which edge), so that tests/test_train_cases.py can assert that every path stays covered."""
@@ -288,3 +288,330 @@ def bn_problem(case):
         if isinstance(a, np.ndarray):
             a.setflags(write=False)
     return out
+
+
+# ------------------------------------------------------------------------------------------------ the small calls
+# yk_maxpool2_{fwd,bwd}_f32, yk_upsample2x_bwd_f32, yk_bias_add_f32, yk_colsum_f32, yk_axpy_f32, yk_adam_f32 (tests/test_gpu_train_small.py).
+# yk_train.o is built without FMA contraction, so every written operation of these kernels is ONE IEEE rounding: beside the float64
+# reference each bitwise rule has a numpy float32 restatement, one operation per statement in the kernel's written order.
+U = 2.0 ** -24                    # unit roundoff of float32
+TINY = 2.0 ** -150                # half the spacing of the float32 subnormals: the most one rounding is off by below 2^-126
+
+
+def _freeze(out):
+    for a in out.values():
+        if isinstance(a, np.ndarray):
+            a.setflags(write=False)
+    return out
+
+
+# (B, Hi, Wi, C, stride): MaxPool2D 2x2, padding 'same' (bottom / right, -inf).  Odd and even sizes, a single row, a single column, one
+# window that is all padding but its first tap (1 x 1), C = 1, odd C; 13 x 21 x 16 at stride 1 is several workgroups.
+POOL_CASES = ([(2, hi, wi, c, s) for (hi, wi) in ((13, 20), (13, 21), (1, 7), (7, 1)) for s in (1, 2) for c in (1, 3, 16)]
+              + [(2, 2, 2, 3, 1), (2, 2, 2, 3, 2), (1, 1, 1, 1, 1), (1, 1, 1, 1, 2)])
+POOL_KINDS = ('a', 'b', 'c')      # a: {0, 6} (what ReLU6 leaves: ties everywhere), b: integers -3..3 with one plane of -inf, c: normal
+POOL_TIE_SHARE = 0.30
+
+
+def pool_geom(case):
+    B, Hi, Wi, C, stride = case
+    return B, Hi, Wi, C, -(-Hi // stride), -(-Wi // stride), stride
+
+
+def pool_taps(case, x):
+    """[4][B][Ho][Wo][C] float64: tap t = 2 * dy + dx of every window, -inf outside the input (bottom / right)."""
+    B, Hi, Wi, C, Ho, Wo, s = pool_geom(case)
+    xp = np.full((B, (Ho - 1) * s + 2, (Wo - 1) * s + 2, C), -np.inf)
+    xp[:, :Hi, :Wi] = x
+    return np.stack([xp[:, dy:dy + (Ho - 1) * s + 1:s, dx:dx + (Wo - 1) * s + 1:s] for dy in (0, 1) for dx in (0, 1)])
+
+
+def pool_ref(case, x):
+    """(y float64, arg uint8): the maximum of each window and the FIRST tap that holds it (np.argmax returns the first; a window of
+    -inf alone gives tap 0)."""
+    taps = pool_taps(case, x)
+    return taps.max(0), taps.argmax(0).astype(np.uint8)
+
+
+def pool_bwd_ref(case, arg, dy):
+    """dx float64: every dy goes to the one input its window's arg names; an input named by several windows sums them."""
+    B, Hi, Wi, C, Ho, Wo, s = pool_geom(case)
+    b, oy, ox, c = np.indices((B, Ho, Wo, C))
+    iy, ix = oy * s + (arg >> 1), ox * s + (arg & 1)
+    assert (iy < Hi).all() and (ix < Wi).all()                     # no window names a padding tap
+    dx = np.zeros((B, Hi, Wi, C))
+    np.add.at(dx, (b, iy, ix, c), np.asarray(dy, np.float64))
+    return dx
+
+
+def pool_max_wins(case):
+    """How many windows one input can win: 4 at stride 1 on an input of at least 2 x 2, 2 on a single row or column, 1 otherwise."""
+    B, Hi, Wi, C, stride = case
+    return min(2, Hi) * min(2, Wi) if stride == 1 else 1
+
+
+def pool_properties(case, x):
+    """From the reference alone: the share of windows whose maximum is held by more than one tap, the largest number of windows one
+    input wins, and whether some window is -inf on every tap."""
+    taps = pool_taps(case, x)
+    y, arg = pool_ref(case, x)
+    wins = pool_bwd_ref(case, arg, np.ones(arg.shape))
+    return dict(tie_share=float(((taps == y).sum(0) > 1).mean()), most_wins=int(wins.max()), all_inf=bool(np.isneginf(y).any()))
+
+
+def pool_tie_floor(case):
+    """The share of tied windows data (a) must reach.  A window with one valid tap cannot tie: the 1 x 1 input has no other window and is
+    exempt; everywhere else the floor is the 30 % the tests ask for."""
+    return 0.0 if case[1:3] == (1, 1) else POOL_TIE_SHARE
+
+
+def pool_inputs(case, kind):
+    """x [B][Hi][Wi][C] and dy [B][Ho][Wo][C] as float32.  Data (a) is drawn again (next seed) until the reference shows the properties
+    the tests need of it - ties in 30 % of the windows and, at stride 1, an input that wins as many windows as one can; on a handful of
+    windows a single draw misses them about as often as not.  The choice never looks at a kernel's output."""
+    B, Hi, Wi, C, Ho, Wo, s = pool_geom(case)
+    for seed in range(200):
+        rng = np.random.default_rng(1000 * seed + 31 * sum(case) + ord(kind))
+        if kind == 'a':
+            x = rng.integers(0, 2, (B, Hi, Wi, C)) * 6.0
+        elif kind == 'b':
+            x = rng.integers(-3, 4, (B, Hi, Wi, C)).astype(np.float64)
+            x[0, :, :, 0] = -np.inf
+        else:
+            x = rng.normal(size=(B, Hi, Wi, C))
+        dy = rng.normal(size=(B, Ho, Wo, C)) if kind == 'c' else rng.integers(-3, 4, (B, Ho, Wo, C))
+        if kind != 'a':
+            break
+        pr = pool_properties(case, x)
+        if pr['tie_share'] >= pool_tie_floor(case) and pr['most_wins'] == pool_max_wins(case):
+            break
+    else:
+        raise AssertionError(('no draw with the properties', case))
+    return x.astype(np.float32), dy.astype(np.float32)
+
+
+@functools.lru_cache(maxsize=None)
+def pool_problem(case, kind):
+    """Inputs and references of one case, computed once and shared (read-only).  dx: the float64 gradient; dx_abs: the same sum over
+    |dy|, which bounds every partial sum (exactness on integer dy, the rounding bound on normal dy)."""
+    x, dy = pool_inputs(case, kind)
+    y, arg = pool_ref(case, x)
+    out = dict(x=x, dy=dy, y=y, arg=arg, dx=pool_bwd_ref(case, arg, dy), dx_abs=pool_bwd_ref(case, arg, np.abs(dy)))
+    out['abs_sum'] = float(out['dx_abs'].max())
+    return _freeze(out)
+
+
+# (B, H, W, C) of dx; dy is [B][2H][2W][C]
+UPSAMPLE_CASES = [(2, 13, 20, 16), (1, 1, 1, 1), (3, 5, 7, 3)]
+
+
+def upsample_bwd_f32(dy, case):
+    """The kernel's written order in float32: dy[r0] + dy[r0 + C] + dy[r0 + rs] + dy[r0 + rs + C], one rounding per +."""
+    B, H, W, C = case
+    t = np.asarray(dy, np.float32).reshape(B, H, 2, W, 2, C)
+    s = t[:, :, 0, :, 0] + t[:, :, 0, :, 1]
+    s = s + t[:, :, 1, :, 0]
+    s = s + t[:, :, 1, :, 1]
+    assert s.dtype == np.float32
+    return s
+
+
+@functools.lru_cache(maxsize=None)
+def upsample_problem(case):
+    B, H, W, C = case
+    rng = np.random.default_rng(sum(case))
+    dy = rng.normal(size=(B, 2 * H, 2 * W, C)).astype(np.float32)
+    t = dy.astype(np.float64).reshape(B, H, 2, W, 2, C)
+    return _freeze(dict(dy=dy, dx32=upsample_bwd_f32(dy, case), dx64=t.sum((2, 4)), dx_abs=np.abs(t).sum((2, 4))))
+
+
+def colsum_chunking(M, C):
+    """bn_chunking() as yk_colsum_f32 uses it: (rows per chunk, chunks, rows in the last chunk).  A label, like the planners above."""
+    chunks, rpc, RL = bn_chunking(M, C)
+    return rpc, chunks, M - (chunks - 1) * rpc
+
+
+# (M, C): both sides of each lane_split boundary (16 | 17, 32 | 33), one column, several channel groups with a cut last one (75, 130);
+# per C fewer rows than row lanes (1, RL - 1), exactly RL and RL + 1; (8193, 16): 257 chunks, the last of ONE row; (4097, 75): 342
+# chunks of 12 rows, the last of 5 - both more chunks than the 64 lanes of colsum_from_stats_kernel's wave take in one pass.
+COLSUM_CASES = ([(m, c) for c in (1, 16, 17, 32, 33, 75, 130) for r in (256 >> lane_split(c),) for m in (1, r - 1, r, r + 1)]
+                + [(8193, 16), (4097, 75)])
+
+
+@functools.lru_cache(maxsize=None)
+def colsum_problem(case, lattice):
+    """x [M][C] float32 (integers -3..3, or normal with a scale and an offset per column), the float64 column sums and sums of |x|."""
+    M, C = case
+    rng = np.random.default_rng(7 + M + 100000 * C + lattice)
+    x = (rng.integers(-3, 4, (M, C)) if lattice else rng.normal(size=(M, C)) * rng.uniform(0.5, 3, C) + rng.normal(size=C)).astype(np.float32)
+    return _freeze(dict(x=x, sum=x.astype(np.float64).sum(0), abs_sum=np.abs(x.astype(np.float64)).sum(0)))
+
+
+def colsum_bound(M, ref, abs_sum):
+    """One float32 rounding of a float64 sum, plus what reordering a float64 sum of M terms can move it."""
+    return U * np.abs(ref) + M * 2.0 ** -53 * abs_sum
+
+
+BIAS_CASES = [(1, 1), (255, 1), (37, 7), (520, 16), (3, 257)]                 # (M, C)
+AXPY_NS = [1, 255, 256, 257, 10007]
+AXPY_AS = [-0.25, 0.1]                                                        # an exact product, and one that rounds
+AXPY_CASES = [(n, a) for n in AXPY_NS for a in AXPY_AS]
+
+
+def bias_add_f32(y, bias):
+    out = np.asarray(y, np.float32) + np.asarray(bias, np.float32)[None, :]
+    assert out.dtype == np.float32
+    return out
+
+
+def axpy_f32(a, x, y):
+    """y + a * x as the kernel writes it: the product rounded first, then the sum."""
+    prod = np.float32(a) * np.asarray(x, np.float32)
+    out = np.asarray(y, np.float32) + prod
+    assert prod.dtype == np.float32 and out.dtype == np.float32
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def bias_problem(case):
+    M, C = case
+    rng = np.random.default_rng(M + 1000 * C)
+    y, bias = rng.normal(size=(M, C)).astype(np.float32), rng.normal(size=C).astype(np.float32)
+    return _freeze(dict(y=y, bias=bias, out32=bias_add_f32(y, bias), out64=y.astype(np.float64) + bias.astype(np.float64)))
+
+
+@functools.lru_cache(maxsize=None)
+def axpy_problem(case):
+    n, a = case
+    rng = np.random.default_rng(n)
+    x, y = rng.normal(size=n).astype(np.float32), rng.normal(size=n).astype(np.float32)
+    a64 = float(np.float32(a))
+    return _freeze(dict(x=x, y=y, out32=axpy_f32(a, x, y), out64=y.astype(np.float64) + a64 * x.astype(np.float64),
+                        abs64=np.abs(y.astype(np.float64)) + np.abs(a64 * x.astype(np.float64))))
+
+
+# ------------------------------------------------------------------------------------------------ Adam
+# The Trainer's constants (train.py: apply_update), as the float32 values the C call receives
+ADAM_LR, ADAM_B1, ADAM_B2, ADAM_EPS = (float(np.float32(v)) for v in (5e-4, 0.9, 0.999, 1e-7))
+ADAM_NS = [1, 255, 256, 257, 10007]
+ADAM_ITERATIONS = [0, 1, 9, 999, 100000]
+ADAM_GSCALES = [1.0, 0.125, float(np.float32(1.0 / 3.0))]
+ADAM_DECAYS = [0.0, float(np.float32(0.01))]
+# (n, iterations, grad_scale, decay, warm): every (iterations, grad_scale, decay), with the lengths and the two starting states (m = v = 0 |
+# a previous state) cycling through them so that every (n, warm) pair occurs (tests/test_train_cases.py asserts it)
+ADAM_CASES = [(ADAM_NS[i % 5], it, gs, dc, bool(i % 2))
+              for i, (it, gs, dc) in enumerate((it, gs, dc) for it in ADAM_ITERATIONS for gs in ADAM_GSCALES for dc in ADAM_DECAYS)]
+# Four consecutive steps against float64: (n, first iteration, grad_scale, decay, warm).  grad_scale is a power of two here: g * grad_scale
+# is then exact and m and v each take the three roundings their bound counts (two products, one sum).  With 1/3 the rounded gradient
+# enters v twice and three roundings no longer bound it; that value is held bit for bit by the single-step cases instead.
+ADAM_RUN_CASES = [(10007, 0, 1.0, float(np.float32(0.01)), False), (257, 0, 0.125, 0.0, False), (10007, 999, 0.125, float(np.float32(0.01)), True),
+                  (255, 100000, 1.0, 0.0, True)]
+ADAM_STEPS = 4
+
+
+def adam_lr_t(lr, decay, iterations, b1, b2):
+    """lr_t in double exactly as yk_adam_f32 writes it (the arguments are the float32 values widened), then cast to float32.
+    math.pow and math.sqrt are the C library's, as in the host code."""
+    import math
+    t = float(iterations) + 1.0
+    lr_t = lr / (1.0 + decay * float(iterations)) * math.sqrt(1.0 - math.pow(b2, t)) / (1.0 - math.pow(b1, t))
+    return np.float32(lr_t)
+
+
+def adam_step_f32(p, g, m, v, iterations, gscale, decay, lr=ADAM_LR, b1=ADAM_B1, b2=ADAM_B2, eps=ADAM_EPS):
+    """adam_kernel in numpy float32, one rounding per statement, with C's left-to-right grouping of (1.f - b2) * gi * gi and of
+    lr_t * mi / (...).  Needs a correctly rounded float32 divide and square root, which numpy's are.  Returns (p, m, v)."""
+    f = np.float32
+    p, g, m, v = (np.asarray(a, f) for a in (p, g, m, v))
+    lr_t, b1, b2, eps = adam_lr_t(lr, decay, iterations, b1, b2), f(b1), f(b2), f(eps)
+    with np.errstate(under='ignore'):
+        gi = g * f(gscale)
+        c1 = f(1) - b1
+        mi = b1 * m
+        t1 = c1 * gi
+        mi = mi + t1
+        c2 = f(1) - b2
+        vi = b2 * v
+        t2 = c2 * gi
+        t2 = t2 * gi
+        vi = vi + t2
+        num = lr_t * mi
+        den = np.sqrt(vi)
+        den = den + eps
+        upd = num / den
+        pn = p - upd
+    assert all(a.dtype == f for a in (gi, mi, vi, upd, pn))
+    return pn, mi, vi
+
+
+class ScaledAdamRef:
+    """oracle.train_ref.AdamRef (Keras Adam in float64) with the gradient scale of yk_adam_f32 in front, on one flat tensor, starting at
+    a given iteration and state.  Also the sums of |terms| the per-step bounds scale with."""
+
+    def __init__(self, iterations, gscale, decay, m, v):
+        from oracle.train_ref import AdamRef
+        self.ref = AdamRef(ADAM_LR, decay=decay, b1=ADAM_B1, b2=ADAM_B2, eps=ADAM_EPS)
+        self.ref.it, self.gscale = int(iterations), float(gscale)
+        self.ref.m['p'], self.ref.v['p'] = np.asarray(m, np.float64), np.asarray(v, np.float64)
+
+    def step(self, p, g):
+        """One update; returns (p, m, v, bounds) with bounds = this step's rounding allowance for (p, m, v):
+        2^-23 (|p| + 4 |update|), 3 * 2^-24 (|b1 m| + |(1 - b1) g|), 3 * 2^-24 (|b2 v| + |(1 - b2) g^2|).  The last two are three
+        roundings each; a rounding in the subnormal range (the square of a gradient of 1e-20) is off by up to TINY = 2^-150 whatever
+        the value, so each of the three adds that."""
+        g = np.asarray(g, np.float64) * self.gscale
+        m0, v0, p0 = self.ref.m['p'], self.ref.v['p'], np.asarray(p, np.float64)
+        pn = self.ref.apply({'p': p0}, {'p': g})['p']
+        bounds = (2 * U * (np.abs(pn) + 4 * np.abs(pn - p0)), 3 * U * (np.abs(ADAM_B1 * m0) + np.abs((1 - ADAM_B1) * g)) + 3 * TINY,
+                  3 * U * (np.abs(ADAM_B2 * v0) + np.abs((1 - ADAM_B2) * g * g)) + 3 * TINY)
+        return pn, self.ref.m['p'], self.ref.v['p'], bounds
+
+
+def adam_gradients(rng, n):
+    """normal x 10^U{-4..1} as tests/test_gpu_train.py draws them; 5 % exact zeros and a few +-1e-20 (whose squares are subnormal)."""
+    g = (rng.normal(size=n) * 10.0 ** rng.integers(-4, 2, n)).astype(np.float32)
+    g[rng.random(n) < 0.05] = 0.0
+    k = min(n, 6)
+    g[rng.choice(n, k, replace=False)] = np.where(np.arange(k) % 2, -1e-20, 1e-20).astype(np.float32)
+    return g
+
+
+def adam_state(rng, n, warm):
+    """p, m, v float32.  warm: m and v as a few earlier steps leave them (v >= 0), with exact zeros kept where the tests need a fresh v."""
+    p = rng.normal(size=n).astype(np.float32)
+    if not warm:
+        return p, np.zeros(n, np.float32), np.zeros(n, np.float32)
+    m, v = np.zeros(n, np.float32), np.zeros(n, np.float32)
+    for it in range(3):
+        _, m, v = adam_step_f32(p, adam_gradients(rng, n), m, v, it, 1.0, 0.0)
+    return p, m, v
+
+
+@functools.lru_cache(maxsize=None)
+def adam_problem(case):
+    """One step: inputs and the float32 restatement's (p, m, v)."""
+    n, iterations, gscale, decay, warm = case
+    rng = np.random.default_rng(n + 13 * iterations + int(1000 * gscale) + int(warm))
+    p, m, v = adam_state(rng, n, warm)
+    g = adam_gradients(rng, n)
+    pn, mn, vn = adam_step_f32(p, g, m, v, iterations, gscale, decay)
+    return _freeze(dict(p=p, g=g, m=m, v=v, p32=pn, m32=mn, v32=vn))
+
+
+@functools.lru_cache(maxsize=None)
+def adam_run_problem(case):
+    """ADAM_STEPS consecutive steps: the gradients, and per step the float64 (p, m, v) with the ACCUMULATED bounds, and the float32
+    restatement's (p, m, v)."""
+    n, it0, gscale, decay, warm = case
+    rng = np.random.default_rng(5 + n + it0)
+    p0, m0, v0 = adam_state(rng, n, warm)
+    ref = ScaledAdamRef(it0, gscale, decay, m0, v0)
+    p64, acc, steps = p0.astype(np.float64), [0.0, 0.0, 0.0], []
+    p32, m32, v32 = p0, m0, v0
+    for k in range(ADAM_STEPS):
+        g = adam_gradients(rng, n)
+        p64, m64, v64, b = ref.step(p64, g)
+        acc = [a + x for a, x in zip(acc, b)]
+        p32, m32, v32 = adam_step_f32(p32, g, m32, v32, it0 + k, gscale, decay)
+        steps.append(_freeze(dict(g=g, p64=p64, m64=m64, v64=v64, bp=acc[0], bm=acc[1], bv=acc[2], p32=p32, m32=m32, v32=v32)))
+    return dict(p=p0, m=m0, v=v0, steps=steps)
