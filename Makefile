@@ -10,6 +10,7 @@
 #                    [QAT=True QATMOMENTUM=0.99 QATOBSERVE=8]: quantisation-aware fine-tuning, saves yolo_qat_model.h5 + yolo_qat_ranges.npz
 #                    [BOXLOSS=giou|diou|ciou BOXWEIGHT=1.0]: an IoU-family box loss in place of the xy / wh terms (default mse: the reference's loss)
 #                    [MOSAIC=True MOSAICPROB=1.0 MOSAICOFF=0]: four pictures per training sample, composed on the GPU; the last MOSAICOFF epochs without
+#                    [HSV=True HSVHUE=0.1 HSVSAT=1.5 HSVEXP=1.5 HSVPROB=1.0]: HSV colour jitter of every training frame, on the GPU (Darknet's recipe)
 #   make kmodel      CKPT=yolo_model.h5 OUT=yolo.kmodel|.kfpkg [SYNTHETIC=256 | CALIB=data/voc_img_ann.npy]: 8-bit K210 model, calibrated on the GPU
 #                    [RANGES=yolo_qat_ranges.npz]: the ranges a QAT run learned instead of a calibration
 #                    [CALIBMETHOD=minmax|percentile|mse CALIBPCT=99.99 CALIBBINS=2048]: minmax (default) takes each tensor's exact range; percentile
@@ -61,6 +62,11 @@ BOXWEIGHT     ?= 1.0
 MOSAIC        ?= False
 MOSAICPROB    ?= 1.0
 MOSAICOFF     ?= 0
+HSV           ?= False
+HSVHUE        ?= 0.1
+HSVSAT        ?= 1.5
+HSVEXP        ?= 1.5
+HSVPROB       ?= 1.0
 # eval only
 PRECISION     ?= f16x2
 ANN           ?= data/$(DATASET)_img_ann.npy
@@ -97,7 +103,8 @@ TRAIN_ARGS = --pre_ckpt $(CKPT) --augmenter $(IAA) --batch_size $(BATCH) --rand_
              --is_prune $(PRUNE) --prune_initial_sparsity $(INITSPARSITY) --prune_final_sparsity $(FINALSPARSITY) \
              --prune_end_epoch $(END_EPOCH) --prune_frequency $(FREQUENCY) --synthetic $(SYNTHETIC) \
              --qat $(QAT) --qat_momentum $(QATMOMENTUM) --qat_observe $(QATOBSERVE) --val_map $(VALMAP) \
-             --box_loss $(BOXLOSS) --box_weight $(BOXWEIGHT) --mosaic $(MOSAIC) --mosaic_prob $(MOSAICPROB) --mosaic_off_epochs $(MOSAICOFF)
+             --box_loss $(BOXLOSS) --box_weight $(BOXWEIGHT) --mosaic $(MOSAIC) --mosaic_prob $(MOSAICPROB) --mosaic_off_epochs $(MOSAICOFF) \
+             --hsv $(HSV) --hsv_hue $(HSVHUE) --hsv_sat $(HSVSAT) --hsv_exposure $(HSVEXP) --hsv_prob $(HSVPROB)
 ifeq ($(GPUS),1)
 LAUNCH = $(PY)
 else

@@ -333,6 +333,15 @@ int yk_mosaic_params(yk_ragged_row_t *h_rows4, int cx, int cy, const double *gai
  * YK_ERR_ARG; no device: YK_ERR_NO_DEVICE.  Can be recorded in a graph. */
 int yk_mosaic_ragged_u8(const uint8_t *d_src, size_t src_bytes, const yk_ragged_row_t *d_table, const int32_t *d_centre,
                         const double *d_inv, int n, uint8_t *d_dst, int dst_h, int dst_w, void *stream);
+/* ---- HSV colour jitter of finished training frames (k210_yolo_framework_amd/colour.py) ------
+ * In place on d_frames [n][h][w][3] u8: frame i gets the hue rotation dh (turns of the hue circle), the saturation gain gs and the exposure
+ * gain gv of d_params [n][3] float64 = (dh, gs, gv), in Smith's hexcone HSV, float64, the operations of colour.jitter_u8 in its order - the
+ * bytes are that function's, bit for bit.  One thread per pixel, which reads and writes only its own three bytes; one launch (one kernel
+ * node in a graph) up to 2^30 pixels, more are chunked; the pixel index is a size_t, n is not limited by a grid dimension.  The kernel does
+ * not trust the table: a row with a dh, gs or gv that is not finite, or with a negative gain, leaves its frame untouched; (0, 1, 1) changes
+ * no byte.  n == 0: YK_OK, nothing launched.  A NULL pointer with n > 0, n < 0, h <= 0, w <= 0 or 3*n*h*w beyond size_t: YK_ERR_ARG;
+ * no device: YK_ERR_NO_DEVICE.  Can be recorded in a graph. */
+int yk_hsv_jitter_u8(uint8_t *d_frames, int n, int h, int w, const double *d_params, void *stream);
 /* Draws detections INTO the pictures of a ragged batch, in place (inference.py's PIL loop plus keras_inference.py:137-174's label with
  * its filled background), by the painter's rule: for picture i and its rows k = 0 .. count_i - 1 in order, later paint over earlier:
  *   corners   t = max(0, floorf(top + 0.5f)), l likewise from left; b = min(h, floorf(bottom + 0.5f)), r = min(w, floorf(right + 0.5f))

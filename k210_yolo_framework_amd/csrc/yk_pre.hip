@@ -294,6 +294,74 @@ extern "C" int yk_mosaic_ragged_u8(const uint8_t *d_src, size_t src_bytes, const
     return YK_OK;
 }
 
+// ---- HSV colour jitter (k210_yolo_framework_amd/colour.py): every finished u8 frame gets its own hue rotation dh (turns),
+// saturation gain gs and exposure gain gv, in place, one thread per pixel, which reads its own three bytes and writes them back.  Float64,
+// the operations of colour.jitter_u8 in its order (this file is built with -ffp-contract=off), so the bytes are the host function's:
+//   V = max(max(r,g),b); m = min(min(r,g),b); d = V - m
+//   h = 0 when d == 0; else (g-b)/d when V == r; else 2 + (b-r)/d when V == g; else 4 + (r-g)/d
+//   h = h + 6*dh; h = h - 6*floor(h/6); h = 0 unless 0 <= h < 6
+//   S = d/V (0 when V == 0); S' = min(1, S*gs); V' = min(255, V*gv)
+//   i = floor(h); f = h - i; p = V'(1-S'); q = V'(1-S'f); t = V'(1-S'(1-f)); the six sectors; each channel min(255, floor(x + 0.5)).
+// No LDS, no transcendental.  The table is not trusted: a row that is not finite or has a negative gain leaves its frame untouched (every
+// comparison with a NaN is false), and no value of a row can move a thread off its own pixel.  A neutral row (0, 1, 1) returns early: the
+// arithmetic gives the same bytes.  The pixel index is a size_t over the whole batch, so neither n nor n*h*w meets a 16- or 32-bit limit.
+__global__ void __launch_bounds__(256) hsv_jitter_u8_kernel(uint8_t *__restrict__ frames, size_t first, size_t total, size_t per,
+                                                            const double *__restrict__ params) {
+    const size_t idx = first + (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const double *row = params + (idx / per) * 3;
+    const double dh = row[0], gs = row[1], gv = row[2];
+    const double big = 1.7976931348623157e308;                      // DBL_MAX: |x| <= big is "finite"
+    if (!(dh >= -big && dh <= big && gs >= 0.0 && gs <= big && gv >= 0.0 && gv <= big)) return;
+    if (dh == 0.0 && gs == 1.0 && gv == 1.0) return;
+    uint8_t *px = frames + idx * 3;
+    const double r = (double)px[0], g = (double)px[1], b = (double)px[2];
+    const double V = fmax(fmax(r, g), b), m = fmin(fmin(r, g), b), d = V - m;
+    double h = 0.0;
+    if (d > 0.0) h = V == r ? (g - b) / d : V == g ? 2.0 + (b - r) / d : 4.0 + (r - g) / d;
+    h = h + 6.0 * dh;
+    h = h - 6.0 * floor(h / 6.0);
+    if (!(h >= 0.0 && h < 6.0)) h = 0.0;
+    const double S = V > 0.0 ? d / V : 0.0;
+    const double Sg = S * gs, Vg = V * gv;
+    const double S2 = Sg < 1.0 ? Sg : 1.0, V2 = Vg < 255.0 ? Vg : 255.0;
+    const double fi = floor(h), f = h - fi;
+    const double p = V2 * (1.0 - S2), q = V2 * (1.0 - S2 * f), t = V2 * (1.0 - S2 * (1.0 - f));
+    const int i = (int)fi;                                            // 0 .. 5
+    const double R = i == 0 || i == 5 ? V2 : i == 1 ? q : i == 4 ? t : p;
+    const double G = i == 1 || i == 2 ? V2 : i == 0 ? t : i == 3 ? q : p;
+    const double B = i == 3 || i == 4 ? V2 : i == 2 ? t : i == 5 ? q : p;
+    px[0] = (uint8_t)fmin(255.0, floor(R + 0.5));
+    px[1] = (uint8_t)fmin(255.0, floor(G + 0.5));
+    px[2] = (uint8_t)fmin(255.0, floor(B + 0.5));
+}
+
+extern "C" int yk_hsv_jitter_u8(uint8_t *d_frames, int n, int h, int w, const double *d_params, void *stream) {
+    if (n < 0 || h <= 0 || w <= 0 || (n > 0 && (!d_frames || !d_params))) {
+        yk_set_error("yk_hsv_jitter_u8: bad argument");
+        return YK_ERR_ARG;
+    }
+    if (n == 0) return YK_OK;
+    const size_t per = (size_t)h * w;                                 // < 2^62
+    if ((size_t)n > (size_t)-1 / 3 / per) {                           // 3*n*h*w bytes must be addressable
+        yk_set_error("yk_hsv_jitter_u8: %d frames of %d x %d overflow size_t", n, h, w);
+        return YK_ERR_ARG;
+    }
+    if (yk_current_device() < 0) {
+        yk_set_error("yk_hsv_jitter_u8: no HIP device");
+        return YK_ERR_NO_DEVICE;
+    }
+    const size_t total = (size_t)n * per;
+    const size_t chunk = (size_t)1 << 30;                             // pixels per launch: one launch for any batch the pipeline makes
+    for (size_t first = 0; first < total; first += chunk) {
+        const size_t m = total - first < chunk ? total - first : chunk;
+        hipLaunchKernelGGL(hsv_jitter_u8_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_frames, first,
+                           first + m, per, d_params);
+    }
+    YK_HIP(hipGetLastError());
+    return YK_OK;
+}
+
 // ---- `img / np.max(img)` (tools/utils.py:405) for a batch of u8 frames -> fp32, for the TRAINING input pipeline (the inference
 // path fuses it into the stem conv).  numpy divides in float64 and the pipeline then casts to float32 (utils.py:436 py_function
 // output type): one correctly rounded quotient per element.

@@ -564,6 +564,29 @@ def mosaic_ragged_u8(packed, table, centres, dst_hw, inv=None, stream=None, out=
     return out
 
 
+def hsv_jitter_u8(frames, params, stream=None):
+    """HSV colour jitter of finished frames, in place (yk_hsv_jitter_u8; the rule is in colour.py): `frames` cuda uint8 [n, H, W, 3]
+    contiguous; `params` each frame's (dh, gs, gv), either cuda float64 [n, 3] - the kernel leaves the frame of a row that is not finite
+    or has a negative gain untouched - or a host array [n, 3], checked here (such a row is refused) and uploaded.  -> `frames`."""
+    import torch
+    from . import colour
+    require_gpu()
+    assert torch.is_tensor(frames) and frames.is_cuda and frames.dtype == torch.uint8 and frames.is_contiguous(), 'frames: cuda uint8, contiguous'
+    assert frames.dim() == 4 and frames.shape[-1] == 3 and frames.shape[1] > 0 and frames.shape[2] > 0, tuple(frames.shape)
+    n = int(frames.shape[0])
+    if not torch.is_tensor(params):
+        try:
+            host = colour.check_params(params, n)
+        except ValueError as e:
+            raise YkError(str(e)) from e
+        with torch.cuda.stream(torch.cuda.current_stream() if stream is None else stream):
+            params = torch.from_numpy(host).to(frames.device)
+    assert params.is_cuda and params.dtype == torch.float64 and params.is_contiguous() and params.device == frames.device
+    assert tuple(params.shape) == (n, 3), tuple(params.shape)
+    call('yk_hsv_jitter_u8', frames, n, frames.shape[1], frames.shape[2], params, _stream(stream))
+    return frames
+
+
 def draw_detections_u8(packed, table, dets, counts, colormap, atlas, stream=None, max_pixels: Optional[int] = None):
     """Paint detections into the pictures of a ragged batch, in place and on the device (yk_draw_dets_u8; the rule is in include/yolo_hip.h):
     dets cuda fp32 [n, cap, 6] and counts cuda int32 [n] as decode_py / Pipeline.submit leave them, colormap cuda uint8 [n_colors, 3],

@@ -218,9 +218,10 @@ class Helper(object):
         scale = np.full(2, (in_wh / img_wh).min())
         return scale, ((in_wh - img_wh * scale) / 2).astype(int)
 
-    def _process_img(self, img: np.ndarray, true_box, is_training: bool, is_resize: bool, aug=None):
+    def _process_img(self, img: np.ndarray, true_box, is_training: bool, is_resize: bool, aug=None, hsv=None):
         """utils.py:357-406: letterbox (bilinear, zero fill, truncating uint8 cast), with is_training the augmentation drawn from `aug`
         (`data_augmenter`; the training pipeline runs the same two resamples fused on the GPU), then `img / np.max(img)`.
+        hsv (not in the reference): the sample's (dh, gs, gv) of colour.param_table; the finished u8 frame is jittered before the division.
         The warp is skimage.transform.warp(order=1, mode='constant', cval=0, preserve_range=True) restated; pinned against the
         real skimage by tests/golden/letterbox_golden.npz."""
         if is_resize:
@@ -237,6 +238,9 @@ class Helper(object):
             if aug is None:
                 raise NotImplementedError('is_training=True augments: pass `aug`, the row of augment.param_table(seed, pass, rows)')
             img, true_box = self.data_augmenter(img, true_box, aug)
+        if hsv is not None:
+            from . import colour
+            img = colour.jitter_u8(np.asarray(img, np.uint8)[..., :3], hsv)
         img = img / np.max(img)
         return img, true_box
 

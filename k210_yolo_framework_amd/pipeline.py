@@ -27,6 +27,10 @@ their partners on the pool, each picture once however often the batch names it, 
 copies it with the table, the seams and - with augment=True - the inverse maps, and ONE `yk_mosaic_ragged_u8` launch writes the whole
 batch, pictures of any sizes, warped or not.  Every rank computes the partners from the epoch's shared table.  Without mosaic the path
 above runs untouched.
+
+hsv=HsvConfig(hue, sat, exposure, prob) jitters the colours of every finished frame (semantics in colour.py): the batch's (dh, gs, gv)
+rows of the epoch's table travel through a pinned slot, and ONE `yk_hsv_jitter_u8` launch works in place on the u8 frames of the whole
+batch, on either path above, between the geometric launch and `yk_normalise_u8`.  Without hsv no call is added.
 """
 from __future__ import annotations
 
@@ -40,6 +44,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import augment as aug_mod
+from . import colour as colour_mod
 from . import engine
 from . import mosaic as mosaic_mod
 from .helper import Helper
@@ -135,10 +140,11 @@ class InputPipeline:
 
     def __init__(self, h: Helper, items: Sequence, global_batch: int, rank: int = 0, world: int = 1, seed: int = 0, epoch: int = 0,
                  shuffle: bool = True, workers: int = 8, prefetch: int = 2, device: Optional[int] = None, augment: bool = False,
-                 mosaic: Optional[mosaic_mod.MosaicConfig] = None):
+                 mosaic: Optional[mosaic_mod.MosaicConfig] = None, hsv: Optional[colour_mod.HsvConfig] = None):
         import torch
         engine.require_gpu()
         self.h, self.items = h, items
+        self.hsv_table = colour_mod.param_table(seed, epoch, len(items), hsv) if hsv is not None else None       # [n_rows, 3], rank-independent
         self.mosaic = mosaic
         self.mosaic_table = mosaic_mod.param_table(seed, epoch, len(items)) if mosaic is not None else None      # rank-independent too
         self.table = aug_mod.param_table(seed, epoch, len(items)) if augment else None       # per (seed, epoch, row): rank-independent
@@ -249,6 +255,8 @@ class InputPipeline:
                             frames = out
                         else:
                             frames[torch.as_tensor(idx, device=self.dev)] = out
+                    if self.hsv_table is not None:                          # the frames are in batch order again: one launch, in place
+                        engine.hsv_jitter_u8(frames, self._upload('hsv', self.hsv_table[rows], torch.float64), stream=self.stream)
                     x = torch.empty((n, H, W, 3), dtype=torch.float32, device=self.dev)
                     engine.call('yk_normalise_u8', frames, n, H * W * 3, x, engine._stream(self.stream))
                     labels = []
@@ -310,6 +318,8 @@ class InputPipeline:
             d_centres = self._upload('mcen', np.ascontiguousarray(centres, np.int32), torch.int32)
             inv = None if M is None else self._upload('inv', M.reshape(n, 6), torch.float64)
             frames = engine.mosaic_ragged_u8(packed, d_table, d_centres, (H, W), inv=inv, stream=self.stream)
+            if self.hsv_table is not None:
+                engine.hsv_jitter_u8(frames, self._upload('hsv', self.hsv_table[rows], torch.float64), stream=self.stream)
             x = torch.empty((n, H, W, 3), dtype=torch.float32, device=self.dev)
             engine.call('yk_normalise_u8', frames, n, H * W * 3, x, engine._stream(self.stream))
             labels = []

@@ -30,7 +30,13 @@ then name the box term.  The default `mse` is the reference's loss.
 `--mosaic True` (`make train MOSAIC=True MOSAICPROB=1.0 MOSAICOFF=0`; not in the reference, mosaic.py): a share `--mosaic_prob`
 of the training samples is composed of four pictures of the training list by one HIP launch per batch (`InputPipeline(mosaic=...)`), draws keyed
 by (rand_seed, epoch, row); with `--augmenter True` the augmentation acts on the mosaic.  The last `--mosaic_off_epochs` epochs train on plain
-samples; validation is never mosaicked."""
+samples; validation is never mosaicked.
+
+`--hsv True` (`make train HSV=True HSVHUE=0.1 HSVSAT=1.5 HSVEXP=1.5 HSVPROB=1.0`; not in the reference, colour.py): a share
+`--hsv_prob` of the training frames gets a hue rotation of up to +-`--hsv_hue` turns and saturation and exposure gains between 1/x and x of
+`--hsv_sat` and `--hsv_exposure` (Darknet's recipe), by one HIP launch per batch on the finished frame (`InputPipeline(hsv=...)`), draws
+keyed by (rand_seed, epoch, row).  It acts after the letterbox, the augmentation and the mosaic, in every epoch (the `--mosaic_off_epochs`
+tail included); validation is never jittered."""
 from __future__ import annotations
 
 import argparse
@@ -66,16 +72,20 @@ def synthetic_list(n: int, in_hw, class_num: int, seed: int):
     return out
 
 
-def batches(h: Helper, items, batch_size: int, rng, shuffle: bool, augment=None, with_boxes: bool = False, mosaic=None):
+def batches(h: Helper, items, batch_size: int, rng, shuffle: bool, augment=None, with_boxes: bool = False, mosaic=None, hsv=None):
     """tools/utils.py:417-450: (normalised image [B,H,W,3] float32, labels per layer [B,h,w,A,5+C] float32).  augment=(seed, epoch):
     every sample augmented with its row of augment.param_table(seed, epoch, len(items)), like InputPipeline(augment=True).
     with_boxes: a third element, each sample's boxes [n,5] (class, cx, cy, w, h) relative to the letterboxed frame.
     mosaic=(seed, epoch, prob): every sample composed by mosaic.py from its row of mosaic.param_table(seed, epoch, len(items)) on the host
-    (mosaic.compose_u8), like InputPipeline(mosaic=MosaicConfig(prob)); the augmentation, if any, then acts on the mosaic."""
+    (mosaic.compose_u8), like InputPipeline(mosaic=MosaicConfig(prob)); the augmentation, if any, then acts on the mosaic.
+    hsv=(seed, epoch, HsvConfig): the finished u8 frame of every sample jittered on the host (colour.jitter_u8) with its row of
+    colour.param_table(seed, epoch, len(items), HsvConfig), like InputPipeline(hsv=HsvConfig); labels and boxes do not change."""
     from . import augment as aug_mod
+    from . import colour as colour_mod
     from . import mosaic as mosaic_mod
     table = None if augment is None else aug_mod.param_table(augment[0], augment[1], len(items))
     mtable = None if mosaic is None else mosaic_mod.param_table(mosaic[0], mosaic[1], len(items))
+    ctable = None if hsv is None else colour_mod.param_table(hsv[0], hsv[1], len(items), hsv[2])
     hw = (int(h.in_hw[0][0]), int(h.in_hw[0][1]))
     order = rng.permutation(len(items)) if shuffle else np.arange(len(items))
 
@@ -101,7 +111,7 @@ def batches(h: Helper, items, batch_size: int, rng, shuffle: bool, augment=None,
                     img = h._read_img(str(img))
                 boxes = np.array(boxes, np.float64, copy=True)
             img, boxes = h._process_img(img, boxes, is_training=table is not None, is_resize=mtable is None,
-                                        aug=None if table is None else table[i])
+                                        aug=None if table is None else table[i], hsv=None if ctable is None else ctable[i])
             xs.append(img.astype(np.float32))
             bs.append(boxes)
             for l, lab in enumerate(h.box_to_label(boxes)):
@@ -116,7 +126,8 @@ def main(args, train_set, class_num, pre_ckpt, model_def, depth_multiplier, is_a
          rand_seed, max_nrof_epochs, init_learning_rate, learning_rate_decay_factor, obj_weight, noobj_weight, wh_weight,
          obj_thresh, iou_thresh, vaildation_split, log_dir, is_prune, initial_sparsity=0.5, final_sparsity=0.9, end_epoch=5,
          frequency=100, synthetic=0, max_steps=0, is_qat='False', qat_momentum=0.99, qat_observe=8, val_map='False', val_map_obj=0.05,
-         box_loss='mse', box_weight=1.0, is_mosaic='False', mosaic_prob=1.0, mosaic_off_epochs=0):
+         box_loss='mse', box_weight=1.0, is_mosaic='False', mosaic_prob=1.0, mosaic_off_epochs=0, is_hsv='False', hsv_hue=0.1, hsv_sat=1.5,
+         hsv_exposure=1.5, hsv_prob=1.0):
     import torch
     from .train import Trainer
     prune = is_prune == 'True'
@@ -129,6 +140,17 @@ def main(args, train_set, class_num, pre_ckpt, model_def, depth_multiplier, is_a
         raise engine.YkError(f'--mosaic_prob {mosaic_prob}: a probability')
     if mosaic and int(mosaic_off_epochs) < 0:
         raise engine.YkError(f'--mosaic_off_epochs {mosaic_off_epochs}: a number of epochs')
+    hsv = is_hsv == 'True'
+    hsv_cfg = None
+    if hsv:
+        from .colour import HsvConfig
+        for flag, v, ok, want in (('--hsv_hue', float(hsv_hue), 0.0 <= float(hsv_hue) <= 0.5, 'turns of the hue circle, 0 to 0.5'),
+                                  ('--hsv_sat', float(hsv_sat), float(hsv_sat) >= 1.0, 'the largest saturation gain, at least 1'),
+                                  ('--hsv_exposure', float(hsv_exposure), float(hsv_exposure) >= 1.0, 'the largest exposure gain, at least 1'),
+                                  ('--hsv_prob', float(hsv_prob), 0.0 <= float(hsv_prob) <= 1.0, 'a probability')):
+            if not (np.isfinite(v) and ok):
+                raise engine.YkError(f'{flag} {v}: {want}')
+        hsv_cfg = HsvConfig(float(hsv_hue), float(hsv_sat), float(hsv_exposure), float(hsv_prob))
     rank, world = int(os.environ.get('RANK', '0')), int(os.environ.get('WORLD_SIZE', '1'))
     local = int(os.environ.get('LOCAL_RANK', '0'))
     try:
@@ -143,6 +165,8 @@ def main(args, train_set, class_num, pre_ckpt, model_def, depth_multiplier, is_a
             raise engine.YkError('--augmenter True (imgaug OneOf, tools/utils.py:84-88) runs in the GPU input pipeline: no HIP device') from e
         if mosaic:
             raise engine.YkError('--mosaic True (four pictures per sample, mosaic.py) runs in the GPU input pipeline: no HIP device') from e
+        if hsv:
+            raise engine.YkError('--hsv True (HSV colour jitter, colour.py) runs in the GPU input pipeline: no HIP device') from e
         raise
     torch.cuda.set_device(local)
     dist = None
@@ -201,6 +225,7 @@ def main(args, train_set, class_num, pre_ckpt, model_def, depth_multiplier, is_a
     if rank == 0:
         print(INFO, 'data augment is ', str(augment))                            # utils.py:418
         print(INFO, f'mosaic is {mosaic}, mosaic_prob {float(mosaic_prob)}, mosaic_off_epochs {int(mosaic_off_epochs)}')
+        print(INFO, f'hsv is {hsv}, hsv_hue {float(hsv_hue)}, hsv_sat {float(hsv_sat)}, hsv_exposure {float(hsv_exposure)}, hsv_prob {float(hsv_prob)}')
     steps, observed = 0, 0
     iou_box = box_loss != 'mse'
     for epoch in range(max_nrof_epochs):
@@ -211,7 +236,8 @@ def main(args, train_set, class_num, pre_ckpt, model_def, depth_multiplier, is_a
         # letterbox + normalise on the GPU (pipeline.py)
         pipe = InputPipeline(h, h.train_list, batch_size, rank, world, seed=rand_seed, epoch=epoch, shuffle=True, device=local,
                              augment=augment,                                    # the last mosaic_off_epochs epochs train on plain samples
-                             mosaic=MosaicConfig(float(mosaic_prob)) if mosaic and epoch < max_nrof_epochs - int(mosaic_off_epochs) else None)
+                             mosaic=MosaicConfig(float(mosaic_prob)) if mosaic and epoch < max_nrof_epochs - int(mosaic_off_epochs) else None,
+                             hsv=hsv_cfg)                                       # ... the colour jitter stays on in them
         try:                                                                    # an exception in the step must not leave the producer running
             for x, ys in pipe:
                 if qat and epoch == 0 and observed < int(qat_observe):           # the first batches of epoch 0 only set the activation ranges
@@ -354,6 +380,12 @@ def parser() -> argparse.ArgumentParser:
                    help='compose every training sample of four pictures (DESIGN.md 3.15); validation is never mosaicked')
     p.add_argument('--mosaic_prob', type=float, default=1.0, help='share of the training samples that are mosaics')
     p.add_argument('--mosaic_off_epochs', type=int, default=0, help='the last N epochs train without mosaic')
+    p.add_argument('--hsv', type=str, choices=['True', 'False'], default='False',
+                   help='HSV colour jitter of every training frame (DESIGN.md 3.16); validation is never jittered')
+    p.add_argument('--hsv_hue', type=float, default=0.1, help='largest hue rotation, in turns of the hue circle (0 to 0.5)')
+    p.add_argument('--hsv_sat', type=float, default=1.5, help='largest saturation gain x (at least 1): gains between 1/x and x')
+    p.add_argument('--hsv_exposure', type=float, default=1.5, help='largest exposure gain x (at least 1): gains between 1/x and x')
+    p.add_argument('--hsv_prob', type=float, default=1.0, help='share of the training frames that are jittered')
     return p
 
 
@@ -364,7 +396,7 @@ def cli(argv=None):
                 a.noobj_weight, a.wh_weight, a.obj_thresh, a.iou_thresh, a.vaildation_split, a.log_dir, a.is_prune,
                 a.prune_initial_sparsity, a.prune_final_sparsity, a.prune_end_epoch, a.prune_frequency, a.synthetic, a.max_steps,
                 a.qat, a.qat_momentum, a.qat_observe, a.val_map, a.val_map_obj, a.box_loss, a.box_weight, a.mosaic, a.mosaic_prob,
-                a.mosaic_off_epochs)
+                a.mosaic_off_epochs, a.hsv, a.hsv_hue, a.hsv_sat, a.hsv_exposure, a.hsv_prob)
 
 
 if __name__ == '__main__':
