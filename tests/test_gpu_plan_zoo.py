@@ -13,7 +13,20 @@ Measured worst error / E per zoo plan (one MI355X, B = 3): residual 0.558 (the s
 Sensitivity, carried out once and not committed: with xadd_kernel scaling its second operand by the FIRST operand's exponent, every spec
 with a standalone Add fails in both f16x2 tests at that launch - x:add_16 error / E = 2.5e7, x:add_20 6.3e6, x:add_32 5.9e7 - and pyramid,
 which has none, passes.  test_standalone_add_operands_have_different_exponents keeps that so: the operands' exponents differ by 2 or more
-for every image (residual -8 / -10, channels -9..-8 / -7 and -10 / -7, odd -5..-6 / -8)."""
+for every image (residual -8 / -10, channels -9..-8 / -7 and -10 / -7, odd -5..-6 / -8).
+
+The cluster zoo (zoo.CLUSTER_ZOO; the test_cluster_* functions below): the latency schedule's x:persist[...] and x:heads[...] on the
+instantiations yolo_mobilev1 0.75 at 224x320 leaves out, same criterion, no new tolerance.  zoo.persist_plan / zoo.heads_plan restate
+the builders' choice of a variant and can drift there; block count, start shape, phase count, barrier count and the heads' phase list
+are asserted against the launch names the builder emits.  Measured (one MI355X, B = 3), worst error / E per latency plan: cluster_wide
+0.076, cluster_ragged 0.085, cluster_ring 0.079, cluster_deep 0.088 (each on a plain conv launch); worst x:persist store 0.036, worst
+x:heads phase 0.042; throughput plans 0.133 / 0.131 / 0.150 / 0.118.  A store phase checked across TWO blocks sits at 0.002: that bound
+is too wide to see a lost cross product, which is why every block of a chain is stored (plan_zoo._chain).
+Sensitivity, carried out once and not committed, arithmetic only: (1) xp_pw_resident_loop without its w_hi * x_lo products where
+NSH == 2 (adirect 3, resident - cluster_ring's pw_2 alone): that store fails with error / E = 21.2 (0.89, passing, while the bound
+spanned two blocks); (2) xh_fill dropping the last K chunk where a phase has fewer chunks than the 8 members: all four specs fail at
+x:heads, error / E = 9.4e4 (wide, pre_mid), 1.4e5 (ragged, up_mid), 3.5e3 (ring, head_mid + head_out), 7.9e4 (deep, up_only).  Under
+either mutation tests/test_gpu_layers_x2.py::test_yolo_mobilev1_benched_network[latency-*] passes."""
 import re
 import time
 
@@ -34,7 +47,7 @@ _specs = {}
 
 def _spec(name):
     if name not in _specs:
-        _specs[name] = zoo.ZOO[name]()
+        _specs[name] = (zoo.ZOO.get(name) or zoo.CLUSTER_ZOO[name])()
     return _specs[name]
 
 
@@ -226,3 +239,77 @@ def test_refusals_by_name(case):
         plan.run_u8(torch.from_numpy(_frames(spec, B, seed=6)).cuda())
         plan.check()
         assert all(np.isfinite(o.cpu().numpy()).all() for o in plan.outputs())
+
+
+# ---- the latency schedule's two cluster launches on the specs of zoo.CLUSTER_ZOO ----------------------------------------------------
+NAME_MAX = 127                                                         # plan.launches() cuts a name there
+
+
+def _cluster_names(spec):
+    return zoo.persist_plan(spec)['name'][:NAME_MAX], zoo.heads_plan(spec)['name'][:NAME_MAX]
+
+
+def _assert_cluster_launches(spec, names):
+    """the builder took the chain and the convs the restatement says: block count, start shape, phase and barrier count, the heads' phase list"""
+    persist, heads = _cluster_names(spec)
+    assert [n for n in names if n.startswith('x:persist')] == [persist], names
+    assert [n for n in names if n.startswith('x:heads')] == [heads], names
+    assert names[-1] == heads
+
+
+@pytest.mark.parametrize('name', list(zoo.CLUSTER_ZOO))
+def test_cluster_launches_within_their_bound(name):
+    """Latency schedule, the strict criterion of tests/layerwise.py, then the same plan with YK_CLUSTER_WT=1: every output bit for bit."""
+    t0 = time.time()
+    spec, w = _spec(name)
+    names, rows, over = _layerwise(spec, w, B, 'latency')
+    _report(f'zoo {name} {spec.in_hw[0]}x{spec.in_hw[1]} B={B} latency', names, rows, over, t0)
+    _assert_cluster_launches(spec, names)
+    t0 = time.time()
+    names_wt, rows_wt, over = _layerwise(spec, w, B, 'latency', env={'YK_CLUSTER_WT': '1'})
+    _report(f'zoo {name} B={B} latency YK_CLUSTER_WT=1', names_wt, rows_wt, over, t0)
+    assert names_wt == names
+
+
+@pytest.mark.parametrize('name', list(zoo.CLUSTER_ZOO))
+def test_cluster_specs_as_plain_launches(name):
+    """The same shapes in the throughput schedule (fused blocks up to 384 input channels, fused heads, K-split convs) and in the f16 plan."""
+    t0 = time.time()
+    spec, w = _spec(name)
+    names, rows, over = _layerwise(spec, w, B)
+    _report(f'zoo {name} B={B} throughput', names, rows, over, t0)
+    assert not any(n.startswith(('x:persist', 'x:heads')) for n in names)
+    n, names = _layerwise_f16(spec, w, B)
+    print(f'\nzoo {name} f16: {n} tensors checked; {names}')
+    assert n == len(names) - 1 - _count(names, r'/splitk\d+$') + _count(names, r'^splitk_reduce\d+_\d+\+conv')
+
+
+@pytest.mark.parametrize('name', list(zoo.CLUSTER_ZOO))
+def test_cluster_launches_do_not_depend_on_the_batch(name):
+    """Bitwise: the batch twice, the same plan with YK_CLUSTER_WT=1, image 0 alone in a plan for two, and images 0..2 of a batch of 40 (more
+    images than one pass of the 32 clusters).  plan.check() behind every run: a cluster that cannot assemble is an error, not a wait."""
+    import torch
+    from k210_yolo_framework_amd import engine
+    spec, w = _spec(name)
+    frames = _frames(spec, B, seed=5)
+    big = np.concatenate([frames, np.random.default_rng(6).integers(0, 256, (40 - B, *frames.shape[1:]), dtype=np.uint8)])
+
+    def run(f, max_batch, env=None):
+        f = torch.from_numpy(np.ascontiguousarray(f)).cuda()
+        with _switches(env), engine.Plan(spec, w, max_batch=max_batch, precision='f16x2', schedule='latency') as plan:
+            _assert_cluster_launches(spec, [l[0] for l in plan.launches()])
+            outs = []
+            for _ in range(2):
+                plan.run_u8(f)
+                plan.check()
+                outs.append([o[:f.shape[0]].cpu().numpy().copy() for o in plan.outputs()])
+        for a, b in zip(*outs):
+            assert np.isfinite(a).all() and float(np.abs(a).max()) > 0
+            assert a.tobytes() == b.tobytes(), 'two runs of the same batch differ'
+        return outs[0]
+    first = run(frames, B)
+    for what, other in (('YK_CLUSTER_WT=1', run(frames, B, {'YK_CLUSTER_WT': '1'})), ('image 0 alone', run(frames[:1], 2)),
+                        ('a batch of 40', run(big, 40))):
+        for a, b in zip(first, other):
+            k = min(len(a), len(b), B)
+            assert a[:k].tobytes() == b[:k].tobytes(), f'{what}: differs from the batch of {B}'

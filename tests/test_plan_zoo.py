@@ -184,3 +184,96 @@ def test_refusal_graphs_are_well_formed_for_the_oracle():
         x = oracle.normalise_u8(_frames(spec, 1, seed=1)).astype(np.float64)
         ref, _ = xb.run_chain(spec, w, {0: x}, bounds=False)
         assert all(np.isfinite(ref[t]).all() for t in spec.outputs)
+
+
+# ---- the cluster zoo: which instantiations of x:persist / x:heads each spec reaches (zoo.persist_plan, zoo.heads_plan) ----------------
+# persist: (nrb, ncb, adirect, resident, ppw, WR, WC) per block, worked out by hand from x_build_persist; stores: an XP_STORE behind the
+# block; heads: (variant, nrb, ncb, nchunk, tail, pre_barrier) per phase in the launch's order, from x_build_heads_from
+CLUSTER_EXPECT = {
+    'cluster_wide': dict(
+        src_f32=True,
+        persist=[(20, 1, 0, 0, 6, 8, 1), (5, 1, 2, 0, 3, 8, 1), (5, 5, 2, 0, 3, 4, 2), (5, 2, 2, 0, 3, 8, 1), (5, 8, 2, 0, 4, 2, 4)],
+        stores=[1, 1, 1, 1, 1],
+        heads=[(2, 5, 4, 4, 0, 0), (2, 5, 1, 2, 0, 1), (1, 5, 12, 4, 75, 0)]),
+    'cluster_ragged': dict(
+        src_f32=False,
+        persist=[(9, 3, 1, 1, 3, 8, 1), (9, 4, 0, 0, 4, 4, 2), (9, 3, 1, 0, 3, 8, 1), (3, 5, 0, 0, 3, 4, 2), (3, 2, 3, 0, 3, 4, 2),
+                 (3, 8, 0, 0, 3, 1, 8)],
+        stores=[1, 1, 1, 1, 1, 1],
+        heads=[(2, 3, 4, 4, 0, 0), (1, 3, 3, 4, 18, 0), (1, 3, 5, 4, 0, 0), (0, 9, 8, 10, 80, 0)]),
+    'cluster_ring': dict(
+        src_f32=True,
+        persist=[(6, 1, 0, 0, 3, 8, 1), (6, 2, 3, 1, 3, 8, 1), (6, 12, 0, 0, 5, 2, 4)],
+        stores=[1, 1, 1],
+        heads=[(0, 6, 8, 4, 18, 1)]),
+    'cluster_deep': dict(
+        src_f32=True,
+        persist=[(5, 3, 2, 0, 3, 8, 1), (5, 1, 2, 0, 3, 8, 1), (5, 10, 4, 0, 4, 2, 4)],
+        stores=[1, 1, 1],
+        heads=[(2, 5, 2, 4, 0, 0), (2, 5, 4, 4, 18, 0), (1, 5, 8, 4, 18, 0)]),
+}
+
+
+@pytest.fixture(scope='module')
+def cluster_specs():
+    return {n: f() for n, f in zoo.CLUSTER_ZOO.items()}
+
+
+@pytest.mark.parametrize('name', list(zoo.CLUSTER_ZOO))
+def test_cluster_spec_reaches_the_expected_instantiations(cluster_specs, name):
+    spec, _ = cluster_specs[name]
+    want = CLUSTER_EXPECT[name]
+    p, h = zoo.persist_plan(spec), zoo.heads_plan(spec)
+    assert p and h
+    assert [tuple(b[k] for k in ('nrb', 'ncb', 'adirect', 'resident', 'ppw', 'WR', 'WC')) for b in p['blocks']] == want['persist']
+    assert [int(b['store']) for b in p['blocks']] == want['stores'] and p['src_f32'] == want['src_f32']
+    assert [tuple(q[k] for k in ('variant', 'nrb', 'ncb', 'nchunk', 'tail', 'pre_barrier')) for q in h['phases']] == want['heads']
+    # the chain is made of launches the latency schedule keeps apart: fewer than 128 output pixels, or more than 6 steps of 32 channels
+    for b in p['blocks']:
+        assert b['H'] * b['W'] < 128 or b['cin'] >= 224
+        assert b['cin'] % 64 == 0 and b['n'] % 128 == 0 and b['nrb'] + b['ncb'] <= 24
+    assert spec.in_hw[0] <= 64 and spec.in_hw[1] <= 96
+
+
+def test_cluster_zoo_covers_every_target(cluster_specs):
+    hit = {n: zoo.cluster_targets(s) for n, (s, _) in cluster_specs.items()}
+    union = set().union(*hit.values())
+    for t in sorted(zoo.CLUSTER_TARGETS):
+        print(f'{t:60s} {[n for n in hit if t in hit[n]]}')
+    assert zoo.CLUSTER_TARGETS <= union, sorted(zoo.CLUSTER_TARGETS - union)
+    # both kinds of chain input, and a heads phase that reads what the persistent launch stored in mid-chain
+    assert 'chain from fp32 planes' in union and 'chain from a split tensor' in union
+    spec, _ = cluster_specs['cluster_wide']
+    p, h = zoo.persist_plan(spec), zoo.heads_plan(spec)
+    mid = {spec.ops[b['op'] + 1]['out'] for b in p['blocks'][:-1] if b['store']}
+    assert any(set(q['srcs']) & mid for q in h['phases'])
+
+
+def test_the_benched_network_reaches_none_of_the_targets():
+    """yolo_mobilev1 0.75 at 224x320 is the one network tests/test_gpu_layers_x2.py holds to the strict criterion in the latency schedule;
+    the restatement reproduces its two launch names (tests/golden/x2_plan_launches.json), and none of the targets is among what it reaches."""
+    import json
+    from pathlib import Path
+    spec = ns.yolo_mobilev1((224, 320, 3), 3, 20, alpha=0.75)
+    p, h = zoo.persist_plan(spec), zoo.heads_plan(spec)
+    golden = json.dumps(json.loads((Path(__file__).parent / 'golden' / 'x2_plan_launches.json').read_text()))
+    assert json.dumps(p['name'])[1:-1] in golden and json.dumps(h['name'][:127])[1:-1] in golden
+    assert [(b['nrb'], b['ncb'], b['adirect'], b['resident']) for b in p['blocks']] == [(18, 3, 1, 1)] * 5 + [(5, 6, 2, 0)] * 2
+    assert [(q['variant'], q['nrb'], q['nchunk']) for q in h['phases']] == [(2, 5, 24), (1, 5, 24), (0, 18, 16)]
+    assert not zoo.cluster_targets(spec) & zoo.CLUSTER_TARGETS
+
+
+@pytest.mark.parametrize('name', list(zoo.CLUSTER_ZOO))
+def test_float64_chain_agrees_with_fp32_interpreter_on_the_cluster_zoo(cluster_specs, name):
+    spec, w = cluster_specs[name]
+    cp = spec.compile_plan(w)
+    x32 = oracle.normalise_u8(_frames(spec, 3, seed=3))
+    want = [op['out'] for op in spec.ops]
+    got = oracle.net_forward_ex(cp, {0: x32}, range(len(spec.ops)), want, emulate_f16=False)
+    ref, _ = xb.run_chain(spec, w, {0: x32.astype(np.float64)}, bounds=False)
+    for t, g in zip(want, got):
+        r = ref[t]
+        scale = max(float(np.abs(r).max()), 1e-6)
+        assert g.shape == r.shape and float(np.abs(g - r).max()) / scale < 2e-5, (t, float(np.abs(g - r).max()), scale)
+    for t in spec.outputs:
+        assert float(np.abs(ref[t]).max()) > 1e-3
