@@ -17,6 +17,7 @@
 #                    and mse clip it from a histogram taken on the GPU in a second pass over the calibration images (not with RANGES=)
 #   make eval        CKPT=yolo_model.h5|yolo.kmodel [PRECISION=f16x2|f16|kpu] [ANN=data/voc_img_ann.npy | SYNTHETIC=256] [EVALOBJ=0.05] [VOC07=True]:
 #                    VOC mAP of the checkpoint, network and metric on the GPU; prints the per-class AP table, writes eval.json beside CKPT
+#                    [METRIC=coco]: also the COCO-style AP (IoU .50:.95, AP50, AP75, small / medium / large, AR) and a `coco` object in eval.json
 #                    (make train VALMAP=True appends val_mAP to every epoch line)
 #   make detect      CKPT=yolo_model.h5|yolo.kmodel SRC=folder|list.txt [OUTDIR=out] [DRAW=True|False] [PRECISION=...] [DECODE=pil|gpu] [ENCODE=pil|gpu QUALITY=75]: every
 #                    picture of SRC through the pipeline; writes OUTDIR/detections.json and, with DRAW=True, OUTDIR/<stem>_res.jpg (boxes and
@@ -72,6 +73,7 @@ PRECISION     ?= f16x2
 ANN           ?= data/$(DATASET)_img_ann.npy
 EVALOBJ       ?= 0.05
 VOC07         ?= False
+METRIC        ?=
 # detect only
 SRC           ?= data
 OUTDIR        ?= out
@@ -140,7 +142,7 @@ kmodel:
 eval:
 	$(PY) keras_eval.py $(CKPT) --train_set $(DATASET) --class_num $(CLSNUM) --model_def $(MODEL) --depth_multiplier $(DEPTHMUL) \
 		--image_size $(IMGSIZE) --output_size $(OUTSIZE) --iou_thresh $(IOUTHRESH) --precision $(PRECISION) --obj_thresh $(EVALOBJ) \
-		--voc07 $(VOC07) $(if $(filter-out 0,$(SYNTHETIC)),--synthetic $(SYNTHETIC),--ann $(ANN))
+		--voc07 $(VOC07) $(if $(filter-out 0,$(SYNTHETIC)),--synthetic $(SYNTHETIC),--ann $(ANN)) $(if $(METRIC),--metric $(METRIC))
 
 # every picture of SRC (a folder or a text list) -> OUTDIR/detections.json + OUTDIR/<stem>_res.jpg; batches of BATCH pictures of any sizes
 detect:

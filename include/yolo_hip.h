@@ -726,6 +726,37 @@ int yk_map_eval(const float *d_rows, const int32_t *d_img, long long n_rows, int
                 size_t work_bytes, uint8_t *d_flags, int32_t *d_n_gt, int32_t *d_n_det, int32_t *d_tp, int32_t *d_fp, double *d_ap, double *d_map,
                 void *stream);
 
+/* ---- the COCO-style metric on the same rows (map_gpu.MapEvaluator.coco_result): AP over n_thr IoU thresholds, n_area
+ * object-size ranges and n_rec recall points, by the rule of coco_eval.evaluate (restated from pycocotools' public source; parity with
+ * pycocotools' own numbers is unpinned).  Conventions, row formats, class reading and finiteness as yk_map_eval: the caller's buffers,
+ * every launch on `stream`, no allocation, no synchronisation, float64 without contraction, no floating-point atomics: two runs give the
+ * same bits.  d_iou_thr [n_thr], d_area [n_area][2] (a0, a1), d_rec_thr [n_rec]: float64, device.
+ * yk_map_coco_workspace_bytes  bytes of d_work that yk_map_coco_eval needs for these sizes.
+ * yk_map_coco_eval   A ground-truth box is IGNORED under range a if it is difficult or its area (bottom - top) * (right - left) is < a0
+ *                    or > a1.  Per (image, class) group, detections in descending score (-0.0 == +0.0; ties in row order); only the first
+ *                    max_dets take part, the rest get flag 0 under every pair and are counted nowhere.  Per (t, a), each detection in
+ *                    that order looks at the boxes of its image and class not yet matched under (t, a) with IoU >= min(t, 1 - 1e-10)
+ *                    (box_iou's operation order, no plus_one): the non-ignored one with the largest IoU if any, otherwise the ignored
+ *                    one with the largest IoU; the HIGHEST index on equal IoU; the chosen box is matched under (t, a), ignored or not.
+ *                    Matched to a non-ignored box: flag 1; to an ignored box: flag 0; unmatched with its own area outside [a0, a1]:
+ *                    flag 0; unmatched otherwise: flag 2.  (yk_map_eval's rule takes the best box, taken or not; this one falls back
+ *                    to the next free box.)
+ *                    Per (class k, t, a), rows of the class in descending score (ties in row order), tp / fp the running counts of
+ *                    flags 1 / 2, npig the non-ignored boxes of the class under a: rc = tp / npig, pr = tp / ((fp + tp) + 2^-52),
+ *                    pr <- its reverse running maximum; precision[t][r][k][a] = pr at the first row with rc >= d_rec_thr[r] (0 if
+ *                    there is none), recall[t][k][a] = the last rc (0 without rows); npig == 0: both -1 (absent).
+ *                    -> d_flags [n_area][n_thr][n_rows] (uint8, row order); d_npig [class_num][n_area], d_n_det [class_num] (rows that
+ *                    take part), int32; d_precision [n_thr][n_rec][class_num][n_area], d_recall [n_thr][class_num][n_area], float64;
+ *                    d_summary [10]: AP, AP at the thresholds == 0.5 and == 0.75, AP of ranges 1, 2, 3, AR, AR of ranges 1, 2, 3 - each
+ *                    the mean of the entries > -1 of its slice (range 0 where none is named), NaN if there is none; d_ap_class
+ *                    [class_num]: the same mean over t and r for range 0.  The means are added in a fixed order.
+ *                    n_thr * n_area > 64, n_rec > 1024, the sizes yk_map_eval refuses, or a workspace that is too small: YK_ERR_ARG. */
+int yk_map_coco_workspace_bytes(long long n_rows, long long n_gt_rows, int n_img, int class_num, int n_thr, int n_area, int n_rec, size_t *bytes);
+int yk_map_coco_eval(const float *d_rows, const int32_t *d_img, long long n_rows, int n_img, const double *d_gt, const int32_t *d_gt_off,
+                     const uint8_t *d_difficult, long long n_gt_rows, int class_num, const double *d_iou_thr, int n_thr, const double *d_area,
+                     int n_area, const double *d_rec_thr, int n_rec, int max_dets, void *d_work, size_t work_bytes, uint8_t *d_flags,
+                     int32_t *d_npig, int32_t *d_n_det, double *d_precision, double *d_recall, double *d_summary, double *d_ap_class, void *stream);
+
 /* ---- anchor k-means with many restarts in one call (datatools.run_kmeans_gpu): datatools.run_kmeans for each of
  * `restarts` initial centroid sets, independently, on boxes d_wh [n][2] (w, h; finite and > 0, which the caller has checked).  Distance
  * 1 - IoU of boxes centred at the origin, float64 in datatools.fake_iou_distance's operation order without contraction; assignment = argmin,

@@ -12,6 +12,9 @@
 //   curve     one workgroup per class over order A: integer inclusive scan of tp / fp, precision and recall in float64, the monotone
 //             envelope as a reverse max-scan, AP as the sum over the rows where recall steps (the true positives), or the 11-point form.
 //
+// The COCO rule (coco_eval.evaluate) reuses the keys, the sorts and the class offsets; its matcher keeps, per ground-truth box, one
+// bit per (threshold, area range) pair, its curve kernel runs once per (class, pair) and looks the 101 recall points up: see `the COCO rule` below.
+//
 // Everything is integer or order-independent (max) except the AP sum, which is added in a fixed order: two runs give the same bits.
 // This translation unit is compiled with -ffp-contract=off: one rounding per reference operation.
 #include "yk_common.h"
@@ -313,6 +316,276 @@ __global__ void map_mean_kernel(const double *__restrict__ ap, int class_num, do
     }
 }
 
+// ---- the COCO rule (coco_eval.evaluate) ---------------------------------------------------------------------------------
+// T thresholds x A area ranges = at most 64 (t, a) pairs; pair (t, a) is BIT a * T + t of every 64-bit mask and PLANE a * T + t of the flags.
+constexpr int COCO_MAX_BITS = 64;
+constexpr int COCO_MAX_REC = 1024;
+
+// per ground-truth box: the pairs under which it is ignored (difficult, or its area outside the range); per (class, range) the boxes that are not
+__global__ __launch_bounds__(MAP_BLOCK) void coco_gt_kernel(const double *__restrict__ gt, const uint8_t *__restrict__ difficult, long long n_gt_rows,
+                                                            int class_num, const double *__restrict__ area_rng, int T, int A,
+                                                            uint64_t *__restrict__ ign, int32_t *__restrict__ npig) {
+    const uint64_t row = T >= 64 ? ~0ull : ((1ull << T) - 1ull);
+    for (long long g = (long long)blockIdx.x * MAP_BLOCK + threadIdx.x; g < n_gt_rows; g += (long long)gridDim.x * MAP_BLOCK) {
+        const double *t = gt + (size_t)g * 6;
+        const int c = class_of(t[5], class_num);
+        const double area = (t[2] - t[0]) * (t[3] - t[1]);
+        const bool hard = difficult[g] != 0;
+        uint64_t m = 0;
+        for (int a = 0; a < A; ++a) {
+            if (hard || area < area_rng[2 * a] || area > area_rng[2 * a + 1]) m |= row << (a * T);
+            else if (c < class_num) atomicAdd(&npig[c * A + a], 1);
+        }
+        ign[g] = m;
+    }
+}
+
+// the larger of two candidates: a non-ignored box before an ignored one (bit 63 of the key), then the IoU (its bits: IoU >= +0), then the HIGHER index
+__device__ __forceinline__ bool coco_after(uint64_t ka, int ia, uint64_t kb, int ib) { return ka > kb || (ka == kb && ia > ib); }
+
+// One wave per (image, class) group; its detections are sequential.  A chunk of 64 boxes of the image is spread over the lanes: the IoU of the
+// detection with a lane's box is computed once and serves every pair.  Per pair the candidates (class, IoU >= threshold, not matched under the
+// pair) are found by a ballot: none - nothing to do; one - it is the winner; more - a wave max over (key, index).  Lane b keeps the winner of pair
+// b across the chunks, writes pair b's flag, and the lane that owns the winning box sets bit b of its mask (a box is always read and written
+// by the same lane: program order is the matching order).  A detection none of whose boxes reaches the lowest threshold skips all of that.
+__global__ __launch_bounds__(MAP_BLOCK) void coco_match_kernel(const float *__restrict__ rows, const uint64_t *__restrict__ key_b, const uint32_t *__restrict__ row_b,
+                                                               long long n, int n_img, int class_num, const double *__restrict__ gt,
+                                                               const int32_t *__restrict__ gt_off, const uint64_t *__restrict__ ign, uint64_t *matched,
+                                                               const double *__restrict__ iou_thr, const double *__restrict__ area_rng, int T, int A,
+                                                               int max_dets, uint8_t *__restrict__ flags, int32_t *__restrict__ n_det) {
+    __shared__ double sh_thr[COCO_MAX_BITS], sh_a0[COCO_MAX_BITS], sh_a1[COCO_MAX_BITS];
+    const int nb = T * A;
+    if ((int)threadIdx.x < nb) {
+        sh_thr[threadIdx.x] = fmin(iou_thr[threadIdx.x % T], 1.0 - 1e-10);
+        sh_a0[threadIdx.x] = area_rng[2 * (threadIdx.x / T)];
+        sh_a1[threadIdx.x] = area_rng[2 * (threadIdx.x / T) + 1];
+    }
+    __syncthreads();
+    double thr_min = sh_thr[0];
+    for (int t = 1; t < T; ++t) thr_min = fmin(thr_min, sh_thr[t]);
+    const int lane = threadIdx.x & (YK_WAVE - 1);
+    const bool pair = lane < nb;
+    const double my_a0 = pair ? sh_a0[lane] : 0.0, my_a1 = pair ? sh_a1[lane] : 0.0;
+    const long long n_groups = (long long)n_img * class_num;
+    for (long long q = (long long)blockIdx.x * MAP_WAVES + (threadIdx.x / YK_WAVE); q < n_groups; q += (long long)gridDim.x * MAP_WAVES) {
+        const int i = (int)(q / class_num), c = (int)(q % class_num);
+        const uint64_t gkey = (uint64_t)i * (uint64_t)(class_num + 1) + (uint64_t)c;
+        const long long lo = lower_bound_u64(key_b, n, gkey << 32);
+        long long hi = lower_bound_u64(key_b, n, (gkey + 1) << 32);
+        if (hi - lo > (long long)max_dets) hi = lo + max_dets;           // the rest takes no part: flag 0 (the memset), counted nowhere
+        if (hi <= lo) continue;
+        if (lane == 0) atomicAdd(&n_det[c], (int32_t)(hi - lo));
+        const int g0 = gt_off[i], g1 = gt_off[i + 1];
+        for (long long k = lo; k < hi; ++k) {
+            const uint32_t r = row_b[k];
+            const float *d = rows + (size_t)r * 6;
+            const double b0 = (double)d[0], b1 = (double)d[1], b2 = (double)d[2], b3 = (double)d[3];
+            const double area = (b2 - b0) * (b3 - b1);
+            uint64_t win_key = 0;                                         // lane b: the winner of pair b so far
+            int win = -1;
+            for (int gb = g0; gb < g1; gb += YK_WAVE) {
+                const int g = gb + lane;
+                double iou = -1.0;
+                uint64_t ig = 0, mt = 0;
+                if (g < g1) {
+                    const double *t = gt + (size_t)g * 6;
+                    if (class_of(t[5], class_num) == c) {
+                        const double t0 = t[0], t1 = t[1], t2 = t[2], t3 = t[3];
+                        const double ih = fmin(b2, t2) - fmax(b0, t0);
+                        const double iw = fmin(b3, t3) - fmax(b1, t1);
+                        const double inter = fmax(ih, 0.0) * fmax(iw, 0.0);
+                        const double areas = (t2 - t0) * (t3 - t1);
+                        const double uni = area + areas - inter;
+                        iou = uni > 0.0 ? inter / uni : 0.0;
+                        if (iou == 0.0) iou = 0.0;                        // -0.0 -> +0.0: the key below is the bits of a value >= +0
+                    }
+                }
+                const bool near = iou >= thr_min;
+                if (__ballot(near) == 0ull) continue;                     // wave-uniform
+                if (near) {
+                    ig = ign[g];
+                    mt = matched[g];
+                }
+                const uint64_t iou_bits = near ? (uint64_t)__double_as_longlong(iou) : 0ull;
+                for (int b = 0; b < nb; ++b) {
+                    const bool cand = near && iou >= sh_thr[b] && !((mt >> b) & 1ull);
+                    const uint64_t who = __ballot(cand);
+                    if (who == 0ull) continue;                            // wave-uniform
+                    uint64_t key = cand ? (iou_bits | (((ig >> b) & 1ull) ? 0ull : (1ull << 63))) : 0ull;
+                    int idx = cand ? g : -1;
+                    if (who & (who - 1ull)) {
+#pragma unroll
+                        for (int s = YK_WAVE / 2; s > 0; s >>= 1) {
+                            const uint64_t ok = (uint64_t)__shfl_xor((unsigned long long)key, s, YK_WAVE);
+                            const int oi = __shfl_xor(idx, s, YK_WAVE);
+                            if (coco_after(ok, oi, key, idx)) {
+                                key = ok;
+                                idx = oi;
+                            }
+                        }
+                    } else {
+                        const int src = __ffsll((unsigned long long)who) - 1;
+                        key = (uint64_t)__shfl((unsigned long long)key, src, YK_WAVE);
+                        idx = __shfl(idx, src, YK_WAVE);
+                    }
+                    if (lane == b && coco_after(key, idx, win_key, win)) {   // chunks ascend: a later chunk's index is higher
+                        win_key = key;
+                        win = idx;
+                    }
+                }
+            }
+            // lane b: pair b's outcome
+            if (pair) {
+                uint8_t f;
+                if (win >= 0) f = (win_key >> 63) ? 1 : 0;
+                else f = (area < my_a0 || area > my_a1) ? 0 : 2;
+                flags[(size_t)lane * (size_t)n + r] = f;
+            }
+            // the owner of a winning box marks it under the pair
+            uint64_t won = __ballot(win >= 0);
+            while (won) {
+                const int b = __ffsll((unsigned long long)won) - 1;
+                won &= won - 1ull;
+                const int m = __shfl(win, b, YK_WAVE);
+                if (((m - g0) & (YK_WAVE - 1)) == lane) matched[m] |= 1ull << b;
+            }
+        }
+    }
+}
+
+// One workgroup per (class, pair) over order A: the integer scan of tp / fp as ap_kernel's; per recall point the smallest integer tp with
+// (double)tp / npig >= the point and the first row that reaches it (a binary search of the scan); the reverse max-scan of the precision, written
+// over the scan; then the look-ups.
+__global__ __launch_bounds__(MAP_BLOCK) void coco_curve_kernel(const uint32_t *__restrict__ row_a, const int32_t *__restrict__ cls_off, const uint8_t *__restrict__ flags,
+                                                               long long n_rows, const int32_t *__restrict__ npig, const double *__restrict__ rec_thr, int n_rec,
+                                                               int class_num, int T, int A, uint64_t *cum_all, double *__restrict__ precision,
+                                                               double *__restrict__ recall) {
+    __shared__ uint64_t sh_u[MAP_BLOCK];
+    __shared__ double sh_d[MAP_BLOCK];
+    __shared__ uint64_t carry_u;
+    __shared__ double carry_d;
+    __shared__ int32_t sh_row[COCO_MAX_REC];
+    const int nb = T * A;
+    const int c = blockIdx.x / nb, b = blockIdx.x % nb, ta = b / T, tt = b % T, t = threadIdx.x;
+    const long long lo = cls_off[c], n = (long long)cls_off[c + 1] - lo;
+    const uint8_t *fl = flags + (size_t)b * (size_t)n_rows;
+    uint64_t *cum = cum_all + (size_t)b * (size_t)n_rows;
+    const int ng = npig[c * A + ta];
+    double *pout = precision + ((size_t)tt * n_rec * class_num + c) * A + ta;          // + r * class_num * A
+    const size_t pstep = (size_t)class_num * A;
+    if (ng == 0) {                                                                      // absent
+        for (int r = t; r < n_rec; r += MAP_BLOCK) pout[(size_t)r * pstep] = -1.0;
+        if (t == 0) recall[((size_t)tt * class_num + c) * A + ta] = -1.0;
+        return;
+    }
+    if (t == 0) carry_u = 0ull;
+    __syncthreads();
+    for (long long base = 0; base < n; base += MAP_BLOCK) {
+        const long long k = base + t;
+        uint64_t v = 0;
+        if (k < n) {
+            const uint8_t f = fl[row_a[lo + k]];
+            v = f == 1 ? (1ull << 32) : (f == 2 ? 1ull : 0ull);
+        }
+        const uint64_t inc = block_scan(v, sh_u, AddU64()) + carry_u;
+        if (k < n) cum[lo + k] = inc;
+        __syncthreads();
+        if (t == MAP_BLOCK - 1) carry_u = inc;
+        __syncthreads();
+    }
+    const double dgt = (double)ng;
+    const long long total = (long long)(carry_u >> 32);
+    if (t == 0) recall[((size_t)tt * class_num + c) * A + ta] = n > 0 ? (double)total / dgt : 0.0;
+    // the row of every recall point: searchsorted(rc, point, 'left'), or -1 past the end
+    for (int r = t; r < n_rec; r += MAP_BLOCK) {
+        const double want = rec_thr[r];
+        double est = ceil(want * dgt);                                                  // an estimate; the two loops make it exact
+        if (!(est >= 0.0)) est = 0.0;
+        if (est > dgt + 1.0) est = dgt + 1.0;
+        long long tp = (long long)est;
+        while (tp > 0 && (double)(tp - 1) / dgt >= want) --tp;
+        while (tp <= (long long)ng && !((double)tp / dgt >= want)) ++tp;
+        int32_t row = -1;
+        if (tp <= total && n > 0) {
+            long long a0 = 0, a1 = n;                                                   // the first row whose tp count is >= tp
+            while (a0 < a1) {
+                const long long mid = a0 + ((a1 - a0) >> 1);
+                if ((long long)(cum[lo + mid] >> 32) < tp) a0 = mid + 1; else a1 = mid;
+            }
+            row = (int32_t)a0;
+        }
+        sh_row[r] = row;
+    }
+    if (t == 0) carry_d = 0.0;
+    __syncthreads();
+    // backward: thread 0 holds the LAST row of a tile (ap_kernel); the envelope replaces the scan
+    const long long tiles = (n + MAP_BLOCK - 1) / MAP_BLOCK;
+    for (long long tile = tiles - 1; tile >= 0; --tile) {
+        const long long k = tile * MAP_BLOCK + (MAP_BLOCK - 1 - t);
+        double prec = 0.0;
+        if (k < n) {
+            const uint64_t cu = cum[lo + k];
+            const double ctp = (double)(uint32_t)(cu >> 32);
+            const double cfp = (double)(uint32_t)(cu & 0xffffffffull);
+            prec = ctp / ((cfp + ctp) + 2.220446049250313e-16);
+        }
+        const double env = fmax(block_scan(prec, sh_d, MaxF64()), carry_d);
+        if (k < n) cum[lo + k] = (uint64_t)__double_as_longlong(env);
+        __syncthreads();
+        if (t == MAP_BLOCK - 1) carry_d = env;
+        __syncthreads();
+    }
+    for (int r = t; r < n_rec; r += MAP_BLOCK) {
+        const int32_t row = sh_row[r];
+        pout[(size_t)r * pstep] = row >= 0 ? __longlong_as_double((long long)cum[lo + row]) : 0.0;
+    }
+}
+
+// The summary: one workgroup per figure (0 ap, 1 ap50, 2 ap75, 3-5 ap small / medium / large, 6 ar, 7-9 ar small / medium / large, 10 + k
+// ap_class[k]): the mean of the entries > -1 of its slice, NaN if there are none.  Every thread adds its entries in index order, then a fixed tree.
+__global__ __launch_bounds__(MAP_BLOCK) void coco_summary_kernel(const double *__restrict__ precision, const double *__restrict__ recall,
+                                                                 const double *__restrict__ iou_thr, int T, int n_rec, int class_num, int A,
+                                                                 double *__restrict__ summary, double *__restrict__ ap_class) {
+    __shared__ double sh_s[MAP_BLOCK];
+    __shared__ unsigned long long sh_n[MAP_BLOCK];
+    const int fig = blockIdx.x, t = threadIdx.x;
+    const bool is_ar = fig >= 6 && fig < 10, one_class = fig >= 10;
+    const int ta = one_class ? 0 : (fig < 3 ? 0 : (fig < 6 ? fig - 2 : fig - 6));
+    const int k0 = one_class ? fig - 10 : 0, nk = one_class ? 1 : class_num;
+    const double only = fig == 1 ? 0.5 : 0.75;
+    const bool pick = fig == 1 || fig == 2;
+    const int per_t = is_ar ? nk : n_rec * nk;
+    double s = 0.0;
+    unsigned long long cnt = 0;
+    if (ta < A) {
+        for (long long e = t; e < (long long)T * per_t; e += MAP_BLOCK) {
+            const int tt = (int)(e / per_t), rest = (int)(e % per_t);
+            if (pick && !(iou_thr[tt] == only)) continue;
+            const int k = k0 + rest % nk, r = rest / nk;
+            const double v = is_ar ? recall[((size_t)tt * class_num + k) * A + ta]
+                                   : precision[(((size_t)tt * n_rec + r) * class_num + k) * A + ta];
+            if (v > -1.0) {
+                s += v;
+                ++cnt;
+            }
+        }
+    }
+    sh_s[t] = s;
+    sh_n[t] = cnt;
+    __syncthreads();
+    for (int w = MAP_BLOCK / 2; w > 0; w >>= 1) {
+        if (t < w) {
+            sh_s[t] += sh_s[t + w];
+            sh_n[t] += sh_n[t + w];
+        }
+        __syncthreads();
+    }
+    if (t == 0) {
+        const double m = sh_n[0] ? sh_s[0] / (double)sh_n[0] : __builtin_nan("");
+        if (one_class) ap_class[k0] = m; else summary[fig] = m;
+    }
+}
+
 // ---- workspace ------------------------------------------------------------------------------------------------------------------------
 struct Work {
     size_t key_a_in, key_a, key_b_in, key_b, iota, row_a, row_b, cum, taken, cls_off, sort_tmp, sort_bytes, total;
@@ -384,6 +657,49 @@ int check_append(const char *who, const void *src, const void *cnt, long long n_
     }
     if (have + n_new > capacity) {
         yk_set_error("%s: %lld + %lld rows do not fit the buffer of %lld", who, have, n_new, capacity);
+        return YK_ERR_ARG;
+    }
+    return YK_OK;
+}
+
+// the COCO evaluation's workspace: yk_map_eval's (keys, sorts, class offsets) followed by its own
+struct CocoWork {
+    Work w;
+    size_t ign, matched, cum, total;
+};
+
+int coco_layout(long long n_rows, long long n_gt_rows, int n_img, int class_num, int nb, CocoWork *cw) {
+    const int rc = layout(n_rows, n_gt_rows, n_img, class_num, &cw->w);
+    if (rc != YK_OK) return rc;
+    const size_t R = (size_t)(n_rows > 0 ? n_rows : 1), G = (size_t)(n_gt_rows > 0 ? n_gt_rows : 1);
+    size_t at = cw->w.total;
+    cw->ign = at;
+    at += up256(G * 8);
+    cw->matched = at;
+    at += up256(G * 8);
+    cw->cum = at;
+    at += up256(R * 8 * (size_t)nb);
+    cw->total = at;
+    return YK_OK;
+}
+
+int coco_check(const char *who, long long n_rows, long long n_gt_rows, int n_img, int class_num, int n_thr, int n_area, int n_rec) {
+    const int rc = check_sizes(who, n_rows, n_gt_rows, n_img, class_num);
+    if (rc != YK_OK) return rc;
+    if (n_thr <= 0 || n_area <= 0 || n_rec <= 0) {
+        yk_set_error("%s: bad argument", who);
+        return YK_ERR_ARG;
+    }
+    if ((long long)n_thr * n_area > COCO_MAX_BITS) {
+        yk_set_error("%s: %d IoU thresholds x %d area ranges: more than %d pairs", who, n_thr, n_area, COCO_MAX_BITS);
+        return YK_ERR_ARG;
+    }
+    if (n_rec > COCO_MAX_REC) {
+        yk_set_error("%s: %d recall points: more than %d", who, n_rec, COCO_MAX_REC);
+        return YK_ERR_ARG;
+    }
+    if ((long long)class_num * n_thr * n_area > 0x7fffffffLL) {
+        yk_set_error("%s: %d classes x %d pairs: more than 2^31-1 curves", who, class_num, n_thr * n_area);
         return YK_ERR_ARG;
     }
     return YK_OK;
@@ -488,6 +804,83 @@ extern "C" int yk_map_eval(const float *d_rows, const int32_t *d_img, long long 
     hipLaunchKernelGGL(ap_kernel, dim3((unsigned)class_num), dim3(MAP_BLOCK), 0, st, row_a, cls_off, d_flags, d_n_gt, use_07_metric ? 1 : 0, cum, d_n_det,
                        d_tp, d_fp, d_ap);
     hipLaunchKernelGGL(map_mean_kernel, dim3(1), dim3(1), 0, st, d_ap, class_num, d_map);
+    YK_HIP(hipGetLastError());
+    return YK_OK;
+}
+
+extern "C" int yk_map_coco_workspace_bytes(long long n_rows, long long n_gt_rows, int n_img, int class_num, int n_thr, int n_area, int n_rec,
+                                           size_t *bytes) {
+    const int rc = coco_check("yk_map_coco_workspace_bytes", n_rows, n_gt_rows, n_img, class_num, n_thr, n_area, n_rec);
+    if (rc != YK_OK) return rc;
+    if (!bytes) {
+        yk_set_error("yk_map_coco_workspace_bytes: bad argument");
+        return YK_ERR_ARG;
+    }
+    CocoWork cw;
+    if (coco_layout(n_rows, n_gt_rows, n_img, class_num, n_thr * n_area, &cw) != YK_OK) {
+        yk_set_error("yk_map_coco_workspace_bytes: radix sort size query failed");
+        return YK_ERR_HIP;
+    }
+    *bytes = cw.total;
+    return YK_OK;
+}
+
+extern "C" int yk_map_coco_eval(const float *d_rows, const int32_t *d_img, long long n_rows, int n_img, const double *d_gt, const int32_t *d_gt_off,
+                                const uint8_t *d_difficult, long long n_gt_rows, int class_num, const double *d_iou_thr, int n_thr,
+                                const double *d_area, int n_area, const double *d_rec_thr, int n_rec, int max_dets, void *d_work, size_t work_bytes,
+                                uint8_t *d_flags, int32_t *d_npig, int32_t *d_n_det, double *d_precision, double *d_recall, double *d_summary,
+                                double *d_ap_class, void *stream) {
+    const int rc = coco_check("yk_map_coco_eval", n_rows, n_gt_rows, n_img, class_num, n_thr, n_area, n_rec);
+    if (rc != YK_OK) return rc;
+    if (!d_gt_off || !d_work || !d_iou_thr || !d_area || !d_rec_thr || !d_npig || !d_n_det || !d_precision || !d_recall || !d_summary || !d_ap_class ||
+        max_dets < 0 || (n_rows > 0 && (!d_rows || !d_img || !d_flags)) || (n_gt_rows > 0 && (!d_gt || !d_difficult))) {
+        yk_set_error("yk_map_coco_eval: bad argument");
+        return YK_ERR_ARG;
+    }
+    const int nb = n_thr * n_area;
+    CocoWork cw;
+    if (coco_layout(n_rows, n_gt_rows, n_img, class_num, nb, &cw) != YK_OK) {
+        yk_set_error("yk_map_coco_eval: radix sort size query failed");
+        return YK_ERR_HIP;
+    }
+    if (work_bytes < cw.total) {
+        yk_set_error("yk_map_coco_eval: workspace of %zu bytes, %zu needed (yk_map_coco_workspace_bytes)", work_bytes, cw.total);
+        return YK_ERR_ARG;
+    }
+    const Work &w = cw.w;
+    hipStream_t st = (hipStream_t)stream;
+    char *base = (char *)d_work;
+    uint64_t *key_a_in = (uint64_t *)(base + w.key_a_in), *key_a = (uint64_t *)(base + w.key_a);
+    uint64_t *key_b_in = (uint64_t *)(base + w.key_b_in), *key_b = (uint64_t *)(base + w.key_b);
+    uint32_t *iota = (uint32_t *)(base + w.iota), *row_a = (uint32_t *)(base + w.row_a), *row_b = (uint32_t *)(base + w.row_b);
+    int32_t *cls_off = (int32_t *)(base + w.cls_off);
+    uint64_t *ign = (uint64_t *)(base + cw.ign), *matched = (uint64_t *)(base + cw.matched), *cum = (uint64_t *)(base + cw.cum);
+
+    YK_HIP(hipMemsetAsync(d_npig, 0, (size_t)class_num * n_area * 4, st));
+    YK_HIP(hipMemsetAsync(d_n_det, 0, (size_t)class_num * 4, st));
+    YK_HIP(hipMemsetAsync(cls_off, 0, (size_t)(class_num + 1) * 4, st));
+    if (n_gt_rows > 0) {
+        YK_HIP(hipMemsetAsync(matched, 0, (size_t)n_gt_rows * 8, st));
+        hipLaunchKernelGGL(coco_gt_kernel, dim3(grid_for(n_gt_rows, MAP_BLOCK)), dim3(MAP_BLOCK), 0, st, d_gt, d_difficult, n_gt_rows, class_num, d_area,
+                           n_thr, n_area, ign, d_npig);
+    }
+    if (n_rows > 0) {
+        YK_HIP(hipMemsetAsync(d_flags, 0, (size_t)n_rows * (size_t)nb, st));   // rows of no class, rows past max_dets: 0 under every pair
+        hipLaunchKernelGGL(keys_kernel, dim3(grid_for(n_rows, MAP_BLOCK)), dim3(MAP_BLOCK), 0, st, d_rows, d_img, n_rows, class_num, key_a_in, key_b_in, iota);
+        YK_HIP(hipGetLastError());
+        size_t tmp = w.sort_bytes;
+        YK_HIP(rocprim::radix_sort_pairs(base + w.sort_tmp, tmp, key_a_in, key_a, iota, row_a, (size_t)n_rows, 0u, w.bits_a, st));
+        tmp = w.sort_bytes;
+        YK_HIP(rocprim::radix_sort_pairs(base + w.sort_tmp, tmp, key_b_in, key_b, iota, row_b, (size_t)n_rows, 0u, w.bits_b, st));
+        hipLaunchKernelGGL(class_offsets_kernel, dim3((unsigned)(class_num + 1 + 63) / 64), dim3(64), 0, st, key_a, n_rows, class_num, cls_off);
+        if (n_img > 0 && max_dets > 0)
+            hipLaunchKernelGGL(coco_match_kernel, dim3(grid_for((long long)n_img * class_num, MAP_WAVES)), dim3(MAP_BLOCK), 0, st, d_rows, key_b, row_b, n_rows,
+                               n_img, class_num, d_gt, d_gt_off, ign, matched, d_iou_thr, d_area, n_thr, n_area, max_dets, d_flags, d_n_det);
+    }
+    hipLaunchKernelGGL(coco_curve_kernel, dim3((unsigned)(class_num * nb)), dim3(MAP_BLOCK), 0, st, row_a, cls_off, d_flags, n_rows, d_npig, d_rec_thr, n_rec,
+                       class_num, n_thr, n_area, cum, d_precision, d_recall);
+    hipLaunchKernelGGL(coco_summary_kernel, dim3((unsigned)(10 + class_num)), dim3(MAP_BLOCK), 0, st, d_precision, d_recall, d_iou_thr, n_thr, n_rec, class_num,
+                       n_area, d_summary, d_ap_class);
     YK_HIP(hipGetLastError());
     return YK_OK;
 }

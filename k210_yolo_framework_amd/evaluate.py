@@ -1,14 +1,22 @@
-"""`make eval` - VOC mAP of a checkpoint, network and metric both on the GPU.
+"""`make eval` - VOC mAP of a checkpoint, or with --metric coco its COCO-style AP as well, network and metric both on the GPU
+(DESIGN.md 3.11, 3.17).
 
     python keras_eval.py CKPT [network flags of keras_inference.py] (--ann LIST.npy [--all] [--limit N] | --synthetic N)
                               [--precision f16x2|f16|kpu] [--obj_thresh 0.05] [--nms_iou 0.5] [--iou_thresh 0.5] [--voc07 True]
-                              [--out eval.json] [--dump_rows rows.npz]
+                              [--metric voc|coco] [--out eval.json] [--dump_rows rows.npz]
 
 CKPT: a Keras `.h5` / `.npz` checkpoint (float modes, through engine.Pipeline with several batches in flight) or a `.kmodel` / `.kfpkg`
 (`--precision kpu`, the K210 KPU's exact integer arithmetic through engine.KpuPlan).  The images are the validation head of the list
 make_voc_list.py writes (the whole list with --all), or N generated images with known boxes as `make train SYNTHETIC=N` trains on,
 drawn from a seed of their own.  Every batch's detections go from the decode straight into map_gpu.MapEvaluator, in device memory; the
 metric is voc_eval.evaluate's.  Prints the per-class AP table and the mAP, writes them to `eval.json` next to the checkpoint (or --out).
+
+--metric coco (`make eval METRIC=coco`) scores the same accumulated rows a second time by the COCO rule (coco_eval.evaluate's statement,
+computed by MapEvaluator.coco_result on the GPU): AP averaged over IoU 0.50:0.95, AP50, AP75, AP for small / medium / large objects, AR and
+its three, and AP per class; `eval.json` gains a `coco` object.  The VOC lines and keys stay as they are, --iou_thresh and --voc07 keep
+their meaning for them (--voc07 True with --metric coco is refused).  The rule is restated from pycocotools' public source and parity with
+pycocotools' own numbers is unpinned; `difficult` stands in for COCO's `ignore` (no crowd boxes); an object's area is its box area in the
+pixels of the picture it was scored in (COCO: mask area, source-image pixels); AR is at 100 detections per class and image only.
 The reference ships no evaluator; tools/map_eval.py is the host-side developer script this replaces as the product's entry point."""
 from __future__ import annotations
 
@@ -52,6 +60,7 @@ def parse(argv=None):
     p.add_argument('--nms_iou', type=float, default=0.5, help='IoU of the per-class NMS (keras_inference.py --iou_thresh)')
     p.add_argument('--iou_thresh', type=float, default=0.5, help='IoU a detection needs with a ground-truth box')
     p.add_argument('--voc07', type=str, choices=['True', 'False'], default='False', help='11-point AP')
+    p.add_argument('--metric', type=str, choices=['voc', 'coco'], default='voc', help='coco: also AP over IoU .50:.95, by object size, AR')
     p.add_argument('--all', action='store_true', help='evaluate the whole list, not its validation head')
     p.add_argument('--limit', type=int, default=0)
     p.add_argument('--batch', type=int, default=32)
@@ -63,6 +72,8 @@ def parse(argv=None):
         p.error('--precision kpu runs a .kmodel / .kfpkg checkpoint, and only it does (the float modes take .h5 / .npz)')
     if a.synthetic and a.ann:
         p.error('--synthetic N replaces --ann')
+    if a.metric == 'coco' and a.voc07 == 'True':
+        p.error('--voc07 True is the 11-point VOC AP; --metric coco has its own 101-point AP: choose one')
     return a
 
 
@@ -133,6 +144,31 @@ def run(a, h: Helper, model, items, ev) -> None:
         pipe.close()
 
 
+COCO_LINES = (('ap', 'AP   IoU .50:.95  all   '), ('ap50', 'AP   IoU .50      all   '), ('ap75', 'AP   IoU .75      all   '),
+              ('ap_small', 'AP   IoU .50:.95  small '), ('ap_medium', 'AP   IoU .50:.95  medium'), ('ap_large', 'AP   IoU .50:.95  large '),
+              ('ar', 'AR   IoU .50:.95  all   '), ('ar_small', 'AR   IoU .50:.95  small '), ('ar_medium', 'AR   IoU .50:.95  medium'),
+              ('ar_large', 'AR   IoU .50:.95  large '))
+
+
+def coco_report(ev, class_num: int, n_gt) -> dict:
+    """The COCO-style figures of what `ev` holds (MapEvaluator.coco_result, defaults): printed, and returned as eval.json's `coco` object."""
+    from . import coco_eval
+    c = ev.coco_result()
+    num = lambda v: None if v != v else float(v)
+    pct = lambda v: '   nan' if v != v else f'{100 * v:6.2f}'
+    print(f'COCO-style (restated rule, parity with pycocotools unpinned; box area; at most 100 detections per class and image; {CAP_NOTE}):')
+    for key, label in COCO_LINES:
+        print(f'   {label} {pct(c[key])}')
+    for k in range(class_num):
+        if n_gt[k]:
+            print(f'   class {k:2d}: AP .50:.95 {pct(c["ap_class"][k])}   det {c["n_det"][k]:6d}')
+    rep = {key: num(c[key]) for key in coco_eval.SUMMARY}
+    rep.update(ap_class=[num(v) for v in c['ap_class']], iou_thresholds=[float(v) for v in coco_eval.default_iou_thresholds()],
+               area_ranges=coco_eval.default_area_ranges().tolist(), max_dets=100, npig=c['npig'].tolist(), n_det=c['n_det'].tolist(),
+               note=CAP_NOTE)
+    return rep
+
+
 def main(argv=None):
     a = parse(argv)
     from . import engine
@@ -162,6 +198,8 @@ def main(argv=None):
               'nms_iou': a.nms_iou, 'iou_thresh': a.iou_thresh, 'voc07': voc07, 'note': CAP_NOTE, 'map': num(r['map']),
               'ap': [num(v) for v in r['ap']], 'n_gt': r['n_gt'].tolist(), 'n_det': r['n_det'].tolist(), 'tp': r['tp'].tolist(),
               'fp': r['fp'].tolist()}
+    if a.metric == 'coco':
+        report['coco'] = coco_report(ev, a.class_num, r['n_gt'])
     out = Path(a.out) if a.out else Path(a.pre_ckpt).resolve().parent / 'eval.json'
     out.write_text(json.dumps(report, indent=1))
     print(INFO, f' wrote {out}')

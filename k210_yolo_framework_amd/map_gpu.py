@@ -5,6 +5,7 @@ them, in device memory.
     for every batch:  ev.add(dets, counts, gts)          # dets [B, cap, 6] + counts [B] as engine.decode_py / Pipeline.submit return them,
                                                          # or packed rows [R, 6] + offsets [B + 1]; cuda tensors or numpy arrays
     r = ev.result()                                      # {'map', 'ap', 'n_gt', 'n_det', 'tp', 'fp'} as voc_eval.evaluate, + 'flags'
+    c = ev.coco_result()                                 # the COCO-style figures of the same rows, as coco_eval.evaluate
 
 The detection rows are accumulated in device buffers that grow by doubling; the only thing read back per batch is the batch's counts
 (4 bytes per image), which size the append.  The ground truth (a few boxes per image, float64) is kept on the host until `result()`
@@ -195,3 +196,52 @@ class MapEvaluator:
                 h_ints, h_ap, h_flags = ints.cpu().numpy().astype(int), ap.cpu().numpy(), flags[:R].cpu().numpy()
         return {'map': float(h_ap[Cn]), 'ap': h_ap[:Cn].copy(), 'n_gt': h_ints[0], 'n_det': h_ints[1], 'tp': h_ints[2], 'fp': h_ints[3],
                 'flags': h_flags}
+
+    def coco_result(self, iou_thresholds=None, area_ranges=None, max_dets: int = 100, stream=None) -> Dict[str, object]:
+        """The COCO-style metric of the rows added so far, by the rule of coco_eval.evaluate -> its dict: 'ap', 'ap50',
+        'ap75', 'ap_small', 'ap_medium', 'ap_large', 'ar', 'ar_small', 'ar_medium', 'ar_large' (float, nan where nothing is present),
+        'ap_class' [class_num], 'precision' [T,101,class_num,A], 'recall' [T,class_num,A] (-1 where absent), 'npig' [class_num,A],
+        'n_det' [class_num], 'flags' [A,T,rows] uint8.  Independent of `iou_thresh`, `use_07_metric` and `plus_one`, and of `result()`:
+        nothing accumulated is changed.  Runs on `stream` (default: the current one); synchronises to read the results."""
+        import torch
+        from . import coco_eval
+        thr = coco_eval.default_iou_thresholds() if iou_thresholds is None else np.ascontiguousarray(iou_thresholds, np.float64).reshape(-1)
+        area = coco_eval.default_area_ranges() if area_ranges is None else np.ascontiguousarray(area_ranges, np.float64).reshape(-1, 2)
+        rec = coco_eval.REC_THRS
+        T, A, Rn = len(thr), len(area), len(rec)
+        Cn, R, N = self.class_num, self.n_rows, self.n_img
+        gt, off, diff = self.ground_truth()
+        G = int(off[-1])
+        if G > MAX_ROWS:
+            raise engine.YkError(f'MapEvaluator: {G} ground-truth rows: more than 2^31-1')
+        nbytes = C.c_size_t()
+        engine.call('yk_map_coco_workspace_bytes', R, G, N, Cn, T, A, Rn, C.byref(nbytes))          # refuses T * A > 64 by name
+        with torch.cuda.device(self.dev):
+            st = torch.cuda.current_stream() if stream is None else stream
+            with torch.cuda.stream(st):
+                last = getattr(self, '_last', None)
+                if last is not None and last != st:
+                    st.wait_stream(last)
+                up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.dev)
+                d_gt, d_diff = (up(gt), up(diff)) if G else (None, None)
+                d_off = up(off.astype(np.int32))
+                d_thr, d_area, d_rec = up(thr), up(area), up(rec)
+                work = torch.empty((int(nbytes.value),), dtype=torch.uint8, device=self.dev)
+                flags = torch.empty((A * T * max(R, 1),), dtype=torch.uint8, device=self.dev)
+                ints = torch.empty((Cn * A + Cn,), dtype=torch.int32, device=self.dev)             # npig [class_num][A], n_det [class_num]
+                prec = torch.empty((T * Rn * Cn * A,), dtype=torch.float64, device=self.dev)
+                rcl = torch.empty((T * Cn * A,), dtype=torch.float64, device=self.dev)
+                summ = torch.empty((len(coco_eval.SUMMARY) + Cn,), dtype=torch.float64, device=self.dev)
+                engine.call('yk_map_coco_eval', self._rows if R else None, self._img if R else None, R, N, d_gt, d_off, d_diff, G, Cn, d_thr, T,
+                            d_area, A, d_rec, Rn, int(max_dets), work, nbytes.value, flags, ints, ints[Cn * A:], prec, rcl, summ,
+                            summ[len(coco_eval.SUMMARY):], engine._stream(st))
+                st.synchronize()
+                self._last = None
+                h_ints, h_summ = ints.cpu().numpy().astype(int), summ.cpu().numpy()
+                out: Dict[str, object] = {k: float(h_summ[j]) for j, k in enumerate(coco_eval.SUMMARY)}
+                out['ap_class'] = h_summ[len(coco_eval.SUMMARY):].copy()
+                out['precision'] = prec.cpu().numpy().reshape(T, Rn, Cn, A)
+                out['recall'] = rcl.cpu().numpy().reshape(T, Cn, A)
+                out['npig'], out['n_det'] = h_ints[:Cn * A].reshape(Cn, A), h_ints[Cn * A:]
+                out['flags'] = flags[:A * T * R].cpu().numpy().reshape(A, T, R)
+        return out
