@@ -11,6 +11,11 @@
 #                    [BOXLOSS=giou|diou|ciou BOXWEIGHT=1.0]: an IoU-family box loss in place of the xy / wh terms (default mse: the reference's loss)
 #                    [MOSAIC=True MOSAICPROB=1.0 MOSAICOFF=0]: four pictures per training sample, composed on the GPU; the last MOSAICOFF epochs without
 #                    [HSV=True HSVHUE=0.1 HSVSAT=1.5 HSVEXP=1.5 HSVPROB=1.0]: HSV colour jitter of every training frame, on the GPU (Darknet's recipe)
+#                    [TEACHERCKPT=big.h5|.npz TEACHER=yolo_mobilev2 TEACHERDEPTH=1.0 DISTILLWEIGHT=1.0]: knowledge distillation from a trained network of
+#                    the zoo with the same IMGSIZE, OUTSIZE, anchors and CLSNUM (TEACHER / TEACHERDEPTH default to MODEL / DEPTHMUL): per raw output the
+#                    Bernoulli KL from the teacher's sigmoid to the student's, classes and box scaled by the teacher's objectness, squared error on
+#                    the wh logits; the step and epoch lines then name the `distill` term.  Empty TEACHERCKPT (default): off.  The wh term is
+#                    unbounded where the teacher's wh logits are wild, and DISTILLWEIGHT=1.0 is a starting point: DESIGN.md 3.18, profiles/distill_*.txt
 #   make kmodel      CKPT=yolo_model.h5 OUT=yolo.kmodel|.kfpkg [SYNTHETIC=256 | CALIB=data/voc_img_ann.npy]: 8-bit K210 model, calibrated on the GPU
 #                    [RANGES=yolo_qat_ranges.npz]: the ranges a QAT run learned instead of a calibration
 #                    [CALIBMETHOD=minmax|percentile|mse CALIBPCT=99.99 CALIBBINS=2048]: minmax (default) takes each tensor's exact range; percentile
@@ -68,6 +73,10 @@ HSVHUE        ?= 0.1
 HSVSAT        ?= 1.5
 HSVEXP        ?= 1.5
 HSVPROB       ?= 1.0
+TEACHERCKPT   ?=
+TEACHER       ?=
+TEACHERDEPTH  ?=
+DISTILLWEIGHT ?= 1.0
 # eval only
 PRECISION     ?= f16x2
 ANN           ?= data/$(DATASET)_img_ann.npy
@@ -106,7 +115,9 @@ TRAIN_ARGS = --pre_ckpt $(CKPT) --augmenter $(IAA) --batch_size $(BATCH) --rand_
              --prune_end_epoch $(END_EPOCH) --prune_frequency $(FREQUENCY) --synthetic $(SYNTHETIC) \
              --qat $(QAT) --qat_momentum $(QATMOMENTUM) --qat_observe $(QATOBSERVE) --val_map $(VALMAP) \
              --box_loss $(BOXLOSS) --box_weight $(BOXWEIGHT) --mosaic $(MOSAIC) --mosaic_prob $(MOSAICPROB) --mosaic_off_epochs $(MOSAICOFF) \
-             --hsv $(HSV) --hsv_hue $(HSVHUE) --hsv_sat $(HSVSAT) --hsv_exposure $(HSVEXP) --hsv_prob $(HSVPROB)
+             --hsv $(HSV) --hsv_hue $(HSVHUE) --hsv_sat $(HSVSAT) --hsv_exposure $(HSVEXP) --hsv_prob $(HSVPROB) \
+             $(if $(TEACHERCKPT),--teacher_ckpt $(TEACHERCKPT) --distill_weight $(DISTILLWEIGHT) $(if $(TEACHER),--teacher_def $(TEACHER)) \
+             $(if $(TEACHERDEPTH),--teacher_depth $(TEACHERDEPTH)))
 ifeq ($(GPUS),1)
 LAUNCH = $(PY)
 else

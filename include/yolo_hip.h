@@ -492,6 +492,22 @@ typedef struct {
 int yk_yolo_loss_ex(const yk_loss_cfg_ex_t *cfg, const float *d_y_true, const float *d_y_pred, int batch, float *d_loss,
                     float *d_grad, float *d_ignore, float *d_counts, void *stream);
 
+/* Knowledge distillation on the raw outputs of ONE output layer (the rule is stated in distill.py, csrc/yk_distill.hip).
+ * d_teacher / d_pred: device fp32 [batch][rows_per_image][5 + class_num], the teacher's and the student's raw outputs (rows_per_image =
+ * out_h * out_w * A); the teacher is a constant.  With sp(z) = log(1 + e^z) in its stable form (finite for logits of +-80 and beyond),
+ *   kl(q, p) = sigmoid(q) (sp(-p) - sp(-q)) + (1 - sigmoid(q)) (sp(p) - sp(q))      (>= 0; d/dp = sigmoid(p) - sigmoid(q))
+ * and a = sigmoid(q_o), a row p = [x, y, w, h, o, c..] adds
+ *   obj = kl(q_o, p_o),  cls = a sum_c kl(q_c, p_c),  box = a (kl(q_x, p_x) + kl(q_y, p_y) + ((p_w - q_w)^2 + (p_h - q_h)^2) / 2).
+ * d_loss[4]   = {total, obj, cls, box}: weight / batch_size times the sums over all rows (batch_size: the divisor of yk_yolo_loss).
+ * d_grad      = the gradient by d_pred is ADDED to it (same shape; NULL to skip): weight / batch_size times a (sigmoid(p) - sigmoid(q)) for x,
+ *               y and every class, a (p - q) for w and h, sigmoid(p_o) - sigmoid(q_o) for o.
+ * Where the bits of p and q are equal every entry of d_loss is +0.0 and d_grad keeps its bits.  The sums are taken in float64 in a fixed order
+ * and no float atomics are used: two calls give the same bits.  d_loss does not depend on whether d_grad is given.  A NULL d_teacher, d_pred
+ * or d_loss, batch <= 0, rows_per_image <= 0, class_num < 1 or batch_size <= 0: YK_ERR_ARG, nothing launched.  Asynchronous on `stream`; can be
+ * recorded in a graph once the stream has run it eagerly at its largest size. */
+int yk_distill_loss_f32(const float *d_teacher, const float *d_pred, int batch, int rows_per_image, int class_num, float weight,
+                        int batch_size, float *d_loss, float *d_grad, void *stream);
+
 /* ---- training step, network level (keras_train.py:73-98: model.fit = forward in training mode + TF autodiff +
  *      Adam; the reference gets every one of these ops from TensorFlow 1.14).  All tensors are device fp32, NHWC,
  *      dense (no channel padding); "M" is batch*height*width.  k210_yolo_framework_amd/train.py strings them into

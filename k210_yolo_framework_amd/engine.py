@@ -440,6 +440,25 @@ def yolo_loss(y_true, y_pred, anchors_l, obj_thresh, iou_thresh, obj_weight, noo
     return loss, grad, ign
 
 
+def distill_loss(teacher, pred, weight, batch_size, grad=None, stream=None):
+    """Knowledge distillation on the raw outputs of one layer (yk_distill_loss_f32; the rule is in distill.py).
+    teacher / pred: cuda fp32 [B, h, w, A, 5 + C] (or [B, rows, 5 + C]), the teacher's and the student's raw outputs.  grad: dL/dpred is ADDED
+    to it (same shape as pred; None to skip).  -> loss[4] = total, obj, cls, box, each weight / batch_size times its sum (cuda fp32)."""
+    import torch
+    require_gpu()
+    for name, t in (('teacher', teacher), ('pred', pred)) + ((('grad', grad),) if grad is not None else ()):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+            raise YkError(f'distill_loss: {name} must be a contiguous cuda float32 tensor')
+        if t.shape != pred.shape or t.device != pred.device:
+            raise YkError(f'distill_loss: {name} is {tuple(t.shape)} on {t.device}, pred {tuple(pred.shape)} on {pred.device}')
+    if pred.dim() < 3 or pred.shape[-1] < 6 or pred.numel() == 0:
+        raise YkError(f'distill_loss: pred {tuple(pred.shape)}: expected [B, ..., 5 + C] with C >= 1')
+    B, E = int(pred.shape[0]), int(pred.shape[-1])
+    loss = torch.empty(4, dtype=torch.float32, device=pred.device)
+    call('yk_distill_loss_f32', teacher, pred, B, pred.numel() // (B * E), E - 5, float(weight), int(batch_size), loss, grad, _stream(stream))
+    return loss
+
+
 def letterbox_u8(frames, dst_hw, stream=None, out=None):
     """GPU Helper._process_img letterbox (tools/utils.py:378-399): cuda uint8 [B,h,w,3] -> cuda uint8 [B,H,W,3]."""
     import torch

@@ -24,6 +24,11 @@ IoU box losses: `Trainer(box_loss='giou' | 'diou' | 'ciou', box
 by the IoU-family term of csrc/yk_loss.hip (yk_yolo_loss_ex).  Both live in `tr.hyper`, so they are part of the captured step and of its key,
 and the validation pass uses the same loss.  With box_loss='mse' the step calls yk_yolo_loss as before.
 
+Knowledge distillation (distill.py): `Trainer(distill=DistillConfig(teacher_spec, teacher_weights, weight))` runs the teacher as an
+inference plan (engine.Plan, f16x2) on the step's frames, outside the captured graph, copies its raw outputs into static buffers, and adds
+one yk_distill_loss_f32 call per output layer (csrc/yk_distill.hip) into that layer's gradient between the detection loss and the backward
+pass, inside the capture.  The validation loss stays the detection loss.  With distill=None nothing is allocated and nothing is launched.
+
 fp32 storage and fp32 MFMA throughout (TF1.14's default for this model)."""
 from __future__ import annotations
 
@@ -63,7 +68,8 @@ class Trainer:
     def __init__(self, spec: ns.NetSpec, weights: Dict[str, np.ndarray], anchors: np.ndarray, per_rank_batch: int,
                  obj_thresh: float = 0.7, iou_thresh: float = 0.5, obj_weight: float = 1.0, noobj_weight: float = 1.0,
                  wh_weight: float = 1.0, lr: float = 5e-4, decay: float = 0.0, device: int = 0, process_group=None,
-                 world_size: int = 1, use_graph: bool = True, prune=None, qat=None, box_loss: str = 'mse', box_weight: float = 1.0):
+                 world_size: int = 1, use_graph: bool = True, prune=None, qat=None, box_loss: str = 'mse', box_weight: float = 1.0,
+                 distill=None):
         import torch
         if box_loss not in engine.BOX_LOSSES:
             raise ValueError(f'box_loss {box_loss!r}: choose one of ' + ', '.join(repr(k) for k in engine.BOX_LOSSES))
@@ -122,6 +128,10 @@ class Trainer:
         self.qat = qat
         if qat is not None:
             self._qat_init()
+        # knowledge distillation (distill.DistillConfig).  None: nothing is allocated and nothing is launched.
+        self.distill = distill
+        if distill is not None:
+            self._distill_init(device)
 
     # ------------------------------------------------------------------ parameters
     def view(self, buf, name):
@@ -478,8 +488,14 @@ class Trainer:
                                            **self.hyper)
             parts.append(loss6)
             grads.append(g)
+        kd = None
+        if self.distill is not None:                                 # g += dL_distill/dy_pred, the teacher's outputs of THIS batch in self._tq
+            kd = [engine.distill_loss(tq, yp.contiguous(), self.distill_weight, global_batch, grad=g)
+                  for tq, yp, g in zip(self._tq, preds, grads)]
         self.backward(grads)
         res = dict(layers=parts, reg=self.regulariser(add_grad=self.world == 1))
+        if kd is not None:
+            res['distill'] = kd
         if self.qat is not None:
             self._qat_update(False)                                  # after the backward pass: forward and backward saw the same ranges
         return res
@@ -494,7 +510,8 @@ class Trainer:
 
     def _graph_key(self, x_nhwc, y_true):
         return (tuple(sorted(self.hyper.items())), tuple(x_nhwc.shape), tuple(tuple(y.shape) for y in y_true), self.world,
-                None if self.qat is None else self.qat.momentum)           # (a launch scalar of yk_qat_update_f32 inside the capture)
+                None if self.qat is None else self.qat.momentum,           # (a launch scalar of yk_qat_update_f32 inside the capture)
+                None if self.distill is None else self.distill_weight)      # (a launch scalar of yk_distill_loss_f32 inside the capture)
 
     def _loss_and_grads_replayed(self, x_nhwc, y_true):
         """loss_and_grads through a captured HIP graph (after one eager step that also warms allocator and scratch buffers).
@@ -556,6 +573,34 @@ class Trainer:
         """keras Adam(lr, decay) on the flat buffers (keras_train.py:73-76); one launch."""
         self._ck('yk_adam_f32', self.n_params, self.P, self.G, self.m, self.v, self.lr, self.decay, self.iterations, 0.9, 0.999, 1e-7, 1.0)
         self.iterations += 1
+
+    # ------------------------------------------------------------------ knowledge distillation (DESIGN.md 3.18)
+    def _distill_init(self, device: int) -> None:
+        """The teacher's inference plan and one static buffer per output layer for its raw outputs.  Allocated once: the captured step holds
+        the buffers' pointers, every step refills them in place (the way _gx and _gy travel)."""
+        from .distill import check_teacher
+        d = self.distill
+        check_teacher(self.spec, d.spec, self.anchors)               # YkError naming the first difference
+        self.distill_weight = float(d.weight)
+        # 'throughput': one launch per layer.  The cluster launches of 'latency' need their workgroups co-resident, which the input
+        # pipeline's kernels on other streams can prevent, and report that through a flag the step would have to wait for
+        self._teacher = engine.Plan(d.spec, d.weights, max_batch=self.B, device=device, precision=d.precision, schedule='throughput')
+        e = 5 + self.spec.class_num
+        self._tq = [self._new(self.B, *self.spec.tensors[o][:2], self.spec.anchor_num, e) for o in self.spec.outputs]
+
+    def _need_distill(self):
+        if self.distill is None:
+            raise engine.YkError('this Trainer was built without a teacher (distill=None)')
+
+    def teacher_forward(self, x_nhwc) -> List["torch.Tensor"]:
+        """The teacher's raw outputs of these frames, [B,h,w,A,5+C] per layer, into the static buffers the step's distillation calls read.
+        Runs on torch's current stream, outside the captured graph."""
+        self._need_distill()
+        assert tuple(x_nhwc.shape[:1]) == (self.B,)
+        self._teacher.run_f32(x_nhwc.contiguous())
+        for dst, o in zip(self._tq, self._teacher.outputs()):
+            dst.view(self.B, -1).copy_(o[:self.B].reshape(self.B, -1))
+        return self._tq
 
     # ------------------------------------------------------------------ magnitude pruning (DESIGN.md 3.8)
     def _prune_init(self) -> None:
@@ -750,12 +795,16 @@ class Trainer:
             raise engine.YkError('qat: the activation ranges are not set: call qat_observe(x) on a few batches (or qat_set_ranges) before the first step')
         if self.prune is not None:
             self.prune_step()
+        if self.distill is not None:
+            self.teacher_forward(x_nhwc)                             # before the loss, outside the capture: each rank on its own shard
         r = self._loss_and_grads_replayed(x_nhwc, y_true)
         if self.world > 1:
             self.exchange(reduce)
         self.apply_update()
         iou_box = self.hyper['box_loss'] != 'mse'                     # then the layers' loss[6] is the box term (yk_yolo_loss_ex)
         data = torch.stack([p[0::6] for p in r['layers']]).sum(0)     # [total] or, of 7 entries, [total, box]
+        if self.distill is not None:                                  # ... then the distillation term (each rank's carries 1 / global batch)
+            data = torch.cat([data, torch.stack([d[0] for d in r['distill']]).sum().view(1)])
         if self.world > 1:
             if reduce_scalar is not None:
                 reduce_scalar(data)
@@ -766,6 +815,9 @@ class Trainer:
         out = dict(loss=float(vals[0] + vals[-1]), data_loss=float(vals[0]), reg_loss=float(vals[-1]))
         if iou_box:
             out['box'] = float(vals[1])
+        if self.distill is not None:                                  # loss is what the step descends: detection + distillation + regulariser
+            out['distill'] = float(vals[-2])
+            out['loss'] = float(vals[0] + vals[-2] + vals[-1])
         return out
 
     def precision_recall(self):

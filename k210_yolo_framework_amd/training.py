@@ -36,7 +36,14 @@ samples; validation is never mosaicked.
 `--hsv_prob` of the training frames gets a hue rotation of up to +-`--hsv_hue` turns and saturation and exposure gains between 1/x and x of
 `--hsv_sat` and `--hsv_exposure` (Darknet's recipe), by one HIP launch per batch on the finished frame (`InputPipeline(hsv=...)`), draws
 keyed by (rand_seed, epoch, row).  It acts after the letterbox, the augmentation and the mosaic, in every epoch (the `--mosaic_off_epochs`
-tail included); validation is never jittered."""
+tail included); validation is never jittered.
+
+`--teacher_ckpt weights.h5|.npz` (`make train TEACHERCKPT=big.h5 TEACHER=yolo_mobilev2 TEACHERDEPTH=1.0 DISTILLWEIGHT=1.0`; not in the
+reference, distill.py): knowledge distillation from a trained network of the zoo with the same image size, output size, anchor
+count and class count (`--teacher_def` / `--teacher_depth`; by default the student's own, e.g. its float, unpruned checkpoint for a QAT or a
+pruned run).  The teacher runs as an inference plan on the step's frames and one HIP launch per output layer adds the objectness-scaled
+distillation term, weighted by `--distill_weight`, to the loss and its gradient; the step line and the epoch line then name the `distill`
+term.  The validation loss stays the detection loss.  The empty default means off."""
 from __future__ import annotations
 
 import argparse
@@ -127,7 +134,7 @@ def main(args, train_set, class_num, pre_ckpt, model_def, depth_multiplier, is_a
          obj_thresh, iou_thresh, vaildation_split, log_dir, is_prune, initial_sparsity=0.5, final_sparsity=0.9, end_epoch=5,
          frequency=100, synthetic=0, max_steps=0, is_qat='False', qat_momentum=0.99, qat_observe=8, val_map='False', val_map_obj=0.05,
          box_loss='mse', box_weight=1.0, is_mosaic='False', mosaic_prob=1.0, mosaic_off_epochs=0, is_hsv='False', hsv_hue=0.1, hsv_sat=1.5,
-         hsv_exposure=1.5, hsv_prob=1.0):
+         hsv_exposure=1.5, hsv_prob=1.0, teacher_ckpt='', teacher_def=None, teacher_depth=None, distill_weight=1.0):
     import torch
     from .train import Trainer
     prune = is_prune == 'True'
@@ -151,6 +158,9 @@ def main(args, train_set, class_num, pre_ckpt, model_def, depth_multiplier, is_a
             if not (np.isfinite(v) and ok):
                 raise engine.YkError(f'{flag} {v}: {want}')
         hsv_cfg = HsvConfig(float(hsv_hue), float(hsv_sat), float(hsv_exposure), float(hsv_prob))
+    distill = teacher_ckpt not in (None, 'None', '', '""')
+    if distill and not (np.isfinite(float(distill_weight)) and float(distill_weight) >= 0.0):
+        raise engine.YkError(f'--distill_weight {distill_weight}: a finite weight, not negative')
     rank, world = int(os.environ.get('RANK', '0')), int(os.environ.get('WORLD_SIZE', '1'))
     local = int(os.environ.get('LOCAL_RANK', '0'))
     try:
@@ -167,6 +177,8 @@ def main(args, train_set, class_num, pre_ckpt, model_def, depth_multiplier, is_a
             raise engine.YkError('--mosaic True (four pictures per sample, mosaic.py) runs in the GPU input pipeline: no HIP device') from e
         if hsv:
             raise engine.YkError('--hsv True (HSV colour jitter, colour.py) runs in the GPU input pipeline: no HIP device') from e
+        if distill:
+            raise engine.YkError('--teacher_ckpt (knowledge distillation, distill.py) runs the teacher and its loss in HIP kernels: no HIP device') from e
         raise
     torch.cuda.set_device(local)
     dist = None
@@ -200,15 +212,25 @@ def main(args, train_set, class_num, pre_ckpt, model_def, depth_multiplier, is_a
     assert [tuple(x) for x in spec.out_hw()] == [tuple(x) for x in out_hw], (spec.out_hw(), out_hw)
     weights = spec.init_keras_default(rand_seed)
     if pre_ckpt not in (None, 'None', ''):                                       # keras_train.py:52-57
-        if 'h5' in str(pre_ckpt):
-            from . import keras_io
-            weights, _ = keras_io.load_keras_weights(spec, str(pre_ckpt), base=weights, strict=True)
-            print(INFO, f' Load CKPT {str(pre_ckpt)}')
-        elif str(pre_ckpt).endswith('.npz'):
-            weights.update({k: v for k, v in np.load(pre_ckpt).items()})
+        if load_weights(spec, pre_ckpt, weights):
             print(INFO, f' Load CKPT {str(pre_ckpt)}')
         else:
             print(ERROR, ' Pre CKPT path is unvalid')
+    distill_cfg = None
+    if distill:
+        from .distill import DistillConfig, check_teacher
+        t_def = model_def if teacher_def in (None, 'None', '') else teacher_def
+        t_depth = depth_multiplier if teacher_depth in (None, 'None', '') else float(teacher_depth)
+        if t_def not in netspec.NETWORKS:
+            raise engine.YkError(f'--teacher_def {t_def}: choose one of {", ".join(sorted(netspec.NETWORKS))}')
+        t_spec = netspec.NETWORKS[t_def]([image_size[0], image_size[1], 3], len(h.anchors[0]), class_num, alpha=t_depth)
+        check_teacher(spec, t_spec, h.anchors)                                   # before the file is read: names the first difference
+        t_weights = t_spec.init_keras_default(rand_seed)
+        if not load_weights(t_spec, teacher_ckpt, t_weights):
+            raise engine.YkError(f'--teacher_ckpt {teacher_ckpt}: a .h5 or .npz checkpoint of {t_def}-{t_depth}')
+        distill_cfg = DistillConfig(t_spec, t_weights, float(distill_weight))
+        if rank == 0:
+            print(INFO, f' Load teacher CKPT {str(teacher_ckpt)} ({t_def}-{t_depth}), distill_weight {float(distill_weight)}')
     schedule = None
     if prune:                                                                    # keras_train.py:60-66: end_step = train_epoch_step * end_epoch
         from .prune import PruneSchedule
@@ -219,7 +241,7 @@ def main(args, train_set, class_num, pre_ckpt, model_def, depth_multiplier, is_a
         qat_cfg = QatConfig(qat_momentum)
     tr = Trainer(spec, weights, h.anchors, per_rank, obj_thresh=obj_thresh, iou_thresh=iou_thresh, obj_weight=obj_weight,
                  noobj_weight=noobj_weight, wh_weight=wh_weight, lr=init_learning_rate, decay=learning_rate_decay_factor, device=local,
-                 world_size=world, prune=schedule, qat=qat_cfg, box_loss=box_loss, box_weight=box_weight)
+                 world_size=world, prune=schedule, qat=qat_cfg, box_loss=box_loss, box_weight=box_weight, distill=distill_cfg)
     from .mosaic import MosaicConfig
     from .pipeline import InputPipeline
     if rank == 0:
@@ -229,7 +251,7 @@ def main(args, train_set, class_num, pre_ckpt, model_def, depth_multiplier, is_a
     steps, observed = 0, 0
     iou_box = box_loss != 'mse'
     for epoch in range(max_nrof_epochs):
-        t0, seen, run, run_box = time.time(), 0, 0.0, 0.0
+        t0, seen, run, run_box, run_kd = time.time(), 0, 0.0, 0.0, 0.0
         if rank == 0 and mosaic and int(mosaic_off_epochs) > 0 and epoch == max(max_nrof_epochs - int(mosaic_off_epochs), 0):
             print(f'epoch {epoch + 1}: mosaic off from here on', flush=True)
         # tools/utils.py:417-450: each rank decodes only its rows of the global batch, on a thread pool, two batches ahead;
@@ -247,9 +269,11 @@ def main(args, train_set, class_num, pre_ckpt, model_def, depth_multiplier, is_a
                 out = tr.step(x, ys)
                 seen, run, steps = seen + 1, run + out['loss'], steps + 1
                 run_box += out.get('box', 0.0)
+                run_kd += out.get('distill', 0.0)
                 if rank == 0 and (seen % 10 == 0 or seen == 1):
                     pr = tr.precision_recall()
                     print(f'epoch {epoch + 1} step {seen}: loss {out["loss"]:.4f} ' + (f'{box_loss} {out["box"]:.4f} ' if iou_box else '') +
+                          (f'distill {out["distill"]:.4f} ' if distill else '') +
                           ' '.join(f'l{i + 1}_p {p:.3f} l{i + 1}_r {r:.3f}' for i, (p, r) in enumerate(pr)), flush=True)
                 if max_steps and steps >= max_steps:
                     break
@@ -269,6 +293,7 @@ def main(args, train_set, class_num, pre_ckpt, model_def, depth_multiplier, is_a
         if rank == 0:
             print(f'epoch {epoch + 1}: {seen} steps, mean loss {run / max(seen, 1):.4f}, ' +
                   (f'mean {box_loss} {run_box / max(seen, 1):.4f}, ' if iou_box else '') +
+                  (f'mean distill {run_kd / max(seen, 1):.4f}, ' if distill else '') +
                   (f'val_loss {val:.4f}, ' if val is not None else '') + f'{time.time() - t0:.1f}s, input pipeline {pipe_rate:.0f} images/s/rank' +
                   (f', val_mAP {vmap:.4f}' if vmap is not None else ''), flush=True)
         for c in tr.counts:
@@ -296,6 +321,20 @@ def main(args, train_set, class_num, pre_ckpt, model_def, depth_multiplier, is_a
         dist.barrier()
         dist.destroy_process_group()
     return tr
+
+
+def load_weights(spec, path, weights) -> bool:
+    """A checkpoint into `weights` (Keras layout, in place), keras_train.py:52-57: a Keras .h5 file (every layer must be there) or the .npz
+    written beside it.  -> False for any other path."""
+    if 'h5' in str(path):
+        from . import keras_io
+        loaded, _ = keras_io.load_keras_weights(spec, str(path), base=weights, strict=True)
+        weights.update(loaded)
+        return True
+    if str(path).endswith('.npz'):
+        weights.update({k: v for k, v in np.load(path).items()})
+        return True
+    return False
 
 
 def sparsity_line(tr, spec, epoch: int) -> str:
@@ -386,6 +425,10 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument('--hsv_sat', type=float, default=1.5, help='largest saturation gain x (at least 1): gains between 1/x and x')
     p.add_argument('--hsv_exposure', type=float, default=1.5, help='largest exposure gain x (at least 1): gains between 1/x and x')
     p.add_argument('--hsv_prob', type=float, default=1.0, help='share of the training frames that are jittered')
+    p.add_argument('--teacher_ckpt', type=str, default='', help='.h5 / .npz checkpoint of the teacher: knowledge distillation (DESIGN.md 3.18); empty = off')
+    p.add_argument('--teacher_def', type=str, default=None, help="the teacher's network (default: --model_def)")
+    p.add_argument('--teacher_depth', type=float, choices=[0.5, 0.75, 1.0], default=None, help="the teacher's depth multiplier (default: --depth_multiplier)")
+    p.add_argument('--distill_weight', type=float, default=1.0, help='weight of the distillation term')
     return p
 
 
@@ -396,7 +439,8 @@ def cli(argv=None):
                 a.noobj_weight, a.wh_weight, a.obj_thresh, a.iou_thresh, a.vaildation_split, a.log_dir, a.is_prune,
                 a.prune_initial_sparsity, a.prune_final_sparsity, a.prune_end_epoch, a.prune_frequency, a.synthetic, a.max_steps,
                 a.qat, a.qat_momentum, a.qat_observe, a.val_map, a.val_map_obj, a.box_loss, a.box_weight, a.mosaic, a.mosaic_prob,
-                a.mosaic_off_epochs, a.hsv, a.hsv_hue, a.hsv_sat, a.hsv_exposure, a.hsv_prob)
+                a.mosaic_off_epochs, a.hsv, a.hsv_hue, a.hsv_sat, a.hsv_exposure, a.hsv_prob, a.teacher_ckpt, a.teacher_def, a.teacher_depth,
+                a.distill_weight)
 
 
 if __name__ == '__main__':
