@@ -16,6 +16,11 @@
 #                    Bernoulli KL from the teacher's sigmoid to the student's, classes and box scaled by the teacher's objectness, squared error on
 #                    the wh logits; the step and epoch lines then name the `distill` term.  Empty TEACHERCKPT (default): off.  The wh term is
 #                    unbounded where the teacher's wh logits are wild, and DISTILLWEIGHT=1.0 is a starting point: DESIGN.md 3.18, profiles/distill_*.txt
+#                    [CACHE=gpu CACHEGB=8 CACHESTAGE=256]: every training picture is decoded once and kept in device memory (CACHEGB GB; what does
+#                    not fit is brought in every epoch through staging regions of CACHESTAGE MB, which must hold the uncached pictures of one
+#                    batch); every batch is composed from there by one launch and the epoch line names the hits / misses: DESIGN.md 3.19
+#                    [DECODE=gpu]: the pictures that still have to be decoded are, if baseline JPEG files, decoded on the GPU into that
+#                    memory by the project's own integer rule (not PIL's bytes: DESIGN.md 3.12), every other file by PIL; works without CACHE=gpu
 #   make kmodel      CKPT=yolo_model.h5 OUT=yolo.kmodel|.kfpkg [SYNTHETIC=256 | CALIB=data/voc_img_ann.npy]: 8-bit K210 model, calibrated on the GPU
 #                    [RANGES=yolo_qat_ranges.npz]: the ranges a QAT run learned instead of a calibration
 #                    [CALIBMETHOD=minmax|percentile|mse CALIBPCT=99.99 CALIBBINS=2048]: minmax (default) takes each tensor's exact range; percentile
@@ -77,6 +82,9 @@ TEACHERCKPT   ?=
 TEACHER       ?=
 TEACHERDEPTH  ?=
 DISTILLWEIGHT ?= 1.0
+CACHE         ?= off
+CACHEGB       ?= 8
+CACHESTAGE    ?= 256
 # eval only
 PRECISION     ?= f16x2
 ANN           ?= data/$(DATASET)_img_ann.npy
@@ -116,6 +124,7 @@ TRAIN_ARGS = --pre_ckpt $(CKPT) --augmenter $(IAA) --batch_size $(BATCH) --rand_
              --qat $(QAT) --qat_momentum $(QATMOMENTUM) --qat_observe $(QATOBSERVE) --val_map $(VALMAP) \
              --box_loss $(BOXLOSS) --box_weight $(BOXWEIGHT) --mosaic $(MOSAIC) --mosaic_prob $(MOSAICPROB) --mosaic_off_epochs $(MOSAICOFF) \
              --hsv $(HSV) --hsv_hue $(HSVHUE) --hsv_sat $(HSVSAT) --hsv_exposure $(HSVEXP) --hsv_prob $(HSVPROB) \
+             --cache $(CACHE) --cache_gb $(CACHEGB) --cache_stage_mb $(CACHESTAGE) --decode $(DECODE) \
              $(if $(TEACHERCKPT),--teacher_ckpt $(TEACHERCKPT) --distill_weight $(DISTILLWEIGHT) $(if $(TEACHER),--teacher_def $(TEACHER)) \
              $(if $(TEACHERDEPTH),--teacher_depth $(TEACHERDEPTH)))
 ifeq ($(GPUS),1)

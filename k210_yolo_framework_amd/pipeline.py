@@ -31,9 +31,16 @@ above runs untouched.
 hsv=HsvConfig(hue, sat, exposure, prob) jitters the colours of every finished frame (semantics in colour.py): the batch's (dh, gs, gv)
 rows of the epoch's table travel through a pinned slot, and ONE `yk_hsv_jitter_u8` launch works in place on the u8 frames of the whole
 batch, on either path above, between the geometric launch and `yk_normalise_u8`.  Without hsv no call is added.
+
+cache=PictureCache(...) (cache.py) keeps every decoded picture on the device: a batch resolves its rows, brings the pictures
+the cache does not hold into its arena - decoded by the pool and copied (decode='pil'), or, baseline JPEG files, only read and parsed by the
+pool and decoded there by ONE `yk_jpeg_decode_ragged_u8` (decode='gpu'; without a cache it runs on a staging ring of its own) - and ONE
+ragged launch over the arena writes the whole batch, plain, warped or mosaicked; hsv, normalise and labels follow as above.  The batches are
+those of the paths above, bit for bit.  Without cache and with decode='pil' the paths above run untouched.
 """
 from __future__ import annotations
 
+import io
 import os
 import queue
 import threading
@@ -140,9 +147,12 @@ class InputPipeline:
 
     def __init__(self, h: Helper, items: Sequence, global_batch: int, rank: int = 0, world: int = 1, seed: int = 0, epoch: int = 0,
                  shuffle: bool = True, workers: int = 8, prefetch: int = 2, device: Optional[int] = None, augment: bool = False,
-                 mosaic: Optional[mosaic_mod.MosaicConfig] = None, hsv: Optional[colour_mod.HsvConfig] = None):
+                 mosaic: Optional[mosaic_mod.MosaicConfig] = None, hsv: Optional[colour_mod.HsvConfig] = None, cache=None,
+                 decode: str = 'pil'):
         import torch
         engine.require_gpu()
+        if decode not in ('pil', 'gpu'):
+            raise engine.YkError(f'InputPipeline: decode {decode!r}: expected pil or gpu')
         self.h, self.items = h, items
         self.hsv_table = colour_mod.param_table(seed, epoch, len(items), hsv) if hsv is not None else None       # [n_rows, 3], rank-independent
         self.mosaic = mosaic
@@ -158,6 +168,19 @@ class InputPipeline:
         self.seconds = 0.0
         self._thread = None
         self._stop = False
+        # cache=PictureCache (cache.py) and / or decode='gpu': every batch is composed from the cache's arena by one launch
+        self.decode = decode
+        self._own_cache = None
+        if cache is None and decode == 'gpu':                                   # staging only
+            from .cache import PictureCache
+            cache = self._own_cache = PictureCache(0, prefetch=self.q.maxsize, device=self.dev.index)
+        self.cache = cache
+        if cache is not None:
+            if cache.arena is None or cache.device != self.dev:
+                raise engine.YkError(f'InputPipeline: the picture cache lives on {cache.device}, the pipeline runs on {self.dev}')
+            if cache.ring < self.q.maxsize + 2:
+                raise engine.YkError(f'InputPipeline: prefetch {self.q.maxsize} needs a picture cache with {self.q.maxsize + 2} staging '
+                                     f'regions, this one has {cache.ring}')
 
     def __len__(self):
         return len(self.rows)
@@ -201,8 +224,8 @@ class InputPipeline:
                 if self._stop:
                     break
                 t0 = time.perf_counter()
-                if self.mosaic is not None:
-                    batch = self._mosaic_batch(rows, H, W)
+                if self.cache is not None or self.mosaic is not None:
+                    batch = self._cached_batch(rows, H, W) if self.cache is not None else self._mosaic_batch(rows, H, W)
                     self.images += batch.n
                     self.seconds += time.perf_counter() - t0
                     if not self._put(batch):
@@ -331,6 +354,157 @@ class InputPipeline:
             ready.record(self.stream)
         return Batch(x, labels, ready, n)
 
+    # ---- cache= / decode='gpu': the batch is composed from the arena of cache.py -------------------------------------------------
+    def _load(self, i: int):
+        """decode='gpu', a row that is not cached, on a worker thread: -> a jpeg.Baseline (the file read and parsed: the device decodes
+        it), or pixels - an array of the list, or a file the parser refuses (progressive, PNG ...), decoded by PIL as detect.py does."""
+        from . import jpeg
+        img = self.items[int(i)][0]
+        if not isinstance(img, (str, os.PathLike)):
+            return np.ascontiguousarray(img[..., :3], np.uint8)
+        with open(img, 'rb') as f:
+            data = f.read()
+        try:
+            return jpeg.parse_baseline(data)
+        except jpeg.Unsupported:
+            return np.ascontiguousarray(self.h._read_img(io.BytesIO(data))[..., :3], np.uint8)
+
+    def _copy_run(self, key, run, plan, got):
+        """The pictures of `run`, one contiguous run of `plan`, through ONE pinned slot to their arena offsets: one copy."""
+        import torch
+        if not run:
+            return
+        start = plan.table[run[0]][0]
+        end = plan.table[run[-1]][0] + got[run[-1]].size
+        view, slot = self._slot(key, (end - start,), torch.uint8)
+        flat = view.numpy()
+        for i in run:
+            o = plan.table[i][0] - start
+            flat[o:o + got[i].size] = got[i].reshape(-1)
+        self.cache.arena[start:end].copy_(view, non_blocking=True)
+        slot[1] = torch.cuda.Event()
+        slot[1].record(self.stream)
+
+    def _decode_into_arena(self, jp, plan, got):
+        """The parsed files of rows `jp`: their scans and tables cross PCIe and ONE yk_jpeg_decode_ragged_u8 writes the pictures at their
+        arena offsets.  -> the rows whose stream did not decode, with their status (waits for the decode: only batches with misses pay)."""
+        import torch
+        from . import jpeg
+        from .draw import RAGGED_DTYPE
+        if not jp:
+            return []
+        parsed = [got[i] for i in jp]
+        jbytes = sum((len(p.scan) + jpeg.SCAN_PAD + 3) // 4 * 4 for p in parsed) + len(jp) * jpeg.PIC_TABLE_BYTES
+        view, slot = self._slot('jscan', (jbytes,), torch.uint8)
+        _, pics, scan_bytes, table_bytes = jpeg.plan_decode(parsed, out=view.numpy())
+        d_buf = view.to(self.dev, non_blocking=True)
+        slot[1] = torch.cuda.Event()
+        slot[1].record(self.stream)
+        rows = np.zeros(len(jp), RAGGED_DTYPE)
+        for k, i in enumerate(jp):
+            rows[k]['offset'], rows[k]['h'], rows[k]['w'] = plan.table[i]
+        rows = engine.check_ragged_rows(rows, self.cache.arena_bytes)
+        d_pics = self._upload('jpics', pics.view(np.uint8).reshape(len(jp), jpeg.PIC_DTYPE.itemsize), torch.uint8)
+        d_rows = self._upload('jrows', rows.view(np.uint8).reshape(len(jp), RAGGED_DTYPE.itemsize), torch.uint8)
+        status = engine.jpeg_decode_ragged_u8(d_buf[:scan_bytes], d_pics, d_buf[scan_bytes:scan_bytes + table_bytes], d_rows, self.cache.arena,
+                                              stream=self.stream, work_bytes=engine.jpeg_decode_workspace_bytes(pics))
+        return [(i, code) for i, code in zip(jp, status.cpu().tolist()) if code]
+
+    def _cached_batch(self, rows, H: int, W: int) -> Batch:
+        """One batch from the picture cache: resolve the rows, bring the misses into the arena (each distinct picture once), ONE geometric
+        launch over the arena - yk_letterbox_ragged_u8 for plain samples, yk_mosaic_ragged_u8 for mosaics and, each sample four times its
+        own plain letterbox row, for augmented plain samples (bit for bit yk_letterbox_augment_u8: include/yolo_hip.h) - then HSV,
+        normalise and labels as on the other paths."""
+        import torch
+        from .draw import RAGGED_DTYPE
+        cache = self.cache
+        rows = np.asarray(rows, np.int64).reshape(-1)
+        n = len(rows)
+        self._tick += 1
+        if self.mosaic is not None:
+            uniq = [int(i) for i in np.unique(mosaic_mod.members(rows, self.mosaic_table, (H, W), self.mosaic.prob)[0])]
+        else:
+            uniq = [int(i) for i in np.unique(rows)]
+        known = cache.lookup(uniq)
+        missing = [i for i in uniq if i not in known]
+        load = self._load if self.decode == 'gpu' else self._image
+        from_files = any(isinstance(self.items[i][0], (str, os.PathLike)) for i in missing)
+        got = dict(zip(missing, self.pool.map(load, missing) if from_files else [load(i) for i in missing]))
+        raw = [i for i in missing if isinstance(got[i], np.ndarray)]            # pixels on the host: copied in
+        jp = [i for i in missing if not isinstance(got[i], np.ndarray)]         # parsed files: decoded in
+        region = cache.acquire() if missing else None
+        try:
+            # copied pictures first: the copied part of the admissions is one run of the persistent part, that of the staged one of the region
+            plan = cache.plan(raw + jp + sorted(known), lambda i: got[i].shape[:2] if i in raw else (got[i].h, got[i].w), region or 0)
+            hw_of = lambda i: plan.table[int(i)][1:]
+            M = centres = None
+            if self.mosaic is not None:
+                quads, centres, boxes = mosaic_mod.plan(rows, self.mosaic_table, hw_of, (H, W), boxes_of=lambda i: self.items[i][1],
+                                                        prob=self.mosaic.prob)
+            else:
+                boxes = letterbox_boxes_batch(self.h, [hw_of(i) for i in rows], [self.items[int(i)][1] for i in rows])
+            if self.table is not None:
+                A, t, M = aug_mod.matrices(self.table[rows], (H, W))
+                boxes = aug_mod.augment_boxes_batch(boxes, A, t, (H, W))
+            if self.mosaic is None and M is not None:                           # four times the sample's own plain letterbox row
+                quads = np.zeros((n, 4), mosaic_mod.ROW_DTYPE)
+                for b, i in enumerate(rows):
+                    quads[b, :] = (int(i), *hw_of(i), *mosaic_mod.letterbox_params(hw_of(i), (H, W)))
+                centres = np.zeros((n, 2), np.int32)
+            if centres is not None:
+                table = mosaic_mod.ragged_rows(quads, lambda i: plan.table[i][0])
+            else:
+                table = np.zeros(n, RAGGED_DTYPE)
+                for b, i in enumerate(rows):
+                    table[b]['offset'], table[b]['h'], table[b]['w'] = plan.table[int(i)]
+                engine.call('yk_letterbox_ragged_params', table, n, H, W)
+            table = engine.check_ragged_rows(table, cache.arena_bytes)
+            labs = self.h.batch_box_to_label(boxes)
+            lab_slots = [self._slot(('lab', l), labs[l].shape, torch.float32) for l in range(len(labs))]
+            for (view, _), lab in zip(lab_slots, labs):
+                view.numpy()[...] = lab
+            with torch.cuda.stream(self.stream):
+                written = cache.last_write()
+                if written is not None:                                         # (a pipeline of an earlier epoch wrote on its own stream)
+                    self.stream.wait_event(written)
+                if missing:
+                    self._copy_run('cadm', [i for i in plan.admitted if i in raw], plan, got)
+                    self._copy_run('cstg', [i for i in plan.staged if i in raw], plan, got)
+                    failed = self._decode_into_arena(jp, plan, got)
+                    behind = torch.cuda.Event()
+                    behind.record(self.stream)
+                    cache.commit(plan, [i for i, _ in failed], behind)
+                    if failed:
+                        i, code = failed[0]
+                        raise engine.YkError(f'{self.items[i][0]}: the JPEG stream does not decode (status {code}: yk_jpeg_decode_ragged_u8)')
+                else:
+                    cache.commit(plan)
+                d_table = self._upload('mtab', table.view(np.uint8).reshape(len(table), RAGGED_DTYPE.itemsize), torch.uint8)
+                if centres is not None:
+                    d_centres = self._upload('mcen', np.ascontiguousarray(centres, np.int32), torch.int32)
+                    inv = None if M is None else self._upload('inv', M.reshape(n, 6), torch.float64)
+                    frames = engine.mosaic_ragged_u8(cache.arena, d_table, d_centres, (H, W), inv=inv, stream=self.stream)
+                else:
+                    frames = engine.letterbox_ragged_u8(cache.arena, d_table, (H, W), stream=self.stream)
+        finally:
+            if region is not None:                                              # the region is free once everything queued so far has run
+                done = torch.cuda.Event()
+                done.record(self.stream)
+                cache.release(region, done)
+        with torch.cuda.stream(self.stream):
+            if self.hsv_table is not None:
+                engine.hsv_jitter_u8(frames, self._upload('hsv', self.hsv_table[rows], torch.float64), stream=self.stream)
+            x = torch.empty((n, H, W, 3), dtype=torch.float32, device=self.dev)
+            engine.call('yk_normalise_u8', frames, n, H * W * 3, x, engine._stream(self.stream))
+            labels = []
+            for view, slot in lab_slots:
+                labels.append(view.to(self.dev, non_blocking=True))
+                slot[1] = torch.cuda.Event()
+                slot[1].record(self.stream)
+            ready = torch.cuda.Event()
+            ready.record(self.stream)
+        return Batch(x, labels, ready, n)
+
     def _put(self, item) -> bool:
         """queue.put that gives up when the consumer has gone away (close() after an early break): never blocks forever."""
         while not self._stop:
@@ -380,6 +554,9 @@ class InputPipeline:
             pass
         self._thread = None
         self.pool.shutdown(wait=True)
+        if self._own_cache is not None:
+            self._own_cache.close()
+            self._own_cache = self.cache = None
 
     def __enter__(self):
         return self

@@ -43,7 +43,14 @@ reference, distill.py): knowledge distillation from a trained ne
 count and class count (`--teacher_def` / `--teacher_depth`; by default the student's own, e.g. its float, unpruned checkpoint for a QAT or a
 pruned run).  The teacher runs as an inference plan on the step's frames and one HIP launch per output layer adds the objectness-scaled
 distillation term, weighted by `--distill_weight`, to the loss and its gradient; the step line and the epoch line then name the `distill`
-term.  The validation loss stays the detection loss.  The empty default means off."""
+term.  The validation loss stays the detection loss.  The empty default means off.
+
+`--cache gpu` (`make train CACHE=gpu CACHEGB=8 CACHESTAGE=256`; not in the reference, cache.py): every training picture is
+decoded once and kept in `--cache_gb` GB of device memory; what does not fit passes through staging regions of `--cache_stage_mb` MB every
+time.  The loop owns the cache, every epoch's `InputPipeline(cache=...)` composes its batches from it by one launch - the batches of
+`--cache off`, bit for bit - and the epoch line gains `cache hits/misses, GB used/capacity`.  `--decode gpu` (`DECODE=gpu`, with or without
+the cache) has baseline JPEG files decoded on the GPU, directly into that memory: `make detect DECODE=gpu`'s pixels, not PIL's.  Validation
+is not cached."""
 from __future__ import annotations
 
 import argparse
@@ -134,7 +141,8 @@ def main(args, train_set, class_num, pre_ckpt, model_def, depth_multiplier, is_a
          obj_thresh, iou_thresh, vaildation_split, log_dir, is_prune, initial_sparsity=0.5, final_sparsity=0.9, end_epoch=5,
          frequency=100, synthetic=0, max_steps=0, is_qat='False', qat_momentum=0.99, qat_observe=8, val_map='False', val_map_obj=0.05,
          box_loss='mse', box_weight=1.0, is_mosaic='False', mosaic_prob=1.0, mosaic_off_epochs=0, is_hsv='False', hsv_hue=0.1, hsv_sat=1.5,
-         hsv_exposure=1.5, hsv_prob=1.0, teacher_ckpt='', teacher_def=None, teacher_depth=None, distill_weight=1.0):
+         hsv_exposure=1.5, hsv_prob=1.0, teacher_ckpt='', teacher_def=None, teacher_depth=None, distill_weight=1.0, cache='off',
+         cache_gb=8.0, cache_stage_mb=256, decode='pil'):
     import torch
     from .train import Trainer
     prune = is_prune == 'True'
@@ -158,6 +166,15 @@ def main(args, train_set, class_num, pre_ckpt, model_def, depth_multiplier, is_a
             if not (np.isfinite(v) and ok):
                 raise engine.YkError(f'{flag} {v}: {want}')
         hsv_cfg = HsvConfig(float(hsv_hue), float(hsv_sat), float(hsv_exposure), float(hsv_prob))
+    if cache not in ('off', 'gpu'):
+        raise engine.YkError(f'--cache {cache}: off or gpu')
+    if decode not in ('pil', 'gpu'):
+        raise engine.YkError(f'--decode {decode}: pil or gpu')
+    cached = cache == 'gpu'
+    if cached and not (np.isfinite(float(cache_gb)) and float(cache_gb) >= 0.0):
+        raise engine.YkError(f'--cache_gb {cache_gb}: a size in GB, not negative')
+    if (cached or decode == 'gpu') and not (np.isfinite(float(cache_stage_mb)) and float(cache_stage_mb) > 0.0):
+        raise engine.YkError(f'--cache_stage_mb {cache_stage_mb}: a size in MB, positive')
     distill = teacher_ckpt not in (None, 'None', '', '""')
     if distill and not (np.isfinite(float(distill_weight)) and float(distill_weight) >= 0.0):
         raise engine.YkError(f'--distill_weight {distill_weight}: a finite weight, not negative')
@@ -179,6 +196,10 @@ def main(args, train_set, class_num, pre_ckpt, model_def, depth_multiplier, is_a
             raise engine.YkError('--hsv True (HSV colour jitter, colour.py) runs in the GPU input pipeline: no HIP device') from e
         if distill:
             raise engine.YkError('--teacher_ckpt (knowledge distillation, distill.py) runs the teacher and its loss in HIP kernels: no HIP device') from e
+        if cached:
+            raise engine.YkError('--cache gpu (the picture cache, cache.py) keeps the decoded training pictures in device memory: no HIP device') from e
+        if decode == 'gpu':
+            raise engine.YkError('--decode gpu (baseline JPEG files decoded by yk_jpeg_decode_ragged_u8) runs in the GPU input pipeline: no HIP device') from e
         raise
     torch.cuda.set_device(local)
     dist = None
@@ -248,6 +269,14 @@ def main(args, train_set, class_num, pre_ckpt, model_def, depth_multiplier, is_a
         print(INFO, 'data augment is ', str(augment))                            # utils.py:418
         print(INFO, f'mosaic is {mosaic}, mosaic_prob {float(mosaic_prob)}, mosaic_off_epochs {int(mosaic_off_epochs)}')
         print(INFO, f'hsv is {hsv}, hsv_hue {float(hsv_hue)}, hsv_sat {float(hsv_sat)}, hsv_exposure {float(hsv_exposure)}, hsv_prob {float(hsv_prob)}')
+        if cached or decode == 'gpu':
+            print(INFO, f'cache is {cache}, cache_gb {float(cache_gb)}, cache_stage_mb {float(cache_stage_mb)}, decode is {decode}')
+    # the decoded pictures stay on the device from epoch to epoch (cache.py): the loop owns the arena, every epoch's pipeline reads it;
+    # --decode gpu without --cache gpu runs on its staging ring alone
+    pic_cache = None
+    if cached or decode == 'gpu':
+        from .cache import PictureCache
+        pic_cache = PictureCache(int(float(cache_gb) * (1 << 30)) if cached else 0, int(float(cache_stage_mb) * (1 << 20)), prefetch=2, device=local)
     steps, observed = 0, 0
     iou_box = box_loss != 'mse'
     for epoch in range(max_nrof_epochs):
@@ -259,7 +288,8 @@ def main(args, train_set, class_num, pre_ckpt, model_def, depth_multiplier, is_a
         pipe = InputPipeline(h, h.train_list, batch_size, rank, world, seed=rand_seed, epoch=epoch, shuffle=True, device=local,
                              augment=augment,                                    # the last mosaic_off_epochs epochs train on plain samples
                              mosaic=MosaicConfig(float(mosaic_prob)) if mosaic and epoch < max_nrof_epochs - int(mosaic_off_epochs) else None,
-                             hsv=hsv_cfg)                                       # ... the colour jitter stays on in them
+                             hsv=hsv_cfg,                                       # ... the colour jitter stays on in them
+                             **({} if pic_cache is None else dict(cache=pic_cache, decode=decode)))
         try:                                                                    # an exception in the step must not leave the producer running
             for x, ys in pipe:
                 if qat and epoch == 0 and observed < int(qat_observe):           # the first batches of epoch 0 only set the activation ranges
@@ -295,11 +325,13 @@ def main(args, train_set, class_num, pre_ckpt, model_def, depth_multiplier, is_a
                   (f'mean {box_loss} {run_box / max(seen, 1):.4f}, ' if iou_box else '') +
                   (f'mean distill {run_kd / max(seen, 1):.4f}, ' if distill else '') +
                   (f'val_loss {val:.4f}, ' if val is not None else '') + f'{time.time() - t0:.1f}s, input pipeline {pipe_rate:.0f} images/s/rank' +
-                  (f', val_mAP {vmap:.4f}' if vmap is not None else ''), flush=True)
+                  (f', val_mAP {vmap:.4f}' if vmap is not None else '') + (cache_line(pic_cache) if cached else ''), flush=True)
         for c in tr.counts:
             c.zero_()                                                           # Keras resets metrics every epoch
         if max_steps and steps >= max_steps:
             break
+    if pic_cache is not None:
+        pic_cache.close()
     if rank == 0:
         from . import keras_io
         stem = 'yolo_qat_model' if qat else 'yolo_prune_model' if prune else 'yolo_model'      # keras_train.py:102-111
@@ -321,6 +353,13 @@ def main(args, train_set, class_num, pre_ckpt, model_def, depth_multiplier, is_a
         dist.barrier()
         dist.destroy_process_group()
     return tr
+
+
+def cache_line(pic_cache) -> str:
+    """What --cache gpu appends to the epoch line: the distinct pictures of the batches so far served from the cache / brought in, and the
+    persistent part's fill."""
+    s = pic_cache.stats()
+    return f', cache {s.hits}/{s.misses} hits/misses, {s.bytes_used / 2 ** 30:.2f}/{s.capacity / 2 ** 30:.2f} GB'
 
 
 def load_weights(spec, path, weights) -> bool:
@@ -429,6 +468,12 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument('--teacher_def', type=str, default=None, help="the teacher's network (default: --model_def)")
     p.add_argument('--teacher_depth', type=float, choices=[0.5, 0.75, 1.0], default=None, help="the teacher's depth multiplier (default: --depth_multiplier)")
     p.add_argument('--distill_weight', type=float, default=1.0, help='weight of the distillation term')
+    p.add_argument('--cache', type=str, choices=['off', 'gpu'], default='off',
+                   help='gpu: keep the decoded training pictures in device memory and compose every batch from there (DESIGN.md 3.19)')
+    p.add_argument('--cache_gb', type=float, default=8, help='size of the picture cache; pictures that no longer fit are brought in every epoch')
+    p.add_argument('--cache_stage_mb', type=float, default=256, help='size of one staging region: the uncached pictures of ONE batch must fit')
+    p.add_argument('--decode', type=str, choices=['pil', 'gpu'], default='pil',
+                   help='who decodes the training pictures: PIL on the thread pool, or (baseline JPEG files) the GPU, into the cache')
     return p
 
 
@@ -440,7 +485,7 @@ def cli(argv=None):
                 a.prune_initial_sparsity, a.prune_final_sparsity, a.prune_end_epoch, a.prune_frequency, a.synthetic, a.max_steps,
                 a.qat, a.qat_momentum, a.qat_observe, a.val_map, a.val_map_obj, a.box_loss, a.box_weight, a.mosaic, a.mosaic_prob,
                 a.mosaic_off_epochs, a.hsv, a.hsv_hue, a.hsv_sat, a.hsv_exposure, a.hsv_prob, a.teacher_ckpt, a.teacher_def, a.teacher_depth,
-                a.distill_weight)
+                a.distill_weight, a.cache, a.cache_gb, a.cache_stage_mb, a.decode)
 
 
 if __name__ == '__main__':
