@@ -541,7 +541,10 @@ int yk_conv3x3_bwd_weight_f32(const float *x, const float *dz, int B, int Hi, in
                               int Co, float *dw, void *stream);
 int yk_conv3x3_bwd_data_f32(const float *dz, const float *w, int B, int Hi, int Wi, int Ci, int Ho, int Wo, int stride, int pad_t, int pad_l, int Co,
                             float *dx, void *stream);
-/* DepthwiseConv2D 3x3, weights [9][C] */
+/* DepthwiseConv2D 3x3, weights [9][C].  A NULL tensor or a non-positive size: YK_ERR_ARG, checked on the host before anything is launched
+ * (yk_dw3x3_bn_fwd_f32 below too).  Any C and any 4-byte aligned address: four channels per thread when C % 4 == 0 and the call's
+ * tensors are 16-byte aligned, one channel per thread otherwise - the same sums in the same order (the BatchNormalization apply passes
+ * below choose by the same rule). */
 int yk_dw3x3_fwd_f32(const float *x, const float *w, int B, int Hi, int Wi, int C, int Ho, int Wo, int stride, int pad_t,
                      int pad_l, float *y, void *stream);
 int yk_dw3x3_bwd_data_f32(const float *dy, const float *w, int B, int Hi, int Wi, int C, int Ho, int Wo, int stride,

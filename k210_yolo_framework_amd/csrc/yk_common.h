@@ -38,7 +38,25 @@ void yk_set_error(const char *fmt, ...);
         }                                                                                      \
     } while (0)
 
-// grow-only device scratch per (device, stream); safe because work on one stream is ordered.
+// grow-only device scratch per (device, stream, slot); safe because work on one stream is ordered.  Two calls on one stream that name the
+// same slot get the same buffer, so every slot of the library is named here and a new user takes a new name.  The numbers are the ones
+// the callers always used.
+enum yk_scratch_slot {
+    YK_SLOT_DECODE = 0,           // yk_decode.hip: boxes, scores, selections and counts of one yk_decode call
+    YK_SLOT_LOSS = 1,             // yk_loss.hip: the loss columns' partial sums per (image, chunk)
+    YK_SLOT_DWW = 12,             // yk_train.hip: yk_dw3x3_bwd_weight_f32's partials per row chunk
+    YK_SLOT_BN_PARTIAL = 13,      // yk_train.hip: BatchNorm / column-sum partials of every forward (yk_bn_train_fwd*, yk_*_bn_fwd_f32, yk_colsum_f32:
+                                  // doubles) and of yk_bn_train_bwd_f32 (floats).  Shared on purpose: in stream order each call has folded its partials
+                                  // before the next one writes them, and a captured step holds ONE buffer sized by its largest layer
+    YK_SLOT_SPLITK = 14,          // yk_train.hip: the split-K slabs of every ungrouped GEMM (yk_gemm_f32, yk_gemm_bn_fwd_f32, yk_conv3x3_*_f32).  Shared
+                                  // on purpose, for the same reason
+    YK_SLOT_L2 = 15,              // yk_train.hip: yk_l2_segments_f32's partials per block
+    YK_SLOT_NORMALISE = 16,       // yk_pre.hip: yk_normalise_u8's maximum per image
+    YK_SLOT_SPLITK_GROUPED = 22,  // yk_train.hip: the slabs of all problems of one yk_gemm_f32_grouped call (its fallback calls use YK_SLOT_SPLITK)
+    YK_SLOT_DWW_GROUPED = 23,     // yk_train.hip: the partials of all problems of one yk_dw3x3_bwd_weight_grouped_f32 call
+    YK_SLOT_PRUNE = 24,           // yk_prune.hip: the histograms and thresholds of one magnitude-pruning call
+    YK_SLOT_DISTILL = 25,         // yk_distill.hip: the distillation loss's partial sums per (image, chunk)
+};
 void *yk_scratch(int device, void *stream, int slot, size_t bytes);
 void yk_scratch_release_stream(void *stream);
 

@@ -705,7 +705,7 @@ static int decode_impl(const yk_decode_cfg_t *cfg, const float *const *d_pred, i
     const size_t sel_b = (size_t)batch * a.C * max_out * sizeof(int);
     const size_t cnt_b = (size_t)batch * a.C * sizeof(int);
     auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    char *ws = (char *)yk_scratch(dev, stream, 0, up(box_b) + up(sc_b) + 2 * up(sel_b) + up(cnt_b));
+    char *ws = (char *)yk_scratch(dev, stream, YK_SLOT_DECODE, up(box_b) + up(sc_b) + 2 * up(sel_b) + up(cnt_b));
     if (!ws) return YK_ERR_NOMEM;
     float4 *boxes = (float4 *)ws;
     float *scores_t = (float *)(ws + up(box_b));

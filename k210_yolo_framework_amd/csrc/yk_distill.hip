@@ -116,7 +116,7 @@ extern "C" int yk_distill_loss_f32(const float *d_teacher, const float *d_pred, 
         return YK_ERR_NO_DEVICE;
     }
     const int n_partial = batch * chunks;
-    double *partial = (double *)yk_scratch(dev, stream, 25, sizeof(double) * YK_DISTILL_COLS * (size_t)n_partial);
+    double *partial = (double *)yk_scratch(dev, stream, YK_SLOT_DISTILL, sizeof(double) * YK_DISTILL_COLS * (size_t)n_partial);
     if (!partial) return YK_ERR_NOMEM;
     hipStream_t st = (hipStream_t)stream;
     const float scale = weight / (float)batch_size;

@@ -275,7 +275,7 @@ static int loss_launch(const char *who, const yk_loss_cfg_ex_t *cfg, int n_out, 
     a.box_loss = box_loss;
     a.box_w = cfg->box_weight;
     const int chunks = (a.h * a.w * a.A + 255) / 256;
-    double *partial = (double *)yk_scratch(dev, stream, 1, sizeof(double) * YK_LOSS_COLS * batch * chunks);
+    double *partial = (double *)yk_scratch(dev, stream, YK_SLOT_LOSS, sizeof(double) * YK_LOSS_COLS * batch * chunks);
     if (!partial) return YK_ERR_NOMEM;
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid(batch, chunks);

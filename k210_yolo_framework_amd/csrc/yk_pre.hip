@@ -416,7 +416,7 @@ extern "C" int yk_normalise_u8(const uint8_t *d_frames, int batch, size_t per_im
         yk_set_error("yk_normalise_u8: no HIP device");
         return YK_ERR_NO_DEVICE;
     }
-    unsigned *mx = (unsigned *)yk_scratch(dev, stream, 16, sizeof(unsigned) * (size_t)batch);
+    unsigned *mx = (unsigned *)yk_scratch(dev, stream, YK_SLOT_NORMALISE, sizeof(unsigned) * (size_t)batch);
     if (!mx) return YK_ERR_NOMEM;
     hipLaunchKernelGGL(u8_image_max_kernel, dim3((unsigned)batch), dim3(1024), 0, (hipStream_t)stream, d_frames, per_image, mx);
     const size_t total = (size_t)batch * per_image;

@@ -114,7 +114,7 @@ extern "C" int yk_prune_masks_f32(const float *params, const long long *d_offset
     if (dev < 0) return YK_ERR_NO_DEVICE;
     hipStream_t st = (hipStream_t)stream;
     const size_t hist_words = (size_t)4 * nseg * 256;                // one histogram per pass: zeroed once, no pass waits for a clear
-    uint32_t *ws = (uint32_t *)yk_scratch(dev, stream, 24, sizeof(uint32_t) * (hist_words + 2 * (size_t)nseg));
+    uint32_t *ws = (uint32_t *)yk_scratch(dev, stream, YK_SLOT_PRUNE, sizeof(uint32_t) * (hist_words + 2 * (size_t)nseg));
     if (!ws) return YK_ERR_NOMEM;
     uint32_t *prefix = ws + hist_words, *krem = prefix + nseg;
     YK_HIP(hipMemsetAsync(ws, 0, sizeof(uint32_t) * hist_words, st));

@@ -30,6 +30,20 @@
 
 typedef float floatx4t __attribute__((ext_vector_type(4)));
 
+// The host checks of the entry points below: YK_ERR_ARG for a null tensor or a non-positive size, before the device is asked for and before
+// any launch.  A valid call launches what it always did.
+static int small_check(const char *who, bool ok) {
+    if (ok) return YK_OK;
+    yk_set_error("%s: bad argument", who);
+    return YK_ERR_ARG;
+}
+// The ONE rule for the 16-byte paths: a V = 4 kernel (float4 per thread along the channels) may be launched when C % 4 == 0 and every tensor
+// it reads or writes 16 bytes at a time starts 16-byte aligned (a null optional tensor counts as aligned).  Otherwise the scalar kernel runs.
+template <typename... P>
+static bool vec4_ok(int C, const P *...p) {
+    return C % 4 == 0 && ((... | (uintptr_t)p) & 15) == 0;
+}
+
 // --------------------------------------------------------------------------------------------------------
 // GEMM: 64x64 tile per workgroup (2x2 waves, each 32x32 = 2x2 MFMA 16x16x4 f32 tiles), BK = 16.
 // LDS holds both operands k-major (As[k][m], Bs[k][n]) so a wave's fragment read is 16 consecutive floats.
@@ -182,6 +196,25 @@ static int gemm_splits(int M, int N, int K) {
     }
     return s;
 }
+// 16 lanes per output fold the slices (splitk_sum16_kernel, and `wide` of the grouped sum): many slices of a small result
+static bool splitk_wide(int splits, size_t tot) { return splits >= 16 && tot <= 65536; }
+
+static gemm_args make_gemm(int transA, int transB, int M, int N, int K, float alpha, const float *A, int lda, const float *B, int ldb, float beta,
+                           float *C, int ldc) {
+    gemm_args g;
+    g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.transA = transA; g.transB = transB; g.splitk = 1;
+    g.alpha = alpha; g.beta = beta; g.A = A; g.B = B; g.C = C; g.ws = nullptr; g.stats = nullptr;
+    return g;
+}
+
+// Where a forward producer leaves the column partials of the batch statistics: [chunks][2][C] doubles in the BatchNorm slot.  rpc / cwl: the
+// rows per chunk and the channel-lane split of a reducing pass in bn_colreduce_kernel's layout, 0 where the producer has a chunking of its own
+struct bn_partials {
+    double *partial;
+    int chunks, rpc, cwl;
+};
+// the one split-K GEMM driver (defined with the implicit 3x3 GEMMs below): every ungrouped GEMM of this file is a call to it
+static int gemm_run(gemm_args g, const conv_args *cv, const bn_partials *bn, void *stream);
 
 extern "C" int yk_gemm_f32(int transA, int transB, int M, int N, int K, float alpha, const float *A, int lda, const float *B,
                            int ldb, float beta, float *C, int ldc, void *stream) {
@@ -189,35 +222,7 @@ extern "C" int yk_gemm_f32(int transA, int transB, int M, int N, int K, float al
         yk_set_error("yk_gemm_f32: bad argument");
         return YK_ERR_ARG;
     }
-    gemm_args g;
-    g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.transA = transA; g.transB = transB;
-    g.alpha = alpha; g.beta = beta; g.A = A; g.B = B; g.C = C; g.stats = nullptr;
-    const int s = gemm_splits(M, N, K);
-    g.splitk = s;
-    g.ws = nullptr;
-    hipStream_t st = (hipStream_t)stream;
-    if (s > 1) {
-        int dev = yk_current_device();
-        if (dev < 0) return YK_ERR_NO_DEVICE;
-        g.ws = (float *)yk_scratch(dev, stream, 14, sizeof(float) * (size_t)s * M * N);
-        if (!g.ws) return YK_ERR_NOMEM;
-    }
-    const dim3 grid((M + 63) / 64, (N + 63) / 64, s);
-    if (!transA && transB) launch_gemm_v2<false, true>(g, grid, st);          // forward
-    else if (!transA && !transB) launch_gemm_v2<false, false>(g, grid, st);   // data gradient
-    else if (transA && !transB) launch_gemm_v2<true, false>(g, grid, st);     // weight gradient
-    else hipLaunchKernelGGL(gemm_f32_kernel, grid, dim3(256), 0, st, g);
-    if (s > 1) {
-        const size_t tot = (size_t)M * N;
-        if (s >= 16 && tot <= 65536)
-            hipLaunchKernelGGL(splitk_sum16_kernel, dim3((unsigned)((tot + 15) / 16)), dim3(256), 0, st, (const float *)g.ws, s, M, N, alpha,
-                               beta, C, ldc);
-        else
-            hipLaunchKernelGGL(splitk_sum_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, (const float *)g.ws, s, M, N, alpha, beta,
-                               C, ldc);
-    }
-    YK_HIP(hipGetLastError());
-    return YK_OK;
+    return gemm_run(make_gemm(transA, transB, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc), nullptr, nullptr, stream);
 }
 
 // ---- grouped GEMMs (yk_gemm_f32.h): the K-slice sums of all problems of a group in one launch too
@@ -312,7 +317,7 @@ extern "C" int yk_gemm_f32_grouped(int count, int transA, int transB, const int 
     }
     float *ws = nullptr;
     if (ws_floats) {
-        ws = (float *)yk_scratch(dev, stream, 22, sizeof(float) * ws_floats);
+        ws = (float *)yk_scratch(dev, stream, YK_SLOT_SPLITK_GROUPED, sizeof(float) * ws_floats);
         if (!ws) return YK_ERR_NOMEM;
     }
     size_t ws_off = 0;
@@ -328,8 +333,7 @@ extern "C" int yk_gemm_f32_grouped(int count, int transA, int transB, const int 
         for (int j = 0; j < n; ++j) {
             const int i = grouped[g0 + j];
             gemm_args &g = G.p[j];
-            g.M = M[i]; g.N = N[i]; g.K = K[i]; g.lda = lda[i]; g.ldb = ldb[i]; g.ldc = ldc[i]; g.transA = transA; g.transB = transB;
-            g.alpha = alpha; g.beta = beta; g.A = A[i]; g.B = B[i]; g.C = C[i]; g.stats = nullptr; g.ws = nullptr;
+            g = make_gemm(transA, transB, M[i], N[i], K[i], alpha, A[i], lda[i], B[i], ldb[i], beta, C[i], ldc[i]);
             g.splitk = splits[i];
             if (splits[i] > 1) {
                 g.ws = ws + ws_off;
@@ -337,7 +341,7 @@ extern "C" int yk_gemm_f32_grouped(int count, int transA, int transB, const int 
                 sum_item &q = S.p[S.count++];
                 const size_t tot = (size_t)M[i] * N[i];
                 q.ws = g.ws; q.c = C[i]; q.splits = splits[i]; q.M = M[i]; q.N = N[i]; q.ldc = ldc[i]; q.first = swg;
-                q.wide = splits[i] >= 16 && tot <= 65536;
+                q.wide = splitk_wide(splits[i], tot);
                 swg += (int)(q.wide ? (tot + 15) / 16 : (tot + 255) / 256);
             }
             G.first[j] = wg;
@@ -401,7 +405,7 @@ extern "C" int yk_l2_segments_f32(const float *params, float *grads, const long 
     int dev = yk_current_device();
     if (dev < 0) return YK_ERR_NO_DEVICE;
     const int blocks = (int)std::min<long long>(512, (total + 255) / 256);
-    double *part = (double *)yk_scratch(dev, stream, 15, sizeof(double) * 512);
+    double *part = (double *)yk_scratch(dev, stream, YK_SLOT_L2, sizeof(double) * 512);
     if (!part) return YK_ERR_NOMEM;
     hipLaunchKernelGGL(l2_seg_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, params, grads, d_prefix, d_offset, nseg, 2.f * weight, want_value,
                        want_grad, part);
@@ -475,7 +479,7 @@ extern "C" int yk_im2col3x3_f32(const float *x, int B, int Hi, int Wi, int C, in
                                 float *col, void *stream) {
     conv_geom q = {B, Hi, Wi, C, Ho, Wo, stride, pad_t, pad_l};
     const size_t total = (size_t)B * Ho * Wo * 9 * C;
-    if (C % 4 == 0 && total / 4 < 0xffffff00ull && (((uintptr_t)x | (uintptr_t)col) & 15) == 0) {
+    if (vec4_ok(C, x, col) && total / 4 < 0xffffff00ull) {
         const uint32_t total4 = (uint32_t)(total / 4);
         hipLaunchKernelGGL(im2col3x3_v4_kernel, dim3((total4 + 255) / 256), dim3(256), 0, (hipStream_t)stream, q, x, col, total4);
         YK_HIP(hipGetLastError());
@@ -497,7 +501,7 @@ extern "C" int yk_col2im3x3_f32(const float *col, int B, int Hi, int Wi, int C, 
 // --------------------------------------------------------------------------------------------------------
 // depthwise 3x3, NHWC fp32; weights [9][C]
 // --------------------------------------------------------------------------------------------------------
-// V consecutive channels per thread (V = 4 when C % 4 == 0: one 16-byte access instead of four 4-byte ones)
+// V consecutive channels per thread (V = 4 where vec4_ok allows it: one 16-byte access instead of four 4-byte ones)
 template <int V>
 __device__ __forceinline__ void ldv(const float *p, float (&v)[V]) {
     if constexpr (V == 4) {
@@ -713,28 +717,28 @@ __global__ void __launch_bounds__(256) colsum_finish_grouped_kernel(const dww_gr
 
 static int lane_split(int C) { return C <= 16 ? 4 : (C <= 32 ? 5 : 6); }      // log2 of the channel lanes per block
 
-static int chunking(size_t M, int *rows_per_chunk) {
-    int chunks = (int)std::min<size_t>(512, (M + 255) / 256);
-    if (chunks < 1) chunks = 1;
-    *rows_per_chunk = (int)((M + chunks - 1) / chunks);
-    return (int)((M + *rows_per_chunk - 1) / *rows_per_chunk);
+// the three tensors of a depthwise call and every size of its geometry
+static int dw_check(const char *who, const void *a, const void *b, const void *c, const conv_geom &q) {
+    return small_check(who, a && b && c && q.B > 0 && q.Hi > 0 && q.Wi > 0 && q.C > 0 && q.Ho > 0 && q.Wo > 0);
 }
 
 extern "C" int yk_dw3x3_fwd_f32(const float *x, const float *w, int B, int Hi, int Wi, int C, int Ho, int Wo, int stride, int pad_t,
                                 int pad_l, float *y, void *stream) {
     conv_geom q = {B, Hi, Wi, C, Ho, Wo, stride, pad_t, pad_l};
-    const size_t total = (size_t)B * Ho * Wo * C;
-    if (C % 4 == 0) hipLaunchKernelGGL(dw_fwd_kernel<4>, dim3((unsigned)((total / 4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, q, x, w, y);
-    else hipLaunchKernelGGL(dw_fwd_kernel<1>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, q, x, w, y);
+    if (const int rc = dw_check("yk_dw3x3_fwd_f32", x, w, y, q)) return rc;
+    const bool v4 = vec4_ok(C, x, w, y);
+    const size_t threads = (size_t)B * Ho * Wo * C / (v4 ? 4 : 1);
+    hipLaunchKernelGGL(v4 ? dw_fwd_kernel<4> : dw_fwd_kernel<1>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, q, x, w, y);
     YK_HIP(hipGetLastError());
     return YK_OK;
 }
 extern "C" int yk_dw3x3_bwd_data_f32(const float *dy, const float *w, int B, int Hi, int Wi, int C, int Ho, int Wo, int stride,
                                      int pad_t, int pad_l, float *dx, void *stream) {
     conv_geom q = {B, Hi, Wi, C, Ho, Wo, stride, pad_t, pad_l};
-    const size_t total = (size_t)B * Hi * Wi * C;
-    if (C % 4 == 0) hipLaunchKernelGGL(dw_bwd_data_kernel<4>, dim3((unsigned)((total / 4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, q, dy, w, dx);
-    else hipLaunchKernelGGL(dw_bwd_data_kernel<1>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, q, dy, w, dx);
+    if (const int rc = dw_check("yk_dw3x3_bwd_data_f32", dy, w, dx, q)) return rc;
+    const bool v4 = vec4_ok(C, dy, w, dx);
+    const size_t threads = (size_t)B * Hi * Wi * C / (v4 ? 4 : 1);
+    hipLaunchKernelGGL(v4 ? dw_bwd_data_kernel<4> : dw_bwd_data_kernel<1>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, q, dy, w, dx);
     YK_HIP(hipGetLastError());
     return YK_OK;
 }
@@ -759,10 +763,11 @@ static dww_plan dww_planning(int B, int C, int Ho, int Wo) {
 extern "C" int yk_dw3x3_bwd_weight_f32(const float *x, const float *dy, int B, int Hi, int Wi, int C, int Ho, int Wo, int stride,
                                        int pad_t, int pad_l, float *dw, void *stream) {
     conv_geom q = {B, Hi, Wi, C, Ho, Wo, stride, pad_t, pad_l};
+    if (const int rc = dw_check("yk_dw3x3_bwd_weight_f32", x, dy, dw, q)) return rc;
     int dev = yk_current_device();
     if (dev < 0) return YK_ERR_NO_DEVICE;
     const dww_plan p = dww_planning(B, C, Ho, Wo);
-    float *partial = (float *)yk_scratch(dev, stream, 12, sizeof(float) * (size_t)p.chunks * 9 * C);
+    float *partial = (float *)yk_scratch(dev, stream, YK_SLOT_DWW, sizeof(float) * (size_t)p.chunks * 9 * C);
     if (!partial) return YK_ERR_NOMEM;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(dw_bwd_weight_kernel, dim3(p.chunks, p.groups), dim3(256), 0, st, q, x, dy, partial, p.rpc, p.cwl, p.segs, p.wseg);
@@ -791,7 +796,7 @@ extern "C" int yk_dw3x3_bwd_weight_grouped_f32(int count, const float *const *x,
         plans[i] = dww_planning(g[0], g[3], g[4], g[5]);
         floats += (size_t)plans[i].chunks * 9 * g[3];
     }
-    float *partial = (float *)yk_scratch(dev, stream, 23, sizeof(float) * floats);
+    float *partial = (float *)yk_scratch(dev, stream, YK_SLOT_DWW_GROUPED, sizeof(float) * floats);
     if (!partial) return YK_ERR_NOMEM;
     size_t off = 0;
     for (int g0 = 0; g0 < count; g0 += YK_GROUP_MAX) {
@@ -1209,10 +1214,11 @@ __global__ void __launch_bounds__(256) bn_colreduce_bwd_v4_kernel(const float *_
     }
 }
 
-static bool bn_cols_ok(long long M, int C, const void *a, const void *b, const void *c) {
+template <typename... P>
+static bool bn_cols_ok(long long M, int C, const P *...p) {
     // R = 3 rows per thread only: at 4 480 rows (R = 9) a workgroup pulls 287 KB in 32-byte row pieces through ONE CU's L1 and takes 27 / 18 us
     // against 16 / 11 us for the separate launches that spread the same bytes over the chip (r6c58)
-    return M <= 3 * 512 && C % 4 == 0 && (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) == 0;
+    return M <= 3 * 512 && vec4_ok(C, p...);
 }
 
 static int bn_chunking(size_t M, int C, int *rows_per_chunk, int *cwl) {
@@ -1224,8 +1230,67 @@ static int bn_chunking(size_t M, int C, int *rows_per_chunk, int *cwl) {
     return (int)((M + rpc - 1) / rpc);
 }
 
+// The BatchNorm slot for `chunks` partials of C columns, [chunk][2][C]: doubles from the forward producers, floats (the front of the same bytes)
+// from the backward reductions.  Every user of the slot sizes it here.
+static void *bn_partial_buf(int dev, void *stream, int chunks, int C) {
+    return yk_scratch(dev, stream, YK_SLOT_BN_PARTIAL, sizeof(double) * (size_t)chunks * 2 * C + sizeof(float) * C);
+}
+// sum z and sum z^2 per column and row chunk: the first stage of yk_bn_train_fwd_f32 and of yk_colsum_f32
+static int bn_colreduce_stats(const float *z, long long M, int C, void *stream, bn_partials *bp) {
+    int dev = yk_current_device();
+    if (dev < 0) return YK_ERR_NO_DEVICE;
+    bp->chunks = bn_chunking((size_t)M, C, &bp->rpc, &bp->cwl);
+    bp->partial = (double *)bn_partial_buf(dev, stream, bp->chunks, C);
+    if (!bp->partial) return YK_ERR_NOMEM;
+    hipLaunchKernelGGL(bn_colreduce_kernel<true>, dim3(bp->chunks, (C + (1 << bp->cwl) - 1) >> bp->cwl), dim3(256), 0, (hipStream_t)stream, z,
+                       (const float *)nullptr, (size_t)M, C, bp->rpc, bp->cwl, (const float *)nullptr, (const float *)nullptr, (const float *)nullptr,
+                       (const float *)nullptr, 0, 0.f, (void *)bp->partial);
+    return YK_OK;
+}
+// The partials a forward GEMM [M][N] over K leaves: one per 64-row tile from its statistics epilogue when K is not split, else those of the pass
+// that adds the K slices (bn_chunking).
+static int bn_gemm_partials(int M, int N, int K, void *stream, bn_partials *bp) {
+    int dev = yk_current_device();
+    if (dev < 0) return YK_ERR_NO_DEVICE;
+    bp->rpc = bp->cwl = 0;
+    bp->chunks = gemm_splits(M, N, K) > 1 ? bn_chunking((size_t)M, N, &bp->rpc, &bp->cwl) : (M + 63) / 64;
+    bp->partial = (double *)bn_partial_buf(dev, stream, bp->chunks, N);
+    return bp->partial ? YK_OK : YK_ERR_NOMEM;
+}
+
+// The forward tail: statistics from `chunks` partials, then the apply pass.  cols: the one-launch form of the small layers may be taken (the
+// fused producers; yk_bn_train_fwd_f32 keeps its three launches at every size).
+static int bn_finish_apply(const float *z, long long M, int C, const double *partial, int chunks, const float *gamma, const float *beta, float eps, int act,
+                           float alpha, float *y, float *save_mean, float *save_invstd, float *moving_mean, float *moving_var, float momentum,
+                           const float *res, bool cols, hipStream_t st) {
+    if (cols && bn_cols_ok(M, C, z, y, res, gamma, beta)) {
+        hipLaunchKernelGGL(bn_fwd_cols_kernel<3>, dim3((C + 7) / 8), dim3(1024), 0, st, z, (int)M, C, partial, chunks, 1.0 / (double)M, eps, gamma, beta, act,
+                           alpha, y, save_mean, save_invstd, moving_mean, moving_var, momentum, res);
+        YK_HIP(hipGetLastError());
+        return YK_OK;
+    }
+    if (chunks > 1024)
+        hipLaunchKernelGGL(bn_stats_finish_kernel<4>, dim3(C), dim3(256), 0, st, partial, chunks, C, 1.0 / (double)M, eps, save_mean, save_invstd,
+                           moving_mean, moving_var, momentum);
+    else
+        hipLaunchKernelGGL(bn_stats_finish_kernel<1>, dim3((C + 3) / 4), dim3(256), 0, st, partial, chunks, C, 1.0 / (double)M, eps, save_mean, save_invstd,
+                           moving_mean, moving_var, momentum);
+    const size_t total = (size_t)M * C;
+    const bool v4 = vec4_ok(C, z, save_mean, save_invstd, gamma, beta, y, res);
+    hipLaunchKernelGGL(v4 ? bn_apply_fwd_kernel<4> : bn_apply_fwd_kernel<1>, dim3((unsigned)((total / (v4 ? 4 : 1) + 255) / 256)), dim3(256), 0, st, z, total, C,
+                       (const float *)save_mean, (const float *)save_invstd, gamma, beta, act, alpha, y, res);
+    YK_HIP(hipGetLastError());
+    return YK_OK;
+}
+
+// bn_chunking never leaves more than 512 chunks, so the tail finishes with bn_stats_finish_kernel<1> here
 static int bn_train_fwd(const float *z, long long M, int C, const float *gamma, const float *beta, float eps, int act, float alpha, float *y,
-                        float *save_mean, float *save_invstd, float *moving_mean, float *moving_var, float momentum, const float *res, void *stream);
+                        float *save_mean, float *save_invstd, float *moving_mean, float *moving_var, float momentum, const float *res, void *stream) {
+    bn_partials bp;
+    if (const int rc = bn_colreduce_stats(z, M, C, stream, &bp)) return rc;
+    return bn_finish_apply(z, M, C, bp.partial, bp.chunks, gamma, beta, eps, act, alpha, y, save_mean, save_invstd, moving_mean, moving_var, momentum, res,
+                           false, (hipStream_t)stream);
+}
 extern "C" int yk_bn_train_fwd_f32(const float *z, long long M, int C, const float *gamma, const float *beta, float eps, int act,
                                    float alpha, float *y, float *save_mean, float *save_invstd, float *moving_mean,
                                    float *moving_var, float momentum, void *stream) {
@@ -1237,31 +1302,6 @@ extern "C" int yk_bn_train_fwd_res_f32(const float *z, long long M, int C, const
                                        float *moving_var, float momentum, const float *res, void *stream) {
     return bn_train_fwd(z, M, C, gamma, beta, eps, act, alpha, y, save_mean, save_invstd, moving_mean, moving_var, momentum, res, stream);
 }
-static int bn_train_fwd(const float *z, long long M, int C, const float *gamma, const float *beta, float eps, int act, float alpha, float *y,
-                        float *save_mean, float *save_invstd, float *moving_mean, float *moving_var, float momentum, const float *res, void *stream) {
-    int dev = yk_current_device();
-    if (dev < 0) return YK_ERR_NO_DEVICE;
-    int rpc, cwl;
-    const int chunks = bn_chunking((size_t)M, C, &rpc, &cwl);
-    char *ws = (char *)yk_scratch(dev, stream, 13, sizeof(double) * (size_t)chunks * 2 * C + sizeof(float) * C);
-    if (!ws) return YK_ERR_NOMEM;
-    double *partial = (double *)ws;
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(bn_colreduce_kernel<true>, dim3(chunks, (C + (1 << cwl) - 1) >> cwl), dim3(256), 0, st, z, (const float *)nullptr,
-                       (size_t)M, C, rpc, cwl, (const float *)nullptr, (const float *)nullptr, (const float *)nullptr, (const float *)nullptr, 0,
-                       0.f, (void *)partial);
-    hipLaunchKernelGGL(bn_stats_finish_kernel<1>, dim3((C + 3) / 4), dim3(256), 0, st, (const double *)partial, chunks, C, 1.0 / (double)M, eps,
-                       save_mean, save_invstd, moving_mean, moving_var, momentum);
-    const size_t total = (size_t)M * C;
-    if (C % 4 == 0)
-        hipLaunchKernelGGL(bn_apply_fwd_kernel<4>, dim3((unsigned)((total / 4 + 255) / 256)), dim3(256), 0, st, z, total, C, (const float *)save_mean,
-                           (const float *)save_invstd, gamma, beta, act, alpha, y, res);
-    else
-        hipLaunchKernelGGL(bn_apply_fwd_kernel<1>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, z, total, C, (const float *)save_mean,
-                           (const float *)save_invstd, gamma, beta, act, alpha, y, res);
-    YK_HIP(hipGetLastError());
-    return YK_OK;
-}
 
 extern "C" int yk_bn_train_bwd_f32(const float *z, const float *dy, long long M, int C, const float *gamma, const float *beta,
                                    const float *save_mean, const float *save_invstd, int act, float alpha, float *dz, float *dgamma,
@@ -1272,7 +1312,7 @@ extern "C" int yk_bn_train_bwd_f32(const float *z, const float *dy, long long M,
     }
     int dev = yk_current_device();
     if (dev < 0) return YK_ERR_NO_DEVICE;
-    if (bn_cols_ok(M, C, z, dy, dz) && (((uintptr_t)dgamma | (uintptr_t)dbeta | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)save_mean | (uintptr_t)save_invstd) & 15) == 0) {
+    if (bn_cols_ok(M, C, z, dy, dz, dgamma, dbeta, gamma, beta, save_mean, save_invstd)) {
         hipLaunchKernelGGL(bn_bwd_cols_kernel<3>, dim3((C + 7) / 8), dim3(1024), 0, (hipStream_t)stream, z, dy, (int)M, C, 1.f / (float)M, save_mean,
                            save_invstd, gamma, beta, act, alpha, dz, dgamma, dbeta);
         YK_HIP(hipGetLastError());
@@ -1282,32 +1322,27 @@ extern "C" int yk_bn_train_bwd_f32(const float *z, const float *dy, long long M,
     hipStream_t st = (hipStream_t)stream;
     float *partial;
     // (only the large layers: below ~50 000 rows the scalar form's launches are at the 5-9 us floor and the 8-row threads of this one are not: r6c62)
-    const bool v4 = C % 4 == 0 && M >= 50000 && M < (1ll << 31) &&
-                    (((uintptr_t)z | (uintptr_t)dy | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)save_mean | (uintptr_t)save_invstd) & 15) == 0;
-    if (v4) {
+    if (M >= 50000 && M < (1ll << 31) && vec4_ok(C, z, dy, gamma, beta, save_mean, save_invstd)) {
         const int CV = C / 4, CW = std::min(CV, 256), RL = 256 / CW, groups = (CV + CW - 1) / CW;
         chunks = (int)std::min<long long>(2048, (M + RL * 8 - 1) / (RL * 8));                   // ~8 rows per thread
         rpc = (int)(((M + chunks - 1) / chunks + RL - 1) / RL * RL);
         chunks = (int)((M + rpc - 1) / rpc);
-        partial = (float *)yk_scratch(dev, stream, 13, sizeof(double) * (size_t)chunks * 2 * C + sizeof(float) * C);
+        partial = (float *)bn_partial_buf(dev, stream, chunks, C);
         if (!partial) return YK_ERR_NOMEM;
         hipLaunchKernelGGL(bn_colreduce_bwd_v4_kernel, dim3(chunks, groups), dim3(256), 0, st, z, dy, (uint32_t)M, C, rpc, CW, RL, save_mean, save_invstd, gamma,
                            beta, act, alpha, partial);
     } else {
         chunks = bn_chunking((size_t)M, C, &rpc, &cwl);
-        partial = (float *)yk_scratch(dev, stream, 13, sizeof(double) * (size_t)chunks * 2 * C + sizeof(float) * C);
+        partial = (float *)bn_partial_buf(dev, stream, chunks, C);
         if (!partial) return YK_ERR_NOMEM;
         hipLaunchKernelGGL(bn_colreduce_kernel<false>, dim3(chunks, (C + (1 << cwl) - 1) >> cwl), dim3(256), 0, st, z, dy, (size_t)M, C, rpc, cwl,
                            save_mean, save_invstd, gamma, beta, act, alpha, (void *)partial);
     }
     hipLaunchKernelGGL(bn_bwd_finish_kernel, dim3((C + 3) / 4), dim3(256), 0, st, (const float *)partial, chunks, C, dbeta, dgamma);
     const size_t total = (size_t)M * C;
-    if (C % 4 == 0)
-        hipLaunchKernelGGL(bn_apply_bwd_kernel<4>, dim3((unsigned)((total / 4 + 255) / 256)), dim3(256), 0, st, z, dy, total, C, 1.f / (float)M, save_mean,
-                           save_invstd, gamma, beta, (const float *)dbeta, (const float *)dgamma, act, alpha, dz);
-    else
-        hipLaunchKernelGGL(bn_apply_bwd_kernel<1>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, z, dy, total, C, 1.f / (float)M, save_mean,
-                           save_invstd, gamma, beta, (const float *)dbeta, (const float *)dgamma, act, alpha, dz);
+    const bool a4 = vec4_ok(C, z, dy, save_mean, save_invstd, gamma, beta, dbeta, dgamma, dz);
+    hipLaunchKernelGGL(a4 ? bn_apply_bwd_kernel<4> : bn_apply_bwd_kernel<1>, dim3((unsigned)((total / (a4 ? 4 : 1) + 255) / 256)), dim3(256), 0, st, z, dy, total, C,
+                       1.f / (float)M, save_mean, save_invstd, gamma, beta, (const float *)dbeta, (const float *)dgamma, act, alpha, dz);
     YK_HIP(hipGetLastError());
     return YK_OK;
 }
@@ -1413,31 +1448,66 @@ __global__ void __launch_bounds__(256) dw_fwd_stats_kernel(conv_geom q, const fl
     }
 }
 
-// statistics from `chunks` partials, then the apply pass
-static int bn_finish_apply(const float *z, long long M, int C, const double *partial, int chunks, const float *gamma, const float *beta, float eps, int act,
-                           float alpha, float *y, float *save_mean, float *save_invstd, float *moving_mean, float *moving_var, float momentum,
-                           const float *res, hipStream_t st) {
-    if (bn_cols_ok(M, C, z, y, res) && (((uintptr_t)gamma | (uintptr_t)beta) & 15) == 0) {
-        hipLaunchKernelGGL(bn_fwd_cols_kernel<3>, dim3((C + 7) / 8), dim3(1024), 0, st, z, (int)M, C, partial, chunks, 1.0 / (double)M, eps, gamma, beta, act,
-                           alpha, y, save_mean, save_invstd, moving_mean, moving_var, momentum, res);
-        YK_HIP(hipGetLastError());
-        return YK_OK;
+// The split-K GEMM driver: the K slices (gemm_splits) and their slabs in the split-K slot, the tile launch, then the pass that adds the slices.
+//   cv   the 3x3 convolution of an implicit GEMM (yk_gemm_f32.h CONV), which g's layout names: N,T forward (1), T,N weight gradient (2), N,N data
+//        gradient (3); or null for a plain GEMM
+//   bn   forward only (N,T; alpha 1, beta 0): leave the column partials of the batch statistics there - from the tiles' epilogue when K is not
+//        split, else from the pass that adds the slices
+static int gemm_run(gemm_args g, const conv_args *cv, const bn_partials *bn, void *stream) {
+    hipStream_t st = (hipStream_t)stream;
+    const int s = g.splitk = gemm_splits(g.M, g.N, g.K);
+    if (s > 1) {
+        int dev = yk_current_device();
+        if (dev < 0) return YK_ERR_NO_DEVICE;
+        g.ws = (float *)yk_scratch(dev, stream, YK_SLOT_SPLITK, sizeof(float) * (size_t)s * g.M * g.N);
+        if (!g.ws) return YK_ERR_NOMEM;
+    } else if (bn) {
+        g.stats = bn->partial;
     }
-    if (chunks > 1024)
-        hipLaunchKernelGGL(bn_stats_finish_kernel<4>, dim3(C), dim3(256), 0, st, partial, chunks, C, 1.0 / (double)M, eps, save_mean, save_invstd,
-                           moving_mean, moving_var, momentum);
-    else
-        hipLaunchKernelGGL(bn_stats_finish_kernel<1>, dim3((C + 3) / 4), dim3(256), 0, st, partial, chunks, C, 1.0 / (double)M, eps, save_mean, save_invstd,
-                           moving_mean, moving_var, momentum);
-    const size_t total = (size_t)M * C;
-    if (C % 4 == 0)
-        hipLaunchKernelGGL(bn_apply_fwd_kernel<4>, dim3((unsigned)((total / 4 + 255) / 256)), dim3(256), 0, st, z, total, C, (const float *)save_mean,
-                           (const float *)save_invstd, gamma, beta, act, alpha, y, res);
-    else
-        hipLaunchKernelGGL(bn_apply_fwd_kernel<1>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, z, total, C, (const float *)save_mean,
-                           (const float *)save_invstd, gamma, beta, act, alpha, y, res);
+    const dim3 grid((g.M + 63) / 64, (g.N + 63) / 64, s);
+    if (cv) {
+        if (!g.transA && g.transB) {
+            if (g.stats) hipLaunchKernelGGL((gemm_f32_conv_kernel<false, true, true, 1>), grid, dim3(256), 0, st, g, *cv);
+            else hipLaunchKernelGGL((gemm_f32_conv_kernel<false, true, false, 1>), grid, dim3(256), 0, st, g, *cv);
+        } else if (g.transA) {
+            hipLaunchKernelGGL((gemm_f32_conv_kernel<true, false, false, 2>), grid, dim3(256), 0, st, g, *cv);
+        } else {
+            hipLaunchKernelGGL((gemm_f32_conv_kernel<false, false, false, 3>), grid, dim3(256), 0, st, g, *cv);
+        }
+    } else if (g.stats) {
+        launch_gemm_fwd_stats(g, grid, st);
+    } else if (!g.transA && g.transB) {
+        launch_gemm_v2<false, true>(g, grid, st);          // forward
+    } else if (!g.transA && !g.transB) {
+        launch_gemm_v2<false, false>(g, grid, st);         // data gradient
+    } else if (g.transA && !g.transB) {
+        launch_gemm_v2<true, false>(g, grid, st);          // weight gradient
+    } else {
+        hipLaunchKernelGGL(gemm_f32_kernel, grid, dim3(256), 0, st, g);
+    }
+    if (s > 1) {
+        const size_t tot = (size_t)g.M * g.N;
+        if (bn)
+            hipLaunchKernelGGL(splitk_sum_stats_kernel, dim3(bn->chunks, (g.N + (1 << bn->cwl) - 1) >> bn->cwl), dim3(256), 0, st, (const float *)g.ws, s,
+                               (size_t)g.M, g.N, g.C, g.ldc, bn->rpc, bn->cwl, bn->partial);
+        else if (splitk_wide(s, tot))
+            hipLaunchKernelGGL(splitk_sum16_kernel, dim3((unsigned)((tot + 15) / 16)), dim3(256), 0, st, (const float *)g.ws, s, g.M, g.N, g.alpha, g.beta,
+                               g.C, g.ldc);
+        else
+            hipLaunchKernelGGL(splitk_sum_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, (const float *)g.ws, s, g.M, g.N, g.alpha, g.beta,
+                               g.C, g.ldc);
+    }
     YK_HIP(hipGetLastError());
     return YK_OK;
+}
+// forward GEMM (plain or implicit 3x3) + BatchNormalization(training) + activation (+ residual): z = g.C, then y
+static int gemm_bn_fwd(const gemm_args &g, const conv_args *cv, const float *gamma, const float *beta, float eps, int act, float alpha, float *y,
+                       float *save_mean, float *save_invstd, float *moving_mean, float *moving_var, float momentum, const float *res, void *stream) {
+    bn_partials bp;
+    if (const int rc = bn_gemm_partials(g.M, g.N, g.K, stream, &bp)) return rc;
+    if (const int rc = gemm_run(g, cv, &bp, stream)) return rc;
+    return bn_finish_apply(g.C, g.M, g.N, bp.partial, bp.chunks, gamma, beta, eps, act, alpha, y, save_mean, save_invstd, moving_mean, moving_var, momentum,
+                           res, true, (hipStream_t)stream);
 }
 
 extern "C" int yk_gemm_bn_fwd_f32(int M, int N, int K, const float *X, int ldx, const float *W, int ldw, float *z, const float *gamma, const float *beta,
@@ -1447,49 +1517,24 @@ extern "C" int yk_gemm_bn_fwd_f32(int M, int N, int K, const float *X, int ldx, 
         yk_set_error("yk_gemm_bn_fwd_f32: bad argument");
         return YK_ERR_ARG;
     }
-    int dev = yk_current_device();
-    if (dev < 0) return YK_ERR_NO_DEVICE;
-    hipStream_t st = (hipStream_t)stream;
-    gemm_args g;
-    g.M = M; g.N = N; g.K = K; g.lda = ldx; g.ldb = ldw; g.ldc = N; g.transA = 0; g.transB = 1;
-    g.alpha = 1.f; g.beta = 0.f; g.A = X; g.B = W; g.C = z; g.ws = nullptr; g.stats = nullptr;
-    const int s = gemm_splits(M, N, K);
-    g.splitk = s;
-    const int mt = (M + 63) / 64;
-    int rpc = 0, cwl = 0;
-    const int chunks = s > 1 ? bn_chunking((size_t)M, N, &rpc, &cwl) : mt;
-    double *partial = (double *)yk_scratch(dev, stream, 13, sizeof(double) * (size_t)chunks * 2 * N + sizeof(float) * N);
-    if (!partial) return YK_ERR_NOMEM;
-    const dim3 grid(mt, (N + 63) / 64, s);
-    if (s > 1) {
-        g.ws = (float *)yk_scratch(dev, stream, 14, sizeof(float) * (size_t)s * M * N);
-        if (!g.ws) return YK_ERR_NOMEM;
-        launch_gemm_v2<false, true>(g, grid, st);
-        hipLaunchKernelGGL(splitk_sum_stats_kernel, dim3(chunks, (N + (1 << cwl) - 1) >> cwl), dim3(256), 0, st, (const float *)g.ws, s, (size_t)M, N, z, N,
-                           rpc, cwl, partial);
-    } else {
-        g.stats = partial;
-        launch_gemm_fwd_stats(g, grid, st);
-    }
-    return bn_finish_apply(z, M, N, partial, chunks, gamma, beta, eps, act, alpha, y, save_mean, save_invstd, moving_mean, moving_var, momentum, res, st);
+    return gemm_bn_fwd(make_gemm(0, 1, M, N, K, 1.f, X, ldx, W, ldw, 0.f, z, N), nullptr, gamma, beta, eps, act, alpha, y, save_mean, save_invstd, moving_mean,
+                       moving_var, momentum, res, stream);
 }
 
 extern "C" int yk_dw3x3_bn_fwd_f32(const float *x, const float *w, int B, int Hi, int Wi, int C, int Ho, int Wo, int stride, int pad_t, int pad_l,
                                    float *z, const float *gamma, const float *beta, float eps, int act, float alpha, float *y, float *save_mean,
                                    float *save_invstd, float *moving_mean, float *moving_var, float momentum, const float *res, void *stream) {
-    if (!x || !w || !z || !y || !gamma || !beta || !save_mean || !save_invstd || B <= 0 || C <= 0) {
-        yk_set_error("yk_dw3x3_bn_fwd_f32: bad argument");
-        return YK_ERR_ARG;
-    }
+    conv_geom q = {B, Hi, Wi, C, Ho, Wo, stride, pad_t, pad_l};
+    if (const int rc = dw_check("yk_dw3x3_bn_fwd_f32", x, w, z, q)) return rc;
+    if (const int rc = small_check("yk_dw3x3_bn_fwd_f32", y && gamma && beta && save_mean && save_invstd)) return rc;
     int dev = yk_current_device();
     if (dev < 0) return YK_ERR_NO_DEVICE;
-    conv_geom q = {B, Hi, Wi, C, Ho, Wo, stride, pad_t, pad_l};
     const long long M = (long long)B * Ho * Wo;
     if (M >= (1ll << 31)) {
         yk_set_error("yk_dw3x3_bn_fwd_f32: more than 2^31 output pixels");
         return YK_ERR_ARG;
     }
-    const int V = C % 4 == 0 ? 4 : 1, CV = C / V;
+    const int V = vec4_ok(C, x, w, z) ? 4 : 1, CV = C / V;
     // channel lanes: at most 64 per workgroup, the groups of equal width (144 float4 lanes = 3 x 48 with 5 row lanes; one group of 144 would leave one row
     // lane and 112 idle threads)
     const int groups = (CV + 63) / 64, CW = (CV + groups - 1) / groups, RL = 256 / CW;
@@ -1499,12 +1544,11 @@ extern "C" int yk_dw3x3_bn_fwd_f32(const float *x, const float *w, int B, int Hi
     int chunks = (int)std::min<long long>(8192, (M + RL * rpt - 1) / (RL * rpt));
     const int rpc = (int)(((M + chunks - 1) / chunks + RL - 1) / RL * RL);
     chunks = (int)((M + rpc - 1) / rpc);
-    double *partial = (double *)yk_scratch(dev, stream, 13, sizeof(double) * (size_t)chunks * 2 * C + sizeof(float) * C);
+    double *partial = (double *)bn_partial_buf(dev, stream, chunks, C);
     if (!partial) return YK_ERR_NOMEM;
     hipStream_t st = (hipStream_t)stream;
-    if (V == 4) hipLaunchKernelGGL(dw_fwd_stats_kernel<4>, dim3(chunks, groups), dim3(256), 0, st, q, x, w, z, rpc, CW, RL, partial);
-    else hipLaunchKernelGGL(dw_fwd_stats_kernel<1>, dim3(chunks, groups), dim3(256), 0, st, q, x, w, z, rpc, CW, RL, partial);
-    return bn_finish_apply(z, M, C, partial, chunks, gamma, beta, eps, act, alpha, y, save_mean, save_invstd, moving_mean, moving_var, momentum, res, st);
+    hipLaunchKernelGGL(V == 4 ? dw_fwd_stats_kernel<4> : dw_fwd_stats_kernel<1>, dim3(chunks, groups), dim3(256), 0, st, q, x, w, z, rpc, CW, RL, partial);
+    return bn_finish_apply(z, M, C, partial, chunks, gamma, beta, eps, act, alpha, y, save_mean, save_invstd, moving_mean, moving_var, momentum, res, true, st);
 }
 
 // --------------------------------------------------------------------------------------------------------
@@ -1512,47 +1556,10 @@ extern "C" int yk_dw3x3_bn_fwd_f32(const float *x, const float *w, int B, int Hi
 // head conv), multiplies it, and for the data gradient writes a column matrix of gradients and folds it (col2im).  Needs Cin % 4 == 0 (and
 // Cout % 4 == 0, stride 1 for the data gradient); the 3-channel stem and the strided data gradients keep the column matrix.
 // --------------------------------------------------------------------------------------------------------
-static int conv_gemm(gemm_args g, const conv_args &cv, int mode, double *stats_partial, int *chunks_out, int *rpc_out, int *cwl_out, int dev, void *stream) {
-    hipStream_t st = (hipStream_t)stream;
-    const int s = gemm_splits(g.M, g.N, g.K);
-    g.splitk = s;
-    g.ws = nullptr;
-    g.stats = nullptr;
-    if (s > 1) {
-        g.ws = (float *)yk_scratch(dev, stream, 14, sizeof(float) * (size_t)s * g.M * g.N);
-        if (!g.ws) return YK_ERR_NOMEM;
-    } else if (stats_partial) {
-        g.stats = stats_partial;
-    }
-    const dim3 grid((g.M + 63) / 64, (g.N + 63) / 64, s);
-    if (mode == 1) {
-        if (g.stats) hipLaunchKernelGGL((gemm_f32_conv_kernel<false, true, true, 1>), grid, dim3(256), 0, st, g, cv);
-        else hipLaunchKernelGGL((gemm_f32_conv_kernel<false, true, false, 1>), grid, dim3(256), 0, st, g, cv);
-    } else if (mode == 2) {
-        hipLaunchKernelGGL((gemm_f32_conv_kernel<true, false, false, 2>), grid, dim3(256), 0, st, g, cv);
-    } else {
-        hipLaunchKernelGGL((gemm_f32_conv_kernel<false, false, false, 3>), grid, dim3(256), 0, st, g, cv);
-    }
-    if (s > 1) {
-        const size_t tot = (size_t)g.M * g.N;
-        if (stats_partial)
-            hipLaunchKernelGGL(splitk_sum_stats_kernel, dim3(*chunks_out, (g.N + (1 << *cwl_out) - 1) >> *cwl_out), dim3(256), 0, st, (const float *)g.ws, s, (size_t)g.M, g.N,
-                               g.C, g.ldc, *rpc_out, *cwl_out, stats_partial);
-        else if (s >= 16 && tot <= 65536)
-            hipLaunchKernelGGL(splitk_sum16_kernel, dim3((unsigned)((tot + 15) / 16)), dim3(256), 0, st, (const float *)g.ws, s, g.M, g.N, g.alpha, g.beta, g.C, g.ldc);
-        else
-            hipLaunchKernelGGL(splitk_sum_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, (const float *)g.ws, s, g.M, g.N, g.alpha, g.beta, g.C, g.ldc);
-    }
-    YK_HIP(hipGetLastError());
-    return YK_OK;
-}
 // YK_ERR_ARG for a null tensor or a non-positive size, YK_ERR_UNSUPPORTED for what the kernels do not cover (channel counts, alignment)
 static int conv3x3_check(const char *who, const void *a, const void *b, const void *c, int B, int Ci, int Co, bool need_co4) {
-    if (!a || !b || !c || B <= 0 || Ci <= 0 || Co <= 0) {
-        yk_set_error("%s: bad argument", who);
-        return YK_ERR_ARG;
-    }
-    if (Ci % 4 || (need_co4 && Co % 4) || (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15)) {
+    if (const int rc = small_check(who, a && b && c && B > 0 && Ci > 0 && Co > 0)) return rc;
+    if (!vec4_ok(Ci, a, b, c) || (need_co4 && Co % 4)) {
         yk_set_error("%s: needs Cin %% 4 == 0%s and 16-byte aligned tensors (use yk_im2col3x3_f32 + yk_gemm_f32 otherwise)", who, need_co4 ? ", Cout % 4 == 0" : "");
         return YK_ERR_UNSUPPORTED;
     }
@@ -1567,40 +1574,22 @@ extern "C" int yk_conv3x3_bn_fwd_f32(const float *x, const float *w, int B, int 
         yk_set_error("yk_conv3x3_bn_fwd_f32: bad BatchNormalization argument");
         return YK_ERR_ARG;
     }
-    int dev = yk_current_device();
-    if (dev < 0) return YK_ERR_NO_DEVICE;
-    const long long Mll = (long long)B * Ho * Wo;
-    if (Mll >= (1ll << 31) / 9) {
+    const long long M = (long long)B * Ho * Wo;
+    if (M >= (1ll << 31) / 9) {
         yk_set_error("yk_conv3x3_bn_fwd_f32: too many pixels");
         return YK_ERR_ARG;
     }
-    const int M = (int)Mll;
-    gemm_args g;
-    g.M = M; g.N = Co; g.K = 9 * Ci; g.lda = 9 * Ci; g.ldb = 9 * Ci; g.ldc = Co; g.transA = 0; g.transB = 1;
-    g.alpha = 1.f; g.beta = 0.f; g.A = x; g.B = w; g.C = z;
-    conv_args cv = {{B, Hi, Wi, Ci, Ho, Wo, stride, pad_t, pad_l}, Co};
-    if (!gamma) return conv_gemm(g, cv, 1, nullptr, nullptr, nullptr, nullptr, dev, stream);
-    const int s = gemm_splits(M, Co, 9 * Ci), mt = (M + 63) / 64;
-    int rpc = 0, cwl = 0;
-    int chunks = s > 1 ? bn_chunking((size_t)M, Co, &rpc, &cwl) : mt;
-    double *partial = (double *)yk_scratch(dev, stream, 13, sizeof(double) * (size_t)chunks * 2 * Co + sizeof(float) * Co);
-    if (!partial) return YK_ERR_NOMEM;
-    const int rc = conv_gemm(g, cv, 1, partial, &chunks, &rpc, &cwl, dev, stream);
-    if (rc != YK_OK) return rc;
-    return bn_finish_apply(z, M, Co, partial, chunks, gamma, beta, eps, act, alpha, y, save_mean, save_invstd, moving_mean, moving_var, momentum, res,
-                           (hipStream_t)stream);
+    const gemm_args g = make_gemm(0, 1, (int)M, Co, 9 * Ci, 1.f, x, 9 * Ci, w, 9 * Ci, 0.f, z, Co);
+    const conv_args cv = {{B, Hi, Wi, Ci, Ho, Wo, stride, pad_t, pad_l}, Co};
+    if (!gamma) return gemm_run(g, &cv, nullptr, stream);
+    return gemm_bn_fwd(g, &cv, gamma, beta, eps, act, alpha, y, save_mean, save_invstd, moving_mean, moving_var, momentum, res, stream);
 }
 // dw [Co][9 * Ci] = dz^T * col(x)      (tf Conv2DBackpropFilter)
 extern "C" int yk_conv3x3_bwd_weight_f32(const float *x, const float *dz, int B, int Hi, int Wi, int Ci, int Ho, int Wo, int stride, int pad_t, int pad_l,
                                          int Co, float *dw, void *stream) {
     if (const int rc = conv3x3_check("yk_conv3x3_bwd_weight_f32", x, dz, dw, B, Ci, Co, true)) return rc;
-    int dev = yk_current_device();
-    if (dev < 0) return YK_ERR_NO_DEVICE;
-    gemm_args g;
-    g.M = Co; g.N = 9 * Ci; g.K = B * Ho * Wo; g.lda = Co; g.ldb = 9 * Ci; g.ldc = 9 * Ci; g.transA = 1; g.transB = 0;
-    g.alpha = 1.f; g.beta = 0.f; g.A = dz; g.B = x; g.C = dw;
-    conv_args cv = {{B, Hi, Wi, Ci, Ho, Wo, stride, pad_t, pad_l}, Co};
-    return conv_gemm(g, cv, 2, nullptr, nullptr, nullptr, nullptr, dev, stream);
+    const conv_args cv = {{B, Hi, Wi, Ci, Ho, Wo, stride, pad_t, pad_l}, Co};
+    return gemm_run(make_gemm(1, 0, Co, 9 * Ci, B * Ho * Wo, 1.f, dz, Co, x, 9 * Ci, 0.f, dw, 9 * Ci), &cv, nullptr, stream);
 }
 // dx = the transposed convolution of dz (stride 1)      (tf Conv2DBackpropInput)
 extern "C" int yk_conv3x3_bwd_data_f32(const float *dz, const float *w, int B, int Hi, int Wi, int Ci, int Ho, int Wo, int stride, int pad_t, int pad_l, int Co,
@@ -1610,26 +1599,14 @@ extern "C" int yk_conv3x3_bwd_data_f32(const float *dz, const float *w, int B, i
         yk_set_error("yk_conv3x3_bwd_data_f32: stride %d (only stride 1; use yk_gemm_f32 + yk_col2im3x3_f32)", stride);
         return YK_ERR_UNSUPPORTED;
     }
-    int dev = yk_current_device();
-    if (dev < 0) return YK_ERR_NO_DEVICE;
-    gemm_args g;
-    g.M = B * Hi * Wi; g.N = Ci; g.K = 9 * Co; g.lda = 9 * Co; g.ldb = Ci; g.ldc = Ci; g.transA = 0; g.transB = 0;
-    g.alpha = 1.f; g.beta = 0.f; g.A = dz; g.B = w; g.C = dx;
-    conv_args cv = {{B, Hi, Wi, Ci, Ho, Wo, stride, pad_t, pad_l}, Co};
-    return conv_gemm(g, cv, 3, nullptr, nullptr, nullptr, nullptr, dev, stream);
+    const conv_args cv = {{B, Hi, Wi, Ci, Ho, Wo, stride, pad_t, pad_l}, Co};
+    return gemm_run(make_gemm(0, 0, B * Hi * Wi, Ci, 9 * Co, 1.f, dz, 9 * Co, w, Ci, 0.f, dx, Ci), &cv, nullptr, stream);
 }
 
 // bias add (+ optional column sum of the gradient for the bias) for the two biased output convs
 __global__ void __launch_bounds__(256) bias_add_kernel(float *y, size_t total, int C, const float *bias) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i < total) y[i] += bias[i % C];
-}
-// The host checks of the small calls below: YK_ERR_ARG for a null tensor or a non-positive size, before the device is asked for and before
-// any launch.  A valid call launches what it always did.
-static int small_check(const char *who, bool ok) {
-    if (ok) return YK_OK;
-    yk_set_error("%s: bad argument", who);
-    return YK_ERR_ARG;
 }
 // MaxPool2D 2x2 'same': stride 1 or 2 and Ho x Wo = ceil(Hi / stride) x ceil(Wi / stride), the only geometry the kernels index correctly
 static int pool_check(const char *who, const void *a, const void *b, const void *c, int B, int Hi, int Wi, int C, int Ho, int Wo, int stride) {
@@ -1662,17 +1639,9 @@ __global__ void __launch_bounds__(256) colsum_from_stats_kernel(const double *__
 }
 extern "C" int yk_colsum_f32(const float *x, long long M, int C, float *out, void *stream) {
     if (const int rc = small_check("yk_colsum_f32", x && out && M > 0 && C > 0)) return rc;
-    int dev = yk_current_device();
-    if (dev < 0) return YK_ERR_NO_DEVICE;
-    int rpc, cwl;
-    const int chunks = bn_chunking((size_t)M, C, &rpc, &cwl);
-    double *partial = (double *)yk_scratch(dev, stream, 13, sizeof(double) * (size_t)chunks * 2 * C + sizeof(float) * C);
-    if (!partial) return YK_ERR_NOMEM;
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(bn_colreduce_kernel<true>, dim3(chunks, (C + (1 << cwl) - 1) >> cwl), dim3(256), 0, st, x, (const float *)nullptr, (size_t)M,
-                       C, rpc, cwl, (const float *)nullptr, (const float *)nullptr, (const float *)nullptr, (const float *)nullptr, 0, 0.f,
-                       (void *)partial);
-    hipLaunchKernelGGL(colsum_from_stats_kernel, dim3((C + 3) / 4), dim3(256), 0, st, (const double *)partial, chunks, C, out);
+    bn_partials bp;
+    if (const int rc = bn_colreduce_stats(x, M, C, stream, &bp)) return rc;
+    hipLaunchKernelGGL(colsum_from_stats_kernel, dim3((C + 3) / 4), dim3(256), 0, (hipStream_t)stream, (const double *)bp.partial, bp.chunks, C, out);
     YK_HIP(hipGetLastError());
     return YK_OK;
 }

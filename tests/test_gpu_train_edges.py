@@ -333,3 +333,185 @@ def test_depthwise_bn_forward_against_float64(i):
     torch.cuda.synchronize()
     _tails_intact(*bufs)
     _fused_check(o, z_ref, ref, 1e-4)
+
+
+# --------------------------------------------------------------------------------------------- the 16-byte rule of the host wrappers
+# A V = 4 kernel is launched only when C % 4 == 0 AND every tensor it touches 16 bytes at a time starts on a 16-byte boundary (vec4_ok in
+# yk_train.hip); otherwise the scalar kernel runs.  Each entry point is called with every tensor aligned and once per tensor argument with
+# that tensor 4 bytes past a boundary (a [1:] view of a buffer one float longer); every call meets the float64 reference within the bound
+# the tests above apply to that entry point.
+def _placed(which, ins, outs):
+    """Device tensors of one call: inputs from numpy arrays, outputs as views of sentinel-filled buffers with TAIL floats behind them.  The
+    tensor named `which` starts 4 bytes past a 16-byte boundary (one sentinel float in front), every other one on a boundary."""
+    t, bufs = {}, {}
+    for k, a in ins.items():
+        a, off = np.array(a, np.float32), int(k == which)               # (a copy: the shared problems are read-only)
+        buf = torch.zeros(a.size + off, device='cuda')
+        buf[off:] = torch.from_numpy(a.reshape(-1)).cuda()
+        t[k] = buf[off:].view(*a.shape)
+    for k, shape in outs.items():
+        n, off = int(np.prod(shape)), int(k == which)
+        bufs[k] = torch.full((off + n + TAIL,), SENTINEL, device='cuda')
+        t[k] = bufs[k][off:off + n].view(*shape)
+    for k, v in t.items():
+        assert v.data_ptr() % 16 == (4 if k == which else 0), k
+    assert which is None or which in t, which
+    return t, bufs
+
+
+def _guards_intact(bufs, which):
+    _tails_intact(*bufs.values())
+    if which in bufs:
+        assert float(bufs[which][0]) == SENTINEL, f'{which}: written before its start'
+
+
+def _dw_align_call(engine, L, fn, case, which, p, a, out):
+    """One of the two three-tensor depthwise calls (a, w -> out) with `which` misaligned: the output as numpy."""
+    geom, _ = tc.dw_geom(case)
+    B, Hi, Wi, Cc, Ho, Wo = geom[:6]
+    shape = (B, Ho, Wo, Cc) if out == 'y' else (B, Hi, Wi, Cc)
+    t, bufs = _placed(which, {a: p[a], 'w': p['w'].reshape(9, Cc)}, {out: shape})
+    assert fn(engine._ptr(t[a]), engine._ptr(t['w']), *[C.c_int(v) for v in geom], engine._ptr(t[out]), _st()) == 0, L.yk_last_error()
+    torch.cuda.synchronize()
+    _guards_intact(bufs, which)
+    return t[out].cpu().numpy()
+
+
+@pytest.mark.parametrize('which', [None, 'x', 'w', 'y'], ids=str)
+@pytest.mark.parametrize('case', tc.ALIGN_DW_CASES, ids=str)
+def test_depthwise_forward_with_a_misaligned_tensor(case, which):
+    """yk_dw3x3_fwd_f32: exact on integer data, 1e-4 on normal data; dw_fwd_kernel<1> and <4> add the taps in one order, so the call with a
+    misaligned tensor returns the bits of the aligned call."""
+    engine, L = _lib()
+    p = tc.dw_problem(case, True)
+    assert p['abs_sum'] < 2 ** 24
+    assert np.array_equal(_dw_align_call(engine, L, L.yk_dw3x3_fwd_f32, case, which, p, 'x', 'y'), p['y'])
+    p = tc.dw_problem(case, False)
+    y = _dw_align_call(engine, L, L.yk_dw3x3_fwd_f32, case, which, p, 'x', 'y')
+    _close(y, p['y'], 1e-4)
+    if which:
+        assert np.array_equal(y, _dw_align_call(engine, L, L.yk_dw3x3_fwd_f32, case, None, p, 'x', 'y'))
+
+
+@pytest.mark.parametrize('which', [None, 'dy', 'w', 'dx'], ids=str)
+@pytest.mark.parametrize('case', tc.ALIGN_DW_CASES, ids=str)
+def test_depthwise_data_gradient_with_a_misaligned_tensor(case, which):
+    """yk_dw3x3_bwd_data_f32: exact on integer data, 1e-4 on normal data."""
+    engine, L = _lib()
+    p = tc.dw_problem(case, True)
+    assert p['abs_sum'] < 2 ** 24
+    assert np.array_equal(_dw_align_call(engine, L, L.yk_dw3x3_bwd_data_f32, case, which, p, 'dy', 'dx'), p['dx'])
+    p = tc.dw_problem(case, False)
+    _close(_dw_align_call(engine, L, L.yk_dw3x3_bwd_data_f32, case, which, p, 'dy', 'dx'), p['dx'], 1e-4)
+
+
+_BN_FWD_OUTS = ('y', 'mean', 'invstd', 'moving_mean', 'moving_var')
+
+
+def _bn_fwd_tensors(which, ins, M, Cc, z_out):
+    """_placed for a BatchNorm forward: y [M][Cc] (and z when the call produces it), four vectors, the moving statistics at (0, 1)."""
+    outs = dict({'z': (M, Cc)} if z_out else {}, y=(M, Cc), mean=(Cc,), invstd=(Cc,), moving_mean=(Cc,), moving_var=(Cc,))
+    t, bufs = _placed(which, ins, outs)
+    t['moving_mean'].zero_()
+    t['moving_var'].fill_(1.0)
+    return t, bufs
+
+
+@pytest.mark.parametrize('which', [None, 'x', 'w', 'z', 'gamma', 'beta', 'y', 'mean', 'invstd', 'moving_mean', 'moving_var', 'res'], ids=str)
+@pytest.mark.parametrize('case', tc.ALIGN_DW_CASES, ids=str)
+def test_depthwise_bn_forward_with_a_misaligned_tensor(case, which):
+    """yk_dw3x3_bn_fwd_f32 with a residual, against the depthwise reference and BatchNorm in float64: the bounds of
+    test_depthwise_bn_forward_against_float64."""
+    engine, L = _lib()
+    geom, _ = tc.dw_geom(case)
+    B, Hi, Wi, Cc, Ho, Wo = geom[:6]
+    M = B * Ho * Wo
+    act, alpha = tc.ACTS[2]
+    p = tc.dw_problem(case, False)
+    rng = np.random.default_rng(Cc + M)
+    gamma, beta = rng.uniform(0.5, 2, Cc).astype(np.float32), rng.normal(size=Cc).astype(np.float32)
+    r = rng.normal(size=(M, Cc)).astype(np.float32)
+    z_ref = p['y'].reshape(M, Cc)
+    ref = tc.bn_ref(z_ref, gamma, beta, None, act, alpha, res=r)
+    t, bufs = _bn_fwd_tensors(which, dict(x=p['x'], w=p['w'].reshape(9, Cc), gamma=gamma, beta=beta, res=r), M, Cc, True)
+    assert L.yk_dw3x3_bn_fwd_f32(engine._ptr(t['x']), engine._ptr(t['w']), *[C.c_int(v) for v in geom], engine._ptr(t['z']), engine._ptr(t['gamma']),
+                                 engine._ptr(t['beta']), C.c_float(tc.EPS), act, C.c_float(alpha), engine._ptr(t['y']), engine._ptr(t['mean']),
+                                 engine._ptr(t['invstd']), engine._ptr(t['moving_mean']), engine._ptr(t['moving_var']), C.c_float(tc.MOMENTUM),
+                                 engine._ptr(t['res']), _st()) == 0, L.yk_last_error()
+    torch.cuda.synchronize()
+    _guards_intact(bufs, which)
+    _fused_check({k: t[k] for k in ('z',) + _BN_FWD_OUTS}, z_ref, ref, 1e-4)
+
+
+@pytest.mark.parametrize('which', [None, 'z', 'gamma', 'beta', 'y', 'mean', 'invstd', 'moving_mean', 'moving_var', 'res'], ids=str)
+def test_batchnorm_forward_with_residual_and_a_misaligned_tensor(which):
+    """yk_bn_train_fwd_res_f32 at M = 30, C = 4: statistics within 1e-5, y within 2e-5 of max|pre|, as _bn_check asks of the forward."""
+    engine, L = _lib()
+    M, Cc, act, alpha = tc.ALIGN_BN_CASE
+    p = tc.bn_problem(tc.ALIGN_BN_CASE)
+    r = np.random.default_rng(M + Cc).normal(size=(M, Cc)).astype(np.float32)
+    ref = tc.bn_ref(p['z'], p['gamma'], p['beta'], None, act, alpha, res=r)
+    t, bufs = _bn_fwd_tensors(which, dict(z=p['z'], gamma=p['gamma'], beta=p['beta'], res=r), M, Cc, False)
+    assert L.yk_bn_train_fwd_res_f32(engine._ptr(t['z']), C.c_longlong(M), Cc, engine._ptr(t['gamma']), engine._ptr(t['beta']), C.c_float(tc.EPS), act,
+                                     C.c_float(alpha), engine._ptr(t['y']), engine._ptr(t['mean']), engine._ptr(t['invstd']),
+                                     engine._ptr(t['moving_mean']), engine._ptr(t['moving_var']), C.c_float(tc.MOMENTUM), engine._ptr(t['res']),
+                                     _st()) == 0, L.yk_last_error()
+    torch.cuda.synchronize()
+    _guards_intact(bufs, which)
+    got = {k: t[k].cpu().numpy().astype(np.float64) for k in _BN_FWD_OUTS}
+    for k in ('mean', 'invstd', 'moving_mean', 'moving_var'):
+        _close(got[k], ref[k], 1e-5)
+    e_y, b_y = np.abs(got['y'] - ref['y']).max(), 2e-5 * np.abs(ref['pre']).max()
+    print('y err / bound', e_y / b_y)
+    assert e_y <= b_y, (e_y, b_y)
+
+
+@pytest.mark.parametrize('which', [None, 'z', 'dy', 'gamma', 'beta', 'mean', 'invstd', 'dz', 'dgamma', 'dbeta'], ids=str)
+def test_batchnorm_backward_with_a_misaligned_tensor(which):
+    """yk_bn_train_bwd_f32 at M = 30, C = 4 (aligned: bn_bwd_cols_kernel<3>; any tensor misaligned: the scalar reduction and apply pass) on
+    the statistics an aligned yk_bn_train_fwd_f32 saved: the bounds of _bn_check."""
+    engine, L = _lib()
+    case = tc.ALIGN_BN_CASE
+    M, Cc, act, alpha = case
+    p = tc.bn_problem(case)
+    fwd = _bn_fwd_bwd(engine, L, _cu(p['z']), _cu(p['gamma']), _cu(p['beta']), _cu(p['dy']), M, Cc, act, alpha)
+    ins = dict(z=p['z'], dy=p['dy'], gamma=p['gamma'], beta=p['beta'], mean=fwd['mean'].cpu().numpy(), invstd=fwd['invstd'].cpu().numpy())
+    t, bufs = _placed(which, ins, dict(dz=(M, Cc), dgamma=(Cc,), dbeta=(Cc,)))
+    assert L.yk_bn_train_bwd_f32(engine._ptr(t['z']), engine._ptr(t['dy']), C.c_longlong(M), Cc, engine._ptr(t['gamma']), engine._ptr(t['beta']),
+                                 engine._ptr(t['mean']), engine._ptr(t['invstd']), act, C.c_float(alpha), engine._ptr(t['dz']), engine._ptr(t['dgamma']),
+                                 engine._ptr(t['dbeta']), _st()) == 0, L.yk_last_error()
+    torch.cuda.synchronize()
+    _guards_intact(bufs, which)
+    got = {k: v.cpu().numpy().astype(np.float64) for k, v in fwd.items()}
+    got.update({k: t[k].cpu().numpy().astype(np.float64) for k in ('dz', 'dgamma', 'dbeta')})
+    _bn_check(case, got, p['ref'], p['amb'], p['slack_dbeta'], p['slack_dgamma'], p['dz_widen'])
+
+
+def test_depthwise_entry_points_refuse_a_null_tensor_and_an_empty_batch():
+    """yk_dw3x3_fwd_f32, yk_dw3x3_bwd_data_f32, yk_dw3x3_bwd_weight_f32 and yk_dw3x3_bn_fwd_f32: a NULL tensor or B = 0 is YK_ERR_ARG with a
+    message that names the entry point, from the host check at the top of each: nothing is launched."""
+    engine, L = _lib()
+    geom, _ = tc.dw_geom(tc.ALIGN_DW_CASES[0])
+    B, Hi, Wi, Cc, Ho, Wo = geom[:6]
+    M = B * Ho * Wo
+    x, y, w = torch.zeros(B, Hi, Wi, Cc, device='cuda'), torch.zeros(B, Ho, Wo, Cc, device='cuda'), torch.zeros(9, Cc, device='cuda')
+    v = [torch.ones(Cc, device='cuda') for _ in range(6)]
+    z, r = torch.zeros(M, Cc, device='cuda'), torch.zeros(M, Cc, device='cuda')
+    g = lambda b: [C.c_int(b)] + [C.c_int(k) for k in geom[1:]]
+    bn = lambda zz: [engine._ptr(zz) if zz is not None else None, engine._ptr(v[0]), engine._ptr(v[1]), C.c_float(tc.EPS), ns.ACT_RELU, C.c_float(0.0),
+                     engine._ptr(y), engine._ptr(v[2]), engine._ptr(v[3]), engine._ptr(v[4]), engine._ptr(v[5]), C.c_float(tc.MOMENTUM), engine._ptr(r)]
+    calls = {
+        b'yk_dw3x3_fwd_f32': (lambda: L.yk_dw3x3_fwd_f32(engine._ptr(x), engine._ptr(w), *g(B), None, _st()),
+                              lambda: L.yk_dw3x3_fwd_f32(engine._ptr(x), engine._ptr(w), *g(0), engine._ptr(y), _st())),
+        b'yk_dw3x3_bwd_data_f32': (lambda: L.yk_dw3x3_bwd_data_f32(None, engine._ptr(w), *g(B), engine._ptr(x), _st()),
+                                   lambda: L.yk_dw3x3_bwd_data_f32(engine._ptr(y), engine._ptr(w), *g(0), engine._ptr(x), _st())),
+        b'yk_dw3x3_bwd_weight_f32': (lambda: L.yk_dw3x3_bwd_weight_f32(engine._ptr(x), None, *g(B), engine._ptr(w), _st()),
+                                     lambda: L.yk_dw3x3_bwd_weight_f32(engine._ptr(x), engine._ptr(y), *g(0), engine._ptr(w), _st())),
+        b'yk_dw3x3_bn_fwd_f32': (lambda: L.yk_dw3x3_bn_fwd_f32(engine._ptr(x), engine._ptr(w), *g(B), *bn(None), _st()),
+                                 lambda: L.yk_dw3x3_bn_fwd_f32(engine._ptr(x), engine._ptr(w), *g(0), *bn(z), _st())),
+    }
+    for name, (null_tensor, empty_batch) in calls.items():
+        for call in (null_tensor, empty_batch):
+            assert call() == YK_ERR_ARG, name
+            assert name in L.yk_last_error(), (name, L.yk_last_error())
+    torch.cuda.synchronize()

@@ -185,6 +185,10 @@ BN_SEEDS = {(511, 12): 1, (900, 17): 3}
 # the fused forwards: (M, N, K, residual) for yk_gemm_bn_fwd_f32 - bn_fwd_cols_kernel<3> at its row edges and the first M that misses it
 GEMM_BN_CASES = [(512, 8, 16, False), (513, 12, 20, True), (1536, 12, 36, True), (1537, 12, 36, False)]
 DW_BN_CASES = [DW_CASES[2], DW_CASES[4]]
+# The 16-byte rule of the host wrappers (vec4_ok in yk_train.hip): C = 4, one image of 5 x 6, stride 1 and stride 2 (asymmetric "same" padding
+# along the width); called with every tensor on a 16-byte boundary and once per tensor 4 bytes past one.  BatchNorm: the 30 rows of the first.
+ALIGN_DW_CASES = [(1, 5, 6, 4, 1, 1, 1), (1, 5, 6, 4, 2, 1, 0)]
+ALIGN_BN_CASE = (30, 4) + ACTS[1]
 
 
 def bn_inputs(M, C, seed):
