@@ -10,8 +10,10 @@ from k210_yolo_framework_amd import draw
 
 pytestmark = pytest.mark.gpu
 DST = (224, 320)
-# the sizes the kernel can go wrong at: single pixels and lines, one less / equal / one more than the network size (equal = identity),
-# both orientations of a VOC picture, a sliver, and a picture larger than the network size in both dimensions
+# sizes at which the ragged launch could part from yk_letterbox_u8: single pixels and lines, one less / equal / one more than the network
+# size (equal = identity), both orientations of a VOC picture, a sliver, and a picture larger than the network size in both dimensions.
+# These comparisons are against yk_letterbox_u8, a kernel with the same letterbox_px: they hold the table, the offsets and the indexing, not
+# the arithmetic.  The independent check of the arithmetic at such sizes is tests/test_gpu_letterbox_edges.py (table: tests/letterbox_cases.py).
 SIZES = [(1, 1), (1, 37), (37, 1), (223, 319), (224, 320), (225, 321), (500, 375), (375, 500), (640, 7), (300, 400)]
 
 
