@@ -1031,12 +1031,12 @@ int x_launch_fin(int bn, int ns, const xf_args &f, hipStream_t st) {
     return YK_ERR_ARG;
 }
 
-template <int TM, int TN, int SG, bool F32IN = false>
+template <int TM, int TN, int SG, bool F32IN = false, int NW = 4>
 int x_launch_b2(const xb_args &g, int batch, unsigned lds, hipStream_t st) {
     if constexpr (SG > 0 && !F32IN)
         if (g.in_f32) return x_launch_b2<TM, TN, SG, true>(g, batch, lds, st);
     dim3 grid((unsigned)(batch * g.tiles_x * g.tiles_y), (unsigned)((g.N + 64 * TN - 1) / (64 * TN)));
-    yk_launch_lds(xb_kernel<TM, TN, SG, F32IN>, grid, dim3(256), lds, st, g);
+    yk_launch_lds(xb_kernel<TM, TN, SG, F32IN, NW>, grid, dim3(NW * 64), lds, st, g);
     return YK_OK;
 }
 template <int TM, int TN>
@@ -1049,6 +1049,13 @@ int x_launch_b(const xb_args &g, int batch, unsigned lds, hipStream_t st) {
     if (g.stem) {
         yk_set_error("f16x2: stem fusion needs an N tile of 64 and 16, 24 or 32 stem filters");
         return YK_ERR_UNSUPPORTED;
+    }
+    if constexpr (TN == 6) {                                       // the 384-wide tile: same tile, grid and LDS on eight waves of <= 128 registers
+        if (g.waves == 8) return x_launch_b2<TM, TN, 0, false, 8>(g, batch, lds, st);
+    }
+    if (g.waves != 4) {
+        yk_set_error("f16x2: no fused block kernel <%d,%d> on %d waves", TM, TN, g.waves);
+        return YK_ERR_ARG;
     }
     return x_launch_b2<TM, TN, 0>(g, batch, lds, st);
 }
@@ -1147,6 +1154,9 @@ bool xb_geometry(xb_args &g, int *tm_out, int *tn_out, unsigned *lds_out, int ma
     g.fd_pw = yk_make_fastdiv((uint32_t)g.PW);
     g.fd_nk = yk_make_fastdiv((uint32_t)std::max(1, g.nk));
     g.GL = 4;
+    // the long channel walk on the 384-wide tile runs on eight waves (yk_xblock.h: NW); whether its input is stored as fp32 planes or as
+    // (hi | lo) does not matter, the half items read either.  Developer builds can force four for A/B runs
+    g.waves = (wide && *tn_out == 6 && !(yk_dev_env("YK_XB_WAVES") && atoi(yk_dev_env("YK_XB_WAVES")) == 4)) ? 8 : 4;
     return true;
 }
 

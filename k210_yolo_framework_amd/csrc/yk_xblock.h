@@ -2,7 +2,8 @@
 // yk_exact.hip).  MobileNet block: keras_mobilenet.py:359-436, keras_mobilenet_v2.py:452-481.
 //
 // A workgroup (4 waves) owns a TH x TW patch of output pixels of ONE image (BM = 16*TM >= TH*TW GEMM rows) and BN = 64*TN output
-// channels (wave w: channels [w*16*TN, (w+1)*16*TN) of all BM pixels).  The channel axis is walked in steps of 32 (four groups of 8):
+// channels (wave w: channels [w*16*TN, (w+1)*16*TN) of all BM pixels; the 384-wide tile runs on 8 waves with half of that each, see
+// xb_kernel's NW).  The channel axis is walked in steps of 32 (four groups of 8):
 //
 //   DMA(k)    one burst of `buffer_load ... lds`: the input patch of the step's four channel groups ((TH-1)s+3 x (TW-1)s+3 positions
 //             x 4 groups, hi and lo halves in separate regions; pixels outside the image and groups past the tensor's last one get an
@@ -70,6 +71,7 @@ struct xb_args {
     // fused stem: the patch and the A tile hold the GL channel groups that EXIST (24 stem filters: three groups of 8, 48 bytes per position /
     // A row per plane instead of 64): 39 KB instead of 49 - a FOURTH workgroup per CU - and the depthwise pass has no dead items
     int GL;
+    int waves;                         // 4, or 8 on the 384-wide tile of a long channel walk (xb_geometry): xb_kernel's NW
     int dbg;
     long long *stamps;                 // developer builds: per-workgroup phase timestamps [wg][16] (wall_clock64), or null
 };
@@ -183,11 +185,18 @@ __device__ __forceinline__ void xb_stem_patch(const xb_args &a, const void *winp
 
 // SG: 0 = the input is a stored tensor; 2, 3, 4 = fused stem with SG channel groups.  F32IN: the fused stem reads fp32 frames (else u8) - a
 // compile-time choice: with both window loaders in one kernel the stem block kept ~190 scalar registers in vector-register lanes
-template <int TM, int TN, int SG, bool F32IN = false>
-__global__ void __launch_bounds__(256, (TM * TN > 8 ? 2 : 4)) xb_kernel(const xb_args a) {   // 2 (3) workgroups per CU: <= 256 (168) registers; the fused-stem block stays under 128 by itself (4 per CU)
+// NW: waves per workgroup.  4 everywhere but on the 384-wide tile of a long channel walk (xb_geometry: `wide`), which runs the SAME tile,
+// grid, LDS image and arithmetic on 8 waves of <= 128 registers: wave w owns 16 * TNW = 48 output channels instead of 96, the depthwise
+// items are split into their two channel halves (512 half items), every deposit / copy-out loop strides by 512.  Two such workgroups
+// take the registers of a CU's SIMDs that two 4-wave workgroups of <= 256 took; each serial phase of a step sits on twice the waves.
+template <int TM, int TN, int SG, bool F32IN = false, int NW = 4>
+__global__ void __launch_bounds__(NW * 64, (NW == 8 || TM * TN > 8 ? 2 : 4)) xb_kernel(const xb_args a) {   // 2 (3) workgroups per CU: <= 256 (168) registers, <= 128 on 8 waves; the fused-stem block stays under 128 by itself (4 per CU)
     typedef xb_cfg<TM, TN> C;
     constexpr int BM = C::BM, BN = C::BN;
     constexpr bool STEM = SG > 0;
+    constexpr int NT = NW * 64;                                       // threads
+    constexpr int TNW = TN * 4 / NW;                                  // 16-channel slabs per wave
+    static_assert(NW == 4 || (NW == 8 && !STEM && (TN & 1) == 0), "8 waves: stored-tensor blocks with an even number of slabs per 4 waves");
     constexpr int GL = STEM ? SG : 4;                                 // channel groups per patch position and per A row
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int G = a.in.G, s = a.stride;
@@ -220,11 +229,11 @@ __global__ void __launch_bounds__(256, (TM * TN > 8 ? 2 : 4)) xb_kernel(const xb
     // BatchNorm scale / bias of this lane's output channels: requested first, used last (narrow tiles only: 12 float4 pairs of a
     // 384-wide tile would cost the second workgroup per CU its registers)
     constexpr bool EARLY_SB = TN <= 1;
-    float4 sc[TN], bs[TN];
+    float4 sc[TNW], bs[TNW];
     if constexpr (EARLY_SB) {
 #pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            const int n = n0 + (wid * TN + j) * 16 + nl4;
+        for (int j = 0; j < TNW; ++j) {
+            const int n = n0 + (wid * TNW + j) * 16 + nl4;
             sc[j] = *reinterpret_cast<const float4 *>(a.scale + n);
             bs[j] = *reinterpret_cast<const float4 *>(a.bias + n);
         }
@@ -234,13 +243,13 @@ __global__ void __launch_bounds__(256, (TM * TN > 8 ? 2 : 4)) xb_kernel(const xb
     const __amdgpu_buffer_rsrc_t rsp = __builtin_amdgcn_make_buffer_rsrc((void *)a.par, 0, (uint32_t)(11 * G * 32), 0x00020000);
     const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc((void *)a.w, 0, a.w_bytes, 0x00020000);
     // this lane's patch positions are the same for every step: precompute the source offsets of its (up to PQ) DMA slots
-    constexpr int PQ = 6;                                         // patch slots per lane: n16p <= PQ * 256
+    constexpr int PQ = 6 * 4 / NW;                                // patch slots per lane: n16p <= PQ * NT
     uint32_t poff[PQ];
 #pragma unroll
     for (int i = 0; i < PQ; ++i) {
         poff[i] = X_OOB;
-        if (!STEM && i * 256 < a.n16p) {                              // (uniform: a small patch skips the slots it does not have)
-            const uint32_t q = (uint32_t)(i * 256 + tid);
+        if (!STEM && i * NT < a.n16p) {                               // (uniform: a small patch skips the slots it does not have)
+            const uint32_t q = (uint32_t)(i * NT + tid);
             const uint32_t pos = q >> 2, g4 = q & 3;
             const uint32_t r = x_div(pos, a.fd_pw), c = pos - r * a.PW;
             const int iy = iy0 + (int)r, ix = ix0 + (int)c;
@@ -265,10 +274,10 @@ __global__ void __launch_bounds__(256, (TM * TN > 8 ? 2 : 4)) xb_kernel(const xb
         const uint32_t koff = gok ? (uint32_t)ks * 128u : X_OOB;
 #pragma unroll
         for (int i = 0; i < PQ; ++i)
-            if (!STEM && i * 256 + wid * 64 < a.n16p) {                    // wave-uniform: n16p is a multiple of 64, a wave deposits 64 slots
+            if (!STEM && i * NT + wid * 64 < a.n16p) {                     // wave-uniform: n16p is a multiple of 64, a wave deposits 64 slots
                 const uint32_t oh = poff[i] + koff, ol = oh + 16u;
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsx, (lds_ptr_t)(HI + (i * 256 + wid * 64) * 16), 16, oh, 0, 0, 0);
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsx, (lds_ptr_t)(LO + (i * 256 + wid * 64) * 16), 16, ol, 0, 0, 0);
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsx, (lds_ptr_t)(HI + (i * NT + wid * 64) * 16), 16, oh, 0, 0, 0);
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsx, (lds_ptr_t)(LO + (i * NT + wid * 64) * 16), 16, ol, 0, 0, 0);
             }
         if (wid < 2) {                                            // 11 rows x 8 pieces of 16 B = 88 slots
             const int idx = wid * 64 + lane, t = idx >> 3, pc = idx & 7;
@@ -380,12 +389,12 @@ __global__ void __launch_bounds__(256, (TM * TN > 8 ? 2 : 4)) xb_kernel(const xb
         }
     }
     XB_STAMP(2)
-    floatx4 acc[TM][TN];
+    floatx4 acc[TM][TNW];
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
-        for (int j = 0; j < TN; ++j) acc[i][j] = floatx4{0.f, 0.f, 0.f, 0.f};
-    const bool wave_live = n0 + wid * TN * 16 < a.N;                  // wave-uniform
+        for (int j = 0; j < TNW; ++j) acc[i][j] = floatx4{0.f, 0.f, 0.f, 0.f};
+    const bool wave_live = n0 + wid * TNW * 16 < a.N;                 // wave-uniform
     // fragment offsets: rows of 64 bytes with the 16-byte pieces swizzled (weight tile; A tile of a stored-tensor block), rows of GL * 16
     // bytes in a fused-stem block (48-byte rows of a 24-channel stem touch every bank once per 16 lanes without a swizzle)
     const int foff = fr * 64 + ((fq ^ ((fr >> 1) & 3)) * 16);
@@ -402,11 +411,11 @@ __global__ void __launch_bounds__(256, (TM * TN > 8 ? 2 : 4)) xb_kernel(const xb
         // would be written once and read once by one wave: the fragments go from global memory straight into that wave's registers
         // (host order = fragment order: one coalesced 1 KB load per 16-channel block and half), requested here, used after the depthwise
         // pass.  No LDS stage for them: 6 - 24 KB less per workgroup, which is what lets a fourth workgroup onto a CU.
-        half8 wh[TN], wl[TN];
+        half8 wh[TNW], wl[TNW];
         if (wave_live && !X_DBG(a, 16)) {
-            const uint32_t ws = (uint32_t)(n0 >> 4) * 2048u + (uint32_t)kstep(ks) * wstep + (uint32_t)(wid * TN) * 2048u + (uint32_t)foff;
+            const uint32_t ws = (uint32_t)(n0 >> 4) * 2048u + (uint32_t)kstep(ks) * wstep + (uint32_t)(wid * TNW) * 2048u + (uint32_t)foff;
 #pragma unroll
-            for (int j = 0; j < TN; ++j) {
+            for (int j = 0; j < TNW; ++j) {
                 wh[j] = __builtin_bit_cast(half8, __builtin_amdgcn_raw_buffer_load_b128(rsw, ws + (uint32_t)j * 2048u, 0, 0));
                 wl[j] = __builtin_bit_cast(half8, __builtin_amdgcn_raw_buffer_load_b128(rsw, ws + (uint32_t)j * 2048u + 1024u, 0, 0));
             }
@@ -423,7 +432,7 @@ __global__ void __launch_bounds__(256, (TM * TN > 8 ? 2 : 4)) xb_kernel(const xb
         if (!STEM && XB_PREPASS && !a.src_f32) {
             // stride 1: a patch element feeds nine taps.  (hi, lo) -> fp32 once, in place (channels 0-3 over the hi plane's 16 bytes,
             // 4-7 over the lo plane's), instead of in every tap: 8 conversions per element here for 72 per item there
-            for (int e = tid; e < a.n16p; e += 256) {
+            for (int e = tid; e < a.n16p; e += NT) {
                 const u32x4 h = *reinterpret_cast<const u32x4 *>(HI + e * 16), l = *reinterpret_cast<const u32x4 *>(LO + e * 16);
                 u32x4 x0, x1;
                 x0[0] = __float_as_uint(x_mix_sum_lo(h[0], l[0])); x0[1] = __float_as_uint(x_mix_sum_hi(h[0], l[0]));
@@ -438,7 +447,7 @@ __global__ void __launch_bounds__(256, (TM * TN > 8 ? 2 : 4)) xb_kernel(const xb
             asm volatile("" ::: "memory");
         }
         // ---- depthwise: item = (pixel p, group q of this step)
-        if (!X_DBG(a, 2))
+        if (NW == 4 && !X_DBG(a, 2))
             for (int it = tid; it < BM * GL; it += 256) {
                 int p, q;
                 if constexpr (GL != 4) {
@@ -501,6 +510,53 @@ __global__ void __launch_bounds__(256, (TM * TN > 8 ? 2 : 4)) xb_kernel(const xb
                 *reinterpret_cast<half8 *>(dst) = hi;
                 *reinterpret_cast<half8 *>(dst + GL * 256) = lo;
             }
+        // ---- 8 waves: item = (pixel p, group q, channel half hf of the group): the same taps, FMA order, BN, activation and split per
+        // channel as above on half the channels - one 16-byte patch read (fp32 planes; two 8-byte reads of a (hi | lo) patch) and one
+        // 16-byte parameter read per tap, the 8-byte halves of hi and lo to the same A-tile addresses.  hf is wave-uniform (BM * GL is a
+        // multiple of 64): a wave's reads cover the same 64-byte runs of one plane as a 4-wave item's
+        if constexpr (NW == 8) {
+            if (!X_DBG(a, 2))
+                for (int it = tid; it < BM * GL * 2; it += NT) {
+                    const int hf = it >= BM * GL ? 1 : 0, ih = it - hf * (BM * GL);
+                    const int p = ih >> 2, q = ih & 3;
+                    const int py = (int)x_div((uint32_t)p, a.fd_tw), px = p - py * a.TW;
+                    const bool live = py < a.TH && oy0 + py < a.Ho && ox0 + px < a.Wo;
+                    half4 hi = {0, 0, 0, 0}, lo = hi;
+                    if (live) {
+                        const int base = ((py * s) * a.PW + px * s) * GL + q;
+                        const unsigned char *PW_ = PARB_ + (q * 8 + hf * 4) * 4;
+                        float2v d2[2] = {{0.f, 0.f}, {0.f, 0.f}};
+#pragma unroll
+                        for (int t = 0; t < 9; ++t) {
+                            const int at = (base + ((t / 3) * a.PW + (t % 3)) * GL) * 16;
+                            const u32x4 w0 = *reinterpret_cast<const u32x4 *>(PW_ + t * 128);
+                            const float2v w2[2] = {{__uint_as_float(w0[0]), __uint_as_float(w0[1])}, {__uint_as_float(w0[2]), __uint_as_float(w0[3])}};
+                            if (f32patch) {                           // the fp32 planes: channels 0-3 in the first, 4-7 in the second
+                                const u32x4 x = *reinterpret_cast<const u32x4 *>((hf ? LO : HI) + at);
+                                d2[0] = __builtin_elementwise_fma(float2v{__uint_as_float(x[0]), __uint_as_float(x[1])}, w2[0], d2[0]);
+                                d2[1] = __builtin_elementwise_fma(float2v{__uint_as_float(x[2]), __uint_as_float(x[3])}, w2[1], d2[1]);
+                            } else {
+                                const u32x2 h = *reinterpret_cast<const u32x2 *>(HI + at + hf * 8), l = *reinterpret_cast<const u32x2 *>(LO + at + hf * 8);
+#pragma unroll
+                                for (int j = 0; j < 2; ++j) {
+                                    const float2v x2 = {x_mix_sum_lo(h[j], l[j]), x_mix_sum_hi(h[j], l[j])};
+                                    d2[j] = __builtin_elementwise_fma(x2, w2[j], d2[j]);
+                                }
+                            }
+                        }
+                        const float d[4] = {d2[0].x, d2[0].y, d2[1].x, d2[1].y};
+                        const u32x4 s0_ = *reinterpret_cast<const u32x4 *>(PW_ + 9 * 128), b0_ = *reinterpret_cast<const u32x4 *>(PW_ + 10 * 128);
+                        float vd[4];
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) vd[j] = x_actf(__builtin_fmaf(d[j] * up, __uint_as_float(s0_[j]), __uint_as_float(b0_[j])), a.dw_slope, a.dw_cap) * dmid;
+                        x_split4(vd, hi, lo);
+                    }
+                    const int r = p & 15;
+                    unsigned char *dst = A + (p >> 4) * (GL * 512) + r * (GL * 16) + ((q ^ ((r >> 1) & 3)) * 16) + hf * 8;
+                    *reinterpret_cast<half4 *>(dst) = hi;
+                    *reinterpret_cast<half4 *>(dst + GL * 256) = lo;
+                }
+        }
         if (ks == 0) { XB_STAMP(4) }
         if (ks == 1) { XB_STAMP(14) }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");            // (the weight fragments - and, with two stages, step ks+1 - stay in flight)
@@ -521,16 +577,16 @@ __global__ void __launch_bounds__(256, (TM * TN > 8 ? 2 : 4)) xb_kernel(const xb
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll
-                for (int j = 0; j < TN; ++j)                        // (a fused-stem block has ONE step: its first product starts from the zero constant)
+                for (int j = 0; j < TNW; ++j)                       // (a fused-stem block has ONE step: its first product starts from the zero constant)
                     acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl[j], xh[i], STEM ? floatx4{0.f, 0.f, 0.f, 0.f} : acc[i][j], 0, 0, 0);
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll
-                for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[j], xl[i], acc[i][j], 0, 0, 0);
+                for (int j = 0; j < TNW; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[j], xl[i], acc[i][j], 0, 0, 0);
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll
-                for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[j], xh[i], acc[i][j], 0, 0, 0);
+                for (int j = 0; j < TNW; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[j], xh[i], acc[i][j], 0, 0, 0);
         }
     }
     XB_STAMP(6)
@@ -546,15 +602,15 @@ __global__ void __launch_bounds__(256, (TM * TN > 8 ? 2 : 4)) xb_kernel(const xb
     constexpr int VPR = BN / 4, IPP = C::IPP;
     if constexpr (!EARLY_SB) {
 #pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            const int n = n0 + (wid * TN + j) * 16 + nl4;
+        for (int j = 0; j < TNW; ++j) {
+            const int n = n0 + (wid * TNW + j) * 16 + nl4;
             sc[j] = *reinterpret_cast<const float4 *>(a.scale + n);
             bs[j] = *reinterpret_cast<const float4 *>(a.bias + n);
         }
     }
-    float4 scu[TN];                                                   // BN scale with the middle exponent folded in (a power of two: exact)
+    float4 scu[TNW];                                                  // BN scale with the middle exponent folded in (a power of two: exact)
 #pragma unroll
-    for (int j = 0; j < TN; ++j) scu[j] = float4{sc[j].x * umid, sc[j].y * umid, sc[j].z * umid, sc[j].w * umid};
+    for (int j = 0; j < TNW; ++j) scu[j] = float4{sc[j].x * umid, sc[j].y * umid, sc[j].z * umid, sc[j].w * umid};
     if (a.dst_f32 && !a.res.p) {
         // fp32 output (its only reader is another fused block's depthwise conv): a lane's four channels are 16 contiguous bytes of the
         // tensor and the four lanes of a pixel cover 64 - stored straight from the registers.  (The (hi | lo) layout leaves 8-byte
@@ -572,8 +628,8 @@ __global__ void __launch_bounds__(256, (TM * TN > 8 ? 2 : 4)) xb_kernel(const xb
                 const bool mok = py < a.TH && oy < a.Ho && ox < a.Wo;
                 const uint32_t po = (uint32_t)((oy * a.Wo + ox) * a.outG) * 32u;
 #pragma unroll
-                for (int j = 0; j < TN; ++j) {
-                    const int n = n0 + (wid * TN + j) * 16 + nl4;
+                for (int j = 0; j < TNW; ++j) {
+                    const int n = n0 + (wid * TNW + j) * 16 + nl4;
                     float v[4];
                     v[0] = x_actf(__builtin_fmaf(acc[i][j][0], scu[j].x, bs[j].x), a.slope, a.cap);
                     v[1] = x_actf(__builtin_fmaf(acc[i][j][1], scu[j].y, bs[j].y), a.slope, a.cap);
@@ -613,8 +669,8 @@ __global__ void __launch_bounds__(256, (TM * TN > 8 ? 2 : 4)) xb_kernel(const xb
             // the row's pixel index (or -1) rides in the 16 pad bytes of its staging row: the copy-out below needs no division per vector
             if (wid == 0 && fq == 0) *reinterpret_cast<int *>(Cs + (p - i0 * 16) * C::CPITCH + BN * 4) = mok ? m : -1;
 #pragma unroll
-            for (int j = 0; j < TN; ++j) {
-                const int nl = (wid * TN + j) * 16 + nl4, n = n0 + nl;
+            for (int j = 0; j < TNW; ++j) {
+                const int nl = (wid * TNW + j) * 16 + nl4, n = n0 + nl;
                 float v[4];
                 v[0] = x_actf(__builtin_fmaf(acc[i][j][0], scu[j].x, bs[j].x), a.slope, a.cap);
                 v[1] = x_actf(__builtin_fmaf(acc[i][j][1], scu[j].y, bs[j].y), a.slope, a.cap);
@@ -651,7 +707,7 @@ __global__ void __launch_bounds__(256, (TM * TN > 8 ? 2 : 4)) xb_kernel(const xb
         __syncthreads();
         if (last && tid == 0 && smax[0]) x_amax_global(a.amax_out + (size_t)b * XS, smax[0]);
         const int rows = (TM - i0 < IPP ? TM - i0 : IPP) * 16;
-        for (int v = tid; v < rows * VPR; v += 256) {
+        for (int v = tid; v < rows * VPR; v += NT) {
             const int pr = v / VPR, cv = v - pr * VPR;
             const int m = *reinterpret_cast<const int *>(Cs + pr * C::CPITCH + BN * 4), g = (n0 >> 3) + (cv >> 1);
             const uint32_t so = (m >= 0 && g < a.outG) ? (uint32_t)((m * a.outG + g) * 32 + (cv & 1) * 16) : X_OOB;   // (out of range: dropped by the descriptor)
