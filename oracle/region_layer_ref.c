@@ -148,7 +148,13 @@ void rlref_nms(const float *boxes, float *probs, int nb, int C, float nms_value)
     free(r);
 }
 
-static uint32_t to_u32(float v) { return (uint32_t)(int64_t)v; } /* defined form of :397-400's UB cast */
+/* defined form of :397-400's UB cast, as the reference's x86-64 build computes it (cvttss2si to 64 bits, then truncation): NaN and
+ * values outside the int64 range give the "integer indefinite" 0x8000000000000000, i.e. 0 after truncation.  The (int64_t) cast alone
+ * is still undefined for those.  Pinned on saturating boxes by tests/golden/region_live_golden.npz (the reference's own draw calls). */
+static uint32_t to_u32(float v) {
+    if (!(v >= -9223372036854775808.0f && v < 9223372036854775808.0f)) return 0u;
+    return (uint32_t)(int64_t)v;
+}
 
 /* C5: region_layer_draw_boxes :385-404 (+ max_index :285-296). dets: rows of 6 uint32
  * (x1,y1,x2,y2,class,prob-bits).  Returns the number of callbacks the reference would make. */

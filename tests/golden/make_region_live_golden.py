@@ -1,5 +1,6 @@
 """Generate tests/golden/region_live_golden.npz by RUNNING THE REFERENCE's region_layer.c on the cases of
-tests/test_oracle_region.py::test_live_reference_bit_exact.
+tests/test_oracle_region.py::test_live_reference_bit_exact, and on the saturating boxes of tests/region_cases.py (infinite widths, zero heights:
+the reference's own draw casts see +-inf) for ::test_live_reference_saturating_boxes.
 
 Requires oracle/_ref/libregion_ref.so (oracle/build_ref.sh, needs the reference tree).
 The fixture holds only data: per case and input scale, the seeded input, the anchors and the reference's outputs
@@ -13,6 +14,7 @@ import numpy as np
 ROOT = Path(__file__).resolve().parents[2]
 sys.path.insert(0, str(ROOT))
 import oracle  # noqa: E402
+from tests import region_cases  # noqa: E402
 
 # (W, H, A, C, thr, nms, net) - the parameters of test_live_reference_bit_exact
 CASES = [
@@ -45,6 +47,13 @@ def main():
             out[k + '/probs'] = p
             out[k + '/dets'] = d
             print(k, 'dets', len(d))
+    c = region_cases.saturating()
+    B, W, H, A, C = region_cases.dims(c)
+    assert B == 1 and c.image_wh == (320, 224)      # the reference hard-codes the image size
+    o, b, p, d = oracle.ref_region_run(c.x[0], c.anchor, W, H, A, C, c.thr, c.nms, c.net_wh)
+    for name, a in (('input', c.x[0]), ('anchor', c.anchor), ('output', o), ('boxes', b), ('probs', p), ('dets', d)):
+        out[f'{c.name}/{name}'] = a
+    print(c.name, 'dets', len(d), 'infinite box fields', int(np.isinf(b).sum()))
     np.savez_compressed(Path(__file__).with_name('region_live_golden.npz'), **out)
 
 

@@ -95,3 +95,6 @@ def test_nms_overflow_path_many_candidates(hip):
     p = probs[0].cpu().numpy()
     assert (pr[:, 0] != 0).sum() > 100
     assert np.array_equal(p[:, 0] != 0, pr[:, 0] != 0)
+    # and their values: a kept box is parked as -p while the loop runs and must come back as p, bit for bit
+    np.testing.assert_array_equal(p.view(np.uint32), pr.view(np.uint32))
+    np.testing.assert_array_equal(boxes[0].cpu().numpy().view(np.uint32), bx.view(np.uint32))

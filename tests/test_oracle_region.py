@@ -56,6 +56,26 @@ def test_live_reference_bit_exact(W, H, A, C, thr, nms, net, golden_dir):
         np.testing.assert_array_equal(oracle.region_draw(boxes, probs, thr), rd)
 
 
+def test_live_reference_saturating_boxes(golden_dir):
+    """Infinite widths and zero heights (tests/region_cases.py saturating()): the stored outputs are the reference's own, draw casts of +-inf
+    included, and pin the oracle's to_u32 on them.  (The key format above does not fit: the input is built, not drawn at a scale.)"""
+    from tests import region_cases
+    g = np.load(golden_dir / 'region_live_golden.npz')
+    c = region_cases.saturating()
+    _, W, H, A, C = region_cases.dims(c)
+    x, anchor = g['saturating/input'], g['saturating/anchor']
+    np.testing.assert_array_equal(x, c.x[0])                  # the fixture was made from the builder as it is now
+    np.testing.assert_array_equal(anchor, c.anchor)
+    stored = tuple(g[f'saturating/{k}'] for k in ('output', 'boxes', 'probs', 'dets'))
+    assert np.isinf(stored[1]).sum() == 7 and not np.isnan(stored[1]).any()
+    if oracle.have_ref():
+        for live, want in zip(oracle.ref_region_run(x, anchor, W, H, A, C, c.thr, c.nms, c.net_wh), stored):
+            np.testing.assert_array_equal(live, want)
+    out, boxes, probs = oracle.region_run(x, anchor, W, H, A, C, c.thr, c.nms, c.net_wh)
+    for got, want in zip((out, boxes, probs, oracle.region_draw(boxes, probs, c.thr)), stored):
+        np.testing.assert_array_equal(got.view(np.uint32), want.view(np.uint32))
+
+
 def test_negative_coordinate_cast_is_defined():
     # region_layer.c:397-400 converts possibly-negative floats to uint32 (UB); the restatement and the
     # new ABI define it as (uint32_t)(int64_t)x.  A box hanging over the left/top edge exercises it.
