@@ -400,6 +400,40 @@ __global__ void __launch_bounds__(NW * 64, (NW == 8 || TM * TN > 8 ? 2 : 4)) xb_
     const int foff = fr * 64 + ((fq ^ ((fr >> 1) & 3)) * 16);
     // (a k group the stem does not have: the lane re-reads group 0 - finite values against weight rows that are zero)
     const int afoff = fr * (GL * 16) + (GL == 4 ? (fq ^ ((fr >> 1) & 3)) : (fq < GL ? fq : 0)) * 16;
+    // ---- this thread's depthwise items.  item = (pixel p, group q of the step[, channel half hf of the group on 8 waves]); which
+    // pixel, whether it is alive, where its taps start in the patch and where it goes in the A tile depend on tid, the tile and the
+    // launch - never on the step (the rotation `rot` only picks the channel slice a step works on): once per workgroup, as byte offsets
+    //   dsrc  tap (0, 0) from the start of the patch stage (the plane / half of an 8-wave item folded in); -1: a dead pixel (zeros)
+    //   dpar  the item's channels inside a row of the parameter slice
+    //   ddst  the item in the A tile; -1: the thread has no such item
+    // In the step the nine taps are three row bases (+ rowb) and compile-time column offsets in the LDS reads' offset fields.
+    const bool f32patch = STEM || XB_PREPASS || a.src_f32;
+    constexpr int NIT = NW == 8 ? BM * GL * 2 : BM * GL, NITEM = (NIT + NT - 1) / NT;
+    const int plane = a.n16p * 16, rowb = a.PW * (GL * 16);
+    int dsrc[NITEM], dpar[NITEM], ddst[NITEM];
+#pragma unroll
+    for (int j = 0; j < NITEM; ++j) {
+        const int it = tid + j * NT;
+        int p, q, hf = 0;
+        if constexpr (NW == 8) {
+            hf = it >= BM * GL ? 1 : 0;
+            const int ih = it - hf * (BM * GL);
+            p = ih >> 2;
+            q = ih & 3;
+        } else if constexpr (GL != 4) {
+            p = (int)((uint32_t)it / (uint32_t)GL);
+            q = it - p * GL;
+        } else {
+            p = it >> 2;
+            q = it & 3;
+        }
+        const int py = (int)x_div((uint32_t)p, a.fd_tw), px = p - py * a.TW;
+        const bool live = py < a.TH && oy0 + py < a.Ho && ox0 + px < a.Wo;
+        const int r = p & 15;
+        dsrc[j] = live ? (((py * s) * a.PW + px * s) * GL + q) * 16 + (NW == 8 ? (f32patch ? hf * plane : hf * 8) : 0) : -1;
+        dpar[j] = NW == 8 ? (q * 8 + hf * 4) * 4 : q * 32;
+        ddst[j] = it < NIT ? (p >> 4) * (GL * 512) + r * (GL * 16) + ((q ^ (GL == 4 ? (r >> 1) & 3 : 0)) * 16) + hf * 8 : -1;
+    }
     const int nk = X_DBG(a, 1) ? 0 : a.nk;
     for (int ks = 0; ks < nk; ++ks) {
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // this wave's pieces of patch(ks) have landed
@@ -428,7 +462,6 @@ __global__ void __launch_bounds__(NW * 64, (NW == 8 || TM * TN > 8 ? 2 : 4)) xb_
         // flight (s_waitcnt vmcnt(0): the weight tile requested a moment ago) before it, a dword-typed one does not
         const unsigned char *PARB_ = HI + a.n16p * 32;
         const float up = sf[0], dmid = sf[1];
-        const bool f32patch = STEM || XB_PREPASS || a.src_f32;
         if (!STEM && XB_PREPASS && !a.src_f32) {
             // stride 1: a patch element feeds nine taps.  (hi, lo) -> fp32 once, in place (channels 0-3 over the hi plane's 16 bytes,
             // 4-7 over the lo plane's), instead of in every tap: 8 conversions per element here for 72 per item there
@@ -446,116 +479,121 @@ __global__ void __launch_bounds__(NW * 64, (NW == 8 || TM * TN > 8 ? 2 : 4)) xb_
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
         }
-        // ---- depthwise: item = (pixel p, group q of this step)
-        if (NW == 4 && !X_DBG(a, 2))
-            for (int it = tid; it < BM * GL; it += 256) {
-                int p, q;
-                if constexpr (GL != 4) {
-                    p = (int)((uint32_t)it / (uint32_t)GL);
-                    q = it - p * GL;
-                } else {
-                    p = it >> 2;
-                    q = it & 3;
-                }
-                const int py = (int)x_div((uint32_t)p, a.fd_tw), px = p - py * a.TW;
-                const bool live = py < a.TH && oy0 + py < a.Ho && ox0 + px < a.Wo;
+        // ---- depthwise: item = (pixel p, group q of this step), its geometry from dsrc / dpar / ddst above.  The patch format is chosen
+        // ONCE per item, outside the taps: with the choice inside, every tap was a branch with a full LDS wait in front of it - nine
+        // dependent LDS round trips per item and step; now the reads of several taps are in flight together
+        if (NW == 4 && !X_DBG(a, 2)) {
+#pragma unroll
+            for (int j = 0; j < NITEM; ++j) {
+                if (NIT % NT != 0 && ddst[j] < 0) continue;
                 half8 hi = {0, 0, 0, 0, 0, 0, 0, 0}, lo = hi;
-                if (live) {
-                    const int base = ((py * s) * a.PW + px * s) * GL + q;
+                if (dsrc[j] >= 0) {
+                    const unsigned char *R0 = HI + dsrc[j], *PP = PARB_ + dpar[j];
+                    const unsigned char *const R[3] = {R0, R0 + rowb, R0 + 2 * rowb};
                     // x = hi + lo back in fp32 by one mixed-precision op per channel, then packed fp32 FMAs (two channels per
                     // instruction): 12 VALU ops per tap and channel group instead of 16
                     float2v d2[4] = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}};
+                    auto taps = [&](auto f32c) {
 #pragma unroll
-                    for (int t = 0; t < 9; ++t) {
+                        for (int t = 0; t < 9; ++t) {
 #if defined(YK_KO) && (YK_KO & 2)                                     // pricing build: three patch reads (one per row) instead of nine
-                        const int at = (base + ((t / 3) * a.PW) * GL) * 16;
+                            const unsigned char *at = R[t / 3];
 #else
-                        const int at = (base + ((t / 3) * a.PW + (t % 3)) * GL) * 16;
+                            const unsigned char *at = R[t / 3] + (t % 3) * (GL * 16);
 #endif
-                        const u32x4 h = *reinterpret_cast<const u32x4 *>(HI + at), l = *reinterpret_cast<const u32x4 *>(LO + at);
+                            const u32x4 h = *reinterpret_cast<const u32x4 *>(at), l = *reinterpret_cast<const u32x4 *>(at + plane);
 #if defined(YK_KO) && (YK_KO & 1)                                     // pricing build (wrong results on purpose): no weight reads
-                        const u32x4 w0 = {0x3f000000u, 0x3e800000u, 0x3f000000u, 0x3e800000u}, w1 = w0;
+                            const u32x4 w0 = {0x3f000000u, 0x3e800000u, 0x3f000000u, 0x3e800000u}, w1 = w0;
 #else
-                        const u32x4 w0 = *reinterpret_cast<const u32x4 *>(PARB_ + (t * 32 + q * 8) * 4), w1 = *reinterpret_cast<const u32x4 *>(PARB_ + (t * 32 + q * 8 + 4) * 4);
+                            const u32x4 w0 = *reinterpret_cast<const u32x4 *>(PP + t * 128), w1 = *reinterpret_cast<const u32x4 *>(PP + t * 128 + 16);
 #endif
-                        const float2v w2[4] = {{__uint_as_float(w0[0]), __uint_as_float(w0[1])}, {__uint_as_float(w0[2]), __uint_as_float(w0[3])},
-                                               {__uint_as_float(w1[0]), __uint_as_float(w1[1])}, {__uint_as_float(w1[2]), __uint_as_float(w1[3])}};
-                        if (f32patch) {                               // (h, l) are the fp32 planes: channels 0-3 | 4-7
-                            d2[0] = __builtin_elementwise_fma(float2v{__uint_as_float(h[0]), __uint_as_float(h[1])}, w2[0], d2[0]);
-                            d2[1] = __builtin_elementwise_fma(float2v{__uint_as_float(h[2]), __uint_as_float(h[3])}, w2[1], d2[1]);
-                            d2[2] = __builtin_elementwise_fma(float2v{__uint_as_float(l[0]), __uint_as_float(l[1])}, w2[2], d2[2]);
-                            d2[3] = __builtin_elementwise_fma(float2v{__uint_as_float(l[2]), __uint_as_float(l[3])}, w2[3], d2[3]);
-                        } else {
+                            const float2v w2[4] = {{__uint_as_float(w0[0]), __uint_as_float(w0[1])}, {__uint_as_float(w0[2]), __uint_as_float(w0[3])},
+                                                   {__uint_as_float(w1[0]), __uint_as_float(w1[1])}, {__uint_as_float(w1[2]), __uint_as_float(w1[3])}};
+                            if constexpr (decltype(f32c)::value) {    // (h, l) are the fp32 planes: channels 0-3 | 4-7
+                                d2[0] = __builtin_elementwise_fma(float2v{__uint_as_float(h[0]), __uint_as_float(h[1])}, w2[0], d2[0]);
+                                d2[1] = __builtin_elementwise_fma(float2v{__uint_as_float(h[2]), __uint_as_float(h[3])}, w2[1], d2[1]);
+                                d2[2] = __builtin_elementwise_fma(float2v{__uint_as_float(l[0]), __uint_as_float(l[1])}, w2[2], d2[2]);
+                                d2[3] = __builtin_elementwise_fma(float2v{__uint_as_float(l[2]), __uint_as_float(l[3])}, w2[3], d2[3]);
+                            } else {
 #pragma unroll
-                            for (int j = 0; j < 4; ++j) {
-                                const float2v x2 = {x_mix_sum_lo(h[j], l[j]), x_mix_sum_hi(h[j], l[j])};
-                                d2[j] = __builtin_elementwise_fma(x2, w2[j], d2[j]);
+                                for (int c = 0; c < 4; ++c) {
+                                    const float2v x2 = {x_mix_sum_lo(h[c], l[c]), x_mix_sum_hi(h[c], l[c])};
+                                    d2[c] = __builtin_elementwise_fma(x2, w2[c], d2[c]);
+                                }
                             }
+                            // the tiles held to 128 registers: one patch row's reads in flight at a time, on <3,2> one tap's (a row's
+                            // there, or all nine anywhere, spill two registers around the channel loop)
+                            if constexpr (TM * TN <= 8 && !STEM)
+                                if (t < 8 && (t % 3 == 2 || (TM == 3 && TN == 2))) __builtin_amdgcn_sched_barrier(0);
                         }
-                    }
+                    };
+                    if (f32patch) taps(std::true_type{});
+                    else taps(std::false_type{});
                     const float d[8] = {d2[0].x, d2[0].y, d2[1].x, d2[1].y, d2[2].x, d2[2].y, d2[3].x, d2[3].y};
-                    const u32x4 s0_ = *reinterpret_cast<const u32x4 *>(PARB_ + (9 * 32 + q * 8) * 4), s1_ = *reinterpret_cast<const u32x4 *>(PARB_ + (9 * 32 + q * 8 + 4) * 4);
-                    const u32x4 b0_ = *reinterpret_cast<const u32x4 *>(PARB_ + (10 * 32 + q * 8) * 4), b1_ = *reinterpret_cast<const u32x4 *>(PARB_ + (10 * 32 + q * 8 + 4) * 4);
+                    const u32x4 s0_ = *reinterpret_cast<const u32x4 *>(PP + 9 * 128), s1_ = *reinterpret_cast<const u32x4 *>(PP + 9 * 128 + 16);
+                    const u32x4 b0_ = *reinterpret_cast<const u32x4 *>(PP + 10 * 128), b1_ = *reinterpret_cast<const u32x4 *>(PP + 10 * 128 + 16);
                     const float scd[8] = {__uint_as_float(s0_[0]), __uint_as_float(s0_[1]), __uint_as_float(s0_[2]), __uint_as_float(s0_[3]),
                                           __uint_as_float(s1_[0]), __uint_as_float(s1_[1]), __uint_as_float(s1_[2]), __uint_as_float(s1_[3])};
                     const float bsd[8] = {__uint_as_float(b0_[0]), __uint_as_float(b0_[1]), __uint_as_float(b0_[2]), __uint_as_float(b0_[3]),
                                           __uint_as_float(b1_[0]), __uint_as_float(b1_[1]), __uint_as_float(b1_[2]), __uint_as_float(b1_[3])};
                     float vd[8];
 #pragma unroll
-                    for (int j = 0; j < 8; ++j) vd[j] = x_actf(__builtin_fmaf(d[j] * up, scd[j], bsd[j]), a.dw_slope, a.dw_cap) * dmid;
+                    for (int c = 0; c < 8; ++c) vd[c] = x_actf(__builtin_fmaf(d[c] * up, scd[c], bsd[c]), a.dw_slope, a.dw_cap) * dmid;
                     x_split8(vd, hi, lo);
                 }
-                const int r = p & 15;
-                unsigned char *dst = A + (p >> 4) * (GL * 512) + r * (GL * 16) + ((q ^ (GL == 4 ? (r >> 1) & 3 : 0)) * 16);
+                unsigned char *dst = A + ddst[j];
                 *reinterpret_cast<half8 *>(dst) = hi;
                 *reinterpret_cast<half8 *>(dst + GL * 256) = lo;
             }
+        }
         // ---- 8 waves: item = (pixel p, group q, channel half hf of the group): the same taps, FMA order, BN, activation and split per
         // channel as above on half the channels - one 16-byte patch read (fp32 planes; two 8-byte reads of a (hi | lo) patch) and one
         // 16-byte parameter read per tap, the 8-byte halves of hi and lo to the same A-tile addresses.  hf is wave-uniform (BM * GL is a
         // multiple of 64): a wave's reads cover the same 64-byte runs of one plane as a 4-wave item's
         if constexpr (NW == 8) {
-            if (!X_DBG(a, 2))
-                for (int it = tid; it < BM * GL * 2; it += NT) {
-                    const int hf = it >= BM * GL ? 1 : 0, ih = it - hf * (BM * GL);
-                    const int p = ih >> 2, q = ih & 3;
-                    const int py = (int)x_div((uint32_t)p, a.fd_tw), px = p - py * a.TW;
-                    const bool live = py < a.TH && oy0 + py < a.Ho && ox0 + px < a.Wo;
+            if (!X_DBG(a, 2)) {
+#pragma unroll
+                for (int j = 0; j < NITEM; ++j) {
+                    if (NIT % NT != 0 && ddst[j] < 0) continue;
                     half4 hi = {0, 0, 0, 0}, lo = hi;
-                    if (live) {
-                        const int base = ((py * s) * a.PW + px * s) * GL + q;
-                        const unsigned char *PW_ = PARB_ + (q * 8 + hf * 4) * 4;
+                    if (dsrc[j] >= 0) {
+                        const unsigned char *R0 = HI + dsrc[j], *PP = PARB_ + dpar[j];
+                        const unsigned char *const R[3] = {R0, R0 + rowb, R0 + 2 * rowb};
                         float2v d2[2] = {{0.f, 0.f}, {0.f, 0.f}};
+                        if (f32patch) {                               // the fp32 planes: channels 0-3 in the first, 4-7 in the second
 #pragma unroll
-                        for (int t = 0; t < 9; ++t) {
-                            const int at = (base + ((t / 3) * a.PW + (t % 3)) * GL) * 16;
-                            const u32x4 w0 = *reinterpret_cast<const u32x4 *>(PW_ + t * 128);
-                            const float2v w2[2] = {{__uint_as_float(w0[0]), __uint_as_float(w0[1])}, {__uint_as_float(w0[2]), __uint_as_float(w0[3])}};
-                            if (f32patch) {                           // the fp32 planes: channels 0-3 in the first, 4-7 in the second
-                                const u32x4 x = *reinterpret_cast<const u32x4 *>((hf ? LO : HI) + at);
-                                d2[0] = __builtin_elementwise_fma(float2v{__uint_as_float(x[0]), __uint_as_float(x[1])}, w2[0], d2[0]);
-                                d2[1] = __builtin_elementwise_fma(float2v{__uint_as_float(x[2]), __uint_as_float(x[3])}, w2[1], d2[1]);
-                            } else {
-                                const u32x2 h = *reinterpret_cast<const u32x2 *>(HI + at + hf * 8), l = *reinterpret_cast<const u32x2 *>(LO + at + hf * 8);
+                            for (int t = 0; t < 9; ++t) {
+                                const u32x4 w0 = *reinterpret_cast<const u32x4 *>(PP + t * 128);
+                                const u32x4 x = *reinterpret_cast<const u32x4 *>(R[t / 3] + (t % 3) * (GL * 16));
+                                d2[0] = __builtin_elementwise_fma(float2v{__uint_as_float(x[0]), __uint_as_float(x[1])}, float2v{__uint_as_float(w0[0]), __uint_as_float(w0[1])}, d2[0]);
+                                d2[1] = __builtin_elementwise_fma(float2v{__uint_as_float(x[2]), __uint_as_float(x[3])}, float2v{__uint_as_float(w0[2]), __uint_as_float(w0[3])}, d2[1]);
+                            }
+                        } else {
 #pragma unroll
-                                for (int j = 0; j < 2; ++j) {
-                                    const float2v x2 = {x_mix_sum_lo(h[j], l[j]), x_mix_sum_hi(h[j], l[j])};
-                                    d2[j] = __builtin_elementwise_fma(x2, w2[j], d2[j]);
+                            for (int t = 0; t < 9; ++t) {
+                                const u32x4 w0 = *reinterpret_cast<const u32x4 *>(PP + t * 128);
+                                const float2v w2[2] = {{__uint_as_float(w0[0]), __uint_as_float(w0[1])}, {__uint_as_float(w0[2]), __uint_as_float(w0[3])}};
+                                const unsigned char *at = R[t / 3] + (t % 3) * (GL * 16);
+                                const u32x2 h = *reinterpret_cast<const u32x2 *>(at), l = *reinterpret_cast<const u32x2 *>(at + plane);
+#pragma unroll
+                                for (int c = 0; c < 2; ++c) {
+                                    const float2v x2 = {x_mix_sum_lo(h[c], l[c]), x_mix_sum_hi(h[c], l[c])};
+                                    d2[c] = __builtin_elementwise_fma(x2, w2[c], d2[c]);
                                 }
                             }
                         }
                         const float d[4] = {d2[0].x, d2[0].y, d2[1].x, d2[1].y};
-                        const u32x4 s0_ = *reinterpret_cast<const u32x4 *>(PW_ + 9 * 128), b0_ = *reinterpret_cast<const u32x4 *>(PW_ + 10 * 128);
+                        const u32x4 s0_ = *reinterpret_cast<const u32x4 *>(PP + 9 * 128), b0_ = *reinterpret_cast<const u32x4 *>(PP + 10 * 128);
                         float vd[4];
 #pragma unroll
-                        for (int j = 0; j < 4; ++j) vd[j] = x_actf(__builtin_fmaf(d[j] * up, __uint_as_float(s0_[j]), __uint_as_float(b0_[j])), a.dw_slope, a.dw_cap) * dmid;
+                        for (int c = 0; c < 4; ++c) vd[c] = x_actf(__builtin_fmaf(d[c] * up, __uint_as_float(s0_[c]), __uint_as_float(b0_[c])), a.dw_slope, a.dw_cap) * dmid;
                         x_split4(vd, hi, lo);
                     }
-                    const int r = p & 15;
-                    unsigned char *dst = A + (p >> 4) * (GL * 512) + r * (GL * 16) + ((q ^ ((r >> 1) & 3)) * 16) + hf * 8;
+                    unsigned char *dst = A + ddst[j];
                     *reinterpret_cast<half4 *>(dst) = hi;
                     *reinterpret_cast<half4 *>(dst + GL * 256) = lo;
                 }
+            }
         }
         if (ks == 0) { XB_STAMP(4) }
         if (ks == 1) { XB_STAMP(14) }
