@@ -229,6 +229,28 @@ int yk_decode_py_packed(const yk_decode_cfg_t *cfg, const float *const *d_pred, 
                         float obj_thresh, float iou_thresh, int max_out, float *rows, int32_t *offsets, int32_t *rows_index,
                         float *d_dets, int32_t *d_counts, void *stream);
 
+/* The suppression rule of the decode tail.  YK_NMS_HARD is the rule above.  The other three run Soft-NMS (Bodla et al. 2017) and
+ * DIoU-NMS (Zheng et al. 2020) as k210_yolo_framework_amd/softnms.py states them: per class, the live candidate with the largest CURRENT
+ * score (ties: lowest box index) is emitted with that score, then every live candidate's score is multiplied by
+ *   LINEAR    1 - IoU if IoU > iou_thresh, else 1
+ *   GAUSSIAN  expf(-(IoU * IoU) / nms_sigma), for every IoU
+ *   DIOU      0 if IoU - d2 / c2 > iou_thresh, else 1   (d2: squared centre distance, c2: squared diagonal of the enclosing box)
+ * and a candidate whose score falls below obj_thresh (or whose weight is 0) is retired.  Rows of a class are in emission order and carry
+ * the decayed score. */
+#define YK_NMS_HARD 0
+#define YK_NMS_LINEAR 1
+#define YK_NMS_GAUSSIAN 2
+#define YK_NMS_DIOU 3
+/* yk_decode_py_ex / yk_decode_py_packed with the rule chosen: YK_NMS_HARD runs exactly what those two run.  nms_sigma is read by
+ * YK_NMS_GAUSSIAN only.  An unknown nms_method, or an nms_sigma that is not positive and finite with YK_NMS_GAUSSIAN: YK_ERR_ARG with the
+ * argument named in yk_last_error, nothing launched. */
+int yk_decode_py_nms(const yk_decode_cfg_t *cfg, const float *const *d_pred, int batch, const float *d_image_hw,
+                     float obj_thresh, float iou_thresh, int max_out, float *d_dets, int32_t *d_counts, int32_t *d_box_index,
+                     void *stream, int nms_method, float nms_sigma);
+int yk_decode_py_packed_nms(const yk_decode_cfg_t *cfg, const float *const *d_pred, int batch, const float *d_image_hw,
+                            float obj_thresh, float iou_thresh, int max_out, float *rows, int32_t *offsets, int32_t *rows_index,
+                            float *d_dets, int32_t *d_counts, void *stream, int nms_method, float nms_sigma);
+
 /* ---- a step as one hipGraph (the kpu_run_kmodel(..., dma, ai_done_cb) shape of main.c:303-311: submit once, get called back) ----
  * Everything issued on `stream` (a created stream, not NULL) between yk_graph_begin and yk_graph_end - yk_run_*, yk_decode_py*,
  * yk_letterbox_u8, yk_memcpy_async - is recorded, not executed; yk_graph_launch replays the recording with ONE host call.

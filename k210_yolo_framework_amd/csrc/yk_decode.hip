@@ -546,6 +546,128 @@ __global__ void __launch_bounds__(64) nms_py_kernel(int ntot, int C, float obj_t
     if (lane == 0) cnt[b * C + c] = kept;
 }
 
+// ---- Soft-NMS (linear, Gaussian) and DIoU-NMS: the rule of k210_yolo_framework_amd/softnms.py, operation for operation.
+// The weight the selected box m puts on a live box q.  DIoU: centres and enclosing box from the min / max-normalised corners, in this order.
+template <int METHOD>
+__device__ __forceinline__ float soft_weight(const float4 &m, const float4 &q, float iou_thresh, float sigma) {
+    const float o = tf_iou(m, q);
+    if (METHOD == YK_NMS_LINEAR) return o > iou_thresh ? 1.f - o : 1.f;
+    if (METHOD == YK_NMS_GAUSSIAN) return expf(-(o * o) / sigma);
+    const float my0 = fminf(m.x, m.z), mx0 = fminf(m.y, m.w), my1 = fmaxf(m.x, m.z), mx1 = fmaxf(m.y, m.w);
+    const float qy0 = fminf(q.x, q.z), qx0 = fminf(q.y, q.w), qy1 = fmaxf(q.x, q.z), qx1 = fmaxf(q.y, q.w);
+    const float dy = (my0 + my1) * 0.5f - (qy0 + qy1) * 0.5f, dx = (mx0 + mx1) * 0.5f - (qx0 + qx1) * 0.5f;
+    const float d2 = dy * dy + dx * dx;
+    const float ey = fmaxf(my1, qy1) - fminf(my0, qy0), ex = fmaxf(mx1, qx1) - fminf(mx0, qx0);
+    const float c2 = ey * ey + ex * ex;
+    const float pen = c2 > 0.f ? d2 / c2 : 0.f;
+    return o - pen > iou_thresh ? 0.f : 1.f;
+}
+
+// The rounds over `count` entries: entry i has the current score s[i] (live iff >= obj_thresh), the box box_of(i) and the box index idx_of(i),
+// ascending in i.  Lane l owns the entries i = l (mod 64) and is the only one to read or write their scores, so a round needs no barrier
+// and no atomic: an arg-max over (current score, lowest index) across the wave, then one decay pass.  Any max_out: rounds are sequential.
+template <int METHOD, class BoxOf, class IdxOf>
+__device__ __forceinline__ int soft_rounds(int count, float *s, BoxOf box_of, IdxOf idx_of, float obj_thresh, float iou_thresh, float sigma,
+                                           int max_out, int *og, float *os) {
+    const int lane = threadIdx.x;
+    int kept = 0;
+    while (kept < max_out) {
+        float best = -INFINITY;
+        int bidx = 0x7fffffff, bpos = -1;
+        for (int i = lane; i < count; i += 64) {
+            const float v = s[i];
+            if (v >= obj_thresh && (bpos < 0 || v > best)) {          // ascending i: a tie stays with the lower box index
+                best = v;
+                bpos = i;
+            }
+        }
+        if (bpos >= 0) bidx = idx_of(bpos);
+        yk_wave_argmax(best, bidx, bpos);
+        if (bpos < 0) break;
+        if (lane == 0) {
+            og[kept] = bidx;
+            os[kept] = best;
+        }
+        ++kept;
+        if (kept >= max_out) break;
+        const float4 mb = box_of(bpos);
+        for (int i = lane; i < count; i += 64) {
+            const float v = s[i];
+            if (i == bpos) {
+                s[i] = -INFINITY;
+            } else if (v >= obj_thresh) {
+                const float w = soft_weight<METHOD>(mb, box_of(i), iou_thresh, sigma);
+                const float nv = v * w;
+                if (w == 0.f || nv < obj_thresh)
+                    s[i] = -INFINITY;
+                else if (METHOD != YK_NMS_DIOU)
+                    s[i] = nv;
+            }
+        }
+    }
+    return kept;
+}
+
+// grid (C, batch), one wavefront, the LDS of nms_py_kernel<MAXC>.  The candidates are gathered as there (ballot compaction in box-index order,
+// boxes in bulk after the scan).  A class with more candidates than the LDS holds runs the same rounds over its score plane in global
+// memory, decayed in place: the plane is this call's own scratch and decode_py_kernel rewrites it on every call.
+template <int MAXC, int METHOD>
+__global__ void __launch_bounds__(64) softnms_py_kernel(int ntot, int C, float obj_thresh, float iou_thresh, float sigma, int max_out,
+                                                        const float4 *__restrict__ boxes, float *scores_t, int *__restrict__ sel_g,
+                                                        float *__restrict__ sel_s, int *__restrict__ cnt) {
+    __shared__ nms_lds<MAXC> L;
+    const int c = blockIdx.x, b = blockIdx.y, lane = threadIdx.x;
+    float *sc = scores_t + ((size_t)b * C + c) * ntot;
+    const float4 *bx = boxes + (size_t)b * ntot;
+    int *og = sel_g + ((size_t)b * C + c) * max_out;
+    float *os = sel_s + ((size_t)b * C + c) * max_out;
+    int n = 0;
+    for (int base0 = 0; base0 < ntot; base0 += 64 * 8) {
+        float sv[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int i = base0 + u * 64 + lane;
+            sv[u] = (i < ntot) ? sc[i] : -INFINITY;
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int i = base0 + u * 64 + lane;
+            const bool f = (i < ntot) && (sv[u] >= obj_thresh);
+            const unsigned long long m = __ballot(f);
+            const int pos = n + __popcll(m & ((1ull << lane) - 1ull));
+            if (f && pos < MAXC) {
+                L.s[pos] = sv[u];
+                L.idx[pos] = i;
+            }
+            n += __popcll(m);
+        }
+    }
+    __syncthreads();
+    int kept;
+    if (n <= MAXC) {
+        for (int c0 = 0; c0 < n; c0 += 256) {
+            float4 t[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int q = c0 + u * 64 + lane;
+                t[u] = bx[q < n ? L.idx[q] : 0];
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int q = c0 + u * 64 + lane;
+                if (q < n) L.box[q] = t[u];
+            }
+        }
+        __syncthreads();
+        kept = soft_rounds<METHOD>(
+            n, L.s, [&](int i) { return L.box[i]; }, [&](int i) { return L.idx[i]; }, obj_thresh, iou_thresh, sigma, max_out, og, os);
+    } else {
+        kept = soft_rounds<METHOD>(
+            ntot, sc, [&](int i) { return bx[i]; }, [](int i) { return i; }, obj_thresh, iou_thresh, sigma, max_out, og, os);
+    }
+    if (lane == 0) cnt[b * C + c] = kept;
+}
+
 // grid (batch), 256 threads: class-major concatenation (keras_inference.py:133-135); one thread per (class, rank) slot
 __global__ void __launch_bounds__(256) compact_py_kernel(int ntot, int C, int max_out, const float4 *__restrict__ boxes,
                                                          const int *__restrict__ sel_g, const float *__restrict__ sel_s,
@@ -632,7 +754,7 @@ __global__ void __launch_bounds__(256) compact_packed_kernel(int ntot, int C, in
 
 static int decode_impl(const yk_decode_cfg_t *cfg, const float *const *d_pred, int batch, const float *d_image_hw, float obj_thresh,
                        float iou_thresh, int max_out, float *d_dets, int32_t *d_counts, int32_t *d_box_index, float *rows, int32_t *offsets,
-                       int32_t *rows_index, void *stream);
+                       int32_t *rows_index, void *stream, int nms_method = YK_NMS_HARD, float nms_sigma = 0.5f);
 
 extern "C" int yk_decode_py(const yk_decode_cfg_t *cfg, const float *const *d_pred, int batch, const float *d_image_hw,
                             float obj_thresh, float iou_thresh, int max_out, float *d_dets, int32_t *d_counts,
@@ -660,9 +782,60 @@ extern "C" int yk_decode_py_packed(const yk_decode_cfg_t *cfg, const float *cons
     return decode_impl(cfg, d_pred, batch, d_image_hw, obj_thresh, iou_thresh, max_out, d_dets, d_counts, nullptr, rows, offsets, rows_index, stream);
 }
 
+// the rule's own arguments, checked before anything else is looked at or launched
+static int check_nms(const char *who, int nms_method, float nms_sigma) {
+    if (nms_method < YK_NMS_HARD || nms_method > YK_NMS_DIOU) {
+        yk_set_error("%s: nms_method %d is none of YK_NMS_HARD, _LINEAR, _GAUSSIAN, _DIOU", who, nms_method);
+        return YK_ERR_ARG;
+    }
+    if (nms_method == YK_NMS_GAUSSIAN && !(nms_sigma > 0.f && nms_sigma < INFINITY)) {
+        yk_set_error("%s: nms_sigma %g is not positive and finite", who, (double)nms_sigma);
+        return YK_ERR_ARG;
+    }
+    return YK_OK;
+}
+
+extern "C" int yk_decode_py_nms(const yk_decode_cfg_t *cfg, const float *const *d_pred, int batch, const float *d_image_hw,
+                                float obj_thresh, float iou_thresh, int max_out, float *d_dets, int32_t *d_counts,
+                                int32_t *d_box_index, void *stream, int nms_method, float nms_sigma) {
+    if (const int rc = check_nms("yk_decode_py_nms", nms_method, nms_sigma)) return rc;
+    if (!d_dets || !d_counts) {
+        yk_set_error("yk_decode_py_nms: bad argument");
+        return YK_ERR_ARG;
+    }
+    return decode_impl(cfg, d_pred, batch, d_image_hw, obj_thresh, iou_thresh, max_out, d_dets, d_counts, d_box_index, nullptr, nullptr, nullptr, stream,
+                       nms_method, nms_sigma);
+}
+
+extern "C" int yk_decode_py_packed_nms(const yk_decode_cfg_t *cfg, const float *const *d_pred, int batch, const float *d_image_hw,
+                                       float obj_thresh, float iou_thresh, int max_out, float *rows, int32_t *offsets, int32_t *rows_index,
+                                       float *d_dets, int32_t *d_counts, void *stream, int nms_method, float nms_sigma) {
+    if (const int rc = check_nms("yk_decode_py_packed_nms", nms_method, nms_sigma)) return rc;
+    if (!rows || !offsets) {
+        yk_set_error("yk_decode_py_packed_nms: bad argument");
+        return YK_ERR_ARG;
+    }
+    return decode_impl(cfg, d_pred, batch, d_image_hw, obj_thresh, iou_thresh, max_out, d_dets, d_counts, nullptr, rows, offsets, rows_index, stream,
+                       nms_method, nms_sigma);
+}
+
+template <int MAXC>
+static void launch_softnms(int method, dim3 grid, hipStream_t st, int ntot, int C, float obj_thresh, float iou_thresh, float sigma, int max_out,
+                           const float4 *boxes, float *scores_t, int *sel_g, float *sel_s, int *cnt) {
+    if (method == YK_NMS_LINEAR)
+        hipLaunchKernelGGL((softnms_py_kernel<MAXC, YK_NMS_LINEAR>), grid, dim3(64), 0, st, ntot, C, obj_thresh, iou_thresh, sigma, max_out, boxes,
+                           scores_t, sel_g, sel_s, cnt);
+    else if (method == YK_NMS_GAUSSIAN)
+        hipLaunchKernelGGL((softnms_py_kernel<MAXC, YK_NMS_GAUSSIAN>), grid, dim3(64), 0, st, ntot, C, obj_thresh, iou_thresh, sigma, max_out, boxes,
+                           scores_t, sel_g, sel_s, cnt);
+    else
+        hipLaunchKernelGGL((softnms_py_kernel<MAXC, YK_NMS_DIOU>), grid, dim3(64), 0, st, ntot, C, obj_thresh, iou_thresh, sigma, max_out, boxes,
+                           scores_t, sel_g, sel_s, cnt);
+}
+
 static int decode_impl(const yk_decode_cfg_t *cfg, const float *const *d_pred, int batch, const float *d_image_hw, float obj_thresh,
                        float iou_thresh, int max_out, float *d_dets, int32_t *d_counts, int32_t *d_box_index, float *rows, int32_t *offsets,
-                       int32_t *rows_index, void *stream) {
+                       int32_t *rows_index, void *stream, int nms_method, float nms_sigma) {
     if (!cfg || !d_pred || batch <= 0 || max_out <= 0 || cfg->n_layers <= 0 ||
         cfg->n_layers > YK_MAX_LAYERS || cfg->anchor_num <= 0 || cfg->anchor_num > YK_MAX_ANCHORS ||
         cfg->class_num <= 0) {
@@ -716,7 +889,12 @@ static int decode_impl(const yk_decode_cfg_t *cfg, const float *const *d_pred, i
     const int total = batch * ntot;
     hipLaunchKernelGGL(decode_py_kernel, dim3((total + 255) / 256), dim3(256), 0, st, a, batch, d_image_hw, boxes,
                        scores_t);
-    if (ntot <= 1088)
+    if (nms_method != YK_NMS_HARD) {
+        if (ntot <= 1088)
+            launch_softnms<1088>(nms_method, dim3(a.C, batch), st, ntot, a.C, obj_thresh, iou_thresh, nms_sigma, max_out, boxes, scores_t, sel_g, sel_s, cnt);
+        else
+            launch_softnms<2048>(nms_method, dim3(a.C, batch), st, ntot, a.C, obj_thresh, iou_thresh, nms_sigma, max_out, boxes, scores_t, sel_g, sel_s, cnt);
+    } else if (ntot <= 1088)
         hipLaunchKernelGGL(nms_py_kernel<1088>, dim3(a.C, batch), dim3(64), 0, st, ntot, a.C, obj_thresh, iou_thresh, max_out, boxes, scores_t,
                            sel_g, sel_s, cnt);
     else

@@ -29,6 +29,7 @@ import numpy as np
 
 from . import draw as dr
 from . import jpeg
+from . import softnms
 from .helper import INFO, NOTE, Helper, VOC_ANCHORS
 from .yolonet import MODEL_DEFS
 
@@ -59,6 +60,8 @@ def parse(argv=None):
     p.add_argument('--obj_thresh', type=float, default=0.7)
     p.add_argument('--iou_thresh', type=float, default=0.3)
     p.add_argument('--precision', type=str, choices=['f16', 'f16x2', 'kpu'], default='f16x2')
+    p.add_argument('--nms', type=str, default='hard', help="suppression rule of the decode: hard (the reference's), linear or gaussian (Soft-NMS), diou")
+    p.add_argument('--nms_sigma', type=float, default=0.5, help='sigma of --nms gaussian')
     a = p.parse_args(sys.argv[1:] if argv is None else argv)
     if (a.precision == 'kpu') != a.pre_ckpt.endswith(('.kmodel', '.kfpkg')):
         p.error('--precision kpu runs a .kmodel / .kfpkg checkpoint, and only it does (the float modes take .h5 / .npz)')
@@ -66,6 +69,10 @@ def parse(argv=None):
         p.error('--batch, --depth and --workers are at least 1')
     if not 1 <= a.quality <= 100:
         p.error('--quality is 1 .. 100')
+    try:
+        softnms.check(a.nms, a.nms_sigma)
+    except ValueError as e:
+        p.error(str(e))
     a.draw = a.draw == 'True'
     return a
 
@@ -128,7 +135,8 @@ class _Stage:
 
 def run(h: Helper, model, sources, out_dir=None, draw: bool = True, batch: int = 32, depth: int = 4, precision: str = 'f16x2',
         obj_thresh: float = 0.7, iou_thresh: float = 0.3, workers: int = 8, names: Optional[Sequence[str]] = None,
-        return_arrays: bool = False, verbose: bool = True, max_out: int = 30, encode: str = 'pil', quality: int = 75, decode: str = 'pil'):
+        return_arrays: bool = False, verbose: bool = True, max_out: int = 30, encode: str = 'pil', quality: int = 75, decode: str = 'pil',
+        nms: str = 'hard', nms_sigma: float = 0.5):
     """sources: picture paths, or [h, w, 3] uint8 arrays already in memory (then `names` names them); with decode='gpu' paths or the bytes of
     picture files: baseline JPEGs are decoded on the device by the rule of include/yolo_hip.h (not PIL's bytes: DESIGN.md 3.12), every other
     file by PIL on the pool as with decode='pil'; a stream the device cannot finish raises YkError naming the file.  -> {'names', 'detections': one
@@ -146,6 +154,10 @@ def run(h: Helper, model, sources, out_dir=None, draw: bool = True, batch: int =
         raise engine.YkError(f'detect: encode {encode!r}: expected pil or gpu')
     if decode not in ('pil', 'gpu'):
         raise engine.YkError(f'detect: decode {decode!r}: expected pil or gpu')
+    try:
+        softnms.check(nms, nms_sigma)
+    except ValueError as e:
+        raise engine.YkError(f'detect: {e}') from None
     gpu_decode = decode == 'gpu'
     in_memory = isinstance(sources[0], (np.ndarray, bytes))
     if gpu_decode and any(isinstance(s, np.ndarray) for s in sources):
@@ -328,10 +340,10 @@ def run(h: Helper, model, sources, out_dir=None, draw: bool = True, batch: int =
             engine.letterbox_ragged_u8(d_packed, table_d, in_hw, stream=stream, out=dst)
             hw = np.asarray(shapes, np.float32)
             if pipe is not None:
-                dets, counts, _ = pipe.submit(None, image_hw=hw, obj_thresh=obj_thresh, iou_thresh=iou_thresh, max_out=max_out, batch=n)
+                dets, counts, _ = pipe.submit(None, image_hw=hw, obj_thresh=obj_thresh, iou_thresh=iou_thresh, max_out=max_out, batch=n, nms=nms, sigma=nms_sigma)
             else:
                 plan.run_u8(frames[:n])
-                dets, counts = engine.decode_py(cfg, plan.outputs(), n, hw, obj_thresh, iou_thresh, max_out=max_out)
+                dets, counts = engine.decode_py(cfg, plan.outputs(), n, hw, obj_thresh, iou_thresh, max_out=max_out, nms=nms, sigma=nms_sigma)
             if want_pixels:
                 max_px = int(max(s[0] * s[1] for s in shapes))
                 engine.draw_detections_u8(d_packed, table_d, dets, counts, colormap, atlas, stream=stream, max_pixels=max_px)
@@ -362,7 +374,8 @@ def run(h: Helper, model, sources, out_dir=None, draw: bool = True, batch: int =
         if pipe is not None:
             pipe.close()
     if out_dir is not None:
-        doc = [{'path': names[i], 'detections': [[float(v) for v in row] for row in results[i]]} for i in range(n_all)]
+        rule = {} if nms == 'hard' else {'nms': nms, 'nms_sigma': float(nms_sigma)}      # (hard: the file is what it always was)
+        doc = [{'path': names[i], **rule, 'detections': [[float(v) for v in row] for row in results[i]]} for i in range(n_all)]
         (Path(out_dir) / 'detections.json').write_text(json.dumps(doc, indent=1))
     out = {'names': names, 'detections': results, 'files': written}
     if arrays is not None:
@@ -388,7 +401,10 @@ def main(argv=None):
     if not paths:
         raise engine.YkError(f'detect: no pictures ({", ".join(EXTENSIONS)}) in {a.src}')
     res = run(h, model, paths, out_dir=a.out_dir, draw=a.draw, batch=a.batch, depth=a.depth, precision=a.precision,
-              obj_thresh=a.obj_thresh, iou_thresh=a.iou_thresh, workers=a.workers, encode=a.encode, quality=a.quality, decode=a.decode)
+              obj_thresh=a.obj_thresh, iou_thresh=a.iou_thresh, workers=a.workers, encode=a.encode, quality=a.quality, decode=a.decode,
+              nms=a.nms, nms_sigma=a.nms_sigma)
+    if a.nms != 'hard':
+        print(INFO, f' nms {a.nms}, sigma {a.nms_sigma:g}: scores are the decayed ones')
     print(INFO, f' {len(paths)} pictures, {sum(len(d) for d in res["detections"])} detections -> {Path(a.out_dir) / "detections.json"}'
           + (f', {len(res["files"])} annotated pictures' if a.draw else ''))
     return res

@@ -362,13 +362,25 @@ def make_decode_cfg(anchors: np.ndarray, class_num: int, in_hw, out_hw) -> Decod
     return cfg
 
 
+def _nms_method(nms: str, sigma: float) -> int:
+    """YK_NMS_* of a rule's name; an unknown name or a sigma the Gaussian cannot use is refused by name."""
+    from . import softnms
+    try:
+        softnms.check(nms, float(sigma))
+    except ValueError as e:
+        raise YkError(str(e)) from None
+    return softnms.method_id(nms)
+
+
 def decode_py(cfg: DecodeCfg, preds: Sequence, batch: int, image_hw=None, obj_thresh: float = 0.7,
-              iou_thresh: float = 0.5, max_out: int = 30, stream=None, return_index: bool = False):
+              iou_thresh: float = 0.5, max_out: int = 30, stream=None, return_index: bool = False, nms: str = 'hard', sigma: float = 0.5):
     """Batched keras_inference.py:94-135 on the GPU.  preds: cuda fp32 tensors [>=batch,h,w,A*(5+C)].
+    nms: 'hard' (the reference's rule) or 'linear' / 'gaussian' / 'diou' (softnms.py: rows then carry the decayed scores); sigma: the Gaussian's.
     -> (dets [batch, C*max_out, 6] cuda fp32, counts [batch] cuda int32[, box_index [batch, C*max_out] cuda int32: each row's index
     in the reference's flattened (layer, h, w, anchor) box list])."""
     import torch
     require_gpu()
+    method = _nms_method(nms, sigma)
     dev = preds[0].device
     dets = torch.empty((batch, cfg.class_num * max_out, 6), dtype=torch.float32, device=dev)
     counts = torch.empty((batch,), dtype=torch.int32, device=dev)
@@ -376,6 +388,10 @@ def decode_py(cfg: DecodeCfg, preds: Sequence, batch: int, image_hw=None, obj_th
     ihw = None
     if image_hw is not None:
         ihw = torch.as_tensor(np.broadcast_to(np.asarray(image_hw, np.float32), (batch, 2)).copy(), device=dev)
+    if method != 0:
+        index = torch.full((batch, cfg.class_num * max_out), -1, dtype=torch.int32, device=dev) if return_index else None
+        call('yk_decode_py_nms', C.byref(cfg), arr, batch, ihw, obj_thresh, iou_thresh, max_out, dets, counts, index, _stream(stream), method, sigma)
+        return (dets, counts, index) if return_index else (dets, counts)
     if return_index:
         index = torch.full((batch, cfg.class_num * max_out), -1, dtype=torch.int32, device=dev)
         call('yk_decode_py_ex', C.byref(cfg), arr, batch, ihw, obj_thresh, iou_thresh, max_out, dets, counts, index, _stream(stream))
@@ -989,7 +1005,7 @@ class Pipeline:
         ev.record(s.stream)
         s.h2d_free[s.h2d_last] = ev
 
-    def _issue(self, s, B, src_ptr, host, use_hw, obj, iou, max_out, want_index):
+    def _issue(self, s, B, src_ptr, host, use_hw, obj, iou, max_out, want_index, nms='hard', sigma=0.5):
         H, W = self.spec.in_hw
         x = src_ptr
         if self.src_hw:
@@ -997,7 +1013,15 @@ class Pipeline:
             x = s.frames
         call('yk_run_u8', s.plan._h, x, B, s.st)
         ihw = s.image_hw if use_hw else None
-        if host:
+        if nms != 'hard':
+            method = _nms_method(nms, sigma)
+            if host:
+                call('yk_decode_py_packed_nms', C.byref(self.cfg), s.preds, B, ihw, obj, iou, max_out, s.d_rows, s.d_offsets,
+                     s.d_index if want_index else None, None, None, s.st, method, sigma)
+            else:
+                call('yk_decode_py_nms', C.byref(self.cfg), s.preds, B, ihw, obj, iou, max_out, s.dets, s.counts,
+                     s.index if want_index else None, s.st, method, sigma)
+        elif host:
             call('yk_decode_py_packed', C.byref(self.cfg), s.preds, B, ihw, obj, iou, max_out, s.d_rows, s.d_offsets,
                  s.d_index if want_index else None, None, None, s.st)
         else:
@@ -1011,12 +1035,14 @@ class Pipeline:
             g.close()
         s.graphs.clear()
 
-    def _run(self, s, B, src_ptr, host, use_hw, obj, iou, max_out, want_index):
+    def _run(self, s, B, src_ptr, host, use_hw, obj, iou, max_out, want_index, nms='hard', sigma=0.5):
+        if nms != 'hard':
+            _nms_method(nms, sigma)                                # refused by name before anything is issued or captured
         if max_out > self.max_out:
             raise YkError(f'max_out {max_out} > the pipeline\'s max_out {self.max_out}')
         if host:
             src_ptr = self._h2d(s, B)
-        args = (B, src_ptr, host, use_hw, float(obj), float(iou), int(max_out), bool(want_index))
+        args = (B, src_ptr, host, use_hw, float(obj), float(iou), int(max_out), bool(want_index), nms, float(sigma) if nms == 'gaussian' else 0.0)
         if not self.graph:
             self._issue(s, *args)
             if host:
@@ -1069,7 +1095,7 @@ class Pipeline:
         return True
 
     def submit(self, frames_u8=None, image_hw=None, obj_thresh: float = 0.7, iou_thresh: float = 0.5, max_out: int = 30,
-               return_index: bool = False, batch: Optional[int] = None, sync_input: bool = True):
+               return_index: bool = False, batch: Optional[int] = None, sync_input: bool = True, nms: str = 'hard', sigma: float = 0.5):
         """frames_u8: cuda uint8 [B,h,w,3] that stays alive until the results are consumed (None: the slot's own input(i) buffer, `batch`
         images of it).  -> (dets [B, C*max_out, 6], counts [B], stream[, box_index [B, C*max_out]]) - the slot's tensors, sliced to B."""
         import time
@@ -1096,14 +1122,14 @@ class Pipeline:
                     ptr = s.src.data_ptr()
         assert 0 < B <= self.max_batch
         use_hw = self._set_hw(s, B, image_hw)
-        self._run(s, B, ptr, False, use_hw, obj_thresh, iou_thresh, max_out, return_index)
+        self._run(s, B, ptr, False, use_hw, obj_thresh, iou_thresh, max_out, return_index, nms, sigma)
         self.host_us = (time.perf_counter() - t0) * 1e6
         if return_index:
             return s.dets[:B], s.counts[:B], s.stream, s.index[:B]
         return s.dets[:B], s.counts[:B], s.stream
 
     def submit_host(self, frames_u8=None, image_hw=None, obj_thresh: float = 0.7, iou_thresh: float = 0.5, max_out: int = 30,
-                    return_index: bool = False, batch: Optional[int] = None) -> Ticket:
+                    return_index: bool = False, batch: Optional[int] = None, nms: str = 'hard', sigma: float = 0.5) -> Ticket:
         """frames_u8: host uint8 [B,h,w,3] (numpy or torch; copied into the slot's pinned buffer) or None = `batch` images already
         written to host_input(i).  The frames cross PCIe, the detections come back to pinned host memory at their live size."""
         import time
@@ -1124,7 +1150,7 @@ class Pipeline:
             s.h_src[:B].copy_(f)
         assert 0 < B <= self.max_batch
         use_hw = self._set_hw(s, B, image_hw)
-        self._run(s, B, None, True, use_hw, obj_thresh, iou_thresh, max_out, return_index)
+        self._run(s, B, None, True, use_hw, obj_thresh, iou_thresh, max_out, return_index, nms, sigma)
         ev = torch.cuda.Event()
         ev.record(s.stream)
         self.host_us = (time.perf_counter() - t0) * 1e6

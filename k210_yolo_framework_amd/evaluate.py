@@ -3,6 +3,7 @@
 
     python keras_eval.py CKPT [network flags of keras_inference.py] (--ann LIST.npy [--all] [--limit N] | --synthetic N)
                               [--precision f16x2|f16|kpu] [--obj_thresh 0.05] [--nms_iou 0.5] [--iou_thresh 0.5] [--voc07 True]
+                              [--nms hard|linear|gaussian|diou] [--nms_sigma 0.5]
                               [--metric voc|coco] [--out eval.json] [--dump_rows rows.npz]
 
 CKPT: a Keras `.h5` / `.npz` checkpoint (float modes, through engine.Pipeline with several batches in flight) or a `.kmodel` / `.kfpkg`
@@ -28,6 +29,7 @@ from pathlib import Path
 
 import numpy as np
 
+from . import softnms
 from .helper import INFO, Helper, VOC_ANCHORS
 from .yolonet import MODEL_DEFS
 
@@ -59,6 +61,8 @@ def parse(argv=None):
     p.add_argument('--obj_thresh', type=float, default=0.05)
     p.add_argument('--nms_iou', type=float, default=0.5, help='IoU of the per-class NMS (keras_inference.py --iou_thresh)')
     p.add_argument('--iou_thresh', type=float, default=0.5, help='IoU a detection needs with a ground-truth box')
+    p.add_argument('--nms', type=str, default='hard', help="suppression rule of the decode: hard (the reference's), linear or gaussian (Soft-NMS), diou")
+    p.add_argument('--nms_sigma', type=float, default=0.5, help='sigma of --nms gaussian')
     p.add_argument('--voc07', type=str, choices=['True', 'False'], default='False', help='11-point AP')
     p.add_argument('--metric', type=str, choices=['voc', 'coco'], default='voc', help='coco: also AP over IoU .50:.95, by object size, AR')
     p.add_argument('--all', action='store_true', help='evaluate the whole list, not its validation head')
@@ -72,6 +76,10 @@ def parse(argv=None):
         p.error('--precision kpu runs a .kmodel / .kfpkg checkpoint, and only it does (the float modes take .h5 / .npz)')
     if a.synthetic and a.ann:
         p.error('--synthetic N replaces --ann')
+    try:
+        softnms.check(a.nms, a.nms_sigma)
+    except ValueError as e:
+        p.error(str(e))
     if a.metric == 'coco' and a.voc07 == 'True':
         p.error('--voc07 True is the 11-point VOC AP; --metric coco has its own 101-point AP: choose one')
     return a
@@ -113,7 +121,7 @@ def run(a, h: Helper, model, items, ev) -> None:
             frames = torch.cat([engine.letterbox_u8(torch.from_numpy(im[None]).cuda(), in_hw) for im, _ in loaded])
             plan.run_u8(frames)
             shapes = np.asarray([im.shape[:2] for im, _ in loaded], np.float32)
-            dets, counts = engine.decode_py(cfg, plan.outputs(), len(loaded), shapes, a.obj_thresh, a.nms_iou)
+            dets, counts = engine.decode_py(cfg, plan.outputs(), len(loaded), shapes, a.obj_thresh, a.nms_iou, nms=a.nms, sigma=a.nms_sigma)
             ev.add(dets, counts, [ground_truth_rows(b, im.shape[:2]) for im, b in loaded])
         return
     pipe = engine.Pipeline(model.spec, model.get_weights(), h.anchors, max_batch=B, depth=max(1, int(a.depth)), precision=a.precision)
@@ -134,7 +142,7 @@ def run(a, h: Helper, model, items, ev) -> None:
                 for j, (im, _) in enumerate(loaded):
                     engine.letterbox_u8(torch.from_numpy(im[None]).to(buf.device, non_blocking=False), in_hw, stream=st, out=buf[j:j + 1])
             shapes = np.asarray([im.shape[:2] for im, _ in loaded], np.float32)
-            dets, counts, stream = pipe.submit(None, image_hw=shapes, obj_thresh=a.obj_thresh, iou_thresh=a.nms_iou, batch=len(loaded))
+            dets, counts, stream = pipe.submit(None, image_hw=shapes, obj_thresh=a.obj_thresh, iou_thresh=a.nms_iou, batch=len(loaded), nms=a.nms, sigma=a.nms_sigma)
             pending.append((dets, counts, stream, [ground_truth_rows(b, im.shape[:2]) for im, b in loaded]))
         while pending:
             drain()
@@ -190,6 +198,8 @@ def main(argv=None):
     r = ev.result()
     print(f'{a.precision}: mAP {100 * r["map"]:.2f} over {len(items)} images ({"VOC07 11-point" if voc07 else "area"} AP, IoU {a.iou_thresh}; '
           f'obj_thresh {a.obj_thresh}, {CAP_NOTE})')
+    if a.nms != 'hard':
+        print(f'   nms {a.nms}, sigma {a.nms_sigma:g}: rows carry the decayed scores (softnms.py)')
     for c in range(a.class_num):
         if r['n_gt'][c]:
             print(f'   class {c:2d}: AP {100 * r["ap"][c]:6.2f}   gt {r["n_gt"][c]:5d}  det {r["n_det"][c]:6d}  tp {r["tp"][c]:5d}')
@@ -198,6 +208,8 @@ def main(argv=None):
               'nms_iou': a.nms_iou, 'iou_thresh': a.iou_thresh, 'voc07': voc07, 'note': CAP_NOTE, 'map': num(r['map']),
               'ap': [num(v) for v in r['ap']], 'n_gt': r['n_gt'].tolist(), 'n_det': r['n_det'].tolist(), 'tp': r['tp'].tolist(),
               'fp': r['fp'].tolist()}
+    if a.nms != 'hard':
+        report.update(nms=a.nms, nms_sigma=a.nms_sigma)
     if a.metric == 'coco':
         report['coco'] = coco_report(ev, a.class_num, r['n_gt'])
     out = Path(a.out) if a.out else Path(a.pre_ckpt).resolve().parent / 'eval.json'

@@ -14,11 +14,12 @@ from pathlib import Path
 
 import numpy as np
 
+from . import softnms
 from .helper import INFO, NOTE, Helper, VOC_ANCHORS
 from .yolonet import MODEL_DEFS
 
 
-def detect(h: Helper, model, orig_imgs, obj_thresh: float, iou_thresh: float):
+def detect(h: Helper, model, orig_imgs, obj_thresh: float, iou_thresh: float, nms: str = 'hard', nms_sigma: float = 0.5):
     """orig_imgs: list of HxWx3 uint8 arrays -> list of [K,6] (top,left,bottom,right,score,class) numpy."""
     import torch
     from . import engine
@@ -34,14 +35,14 @@ def detect(h: Helper, model, orig_imgs, obj_thresh: float, iou_thresh: float):
     plan = model._plan(n)
     plan.run_u8(frames.contiguous())
     cfg = engine.make_decode_cfg(h.anchors, h.class_num, h.in_hw[0], h.out_hw)
-    dets, counts = engine.decode_py(cfg, plan.outputs(), n, np.asarray(shapes, np.float32), obj_thresh, iou_thresh)
+    dets, counts = engine.decode_py(cfg, plan.outputs(), n, np.asarray(shapes, np.float32), obj_thresh, iou_thresh, nms=nms, sigma=nms_sigma)
     torch.cuda.synchronize()
     dets, counts = dets.cpu().numpy(), counts.cpu().numpy()
     return [dets[i, :counts[i]] for i in range(n)]
 
 
 def main(ckpt_weights, image_size, output_size, model_def, class_num, depth_multiplier, obj_thresh, iou_thresh,
-         train_set, test_image, anchors=None, precision='f16x2'):
+         train_set, test_image, anchors=None, precision='f16x2', nms='hard', nms_sigma=0.5):
     anchor_file = Path(f'data/{train_set}_anchor.npy')
     anc = str(anchor_file) if anchor_file.exists() else (anchors if anchors is not None else VOC_ANCHORS)
     h = Helper(None, class_num, anc, np.reshape(np.array(image_size), (-1, 2)), np.reshape(np.array(output_size), (-1, 2)))
@@ -54,7 +55,9 @@ def main(ckpt_weights, image_size, output_size, model_def, class_num, depth_mult
     else:
         print(NOTE, ' no checkpoint given: seeded random weights')
     orig_img = h._read_img(str(test_image))
-    dets = detect(h, yolo_model, [orig_img], obj_thresh, iou_thresh)[0]
+    dets = detect(h, yolo_model, [orig_img], obj_thresh, iou_thresh, nms, nms_sigma)[0]
+    if nms != 'hard':
+        print(INFO, f' nms {nms}' + (f', sigma {nms_sigma:g}' if nms == 'gaussian' else '') + ': scores are the decayed ones')
     if len(dets) > 0:
         print('[top\tleft\tbottom\tright\tscore\tclass]')
         for top, left, bottom, right, score, c in dets:
@@ -97,11 +100,17 @@ def cli(argv=None):
     parser.add_argument('--precision', type=str, choices=['f16', 'f16x2', 'kpu'], default='f16x2',
                         help="arithmetic of the conv stack (not in the reference): 'f16x2' = fp32-class results (default), 'f16' = fastest, "
                              "'kpu' = a .kmodel/.kfpkg on the K210 KPU's integer arithmetic (raw 0..255 pixels, the board's outputs)")
+    parser.add_argument('--nms', type=str, default='hard', help="suppression rule of the decode: hard (the reference's), linear or gaussian (Soft-NMS), diou")
+    parser.add_argument('--nms_sigma', type=float, default=0.5, help='sigma of --nms gaussian')
     parser.add_argument('pre_ckpt', type=str, help='pre-train weights path')
     parser.add_argument('test_image', type=str, help='test image path')
     args = parser.parse_args(sys.argv[1:] if argv is None else argv)
+    try:
+        softnms.check(args.nms, args.nms_sigma)
+    except ValueError as e:
+        parser.error(str(e))
     return main(args.pre_ckpt, args.image_size, args.output_size, args.model_def, args.class_num, args.depth_multiplier,
-                args.obj_thresh, args.iou_thresh, args.train_set, args.test_image, precision=args.precision)
+                args.obj_thresh, args.iou_thresh, args.train_set, args.test_image, precision=args.precision, nms=args.nms, nms_sigma=args.nms_sigma)
 
 
 if __name__ == '__main__':
