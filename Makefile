@@ -21,6 +21,9 @@
 #                    batch); every batch is composed from there by one launch and the epoch line names the hits / misses: DESIGN.md 3.19
 #                    [DECODE=gpu]: the pictures that still have to be decoded are, if baseline JPEG files, decoded on the GPU into that
 #                    memory by the project's own integer rule (not PIL's bytes: DESIGN.md 3.12), every other file by PIL; works without CACHE=gpu
+#                    [EMA=True EMADECAY=0.9999 EMATAU=2000]: an exponential moving average of the weights (decay ramped over EMATAU updates) is
+#                    validated and saved as yolo_ema_model.h5 beside the usual checkpoint; [CLIPNORM=10.0]: global-norm gradient clipping (0: off);
+#                    [LRSCHED=cosine|step|constant WARMUP=N LRFINAL=0.01]: linear warmup and a schedule over the whole run: DESIGN.md 3.21
 #   make kmodel      CKPT=yolo_model.h5 OUT=yolo.kmodel|.kfpkg [SYNTHETIC=256 | CALIB=data/voc_img_ann.npy]: 8-bit K210 model, calibrated on the GPU
 #                    [RANGES=yolo_qat_ranges.npz]: the ranges a QAT run learned instead of a calibration
 #                    [CALIBMETHOD=minmax|percentile|mse CALIBPCT=99.99 CALIBBINS=2048]: minmax (default) takes each tensor's exact range; percentile
@@ -88,6 +91,13 @@ DISTILLWEIGHT ?= 1.0
 CACHE         ?= off
 CACHEGB       ?= 8
 CACHESTAGE    ?= 256
+EMA           ?= False
+EMADECAY      ?= 0.9999
+EMATAU        ?= 2000
+CLIPNORM      ?= 0
+LRSCHED       ?=
+WARMUP        ?= 0
+LRFINAL       ?= 0.01
 # eval only
 PRECISION     ?= f16x2
 ANN           ?= data/$(DATASET)_img_ann.npy
@@ -131,7 +141,10 @@ TRAIN_ARGS = --pre_ckpt $(CKPT) --augmenter $(IAA) --batch_size $(BATCH) --rand_
              --hsv $(HSV) --hsv_hue $(HSVHUE) --hsv_sat $(HSVSAT) --hsv_exposure $(HSVEXP) --hsv_prob $(HSVPROB) \
              --cache $(CACHE) --cache_gb $(CACHEGB) --cache_stage_mb $(CACHESTAGE) --decode $(DECODE) \
              $(if $(TEACHERCKPT),--teacher_ckpt $(TEACHERCKPT) --distill_weight $(DISTILLWEIGHT) $(if $(TEACHER),--teacher_def $(TEACHER)) \
-             $(if $(TEACHERDEPTH),--teacher_depth $(TEACHERDEPTH)))
+             $(if $(TEACHERDEPTH),--teacher_depth $(TEACHERDEPTH))) \
+             $(if $(filter True,$(EMA)),--ema True --ema_decay $(EMADECAY) --ema_tau $(EMATAU)) \
+             $(if $(filter-out 0 0.0,$(CLIPNORM)),--clip_norm $(CLIPNORM)) \
+             $(if $(LRSCHED),--lr_schedule $(LRSCHED) --warmup_steps $(WARMUP) --lr_final $(LRFINAL))
 ifeq ($(GPUS),1)
 LAUNCH = $(PY)
 else

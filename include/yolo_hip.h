@@ -621,6 +621,27 @@ int yk_axpy_f32(long long n, float a, const float *x, float *y, void *stream);  
  * g is multiplied by grad_scale first (1/world_size after a sum all-reduce). */
 int yk_adam_f32(long long n, float *p, const float *g, float *m, float *v, float lr, float decay, long long iterations,
                 float beta1, float beta2, float eps, float grad_scale, void *stream);
+/* The optional parts of the update (the rule is stated in k210_yolo_framework_amd/optim.py).
+ * yk_sumsq_f32: *d_out = sum of x[i]^2, every square (exact) and the whole sum in float64.  Workgroups own tiles of YK_SUMSQ_TILE floats and
+ *   leave one partial each in d_work (yk_sumsq_workspace_bytes, needs no device; 8-byte aligned, contents undefined before and after); a
+ *   finishing launch folds them.  Who adds what depends on n alone and no atomics are used: two calls give the same bits, all zeros give
+ *   +0.0.  Asynchronous on `stream`, nothing allocated, nothing synchronised: capturable.
+ * yk_adam_ex_f32: yk_adam_f32 with two optional parts around adam_kernel's unchanged statements, in one pass.
+ *   d_sumsq (NULL: no clipping): every thread forms c = (float)fmin(1.0, clip_norm / (sqrt(*d_sumsq) + 1e-6)) in double and uses
+ *            (g[i] * grad_scale) * c for the gradient; g is only read.  A NaN sum gives c = 1 (the NaN gradients reach the update), an
+ *            infinite one c = 0.
+ *   ema     (NULL: none): after the update, e = ema[i]; ema[i] = e + ema_omd * (p_new - e), ema_omd = 1 - decay.  Where p_new == e the average
+ *            keeps its bits, and ema_omd = 0 changes nothing.
+ *   With both NULL the stored p, m, v are yk_adam_f32's bit for bit.  16-byte accesses when n % 4 == 0 and every buffer is 16-byte aligned,
+ *   element by element otherwise.
+ * yk_ema_f32: the average's statement alone, ema[i] += ema_omd * (src[i] - ema[i]) in the written order, for buffers Adam does not own.
+ * NULL required pointers, n <= 0, iterations < 0, a negative clip_norm with d_sumsq, a misaligned double pointer: YK_ERR_ARG, nothing launched. */
+#define YK_SUMSQ_TILE 4096
+int yk_sumsq_workspace_bytes(long long n, size_t *bytes);
+int yk_sumsq_f32(const float *x, long long n, double *d_work, double *d_out, void *stream);
+int yk_adam_ex_f32(long long n, float *p, const float *g, float *m, float *v, float *ema, const double *d_sumsq, float lr, float decay,
+                   long long iterations, float beta1, float beta2, float eps, float grad_scale, float clip_norm, float ema_omd, void *stream);
+int yk_ema_f32(long long n, const float *src, float *ema, float ema_omd, void *stream);
 /* Magnitude pruning (tfmot prune_low_magnitude of keras_train.py:59-71) over `nseg` segments of one flat parameter buffer
  * in one call.  Segment s = params[d_offset[s] .. + d_size[s]) (device, int64; d_size >= 1); d_keep[s] = k, clamped to [1, d_size[s]].
  * Outputs per segment: d_threshold[s] = the exact k-th largest |w| (a radix select on the uint32 pattern of |w|: equal to a sort),

@@ -29,6 +29,11 @@ inference plan (engine.Plan, f16x2) on the step's frames, outside the captured g
 one yk_distill_loss_f32 call per output layer (csrc/yk_distill.hip) into that layer's gradient between the detection loss and the backward
 pass, inside the capture.  The validation loss stays the detection loss.  With distill=None nothing is allocated and nothing is launched.
 
+Weight EMA, learning-rate schedule and gradient clipping (optim.py): `Trainer(ema=EmaConfig(...), clip_norm=..., lr_schedule=
+LrSchedule(...))` replace the update's one yk_adam_f32 launch by yk_sumsq_f32 (clipping only) and one yk_adam_ex_f32 launch (csrc/yk_optim.hip),
+outside the captured graph like Adam; the average E of P and the average of the BatchNorm moving statistics are what `export_weights(ema=True)`
+returns.  With the defaults nothing is allocated and apply_update issues yk_adam_f32 as before.
+
 fp32 storage and fp32 MFMA throughout (TF1.14's default for this model)."""
 from __future__ import annotations
 
@@ -69,10 +74,17 @@ class Trainer:
                  obj_thresh: float = 0.7, iou_thresh: float = 0.5, obj_weight: float = 1.0, noobj_weight: float = 1.0,
                  wh_weight: float = 1.0, lr: float = 5e-4, decay: float = 0.0, device: int = 0, process_group=None,
                  world_size: int = 1, use_graph: bool = True, prune=None, qat=None, box_loss: str = 'mse', box_weight: float = 1.0,
-                 distill=None):
+                 distill=None, ema=None, clip_norm: float = 0.0, lr_schedule=None):
         import torch
         if box_loss not in engine.BOX_LOSSES:
             raise ValueError(f'box_loss {box_loss!r}: choose one of ' + ', '.join(repr(k) for k in engine.BOX_LOSSES))
+        if ema is not None and qat is not None:
+            raise engine.YkError('ema= together with qat= is not supported: the learned activation ranges belong to the live weights, not to '
+                                 'their average')
+        if lr_schedule is not None and float(decay) != 0.0:
+            raise engine.YkError(f'lr_schedule= together with decay={decay} would be two learning-rate schedules: pass decay=0')
+        if not float(clip_norm) >= 0.0:
+            raise engine.YkError(f'clip_norm {clip_norm} must not be negative (0 is off)')
         engine.require_gpu()
         self.torch = torch
         self.spec, self.B = spec, int(per_rank_batch)
@@ -105,8 +117,31 @@ class Trainer:
         self.G = torch.zeros_like(self.P)
         self.m = torch.zeros_like(self.P)
         self.v = torch.zeros_like(self.P)
-        self.moving: Dict[str, "torch.Tensor"] = {}
+        # BatchNorm moving statistics: views of one flat buffer, padded like the parameter slots, so that one launch can cover them all.
+        # The tensors of self.moving are never rebound: a captured step holds their pointers
+        self.mslots: Dict[str, tuple] = {}
+        off = 0
+        for l in spec.layers:
+            if l.bn_name:
+                c = l.kernel_shape[3] if l.kind == 'conv' else l.kernel_shape[2]
+                for s in ('/moving_mean', '/moving_variance'):
+                    self.mslots[l.bn_name + s] = (off, c)
+                    off += (c + 7) // 8 * 8
+        self.M = torch.zeros(off, dtype=torch.float32, device=self.dev)
+        self.moving: Dict[str, "torch.Tensor"] = {nm: self.M[o:o + c] for nm, (o, c) in self.mslots.items()}
+        # the optional parts of the update (optim.py).  None / 0: nothing is allocated and nothing is launched.
+        self.ema, self.clip_norm, self.lr_schedule = ema, float(clip_norm), lr_schedule
+        self.E = self.EM = None
+        self.ema_updates = 0
         self.load_weights(weights)
+        if ema is not None:                                          # the average of the weights and of the moving statistics
+            self.E, self.EM = self.P.clone(), self.M.clone()
+            self.ema_moving = {nm: self.EM[o:o + c] for nm, (o, c) in self.mslots.items()}
+        if self.clip_norm:
+            nbytes = C.c_size_t()
+            engine.call('yk_sumsq_workspace_bytes', self.n_params, C.byref(nbytes))
+            self._sq_work = torch.zeros(nbytes.value // 8, dtype=torch.float64, device=self.dev)
+            self._sumsq = torch.zeros(1, dtype=torch.float64, device=self.dev)
         self.counts = [torch.zeros(3, dtype=torch.float32, device=self.dev) for _ in spec.outputs]
         self.saved: Dict[int, dict] = {}
         self.T: Dict[int, "torch.Tensor"] = {}
@@ -153,21 +188,23 @@ class Trainer:
                 for s in ('/gamma', '/beta'):
                     self.view(self.P, l.bn_name + s).copy_(torch.from_numpy(np.asarray(weights[l.bn_name + s], np.float32)))
                 for s in ('/moving_mean', '/moving_variance'):
-                    src = torch.from_numpy(np.asarray(weights[l.bn_name + s], np.float32).copy())
-                    cur = self.moving.get(l.bn_name + s)
-                    if cur is None:
-                        self.moving[l.bn_name + s] = src.to(self.dev)
-                    else:
-                        # IN PLACE: a captured step holds the raw pointer of this tensor (yk_bn_train_fwd updates the moving statistics
-                        # inside the replayed graph); rebinding the name would leave the graph writing a freed buffer while
-                        # export_weights / validate read a tensor nobody updates
-                        cur.copy_(src)
+                    # IN PLACE: a captured step holds the raw pointer of this tensor (yk_bn_train_fwd updates the moving statistics
+                    # inside the replayed graph); rebinding the name would leave the graph writing a freed buffer while
+                    # export_weights / validate read a tensor nobody updates
+                    self.moving[l.bn_name + s].copy_(torch.from_numpy(np.asarray(weights[l.bn_name + s], np.float32).copy()))
+        if self.E is not None:                                       # the average starts again from what was loaded
+            self.E.copy_(self.P)
+            self.EM.copy_(self.M)
 
-    def export_weights(self, quantized: bool = False) -> Dict[str, np.ndarray]:
+    def export_weights(self, quantized: bool = False, ema: bool = False) -> Dict[str, np.ndarray]:
         """Keras-layout arrays again (what keras.models.save_model would hold, keras_train.py:107).  quantized=True (a QAT Trainer): the
-        kernels as the step reads them, fq of the current P over each kernel's own range; everything else as in P."""
+        kernels as the step reads them, fq of the current P over each kernel's own range; everything else as in P.  ema=True (a Trainer
+        with ema=): the averaged weights and the averaged BatchNorm moving statistics, same keys and shapes."""
         out = {}
-        src = self.P
+        if ema and self.E is None:
+            raise engine.YkError('this Trainer was built without a weight average (ema=None)')
+        par, moving = (self.E, self.ema_moving) if ema else (self.P, self.moving)
+        src = par
         if quantized:
             self._need_qat()
             self._qat_weights()
@@ -178,12 +215,12 @@ class Trainer:
             out[l.name + '/kernel'] = (np.transpose(k.reshape(co, kh, kw, ci), (1, 2, 3, 0)) if l.kind == 'conv'
                                        else k.reshape(3, 3, ci)[..., None]).copy()
             if l.use_bias:
-                out[l.name + '/bias'] = self.view(self.P, l.name + '/bias').cpu().numpy().copy()
+                out[l.name + '/bias'] = self.view(par, l.name + '/bias').cpu().numpy().copy()
             if l.bn_name:
                 for s in ('/gamma', '/beta'):
-                    out[l.bn_name + s] = self.view(self.P, l.bn_name + s).cpu().numpy().copy()
+                    out[l.bn_name + s] = self.view(par, l.bn_name + s).cpu().numpy().copy()
                 for s in ('/moving_mean', '/moving_variance'):
-                    out[l.bn_name + s] = self.moving[l.bn_name + s].cpu().numpy().copy()
+                    out[l.bn_name + s] = moving[l.bn_name + s].cpu().numpy().copy()
         return out
 
     def grads(self) -> Dict[str, np.ndarray]:
@@ -570,8 +607,27 @@ class Trainer:
         self.regulariser(add_grad=True)
 
     def apply_update(self) -> None:
-        """keras Adam(lr, decay) on the flat buffers (keras_train.py:73-76); one launch."""
-        self._ck('yk_adam_f32', self.n_params, self.P, self.G, self.m, self.v, self.lr, self.decay, self.iterations, 0.9, 0.999, 1e-7, 1.0)
+        """keras Adam(lr, decay) on the flat buffers (keras_train.py:73-76); one launch.
+        With ema=, clip_norm= or lr_schedule= (optim.py): the learning rate of this iteration from the schedule, the sum of squares of G as
+        the update consumes it (after exchange() and the regulariser's gradient: the same on every rank), then one yk_adam_ex_f32 launch
+        that clips, updates and averages in a single pass over the flat buffers, and one yk_ema_f32 over the BatchNorm moving statistics."""
+        if self.ema is None and not self.clip_norm and self.lr_schedule is None:
+            self._ck('yk_adam_f32', self.n_params, self.P, self.G, self.m, self.v, self.lr, self.decay, self.iterations, 0.9, 0.999, 1e-7, 1.0)
+            self.iterations += 1
+            return
+        self.last_lr = lr = self.lr if self.lr_schedule is None else self.lr_schedule.lr_at(self.iterations)
+        sumsq = None
+        if self.clip_norm:
+            self._ck('yk_sumsq_f32', self.G, self.n_params, self._sq_work, self._sumsq)
+            sumsq = self._sumsq
+        omd = 0.0
+        if self.ema is not None:
+            self.ema_updates += 1
+            omd = self.ema.omd_at(self.ema_updates)
+        self._ck('yk_adam_ex_f32', self.n_params, self.P, self.G, self.m, self.v, self.E, sumsq, lr, self.decay, self.iterations, 0.9, 0.999, 1e-7,
+                 1.0, self.clip_norm, omd)
+        if self.ema is not None and self.M.numel():
+            self._ck('yk_ema_f32', self.M.numel(), self.M, self.EM, omd)
         self.iterations += 1
 
     # ------------------------------------------------------------------ knowledge distillation (DESIGN.md 3.18)
@@ -652,6 +708,8 @@ class Trainer:
         """P *= mask, in place (tfmot's weight assignment at the start of a step and its on_epoch_end)."""
         self._need_prune()
         self._ck('yk_mask_apply_f32', self.P, self._pr_mask, self.n_params)
+        if self.E is not None:                                       # the exported average is as sparse as the live weights
+            self._ck('yk_mask_apply_f32', self.E, self._pr_mask, self.n_params)
 
     def prune_step(self) -> None:
         """What pruning does at the start of step `iterations`: new masks on an update step, then P *= mask.  Outside the captured
@@ -811,13 +869,23 @@ class Trainer:
             else:
                 import torch.distributed as dist
                 dist.all_reduce(data, op=dist.ReduceOp.SUM, group=self.pg)
-        vals = torch.cat([data, r['reg'].view(1)]).cpu().numpy()
+        tail = [r['reg'].view(1)]
+        if self.clip_norm:                                            # the float64 sum of squares rides along as two float32 words: one transfer
+            tail.append(self._sumsq.view(torch.float32))
+        vals = torch.cat([data] + tail).cpu().numpy()
+        extra = {}
+        if self.lr_schedule is not None:
+            extra['lr'] = self.last_lr
+        if self.clip_norm:
+            extra['grad_norm'] = float(np.sqrt(vals[-2:].copy().view(np.float64)[0]))      # the norm BEFORE clipping
+            vals = vals[:-2]
         out = dict(loss=float(vals[0] + vals[-1]), data_loss=float(vals[0]), reg_loss=float(vals[-1]))
         if iou_box:
             out['box'] = float(vals[1])
         if self.distill is not None:                                  # loss is what the step descends: detection + distillation + regulariser
             out['distill'] = float(vals[-2])
             out['loss'] = float(vals[0] + vals[-2] + vals[-1])
+        out.update(extra)
         return out
 
     def precision_recall(self):

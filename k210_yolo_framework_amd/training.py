@@ -50,7 +50,15 @@ decoded once and kept in `--cache_gb` GB of device memory; what does not fit pas
 time.  The loop owns the cache, every epoch's `InputPipeline(cache=...)` composes its batches from it by one launch - the batches of
 `--cache off`, bit for bit - and the epoch line gains `cache hits/misses, GB used/capacity`.  `--decode gpu` (`DECODE=gpu`, with or without
 the cache) has baseline JPEG files decoded on the GPU, directly into that memory: `make detect DECODE=gpu`'s pixels, not PIL's.  Validation
-is not cached."""
+is not cached.
+
+`--ema True`, `--clip_norm N`, `--lr_schedule cosine|step|constant` (`make train EMA=True EMADECAY=0.9999 EMATAU=2000 CLIPNORM=10.0
+LRSCHED=cosine WARMUP=N LRFINAL=0.01`; not in the reference, optim.py): an exponential moving average of the weights and of the
+BatchNorm moving statistics, which validation scores (`(ema)` on the epoch line) and rank 0 saves as `yolo_ema_model.h5` / `.npz` (with
+`--is_prune True` `yolo_prune_ema_model.*`, as sparse as the live one) beside the usual checkpoint of the live weights; global-norm gradient
+clipping, the step line then shows `gnorm`, the norm before clipping; a learning-rate schedule with linear warmup over the run's
+`train_epoch_step x max_nrof_epochs` steps (capped by `--max_steps`), the step line then shows `lr`.  All off by default: then the update is
+the reference's Adam call and no line changes."""
 from __future__ import annotations
 
 import argparse
@@ -142,7 +150,8 @@ def main(args, train_set, class_num, pre_ckpt, model_def, depth_multiplier, is_a
          frequency=100, synthetic=0, max_steps=0, is_qat='False', qat_momentum=0.99, qat_observe=8, val_map='False', val_map_obj=0.05,
          box_loss='mse', box_weight=1.0, is_mosaic='False', mosaic_prob=1.0, mosaic_off_epochs=0, is_hsv='False', hsv_hue=0.1, hsv_sat=1.5,
          hsv_exposure=1.5, hsv_prob=1.0, teacher_ckpt='', teacher_def=None, teacher_depth=None, distill_weight=1.0, cache='off',
-         cache_gb=8.0, cache_stage_mb=256, decode='pil'):
+         cache_gb=8.0, cache_stage_mb=256, decode='pil', is_ema='False', ema_decay=0.9999, ema_tau=2000.0, clip_norm=0.0, lr_schedule='none',
+         warmup_steps=0, lr_final=0.01):
     import torch
     from .train import Trainer
     prune = is_prune == 'True'
@@ -175,6 +184,16 @@ def main(args, train_set, class_num, pre_ckpt, model_def, depth_multiplier, is_a
         raise engine.YkError(f'--cache_gb {cache_gb}: a size in GB, not negative')
     if (cached or decode == 'gpu') and not (np.isfinite(float(cache_stage_mb)) and float(cache_stage_mb) > 0.0):
         raise engine.YkError(f'--cache_stage_mb {cache_stage_mb}: a size in MB, positive')
+    ema = is_ema == 'True'
+    if ema and qat:
+        raise engine.YkError('--ema True together with --qat True is not supported: the learned activation ranges belong to the live weights')
+    if not (np.isfinite(float(clip_norm)) and float(clip_norm) >= 0.0):
+        raise engine.YkError(f'--clip_norm {clip_norm}: the largest gradient norm, not negative (0 is off)')
+    if lr_schedule not in ('none', 'constant', 'cosine', 'step'):
+        raise engine.YkError(f'--lr_schedule {lr_schedule}: none, constant, cosine or step')
+    scheduled = lr_schedule != 'none'
+    if scheduled and float(learning_rate_decay_factor) != 0.0:
+        raise engine.YkError(f'--lr_schedule {lr_schedule} together with --learning_rate_decay_factor {learning_rate_decay_factor} would be two schedules')
     distill = teacher_ckpt not in (None, 'None', '', '""')
     if distill and not (np.isfinite(float(distill_weight)) and float(distill_weight) >= 0.0):
         raise engine.YkError(f'--distill_weight {distill_weight}: a finite weight, not negative')
@@ -198,6 +217,8 @@ def main(args, train_set, class_num, pre_ckpt, model_def, depth_multiplier, is_a
             raise engine.YkError('--teacher_ckpt (knowledge distillation, distill.py) runs the teacher and its loss in HIP kernels: no HIP device') from e
         if cached:
             raise engine.YkError('--cache gpu (the picture cache, cache.py) keeps the decoded training pictures in device memory: no HIP device') from e
+        if ema or scheduled or float(clip_norm):
+            raise engine.YkError('--ema / --clip_norm / --lr_schedule (optim.py) run in HIP kernels on the training step: no HIP device') from e
         if decode == 'gpu':
             raise engine.YkError('--decode gpu (baseline JPEG files decoded by yk_jpeg_decode_ragged_u8) runs in the GPU input pipeline: no HIP device') from e
         raise
@@ -260,9 +281,24 @@ def main(args, train_set, class_num, pre_ckpt, model_def, depth_multiplier, is_a
     if qat:
         from .qat import QatConfig
         qat_cfg = QatConfig(qat_momentum)
+    ema_cfg = lr_cfg = None
+    try:
+        if ema:
+            from .optim import EmaConfig
+            ema_cfg = EmaConfig(float(ema_decay), float(ema_tau))
+        if scheduled:                                                            # the run's length: every epoch's steps, capped by --max_steps
+            from .optim import LrSchedule
+            total = (len(h.train_list) // batch_size) * max_nrof_epochs
+            total = min(total, int(max_steps)) if max_steps else total
+            lr_cfg = LrSchedule(lr_schedule, float(init_learning_rate), max(total, 1), warmup_steps=int(warmup_steps), final_frac=float(lr_final))
+    except ValueError as e:
+        raise engine.YkError(f'--ema_decay / --ema_tau / --lr_schedule / --warmup_steps / --lr_final: {e}') from e
+    if rank == 0 and (ema or scheduled or float(clip_norm)):
+        print(INFO, f'ema is {ema_cfg}, clip_norm {float(clip_norm)}, lr schedule {lr_cfg}')
     tr = Trainer(spec, weights, h.anchors, per_rank, obj_thresh=obj_thresh, iou_thresh=iou_thresh, obj_weight=obj_weight,
                  noobj_weight=noobj_weight, wh_weight=wh_weight, lr=init_learning_rate, decay=learning_rate_decay_factor, device=local,
-                 world_size=world, prune=schedule, qat=qat_cfg, box_loss=box_loss, box_weight=box_weight, distill=distill_cfg)
+                 world_size=world, prune=schedule, qat=qat_cfg, box_loss=box_loss, box_weight=box_weight, distill=distill_cfg,
+                 ema=ema_cfg, clip_norm=float(clip_norm), lr_schedule=lr_cfg)
     from .mosaic import MosaicConfig
     from .pipeline import InputPipeline
     if rank == 0:
@@ -303,7 +339,8 @@ def main(args, train_set, class_num, pre_ckpt, model_def, depth_multiplier, is_a
                 if rank == 0 and (seen % 10 == 0 or seen == 1):
                     pr = tr.precision_recall()
                     print(f'epoch {epoch + 1} step {seen}: loss {out["loss"]:.4f} ' + (f'{box_loss} {out["box"]:.4f} ' if iou_box else '') +
-                          (f'distill {out["distill"]:.4f} ' if distill else '') +
+                          (f'distill {out["distill"]:.4f} ' if distill else '') + (f'lr {out["lr"]:.3g} ' if scheduled else '') +
+                          (f'gnorm {out["grad_norm"]:.4g} ' if float(clip_norm) else '') +
                           ' '.join(f'l{i + 1}_p {p:.3f} l{i + 1}_r {r:.3f}' for i, (p, r) in enumerate(pr)), flush=True)
                 if max_steps and steps >= max_steps:
                     break
@@ -317,14 +354,14 @@ def main(args, train_set, class_num, pre_ckpt, model_def, depth_multiplier, is_a
         val = vmap = None
         if rank == 0 and len(h.test_list) >= per_rank:
             if val_map == 'True':                                               # opt-in: the pass also scores its detections
-                val, vmap = validate(tr, h, spec, per_rank, rank, map_obj=val_map_obj)
+                val, vmap = validate(tr, h, spec, per_rank, rank, map_obj=val_map_obj, ema=ema)
             else:
-                val = validate(tr, h, spec, per_rank, rank)
+                val = validate(tr, h, spec, per_rank, rank, ema=ema)
         if rank == 0:
             print(f'epoch {epoch + 1}: {seen} steps, mean loss {run / max(seen, 1):.4f}, ' +
                   (f'mean {box_loss} {run_box / max(seen, 1):.4f}, ' if iou_box else '') +
                   (f'mean distill {run_kd / max(seen, 1):.4f}, ' if distill else '') +
-                  (f'val_loss {val:.4f}, ' if val is not None else '') + f'{time.time() - t0:.1f}s, input pipeline {pipe_rate:.0f} images/s/rank' +
+                  (f'val_loss {val:.4f}{" (ema)" if ema else ""}, ' if val is not None else '') + f'{time.time() - t0:.1f}s, input pipeline {pipe_rate:.0f} images/s/rank' +
                   (f', val_mAP {vmap:.4f}' if vmap is not None else '') + (cache_line(pic_cache) if cached else ''), flush=True)
         for c in tr.counts:
             c.zero_()                                                           # Keras resets metrics every epoch
@@ -346,7 +383,14 @@ def main(args, train_set, class_num, pre_ckpt, model_def, depth_multiplier, is_a
             if flagged:
                 print(ERROR, f' QAT met non-finite values (NaN or infinity) in {", ".join(flagged)}; yolo_qat_ranges.npz holds the ranges of the finite ones')
             np.savez(log_dir / 'yolo_qat_ranges.npz', **{k: np.asarray(v, np.float32) for k, v in tr.qat_ranges(check=False).items()})
+        if ema:                                                                 # beside the live checkpoint: the averaged weights and statistics
+            ema_stem = 'yolo_prune_ema_model' if prune else 'yolo_ema_model'
+            averaged = tr.export_weights(ema=True)
+            keras_io.save_keras_model(spec, averaged, str(log_dir / f'{ema_stem}.h5'))
+            np.savez(log_dir / f'{ema_stem}.npz', **averaged)
         print()
+        if ema:
+            print(INFO, f' Save EMA Model as {str(log_dir / (ema_stem + ".h5"))}')
         print(INFO, f' Save QAT Model as {str(ckpt)} (ranges: yolo_qat_ranges.npz)' if qat else
               f' Save Pruned Model as {str(ckpt)}' if prune else f' Save Model as {str(ckpt)}')
     if dist is not None:
@@ -387,11 +431,12 @@ def sparsity_line(tr, spec, epoch: int) -> str:
             ' '.join(f'{nm} {rep[nm + "/kernel"]["sparsity"]:.4f}' for nm in heads))
 
 
-def validate(tr, h: Helper, spec, batch: int, rank: int, map_obj=None):
+def validate(tr, h: Helper, spec, batch: int, rank: int, map_obj=None, ema: bool = False):
     """validation_data pass (keras_train.py:96-98): inference-mode forward on the engine (the f16x2 mode, the boundary default) + the same loss.
     map_obj (`--val_map True`): the plan's outputs are also decoded on the GPU at this objectness threshold (NMS and match IoU = the run's
     iou_thresh) and scored in device memory by map_gpu.MapEvaluator against the validation boxes in network-input pixels - the letterboxed
-    frame is the image; -> (val_loss, val_mAP) instead of val_loss."""
+    frame is the image; -> (val_loss, val_mAP) instead of val_loss.
+    ema (`--ema True`): the plan is built from the averaged weights, tr.export_weights(ema=True), for the loss and the mAP alike."""
     import torch
     tot, n = 0.0, 0
     e = 5 + spec.class_num
@@ -401,7 +446,7 @@ def validate(tr, h: Helper, spec, batch: int, rank: int, map_obj=None):
         from .map_gpu import MapEvaluator
         ev = MapEvaluator(spec.class_num, tr.hyper['iou_thresh'], device=tr.dev.index or 0)
         cfg = engine.make_decode_cfg(h.anchors, spec.class_num, spec.in_hw, spec.out_hw())
-    with engine.Plan(spec, tr.export_weights(), max_batch=batch, device=tr.dev.index or 0) as plan:   # freed on exit, every epoch
+    with engine.Plan(spec, tr.export_weights(ema=True) if ema else tr.export_weights(), max_batch=batch, device=tr.dev.index or 0) as plan:   # freed on exit, every epoch
         for x, ys, *boxes in batches(h, h.test_list, batch, np.random.default_rng(0), shuffle=False, with_boxes=ev is not None):
             plan.run_f32(torch.from_numpy(x).cuda())
             if ev is not None:
@@ -474,6 +519,15 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument('--cache_stage_mb', type=float, default=256, help='size of one staging region: the uncached pictures of ONE batch must fit')
     p.add_argument('--decode', type=str, choices=['pil', 'gpu'], default='pil',
                    help='who decodes the training pictures: PIL on the thread pool, or (baseline JPEG files) the GPU, into the cache')
+    p.add_argument('--ema', type=str, choices=['True', 'False'], default='False',
+                   help='keep an exponential moving average of the weights; it is validated and saved as yolo_ema_model (DESIGN.md 3.21)')
+    p.add_argument('--ema_decay', type=float, default=0.9999, help='decay of the weight average')
+    p.add_argument('--ema_tau', type=float, default=2000.0, help='updates over which the decay ramps up: decay (1 - exp(-updates / tau)); 0 = no ramp')
+    p.add_argument('--clip_norm', type=float, default=0.0, help='clip the global gradient norm to this value; 0 = off')
+    p.add_argument('--lr_schedule', type=str, choices=['none', 'constant', 'cosine', 'step'], default='none',
+                   help='learning-rate schedule over the whole run, from --init_learning_rate; none = Keras lr / (1 + decay t) as before')
+    p.add_argument('--warmup_steps', type=int, default=0, help='linear warmup over the first N steps (with --lr_schedule)')
+    p.add_argument('--lr_final', type=float, default=0.01, help='cosine: the last learning rate as a fraction of the first')
     return p
 
 
@@ -485,7 +539,8 @@ def cli(argv=None):
                 a.prune_initial_sparsity, a.prune_final_sparsity, a.prune_end_epoch, a.prune_frequency, a.synthetic, a.max_steps,
                 a.qat, a.qat_momentum, a.qat_observe, a.val_map, a.val_map_obj, a.box_loss, a.box_weight, a.mosaic, a.mosaic_prob,
                 a.mosaic_off_epochs, a.hsv, a.hsv_hue, a.hsv_sat, a.hsv_exposure, a.hsv_prob, a.teacher_ckpt, a.teacher_def, a.teacher_depth,
-                a.distill_weight, a.cache, a.cache_gb, a.cache_stage_mb, a.decode)
+                a.distill_weight, a.cache, a.cache_gb, a.cache_stage_mb, a.decode, a.ema, a.ema_decay, a.ema_tau, a.clip_norm, a.lr_schedule,
+                a.warmup_steps, a.lr_final)
 
 
 if __name__ == '__main__':
