@@ -52,6 +52,13 @@ IOUTHRESH     ?= 0.5
 # inference, detect, eval: the decode's suppression rule, hard | linear | gaussian | diou (train VALMAP=True stays on hard)
 NMS           ?= hard
 NMSSIGMA      ?= 0.5
+# detect, eval: sliced inference, TILES=NXxNY runs every picture as overlapping tiles (+ the whole picture with TILEFULL=True) and merges
+# the rows on the GPU (k210_yolo_framework_amd/tiles.py); empty = off
+TILES         ?=
+TILEOVERLAP   ?= 0.2
+TILEFULL      ?= True
+TILEMATCH     ?= ios
+TILETHRESH    ?= 0.5
 CKPT          ?= ""
 IMG           ?= data/synthetic_320x224.jpg
 # training only
@@ -131,6 +138,7 @@ NET_ARGS   = --train_set $(DATASET) --class_num $(CLSNUM) --model_def $(MODEL) -
              --image_size $(IMGSIZE) --output_size $(OUTSIZE) --obj_thresh $(OBJTHRESH) --iou_thresh $(IOUTHRESH)
 # (nothing for the default rule: the command lines of the three targets stay what they were)
 NMS_ARGS   = $(if $(filter-out hard,$(NMS)),--nms $(NMS) --nms_sigma $(NMSSIGMA))
+TILE_ARGS  = $(if $(TILES),--tiles $(TILES) --tile_overlap $(TILEOVERLAP) --tile_full $(TILEFULL) --tile_match $(TILEMATCH) --tile_thresh $(TILETHRESH))
 TRAIN_ARGS = --pre_ckpt $(CKPT) --augmenter $(IAA) --batch_size $(BATCH) --rand_seed 3 --max_nrof_epochs $(MAXEP) \
              --init_learning_rate $(ILR) --learning_rate_decay_factor $(LRDECAYFACTOR) --obj_weight $(OBJWEIGHT) \
              --noobj_weight $(NOOBJWEIGHT) --wh_weight $(WHWEIGHT) --vaildation_split $(SPLITFACTOR) --log_dir log \
@@ -180,11 +188,11 @@ kmodel:
 eval:
 	$(PY) keras_eval.py $(CKPT) --train_set $(DATASET) --class_num $(CLSNUM) --model_def $(MODEL) --depth_multiplier $(DEPTHMUL) \
 		--image_size $(IMGSIZE) --output_size $(OUTSIZE) --iou_thresh $(IOUTHRESH) --precision $(PRECISION) --obj_thresh $(EVALOBJ) \
-		--voc07 $(VOC07) $(if $(filter-out 0,$(SYNTHETIC)),--synthetic $(SYNTHETIC),--ann $(ANN)) $(if $(METRIC),--metric $(METRIC)) $(NMS_ARGS)
+		--voc07 $(VOC07) $(if $(filter-out 0,$(SYNTHETIC)),--synthetic $(SYNTHETIC),--ann $(ANN)) $(if $(METRIC),--metric $(METRIC)) $(NMS_ARGS) $(TILE_ARGS)
 
 # every picture of SRC (a folder or a text list) -> OUTDIR/detections.json + OUTDIR/<stem>_res.jpg; batches of BATCH pictures of any sizes
 detect:
-	$(PY) keras_detect.py $(CKPT) $(SRC) --out_dir $(OUTDIR) --draw $(DRAW) --decode $(DECODE) --encode $(ENCODE) --quality $(QUALITY) --batch $(BATCH) --precision $(PRECISION) $(NET_ARGS) $(NMS_ARGS)
+	$(PY) keras_detect.py $(CKPT) $(SRC) --out_dir $(OUTDIR) --draw $(DRAW) --decode $(DECODE) --encode $(ENCODE) --quality $(QUALITY) --batch $(BATCH) --precision $(PRECISION) $(NET_ARGS) $(NMS_ARGS) $(TILE_ARGS)
 
 # reference Makefile:78-87 (same flags; --is_random True as there)
 anchors:

@@ -251,6 +251,30 @@ int yk_decode_py_packed_nms(const yk_decode_cfg_t *cfg, const float *const *d_pr
                             float obj_thresh, float iou_thresh, int max_out, float *rows, int32_t *offsets, int32_t *rows_index,
                             float *d_dets, int32_t *d_counts, void *stream, int nms_method, float nms_sigma);
 
+/* ---- sliced inference: the rows of the tile frames of a picture merged into one row set (k210_yolo_framework_amd/tiles.py states the
+ * rule).  d_dets [n_tiles][class_num*max_out][6] and d_counts [n_tiles] as yk_decode_py* leaves them (counts are clamped to
+ * [0, class_num*max_out]); d_origin [n_tiles][2] float (y0, x0) of each tile in its picture; d_first [n_pics + 1] int32: the tiles of
+ * picture p are d_first[p] .. d_first[p+1] - 1 (contiguous; their number may differ between pictures; a value outside [0, n_tiles] is
+ * clamped, a descending pair is an empty picture).  Candidates of a picture: every row of its tiles, tile by tile, in row order, translated by
+ * ONE float add per coordinate (top, bottom += y0; left, right += x0).  A row whose class is not exactly one of 0 .. class_num - 1, or whose
+ * score is not above -inf, is dropped.  Per (picture, class) a greedy hard NMS: the live candidate with the largest score (ties: the lowest
+ * candidate index) is kept, every live candidate whose match with it is > thresh is retired, at most max_out kept.
+ *   YK_MATCH_IOU  the IoU of yk_decode_py's own NMS        YK_MATCH_IOS  the same intersection / the smaller area (not positive: no match)
+ * d_out [n_pics][class_num*max_out][6] (class-major ascending, score-descending within a class) and d_out_counts [n_pics]: the padded form
+ * again, so yk_draw_dets_u8, yk_map_append_padded and the copies downstream take it unchanged; rows past the count are not written.
+ * One wavefront per (picture, class); a class's candidates are staged in LDS when at most yk_merge_tiles_lds_candidates(...) of them exist
+ * and are walked in global memory (per-stream scratch: 8 bytes per input row) otherwise - no bound on tiles * max_out other than memory and
+ * n_tiles * class_num * max_out < 2^31.  Two launches and one 4-byte-per-picture fill on `stream`; can be recorded in a graph once the
+ * stream's scratch has been sized by an eager call of the same size.  The tiles of different pictures must not overlap.  A NULL pointer,
+ * n_tiles <= 0, n_pics <= 0, class_num <= 0, max_out <= 0, a thresh that is NaN, an unknown metric, or 2^31 or more input or output rows:
+ * YK_ERR_ARG with the argument named in yk_last_error, nothing launched. */
+#define YK_MATCH_IOU 0
+#define YK_MATCH_IOS 1
+int yk_merge_tiles(const float *d_dets, const int32_t *d_counts, const float *d_origin, const int32_t *d_first, int n_tiles, int n_pics,
+                   int class_num, int max_out, float thresh, int metric, float *d_out, int32_t *d_out_counts, void *stream);
+/* Candidates of one (picture, class) that yk_merge_tiles with these sizes stages in LDS on the current device; more take the global path. */
+int yk_merge_tiles_lds_candidates(int n_tiles, int n_pics, int max_out);
+
 /* ---- a step as one hipGraph (the kpu_run_kmodel(..., dma, ai_done_cb) shape of main.c:303-311: submit once, get called back) ----
  * Everything issued on `stream` (a created stream, not NULL) between yk_graph_begin and yk_graph_end - yk_run_*, yk_decode_py*,
  * yk_letterbox_u8, yk_memcpy_async - is recorded, not executed; yk_graph_launch replays the recording with ONE host call.
@@ -336,6 +360,27 @@ int yk_letterbox_ragged_params(yk_ragged_row_t *h_table, int n, int dst_h, int d
  * zeros and nothing of d_src is read for it.  Can be recorded in a graph. */
 int yk_letterbox_ragged_u8(const uint8_t *d_src, size_t src_bytes, const yk_ragged_row_t *d_table, int n, uint8_t *d_dst, int dst_h,
                            int dst_w, void *stream);
+/* ---- sliced inference: tiles of the pictures of a ragged batch as frames (k210_yolo_framework_amd/tiles.py) ------
+ * A tile is a sub-rectangle of a packed picture: h rows of w pixels, the first at byte `offset` of the packed buffer, consecutive rows
+ * `stride` bytes apart (3 * the parent picture's width; stride == 3*w is a whole picture). */
+typedef struct yk_tile_row {
+    uint64_t offset;    /* byte offset of the tile's first pixel in the packed buffer */
+    int32_t h, w;       /* the tile's size */
+    int64_t stride;     /* bytes per row of the parent picture */
+    double scale;       /* letterbox of this tile into dst_h x dst_w: yk_letterbox_tiles_params fills these three */
+    int32_t tx, ty;
+} yk_tile_row_t;        /* 40 bytes, no padding */
+/* HOST helper: fills scale, tx, ty of n rows in host memory with the arithmetic yk_letterbox_ragged_params uses for (h, w) -> (dst_h, dst_w).
+ * A row with h <= 0 or w <= 0, a NULL table, n <= 0 or a non-positive dst size: YK_ERR_ARG.  Needs no device. */
+int yk_letterbox_tiles_params(yk_tile_row_t *h_table, int n, int dst_h, int dst_w);
+/* One launch for all tiles (one thread per output pixel): d_dst [n][dst_h][dst_w][3]; frame t equals yk_letterbox_u8 on a contiguous copy of
+ * tile t alone, bit for bit - the same per-pixel arithmetic, and a tap outside the TILE reads 0, not the parent's neighbouring pixel.
+ * d_table is DEVICE memory: NULL pointers, n <= 0, src_bytes == 0 and non-positive dst sizes are YK_ERR_ARG here, refusing bad rows is the
+ * caller's job (engine.letterbox_tiles_u8 does it on the host table).  The kernel does not trust the table either: the frame of a row
+ * with h <= 0, w <= 0, stride < 3*w or offset + (h-1)*stride + 3*w > src_bytes is written as zeros and nothing of d_src is read for it.
+ * Can be recorded in a graph. */
+int yk_letterbox_tiles_u8(const uint8_t *d_src, size_t src_bytes, const yk_tile_row_t *d_table, int n, uint8_t *d_dst, int dst_h,
+                          int dst_w, void *stream);
 /* ---- mosaic: one training frame from four pictures (k210_yolo_framework_amd/mosaic.py) ------
  * A sample is four table rows in quadrant order - 0 top left [0,cx) x [0,cy), 1 top right [cx,W) x [0,cy), 2 bottom left, 3 bottom right -
  * and a seam (cx, cy).  Output pixel (x, y) is the letterbox pixel (yk_letterbox_u8's arithmetic, unchanged: truncating cast, taps outside

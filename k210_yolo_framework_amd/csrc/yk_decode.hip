@@ -61,19 +61,6 @@ __global__ void __launch_bounds__(256) decode_py_kernel(decode_args a, int batch
     boxes[(size_t)b * ntot + g] = make_float4((cy - hy) * im_h, (cx - hx) * im_w, (cy + hy) * im_h, (cx + hx) * im_w);
 }
 
-// TF 1.14 non_max_suppression_op.cc IOU on (y1,x1,y2,x2)
-__device__ __forceinline__ float tf_iou(const float4 &i, const float4 &j) {
-    const float ymin_i = fminf(i.x, i.z), xmin_i = fminf(i.y, i.w), ymax_i = fmaxf(i.x, i.z), xmax_i = fmaxf(i.y, i.w);
-    const float ymin_j = fminf(j.x, j.z), xmin_j = fminf(j.y, j.w), ymax_j = fmaxf(j.x, j.z), xmax_j = fmaxf(j.y, j.w);
-    const float area_i = (ymax_i - ymin_i) * (xmax_i - xmin_i);
-    const float area_j = (ymax_j - ymin_j) * (xmax_j - xmin_j);
-    if (area_i <= 0.f || area_j <= 0.f) return 0.f;
-    const float iy0 = fmaxf(ymin_i, ymin_j), ix0 = fmaxf(xmin_i, xmin_j);
-    const float iy1 = fminf(ymax_i, ymax_j), ix1 = fminf(xmax_i, xmax_j);
-    const float inter = fmaxf(iy1 - iy0, 0.f) * fmaxf(ix1 - ix0, 0.f);
-    return inter / (area_i + area_j - inter);
-}
-
 // grid (C, batch), one wavefront.  sel_g/sel_s: [batch][C][max_out]; cnt: [batch][C]
 // MAXC: LDS capacity in candidates.  1 088 (26 KB) covers the 224x320 heads (1 050 boxes) and leaves the CU's LDS to the conv kernels
 // of other batches in flight; 2 048 (48 KB) otherwise.

@@ -19,6 +19,20 @@ struct yk_cand_lds {
     float4 box[YK_NMS_MAXC];
 };
 
+// TF 1.14 non_max_suppression_op.cc IOU on (y1,x1,y2,x2): the match of the Python-mode NMS (yk_decode.hip) and of the cross-tile merge
+// (yk_tiles.hip); both units are built with -ffp-contract=off
+__device__ __forceinline__ float tf_iou(const float4 &i, const float4 &j) {
+    const float ymin_i = fminf(i.x, i.z), xmin_i = fminf(i.y, i.w), ymax_i = fmaxf(i.x, i.z), xmax_i = fmaxf(i.y, i.w);
+    const float ymin_j = fminf(j.x, j.z), xmin_j = fminf(j.y, j.w), ymax_j = fmaxf(j.x, j.z), xmax_j = fmaxf(j.y, j.w);
+    const float area_i = (ymax_i - ymin_i) * (xmax_i - xmin_i);
+    const float area_j = (ymax_j - ymin_j) * (xmax_j - xmin_j);
+    if (area_i <= 0.f || area_j <= 0.f) return 0.f;
+    const float iy0 = fmaxf(ymin_i, ymin_j), ix0 = fmaxf(xmin_i, xmin_j);
+    const float iy1 = fminf(ymax_i, ymax_j), ix1 = fminf(xmax_i, xmax_j);
+    const float inter = fmaxf(iy1 - iy0, 0.f) * fmaxf(ix1 - ix0, 0.f);
+    return inter / (area_i + area_j - inter);
+}
+
 // arg-max over (score desc, idx asc) across the wave; score == -INF means "not a candidate".
 __device__ __forceinline__ void yk_wave_argmax(float &best, int &bidx, int &bpos) {
 #pragma unroll

@@ -14,16 +14,17 @@
 // The per-image max normalisation that follows (utils.py:405) is fused into the stem conv (yk_run_u8).
 #include "yk_common.h"
 
-// One letterboxed pixel (x, y) of the network tensor from source frame `im` [sh][sw][3]: the arithmetic above, truncating cast.
-__device__ __forceinline__ void letterbox_px(const uint8_t *__restrict__ im, int sh, int sw, double scale, int tx, int ty, int x, int y,
-                                             uint8_t out[3]) {
+// One letterboxed pixel (x, y) of the network tensor from source frame `im`, sh rows of sw pixels `stride` bytes apart: the arithmetic above,
+// truncating cast.
+__device__ __forceinline__ void letterbox_px(const uint8_t *__restrict__ im, int sh, int sw, size_t stride, double scale, int tx, int ty, int x,
+                                             int y, uint8_t out[3]) {
     const double inv = 1.0 / scale;
     const double c = inv * (double)x + (-((double)tx * inv)), r = inv * (double)y + (-((double)ty * inv));
     const double minc_f = floor(c), minr_f = floor(r);
     const int minc = (int)minc_f, minr = (int)minr_f, maxc = (int)ceil(c), maxr = (int)ceil(r);
     const double dc = c - minc_f, dr = r - minr_f;
     auto px = [&](int yy, int xx, int ch) -> double {
-        return (yy >= 0 && yy < sh && xx >= 0 && xx < sw) ? (double)im[((size_t)yy * sw + xx) * 3 + ch] : 0.0;
+        return (yy >= 0 && yy < sh && xx >= 0 && xx < sw) ? (double)im[(size_t)yy * stride + (size_t)xx * 3 + ch] : 0.0;
     };
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch) {
@@ -31,6 +32,12 @@ __device__ __forceinline__ void letterbox_px(const uint8_t *__restrict__ im, int
         const double bottom = (1.0 - dc) * px(maxr, minc, ch) + dc * px(maxr, maxc, ch);
         out[ch] = (uint8_t)((1.0 - dr) * top + dr * bottom);    // astype('uint8'): truncation
     }
+}
+
+// ... from a contiguous frame [sh][sw][3]
+__device__ __forceinline__ void letterbox_px(const uint8_t *__restrict__ im, int sh, int sw, double scale, int tx, int ty, int x, int y,
+                                             uint8_t out[3]) {
+    letterbox_px(im, sh, sw, (size_t)sw * 3, scale, tx, ty, x, y, out);
 }
 
 __global__ void __launch_bounds__(256) letterbox_u8_kernel(const uint8_t *__restrict__ src, int batch, int sh, int sw,
@@ -129,6 +136,71 @@ extern "C" int yk_letterbox_ragged_u8(const uint8_t *d_src, size_t src_bytes, co
     for (int base = 0; base < n; base += 65535) {                                 // grid.y holds at most 65535 pictures
         const int m = n - base < 65535 ? n - base : 65535;
         hipLaunchKernelGGL(letterbox_ragged_u8_kernel, dim3((unsigned)((per + 255) / 256), (unsigned)m), dim3(256), 0, (hipStream_t)stream,
+                           d_src, src_bytes, d_table + base, d_dst + (size_t)base * per * 3, dst_h, dst_w);
+    }
+    YK_HIP(hipGetLastError());
+    return YK_OK;
+}
+
+// ---- the same letterbox for TILES of the pictures of a ragged batch (sliced inference: k210_yolo_framework_amd/tiles.py): a
+// tile is h rows of w pixels `stride` bytes apart, so letterbox_px reads it in place and its bounds are the tile's - a tap outside the tile
+// reads 0, not the parent's neighbouring pixel, and frame t is yk_letterbox_u8 of a contiguous copy of the crop, bit for bit.
+__global__ void __launch_bounds__(256) letterbox_tiles_u8_kernel(const uint8_t *__restrict__ src, size_t src_bytes,
+                                                                 const yk_tile_row_t *__restrict__ table, uint8_t *__restrict__ dst, int dh,
+                                                                 int dw) {
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t per = (size_t)dh * dw;
+    if (idx >= per) return;
+    const yk_tile_row_t row = table[blockIdx.y];
+    const int x = (int)(idx % dw), y = (int)(idx / dw);
+    uint8_t v[3] = {0, 0, 0};
+    // a row the host should have refused: nothing of src is read for it.  Its last byte is offset + (h-1)*stride + 3*w - 1; tested by
+    // division, so that no product can overflow
+    bool ok = row.h > 0 && row.w > 0 && row.stride >= (int64_t)3 * row.w && row.offset <= src_bytes;
+    if (ok) {
+        const size_t room = src_bytes - row.offset, last = (size_t)3 * row.w, st = (size_t)row.stride, rows = (size_t)(row.h - 1);
+        ok = last <= room && (rows == 0 || st <= (room - last) / rows);
+    }
+    if (ok) letterbox_px(src + row.offset, row.h, row.w, (size_t)row.stride, row.scale, row.tx, row.ty, x, y, v);
+    uint8_t *o = dst + ((size_t)blockIdx.y * per + idx) * 3;
+    o[0] = v[0];
+    o[1] = v[1];
+    o[2] = v[2];
+}
+
+extern "C" int yk_letterbox_tiles_params(yk_tile_row_t *h_table, int n, int dst_h, int dst_w) {
+    if (!h_table || n <= 0 || dst_h <= 0 || dst_w <= 0) {
+        yk_set_error("yk_letterbox_tiles_params: bad argument");
+        return YK_ERR_ARG;
+    }
+    for (int i = 0; i < n; ++i)
+        if (h_table[i].h <= 0 || h_table[i].w <= 0) {
+            yk_set_error("yk_letterbox_tiles_params: row %d is %d x %d", i, (int)h_table[i].h, (int)h_table[i].w);
+            return YK_ERR_ARG;
+        }
+    for (int i = 0; i < n; ++i) {
+        int tx, ty;
+        letterbox_params(h_table[i].h, h_table[i].w, dst_h, dst_w, &h_table[i].scale, &tx, &ty);
+        h_table[i].tx = tx;
+        h_table[i].ty = ty;
+    }
+    return YK_OK;
+}
+
+extern "C" int yk_letterbox_tiles_u8(const uint8_t *d_src, size_t src_bytes, const yk_tile_row_t *d_table, int n, uint8_t *d_dst, int dst_h,
+                                     int dst_w, void *stream) {
+    if (!d_src || !d_table || !d_dst || n <= 0 || src_bytes == 0 || dst_h <= 0 || dst_w <= 0) {
+        yk_set_error("yk_letterbox_tiles_u8: bad argument");
+        return YK_ERR_ARG;
+    }
+    if (yk_current_device() < 0) {
+        yk_set_error("yk_letterbox_tiles_u8: no HIP device");
+        return YK_ERR_NO_DEVICE;
+    }
+    const size_t per = (size_t)dst_h * dst_w;
+    for (int base = 0; base < n; base += 65535) {                                 // grid.y holds at most 65535 tiles
+        const int m = n - base < 65535 ? n - base : 65535;
+        hipLaunchKernelGGL(letterbox_tiles_u8_kernel, dim3((unsigned)((per + 255) / 256), (unsigned)m), dim3(256), 0, (hipStream_t)stream,
                            d_src, src_bytes, d_table + base, d_dst + (size_t)base * per * 3, dst_h, dst_w);
     }
     YK_HIP(hipGetLastError());

@@ -1,6 +1,7 @@
 """`make detect` - a folder of pictures through the pipeline: detections and annotated pictures out.
 
     python keras_detect.py CKPT SRC --out_dir D [--draw True|False] [--decode pil|gpu] [--encode pil|gpu] [--quality 75] [--batch 32] [--depth 4]
+                           [--tiles NXxNY --tile_overlap 0.2 --tile_full True --tile_match ios|iou --tile_thresh 0.5]
                            [network and threshold flags of keras_inference.py]
 
 SRC: a folder (its .jpg / .jpeg / .png / .bmp files, in sorted order), a text file with one picture path per line, or one picture.
@@ -30,6 +31,7 @@ import numpy as np
 from . import draw as dr
 from . import jpeg
 from . import softnms
+from . import tiles as tl
 from .helper import INFO, NOTE, Helper, VOC_ANCHORS
 from .yolonet import MODEL_DEFS
 
@@ -62,6 +64,7 @@ def parse(argv=None):
     p.add_argument('--precision', type=str, choices=['f16', 'f16x2', 'kpu'], default='f16x2')
     p.add_argument('--nms', type=str, default='hard', help="suppression rule of the decode: hard (the reference's), linear or gaussian (Soft-NMS), diou")
     p.add_argument('--nms_sigma', type=float, default=0.5, help='sigma of --nms gaussian')
+    tl.add_arguments(p)
     a = p.parse_args(sys.argv[1:] if argv is None else argv)
     if (a.precision == 'kpu') != a.pre_ckpt.endswith(('.kmodel', '.kfpkg')):
         p.error('--precision kpu runs a .kmodel / .kfpkg checkpoint, and only it does (the float modes take .h5 / .npz)')
@@ -71,6 +74,10 @@ def parse(argv=None):
         p.error('--quality is 1 .. 100')
     try:
         softnms.check(a.nms, a.nms_sigma)
+    except ValueError as e:
+        p.error(str(e))
+    try:
+        tl.parse_arguments(a)
     except ValueError as e:
         p.error(str(e))
     a.draw = a.draw == 'True'
@@ -131,19 +138,25 @@ class _Stage:
         self.pinned = self.d_packed = self.h_dets = self.h_counts = None
         self.d_work = self.d_scan = self.h_scan = self.d_off = self.h_off = None       # encode='gpu'
         self.d_stage = self.d_jwork = self.d_jstatus = self.h_jstatus = None           # decode='gpu'
+        self.d_mdets = self.d_mcounts = None                                            # tiles: the merged rows per picture
 
 
 def run(h: Helper, model, sources, out_dir=None, draw: bool = True, batch: int = 32, depth: int = 4, precision: str = 'f16x2',
         obj_thresh: float = 0.7, iou_thresh: float = 0.3, workers: int = 8, names: Optional[Sequence[str]] = None,
         return_arrays: bool = False, verbose: bool = True, max_out: int = 30, encode: str = 'pil', quality: int = 75, decode: str = 'pil',
-        nms: str = 'hard', nms_sigma: float = 0.5):
+        nms: str = 'hard', nms_sigma: float = 0.5, tiles=None, tile_overlap: float = 0.2, tile_full: bool = True, tile_match: str = 'ios',
+        tile_thresh: float = 0.5):
     """sources: picture paths, or [h, w, 3] uint8 arrays already in memory (then `names` names them); with decode='gpu' paths or the bytes of
     picture files: baseline JPEGs are decoded on the device by the rule of include/yolo_hip.h (not PIL's bytes: DESIGN.md 3.12), every other
     file by PIL on the pool as with decode='pil'; a stream the device cannot finish raises YkError naming the file.  -> {'names', 'detections': one
     [k, 6] float32 array per picture, 'files': the pictures written, 'arrays': the annotated pictures as they leave the GPU, before any JPEG
     encoding (return_arrays=True with draw=True)}.  With out_dir also writes detections.json and, when drawing, the _res.jpg files:
     encode='pil' through PIL's save() on the pool; encode='gpu' encodes them on the slot's stream right after the draw at `quality`
-     - then the uncompressed pictures come back only for return_arrays, and the files are headers + scan + EOI."""
+     - then the uncompressed pictures come back only for return_arrays, and the files are headers + scan + EOI.
+    tiles=(nx, ny): sliced inference (tiles.py) - every picture runs as nx * ny overlapping tiles (tile_overlap of a tile's
+    side) plus, with tile_full, the whole picture, each a network frame of its own (yk_letterbox_tiles_u8 cuts them out of the resident
+    originals), and yk_merge_tiles turns their rows into the picture's rows by a hard NMS at tile_thresh under tile_match ('ios' or 'iou');
+    a batch then holds max(1, batch // frames per picture) pictures.  None (the default): everything as without the option."""
     import torch
     from . import engine
     engine.require_gpu()
@@ -158,13 +171,18 @@ def run(h: Helper, model, sources, out_dir=None, draw: bool = True, batch: int =
         softnms.check(nms, nms_sigma)
     except ValueError as e:
         raise engine.YkError(f'detect: {e}') from None
+    try:
+        grid_xy = tl.check(tiles, tile_overlap, tile_match, tile_thresh, nms)
+    except ValueError as e:
+        raise engine.YkError(f'detect: {e}') from None
+    T = 1 if grid_xy is None else grid_xy[0] * grid_xy[1] + (1 if tile_full else 0)      # network frames per picture
     gpu_decode = decode == 'gpu'
     in_memory = isinstance(sources[0], (np.ndarray, bytes))
     if gpu_decode and any(isinstance(s, np.ndarray) for s in sources):
         raise engine.YkError("detect: decode='gpu' takes paths or the bytes of picture files, not arrays")
     names = list(names) if names is not None else ([f'img{i:05d}' for i in range(n_all)] if in_memory else [str(s) for s in sources])
     in_hw = tuple(int(v) for v in h.in_hw[0])
-    B = max(1, min(int(batch), n_all))
+    B = max(1, min(int(batch) // T, n_all))                  # pictures per batch; the network sees B * T frames
     dev = torch.device('cuda', torch.cuda.current_device())
     if out_dir is not None:
         Path(out_dir).mkdir(parents=True, exist_ok=True)
@@ -181,13 +199,13 @@ def run(h: Helper, model, sources, out_dir=None, draw: bool = True, batch: int =
 
     pipe = plan = None
     if precision == 'kpu':                                  # one batch at a time through the KPU's integer arithmetic, on the current stream
-        plan = model._plan(B)
+        plan = model._plan(B * T)
         cfg = engine.make_decode_cfg(h.anchors, h.class_num, h.in_hw[0], h.out_hw)
-        frames = torch.empty((B, *in_hw, 3), dtype=torch.uint8, device=dev)
+        frames = torch.empty((B * T, *in_hw, 3), dtype=torch.uint8, device=dev)
         depth = 1
     else:
         depth = max(1, int(depth))
-        pipe = engine.Pipeline(model.spec, model.get_weights(), h.anchors, max_batch=B, depth=depth, precision=precision, max_out=max_out)
+        pipe = engine.Pipeline(model.spec, model.get_weights(), h.anchors, max_batch=B * T, depth=depth, precision=precision, max_out=max_out)
     stages = [_Stage() for _ in range(depth)]
     pool = ThreadPoolExecutor(max_workers=max(1, min(MAX_WORKERS, int(workers))))
     load = (lambda s: np.ascontiguousarray(s[..., :3], np.uint8)) if in_memory else \
@@ -336,14 +354,33 @@ def run(h: Helper, model, sources, out_dir=None, draw: bool = True, batch: int =
                 table_d = engine.ragged_table_to_device(table, in_hw, total, dev)          # (a blocking copy of 40 bytes per picture)
                 copy(d_packed, st.pinned, total, stream)                                    # the batch's one copy to the device
                 keep = (table_d, None)
-            dst = pipe.input(slot)[:n] if pipe is not None else frames[:n]
-            engine.letterbox_ragged_u8(d_packed, table_d, in_hw, stream=stream, out=dst)
-            hw = np.asarray(shapes, np.float32)
-            if pipe is not None:
-                dets, counts, _ = pipe.submit(None, image_hw=hw, obj_thresh=obj_thresh, iou_thresh=iou_thresh, max_out=max_out, batch=n, nms=nms, sigma=nms_sigma)
+            nf = n * T                                                                      # network frames of this batch
+            dst = pipe.input(slot)[:nf] if pipe is not None else frames[:nf]
+            if grid_xy is None:
+                engine.letterbox_ragged_u8(d_packed, table_d, in_hw, stream=stream, out=dst)
+                hw = np.asarray(shapes, np.float32)
             else:
-                plan.run_u8(frames[:n])
-                dets, counts = engine.decode_py(cfg, plan.outputs(), n, hw, obj_thresh, iou_thresh, max_out=max_out, nms=nms, sigma=nms_sigma)
+                grids = [tl.grid(sh, sw, grid_xy[0], grid_xy[1], tile_overlap, tile_full) for sh, sw in shapes]
+                rows = np.concatenate([tl.table_rows(g, int(table['offset'][i]), shapes[i][1]) for i, g in enumerate(grids)])
+                g_all = np.concatenate(grids)
+                tiles_d = engine.tile_table_to_device(rows, in_hw, total, dev)             # (blocking copies of a few bytes per tile, as above)
+                engine.letterbox_tiles_u8(d_packed, tiles_d, in_hw, stream=stream, out=dst)
+                hw = g_all[:, 2:4].astype(np.float32)                                       # every frame is decoded at its tile's size
+                origin_d = torch.from_numpy(np.ascontiguousarray(g_all[:, 0:2], np.float32)).to(dev)
+                first_d = torch.from_numpy(np.arange(n + 1, dtype=np.int32) * T).to(dev)
+                if st.d_mdets is None:
+                    st.d_mdets = torch.zeros((B, cap, 6), dtype=torch.float32, device=dev)
+                    st.d_mcounts = torch.zeros((B,), dtype=torch.int32, device=dev)
+                    torch.cuda.current_stream().synchronize()                               # (filled on torch's stream, written on the slot's)
+                keep = (*keep, tiles_d, origin_d, first_d)
+            if pipe is not None:
+                dets, counts, _ = pipe.submit(None, image_hw=hw, obj_thresh=obj_thresh, iou_thresh=iou_thresh, max_out=max_out, batch=nf, nms=nms, sigma=nms_sigma)
+            else:
+                plan.run_u8(frames[:nf])
+                dets, counts = engine.decode_py(cfg, plan.outputs(), nf, hw, obj_thresh, iou_thresh, max_out=max_out, nms=nms, sigma=nms_sigma)
+            if grid_xy is not None:
+                dets, counts = engine.merge_tiles(dets, counts, origin_d, first_d, h.class_num, max_out, tile_thresh, tile_match, stream=stream,
+                                                  out=st.d_mdets[:n], out_counts=st.d_mcounts[:n])
             if want_pixels:
                 max_px = int(max(s[0] * s[1] for s in shapes))
                 engine.draw_detections_u8(d_packed, table_d, dets, counts, colormap, atlas, stream=stream, max_pixels=max_px)
@@ -375,6 +412,9 @@ def run(h: Helper, model, sources, out_dir=None, draw: bool = True, batch: int =
             pipe.close()
     if out_dir is not None:
         rule = {} if nms == 'hard' else {'nms': nms, 'nms_sigma': float(nms_sigma)}      # (hard: the file is what it always was)
+        if grid_xy is not None:
+            rule.update(tiles=[int(grid_xy[0]), int(grid_xy[1])], tile_overlap=float(tile_overlap), tile_full=bool(tile_full), tile_match=tile_match,
+                        tile_thresh=float(tile_thresh))
         doc = [{'path': names[i], **rule, 'detections': [[float(v) for v in row] for row in results[i]]} for i in range(n_all)]
         (Path(out_dir) / 'detections.json').write_text(json.dumps(doc, indent=1))
     out = {'names': names, 'detections': results, 'files': written}
@@ -402,9 +442,11 @@ def main(argv=None):
         raise engine.YkError(f'detect: no pictures ({", ".join(EXTENSIONS)}) in {a.src}')
     res = run(h, model, paths, out_dir=a.out_dir, draw=a.draw, batch=a.batch, depth=a.depth, precision=a.precision,
               obj_thresh=a.obj_thresh, iou_thresh=a.iou_thresh, workers=a.workers, encode=a.encode, quality=a.quality, decode=a.decode,
-              nms=a.nms, nms_sigma=a.nms_sigma)
+              nms=a.nms, nms_sigma=a.nms_sigma, **tl.run_options(a))
     if a.nms != 'hard':
         print(INFO, f' nms {a.nms}, sigma {a.nms_sigma:g}: scores are the decayed ones')
+    if a.tiles is not None:
+        print(INFO, f' tiles {a.tiles[0]}x{a.tiles[1]}, overlap {a.tile_overlap:g}, whole picture {a.tile_full}: merged by {a.tile_match} > {a.tile_thresh:g}')
     print(INFO, f' {len(paths)} pictures, {sum(len(d) for d in res["detections"])} detections -> {Path(a.out_dir) / "detections.json"}'
           + (f', {len(res["files"])} annotated pictures' if a.draw else ''))
     return res

@@ -568,6 +568,104 @@ def check_ragged_rows(table, packed_bytes: int) -> np.ndarray:
     return t
 
 
+def check_tile_rows(table, packed_bytes: int) -> np.ndarray:
+    """The rows of a host tile table (tiles.TILE_DTYPE = yk_tile_row_t) as one flat copy, refused with YkError unless every row is a non-empty
+    tile whose rows do not overlap (stride >= 3 * w) and whose last byte lies inside the `packed_bytes` of its buffer: what
+    yk_letterbox_tiles_u8 would otherwise answer with a zero frame."""
+    from .tiles import TILE_DTYPE
+    t = np.array(table, dtype=TILE_DTYPE, copy=True).reshape(-1)
+    bad = (t['h'] <= 0) | (t['w'] <= 0)
+    if bad.any():
+        i = int(np.nonzero(bad)[0][0])
+        raise YkError(f'tile table: row {i} is {int(t["h"][i])} x {int(t["w"][i])}')
+    bad = t['stride'] < 3 * t['w'].astype(np.int64)
+    if bad.any():
+        i = int(np.nonzero(bad)[0][0])
+        raise YkError(f'tile table: row {i} has stride {int(t["stride"][i])}, less than the {3 * int(t["w"][i])} bytes of one of its rows')
+    end = t['offset'].astype(object) + (t['h'].astype(object) - 1) * t['stride'].astype(object) + 3 * t['w'].astype(object)
+    if len(t) and max(end) > int(packed_bytes):
+        raise YkError(f'tile table: row {int(np.argmax(end))} ends at byte {max(end)} of a {int(packed_bytes)}-byte buffer')
+    return t
+
+
+def tile_table_to_device(table, dst_hw, packed_bytes: int, device, stream=None):
+    """A host tile table (tiles.table_rows) checked (check_tile_rows), its scale / tx / ty filled for the network size dst_hw and uploaded
+    -> cuda uint8 [n, 40], what letterbox_tiles_u8 takes as its table."""
+    import torch
+    t = check_tile_rows(table, packed_bytes)
+    if len(t) == 0:
+        raise YkError('tile table: no rows')
+    call('yk_letterbox_tiles_params', t, len(t), int(dst_hw[0]), int(dst_hw[1]))
+    host = torch.from_numpy(t.view(np.uint8).reshape(len(t), t.dtype.itemsize))
+    with torch.cuda.stream(torch.cuda.current_stream() if stream is None else stream):
+        return host.to(device, non_blocking=False)
+
+
+def letterbox_tiles_u8(packed, table, dst_hw, stream=None, out=None):
+    """Tiles of the pictures of a packed buffer letterboxed into network frames in one launch (yk_letterbox_tiles_u8): `packed` cuda uint8
+    [bytes]; `table` a host table of tiles.TILE_DTYPE (checked here: a row the kernel would answer with zeros is refused) or the device table
+    tile_table_to_device returned for this dst_hw.  -> cuda uint8 [n, H, W, 3]; frame t is bit for bit letterbox_u8 of a contiguous copy of
+    tile t."""
+    import torch
+    from .tiles import TILE_DTYPE
+    require_gpu()
+    assert packed.is_cuda and packed.dtype == torch.uint8 and packed.is_contiguous() and packed.numel() > 0
+    if not torch.is_tensor(table):
+        table = tile_table_to_device(table, dst_hw, packed.numel(), packed.device, stream)
+    assert table.is_cuda and table.dtype == torch.uint8 and table.is_contiguous() and table.dim() == 2 and table.device == packed.device
+    assert table.shape[1] == TILE_DTYPE.itemsize and table.shape[0] > 0, tuple(table.shape)
+    n = int(table.shape[0])
+    if out is None:
+        out = torch.empty((n, int(dst_hw[0]), int(dst_hw[1]), 3), dtype=torch.uint8, device=packed.device)
+    assert out.is_cuda and out.is_contiguous() and tuple(out.shape) == (n, int(dst_hw[0]), int(dst_hw[1]), 3), tuple(out.shape)
+    call('yk_letterbox_tiles_u8', packed, packed.numel(), table, n, out, out.shape[1], out.shape[2], _stream(stream))
+    return out
+
+
+def merge_tiles_lds_candidates(n_tiles: int, n_pics: int, max_out: int) -> int:
+    """Candidates of one (picture, class) that merge_tiles with these sizes stages in LDS on the current device; more take the global path."""
+    n = lib().yk_merge_tiles_lds_candidates(int(n_tiles), int(n_pics), int(max_out))
+    if n < 0:
+        _check(n, 'yk_merge_tiles_lds_candidates')
+    return int(n)
+
+
+def merge_tiles(dets, counts, origins, first, class_num: int, max_out: int, thresh: float = 0.5, metric: str = 'ios', stream=None,
+                out=None, out_counts=None):
+    """The rows of tile frames merged into one padded row set per picture (yk_merge_tiles; the rule is tiles.merge): dets cuda fp32
+    [n_tiles, class_num * max_out, 6] and counts cuda int32 [n_tiles] as decode_py / Pipeline.submit leave them; origins (y0, x0) per tile and
+    first [n_pics + 1] (the tiles of picture p are first[p] .. first[p + 1] - 1), host arrays or cuda float32 [n_tiles, 2] / int32 [n_pics + 1].
+    -> (rows cuda fp32 [n_pics, class_num * max_out, 6], counts cuda int32 [n_pics])."""
+    import torch
+    from . import tiles
+    require_gpu()
+    try:
+        method = tiles.metric_id(metric)
+    except ValueError as e:
+        raise YkError(str(e)) from None
+    cap = int(class_num) * int(max_out)
+    assert dets.is_cuda and dets.dtype == torch.float32 and dets.is_contiguous() and dets.dim() == 3 and tuple(dets.shape[1:]) == (cap, 6), tuple(dets.shape)
+    n_tiles = int(dets.shape[0])
+    assert counts.is_cuda and counts.dtype == torch.int32 and counts.is_contiguous() and tuple(counts.shape) == (n_tiles,)
+    with torch.cuda.stream(torch.cuda.current_stream() if stream is None else stream):
+        if not torch.is_tensor(origins):
+            origins = torch.from_numpy(np.ascontiguousarray(origins, np.float32).reshape(-1, 2)).to(dets.device)
+        if not torch.is_tensor(first):
+            first = torch.from_numpy(np.ascontiguousarray(first, np.int32).reshape(-1)).to(dets.device)
+    assert origins.is_cuda and origins.dtype == torch.float32 and origins.is_contiguous() and tuple(origins.shape) == (n_tiles, 2), tuple(origins.shape)
+    assert first.is_cuda and first.dtype == torch.int32 and first.is_contiguous() and first.dim() == 1 and first.numel() >= 2
+    n_pics = int(first.numel()) - 1
+    if out is None:
+        out = torch.zeros((n_pics, cap, 6), dtype=torch.float32, device=dets.device)
+    if out_counts is None:
+        out_counts = torch.zeros((n_pics,), dtype=torch.int32, device=dets.device)
+    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (n_pics, cap, 6), tuple(out.shape)
+    assert out_counts.is_cuda and out_counts.dtype == torch.int32 and out_counts.is_contiguous() and tuple(out_counts.shape) == (n_pics,)
+    call('yk_merge_tiles', dets, counts, origins, first, n_tiles, n_pics, int(class_num), int(max_out), float(thresh), method, out, out_counts,
+         _stream(stream))
+    return out, out_counts
+
+
 def mosaic_ragged_u8(packed, table, centres, dst_hw, inv=None, stream=None, out=None):
     """One training frame from four pictures per sample, the whole batch in one launch (yk_mosaic_ragged_u8; the rule is in mosaic.py):
     `packed` cuda uint8 [bytes], the pictures of draw.pack_ragged; `table` the samples' rows in quadrant order with scale / tx / ty filled

@@ -5,6 +5,7 @@
                               [--precision f16x2|f16|kpu] [--obj_thresh 0.05] [--nms_iou 0.5] [--iou_thresh 0.5] [--voc07 True]
                               [--nms hard|linear|gaussian|diou] [--nms_sigma 0.5]
                               [--metric voc|coco] [--out eval.json] [--dump_rows rows.npz]
+                              [--tiles NXxNY --tile_overlap 0.2 --tile_full True --tile_match ios|iou --tile_thresh 0.5]
 
 CKPT: a Keras `.h5` / `.npz` checkpoint (float modes, through engine.Pipeline with several batches in flight) or a `.kmodel` / `.kfpkg`
 (`--precision kpu`, the K210 KPU's exact integer arithmetic through engine.KpuPlan).  The images are the validation head of the list
@@ -30,6 +31,7 @@ from pathlib import Path
 import numpy as np
 
 from . import softnms
+from . import tiles as tl
 from .helper import INFO, Helper, VOC_ANCHORS
 from .yolonet import MODEL_DEFS
 
@@ -71,6 +73,7 @@ def parse(argv=None):
     p.add_argument('--depth', type=int, default=3, help='batches in flight (float modes)')
     p.add_argument('--out', type=str, default=None, help='result file (default: eval.json next to the checkpoint)')
     p.add_argument('--dump_rows', type=str, default=None, help='also write the detections and the ground truth that were scored (.npz)')
+    tl.add_arguments(p)
     a = p.parse_args(sys.argv[1:] if argv is None else argv)
     if (a.precision == 'kpu') != a.pre_ckpt.endswith(('.kmodel', '.kfpkg')):
         p.error('--precision kpu runs a .kmodel / .kfpkg checkpoint, and only it does (the float modes take .h5 / .npz)')
@@ -78,6 +81,10 @@ def parse(argv=None):
         p.error('--synthetic N replaces --ann')
     try:
         softnms.check(a.nms, a.nms_sigma)
+    except ValueError as e:
+        p.error(str(e))
+    try:
+        tl.parse_arguments(a)
     except ValueError as e:
         p.error(str(e))
     if a.metric == 'coco' and a.voc07 == 'True':
@@ -112,19 +119,46 @@ def run(a, h: Helper, model, items, ev) -> None:
     import torch
     from . import engine
     in_hw = tuple(int(v) for v in h.in_hw[0])
-    B = max(1, min(int(a.batch), len(items)))
+    try:
+        grid_xy = tl.check(a.tiles, a.tile_overlap, a.tile_match, a.tile_thresh, a.nms)
+    except ValueError as e:
+        raise engine.YkError(f'evaluate: {e}') from None
+    T = 1 if grid_xy is None else grid_xy[0] * grid_xy[1] + (1 if a.tile_full else 0)      # network frames per picture
+    B = max(1, min(int(a.batch) // T, len(items)))
+    max_out = 30
+
+    def tile_frames(imgs, out, stream):
+        """Sliced inference (tiles.py): the pictures packed into one device buffer, their tiles letterboxed into `out` by one launch
+        -> (what must stay alive until the batch has run, each frame's (h, w), origins, first)."""
+        from . import draw as dr
+        packed, table, shapes = dr.pack_ragged(imgs)
+        with torch.cuda.stream(stream):
+            d_packed = packed.to(out.device, non_blocking=False)
+        grids = [tl.grid(sh, sw, grid_xy[0], grid_xy[1], a.tile_overlap, a.tile_full) for sh, sw in shapes]
+        rows = np.concatenate([tl.table_rows(g, int(table['offset'][i]), shapes[i][1]) for i, g in enumerate(grids)])
+        g_all = np.concatenate(grids)
+        engine.letterbox_tiles_u8(d_packed, rows, in_hw, stream=stream, out=out)
+        return d_packed, g_all[:, 2:4].astype(np.float32), np.ascontiguousarray(g_all[:, 0:2], np.float32), np.arange(len(imgs) + 1, dtype=np.int32) * T
+
     if a.precision == 'kpu':
-        plan = model._plan(B)
+        plan = model._plan(B * T)
         cfg = engine.make_decode_cfg(h.anchors, h.class_num, h.in_hw[0], h.out_hw)
         for k in range(0, len(items), B):
             loaded = [_load(h, it) for it in items[k:k + B]]
-            frames = torch.cat([engine.letterbox_u8(torch.from_numpy(im[None]).cuda(), in_hw) for im, _ in loaded])
+            if grid_xy is None:
+                frames = torch.cat([engine.letterbox_u8(torch.from_numpy(im[None]).cuda(), in_hw) for im, _ in loaded])
+                shapes = np.asarray([im.shape[:2] for im, _ in loaded], np.float32)
+            else:
+                frames = torch.empty((len(loaded) * T, *in_hw, 3), dtype=torch.uint8, device='cuda')
+                _, shapes, origins, first = tile_frames([im for im, _ in loaded], frames, torch.cuda.current_stream())
             plan.run_u8(frames)
-            shapes = np.asarray([im.shape[:2] for im, _ in loaded], np.float32)
-            dets, counts = engine.decode_py(cfg, plan.outputs(), len(loaded), shapes, a.obj_thresh, a.nms_iou, nms=a.nms, sigma=a.nms_sigma)
+            dets, counts = engine.decode_py(cfg, plan.outputs(), len(frames), shapes, a.obj_thresh, a.nms_iou, max_out=max_out, nms=a.nms, sigma=a.nms_sigma)
+            if grid_xy is not None:
+                dets, counts = engine.merge_tiles(dets, counts, origins, first, h.class_num, max_out, a.tile_thresh, a.tile_match)
             ev.add(dets, counts, [ground_truth_rows(b, im.shape[:2]) for im, b in loaded])
         return
-    pipe = engine.Pipeline(model.spec, model.get_weights(), h.anchors, max_batch=B, depth=max(1, int(a.depth)), precision=a.precision)
+    pipe = engine.Pipeline(model.spec, model.get_weights(), h.anchors, max_batch=B * T, depth=max(1, int(a.depth)), precision=a.precision, max_out=max_out)
+    merged = [None] * pipe.depth                            # tiles: each slot's merged rows per picture
     pending = deque()                                       # (dets, counts, stream, ground truth) of the batches in flight
 
     def drain():
@@ -138,11 +172,23 @@ def run(a, h: Helper, model, items, ev) -> None:
             loaded = [_load(h, it) for it in items[k:k + B]]
             slot = pipe.next_slot()
             buf, st = pipe.input(slot), pipe.streams[slot]
-            with torch.cuda.stream(st):
-                for j, (im, _) in enumerate(loaded):
-                    engine.letterbox_u8(torch.from_numpy(im[None]).to(buf.device, non_blocking=False), in_hw, stream=st, out=buf[j:j + 1])
-            shapes = np.asarray([im.shape[:2] for im, _ in loaded], np.float32)
-            dets, counts, stream = pipe.submit(None, image_hw=shapes, obj_thresh=a.obj_thresh, iou_thresh=a.nms_iou, batch=len(loaded), nms=a.nms, sigma=a.nms_sigma)
+            if grid_xy is None:
+                with torch.cuda.stream(st):
+                    for j, (im, _) in enumerate(loaded):
+                        engine.letterbox_u8(torch.from_numpy(im[None]).to(buf.device, non_blocking=False), in_hw, stream=st, out=buf[j:j + 1])
+                shapes = np.asarray([im.shape[:2] for im, _ in loaded], np.float32)
+            else:
+                keep, shapes, origins, first = tile_frames([im for im, _ in loaded], buf[:len(loaded) * T], st)
+            dets, counts, stream = pipe.submit(None, image_hw=shapes, obj_thresh=a.obj_thresh, iou_thresh=a.nms_iou, max_out=max_out,
+                                               batch=len(loaded) * T, nms=a.nms, sigma=a.nms_sigma)
+            if grid_xy is not None:
+                if merged[slot] is None:
+                    merged[slot] = (torch.zeros((B, h.class_num * max_out, 6), dtype=torch.float32, device=buf.device),
+                                    torch.zeros((B,), dtype=torch.int32, device=buf.device))
+                    torch.cuda.current_stream().synchronize()           # (filled on torch's stream, written on the slot's)
+                dets, counts = engine.merge_tiles(dets, counts, origins, first, h.class_num, max_out, a.tile_thresh, a.tile_match, stream=stream,
+                                                  out=merged[slot][0][:len(loaded)], out_counts=merged[slot][1][:len(loaded)])
+                stream.synchronize()                                    # `keep`, the packed originals, may go once the tiles are cut
             pending.append((dets, counts, stream, [ground_truth_rows(b, im.shape[:2]) for im, b in loaded]))
         while pending:
             drain()
@@ -210,6 +256,9 @@ def main(argv=None):
               'fp': r['fp'].tolist()}
     if a.nms != 'hard':
         report.update(nms=a.nms, nms_sigma=a.nms_sigma)
+    if a.tiles is not None:
+        report.update(tiles=list(a.tiles), tile_overlap=a.tile_overlap, tile_full=a.tile_full, tile_match=a.tile_match, tile_thresh=a.tile_thresh)
+        print(f'   tiles {a.tiles[0]}x{a.tiles[1]}, overlap {a.tile_overlap:g}, whole picture {a.tile_full}: merged by {a.tile_match} > {a.tile_thresh:g} (tiles.py)')
     if a.metric == 'coco':
         report['coco'] = coco_report(ev, a.class_num, r['n_gt'])
     out = Path(a.out) if a.out else Path(a.pre_ckpt).resolve().parent / 'eval.json'
