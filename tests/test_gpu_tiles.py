@@ -1,11 +1,33 @@
 """Sliced inference on the GPU: yk_letterbox_tiles_u8 against yk_letterbox_u8 on a contiguous copy of every crop,
-yk_merge_tiles against tiles.merge, both bit for bit, and detect.run(tiles=...) against the untiled path composed by hand."""
+yk_merge_tiles against tiles.merge, both bit for bit, and detect.run(tiles=...) against the untiled path composed by hand.
+
+The merge, beyond the cases that came with it (threshold, ties, cap, empty tiles, 1 and 80 classes, 65 tiles of one class on both paths, the
+refusals), on the inputs of tests/tile_cases.py, each of which tests/test_tile_cases.py shows to sit where it claims, and each asked of
+engine.merge_tiles_lds_candidates for its path before it runs:
+  two_classes_global_small    two classes of ONE picture off LDS at lds_cap 64, six more in LDS beside them; rows that are not decode-shaped
+  four_classes_global_stride8 the same with 16 classes and classes 0, 1, 8, 9 off LDS: workgroups 8 apart share a cache on a device of 8 dies, and
+                              only there do two segments that overlap show (measured: with `seg` dropped from the segment base this case fails and
+                              two_classes_global_small passes)
+  boundary-64 / -65           n == lds_cap (the last LDS case) and lds_cap + 1 (the first global one; the extra candidate is the picture's best)
+  two_classes_global_decode_shaped, three_pictures_mixed
+                              2 x 2112 candidates at lds_cap 2048, both metrics; four segments in two list regions around a small picture
+  dropped_rows                counted rows with score NaN / -inf and class -1 / C / 1.5 / NaN vanish; +inf wins; -0.0 is a score and keeps its sign
+  box_edges                   swapped corners, zero-area boxes, thresh 0 (touching stays, one shared cell goes), thresh +inf (the cap ends it)
+  far_origin, far_origin_touch   origins (4000.3, 2999.7), (-0.1, 1e-3): the rows are the float32 sums and the decisions are made on those
+  ties                        equal scores across tiles and across one lane's entries i and i + 64, in LDS and in global memory
+  clamps                      the C entry point with counts [cap + 5, -3, 7] and first [0, 5, 2] / [-1, 2] / [0, n_tiles + 4]
+Rows are compared as int32 patterns (so -0.0 is not 0.0); d_out is filled with a sentinel first and every row beyond a picture's count must
+still hold it (the kernel writes the counted rows only).  three_pictures_mixed twice gives the same bytes; the call is captured
+in a graph (memset + two kernel nodes, nothing run meanwhile) and replayed on rows A, B, A.
+Measured on the MI355X: the whole file (48 tests) 3.0 - 4.0 s, of which 1.6 - 2.7 s is the first test's set-up (library and device); every merge
+test under 0.05 s, the largest new ones (three_pictures_mixed, 8.6k rows; the graph replay) 0.02 s."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
 from k210_yolo_framework_amd import draw, tiles
+from tests import tile_cases
 
 pytestmark = pytest.mark.gpu
 F = np.float32
@@ -237,6 +259,152 @@ def test_merge_bad_arguments_are_refused_by_name():
     torch.cuda.synchronize()
     with pytest.raises(engine.YkError, match='tile_match'):
         engine.merge_tiles(dets, counts, origin, first, 2, 3, 0.5, 'giou')
+
+
+# ---------------------------------------------------------------------------------------------------- the merge on tests/tile_cases.py
+CASES = tile_cases.all_cases()
+CLAMPS = tile_cases.clamps()
+
+
+def _bits(t):
+    import torch
+    return t.contiguous().view(torch.int32)
+
+
+class _Device:
+    """The buffers of one yk_merge_tiles call: rows beyond a tile's count hold NaN (reading one would show), d_out holds SENTINEL and
+    d_out_counts -1 before every call."""
+
+    def __init__(self, case):
+        import torch
+        self.cap = case.class_num * case.max_out
+        self.n_tiles, self.n_pics = len(case.rows), len(case.first) - 1
+        self.dets = torch.empty((self.n_tiles, self.cap, 6), dtype=torch.float32, device='cuda')
+        self.counts = torch.empty(self.n_tiles, dtype=torch.int32, device='cuda')
+        self.origins = torch.empty((self.n_tiles, 2), dtype=torch.float32, device='cuda')
+        self.first = torch.from_numpy(np.asarray(case.first, np.int32)).cuda()
+        self.out = torch.empty((self.n_pics, self.cap, 6), dtype=torch.float32, device='cuda')
+        self.out_counts = torch.empty(self.n_pics, dtype=torch.int32, device='cuda')
+        self.load(case)
+
+    def load(self, case):
+        import torch
+        dets = np.full((self.n_tiles, self.cap, 6), np.nan, F)
+        for t, r in enumerate(case.rows):
+            dets[t, :len(r)] = r
+        self.dets.copy_(torch.from_numpy(dets))
+        self.counts.copy_(torch.from_numpy(np.asarray([len(r) for r in case.rows], np.int32)))
+        self.origins.copy_(torch.from_numpy(case.origins.copy()))
+        self.clear()
+
+    def clear(self):
+        self.out.fill_(tile_cases.SENTINEL)
+        self.out_counts.fill_(-1)
+
+    def untouched(self):
+        return bool((self.out == tile_cases.SENTINEL).all().item()) and bool((self.out_counts == -1).all().item())
+
+    def check(self, want, what):
+        """counts and rows equal to the reference bit for bit, and every row beyond a picture's count left as it was"""
+        import torch
+        assert self.out_counts.tolist() == [len(w) for w in want], (what, self.out_counts.tolist(), [len(w) for w in want])
+        for p, w in enumerate(want):
+            assert torch.equal(_bits(self.out[p, :len(w)]).cpu(), _bits(torch.from_numpy(np.array(w, F, copy=True)).reshape(-1, 6))), (what, p)
+            assert bool((self.out[p, len(w):] == tile_cases.SENTINEL).all().item()), (what, p)
+
+
+def _path_is_the_claimed_one(engine, case):
+    cap = engine.merge_tiles_lds_candidates(len(case.rows), len(case.first) - 1, case.max_out)
+    assert cap == tile_cases.case_lds_cap(case) == case.claims['lds_cap'], (case.name, cap)
+    assert [[c for c, n in enumerate(per) if n > cap] for per in tile_cases.candidates(case)] == case.claims['over'], case.name
+
+
+@pytest.mark.parametrize('case', CASES, ids=[c.name for c in CASES])
+def test_merge_cases_equal_the_reference_bit_for_bit(case):
+    import torch
+    from k210_yolo_framework_amd import engine
+    _path_is_the_claimed_one(engine, case)
+    d = _Device(case)
+    engine.merge_tiles(d.dets, d.counts, d.origins, d.first, case.class_num, case.max_out, case.thresh, case.metric, out=d.out, out_counts=d.out_counts)
+    torch.cuda.synchronize()
+    want = [rows for rows, _ in tile_cases.reference(case)]
+    d.check(want, case.name)
+    if 'first_row' in case.claims:                                   # boundary: the candidate at position lds_cap is the picture's best
+        assert torch.equal(_bits(d.out[0, 0]).cpu(), _bits(torch.from_numpy(case.claims['first_row'].copy())))
+    if 'class2' in case.claims:                                      # dropped_rows: +inf first, -0.0 last and still negative
+        got = d.out[0, :len(want[0])].cpu().numpy()
+        assert np.array_equal(got[got[:, 5] == 2].view(np.int32), np.asarray(case.claims['class2'], F).view(np.int32))
+
+
+@pytest.mark.parametrize('case', CLAMPS, ids=[c.name for c in CLAMPS])
+def test_merge_clamps_counts_and_first_on_the_device(case):
+    """Tables engine.merge_tiles never sees from the pipeline and the C entry point takes: counts [cap + 5, -3, 7] are read as [cap, 0, 7],
+    first [0, 5, 2] / [-1, 2] / [0, n_tiles + 4] as [0, 3, 2] (the second picture empty) / [0, 2] / [0, 3].  A row out of reach has the best
+    score there is, so one read shows as the first row."""
+    import torch
+    from k210_yolo_framework_amd import engine
+    cap = case.class_num * case.max_out
+    dets = torch.from_numpy(case.dets.copy()).cuda()
+    counts, origins, first = torch.from_numpy(case.counts.copy()).cuda(), torch.from_numpy(case.origins.copy()).cuda(), torch.from_numpy(case.first.copy()).cuda()
+    out = torch.full((case.n_pics, cap, 6), tile_cases.SENTINEL, dtype=torch.float32, device='cuda')
+    out_counts = torch.full((case.n_pics,), -1, dtype=torch.int32, device='cuda')
+    engine.call('yk_merge_tiles', dets, counts, origins, first, case.n_tiles, case.n_pics, case.class_num, case.max_out, case.thresh,
+                tiles.metric_id(case.metric), out, out_counts, C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    torch.cuda.synchronize()
+    assert out_counts.tolist() == [len(w) for w in case.want], case.name
+    for p, w in enumerate(case.want):
+        assert torch.equal(_bits(out[p, :len(w)]).cpu(), _bits(torch.from_numpy(w.copy()).reshape(-1, 6))), (case.name, p)
+        assert bool((out[p, len(w):] == tile_cases.SENTINEL).all().item()), (case.name, p)
+
+
+def test_merge_two_runs_of_four_global_segments_give_the_same_bytes():
+    """three_pictures_mixed twice (twice only): where each class's segment lands in its picture's list depends on which wave reaches the cursor
+    first; what comes out does not."""
+    import torch
+    from k210_yolo_framework_amd import engine
+    case = next(c for c in CASES if c.name == 'three_pictures_mixed-ios')
+    runs = []
+    for _ in range(2):
+        d = _Device(case)
+        engine.merge_tiles(d.dets, d.counts, d.origins, d.first, case.class_num, case.max_out, case.thresh, case.metric, out=d.out, out_counts=d.out_counts)
+        torch.cuda.synchronize()
+        runs.append((d.out.cpu(), d.out_counts.cpu()))
+    assert torch.equal(_bits(runs[0][0]), _bits(runs[1][0])) and torch.equal(runs[0][1], runs[1][1])
+    assert runs[0][1].tolist() == [len(rows) for rows, _ in tile_cases.reference(case)]
+
+
+def test_merge_recorded_in_a_graph_and_replayed_on_new_rows():
+    """The cursor's memset and both kernels are recorded (nothing runs during the capture) and the per-stream scratch survives: the replay reads
+    the rows that are in the buffers when it runs - seed A, then B, then A again, each equal to the reference of its own rows."""
+    import torch
+    from k210_yolo_framework_amd import engine
+    a, b = tile_cases.two_classes_global_decode_shaped('ios', seed=3), tile_cases.two_classes_global_decode_shaped('ios', seed=13)
+    _path_is_the_claimed_one(engine, a)
+    _path_is_the_claimed_one(engine, b)
+    stream = torch.cuda.Stream()
+    st = C.c_void_p(stream.cuda_stream)
+    with torch.cuda.stream(stream):
+        d = _Device(a)
+        issue = lambda: engine.call('yk_merge_tiles', d.dets, d.counts, d.origins, d.first, d.n_tiles, d.n_pics, a.class_num, a.max_out, a.thresh,
+                                    tiles.metric_id(a.metric), d.out, d.out_counts, st)
+        issue()                                                     # eagerly once: the stream's scratch exists before the capture
+        stream.synchronize()
+        d.check([rows for rows, _ in tile_cases.reference(a)], 'eager')
+        d.clear()
+        stream.synchronize()
+        graph = engine.capture(st, issue)
+        try:
+            assert graph.kernel_nodes == 2
+            stream.synchronize()
+            assert d.untouched()                                    # recorded, not executed
+            for case in (a, b, a):
+                d.load(case)
+                stream.synchronize()
+                graph.launch(st)
+                stream.synchronize()
+                d.check([rows for rows, _ in tile_cases.reference(case)], case.name)
+        finally:
+            graph.close()
 
 
 # ---------------------------------------------------------------------------------------------------- end to end
