@@ -32,10 +32,12 @@
 #                    VOC mAP of the checkpoint, network and metric on the GPU; prints the per-class AP table, writes eval.json beside CKPT
 #                    [METRIC=coco]: also the COCO-style AP (IoU .50:.95, AP50, AP75, small / medium / large, AR) and a `coco` object in eval.json
 #                    (make train VALMAP=True appends val_mAP to every epoch line)
+#                    [TTA=flip|v5|1,0.83f,0.67 TTATHRESH=0.55]: test-time augmentation, every picture also mirrored / shrunk, the views' rows fused on the GPU
 #   make detect      CKPT=yolo_model.h5|yolo.kmodel SRC=folder|list.txt [OUTDIR=out] [DRAW=True|False] [PRECISION=...] [DECODE=pil|gpu] [ENCODE=pil|gpu QUALITY=75]: every
 #                    picture of SRC through the pipeline; writes OUTDIR/detections.json and, with DRAW=True, OUTDIR/<stem>_res.jpg (boxes and
 #                    labels drawn on the GPU; ENCODE=gpu also JPEG-encodes them there at QUALITY, ENCODE=pil leaves that to PIL on the host;
 #                    DECODE=gpu decodes baseline JPEG files there too, by the project's own integer rule, every other file by PIL)
+#                    [TTA=flip|v5|1,0.83f,0.67 TTATHRESH=0.55]: test-time augmentation, every picture also mirrored / shrunk, the views' rows fused on the GPU
 #   make anchors     DATASET=voc ANCNUM=3 [LOW='0.0 0.0' HIGH='1.0 1.0']   (reference Makefile:78-87: k-means anchors from data/<set>_img_ann.npy)
 #                    [ANCDEVICE=gpu RESTARTS=256 ANCSEED=0]: RESTARTS random starts in one GPU call; the set with the highest mean IoU is
 #                    kept and that IoU printed (ANCDEVICE=cpu RESTARTS=N loops the same rule in numpy)
@@ -59,6 +61,10 @@ TILEOVERLAP   ?= 0.2
 TILEFULL      ?= True
 TILEMATCH     ?= ios
 TILETHRESH    ?= 0.5
+# detect, eval: test-time augmentation, TTA=a comma list of gains in (0, 1], f appended for a mirrored view (flip = 1,1f; v5 = 1,0.83f,0.67):
+# every picture runs once per view and the rows are fused by Weighted Boxes Fusion on the GPU (k210_yolo_framework_amd/tta.py); empty = off
+TTA           ?=
+TTATHRESH     ?= 0.55
 CKPT          ?= ""
 IMG           ?= data/synthetic_320x224.jpg
 # training only
@@ -139,6 +145,7 @@ NET_ARGS   = --train_set $(DATASET) --class_num $(CLSNUM) --model_def $(MODEL) -
 # (nothing for the default rule: the command lines of the three targets stay what they were)
 NMS_ARGS   = $(if $(filter-out hard,$(NMS)),--nms $(NMS) --nms_sigma $(NMSSIGMA))
 TILE_ARGS  = $(if $(TILES),--tiles $(TILES) --tile_overlap $(TILEOVERLAP) --tile_full $(TILEFULL) --tile_match $(TILEMATCH) --tile_thresh $(TILETHRESH))
+TTA_ARGS   = $(if $(TTA),--tta $(TTA) --tta_thresh $(TTATHRESH))
 TRAIN_ARGS = --pre_ckpt $(CKPT) --augmenter $(IAA) --batch_size $(BATCH) --rand_seed 3 --max_nrof_epochs $(MAXEP) \
              --init_learning_rate $(ILR) --learning_rate_decay_factor $(LRDECAYFACTOR) --obj_weight $(OBJWEIGHT) \
              --noobj_weight $(NOOBJWEIGHT) --wh_weight $(WHWEIGHT) --vaildation_split $(SPLITFACTOR) --log_dir log \
@@ -188,11 +195,11 @@ kmodel:
 eval:
 	$(PY) keras_eval.py $(CKPT) --train_set $(DATASET) --class_num $(CLSNUM) --model_def $(MODEL) --depth_multiplier $(DEPTHMUL) \
 		--image_size $(IMGSIZE) --output_size $(OUTSIZE) --iou_thresh $(IOUTHRESH) --precision $(PRECISION) --obj_thresh $(EVALOBJ) \
-		--voc07 $(VOC07) $(if $(filter-out 0,$(SYNTHETIC)),--synthetic $(SYNTHETIC),--ann $(ANN)) $(if $(METRIC),--metric $(METRIC)) $(NMS_ARGS) $(TILE_ARGS)
+		--voc07 $(VOC07) $(if $(filter-out 0,$(SYNTHETIC)),--synthetic $(SYNTHETIC),--ann $(ANN)) $(if $(METRIC),--metric $(METRIC)) $(NMS_ARGS) $(TILE_ARGS) $(TTA_ARGS)
 
 # every picture of SRC (a folder or a text list) -> OUTDIR/detections.json + OUTDIR/<stem>_res.jpg; batches of BATCH pictures of any sizes
 detect:
-	$(PY) keras_detect.py $(CKPT) $(SRC) --out_dir $(OUTDIR) --draw $(DRAW) --decode $(DECODE) --encode $(ENCODE) --quality $(QUALITY) --batch $(BATCH) --precision $(PRECISION) $(NET_ARGS) $(NMS_ARGS) $(TILE_ARGS)
+	$(PY) keras_detect.py $(CKPT) $(SRC) --out_dir $(OUTDIR) --draw $(DRAW) --decode $(DECODE) --encode $(ENCODE) --quality $(QUALITY) --batch $(BATCH) --precision $(PRECISION) $(NET_ARGS) $(NMS_ARGS) $(TILE_ARGS) $(TTA_ARGS)
 
 # reference Makefile:78-87 (same flags; --is_random True as there)
 anchors:

@@ -275,6 +275,32 @@ int yk_merge_tiles(const float *d_dets, const int32_t *d_counts, const float *d_
 /* Candidates of one (picture, class) that yk_merge_tiles with these sizes stages in LDS on the current device; more take the global path. */
 int yk_merge_tiles_lds_candidates(int n_tiles, int n_pics, int max_out);
 
+/* ---- test-time augmentation: the rows of the view frames of a picture fused into one row set (k210_yolo_framework_amd/tta.py states the
+ * rule, Weighted Boxes Fusion).  d_dets [n_pics * views][class_num*max_out][6] and d_counts [n_pics * views] as yk_decode_py*
+ * leaves them (counts are clamped to [0, class_num*max_out]); the frames of picture p are p*views .. (p+1)*views - 1 and N = views.
+ * d_xform [n_pics * views][3] float (dy, dx, mw) per frame: a row is mapped back by left' = mw - right, right' = mw - left when mw >= 0, then
+ * top, bottom += dy and left, right += dx, one float operation each.  Candidates of a picture: every row of its frames, frame by frame, in
+ * row order, mapped back.  A row whose class is not exactly one of 0 .. class_num - 1, or whose score is not above 0 (a NaN included), is
+ * dropped.  Per (picture, class) the candidates are walked by score descending (ties: the lowest candidate index) against the clusters made so
+ * far, in creation order: the cluster whose current fused box has the largest IoU with the candidate (the IoU of yk_decode_py's own NMS; ties:
+ * the lowest cluster index) takes it when that IoU is > thresh, otherwise the candidate opens a cluster.  A cluster accumulates, in join
+ * order, sw += s and (st, sl, sb, sr) += s * (top, left, bottom, right); its box is its member's verbatim while it has one and
+ * (st, sl, sb, sr) / sw afterwards; its score is ((sw / cnt) * min(cnt, N)) / N.  Every step one float operation, no contraction.
+ * d_out [n_pics][class_num*max_out][6] (class-major ascending; within a class by final score descending, ties to the older cluster, at most
+ * max_out) and d_out_counts [n_pics]: the decode's padded form, so yk_draw_dets_u8, yk_map_append_padded and the copies downstream take it
+ * unchanged; rows past the count are not written.  One wavefront per (picture, class), candidates and clusters in LDS, no atomics: two calls
+ * give the same bytes.  There is one path: views * max_out must not exceed yk_fuse_views_lds_candidates(max_out), and more is refused, never
+ * truncated.  (That bound is the decode's: a frame holds at most max_out rows of a class.  Frames that are not decode-shaped may hold more; of a
+ * class's candidates only the first views * max_out in candidate order are then read.)  Two launches on `stream`; can be recorded in a graph once the stream's scratch has been sized by an eager call of the same
+ * size.  A NULL pointer, views <= 0 or > 8, n_pics <= 0, class_num <= 0, max_out <= 0, a thresh that is NaN or negative, 2^31 or more input
+ * rows, or views * max_out above the capacity: YK_ERR_ARG with the argument named in yk_last_error, nothing launched. */
+#define YK_TTA_MAX_VIEWS 8
+int yk_fuse_views(const float *d_dets, const int32_t *d_counts, const float *d_xform, int views, int n_pics, int class_num, int max_out,
+                  float thresh, float *d_out, int32_t *d_out_counts, void *stream);
+/* Candidates of one (picture, class), views * max_out, that yk_fuse_views holds in LDS on the current device (68 bytes each); max_out <= 0:
+ * YK_ERR_ARG, no device: YK_ERR_NO_DEVICE. */
+int yk_fuse_views_lds_candidates(int max_out);
+
 /* ---- a step as one hipGraph (the kpu_run_kmodel(..., dma, ai_done_cb) shape of main.c:303-311: submit once, get called back) ----
  * Everything issued on `stream` (a created stream, not NULL) between yk_graph_begin and yk_graph_end - yk_run_*, yk_decode_py*,
  * yk_letterbox_u8, yk_memcpy_async - is recorded, not executed; yk_graph_launch replays the recording with ONE host call.
@@ -380,6 +406,30 @@ int yk_letterbox_tiles_params(yk_tile_row_t *h_table, int n, int dst_h, int dst_
  * with h <= 0, w <= 0, stride < 3*w or offset + (h-1)*stride + 3*w > src_bytes is written as zeros and nothing of d_src is read for it.
  * Can be recorded in a graph. */
 int yk_letterbox_tiles_u8(const uint8_t *d_src, size_t src_bytes, const yk_tile_row_t *d_table, int n, uint8_t *d_dst, int dst_h,
+                          int dst_w, void *stream);
+/* ---- test-time augmentation: views of the pictures of a ragged batch as frames (k210_yolo_framework_amd/tta.py) ------
+ * A view is a zero canvas of ch x cw pixels with the h x w picture at byte `offset` of the packed buffer pasted at row oy, column ox,
+ * left-right mirrored when `mirror` is not 0.  The canvas is never built: its pixels are read out of the picture in place. */
+typedef struct yk_view_row {
+    uint64_t offset;    /* byte offset of the picture in the packed buffer */
+    int32_t h, w;       /* the picture's size */
+    int32_t ch, cw;     /* the canvas */
+    int32_t oy, ox;     /* where the picture sits in it */
+    int32_t mirror;     /* not 0: canvas pixel (y, x) inside the picture is picture pixel (y - oy, w - 1 - (x - ox)) */
+    int32_t reserved;   /* 0 */
+    double scale;       /* letterbox of the canvas into dst_h x dst_w: yk_letterbox_views_params fills these three */
+    int32_t tx, ty;
+} yk_view_row_t;        /* 56 bytes, no padding */
+/* HOST helper: fills scale, tx, ty of n rows in host memory with the arithmetic yk_letterbox_ragged_params uses for (ch, cw) -> (dst_h, dst_w).
+ * A row with ch <= 0 or cw <= 0, a NULL table, n <= 0 or a non-positive dst size: YK_ERR_ARG.  Needs no device. */
+int yk_letterbox_views_params(yk_view_row_t *h_table, int n, int dst_h, int dst_w);
+/* One launch for all views (one thread per output pixel): d_dst [n][dst_h][dst_w][3]; frame v equals yk_letterbox_u8 of the canvas of view v,
+ * bit for bit - the same per-pixel arithmetic; a tap outside the pasted picture reads 0, a tap inside reads picture pixel (y - oy, x - ox),
+ * or (y - oy, w - 1 - (x - ox)) when mirrored.  d_table is DEVICE memory: NULL pointers, n <= 0, src_bytes == 0 and non-positive dst sizes are
+ * YK_ERR_ARG here, refusing bad rows is the caller's job (engine.letterbox_views_u8 does it on the host table).  The kernel does not trust the
+ * table either: the frame of a row with h <= 0, w <= 0, a picture that is not inside its canvas (oy < 0, oy + h > ch, ox < 0, ox + w > cw) or
+ * offset + 3*h*w > src_bytes is written as zeros and nothing of d_src is read for it.  Can be recorded in a graph. */
+int yk_letterbox_views_u8(const uint8_t *d_src, size_t src_bytes, const yk_view_row_t *d_table, int n, uint8_t *d_dst, int dst_h,
                           int dst_w, void *stream);
 /* ---- mosaic: one training frame from four pictures (k210_yolo_framework_amd/mosaic.py) ------
  * A sample is four table rows in quadrant order - 0 top left [0,cx) x [0,cy), 1 top right [cx,W) x [0,cy), 2 bottom left, 3 bottom right -

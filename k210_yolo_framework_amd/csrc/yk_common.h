@@ -57,6 +57,7 @@ enum yk_scratch_slot {
     YK_SLOT_PRUNE = 24,           // yk_prune.hip: the histograms and thresholds of one magnitude-pruning call
     YK_SLOT_DISTILL = 25,         // yk_distill.hip: the distillation loss's partial sums per (image, chunk)
     YK_SLOT_TILES = 26,           // yk_tiles.hip: cursors, overflow lists, selections and counts of one yk_merge_tiles call
+    YK_SLOT_TTA = 27,             // yk_tta.hip: the fused rows per (picture, class) and their counts of one yk_fuse_views call
 };
 void *yk_scratch(int device, void *stream, int slot, size_t bytes);
 void yk_scratch_release_stream(void *stream);

@@ -14,24 +14,28 @@
 // The per-image max normalisation that follows (utils.py:405) is fused into the stem conv (yk_run_u8).
 #include "yk_common.h"
 
-// One letterboxed pixel (x, y) of the network tensor from source frame `im`, sh rows of sw pixels `stride` bytes apart: the arithmetic above,
-// truncating cast.
-__device__ __forceinline__ void letterbox_px(const uint8_t *__restrict__ im, int sh, int sw, size_t stride, double scale, int tx, int ty, int x,
-                                             int y, uint8_t out[3]) {
+// One letterboxed pixel (x, y) of the network tensor from a source of sh x sw pixels: the arithmetic above, truncating cast.  tap(yy, xx, ch)
+// is the source's byte at a position inside it; a tap outside reads 0.
+template <class Tap>
+__device__ __forceinline__ void letterbox_px_of(Tap tap, int sh, int sw, double scale, int tx, int ty, int x, int y, uint8_t out[3]) {
     const double inv = 1.0 / scale;
     const double c = inv * (double)x + (-((double)tx * inv)), r = inv * (double)y + (-((double)ty * inv));
     const double minc_f = floor(c), minr_f = floor(r);
     const int minc = (int)minc_f, minr = (int)minr_f, maxc = (int)ceil(c), maxr = (int)ceil(r);
     const double dc = c - minc_f, dr = r - minr_f;
-    auto px = [&](int yy, int xx, int ch) -> double {
-        return (yy >= 0 && yy < sh && xx >= 0 && xx < sw) ? (double)im[(size_t)yy * stride + (size_t)xx * 3 + ch] : 0.0;
-    };
+    auto px = [&](int yy, int xx, int ch) -> double { return (yy >= 0 && yy < sh && xx >= 0 && xx < sw) ? (double)tap(yy, xx, ch) : 0.0; };
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch) {
         const double top = (1.0 - dc) * px(minr, minc, ch) + dc * px(minr, maxc, ch);
         const double bottom = (1.0 - dc) * px(maxr, minc, ch) + dc * px(maxr, maxc, ch);
         out[ch] = (uint8_t)((1.0 - dr) * top + dr * bottom);    // astype('uint8'): truncation
     }
+}
+
+// ... from source frame `im`, sh rows of sw pixels `stride` bytes apart
+__device__ __forceinline__ void letterbox_px(const uint8_t *__restrict__ im, int sh, int sw, size_t stride, double scale, int tx, int ty, int x,
+                                             int y, uint8_t out[3]) {
+    letterbox_px_of([&](int yy, int xx, int ch) { return im[(size_t)yy * stride + (size_t)xx * 3 + ch]; }, sh, sw, scale, tx, ty, x, y, out);
 }
 
 // ... from a contiguous frame [sh][sw][3]
@@ -201,6 +205,79 @@ extern "C" int yk_letterbox_tiles_u8(const uint8_t *d_src, size_t src_bytes, con
     for (int base = 0; base < n; base += 65535) {                                 // grid.y holds at most 65535 tiles
         const int m = n - base < 65535 ? n - base : 65535;
         hipLaunchKernelGGL(letterbox_tiles_u8_kernel, dim3((unsigned)((per + 255) / 256), (unsigned)m), dim3(256), 0, (hipStream_t)stream,
+                           d_src, src_bytes, d_table + base, d_dst + (size_t)base * per * 3, dst_h, dst_w);
+    }
+    YK_HIP(hipGetLastError());
+    return YK_OK;
+}
+
+// ---- the same letterbox for VIEWS of the pictures of a ragged batch (test-time augmentation: k210_yolo_framework_amd/tta.py): a
+// view is a zero canvas of ch x cw pixels with the picture pasted at (oy, ox), mirrored or not.  The canvas is the source letterbox_px_of sees,
+// its taps read out of the picture in place, so frame v is yk_letterbox_u8 of the canvas, bit for bit, and no canvas is ever written.
+static_assert(sizeof(yk_view_row_t) == 56, "yk_view_row_t has no padding");
+__global__ void __launch_bounds__(256) letterbox_views_u8_kernel(const uint8_t *__restrict__ src, size_t src_bytes,
+                                                                 const yk_view_row_t *__restrict__ table, uint8_t *__restrict__ dst, int dh,
+                                                                 int dw) {
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t per = (size_t)dh * dw;
+    if (idx >= per) return;
+    const yk_view_row_t row = table[blockIdx.y];
+    const int x = (int)(idx % dw), y = (int)(idx / dw);
+    uint8_t v[3] = {0, 0, 0};
+    // a row the host should have refused: nothing of src is read for it.  The sums are taken in 64 bits, so none can overflow
+    const bool ok = row.h > 0 && row.w > 0 && row.oy >= 0 && row.ox >= 0 && (int64_t)row.oy + row.h <= (int64_t)row.ch &&
+                    (int64_t)row.ox + row.w <= (int64_t)row.cw && row.offset <= src_bytes && (size_t)row.h * row.w * 3 <= src_bytes - row.offset;
+    if (ok) {
+        const uint8_t *im = src + row.offset;
+        const int h = row.h, w = row.w, oy = row.oy, ox = row.ox;
+        const bool mirror = row.mirror != 0;
+        letterbox_px_of(
+            [&](int yy, int xx, int ch) -> uint8_t {
+                const int py = yy - oy, qx = xx - ox;                  // yy in [0, ch), oy in [0, ch]: no overflow
+                if (py < 0 || py >= h || qx < 0 || qx >= w) return 0;
+                return im[((size_t)py * w + (size_t)(mirror ? w - 1 - qx : qx)) * 3 + ch];
+            },
+            row.ch, row.cw, row.scale, row.tx, row.ty, x, y, v);
+    }
+    uint8_t *o = dst + ((size_t)blockIdx.y * per + idx) * 3;
+    o[0] = v[0];
+    o[1] = v[1];
+    o[2] = v[2];
+}
+
+extern "C" int yk_letterbox_views_params(yk_view_row_t *h_table, int n, int dst_h, int dst_w) {
+    if (!h_table || n <= 0 || dst_h <= 0 || dst_w <= 0) {
+        yk_set_error("yk_letterbox_views_params: bad argument");
+        return YK_ERR_ARG;
+    }
+    for (int i = 0; i < n; ++i)
+        if (h_table[i].ch <= 0 || h_table[i].cw <= 0) {
+            yk_set_error("yk_letterbox_views_params: row %d has a canvas of %d x %d", i, (int)h_table[i].ch, (int)h_table[i].cw);
+            return YK_ERR_ARG;
+        }
+    for (int i = 0; i < n; ++i) {
+        int tx, ty;
+        letterbox_params(h_table[i].ch, h_table[i].cw, dst_h, dst_w, &h_table[i].scale, &tx, &ty);
+        h_table[i].tx = tx;
+        h_table[i].ty = ty;
+    }
+    return YK_OK;
+}
+
+extern "C" int yk_letterbox_views_u8(const uint8_t *d_src, size_t src_bytes, const yk_view_row_t *d_table, int n, uint8_t *d_dst, int dst_h,
+                                     int dst_w, void *stream) {
+    if (!d_src || !d_table || !d_dst || n <= 0 || src_bytes == 0 || dst_h <= 0 || dst_w <= 0) {
+        yk_set_error("yk_letterbox_views_u8: bad argument");
+        return YK_ERR_ARG;
+    }
+    if (yk_current_device() < 0) {
+        yk_set_error("yk_letterbox_views_u8: no HIP device");
+        return YK_ERR_NO_DEVICE;
+    }
+    const size_t per = (size_t)dst_h * dst_w;
+    for (int base = 0; base < n; base += 65535) {                                 // grid.y holds at most 65535 views
+        const int m = n - base < 65535 ? n - base : 65535;
+        hipLaunchKernelGGL(letterbox_views_u8_kernel, dim3((unsigned)((per + 255) / 256), (unsigned)m), dim3(256), 0, (hipStream_t)stream,
                            d_src, src_bytes, d_table + base, d_dst + (size_t)base * per * 3, dst_h, dst_w);
     }
     YK_HIP(hipGetLastError());

@@ -2,6 +2,7 @@
 
     python keras_detect.py CKPT SRC --out_dir D [--draw True|False] [--decode pil|gpu] [--encode pil|gpu] [--quality 75] [--batch 32] [--depth 4]
                            [--tiles NXxNY --tile_overlap 0.2 --tile_full True --tile_match ios|iou --tile_thresh 0.5]
+                           [--tta 1,1f|flip|v5 --tta_thresh 0.55]
                            [network and threshold flags of keras_inference.py]
 
 SRC: a folder (its .jpg / .jpeg / .png / .bmp files, in sorted order), a text file with one picture path per line, or one picture.
@@ -32,6 +33,7 @@ from . import draw as dr
 from . import jpeg
 from . import softnms
 from . import tiles as tl
+from . import tta as tt
 from .helper import INFO, NOTE, Helper, VOC_ANCHORS
 from .yolonet import MODEL_DEFS
 
@@ -65,6 +67,7 @@ def parse(argv=None):
     p.add_argument('--nms', type=str, default='hard', help="suppression rule of the decode: hard (the reference's), linear or gaussian (Soft-NMS), diou")
     p.add_argument('--nms_sigma', type=float, default=0.5, help='sigma of --nms gaussian')
     tl.add_arguments(p)
+    tt.add_arguments(p)
     a = p.parse_args(sys.argv[1:] if argv is None else argv)
     if (a.precision == 'kpu') != a.pre_ckpt.endswith(('.kmodel', '.kfpkg')):
         p.error('--precision kpu runs a .kmodel / .kfpkg checkpoint, and only it does (the float modes take .h5 / .npz)')
@@ -78,8 +81,11 @@ def parse(argv=None):
         p.error(str(e))
     try:
         tl.parse_arguments(a)
+        tt.parse_arguments(a)
     except ValueError as e:
         p.error(str(e))
+    if a.tta is not None and len(a.tta) > a.batch:
+        p.error(f'--tta {tt.text_of(a.tta)}: a picture is {len(a.tta)} frames and --batch holds {a.batch}')
     a.draw = a.draw == 'True'
     return a
 
@@ -138,14 +144,14 @@ class _Stage:
         self.pinned = self.d_packed = self.h_dets = self.h_counts = None
         self.d_work = self.d_scan = self.h_scan = self.d_off = self.h_off = None       # encode='gpu'
         self.d_stage = self.d_jwork = self.d_jstatus = self.h_jstatus = None           # decode='gpu'
-        self.d_mdets = self.d_mcounts = None                                            # tiles: the merged rows per picture
+        self.d_mdets = self.d_mcounts = None                                            # tiles, tta: the merged / fused rows per picture
 
 
 def run(h: Helper, model, sources, out_dir=None, draw: bool = True, batch: int = 32, depth: int = 4, precision: str = 'f16x2',
         obj_thresh: float = 0.7, iou_thresh: float = 0.3, workers: int = 8, names: Optional[Sequence[str]] = None,
         return_arrays: bool = False, verbose: bool = True, max_out: int = 30, encode: str = 'pil', quality: int = 75, decode: str = 'pil',
         nms: str = 'hard', nms_sigma: float = 0.5, tiles=None, tile_overlap: float = 0.2, tile_full: bool = True, tile_match: str = 'ios',
-        tile_thresh: float = 0.5):
+        tile_thresh: float = 0.5, tta=None, tta_thresh: float = 0.55):
     """sources: picture paths, or [h, w, 3] uint8 arrays already in memory (then `names` names them); with decode='gpu' paths or the bytes of
     picture files: baseline JPEGs are decoded on the device by the rule of include/yolo_hip.h (not PIL's bytes: DESIGN.md 3.12), every other
     file by PIL on the pool as with decode='pil'; a stream the device cannot finish raises YkError naming the file.  -> {'names', 'detections': one
@@ -156,7 +162,11 @@ def run(h: Helper, model, sources, out_dir=None, draw: bool = True, batch: int =
     tiles=(nx, ny): sliced inference (tiles.py) - every picture runs as nx * ny overlapping tiles (tile_overlap of a tile's
     side) plus, with tile_full, the whole picture, each a network frame of its own (yk_letterbox_tiles_u8 cuts them out of the resident
     originals), and yk_merge_tiles turns their rows into the picture's rows by a hard NMS at tile_thresh under tile_match ('ios' or 'iou');
-    a batch then holds max(1, batch // frames per picture) pictures.  None (the default): everything as without the option."""
+    a batch then holds max(1, batch // frames per picture) pictures.  None (the default): everything as without the option.
+    tta='1,0.83f,0.67' | 'flip' | 'v5' | ((gain, mirror), ...): test-time augmentation (tta.py) - every picture runs as one
+    frame per view (yk_letterbox_views_u8 reads the shrunk and mirrored canvases out of the resident originals), each decoded at its canvas's
+    size, and yk_fuse_views fuses their rows by Weighted Boxes Fusion at IoU > tta_thresh; a batch holds batch // views pictures (more views
+    than `batch` are refused), and tta together with tiles or with a soft nms is refused.  None (the default): everything as without it."""
     import torch
     from . import engine
     engine.require_gpu()
@@ -176,6 +186,14 @@ def run(h: Helper, model, sources, out_dir=None, draw: bool = True, batch: int =
     except ValueError as e:
         raise engine.YkError(f'detect: {e}') from None
     T = 1 if grid_xy is None else grid_xy[0] * grid_xy[1] + (1 if tile_full else 0)      # network frames per picture
+    try:
+        tta_spec = tt.check(tta, tta_thresh, nms, tiles)
+    except ValueError as e:
+        raise engine.YkError(f'detect: {e}') from None
+    if tta_spec is not None:
+        T = len(tta_spec)
+        if T > int(batch):
+            raise engine.YkError(f'detect: tta {tt.text_of(tta_spec)}: a picture is {T} frames and a batch holds {int(batch)}')
     gpu_decode = decode == 'gpu'
     in_memory = isinstance(sources[0], (np.ndarray, bytes))
     if gpu_decode and any(isinstance(s, np.ndarray) for s in sources):
@@ -356,7 +374,20 @@ def run(h: Helper, model, sources, out_dir=None, draw: bool = True, batch: int =
                 keep = (table_d, None)
             nf = n * T                                                                      # network frames of this batch
             dst = pipe.input(slot)[:nf] if pipe is not None else frames[:nf]
-            if grid_xy is None:
+            if tta_spec is not None:
+                vws = [tt.views(sh, sw, tta_spec) for sh, sw in shapes]
+                rows = np.concatenate([tt.table_rows(v, int(table['offset'][i]), *shapes[i]) for i, v in enumerate(vws)])
+                v_all = np.concatenate(vws)
+                views_d = engine.view_table_to_device(rows, in_hw, total, dev)             # (blocking copies of a few bytes per view, as above)
+                engine.letterbox_views_u8(d_packed, views_d, in_hw, stream=stream, out=dst)
+                hw = v_all[:, 0:2].astype(np.float32)                                       # every frame is decoded at its canvas's size
+                xform_d = torch.from_numpy(tt.xforms(v_all)).to(dev)
+                if st.d_mdets is None:
+                    st.d_mdets = torch.zeros((B, cap, 6), dtype=torch.float32, device=dev)
+                    st.d_mcounts = torch.zeros((B,), dtype=torch.int32, device=dev)
+                    torch.cuda.current_stream().synchronize()                               # (filled on torch's stream, written on the slot's)
+                keep = (*keep, views_d, xform_d)
+            elif grid_xy is None:
                 engine.letterbox_ragged_u8(d_packed, table_d, in_hw, stream=stream, out=dst)
                 hw = np.asarray(shapes, np.float32)
             else:
@@ -381,6 +412,9 @@ def run(h: Helper, model, sources, out_dir=None, draw: bool = True, batch: int =
             if grid_xy is not None:
                 dets, counts = engine.merge_tiles(dets, counts, origin_d, first_d, h.class_num, max_out, tile_thresh, tile_match, stream=stream,
                                                   out=st.d_mdets[:n], out_counts=st.d_mcounts[:n])
+            if tta_spec is not None:
+                dets, counts = engine.fuse_views(dets, counts, xform_d, T, h.class_num, max_out, tta_thresh, stream=stream, out=st.d_mdets[:n],
+                                                 out_counts=st.d_mcounts[:n])
             if want_pixels:
                 max_px = int(max(s[0] * s[1] for s in shapes))
                 engine.draw_detections_u8(d_packed, table_d, dets, counts, colormap, atlas, stream=stream, max_pixels=max_px)
@@ -415,6 +449,8 @@ def run(h: Helper, model, sources, out_dir=None, draw: bool = True, batch: int =
         if grid_xy is not None:
             rule.update(tiles=[int(grid_xy[0]), int(grid_xy[1])], tile_overlap=float(tile_overlap), tile_full=bool(tile_full), tile_match=tile_match,
                         tile_thresh=float(tile_thresh))
+        if tta_spec is not None:
+            rule.update(tt.rule_of(tta_spec, tta_thresh))
         doc = [{'path': names[i], **rule, 'detections': [[float(v) for v in row] for row in results[i]]} for i in range(n_all)]
         (Path(out_dir) / 'detections.json').write_text(json.dumps(doc, indent=1))
     out = {'names': names, 'detections': results, 'files': written}
@@ -442,11 +478,13 @@ def main(argv=None):
         raise engine.YkError(f'detect: no pictures ({", ".join(EXTENSIONS)}) in {a.src}')
     res = run(h, model, paths, out_dir=a.out_dir, draw=a.draw, batch=a.batch, depth=a.depth, precision=a.precision,
               obj_thresh=a.obj_thresh, iou_thresh=a.iou_thresh, workers=a.workers, encode=a.encode, quality=a.quality, decode=a.decode,
-              nms=a.nms, nms_sigma=a.nms_sigma, **tl.run_options(a))
+              nms=a.nms, nms_sigma=a.nms_sigma, **tl.run_options(a), **tt.run_options(a))
     if a.nms != 'hard':
         print(INFO, f' nms {a.nms}, sigma {a.nms_sigma:g}: scores are the decayed ones')
     if a.tiles is not None:
         print(INFO, f' tiles {a.tiles[0]}x{a.tiles[1]}, overlap {a.tile_overlap:g}, whole picture {a.tile_full}: merged by {a.tile_match} > {a.tile_thresh:g}')
+    if a.tta is not None:
+        print(INFO, f' tta {tt.text_of(a.tta)}: {len(a.tta)} views a picture, fused by IoU > {a.tta_thresh:g} (tta.py); scores are the fused ones')
     print(INFO, f' {len(paths)} pictures, {sum(len(d) for d in res["detections"])} detections -> {Path(a.out_dir) / "detections.json"}'
           + (f', {len(res["files"])} annotated pictures' if a.draw else ''))
     return res

@@ -666,6 +666,99 @@ def merge_tiles(dets, counts, origins, first, class_num: int, max_out: int, thre
     return out, out_counts
 
 
+def check_view_rows(table, packed_bytes: int) -> np.ndarray:
+    """The rows of a host view table (tta.VIEW_DTYPE = yk_view_row_t) as one flat copy, refused with YkError unless every row is a non-empty
+    picture inside the `packed_bytes` of its buffer and inside its canvas: what yk_letterbox_views_u8 would otherwise answer with a zero
+    frame."""
+    from .tta import VIEW_DTYPE
+    t = np.array(table, dtype=VIEW_DTYPE, copy=True).reshape(-1)
+    bad = (t['h'] <= 0) | (t['w'] <= 0)
+    if bad.any():
+        i = int(np.nonzero(bad)[0][0])
+        raise YkError(f'view table: row {i} is {int(t["h"][i])} x {int(t["w"][i])}')
+    i64 = lambda name: t[name].astype(np.int64)
+    bad = (t['oy'] < 0) | (t['ox'] < 0) | (i64('oy') + i64('h') > i64('ch')) | (i64('ox') + i64('w') > i64('cw'))
+    if bad.any():
+        i = int(np.nonzero(bad)[0][0])
+        raise YkError(f'view table: row {i} puts its {int(t["h"][i])} x {int(t["w"][i])} picture at ({int(t["oy"][i])}, {int(t["ox"][i])}), outside its '
+                      f'canvas of {int(t["ch"][i])} x {int(t["cw"][i])}')
+    end = t['offset'].astype(object) + 3 * t['h'].astype(object) * t['w'].astype(object)
+    if len(t) and max(end) > int(packed_bytes):
+        raise YkError(f'view table: row {int(np.argmax(end))} ends at byte {max(end)} of a {int(packed_bytes)}-byte buffer')
+    return t
+
+
+def view_table_to_device(table, dst_hw, packed_bytes: int, device, stream=None):
+    """A host view table (tta.table_rows) checked (check_view_rows), its scale / tx / ty filled for the network size dst_hw and uploaded
+    -> cuda uint8 [n, 56], what letterbox_views_u8 takes as its table."""
+    import torch
+    t = check_view_rows(table, packed_bytes)
+    if len(t) == 0:
+        raise YkError('view table: no rows')
+    call('yk_letterbox_views_params', t, len(t), int(dst_hw[0]), int(dst_hw[1]))
+    host = torch.from_numpy(t.view(np.uint8).reshape(len(t), t.dtype.itemsize))
+    with torch.cuda.stream(torch.cuda.current_stream() if stream is None else stream):
+        return host.to(device, non_blocking=False)
+
+
+def letterbox_views_u8(packed, table, dst_hw, stream=None, out=None):
+    """Views of the pictures of a packed buffer (test-time augmentation, tta.py) letterboxed into network frames in one launch
+    (yk_letterbox_views_u8): `packed` cuda uint8 [bytes]; `table` a host table of tta.VIEW_DTYPE (checked here: a row the kernel would answer
+    with zeros is refused) or the device table view_table_to_device returned for this dst_hw.  -> cuda uint8 [n, H, W, 3]; frame v is bit for
+    bit letterbox_u8 of the canvas of view v (tta.canvas)."""
+    import torch
+    from .tta import VIEW_DTYPE
+    require_gpu()
+    assert packed.is_cuda and packed.dtype == torch.uint8 and packed.is_contiguous() and packed.numel() > 0
+    if not torch.is_tensor(table):
+        table = view_table_to_device(table, dst_hw, packed.numel(), packed.device, stream)
+    assert table.is_cuda and table.dtype == torch.uint8 and table.is_contiguous() and table.dim() == 2 and table.device == packed.device
+    assert table.shape[1] == VIEW_DTYPE.itemsize and table.shape[0] > 0, tuple(table.shape)
+    n = int(table.shape[0])
+    if out is None:
+        out = torch.empty((n, int(dst_hw[0]), int(dst_hw[1]), 3), dtype=torch.uint8, device=packed.device)
+    assert out.is_cuda and out.is_contiguous() and tuple(out.shape) == (n, int(dst_hw[0]), int(dst_hw[1]), 3), tuple(out.shape)
+    call('yk_letterbox_views_u8', packed, packed.numel(), table, n, out, out.shape[1], out.shape[2], _stream(stream))
+    return out
+
+
+def fuse_views_lds_candidates(max_out: int) -> int:
+    """Candidates of one (picture, class), views * max_out, that fuse_views holds in LDS on the current device; more are refused."""
+    n = lib().yk_fuse_views_lds_candidates(int(max_out))
+    if n < 0:
+        _check(n, 'yk_fuse_views_lds_candidates')
+    return int(n)
+
+
+def fuse_views(dets, counts, xforms, views: int, class_num: int, max_out: int, thresh: float = 0.55, stream=None, out=None, out_counts=None):
+    """The rows of view frames fused into one padded row set per picture (yk_fuse_views; the rule is tta.fuse): dets cuda fp32
+    [n_pics * views, class_num * max_out, 6] and counts cuda int32 [n_pics * views] as decode_py / Pipeline.submit leave them, the frames of
+    picture p being p * views .. (p + 1) * views - 1; xforms (dy, dx, mw) per frame (tta.xforms), a host array or cuda float32
+    [n_pics * views, 3].  -> (rows cuda fp32 [n_pics, class_num * max_out, 6], counts cuda int32 [n_pics])."""
+    import torch
+    require_gpu()
+    cap = int(class_num) * int(max_out)
+    views = int(views)
+    assert dets.is_cuda and dets.dtype == torch.float32 and dets.is_contiguous() and dets.dim() == 3 and tuple(dets.shape[1:]) == (cap, 6), tuple(dets.shape)
+    n_frames = int(dets.shape[0])
+    if views < 1 or n_frames % views:
+        raise YkError(f'fuse_views: {n_frames} frames are not whole pictures of {views} views')
+    n_pics = n_frames // views
+    assert counts.is_cuda and counts.dtype == torch.int32 and counts.is_contiguous() and tuple(counts.shape) == (n_frames,)
+    if not torch.is_tensor(xforms):
+        with torch.cuda.stream(torch.cuda.current_stream() if stream is None else stream):
+            xforms = torch.from_numpy(np.ascontiguousarray(xforms, np.float32).reshape(-1, 3)).to(dets.device)
+    assert xforms.is_cuda and xforms.dtype == torch.float32 and xforms.is_contiguous() and tuple(xforms.shape) == (n_frames, 3), tuple(xforms.shape)
+    if out is None:
+        out = torch.zeros((n_pics, cap, 6), dtype=torch.float32, device=dets.device)
+    if out_counts is None:
+        out_counts = torch.zeros((n_pics,), dtype=torch.int32, device=dets.device)
+    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (n_pics, cap, 6), tuple(out.shape)
+    assert out_counts.is_cuda and out_counts.dtype == torch.int32 and out_counts.is_contiguous() and tuple(out_counts.shape) == (n_pics,)
+    call('yk_fuse_views', dets, counts, xforms, views, n_pics, int(class_num), int(max_out), float(thresh), out, out_counts, _stream(stream))
+    return out, out_counts
+
+
 def mosaic_ragged_u8(packed, table, centres, dst_hw, inv=None, stream=None, out=None):
     """One training frame from four pictures per sample, the whole batch in one launch (yk_mosaic_ragged_u8; the rule is in mosaic.py):
     `packed` cuda uint8 [bytes], the pictures of draw.pack_ragged; `table` the samples' rows in quadrant order with scale / tx / ty filled

@@ -6,6 +6,7 @@
                               [--nms hard|linear|gaussian|diou] [--nms_sigma 0.5]
                               [--metric voc|coco] [--out eval.json] [--dump_rows rows.npz]
                               [--tiles NXxNY --tile_overlap 0.2 --tile_full True --tile_match ios|iou --tile_thresh 0.5]
+                              [--tta 1,1f|flip|v5 --tta_thresh 0.55]
 
 CKPT: a Keras `.h5` / `.npz` checkpoint (float modes, through engine.Pipeline with several batches in flight) or a `.kmodel` / `.kfpkg`
 (`--precision kpu`, the K210 KPU's exact integer arithmetic through engine.KpuPlan).  The images are the validation head of the list
@@ -32,6 +33,7 @@ import numpy as np
 
 from . import softnms
 from . import tiles as tl
+from . import tta as tt
 from .helper import INFO, Helper, VOC_ANCHORS
 from .yolonet import MODEL_DEFS
 
@@ -74,6 +76,7 @@ def parse(argv=None):
     p.add_argument('--out', type=str, default=None, help='result file (default: eval.json next to the checkpoint)')
     p.add_argument('--dump_rows', type=str, default=None, help='also write the detections and the ground truth that were scored (.npz)')
     tl.add_arguments(p)
+    tt.add_arguments(p)
     a = p.parse_args(sys.argv[1:] if argv is None else argv)
     if (a.precision == 'kpu') != a.pre_ckpt.endswith(('.kmodel', '.kfpkg')):
         p.error('--precision kpu runs a .kmodel / .kfpkg checkpoint, and only it does (the float modes take .h5 / .npz)')
@@ -85,8 +88,11 @@ def parse(argv=None):
         p.error(str(e))
     try:
         tl.parse_arguments(a)
+        tt.parse_arguments(a)
     except ValueError as e:
         p.error(str(e))
+    if a.tta is not None and len(a.tta) > a.batch:
+        p.error(f'--tta {tt.text_of(a.tta)}: a picture is {len(a.tta)} frames and --batch holds {a.batch}')
     if a.metric == 'coco' and a.voc07 == 'True':
         p.error('--voc07 True is the 11-point VOC AP; --metric coco has its own 101-point AP: choose one')
     return a
@@ -114,8 +120,9 @@ def _load(h: Helper, item):
     return np.ascontiguousarray(img[..., :3], np.uint8), np.asarray(boxes, np.float64)
 
 
-def run(a, h: Helper, model, items, ev) -> None:
-    """Every image of `items` through the network and the decode; detections and ground truth into `ev`."""
+def run(a, h: Helper, model, items, ev, tta=None, tta_thresh=None) -> None:
+    """Every image of `items` through the network and the decode; detections and ground truth into `ev`.  tta / tta_thresh: test-time
+    augmentation as detect.run takes it (tta.py); left None they are read from a.tta / a.tta_thresh where `a` has them (off, 0.55)."""
     import torch
     from . import engine
     in_hw = tuple(int(v) for v in h.in_hw[0])
@@ -124,6 +131,16 @@ def run(a, h: Helper, model, items, ev) -> None:
     except ValueError as e:
         raise engine.YkError(f'evaluate: {e}') from None
     T = 1 if grid_xy is None else grid_xy[0] * grid_xy[1] + (1 if a.tile_full else 0)      # network frames per picture
+    tta = getattr(a, 'tta', None) if tta is None else tta
+    tta_thresh = getattr(a, 'tta_thresh', tt.DEFAULT_THRESH) if tta_thresh is None else tta_thresh
+    try:
+        tta_spec = tt.check(tta, tta_thresh, a.nms, a.tiles)
+    except ValueError as e:
+        raise engine.YkError(f'evaluate: {e}') from None
+    if tta_spec is not None:
+        T = len(tta_spec)
+        if T > int(a.batch):
+            raise engine.YkError(f'evaluate: tta {tt.text_of(tta_spec)}: a picture is {T} frames and a batch holds {int(a.batch)}')
     B = max(1, min(int(a.batch) // T, len(items)))
     max_out = 30
 
@@ -140,12 +157,28 @@ def run(a, h: Helper, model, items, ev) -> None:
         engine.letterbox_tiles_u8(d_packed, rows, in_hw, stream=stream, out=out)
         return d_packed, g_all[:, 2:4].astype(np.float32), np.ascontiguousarray(g_all[:, 0:2], np.float32), np.arange(len(imgs) + 1, dtype=np.int32) * T
 
+    def view_frames(imgs, out, stream):
+        """Test-time augmentation (tta.py): the pictures packed into one device buffer, their views letterboxed into `out` by one launch
+        -> (what must stay alive until the batch has run, each frame's (h, w), the frames' (dy, dx, mw))."""
+        from . import draw as dr
+        packed, table, shapes = dr.pack_ragged(imgs)
+        with torch.cuda.stream(stream):
+            d_packed = packed.to(out.device, non_blocking=False)
+        vws = [tt.views(sh, sw, tta_spec) for sh, sw in shapes]
+        rows = np.concatenate([tt.table_rows(v, int(table['offset'][i]), *shapes[i]) for i, v in enumerate(vws)])
+        v_all = np.concatenate(vws)
+        engine.letterbox_views_u8(d_packed, rows, in_hw, stream=stream, out=out)
+        return d_packed, v_all[:, 0:2].astype(np.float32), tt.xforms(v_all)
+
     if a.precision == 'kpu':
         plan = model._plan(B * T)
         cfg = engine.make_decode_cfg(h.anchors, h.class_num, h.in_hw[0], h.out_hw)
         for k in range(0, len(items), B):
             loaded = [_load(h, it) for it in items[k:k + B]]
-            if grid_xy is None:
+            if tta_spec is not None:
+                frames = torch.empty((len(loaded) * T, *in_hw, 3), dtype=torch.uint8, device='cuda')
+                _, shapes, xf = view_frames([im for im, _ in loaded], frames, torch.cuda.current_stream())
+            elif grid_xy is None:
                 frames = torch.cat([engine.letterbox_u8(torch.from_numpy(im[None]).cuda(), in_hw) for im, _ in loaded])
                 shapes = np.asarray([im.shape[:2] for im, _ in loaded], np.float32)
             else:
@@ -155,10 +188,12 @@ def run(a, h: Helper, model, items, ev) -> None:
             dets, counts = engine.decode_py(cfg, plan.outputs(), len(frames), shapes, a.obj_thresh, a.nms_iou, max_out=max_out, nms=a.nms, sigma=a.nms_sigma)
             if grid_xy is not None:
                 dets, counts = engine.merge_tiles(dets, counts, origins, first, h.class_num, max_out, a.tile_thresh, a.tile_match)
+            if tta_spec is not None:
+                dets, counts = engine.fuse_views(dets, counts, xf, T, h.class_num, max_out, tta_thresh)
             ev.add(dets, counts, [ground_truth_rows(b, im.shape[:2]) for im, b in loaded])
         return
     pipe = engine.Pipeline(model.spec, model.get_weights(), h.anchors, max_batch=B * T, depth=max(1, int(a.depth)), precision=a.precision, max_out=max_out)
-    merged = [None] * pipe.depth                            # tiles: each slot's merged rows per picture
+    merged = [None] * pipe.depth                            # tiles, tta: each slot's merged / fused rows per picture
     pending = deque()                                       # (dets, counts, stream, ground truth) of the batches in flight
 
     def drain():
@@ -172,7 +207,9 @@ def run(a, h: Helper, model, items, ev) -> None:
             loaded = [_load(h, it) for it in items[k:k + B]]
             slot = pipe.next_slot()
             buf, st = pipe.input(slot), pipe.streams[slot]
-            if grid_xy is None:
+            if tta_spec is not None:
+                keep, shapes, xf = view_frames([im for im, _ in loaded], buf[:len(loaded) * T], st)
+            elif grid_xy is None:
                 with torch.cuda.stream(st):
                     for j, (im, _) in enumerate(loaded):
                         engine.letterbox_u8(torch.from_numpy(im[None]).to(buf.device, non_blocking=False), in_hw, stream=st, out=buf[j:j + 1])
@@ -181,14 +218,18 @@ def run(a, h: Helper, model, items, ev) -> None:
                 keep, shapes, origins, first = tile_frames([im for im, _ in loaded], buf[:len(loaded) * T], st)
             dets, counts, stream = pipe.submit(None, image_hw=shapes, obj_thresh=a.obj_thresh, iou_thresh=a.nms_iou, max_out=max_out,
                                                batch=len(loaded) * T, nms=a.nms, sigma=a.nms_sigma)
-            if grid_xy is not None:
+            if grid_xy is not None or tta_spec is not None:
                 if merged[slot] is None:
                     merged[slot] = (torch.zeros((B, h.class_num * max_out, 6), dtype=torch.float32, device=buf.device),
                                     torch.zeros((B,), dtype=torch.int32, device=buf.device))
                     torch.cuda.current_stream().synchronize()           # (filled on torch's stream, written on the slot's)
-                dets, counts = engine.merge_tiles(dets, counts, origins, first, h.class_num, max_out, a.tile_thresh, a.tile_match, stream=stream,
-                                                  out=merged[slot][0][:len(loaded)], out_counts=merged[slot][1][:len(loaded)])
-                stream.synchronize()                                    # `keep`, the packed originals, may go once the tiles are cut
+                if tta_spec is not None:
+                    dets, counts = engine.fuse_views(dets, counts, xf, T, h.class_num, max_out, tta_thresh, stream=stream,
+                                                     out=merged[slot][0][:len(loaded)], out_counts=merged[slot][1][:len(loaded)])
+                else:
+                    dets, counts = engine.merge_tiles(dets, counts, origins, first, h.class_num, max_out, a.tile_thresh, a.tile_match, stream=stream,
+                                                      out=merged[slot][0][:len(loaded)], out_counts=merged[slot][1][:len(loaded)])
+                stream.synchronize()                                    # `keep`, the packed originals, may go once the frames are cut
             pending.append((dets, counts, stream, [ground_truth_rows(b, im.shape[:2]) for im, b in loaded]))
         while pending:
             drain()
@@ -259,6 +300,9 @@ def main(argv=None):
     if a.tiles is not None:
         report.update(tiles=list(a.tiles), tile_overlap=a.tile_overlap, tile_full=a.tile_full, tile_match=a.tile_match, tile_thresh=a.tile_thresh)
         print(f'   tiles {a.tiles[0]}x{a.tiles[1]}, overlap {a.tile_overlap:g}, whole picture {a.tile_full}: merged by {a.tile_match} > {a.tile_thresh:g} (tiles.py)')
+    if a.tta is not None:
+        report.update(tt.rule_of(a.tta, a.tta_thresh))
+        print(f'   tta {tt.text_of(a.tta)}: {len(a.tta)} views a picture, fused by IoU > {a.tta_thresh:g}; rows carry the fused scores (tta.py)')
     if a.metric == 'coco':
         report['coco'] = coco_report(ev, a.class_num, r['n_gt'])
     out = Path(a.out) if a.out else Path(a.pre_ckpt).resolve().parent / 'eval.json'
