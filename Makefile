@@ -31,6 +31,8 @@
 #   make eval        CKPT=yolo_model.h5|yolo.kmodel [PRECISION=f16x2|f16|kpu] [ANN=data/voc_img_ann.npy | SYNTHETIC=256] [EVALOBJ=0.05] [VOC07=True]:
 #                    VOC mAP of the checkpoint, network and metric on the GPU; prints the per-class AP table, writes eval.json beside CKPT
 #                    [METRIC=coco]: also the COCO-style AP (IoU .50:.95, AP50, AP75, small / medium / large, AR) and a `coco` object in eval.json
+#                    [CURVES=True CONF=0.6 CURVESTEPS=1000 CURVESOUT=curves.npz]: also precision / recall / F1 per class at CONF and at each class's
+#                    best-F1 threshold, the threshold with the best mean F1 and the confusion matrix at CONF; an `operating` object in eval.json
 #                    (make train VALMAP=True appends val_mAP to every epoch line)
 #                    [TTA=flip|v5|1,0.83f,0.67 TTATHRESH=0.55]: test-time augmentation, every picture also mirrored / shrunk, the views' rows fused on the GPU
 #   make detect      CKPT=yolo_model.h5|yolo.kmodel SRC=folder|list.txt [OUTDIR=out] [DRAW=True|False] [PRECISION=...] [DECODE=pil|gpu] [ENCODE=pil|gpu QUALITY=75]: every
@@ -117,6 +119,10 @@ ANN           ?= data/$(DATASET)_img_ann.npy
 EVALOBJ       ?= 0.05
 VOC07         ?= False
 METRIC        ?=
+CURVES        ?= False
+CONF          ?= 0.6
+CURVESTEPS    ?= 1000
+CURVESOUT     ?=
 # detect only
 SRC           ?= data
 OUTDIR        ?= out
@@ -195,7 +201,8 @@ kmodel:
 eval:
 	$(PY) keras_eval.py $(CKPT) --train_set $(DATASET) --class_num $(CLSNUM) --model_def $(MODEL) --depth_multiplier $(DEPTHMUL) \
 		--image_size $(IMGSIZE) --output_size $(OUTSIZE) --iou_thresh $(IOUTHRESH) --precision $(PRECISION) --obj_thresh $(EVALOBJ) \
-		--voc07 $(VOC07) $(if $(filter-out 0,$(SYNTHETIC)),--synthetic $(SYNTHETIC),--ann $(ANN)) $(if $(METRIC),--metric $(METRIC)) $(NMS_ARGS) $(TILE_ARGS) $(TTA_ARGS)
+		--voc07 $(VOC07) $(if $(filter-out 0,$(SYNTHETIC)),--synthetic $(SYNTHETIC),--ann $(ANN)) $(if $(METRIC),--metric $(METRIC)) $(NMS_ARGS) $(TILE_ARGS) $(TTA_ARGS) \
+		$(if $(filter True,$(CURVES)),--curves True --conf_thresh $(CONF) --curve_steps $(CURVESTEPS) $(if $(CURVESOUT),--curves_out $(CURVESOUT)))
 
 # every picture of SRC (a folder or a text list) -> OUTDIR/detections.json + OUTDIR/<stem>_res.jpg; batches of BATCH pictures of any sizes
 detect:

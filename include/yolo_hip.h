@@ -914,6 +914,43 @@ int yk_map_coco_eval(const float *d_rows, const int32_t *d_img, long long n_rows
                      int n_area, const double *d_rec_thr, int n_rec, int max_dets, void *d_work, size_t work_bytes, uint8_t *d_flags,
                      int32_t *d_npig, int32_t *d_n_det, double *d_precision, double *d_recall, double *d_summary, double *d_ap_class, void *stream);
 
+/* ---- operating points of the same rows (map_gpu.MapEvaluator.sweep / .confusion): precision / recall / F1 over a sweep of
+ * confidence thresholds and a confusion matrix at one threshold, by the rule of oppoint.py (the project's own: exact counting, parity with
+ * other frameworks' interpolated curves is unpinned).  Conventions, row formats, class reading and finiteness as yk_map_eval: the caller's
+ * buffers, every launch on `stream`, no allocation, no synchronisation, float64 without contraction, integer atomics only: two runs give
+ * the same bytes.
+ * yk_map_sweep_workspace_bytes  bytes of d_work that yk_map_sweep needs for these sizes (two integer histograms [class_num][n_thr]).
+ * yk_map_sweep       d_flags [n_rows] and d_n_gt [class_num] are what yk_map_eval wrote for the same rows; d_thr [n_thr] float64, device,
+ *                    finite and STRICTLY ASCENDING (the caller's promise: checking it here would need a synchronisation; MapEvaluator.sweep
+ *                    checks on the host).  A row is in at threshold t if (double)score >= t.  -> d_tp, d_fp int32 [class_num][n_thr]: the
+ *                    in-rows of the class with flag 1 / 2; d_precision = tp / (tp + fp), 1.0 where tp + fp == 0; d_recall = tp / n_gt, NaN
+ *                    where n_gt == 0; d_f1 = ((2.0 * p) * r) / (p + r), 0.0 where p + r == 0, NaN where n_gt == 0 (float64
+ *                    [class_num][n_thr]); d_best int32 [class_num]: the lowest k with the largest f1, -1 where n_gt == 0; d_mean_f1 float64
+ *                    [n_thr]: the f1 of the classes with n_gt > 0 added in ascending class order, divided by their number, NaN if there are
+ *                    none; d_best_all int32 [1]: the lowest k with the largest mean, -1 if there are none.
+ *                    n_thr outside 1 .. 4096, the sizes yk_map_eval refuses, or a workspace that is too small: YK_ERR_ARG.
+ * yk_map_confusion_lds_boxes  the largest (rows taking part + ground-truth boxes) of one image whose coordinates the matching stages in
+ *                    LDS; a larger image runs the same loop on global memory: nothing is truncated.
+ * yk_map_confusion_workspace_bytes  bytes of d_work that yk_map_confusion needs (one state byte per ground-truth box).
+ * yk_map_confusion   d_img, d_gt, d_gt_off, d_difficult as yk_map_eval.  Per image, class-agnostic: the rows with (double)score >=
+ *                    conf_thresh and a class in range and every box with a class in range (difficult or not) take part; pairs with IoU
+ *                    (box_iou's operation order, `plus_one`) >= iou_thresh are candidates; repeatedly the best pair of a free row and a
+ *                    free box is matched: the largest IoU, then the larger score (-0.0 == +0.0), then the lower row, then the lower box.
+ *                    -> d_matrix int32 [(class_num + 1)^2], [true][predicted], index class_num = background, zeroed by the call: a pair
+ *                    on a non-difficult box counts at [box class][row class], on a difficult box nowhere; an unmatched row at
+ *                    [class_num][row class]; an unmatched non-difficult box at [box class][class_num]; d_match int32 [n_rows]: the row's
+ *                    box (index into d_gt), -1 unmatched, -2 the row takes no part.
+ *                    NaN thresholds, the sizes yk_map_eval refuses, or a workspace that is too small: YK_ERR_ARG. */
+int yk_map_sweep_workspace_bytes(long long n_rows, int class_num, int n_thr, size_t *bytes);
+int yk_map_sweep(const float *d_rows, const uint8_t *d_flags, long long n_rows, int class_num, const int32_t *d_n_gt, const double *d_thr, int n_thr,
+                 void *d_work, size_t work_bytes, int32_t *d_tp, int32_t *d_fp, double *d_precision, double *d_recall, double *d_f1, int32_t *d_best,
+                 double *d_mean_f1, int32_t *d_best_all, void *stream);
+int yk_map_confusion_lds_boxes(void);
+int yk_map_confusion_workspace_bytes(long long n_gt_rows, size_t *bytes);
+int yk_map_confusion(const float *d_rows, const int32_t *d_img, long long n_rows, int n_img, const double *d_gt, const int32_t *d_gt_off,
+                     const uint8_t *d_difficult, long long n_gt_rows, int class_num, double conf_thresh, double iou_thresh, int plus_one, void *d_work,
+                     size_t work_bytes, int32_t *d_matrix, int32_t *d_match, void *stream);
+
 /* ---- anchor k-means with many restarts in one call (datatools.run_kmeans_gpu): datatools.run_kmeans for each of
  * `restarts` initial centroid sets, independently, on boxes d_wh [n][2] (w, h; finite and > 0, which the caller has checked).  Distance
  * 1 - IoU of boxes centred at the origin, float64 in datatools.fake_iou_distance's operation order without contraction; assignment = argmin,

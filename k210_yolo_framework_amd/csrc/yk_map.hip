@@ -586,6 +586,263 @@ __global__ __launch_bounds__(MAP_BLOCK) void coco_summary_kernel(const double *_
     }
 }
 
+// ---- operating points (oppoint.py) --------------------------------------------------------------------------------------
+// sweep: the rows' flags are yk_map_eval's; a row of score s is in at the first j thresholds, j = the number of thresholds <= float64(s).  An
+// integer histogram per (flag, class, j - 1), its suffix sums are tp / fp; the curves are fixed chains of float64 operations on those integers.
+constexpr int SWEEP_MAX_THR = 4096;
+
+__global__ __launch_bounds__(MAP_BLOCK) void sweep_hist_kernel(const float *__restrict__ rows, const uint8_t *__restrict__ flags, long long n, int class_num,
+                                                               const double *__restrict__ thr, int n_thr, int32_t *__restrict__ hist) {
+    for (long long r = (long long)blockIdx.x * MAP_BLOCK + threadIdx.x; r < n; r += (long long)gridDim.x * MAP_BLOCK) {
+        const uint8_t f = flags[r];
+        if (f != 1 && f != 2) continue;
+        const int c = class_of((double)rows[(size_t)r * 6 + 5], class_num);
+        if (c >= class_num) continue;
+        const double s = (double)rows[(size_t)r * 6 + 4];
+        int lo = 0, hi = n_thr;                                   // the first k with thr[k] > s = the number of thresholds <= s
+        while (lo < hi) {
+            const int mid = lo + ((hi - lo) >> 1);
+            if (thr[mid] <= s) lo = mid + 1; else hi = mid;
+        }
+        if (lo > 0) atomicAdd(&hist[((size_t)(f - 1) * class_num + c) * n_thr + (lo - 1)], 1);
+    }
+}
+
+// the larger f1, then the lower index
+__device__ __forceinline__ bool sweep_better(double fa, int ka, double fb, int kb) { return fa > fb || (fa == fb && ka < kb); }
+
+// one wave per class: lane 0 holds the HIGHEST threshold of a chunk, so an inclusive scan over the lanes is the suffix sum over the thresholds
+__global__ __launch_bounds__(YK_WAVE) void sweep_curve_kernel(const int32_t *__restrict__ hist, const int32_t *__restrict__ n_gt, int class_num, int n_thr,
+                                                              int32_t *__restrict__ tp, int32_t *__restrict__ fp, double *__restrict__ precision,
+                                                              double *__restrict__ recall, double *__restrict__ f1, int32_t *__restrict__ best) {
+    const int c = blockIdx.x, lane = threadIdx.x;
+    const int32_t *h_tp = hist + (size_t)c * n_thr, *h_fp = hist + ((size_t)class_num + c) * n_thr;
+    const int ngt = n_gt[c];
+    const double dgt = (double)ngt;
+    int carry_tp = 0, carry_fp = 0, bk = 0x7fffffff;
+    double bf = -1.0;
+    for (int top = n_thr - 1; top >= 0; top -= YK_WAVE) {
+        const int k = top - lane;
+        int a = k >= 0 ? h_tp[k] : 0, b = k >= 0 ? h_fp[k] : 0;
+#pragma unroll
+        for (int s = 1; s < YK_WAVE; s <<= 1) {
+            const int oa = __shfl_up(a, s, YK_WAVE), ob = __shfl_up(b, s, YK_WAVE);
+            if (lane >= s) {
+                a += oa;
+                b += ob;
+            }
+        }
+        a += carry_tp;
+        b += carry_fp;
+        carry_tp = __shfl(a, YK_WAVE - 1, YK_WAVE);
+        carry_fp = __shfl(b, YK_WAVE - 1, YK_WAVE);
+        if (k >= 0) {
+            const size_t at = (size_t)c * n_thr + k;
+            tp[at] = a;
+            fp[at] = b;
+            const double t = (double)a;
+            const double p = (a + b == 0) ? 1.0 : t / (double)(a + b);
+            double r = __builtin_nan(""), f = __builtin_nan("");
+            if (ngt > 0) {
+                r = t / dgt;
+                const double pr = p + r;
+                f = pr == 0.0 ? 0.0 : ((2.0 * p) * r) / pr;
+                if (sweep_better(f, k, bf, bk)) {
+                    bf = f;
+                    bk = k;
+                }
+            }
+            precision[at] = p;
+            recall[at] = r;
+            f1[at] = f;
+        }
+    }
+#pragma unroll
+    for (int s = YK_WAVE / 2; s > 0; s >>= 1) {
+        const double of = __shfl_xor(bf, s, YK_WAVE);
+        const int ok = __shfl_xor(bk, s, YK_WAVE);
+        if (sweep_better(of, ok, bf, bk)) {
+            bf = of;
+            bk = ok;
+        }
+    }
+    if (lane == 0) best[c] = ngt > 0 ? bk : -1;
+}
+
+// one thread per threshold: the classes with ground truth in ascending order, one after another
+__global__ __launch_bounds__(MAP_BLOCK) void sweep_mean_kernel(const double *__restrict__ f1, const int32_t *__restrict__ n_gt, int class_num, int n_thr,
+                                                               double *__restrict__ mean_f1) {
+    const int k = blockIdx.x * MAP_BLOCK + threadIdx.x;
+    if (k >= n_thr) return;
+    double s = 0.0;
+    int n = 0;
+    for (int c = 0; c < class_num; ++c)
+        if (n_gt[c] > 0) {
+            s = s + f1[(size_t)c * n_thr + k];
+            ++n;
+        }
+    mean_f1[k] = n ? s / (double)n : __builtin_nan("");
+}
+
+// one wave: the lowest index of the largest mean (a NaN mean = no class has ground truth = -1)
+__global__ __launch_bounds__(YK_WAVE) void sweep_best_all_kernel(const double *__restrict__ mean_f1, int n_thr, int32_t *__restrict__ best_all) {
+    const int lane = threadIdx.x;
+    double bf = -1.0;
+    int bk = 0x7fffffff;
+    for (int k = lane; k < n_thr; k += YK_WAVE) {
+        const double f = mean_f1[k];
+        if (f == f && sweep_better(f, k, bf, bk)) {
+            bf = f;
+            bk = k;
+        }
+    }
+#pragma unroll
+    for (int s = YK_WAVE / 2; s > 0; s >>= 1) {
+        const double of = __shfl_xor(bf, s, YK_WAVE);
+        const int ok = __shfl_xor(bk, s, YK_WAVE);
+        if (sweep_better(of, ok, bf, bk)) {
+            bf = of;
+            bk = ok;
+        }
+    }
+    if (lane == 0) best_all[0] = bk == 0x7fffffff ? -1 : bk;
+}
+
+// confusion: one workgroup of ONE wave per image, so that __syncthreads() orders lane 0's writes of the matching state (d_match of the rows,
+// `taken` of the boxes, both in global memory) before every lane's reads of the next round.  d_match doubles as the rows' state: -2 takes no
+// part, -1 free, >= 0 the box.  taken: 0 free, 1 matched, 2 takes no part.  While the rows taking part + the boxes of the image fit CONF_LDS
+// their coordinates are staged in LDS as float64 (rows compacted: slot -> row index); above it the same loop reads them from global memory.
+constexpr int CONF_LDS = 1024;
+
+struct ConfKey {
+    double iou;
+    float score;
+    int row, box;
+};
+// the larger IoU, then the larger score (-0.0 == +0.0 as floats compare), then the lower row, then the lower box
+__device__ __forceinline__ bool conf_better(const ConfKey &a, const ConfKey &b) {
+    if (a.iou != b.iou) return a.iou > b.iou;
+    if (a.score != b.score) return a.score > b.score;
+    if (a.row != b.row) return a.row < b.row;
+    return a.box < b.box;
+}
+
+__device__ __forceinline__ int lower_bound_i32(const int32_t *__restrict__ a, long long n, int v) {
+    long long lo = 0, hi = n;
+    while (lo < hi) {
+        const long long mid = lo + ((hi - lo) >> 1);
+        if (a[mid] < v) lo = mid + 1; else hi = mid;
+    }
+    return (int)lo;
+}
+
+__global__ __launch_bounds__(YK_WAVE) void confusion_kernel(const float *__restrict__ rows, const int32_t *__restrict__ img, long long n_rows, int n_img,
+                                                            const double *__restrict__ gt, const int32_t *__restrict__ gt_off,
+                                                            const uint8_t *__restrict__ difficult, int class_num, double conf_thresh, double iou_thresh,
+                                                            double o, uint8_t *taken, int32_t *matrix, int32_t *match) {
+    __shared__ double sh_box[CONF_LDS * 4];
+    __shared__ float sh_score[CONF_LDS];
+    __shared__ int32_t sh_row[CONF_LDS];
+    const int lane = threadIdx.x;
+    const int K1 = class_num + 1;
+    for (int i = blockIdx.x; i < n_img; i += gridDim.x) {
+        const int r0 = lower_bound_i32(img, n_rows, i), r1 = lower_bound_i32(img, n_rows, i + 1);
+        const int g0 = gt_off[i], g1 = gt_off[i + 1];
+        const int nbx = g1 - g0;
+        __syncthreads();                                          // the previous image's LDS is no longer read
+        // who takes part; the rows that do are compacted into LDS while they fit
+        int nd = 0;
+        for (int base = r0; base < r1; base += YK_WAVE) {
+            const int r = base + lane;
+            bool part = false;
+            if (r < r1) {
+                const float *d = rows + (size_t)r * 6;
+                part = (double)d[4] >= conf_thresh && class_of((double)d[5], class_num) < class_num;
+                match[r] = part ? -1 : -2;
+            }
+            const unsigned long long who = __ballot(part);
+            const int at = nd + __popcll(who & ((1ull << lane) - 1ull));
+            if (part && at < CONF_LDS) {
+                const float *d = rows + (size_t)r * 6;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) sh_box[at * 4 + e] = (double)d[e];
+                sh_score[at] = d[4];
+                sh_row[at] = r;
+            }
+            nd += __popcll(who);
+        }
+        const bool staged = (long long)nd + nbx <= CONF_LDS;
+        for (int g = g0 + lane; g < g1; g += YK_WAVE) {
+            taken[g] = class_of(gt[(size_t)g * 6 + 5], class_num) < class_num ? 0 : 2;
+            if (staged) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) sh_box[(nd + (g - g0)) * 4 + e] = gt[(size_t)g * 6 + e];
+            }
+        }
+        __syncthreads();
+        // the rounds: every lane strides over the pairs (row slot, box), the wave keeps the best free pair
+        const int n_slots = staged ? nd : r1 - r0;               // staged: the rows taking part; global: every row of the image
+        const long long n_pairs = (long long)n_slots * nbx;
+        const int max_rounds = nd < nbx ? nd : nbx;
+        for (int round = 0; round < max_rounds; ++round) {
+            ConfKey best = {-1.0, 0.0f, 0x7fffffff, 0x7fffffff};
+            for (long long p = lane; p < n_pairs; p += YK_WAVE) {
+                const int slot = (int)(p / nbx), g = g0 + (int)(p % nbx);
+                const int r = staged ? sh_row[slot] : r0 + slot;
+                if (match[r] != -1 || taken[g] != 0) continue;
+                double b0, b1, b2, b3, t0, t1, t2, t3;
+                float sc;
+                if (staged) {
+                    const double *b = sh_box + slot * 4, *t = sh_box + (nd + (g - g0)) * 4;
+                    b0 = b[0], b1 = b[1], b2 = b[2], b3 = b[3], t0 = t[0], t1 = t[1], t2 = t[2], t3 = t[3];
+                    sc = sh_score[slot];
+                } else {
+                    const float *b = rows + (size_t)r * 6;
+                    const double *t = gt + (size_t)g * 6;
+                    b0 = (double)b[0], b1 = (double)b[1], b2 = (double)b[2], b3 = (double)b[3], t0 = t[0], t1 = t[1], t2 = t[2], t3 = t[3];
+                    sc = b[4];
+                }
+                const double ih = fmin(b2, t2) - fmax(b0, t0) + o;
+                const double iw = fmin(b3, t3) - fmax(b1, t1) + o;
+                const double inter = fmax(ih, 0.0) * fmax(iw, 0.0);
+                const double area = (b2 - b0 + o) * (b3 - b1 + o);
+                const double areas = (t2 - t0 + o) * (t3 - t1 + o);
+                const double uni = area + areas - inter;
+                const double iou = uni > 0.0 ? inter / uni : 0.0;
+                if (!(iou >= iou_thresh)) continue;
+                const ConfKey key = {iou, sc, r, g};
+                if (best.row == 0x7fffffff || conf_better(key, best)) best = key;
+            }
+#pragma unroll
+            for (int s = YK_WAVE / 2; s > 0; s >>= 1) {
+                ConfKey other;
+                other.iou = __shfl_xor(best.iou, s, YK_WAVE);
+                other.score = __shfl_xor(best.score, s, YK_WAVE);
+                other.row = __shfl_xor(best.row, s, YK_WAVE);
+                other.box = __shfl_xor(best.box, s, YK_WAVE);
+                if (other.row != 0x7fffffff && (best.row == 0x7fffffff || conf_better(other, best))) best = other;
+            }
+            if (best.row == 0x7fffffff) break;                    // wave-uniform: no candidate pair is left
+            if (lane == 0) {
+                match[best.row] = best.box;
+                taken[best.box] = 1;
+            }
+            __syncthreads();
+        }
+        __syncthreads();
+        // the counts
+        for (int r = r0 + lane; r < r1; r += YK_WAVE) {
+            const int m = match[r];
+            if (m == -2) continue;
+            const int pc = class_of((double)rows[(size_t)r * 6 + 5], class_num);
+            if (m == -1) atomicAdd(&matrix[class_num * K1 + pc], 1);
+            else if (!difficult[m]) atomicAdd(&matrix[class_of(gt[(size_t)m * 6 + 5], class_num) * K1 + pc], 1);
+        }
+        for (int g = g0 + lane; g < g1; g += YK_WAVE)
+            if (taken[g] == 0 && !difficult[g]) atomicAdd(&matrix[class_of(gt[(size_t)g * 6 + 5], class_num) * K1 + class_num], 1);
+    }
+}
+
 // ---- workspace ------------------------------------------------------------------------------------------------------------------------
 struct Work {
     size_t key_a_in, key_a, key_b_in, key_b, iota, row_a, row_b, cum, taken, cls_off, sort_tmp, sort_bytes, total;
@@ -881,6 +1138,100 @@ extern "C" int yk_map_coco_eval(const float *d_rows, const int32_t *d_img, long 
                        class_num, n_thr, n_area, cum, d_precision, d_recall);
     hipLaunchKernelGGL(coco_summary_kernel, dim3((unsigned)(10 + class_num)), dim3(MAP_BLOCK), 0, st, d_precision, d_recall, d_iou_thr, n_thr, n_rec, class_num,
                        n_area, d_summary, d_ap_class);
+    YK_HIP(hipGetLastError());
+    return YK_OK;
+}
+
+// ---- operating points: the C-ABI ------------------------------------------------------------------------------------------------------
+namespace {
+
+int sweep_check(const char *who, long long n_rows, int class_num, int n_thr) {
+    const int rc = check_sizes(who, n_rows, 0, 0, class_num);
+    if (rc != YK_OK) return rc;
+    if (n_thr < 1 || n_thr > SWEEP_MAX_THR) {
+        yk_set_error("%s: %d thresholds: outside 1 .. %d", who, n_thr, SWEEP_MAX_THR);
+        return YK_ERR_ARG;
+    }
+    return YK_OK;
+}
+
+inline size_t sweep_bytes(int class_num, int n_thr) { return up256((size_t)2 * (size_t)class_num * (size_t)n_thr * 4); }
+
+}  // namespace
+
+extern "C" int yk_map_sweep_workspace_bytes(long long n_rows, int class_num, int n_thr, size_t *bytes) {
+    const int rc = sweep_check("yk_map_sweep_workspace_bytes", n_rows, class_num, n_thr);
+    if (rc != YK_OK) return rc;
+    if (!bytes) {
+        yk_set_error("yk_map_sweep_workspace_bytes: bad argument");
+        return YK_ERR_ARG;
+    }
+    *bytes = sweep_bytes(class_num, n_thr);
+    return YK_OK;
+}
+
+extern "C" int yk_map_sweep(const float *d_rows, const uint8_t *d_flags, long long n_rows, int class_num, const int32_t *d_n_gt, const double *d_thr,
+                            int n_thr, void *d_work, size_t work_bytes, int32_t *d_tp, int32_t *d_fp, double *d_precision, double *d_recall,
+                            double *d_f1, int32_t *d_best, double *d_mean_f1, int32_t *d_best_all, void *stream) {
+    const int rc = sweep_check("yk_map_sweep", n_rows, class_num, n_thr);
+    if (rc != YK_OK) return rc;
+    if (!d_n_gt || !d_thr || !d_work || !d_tp || !d_fp || !d_precision || !d_recall || !d_f1 || !d_best || !d_mean_f1 || !d_best_all ||
+        (n_rows > 0 && (!d_rows || !d_flags))) {
+        yk_set_error("yk_map_sweep: bad argument");
+        return YK_ERR_ARG;
+    }
+    if (work_bytes < sweep_bytes(class_num, n_thr)) {
+        yk_set_error("yk_map_sweep: workspace of %zu bytes, %zu needed (yk_map_sweep_workspace_bytes)", work_bytes, sweep_bytes(class_num, n_thr));
+        return YK_ERR_ARG;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    int32_t *hist = (int32_t *)d_work;
+    YK_HIP(hipMemsetAsync(hist, 0, (size_t)2 * class_num * n_thr * 4, st));
+    if (n_rows > 0)
+        hipLaunchKernelGGL(sweep_hist_kernel, dim3(grid_for(n_rows, MAP_BLOCK)), dim3(MAP_BLOCK), 0, st, d_rows, d_flags, n_rows, class_num, d_thr, n_thr, hist);
+    hipLaunchKernelGGL(sweep_curve_kernel, dim3((unsigned)class_num), dim3(YK_WAVE), 0, st, hist, d_n_gt, class_num, n_thr, d_tp, d_fp, d_precision, d_recall,
+                       d_f1, d_best);
+    hipLaunchKernelGGL(sweep_mean_kernel, dim3((unsigned)(n_thr + MAP_BLOCK - 1) / MAP_BLOCK), dim3(MAP_BLOCK), 0, st, d_f1, d_n_gt, class_num, n_thr, d_mean_f1);
+    hipLaunchKernelGGL(sweep_best_all_kernel, dim3(1), dim3(YK_WAVE), 0, st, d_mean_f1, n_thr, d_best_all);
+    YK_HIP(hipGetLastError());
+    return YK_OK;
+}
+
+extern "C" int yk_map_confusion_lds_boxes(void) { return CONF_LDS; }
+
+extern "C" int yk_map_confusion_workspace_bytes(long long n_gt_rows, size_t *bytes) {
+    if (n_gt_rows < 0 || n_gt_rows > MAP_MAX_ROWS || !bytes) {
+        yk_set_error("yk_map_confusion_workspace_bytes: bad argument");
+        return YK_ERR_ARG;
+    }
+    *bytes = up256((size_t)(n_gt_rows > 0 ? n_gt_rows : 1));
+    return YK_OK;
+}
+
+extern "C" int yk_map_confusion(const float *d_rows, const int32_t *d_img, long long n_rows, int n_img, const double *d_gt, const int32_t *d_gt_off,
+                                const uint8_t *d_difficult, long long n_gt_rows, int class_num, double conf_thresh, double iou_thresh, int plus_one,
+                                void *d_work, size_t work_bytes, int32_t *d_matrix, int32_t *d_match, void *stream) {
+    const int rc = check_sizes("yk_map_confusion", n_rows, n_gt_rows, n_img, class_num);
+    if (rc != YK_OK) return rc;
+    if (!d_gt_off || !d_work || !d_matrix || (n_rows > 0 && (!d_rows || !d_img || !d_match)) || (n_gt_rows > 0 && (!d_gt || !d_difficult)) ||
+        !(iou_thresh == iou_thresh) || !(conf_thresh == conf_thresh)) {
+        yk_set_error("yk_map_confusion: bad argument");
+        return YK_ERR_ARG;
+    }
+    if ((long long)(class_num + 1) * (class_num + 1) > 0x7fffffffLL / 4) {
+        yk_set_error("yk_map_confusion: a matrix of %d x %d classes is too large", class_num + 1, class_num + 1);
+        return YK_ERR_ARG;
+    }
+    if (work_bytes < up256((size_t)(n_gt_rows > 0 ? n_gt_rows : 1))) {
+        yk_set_error("yk_map_confusion: workspace of %zu bytes, %zu needed (yk_map_confusion_workspace_bytes)", work_bytes,
+                     up256((size_t)(n_gt_rows > 0 ? n_gt_rows : 1)));
+        return YK_ERR_ARG;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    YK_HIP(hipMemsetAsync(d_matrix, 0, (size_t)(class_num + 1) * (class_num + 1) * 4, st));
+    if (n_img > 0)
+        hipLaunchKernelGGL(confusion_kernel, dim3(grid_for(n_img, 1)), dim3(YK_WAVE), 0, st, d_rows, d_img, n_rows, n_img, d_gt, d_gt_off, d_difficult, class_num,
+                           conf_thresh, iou_thresh, plus_one ? 1.0 : 0.0, (uint8_t *)d_work, d_matrix, d_match);
     YK_HIP(hipGetLastError());
     return YK_OK;
 }

@@ -7,6 +7,7 @@
                               [--metric voc|coco] [--out eval.json] [--dump_rows rows.npz]
                               [--tiles NXxNY --tile_overlap 0.2 --tile_full True --tile_match ios|iou --tile_thresh 0.5]
                               [--tta 1,1f|flip|v5 --tta_thresh 0.55]
+                              [--curves True --conf_thresh 0.6 --curve_steps 1000 --curves_out curves.npz]
 
 CKPT: a Keras `.h5` / `.npz` checkpoint (float modes, through engine.Pipeline with several batches in flight) or a `.kmodel` / `.kfpkg`
 (`--precision kpu`, the K210 KPU's exact integer arithmetic through engine.KpuPlan).  The images are the validation head of the list
@@ -20,6 +21,12 @@ its three, and AP per class; `eval.json` gains a `coco` object.  The VOC lines a
 their meaning for them (--voc07 True with --metric coco is refused).  The rule is restated from pycocotools' public source and parity with
 pycocotools' own numbers is unpinned; `difficult` stands in for COCO's `ignore` (no crowd boxes); an object's area is its box area in the
 pixels of the picture it was scored in (COCO: mask area, source-image pixels); AR is at 100 detections per class and image only.
+
+--curves True (`make eval CURVES=True`) adds the operating points of the same accumulated rows (oppoint.py's statement, computed by
+MapEvaluator.sweep and .confusion on the GPU): per class precision / recall / F1 at --conf_thresh and at the class's best-F1
+threshold, the threshold that maximises the mean F1, and the confusion matrix at --conf_thresh; `eval.json` gains an `operating` object and
+--curves_out writes the full arrays.  The thresholds swept are k / --curve_steps at or above --obj_thresh (the decode never emitted the rows
+below it), plus --conf_thresh.  Exact counting, not other frameworks' interpolated curves: parity with their numbers is unpinned.
 The reference ships no evaluator; tools/map_eval.py is the host-side developer script this replaces as the product's entry point."""
 from __future__ import annotations
 
@@ -75,6 +82,10 @@ def parse(argv=None):
     p.add_argument('--depth', type=int, default=3, help='batches in flight (float modes)')
     p.add_argument('--out', type=str, default=None, help='result file (default: eval.json next to the checkpoint)')
     p.add_argument('--dump_rows', type=str, default=None, help='also write the detections and the ground truth that were scored (.npz)')
+    p.add_argument('--curves', type=str, choices=['True', 'False'], default='False', help='also precision / recall / F1 over confidence and a confusion matrix')
+    p.add_argument('--conf_thresh', type=float, default=0.6, help="--curves: the confidence threshold reported (the K210 demo's 0.6)")
+    p.add_argument('--curve_steps', type=int, default=1000, help='--curves: thresholds k / N are swept')
+    p.add_argument('--curves_out', type=str, default=None, help='--curves: also write the full arrays (.npz)')
     tl.add_arguments(p)
     tt.add_arguments(p)
     a = p.parse_args(sys.argv[1:] if argv is None else argv)
@@ -95,7 +106,32 @@ def parse(argv=None):
         p.error(f'--tta {tt.text_of(a.tta)}: a picture is {len(a.tta)} frames and --batch holds {a.batch}')
     if a.metric == 'coco' and a.voc07 == 'True':
         p.error('--voc07 True is the 11-point VOC AP; --metric coco has its own 101-point AP: choose one')
+    if a.curves == 'True':
+        try:
+            curve_grid(a.obj_thresh, a.conf_thresh, a.curve_steps)
+        except ValueError as e:
+            p.error(str(e))
+    elif a.curves_out:
+        p.error('--curves_out FILE is written by --curves True')
     return a
+
+
+def curve_grid(obj_thresh: float, conf_thresh: float, steps: int) -> np.ndarray:
+    """The thresholds `--curves True` sweeps: k / steps for k in range(steps) that are >= obj_thresh (the decode emitted no row below
+    it, so counts there would be wrong), and conf_thresh in its place if it is not among them.  ValueError names what is refused."""
+    from . import oppoint
+    obj, conf, steps = float(obj_thresh), float(conf_thresh), int(steps)
+    if not (conf == conf and abs(conf) != float('inf')):
+        raise ValueError(f'--conf_thresh {conf_thresh}: not a finite number')
+    if conf < obj:
+        raise ValueError(f'--conf_thresh {conf:g} is below --obj_thresh {obj:g}: the decode emitted no row below --obj_thresh, the counts would be wrong')
+    if steps < 1 or steps > oppoint.MAX_THRESHOLDS - 1:
+        raise ValueError(f'--curve_steps {steps}: outside 1 .. {oppoint.MAX_THRESHOLDS - 1}')
+    grid = np.arange(steps) / steps
+    grid = grid[grid >= obj]
+    if not np.any(grid == conf):
+        grid = np.sort(np.append(grid, conf))
+    return grid
 
 
 def _items(a, h: Helper):
@@ -264,6 +300,56 @@ def coco_report(ev, class_num: int, n_gt) -> dict:
     return rep
 
 
+def operating_report(ev, a, n_gt) -> dict:
+    """The operating points of what `ev` holds (MapEvaluator.sweep over curve_grid, MapEvaluator.confusion at a.conf_thresh): printed, and
+    returned as eval.json's `operating` object; a.curves_out receives the full arrays."""
+    K, conf = a.class_num, float(a.conf_thresh)
+    grid = curve_grid(a.obj_thresh, conf, a.curve_steps)
+    s = ev.sweep(grid)
+    cm = ev.confusion(conf)
+    at = int(np.nonzero(grid == conf)[0][0])
+    num = lambda v: None if v != v else float(v)
+    pct = lambda v: '   nan' if v != v else f'{100 * v:6.2f}'
+    rule = 'hard NMS scores' if a.nms == 'hard' else f'the decayed scores of nms {a.nms} (softnms.py)'
+    print(f'operating points (oppoint.py: exact counting, parity with other frameworks\' curves unpinned; IoU {a.iou_thresh}; {rule}; '
+          f'{len(grid)} thresholds from {grid[0]:g}; {CAP_NOTE}):')
+    print(f'   class     gt |  at {conf:<5g}  P      R     F1 |  best thr      P      R     F1')
+    have = [c for c in range(K) if n_gt[c]]
+    for c in have:
+        b = int(s['best'][c])
+        print(f'   class {c:2d} {int(n_gt[c]):5d} |         {pct(s["precision"][c, at])} {pct(s["recall"][c, at])} {pct(s["f1"][c, at])} |'
+              f'  {grid[b]:8.4f} {pct(s["precision"][c, b])} {pct(s["recall"][c, b])} {pct(s["f1"][c, b])}')
+    mean = lambda key, k: float(np.mean([s[key][c, k] for c in have])) if have else float('nan')
+    ba = int(s['best_all'])
+    best_thr, best_f1 = (float(grid[ba]), float(s['mean_f1'][ba])) if ba >= 0 else (float('nan'), float('nan'))
+    print(f'   all classes  |  at {conf:<5g}{pct(mean("precision", at))} {pct(mean("recall", at))} {pct(s["mean_f1"][at])} |'
+          f'  best mean F1 {pct(best_f1)} at threshold {best_thr:g}')
+    m = cm['matrix']
+    shown = [c for c in range(K) if m[c].any() or m[:, c].any()]
+    print(f'   confusion at {conf:g} (rows: true class, columns: predicted class; bg = background: a row of bg is a false positive, a column '
+          f'of bg a missed box; classes without a count left out):')
+    print('        true \\ pred ' + ' '.join(f'{c:5d}' for c in shown) + '    bg')
+    for c in shown + [K]:
+        print(f'        {"bg" if c == K else c:>11} ' + ' '.join(f'{int(m[c, d]):5d}' for d in shown) + f' {int(m[c, K]):5d}')
+    rep = {'conf_thresh': conf, 'iou_thresh': a.iou_thresh, 'steps': int(a.curve_steps), 'thresholds': len(grid), 'scores': rule,
+           'n_gt': [int(v) for v in n_gt],
+           'precision': [num(v) for v in s['precision'][:, at]], 'recall': [num(v) for v in s['recall'][:, at]],
+           'f1': [num(v) for v in s['f1'][:, at]], 'mean_precision': num(mean('precision', at)), 'mean_recall': num(mean('recall', at)),
+           'mean_f1': num(s['mean_f1'][at]),
+           'class_best_threshold': [None if b < 0 else float(grid[b]) for b in s['best']],
+           'class_best_precision': [None if b < 0 else num(s['precision'][c, b]) for c, b in enumerate(s['best'])],
+           'class_best_recall': [None if b < 0 else num(s['recall'][c, b]) for c, b in enumerate(s['best'])],
+           'class_best_f1': [None if b < 0 else num(s['f1'][c, b]) for c, b in enumerate(s['best'])],
+           'best_threshold': num(best_thr), 'best_mean_f1': num(best_f1),
+           'confusion': m.tolist(), 'confusion_axes': f'confusion[true][predicted]; index {K} is background: confusion[{K}][c] counts false '
+                                                      f'positives of class c, confusion[c][{K}] its missed boxes',
+           'note': CAP_NOTE}
+    if a.curves_out:
+        np.savez(a.curves_out, thresholds=grid, tp=s['tp'], fp=s['fp'], precision=s['precision'], recall=s['recall'], f1=s['f1'],
+                 mean_f1=s['mean_f1'], matrix=m)
+    return rep
+
+
 def main(argv=None):
     a = parse(argv)
     from . import engine
@@ -305,6 +391,8 @@ def main(argv=None):
         print(f'   tta {tt.text_of(a.tta)}: {len(a.tta)} views a picture, fused by IoU > {a.tta_thresh:g}; rows carry the fused scores (tta.py)')
     if a.metric == 'coco':
         report['coco'] = coco_report(ev, a.class_num, r['n_gt'])
+    if a.curves == 'True':
+        report['operating'] = operating_report(ev, a, r['n_gt'])
     out = Path(a.out) if a.out else Path(a.pre_ckpt).resolve().parent / 'eval.json'
     out.write_text(json.dumps(report, indent=1))
     print(INFO, f' wrote {out}')

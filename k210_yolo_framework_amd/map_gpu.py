@@ -6,6 +6,8 @@ them, in device memory.
                                                          # or packed rows [R, 6] + offsets [B + 1]; cuda tensors or numpy arrays
     r = ev.result()                                      # {'map', 'ap', 'n_gt', 'n_det', 'tp', 'fp'} as voc_eval.evaluate, + 'flags'
     c = ev.coco_result()                                 # the COCO-style figures of the same rows, as coco_eval.evaluate
+    s = ev.sweep()                                       # precision / recall / F1 at 1000 confidence thresholds, as oppoint.sweep
+    m = ev.confusion(0.6)                                # the confusion matrix of the rows at or above a threshold, as oppoint.confusion
 
 The detection rows are accumulated in device buffers that grow by doubling; the only thing read back per batch is the batch's counts
 (4 bytes per image), which size the append.  The ground truth (a few boxes per image, float64) is kept on the host until `result()`
@@ -245,3 +247,96 @@ class MapEvaluator:
                 out['npig'], out['n_det'] = h_ints[:Cn * A].reshape(Cn, A), h_ints[Cn * A:]
                 out['flags'] = flags[:A * T * R].cpu().numpy().reshape(A, T, R)
         return out
+
+    # -- operating points (oppoint.py) ------------------------------------------------
+    def sweep(self, thresholds=None, stream=None) -> Dict[str, object]:
+        """Precision / recall / F1 of the rows added so far at every confidence threshold, by the rule of oppoint.sweep with the evaluator's
+        iou_thresh / plus_one -> its dict: 'thresholds' [n], 'tp', 'fp' [class_num, n] int, 'n_gt' [class_num] int, 'precision', 'recall',
+        'f1' [class_num, n] float64 (recall / f1 NaN where a class has no ground truth), 'best' [class_num] int (-1 there), 'mean_f1' [n],
+        'best_all' int, 'flags' [rows] uint8.  thresholds: float64, finite, strictly ascending, 1 .. 4096 of them (default
+        np.arange(1000) / 1000); anything else raises engine.YkError.  Runs yk_map_eval, then yk_map_sweep, on `stream` (default: the current
+        one); synchronises to read the results.  Nothing accumulated is changed."""
+        import torch
+        from . import oppoint
+        try:
+            thr = oppoint.check_thresholds(np.arange(1000) / 1000 if thresholds is None else thresholds)
+        except ValueError as e:
+            raise engine.YkError(f'MapEvaluator.sweep: {e}') from None
+        T = len(thr)
+        Cn, R, N = self.class_num, self.n_rows, self.n_img
+        gt, off, diff = self.ground_truth()
+        G = int(off[-1])
+        if G > MAX_ROWS:
+            raise engine.YkError(f'MapEvaluator: {G} ground-truth rows: more than 2^31-1')
+        nbytes, sbytes = C.c_size_t(), C.c_size_t()
+        engine.call('yk_map_workspace_bytes', R, G, N, Cn, C.byref(nbytes))
+        engine.call('yk_map_sweep_workspace_bytes', R, Cn, T, C.byref(sbytes))
+        with torch.cuda.device(self.dev):
+            st = torch.cuda.current_stream() if stream is None else stream
+            with torch.cuda.stream(st):
+                last = getattr(self, '_last', None)
+                if last is not None and last != st:
+                    st.wait_stream(last)
+                up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.dev)
+                d_gt, d_diff = (up(gt), up(diff)) if G else (None, None)
+                d_off, d_thr = up(off.astype(np.int32)), up(thr)
+                work = torch.empty((int(nbytes.value),), dtype=torch.uint8, device=self.dev)
+                swork = torch.empty((int(sbytes.value),), dtype=torch.uint8, device=self.dev)
+                flags = torch.empty((max(R, 1),), dtype=torch.uint8, device=self.dev)
+                ints = torch.empty((4, Cn), dtype=torch.int32, device=self.dev)
+                ap = torch.empty((Cn + 1,), dtype=torch.float64, device=self.dev)
+                counts = torch.empty((2, Cn, T), dtype=torch.int32, device=self.dev)               # tp, fp
+                curves = torch.empty((3, Cn, T), dtype=torch.float64, device=self.dev)             # precision, recall, f1
+                mean = torch.empty((T,), dtype=torch.float64, device=self.dev)
+                best = torch.empty((Cn + 1,), dtype=torch.int32, device=self.dev)                  # [class_num] + best_all
+                engine.call('yk_map_eval', self._rows if R else None, self._img if R else None, R, N, d_gt, d_off, d_diff, G, Cn, self.iou_thresh,
+                            int(self.use_07_metric), int(self.plus_one), work, nbytes.value, flags, ints[0], ints[1], ints[2], ints[3], ap,
+                            ap[Cn:], engine._stream(st))
+                engine.call('yk_map_sweep', self._rows if R else None, flags if R else None, R, Cn, ints[0], d_thr, T, swork, sbytes.value,
+                            counts[0], counts[1], curves[0], curves[1], curves[2], best, mean, best[Cn:], engine._stream(st))
+                st.synchronize()
+                self._last = None
+                h_counts, h_curves, h_best = counts.cpu().numpy().astype(int), curves.cpu().numpy(), best.cpu().numpy().astype(int)
+                return {'thresholds': thr, 'tp': h_counts[0], 'fp': h_counts[1], 'n_gt': ints[0].cpu().numpy().astype(int),
+                        'precision': h_curves[0], 'recall': h_curves[1], 'f1': h_curves[2], 'best': h_best[:Cn].copy(),
+                        'mean_f1': mean.cpu().numpy(), 'best_all': int(h_best[Cn]), 'flags': flags[:R].cpu().numpy()}
+
+    def confusion(self, conf_thresh: float, iou_thresh: Optional[float] = None, stream=None) -> Dict[str, np.ndarray]:
+        """The confusion matrix of the rows added so far with score >= conf_thresh, by the rule of oppoint.confusion (iou_thresh: the
+        evaluator's by default; its plus_one) -> {'matrix' [class_num + 1, class_num + 1] int, [true][predicted], index class_num =
+        background; 'match' [rows] int: the row's box in the concatenated ground truth, -1 unmatched, -2 the row takes no part}.  Runs on
+        `stream` (default: the current one); synchronises to read the results.  Nothing accumulated is changed."""
+        import torch
+        conf, iou = float(conf_thresh), float(self.iou_thresh if iou_thresh is None else iou_thresh)
+        if conf != conf or iou != iou:
+            raise engine.YkError(f'MapEvaluator.confusion: conf_thresh {conf_thresh}, iou_thresh {iou_thresh}: not a number')
+        Cn, R, N = self.class_num, self.n_rows, self.n_img
+        gt, off, diff = self.ground_truth()
+        G = int(off[-1])
+        if G > MAX_ROWS:
+            raise engine.YkError(f'MapEvaluator: {G} ground-truth rows: more than 2^31-1')
+        nbytes = C.c_size_t()
+        engine.call('yk_map_confusion_workspace_bytes', G, C.byref(nbytes))
+        with torch.cuda.device(self.dev):
+            st = torch.cuda.current_stream() if stream is None else stream
+            with torch.cuda.stream(st):
+                last = getattr(self, '_last', None)
+                if last is not None and last != st:
+                    st.wait_stream(last)
+                up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.dev)
+                d_gt, d_diff = (up(gt), up(diff)) if G else (None, None)
+                d_off = up(off.astype(np.int32))
+                work = torch.empty((int(nbytes.value),), dtype=torch.uint8, device=self.dev)
+                matrix = torch.empty(((Cn + 1) * (Cn + 1),), dtype=torch.int32, device=self.dev)
+                match = torch.empty((max(R, 1),), dtype=torch.int32, device=self.dev)
+                engine.call('yk_map_confusion', self._rows if R else None, self._img if R else None, R, N, d_gt, d_off, d_diff, G, Cn, conf, iou,
+                            int(self.plus_one), work, nbytes.value, matrix, match, engine._stream(st))
+                st.synchronize()
+                self._last = None
+                return {'matrix': matrix.cpu().numpy().astype(int).reshape(Cn + 1, Cn + 1), 'match': match[:R].cpu().numpy().astype(int)}
+
+
+def confusion_lds_boxes() -> int:
+    """The largest (rows taking part + ground-truth boxes) of one image that MapEvaluator.confusion matches out of LDS; above it the same
+    loop reads global memory."""
+    return int(engine.lib().yk_map_confusion_lds_boxes())
