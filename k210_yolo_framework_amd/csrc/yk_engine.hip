@@ -63,6 +63,26 @@ struct yk_plan {
 
 #include "yk_plan_build.h"
 
+// the device side of the weight store: plain device memory, written once before the entry is handed out
+yk_wstore &yk_weights() {
+    static const yk_wstore_dev dev = {
+        nullptr,
+        [](void *, int, const void *src, size_t bytes) -> void * {
+            void *d = nullptr;
+            hipError_t e = hipMalloc(&d, bytes ? bytes : 1);
+            if (e == hipSuccess && bytes) e = hipMemcpy(d, src, bytes, hipMemcpyHostToDevice);
+            if (e != hipSuccess) {
+                yk_set_error("yk_plan_create: packed weights (%zu bytes): %s", bytes, hipGetErrorString(e));
+                if (d) (void)hipFree(d);
+                return nullptr;
+            }
+            return d;
+        },
+        [](void *, int, void *d) { (void)hipFree(d); }};
+    static yk_wstore &store = *new yk_wstore(dev);      // never destroyed: a plan may be closed while the process exits
+    return store;
+}
+
 extern "C" void yk_plan_destroy(yk_plan_t *p) {
     if (!p) return;
     (void)hipSetDevice(p->device);

@@ -93,6 +93,10 @@ struct builder {
     std::vector<char> skip;                // op i emits no launch of its own
 
     const int32_t *op(int i) const { return ops + (size_t)i * YK_OP_FIELDS; }
+    int upload_dw(const float *w, int c, int cp, const yk_half **d) {
+        return p->mem.packed(YK_WT_DW, {c, cp}, {{w, (size_t)9 * c * sizeof(float)}},
+                             [&](std::vector<uint8_t> &out, std::vector<float> &) { yk_wput(out, pack_dw(w, c, cp)); }, d);
+    }
     int upload_scale_bias(const int32_t *o, int n, const float **scale, const float **bias) {
         int rc = p->mem.upload_f(blob + o[YK_F_SCALE_OFF], n, scale);
         return rc ? rc : p->mem.upload_f(blob + o[YK_F_BIAS_OFF], n, bias);
@@ -180,11 +184,12 @@ struct builder {
         first_args &f = l.f;
         memset(&f, 0, sizeof(f));
         int rc;
-        if ((rc = p->mem.upload(pack_stem(w, co), &f.w))) return rc;
+        const yk_wsrc wsrc{w, (size_t)27 * co * sizeof(float)};
+        if ((rc = p->mem.packed(YK_WT_STEM, {co}, {wsrc}, [&](std::vector<uint8_t> &out, std::vector<float> &) { yk_wput(out, pack_stem(w, co)); }, &f.w))) return rc;
         f.Hi = X.h; f.Wi = X.w; f.Ho = Y.h; f.Wo = Y.w;
         f.stride = o[YK_F_STRIDE]; f.pad_t = o[YK_F_PAD_T]; f.pad_l = o[YK_F_PAD_L];
         f.Cout = co; f.outp = Y.cp;
-        if (co <= 32 && (rc = p->mem.upload(pack_stem_mfma(w, co), &f.wm))) return rc;
+        if (co <= 32 && (rc = p->mem.packed(YK_WT_STEM_MFMA, {co}, {wsrc}, [&](std::vector<uint8_t> &out, std::vector<float> &) { yk_wput(out, pack_stem_mfma(w, co)); }, &f.wm))) return rc;
         if ((rc = upload_scale_bias(o, co, &f.scale, &f.bias))) return rc;
         f.act = o[YK_F_ACT]; f.alpha = yk_op_alpha(o); f.out = Y.d;
         yk_act_params(f.act, f.alpha, &f.slope, &f.cap);
@@ -204,7 +209,7 @@ struct builder {
     int fuse_dw_into(igemm_args &g, const int32_t *dwo, const tinfo &dwX, const tinfo &X, double *flops, double *bytes) {
         const int c0 = X.c;
         int rc;
-        if ((rc = p->mem.upload(pack_dw(blob + dwo[YK_F_W_OFF], c0, g.c0p), &g.dw_w))) return rc;
+        if ((rc = upload_dw(blob + dwo[YK_F_W_OFF], c0, g.c0p, &g.dw_w))) return rc;
         if ((rc = upload_scale_bias(dwo, c0, &g.dw_scale, &g.dw_bias))) return rc;
         g.dw_act = dwo[YK_F_ACT]; g.dw_stride = dwo[YK_F_STRIDE];
         g.dw_pad_t = dwo[YK_F_PAD_T]; g.dw_pad_l = dwo[YK_F_PAD_L];
@@ -227,19 +232,21 @@ struct builder {
         return &p->T[q[YK_F_OUT]];
     }
 
-    // tile configuration of conv launch l (panel w, fp16 [N][K]), fixed here for max_batch; the fused kernels that read their pointwise panel
-    // in MFMA fragment order get it that way; K split and slab size of a plain conv
-    int plan_conv(launch &l, bool fused, const std::vector<uint16_t> &w) {
+    // tile configuration of conv launch l, fixed here for max_batch, and its weights in the one form that configuration reads: the panel
+    // (fp16 [N][K]), or for the fused kernels that read their pointwise panel in MFMA fragment order, that order; K split and slab size
+    // of a plain conv
+    int plan_conv(launch &l, bool fused, const std::vector<int32_t> &wpar, const yk_wsrc &wsrc, const std::function<std::vector<uint16_t>()> &pack_panel) {
         igemm_args &g = l.g;
         g.M = max_batch * g.Ho * g.Wo;   // for config choice; patched per run
         l.cfg = fused ? yk_igemm_fused_pick(g) : yk_igemm_pick(g, l.out_f32);
-        if (fused && (l.cfg == FUSED_DMA || l.cfg == LR_T1 || l.cfg == LR_T2)) {
-            if (l.cfg == FUSED_DMA) yk_fdma_fill(g);
-            const std::vector<uint16_t> wf = pack_fragments(w, g.N, g.K);
-            int rc = p->mem.upload(wf, &g.w);
-            if (rc) return rc;
-            g.w_bytes = (uint32_t)(wf.size() * 2);
-        }
+        const bool frag = fused && (l.cfg == FUSED_DMA || l.cfg == LR_T1 || l.cfg == LR_T2);
+        if (fused && l.cfg == FUSED_DMA) yk_fdma_fill(g);
+        size_t bytes;
+        int rc = p->mem.packed(frag ? YK_WT_FRAG : YK_WT_CONV, wpar, {wsrc}, [&](std::vector<uint8_t> &out, std::vector<float> &) {
+            yk_wput(out, frag ? pack_fragments(pack_panel(), g.N, g.K) : pack_panel());
+        }, &g.w, &bytes);
+        if (rc) return rc;
+        g.w_bytes = (uint32_t)bytes;
         if (!fused && opt.splitk) {
             g.split_k = yk_igemm_split(l.cfg, g);
             if (g.split_k > 1) {
@@ -286,9 +293,9 @@ struct builder {
         g.Hi = X.h; g.Wi = X.w; g.Ho = Y.h; g.Wo = Y.w;
         g.ks = ks; g.stride = o[YK_F_STRIDE]; g.pad_t = o[YK_F_PAD_T]; g.pad_l = o[YK_F_PAD_L];
         g.N = co; g.K = ks * ks * (c0p + c1p);
-        const std::vector<uint16_t> w = pack_conv(blob + o[YK_F_W_OFF], co, ks * ks, c0, c0p, c1, c1p);
-        if ((rc = p->mem.upload(w, &g.w))) return rc;
-        g.w_bytes = (uint32_t)(w.size() * 2);
+        const yk_wsrc wsrc{blob + o[YK_F_W_OFF], (size_t)co * ks * ks * (c0 + c1) * sizeof(float)};
+        const auto pack_panel = [&] { return pack_conv(blob + o[YK_F_W_OFF], co, ks * ks, c0, c0p, c1, c1p); };
+        const std::vector<int32_t> wpar{co, ks * ks, c0, c0p, c1, c1p};
         if ((rc = upload_scale_bias(o, co, &g.scale, &g.bias))) return rc;
         g.act = o[YK_F_ACT]; g.alpha = yk_op_alpha(o);
         yk_act_params(g.act, g.alpha, &g.slope, &g.cap);
@@ -314,7 +321,7 @@ struct builder {
         double dw_flops = 0, dw_bytes = 0;
         if (dwo && (rc = fuse_dw_into(g, dwo, *dwX, X, &dw_flops, &dw_bytes))) return rc;
         l.out_f32 = f32;
-        if ((rc = plan_conv(l, dwo != nullptr, w))) return rc;
+        if ((rc = plan_conv(l, dwo != nullptr, wpar, wsrc, pack_panel))) return rc;
         char nm[96];
         snprintf(nm, sizeof nm, "%sconv%dx%ds%d_%dto%d%s%s[%s]", dwo ? "dw3x3+" : "", ks, ks, g.stride, o[YK_F_CIN], co,
                  g.res ? "+add" : "", s1 ? "+upcat" : (up0 ? "+up" : ""), dwo ? yk_igemm_fused_name(l.cfg) : yk_igemm_name(l.cfg));
@@ -347,7 +354,7 @@ struct builder {
         memset(&d, 0, sizeof(d));
         const int c = X.c, cp = X.cp;
         int rc;
-        if ((rc = p->mem.upload(pack_dw(blob + o[YK_F_W_OFF], c, cp), &d.w))) return rc;
+        if ((rc = upload_dw(blob + o[YK_F_W_OFF], c, cp, &d.w))) return rc;
         d.in = X.d; d.Hi = X.h; d.Wi = X.w; d.Ho = Y.h; d.Wo = Y.w; d.Cp = cp;
         d.stride = o[YK_F_STRIDE]; d.pad_t = o[YK_F_PAD_T]; d.pad_l = o[YK_F_PAD_L];
         if ((rc = upload_scale_bias(o, c, &d.scale, &d.bias))) return rc;

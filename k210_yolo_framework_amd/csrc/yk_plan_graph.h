@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "yk_conv.h"
+#include "yk_wstore.h"
 
 static inline uint16_t yk_f2h(float f) {   // round-to-nearest-even fp32 -> fp16 bits (normal / subnormal / overflow to inf)
     _Float16 h = (_Float16)f;
@@ -26,9 +27,26 @@ static inline float yk_op_alpha(const int32_t *o) {   // an op row's LeakyReLU s
     return a;
 }
 
-// the device allocations of a plan, freed together by its destroy function
+// The library's store of packed immutable buffers (yk_wstore.h; defined once, in yk_engine.hip).  The tag names the packer, so two
+// packers never share an entry; each packer lists the parameters its layout depends on beside it.
+yk_wstore &yk_weights();
+enum yk_wtag {
+    YK_WT_F32 = 1,                                                   // upload_f
+    YK_WT_STEM, YK_WT_STEM_MFMA, YK_WT_CONV, YK_WT_FRAG, YK_WT_DW,   // yk_plan_build.h
+    YK_WT_XW, YK_WT_XDW, YK_WT_XSTEM, YK_WT_XSTEM_FRAG,              // yk_xplan_build.h
+};
+template <class E>
+static inline void yk_wput(std::vector<uint8_t> &packed, const std::vector<E> &v) {
+    packed.resize(v.size() * sizeof(E));
+    if (!v.empty()) memcpy(packed.data(), v.data(), packed.size());
+}
+
+// the device allocations of a plan, freed together by its destroy function: what a step writes is the plan's own (alloc, upload), the
+// packed weights and parameter tables no kernel writes are references into the store (packed)
 struct yk_dev_mem {
     std::vector<void *> ptrs;
+    std::vector<yk_went *> refs;
+    bool share = yk_env_flag("YK_SHARE_WEIGHTS", true);   // read where the plan is created; 0: every packed buffer is the plan's own
 
     int alloc(void **ptr, size_t bytes, bool zero = true) {
         YK_HIP(hipMalloc(ptr, bytes));
@@ -42,22 +60,47 @@ struct yk_dev_mem {
         YK_HIP(hipMemcpy(*ptr, src, bytes, hipMemcpyHostToDevice));
         return YK_OK;
     }
-    template <class E, class D>
-    int upload(const std::vector<E> &v, const D **d) {   // a packed host panel, to the pointer type its kernel reads it through
-        void *q;
-        int rc = upload(&q, v.data(), v.size() * sizeof(E));
-        *d = (const D *)q;
-        return rc;
+    // A packed immutable buffer, to the pointer type its kernel reads it through: `pack` turns the source ranges `src` into the packed
+    // bytes and the host-side floats derived with them (`aux`); `par` lists every parameter of the packer that the result depends on.
+    // Shared: the store's entry for (device, tag, par, src) - packed and uploaded only if it is not there yet.
+    template <class D>
+    int packed(int tag, const std::vector<int32_t> &par, const std::vector<yk_wsrc> &src, const yk_wpack_fn &pack, const D **d,
+               size_t *bytes = nullptr, std::vector<float> *aux = nullptr) {
+        if (!share) {
+            std::vector<uint8_t> host;
+            std::vector<float> a;
+            pack(host, a);
+            void *q;
+            int rc = upload(&q, host.data(), host.size());
+            if (rc) return rc;
+            *d = (const D *)q;
+            if (bytes) *bytes = host.size();
+            if (aux) *aux = a;
+            return YK_OK;
+        }
+        yk_went *e = yk_weights().acquire(yk_current_device(), tag, par.data(), (int)par.size(), src.data(), (int)src.size(), pack);
+        if (!e) return YK_ERR_HIP;                             // (the error text is set where the upload failed)
+        refs.push_back(e);
+        *d = (const D *)e->d;
+        if (bytes) *bytes = e->bytes;
+        if (aux) *aux = e->aux;
+        return YK_OK;
     }
     // n floats times `mul` (BatchNorm scale / bias), padded with 256 zeros so an epilogue may read past n unguarded
     int upload_f(const float *src, int n, const float **d, float mul = 1.f) {
-        std::vector<float> v((size_t)n + 256, 0.f);
-        for (int i = 0; i < n; ++i) v[i] = src[i] * mul;
-        return upload(v, d);
+        int32_t mul_bits;
+        memcpy(&mul_bits, &mul, 4);
+        return packed(YK_WT_F32, {n, mul_bits}, {{src, (size_t)n * sizeof(float)}}, [&](std::vector<uint8_t> &out, std::vector<float> &) {
+            std::vector<float> v((size_t)n + 256, 0.f);
+            for (int i = 0; i < n; ++i) v[i] = src[i] * mul;
+            yk_wput(out, v);
+        }, d);
     }
     void free_all() {
         for (void *q : ptrs) (void)hipFree(q);
         ptrs.clear();
+        for (yk_went *e : refs) yk_weights().release(e);
+        refs.clear();
     }
 };
 

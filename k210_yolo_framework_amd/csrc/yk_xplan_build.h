@@ -282,63 +282,83 @@ struct xbuilder {
                const float **dbias, float *gain0, float *gain1, float *off) {
         const int co = o[YK_F_COUT], cin = o[YK_F_CIN];
         const int nsteps = taps * (nc0 + nc1);
-        float wmax = 0.f;
         const size_t nw = (size_t)co * taps * cin;
-        for (size_t k = 0; k < nw; ++k) wmax = std::max(wmax, fabsf(blob[o[YK_F_W_OFF] + k]));
-        const int sexp = (wmax > 0.f && std::isfinite(wmax)) ? 13 - ilogbf(wmax) : 0;
-        std::vector<uint16_t> wt((size_t)nsteps * nslab * 1024, 0);
-        std::vector<double> sum0(co, 0.0), sum1(co, 0.0);
-        for (int n = 0; n < co; ++n)
-            for (int t = 0; t < taps; ++t)
-                for (int c = 0; c < cin; ++c) {
-                    const float wv = blob[o[YK_F_W_OFF] + ((size_t)n * taps + t) * cin + c];
-                    const bool second = c >= c0;
-                    const int cc = second ? c - c0 : c;
-                    const int step = second ? taps * nc0 + (cc / 32) * taps + t : (cc / 32) * taps + t;      // channel step outer, tap inner
-                    const int k32 = cc % 32, chunk = k32 >> 3, e = k32 & 7, r = n & 15, pos = chunk ^ ((r >> 1) & 3);
-                    const float v = ldexpf(wv, sexp);
-                    const uint16_t hi = yk_f2h(v);
-                    const size_t at = ((size_t)step * nslab + (n >> 4)) * 1024 + (size_t)r * 32 + pos * 8 + e;
-                    wt[at] = hi;
-                    wt[at + 512] = yk_f2h(v - yk_h2f(hi));
-                    (second ? sum1 : sum0)[n] += fabs((double)wv);
-                }
-        int rc2 = p->mem.upload(wt, dw);
+        // everything below the three source ranges is computed where the store has no entry for them yet: the tiles, and with them the
+        // weight exponent and the gains {gain0, gain1, off, sexp}
+        const std::vector<yk_wsrc> src{{blob + o[YK_F_W_OFF], nw * sizeof(float)}, {blob + o[YK_F_SCALE_OFF], (size_t)co * sizeof(float)},
+                                       {blob + o[YK_F_BIAS_OFF], (size_t)co * sizeof(float)}};
+        const auto pack = [&](std::vector<uint8_t> &out, std::vector<float> &aux) {
+            float wmax = 0.f;
+            for (size_t k = 0; k < nw; ++k) wmax = std::max(wmax, fabsf(blob[o[YK_F_W_OFF] + k]));
+            const int sexp = (wmax > 0.f && std::isfinite(wmax)) ? 13 - ilogbf(wmax) : 0;
+            out.assign((size_t)nsteps * nslab * 1024 * sizeof(uint16_t), 0);
+            uint16_t *wt = reinterpret_cast<uint16_t *>(out.data());
+            std::vector<double> sum0(co, 0.0), sum1(co, 0.0);
+            for (int n = 0; n < co; ++n)
+                for (int t = 0; t < taps; ++t)
+                    for (int c = 0; c < cin; ++c) {
+                        const float wv = blob[o[YK_F_W_OFF] + ((size_t)n * taps + t) * cin + c];
+                        const bool second = c >= c0;
+                        const int cc = second ? c - c0 : c;
+                        const int step = second ? taps * nc0 + (cc / 32) * taps + t : (cc / 32) * taps + t;      // channel step outer, tap inner
+                        const int k32 = cc % 32, chunk = k32 >> 3, e = k32 & 7, r = n & 15, pos = chunk ^ ((r >> 1) & 3);
+                        const float v = ldexpf(wv, sexp);
+                        const uint16_t hi = yk_f2h(v);
+                        const size_t at = ((size_t)step * nslab + (n >> 4)) * 1024 + (size_t)r * 32 + pos * 8 + e;
+                        wt[at] = hi;
+                        wt[at + 512] = yk_f2h(v - yk_h2f(hi));
+                        (second ? sum1 : sum0)[n] += fabs((double)wv);
+                    }
+            float g0 = 0.f, g1 = 0.f, of = 0.f;
+            for (int n = 0; n < co; ++n) {
+                const float sc = fabsf(blob[o[YK_F_SCALE_OFF] + n]);
+                g0 = std::max(g0, (float)(sc * sum0[n]));
+                g1 = std::max(g1, (float)(sc * sum1[n]));
+                of = std::max(of, fabsf(blob[o[YK_F_BIAS_OFF] + n]));
+            }
+            aux = {g0 * 1.0001f, g1 * 1.0001f, of * 1.0001f, (float)sexp};
+        };
+        std::vector<float> aux;
+        size_t bytes;
+        int rc2 = p->mem.packed(YK_WT_XW, {co, cin, c0, nc0, nc1, taps, nslab}, src, pack, dw, &bytes, &aux);
         if (rc2) return rc2;
-        *dbytes = (uint32_t)(wt.size() * 2);
-        *gain0 = *gain1 = *off = 0.f;
-        for (int n = 0; n < co; ++n) {
-            const float sc = fabsf(blob[o[YK_F_SCALE_OFF] + n]);
-            *gain0 = std::max(*gain0, (float)(sc * sum0[n]));
-            *gain1 = std::max(*gain1, (float)(sc * sum1[n]));
-            *off = std::max(*off, fabsf(blob[o[YK_F_BIAS_OFF] + n]));
-        }
-        *gain0 *= 1.0001f;
-        *gain1 *= 1.0001f;
-        *off *= 1.0001f;
+        *dbytes = (uint32_t)bytes;
+        *gain0 = aux[0];
+        *gain1 = aux[1];
+        *off = aux[2];
+        const int sexp = (int)aux[3];
         if ((rc2 = p->mem.upload_f(blob + o[YK_F_SCALE_OFF], co, dscale, ldexpf(1.f, -sexp)))) return rc2;
         return p->mem.upload_f(blob + o[YK_F_BIAS_OFF], co, dbias);
     }
     // [11][cp] depthwise parameters (nine taps, BN scale, BN bias) -> device; bound of the output from the input's max
     int pack_dw(const int32_t *o, int c, int cp, const float **dpar, float *gain, float *off) {
-        std::vector<float> par((size_t)11 * cp, 0.f);
-        *gain = *off = 0.f;
-        for (int k = 0; k < c; ++k) {
-            float sw = 0.f;
-            for (int t = 0; t < 9; ++t) {
-                const float w = blob[o[YK_F_W_OFF] + (size_t)t * c + k];
-                par[(size_t)t * cp + k] = w;
-                sw += fabsf(w);
+        const std::vector<yk_wsrc> src{{blob + o[YK_F_W_OFF], (size_t)9 * c * sizeof(float)}, {blob + o[YK_F_SCALE_OFF], (size_t)c * sizeof(float)},
+                                       {blob + o[YK_F_BIAS_OFF], (size_t)c * sizeof(float)}};
+        const auto pack = [&](std::vector<uint8_t> &out, std::vector<float> &aux) {
+            std::vector<float> par((size_t)11 * cp, 0.f);
+            float g = 0.f, of = 0.f;
+            for (int k = 0; k < c; ++k) {
+                float sw = 0.f;
+                for (int t = 0; t < 9; ++t) {
+                    const float w = blob[o[YK_F_W_OFF] + (size_t)t * c + k];
+                    par[(size_t)t * cp + k] = w;
+                    sw += fabsf(w);
+                }
+                const float sc = blob[o[YK_F_SCALE_OFF] + k], bs = blob[o[YK_F_BIAS_OFF] + k];
+                par[(size_t)9 * cp + k] = sc;
+                par[(size_t)10 * cp + k] = bs;
+                g = std::max(g, fabsf(sc) * sw);
+                of = std::max(of, fabsf(bs));
             }
-            const float sc = blob[o[YK_F_SCALE_OFF] + k], bs = blob[o[YK_F_BIAS_OFF] + k];
-            par[(size_t)9 * cp + k] = sc;
-            par[(size_t)10 * cp + k] = bs;
-            *gain = std::max(*gain, fabsf(sc) * sw);
-            *off = std::max(*off, fabsf(bs));
-        }
-        *gain *= 1.0001f;
-        *off *= 1.0001f;
-        return p->mem.upload(par, dpar);
+            aux = {g * 1.0001f, of * 1.0001f};
+            yk_wput(out, par);
+        };
+        std::vector<float> aux;
+        int rc = p->mem.packed(YK_WT_XDW, {c, cp}, src, pack, dpar, nullptr, &aux);
+        if (rc) return rc;
+        *gain = aux[0];
+        *off = aux[1];
+        return YK_OK;
     }
     // the stem conv's output bound from its weights (the normalised image is in [0, 1]: the bound needs no measurement):
     // gain = max_c |scale_c| * sum_t |w_ct|, off = max |bias|, wmax = max |w|
@@ -405,15 +425,18 @@ struct xbuilder {
             yk_set_error("op %d: stem conv must be 3x3 with 16/24/32 filters", i);
             return YK_ERR_UNSUPPORTED;
         }
-        std::vector<float> w((size_t)27 * co);
-        for (int c = 0; c < co; ++c)
-            for (int t = 0; t < 27; ++t) w[(size_t)t * co + c] = blob[o[YK_F_W_OFF] + (size_t)c * 27 + t];
+        const auto pack = [&](std::vector<uint8_t> &out, std::vector<float> &) {
+            std::vector<float> w((size_t)27 * co);
+            for (int c = 0; c < co; ++c)
+                for (int t = 0; t < 27; ++t) w[(size_t)t * co + c] = blob[o[YK_F_W_OFF] + (size_t)c * 27 + t];
+            yk_wput(out, w);
+        };
         float gain, off, wmax;
         stem_gain(o, &gain, &off, &wmax);
         l.kind = XK_STEM;
         xstem_args &s = l.s;
         memset(&s, 0, sizeof(s));
-        if ((rc = p->mem.upload(w, &s.w))) return rc;
+        if ((rc = p->mem.packed(YK_WT_XSTEM, {co}, {{blob + o[YK_F_W_OFF], (size_t)27 * co * sizeof(float)}}, pack, &s.w))) return rc;
         s.Hi = X.h; s.Wi = X.w; s.Ho = Y.h; s.Wo = Y.w;
         s.stride = o[YK_F_STRIDE]; s.pad_t = o[YK_F_PAD_T]; s.pad_l = o[YK_F_PAD_L];
         s.Cout = co; s.outG = Y.cp >> 3;
@@ -443,21 +466,24 @@ struct xbuilder {
         // MFMA fragments of the 32 x 32 weight matrix (k = ky*8 + j for the first eight of a filter row's nine values, 24 + ky
         // for the ninth), w * 2^s = hi + lo
         const int sexp = (wmax > 0.f && std::isfinite(wmax)) ? 13 - ilogbf(wmax) : 0;
-        std::vector<uint16_t> wf((size_t)2 * 2 * 64 * 8, 0);
-        for (int nf = 0; nf < 2; ++nf)
-            for (int ln = 0; ln < 64; ++ln)
-                for (int e = 0; e < 8; ++e) {
-                    const int n = nf * 16 + (ln & 15), k = (ln >> 4) * 8 + e;
-                    int t = -1;
-                    if (k < 24) t = (k >> 3) * 9 + (k & 7);            // tap row ky = k/8, j = kx*3 + ci
-                    else if (k < 27) t = (k - 24) * 9 + 8;
-                    if (n >= sco || t < 0) continue;
-                    const float v = ldexpf(blob[so[YK_F_W_OFF] + (size_t)n * 27 + t], sexp);
-                    const uint16_t hi = yk_f2h(v);
-                    wf[((size_t)(nf * 2 + 0) * 64 + ln) * 8 + e] = hi;
-                    wf[((size_t)(nf * 2 + 1) * 64 + ln) * 8 + e] = yk_f2h(v - yk_h2f(hi));
-                }
-        if ((rc = p->mem.upload(wf, &g.st_wf))) return rc;
+        const auto pack = [&](std::vector<uint8_t> &out, std::vector<float> &) {
+            std::vector<uint16_t> wf((size_t)2 * 2 * 64 * 8, 0);
+            for (int nf = 0; nf < 2; ++nf)
+                for (int ln = 0; ln < 64; ++ln)
+                    for (int e = 0; e < 8; ++e) {
+                        const int n = nf * 16 + (ln & 15), k = (ln >> 4) * 8 + e;
+                        int t = -1;
+                        if (k < 24) t = (k >> 3) * 9 + (k & 7);            // tap row ky = k/8, j = kx*3 + ci
+                        else if (k < 27) t = (k - 24) * 9 + 8;
+                        if (n >= sco || t < 0) continue;
+                        const float v = ldexpf(blob[so[YK_F_W_OFF] + (size_t)n * 27 + t], sexp);
+                        const uint16_t hi = yk_f2h(v);
+                        wf[((size_t)(nf * 2 + 0) * 64 + ln) * 8 + e] = hi;
+                        wf[((size_t)(nf * 2 + 1) * 64 + ln) * 8 + e] = yk_f2h(v - yk_h2f(hi));
+                    }
+            yk_wput(out, wf);
+        };
+        if ((rc = p->mem.packed(YK_WT_XSTEM_FRAG, {sco}, {{blob + so[YK_F_W_OFF], (size_t)27 * sco * sizeof(float)}}, pack, &g.st_wf))) return rc;
         g.stem = 1;
         if ((rc = p->mem.upload_f(blob + so[YK_F_SCALE_OFF], sco, &g.st_scale, ldexpf(1.f, -sexp)))) return rc;
         if ((rc = p->mem.upload_f(blob + so[YK_F_BIAS_OFF], sco, &g.st_bias))) return rc;
