@@ -65,7 +65,7 @@ class _Bits:
 
 def encode(img, quality=75):
     """-> (scan bytes, stats).  stats: bits (before padding), stuffed, zrl, eob_only (blocks that are a DC code and EOB), clamped_ac,
-    clamped_dc, blocks."""
+    clamped_dc, blocks, and what stuffing_positions says of the unstuffed stream."""
     img = np.asarray(img)
     assert img.ndim == 3 and img.shape[2] == 3 and img.dtype == np.uint8 and img.shape[0] > 0 and img.shape[1] > 0
     qt = jpeg.quant_tables(quality).astype(np.int64)
@@ -121,7 +121,21 @@ def encode(img, quality=75):
         bits.total -= pad
     raw = bytes(bits.out)
     st['stuffed'] = raw.count(b'\xff')
+    st.update(stuffing_positions(raw))
     return raw.replace(b'\xff', b'\xff\x00'), st
+
+
+CHUNK_BYTES, LANE_BYTES = 1248, 20          # the device stuffs a picture in chunks of 1248 unstuffed bytes, 63 lanes of 20 bytes each
+
+
+def stuffing_positions(raw):
+    """Where the 0xFF bytes of an unstuffed, padded stream lie in the device's chunks and lanes: unstuffed_bytes, ff_positions (int64,
+    ascending), ff_at_lane_end (a lane's last byte), ff_at_chunk_end (a chunk's last byte: its 0x00 opens the next chunk's output),
+    last_byte_ff (the picture's last byte, after the 1-padding)."""
+    ff = np.flatnonzero(np.frombuffer(raw, np.uint8) == 0xFF).astype(np.int64)
+    in_chunk = ff % CHUNK_BYTES
+    return dict(unstuffed_bytes=len(raw), ff_positions=ff, ff_at_lane_end=int((in_chunk % LANE_BYTES == LANE_BYTES - 1).sum()),
+                ff_at_chunk_end=int((in_chunk == CHUNK_BYTES - 1).sum()), last_byte_ff=bool(len(raw)) and raw[-1] == 0xFF)
 
 
 def file(img, quality=75):
