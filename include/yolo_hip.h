@@ -356,7 +356,9 @@ int yk_letterbox_u8(const uint8_t *d_src, int batch, int src_h, int src_w, uint8
  * each image's inverse map M (row-major 2x3, pixel-index coordinates of the dst_h x dst_w tensor, src_idx = M . (x, y, 1)), built on
  * the host.  The letterboxed image is warped bilinearly through M (taps outside the tensor read 0, round half up, capped at 255);
  * no intermediate frame is written, and the result is bit-identical to yk_letterbox_u8 followed by that warp.  Integer M (identity,
- * mirror) gives an exact pixel copy.  Bad arguments, a NULL d_inv included: YK_ERR_ARG.  Can be recorded in a graph. */
+ * mirror) gives an exact pixel copy.  Any finite M is safe: the taps are tested as doubles before any conversion.  A map with an entry that
+ * is not finite yields an unspecified but deterministic frame and reads nothing of d_src.  Bad arguments, a NULL d_inv included:
+ * YK_ERR_ARG.  Can be recorded in a graph. */
 int yk_letterbox_augment_u8(const uint8_t *d_src, int batch, int src_h, int src_w, const double *d_inv /* [batch][6] */,
                             uint8_t *d_dst, int dst_h, int dst_w, void *stream);
 /* `img / np.max(img)` (tools/utils.py:405) for a batch of u8 frames of per_image bytes each -> fp32 (one correctly rounded quotient
@@ -446,8 +448,9 @@ int yk_mosaic_params(yk_ragged_row_t *h_rows4, int cx, int cy, const double *gai
  * by each sample's inverse map as yk_letterbox_augment_u8 warps the letterbox: the four bilinear taps each evaluate the mosaic pixel on the
  * fly, no intermediate frame, bit-identical to the mosaic followed by that warp.  The kernel does not trust the table: a row with h <= 0,
  * w <= 0 or offset + 3*h*w > src_bytes makes its quadrant zeros and nothing of d_src is read for it; cx and cy are clamped to [0, dst_w] and
- * [0, dst_h] (an empty quadrant is legal).  NULL pointers other than d_inv, n <= 0, src_bytes == 0 and non-positive dst sizes:
- * YK_ERR_ARG; no device: YK_ERR_NO_DEVICE.  Can be recorded in a graph. */
+ * [0, dst_h] (an empty quadrant is legal).  A d_inv row with an entry that is not finite yields an unspecified but deterministic frame and
+ * reads nothing of d_src.  NULL pointers other than d_inv, n <= 0, src_bytes == 0 and non-positive dst sizes: YK_ERR_ARG; no device:
+ * YK_ERR_NO_DEVICE.  Can be recorded in a graph (one kernel node per 65535 samples). */
 int yk_mosaic_ragged_u8(const uint8_t *d_src, size_t src_bytes, const yk_ragged_row_t *d_table, const int32_t *d_centre,
                         const double *d_inv, int n, uint8_t *d_dst, int dst_h, int dst_w, void *stream);
 /* ---- HSV colour jitter of finished training frames (k210_yolo_framework_amd/colour.py) ------
