@@ -78,6 +78,18 @@ static inline int yk_current_device() {
     return d;
 }
 
+// Kernels that put a table row in blockIdx.y: grid.y holds at most 65535 rows, so n rows are launch(base, m) once per chunk - rows base ..
+// base + m - 1, every pointer advanced by the caller - and one kernel node per chunk in a captured graph.
+template <class Launch>
+static inline void yk_for_grid_y(int n, Launch launch) {
+    for (int base = 0; base < n; base += 65535) launch(base, n - base < 65535 ? n - base : 65535);
+}
+
+// A row whose picture has pixels and lies inside the src_bytes of its buffer.  Kernels do not trust their tables: any other row is not read.
+__device__ __forceinline__ bool yk_ragged_row_inside(const yk_ragged_row_t &row, size_t src_bytes) {
+    return row.h > 0 && row.w > 0 && row.offset <= src_bytes && (size_t)row.h * row.w * 3 <= src_bytes - row.offset;
+}
+
 __device__ __forceinline__ float yk_wave_max(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));

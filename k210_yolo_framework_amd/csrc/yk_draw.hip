@@ -42,7 +42,7 @@ __global__ void __launch_bounds__(256) draw_dets_u8_kernel(uint8_t *__restrict__
     const int img = blockIdx.y;
     const yk_ragged_row_t row = table[img];
     const int h = row.h, w = row.w;
-    if (h <= 0 || w <= 0 || row.offset > src_bytes || (size_t)h * w * 3 > src_bytes - row.offset) return;       // uniform: the whole workgroup
+    if (!yk_ragged_row_inside(row, src_bytes)) return;                                                          // uniform: the whole workgroup
     size_t npx = (size_t)h * w;
     if (npx > max_pixels) npx = max_pixels;
     const size_t first = (size_t)blockIdx.x * 256;
@@ -138,12 +138,11 @@ extern "C" int yk_draw_dets_u8(uint8_t *d_buf, size_t src_bytes, const yk_ragged
         yk_set_error("yk_draw_dets_u8: no HIP device");
         return YK_ERR_NO_DEVICE;
     }
-    for (int base = 0; base < n; base += 65535) {                                 // grid.y holds at most 65535 pictures
-        const int m = n - base < 65535 ? n - base : 65535;
+    yk_for_grid_y(n, [&](int base, int m) {
         hipLaunchKernelGGL(draw_dets_u8_kernel, dim3((unsigned)blocks, (unsigned)m), dim3(256), 0, (hipStream_t)stream, d_buf, src_bytes,
                            d_table + base, d_dets + (size_t)base * cap * 6, cap, d_counts + base, d_colors, n_colors, d_atlas, gh, gw,
                            max_pixels);
-    }
+    });
     YK_HIP(hipGetLastError());
     return YK_OK;
 }

@@ -85,203 +85,135 @@ extern "C" int yk_letterbox_u8(const uint8_t *d_src, int batch, int src_h, int s
     return YK_OK;
 }
 
-// ---- the same letterbox for a RAGGED batch: pictures of different sizes packed into one buffer, one table row each (yolo_hip.h), one
-// launch.  blockIdx.y is the picture, so a workgroup reads one row (uniform loads) and every pixel goes through letterbox_px with that
-// row's (scale, tx, ty) - the values letterbox_params gives yk_letterbox_u8 for the same sizes, hence the same bytes.  Picture offsets carry
-// no alignment (3-byte pixels): sources are read a byte at a time, as above.
-__global__ void __launch_bounds__(256) letterbox_ragged_u8_kernel(const uint8_t *__restrict__ src, size_t src_bytes,
-                                                                  const yk_ragged_row_t *__restrict__ table, uint8_t *__restrict__ dst, int dh,
-                                                                  int dw) {
-    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
-    const size_t per = (size_t)dh * dw;
-    if (idx >= per) return;
-    const yk_ragged_row_t row = table[blockIdx.y];
-    const int x = (int)(idx % dw), y = (int)(idx / dw);
-    uint8_t v[3] = {0, 0, 0};
-    // a row the host should have refused: nothing of src is read for it
-    const bool ok = row.h > 0 && row.w > 0 && row.offset <= src_bytes && (size_t)row.h * row.w * 3 <= src_bytes - row.offset;
-    if (ok) letterbox_px(src + row.offset, row.h, row.w, row.scale, row.tx, row.ty, x, y, v);
-    uint8_t *o = dst + ((size_t)blockIdx.y * per + idx) * 3;
-    o[0] = v[0];
-    o[1] = v[1];
-    o[2] = v[2];
+// ---- the same letterbox with ONE FRAME PER TABLE ROW (the three row types of yolo_hip.h), one launch: blockIdx.y is the row, so a workgroup
+// reads one row (uniform loads) and every pixel goes through letterbox_px_of with that row's (scale, tx, ty) - the values letterbox_params gives
+// yk_letterbox_u8 for the same sizes, hence the same bytes.  Offsets carry no alignment (3-byte pixels): sources are read a byte at a time, as
+// above.  A row type states two things: row_ok(row, src_bytes), false for a row the host should have refused - nothing of src is read for it and
+// its frame is zeros - and row_px(src, row, x, y, out), the source size and the tap this row hands to the arithmetic.
+//
+// A RAGGED batch: pictures of different sizes packed into one buffer, one row each.
+__device__ __forceinline__ bool row_ok(const yk_ragged_row_t row, size_t src_bytes) { return yk_ragged_row_inside(row, src_bytes); }
+__device__ __forceinline__ void row_px(const uint8_t *__restrict__ src, const yk_ragged_row_t row, int x, int y, uint8_t out[3]) {
+    letterbox_px(src + row.offset, row.h, row.w, row.scale, row.tx, row.ty, x, y, out);
 }
 
-extern "C" int yk_letterbox_ragged_params(yk_ragged_row_t *h_table, int n, int dst_h, int dst_w) {
-    if (!h_table || n <= 0 || dst_h <= 0 || dst_w <= 0) {
-        yk_set_error("yk_letterbox_ragged_params: bad argument");
-        return YK_ERR_ARG;
-    }
-    for (int i = 0; i < n; ++i)
-        if (h_table[i].h <= 0 || h_table[i].w <= 0) {
-            yk_set_error("yk_letterbox_ragged_params: row %d is %d x %d", i, (int)h_table[i].h, (int)h_table[i].w);
-            return YK_ERR_ARG;
-        }
-    for (int i = 0; i < n; ++i) {
-        int tx, ty;
-        letterbox_params(h_table[i].h, h_table[i].w, dst_h, dst_w, &h_table[i].scale, &tx, &ty);
-        h_table[i].tx = tx;
-        h_table[i].ty = ty;
-    }
-    return YK_OK;
-}
-
-extern "C" int yk_letterbox_ragged_u8(const uint8_t *d_src, size_t src_bytes, const yk_ragged_row_t *d_table, int n, uint8_t *d_dst,
-                                      int dst_h, int dst_w, void *stream) {
-    if (!d_src || !d_table || !d_dst || n <= 0 || src_bytes == 0 || dst_h <= 0 || dst_w <= 0) {
-        yk_set_error("yk_letterbox_ragged_u8: bad argument");
-        return YK_ERR_ARG;
-    }
-    if (yk_current_device() < 0) {
-        yk_set_error("yk_letterbox_ragged_u8: no HIP device");
-        return YK_ERR_NO_DEVICE;
-    }
-    const size_t per = (size_t)dst_h * dst_w;
-    for (int base = 0; base < n; base += 65535) {                                 // grid.y holds at most 65535 pictures
-        const int m = n - base < 65535 ? n - base : 65535;
-        hipLaunchKernelGGL(letterbox_ragged_u8_kernel, dim3((unsigned)((per + 255) / 256), (unsigned)m), dim3(256), 0, (hipStream_t)stream,
-                           d_src, src_bytes, d_table + base, d_dst + (size_t)base * per * 3, dst_h, dst_w);
-    }
-    YK_HIP(hipGetLastError());
-    return YK_OK;
-}
-
-// ---- the same letterbox for TILES of the pictures of a ragged batch (sliced inference: k210_yolo_framework_amd/tiles.py): a
-// tile is h rows of w pixels `stride` bytes apart, so letterbox_px reads it in place and its bounds are the tile's - a tap outside the tile
-// reads 0, not the parent's neighbouring pixel, and frame t is yk_letterbox_u8 of a contiguous copy of the crop, bit for bit.
-__global__ void __launch_bounds__(256) letterbox_tiles_u8_kernel(const uint8_t *__restrict__ src, size_t src_bytes,
-                                                                 const yk_tile_row_t *__restrict__ table, uint8_t *__restrict__ dst, int dh,
-                                                                 int dw) {
-    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
-    const size_t per = (size_t)dh * dw;
-    if (idx >= per) return;
-    const yk_tile_row_t row = table[blockIdx.y];
-    const int x = (int)(idx % dw), y = (int)(idx / dw);
-    uint8_t v[3] = {0, 0, 0};
-    // a row the host should have refused: nothing of src is read for it.  Its last byte is offset + (h-1)*stride + 3*w - 1; tested by
-    // division, so that no product can overflow
+// TILES of the pictures of a ragged batch (sliced inference: k210_yolo_framework_amd/tiles.py): a tile is h rows of w pixels
+// `stride` bytes apart, so letterbox_px reads it in place and its bounds are the tile's - a tap outside the tile reads 0, not the parent's
+// neighbouring pixel, and frame t is yk_letterbox_u8 of a contiguous copy of the crop, bit for bit.
+__device__ __forceinline__ bool row_ok(const yk_tile_row_t row, size_t src_bytes) {
+    // Its last byte is offset + (h-1)*stride + 3*w - 1; tested by division, so that no product can overflow
     bool ok = row.h > 0 && row.w > 0 && row.stride >= (int64_t)3 * row.w && row.offset <= src_bytes;
     if (ok) {
         const size_t room = src_bytes - row.offset, last = (size_t)3 * row.w, st = (size_t)row.stride, rows = (size_t)(row.h - 1);
         ok = last <= room && (rows == 0 || st <= (room - last) / rows);
     }
-    if (ok) letterbox_px(src + row.offset, row.h, row.w, (size_t)row.stride, row.scale, row.tx, row.ty, x, y, v);
-    uint8_t *o = dst + ((size_t)blockIdx.y * per + idx) * 3;
-    o[0] = v[0];
-    o[1] = v[1];
-    o[2] = v[2];
+    return ok;
+}
+__device__ __forceinline__ void row_px(const uint8_t *__restrict__ src, const yk_tile_row_t row, int x, int y, uint8_t out[3]) {
+    letterbox_px(src + row.offset, row.h, row.w, (size_t)row.stride, row.scale, row.tx, row.ty, x, y, out);
 }
 
-extern "C" int yk_letterbox_tiles_params(yk_tile_row_t *h_table, int n, int dst_h, int dst_w) {
-    if (!h_table || n <= 0 || dst_h <= 0 || dst_w <= 0) {
-        yk_set_error("yk_letterbox_tiles_params: bad argument");
-        return YK_ERR_ARG;
-    }
-    for (int i = 0; i < n; ++i)
-        if (h_table[i].h <= 0 || h_table[i].w <= 0) {
-            yk_set_error("yk_letterbox_tiles_params: row %d is %d x %d", i, (int)h_table[i].h, (int)h_table[i].w);
-            return YK_ERR_ARG;
-        }
-    for (int i = 0; i < n; ++i) {
-        int tx, ty;
-        letterbox_params(h_table[i].h, h_table[i].w, dst_h, dst_w, &h_table[i].scale, &tx, &ty);
-        h_table[i].tx = tx;
-        h_table[i].ty = ty;
-    }
-    return YK_OK;
-}
-
-extern "C" int yk_letterbox_tiles_u8(const uint8_t *d_src, size_t src_bytes, const yk_tile_row_t *d_table, int n, uint8_t *d_dst, int dst_h,
-                                     int dst_w, void *stream) {
-    if (!d_src || !d_table || !d_dst || n <= 0 || src_bytes == 0 || dst_h <= 0 || dst_w <= 0) {
-        yk_set_error("yk_letterbox_tiles_u8: bad argument");
-        return YK_ERR_ARG;
-    }
-    if (yk_current_device() < 0) {
-        yk_set_error("yk_letterbox_tiles_u8: no HIP device");
-        return YK_ERR_NO_DEVICE;
-    }
-    const size_t per = (size_t)dst_h * dst_w;
-    for (int base = 0; base < n; base += 65535) {                                 // grid.y holds at most 65535 tiles
-        const int m = n - base < 65535 ? n - base : 65535;
-        hipLaunchKernelGGL(letterbox_tiles_u8_kernel, dim3((unsigned)((per + 255) / 256), (unsigned)m), dim3(256), 0, (hipStream_t)stream,
-                           d_src, src_bytes, d_table + base, d_dst + (size_t)base * per * 3, dst_h, dst_w);
-    }
-    YK_HIP(hipGetLastError());
-    return YK_OK;
-}
-
-// ---- the same letterbox for VIEWS of the pictures of a ragged batch (test-time augmentation: k210_yolo_framework_amd/tta.py): a
-// view is a zero canvas of ch x cw pixels with the picture pasted at (oy, ox), mirrored or not.  The canvas is the source letterbox_px_of sees,
-// its taps read out of the picture in place, so frame v is yk_letterbox_u8 of the canvas, bit for bit, and no canvas is ever written.
+// VIEWS of the pictures of a ragged batch (test-time augmentation: k210_yolo_framework_amd/tta.py): a view is a zero canvas of
+// ch x cw pixels with the picture pasted at (oy, ox), mirrored or not.  The canvas is the source letterbox_px_of sees, its taps read out of the
+// picture in place, so frame v is yk_letterbox_u8 of the canvas, bit for bit, and no canvas is ever written.
 static_assert(sizeof(yk_view_row_t) == 56, "yk_view_row_t has no padding");
-__global__ void __launch_bounds__(256) letterbox_views_u8_kernel(const uint8_t *__restrict__ src, size_t src_bytes,
-                                                                 const yk_view_row_t *__restrict__ table, uint8_t *__restrict__ dst, int dh,
-                                                                 int dw) {
+__device__ __forceinline__ bool row_ok(const yk_view_row_t row, size_t src_bytes) {
+    // The sums are taken in 64 bits, so none can overflow
+    return row.h > 0 && row.w > 0 && row.oy >= 0 && row.ox >= 0 && (int64_t)row.oy + row.h <= (int64_t)row.ch &&
+           (int64_t)row.ox + row.w <= (int64_t)row.cw && row.offset <= src_bytes && (size_t)row.h * row.w * 3 <= src_bytes - row.offset;
+}
+__device__ __forceinline__ void row_px(const uint8_t *__restrict__ src, const yk_view_row_t row, int x, int y, uint8_t out[3]) {
+    const uint8_t *im = src + row.offset;
+    const int h = row.h, w = row.w, oy = row.oy, ox = row.ox;
+    const bool mirror = row.mirror != 0;
+    letterbox_px_of(
+        [&](int yy, int xx, int ch) -> uint8_t {
+            const int py = yy - oy, qx = xx - ox;                  // yy in [0, ch), oy in [0, ch]: no overflow
+            if (py < 0 || py >= h || qx < 0 || qx >= w) return 0;
+            return im[((size_t)py * w + (size_t)(mirror ? w - 1 - qx : qx)) * 3 + ch];
+        },
+        row.ch, row.cw, row.scale, row.tx, row.ty, x, y, out);
+}
+
+template <class Row>
+__global__ void __launch_bounds__(256) letterbox_rows_u8_kernel(const uint8_t *__restrict__ src, size_t src_bytes, const Row *__restrict__ table,
+                                                                uint8_t *__restrict__ dst, int dh, int dw) {
     const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
     const size_t per = (size_t)dh * dw;
     if (idx >= per) return;
-    const yk_view_row_t row = table[blockIdx.y];
+    const Row row = table[blockIdx.y];
     const int x = (int)(idx % dw), y = (int)(idx / dw);
     uint8_t v[3] = {0, 0, 0};
-    // a row the host should have refused: nothing of src is read for it.  The sums are taken in 64 bits, so none can overflow
-    const bool ok = row.h > 0 && row.w > 0 && row.oy >= 0 && row.ox >= 0 && (int64_t)row.oy + row.h <= (int64_t)row.ch &&
-                    (int64_t)row.ox + row.w <= (int64_t)row.cw && row.offset <= src_bytes && (size_t)row.h * row.w * 3 <= src_bytes - row.offset;
-    if (ok) {
-        const uint8_t *im = src + row.offset;
-        const int h = row.h, w = row.w, oy = row.oy, ox = row.ox;
-        const bool mirror = row.mirror != 0;
-        letterbox_px_of(
-            [&](int yy, int xx, int ch) -> uint8_t {
-                const int py = yy - oy, qx = xx - ox;                  // yy in [0, ch), oy in [0, ch]: no overflow
-                if (py < 0 || py >= h || qx < 0 || qx >= w) return 0;
-                return im[((size_t)py * w + (size_t)(mirror ? w - 1 - qx : qx)) * 3 + ch];
-            },
-            row.ch, row.cw, row.scale, row.tx, row.ty, x, y, v);
-    }
+    const bool ok = row_ok(row, src_bytes);
+    if (ok) row_px(src, row, x, y, v);
     uint8_t *o = dst + ((size_t)blockIdx.y * per + idx) * 3;
     o[0] = v[0];
     o[1] = v[1];
     o[2] = v[2];
 }
 
-extern "C" int yk_letterbox_views_params(yk_view_row_t *h_table, int n, int dst_h, int dst_w) {
+template <class Row>
+static int letterbox_rows_u8(const char *name, const uint8_t *d_src, size_t src_bytes, const Row *d_table, int n, uint8_t *d_dst, int dst_h,
+                             int dst_w, void *stream) {
+    if (!d_src || !d_table || !d_dst || n <= 0 || src_bytes == 0 || dst_h <= 0 || dst_w <= 0) {
+        yk_set_error("%s: bad argument", name);
+        return YK_ERR_ARG;
+    }
+    if (yk_current_device() < 0) {
+        yk_set_error("%s: no HIP device", name);
+        return YK_ERR_NO_DEVICE;
+    }
+    const size_t per = (size_t)dst_h * dst_w;
+    yk_for_grid_y(n, [&](int base, int m) {
+        hipLaunchKernelGGL(letterbox_rows_u8_kernel<Row>, dim3((unsigned)((per + 255) / 256), (unsigned)m), dim3(256), 0, (hipStream_t)stream,
+                           d_src, src_bytes, d_table + base, d_dst + (size_t)base * per * 3, dst_h, dst_w);
+    });
+    YK_HIP(hipGetLastError());
+    return YK_OK;
+}
+
+// scale, tx, ty of n host rows from the source size each row's fields sh, sw hold; `what` words the refusal of a row without one
+template <class Row>
+static int fill_params(const char *name, const char *what, int32_t Row::*sh, int32_t Row::*sw, Row *h_table, int n, int dst_h, int dst_w) {
     if (!h_table || n <= 0 || dst_h <= 0 || dst_w <= 0) {
-        yk_set_error("yk_letterbox_views_params: bad argument");
+        yk_set_error("%s: bad argument", name);
         return YK_ERR_ARG;
     }
     for (int i = 0; i < n; ++i)
-        if (h_table[i].ch <= 0 || h_table[i].cw <= 0) {
-            yk_set_error("yk_letterbox_views_params: row %d has a canvas of %d x %d", i, (int)h_table[i].ch, (int)h_table[i].cw);
+        if (h_table[i].*sh <= 0 || h_table[i].*sw <= 0) {
+            yk_set_error("%s: row %d %s %d x %d", name, i, what, (int)(h_table[i].*sh), (int)(h_table[i].*sw));
             return YK_ERR_ARG;
         }
     for (int i = 0; i < n; ++i) {
         int tx, ty;
-        letterbox_params(h_table[i].ch, h_table[i].cw, dst_h, dst_w, &h_table[i].scale, &tx, &ty);
+        letterbox_params(h_table[i].*sh, h_table[i].*sw, dst_h, dst_w, &h_table[i].scale, &tx, &ty);
         h_table[i].tx = tx;
         h_table[i].ty = ty;
     }
     return YK_OK;
 }
 
+extern "C" int yk_letterbox_ragged_params(yk_ragged_row_t *h_table, int n, int dst_h, int dst_w) {
+    return fill_params("yk_letterbox_ragged_params", "is", &yk_ragged_row_t::h, &yk_ragged_row_t::w, h_table, n, dst_h, dst_w);
+}
+extern "C" int yk_letterbox_tiles_params(yk_tile_row_t *h_table, int n, int dst_h, int dst_w) {
+    return fill_params("yk_letterbox_tiles_params", "is", &yk_tile_row_t::h, &yk_tile_row_t::w, h_table, n, dst_h, dst_w);
+}
+extern "C" int yk_letterbox_views_params(yk_view_row_t *h_table, int n, int dst_h, int dst_w) {
+    return fill_params("yk_letterbox_views_params", "has a canvas of", &yk_view_row_t::ch, &yk_view_row_t::cw, h_table, n, dst_h, dst_w);
+}
+
+extern "C" int yk_letterbox_ragged_u8(const uint8_t *d_src, size_t src_bytes, const yk_ragged_row_t *d_table, int n, uint8_t *d_dst,
+                                      int dst_h, int dst_w, void *stream) {
+    return letterbox_rows_u8("yk_letterbox_ragged_u8", d_src, src_bytes, d_table, n, d_dst, dst_h, dst_w, stream);
+}
+extern "C" int yk_letterbox_tiles_u8(const uint8_t *d_src, size_t src_bytes, const yk_tile_row_t *d_table, int n, uint8_t *d_dst, int dst_h,
+                                     int dst_w, void *stream) {
+    return letterbox_rows_u8("yk_letterbox_tiles_u8", d_src, src_bytes, d_table, n, d_dst, dst_h, dst_w, stream);
+}
 extern "C" int yk_letterbox_views_u8(const uint8_t *d_src, size_t src_bytes, const yk_view_row_t *d_table, int n, uint8_t *d_dst, int dst_h,
                                      int dst_w, void *stream) {
-    if (!d_src || !d_table || !d_dst || n <= 0 || src_bytes == 0 || dst_h <= 0 || dst_w <= 0) {
-        yk_set_error("yk_letterbox_views_u8: bad argument");
-        return YK_ERR_ARG;
-    }
-    if (yk_current_device() < 0) {
-        yk_set_error("yk_letterbox_views_u8: no HIP device");
-        return YK_ERR_NO_DEVICE;
-    }
-    const size_t per = (size_t)dst_h * dst_w;
-    for (int base = 0; base < n; base += 65535) {                                 // grid.y holds at most 65535 views
-        const int m = n - base < 65535 ? n - base : 65535;
-        hipLaunchKernelGGL(letterbox_views_u8_kernel, dim3((unsigned)((per + 255) / 256), (unsigned)m), dim3(256), 0, (hipStream_t)stream,
-                           d_src, src_bytes, d_table + base, d_dst + (size_t)base * per * 3, dst_h, dst_w);
-    }
-    YK_HIP(hipGetLastError());
-    return YK_OK;
+    return letterbox_rows_u8("yk_letterbox_views_u8", d_src, src_bytes, d_table, n, d_dst, dst_h, dst_w, stream);
 }
 
 // ---- letterbox + training augmentation (k210_yolo_framework_amd/augment.py; the imgaug OneOf of tools/utils.py:84-88): the u8
@@ -291,6 +223,33 @@ extern "C" int yk_letterbox_views_u8(const uint8_t *d_src, size_t src_bytes, con
 //   out = min(255, floor((1-dr)*top + dr*bottom + 0.5)).
 // Each tap's L value is computed on the fly (letterbox_px), so no intermediate frame goes to HBM and the result is bit-identical
 // to yk_letterbox_u8 followed by the warp.  Identity and mirror matrices have integer entries: an exact pixel copy.
+//
+// The warp of output pixel (x, y) of a dh x dw frame by the map m[6], written to o[3]: frame(xx, yy, v) puts the frame's pixel at an integer
+// position inside it into v, which arrives as zeros.
+template <class Frame>
+__device__ __forceinline__ void warp_px(Frame frame, const double *m, int dh, int dw, int x, int y, uint8_t *o) {
+    const double c = m[0] * (double)x + m[1] * (double)y + m[2], r = m[3] * (double)x + m[4] * (double)y + m[5];
+    const double minc_f = floor(c), minr_f = floor(r), maxc_f = ceil(c), maxr_f = ceil(r);
+    const double dc = c - minc_f, dr = r - minr_f;
+    const double tr[4] = {minr_f, minr_f, maxr_f, maxr_f}, tc[4] = {minc_f, maxc_f, minc_f, maxc_f};
+    double t[4][3];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        uint8_t v[3] = {0, 0, 0};
+        if (tr[k] >= 0.0 && tr[k] < (double)dh && tc[k] >= 0.0 && tc[k] < (double)dw)      // compared as doubles: any M is safe
+            frame((int)tc[k], (int)tr[k], v);
+        t[k][0] = v[0];
+        t[k][1] = v[1];
+        t[k][2] = v[2];
+    }
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+        const double top = (1.0 - dc) * t[0][ch] + dc * t[1][ch];
+        const double bottom = (1.0 - dc) * t[2][ch] + dc * t[3][ch];
+        o[ch] = (uint8_t)fmin(255.0, floor((1.0 - dr) * top + dr * bottom + 0.5));
+    }
+}
+
 __global__ void __launch_bounds__(256) letterbox_augment_u8_kernel(const uint8_t *__restrict__ src, int batch, int sh, int sw,
                                                                    const double *__restrict__ inv, uint8_t *__restrict__ dst, int dh,
                                                                    int dw, double scale, int tx, int ty) {
@@ -298,29 +257,9 @@ __global__ void __launch_bounds__(256) letterbox_augment_u8_kernel(const uint8_t
     const size_t total = (size_t)batch * dh * dw;
     if (idx >= total) return;
     const int x = (int)(idx % dw), y = (int)((idx / dw) % dh), b = (int)(idx / ((size_t)dw * dh));
-    const double *m = inv + (size_t)b * 6;
-    const double c = m[0] * (double)x + m[1] * (double)y + m[2], r = m[3] * (double)x + m[4] * (double)y + m[5];
-    const double minc_f = floor(c), minr_f = floor(r), maxc_f = ceil(c), maxr_f = ceil(r);
-    const double dc = c - minc_f, dr = r - minr_f;
     const uint8_t *im = src + (size_t)b * sh * sw * 3;
-    const double tr[4] = {minr_f, minr_f, maxr_f, maxr_f}, tc[4] = {minc_f, maxc_f, minc_f, maxc_f};
-    double t[4][3];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        uint8_t v[3] = {0, 0, 0};
-        if (tr[k] >= 0.0 && tr[k] < (double)dh && tc[k] >= 0.0 && tc[k] < (double)dw)      // compared as doubles: any M is safe
-            letterbox_px(im, sh, sw, scale, tx, ty, (int)tc[k], (int)tr[k], v);
-        t[k][0] = v[0];
-        t[k][1] = v[1];
-        t[k][2] = v[2];
-    }
-    uint8_t *o = dst + idx * 3;
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch) {
-        const double top = (1.0 - dc) * t[0][ch] + dc * t[1][ch];
-        const double bottom = (1.0 - dc) * t[2][ch] + dc * t[3][ch];
-        o[ch] = (uint8_t)fmin(255.0, floor((1.0 - dr) * top + dr * bottom + 0.5));
-    }
+    warp_px([=](int xx, int yy, uint8_t v[3]) { letterbox_px(im, sh, sw, scale, tx, ty, xx, yy, v); }, inv + (size_t)b * 6, dh, dw, x, y,
+            dst + idx * 3);
 }
 
 extern "C" int yk_letterbox_augment_u8(const uint8_t *d_src, int batch, int src_h, int src_w, const double *d_inv, uint8_t *d_dst,
@@ -352,11 +291,10 @@ __device__ __forceinline__ void mosaic_px(const uint8_t *__restrict__ src, size_
                                           int cy, int x, int y, uint8_t out[3]) {
     const yk_ragged_row_t row = rows4[(x >= cx ? 1 : 0) + (y >= cy ? 2 : 0)];
     out[0] = out[1] = out[2] = 0;
-    const bool ok = row.h > 0 && row.w > 0 && row.offset <= src_bytes && (size_t)row.h * row.w * 3 <= src_bytes - row.offset;
-    if (ok) letterbox_px(src + row.offset, row.h, row.w, row.scale, row.tx, row.ty, x, y, out);
+    if (yk_ragged_row_inside(row, src_bytes)) letterbox_px(src + row.offset, row.h, row.w, row.scale, row.tx, row.ty, x, y, out);
 }
 
-// inv == NULL: the mosaic frame itself.  Otherwise the frame warped by the sample's inverse map exactly as letterbox_augment_u8_kernel warps
+// inv == NULL: the mosaic frame itself.  Otherwise the frame warped by the sample's inverse map - warp_px, as letterbox_augment_u8_kernel warps
 // the letterbox: each of the four taps evaluates the mosaic pixel on the fly, no intermediate frame.
 __global__ void __launch_bounds__(256) mosaic_ragged_u8_kernel(const uint8_t *__restrict__ src, size_t src_bytes,
                                                                const yk_ragged_row_t *__restrict__ table, const int32_t *__restrict__ centre,
@@ -376,27 +314,8 @@ __global__ void __launch_bounds__(256) mosaic_ragged_u8_kernel(const uint8_t *__
         o[2] = v[2];
         return;
     }
-    const double *m = inv + (size_t)blockIdx.y * 6;
-    const double c = m[0] * (double)x + m[1] * (double)y + m[2], r = m[3] * (double)x + m[4] * (double)y + m[5];
-    const double minc_f = floor(c), minr_f = floor(r), maxc_f = ceil(c), maxr_f = ceil(r);
-    const double dc = c - minc_f, dr = r - minr_f;
-    const double tr[4] = {minr_f, minr_f, maxr_f, maxr_f}, tc[4] = {minc_f, maxc_f, minc_f, maxc_f};
-    double t[4][3];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        uint8_t v[3] = {0, 0, 0};
-        if (tr[k] >= 0.0 && tr[k] < (double)dh && tc[k] >= 0.0 && tc[k] < (double)dw)      // compared as doubles: any M is safe
-            mosaic_px(src, src_bytes, rows4, cx, cy, (int)tc[k], (int)tr[k], v);
-        t[k][0] = v[0];
-        t[k][1] = v[1];
-        t[k][2] = v[2];
-    }
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch) {
-        const double top = (1.0 - dc) * t[0][ch] + dc * t[1][ch];
-        const double bottom = (1.0 - dc) * t[2][ch] + dc * t[3][ch];
-        o[ch] = (uint8_t)fmin(255.0, floor((1.0 - dr) * top + dr * bottom + 0.5));
-    }
+    warp_px([=](int xx, int yy, uint8_t v[3]) { mosaic_px(src, src_bytes, rows4, cx, cy, xx, yy, v); }, inv + (size_t)blockIdx.y * 6, dh, dw, x, y,
+            o);
 }
 
 extern "C" int yk_mosaic_params(yk_ragged_row_t *h_rows4, int cx, int cy, const double *gain4, int dst_h, int dst_w) {
@@ -433,12 +352,11 @@ extern "C" int yk_mosaic_ragged_u8(const uint8_t *d_src, size_t src_bytes, const
         return YK_ERR_NO_DEVICE;
     }
     const size_t per = (size_t)dst_h * dst_w;
-    for (int base = 0; base < n; base += 65535) {                                 // grid.y holds at most 65535 samples
-        const int m = n - base < 65535 ? n - base : 65535;
+    yk_for_grid_y(n, [&](int base, int m) {
         hipLaunchKernelGGL(mosaic_ragged_u8_kernel, dim3((unsigned)((per + 255) / 256), (unsigned)m), dim3(256), 0, (hipStream_t)stream, d_src,
                            src_bytes, d_table + (size_t)base * 4, d_centre + (size_t)base * 2, d_inv ? d_inv + (size_t)base * 6 : nullptr,
                            d_dst + (size_t)base * per * 3, dst_h, dst_w);
-    }
+    });
     YK_HIP(hipGetLastError());
     return YK_OK;
 }

@@ -14,11 +14,11 @@ import ctypes as C
 import functools
 import os
 from pathlib import Path
-from typing import List, Optional, Sequence, Tuple
+from typing import Callable, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
-from . import abi
+from . import abi, draw, tiles, tta
 from . import netspec as ns
 
 # YK_LIB_PATH: the developer build of the same library (`make -C csrc dev`: tuning switches compiled in), for tools/ only
@@ -503,38 +503,94 @@ def letterbox_augment_u8(frames, dst_hw, inv, stream=None, out=None):
     return out
 
 
-def ragged_table_to_device(table, dst_hw, packed_bytes: int, device, stream=None):
-    """A host table of a ragged batch (draw.RAGGED_DTYPE = yk_ragged_row_t; draw.pack_ragged writes it) checked, completed and uploaded:
-    every row must be a non-empty picture inside the `packed_bytes` of its buffer; scale / tx / ty are filled for the network size dst_hw
-    (None: left as they are - drawing does not read them).  -> cuda uint8 [n, 40], what the ragged calls take as their table."""
+class _RowKind(NamedTuple):
+    """What tells the three per-picture tables of include/yolo_hip.h apart.  _check_rows, _table_to_device and _letterbox_rows_u8 are the one
+    implementation behind the ragged, tile and view functions below."""
+    label: str                      # '<label> table: ...' in every message
+    dtype: np.dtype
+    extra: Optional[Callable]       # t -> (the rows it refuses, i -> the rest of '<label> table: row i ...'); after the test for pixels
+    end: Callable                   # (name -> that column as Python ints) -> the byte one past each row's last
+    params: str                     # the C function that fills scale / tx / ty
+    launch: str                     # the C function that letterboxes the rows
+
+
+def _tile_stride(t):
+    return (t['stride'] < 3 * t['w'].astype(np.int64),
+            lambda i: f'has stride {int(t["stride"][i])}, less than the {3 * int(t["w"][i])} bytes of one of its rows')
+
+
+def _view_canvas(t):
+    i64 = lambda name: t[name].astype(np.int64)
+    return ((t['oy'] < 0) | (t['ox'] < 0) | (i64('oy') + i64('h') > i64('ch')) | (i64('ox') + i64('w') > i64('cw')),
+            lambda i: f'puts its {int(t["h"][i])} x {int(t["w"][i])} picture at ({int(t["oy"][i])}, {int(t["ox"][i])}), outside its '
+                      f'canvas of {int(t["ch"][i])} x {int(t["cw"][i])}')
+
+
+def _picture_end(col):
+    return col('offset') + 3 * col('h') * col('w')
+
+
+_RAGGED = _RowKind('ragged', draw.RAGGED_DTYPE, None, _picture_end, 'yk_letterbox_ragged_params', 'yk_letterbox_ragged_u8')
+_TILE = _RowKind('tile', tiles.TILE_DTYPE, _tile_stride, lambda col: col('offset') + (col('h') - 1) * col('stride') + 3 * col('w'),
+                 'yk_letterbox_tiles_params', 'yk_letterbox_tiles_u8')
+_VIEW = _RowKind('view', tta.VIEW_DTYPE, _view_canvas, _picture_end, 'yk_letterbox_views_params', 'yk_letterbox_views_u8')
+
+
+def _check_rows(kind: _RowKind, table, packed_bytes: int) -> np.ndarray:
+    t = np.array(table, dtype=kind.dtype, copy=True).reshape(-1)
+    checks = [((t['h'] <= 0) | (t['w'] <= 0), lambda i: f'is {int(t["h"][i])} x {int(t["w"][i])}')]
+    if kind.extra is not None:
+        checks.append(kind.extra(t))
+    for bad, what in checks:
+        if bad.any():
+            i = int(np.nonzero(bad)[0][0])
+            raise YkError(f'{kind.label} table: row {i} {what(i)}')
+    end = kind.end(lambda name: t[name].astype(object))
+    if len(t) and max(end) > int(packed_bytes):
+        raise YkError(f'{kind.label} table: row {int(np.argmax(end))} ends at byte {max(end)} of a {int(packed_bytes)}-byte buffer')
+    return t
+
+
+def _table_to_device(kind: _RowKind, table, dst_hw, packed_bytes: int, device, stream):
     import torch
-    from .draw import RAGGED_DTYPE
-    t = np.array(table, dtype=RAGGED_DTYPE, copy=True).reshape(-1)
-    if len(t) == 0:
-        raise YkError('ragged table: no rows')
-    bad = (t['h'] <= 0) | (t['w'] <= 0)
-    if bad.any():
-        i = int(np.nonzero(bad)[0][0])
-        raise YkError(f'ragged table: row {i} is {int(t["h"][i])} x {int(t["w"][i])}')
-    end = t['offset'].astype(object) + 3 * t['h'].astype(object) * t['w'].astype(object)
-    if max(end) > int(packed_bytes):
-        raise YkError(f'ragged table: row {int(np.argmax(end))} ends at byte {max(end)} of a {int(packed_bytes)}-byte buffer')
+    t = _check_rows(kind, table, packed_bytes)
+    if len(t) == 0:                                    # (an empty table passes _check_rows: this is the first thing said about it)
+        raise YkError(f'{kind.label} table: no rows')
     if dst_hw is not None:
-        call('yk_letterbox_ragged_params', t, len(t), int(dst_hw[0]), int(dst_hw[1]))
-    host = torch.from_numpy(t.view(np.uint8).reshape(len(t), RAGGED_DTYPE.itemsize))
+        call(kind.params, t, len(t), int(dst_hw[0]), int(dst_hw[1]))
+    host = torch.from_numpy(t.view(np.uint8).reshape(len(t), kind.dtype.itemsize))
     with torch.cuda.stream(torch.cuda.current_stream() if stream is None else stream):
         return host.to(device, non_blocking=False)
 
 
-def _ragged_args(packed, table, dst_hw, stream):
+def _device_table(kind: _RowKind, packed, table, dst_hw, stream):
+    """`table` as the calls on a packed buffer take it: a host table goes through _table_to_device, a device table is checked for its shape."""
     import torch
-    from .draw import RAGGED_DTYPE
     assert packed.is_cuda and packed.dtype == torch.uint8 and packed.is_contiguous() and packed.numel() > 0
     if not torch.is_tensor(table):
-        table = ragged_table_to_device(table, dst_hw, packed.numel(), packed.device, stream)
+        table = _table_to_device(kind, table, dst_hw, packed.numel(), packed.device, stream)
     assert table.is_cuda and table.dtype == torch.uint8 and table.is_contiguous() and table.dim() == 2 and table.device == packed.device
-    assert table.shape[1] == RAGGED_DTYPE.itemsize and table.shape[0] > 0, tuple(table.shape)
+    assert table.shape[1] == kind.dtype.itemsize and table.shape[0] > 0, tuple(table.shape)
     return table
+
+
+def _letterbox_rows_u8(kind: _RowKind, packed, table, dst_hw, stream, out):
+    import torch
+    require_gpu()
+    table = _device_table(kind, packed, table, dst_hw, stream)
+    n = int(table.shape[0])
+    if out is None:
+        out = torch.empty((n, int(dst_hw[0]), int(dst_hw[1]), 3), dtype=torch.uint8, device=packed.device)
+    assert out.is_cuda and out.is_contiguous() and tuple(out.shape) == (n, int(dst_hw[0]), int(dst_hw[1]), 3), tuple(out.shape)
+    call(kind.launch, packed, packed.numel(), table, n, out, out.shape[1], out.shape[2], _stream(stream))
+    return out
+
+
+def ragged_table_to_device(table, dst_hw, packed_bytes: int, device, stream=None):
+    """A host table of a ragged batch (draw.RAGGED_DTYPE = yk_ragged_row_t; draw.pack_ragged writes it) checked, completed and uploaded:
+    every row must be a non-empty picture inside the `packed_bytes` of its buffer; scale / tx / ty are filled for the network size dst_hw
+    (None: left as they are - drawing does not read them).  -> cuda uint8 [n, 40], what the ragged calls take as their table."""
+    return _table_to_device(_RAGGED, table, dst_hw, packed_bytes, device, stream)
 
 
 def letterbox_ragged_u8(packed, table, dst_hw, stream=None, out=None):
@@ -542,63 +598,26 @@ def letterbox_ragged_u8(packed, table, dst_hw, stream=None, out=None):
     pictures of draw.pack_ragged; `table` its host table (checked here: a row without pixels, or one that leaves the buffer, is refused) or
     the device table ragged_table_to_device returned for this dst_hw.  -> cuda uint8 [n, H, W, 3]; image i is bit for bit
     letterbox_u8 of picture i alone."""
-    import torch
-    require_gpu()
-    table = _ragged_args(packed, table, dst_hw, stream)
-    n = int(table.shape[0])
-    if out is None:
-        out = torch.empty((n, int(dst_hw[0]), int(dst_hw[1]), 3), dtype=torch.uint8, device=packed.device)
-    assert out.is_cuda and out.is_contiguous() and tuple(out.shape) == (n, int(dst_hw[0]), int(dst_hw[1]), 3), tuple(out.shape)
-    call('yk_letterbox_ragged_u8', packed, packed.numel(), table, n, out, out.shape[1], out.shape[2], _stream(stream))
-    return out
+    return _letterbox_rows_u8(_RAGGED, packed, table, dst_hw, stream, out)
 
 
 def check_ragged_rows(table, packed_bytes: int) -> np.ndarray:
     """The rows of a host table (draw.RAGGED_DTYPE) as one flat copy, refused with YkError unless every row is a non-empty picture inside
     the `packed_bytes` of its buffer: what the kernels would otherwise answer with zeros."""
-    from .draw import RAGGED_DTYPE
-    t = np.array(table, dtype=RAGGED_DTYPE, copy=True).reshape(-1)
-    bad = (t['h'] <= 0) | (t['w'] <= 0)
-    if bad.any():
-        i = int(np.nonzero(bad)[0][0])
-        raise YkError(f'ragged table: row {i} is {int(t["h"][i])} x {int(t["w"][i])}')
-    end = t['offset'].astype(object) + 3 * t['h'].astype(object) * t['w'].astype(object)
-    if len(t) and max(end) > int(packed_bytes):
-        raise YkError(f'ragged table: row {int(np.argmax(end))} ends at byte {max(end)} of a {int(packed_bytes)}-byte buffer')
-    return t
+    return _check_rows(_RAGGED, table, packed_bytes)
 
 
 def check_tile_rows(table, packed_bytes: int) -> np.ndarray:
     """The rows of a host tile table (tiles.TILE_DTYPE = yk_tile_row_t) as one flat copy, refused with YkError unless every row is a non-empty
     tile whose rows do not overlap (stride >= 3 * w) and whose last byte lies inside the `packed_bytes` of its buffer: what
     yk_letterbox_tiles_u8 would otherwise answer with a zero frame."""
-    from .tiles import TILE_DTYPE
-    t = np.array(table, dtype=TILE_DTYPE, copy=True).reshape(-1)
-    bad = (t['h'] <= 0) | (t['w'] <= 0)
-    if bad.any():
-        i = int(np.nonzero(bad)[0][0])
-        raise YkError(f'tile table: row {i} is {int(t["h"][i])} x {int(t["w"][i])}')
-    bad = t['stride'] < 3 * t['w'].astype(np.int64)
-    if bad.any():
-        i = int(np.nonzero(bad)[0][0])
-        raise YkError(f'tile table: row {i} has stride {int(t["stride"][i])}, less than the {3 * int(t["w"][i])} bytes of one of its rows')
-    end = t['offset'].astype(object) + (t['h'].astype(object) - 1) * t['stride'].astype(object) + 3 * t['w'].astype(object)
-    if len(t) and max(end) > int(packed_bytes):
-        raise YkError(f'tile table: row {int(np.argmax(end))} ends at byte {max(end)} of a {int(packed_bytes)}-byte buffer')
-    return t
+    return _check_rows(_TILE, table, packed_bytes)
 
 
 def tile_table_to_device(table, dst_hw, packed_bytes: int, device, stream=None):
     """A host tile table (tiles.table_rows) checked (check_tile_rows), its scale / tx / ty filled for the network size dst_hw and uploaded
     -> cuda uint8 [n, 40], what letterbox_tiles_u8 takes as its table."""
-    import torch
-    t = check_tile_rows(table, packed_bytes)
-    if len(t) == 0:
-        raise YkError('tile table: no rows')
-    call('yk_letterbox_tiles_params', t, len(t), int(dst_hw[0]), int(dst_hw[1]))
-    host = torch.from_numpy(t.view(np.uint8).reshape(len(t), t.dtype.itemsize))
-    with torch.cuda.stream(torch.cuda.current_stream() if stream is None else stream):
-        return host.to(device, non_blocking=False)
+    return _table_to_device(_TILE, table, dst_hw, packed_bytes, device, stream)
 
 
 def letterbox_tiles_u8(packed, table, dst_hw, stream=None, out=None):
@@ -606,20 +625,7 @@ def letterbox_tiles_u8(packed, table, dst_hw, stream=None, out=None):
     [bytes]; `table` a host table of tiles.TILE_DTYPE (checked here: a row the kernel would answer with zeros is refused) or the device table
     tile_table_to_device returned for this dst_hw.  -> cuda uint8 [n, H, W, 3]; frame t is bit for bit letterbox_u8 of a contiguous copy of
     tile t."""
-    import torch
-    from .tiles import TILE_DTYPE
-    require_gpu()
-    assert packed.is_cuda and packed.dtype == torch.uint8 and packed.is_contiguous() and packed.numel() > 0
-    if not torch.is_tensor(table):
-        table = tile_table_to_device(table, dst_hw, packed.numel(), packed.device, stream)
-    assert table.is_cuda and table.dtype == torch.uint8 and table.is_contiguous() and table.dim() == 2 and table.device == packed.device
-    assert table.shape[1] == TILE_DTYPE.itemsize and table.shape[0] > 0, tuple(table.shape)
-    n = int(table.shape[0])
-    if out is None:
-        out = torch.empty((n, int(dst_hw[0]), int(dst_hw[1]), 3), dtype=torch.uint8, device=packed.device)
-    assert out.is_cuda and out.is_contiguous() and tuple(out.shape) == (n, int(dst_hw[0]), int(dst_hw[1]), 3), tuple(out.shape)
-    call('yk_letterbox_tiles_u8', packed, packed.numel(), table, n, out, out.shape[1], out.shape[2], _stream(stream))
-    return out
+    return _letterbox_rows_u8(_TILE, packed, table, dst_hw, stream, out)
 
 
 def merge_tiles_lds_candidates(n_tiles: int, n_pics: int, max_out: int) -> int:
@@ -670,35 +676,13 @@ def check_view_rows(table, packed_bytes: int) -> np.ndarray:
     """The rows of a host view table (tta.VIEW_DTYPE = yk_view_row_t) as one flat copy, refused with YkError unless every row is a non-empty
     picture inside the `packed_bytes` of its buffer and inside its canvas: what yk_letterbox_views_u8 would otherwise answer with a zero
     frame."""
-    from .tta import VIEW_DTYPE
-    t = np.array(table, dtype=VIEW_DTYPE, copy=True).reshape(-1)
-    bad = (t['h'] <= 0) | (t['w'] <= 0)
-    if bad.any():
-        i = int(np.nonzero(bad)[0][0])
-        raise YkError(f'view table: row {i} is {int(t["h"][i])} x {int(t["w"][i])}')
-    i64 = lambda name: t[name].astype(np.int64)
-    bad = (t['oy'] < 0) | (t['ox'] < 0) | (i64('oy') + i64('h') > i64('ch')) | (i64('ox') + i64('w') > i64('cw'))
-    if bad.any():
-        i = int(np.nonzero(bad)[0][0])
-        raise YkError(f'view table: row {i} puts its {int(t["h"][i])} x {int(t["w"][i])} picture at ({int(t["oy"][i])}, {int(t["ox"][i])}), outside its '
-                      f'canvas of {int(t["ch"][i])} x {int(t["cw"][i])}')
-    end = t['offset'].astype(object) + 3 * t['h'].astype(object) * t['w'].astype(object)
-    if len(t) and max(end) > int(packed_bytes):
-        raise YkError(f'view table: row {int(np.argmax(end))} ends at byte {max(end)} of a {int(packed_bytes)}-byte buffer')
-    return t
+    return _check_rows(_VIEW, table, packed_bytes)
 
 
 def view_table_to_device(table, dst_hw, packed_bytes: int, device, stream=None):
     """A host view table (tta.table_rows) checked (check_view_rows), its scale / tx / ty filled for the network size dst_hw and uploaded
     -> cuda uint8 [n, 56], what letterbox_views_u8 takes as its table."""
-    import torch
-    t = check_view_rows(table, packed_bytes)
-    if len(t) == 0:
-        raise YkError('view table: no rows')
-    call('yk_letterbox_views_params', t, len(t), int(dst_hw[0]), int(dst_hw[1]))
-    host = torch.from_numpy(t.view(np.uint8).reshape(len(t), t.dtype.itemsize))
-    with torch.cuda.stream(torch.cuda.current_stream() if stream is None else stream):
-        return host.to(device, non_blocking=False)
+    return _table_to_device(_VIEW, table, dst_hw, packed_bytes, device, stream)
 
 
 def letterbox_views_u8(packed, table, dst_hw, stream=None, out=None):
@@ -706,20 +690,7 @@ def letterbox_views_u8(packed, table, dst_hw, stream=None, out=None):
     (yk_letterbox_views_u8): `packed` cuda uint8 [bytes]; `table` a host table of tta.VIEW_DTYPE (checked here: a row the kernel would answer
     with zeros is refused) or the device table view_table_to_device returned for this dst_hw.  -> cuda uint8 [n, H, W, 3]; frame v is bit for
     bit letterbox_u8 of the canvas of view v (tta.canvas)."""
-    import torch
-    from .tta import VIEW_DTYPE
-    require_gpu()
-    assert packed.is_cuda and packed.dtype == torch.uint8 and packed.is_contiguous() and packed.numel() > 0
-    if not torch.is_tensor(table):
-        table = view_table_to_device(table, dst_hw, packed.numel(), packed.device, stream)
-    assert table.is_cuda and table.dtype == torch.uint8 and table.is_contiguous() and table.dim() == 2 and table.device == packed.device
-    assert table.shape[1] == VIEW_DTYPE.itemsize and table.shape[0] > 0, tuple(table.shape)
-    n = int(table.shape[0])
-    if out is None:
-        out = torch.empty((n, int(dst_hw[0]), int(dst_hw[1]), 3), dtype=torch.uint8, device=packed.device)
-    assert out.is_cuda and out.is_contiguous() and tuple(out.shape) == (n, int(dst_hw[0]), int(dst_hw[1]), 3), tuple(out.shape)
-    call('yk_letterbox_views_u8', packed, packed.numel(), table, n, out, out.shape[1], out.shape[2], _stream(stream))
-    return out
+    return _letterbox_rows_u8(_VIEW, packed, table, dst_hw, stream, out)
 
 
 def fuse_views_lds_candidates(max_out: int) -> int:
@@ -825,7 +796,7 @@ def draw_detections_u8(packed, table, dets, counts, colormap, atlas, stream=None
         max_pixels = int((t['h'].astype(np.int64) * t['w'].astype(np.int64)).max()) if len(t) else 0
     elif max_pixels is None:
         raise YkError('draw_detections_u8: a device table needs max_pixels')
-    table = _ragged_args(packed, table, None, stream)
+    table = _device_table(_RAGGED, packed, table, None, stream)
     n = int(table.shape[0])
     assert dets.is_cuda and dets.dtype == torch.float32 and dets.is_contiguous() and dets.dim() == 3 and dets.shape[0] == n and dets.shape[2] == 6
     assert counts.is_cuda and counts.dtype == torch.int32 and counts.is_contiguous() and tuple(counts.shape) == (n,)
@@ -864,7 +835,7 @@ def jpeg_encode_ragged_u8(packed, table, qtab, stream=None, sizes=None, work=Non
         sizes = jpeg_workspace_bytes(table)
     elif sizes is None:
         raise YkError('jpeg_encode_ragged_u8: a device table needs sizes = jpeg_workspace_bytes(host table)')
-    table = _ragged_args(packed, table, None, stream)
+    table = _device_table(_RAGGED, packed, table, None, stream)
     n = int(table.shape[0])
     dev = packed.device
     if work is None:

@@ -1,5 +1,5 @@
 """The case table, the pictures and the reference for the letterbox arithmetic of csrc/yk_pre.hip (letterbox_px, behind letterbox_u8_kernel,
-letterbox_ragged_u8_kernel, letterbox_augment_u8_kernel and mosaic_ragged_u8_kernel), shared by tests/test_letterbox_cases.py (CPU: the table
+letterbox_rows_u8_kernel<yk_ragged_row_t>, letterbox_augment_u8_kernel and mosaic_ragged_u8_kernel), shared by tests/test_letterbox_cases.py (CPU: the table
 and the reference checked on their own) and tests/test_gpu_letterbox_edges.py (the kernels).  Nothing here touches a GPU.
 
 CASES.  (source h x w -> destination h x w), each with the conditions it is in the table for.  tests/test_letterbox_cases.py asserts every

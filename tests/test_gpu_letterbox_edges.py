@@ -1,4 +1,4 @@
-"""The four letterbox kernels of csrc/yk_pre.hip (letterbox_u8_kernel, letterbox_ragged_u8_kernel, letterbox_augment_u8_kernel,
+"""The four letterbox kernels of csrc/yk_pre.hip (letterbox_u8_kernel, letterbox_rows_u8_kernel<yk_ragged_row_t>, letterbox_augment_u8_kernel,
 mosaic_ragged_u8_kernel: one letterbox_px behind all of them) against the host reference of tests/letterbox_cases.py at the sizes of its
 table: single pixels, lines, slivers, upscales to 28-fold, exact scales 2 and 0.5, destinations smaller than a workgroup or no multiple of
 one, constant-255 pictures whose blend falls an ulp short of 255, taps one past both edges, negative translations.

@@ -75,6 +75,64 @@ def test_four_places_compute_the_same_scale_and_translation(lib):
             assert (int(row['h']), int(row['w'])) == src
 
 
+def test_tile_and_view_params_are_the_ragged_ones(lib):
+    """The one fill behind yk_letterbox_{ragged,tiles,views}_params, on the other two row types (host code: no device needed): a tile that is the
+    whole picture, a view whose canvas is the picture, and a view whose canvas is larger - there the canvas, not (h, w), gives the result."""
+    from k210_yolo_framework_amd import tiles, tta
+    n = len(lc.CASES)
+    for dst in sorted({c.dst for c in lc.CASES}):
+        srcs = [c.src for c in lc.CASES if c.dst == dst]
+        tile, view, wide = np.zeros(len(srcs), tiles.TILE_DTYPE), np.zeros(len(srcs), tta.VIEW_DTYPE), np.zeros(len(srcs), tta.VIEW_DTYPE)
+        for t in (tile, view, wide):
+            t['h'], t['w'] = [s[0] for s in srcs], [s[1] for s in srcs]
+        tile['stride'] = 3 * tile['w'].astype(np.int64)
+        view['ch'], view['cw'] = view['h'], view['w']
+        wide['ch'], wide['cw'], wide['oy'], wide['ox'] = wide['h'] + 3, wide['w'] + 5, 1, 2
+        assert lib.yk_letterbox_tiles_params(tile, len(tile), dst[0], dst[1]) == 0
+        assert lib.yk_letterbox_views_params(view, len(view), dst[0], dst[1]) == 0
+        assert lib.yk_letterbox_views_params(wide, len(wide), dst[0], dst[1]) == 0
+        differ = 0
+        for i, src in enumerate(srcs):
+            scale, tx, ty = preprocess_ref.letterbox_params(src, dst)
+            want = (_bits(scale).item(), tx, ty)
+            for row in (tile[i], view[i]):
+                assert (_bits(row['scale']).item(), int(row['tx']), int(row['ty'])) == want, (src, dst, row)
+            scale, tx, ty = preprocess_ref.letterbox_params((src[0] + 3, src[1] + 5), dst)
+            assert (_bits(wide['scale'][i]).item(), int(wide['tx'][i]), int(wide['ty'][i])) == (_bits(scale).item(), tx, ty), (src, dst, wide[i])
+            differ += (_bits(scale).item(), tx, ty) != want
+            n -= 1
+        assert differ                                   # (the larger canvas is told from the picture for every destination)
+    assert n == 0
+
+
+def test_every_params_helper_refuses_what_it_cannot_fill(lib):
+    """YK_ERR_ARG (-10) for a non-positive size in the fields the helper reads, n <= 0 and a NULL table; a view's (h, w) is not read."""
+    from k210_yolo_framework_amd import tiles, tta
+    for fn, dtype, fields in ((lib.yk_letterbox_ragged_params, draw.RAGGED_DTYPE, ('h', 'w')),
+                              (lib.yk_letterbox_tiles_params, tiles.TILE_DTYPE, ('h', 'w')),
+                              (lib.yk_letterbox_views_params, tta.VIEW_DTYPE, ('ch', 'cw'))):
+        good = np.zeros(2, dtype)
+        for name in fields:
+            good[name] = 5
+        assert fn(good.copy(), 2, 7, 5) == 0
+        for name in fields:
+            for v in (0, -1):
+                bad = good.copy()
+                bad[name][1] = v
+                assert fn(bad, 2, 7, 5) == -10, (fn.__name__, name, v)
+        for n in (0, -1):
+            assert fn(good.copy(), n, 7, 5) == -10
+        assert fn(None, 2, 7, 5) == -10
+        assert fn(good.copy(), 2, 0, 5) == -10 and fn(good.copy(), 2, 7, -1) == -10
+    view = np.zeros(1, tta.VIEW_DTYPE)
+    view['ch'], view['cw'] = 8, 9
+    assert lib.yk_letterbox_views_params(view, 1, 7, 5) == 0                 # h = w = 0: the check of rows is engine.check_view_rows's
+    bad = np.zeros(1, tta.VIEW_DTYPE)
+    assert lib.yk_letterbox_views_params(bad, 1, 7, 5) == -10 and lib.yk_last_error().decode() == 'yk_letterbox_views_params: row 0 has a canvas of 0 x 0'
+    bad = np.zeros(1, tiles.TILE_DTYPE)
+    assert lib.yk_letterbox_tiles_params(bad, 1, 7, 5) == -10 and lib.yk_last_error().decode() == 'yk_letterbox_tiles_params: row 0 is 0 x 0'
+
+
 @pytest.mark.parametrize('case', lc.CASES, ids=lc.IDS)
 def test_taps_rebuild_the_reference(case):
     """taps() is what the condition checks below read: the reference's bytes rebuilt from those values alone, every content."""
