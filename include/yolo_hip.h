@@ -794,13 +794,18 @@ int yk_kpu_profile(yk_kpu_plan_t *p, const uint8_t *d_frames, int batch, int lay
  * yk_scale_act_range_f32  y[m][c] = act(z[m][c] * scale[c] + bias[c]) (act: YK_ACT_*, one rounding per operation: no FMA contraction),
  *                         M x C row-major, any M, C >= 1 (16-byte accesses when C % 4 == 0 and the pointers allow), and folds min / max
  *                         of y into `slot`;
- * yk_range_read           ONE device-to-host copy (synchronises), decoded on the host: h_min / h_max [n_slots] (+inf / -inf for a slot that
+ * yk_scale_act_chrange_f32  the per-channel twin (equalize.py): the same y, bit for bit, and min / max of y[.][c] into slot slot0 + c of a
+ *                         buffer of the same layout (C slots from slot0; reset and read by the two calls around it).  One atomicMin /
+ *                         atomicMax pair per channel and workgroup; any M, C >= 1, M * C may exceed 2^31;
+ * yk_range_read          ONE device-to-host copy (synchronises), decoded on the host: h_min / h_max [n_slots] (+inf / -inf for a slot that
  *                         has seen nothing finite), h_flags [n_slots]. */
 #define YK_RANGE_WORDS 4
 int yk_range_reset(uint32_t *d_range, int n_slots, void *stream);
 int yk_range_f32(const float *x, long long n, uint32_t *d_range, int slot, void *stream);
 int yk_scale_act_range_f32(const float *z, long long M, int C, const float *scale, const float *bias, int act, float alpha, float *y,
                            uint32_t *d_range, int slot, void *stream);
+int yk_scale_act_chrange_f32(const float *z, long long M, int C, const float *scale, const float *bias, int act, float alpha, float *y,
+                             uint32_t *d_range, int slot0, void *stream);
 int yk_range_read(const uint32_t *d_range, int n_slots, float *h_min, float *h_max, int *h_flags);
 
 /* ---- histograms for the clipped calibrations (quantize.clip_range): a second pass over the calibration set, after the ranges.

@@ -11,6 +11,9 @@
 // words of LDS, then ONE atomicMin and ONE atomicMax per workgroup (vector atomics on global memory), and an atomicOr only from a
 // workgroup that met a non-finite value.  The key, the accumulator and the workgroup fold live in yk_range.h (yk_qat.hip shares them).
 //
+// Per channel, for cross-layer equalisation (equalize.py): yk_scale_act_chrange_f32 stores the same y and folds channel c into slot
+// slot0 + c of such a buffer - a column reduction of [M][C] with lanes along the channels (scale_act_chrange_kernel below).
+//
 // Second pass, for the clipped calibrations (quantize.clip_range): a histogram of NB equal bins per tensor over the range the first pass
 // found, uint64 counts [n_slots][NB].  The bin of v is  t = (v - lo) * inv  (one rounding per operation), truncated and clamped to
 // [0, NB - 1]: values outside [lo, hi] land in the end bins, a NaN or an infinity is not counted and sets the slot's flag.  Same launch shape
@@ -85,6 +88,106 @@ __global__ __launch_bounds__(CAL_BLOCK) void scale_act_range_kernel(const float 
         a.add(r);
     }
     fold(a, slot);
+}
+
+// ---- per-channel ranges (equalize.py): the column reduction of [M][C] -------------------------------------------------
+// V = 4 (C % 4 == 0, 16-byte accesses) or 1 elements per thread; cw = C / V "columns".  The columns are walked in chunks of at most CAL_BLOCK;
+// in a chunk of w columns thread t holds column t % w of row t / w of a tile of R = CAL_BLOCK / w whole rows (R * w <= CAL_BLOCK threads work,
+// the others idle), so a tile is one contiguous piece of memory and a thread's channels never change: scale and bias are loaded once, and the
+// accumulators are per channel.  Tiles are strided over the grid.  Then the R accumulators of a column are folded by a tree over rows in LDS
+// and the chunk's w * V channels go to their slots: one atomicMin / atomicMax pair per channel and workgroup, none from a workgroup that saw
+// nothing finite there.  The same expression for y as the kernels above.
+constexpr int CHR_MIN_TRIPS = 4;                          // tiles a workgroup walks at least (chrange_grid)
+constexpr int CHR_MIN_FOLD = 32;                          // values a workgroup folds per channel, at least, before its pair of atomics
+
+template <int V>
+__global__ __launch_bounds__(CAL_BLOCK) void scale_act_chrange_kernel(const float *__restrict__ z, size_t M, int cw, const float *__restrict__ scale,
+                                                                       const float *__restrict__ bias, int act, float alpha, float *__restrict__ y,
+                                                                       uint32_t *slots) {
+    __shared__ uint32_t s_lo[CAL_BLOCK * V], s_hi[CAL_BLOCK * V], s_bad[CAL_BLOCK * V];
+    const int t = threadIdx.x;
+    for (int c0 = 0; c0 < cw; c0 += CAL_BLOCK) {
+        const int w = cw - c0 < CAL_BLOCK ? cw - c0 : CAL_BLOCK;
+        const int R = CAL_BLOCK / w, r = t / w;
+        const size_t col = (size_t)(c0 + t % w);
+        Acc a[V];
+        if (r < R) {
+            float s[V], b[V];
+#pragma unroll
+            for (int j = 0; j < V; ++j) {
+                s[j] = scale[col * V + j];
+                b[j] = bias[col * V + j];
+            }
+            for (size_t row = (size_t)blockIdx.x * R + r; row < M; row += (size_t)gridDim.x * R) {
+                const size_t i = row * (size_t)cw + col;
+                if constexpr (V == 4) {
+                    const float4 v = reinterpret_cast<const float4 *>(z)[i];
+                    float4 o;
+                    o.x = c_act(v.x * s[0] + b[0], act, alpha);
+                    o.y = c_act(v.y * s[1] + b[1], act, alpha);
+                    o.z = c_act(v.z * s[2] + b[2], act, alpha);
+                    o.w = c_act(v.w * s[3] + b[3], act, alpha);
+                    reinterpret_cast<float4 *>(y)[i] = o;
+                    a[0].add(o.x);
+                    a[1].add(o.y);
+                    a[2].add(o.z);
+                    a[3].add(o.w);
+                } else {
+                    const float o = c_act(z[i] * s[0] + b[0], act, alpha);
+                    y[i] = o;
+                    a[0].add(o);
+                }
+            }
+        }
+        __syncthreads();                                                       // the previous chunk's results have been read
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            s_lo[t * V + j] = a[j].lo;
+            s_hi[t * V + j] = a[j].hi;
+            s_bad[t * V + j] = a[j].bad;
+        }
+        for (int n = R; n > 1;) {                                              // rows [half, n) onto rows [0, n - half): nobody reads what is written
+            const int half = (n + 1) / 2;
+            __syncthreads();
+            if (r + half < n) {
+                const int o = (t + half * w) * V;
+#pragma unroll
+                for (int j = 0; j < V; ++j) {
+                    const uint32_t l = s_lo[o + j], h = s_hi[o + j];
+                    a[j].lo = l < a[j].lo ? l : a[j].lo;
+                    a[j].hi = h > a[j].hi ? h : a[j].hi;
+                    a[j].bad |= s_bad[o + j];
+                    s_lo[t * V + j] = a[j].lo;
+                    s_hi[t * V + j] = a[j].hi;
+                    s_bad[t * V + j] = a[j].bad;
+                }
+            }
+            n = half;
+        }
+        __syncthreads();
+        for (int e = t; e < w * V; e += CAL_BLOCK) {                           // row 0 holds channel c0 * V + e at word e
+            uint32_t *slot = slots + (size_t)YK_RANGE_WORDS * ((size_t)c0 * V + e);
+            // a slot's min only falls and its max only rises, so a value read here - however old - that ours cannot improve means the
+            // atomic would change nothing: skipped.  (Up to 2048 workgroups share C slots; once the ranges have settled, over the batches of
+            // a calibration, almost none of them has anything to add.)
+            if (s_lo[e] <= s_hi[e]) {
+                if (s_lo[e] < __hip_atomic_load(slot + 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(slot + 0, s_lo[e]);
+                if (s_hi[e] > __hip_atomic_load(slot + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(slot + 1, s_hi[e]);
+            }
+            if (s_bad[e]) atomicOr(slot + 2, 1u);
+        }
+    }
+}
+
+// workgroups for M rows of cw columns: every one walks at least CHR_MIN_TRIPS tiles and folds at least CHR_MIN_FOLD values per channel
+// (workgroups x C atomics beside M x C loads)
+inline unsigned chrange_grid(size_t M, int cw) {
+    const size_t R = (size_t)(cw < CAL_BLOCK ? CAL_BLOCK / cw : 1);
+    const size_t tiles = (M + R - 1) / R;
+    size_t trips = (CHR_MIN_FOLD + R - 1) / R;
+    if (trips < (size_t)CHR_MIN_TRIPS) trips = CHR_MIN_TRIPS;
+    const size_t g = (tiles + trips - 1) / trips;
+    return (unsigned)(g < 1 ? 1 : (g > CAL_MAX_GRID ? CAL_MAX_GRID : g));
 }
 
 // ---- histograms ---------------------------------------------------------------------------------------------------------------------
@@ -263,6 +366,24 @@ extern "C" int yk_scale_act_range_f32(const float *z, long long M, int C, const 
                            alpha, y, s);
     else
         hipLaunchKernelGGL(scale_act_range_kernel, dim3(grid_for(n)), dim3(CAL_BLOCK), 0, (hipStream_t)stream, z, n, C, scale, bias, act, alpha, y, s);
+    YK_HIP(hipGetLastError());
+    return YK_OK;
+}
+
+extern "C" int yk_scale_act_chrange_f32(const float *z, long long M, int C, const float *scale, const float *bias, int act, float alpha, float *y,
+                                        uint32_t *d_range, int slot0, void *stream) {
+    if (!z || !scale || !bias || !y || !d_range || M <= 0 || C <= 0 || slot0 < 0 || act < YK_ACT_NONE || act > YK_ACT_LEAKY ||
+        M > (long long)(~0ull >> 1) / C) {                                     // M * C is a size_t below: past 2^31 elements is fine, past 2^63 is not
+        yk_set_error("yk_scale_act_chrange_f32: bad argument");
+        return YK_ERR_ARG;
+    }
+    uint32_t *s = d_range + (size_t)YK_RANGE_WORDS * slot0;
+    if (C % 4 == 0 && aligned16(z) && aligned16(y) && aligned16(scale) && aligned16(bias))
+        hipLaunchKernelGGL(scale_act_chrange_kernel<4>, dim3(chrange_grid((size_t)M, C / 4)), dim3(CAL_BLOCK), 0, (hipStream_t)stream, z, (size_t)M, C / 4,
+                           scale, bias, act, alpha, y, s);
+    else
+        hipLaunchKernelGGL(scale_act_chrange_kernel<1>, dim3(chrange_grid((size_t)M, C)), dim3(CAL_BLOCK), 0, (hipStream_t)stream, z, (size_t)M, C, scale,
+                           bias, act, alpha, y, s);
     YK_HIP(hipGetLastError());
     return YK_OK;
 }

@@ -2,6 +2,7 @@
 
     python make_kmodel.py CKPT OUT [network flags of keras_inference.py] (--calib LIST.npy | --synthetic N | --ranges FILE.npz) [--calib_seed S]
                           [--calib_method minmax|percentile|mse] [--calib_percentile P] [--calib_bins NB]
+                          [--equalize True [--equalize_max_gain G]]
 
 CKPT: a Keras `.h5` or `.npz` checkpoint; OUT: `.kmodel` or `.kfpkg`.  The calibration images are a list file as make_voc_list.py writes
 (data/<set>_img_ann.npy) or N generated images as `make train SYNTHETIC=N` trains on; they are decoded as the input pipeline decodes them
@@ -10,7 +11,11 @@ the file size.  `--ranges FILE` (`make kmodel RANGES=`) quantises with the range
 (`yolo_qat_ranges.npz`: tensor name -> [lo, hi]) instead of calibrating; no image is read and no GPU is needed.
 `--calib_method` (`make kmodel CALIBMETHOD=`): `minmax`, the default, spreads the 256 codes over each tensor's exact range; `percentile`
 (`--calib_percentile`, default 99.99) and `mse` clip the range from a histogram of `--calib_bins` bins per tensor, taken on the GPU in a second
-pass over the same images (quantize.clip_range).  The report then lists every clipped tensor."""
+pass over the same images (quantize.clip_range).  The report then lists every clipped tensor.
+`--equalize True` (`make kmodel EQUALIZE=True EQMAXGAIN=64`): cross-layer range equalisation (equalize.py) before the calibration - one more
+pass over the images measures every conv output per channel, the weights are rewritten so that the channels of a tensor fill its range
+(gains up to `--equalize_max_gain`), and the file written is that network: the same function, other weights.  Not with `--ranges`: QAT
+ranges belong to the unequalised weights.  The report names the gains of every layer."""
 from __future__ import annotations
 
 import argparse
@@ -54,7 +59,7 @@ def load_ranges(path, spec):
 
 
 def main(ckpt, out, image_size, output_size, model_def, class_num, depth_multiplier, train_set, calib, synthetic, calib_seed, batch, limit=0,
-         ranges=None, method='minmax', percentile=99.99, bins=2048):
+         ranges=None, method='minmax', percentile=99.99, bins=2048, equalize=False, max_gain=64.0):
     from pathlib import Path
     from . import quantize
     anchor_file = Path(f'data/{train_set}_anchor.npy')
@@ -75,10 +80,11 @@ def main(ckpt, out, image_size, output_size, model_def, class_num, depth_multipl
         print(INFO, f' ranges of {ranges}, no calibration, {time.time() - t0:.2f} s')
     else:
         frames = calibration_frames(h, calib, synthetic, calib_seed, class_num, limit)
-        report = model.save_kmodel(str(out), frames, batch=batch, method=method, percentile=percentile, bins=bins)
+        eq = dict(equalize=True, max_gain=max_gain) if equalize else {}
+        report = model.save_kmodel(str(out), frames, batch=batch, method=method, percentile=percentile, bins=bins, **eq)
         print(quantize.format_report(report))
-        print(INFO, f' {len(frames)} calibration images{"" if method == "minmax" else f", {method} ranges from {bins}-bin histograms"}, '
-                    f'{time.time() - t0:.2f} s')
+        print(INFO, f' {len(frames)} calibration images{"" if method == "minmax" else f", {method} ranges from {bins}-bin histograms"}'
+                    f'{f", channel ranges equalised first (max gain {max_gain:g}, one more pass)" if equalize else ""}, {time.time() - t0:.2f} s')
     print(INFO, f' wrote {out}: kmodel of {report["file_bytes"]} bytes')
     return report
 
@@ -102,6 +108,9 @@ def cli(argv=None):
     p.add_argument('--calib_percentile', type=float, default=99.99, help='share of the values --calib_method percentile keeps at each end, '
                                                                          'in (50, 100]')
     p.add_argument('--calib_bins', type=int, default=2048, help='histogram bins per tensor, 16..4096')
+    p.add_argument('--equalize', type=str, default=None, help='True: equalise the channel ranges before quantising (equalize.py; one more pass '
+                                                              'over the images); the file is the equalised network')
+    p.add_argument('--equalize_max_gain', type=float, default=64.0, help='largest gain --equalize gives a channel, > 1')
     p.add_argument('pre_ckpt', type=str, help='trained weights (.h5 / .npz)')
     p.add_argument('output', type=str, help='.kmodel or .kfpkg to write')
     a = p.parse_args(sys.argv[1:] if argv is None else argv)
@@ -111,6 +120,13 @@ def cli(argv=None):
         p.error('--ranges replaces calibration: it cannot be combined with --calib_method')
     if not a.calib and not a.synthetic and not a.ranges:
         p.error('give --calib LIST.npy, --synthetic N or --ranges FILE.npz')
+    if a.equalize not in (None, 'True', 'False'):
+        p.error(f'--equalize {a.equalize}: True or False')
+    equalize = a.equalize == 'True'
+    if a.ranges and equalize:
+        p.error('--equalize cannot be combined with --ranges: QAT ranges belong to the unequalised weights')
+    if equalize and not a.equalize_max_gain > 1.0:
+        p.error(f'--equalize_max_gain {a.equalize_max_gain} must be above 1')
     method = a.calib_method or 'minmax'
     if method not in ('minmax', 'percentile', 'mse'):
         p.error(f'--calib_method {method}: one of minmax, percentile, mse')
@@ -119,7 +135,8 @@ def cli(argv=None):
     if not 16 <= a.calib_bins <= 4096:
         p.error(f'--calib_bins {a.calib_bins} outside 16..4096')
     return main(a.pre_ckpt, a.output, a.image_size, a.output_size, a.model_def, a.class_num, a.depth_multiplier, a.train_set, a.calib,
-                a.synthetic, a.calib_seed, a.calib_batch, a.calib_limit, a.ranges, method, a.calib_percentile, a.calib_bins)
+                a.synthetic, a.calib_seed, a.calib_batch, a.calib_limit, a.ranges, method, a.calib_percentile, a.calib_bins, equalize,
+                a.equalize_max_gain)
 
 
 if __name__ == '__main__':

@@ -167,8 +167,8 @@ def _act_table(act: int, alpha: float, zp_y: int, p: int):
 def quantize(spec: ns.NetSpec, weights: Dict[str, np.ndarray], ranges: Dict[str, Tuple[float, float]]):
     """-> (kmodel.Kmodel, report).  `ranges`: {tensor name (tensor_names): (min, max)} of the calibration set, at least for the input-side
     of every conv ('input' is fixed to the raw pixel and need not be given; upsample / concat outputs take their producers' ranges).
-    report['layers'][name] = scales, zero points, FINE_BITS used, the BatchNorm shifts chosen and the share of weights equal to the zero
-    point.  CPU only, deterministic."""
+    report['layers'][name] = scales, zero points, FINE_BITS used, the BatchNorm shifts chosen, the share of weights equal to the zero
+    point and the smallest non-zero |bn_mul| (what equalize.py's step A lowers for an amplified consumer).  CPU only, deterministic."""
     plan = plan_convs(spec)
     names = tensor_names(spec)
     lay = {l.name: l for l in spec.layers}
@@ -246,7 +246,7 @@ def quantize(spec: ns.NetSpec, weights: Dict[str, np.ndarray], ranges: Dict[str,
             kpu_of[tout], q[tout], rng[tout] = dst, (s_y, zp_y), (-zp_y * s_y, (255 - zp_y) * s_y)
             report['layers'][l.name] = dict(index=idx, s_x=s_x, zp_x=zp_x, s_w=s_w, zp_w=zp_w, s_y=s_y, zp_y=zp_y, fine_bits=p, pool=g['pool'],
                                             bn_shift=(int(shift.min()), int(shift.max())), zero_share=float((wq == zp_w).mean()),
-                                            range=(lo, hi))
+                                            range=(lo, hi), bn_mul_min=int(np.abs(bn_mul[bn_mul != 0]).min()) if bn_mul.any() else 0)
             if tout in spec.outputs:
                 n = co * g['out_h'] * g['out_w']
                 d = mem_alloc(4 * n)
@@ -313,6 +313,9 @@ def format_report(report: dict) -> str:
     for r in report.get('clipped', []):
         rows.append(f"clipped {r['tensor']} ({r['method']}): ({r['lo']:.6g}, {r['hi']:.6g}) -> ({r['new_lo']:.6g}, {r['new_hi']:.6g}), "
                     f"{100.0 * r['outside']:.4f}% of the calibration values outside")
+    if report.get('equalize'):
+        from . import equalize
+        rows.append(equalize.format_report(report['equalize']))
     rows.append(f"main memory {report['main_mem_usage']} bytes, KPU RAM peak {report['kpu_ram_peak']} bytes")
     return '\n'.join(rows)
 
@@ -437,7 +440,12 @@ class Calibrator:
     The clipped calibrations (`ranges('percentile' | 'mse')`, clip_range) need a second pass over the same frames, `feed_hist`: the same walk
     with yk_scale_act_hist_f32 / yk_hist_f32 in place of the range launches, which count every tensor into `bins` equal bins of the range
     the first pass found (widened to contain 0, as qparams widens it).  The first `feed_hist` freezes those ranges; the counts are uint64,
-    integer adds, order-free like the ranges."""
+    integer adds, order-free like the ranges.
+
+    Cross-layer equalisation (equalize.py) needs the range of every CHANNEL of every conv output: `feed_channels` is the same walk with
+    yk_scale_act_chrange_f32 as the epilogue, which folds channel c of a conv output into slot (the layer's first slot) + c of a second
+    range buffer of sum(C over the conv outputs) slots (+ one scratch slot for the input tensor); `channel_ranges()` reads it.  It shares
+    nothing with the per-tensor buffer, so `feed` / `ranges()` do not see it."""
 
     def __init__(self, spec: ns.NetSpec, weights: Dict[str, np.ndarray], max_batch: int = 32, device: int = 0, bins: int = DEFAULT_BINS):
         import torch
@@ -470,6 +478,13 @@ class Calibrator:
         if not MIN_BINS <= self.bins <= MAX_BINS:
             raise engine.YkError(f'Calibrator: bins = {bins} outside {MIN_BINS}..{MAX_BINS}')
         self.d_hist = self.d_hflags = None                                                               # allocated by the first feed_hist
+        self.ch_slot0: Dict[str, int] = {}                                                               # conv layer -> its first channel slot
+        self.n_ch = 0
+        for op in spec.ops:
+            if op['type'] in (ns.OP_CONV, ns.OP_DWCONV):
+                self.ch_slot0[op['layer']] = self.n_ch
+                self.n_ch += int(op['cout'])
+        self.d_chrange = None                                                                            # allocated by the first feed_channels
         self._last_use = {}
         for k, op in enumerate(spec.ops):
             for key in ('in0', 'in1'):
@@ -484,7 +499,9 @@ class Calibrator:
 
     def reset(self) -> None:
         self._ck('yk_range_reset', self.d_range, self.n_slots)
-        self.images = self.hist_images = 0
+        self.images = self.hist_images = self.ch_images = 0
+        if self.d_chrange is not None:
+            self._ck('yk_range_reset', self.d_chrange, self.n_ch + 1)
         self.h_lo = self.h_hi = self.h_inv = None                                                        # frozen by the first feed_hist
         self.last_clip: List[dict] = []
 
@@ -500,6 +517,37 @@ class Calibrator:
 
     def _hist(self, x, slot):
         self._ck('yk_hist_f32', x, x.numel(), float(self.h_lo[slot]), float(self.h_inv[slot]), self.bins, self.d_hist, self.d_hflags, slot)
+
+    def _epilogue_channels(self, z, M, Cn, scale, bias, act, alpha, y, slot):
+        if slot == 0:                                                                                # the input: no conv output, into the scratch slot
+            self._ck('yk_scale_act_range_f32', z, M, Cn, scale, bias, act, alpha, y, self.d_chrange, self.n_ch)
+        else:
+            self._ck('yk_scale_act_chrange_f32', z, M, Cn, scale, bias, act, alpha, y, self.d_chrange, self.ch_slot0[self.names[slot]])
+
+    def feed_channels(self, frames_u8, keep=None) -> "Calibrator":
+        """frames_u8 as `feed` takes them: the range of every output channel of every conv layer, accumulated over calls like `feed` (and
+        as independent of the batching).  Leaves the per-tensor ranges and histograms alone."""
+        if self.d_chrange is None:
+            self.d_chrange = self.torch.zeros((self.n_ch + 1) * 4, dtype=self.torch.int32, device=self.dev)
+            self._ck('yk_range_reset', self.d_chrange, self.n_ch + 1)
+        self._walk(frames_u8, keep, self._epilogue_channels, lambda x, slot: None, 'feed_channels')
+        self.ch_images += int(frames_u8.shape[0])
+        return self
+
+    def channel_ranges(self) -> Dict[str, Tuple[np.ndarray, np.ndarray]]:
+        """{conv layer name: (lo[C], hi[C])} float32 over everything fed to feed_channels.  YkError naming the layer when one of its channels
+        held a NaN or an infinity."""
+        if not self.ch_images:
+            raise self.engine.YkError('Calibrator.channel_ranges: nothing has been fed to feed_channels')
+        lo, hi, fl = (np.empty(self.n_ch, t) for t in (np.float32, np.float32, np.int32))
+        self.torch.cuda.current_stream().synchronize()
+        self.engine.call('yk_range_read', self.d_chrange, self.n_ch, lo, hi, fl)
+        ends = {name: (s0, s0 + int(self.lay[name].kernel_shape[3 if self.lay[name].kind == 'conv' else 2])) for name, s0 in self.ch_slot0.items()}
+        bad = [name for name, (s0, s1) in ends.items() if fl[s0:s1].any()]
+        if bad:
+            raise self.engine.YkError(f'Calibrator: non-finite values (NaN or infinity) in tensor(s) {", ".join(bad)}: the weights or the frames '
+                                      f'are broken; no range is defined')
+        return {name: (lo[s0:s1].copy(), hi[s0:s1].copy()) for name, (s0, s1) in ends.items()}
 
     def feed(self, frames_u8, keep=None) -> "Calibrator":
         """frames_u8: device uint8 [B, H, W, 3], B <= max_batch, H x W = the spec's input size.  `keep`: a dict that receives every tensor
@@ -705,3 +753,14 @@ def calibrate(spec: ns.NetSpec, weights, frames_u8, batch: int = 32, method: str
     if clipped is not None:
         clipped.extend(cal.last_clip)
     return out
+
+
+def calibrate_channels(spec: ns.NetSpec, weights, frames_u8, batch: int = 32) -> Dict[str, Tuple[np.ndarray, np.ndarray]]:
+    """{conv layer name: (lo[C], hi[C])} of `frames_u8` (as `calibrate` takes them) in batches of `batch`: what equalize.equalize needs."""
+    import torch
+    frames = frames_u8 if torch.is_tensor(frames_u8) else torch.from_numpy(np.ascontiguousarray(frames_u8))
+    batch = max(1, min(int(batch), len(frames)))
+    cal = Calibrator(spec, weights, max_batch=batch)
+    for i in range(0, len(frames), batch):
+        cal.feed_channels(frames[i:i + batch].cuda())
+    return cal.channel_ranges()

@@ -115,27 +115,43 @@ class YoloModel:
         else:
             np.savez(path, **self._s['weights'])
 
-    def save_kmodel(self, path: str, calibration_frames, batch: int = 32, method: str = 'minmax', percentile: float = 99.99, bins: int = 2048):
+    def save_kmodel(self, path: str, calibration_frames, batch: int = 32, method: str = 'minmax', percentile: float = 99.99, bins: int = 2048,
+                    equalize: bool = False, max_gain: float = 64.0):
         """Quantise these weights to a K210 kmodel (quantize.py) and write it: `.kmodel`, or `.kfpkg` (model + flash list, no
         firmware).  calibration_frames: uint8 [N, H, W, 3] at the network's input size (host numpy or a device tensor); their tensor ranges
         are measured on the GPU in batches of `batch`, from the raw pixels / 255 as the KPU sees them.  The new Kmodel is kept beside the
         float weights, so precision='kpu' runs it on this object without reloading.  Returns the quantiser's report (also
         `last_quantize_report`).  A network the KPU path cannot express raises YkError with the quantiser's reason.
         method 'percentile' / 'mse' (quantize.clip_range) clips every range from a histogram of `bins` bins, taken on the GPU in a second
-        pass over the frames; report['clipped'] lists the tensors it moved.  The default, 'minmax', is the exact range and one pass."""
+        pass over the frames; report['clipped'] lists the tensors it moved.  The default, 'minmax', is the exact range and one pass.
+        equalize=True first equalises the channel ranges (equalize.py): one more pass over the frames measures every conv output per channel
+        (Calibrator.feed_channels), equalize.equalize rewrites the weights (gains up to `max_gain`), and calibration and quantisation then run
+        on THOSE weights; report['equalize'] holds the gains.  The written file is the equalised network - the same function, other weights;
+        this object's float weights are not touched."""
         import torch
         from . import engine, kmodel, quantize
         try:
             quantize.plan_convs(self.spec)                       # refuse before any GPU work
+            if equalize and not float(max_gain) > 1.0:
+                raise kmodel.KmodelError(f'equalize: max_gain {max_gain} must be above 1')
         except kmodel.KmodelError as e:
             raise engine.YkError(f'save_kmodel: {e}') from e
         frames = calibration_frames if torch.is_tensor(calibration_frames) else torch.from_numpy(np.ascontiguousarray(calibration_frames))
         if frames.dtype != torch.uint8 or frames.dim() != 4 or len(frames) == 0:
             raise engine.YkError('save_kmodel: calibration_frames must be uint8 [N, H, W, 3], N >= 1')
         clipped = []
-        ranges = quantize.calibrate(self.spec, self._s['weights'], frames, batch, method, percentile, bins, clipped)
+        weights, eq_report = self._s['weights'], None
+        if equalize:
+            from . import equalize as eq
+            try:
+                weights, eq_report = eq.equalize(self.spec, weights, quantize.calibrate_channels(self.spec, weights, frames, batch), max_gain)
+            except kmodel.KmodelError as e:
+                raise engine.YkError(f'save_kmodel: {e}') from e
+        ranges = quantize.calibrate(self.spec, weights, frames, batch, method, percentile, bins, clipped)
         try:
-            km, report = quantize.quantize(self.spec, self._s['weights'], ranges)
+            km, report = quantize.quantize(self.spec, weights, ranges)
+            if eq_report is not None:
+                report['equalize'] = eq_report
             if method != 'minmax':
                 report['clipped'] = clipped
             report['file_bytes'] = kmodel.write(path, km)
