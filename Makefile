@@ -31,6 +31,9 @@
 #                    [EQUALIZE=True EQMAXGAIN=64]: cross-layer range equalisation first (k210_yolo_framework_amd/equalize.py): one more pass
 #                    measures every conv output per channel on the GPU, the weights are rewritten so that the channels of a tensor fill its
 #                    range, and the file is that network - the same function, other weights (not with RANGES=; default off)
+#                    [BIASCORRECT=True]: per-channel bias correction after the calibration (k210_yolo_framework_amd/biascorrect.py): on the same
+#                    images, one KPU-exact statistics pass per conv layer finds the integer to add to every channel's bn_add so that its mean
+#                    pre-activation equals the float network's (not with RANGES=: it needs frames; default off)
 #   make eval        CKPT=yolo_model.h5|yolo.kmodel [PRECISION=f16x2|f16|kpu] [ANN=data/voc_img_ann.npy | SYNTHETIC=256] [EVALOBJ=0.05] [VOC07=True]:
 #                    VOC mAP of the checkpoint, network and metric on the GPU; prints the per-class AP table, writes eval.json beside CKPT
 #                    [METRIC=coco]: also the COCO-style AP (IoU .50:.95, AP50, AP75, small / medium / large, AR) and a `coco` object in eval.json
@@ -142,6 +145,7 @@ CALIBPCT      ?= 99.99
 CALIBBINS     ?= 2048
 EQUALIZE      ?= False
 EQMAXGAIN     ?= 64
+BIASCORRECT   ?= False
 GPUS          ?= 1
 # anchors only (reference Makefile:27-29)
 ANCNUM        ?= 3
@@ -200,7 +204,7 @@ train:
 kmodel:
 	$(PY) make_kmodel.py $(CKPT) $(OUT) --train_set $(DATASET) --class_num $(CLSNUM) --model_def $(MODEL) --depth_multiplier $(DEPTHMUL) \
 		--image_size $(IMGSIZE) --output_size $(OUTSIZE) $(if $(RANGES),--ranges $(RANGES),$(if $(filter-out 0,$(SYNTHETIC)),--synthetic $(SYNTHETIC),--calib $(CALIB))) \
-		$(if $(CALIBMETHOD),--calib_method $(CALIBMETHOD) --calib_percentile $(CALIBPCT) --calib_bins $(CALIBBINS))$(if $(filter True,$(EQUALIZE)), --equalize True --equalize_max_gain $(EQMAXGAIN))
+		$(if $(CALIBMETHOD),--calib_method $(CALIBMETHOD) --calib_percentile $(CALIBPCT) --calib_bins $(CALIBBINS))$(if $(filter True,$(EQUALIZE)), --equalize True --equalize_max_gain $(EQMAXGAIN))$(if $(filter True,$(BIASCORRECT)), --bias_correct True)
 
 # VOC mAP of CKPT (.h5 / .npz, or .kmodel / .kfpkg with PRECISION=kpu) on the validation head of ANN, or on SYNTHETIC=N generated images
 eval:

@@ -775,6 +775,16 @@ int yk_kpu_plan_create(yk_kpu_plan_t **out, const int64_t *ops, int n_ops, const
 void yk_kpu_plan_destroy(yk_kpu_plan_t *p);
 /* asynchronous on `stream`; one launch per op, no other stream touched (capturable with yk_graph_*) */
 int yk_kpu_run_u8(yk_kpu_plan_t *p, const uint8_t *d_frames, int batch, int layout, void *stream);
+/* The statistics run (biascorrect.py): the launches of yk_kpu_run_u8 with the conv kernels' statistics instantiations, which
+ * leave every tensor and output bit-identical and add z - the int64 pre-activation (acc * bn_mul >> bn_shift) + bn_add, before the segment
+ * table - of every counted output element into d_zsum[first slot of the conv + oc].  The conv ops (dense and depthwise, in issue order) own
+ * consecutive runs of OC slots, yk_kpu_stat_slots in all.  h_step [n_step = number of conv ops], each 1 or 2: with 2 only output pixels with
+ * even oy and even ox are counted (a stride-2 depthwise conv that runs at stride 1 and is pooled by its reader).  Integer adds that wrap (sums
+ * reduced in registers / LDS, then one 64-bit atomic per channel and wave / workgroup): independent of scheduling and launch geometry.  The sums
+ * accumulate over runs; the caller zeroes d_zsum (8-byte aligned).  h_step is read before the call returns. */
+int yk_kpu_stat_slots(const yk_kpu_plan_t *p);
+int yk_kpu_run_stats_u8(yk_kpu_plan_t *p, const uint8_t *d_frames, int batch, int layout, const int *h_step, int n_step, uint64_t *d_zsum,
+                        void *stream);
 /* borrowed device pointer to output idx, fp32 [max_batch][h][w][c] (the layout of yk_get_output: yk_decode_py consumes it) */
 int yk_kpu_get_output(yk_kpu_plan_t *p, int idx, float **d_ptr, size_t *bytes, int *h, int *w, int *c);
 int yk_kpu_output_count(const yk_kpu_plan_t *p);
@@ -807,6 +817,24 @@ int yk_scale_act_range_f32(const float *z, long long M, int C, const float *scal
 int yk_scale_act_chrange_f32(const float *z, long long M, int C, const float *scale, const float *bias, int act, float alpha, float *y,
                              uint32_t *d_range, int slot0, void *stream);
 int yk_range_read(const uint32_t *d_range, int n_slots, float *h_min, float *h_max, int *h_flags);
+
+/* ---- per-channel sums of the pre-activation, for bias correction (biascorrect.py).
+ * yk_scale_act_chsum_f32  the third twin of yk_scale_act_range_f32: the same y, bit for bit, and the sum over m of the fp32 PRE-activation
+ *                         t = z[m][c] * scale[c] + bias[c] (before `act`: the quantity a kmodel's bn_add shifts) added to d_sum[slot0 + c], in
+ *                         float64.  No floating-point atomics: workgroups own about YK_CHSUM_TILE elements (whole rows) and leave one partial
+ *                         per channel in d_work (yk_chsum_workspace_bytes; needs no device; contents undefined before and after), a finishing
+ *                         launch folds them; who adds what, and in which order, follows from (M, C) alone, so the same calls give the same bits
+ *                         on any stream and with any alignment of the pointers.  The finishing launch walks the partials of a channel with
+ *                         max(1, 256 / min(C, 256)) accumulators: more workgroups than that take more than one pass.  Sums accumulate over calls
+ *                         (calls on one d_sum are ordered by their stream).  A NaN or an infinity is not added; it sets d_flags[slot0 + c].
+ *                         Any M, C >= 1, M * C may exceed 2^31; 16-byte accesses when C % 4 == 0 and the pointers allow.
+ * yk_chsum_reset          sums and flags of slots [0, n_slots) to zero;  yk_chsum_read  two device-to-host copies (synchronises). */
+#define YK_CHSUM_TILE 16384
+int yk_chsum_workspace_bytes(long long M, int C, size_t *bytes);
+int yk_chsum_reset(double *d_sum, uint32_t *d_flags, int n_slots, void *stream);
+int yk_scale_act_chsum_f32(const float *z, long long M, int C, const float *scale, const float *bias, int act, float alpha, float *y,
+                           double *d_sum, uint32_t *d_flags, int slot0, double *d_work, void *stream);
+int yk_chsum_read(const double *d_sum, const uint32_t *d_flags, int n_slots, double *h_sum, int *h_flags);
 
 /* ---- histograms for the clipped calibrations (quantize.clip_range): a second pass over the calibration set, after the ranges.
  * d_hist holds uint64 counts [n_slots][nbins], 16 <= nbins <= 4096; d_flags one uint32 per slot.  A slot's bins are equal parts of [lo, hi],

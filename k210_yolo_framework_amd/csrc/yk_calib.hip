@@ -14,6 +14,9 @@
 // Per channel, for cross-layer equalisation (equalize.py): yk_scale_act_chrange_f32 stores the same y and folds channel c into slot
 // slot0 + c of such a buffer - a column reduction of [M][C] with lanes along the channels (scale_act_chrange_kernel below).
 //
+// Per channel, for bias correction (biascorrect.py): yk_scale_act_chsum_f32 stores the same y and adds the float64 sum of the PRE-activation of
+// channel c to d_sum[slot0 + c] - per-workgroup partials and a fold in a fixed order, no floating-point atomics (scale_act_chsum_kernel below).
+//
 // Second pass, for the clipped calibrations (quantize.clip_range): a histogram of NB equal bins per tensor over the range the first pass
 // found, uint64 counts [n_slots][NB].  The bin of v is  t = (v - lo) * inv  (one rounding per operation), truncated and clamped to
 // [0, NB - 1]: values outside [lo, hi] land in the end bins, a NaN or an infinity is not counted and sets the slot's flag.  Same launch shape
@@ -188,6 +191,122 @@ inline unsigned chrange_grid(size_t M, int cw) {
     if (trips < (size_t)CHR_MIN_TRIPS) trips = CHR_MIN_TRIPS;
     const size_t g = (tiles + trips - 1) / trips;
     return (unsigned)(g < 1 ? 1 : (g > CAL_MAX_GRID ? CAL_MAX_GRID : g));
+}
+
+// ---- per-channel sums of the pre-activation (biascorrect.py) ------------------------------------------------------------
+// t = z * scale + bias (fp32, BEFORE the activation) summed per channel in float64, without floating-point atomics and in an order that
+// (M, C) alone fix - not the pointers' alignment, the stream or the scheduling:
+//   * the channels are walked in chunks of w = min(C - c0, CAL_BLOCK); a chunk has L = 4 * (CAL_BLOCK / w) ROW LANES;
+//   * workgroup g owns rows [g * T, (g + 1) * T), T = chsum_rows(C); lane l of a chunk adds rows g * T + l, + L, + 2 L, ... in that order;
+//   * the L lanes of a channel are folded by a tree in LDS (lanes [half, n) onto [0, n - half)), and the result is partial[g][c];
+//   * the finishing launch (one workgroup per chunk) walks the G partials of a channel with R = CAL_BLOCK / w lanes the same way - lane r adds
+//     g = r, r + R, ... : ceil(G / R) passes - folds them by the same tree and adds the result to d_sum[slot0 + c] (a plain load and store: calls
+//     on one buffer are ordered by their stream).
+// The two thread layouts realise the same lanes: with 16-byte accesses a thread is one lane of four channels (w / 4 columns x L lanes); without,
+// a thread is one channel and holds lanes r, r + R, r + 2 R, r + 3 R in four accumulators, taking rows r + k R into accumulator k % 4.
+// A non-finite t is not added and sets the channel's flag (an integer atomicOr from the threads that met one).
+constexpr int CHS_TILE = YK_CHSUM_TILE;                   // elements a workgroup covers, about
+
+inline size_t chsum_rows(int C) { return (size_t)((CHS_TILE + C - 1) / C); }                  // T: rows of one workgroup (>= 1)
+inline size_t chsum_groups(size_t M, int C) { return (M + chsum_rows(C) - 1) / chsum_rows(C); }   // G
+
+__device__ __forceinline__ bool chs_finite(float t) { return (__float_as_uint(t) & 0x7F800000u) != 0x7F800000u; }
+
+// the tree over `n` lanes of `w` channels held as s[lane * w + channel]; every thread of the workgroup calls it
+__device__ __forceinline__ void chs_tree(double *s, int n, int w) {
+    while (n > 1) {
+        const int half = (n + 1) / 2;
+        __syncthreads();
+        for (int e = threadIdx.x; e < (n - half) * w; e += CAL_BLOCK) s[e] += s[e + half * w];
+        n = half;
+    }
+    __syncthreads();
+}
+
+template <int V>
+__global__ __launch_bounds__(CAL_BLOCK) void scale_act_chsum_kernel(const float *__restrict__ z, size_t M, int C, size_t T, const float *__restrict__ scale,
+                                                                     const float *__restrict__ bias, int act, float alpha, float *__restrict__ y,
+                                                                     double *__restrict__ partial, uint32_t *flags) {
+    __shared__ double s_sum[4 * CAL_BLOCK];
+    const int t = threadIdx.x;
+    const size_t row0 = (size_t)blockIdx.x * T;
+    const size_t row1 = row0 + T < M ? row0 + T : M;
+    for (int c0 = 0; c0 < C; c0 += CAL_BLOCK) {
+        const int w = C - c0 < CAL_BLOCK ? C - c0 : CAL_BLOCK;
+        const int R = CAL_BLOCK / w, L = 4 * R;
+        double a[4] = {0.0, 0.0, 0.0, 0.0};
+        if constexpr (V == 4) {
+            const int wq = w / 4, q = t % wq, l = t / wq;                          // wq * L = R * w <= CAL_BLOCK threads work
+            if (l < L) {
+                const int c = c0 + 4 * q;
+                const float4 s = *reinterpret_cast<const float4 *>(scale + c);
+                const float4 b = *reinterpret_cast<const float4 *>(bias + c);
+                uint32_t bad = 0u;
+                for (size_t row = row0 + l; row < row1; row += L) {
+                    const size_t i = (row * (size_t)C + c) / 4;
+                    const float4 v = reinterpret_cast<const float4 *>(z)[i];
+                    const float p0 = v.x * s.x + b.x, p1 = v.y * s.y + b.y, p2 = v.z * s.z + b.z, p3 = v.w * s.w + b.w;
+                    float4 o;
+                    o.x = c_act(p0, act, alpha);
+                    o.y = c_act(p1, act, alpha);
+                    o.z = c_act(p2, act, alpha);
+                    o.w = c_act(p3, act, alpha);
+                    reinterpret_cast<float4 *>(y)[i] = o;
+                    if (chs_finite(p0)) a[0] += (double)p0; else bad |= 1u;
+                    if (chs_finite(p1)) a[1] += (double)p1; else bad |= 2u;
+                    if (chs_finite(p2)) a[2] += (double)p2; else bad |= 4u;
+                    if (chs_finite(p3)) a[3] += (double)p3; else bad |= 8u;
+                }
+                for (int j = 0; j < 4; ++j)
+                    if (bad >> j & 1u) atomicOr(flags + c + j, 1u);
+            }
+            __syncthreads();                                                       // the previous chunk's results have been read
+            if (l < L)
+                for (int j = 0; j < 4; ++j) s_sum[l * w + 4 * q + j] = a[j];
+        } else {
+            const int col = t % w, r = t / w;
+            if (r < R) {
+                const int c = c0 + col;
+                const float s = scale[c], b = bias[c];
+                bool bad = false;
+                int k = 0;
+                for (size_t row = row0 + r; row < row1; row += R, k = (k + 1) & 3) {
+                    const size_t i = row * (size_t)C + c;
+                    const float p = z[i] * s + b;
+                    y[i] = c_act(p, act, alpha);
+                    if (chs_finite(p)) {
+                        a[0] += k == 0 ? (double)p : 0.0;                          // (adding +0.0 changes no finite sum)
+                        a[1] += k == 1 ? (double)p : 0.0;
+                        a[2] += k == 2 ? (double)p : 0.0;
+                        a[3] += k == 3 ? (double)p : 0.0;
+                    } else {
+                        bad = true;
+                    }
+                }
+                if (bad) atomicOr(flags + c, 1u);
+            }
+            __syncthreads();
+            if (r < R)
+                for (int j = 0; j < 4; ++j) s_sum[(r + j * R) * w + col] = a[j];
+        }
+        chs_tree(s_sum, L, w);
+        for (int e = t; e < w; e += CAL_BLOCK) partial[(size_t)blockIdx.x * C + c0 + e] = s_sum[e];
+    }
+}
+
+// workgroup blockIdx.x = chunk c0 = blockIdx.x * CAL_BLOCK of the channels
+__global__ __launch_bounds__(CAL_BLOCK) void chsum_finish_kernel(const double *__restrict__ partial, size_t G, int C, double *d_sum) {
+    __shared__ double s_sum[CAL_BLOCK];
+    const int t = threadIdx.x, c0 = blockIdx.x * CAL_BLOCK;
+    const int w = C - c0 < CAL_BLOCK ? C - c0 : CAL_BLOCK;
+    const int R = CAL_BLOCK / w, col = t % w, r = t / w;
+    if (r < R) {
+        double a = 0.0;
+        for (size_t g = r; g < G; g += R) a += partial[g * (size_t)C + c0 + col];
+        s_sum[r * w + col] = a;
+    }
+    chs_tree(s_sum, R, w);
+    for (int e = t; e < w; e += CAL_BLOCK) d_sum[c0 + e] += s_sum[e];
 }
 
 // ---- histograms ---------------------------------------------------------------------------------------------------------------------
@@ -385,6 +504,65 @@ extern "C" int yk_scale_act_chrange_f32(const float *z, long long M, int C, cons
         hipLaunchKernelGGL(scale_act_chrange_kernel<1>, dim3(chrange_grid((size_t)M, C)), dim3(CAL_BLOCK), 0, (hipStream_t)stream, z, (size_t)M, C, scale,
                            bias, act, alpha, y, s);
     YK_HIP(hipGetLastError());
+    return YK_OK;
+}
+
+extern "C" int yk_chsum_workspace_bytes(long long M, int C, size_t *bytes) {
+    if (M <= 0 || C <= 0 || !bytes || M > (long long)(~0ull >> 1) / C) {
+        yk_set_error("yk_chsum_workspace_bytes: bad argument");
+        return YK_ERR_ARG;
+    }
+    *bytes = sizeof(double) * chsum_groups((size_t)M, C) * (size_t)C;
+    return YK_OK;
+}
+
+extern "C" int yk_chsum_reset(double *d_sum, uint32_t *d_flags, int n_slots, void *stream) {
+    if (!d_sum || !d_flags || n_slots <= 0) {
+        yk_set_error("yk_chsum_reset: bad argument");
+        return YK_ERR_ARG;
+    }
+    YK_HIP(hipMemsetAsync(d_sum, 0, (size_t)n_slots * sizeof(double), (hipStream_t)stream));
+    YK_HIP(hipMemsetAsync(d_flags, 0, (size_t)n_slots * sizeof(uint32_t), (hipStream_t)stream));
+    return YK_OK;
+}
+
+extern "C" int yk_scale_act_chsum_f32(const float *z, long long M, int C, const float *scale, const float *bias, int act, float alpha, float *y,
+                                      double *d_sum, uint32_t *d_flags, int slot0, double *d_work, void *stream) {
+    if (!z || !scale || !bias || !y || !d_sum || !d_flags || !d_work || M <= 0 || C <= 0 || slot0 < 0 || act < YK_ACT_NONE || act > YK_ACT_LEAKY ||
+        M > (long long)(~0ull >> 1) / C || ((uintptr_t)d_sum & 7u) != 0 || ((uintptr_t)d_work & 7u) != 0) {
+        yk_set_error("yk_scale_act_chsum_f32: bad argument (d_sum and d_work 8-byte aligned)");
+        return YK_ERR_ARG;
+    }
+    const size_t T = chsum_rows(C), G = chsum_groups((size_t)M, C);
+    if (G > 0x7FFFFFFFull) {
+        yk_set_error("yk_scale_act_chsum_f32: M %lld is more than one grid dimension of workgroups", M);
+        return YK_ERR_ARG;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if (C % 4 == 0 && aligned16(z) && aligned16(y) && aligned16(scale) && aligned16(bias))
+        hipLaunchKernelGGL(scale_act_chsum_kernel<4>, dim3((unsigned)G), dim3(CAL_BLOCK), 0, st, z, (size_t)M, C, T, scale, bias, act, alpha, y, d_work,
+                           d_flags + slot0);
+    else
+        hipLaunchKernelGGL(scale_act_chsum_kernel<1>, dim3((unsigned)G), dim3(CAL_BLOCK), 0, st, z, (size_t)M, C, T, scale, bias, act, alpha, y, d_work,
+                           d_flags + slot0);
+    YK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(chsum_finish_kernel, dim3((unsigned)((C + CAL_BLOCK - 1) / CAL_BLOCK)), dim3(CAL_BLOCK), 0, st, (const double *)d_work, G, C,
+                       d_sum + slot0);
+    YK_HIP(hipGetLastError());
+    return YK_OK;
+}
+
+extern "C" int yk_chsum_read(const double *d_sum, const uint32_t *d_flags, int n_slots, double *h_sum, int *h_flags) {
+    if (!d_sum || !d_flags || n_slots <= 0 || !h_sum || !h_flags) {
+        yk_set_error("yk_chsum_read: bad argument");
+        return YK_ERR_ARG;
+    }
+    hipError_t e = hipMemcpy(h_sum, d_sum, (size_t)n_slots * sizeof(double), hipMemcpyDeviceToHost);                         // synchronises
+    if (e == hipSuccess) e = hipMemcpy(h_flags, d_flags, (size_t)n_slots * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) {
+        yk_set_error("yk_chsum_read: hipMemcpy -> %s", hipGetErrorString(e));
+        return YK_ERR_HIP;
+    }
     return YK_OK;
 }
 

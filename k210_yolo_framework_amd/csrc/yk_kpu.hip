@@ -72,11 +72,14 @@ __device__ __forceinline__ int64_t carry_shift(int64_t v, int64_t s) {
     return (v & 1) ? (v < 0 ? half : half + 1) : half;
 }
 
-// THE epilogue of every KPU conv output element (dense and depthwise)
-__device__ __forceinline__ uint8_t kpu_epilogue(int64_t sum_xw, int64_t sum_x, long long arg_x, int shr_x, const KpuChan &c,
-                                                const KpuSeg *__restrict__ seg) {
+// THE epilogue of every KPU conv output element (dense and depthwise), in its two halves: z, the pre-activation in 2^-p output steps (what
+// bn_add shifts and the statistics run sums), and the segment table over it
+__device__ __forceinline__ int64_t kpu_z(int64_t sum_xw, int64_t sum_x, long long arg_x, int shr_x, const KpuChan &c) {
     const int64_t acc = wrap_add(wrap_add(sum_xw, np_shr(wrap_mul(arg_x, sum_x), shr_x)), c.wconst);
-    const int64_t z = wrap_add(np_shr(wrap_mul(acc, c.bn_mul), c.bn_shift), c.bn_add);
+    return wrap_add(np_shr(wrap_mul(acc, c.bn_mul), c.bn_shift), c.bn_add);
+}
+
+__device__ __forceinline__ uint8_t kpu_table(int64_t z, const KpuSeg *__restrict__ seg) {
     int s = 0;
 #pragma unroll
     for (int i = 0; i < 16; ++i)
@@ -86,6 +89,19 @@ __device__ __forceinline__ uint8_t kpu_epilogue(int64_t sum_xw, int64_t sum_x, l
     y = y < 0 ? 0 : (y > 255 ? 255 : y);
     return (uint8_t)y;
 }
+
+__device__ __forceinline__ uint8_t kpu_epilogue(int64_t sum_xw, int64_t sum_x, long long arg_x, int shr_x, const KpuChan &c,
+                                                const KpuSeg *__restrict__ seg) {
+    return kpu_table(kpu_z(sum_xw, sum_x, arg_x, shr_x, c), seg);
+}
+
+// The statistics run (yk_kpu_run_stats_u8): sums of z per output channel, uint64 adds that wrap like everything here - so the result does not
+// depend on scheduling or launch geometry.  `step` 2 counts only output pixels with even oy and even ox (a stride-2 depthwise conv the KPU
+// runs at stride 1: only those positions reach its pooling reader).
+struct StatArgs {
+    unsigned long long *zsum;     // [OC] of this conv
+    int step;
+};
 
 typedef int v4i __attribute__((ext_vector_type(4)));
 
@@ -105,11 +121,15 @@ __device__ __forceinline__ int sum16_signed(v4i v) {
 // (columns), so a lane's four accumulator registers are four consecutive channels of one pixel (C/D: col = lane&15, row = 4(lane>>4)+r).
 // Inside a 64-wide K chunk, lane group h = lane>>4 holds K entries 16h..16h+15 of both operands (the same (group, byte) -> k map for A
 // and B, so the order inside the chunk is immaterial to the exact integer sum).
-template <bool FAST>
-__global__ __launch_bounds__(256) void kpu_conv_mfma(ConvArgs a) {
+// STATS: the same stores, and z of every counted element added to st.zsum[oc].  A lane's eight (i, t) channels are first summed over its four
+// pixels j in registers, then over the 16 lanes of its group h (the same channels, 16 pixels) by shuffles, and lane r == 0 of every group
+// issues one 64-bit atomic per channel: 32 per wave.  The shuffles sit after the pixel loop, outside every per-lane condition; the one return
+// above them is taken by whole waves (px0 depends on the wave alone), so no shuffle reads a lane that has left.
+template <bool FAST, bool STATS>
+__device__ __forceinline__ void kpu_conv_mfma_body(const ConvArgs &a, const StatArgs &st) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int px0 = (blockIdx.x * 4 + wave) * 64;
-    if (px0 >= a.M) return;
+    if (px0 >= a.M) return;                   // wave-uniform
     const int oc0 = blockIdx.y * 32;
     const int r = lane & 15, h = lane >> 4;
     const int ohw = a.OH * a.OW;
@@ -187,12 +207,18 @@ __global__ __launch_bounds__(256) void kpu_conv_mfma(ConvArgs a) {
         sx[j] += __shfl_xor(sx[j], 32, 64);
     }
     const bool vec = (a.OC & 3) == 0;
+    unsigned long long zs[2][4] = {{0ull, 0ull, 0ull, 0ull}, {0ull, 0ull, 0ull, 0ull}};
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         if (!pv[j]) continue;
         const int m = px0 + 16 * j + r;
         const int64_t sum_x = (int64_t)sx[j] + 128 * (int64_t)a.K;
         uint8_t *dst = a.out + (size_t)m * a.OC;
+        bool counted = true;
+        if (STATS && st.step > 1) {
+            const int rem = m % ohw, oy = rem / a.OW, ox = rem - oy * a.OW;
+            counted = oy % st.step == 0 && ox % st.step == 0;
+        }
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int oc = oc0 + 16 * i + 4 * h;
@@ -203,7 +229,13 @@ __global__ __launch_bounds__(256) void kpu_conv_mfma(ConvArgs a) {
                 if (oc + t < a.OC) {
                     const KpuChan c = a.ch[oc + t];
                     const int64_t sum_xw = (int64_t)acc[i][j][t] + 128 * (int64_t)sx[j] + c.fix;
-                    pack |= (unsigned)kpu_epilogue(sum_xw, sum_x, a.arg_x, a.shr_x, c, a.seg) << (8 * t);
+                    if (STATS) {
+                        const int64_t z = kpu_z(sum_xw, sum_x, a.arg_x, a.shr_x, c);
+                        if (counted) zs[i][t] += (unsigned long long)z;
+                        pack |= (unsigned)kpu_table(z, a.seg) << (8 * t);
+                    } else {
+                        pack |= (unsigned)kpu_epilogue(sum_xw, sum_x, a.arg_x, a.shr_x, c, a.seg) << (8 * t);
+                    }
                 }
             }
             if (vec) {
@@ -213,19 +245,33 @@ __global__ __launch_bounds__(256) void kpu_conv_mfma(ConvArgs a) {
             }
         }
     }
+    if (STATS) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                unsigned long long v = zs[i][t];
+#pragma unroll
+                for (int d = 1; d < 16; d <<= 1) v += __shfl_xor(v, d, 64);    // lanes 16 h .. 16 h + 15: every lane of the wave is here
+                const int oc = oc0 + 16 * i + 4 * h + t;
+                if (r == 0 && oc < a.OC && v) atomicAdd(st.zsum + oc, v);       // (adding 0 changes nothing: skipped)
+            }
+    }
+}
+
+template <bool FAST>
+__global__ __launch_bounds__(256) void kpu_conv_mfma(ConvArgs a) {
+    kpu_conv_mfma_body<FAST, false>(a, StatArgs{nullptr, 1});
+}
+
+template <bool FAST>
+__global__ __launch_bounds__(256) void kpu_conv_mfma_stats(ConvArgs a, StatArgs st) {
+    kpu_conv_mfma_body<FAST, true>(a, st);
 }
 
 // Depthwise conv on the VALU: one thread per output element (pixel, channel)
-__global__ __launch_bounds__(256) void kpu_dwconv(ConvArgs a) {
-    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (long long)a.M * a.C) return;
-    const int m = (int)(idx / a.C), c = (int)(idx - (long long)m * a.C);
-    const int ohw = a.OH * a.OW;
-    const int b = m / ohw, rem = m - b * ohw;
-    const int oy = rem / a.OW, ox = rem - oy * a.OW;
-    const uint8_t *src = a.in + (long long)b * a.in_sb + (long long)c * a.in_sc;
-    const uint8_t *w = reinterpret_cast<const uint8_t *>(a.w) + (size_t)c * a.k * a.k;
-    int sum_xw = 0, sum_x = 0;
+__device__ __forceinline__ void kpu_dw_sums(const ConvArgs &a, int oy, int ox, const uint8_t *src, const uint8_t *w, int &sum_xw, int &sum_x) {
+    sum_xw = 0, sum_x = 0;
     for (int ky = 0; ky < a.k; ++ky) {
         const int iy = oy * a.stride - a.pad + ky;
         for (int kx = 0; kx < a.k; ++kx) {
@@ -236,7 +282,55 @@ __global__ __launch_bounds__(256) void kpu_dwconv(ConvArgs a) {
             sum_x += x;
         }
     }
+}
+
+__global__ __launch_bounds__(256) void kpu_dwconv(ConvArgs a) {
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long long)a.M * a.C) return;
+    const int m = (int)(idx / a.C), c = (int)(idx - (long long)m * a.C);
+    const int ohw = a.OH * a.OW;
+    const int b = m / ohw, rem = m - b * ohw;
+    const int oy = rem / a.OW, ox = rem - oy * a.OW;
+    const uint8_t *src = a.in + (long long)b * a.in_sb + (long long)c * a.in_sc;
+    const uint8_t *w = reinterpret_cast<const uint8_t *>(a.w) + (size_t)c * a.k * a.k;
+    int sum_xw, sum_x;
+    kpu_dw_sums(a, oy, ox, src, w, sum_xw, sum_x);
     a.out[idx] = kpu_epilogue(sum_xw, sum_x, a.arg_x, a.shr_x, a.ch[c], a.seg);
+}
+
+// The statistics twin: the same store; no thread leaves before the barriers.  Consecutive threads are consecutive channels, so with C <= 256 a
+// workgroup meets every channel 256 / C times: its z are summed per channel in LDS (64-bit LDS atomics) and each channel's sum goes out as one
+// global atomic per workgroup.  With C > 256 the 256 threads of a workgroup hold 256 different channels - there is nothing to fold, and an
+// address is met once per workgroup as well.
+__global__ __launch_bounds__(256) void kpu_dwconv_stats(ConvArgs a, StatArgs st) {
+    __shared__ unsigned long long s_z[256];
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    const bool valid = idx < (long long)a.M * a.C;
+    const bool lds = a.C <= 256;
+    if (lds) s_z[threadIdx.x] = 0ull;
+    if (lds) __syncthreads();
+    if (valid) {
+        const int m = (int)(idx / a.C), c = (int)(idx - (long long)m * a.C);
+        const int ohw = a.OH * a.OW;
+        const int b = m / ohw, rem = m - b * ohw;
+        const int oy = rem / a.OW, ox = rem - oy * a.OW;
+        const uint8_t *src = a.in + (long long)b * a.in_sb + (long long)c * a.in_sc;
+        const uint8_t *w = reinterpret_cast<const uint8_t *>(a.w) + (size_t)c * a.k * a.k;
+        int sum_xw, sum_x;
+        kpu_dw_sums(a, oy, ox, src, w, sum_xw, sum_x);
+        const int64_t z = kpu_z(sum_xw, sum_x, a.arg_x, a.shr_x, a.ch[c]);
+        a.out[idx] = kpu_table(z, a.seg);
+        if (oy % st.step == 0 && ox % st.step == 0 && z != 0) {
+            if (lds)
+                atomicAdd(s_z + c, (unsigned long long)z);
+            else
+                atomicAdd(st.zsum + c, (unsigned long long)z);
+        }
+    }
+    if (lds) {
+        __syncthreads();
+        if ((int)threadIdx.x < a.C && s_z[threadIdx.x]) atomicAdd(st.zsum + threadIdx.x, s_z[threadIdx.x]);
+    }
 }
 
 // REQUANTIZE / RESIZE_NEAREST / one part of a CONCAT:  out[b][y][x][c_off + c] = T[in[b][(y*ih)/oh][(x*iw)/ow][c]]
@@ -487,27 +581,41 @@ static ConvArgs conv_args(const yk_kpu_plan *p, const Op &o, const uint8_t *d_fr
     return a;
 }
 
-extern "C" int yk_kpu_run_u8(yk_kpu_plan_t *p, const uint8_t *d_frames, int batch, int layout, void *stream) {
-    if (!p || !d_frames || batch <= 0 || batch > p->max_batch || (layout != YK_KPU_NHWC && layout != YK_KPU_CHW)) {
-        yk_set_error("yk_kpu_run_u8: bad argument (batch %d, max_batch %d, layout %d)", batch, p ? p->max_batch : 0, layout);
-        return YK_ERR_ARG;
-    }
+// One run: d_zsum == nullptr is yk_kpu_run_u8; otherwise the conv launches are the statistics instantiations (the same grids), conv number n (in
+// issue order) adding into d_zsum[sum of the earlier convs' OC ..] with step h_step[n].
+static int kpu_run(yk_kpu_plan_t *p, const uint8_t *d_frames, int batch, int layout, const int *h_step, unsigned long long *d_zsum, void *stream) {
     YK_HIP(hipSetDevice(p->device));
     hipStream_t st = (hipStream_t)stream;
+    int n_conv = 0;
+    size_t slot = 0;
     for (const Op &o : p->ops) {
         const Value &vo = p->V[o.out];
+        StatArgs sa{nullptr, 1};
+        if (d_zsum && (o.op == OP_CONV || o.op == OP_DWCONV)) {
+            sa = StatArgs{d_zsum + slot, h_step[n_conv++]};
+            slot += (size_t)vo.C;
+        }
         if (o.op == OP_CONV) {
             const ConvArgs a = conv_args(p, o, d_frames, batch, layout);
             const dim3 grid((a.M + 255) / 256, (unsigned)(up(a.OC, 32) / 32));
             const bool fast = a.in_sc == 1 && a.C % 16 == 0 && a.in_sx % 16 == 0 && ((uintptr_t)a.in & 15) == 0;
-            if (fast)
+            if (d_zsum) {
+                if (fast)
+                    hipLaunchKernelGGL(kpu_conv_mfma_stats<true>, grid, dim3(256), 0, st, a, sa);
+                else
+                    hipLaunchKernelGGL(kpu_conv_mfma_stats<false>, grid, dim3(256), 0, st, a, sa);
+            } else if (fast) {
                 hipLaunchKernelGGL(kpu_conv_mfma<true>, grid, dim3(256), 0, st, a);
-            else
+            } else {
                 hipLaunchKernelGGL(kpu_conv_mfma<false>, grid, dim3(256), 0, st, a);
+            }
         } else if (o.op == OP_DWCONV) {
             const ConvArgs a = conv_args(p, o, d_frames, batch, layout);
             const long long n = (long long)a.M * a.C;
-            hipLaunchKernelGGL(kpu_dwconv, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a);
+            if (d_zsum)
+                hipLaunchKernelGGL(kpu_dwconv_stats, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a, sa);
+            else
+                hipLaunchKernelGGL(kpu_dwconv, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a);
         } else if (o.op == OP_GATHER) {
             const Value &vi = p->V[o.in];
             const long long n = (long long)batch * vo.H * vo.W * vi.C;
@@ -523,6 +631,45 @@ extern "C" int yk_kpu_run_u8(yk_kpu_plan_t *p, const uint8_t *d_frames, int batc
         YK_HIP(hipGetLastError());
     }
     return YK_OK;
+}
+
+static int kpu_stat_slots(const yk_kpu_plan_t *p, int *n_convs) {
+    int slots = 0, n = 0;
+    for (const Op &o : p->ops)
+        if (o.op == OP_CONV || o.op == OP_DWCONV) slots += p->V[o.out].C, ++n;
+    if (n_convs) *n_convs = n;
+    return slots;
+}
+
+extern "C" int yk_kpu_run_u8(yk_kpu_plan_t *p, const uint8_t *d_frames, int batch, int layout, void *stream) {
+    if (!p || !d_frames || batch <= 0 || batch > p->max_batch || (layout != YK_KPU_NHWC && layout != YK_KPU_CHW)) {
+        yk_set_error("yk_kpu_run_u8: bad argument (batch %d, max_batch %d, layout %d)", batch, p ? p->max_batch : 0, layout);
+        return YK_ERR_ARG;
+    }
+    return kpu_run(p, d_frames, batch, layout, nullptr, nullptr, stream);
+}
+
+extern "C" int yk_kpu_stat_slots(const yk_kpu_plan_t *p) { return p ? kpu_stat_slots(p, nullptr) : 0; }
+
+extern "C" int yk_kpu_run_stats_u8(yk_kpu_plan_t *p, const uint8_t *d_frames, int batch, int layout, const int *h_step, int n_step,
+                                   uint64_t *d_zsum, void *stream) {
+    if (!p || !d_frames || !h_step || !d_zsum || batch <= 0 || batch > p->max_batch || (layout != YK_KPU_NHWC && layout != YK_KPU_CHW) ||
+        ((uintptr_t)d_zsum & 7u) != 0) {
+        yk_set_error("yk_kpu_run_stats_u8: bad argument (batch %d, max_batch %d, layout %d)", batch, p ? p->max_batch : 0, layout);
+        return YK_ERR_ARG;
+    }
+    int n_convs = 0;
+    (void)kpu_stat_slots(p, &n_convs);
+    if (n_step != n_convs) {
+        yk_set_error("yk_kpu_run_stats_u8: %d steps for the %d conv ops of the plan", n_step, n_convs);
+        return YK_ERR_ARG;
+    }
+    for (int i = 0; i < n_step; ++i)
+        if (h_step[i] != 1 && h_step[i] != 2) {
+            yk_set_error("yk_kpu_run_stats_u8: step %d of conv op %d (1 or 2)", h_step[i], i);
+            return YK_ERR_ARG;
+        }
+    return kpu_run(p, d_frames, batch, layout, h_step, reinterpret_cast<unsigned long long *>(d_zsum), stream);
 }
 
 extern "C" int yk_kpu_get_output(yk_kpu_plan_t *p, int idx, float **d_ptr, size_t *bytes, int *h, int *w, int *c) {

@@ -318,6 +318,60 @@ class KpuPlan(_PlanBase):
             raise YkError(f'KpuPlan.run_u8: frames {tuple(frames.shape)}, expected [<= {self.max_batch}, {", ".join(map(str, self._frame_shape(layout)))}]')
         call('yk_kpu_run_u8', self._h, frames, frames.shape[0], KPU_LAYOUTS[layout], _stream(stream))
 
+    # -- statistics run (biascorrect.py): per-channel integer sums of z ------
+    def _stat_layout(self):
+        """[(kmodel layer index, first slot, OC)] of the conv ops in issue order, and the slot count (yk_kpu_run_stats_u8's layout)."""
+        from . import kmodel as km_
+        rows, at = [], 0
+        for r in self.program.ops:
+            if int(r[km_.KF_OP]) in (km_.KPU_OP_CONV, km_.KPU_OP_DWCONV):
+                oc = int(self.program.values[int(r[km_.KF_OUT]), 0])
+                rows.append((int(r[km_.KF_LAYER]), at, oc))
+                at += oc
+        return rows, at
+
+    def _zsums(self):
+        import torch
+        if getattr(self, '_d_zsum', None) is None:
+            n = self._stat_layout()[1]
+            if n != lib().yk_kpu_stat_slots(self._h):
+                raise YkError('KpuPlan: the library counts other statistics slots than the program has conv channels')
+            self._d_zsum = torch.zeros(n, dtype=torch.int64, device=f'cuda:{self.device}')
+        return self._d_zsum
+
+    def run_stats_u8(self, frames, steps, layout: str = 'nhwc', stream=None) -> None:
+        """run_u8 with the statistics kernels: the same tensors and outputs, bit for bit, and z of every counted output element added to the
+        per-channel sums `read_zsums` returns.  steps: {kmodel layer index: 1 | 2} (missing: 1) or one value per conv in issue order; 2
+        counts only even oy and even ox.  Sums accumulate over runs until reset_zsums."""
+        import torch
+        if layout not in KPU_LAYOUTS:
+            raise YkError(f'layout {layout!r}: expected one of {sorted(KPU_LAYOUTS)}')
+        if not (frames.is_cuda and frames.dtype == torch.uint8 and frames.is_contiguous()):
+            raise YkError('KpuPlan.run_stats_u8: frames must be a contiguous cuda uint8 tensor')
+        if tuple(frames.shape[1:]) != self._frame_shape(layout) or not 0 < frames.shape[0] <= self.max_batch:
+            raise YkError(f'KpuPlan.run_stats_u8: frames {tuple(frames.shape)}, expected [<= {self.max_batch}, '
+                          f'{", ".join(map(str, self._frame_shape(layout)))}]')
+        rows = self._stat_layout()[0]
+        if isinstance(steps, dict):
+            unknown = sorted(set(steps) - {r[0] for r in rows})
+            if unknown:
+                raise YkError(f'KpuPlan.run_stats_u8: steps for layer(s) {unknown}, which are not conv layers of this kmodel')
+            steps = [steps.get(r[0], 1) for r in rows]
+        h_step = np.ascontiguousarray([int(s) for s in steps], np.int32)
+        if len(h_step) != len(rows) or not np.isin(h_step, (1, 2)).all():
+            raise YkError(f'KpuPlan.run_stats_u8: {len(rows)} steps of 1 or 2 expected, got {h_step.tolist()}')
+        call('yk_kpu_run_stats_u8', self._h, frames, frames.shape[0], KPU_LAYOUTS[layout], h_step, len(h_step), self._zsums(), _stream(stream))
+
+    def read_zsums(self):
+        """{kmodel layer index: int64 [OC]}: the sums of z since the last reset_zsums (waits for the device)."""
+        import torch
+        torch.cuda.synchronize(self.device)
+        h = self._zsums().cpu().numpy()
+        return {layer: h[at:at + oc].copy() for layer, at, oc in self._stat_layout()[0]}
+
+    def reset_zsums(self) -> None:
+        self._zsums().zero_()
+
     def read_layer(self, index: int, image: int) -> np.ndarray:
         """uint8 [C][H][W] output of the conv at kmodel layer `index` for image `image` of the last run (waits for the device)."""
         v = self.program.conv_values.get(int(index))

@@ -3,6 +3,7 @@
     python make_kmodel.py CKPT OUT [network flags of keras_inference.py] (--calib LIST.npy | --synthetic N | --ranges FILE.npz) [--calib_seed S]
                           [--calib_method minmax|percentile|mse] [--calib_percentile P] [--calib_bins NB]
                           [--equalize True [--equalize_max_gain G]]
+                          [--bias_correct True]
 
 CKPT: a Keras `.h5` or `.npz` checkpoint; OUT: `.kmodel` or `.kfpkg`.  The calibration images are a list file as make_voc_list.py writes
 (data/<set>_img_ann.npy) or N generated images as `make train SYNTHETIC=N` trains on; they are decoded as the input pipeline decodes them
@@ -15,7 +16,10 @@ pass over the same images (quantize.clip_range).  The report then lists every cl
 `--equalize True` (`make kmodel EQUALIZE=True EQMAXGAIN=64`): cross-layer range equalisation (equalize.py) before the calibration - one more
 pass over the images measures every conv output per channel, the weights are rewritten so that the channels of a tensor fill its range
 (gains up to `--equalize_max_gain`), and the file written is that network: the same function, other weights.  Not with `--ranges`: QAT
-ranges belong to the unequalised weights.  The report names the gains of every layer."""
+ranges belong to the unequalised weights.  The report names the gains of every layer.
+`--bias_correct True` (`make kmodel BIASCORRECT=True`): per-channel bias correction (biascorrect.py) after the calibration, on the same images -
+one more float pass and one KPU-exact statistics pass per conv layer find the integer to add to every channel's bn_add so that the kmodel's mean
+pre-activation equals the float network's.  Not with `--ranges`: it needs calibration frames.  The report gets one line per corrected layer."""
 from __future__ import annotations
 
 import argparse
@@ -59,7 +63,7 @@ def load_ranges(path, spec):
 
 
 def main(ckpt, out, image_size, output_size, model_def, class_num, depth_multiplier, train_set, calib, synthetic, calib_seed, batch, limit=0,
-         ranges=None, method='minmax', percentile=99.99, bins=2048, equalize=False, max_gain=64.0):
+         ranges=None, method='minmax', percentile=99.99, bins=2048, equalize=False, max_gain=64.0, bias_correct=False):
     from pathlib import Path
     from . import quantize
     anchor_file = Path(f'data/{train_set}_anchor.npy')
@@ -81,10 +85,13 @@ def main(ckpt, out, image_size, output_size, model_def, class_num, depth_multipl
     else:
         frames = calibration_frames(h, calib, synthetic, calib_seed, class_num, limit)
         eq = dict(equalize=True, max_gain=max_gain) if equalize else {}
+        if bias_correct:
+            eq['bias_correct'] = True
         report = model.save_kmodel(str(out), frames, batch=batch, method=method, percentile=percentile, bins=bins, **eq)
         print(quantize.format_report(report))
         print(INFO, f' {len(frames)} calibration images{"" if method == "minmax" else f", {method} ranges from {bins}-bin histograms"}'
-                    f'{f", channel ranges equalised first (max gain {max_gain:g}, one more pass)" if equalize else ""}, {time.time() - t0:.2f} s')
+                    f'{f", channel ranges equalised first (max gain {max_gain:g}, one more pass)" if equalize else ""}'
+                    f'{", channel biases corrected (one statistics pass per conv)" if bias_correct else ""}, {time.time() - t0:.2f} s')
     print(INFO, f' wrote {out}: kmodel of {report["file_bytes"]} bytes')
     return report
 
@@ -111,6 +118,8 @@ def cli(argv=None):
     p.add_argument('--equalize', type=str, default=None, help='True: equalise the channel ranges before quantising (equalize.py; one more pass '
                                                               'over the images); the file is the equalised network')
     p.add_argument('--equalize_max_gain', type=float, default=64.0, help='largest gain --equalize gives a channel, > 1')
+    p.add_argument('--bias_correct', type=str, default=None, help='True: correct every channel\'s bn_add after the calibration so that its mean '
+                                                                  'pre-activation equals the float network\'s (biascorrect.py); needs frames')
     p.add_argument('pre_ckpt', type=str, help='trained weights (.h5 / .npz)')
     p.add_argument('output', type=str, help='.kmodel or .kfpkg to write')
     a = p.parse_args(sys.argv[1:] if argv is None else argv)
@@ -127,6 +136,11 @@ def cli(argv=None):
         p.error('--equalize cannot be combined with --ranges: QAT ranges belong to the unequalised weights')
     if equalize and not a.equalize_max_gain > 1.0:
         p.error(f'--equalize_max_gain {a.equalize_max_gain} must be above 1')
+    if a.bias_correct not in (None, 'True', 'False'):
+        p.error(f'--bias_correct {a.bias_correct}: True or False')
+    bias_correct = a.bias_correct == 'True'
+    if a.ranges and bias_correct:
+        p.error('--bias_correct needs calibration frames: it cannot be combined with --ranges (QAT ranges, no frames)')
     method = a.calib_method or 'minmax'
     if method not in ('minmax', 'percentile', 'mse'):
         p.error(f'--calib_method {method}: one of minmax, percentile, mse')
@@ -136,7 +150,7 @@ def cli(argv=None):
         p.error(f'--calib_bins {a.calib_bins} outside 16..4096')
     return main(a.pre_ckpt, a.output, a.image_size, a.output_size, a.model_def, a.class_num, a.depth_multiplier, a.train_set, a.calib,
                 a.synthetic, a.calib_seed, a.calib_batch, a.calib_limit, a.ranges, method, a.calib_percentile, a.calib_bins, equalize,
-                a.equalize_max_gain)
+                a.equalize_max_gain, bias_correct)
 
 
 if __name__ == '__main__':

@@ -30,6 +30,7 @@ for every network output.  What the KPU path cannot express raises `KmodelError`
 """
 from __future__ import annotations
 
+import ctypes as C
 from typing import Dict, List, Optional, Tuple
 
 import numpy as np
@@ -164,12 +165,20 @@ def _act_table(act: int, alpha: float, zp_y: int, p: int):
     return tuple(np.array(col, np.int64) for col in zip(*segs))
 
 
-def quantize(spec: ns.NetSpec, weights: Dict[str, np.ndarray], ranges: Dict[str, Tuple[float, float]]):
+def quantize(spec: ns.NetSpec, weights: Dict[str, np.ndarray], ranges: Dict[str, Tuple[float, float]],
+             bn_add_delta: Optional[Dict[str, np.ndarray]] = None):
     """-> (kmodel.Kmodel, report).  `ranges`: {tensor name (tensor_names): (min, max)} of the calibration set, at least for the input-side
     of every conv ('input' is fixed to the raw pixel and need not be given; upsample / concat outputs take their producers' ranges).
     report['layers'][name] = scales, zero points, FINE_BITS used, the BatchNorm shifts chosen, the share of weights equal to the zero
-    point and the smallest non-zero |bn_mul| (what equalize.py's step A lowers for an amplified consumer).  CPU only, deterministic."""
+    point and the smallest non-zero |bn_mul| (what equalize.py's step A lowers for an amplified consumer).  CPU only, deterministic.
+    `bn_add_delta` (bias correction, biascorrect.py): {conv layer name: int64 [C]} added to that layer's bn_add after its rounding, which
+    moves every pre-activation z of channel c by exactly that many 2^-p output steps; None or {} changes nothing.  The report of a corrected
+    layer gains `bias_delta_max` (the largest |delta| in output codes, |delta| / 2^p) and `bias_limited` (filled in by biascorrect.correct)."""
     plan = plan_convs(spec)
+    bn_add_delta = dict(bn_add_delta or {})
+    unknown = sorted(set(bn_add_delta) - {op['layer'] for op in spec.ops if op['type'] in (ns.OP_CONV, ns.OP_DWCONV)})
+    if unknown:
+        raise KmodelError(f'quantize: bn_add_delta names layer(s) {", ".join(map(repr, unknown))}, which are not conv layers of {spec.name}')
     names = tensor_names(spec)
     lay = {l.name: l for l in spec.layers}
     readers = _consumers(spec)
@@ -232,6 +241,12 @@ def quantize(spec: ns.NetSpec, weights: Dict[str, np.ndarray], ranges: Dict[str,
             shift = np.where(over & (shift > 0), shift - 1, shift)
             bn_mul = np.rint(mf * np.exp2(shift)).astype(np.int64)
             bn_add = np.rint(bias / s_y * float(1 << p)).astype(np.int64)
+            delta = None
+            if l.name in bn_add_delta:
+                delta = np.asarray(bn_add_delta[l.name])
+                if delta.shape != (co,) or delta.dtype.kind not in 'iu':
+                    raise KmodelError(f'quantize: bn_add_delta of conv {l.name!r} is {delta.dtype} {delta.shape}, {co} integers expected')
+                bn_add = bn_add + delta.astype(np.int64)
             a_start, a_mul, a_shift, a_bias = _act_table(op['act'], float(op['alpha']), zp_y, p)
             dst = new_buf(co, g['out_h'], g['out_w'], idx)
             bufs[kpu_of[tin]]['death'] = idx
@@ -247,6 +262,8 @@ def quantize(spec: ns.NetSpec, weights: Dict[str, np.ndarray], ranges: Dict[str,
             report['layers'][l.name] = dict(index=idx, s_x=s_x, zp_x=zp_x, s_w=s_w, zp_w=zp_w, s_y=s_y, zp_y=zp_y, fine_bits=p, pool=g['pool'],
                                             bn_shift=(int(shift.min()), int(shift.max())), zero_share=float((wq == zp_w).mean()),
                                             range=(lo, hi), bn_mul_min=int(np.abs(bn_mul[bn_mul != 0]).min()) if bn_mul.any() else 0)
+            if delta is not None:
+                report['layers'][l.name].update(bias_delta_max=float(np.abs(delta).max()) / float(1 << p), bias_limited=0)
             if tout in spec.outputs:
                 n = co * g['out_h'] * g['out_w']
                 d = mem_alloc(4 * n)
@@ -316,6 +333,9 @@ def format_report(report: dict) -> str:
     if report.get('equalize'):
         from . import equalize
         rows.append(equalize.format_report(report['equalize']))
+    if report.get('biascorrect'):
+        from . import biascorrect
+        rows.append(biascorrect.format_report(report['biascorrect']))
     rows.append(f"main memory {report['main_mem_usage']} bytes, KPU RAM peak {report['kpu_ram_peak']} bytes")
     return '\n'.join(rows)
 
@@ -485,6 +505,7 @@ class Calibrator:
                 self.ch_slot0[op['layer']] = self.n_ch
                 self.n_ch += int(op['cout'])
         self.d_chrange = None                                                                            # allocated by the first feed_channels
+        self.d_chsum = None                                                                              # allocated by the first feed_means
         self._last_use = {}
         for k, op in enumerate(spec.ops):
             for key in ('in0', 'in1'):
@@ -499,9 +520,11 @@ class Calibrator:
 
     def reset(self) -> None:
         self._ck('yk_range_reset', self.d_range, self.n_slots)
-        self.images = self.hist_images = self.ch_images = 0
+        self.images = self.hist_images = self.ch_images = self.mean_images = 0
         if self.d_chrange is not None:
             self._ck('yk_range_reset', self.d_chrange, self.n_ch + 1)
+        if self.d_chsum is not None:
+            self._ck('yk_chsum_reset', self.d_chsum, self.d_chflags, self.n_ch)
         self.h_lo = self.h_hi = self.h_inv = None                                                        # frozen by the first feed_hist
         self.last_clip: List[dict] = []
 
@@ -548,6 +571,52 @@ class Calibrator:
             raise self.engine.YkError(f'Calibrator: non-finite values (NaN or infinity) in tensor(s) {", ".join(bad)}: the weights or the frames '
                                       f'are broken; no range is defined')
         return {name: (lo[s0:s1].copy(), hi[s0:s1].copy()) for name, (s0, s1) in ends.items()}
+
+    def _epilogue_means(self, z, M, Cn, scale, bias, act, alpha, y, slot):
+        if slot == 0:                                                                                # the input: no conv output, into a scratch slot
+            self._ck('yk_scale_act_range_f32', z, M, Cn, scale, bias, act, alpha, y, self.d_mscratch, 0)
+            return
+        need = C.c_size_t()
+        self.engine.call('yk_chsum_workspace_bytes', M, Cn, C.byref(need))
+        if self.d_chwork is None or self.d_chwork.numel() * 8 < need.value:
+            self.d_chwork = self.torch.empty((need.value + 7) // 8, dtype=self.torch.float64, device=self.dev)
+        self._ck('yk_scale_act_chsum_f32', z, M, Cn, scale, bias, act, alpha, y, self.d_chsum, self.d_chflags, self.ch_slot0[self.names[slot]],
+                 self.d_chwork)
+
+    def feed_means(self, frames_u8, keep=None) -> "Calibrator":
+        """frames_u8 as `feed` takes them: the float64 sum of the fp32 PRE-activation (folded BatchNorm applied, activation not) of every output
+        channel of every conv layer, accumulated over calls (yk_scale_act_chsum_f32: no floating-point atomics, the same calls give the same
+        bits).  What bias correction (biascorrect.py) compares the kmodel's z against.  Leaves ranges and histograms alone."""
+        if self.d_chsum is None:
+            self.d_chsum = self.torch.zeros(self.n_ch, dtype=self.torch.float64, device=self.dev)
+            self.d_chflags = self.torch.zeros(self.n_ch, dtype=self.torch.int32, device=self.dev)
+            self.d_mscratch = self.torch.zeros(4, dtype=self.torch.int32, device=self.dev)
+            self.d_chwork = None
+            self._ck('yk_chsum_reset', self.d_chsum, self.d_chflags, self.n_ch)
+        self._walk(frames_u8, keep, self._epilogue_means, lambda x, slot: None, 'feed_means')
+        self.mean_images += int(frames_u8.shape[0])
+        return self
+
+    def channel_means(self) -> Dict[str, Tuple[np.ndarray, int]]:
+        """{conv layer name: (sum float64 [C], count)} over everything fed to feed_means; count = images x out_h x out_w of the SPEC's tensor
+        (a stride-2 depthwise conv counts its half-size output).  YkError naming the layer when one of its channels held a NaN or an infinity,
+        and when nothing was fed."""
+        if not self.mean_images:
+            raise self.engine.YkError('Calibrator.channel_means: nothing has been fed to feed_means')
+        s, fl = np.empty(self.n_ch, np.float64), np.empty(self.n_ch, np.int32)
+        self.torch.cuda.current_stream().synchronize()
+        self.engine.call('yk_chsum_read', self.d_chsum, self.d_chflags, self.n_ch, s, fl)
+        out, bad = {}, []
+        for op in self.spec.ops:
+            if op['type'] in (ns.OP_CONV, ns.OP_DWCONV):
+                s0, (h, w, c) = self.ch_slot0[op['layer']], self.spec.tensors[op['out']]
+                if fl[s0:s0 + c].any():
+                    bad.append(op['layer'])
+                out[op['layer']] = (s[s0:s0 + c].copy(), self.mean_images * int(h) * int(w))
+        if bad:
+            raise self.engine.YkError(f'Calibrator: non-finite values (NaN or infinity) in tensor(s) {", ".join(bad)}: the weights or the frames '
+                                      f'are broken; no mean is defined')
+        return out
 
     def feed(self, frames_u8, keep=None) -> "Calibrator":
         """frames_u8: device uint8 [B, H, W, 3], B <= max_batch, H x W = the spec's input size.  `keep`: a dict that receives every tensor
@@ -764,3 +833,15 @@ def calibrate_channels(spec: ns.NetSpec, weights, frames_u8, batch: int = 32) ->
     for i in range(0, len(frames), batch):
         cal.feed_channels(frames[i:i + batch].cuda())
     return cal.channel_ranges()
+
+
+def calibrate_means(spec: ns.NetSpec, weights, frames_u8, batch: int = 32) -> Dict[str, Tuple[np.ndarray, int]]:
+    """{conv layer name: (sum float64 [C], count)} of the pre-activations over `frames_u8` (as `calibrate` takes them) in batches of `batch`:
+    what biascorrect.correct needs."""
+    import torch
+    frames = frames_u8 if torch.is_tensor(frames_u8) else torch.from_numpy(np.ascontiguousarray(frames_u8))
+    batch = max(1, min(int(batch), len(frames)))
+    cal = Calibrator(spec, weights, max_batch=batch)
+    for i in range(0, len(frames), batch):
+        cal.feed_means(frames[i:i + batch].cuda())
+    return cal.channel_means()

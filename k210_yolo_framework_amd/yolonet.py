@@ -116,7 +116,7 @@ class YoloModel:
             np.savez(path, **self._s['weights'])
 
     def save_kmodel(self, path: str, calibration_frames, batch: int = 32, method: str = 'minmax', percentile: float = 99.99, bins: int = 2048,
-                    equalize: bool = False, max_gain: float = 64.0):
+                    equalize: bool = False, max_gain: float = 64.0, bias_correct: bool = False):
         """Quantise these weights to a K210 kmodel (quantize.py) and write it: `.kmodel`, or `.kfpkg` (model + flash list, no
         firmware).  calibration_frames: uint8 [N, H, W, 3] at the network's input size (host numpy or a device tensor); their tensor ranges
         are measured on the GPU in batches of `batch`, from the raw pixels / 255 as the KPU sees them.  The new Kmodel is kept beside the
@@ -127,7 +127,11 @@ class YoloModel:
         equalize=True first equalises the channel ranges (equalize.py): one more pass over the frames measures every conv output per channel
         (Calibrator.feed_channels), equalize.equalize rewrites the weights (gains up to `max_gain`), and calibration and quantisation then run
         on THOSE weights; report['equalize'] holds the gains.  The written file is the equalised network - the same function, other weights;
-        this object's float weights are not touched."""
+        this object's float weights are not touched.
+        bias_correct=True (biascorrect.py) then removes the systematic error the chosen ranges leave: on the same frames, one more float pass
+        sums every channel's pre-activation (Calibrator.feed_means), and one KPU-exact statistics pass PER CONV (KpuPlan.run_stats_u8) finds the
+        integer to add to each channel's bn_add so that its mean pre-activation equals the float network's within 2^-(p + 1) of a code;
+        report['biascorrect'] lists the layers.  Order: equalise, calibrate, bias-correct, write."""
         import torch
         from . import engine, kmodel, quantize
         try:
@@ -149,7 +153,16 @@ class YoloModel:
                 raise engine.YkError(f'save_kmodel: {e}') from e
         ranges = quantize.calibrate(self.spec, weights, frames, batch, method, percentile, bins, clipped)
         try:
-            km, report = quantize.quantize(self.spec, weights, ranges)
+            delta, bc_report = None, None
+            if bias_correct:
+                from . import biascorrect
+                delta, bc_report = biascorrect.correct(self.spec, weights, ranges, quantize.calibrate_means(self.spec, weights, frames, batch),
+                                                       biascorrect.gpu_measure(frames, batch))
+            km, report = quantize.quantize(self.spec, weights, ranges, delta)
+            if bc_report is not None:
+                report['biascorrect'] = bc_report
+                for name, r in bc_report['layers'].items():
+                    report['layers'][name]['bias_limited'] = len(r['limited'])
             if eq_report is not None:
                 report['equalize'] = eq_report
             if method != 'minmax':
