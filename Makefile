@@ -9,6 +9,9 @@
 #                    [PRUNE=True INITSPARSITY=0.5 FINALSPARSITY=0.9 END_EPOCH=5 FREQUENCY=100]: magnitude pruning, saves yolo_prune_model.h5
 #                    [QAT=True QATMOMENTUM=0.99 QATOBSERVE=8]: quantisation-aware fine-tuning, saves yolo_qat_model.h5 + yolo_qat_ranges.npz
 #                    [BOXLOSS=giou|diou|ciou BOXWEIGHT=1.0]: an IoU-family box loss in place of the xy / wh terms (default mse: the reference's loss)
+#                    [FOCAL=obj|cls|all FOCALGAMMA=2.0 FOCALALPHA=0.25 LABELSMOOTH=0.1 OBJTARGET=iou]: focal loss on the objectness and / or class
+#                    terms, smoothed class targets, the IoU of the predicted box as an object cell's objectness target (all off by default: the
+#                    reference's loss; the values named here are starting points, not findings: DESIGN.md 3.25, profiles/lossopt_*.txt)
 #                    [MOSAIC=True MOSAICPROB=1.0 MOSAICOFF=0]: four pictures per training sample, composed on the GPU; the last MOSAICOFF epochs without
 #                    [HSV=True HSVHUE=0.1 HSVSAT=1.5 HSVEXP=1.5 HSVPROB=1.0]: HSV colour jitter of every training frame, on the GPU (Darknet's recipe)
 #                    [TEACHERCKPT=big.h5|.npz TEACHER=yolo_mobilev2 TEACHERDEPTH=1.0 DISTILLWEIGHT=1.0]: knowledge distillation from a trained network of
@@ -97,6 +100,11 @@ QATOBSERVE    ?= 8
 VALMAP        ?= False
 BOXLOSS       ?= mse
 BOXWEIGHT     ?= 1.0
+FOCAL         ?=
+FOCALGAMMA    ?= 2.0
+FOCALALPHA    ?= 0
+LABELSMOOTH   ?= 0
+OBJTARGET     ?=
 MOSAIC        ?= False
 MOSAICPROB    ?= 1.0
 MOSAICOFF     ?= 0
@@ -174,7 +182,9 @@ TRAIN_ARGS = --pre_ckpt $(CKPT) --augmenter $(IAA) --batch_size $(BATCH) --rand_
              $(if $(TEACHERDEPTH),--teacher_depth $(TEACHERDEPTH))) \
              $(if $(filter True,$(EMA)),--ema True --ema_decay $(EMADECAY) --ema_tau $(EMATAU)) \
              $(if $(filter-out 0 0.0,$(CLIPNORM)),--clip_norm $(CLIPNORM)) \
-             $(if $(LRSCHED),--lr_schedule $(LRSCHED) --warmup_steps $(WARMUP) --lr_final $(LRFINAL))
+             $(if $(LRSCHED),--lr_schedule $(LRSCHED) --warmup_steps $(WARMUP) --lr_final $(LRFINAL))$(if \
+             $(filter-out off,$(FOCAL))$(filter-out 0 0.0,$(LABELSMOOTH))$(filter-out label,$(OBJTARGET)), --focal $(or $(FOCAL),off) \
+             --focal_gamma $(FOCALGAMMA) --focal_alpha $(FOCALALPHA) --label_smooth $(LABELSMOOTH) --obj_target $(or $(OBJTARGET),label))
 ifeq ($(GPUS),1)
 LAUNCH = $(PY)
 else

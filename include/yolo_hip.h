@@ -611,6 +611,34 @@ typedef struct {
 } yk_loss_cfg_ex_t;
 int yk_yolo_loss_ex(const yk_loss_cfg_ex_t *cfg, const float *d_y_true, const float *d_y_pred, int batch, float *d_loss,
                     float *d_grad, float *d_ignore, float *d_counts, void *stream);
+/* The same loss with options on the objectness and class terms (the rule is stated in lossopt.py).  With p = sigmoid(x),
+ * bce the cross entropy above and z a target in [0, 1]:
+ *   label_smooth eps  every class target becomes z (1 - eps) + eps / 2.
+ *   obj_target        YK_OBJ_TARGET_IOU: in an object cell (y_true conf > obj_thresh) the objectness target is clamp(IoU, 0, 1) of the decoded
+ *                     prediction with the label box, IoU = I / (bw bh + tw th - I + 1e-7), a constant in the gradient; in the IoU box modes
+ *                     it is the IoU of the box term.  The weights, the ignore mask, (2 - tw th) and the counters stay on y_true conf.
+ *   focal             bit 0 (YK_FOCAL_OBJ): the obj and noobj sums, bit 1 (YK_FOCAL_CLS): the class sum take
+ *                     fl(z, x) = a_t (1 - p_t)^gamma bce(z, x),  1 - p_t = z sigmoid(-x) + (1 - z) sigmoid(x),
+ *                     a_t = z alpha + (1 - z)(1 - alpha), or 1 when alpha = 0, in place of bce; the gradient is the full derivative.
+ * Ranges: focal 0 .. 3; focal_gamma 0 or 1 .. 5; focal_alpha 0 or inside (0, 1); label_smooth in [0, 1); obj_target YK_OBJ_TARGET_*.
+ * Anything else is YK_ERR_ARG, the message names the field, nothing is launched.  gamma = 0 with alpha = 0 is bce.  With every option off
+ * the call gives the bits of yk_yolo_loss_ex.  d_loss[7] and the other parameters are those of yk_yolo_loss_ex; obj, noobj and cls report
+ * the new terms.  The sums are taken in the same fixed order: two calls give the same bits. */
+enum { YK_FOCAL_OBJ = 1, YK_FOCAL_CLS = 2 };
+enum { YK_OBJ_TARGET_LABEL = 0, YK_OBJ_TARGET_IOU = 1 };
+typedef struct {
+    int32_t out_h, out_w, anchor_num, class_num;       /* yk_loss_cfg_ex_t's fields, in its order ... */
+    float anchors[YK_MAX_ANCHORS][2];
+    float obj_thresh, iou_thresh, obj_weight, noobj_weight, wh_weight;
+    int32_t batch_size;
+    int32_t box_loss;
+    float box_weight;
+    int32_t focal;                                      /* ... then YK_FOCAL_* bits */
+    float focal_gamma, focal_alpha, label_smooth;
+    int32_t obj_target;                                 /* YK_OBJ_TARGET_* */
+} yk_loss_cfg_opt_t;
+int yk_yolo_loss_opt(const yk_loss_cfg_opt_t *cfg, const float *d_y_true, const float *d_y_pred, int batch, float *d_loss,
+                     float *d_grad, float *d_ignore, float *d_counts, void *stream);
 
 /* Knowledge distillation on the raw outputs of ONE output layer (the rule is stated in distill.py, csrc/yk_distill.hip).
  * d_teacher / d_pred: device fp32 [batch][rows_per_image][5 + class_num], the teacher's and the student's raw outputs (rows_per_image =

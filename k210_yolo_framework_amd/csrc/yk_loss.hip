@@ -15,6 +15,10 @@
 // Box term: the reference's xy / wh terms (YK_BOX_LOSS_MSE, the default) or, opt-in, one of the IoU-family losses between
 // the decoded prediction and the label box: GIoU (Rezatofighi et al. 2019), DIoU / CIoU (Zheng et al. 2020).  The mode is a template
 // parameter of the kernel: the MSE instance is the kernel as it was, the others replace the xy / wh arithmetic of an object cell.
+//
+// Options on the objectness and class terms (the rule is stated in lossopt.py; yk_yolo_loss_opt): focal loss, label smoothing
+// and an IoU objectness target.  They are the second template parameter, a set of L_* bits: the instances with OPT = 0 are the kernels that
+// yk_yolo_loss / yk_yolo_loss_ex launch, and an option that is off costs its instances nothing.
 #include "yk_common.h"
 
 #define YK_LOSS_MAXGT 1024
@@ -26,10 +30,38 @@ struct loss_args {
     float obj_thresh, iou_thresh, obj_w, noobj_w, wh_w;
     int box_loss;
     float box_w;
+    float gamma, alpha, smooth_k, smooth_h;   // focal exponent and balance; label smoothing z -> z smooth_k + smooth_h (1 - eps, eps / 2)
 };
+
+// OPT bits.  L_POW: gamma is not 2 (everyone's default, two multiplications) and the focal factor takes a powf
+enum { L_FOBJ = 1, L_FCLS = 2, L_POW = 4, L_SMOOTH = 8, L_IOU = 16 };
 
 __device__ __forceinline__ float l_sigmoid(float v) { return 1.f / (1.f + expf(-v)); }
 __device__ __forceinline__ float l_bce(float z, float x) { return fmaxf(x, 0.f) - x * z + log1pf(expf(-fabsf(x))); }
+
+// Focal term fl(z, x) = a_t m^gamma bce(z, x) with m = 1 - p_t = z sigmoid(-x) + (1 - z) sigmoid(x), and dx = d fl / d x, the full derivative:
+// d m / d x = (1 - 2 z) p (1 - p), d bce / d x = p - z.  Both sigmoids come from one expf(-|x|) with no subtraction from 1, so a saturated
+// logit keeps the bits of its small side; the same expf feeds the bce.
+template <bool POW>
+__device__ __forceinline__ float l_focal(float z, float x, float gamma, float alpha, float &dx) {
+    const float e = expf(-fabsf(x)), r = 1.f / (1.f + e);
+    const float big = r, small = e * r;                                  // sigmoid(|x|), sigmoid(-|x|)
+    const float p = x >= 0.f ? big : small, q = x >= 0.f ? small : big;
+    const float bce = fmaxf(x, 0.f) - x * z + log1pf(e);
+    const float m = z * q + (1.f - z) * p;
+    const float at = alpha > 0.f ? z * alpha + (1.f - z) * (1.f - alpha) : 1.f;
+    float pw, dpw;                                                       // m^gamma and its derivative by m
+    if (POW) {
+        const float p1 = gamma > 0.f ? powf(m, gamma - 1.f) : 0.f;       // gamma >= 1: finite at m = 0
+        pw = gamma > 0.f ? p1 * m : 1.f;
+        dpw = gamma * p1;
+    } else {
+        pw = m * m;
+        dpw = 2.f * m;
+    }
+    dx = at * (dpw * ((1.f - 2.f * z) * p * q) * bce + pw * (p - z));
+    return at * pw * bce;
+}
 
 // 0.5 at a tie: where two edges coincide the loss has a kink, and the even split is the one sub-gradient that is zero for equal boxes
 __device__ __forceinline__ float l_less(float u, float v) { return u < v ? 1.f : (u == v ? 0.5f : 0.f); }
@@ -56,13 +88,16 @@ __device__ __forceinline__ l_axis l_box_axis(float bc, float bs, float tc, float
 }
 
 // IoU-family loss of one object cell and its gradient g = d loss / d (bx, by, bw, bh); alpha of CIoU is a constant.
+// iou_out: the IoU the loss is built on (the objectness target of L_IOU).
 template <int MODE>
-__device__ __forceinline__ float l_box_loss(float bx, float by, float bw, float bh, float tx, float ty, float tw, float th, float g[4]) {
+__device__ __forceinline__ float l_box_loss(float bx, float by, float bw, float bh, float tx, float ty, float tw, float th, float g[4],
+                                            float &iou_out) {
     const float eps = 1e-7f;
     const l_axis X = l_box_axis(bx, bw, tx, tw), Y = l_box_axis(by, bh, ty, th);
     const float I = X.ov * Y.ov;
     const float U = bw * bh + tw * th - I + eps;
     const float iou = I / U;
+    iou_out = iou;
     const float dI[4] = {Y.ov * X.ov_c, X.ov * Y.ov_c, Y.ov * X.ov_s, X.ov * Y.ov_s};
     const float dU[4] = {-dI[0], -dI[1], bh - dI[2], bw - dI[3]};
     float l = 1.f - iou;
@@ -97,7 +132,7 @@ __device__ __forceinline__ float l_box_loss(float bx, float by, float bw, float 
     return l;
 }
 
-template <int MODE>
+template <int MODE, int OPT = 0>
 __global__ void __launch_bounds__(256) yolo_loss_kernel(loss_args a, const float *__restrict__ y_true,
                                                         const float *__restrict__ y_pred, float *__restrict__ grad,
                                                         float *__restrict__ ignore_out, double *__restrict__ partial) {
@@ -162,27 +197,51 @@ __global__ void __launch_bounds__(256) yolo_loss_kernel(loss_args a, const float
         const float gw = ob ? logf(tw / a.anchors[an][0]) : 0.f, gh = ob ? logf(th / a.anchors[an][1]) : 0.f;
         const float cw = 2.f - tw * th;
         float gb[4] = {0.f, 0.f, 0.f, 0.f};     // the IoU modes' gradient entries 0..3
+        float iou = 0.f;                        // of an object cell's prediction with its label box (L_IOU)
         if (MODE == YK_BOX_LOSS_MSE) {
             s_xy += (double)(obj * cw * (l_bce(gx, px) + l_bce(gy, py)));
             s_wh += (double)(obj * cw * a.wh_w * ((gw - pw) * (gw - pw) + (gh - ph) * (gh - ph)));
+            if ((OPT & L_IOU) && ob) {          // the IoU of l_box_loss; no box term uses it here
+                const l_axis X = l_box_axis(ax, aw, tx, tw), Y = l_box_axis(ay, ah, ty, th);
+                const float I = X.ov * Y.ov;
+                iou = I / (aw * ah + tw * th - I + 1e-7f);
+            }
         } else if (ob) {
             // skipped, not multiplied away, elsewhere: the label box of a cell without an object is all zeros (atan(0 / 0), 0 * NaN)
             const float k = obj * cw * a.box_w;
-            s_box += (double)(k * l_box_loss<MODE>(ax, ay, aw, ah, tx, ty, tw, th, gb));
+            s_box += (double)(k * l_box_loss<MODE>(ax, ay, aw, ah, tx, ty, tw, th, gb, iou));
             gb[0] = k * gb[0] * (sx * (1.f - sx) / (float)a.w) * inv_bs;
             gb[1] = k * gb[1] * (sy * (1.f - sy) / (float)a.h) * inv_bs;
             gb[2] = k * gb[2] * aw * inv_bs;
             gb[3] = k * gb[3] * ah * inv_bs;
         }
-        const float bc = l_bce(tc, pc);
+        // objectness: the target is y_true conf or, in an object cell under L_IOU, the clamped IoU, a constant in the gradient; the weights
+        // (obj, the ignore mask) stay on y_true conf.  dbc = d bc / d pc
+        float zo = tc;
+        if ((OPT & L_IOU) && ob) zo = fminf(fmaxf(iou, 0.f), 1.f);
+        float bc, dbc;
+        if (OPT & L_FOBJ) {
+            bc = l_focal<(OPT & L_POW) != 0>(zo, pc, a.gamma, a.alpha, dbc);
+        } else {
+            bc = l_bce(zo, pc);
+            dbc = l_sigmoid(pc) - zo;
+        }
         s_obj += (double)(obj * bc);
         s_noobj += (double)((1.f - obj) * ign * bc);
         float cls = 0.f;
         float *gr = grad ? grad + ((size_t)b * P + p) * a.E : nullptr;
         for (int c = 0; c < a.C; ++c) {
-            const float x = q[5 + c], z = t[5 + c];
-            cls += l_bce(z, x);
-            if (gr) gr[5 + c] = obj * (l_sigmoid(x) - z) * inv_bs;
+            const float x = q[5 + c];
+            float z = t[5 + c];
+            if (OPT & L_SMOOTH) z = z * a.smooth_k + a.smooth_h;
+            if (OPT & L_FCLS) {
+                float d;
+                cls += l_focal<(OPT & L_POW) != 0>(z, x, a.gamma, a.alpha, d);
+                if (gr) gr[5 + c] = obj * d * inv_bs;
+            } else {
+                cls += l_bce(z, x);
+                if (gr) gr[5 + c] = obj * (l_sigmoid(x) - z) * inv_bs;
+            }
         }
         s_cls += (double)(obj * cls);
         if (gr) {
@@ -195,7 +254,7 @@ __global__ void __launch_bounds__(256) yolo_loss_kernel(loss_args a, const float
 #pragma unroll
                 for (int k = 0; k < 4; ++k) gr[k] = gb[k];
             }
-            gr[4] = (a.obj_w * obj + a.noobj_w * (1.f - obj) * ign) * (l_sigmoid(pc) - tc) * inv_bs;
+            gr[4] = (a.obj_w * obj + a.noobj_w * (1.f - obj) * ign) * dbc * inv_bs;
         }
         const bool pp = pc > a.obj_thresh;     // custom.py:33: raw logit
         tp += (ob && pp);
@@ -238,9 +297,27 @@ __global__ void yolo_loss_finish_kernel(loss_args a, int batch, const double *__
     }
 }
 
-// both entry points: `who` names the caller in the messages, n_out is the length of d_loss
-static int loss_launch(const char *who, const yk_loss_cfg_ex_t *cfg, int n_out, const float *d_y_true, const float *d_y_pred, int batch,
-                       float *d_loss, float *d_grad, float *d_ignore, float *d_counts, void *stream) {
+// The instances with options: every set of L_* bits that can be asked for (L_POW only beside a focal bit), for one box mode.
+template <int MODE>
+static void loss_launch_opt(int bits, dim3 grid, hipStream_t st, const loss_args &a, const float *d_y_true, const float *d_y_pred, float *d_grad,
+                            float *d_ignore, double *partial) {
+#define YK_L1(o)                                                                                                                          \
+    case (o):                                                                                                                             \
+        hipLaunchKernelGGL((yolo_loss_kernel<MODE, (o)>), grid, dim3(256), 0, st, a, d_y_true, d_y_pred, d_grad, d_ignore, partial);      \
+        break;
+#define YK_L4(o) YK_L1(o) YK_L1((o) | L_SMOOTH) YK_L1((o) | L_IOU) YK_L1((o) | L_SMOOTH | L_IOU)
+    switch (bits) {
+        YK_L1(L_SMOOTH) YK_L1(L_IOU) YK_L1(L_SMOOTH | L_IOU)
+        YK_L4(L_FOBJ) YK_L4(L_FCLS) YK_L4(L_FOBJ | L_FCLS)
+        YK_L4(L_FOBJ | L_POW) YK_L4(L_FCLS | L_POW) YK_L4(L_FOBJ | L_FCLS | L_POW)
+    }
+#undef YK_L4
+#undef YK_L1
+}
+
+// all entry points: `who` names the caller in the messages, n_out is the length of d_loss, opt (yk_yolo_loss_opt alone) holds the options
+static int loss_launch(const char *who, const yk_loss_cfg_ex_t *cfg, const yk_loss_cfg_opt_t *opt, int n_out, const float *d_y_true,
+                       const float *d_y_pred, int batch, float *d_loss, float *d_grad, float *d_ignore, float *d_counts, void *stream) {
     if (!cfg || !d_y_true || !d_y_pred || !d_loss || batch <= 0 || cfg->out_h <= 0 || cfg->out_w <= 0 || cfg->anchor_num <= 0 ||
         cfg->anchor_num > YK_MAX_ANCHORS || cfg->class_num <= 0 || cfg->batch_size <= 0) {
         yk_set_error("%s: bad argument", who);
@@ -250,6 +327,36 @@ static int loss_launch(const char *who, const yk_loss_cfg_ex_t *cfg, int n_out, 
     if (box_loss != YK_BOX_LOSS_MSE && box_loss != YK_BOX_LOSS_GIOU && box_loss != YK_BOX_LOSS_DIOU && box_loss != YK_BOX_LOSS_CIOU) {
         yk_set_error("%s: box_loss %d is none of YK_BOX_LOSS_MSE (0), _GIOU (1), _DIOU (2), _CIOU (3)", who, box_loss);
         return YK_ERR_ARG;
+    }
+    int bits = 0;                                                       // L_*: what is on, and so which instance runs
+    if (opt) {
+        const float g = opt->focal_gamma, al = opt->focal_alpha, eps = opt->label_smooth;
+        if (opt->focal < 0 || opt->focal > (YK_FOCAL_OBJ | YK_FOCAL_CLS)) {
+            yk_set_error("%s: focal %d is no set of YK_FOCAL_OBJ (1), YK_FOCAL_CLS (2)", who, opt->focal);
+            return YK_ERR_ARG;
+        }
+        if (!(g == 0.f || (g >= 1.f && g <= 5.f))) {                     // (a NaN fails every comparison)
+            yk_set_error("%s: focal_gamma %g is neither 0 nor in 1 .. 5 (below 1 the gradient is unbounded)", who, (double)g);
+            return YK_ERR_ARG;
+        }
+        if (!(al >= 0.f && al < 1.f)) {
+            yk_set_error("%s: focal_alpha %g is neither 0 (off) nor inside (0, 1)", who, (double)al);
+            return YK_ERR_ARG;
+        }
+        if (!(eps >= 0.f && eps < 1.f)) {
+            yk_set_error("%s: label_smooth %g is not in [0, 1)", who, (double)eps);
+            return YK_ERR_ARG;
+        }
+        if (opt->obj_target != YK_OBJ_TARGET_LABEL && opt->obj_target != YK_OBJ_TARGET_IOU) {
+            yk_set_error("%s: obj_target %d is neither YK_OBJ_TARGET_LABEL (0) nor YK_OBJ_TARGET_IOU (1)", who, opt->obj_target);
+            return YK_ERR_ARG;
+        }
+        if (g != 0.f || al != 0.f) {                                     // gamma = 0, alpha = 0: fl is bce
+            bits |= (opt->focal & YK_FOCAL_OBJ ? L_FOBJ : 0) | (opt->focal & YK_FOCAL_CLS ? L_FCLS : 0);
+            if (bits && g != 2.f) bits |= L_POW;
+        }
+        if (eps > 0.f) bits |= L_SMOOTH;
+        if (opt->obj_target == YK_OBJ_TARGET_IOU) bits |= L_IOU;
     }
     int dev = yk_current_device();
     if (dev < 0) {
@@ -274,11 +381,30 @@ static int loss_launch(const char *who, const yk_loss_cfg_ex_t *cfg, int n_out, 
     a.wh_w = cfg->wh_weight;
     a.box_loss = box_loss;
     a.box_w = cfg->box_weight;
+    a.gamma = opt ? opt->focal_gamma : 0.f;
+    a.alpha = opt ? opt->focal_alpha : 0.f;
+    a.smooth_k = opt ? 1.f - opt->label_smooth : 1.f;
+    a.smooth_h = opt ? opt->label_smooth / 2.f : 0.f;
     const int chunks = (a.h * a.w * a.A + 255) / 256;
     double *partial = (double *)yk_scratch(dev, stream, YK_SLOT_LOSS, sizeof(double) * YK_LOSS_COLS * batch * chunks);
     if (!partial) return YK_ERR_NOMEM;
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid(batch, chunks);
+    if (bits) {
+        switch (box_loss) {
+        case YK_BOX_LOSS_GIOU:
+            loss_launch_opt<YK_BOX_LOSS_GIOU>(bits, grid, st, a, d_y_true, d_y_pred, d_grad, d_ignore, partial);
+            break;
+        case YK_BOX_LOSS_DIOU:
+            loss_launch_opt<YK_BOX_LOSS_DIOU>(bits, grid, st, a, d_y_true, d_y_pred, d_grad, d_ignore, partial);
+            break;
+        case YK_BOX_LOSS_CIOU:
+            loss_launch_opt<YK_BOX_LOSS_CIOU>(bits, grid, st, a, d_y_true, d_y_pred, d_grad, d_ignore, partial);
+            break;
+        default:
+            loss_launch_opt<YK_BOX_LOSS_MSE>(bits, grid, st, a, d_y_true, d_y_pred, d_grad, d_ignore, partial);
+        }
+    } else
     switch (box_loss) {
     case YK_BOX_LOSS_GIOU:
         hipLaunchKernelGGL(yolo_loss_kernel<YK_BOX_LOSS_GIOU>, grid, dim3(256), 0, st, a, d_y_true, d_y_pred, d_grad, d_ignore, partial);
@@ -315,10 +441,19 @@ extern "C" int yk_yolo_loss(const yk_loss_cfg_t *cfg, const float *d_y_true, con
         ex.box_loss = YK_BOX_LOSS_MSE;
         ex.box_weight = 0.f;
     }
-    return loss_launch("yk_yolo_loss", cfg ? &ex : nullptr, 6, d_y_true, d_y_pred, batch, d_loss, d_grad, d_ignore, d_counts, stream);
+    return loss_launch("yk_yolo_loss", cfg ? &ex : nullptr, nullptr, 6, d_y_true, d_y_pred, batch, d_loss, d_grad, d_ignore, d_counts, stream);
 }
 
 extern "C" int yk_yolo_loss_ex(const yk_loss_cfg_ex_t *cfg, const float *d_y_true, const float *d_y_pred, int batch, float *d_loss,
                                float *d_grad, float *d_ignore, float *d_counts, void *stream) {
-    return loss_launch("yk_yolo_loss_ex", cfg, 7, d_y_true, d_y_pred, batch, d_loss, d_grad, d_ignore, d_counts, stream);
+    return loss_launch("yk_yolo_loss_ex", cfg, nullptr, 7, d_y_true, d_y_pred, batch, d_loss, d_grad, d_ignore, d_counts, stream);
+}
+
+static_assert(offsetof(yk_loss_cfg_opt_t, focal) == sizeof(yk_loss_cfg_ex_t), "yk_loss_cfg_opt_t begins with yk_loss_cfg_ex_t's fields");
+
+extern "C" int yk_yolo_loss_opt(const yk_loss_cfg_opt_t *cfg, const float *d_y_true, const float *d_y_pred, int batch, float *d_loss,
+                                float *d_grad, float *d_ignore, float *d_counts, void *stream) {
+    yk_loss_cfg_ex_t ex;
+    if (cfg) memcpy(&ex, cfg, sizeof(ex));
+    return loss_launch("yk_yolo_loss_opt", cfg ? &ex : nullptr, cfg, 7, d_y_true, d_y_pred, batch, d_loss, d_grad, d_ignore, d_counts, stream);
 }

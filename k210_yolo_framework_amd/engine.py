@@ -66,6 +66,12 @@ class LossCfgEx(C.Structure):
     _fields_ = LossCfg._fields_ + [('box_loss', C.c_int32), ('box_weight', C.c_float)]
 
 
+class LossCfgOpt(C.Structure):
+    """yk_loss_cfg_opt_t"""
+    _fields_ = LossCfgEx._fields_ + [('focal', C.c_int32), ('focal_gamma', C.c_float), ('focal_alpha', C.c_float),
+                                     ('label_smooth', C.c_float), ('obj_target', C.c_int32)]
+
+
 BOX_LOSSES = {'mse': 0, 'giou': 1, 'diou': 2, 'ciou': 3}      # YK_BOX_LOSS_* (include/yolo_hip.h)
 
 
@@ -480,23 +486,33 @@ def region_batched(inp, W: int, H: int, A: int, Cn: int, anchor, threshold: floa
 
 
 def yolo_loss(y_true, y_pred, anchors_l, obj_thresh, iou_thresh, obj_weight, noobj_weight, wh_weight, batch_size=None,
-              counts=None, want_grad=True, want_ignore=False, stream=None, box_loss='mse', box_weight=1.0):
+              counts=None, want_grad=True, want_ignore=False, stream=None, box_loss='mse', box_weight=1.0, focal='off', focal_gamma=2.0,
+              focal_alpha=0.0, label_smooth=0.0, obj_target='label'):
     """tools/utils.py:741-791 loss_fn + custom.py metrics for one layer on the GPU.
     y_true / y_pred: cuda fp32 [B,h,w,A,5+C].  -> (loss[6] = total,xy,wh,obj,noobj,cls ; grad | None ; ignore | None).
     `counts` (cuda fp32 [3], running tp/fp/fn) is updated in place when given.
     box_loss 'giou' | 'diou' | 'ciou' (DESIGN.md 3.14): the IoU-family box term, weighted by box_weight, in place of xy and wh (both then
-    0); -> loss[7] = total,xy,wh,obj,noobj,cls,box (yk_yolo_loss_ex)."""
+    0); -> loss[7] = total,xy,wh,obj,noobj,cls,box (yk_yolo_loss_ex).
+    focal 'obj' | 'cls' | 'all' with focal_gamma, focal_alpha; label_smooth; obj_target 'iou' (the rule is in lossopt.py):
+    options on the objectness and class terms; with one of them on the call is yk_yolo_loss_opt and -> loss[7] whatever the box loss; with
+    all of them off it is the call above."""
     import torch
+    from . import lossopt
     if box_loss not in BOX_LOSSES:
         raise ValueError(f'box_loss {box_loss!r}: choose one of ' + ', '.join(repr(k) for k in BOX_LOSSES))
+    o = lossopt.validate(focal, focal_gamma, focal_alpha, label_smooth, obj_target)
     require_gpu()
     assert y_true.is_cuda and y_pred.is_cuda and y_true.shape == y_pred.shape and y_pred.dtype == torch.float32
     y_true, y_pred = y_true.contiguous(), y_pred.contiguous()
     B, h, w, A, E = y_pred.shape
-    ex = box_loss != 'mse'
-    cfg = LossCfgEx() if ex else LossCfg()
+    opt = not lossopt.is_off(**o)
+    ex = opt or box_loss != 'mse'
+    cfg = LossCfgOpt() if opt else LossCfgEx() if ex else LossCfg()
     if ex:
         cfg.box_loss, cfg.box_weight = BOX_LOSSES[box_loss], box_weight
+    if opt:
+        cfg.focal, cfg.focal_gamma, cfg.focal_alpha = lossopt.FOCAL[o['focal']], o['focal_gamma'], o['focal_alpha']
+        cfg.label_smooth, cfg.obj_target = o['label_smooth'], lossopt.OBJ_TARGETS[o['obj_target']]
     cfg.out_h, cfg.out_w, cfg.anchor_num, cfg.class_num = h, w, A, E - 5
     for n, (aw, ah) in enumerate(np.asarray(anchors_l, np.float32)):
         cfg.anchors[n][0], cfg.anchors[n][1] = float(aw), float(ah)
@@ -506,7 +522,7 @@ def yolo_loss(y_true, y_pred, anchors_l, obj_thresh, iou_thresh, obj_weight, noo
     loss = torch.empty(7 if ex else 6, dtype=torch.float32, device=y_pred.device)
     grad = torch.empty_like(y_pred) if want_grad else None
     ign = torch.empty((B, h, w, A), dtype=torch.float32, device=y_pred.device) if want_ignore else None
-    call('yk_yolo_loss_ex' if ex else 'yk_yolo_loss', C.byref(cfg), y_true, y_pred, B, loss, grad, ign, counts, _stream(stream))
+    call('yk_yolo_loss_opt' if opt else 'yk_yolo_loss_ex' if ex else 'yk_yolo_loss', C.byref(cfg), y_true, y_pred, B, loss, grad, ign, counts, _stream(stream))
     return loss, grad, ign
 
 

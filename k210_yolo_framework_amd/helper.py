@@ -419,19 +419,24 @@ def calc_ignore_mask(t_xy_A, t_wh_A, p_xy, p_wh, obj_mask, iou_thresh: float, la
 
 # ---- loss / metrics (tools/utils.py:708-793, tools/custom.py:13-75): same names, GPU arithmetic ---------------
 def create_loss_fn(h: Helper, obj_thresh: float, iou_thresh: float, obj_weight: float, noobj_weight: float,
-                   wh_weight: float, layer: int, box_loss: str = 'mse', box_weight: float = 1.0):
+                   wh_weight: float, layer: int, box_loss: str = 'mse', box_weight: float = 1.0, focal: str = 'off', focal_gamma: float = 2.0,
+                   focal_alpha: float = 0.0, label_smooth: float = 0.0, obj_target: str = 'label'):
     """tools/utils.py:708-793.  Returns loss_fn(y_true, y_pred) -> scalar loss (cuda tensor); the five terms, the
     gradient dL/dy_pred and the ignore mask of the last call are kept on the function object
     (`loss_fn.terms`, `loss_fn.grad`).  y_* are cuda fp32 tensors [B,h,w,A,5+C]; all arithmetic is in
     libyolo_hip.so (yk_yolo_loss).  box_loss 'giou' | 'diou' | 'ciou' (not in the reference): the IoU-family box term
-    weighted by box_weight in place of xy and wh, `loss_fn.terms` then has a seventh entry, box (yk_yolo_loss_ex)."""
-    from . import engine
+    weighted by box_weight in place of xy and wh, `loss_fn.terms` then has a seventh entry, box (yk_yolo_loss_ex).  focal, focal_gamma,
+    focal_alpha, label_smooth, obj_target (not in the reference; DESIGN.md 3.25, lossopt.py): focal loss, label smoothing and the IoU
+    objectness target; with one of them on `loss_fn.terms` has seven entries as well (yk_yolo_loss_opt)."""
+    from . import engine, lossopt
     if box_loss not in engine.BOX_LOSSES:
         raise ValueError(f'box_loss {box_loss!r}: choose one of ' + ', '.join(repr(k) for k in engine.BOX_LOSSES))
+    opts = lossopt.validate(focal, focal_gamma, focal_alpha, label_smooth, obj_target)
 
     def loss_fn(y_true, y_pred):
         loss, grad, _ = engine.yolo_loss(y_true, y_pred, h.anchors[layer], obj_thresh, iou_thresh, obj_weight,
-                                         noobj_weight, wh_weight, batch_size=h.batch_size, box_loss=box_loss, box_weight=box_weight)
+                                         noobj_weight, wh_weight, batch_size=h.batch_size, box_loss=box_loss, box_weight=box_weight,
+                                         **opts)
         loss_fn.terms, loss_fn.grad = loss, grad
         return loss[0]
     loss_fn.terms = loss_fn.grad = None

@@ -24,6 +24,10 @@ IoU box losses: `Trainer(box_loss='giou' | 'diou' | 'ciou', box
 by the IoU-family term of csrc/yk_loss.hip (yk_yolo_loss_ex).  Both live in `tr.hyper`, so they are part of the captured step and of its key,
 and the validation pass uses the same loss.  With box_loss='mse' the step calls yk_yolo_loss as before.
 
+Focal loss, label smoothing, IoU objectness target (lossopt.py): `Trainer(focal='obj' | 'cls' | 'all', focal_gamma=, focal_alpha=,
+label_smooth=, obj_target='iou')` change the objectness and class terms inside the same loss kernel (yk_yolo_loss_opt).  They live in
+`tr.hyper` like the box loss.  With all of them off the step calls yk_yolo_loss / yk_yolo_loss_ex as before.
+
 Knowledge distillation (distill.py): `Trainer(distill=DistillConfig(teacher_spec, teacher_weights, weight))` runs the teacher as an
 inference plan (engine.Plan, f16x2) on the step's frames, outside the captured graph, copies its raw outputs into static buffers, and adds
 one yk_distill_loss_f32 call per output layer (csrc/yk_distill.hip) into that layer's gradient between the detection loss and the backward
@@ -74,8 +78,11 @@ class Trainer:
                  obj_thresh: float = 0.7, iou_thresh: float = 0.5, obj_weight: float = 1.0, noobj_weight: float = 1.0,
                  wh_weight: float = 1.0, lr: float = 5e-4, decay: float = 0.0, device: int = 0, process_group=None,
                  world_size: int = 1, use_graph: bool = True, prune=None, qat=None, box_loss: str = 'mse', box_weight: float = 1.0,
-                 distill=None, ema=None, clip_norm: float = 0.0, lr_schedule=None):
+                 distill=None, ema=None, clip_norm: float = 0.0, lr_schedule=None, focal: str = 'off', focal_gamma: float = 2.0,
+                 focal_alpha: float = 0.0, label_smooth: float = 0.0, obj_target: str = 'label'):
         import torch
+        from . import lossopt
+        loss_opts = lossopt.validate(focal, focal_gamma, focal_alpha, label_smooth, obj_target)
         if box_loss not in engine.BOX_LOSSES:
             raise ValueError(f'box_loss {box_loss!r}: choose one of ' + ', '.join(repr(k) for k in engine.BOX_LOSSES))
         if ema is not None and qat is not None:
@@ -91,7 +98,7 @@ class Trainer:
         self.dev = torch.device('cuda', device)
         self.anchors = np.asarray(anchors, np.float32)
         self.hyper = dict(obj_thresh=obj_thresh, iou_thresh=iou_thresh, obj_weight=obj_weight, noobj_weight=noobj_weight,
-                          wh_weight=wh_weight, box_loss=box_loss, box_weight=box_weight)
+                          wh_weight=wh_weight, box_loss=box_loss, box_weight=box_weight, **loss_opts)
         self.lr, self.decay, self.iterations = float(lr), float(decay), 0
         self.pg, self.world = process_group, int(world_size)
         self.lay = {l.name: l for l in spec.layers}

@@ -27,6 +27,11 @@ with fewer batches is observed whole and training starts with epoch 1); afterwar
 `--box_weight`, in place of the xy and wh terms, in the training step and in the validation loss alike; the step line and the epoch line
 then name the box term.  The default `mse` is the reference's loss.
 
+`--focal obj | cls | all` with `--focal_gamma`, `--focal_alpha`, `--label_smooth` and `--obj_target iou` (`make train FOCAL=all FOCALGAMMA=2.0
+FOCALALPHA=0.25 LABELSMOOTH=0.1 OBJTARGET=iou`; not in the reference, lossopt.py): focal loss on the objectness and / or class
+terms, smoothed class targets, and the IoU of the predicted box as the objectness target of an object cell, in the training step and in the
+validation loss alike.  One line at the start names the options in force; with all of them off (the default) nothing changes.
+
 `--mosaic True` (`make train MOSAIC=True MOSAICPROB=1.0 MOSAICOFF=0`; not in the reference, mosaic.py): a share `--mosaic_prob`
 of the training samples is composed of four pictures of the training list by one HIP launch per batch (`InputPipeline(mosaic=...)`), draws keyed
 by (rand_seed, epoch, row); with `--augmenter True` the augmentation acts on the mosaic.  The last `--mosaic_off_epochs` epochs train on plain
@@ -151,9 +156,14 @@ def main(args, train_set, class_num, pre_ckpt, model_def, depth_multiplier, is_a
          box_loss='mse', box_weight=1.0, is_mosaic='False', mosaic_prob=1.0, mosaic_off_epochs=0, is_hsv='False', hsv_hue=0.1, hsv_sat=1.5,
          hsv_exposure=1.5, hsv_prob=1.0, teacher_ckpt='', teacher_def=None, teacher_depth=None, distill_weight=1.0, cache='off',
          cache_gb=8.0, cache_stage_mb=256, decode='pil', is_ema='False', ema_decay=0.9999, ema_tau=2000.0, clip_norm=0.0, lr_schedule='none',
-         warmup_steps=0, lr_final=0.01):
+         warmup_steps=0, lr_final=0.01, focal='off', focal_gamma=2.0, focal_alpha=0.0, label_smooth=0.0, obj_target='label'):
     import torch
+    from . import lossopt
     from .train import Trainer
+    try:
+        loss_opts = lossopt.validate(focal, focal_gamma, focal_alpha, label_smooth, obj_target)
+    except ValueError as e:
+        raise engine.YkError(f'--focal / --focal_gamma / --focal_alpha / --label_smooth / --obj_target: {e}') from e
     prune = is_prune == 'True'
     qat = is_qat == 'True'
     if qat and int(qat_observe) < 1:
@@ -295,10 +305,12 @@ def main(args, train_set, class_num, pre_ckpt, model_def, depth_multiplier, is_a
         raise engine.YkError(f'--ema_decay / --ema_tau / --lr_schedule / --warmup_steps / --lr_final: {e}') from e
     if rank == 0 and (ema or scheduled or float(clip_norm)):
         print(INFO, f'ema is {ema_cfg}, clip_norm {float(clip_norm)}, lr schedule {lr_cfg}')
+    if rank == 0 and not lossopt.is_off(**loss_opts):
+        print(INFO, f'loss options: {lossopt.describe(**loss_opts)}')
     tr = Trainer(spec, weights, h.anchors, per_rank, obj_thresh=obj_thresh, iou_thresh=iou_thresh, obj_weight=obj_weight,
                  noobj_weight=noobj_weight, wh_weight=wh_weight, lr=init_learning_rate, decay=learning_rate_decay_factor, device=local,
                  world_size=world, prune=schedule, qat=qat_cfg, box_loss=box_loss, box_weight=box_weight, distill=distill_cfg,
-                 ema=ema_cfg, clip_norm=float(clip_norm), lr_schedule=lr_cfg)
+                 ema=ema_cfg, clip_norm=float(clip_norm), lr_schedule=lr_cfg, **loss_opts)
     from .mosaic import MosaicConfig
     from .pipeline import InputPipeline
     if rank == 0:
@@ -528,6 +540,13 @@ def parser() -> argparse.ArgumentParser:
                    help='learning-rate schedule over the whole run, from --init_learning_rate; none = Keras lr / (1 + decay t) as before')
     p.add_argument('--warmup_steps', type=int, default=0, help='linear warmup over the first N steps (with --lr_schedule)')
     p.add_argument('--lr_final', type=float, default=0.01, help='cosine: the last learning rate as a fraction of the first')
+    p.add_argument('--focal', type=str, choices=['off', 'obj', 'cls', 'all'], default='off',
+                   help='focal loss on the objectness (obj + noobj) and / or the class term (DESIGN.md 3.25)')
+    p.add_argument('--focal_gamma', type=float, default=2.0, help='focal exponent: 0 or 1 to 5')
+    p.add_argument('--focal_alpha', type=float, default=0.0, help='focal balance inside (0, 1); 0 = off')
+    p.add_argument('--label_smooth', type=float, default=0.0, help='class targets z -> z (1 - eps) + eps / 2, eps in [0, 1); 0 = off')
+    p.add_argument('--obj_target', type=str, choices=['label', 'iou'], default='label',
+                   help="iou: an object cell's objectness target is the IoU of its predicted box with the label box")
     return p
 
 
@@ -540,7 +559,7 @@ def cli(argv=None):
                 a.qat, a.qat_momentum, a.qat_observe, a.val_map, a.val_map_obj, a.box_loss, a.box_weight, a.mosaic, a.mosaic_prob,
                 a.mosaic_off_epochs, a.hsv, a.hsv_hue, a.hsv_sat, a.hsv_exposure, a.hsv_prob, a.teacher_ckpt, a.teacher_def, a.teacher_depth,
                 a.distill_weight, a.cache, a.cache_gb, a.cache_stage_mb, a.decode, a.ema, a.ema_decay, a.ema_tau, a.clip_norm, a.lr_schedule,
-                a.warmup_steps, a.lr_final)
+                a.warmup_steps, a.lr_final, a.focal, a.focal_gamma, a.focal_alpha, a.label_smooth, a.obj_target)
 
 
 if __name__ == '__main__':
