@@ -37,6 +37,9 @@
 #                    [BIASCORRECT=True]: per-channel bias correction after the calibration (k210_yolo_framework_amd/biascorrect.py): on the same
 #                    images, one KPU-exact statistics pass per conv layer finds the integer to add to every channel's bn_add so that its mean
 #                    pre-activation equals the float network's (not with RANGES=: it needs frames; default off)
+#                    [ADAROUND=True ADAITERS=1000 ADALAMBDA=0.01 ADALR=0.01]: adaptive weight rounding after the calibration and before the bias
+#                    correction (k210_yolo_framework_amd/adaround.py): every kernel weight takes its lower or upper code so that each output
+#                    channel's error over the calibration images falls (not with RANGES=: it needs frames; default off)
 #   make eval        CKPT=yolo_model.h5|yolo.kmodel [PRECISION=f16x2|f16|kpu] [ANN=data/voc_img_ann.npy | SYNTHETIC=256] [EVALOBJ=0.05] [VOC07=True]:
 #                    VOC mAP of the checkpoint, network and metric on the GPU; prints the per-class AP table, writes eval.json beside CKPT
 #                    [METRIC=coco]: also the COCO-style AP (IoU .50:.95, AP50, AP75, small / medium / large, AR) and a `coco` object in eval.json
@@ -154,6 +157,10 @@ CALIBBINS     ?= 2048
 EQUALIZE      ?= False
 EQMAXGAIN     ?= 64
 BIASCORRECT   ?= False
+ADAROUND      ?= False
+ADAITERS      ?= 1000
+ADALAMBDA     ?= 0.01
+ADALR         ?= 0.01
 GPUS          ?= 1
 # anchors only (reference Makefile:27-29)
 ANCNUM        ?= 3
@@ -214,7 +221,7 @@ train:
 kmodel:
 	$(PY) make_kmodel.py $(CKPT) $(OUT) --train_set $(DATASET) --class_num $(CLSNUM) --model_def $(MODEL) --depth_multiplier $(DEPTHMUL) \
 		--image_size $(IMGSIZE) --output_size $(OUTSIZE) $(if $(RANGES),--ranges $(RANGES),$(if $(filter-out 0,$(SYNTHETIC)),--synthetic $(SYNTHETIC),--calib $(CALIB))) \
-		$(if $(CALIBMETHOD),--calib_method $(CALIBMETHOD) --calib_percentile $(CALIBPCT) --calib_bins $(CALIBBINS))$(if $(filter True,$(EQUALIZE)), --equalize True --equalize_max_gain $(EQMAXGAIN))$(if $(filter True,$(BIASCORRECT)), --bias_correct True)
+		$(if $(CALIBMETHOD),--calib_method $(CALIBMETHOD) --calib_percentile $(CALIBPCT) --calib_bins $(CALIBBINS))$(if $(filter True,$(EQUALIZE)), --equalize True --equalize_max_gain $(EQMAXGAIN))$(if $(filter True,$(BIASCORRECT)), --bias_correct True)$(if $(filter True,$(ADAROUND)), --adaround True --adaround_iters $(ADAITERS) --adaround_lambda $(ADALAMBDA) --adaround_lr $(ADALR))
 
 # VOC mAP of CKPT (.h5 / .npz, or .kmodel / .kfpkg with PRECISION=kpu) on the validation head of ANN, or on SYNTHETIC=N generated images
 eval:

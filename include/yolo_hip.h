@@ -864,6 +864,35 @@ int yk_scale_act_chsum_f32(const float *z, long long M, int C, const float *scal
                            double *d_sum, uint32_t *d_flags, int slot0, double *d_work, void *stream);
 int yk_chsum_read(const double *d_sum, const uint32_t *d_flags, int n_slots, double *h_sum, int *h_flags);
 
+/* ---- adaptive weight rounding (adaround.py, which states the rule).  All calls are asynchronous on `stream`, allocate nothing
+ *      and do not synchronise; no floating-point atomics: the same calls give the same bits.  A NULL tensor or a non-positive size:
+ *      YK_ERR_ARG, checked on the host before anything is launched.
+ * yk_dw3x3_gram_f32        d_gram[c][i][j] += sum over (b, oy, ox) of x_i x_j, x_t = tap t = ky * 3 + kx of channel c at that output position
+ *                          (0 outside the image); x NHWC fp32, the geometry arguments of yk_dw3x3_fwd_f32.  d_gram is float64 [C][9][9], the
+ *                          FULL symmetric matrix (both halves are written, from the same sums).  Every product is exact in float64.  It ADDS,
+ *                          so batches accumulate; the caller zeroes d_gram.  Workgroups own chunks of rows (output positions) - YK_DWGRAM_ROWS
+ *                          each, more once there are over YK_DWGRAM_ROWS * YK_DWGRAM_MAX_CHUNKS rows - and leave 45 partials per channel in
+ *                          d_work (yk_dw3x3_gram_workspace_bytes, needs no device; 8-byte aligned; contents undefined before and after); a
+ *                          finishing launch adds the chunks in ascending order.  Who adds what follows from the shape alone.  Reads are
+ *                          coalesced along C.
+ * yk_adaround_step_f32     one Adam step (beta1 0.9, beta2 0.999, eps 1e-8, bias-corrected, step number t >= 1) on V [Co][K] of the loss
+ *                          (1 / Co) sum_c E_c / E_c(nearest) + lam (1 / n_free) sum (1 - |2 h - 1|^beta), h = clip(sigmoid(V) 1.2 - 0.1, 0, 1),
+ *                          whose gradient with respect to h is (2 s_w / Co) inv_e[c] P[c][k] - (2 lam beta / n_free) |2 h - 1|^(beta - 1)
+ *                          sign(2 h - 1), P = D G for the D of the V given.  Elements with frozen[i] != 0 keep V, m and v.  Writes the next
+ *                          D = s_w (h(V) - r), 0 at frozen elements.  One thread per element.
+ * yk_adaround_dw_quad_f32  P[c][i] = sum_j G[c][i][j] D[c][j] for a depthwise layer: G float64 [C][9][9] as yk_dw3x3_gram_f32 leaves it, D and P
+ *                          fp32 [C][9]; summed in float64, j ascending, rounded once.  (A dense layer's P = D G is yk_gemm_f32.)
+ * yk_adaround_rowerr_f64   E[c] = sum_k D[c][k] P[c][k], D and P fp32 [Co][K], E float64 [Co]: exact products, a fixed order. */
+#define YK_DWGRAM_ROWS 64
+#define YK_DWGRAM_MAX_CHUNKS 256
+int yk_dw3x3_gram_workspace_bytes(int B, int Ho, int Wo, int C, size_t *bytes);
+int yk_dw3x3_gram_f32(const float *x, int B, int Hi, int Wi, int C, int Ho, int Wo, int stride, int pad_t, int pad_l, double *d_gram,
+                      double *d_work, void *stream);
+int yk_adaround_step_f32(float *V, float *m, float *v, const float *r, const uint8_t *frozen, const float *P, const float *inv_e, float *D,
+                         int Co, int K, long long n_free, float s_w, float lam, float beta, float lr, int t, void *stream);
+int yk_adaround_dw_quad_f32(const double *G, const float *D, int C, float *P, void *stream);
+int yk_adaround_rowerr_f64(const float *D, const float *P, int Co, int K, double *E, void *stream);
+
 /* ---- histograms for the clipped calibrations (quantize.clip_range): a second pass over the calibration set, after the ranges.
  * d_hist holds uint64 counts [n_slots][nbins], 16 <= nbins <= 4096; d_flags one uint32 per slot.  A slot's bins are equal parts of [lo, hi],
  * the range of its tensor widened to contain 0; the caller passes lo and inv = (float)(nbins / ((double)hi - lo)), rounded once (0 for

@@ -93,12 +93,13 @@ def residuals(report: dict, float_means, measured) -> Dict[str, np.ndarray]:
 
 
 def correct(spec: ns.NetSpec, weights, ranges, float_means: Dict[str, Tuple[np.ndarray, int]],
-            measure: Callable[[km_.Kmodel], Dict[int, Tuple[np.ndarray, int]]]):
+            measure: Callable[[km_.Kmodel], Dict[int, Tuple[np.ndarray, int]]], weight_codes=None):
     """-> (delta {conv layer name: int64 [C]} for quantize.quantize(bn_add_delta=), report).  float_means: {conv layer name: (sum float64 [C],
     count)} of the float network's pre-activations (Calibrator.channel_means); measure: see the module's text.  report['layers'][name] =
     dict(before = the largest |mean z - T| in output codes before this layer's correction, delta_max = the largest |delta| in output codes,
     limited = [channels whose delta was limited]); report['passes'] = the number of measuring passes.  KmodelError when a layer's count
-    differs from the float side's (other frames, or another geometry)."""
+    differs from the float side's (other frames, or another geometry).  `weight_codes` (adaround.py) goes to every quantize call made here, so
+    the correction is measured on the weights the file will hold."""
     from . import quantize as qz
     delta: Dict[str, np.ndarray] = {}
     rep = {'layers': {}, 'passes': 0}
@@ -108,7 +109,7 @@ def correct(spec: ns.NetSpec, weights, ranges, float_means: Dict[str, Tuple[np.n
         name = op['layer']
         if name not in float_means:
             raise KmodelError(f'biascorrect: no float mean for conv {name!r}')
-        model, qrep = qz.quantize(spec, weights, ranges, delta)
+        model, qrep = qz.quantize(spec, weights, ranges, delta, weight_codes)
         r = qrep['layers'][name]
         p = int(r['fine_bits'])
         zsum, count = measure(model)[r['index']]

@@ -4,6 +4,7 @@
                           [--calib_method minmax|percentile|mse] [--calib_percentile P] [--calib_bins NB]
                           [--equalize True [--equalize_max_gain G]]
                           [--bias_correct True]
+                          [--adaround True [--adaround_iters N] [--adaround_lambda L] [--adaround_lr R]]
 
 CKPT: a Keras `.h5` or `.npz` checkpoint; OUT: `.kmodel` or `.kfpkg`.  The calibration images are a list file as make_voc_list.py writes
 (data/<set>_img_ann.npy) or N generated images as `make train SYNTHETIC=N` trains on; they are decoded as the input pipeline decodes them
@@ -19,7 +20,11 @@ pass over the images measures every conv output per channel, the weights are rew
 ranges belong to the unequalised weights.  The report names the gains of every layer.
 `--bias_correct True` (`make kmodel BIASCORRECT=True`): per-channel bias correction (biascorrect.py) after the calibration, on the same images -
 one more float pass and one KPU-exact statistics pass per conv layer find the integer to add to every channel's bn_add so that the kmodel's mean
-pre-activation equals the float network's.  Not with `--ranges`: it needs calibration frames.  The report gets one line per corrected layer."""
+pre-activation equals the float network's.  Not with `--ranges`: it needs calibration frames.  The report gets one line per corrected layer.
+`--adaround True` (`make kmodel ADAROUND=True ADAITERS=1000 ADALAMBDA=0.01 ADALR=0.01`): adaptive weight rounding (adaround.py) after the
+calibration and before the bias correction, on the same images - one more float pass builds every layer's input Gram matrix, then
+`--adaround_iters` Adam steps per layer on the GPU choose the lower or upper code of every weight.  Not with `--ranges`: it needs calibration
+frames.  The report gets one line per layer."""
 from __future__ import annotations
 
 import argparse
@@ -63,7 +68,8 @@ def load_ranges(path, spec):
 
 
 def main(ckpt, out, image_size, output_size, model_def, class_num, depth_multiplier, train_set, calib, synthetic, calib_seed, batch, limit=0,
-         ranges=None, method='minmax', percentile=99.99, bins=2048, equalize=False, max_gain=64.0, bias_correct=False):
+         ranges=None, method='minmax', percentile=99.99, bins=2048, equalize=False, max_gain=64.0, bias_correct=False,
+         adaround=False, ada_iters=1000, ada_lambda=0.01, ada_lr=1e-2):
     from pathlib import Path
     from . import quantize
     anchor_file = Path(f'data/{train_set}_anchor.npy')
@@ -87,10 +93,13 @@ def main(ckpt, out, image_size, output_size, model_def, class_num, depth_multipl
         eq = dict(equalize=True, max_gain=max_gain) if equalize else {}
         if bias_correct:
             eq['bias_correct'] = True
+        if adaround:
+            eq.update(adaround=True, ada_iters=ada_iters, ada_lambda=ada_lambda, ada_lr=ada_lr)
         report = model.save_kmodel(str(out), frames, batch=batch, method=method, percentile=percentile, bins=bins, **eq)
         print(quantize.format_report(report))
         print(INFO, f' {len(frames)} calibration images{"" if method == "minmax" else f", {method} ranges from {bins}-bin histograms"}'
                     f'{f", channel ranges equalised first (max gain {max_gain:g}, one more pass)" if equalize else ""}'
+                    f'{f", weights rounded adaptively ({ada_iters} steps per layer)" if adaround else ""}'
                     f'{", channel biases corrected (one statistics pass per conv)" if bias_correct else ""}, {time.time() - t0:.2f} s')
     print(INFO, f' wrote {out}: kmodel of {report["file_bytes"]} bytes')
     return report
@@ -120,6 +129,11 @@ def cli(argv=None):
     p.add_argument('--equalize_max_gain', type=float, default=64.0, help='largest gain --equalize gives a channel, > 1')
     p.add_argument('--bias_correct', type=str, default=None, help='True: correct every channel\'s bn_add after the calibration so that its mean '
                                                                   'pre-activation equals the float network\'s (biascorrect.py); needs frames')
+    p.add_argument('--adaround', type=str, default=None, help='True: round every kernel weight down or up so that each output channel\'s error '
+                                                              'over the calibration frames falls (adaround.py); needs frames')
+    p.add_argument('--adaround_iters', type=int, default=1000, help='Adam steps per layer of --adaround')
+    p.add_argument('--adaround_lambda', type=float, default=0.01, help='weight of the rounding regulariser of --adaround')
+    p.add_argument('--adaround_lr', type=float, default=1e-2, help='Adam step size of --adaround')
     p.add_argument('pre_ckpt', type=str, help='trained weights (.h5 / .npz)')
     p.add_argument('output', type=str, help='.kmodel or .kfpkg to write')
     a = p.parse_args(sys.argv[1:] if argv is None else argv)
@@ -141,6 +155,14 @@ def cli(argv=None):
     bias_correct = a.bias_correct == 'True'
     if a.ranges and bias_correct:
         p.error('--bias_correct needs calibration frames: it cannot be combined with --ranges (QAT ranges, no frames)')
+    if a.adaround not in (None, 'True', 'False'):
+        p.error(f'--adaround {a.adaround}: True or False')
+    adaround = a.adaround == 'True'
+    if a.ranges and adaround:
+        p.error('--adaround needs calibration frames: it cannot be combined with --ranges (QAT ranges, no frames)')
+    if adaround and not (a.adaround_iters >= 0 and a.adaround_lambda >= 0.0 and a.adaround_lr > 0.0):
+        p.error(f'--adaround_iters {a.adaround_iters} and --adaround_lambda {a.adaround_lambda} must not be negative, --adaround_lr '
+                f'{a.adaround_lr} must be positive')
     method = a.calib_method or 'minmax'
     if method not in ('minmax', 'percentile', 'mse'):
         p.error(f'--calib_method {method}: one of minmax, percentile, mse')
@@ -150,7 +172,7 @@ def cli(argv=None):
         p.error(f'--calib_bins {a.calib_bins} outside 16..4096')
     return main(a.pre_ckpt, a.output, a.image_size, a.output_size, a.model_def, a.class_num, a.depth_multiplier, a.train_set, a.calib,
                 a.synthetic, a.calib_seed, a.calib_batch, a.calib_limit, a.ranges, method, a.calib_percentile, a.calib_bins, equalize,
-                a.equalize_max_gain, bias_correct)
+                a.equalize_max_gain, bias_correct, adaround, a.adaround_iters, a.adaround_lambda, a.adaround_lr)
 
 
 if __name__ == '__main__':

@@ -166,16 +166,23 @@ def _act_table(act: int, alpha: float, zp_y: int, p: int):
 
 
 def quantize(spec: ns.NetSpec, weights: Dict[str, np.ndarray], ranges: Dict[str, Tuple[float, float]],
-             bn_add_delta: Optional[Dict[str, np.ndarray]] = None):
+             bn_add_delta: Optional[Dict[str, np.ndarray]] = None, weight_codes: Optional[Dict[str, np.ndarray]] = None):
     """-> (kmodel.Kmodel, report).  `ranges`: {tensor name (tensor_names): (min, max)} of the calibration set, at least for the input-side
     of every conv ('input' is fixed to the raw pixel and need not be given; upsample / concat outputs take their producers' ranges).
     report['layers'][name] = scales, zero points, FINE_BITS used, the BatchNorm shifts chosen, the share of weights equal to the zero
     point and the smallest non-zero |bn_mul| (what equalize.py's step A lowers for an amplified consumer).  CPU only, deterministic.
     `bn_add_delta` (bias correction, biascorrect.py): {conv layer name: int64 [C]} added to that layer's bn_add after its rounding, which
     moves every pre-activation z of channel c by exactly that many 2^-p output steps; None or {} changes nothing.  The report of a corrected
-    layer gains `bias_delta_max` (the largest |delta| in output codes, |delta| / 2^p) and `bias_limited` (filled in by biascorrect.correct)."""
+    layer gains `bias_delta_max` (the largest |delta| in output codes, |delta| / 2^p) and `bias_limited` (filled in by biascorrect.correct).
+    `weight_codes` (adaptive rounding, adaround.py): {conv layer name: uint8 array of the kernel's shape} used in place of the nearest codes;
+    every code must be the down code floor(kern / s_w) + zp_w or the up code, one above (both clipped to 0..255), of its weight; None or {}
+    changes nothing.  `zero_share` is computed from the codes used."""
     plan = plan_convs(spec)
     bn_add_delta = dict(bn_add_delta or {})
+    weight_codes = dict(weight_codes or {})
+    unknown = sorted(set(weight_codes) - {op['layer'] for op in spec.ops if op['type'] in (ns.OP_CONV, ns.OP_DWCONV)})
+    if unknown:
+        raise KmodelError(f'quantize: weight_codes names layer(s) {", ".join(map(repr, unknown))}, which are not conv layers of {spec.name}')
     unknown = sorted(set(bn_add_delta) - {op['layer'] for op in spec.ops if op['type'] in (ns.OP_CONV, ns.OP_DWCONV)})
     if unknown:
         raise KmodelError(f'quantize: bn_add_delta names layer(s) {", ".join(map(repr, unknown))}, which are not conv layers of {spec.name}')
@@ -221,7 +228,17 @@ def quantize(spec: ns.NetSpec, weights: Dict[str, np.ndarray], ranges: Dict[str,
             s_x, zp_x = q[tin]
             kern = np.asarray(weights[l.name + '/kernel'], np.float64)
             s_w, zp_w = qparams(kern.min(), kern.max())
-            wq = np.clip(np.rint(kern / s_w) + zp_w, 0, 255).astype(np.uint8)
+            if l.name in weight_codes:
+                wq = np.asarray(weight_codes[l.name])
+                down = np.floor(kern / s_w) + zp_w
+                if wq.shape != kern.shape or wq.dtype != np.uint8:
+                    raise KmodelError(f'quantize: weight_codes of conv {l.name!r} is {wq.dtype} {wq.shape}, uint8 {kern.shape} expected')
+                off = (wq != np.clip(down, 0, 255)) & (wq != np.clip(down + 1, 0, 255))
+                if off.any():
+                    raise KmodelError(f'quantize: weight_codes of conv {l.name!r}: {int(off.sum())} code(s) are neither the down nor the up code '
+                                      f'of their weight (the first at {tuple(int(v) for v in np.argwhere(off)[0])})')
+            else:
+                wq = np.clip(np.rint(kern / s_w) + zp_w, 0, 255).astype(np.uint8)
             wq = (wq[..., 0].transpose(2, 0, 1).reshape(co, 1, kk) if dw else wq.transpose(3, 2, 0, 1).reshape(co, ci, kk))
             lo, hi = (float(v) for v in ranges[l.name])
             s_y, zp_y = qparams(lo, hi)
@@ -333,6 +350,9 @@ def format_report(report: dict) -> str:
     if report.get('equalize'):
         from . import equalize
         rows.append(equalize.format_report(report['equalize']))
+    if report.get('adaround'):
+        from . import adaround
+        rows.append(adaround.format_report(report['adaround']))
     if report.get('biascorrect'):
         from . import biascorrect
         rows.append(biascorrect.format_report(report['biascorrect']))

@@ -116,7 +116,8 @@ class YoloModel:
             np.savez(path, **self._s['weights'])
 
     def save_kmodel(self, path: str, calibration_frames, batch: int = 32, method: str = 'minmax', percentile: float = 99.99, bins: int = 2048,
-                    equalize: bool = False, max_gain: float = 64.0, bias_correct: bool = False):
+                    equalize: bool = False, max_gain: float = 64.0, bias_correct: bool = False, adaround: bool = False, ada_iters: int = 1000,
+                    ada_lambda: float = 0.01, ada_lr: float = 1e-2):
         """Quantise these weights to a K210 kmodel (quantize.py) and write it: `.kmodel`, or `.kfpkg` (model + flash list, no
         firmware).  calibration_frames: uint8 [N, H, W, 3] at the network's input size (host numpy or a device tensor); their tensor ranges
         are measured on the GPU in batches of `batch`, from the raw pixels / 255 as the KPU sees them.  The new Kmodel is kept beside the
@@ -131,7 +132,11 @@ class YoloModel:
         bias_correct=True (biascorrect.py) then removes the systematic error the chosen ranges leave: on the same frames, one more float pass
         sums every channel's pre-activation (Calibrator.feed_means), and one KPU-exact statistics pass PER CONV (KpuPlan.run_stats_u8) finds the
         integer to add to each channel's bn_add so that its mean pre-activation equals the float network's within 2^-(p + 1) of a code;
-        report['biascorrect'] lists the layers.  Order: equalise, calibrate, bias-correct, write."""
+        report['biascorrect'] lists the layers.
+        adaround=True (adaround.py) chooses, after the calibration and on the same frames, for every kernel weight the lower or the upper of its
+        two neighbouring codes so that each output channel's error over the frames falls (`ada_iters` Adam steps per layer on the GPU, rounding
+        regulariser `ada_lambda`, step `ada_lr`); no row ends worse than nearest rounding in that objective; report['adaround'] lists the layers.
+        Order: equalise, calibrate, adaround, bias-correct, write."""
         import torch
         from . import engine, kmodel, quantize
         try:
@@ -153,12 +158,17 @@ class YoloModel:
                 raise engine.YkError(f'save_kmodel: {e}') from e
         ranges = quantize.calibrate(self.spec, weights, frames, batch, method, percentile, bins, clipped)
         try:
-            delta, bc_report = None, None
+            delta, bc_report, codes, ada_report = None, None, None, None
+            if adaround:
+                from . import adaround as ada
+                codes, ada_report = ada.gpu_optimise(self.spec, weights, frames, batch, ada_iters, ada_lambda, ada_lr)
             if bias_correct:
                 from . import biascorrect
                 delta, bc_report = biascorrect.correct(self.spec, weights, ranges, quantize.calibrate_means(self.spec, weights, frames, batch),
-                                                       biascorrect.gpu_measure(frames, batch))
-            km, report = quantize.quantize(self.spec, weights, ranges, delta)
+                                                       biascorrect.gpu_measure(frames, batch), codes)
+            km, report = quantize.quantize(self.spec, weights, ranges, delta, codes)
+            if ada_report is not None:
+                report['adaround'] = ada_report
             if bc_report is not None:
                 report['biascorrect'] = bc_report
                 for name, r in bc_report['layers'].items():
