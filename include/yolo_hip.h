@@ -769,17 +769,24 @@ int yk_adam_ex_f32(long long n, float *p, const float *g, float *m, float *v, fl
                    long long iterations, float beta1, float beta2, float eps, float grad_scale, float clip_norm, float ema_omd, void *stream);
 int yk_ema_f32(long long n, const float *src, float *ema, float ema_omd, void *stream);
 /* Magnitude pruning (tfmot prune_low_magnitude of keras_train.py:59-71) over `nseg` segments of one flat parameter buffer
- * in one call.  Segment s = params[d_offset[s] .. + d_size[s]) (device, int64; d_size >= 1); d_keep[s] = k, clamped to [1, d_size[s]].
+ * in one call.  Segment s = params[d_offset[s] .. + d_size[s]) (device, int64; d_size >= 0); d_keep[s] = k, any int64, clamped to
+ * [1, d_size[s]] (0, a negative k: 1; k > d_size: d_size).
  * Outputs per segment: d_threshold[s] = the exact k-th largest |w| (a radix select on the uint32 pattern of |w|: equal to a sort),
  * mask[d_offset[s] + e] = |w| >= threshold (1 / 0; ties at the threshold are all kept; bytes outside the segments are not written),
- * d_kept[s] = number of mask bytes set.  Workgroups own tiles of YK_PRUNE_TILE elements of one segment: d_tile_first [nseg + 1] (device,
+ * d_kept[s] = number of mask bytes set.  "Largest" and ">=" are those of the sign-cleared bit pattern as an unsigned integer: -0.0 equals
+ * +0.0, denormals order like any number, and a NaN ranks above infinity (among NaNs the payload decides); d_threshold[s] carries that
+ * pattern, payload included.  A segment of size 0 gets no output: d_threshold[s], d_kept[s] and every mask byte keep what the caller
+ * left there, it owns no tile (d_tile_first[s] == d_tile_first[s + 1]) and it changes nothing for the other segments; at least one
+ * segment must have a tile.  Workgroups own tiles of YK_PRUNE_TILE elements of one segment: d_tile_first [nseg + 1] (device,
  * int32) = running sum of ceil(d_size / YK_PRUNE_TILE), ntiles = d_tile_first[nseg].  Integer atomics only: bitwise reproducible.
- * The call itself does not synchronise with the host; capturable once the stream's scratch has its size (one eager call). */
+ * The call itself does not synchronise with the host; capturable once the stream's scratch has its size (one eager call); the clear of
+ * the histograms is part of the recording.  A NULL pointer, nseg <= 0 or ntiles <= 0: YK_ERR_ARG, nothing launched. */
 #define YK_PRUNE_TILE 4096
 int yk_prune_tile(void); /* YK_PRUNE_TILE of the loaded library: callers that build d_tile_first without this header ask here */
 int yk_prune_masks_f32(const float *params, const long long *d_offset, const long long *d_size, const long long *d_keep,
                        const int *d_tile_first, int nseg, int ntiles, uint8_t *mask, float *d_threshold, long long *d_kept, void *stream);
-/* params[i] = mask[i] ? params[i] : +0.0f over n elements */
+/* params[i] = mask[i] ? params[i] : +0.0f over n elements: any non-zero byte keeps, and a kept element keeps its bits (-0.0, a NaN's
+ * payload).  Any alignment of either pointer; nothing outside [0, n) is written.  A NULL pointer or n <= 0: YK_ERR_ARG, nothing launched. */
 int yk_mask_apply_f32(float *params, const uint8_t *mask, long long n, void *stream);
 
 /* ---- KPU-exact mode: a kmodel v3 on the K210 KPU's integer arithmetic (kpu_load_kmodel / kpu_run_kmodel / kpu_get_output of

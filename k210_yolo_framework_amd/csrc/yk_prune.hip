@@ -2,7 +2,8 @@
 //
 // Per prunable segment (one Conv2D kernel) of the flat fp32 buffer: the exact k-th largest |w|, the mask |w| >= threshold and the
 // number of kept elements, for ALL segments in one call.  Everything is defined on the uint32 pattern of |w| (sign bit cleared), which
-// orders non-negative floats: -0.0, denormals and +-inf need no special case.
+// orders non-negative floats: -0.0, denormals and +-inf need no special case, and a NaN is a pattern above infinity's (top digit 127 too).
+// A segment of size 0 owns no tile; its pick workgroup reads an all-zero histogram, matches no bin and writes nothing.
 //
 // Selection = radix select, most significant digit first, four 8-bit digits of the pattern (shift 24, 16, 8, 0; the top digit only
 // reaches 127).  A pass is
@@ -32,6 +33,13 @@ __device__ __forceinline__ int prune_tile_segment(const prune_seg &S, int t) {
         else hi = mid;
     }
     return lo;
+}
+
+// Zeroes the four histograms of a call.  A kernel of the call's own and not a hipMemsetAsync: as a node of a recorded graph the runtime's fill
+// left other values than 0 in the histograms on a replay that followed unrelated launches (tests/test_gpu_prune_edges.py, the replay test).
+__global__ void __launch_bounds__(256) prune_clear_kernel(uint32_t *__restrict__ hist, size_t words) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < words) hist[i] = 0u;
 }
 
 __global__ void __launch_bounds__(256) prune_hist_kernel(prune_seg S, const float *__restrict__ P, int pass, const uint32_t *__restrict__ prefix,
@@ -117,7 +125,8 @@ extern "C" int yk_prune_masks_f32(const float *params, const long long *d_offset
     uint32_t *ws = (uint32_t *)yk_scratch(dev, stream, YK_SLOT_PRUNE, sizeof(uint32_t) * (hist_words + 2 * (size_t)nseg));
     if (!ws) return YK_ERR_NOMEM;
     uint32_t *prefix = ws + hist_words, *krem = prefix + nseg;
-    YK_HIP(hipMemsetAsync(ws, 0, sizeof(uint32_t) * hist_words, st));
+    hipLaunchKernelGGL(prune_clear_kernel, dim3((unsigned)(hist_words / 256)), dim3(256), 0, st, ws, hist_words);
+    YK_HIP(hipGetLastError());
     const prune_seg S{d_offset, d_size, d_keep, d_tile_first, nseg};
     for (int pass = 0; pass < 4; ++pass) {
         uint32_t *hist = ws + (size_t)pass * nseg * 256;
