@@ -239,12 +239,13 @@ def gpu_grams(spec: ns.NetSpec, weights, frames, batch: int = 32, max_gram_mb: f
     yk_dw3x3_gram_f32, a dense layer's one fp32 product X^T X per batch (yk_im2col3x3_f32 for 3x3, the tensor itself for 1x1, into yk_gemm_f32)
     added into the float64 accumulator.  `only`: a set of layer names (the others are not built)."""
     import ctypes as C
+    from types import SimpleNamespace
     import torch
     from . import engine
-    from .quantize import Calibrator
-    frames = frames if torch.is_tensor(frames) else torch.from_numpy(np.ascontiguousarray(frames))
+    from .quantize import Calibrator, device_batches
     batch = max(1, min(int(batch), len(frames)))
     cal = Calibrator(spec, weights, max_batch=batch)
+    convs_only = SimpleNamespace(conv=cal.range.conv, moved=lambda y, slot: None)      # a measure that leaves the moved tensors alone
     dev = cal.dev
     convs = [op for op in spec.ops if op['type'] in (ns.OP_CONV, ns.OP_DWCONV) and (only is None or op['layer'] in only)]
     G: Dict[str, "torch.Tensor"] = {}
@@ -257,11 +258,10 @@ def gpu_grams(spec: ns.NetSpec, weights, frames, batch: int = 32, max_gram_mb: f
         else:
             G[op['layer']] = torch.zeros(shape, dtype=torch.float64, device=dev)
     stream = lambda: torch.cuda.current_stream().cuda_stream                            # noqa: E731
-    for i in range(0, len(frames), batch):
-        fr = frames[i:i + batch].cuda()
+    for fr in device_batches(frames, batch):
         B = int(fr.shape[0])
         keep: Dict[str, "torch.Tensor"] = {}
-        cal._walk(fr, keep, cal._epilogue, lambda x, slot: None, 'adaround')           # the float network on frames / 255
+        cal.forward(fr, convs_only, keep, 'adaround')                                  # the float network on frames / 255
         for op in convs:
             name = op['layer']
             if name not in G:

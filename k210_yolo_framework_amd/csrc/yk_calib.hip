@@ -11,6 +11,10 @@
 // words of LDS, then ONE atomicMin and ONE atomicMax per workgroup (vector atomics on global memory), and an atomicOr only from a
 // workgroup that met a non-finite value.  The key, the accumulator and the workgroup fold live in yk_range.h (yk_qat.hip shares them).
 //
+// Every kernel that finishes a conv - y = act(z * scale + bias) - makes y in scale_act below, so all of them round y the same way; the
+// per-tensor ones are ONE template, tensor_kernel, over what takes y (the Range or the Hist sink), whether there is a z to finish, and
+// whether the accesses are 16 bytes wide.
+//
 // Per channel, for cross-layer equalisation (equalize.py): yk_scale_act_chrange_f32 stores the same y and folds channel c into slot
 // slot0 + c of such a buffer - a column reduction of [M][C] with lanes along the channels (scale_act_chrange_kernel below).
 //
@@ -35,62 +39,74 @@ __device__ __forceinline__ float c_act(float v, int act, float alpha) {      // 
     return v;
 }
 
-// n4 float4 + the scalar tail [4 * n4, n)
-__global__ __launch_bounds__(CAL_BLOCK) void range_kernel(const float *__restrict__ x, size_t n4, size_t n, uint32_t *slot) {
-    Acc a;
-    const size_t step = (size_t)gridDim.x * CAL_BLOCK;
-    const float4 *x4 = reinterpret_cast<const float4 *>(x);
-    for (size_t i = (size_t)blockIdx.x * CAL_BLOCK + threadIdx.x; i < n4; i += step) {
-        const float4 v = x4[i];
-        a.add(v.x);
-        a.add(v.y);
-        a.add(v.z);
-        a.add(v.w);
+// item i of V = 1 or 4 floats (V = 4: one 16-byte access, so p + 4 * i is 16-byte aligned)
+template <int V>
+__device__ __forceinline__ void load_v(const float *__restrict__ p, size_t i, float (&v)[V]) {
+    if constexpr (V == 4) {
+        const float4 q = reinterpret_cast<const float4 *>(p)[i];
+        v[0] = q.x, v[1] = q.y, v[2] = q.z, v[3] = q.w;
+    } else {
+        v[0] = p[i];
     }
-    for (size_t i = 4 * n4 + (size_t)blockIdx.x * CAL_BLOCK + threadIdx.x; i < n; i += step) a.add(x[i]);
-    fold(a, slot);
 }
 
-// C % 4 == 0, all pointers 16-byte aligned: element 4 * i starts at channel (4 * i) % C and the four share one row
-__global__ __launch_bounds__(CAL_BLOCK) void scale_act_range_vec_kernel(const float *__restrict__ z, size_t n4, int C, const float *__restrict__ scale,
-                                                                         const float *__restrict__ bias, int act, float alpha, float *__restrict__ y,
-                                                                         uint32_t *slot) {
-    Acc a;
-    const size_t step = (size_t)gridDim.x * CAL_BLOCK;
-    const float4 *z4 = reinterpret_cast<const float4 *>(z);
-    float4 *y4 = reinterpret_cast<float4 *>(y);
-    const size_t c4 = (size_t)(C / 4);
-    for (size_t i = (size_t)blockIdx.x * CAL_BLOCK + threadIdx.x; i < n4; i += step) {
-        const size_t c = (i % c4) * 4;
-        const float4 v = z4[i];
-        const float4 s = *reinterpret_cast<const float4 *>(scale + c);
-        const float4 b = *reinterpret_cast<const float4 *>(bias + c);
-        float4 r;
-        r.x = c_act(v.x * s.x + b.x, act, alpha);
-        r.y = c_act(v.y * s.y + b.y, act, alpha);
-        r.z = c_act(v.z * s.z + b.z, act, alpha);
-        r.w = c_act(v.w * s.w + b.w, act, alpha);
-        y4[i] = r;
-        a.add(r.x);
-        a.add(r.y);
-        a.add(r.z);
-        a.add(r.w);
+// THE epilogue of a conv: item i of z to item i of y, o = y = c_act(p), p = z * s + b the pre-activation (this unit compiles with
+// -ffp-contract=off: two roundings).  Every kernel below that makes a y makes it here.
+template <int V>
+__device__ __forceinline__ void scale_act(const float *__restrict__ z, float *__restrict__ y, size_t i, const float (&s)[V], const float (&b)[V],
+                                          int act, float alpha, float (&p)[V], float (&o)[V]) {
+    float v[V];
+    load_v<V>(z, i, v);
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+        p[j] = v[j] * s[j] + b[j];
+        o[j] = c_act(p[j], act, alpha);
     }
-    fold(a, slot);
+    if constexpr (V == 4)
+        reinterpret_cast<float4 *>(y)[i] = make_float4(o[0], o[1], o[2], o[3]);
+    else
+        y[i] = o[0];
 }
 
-__global__ __launch_bounds__(CAL_BLOCK) void scale_act_range_kernel(const float *__restrict__ z, size_t n, int C, const float *__restrict__ scale,
-                                                                     const float *__restrict__ bias, int act, float alpha, float *__restrict__ y,
-                                                                     uint32_t *slot) {
-    Acc a;
+// ---- per tensor: one walk, a sink for what it yields ------------------------------------------------------------------------------------
+// A sink is built from its Args by every thread of the workgroup, takes values with add(float) and ends with finish(), which every
+// thread calls.  Range: the min / max slot (Acc + fold of yk_range.h).  Hist, further down: the counts of one slot.
+struct Range : Acc {
+    struct Args {
+        uint32_t *slot;
+    };
+    uint32_t *slot;
+    __device__ __forceinline__ Range(const Args &p) : slot(p.slot) {}
+    __device__ __forceinline__ void finish() { fold(*this, slot); }
+};
+
+// nv items of V floats, then the scalar tail [V * nv, n).  EPI: x is z [M][C] and each value goes through scale_act into y first; then
+// C % V == 0 (V = 4: all pointers 16-byte aligned; item i starts at channel (V * i) % C and its floats share one row) and n = V * nv, no
+// tail.  Without EPI the values of x are taken as they are and C ... y are not read.
+template <class Sink, bool EPI, int V>
+__global__ __launch_bounds__(CAL_BLOCK) void tensor_kernel(const float *__restrict__ x, size_t nv, size_t n, int C, const float *__restrict__ scale,
+                                                            const float *__restrict__ bias, int act, float alpha, float *__restrict__ y,
+                                                            typename Sink::Args sink_args) {
+    Sink k(sink_args);
     const size_t step = (size_t)gridDim.x * CAL_BLOCK;
-    for (size_t i = (size_t)blockIdx.x * CAL_BLOCK + threadIdx.x; i < n; i += step) {
-        const int c = (int)(i % (size_t)C);
-        const float r = c_act(z[i] * scale[c] + bias[c], act, alpha);
-        y[i] = r;
-        a.add(r);
+    const size_t cw = EPI ? (size_t)(C / V) : 1;
+    for (size_t i = (size_t)blockIdx.x * CAL_BLOCK + threadIdx.x; i < nv; i += step) {
+        float o[V];
+        if constexpr (EPI) {
+            const size_t c = i % cw;
+            float s[V], b[V], p[V];
+            load_v<V>(scale, c, s);
+            load_v<V>(bias, c, b);
+            scale_act<V>(x, y, i, s, b, act, alpha, p, o);
+        } else {
+            load_v<V>(x, i, o);
+        }
+#pragma unroll
+        for (int j = 0; j < V; ++j) k.add(o[j]);
     }
-    fold(a, slot);
+    if constexpr (!EPI)
+        for (size_t i = V * nv + (size_t)blockIdx.x * CAL_BLOCK + threadIdx.x; i < n; i += step) k.add(x[i]);
+    k.finish();
 }
 
 // ---- per-channel ranges (equalize.py): the column reduction of [M][C] -------------------------------------------------
@@ -99,7 +115,7 @@ __global__ __launch_bounds__(CAL_BLOCK) void scale_act_range_kernel(const float 
 // the others idle), so a tile is one contiguous piece of memory and a thread's channels never change: scale and bias are loaded once, and the
 // accumulators are per channel.  Tiles are strided over the grid.  Then the R accumulators of a column are folded by a tree over rows in LDS
 // and the chunk's w * V channels go to their slots: one atomicMin / atomicMax pair per channel and workgroup, none from a workgroup that saw
-// nothing finite there.  The same expression for y as the kernels above.
+// nothing finite there.
 constexpr int CHR_MIN_TRIPS = 4;                          // tiles a workgroup walks at least (chrange_grid)
 constexpr int CHR_MIN_FOLD = 32;                          // values a workgroup folds per channel, at least, before its pair of atomics
 
@@ -122,24 +138,10 @@ __global__ __launch_bounds__(CAL_BLOCK) void scale_act_chrange_kernel(const floa
                 b[j] = bias[col * V + j];
             }
             for (size_t row = (size_t)blockIdx.x * R + r; row < M; row += (size_t)gridDim.x * R) {
-                const size_t i = row * (size_t)cw + col;
-                if constexpr (V == 4) {
-                    const float4 v = reinterpret_cast<const float4 *>(z)[i];
-                    float4 o;
-                    o.x = c_act(v.x * s[0] + b[0], act, alpha);
-                    o.y = c_act(v.y * s[1] + b[1], act, alpha);
-                    o.z = c_act(v.z * s[2] + b[2], act, alpha);
-                    o.w = c_act(v.w * s[3] + b[3], act, alpha);
-                    reinterpret_cast<float4 *>(y)[i] = o;
-                    a[0].add(o.x);
-                    a[1].add(o.y);
-                    a[2].add(o.z);
-                    a[3].add(o.w);
-                } else {
-                    const float o = c_act(z[i] * s[0] + b[0], act, alpha);
-                    y[i] = o;
-                    a[0].add(o);
-                }
+                float p[V], o[V];
+                scale_act<V>(z, y, row * (size_t)cw + col, s, b, act, alpha, p, o);
+#pragma unroll
+                for (int j = 0; j < V; ++j) a[j].add(o[j]);
             }
         }
         __syncthreads();                                                       // the previous chunk's results have been read
@@ -194,8 +196,8 @@ inline unsigned chrange_grid(size_t M, int cw) {
 }
 
 // ---- per-channel sums of the pre-activation (biascorrect.py) ------------------------------------------------------------
-// t = z * scale + bias (fp32, BEFORE the activation) summed per channel in float64, without floating-point atomics and in an order that
-// (M, C) alone fix - not the pointers' alignment, the stream or the scheduling:
+// t = z * scale + bias (fp32, BEFORE the activation: scale_act's p) summed per channel in float64, without floating-point atomics and in an
+// order that (M, C) alone fix - not the pointers' alignment, the stream or the scheduling:
 //   * the channels are walked in chunks of w = min(C - c0, CAL_BLOCK); a chunk has L = 4 * (CAL_BLOCK / w) ROW LANES;
 //   * workgroup g owns rows [g * T, (g + 1) * T), T = chsum_rows(C); lane l of a chunk adds rows g * T + l, + L, + 2 L, ... in that order;
 //   * the L lanes of a channel are folded by a tree in LDS (lanes [half, n) onto [0, n - half)), and the result is partial[g][c];
@@ -235,27 +237,20 @@ __global__ __launch_bounds__(CAL_BLOCK) void scale_act_chsum_kernel(const float 
         const int w = C - c0 < CAL_BLOCK ? C - c0 : CAL_BLOCK;
         const int R = CAL_BLOCK / w, L = 4 * R;
         double a[4] = {0.0, 0.0, 0.0, 0.0};
+        float s[V], b[V], p[V], o[V];
         if constexpr (V == 4) {
             const int wq = w / 4, q = t % wq, l = t / wq;                          // wq * L = R * w <= CAL_BLOCK threads work
             if (l < L) {
                 const int c = c0 + 4 * q;
-                const float4 s = *reinterpret_cast<const float4 *>(scale + c);
-                const float4 b = *reinterpret_cast<const float4 *>(bias + c);
+                load_v<4>(scale + c, 0, s);
+                load_v<4>(bias + c, 0, b);
                 uint32_t bad = 0u;
                 for (size_t row = row0 + l; row < row1; row += L) {
-                    const size_t i = (row * (size_t)C + c) / 4;
-                    const float4 v = reinterpret_cast<const float4 *>(z)[i];
-                    const float p0 = v.x * s.x + b.x, p1 = v.y * s.y + b.y, p2 = v.z * s.z + b.z, p3 = v.w * s.w + b.w;
-                    float4 o;
-                    o.x = c_act(p0, act, alpha);
-                    o.y = c_act(p1, act, alpha);
-                    o.z = c_act(p2, act, alpha);
-                    o.w = c_act(p3, act, alpha);
-                    reinterpret_cast<float4 *>(y)[i] = o;
-                    if (chs_finite(p0)) a[0] += (double)p0; else bad |= 1u;
-                    if (chs_finite(p1)) a[1] += (double)p1; else bad |= 2u;
-                    if (chs_finite(p2)) a[2] += (double)p2; else bad |= 4u;
-                    if (chs_finite(p3)) a[3] += (double)p3; else bad |= 8u;
+                    scale_act<4>(z, y, (row * (size_t)C + c) / 4, s, b, act, alpha, p, o);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        if (chs_finite(p[j])) a[j] += (double)p[j]; else bad |= 1u << j;
+                    }
                 }
                 for (int j = 0; j < 4; ++j)
                     if (bad >> j & 1u) atomicOr(flags + c + j, 1u);
@@ -267,18 +262,16 @@ __global__ __launch_bounds__(CAL_BLOCK) void scale_act_chsum_kernel(const float 
             const int col = t % w, r = t / w;
             if (r < R) {
                 const int c = c0 + col;
-                const float s = scale[c], b = bias[c];
+                s[0] = scale[c], b[0] = bias[c];
                 bool bad = false;
                 int k = 0;
                 for (size_t row = row0 + r; row < row1; row += R, k = (k + 1) & 3) {
-                    const size_t i = row * (size_t)C + c;
-                    const float p = z[i] * s + b;
-                    y[i] = c_act(p, act, alpha);
-                    if (chs_finite(p)) {
-                        a[0] += k == 0 ? (double)p : 0.0;                          // (adding +0.0 changes no finite sum)
-                        a[1] += k == 1 ? (double)p : 0.0;
-                        a[2] += k == 2 ? (double)p : 0.0;
-                        a[3] += k == 3 ? (double)p : 0.0;
+                    scale_act<1>(z, y, row * (size_t)C + c, s, b, act, alpha, p, o);
+                    if (chs_finite(p[0])) {
+                        a[0] += k == 0 ? (double)p[0] : 0.0;                       // (adding +0.0 changes no finite sum)
+                        a[1] += k == 1 ? (double)p[0] : 0.0;
+                        a[2] += k == 2 ? (double)p[0] : 0.0;
+                        a[3] += k == 3 ? (double)p[0] : 0.0;
                     } else {
                         bad = true;
                     }
@@ -320,20 +313,29 @@ __device__ __forceinline__ int bin_of(float v, float lo, float inv, int nb) {
     return t >= (float)nb ? nb - 1 : (t > 0.f ? (int)t : 0);
 }
 
+// the sink of tensor_kernel that counts: the workgroup's uint32 [nb] in dynamic LDS (the launch gives nb * 4 bytes)
 struct Hist {
+    struct Args {
+        float lo, inv;
+        int nb;
+        unsigned long long *row;                         // the slot's counts [nb]
+        uint32_t *flag;
+    };
     uint32_t *s_h;                                       // LDS, [nb]
-    float lo, inv;
-    int nb, zbin;
+    const Args p;
+    int zbin;
     uint32_t bad = 0u;
-    __device__ __forceinline__ Hist(uint32_t *lds, float lo_, float inv_, int nb_) : s_h(lds), lo(lo_), inv(inv_), nb(nb_) {
-        zbin = bin_of(0.f, lo, inv, nb);
-        for (int b = threadIdx.x; b < nb; b += CAL_BLOCK) s_h[b] = 0u;
+    __device__ __forceinline__ Hist(const Args &args) : p(args) {
+        extern __shared__ uint32_t s_hist[];
+        s_h = s_hist;
+        zbin = bin_of(0.f, p.lo, p.inv, p.nb);
+        for (int b = threadIdx.x; b < p.nb; b += CAL_BLOCK) s_h[b] = 0u;
         __syncthreads();
     }
     __device__ __forceinline__ void add(float v) {
         const bool ok = (__float_as_uint(v) & 0x7F800000u) != 0x7F800000u;
         if (!ok) bad = 1u;
-        const int b = bin_of(v, lo, inv, nb);
+        const int b = bin_of(v, p.lo, p.inv, p.nb);
         if (HIST_WAVE_ZERO) {
             const bool z = ok && b == zbin;
             const unsigned long long m = __ballot(z);                          // over the lanes active here
@@ -347,87 +349,64 @@ struct Hist {
         }
     }
     // the workgroup's non-zero bins into the slot's row; the flag only from a workgroup that met a non-finite value
-    __device__ __forceinline__ void flush(unsigned long long *row, uint32_t *flag) {
+    __device__ __forceinline__ void finish() {
         __shared__ uint32_t s_bad;
         if (threadIdx.x == 0) s_bad = 0u;
         __syncthreads();                                                       // also: every LDS count is in
         if (bad) atomicOr(&s_bad, 1u);
-        for (int b = threadIdx.x; b < nb; b += CAL_BLOCK) {
+        for (int b = threadIdx.x; b < p.nb; b += CAL_BLOCK) {
             const uint32_t c = s_h[b];
-            if (c) atomicAdd(row + b, (unsigned long long)c);
+            if (c) atomicAdd(p.row + b, (unsigned long long)c);
         }
         __syncthreads();
-        if (threadIdx.x == 0 && s_bad) atomicOr(flag, 1u);
+        if (threadIdx.x == 0 && s_bad) atomicOr(p.flag, 1u);
     }
 };
-
-__global__ __launch_bounds__(CAL_BLOCK) void hist_kernel(const float *__restrict__ x, size_t n4, size_t n, float lo, float inv, int nb,
-                                                          unsigned long long *row, uint32_t *flag) {
-    extern __shared__ uint32_t s_hist[];
-    Hist h(s_hist, lo, inv, nb);
-    const size_t step = (size_t)gridDim.x * CAL_BLOCK;
-    const float4 *x4 = reinterpret_cast<const float4 *>(x);
-    for (size_t i = (size_t)blockIdx.x * CAL_BLOCK + threadIdx.x; i < n4; i += step) {
-        const float4 v = x4[i];
-        h.add(v.x);
-        h.add(v.y);
-        h.add(v.z);
-        h.add(v.w);
-    }
-    for (size_t i = 4 * n4 + (size_t)blockIdx.x * CAL_BLOCK + threadIdx.x; i < n; i += step) h.add(x[i]);
-    h.flush(row, flag);
-}
-
-// the twins of scale_act_range_vec_kernel / scale_act_range_kernel: the same expression for y (this unit compiles with -ffp-contract=off, so
-// it rounds the same way in both), the histogram in place of the min / max
-__global__ __launch_bounds__(CAL_BLOCK) void scale_act_hist_vec_kernel(const float *__restrict__ z, size_t n4, int C, const float *__restrict__ scale,
-                                                                        const float *__restrict__ bias, int act, float alpha, float *__restrict__ y,
-                                                                        float lo, float inv, int nb, unsigned long long *row, uint32_t *flag) {
-    extern __shared__ uint32_t s_hist[];
-    Hist h(s_hist, lo, inv, nb);
-    const size_t step = (size_t)gridDim.x * CAL_BLOCK;
-    const float4 *z4 = reinterpret_cast<const float4 *>(z);
-    float4 *y4 = reinterpret_cast<float4 *>(y);
-    const size_t c4 = (size_t)(C / 4);
-    for (size_t i = (size_t)blockIdx.x * CAL_BLOCK + threadIdx.x; i < n4; i += step) {
-        const size_t c = (i % c4) * 4;
-        const float4 v = z4[i];
-        const float4 s = *reinterpret_cast<const float4 *>(scale + c);
-        const float4 b = *reinterpret_cast<const float4 *>(bias + c);
-        float4 r;
-        r.x = c_act(v.x * s.x + b.x, act, alpha);
-        r.y = c_act(v.y * s.y + b.y, act, alpha);
-        r.z = c_act(v.z * s.z + b.z, act, alpha);
-        r.w = c_act(v.w * s.w + b.w, act, alpha);
-        y4[i] = r;
-        h.add(r.x);
-        h.add(r.y);
-        h.add(r.z);
-        h.add(r.w);
-    }
-    h.flush(row, flag);
-}
-
-__global__ __launch_bounds__(CAL_BLOCK) void scale_act_hist_kernel(const float *__restrict__ z, size_t n, int C, const float *__restrict__ scale,
-                                                                    const float *__restrict__ bias, int act, float alpha, float *__restrict__ y,
-                                                                    float lo, float inv, int nb, unsigned long long *row, uint32_t *flag) {
-    extern __shared__ uint32_t s_hist[];
-    Hist h(s_hist, lo, inv, nb);
-    const size_t step = (size_t)gridDim.x * CAL_BLOCK;
-    for (size_t i = (size_t)blockIdx.x * CAL_BLOCK + threadIdx.x; i < n; i += step) {
-        const int c = (int)(i % (size_t)C);
-        const float r = c_act(z[i] * scale[c] + bias[c], act, alpha);
-        y[i] = r;
-        h.add(r);
-    }
-    h.flush(row, flag);
-}
 
 // what a call may histogram: NB in range, a finite lo, inv >= 0 (+inf allowed: a range narrower than NB / FLT_MAX), and no workgroup of
 // `grid` that could count 2^32 elements into one uint32 bin (a workgroup takes at most n / grid + 4 * CAL_BLOCK + 3 of them)
 inline bool hist_args_ok(long long n, float lo, float inv, int nbins, int slot, unsigned grid) {
     return n > 0 && nbins >= HIST_MIN_BINS && nbins <= HIST_MAX_BINS && slot >= 0 && lo - lo == 0.f && inv >= 0.f &&
            (unsigned long long)n / grid + 4ull * CAL_BLOCK + 3ull < (1ull << 32);
+}
+
+inline Hist::Args hist_sink(float lo, float inv, int nbins, uint64_t *d_hist, uint32_t *d_flags, int slot) {
+    return {lo, inv, nbins, reinterpret_cast<unsigned long long *>(d_hist) + (size_t)slot * nbins, d_flags + slot};
+}
+
+// ---- what the entry points share ----------------------------------------------------------------------------------------------------------
+// a tensor taken as it is: n4 float4 (none unless x is 16-byte aligned) + the scalar tail [4 * n4, n); -> the workgroups for both loops
+inline unsigned plain_grid(const float *x, long long n, size_t *n4) {
+    *n4 = aligned16(x) ? (size_t)n / 4 : 0;
+    const size_t tail = (size_t)n - 4 * *n4;
+    return grid_for(*n4 > tail ? *n4 : tail);
+}
+
+template <class Sink>
+void launch_plain(unsigned grid, size_t lds, void *stream, const float *x, size_t n4, long long n, typename Sink::Args sink) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(tensor_kernel<Sink, false, 4>), dim3(grid), dim3(CAL_BLOCK), lds, (hipStream_t)stream, x, n4, (size_t)n, 0,
+                       (const float *)nullptr, (const float *)nullptr, 0, 0.f, (float *)nullptr, sink);
+}
+
+// the arguments every yk_scale_act_* call takes.  M * C is a size_t after it: past 2^31 elements is fine, past 2^63 is not
+inline bool scale_act_args_ok(const float *z, long long M, int C, const float *scale, const float *bias, int act, const float *y) {
+    return z && scale && bias && y && M > 0 && C > 0 && act >= YK_ACT_NONE && act <= YK_ACT_LEAKY && M <= (long long)(~0ull >> 1) / C;
+}
+
+// whether a yk_scale_act_* call runs its 16-byte kernel (V = 4): four channels of one row per access
+inline bool scale_act_vec(const float *z, int C, const float *scale, const float *bias, const float *y) {
+    return C % 4 == 0 && aligned16(z) && aligned16(y) && aligned16(scale) && aligned16(bias);
+}
+
+template <class Sink>
+void launch_scale_act(bool vec, unsigned grid, size_t lds, void *stream, const float *z, size_t n, int C, const float *scale, const float *bias, int act,
+                      float alpha, float *y, typename Sink::Args sink) {
+    if (vec)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(tensor_kernel<Sink, true, 4>), dim3(grid), dim3(CAL_BLOCK), lds, (hipStream_t)stream, z, n / 4, n, C, scale,
+                           bias, act, alpha, y, sink);
+    else
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(tensor_kernel<Sink, true, 1>), dim3(grid), dim3(CAL_BLOCK), lds, (hipStream_t)stream, z, n, n, C, scale, bias,
+                           act, alpha, y, sink);
 }
 
 __global__ void range_reset_kernel(uint32_t *r, int n_slots) {
@@ -464,40 +443,34 @@ extern "C" int yk_range_f32(const float *x, long long n, uint32_t *d_range, int 
         yk_set_error("yk_range_f32: bad argument");
         return YK_ERR_ARG;
     }
-    const size_t n4 = aligned16(x) ? (size_t)n / 4 : 0;
-    const size_t items = n4 > (size_t)n - 4 * n4 ? n4 : (size_t)n - 4 * n4;
-    hipLaunchKernelGGL(range_kernel, dim3(grid_for(items)), dim3(CAL_BLOCK), 0, (hipStream_t)stream, x, n4, (size_t)n,
-                       d_range + (size_t)YK_RANGE_WORDS * slot);
+    size_t n4;
+    const unsigned grid = plain_grid(x, n, &n4);
+    launch_plain<Range>(grid, 0, stream, x, n4, n, {d_range + (size_t)YK_RANGE_WORDS * slot});
     YK_HIP(hipGetLastError());
     return YK_OK;
 }
 
 extern "C" int yk_scale_act_range_f32(const float *z, long long M, int C, const float *scale, const float *bias, int act, float alpha, float *y,
                                       uint32_t *d_range, int slot, void *stream) {
-    if (!z || !scale || !bias || !y || !d_range || M <= 0 || C <= 0 || slot < 0 || act < YK_ACT_NONE || act > YK_ACT_LEAKY) {
+    if (!scale_act_args_ok(z, M, C, scale, bias, act, y) || !d_range || slot < 0) {
         yk_set_error("yk_scale_act_range_f32: bad argument");
         return YK_ERR_ARG;
     }
     const size_t n = (size_t)M * (size_t)C;
-    uint32_t *s = d_range + (size_t)YK_RANGE_WORDS * slot;
-    if (C % 4 == 0 && aligned16(z) && aligned16(y) && aligned16(scale) && aligned16(bias))
-        hipLaunchKernelGGL(scale_act_range_vec_kernel, dim3(grid_for(n / 4)), dim3(CAL_BLOCK), 0, (hipStream_t)stream, z, n / 4, C, scale, bias, act,
-                           alpha, y, s);
-    else
-        hipLaunchKernelGGL(scale_act_range_kernel, dim3(grid_for(n)), dim3(CAL_BLOCK), 0, (hipStream_t)stream, z, n, C, scale, bias, act, alpha, y, s);
+    const bool vec = scale_act_vec(z, C, scale, bias, y);
+    launch_scale_act<Range>(vec, grid_for(vec ? n / 4 : n), 0, stream, z, n, C, scale, bias, act, alpha, y, {d_range + (size_t)YK_RANGE_WORDS * slot});
     YK_HIP(hipGetLastError());
     return YK_OK;
 }
 
 extern "C" int yk_scale_act_chrange_f32(const float *z, long long M, int C, const float *scale, const float *bias, int act, float alpha, float *y,
                                         uint32_t *d_range, int slot0, void *stream) {
-    if (!z || !scale || !bias || !y || !d_range || M <= 0 || C <= 0 || slot0 < 0 || act < YK_ACT_NONE || act > YK_ACT_LEAKY ||
-        M > (long long)(~0ull >> 1) / C) {                                     // M * C is a size_t below: past 2^31 elements is fine, past 2^63 is not
+    if (!scale_act_args_ok(z, M, C, scale, bias, act, y) || !d_range || slot0 < 0) {
         yk_set_error("yk_scale_act_chrange_f32: bad argument");
         return YK_ERR_ARG;
     }
     uint32_t *s = d_range + (size_t)YK_RANGE_WORDS * slot0;
-    if (C % 4 == 0 && aligned16(z) && aligned16(y) && aligned16(scale) && aligned16(bias))
+    if (scale_act_vec(z, C, scale, bias, y))
         hipLaunchKernelGGL(scale_act_chrange_kernel<4>, dim3(chrange_grid((size_t)M, C / 4)), dim3(CAL_BLOCK), 0, (hipStream_t)stream, z, (size_t)M, C / 4,
                            scale, bias, act, alpha, y, s);
     else
@@ -528,8 +501,8 @@ extern "C" int yk_chsum_reset(double *d_sum, uint32_t *d_flags, int n_slots, voi
 
 extern "C" int yk_scale_act_chsum_f32(const float *z, long long M, int C, const float *scale, const float *bias, int act, float alpha, float *y,
                                       double *d_sum, uint32_t *d_flags, int slot0, double *d_work, void *stream) {
-    if (!z || !scale || !bias || !y || !d_sum || !d_flags || !d_work || M <= 0 || C <= 0 || slot0 < 0 || act < YK_ACT_NONE || act > YK_ACT_LEAKY ||
-        M > (long long)(~0ull >> 1) / C || ((uintptr_t)d_sum & 7u) != 0 || ((uintptr_t)d_work & 7u) != 0) {
+    if (!scale_act_args_ok(z, M, C, scale, bias, act, y) || !d_sum || !d_flags || !d_work || slot0 < 0 || ((uintptr_t)d_sum & 7u) != 0 ||
+        ((uintptr_t)d_work & 7u) != 0) {
         yk_set_error("yk_scale_act_chsum_f32: bad argument (d_sum and d_work 8-byte aligned)");
         return YK_ERR_ARG;
     }
@@ -539,7 +512,7 @@ extern "C" int yk_scale_act_chsum_f32(const float *z, long long M, int C, const 
         return YK_ERR_ARG;
     }
     hipStream_t st = (hipStream_t)stream;
-    if (C % 4 == 0 && aligned16(z) && aligned16(y) && aligned16(scale) && aligned16(bias))
+    if (scale_act_vec(z, C, scale, bias, y))
         hipLaunchKernelGGL(scale_act_chsum_kernel<4>, dim3((unsigned)G), dim3(CAL_BLOCK), 0, st, z, (size_t)M, C, T, scale, bias, act, alpha, y, d_work,
                            d_flags + slot0);
     else
@@ -608,41 +581,32 @@ extern "C" int yk_hist_f32(const float *x, long long n, float lo, float inv, int
         yk_set_error("yk_hist_f32: bad argument");
         return YK_ERR_ARG;
     }
-    const size_t n4 = aligned16(x) ? (size_t)n / 4 : 0;
-    const size_t items = n4 > (size_t)n - 4 * n4 ? n4 : (size_t)n - 4 * n4;
-    const unsigned grid = grid_for(items);
+    size_t n4;
+    const unsigned grid = plain_grid(x, n, &n4);
     if (!hist_args_ok(n, lo, inv, nbins, slot, grid)) {
         yk_set_error("yk_hist_f32: bad argument (16 <= nbins <= 4096, finite lo, inv >= 0, n / workgroups < 2^32)");
         return YK_ERR_ARG;
     }
-    hipLaunchKernelGGL(hist_kernel, dim3(grid), dim3(CAL_BLOCK), (size_t)nbins * sizeof(uint32_t), (hipStream_t)stream, x, n4, (size_t)n, lo, inv,
-                       nbins, reinterpret_cast<unsigned long long *>(d_hist) + (size_t)slot * nbins, d_flags + slot);
+    launch_plain<Hist>(grid, (size_t)nbins * sizeof(uint32_t), stream, x, n4, n, hist_sink(lo, inv, nbins, d_hist, d_flags, slot));
     YK_HIP(hipGetLastError());
     return YK_OK;
 }
 
 extern "C" int yk_scale_act_hist_f32(const float *z, long long M, int C, const float *scale, const float *bias, int act, float alpha, float *y,
                                      float lo, float inv, int nbins, uint64_t *d_hist, uint32_t *d_flags, int slot, void *stream) {
-    if (!z || !scale || !bias || !y || !d_hist || !d_flags || M <= 0 || C <= 0 || act < YK_ACT_NONE || act > YK_ACT_LEAKY ||
-        M > (long long)(~0ull >> 1) / C) {
+    if (!scale_act_args_ok(z, M, C, scale, bias, act, y) || !d_hist || !d_flags) {
         yk_set_error("yk_scale_act_hist_f32: bad argument");
         return YK_ERR_ARG;
     }
     const size_t n = (size_t)M * (size_t)C;
-    const bool vec = C % 4 == 0 && aligned16(z) && aligned16(y) && aligned16(scale) && aligned16(bias);
+    const bool vec = scale_act_vec(z, C, scale, bias, y);
     const unsigned grid = grid_for(vec ? n / 4 : n);
     if (!hist_args_ok((long long)n, lo, inv, nbins, slot, grid)) {
         yk_set_error("yk_scale_act_hist_f32: bad argument (16 <= nbins <= 4096, finite lo, inv >= 0, M * C / workgroups < 2^32)");
         return YK_ERR_ARG;
     }
-    unsigned long long *row = reinterpret_cast<unsigned long long *>(d_hist) + (size_t)slot * nbins;
-    const size_t lds = (size_t)nbins * sizeof(uint32_t);
-    if (vec)
-        hipLaunchKernelGGL(scale_act_hist_vec_kernel, dim3(grid), dim3(CAL_BLOCK), lds, (hipStream_t)stream, z, n / 4, C, scale, bias, act, alpha, y, lo,
-                           inv, nbins, row, d_flags + slot);
-    else
-        hipLaunchKernelGGL(scale_act_hist_kernel, dim3(grid), dim3(CAL_BLOCK), lds, (hipStream_t)stream, z, n, C, scale, bias, act, alpha, y, lo, inv,
-                           nbins, row, d_flags + slot);
+    launch_scale_act<Hist>(vec, grid, (size_t)nbins * sizeof(uint32_t), stream, z, n, C, scale, bias, act, alpha, y,
+                           hist_sink(lo, inv, nbins, d_hist, d_flags, slot));
     YK_HIP(hipGetLastError());
     return YK_OK;
 }

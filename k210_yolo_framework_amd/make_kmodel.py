@@ -33,6 +33,7 @@ import time
 
 import numpy as np
 
+from . import quantize
 from .helper import INFO, Helper, VOC_ANCHORS
 from .yolonet import MODEL_DEFS
 
@@ -71,7 +72,6 @@ def main(ckpt, out, image_size, output_size, model_def, class_num, depth_multipl
          ranges=None, method='minmax', percentile=99.99, bins=2048, equalize=False, max_gain=64.0, bias_correct=False,
          adaround=False, ada_iters=1000, ada_lambda=0.01, ada_lr=1e-2):
     from pathlib import Path
-    from . import quantize
     anchor_file = Path(f'data/{train_set}_anchor.npy')
     h = Helper(None, class_num, str(anchor_file) if anchor_file.exists() else VOC_ANCHORS, np.reshape(np.array(image_size), (-1, 2)),
                np.reshape(np.array(output_size), (-1, 2)))
@@ -103,6 +103,12 @@ def main(ckpt, out, image_size, output_size, model_def, class_num, depth_multipl
                     f'{", channel biases corrected (one statistics pass per conv)" if bias_correct else ""}, {time.time() - t0:.2f} s')
     print(INFO, f' wrote {out}: kmodel of {report["file_bytes"]} bytes')
     return report
+
+
+def _true_or_false(p, name, value) -> bool:
+    if value not in (None, 'True', 'False'):
+        p.error(f'--{name} {value}: True or False')
+    return value == 'True'
 
 
 def cli(argv=None):
@@ -143,36 +149,28 @@ def cli(argv=None):
         p.error('--ranges replaces calibration: it cannot be combined with --calib_method')
     if not a.calib and not a.synthetic and not a.ranges:
         p.error('give --calib LIST.npy, --synthetic N or --ranges FILE.npz')
-    if a.equalize not in (None, 'True', 'False'):
-        p.error(f'--equalize {a.equalize}: True or False')
-    equalize = a.equalize == 'True'
-    if a.ranges and equalize:
-        p.error('--equalize cannot be combined with --ranges: QAT ranges belong to the unequalised weights')
-    if equalize and not a.equalize_max_gain > 1.0:
+    on = {}
+    for name, why in (('equalize', 'cannot be combined with --ranges: QAT ranges belong to the unequalised weights'),
+                      ('bias_correct', 'needs calibration frames: it cannot be combined with --ranges (QAT ranges, no frames)'),
+                      ('adaround', 'needs calibration frames: it cannot be combined with --ranges (QAT ranges, no frames)')):
+        on[name] = _true_or_false(p, name, getattr(a, name))
+        if a.ranges and on[name]:
+            p.error(f'--{name} {why}')
+    if on['equalize'] and not a.equalize_max_gain > 1.0:
         p.error(f'--equalize_max_gain {a.equalize_max_gain} must be above 1')
-    if a.bias_correct not in (None, 'True', 'False'):
-        p.error(f'--bias_correct {a.bias_correct}: True or False')
-    bias_correct = a.bias_correct == 'True'
-    if a.ranges and bias_correct:
-        p.error('--bias_correct needs calibration frames: it cannot be combined with --ranges (QAT ranges, no frames)')
-    if a.adaround not in (None, 'True', 'False'):
-        p.error(f'--adaround {a.adaround}: True or False')
-    adaround = a.adaround == 'True'
-    if a.ranges and adaround:
-        p.error('--adaround needs calibration frames: it cannot be combined with --ranges (QAT ranges, no frames)')
-    if adaround and not (a.adaround_iters >= 0 and a.adaround_lambda >= 0.0 and a.adaround_lr > 0.0):
+    if on['adaround'] and not (a.adaround_iters >= 0 and a.adaround_lambda >= 0.0 and a.adaround_lr > 0.0):
         p.error(f'--adaround_iters {a.adaround_iters} and --adaround_lambda {a.adaround_lambda} must not be negative, --adaround_lr '
                 f'{a.adaround_lr} must be positive')
     method = a.calib_method or 'minmax'
-    if method not in ('minmax', 'percentile', 'mse'):
-        p.error(f'--calib_method {method}: one of minmax, percentile, mse')
-    if not 50.0 < a.calib_percentile <= 100.0:
-        p.error(f'--calib_percentile {a.calib_percentile} outside (50, 100]')
-    if not 16 <= a.calib_bins <= 4096:
-        p.error(f'--calib_bins {a.calib_bins} outside 16..4096')
+    try:
+        quantize.check_method(method, a.calib_percentile, a.calib_bins)
+    except quantize.KmodelError as e:
+        p.error({'method': f'--calib_method {method}: one of {", ".join(quantize.CALIB_METHODS)}',
+                 'percentile': f'--calib_percentile {a.calib_percentile} outside (50, 100]',
+                 'bins': f'--calib_bins {a.calib_bins} outside {quantize.MIN_BINS}..{quantize.MAX_BINS}'}[e.argument])
     return main(a.pre_ckpt, a.output, a.image_size, a.output_size, a.model_def, a.class_num, a.depth_multiplier, a.train_set, a.calib,
-                a.synthetic, a.calib_seed, a.calib_batch, a.calib_limit, a.ranges, method, a.calib_percentile, a.calib_bins, equalize,
-                a.equalize_max_gain, bias_correct, adaround, a.adaround_iters, a.adaround_lambda, a.adaround_lr)
+                a.synthetic, a.calib_seed, a.calib_batch, a.calib_limit, a.ranges, method, a.calib_percentile, a.calib_bins, on['equalize'],
+                a.equalize_max_gain, on['bias_correct'], on['adaround'], a.adaround_iters, a.adaround_lambda, a.adaround_lr)
 
 
 if __name__ == '__main__':

@@ -84,12 +84,16 @@ def fold_bn(layer: ns.Layer, weights) -> Tuple[np.ndarray, np.ndarray]:
     return np.ones(c), (np.asarray(weights[layer.name + '/bias'], np.float64) if layer.use_bias else np.zeros(c))
 
 
+def _op_inputs(op: dict) -> List[int]:
+    """The tensors an op reads."""
+    return [op[key] for key in ('in0', 'in1') if op.get(key, -1) is not None and op.get(key, -1) >= 0]
+
+
 def _consumers(spec: ns.NetSpec) -> Dict[int, List[int]]:
     r: Dict[int, List[int]] = {}
     for k, op in enumerate(spec.ops):
-        for key in ('in0', 'in1'):
-            if op.get(key, -1) is not None and op.get(key, -1) >= 0:
-                r.setdefault(op[key], []).append(k)
+        for t in _op_inputs(op):
+            r.setdefault(t, []).append(k)
     return r
 
 
@@ -180,12 +184,11 @@ def quantize(spec: ns.NetSpec, weights: Dict[str, np.ndarray], ranges: Dict[str,
     plan = plan_convs(spec)
     bn_add_delta = dict(bn_add_delta or {})
     weight_codes = dict(weight_codes or {})
-    unknown = sorted(set(weight_codes) - {op['layer'] for op in spec.ops if op['type'] in (ns.OP_CONV, ns.OP_DWCONV)})
-    if unknown:
-        raise KmodelError(f'quantize: weight_codes names layer(s) {", ".join(map(repr, unknown))}, which are not conv layers of {spec.name}')
-    unknown = sorted(set(bn_add_delta) - {op['layer'] for op in spec.ops if op['type'] in (ns.OP_CONV, ns.OP_DWCONV)})
-    if unknown:
-        raise KmodelError(f'quantize: bn_add_delta names layer(s) {", ".join(map(repr, unknown))}, which are not conv layers of {spec.name}')
+    convs = {op['layer'] for op in spec.ops if op['type'] in (ns.OP_CONV, ns.OP_DWCONV)}
+    for what, given in (('weight_codes', weight_codes), ('bn_add_delta', bn_add_delta)):
+        unknown = sorted(set(given) - convs)
+        if unknown:
+            raise KmodelError(f'quantize: {what} names layer(s) {", ".join(map(repr, unknown))}, which are not conv layers of {spec.name}')
     names = tensor_names(spec)
     lay = {l.name: l for l in spec.layers}
     readers = _consumers(spec)
@@ -464,6 +467,82 @@ def outside_share(counts, lo: float, hi: float, new_lo: float, new_hi: float) ->
 
 
 # ---- calibration on the GPU -------------------------------------------------------------------------------------------------------------
+class _Ranges:
+    """A measure: min / max, YK_RANGE_WORDS words per slot, of every tensor - or, `per_channel`, of every output channel of
+    every conv, from slot cal.ch_slot0[tensor]; the input tensor, no conv output, then goes to a last slot that nobody reads."""
+
+    def __init__(self, cal: "Calibrator", per_channel: bool = False):
+        self.cal, self.per_channel, self.n = cal, per_channel, cal.n_ch + 1 if per_channel else cal.n_slots
+        self.d = cal.torch.empty(4 * self.n, dtype=cal.torch.int32, device=cal.dev)
+
+    def clear(self):
+        self.images = 0
+        self.cal._ck('yk_range_reset', self.d, self.n)
+
+    def conv(self, z, M, Cn, scale, bias, act, alpha, y, slot):
+        if self.per_channel and slot:
+            self.cal._ck('yk_scale_act_chrange_f32', z, M, Cn, scale, bias, act, alpha, y, self.d, self.cal.ch_slot0[slot])
+        else:
+            self.cal._ck('yk_scale_act_range_f32', z, M, Cn, scale, bias, act, alpha, y, self.d, self.n - 1 if self.per_channel else slot)
+
+    def moved(self, y, slot):
+        if not self.per_channel:
+            self.cal._ck('yk_range_f32', y, y.numel(), self.d, slot)
+
+    def read(self):
+        return self.cal._back('yk_range_read', (self.d, self.n), (self.n, np.float32), (self.n, np.float32), (self.n, np.int32))
+
+
+class _Hists:
+    """uint64 counts [n_slots][bins] and a flag per slot, over the float32 spans lo .. hi (inv = bins / width) that feed_hist freezes."""
+
+    def __init__(self, cal: "Calibrator"):
+        self.cal, self.n, self.nb = cal, cal.n_slots, cal.bins
+        self.d = cal.torch.empty(self.n * self.nb, dtype=cal.torch.int64, device=cal.dev)
+        self.f = cal.torch.empty(self.n, dtype=cal.torch.int32, device=cal.dev)
+
+    def clear(self):
+        self.images, self.lo, self.hi, self.inv = 0, None, None, None
+        self.cal._ck('yk_hist_reset', self.d, self.n, self.nb)
+        self.f.zero_()
+
+    def conv(self, z, M, Cn, scale, bias, act, alpha, y, slot):
+        self.cal._ck('yk_scale_act_hist_f32', z, M, Cn, scale, bias, act, alpha, y, float(self.lo[slot]), float(self.inv[slot]), self.nb, self.d,
+                     self.f, slot)
+
+    def moved(self, y, slot):
+        self.cal._ck('yk_hist_f32', y, y.numel(), float(self.lo[slot]), float(self.inv[slot]), self.nb, self.d, self.f, slot)
+
+    def read(self):
+        return self.cal._back('yk_hist_read', (self.d, self.f, self.n, self.nb), ((self.n, self.nb), np.uint64), (self.n, np.int32))
+
+
+class _ChannelSums:
+    """float64 sum of every output channel's pre-activation, a flag per channel, the workspace of the largest call so far, the scratch slot."""
+    moved = staticmethod(lambda y, slot: None)
+
+    def __init__(self, cal: "Calibrator"):
+        self.cal, self.n, self.work = cal, cal.n_ch, None
+        self.sum = cal.torch.empty(self.n, dtype=cal.torch.float64, device=cal.dev)
+        self.f, self.scratch = (cal.torch.empty(n, dtype=cal.torch.int32, device=cal.dev) for n in (self.n, 4))
+
+    def clear(self):
+        self.images = 0
+        self.cal._ck('yk_chsum_reset', self.sum, self.f, self.n)
+
+    def conv(self, z, M, Cn, scale, bias, act, alpha, y, slot):
+        if slot == 0:
+            return self.cal._ck('yk_scale_act_range_f32', z, M, Cn, scale, bias, act, alpha, y, self.scratch, 0)
+        need = C.c_size_t()
+        self.cal.engine.call('yk_chsum_workspace_bytes', M, Cn, C.byref(need))
+        if self.work is None or self.work.numel() * 8 < need.value:
+            self.work = self.cal.torch.empty((need.value + 7) // 8, dtype=self.cal.torch.float64, device=self.cal.dev)
+        self.cal._ck('yk_scale_act_chsum_f32', z, M, Cn, scale, bias, act, alpha, y, self.sum, self.f, self.cal.ch_slot0[slot], self.work)
+
+    def read(self):
+        return self.cal._back('yk_chsum_read', (self.sum, self.f, self.n), (self.n, np.float64), (self.n, np.int32))
+
+
 class Calibrator:
     """The range of every tensor of `spec` over a calibration set, measured by an fp32 forward pass on the GPU.
 
@@ -485,7 +564,7 @@ class Calibrator:
     Cross-layer equalisation (equalize.py) needs the range of every CHANNEL of every conv output: `feed_channels` is the same walk with
     yk_scale_act_chrange_f32 as the epilogue, which folds channel c of a conv output into slot (the layer's first slot) + c of a second
     range buffer of sum(C over the conv outputs) slots (+ one scratch slot for the input tensor); `channel_ranges()` reads it.  It shares
-    nothing with the per-tensor buffer, so `feed` / `ranges()` do not see it."""
+    nothing with the per-tensor buffer, so `feed` / `ranges()` do not see it.  Every `feed*` is `forward`, the one walk, with its own measure."""
 
     def __init__(self, spec: ns.NetSpec, weights: Dict[str, np.ndarray], max_batch: int = 32, device: int = 0, bins: int = DEFAULT_BINS):
         import torch
@@ -513,109 +592,65 @@ class Calibrator:
         self.P['input/scale'] = torch.full((3,), np.float32(INPUT_SCALE), dtype=torch.float32, device=dev)
         self.P['input/bias'] = torch.zeros(3, dtype=torch.float32, device=dev)
         self.n_slots = len(spec.tensors)
-        self.d_range = torch.zeros(self.n_slots * 4, dtype=torch.int32, device=dev)                      # YK_RANGE_WORDS per slot
         self.bins = int(bins)
         if not MIN_BINS <= self.bins <= MAX_BINS:
             raise engine.YkError(f'Calibrator: bins = {bins} outside {MIN_BINS}..{MAX_BINS}')
-        self.d_hist = self.d_hflags = None                                                               # allocated by the first feed_hist
-        self.ch_slot0: Dict[str, int] = {}                                                               # conv layer -> its first channel slot
-        self.n_ch = 0
-        for op in spec.ops:
-            if op['type'] in (ns.OP_CONV, ns.OP_DWCONV):
-                self.ch_slot0[op['layer']] = self.n_ch
-                self.n_ch += int(op['cout'])
-        self.d_chrange = None                                                                            # allocated by the first feed_channels
-        self.d_chsum = None                                                                              # allocated by the first feed_means
-        self._last_use = {}
-        for k, op in enumerate(spec.ops):
-            for key in ('in0', 'in1'):
-                if op.get(key, -1) is not None and op.get(key, -1) >= 0:
-                    self._last_use[op[key]] = k
-        self.images = 0
+        ops = [op for op in spec.ops if op['type'] in (ns.OP_CONV, ns.OP_DWCONV)]
+        ends = [sum(int(op['cout']) for op in ops[:k]) for k in range(len(ops) + 1)]                     # the first channel slot of conv k, and n_ch
+        self.convs = [(op['layer'], slice(a, b), spec.tensors[op['out']]) for op, a, b in zip(ops, ends, ends[1:])]   # layer, its slots, its tensor
+        self.n_ch, self.ch_slot0 = ends[-1], {op['out']: a for op, a in zip(ops, ends)}
+        self._last_use = {t: k for k, op in enumerate(spec.ops) for t in _op_inputs(op)}
+        self.range, self.hist, self.channels, self.means = _Ranges(self), _Hists(self), _Ranges(self, per_channel=True), _ChannelSums(self)
         self.reset()
+
+    # the frames each measure has seen
+    images, hist_images, ch_images, mean_images = (property(lambda self, m=m: getattr(self, m).images) for m in ('range', 'hist', 'channels', 'means'))
 
     def _ck(self, name, *args):
         """engine.call of a library function whose last parameter is the stream: torch's current one."""
         self.engine.call(name, *args, self.torch.cuda.current_stream().cuda_stream)
 
+    def _back(self, name: str, dev: tuple, *host):
+        """One synchronising copy back, `name`(*dev, *host arrays), into new numpy arrays of the (shape, dtype) pairs `host`."""
+        host = tuple(np.empty(n, t) for n, t in host)
+        self.torch.cuda.current_stream().synchronize()
+        self.engine.call(name, *dev, *host)
+        return host
+
     def reset(self) -> None:
-        self._ck('yk_range_reset', self.d_range, self.n_slots)
-        self.images = self.hist_images = self.ch_images = self.mean_images = 0
-        if self.d_chrange is not None:
-            self._ck('yk_range_reset', self.d_chrange, self.n_ch + 1)
-        if self.d_chsum is not None:
-            self._ck('yk_chsum_reset', self.d_chsum, self.d_chflags, self.n_ch)
-        self.h_lo = self.h_hi = self.h_inv = None                                                        # frozen by the first feed_hist
+        for m in (self.range, self.hist, self.channels, self.means):
+            m.clear()
         self.last_clip: List[dict] = []
 
-    def _epilogue(self, z, M, Cn, scale, bias, act, alpha, y, slot):
-        self._ck('yk_scale_act_range_f32', z, M, Cn, scale, bias, act, alpha, y, self.d_range, slot)
+    def _feed(self, measure, frames_u8, keep, who: str) -> "Calibrator":
+        self.forward(frames_u8, measure, keep, who)
+        measure.images += int(frames_u8.shape[0])
+        return self
 
-    def _range(self, x, slot):
-        self._ck('yk_range_f32', x, x.numel(), self.d_range, slot)
-
-    def _epilogue_hist(self, z, M, Cn, scale, bias, act, alpha, y, slot):
-        self._ck('yk_scale_act_hist_f32', z, M, Cn, scale, bias, act, alpha, y, float(self.h_lo[slot]), float(self.h_inv[slot]), self.bins,
-                 self.d_hist, self.d_hflags, slot)
-
-    def _hist(self, x, slot):
-        self._ck('yk_hist_f32', x, x.numel(), float(self.h_lo[slot]), float(self.h_inv[slot]), self.bins, self.d_hist, self.d_hflags, slot)
-
-    def _epilogue_channels(self, z, M, Cn, scale, bias, act, alpha, y, slot):
-        if slot == 0:                                                                                # the input: no conv output, into the scratch slot
-            self._ck('yk_scale_act_range_f32', z, M, Cn, scale, bias, act, alpha, y, self.d_chrange, self.n_ch)
-        else:
-            self._ck('yk_scale_act_chrange_f32', z, M, Cn, scale, bias, act, alpha, y, self.d_chrange, self.ch_slot0[self.names[slot]])
+    def _refuse_non_finite(self, bad: List[str], what: str = 'range') -> None:
+        if bad:
+            raise self.engine.YkError(f'Calibrator: non-finite values (NaN or infinity) in tensor(s) {", ".join(bad)}: the weights or the frames '
+                                      f'are broken; no {what} is defined')
 
     def feed_channels(self, frames_u8, keep=None) -> "Calibrator":
         """frames_u8 as `feed` takes them: the range of every output channel of every conv layer, accumulated over calls like `feed` (and
         as independent of the batching).  Leaves the per-tensor ranges and histograms alone."""
-        if self.d_chrange is None:
-            self.d_chrange = self.torch.zeros((self.n_ch + 1) * 4, dtype=self.torch.int32, device=self.dev)
-            self._ck('yk_range_reset', self.d_chrange, self.n_ch + 1)
-        self._walk(frames_u8, keep, self._epilogue_channels, lambda x, slot: None, 'feed_channels')
-        self.ch_images += int(frames_u8.shape[0])
-        return self
+        return self._feed(self.channels, frames_u8, keep, 'feed_channels')
 
     def channel_ranges(self) -> Dict[str, Tuple[np.ndarray, np.ndarray]]:
         """{conv layer name: (lo[C], hi[C])} float32 over everything fed to feed_channels.  YkError naming the layer when one of its channels
         held a NaN or an infinity."""
         if not self.ch_images:
             raise self.engine.YkError('Calibrator.channel_ranges: nothing has been fed to feed_channels')
-        lo, hi, fl = (np.empty(self.n_ch, t) for t in (np.float32, np.float32, np.int32))
-        self.torch.cuda.current_stream().synchronize()
-        self.engine.call('yk_range_read', self.d_chrange, self.n_ch, lo, hi, fl)
-        ends = {name: (s0, s0 + int(self.lay[name].kernel_shape[3 if self.lay[name].kind == 'conv' else 2])) for name, s0 in self.ch_slot0.items()}
-        bad = [name for name, (s0, s1) in ends.items() if fl[s0:s1].any()]
-        if bad:
-            raise self.engine.YkError(f'Calibrator: non-finite values (NaN or infinity) in tensor(s) {", ".join(bad)}: the weights or the frames '
-                                      f'are broken; no range is defined')
-        return {name: (lo[s0:s1].copy(), hi[s0:s1].copy()) for name, (s0, s1) in ends.items()}
-
-    def _epilogue_means(self, z, M, Cn, scale, bias, act, alpha, y, slot):
-        if slot == 0:                                                                                # the input: no conv output, into a scratch slot
-            self._ck('yk_scale_act_range_f32', z, M, Cn, scale, bias, act, alpha, y, self.d_mscratch, 0)
-            return
-        need = C.c_size_t()
-        self.engine.call('yk_chsum_workspace_bytes', M, Cn, C.byref(need))
-        if self.d_chwork is None or self.d_chwork.numel() * 8 < need.value:
-            self.d_chwork = self.torch.empty((need.value + 7) // 8, dtype=self.torch.float64, device=self.dev)
-        self._ck('yk_scale_act_chsum_f32', z, M, Cn, scale, bias, act, alpha, y, self.d_chsum, self.d_chflags, self.ch_slot0[self.names[slot]],
-                 self.d_chwork)
+        lo, hi, fl = self.channels.read()
+        self._refuse_non_finite([name for name, sl, _ in self.convs if fl[sl].any()])
+        return {name: (lo[sl].copy(), hi[sl].copy()) for name, sl, _ in self.convs}
 
     def feed_means(self, frames_u8, keep=None) -> "Calibrator":
         """frames_u8 as `feed` takes them: the float64 sum of the fp32 PRE-activation (folded BatchNorm applied, activation not) of every output
         channel of every conv layer, accumulated over calls (yk_scale_act_chsum_f32: no floating-point atomics, the same calls give the same
         bits).  What bias correction (biascorrect.py) compares the kmodel's z against.  Leaves ranges and histograms alone."""
-        if self.d_chsum is None:
-            self.d_chsum = self.torch.zeros(self.n_ch, dtype=self.torch.float64, device=self.dev)
-            self.d_chflags = self.torch.zeros(self.n_ch, dtype=self.torch.int32, device=self.dev)
-            self.d_mscratch = self.torch.zeros(4, dtype=self.torch.int32, device=self.dev)
-            self.d_chwork = None
-            self._ck('yk_chsum_reset', self.d_chsum, self.d_chflags, self.n_ch)
-        self._walk(frames_u8, keep, self._epilogue_means, lambda x, slot: None, 'feed_means')
-        self.mean_images += int(frames_u8.shape[0])
-        return self
+        return self._feed(self.means, frames_u8, keep, 'feed_means')
 
     def channel_means(self) -> Dict[str, Tuple[np.ndarray, int]]:
         """{conv layer name: (sum float64 [C], count)} over everything fed to feed_means; count = images x out_h x out_w of the SPEC's tensor
@@ -623,52 +658,33 @@ class Calibrator:
         and when nothing was fed."""
         if not self.mean_images:
             raise self.engine.YkError('Calibrator.channel_means: nothing has been fed to feed_means')
-        s, fl = np.empty(self.n_ch, np.float64), np.empty(self.n_ch, np.int32)
-        self.torch.cuda.current_stream().synchronize()
-        self.engine.call('yk_chsum_read', self.d_chsum, self.d_chflags, self.n_ch, s, fl)
-        out, bad = {}, []
-        for op in self.spec.ops:
-            if op['type'] in (ns.OP_CONV, ns.OP_DWCONV):
-                s0, (h, w, c) = self.ch_slot0[op['layer']], self.spec.tensors[op['out']]
-                if fl[s0:s0 + c].any():
-                    bad.append(op['layer'])
-                out[op['layer']] = (s[s0:s0 + c].copy(), self.mean_images * int(h) * int(w))
-        if bad:
-            raise self.engine.YkError(f'Calibrator: non-finite values (NaN or infinity) in tensor(s) {", ".join(bad)}: the weights or the frames '
-                                      f'are broken; no mean is defined')
-        return out
+        s, fl = self.means.read()
+        self._refuse_non_finite([name for name, sl, _ in self.convs if fl[sl].any()], 'mean')
+        return {name: (s[sl].copy(), self.mean_images * int(t[0]) * int(t[1])) for name, sl, t in self.convs}
 
     def feed(self, frames_u8, keep=None) -> "Calibrator":
         """frames_u8: device uint8 [B, H, W, 3], B <= max_batch, H x W = the spec's input size.  `keep`: a dict that receives every tensor
         {name: device fp32 NHWC} of this batch (tests)."""
-        if self.h_lo is not None:
+        if self.hist.lo is not None:
             raise self.engine.YkError('Calibrator.feed: the ranges are frozen by feed_hist; reset() starts a new calibration')
-        self._walk(frames_u8, keep, self._epilogue, self._range, 'feed')
-        self.images += int(frames_u8.shape[0])
-        return self
+        return self._feed(self.range, frames_u8, keep, 'feed')
 
     def feed_hist(self, frames_u8, keep=None) -> "Calibrator":
         """The second pass: `frames_u8` (as `feed` takes them - the frames the ranges came from) counted into the histogram of every tensor.
         The first call freezes the ranges fed so far, widened to contain 0, as the span of the bins.  YkError unless ranges have been fed."""
         if not self.images:
             raise self.engine.YkError('Calibrator.feed_hist: feed the ranges first (the bins span them)')
-        if self.h_lo is None:
+        if self.hist.lo is None:
             self.ranges()                                                                            # raises on a non-finite tensor
             lo, hi, _ = self.read()
-            lo, hi = np.minimum(lo, np.float32(0)), np.maximum(hi, np.float32(0))
-            inv = np.array([hist_inv(a, b, self.bins) for a, b in zip(lo, hi)], np.float32)
-            if self.d_hist is None:
-                self.d_hist = self.torch.zeros(self.n_slots * self.bins, dtype=self.torch.int64, device=self.dev)
-                self.d_hflags = self.torch.zeros(self.n_slots, dtype=self.torch.int32, device=self.dev)
-            self._ck('yk_hist_reset', self.d_hist, self.n_slots, self.bins)
-            self.d_hflags.zero_()
-            self.h_lo, self.h_hi, self.h_inv = lo, hi, inv
-        self._walk(frames_u8, keep, self._epilogue_hist, self._hist, 'feed_hist')
-        self.hist_images += int(frames_u8.shape[0])
-        return self
+            self.hist.lo, self.hist.hi = lo, hi = np.minimum(lo, np.float32(0)), np.maximum(hi, np.float32(0))
+            self.hist.inv = np.array([hist_inv(a, b, self.bins) for a, b in zip(lo, hi)], np.float32)
+        return self._feed(self.hist, frames_u8, keep, 'feed_hist')
 
-    def _walk(self, frames_u8, keep, epilogue, plain, who) -> None:
-        """One fp32 forward pass of the spec; `epilogue` finishes a conv (and the input) and measures it, `plain` measures a moved tensor."""
+    def forward(self, frames_u8, measure, keep=None, who: str = 'forward') -> None:
+        """One fp32 forward pass of the spec over device uint8 frames [B, H, W, 3], B <= max_batch: `measure.conv` finishes every conv (and the
+        input) and measures it, `measure.moved` measures a moved tensor.  `keep`: a dict that receives every tensor {name: device fp32 NHWC};
+        `who` names the caller in the refusals."""
         torch, eng = self.torch, self.engine
         H, W = self.spec.in_hw
         if not (frames_u8.is_cuda and frames_u8.dtype == torch.uint8 and frames_u8.dim() == 4 and tuple(frames_u8.shape[1:]) == (H, W, 3)):
@@ -679,7 +695,7 @@ class Calibrator:
         new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=self.dev)            # noqa: E731
         raw = frames_u8.contiguous().to(torch.float32)                                           # 0..255, exact
         x = new(B, H, W, 3)
-        epilogue(raw, B * H * W, 3, self.P['input/scale'], self.P['input/bias'], ns.ACT_NONE, 0.0, x, 0)
+        measure.conv(raw, B * H * W, 3, self.P['input/scale'], self.P['input/bias'], ns.ACT_NONE, 0.0, x, 0)
         T = {0: x}
         for i, op in enumerate(self.spec.ops):
             x, t = T[op['in0']], op['type']
@@ -703,36 +719,23 @@ class Calibrator:
                     self._ck('yk_gemm_f32', 0, 1, M, co, 9 * ci, 1.0, col, 9 * ci, w, 9 * ci, 0.0, z, co)
                     del col
                 y = new(B, ho, wo, co)
-                epilogue(z, M, co, self.P[name + '/scale'], self.P[name + '/bias'], op['act'], float(op['alpha']), y, op['out'])
+                measure.conv(z, M, co, self.P[name + '/scale'], self.P[name + '/bias'], op['act'], float(op['alpha']), y, op['out'])
             else:
                 if t == ns.OP_UPSAMPLE:                                                          # nearest x2: pure data movement
                     y = x.repeat_interleave(2, dim=1).repeat_interleave(2, dim=2).contiguous()
                 else:
                     y = torch.cat([x, T[op['in1']]], dim=3)
-                plain(y, op['out'])
+                measure.moved(y, op['out'])
             T[op['out']] = y
-            if keep is None:
-                for key in ('in0', 'in1'):
-                    tid = op.get(key, -1)
-                    if tid is not None and tid >= 0 and self._last_use.get(tid) == i and tid not in self.spec.outputs:
-                        T.pop(tid, None)
+            for tid in _op_inputs(op) if keep is None else ():
+                if self._last_use.get(tid) == i and tid not in self.spec.outputs:
+                    T.pop(tid, None)
         if keep is not None:
             keep.update({self.names[tid]: v for tid, v in T.items()})
 
     def read(self):
         """(min, max, flags) as numpy arrays over the spec's tensors: one device-to-host copy."""
-        lo = np.empty(self.n_slots, np.float32)
-        hi = np.empty(self.n_slots, np.float32)
-        fl = np.empty(self.n_slots, np.int32)
-        self.torch.cuda.current_stream().synchronize()
-        self.engine.call('yk_range_read', self.d_range, self.n_slots, lo, hi, fl)
-        return lo, hi, fl
-
-    def _raise_non_finite(self, flags) -> None:
-        bad = [self.names[i] for i in range(self.n_slots) if flags[i]]
-        if bad:
-            raise self.engine.YkError(f'Calibrator: non-finite values (NaN or infinity) in tensor(s) {", ".join(bad)}: the weights or the frames '
-                                      f'are broken; no range is defined')
+        return self.range.read()
 
     def histograms(self):
         """(counts uint64 [n_slots, bins], lo, hi): the histogram of every tensor over everything fed to feed_hist, and the float32 ends of
@@ -740,12 +743,9 @@ class Calibrator:
         a tensor held a NaN or an infinity."""
         if not self.hist_images:
             raise self.engine.YkError('Calibrator.histograms: nothing has been fed to feed_hist')
-        counts = np.empty((self.n_slots, self.bins), np.uint64)
-        fl = np.empty(self.n_slots, np.int32)
-        self.torch.cuda.current_stream().synchronize()
-        self.engine.call('yk_hist_read', self.d_hist, self.d_hflags, self.n_slots, self.bins, counts, fl)
-        self._raise_non_finite(fl)
-        return counts, self.h_lo.copy(), self.h_hi.copy()
+        counts, fl = self.hist.read()
+        self._refuse_non_finite([self.names[i] for i in np.flatnonzero(fl)])
+        return counts, self.hist.lo.copy(), self.hist.hi.copy()
 
     def ranges(self, method: str = 'minmax', percentile: float = 99.99) -> Dict[str, Tuple[float, float]]:
         """{tensor name: (min, max)} over everything fed so far.  YkError naming the layer when a tensor held a NaN or an infinity.
@@ -757,7 +757,7 @@ class Calibrator:
         if method not in CALIB_METHODS:
             raise self.engine.YkError(f'Calibrator.ranges: unknown method {method!r} (one of {", ".join(CALIB_METHODS)})')
         lo, hi, fl = self.read()
-        self._raise_non_finite(fl)
+        self._refuse_non_finite([self.names[i] for i in np.flatnonzero(fl)])
         out = {self.names[i]: (float(lo[i]), float(hi[i])) for i in range(self.n_slots)}
         self.last_clip = []
         if method == 'minmax':
@@ -811,12 +811,21 @@ def synthetic_frames(n: int, in_hw, seed: int) -> np.ndarray:
 
 def check_method(method: str, percentile: float, bins: int) -> None:
     """KmodelError for a calibration method, percentile or bin count the quantiser does not take."""
-    if method not in CALIB_METHODS:
-        raise KmodelError(f'unknown calibration method {method!r} (one of {", ".join(CALIB_METHODS)})')
-    if not 50.0 < float(percentile) <= 100.0:
-        raise KmodelError(f'calibration percentile {percentile} outside (50, 100]')
-    if not MIN_BINS <= int(bins) <= MAX_BINS:
-        raise KmodelError(f'calibration bins {bins} outside {MIN_BINS}..{MAX_BINS}')
+    for argument, ok, why in (('method', method in CALIB_METHODS, f'unknown calibration method {method!r} (one of {", ".join(CALIB_METHODS)})'),
+                              ('percentile', 50.0 < float(percentile) <= 100.0, f'calibration percentile {percentile} outside (50, 100]'),
+                              ('bins', MIN_BINS <= int(bins) <= MAX_BINS, f'calibration bins {bins} outside {MIN_BINS}..{MAX_BINS}')):
+        if not ok:
+            e = KmodelError(why)
+            e.argument = argument                                                # for a caller that words the refusal itself (make_kmodel.cli)
+            raise e
+
+
+def device_batches(frames_u8, batch: int):
+    """`frames_u8` (uint8 [N, H, W, 3], host numpy or a device tensor) in device batches of `batch`."""
+    import torch
+    frames = frames_u8 if torch.is_tensor(frames_u8) else torch.from_numpy(np.ascontiguousarray(frames_u8))
+    for i in range(0, len(frames), batch):
+        yield frames[i:i + batch].cuda()
 
 
 def calibrate(spec: ns.NetSpec, weights, frames_u8, batch: int = 32, method: str = 'minmax', percentile: float = 99.99,
@@ -824,20 +833,15 @@ def calibrate(spec: ns.NetSpec, weights, frames_u8, batch: int = 32, method: str
     """Ranges of `frames_u8` (uint8 [N, H, W, 3], host numpy or a device tensor) in batches of `batch`.  A method other than 'minmax' walks
     the frames a second time for the histograms (`bins` bins per tensor) and clips every range by clip_range; `clipped`, a list, receives
     Calibrator.last_clip.  The input tensor's range is the raw pixel's whatever the method."""
-    import torch
     from . import engine
     try:
         check_method(method, percentile, bins)
     except KmodelError as e:
         raise engine.YkError(f'calibrate: {e}') from e
-    frames = frames_u8 if torch.is_tensor(frames_u8) else torch.from_numpy(np.ascontiguousarray(frames_u8))
-    batch = max(1, min(int(batch), len(frames)))
-    cal = Calibrator(spec, weights, max_batch=batch, bins=bins)
-    for i in range(0, len(frames), batch):
-        cal.feed(frames[i:i + batch].cuda())
-    if method != 'minmax':
-        for i in range(0, len(frames), batch):
-            cal.feed_hist(frames[i:i + batch].cuda())
+    cal = Calibrator(spec, weights, max_batch=max(1, min(int(batch), len(frames_u8))), bins=bins)
+    for feed in (cal.feed, cal.feed_hist)[:1 if method == 'minmax' else 2]:
+        for fr in device_batches(frames_u8, cal.max_batch):
+            feed(fr)
     out = cal.ranges(method, percentile)
     if clipped is not None:
         clipped.extend(cal.last_clip)
@@ -846,22 +850,16 @@ def calibrate(spec: ns.NetSpec, weights, frames_u8, batch: int = 32, method: str
 
 def calibrate_channels(spec: ns.NetSpec, weights, frames_u8, batch: int = 32) -> Dict[str, Tuple[np.ndarray, np.ndarray]]:
     """{conv layer name: (lo[C], hi[C])} of `frames_u8` (as `calibrate` takes them) in batches of `batch`: what equalize.equalize needs."""
-    import torch
-    frames = frames_u8 if torch.is_tensor(frames_u8) else torch.from_numpy(np.ascontiguousarray(frames_u8))
-    batch = max(1, min(int(batch), len(frames)))
-    cal = Calibrator(spec, weights, max_batch=batch)
-    for i in range(0, len(frames), batch):
-        cal.feed_channels(frames[i:i + batch].cuda())
+    cal = Calibrator(spec, weights, max_batch=max(1, min(int(batch), len(frames_u8))))
+    for fr in device_batches(frames_u8, cal.max_batch):
+        cal.feed_channels(fr)
     return cal.channel_ranges()
 
 
 def calibrate_means(spec: ns.NetSpec, weights, frames_u8, batch: int = 32) -> Dict[str, Tuple[np.ndarray, int]]:
     """{conv layer name: (sum float64 [C], count)} of the pre-activations over `frames_u8` (as `calibrate` takes them) in batches of `batch`:
     what biascorrect.correct needs."""
-    import torch
-    frames = frames_u8 if torch.is_tensor(frames_u8) else torch.from_numpy(np.ascontiguousarray(frames_u8))
-    batch = max(1, min(int(batch), len(frames)))
-    cal = Calibrator(spec, weights, max_batch=batch)
-    for i in range(0, len(frames), batch):
-        cal.feed_means(frames[i:i + batch].cuda())
+    cal = Calibrator(spec, weights, max_batch=max(1, min(int(batch), len(frames_u8))))
+    for fr in device_batches(frames_u8, cal.max_batch):
+        cal.feed_means(fr)
     return cal.channel_means()

@@ -221,7 +221,7 @@ CALIB_ACT, CALIB_ALPHA = 3, 0.3                      # YK_ACT_LEAKY
 
 
 def calib_vec(M, C, aligned=True):
-    """The dispatch of yk_scale_act_range_f32 / yk_scale_act_hist_f32 (csrc/yk_calib.hip:261 and :333): the 16-byte kernel iff C % 4 == 0
+    """The dispatch of yk_scale_act_range_f32 / yk_scale_act_hist_f32 (csrc/yk_calib.hip, scale_act_vec): the 16-byte kernel iff C % 4 == 0
     and z, y, scale and bias are 16-byte aligned (whole device allocations are)."""
     return C % 4 == 0 and aligned
 

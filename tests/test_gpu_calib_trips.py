@@ -37,7 +37,7 @@ def _range_run(path):
 def test_scale_act_range_kernel_past_one_grid(path):
     from tests.test_gpu_quantize import FP32_TOL, np_min_max
     M, Cn = gt.CALIB_SHAPES[path]
-    assert gt.calib_vec(M, Cn) == (path == 'vector') and gt.calib_items(M, Cn) > CAL_ITEMS        # csrc/yk_calib.hip:261; a second trip
+    assert gt.calib_vec(M, Cn) == (path == 'vector') and gt.calib_items(M, Cn) > CAL_ITEMS        # csrc/yk_calib.hip, scale_act_vec; a second trip
     _, _, _, y, (lo, hi, fl) = _range_run(path)
     z, sc, bi = gt.calib_case(path)
     v = z * sc + bi                                        # fp32, one rounding per operation
@@ -56,7 +56,7 @@ def test_fused_histogram_kernel_past_one_grid(path):
     import torch
     from tests.test_gpu_hist import Hists
     M, Cn = gt.CALIB_SHAPES[path]
-    assert gt.calib_vec(M, Cn) == (path == 'vector') and gt.calib_items(M, Cn) > CAL_ITEMS        # csrc/yk_calib.hip:333; a second trip
+    assert gt.calib_vec(M, Cn) == (path == 'vector') and gt.calib_items(M, Cn) > CAL_ITEMS        # csrc/yk_calib.hip, scale_act_vec; a second trip
     zd, sd, bd, want_y, _ = _range_run(path)
     lo, hi = calib_ref.widen(want_y.min(), want_y.max())
     H = Hists(2048)
