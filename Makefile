@@ -40,6 +40,10 @@
 #                    [ADAROUND=True ADAITERS=1000 ADALAMBDA=0.01 ADALR=0.01]: adaptive weight rounding after the calibration and before the bias
 #                    correction (k210_yolo_framework_amd/adaround.py): every kernel weight takes its lower or upper code so that each output
 #                    channel's error over the calibration images falls (not with RANGES=: it needs frames; default off)
+#                    [ANALYZE=True ANALYZESEED=S ANALYZETOP=3]: after the file is written, the finished kmodel is measured against the float network
+#                    conv by conv on the GPU (k210_yolo_framework_amd/qerror.py): accumulated and local SQNR, cosine, mean and largest error in
+#                    codes, share of codes at 0 and 255, the ANALYZETOP worst channels; one table row per conv and OUT.qerror.json; on the
+#                    calibration images, or with SYNTHETIC=N ANALYZESEED=S on N generated images of seed S (not with RANGES=: no frames; default off)
 #   make eval        CKPT=yolo_model.h5|yolo.kmodel [PRECISION=f16x2|f16|kpu] [ANN=data/voc_img_ann.npy | SYNTHETIC=256] [EVALOBJ=0.05] [VOC07=True]:
 #                    VOC mAP of the checkpoint, network and metric on the GPU; prints the per-class AP table, writes eval.json beside CKPT
 #                    [METRIC=coco]: also the COCO-style AP (IoU .50:.95, AP50, AP75, small / medium / large, AR) and a `coco` object in eval.json
@@ -161,6 +165,9 @@ ADAROUND      ?= False
 ADAITERS      ?= 1000
 ADALAMBDA     ?= 0.01
 ADALR         ?= 0.01
+ANALYZE       ?= False
+ANALYZESEED   ?=
+ANALYZETOP    ?= 3
 GPUS          ?= 1
 # anchors only (reference Makefile:27-29)
 ANCNUM        ?= 3
@@ -221,7 +228,7 @@ train:
 kmodel:
 	$(PY) make_kmodel.py $(CKPT) $(OUT) --train_set $(DATASET) --class_num $(CLSNUM) --model_def $(MODEL) --depth_multiplier $(DEPTHMUL) \
 		--image_size $(IMGSIZE) --output_size $(OUTSIZE) $(if $(RANGES),--ranges $(RANGES),$(if $(filter-out 0,$(SYNTHETIC)),--synthetic $(SYNTHETIC),--calib $(CALIB))) \
-		$(if $(CALIBMETHOD),--calib_method $(CALIBMETHOD) --calib_percentile $(CALIBPCT) --calib_bins $(CALIBBINS))$(if $(filter True,$(EQUALIZE)), --equalize True --equalize_max_gain $(EQMAXGAIN))$(if $(filter True,$(BIASCORRECT)), --bias_correct True)$(if $(filter True,$(ADAROUND)), --adaround True --adaround_iters $(ADAITERS) --adaround_lambda $(ADALAMBDA) --adaround_lr $(ADALR))
+		$(if $(CALIBMETHOD),--calib_method $(CALIBMETHOD) --calib_percentile $(CALIBPCT) --calib_bins $(CALIBBINS))$(if $(filter True,$(EQUALIZE)), --equalize True --equalize_max_gain $(EQMAXGAIN))$(if $(filter True,$(BIASCORRECT)), --bias_correct True)$(if $(filter True,$(ADAROUND)), --adaround True --adaround_iters $(ADAITERS) --adaround_lambda $(ADALAMBDA) --adaround_lr $(ADALR))$(if $(filter True,$(ANALYZE)), --analyze True --analyze_top $(ANALYZETOP)$(if $(ANALYZESEED), --analyze_seed $(ANALYZESEED)))
 
 # VOC mAP of CKPT (.h5 / .npz, or .kmodel / .kfpkg with PRECISION=kpu) on the validation head of ANN, or on SYNTHETIC=N generated images
 eval:

@@ -825,6 +825,9 @@ int yk_kpu_get_output(yk_kpu_plan_t *p, int idx, float **d_ptr, size_t *bytes, i
 int yk_kpu_output_count(const yk_kpu_plan_t *p);
 /* conv layer `layer_index` (kmodel layer index) of image `image` of the last run, uint8 CHW (n = C*H*W bytes); synchronises */
 int yk_kpu_debug_read(yk_kpu_plan_t *p, int layer_index, int image, uint8_t *h_dst, size_t n);
+/* the device-side twin: a BORROWED pointer to that layer's uint8 output of the last run, [max_batch][h][w][c] (NHWC, images h * w * c bytes
+ * apart), valid until the plan is destroyed and rewritten by every run; does not synchronise (read it on the stream the run was issued on) */
+int yk_kpu_layer_ptr(yk_kpu_plan_t *p, int layer_index, uint8_t **d_ptr, int *h, int *w, int *c);
 /* launches one yk_kpu_run_u8 issues, and their median durations over `iters` runs (HIP events around every launch) */
 int yk_kpu_launch_count(const yk_kpu_plan_t *p);
 int yk_kpu_profile(yk_kpu_plan_t *p, const uint8_t *d_frames, int batch, int layout, int iters, void *stream, float *ms_out);
@@ -870,6 +873,34 @@ int yk_chsum_reset(double *d_sum, uint32_t *d_flags, int n_slots, void *stream);
 int yk_scale_act_chsum_f32(const float *z, long long M, int C, const float *scale, const float *bias, int act, float alpha, float *y,
                            double *d_sum, uint32_t *d_flags, int slot0, double *d_work, void *stream);
 int yk_chsum_read(const double *d_sum, const uint32_t *d_flags, int n_slots, double *h_sum, int *h_flags);
+
+/* ---- per-channel quantisation error of a KPU tensor against a float tensor (qerror.py, which states the rule).
+ * yk_qerr_u8_f32   q = uint8 codes [B][qH][qW][C], y = fp32 [B][ho][wo][C] with ho = ceil(qH / step), wo = ceil(qW / step), step 1 or 2: float
+ *                  position (oy, ox) is compared with code position (step oy, step ox).  With yh = (double)(q - zp_y) * (double)s_y and
+ *                  e = (double)y - yh (one rounding per operation, no contraction), channel c adds into slot slot0 + c of d_slots:
+ *                    words 0..3, uint64: n (positions), the counts of q == 0 and of q == 255, a sticky flag;
+ *                    words 4..9, double: sum y^2, sum e^2, sum e, sum y yh, sum yh^2, and the largest |e| (a maximum, not a sum).
+ *                  A position whose y is a NaN or an infinity enters none of them and sets the flag.  No floating-point atomics: workgroups
+ *                  own about YK_QERR_TILE elements (whole rows of C) and leave one partial per channel and quantity in d_work
+ *                  (yk_qerr_workspace_bytes; needs no device; contents undefined before and after), a finishing launch folds them with
+ *                  max(1, YK_QERR_BLOCK / min(C, YK_QERR_BLOCK)) accumulators per channel - more workgroups than that take more than one pass -
+ *                  and adds the result to the slot (a plain load and store: calls on one d_slots are ordered by their stream).  Who adds what,
+ *                  and in which order, follows from (B ho wo, C) alone: the same calls give the same bits on any stream and with any alignment
+ *                  of the pointers.  16-byte loads of y and 4-byte loads of q when C % 4 == 0 and the pointers allow; any C >= 1;
+ *                  B ho wo C may exceed 2^31.  d_slots and d_work 8-byte aligned.
+ * yk_qerr_reset    slots [0, n_slots) to zero;  yk_qerr_read  one device-to-host copy (synchronises): h_counts [n_slots][4] = words 0..3,
+ *                  h_sums [n_slots][6] = words 4..9.
+ * yk_dequant_u8_f32  y[b][oy][ox][c] = (float)(q[b][step oy][step ox][c] - zp_y) * s_y, one fp32 rounding: what a reader of that KPU tensor
+ *                  sees, in real units (the local walk of qerror.analyze). */
+#define YK_QERR_WORDS 10
+#define YK_QERR_TILE 16384
+#define YK_QERR_BLOCK 256
+int yk_qerr_workspace_bytes(long long M, int C, size_t *bytes);
+int yk_qerr_reset(uint64_t *d_slots, int n_slots, void *stream);
+int yk_qerr_u8_f32(const uint8_t *q, const float *y, int B, int qH, int qW, int C, int step, float s_y, int zp_y, uint64_t *d_slots, int slot0,
+                   uint64_t *d_work, void *stream);
+int yk_qerr_read(const uint64_t *d_slots, int n_slots, long long *h_counts, double *h_sums);
+int yk_dequant_u8_f32(const uint8_t *q, int B, int qH, int qW, int C, int step, float s_y, int zp_y, float *y, void *stream);
 
 /* ---- adaptive weight rounding (adaround.py, which states the rule).  All calls are asynchronous on `stream`, allocate nothing
  *      and do not synchronise; no floating-point atomics: the same calls give the same bits.  A NULL tensor or a non-positive size:

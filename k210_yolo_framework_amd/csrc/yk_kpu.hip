@@ -716,6 +716,24 @@ extern "C" int yk_kpu_debug_read(yk_kpu_plan_t *p, int layer_index, int image, u
     return YK_ERR_ARG;
 }
 
+extern "C" int yk_kpu_layer_ptr(yk_kpu_plan_t *p, int layer_index, uint8_t **d_ptr, int *h, int *w, int *c) {
+    if (!p || !d_ptr) {
+        yk_set_error("yk_kpu_layer_ptr: bad argument");
+        return YK_ERR_ARG;
+    }
+    for (const Op &o : p->ops) {
+        if ((o.op != OP_CONV && o.op != OP_DWCONV) || o.layer != layer_index) continue;
+        const Value &v = p->V[o.out];
+        *d_ptr = p->arena + v.off;
+        if (h) *h = v.H;
+        if (w) *w = v.W;
+        if (c) *c = v.C;
+        return YK_OK;
+    }
+    yk_set_error("yk_kpu_layer_ptr: layer %d is not a conv layer of this plan", layer_index);
+    return YK_ERR_ARG;
+}
+
 // Per-launch timing: the run replayed `iters` times with HIP events around every launch; ms_out[i] = median of launch i.
 extern "C" int yk_kpu_profile(yk_kpu_plan_t *p, const uint8_t *d_frames, int batch, int layout, int iters, void *stream, float *ms_out) {
     if (!p || !ms_out || iters <= 0) {

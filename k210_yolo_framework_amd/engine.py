@@ -388,6 +388,14 @@ class KpuPlan(_PlanBase):
         call('yk_kpu_debug_read', self._h, int(index), int(image), out, out.size)
         return out
 
+    def layer_view(self, index: int):
+        """Borrowed torch view uint8 [max_batch, H, W, C] of the output of the conv at kmodel layer `index`, where the last run left it
+        (yk_kpu_layer_ptr): valid until the plan is closed, rewritten by every run, and not synchronised - read it on the run's stream."""
+        import torch
+        p, h, w, c = C.c_void_p(), C.c_int(), C.c_int(), C.c_int()
+        call('yk_kpu_layer_ptr', self._h, int(index), C.byref(p), C.byref(h), C.byref(w), C.byref(c))
+        return torch.as_tensor(_DevView(p.value, (self.max_batch, h.value, w.value, c.value), '|u1', self), device=f'cuda:{self.device}')
+
     def profile(self, frames, layout: str = 'nhwc', iters: int = 10, stream=None) -> np.ndarray:
         """Median duration (ms) of every launch of one run, HIP events around each (yk_kpu_profile)."""
         n = lib().yk_kpu_launch_count(self._h)

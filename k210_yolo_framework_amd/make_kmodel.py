@@ -5,6 +5,7 @@
                           [--equalize True [--equalize_max_gain G]]
                           [--bias_correct True]
                           [--adaround True [--adaround_iters N] [--adaround_lambda L] [--adaround_lr R]]
+                          [--analyze True [--analyze_seed S] [--analyze_top K]]
 
 CKPT: a Keras `.h5` or `.npz` checkpoint; OUT: `.kmodel` or `.kfpkg`.  The calibration images are a list file as make_voc_list.py writes
 (data/<set>_img_ann.npy) or N generated images as `make train SYNTHETIC=N` trains on; they are decoded as the input pipeline decodes them
@@ -24,7 +25,11 @@ pre-activation equals the float network's.  Not with `--ranges`: it needs calibr
 `--adaround True` (`make kmodel ADAROUND=True ADAITERS=1000 ADALAMBDA=0.01 ADALR=0.01`): adaptive weight rounding (adaround.py) after the
 calibration and before the bias correction, on the same images - one more float pass builds every layer's input Gram matrix, then
 `--adaround_iters` Adam steps per layer on the GPU choose the lower or upper code of every weight.  Not with `--ranges`: it needs calibration
-frames.  The report gets one line per layer."""
+frames.  The report gets one line per layer.
+`--analyze True` (`make kmodel ANALYZE=True ANALYZESEED=S ANALYZETOP=3`): after the file is written, the finished kmodel is measured against the
+float network conv by conv (qerror.py) - on the calibration images, or, with `--synthetic N --analyze_seed S`, on N generated images of seed S,
+which the calibration has not seen.  One table row per conv, and the same data in OUT.qerror.json.  The kmodel's bytes do not change.  Not with
+`--ranges`: no frames are read then (measuring a QAT kmodel on frames of its own is later work)."""
 from __future__ import annotations
 
 import argparse
@@ -70,7 +75,7 @@ def load_ranges(path, spec):
 
 def main(ckpt, out, image_size, output_size, model_def, class_num, depth_multiplier, train_set, calib, synthetic, calib_seed, batch, limit=0,
          ranges=None, method='minmax', percentile=99.99, bins=2048, equalize=False, max_gain=64.0, bias_correct=False,
-         adaround=False, ada_iters=1000, ada_lambda=0.01, ada_lr=1e-2):
+         adaround=False, ada_iters=1000, ada_lambda=0.01, ada_lr=1e-2, analyze=False, analyze_seed=None, analyze_top=3):
     from pathlib import Path
     anchor_file = Path(f'data/{train_set}_anchor.npy')
     h = Helper(None, class_num, str(anchor_file) if anchor_file.exists() else VOC_ANCHORS, np.reshape(np.array(image_size), (-1, 2)),
@@ -95,12 +100,17 @@ def main(ckpt, out, image_size, output_size, model_def, class_num, depth_multipl
             eq['bias_correct'] = True
         if adaround:
             eq.update(adaround=True, ada_iters=ada_iters, ada_lambda=ada_lambda, ada_lr=ada_lr)
+        if analyze:
+            held_out = synthetic and analyze_seed is not None and int(analyze_seed) != int(calib_seed)
+            eq.update(analyze=True, analyze_top=analyze_top,
+                      analyze_frames=calibration_frames(h, calib, synthetic, int(analyze_seed), class_num, limit) if held_out else None)
         report = model.save_kmodel(str(out), frames, batch=batch, method=method, percentile=percentile, bins=bins, **eq)
         print(quantize.format_report(report))
         print(INFO, f' {len(frames)} calibration images{"" if method == "minmax" else f", {method} ranges from {bins}-bin histograms"}'
                     f'{f", channel ranges equalised first (max gain {max_gain:g}, one more pass)" if equalize else ""}'
                     f'{f", weights rounded adaptively ({ada_iters} steps per layer)" if adaround else ""}'
-                    f'{", channel biases corrected (one statistics pass per conv)" if bias_correct else ""}, {time.time() - t0:.2f} s')
+                    f'{", channel biases corrected (one statistics pass per conv)" if bias_correct else ""}'
+                    f'{f", quantisation error written to {out}.qerror.json" if analyze else ""}, {time.time() - t0:.2f} s')
     print(INFO, f' wrote {out}: kmodel of {report["file_bytes"]} bytes')
     return report
 
@@ -140,6 +150,11 @@ def cli(argv=None):
     p.add_argument('--adaround_iters', type=int, default=1000, help='Adam steps per layer of --adaround')
     p.add_argument('--adaround_lambda', type=float, default=0.01, help='weight of the rounding regulariser of --adaround')
     p.add_argument('--adaround_lr', type=float, default=1e-2, help='Adam step size of --adaround')
+    p.add_argument('--analyze', type=str, default=None, help='True: measure the finished kmodel against the float network, conv by conv '
+                                                             '(qerror.py); prints a table and writes OUT.qerror.json; needs frames')
+    p.add_argument('--analyze_seed', type=int, default=None, help='with --synthetic N: measure on N generated images of this seed instead of the '
+                                                                  'calibration images')
+    p.add_argument('--analyze_top', type=int, default=3, help='worst channels --analyze names per conv')
     p.add_argument('pre_ckpt', type=str, help='trained weights (.h5 / .npz)')
     p.add_argument('output', type=str, help='.kmodel or .kfpkg to write')
     a = p.parse_args(sys.argv[1:] if argv is None else argv)
@@ -152,7 +167,9 @@ def cli(argv=None):
     on = {}
     for name, why in (('equalize', 'cannot be combined with --ranges: QAT ranges belong to the unequalised weights'),
                       ('bias_correct', 'needs calibration frames: it cannot be combined with --ranges (QAT ranges, no frames)'),
-                      ('adaround', 'needs calibration frames: it cannot be combined with --ranges (QAT ranges, no frames)')):
+                      ('adaround', 'needs calibration frames: it cannot be combined with --ranges (QAT ranges, no frames)'),
+                      ('analyze', 'cannot be combined with --ranges: no frames are read then, and it measures the kmodel on frames (measuring a QAT '
+                                  'kmodel on frames of its own is later work)')):
         on[name] = _true_or_false(p, name, getattr(a, name))
         if a.ranges and on[name]:
             p.error(f'--{name} {why}')
@@ -161,6 +178,8 @@ def cli(argv=None):
     if on['adaround'] and not (a.adaround_iters >= 0 and a.adaround_lambda >= 0.0 and a.adaround_lr > 0.0):
         p.error(f'--adaround_iters {a.adaround_iters} and --adaround_lambda {a.adaround_lambda} must not be negative, --adaround_lr '
                 f'{a.adaround_lr} must be positive')
+    if on['analyze'] and a.analyze_top < 0:
+        p.error(f'--analyze_top {a.analyze_top} must not be negative')
     method = a.calib_method or 'minmax'
     try:
         quantize.check_method(method, a.calib_percentile, a.calib_bins)
@@ -170,7 +189,8 @@ def cli(argv=None):
                  'bins': f'--calib_bins {a.calib_bins} outside {quantize.MIN_BINS}..{quantize.MAX_BINS}'}[e.argument])
     return main(a.pre_ckpt, a.output, a.image_size, a.output_size, a.model_def, a.class_num, a.depth_multiplier, a.train_set, a.calib,
                 a.synthetic, a.calib_seed, a.calib_batch, a.calib_limit, a.ranges, method, a.calib_percentile, a.calib_bins, on['equalize'],
-                a.equalize_max_gain, on['bias_correct'], on['adaround'], a.adaround_iters, a.adaround_lambda, a.adaround_lr)
+                a.equalize_max_gain, on['bias_correct'], on['adaround'], a.adaround_iters, a.adaround_lambda, a.adaround_lr, on['analyze'],
+                a.analyze_seed, a.analyze_top)
 
 
 if __name__ == '__main__':

@@ -360,6 +360,9 @@ def format_report(report: dict) -> str:
         from . import biascorrect
         rows.append(biascorrect.format_report(report['biascorrect']))
     rows.append(f"main memory {report['main_mem_usage']} bytes, KPU RAM peak {report['kpu_ram_peak']} bytes")
+    if report.get('qerror'):
+        from . import qerror
+        rows.append(qerror.format_report(report['qerror']))
     return '\n'.join(rows)
 
 
@@ -681,10 +684,9 @@ class Calibrator:
             self.hist.inv = np.array([hist_inv(a, b, self.bins) for a, b in zip(lo, hi)], np.float32)
         return self._feed(self.hist, frames_u8, keep, 'feed_hist')
 
-    def forward(self, frames_u8, measure, keep=None, who: str = 'forward') -> None:
-        """One fp32 forward pass of the spec over device uint8 frames [B, H, W, 3], B <= max_batch: `measure.conv` finishes every conv (and the
-        input) and measures it, `measure.moved` measures a moved tensor.  `keep`: a dict that receives every tensor {name: device fp32 NHWC};
-        `who` names the caller in the refusals."""
+    def frame_tensor(self, frames_u8, measure, who: str = 'forward'):
+        """The input tensor of the walk, device fp32 [B, H, W, 3] = pixels / 255, made (and measured, as slot 0) by `measure.conv` from device uint8
+        frames [B, H, W, 3], B <= max_batch; `who` names the caller in the refusals."""
         torch, eng = self.torch, self.engine
         H, W = self.spec.in_hw
         if not (frames_u8.is_cuda and frames_u8.dtype == torch.uint8 and frames_u8.dim() == 4 and tuple(frames_u8.shape[1:]) == (H, W, 3)):
@@ -692,34 +694,48 @@ class Calibrator:
         B = int(frames_u8.shape[0])
         if not 1 <= B <= self.max_batch:
             raise eng.YkError(f'Calibrator.{who}: {B} frames, max_batch is {self.max_batch}')
-        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=self.dev)            # noqa: E731
         raw = frames_u8.contiguous().to(torch.float32)                                           # 0..255, exact
-        x = new(B, H, W, 3)
+        x = torch.empty((B, H, W, 3), dtype=torch.float32, device=self.dev)
         measure.conv(raw, B * H * W, 3, self.P['input/scale'], self.P['input/bias'], ns.ACT_NONE, 0.0, x, 0)
-        T = {0: x}
+        return x
+
+    def conv(self, op: dict, x, B: int, measure):
+        """The conv op `op` of the spec on x (device fp32 NHWC, B images) -> its output tensor: the fp32 forward launches, then `measure.conv`, which
+        finishes it (folded BatchNorm, activation) and measures it."""
+        new = lambda *shape: self.torch.empty(shape, dtype=self.torch.float32, device=self.dev)   # noqa: E731
+        ho, wo, co = self.spec.tensors[op['out']]
+        hi, wi, ci = self.spec.tensors[op['in0']]
+        M = B * ho * wo
+        name = op['layer']
+        w = self.P[name + '/w']
+        geom = [B, hi, wi, ci, ho, wo, op['stride'], op['pad_t'], op['pad_l']]
+        z = new(B, ho, wo, co)
+        if op['type'] == ns.OP_DWCONV:
+            self._ck('yk_dw3x3_fwd_f32', x, w, *geom, z)
+        elif op['k'] == 1:
+            self._ck('yk_gemm_f32', 0, 1, M, co, ci, 1.0, x, ci, w, ci, 0.0, z, co)
+        elif ci % 4 == 0:
+            self._ck('yk_conv3x3_bn_fwd_f32', x, w, *geom, co, z, None, None, 0.0, 0, 0.0, None, None, None, None, None, 0.0, None)
+        else:
+            col = new(M, 9 * ci)
+            self._ck('yk_im2col3x3_f32', x, *geom, col)
+            self._ck('yk_gemm_f32', 0, 1, M, co, 9 * ci, 1.0, col, 9 * ci, w, 9 * ci, 0.0, z, co)
+            del col
+        y = new(B, ho, wo, co)
+        measure.conv(z, M, co, self.P[name + '/scale'], self.P[name + '/bias'], op['act'], float(op['alpha']), y, op['out'])
+        return y
+
+    def forward(self, frames_u8, measure, keep=None, who: str = 'forward') -> None:
+        """One fp32 forward pass of the spec over device uint8 frames [B, H, W, 3], B <= max_batch: `measure.conv` finishes every conv (and the
+        input) and measures it, `measure.moved` measures a moved tensor.  `keep`: a dict that receives every tensor {name: device fp32 NHWC};
+        `who` names the caller in the refusals."""
+        torch = self.torch
+        T = {0: self.frame_tensor(frames_u8, measure, who)}
+        B = int(frames_u8.shape[0])
         for i, op in enumerate(self.spec.ops):
             x, t = T[op['in0']], op['type']
-            ho, wo, co = self.spec.tensors[op['out']]
-            hi, wi, ci = self.spec.tensors[op['in0']]
-            M = B * ho * wo
             if t in (ns.OP_CONV, ns.OP_DWCONV):
-                name = op['layer']
-                w = self.P[name + '/w']
-                geom = [B, hi, wi, ci, ho, wo, op['stride'], op['pad_t'], op['pad_l']]
-                z = new(B, ho, wo, co)
-                if t == ns.OP_DWCONV:
-                    self._ck('yk_dw3x3_fwd_f32', x, w, *geom, z)
-                elif op['k'] == 1:
-                    self._ck('yk_gemm_f32', 0, 1, M, co, ci, 1.0, x, ci, w, ci, 0.0, z, co)
-                elif ci % 4 == 0:
-                    self._ck('yk_conv3x3_bn_fwd_f32', x, w, *geom, co, z, None, None, 0.0, 0, 0.0, None, None, None, None, None, 0.0, None)
-                else:
-                    col = new(M, 9 * ci)
-                    self._ck('yk_im2col3x3_f32', x, *geom, col)
-                    self._ck('yk_gemm_f32', 0, 1, M, co, 9 * ci, 1.0, col, 9 * ci, w, 9 * ci, 0.0, z, co)
-                    del col
-                y = new(B, ho, wo, co)
-                measure.conv(z, M, co, self.P[name + '/scale'], self.P[name + '/bias'], op['act'], float(op['alpha']), y, op['out'])
+                y = self.conv(op, x, B, measure)
             else:
                 if t == ns.OP_UPSAMPLE:                                                          # nearest x2: pure data movement
                     y = x.repeat_interleave(2, dim=1).repeat_interleave(2, dim=2).contiguous()

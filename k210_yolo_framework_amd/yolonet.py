@@ -117,7 +117,7 @@ class YoloModel:
 
     def save_kmodel(self, path: str, calibration_frames, batch: int = 32, method: str = 'minmax', percentile: float = 99.99, bins: int = 2048,
                     equalize: bool = False, max_gain: float = 64.0, bias_correct: bool = False, adaround: bool = False, ada_iters: int = 1000,
-                    ada_lambda: float = 0.01, ada_lr: float = 1e-2):
+                    ada_lambda: float = 0.01, ada_lr: float = 1e-2, analyze: bool = False, analyze_frames=None, analyze_top: int = 3):
         """Quantise these weights to a K210 kmodel (quantize.py) and write it: `.kmodel`, or `.kfpkg` (model + flash list, no
         firmware).  calibration_frames: uint8 [N, H, W, 3] at the network's input size (host numpy or a device tensor); their tensor ranges
         are measured on the GPU in batches of `batch`, from the raw pixels / 255 as the KPU sees them.  The new Kmodel is kept beside the
@@ -136,7 +136,11 @@ class YoloModel:
         adaround=True (adaround.py) chooses, after the calibration and on the same frames, for every kernel weight the lower or the upper of its
         two neighbouring codes so that each output channel's error over the frames falls (`ada_iters` Adam steps per layer on the GPU, rounding
         regulariser `ada_lambda`, step `ada_lr`); no row ends worse than nearest rounding in that objective; report['adaround'] lists the layers.
-        Order: equalise, calibrate, adaround, bias-correct, write."""
+        Order: equalise, calibrate, adaround, bias-correct, write.
+        analyze=True (qerror.py) then measures the FINISHED kmodel - whatever of the above made it - against the float network it was made of, conv
+        by conv, on `analyze_frames` (as calibration_frames; None: the calibration frames): accumulated and local SQNR, cosine, mean and largest
+        error in codes, the share of codes at 0 and 255 and the `analyze_top` worst channels.  report['qerror'] holds it, format_report prints
+        it, and `path`.qerror.json gets the same data.  The written kmodel has the same bytes with it on and off."""
         import torch
         from . import engine, kmodel, quantize
         try:
@@ -184,6 +188,12 @@ class YoloModel:
         self._s.pop('kpu_program', None)
         if self.precision == 'kpu':
             self._drop_plan()
+        if analyze:
+            from . import qerror
+            report['qerror'] = qerror.analyze(self.spec, weights, km, report, frames if analyze_frames is None else analyze_frames, batch,
+                                              top=analyze_top)
+            with open(str(path) + '.qerror.json', 'w') as f:
+                f.write(qerror.to_json(report['qerror']))
         self.last_quantize_report = report
         return report
 
