@@ -23,7 +23,9 @@ pixels.  Per frame the triple (dy, dx, mw) = (-oy, -ox, cw if mirror else -1) in
 right' = mw - left; then top, bottom += dy and left, right += dx.  Each step is one float32 operation.
 
 fuse(), for one picture of N views.  Candidates are the rows of all views, view by view and in row order, mapped back.  A row whose class is
-not exactly one of 0 .. class_num - 1, or whose score is not above 0 (a NaN included), is dropped.  Per class the candidates are walked by
+not exactly one of 0 .. class_num - 1, or whose score is not above 0 (a NaN included), is dropped.  Of a class's candidates the first
+N * max_out in candidate order take part and the rest are ignored: the decode leaves at most max_out rows of a class per frame, so this binds
+only on rows that are not decode-shaped (it is the room yk_fuse_views has for a class; include/yolo_hip.h).  Per class the candidates are walked by
 score descending (ties: the lowest candidate index) against a list of clusters in creation order: the candidate's IoU with every cluster's
 CURRENT fused box (softnms.iou_to_all's float32 expression, the decode's own); the best cluster is the one with the largest IoU (ties: the
 lowest cluster index); if that IoU is > thresh (strict) the candidate joins it, otherwise it opens a new cluster.  A cluster carries, in
@@ -204,6 +206,7 @@ def fuse(rows_per_view: Sequence[np.ndarray], xforms_, class_num: int, max_out: 
             mine = np.flatnonzero((cand[:, 5] == F(c)) & (cand[:, 4] > 0))
         if not len(mine):
             continue
+        mine = mine[:len(rows_per_view) * int(max_out)]                   # more than N * max_out of a class: the first in candidate order
         mine = mine[np.argsort(-cand[mine, 4], kind='stable')]           # score descending, ties to the lowest candidate index
         box = np.zeros((len(mine), 4), F)                                 # per cluster: the current fused box,
         acc = np.zeros((len(mine), 4), F)                                 # st, sl, sb, sr,

@@ -118,21 +118,70 @@ def step_case(Co, K, seed=0):
     return dict(V=V, r=r, frozen=frozen, G=G, inv_e=1.0 / e, s_w=s_w, n_free=int((~frozen).sum()), D=D)
 
 
-def run_steps(case, lam, beta, steps, dtype, products=None):
-    """`steps` steps of adaround.step in `dtype` from the case's state; P of step t is products[t] when given (the device's own), D G in
-    float64 otherwise.  -> ([(V, m, v, D) after every step] as float64, [P of every step])."""
+STEP_EDGES = ('zeros', 'zeros_late', 'rows_of_one', 'all_frozen')
+
+
+def step_edge_case(kind):
+    """The step kernel's inputs step_case does not hold, as step_case's dict (+ first_t, and m, v, p_zero where set).  step_case itself stays
+    as it is: step_float32_figure is measured on it.
+      zeros        (3, 86) with V[0, :8] = 0.0 exactly: h = 0.5, x = 0, |x| = 0 and sign(x) = 0; P is 0 at [0, :4], so the gradient there is 0;
+      zeros_late   the same from t = 10000 (c1 and c2 round to about 1), m and v as a long run leaves them: about g and g * g; the frozen
+                   elements' m and v are set too, to show that nothing touches them;
+      rows_of_one  (300, 1): K = 1, inv_e is one value per element across a workgroup boundary, nothing frozen;
+      all_frozen   (2, 129) with every element frozen, m and v set.  n_free would be 0, which the pipeline never passes (it runs no step then)
+                   and the entry point refuses; nothing reads it here, and it is 1."""
+    Co, K = {'zeros': (3, 86), 'zeros_late': (3, 86), 'rows_of_one': (300, 1), 'all_frozen': (2, 129)}[kind]
+    case = step_case(Co, K)
+    case['first_t'] = 10000 if kind == 'zeros_late' else 1
+    rng = np.random.default_rng(4321 + STEP_EDGES.index(kind))
+    if kind in ('zeros', 'zeros_late'):
+        case['V'][0, :8] = 0.0
+        case['p_zero'] = np.zeros((Co, K), bool)
+        case['p_zero'][0, :4] = True
+    if kind == 'all_frozen':
+        case['frozen'][:] = True
+        case['n_free'] = 1
+    case['D'] = np.where(case['frozen'], 0.0, case['s_w'] * (adaround.h_of(case['V']) - case['r']))
+    if kind in ('zeros_late', 'all_frozen'):
+        first, _ = run_steps(case, 0.0, 20.0, 1, np.float64)                    # m after one step from 0 is 0.1 g
+        g = 10.0 * first[0][1]
+        g = np.where(case['frozen'], 1e-3, g)
+        case['m'] = g * rng.uniform(0.5, 1.5, (Co, K))
+        case['v'] = g * g * rng.uniform(0.5, 2.0, (Co, K))
+    return case
+
+
+def run_steps(case, lam, beta, steps, dtype, products=None, first_t=1):
+    """`steps` steps (t = first_t, first_t + 1, ...) of adaround.step in `dtype` from the case's state (m and v zero unless the case has them); P
+    of step t is products[t] when given (the device's own), D G in float64 otherwise, 0 where the case's `p_zero` says so.
+    -> ([(V, m, v, D) after every step] as float64, [P of every step])."""
     dt = dtype
     V, r = case['V'].astype(dt), case['r'].astype(dt)
-    m, v = np.zeros_like(V), np.zeros_like(V)
+    m, v = (case[k].astype(dt) if k in case else np.zeros_like(V) for k in ('m', 'v'))
     D = case['D'].astype(dt)
     inv_e = case['inv_e'].astype(dt)
     out, used = [], []
     for t in range(steps):
         P = (np.asarray(products[t], np.float64) if products is not None else adaround.quad(D.astype(np.float64), case['G'])).astype(dt)
-        D = adaround.step(V, m, v, r, case['frozen'], P, inv_e, case['n_free'], case['s_w'], lam, beta, STEP_LR, t + 1, dtype=dt)
+        if products is None and 'p_zero' in case:
+            P[case['p_zero']] = 0
+        D = adaround.step(V, m, v, r, case['frozen'], P, inv_e, case['n_free'], case['s_w'], lam, beta, STEP_LR, first_t + t, dtype=dt)
         used.append(P.astype(np.float64))
         out.append(tuple(a.astype(np.float64).copy() for a in (V, m, v, D)))
     return out, used
+
+
+def step_figure_of(case, lam, beta, steps=3, first_t=1):
+    """The worst difference over `steps` steps on ONE case between the float32 numpy restatement of the step and the float64 rule fed the
+    float32 run's own P, per array (V, m, v, D), each relative to the largest magnitude of that array in the float64 run."""
+    a32, used = run_steps(case, lam, beta, steps, np.float32, first_t=first_t)
+    a64, _ = run_steps(case, lam, beta, steps, np.float64, used, first_t=first_t)
+    worst = np.zeros(4)
+    for s64, s32 in zip(a64, a32):
+        for k in range(4):
+            scale = max(float(np.abs(s64[k]).max()), 1e-300)
+            worst[k] = max(worst[k], float(np.abs(s32[k] - s64[k]).max()) / scale)
+    return worst
 
 
 @functools.lru_cache(maxsize=None)
@@ -142,11 +191,16 @@ def step_float32_figure(steps=3):
     that array in the float64 run of its case."""
     worst = np.zeros(4)
     for (Co, K), (lam, beta) in itertools.product(STEP_SHAPES, STEP_MODES.values()):
-        case = step_case(Co, K)
-        a32, used = run_steps(case, lam, beta, steps, np.float32)
-        a64, _ = run_steps(case, lam, beta, steps, np.float64, used)
-        for s64, s32 in zip(a64, a32):
-            for k in range(4):
-                scale = max(float(np.abs(s64[k]).max()), 1e-300)
-                worst[k] = max(worst[k], float(np.abs(s32[k] - s64[k]).max()) / scale)
+        worst = np.maximum(worst, step_figure_of(step_case(Co, K), lam, beta, steps))
+    return tuple(float(x) for x in worst)
+
+
+@functools.lru_cache(maxsize=None)
+def step_edge_figure(steps=3):
+    """step_float32_figure's measurement on the inputs of step_edge_case: the worst of step_figure_of over STEP_EDGES x STEP_MODES, each case
+    from its own first_t."""
+    worst = np.zeros(4)
+    for kind, (lam, beta) in itertools.product(STEP_EDGES, STEP_MODES.values()):
+        case = step_edge_case(kind)
+        worst = np.maximum(worst, step_figure_of(case, lam, beta, steps, case['first_t']))
     return tuple(float(x) for x in worst)
