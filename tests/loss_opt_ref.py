@@ -5,6 +5,8 @@ and GPU tests share.  CPU only.
 `layer_loss_torch` is tests/box_loss_ref.layer_loss_torch with three changes: the class targets are smoothed, the objectness target of an
 object cell is the detached, clamped IoU of box_loss_ref's box term, and bce is replaced by fl(z, x) = a_t (1 - p_t)^gamma bce(z, x) where
 focal says so, (1 - p_t) = z sigmoid(-x) + (1 - z) sigmoid(x) written as the rule writes it.  With every option off it IS box_loss_ref's."""
+import functools
+
 import numpy as np
 import torch
 import torch.nn.functional as TF
@@ -82,6 +84,78 @@ BOX_MODES = ('mse', 'ciou')
 
 def options(name):
     return dict(OFF, **OPTION_SETS[name])
+
+
+# ---- every instance (tests/test_gpu_loss_instances.py).  csrc/yk_loss.hip compiles yolo_loss_kernel<MODE, OPT> for 27 sets of L_* bits in
+# each of the four box modes; `instance_bits` restates loss_launch's rule from the options to the bits, and INSTANCE_SETS holds one option set
+# per compiled OPT (alpha 0; gamma 1.5 sets L_POW), all-off left out: its instances are test_gpu_loss.py's and test_gpu_box_loss.py's.
+L_FOBJ, L_FCLS, L_POW, L_SMOOTH, L_IOU = 1, 2, 4, 8, 16
+BIT_NAMES = {L_FOBJ: 'L_FOBJ', L_FCLS: 'L_FCLS', L_POW: 'L_POW', L_SMOOTH: 'L_SMOOTH', L_IOU: 'L_IOU'}
+
+
+def instance_bits(focal='off', focal_gamma=2.0, focal_alpha=0.0, label_smooth=0.0, obj_target='label'):
+    """The OPT of the instance loss_launch picks: focal counts only with gamma or alpha away from 0, L_POW only beside a focal bit."""
+    bits = 0
+    if focal_gamma != 0 or focal_alpha != 0:
+        bits |= {'off': 0, 'obj': L_FOBJ, 'cls': L_FCLS, 'all': L_FOBJ | L_FCLS}[focal]
+        if bits and focal_gamma != 2:
+            bits |= L_POW
+    if label_smooth > 0:
+        bits |= L_SMOOTH
+    if obj_target == 'iou':
+        bits |= L_IOU
+    return bits
+
+
+def _instance_sets():
+    sets = {}
+    for focal, gamma in (('off', 2.0),) + tuple((f, g) for f in ('obj', 'cls', 'all') for g in (2.0, 1.5)):
+        for eps in (0.0, 0.1):
+            for target in ('label', 'iou'):
+                name = '+'.join([f'{focal}_g{gamma:g}'] * (focal != 'off') + ['smooth'] * (eps > 0) + ['iou'] * (target == 'iou'))
+                if name:                                                 # (all-off has none)
+                    sets[name] = dict(focal=focal, focal_gamma=gamma, label_smooth=eps, obj_target=target)
+    return sets
+
+
+INSTANCE_SETS = _instance_sets()
+ALL_BOX_MODES = ('mse', 'giou', 'diou', 'ciou')
+# the ends of what loss_launch accepts: gamma 1 (powf(m, 0)) and 5, gamma 0 with alpha (alpha-balanced bce through the L_POW instance), alpha
+# and label_smooth near 1, gamma 1 beside the IoU target
+EDGE_SETS = {
+    'all_g1': dict(focal='all', focal_gamma=1.0),
+    'all_g5': dict(focal='all', focal_gamma=5.0),
+    'all_g0_a.25': dict(focal='all', focal_gamma=0.0, focal_alpha=0.25),
+    'all_g1_a.75': dict(focal='all', focal_gamma=1.0, focal_alpha=0.75),
+    'cls_g5_a.999_smooth.9': dict(focal='cls', focal_gamma=5.0, focal_alpha=0.999, label_smooth=0.9),
+    'smooth.999': dict(label_smooth=0.999),
+    'obj_g1+iou': dict(focal='obj', focal_gamma=1.0, obj_target='iou'),
+}
+SWEEP_SETS = dict(INSTANCE_SETS, **EDGE_SETS)
+assert len(SWEEP_SETS) == len(INSTANCE_SETS) + len(EDGE_SETS)
+# the smallest inputs on which each failure exists: batch_size != batch, an image without objects and garbage under conf 0; two chunks of
+# blockIdx.y, the second of one box; box_loss_ref's four forced box relations (disjoint: the IoU target is exactly 0); logits of +-80
+INSTANCE_CASES = ('head_7x10', 'p257', 'geometry')
+EDGE_CASES = ('head_7x10', 'saturated')
+
+
+def corner_case():
+    """`geometry` with the disjoint cell's prediction moved to the label box's corner: 0.0125 and 0.02 clear of it in x and in y.  Both
+    overlaps are negative and their product, 0.00025, is positive and smaller than the two areas (0.01 + 0.003): an IoU built on the
+    overlaps before their clamp is 0.0196 here, where `geometry`'s own disjoint cell (product 0.0125, larger than the areas) gives a
+    negative quotient that the clamp of the target hides.  -> (anchors, y_true, y_pred, keywords, the cell)."""
+    anc, y_true, y_pred, cells = B.geometry_case()
+    b, r, c, a = cells[0]
+    y_pred = y_pred.copy()
+    y_pred[b, r, c, a, 0:4] = (B._logit(0.5), B._logit(0.6), np.log(0.1 / anc[a, 0]), np.log(0.1 / anc[a, 1]))
+    return anc, y_true, y_pred, parity_case('geometry')[3], cells[0]
+
+
+@functools.lru_cache(maxsize=None)
+def sweep_ref(case, box, oname, dtype=torch.float64):
+    """`autograd` of a SWEEP_SETS entry on a parity case, computed once and shared: the arrays are not to be written to."""
+    anc, y_true, y_pred, kw = parity_case(case)
+    return autograd(y_true, y_pred, anc, box_loss=box, dtype=dtype, **kw, **SWEEP_SETS[oname])
 
 
 # ---- the seeded inputs: box_loss_ref's one cell, 7x10 head with 20 classes, 255 / 256 / 257 predictions, and three of this file's

@@ -2,6 +2,7 @@
 holds the kernel to; the statement with every option off against tests/box_loss_ref.py; and the way of the five options through the Python
 layer, the command line, the Makefile and the header.  CPU only."""
 import ctypes as C
+import re
 import subprocess
 from pathlib import Path
 
@@ -66,6 +67,131 @@ def test_float32_build_of_the_reference_meets_the_recorded_atol():
                 worst = max(worst, a)
     print('largest', worst, 'recorded', R.F32_ATOL_MEASURED)
     assert worst <= R.F32_ATOL_MEASURED
+
+
+# ------------------------------------------------------------------------------ what tests/test_gpu_loss_instances.py rests on (reference alone)
+GPU_RTOL, GPU_ATOL = 2e-5, R.ATOL_FACTOR * R.F32_ATOL_MEASURED
+SWEEPS = ((R.INSTANCE_CASES, R.INSTANCE_SETS), (R.EDGE_CASES, R.EDGE_SETS))
+
+
+def test_instance_sets_are_the_27_cases_of_the_dispatch():
+    """(a) INSTANCE_SETS maps one-to-one onto the OPT values loss_launch_opt's switch has a case for, written out here from the enum and read
+    again from the macro list in the source; every EDGE_SETS entry runs one of them."""
+    F, K, P, S, I = R.L_FOBJ, R.L_FCLS, R.L_POW, R.L_SMOOTH, R.L_IOU
+    l4 = lambda o: {o, o | S, o | I, o | S | I}
+    want = {S, I, S | I} | l4(F) | l4(K) | l4(F | K) | l4(F | P) | l4(K | P) | l4(F | K | P)
+    bits = [R.instance_bits(**o) for o in R.INSTANCE_SETS.values()]
+    assert len(bits) == 27 and len(set(bits)) == 27 and set(bits) == want
+    assert all(R.instance_bits(**dict(R.OFF, **o)) in want for o in R.EDGE_SETS.values())
+    assert R.instance_bits(**R.OFF) == 0 and R.instance_bits(**dict(R.OFF, focal='all', focal_gamma=0.0)) == 0
+    src = (ROOT / 'k210_yolo_framework_amd' / 'csrc' / 'yk_loss.hip').read_text()
+    assert 'enum { L_FOBJ = 1, L_FCLS = 2, L_POW = 4, L_SMOOTH = 8, L_IOU = 16 };' in src
+    assert '#define YK_L4(o) YK_L1(o) YK_L1((o) | L_SMOOTH) YK_L1((o) | L_IOU) YK_L1((o) | L_SMOOTH | L_IOU)' in src
+    body = src[src.index('switch (bits) {'):]
+    cases = []
+    for macro, arg in re.findall(r'YK_L([14])\(([A-Z_| ]+)\)', body[:body.index('}')]):
+        o = 0
+        for name in arg.split('|'):
+            o |= getattr(R, name.strip())
+        cases += [o] if macro == '1' else sorted(l4(o))
+    assert sorted(cases) == sorted(want)                                 # each once
+
+
+def test_float32_build_of_the_reference_meets_the_recorded_atol_on_both_instance_sweeps():
+    """(b) A condition on the inputs of the two sweeps, not a new tolerance: the statement in torch float32 against float64 stays within the
+    figures of the existing GPU test on every (case, box mode, set) - gradient entries 4.. at rtol 2e-5 need no more than F32_ATOL_MEASURED,
+    every loss term is within 2e-5 of max(1, |ref|), the ignore masks are equal.  Measured: atol 2.6e-11 at most on the 27 x 4 sweep, 1.7e-10
+    on the edge sets (head_7x10, label_smooth 0.999); the worst loss term 1.7e-6 relative (xy on p257)."""
+    for sweep, (cases, sets) in zip(('instances', 'edges'), SWEEPS):
+        worst_a, worst_t = 0.0, (0.0, None)
+        for case in cases:
+            for box in R.ALL_BOX_MODES:
+                for oname in sets:
+                    l64, g64, i64, _ = R.sweep_ref(case, box, oname)
+                    l32, g32, i32, _ = R.sweep_ref(case, box, oname, torch.float32)
+                    assert np.array_equal(i64, i32), (case, box, oname)
+                    assert np.isfinite(g64).all() and np.isfinite(g32).all()
+                    worst_a = max(worst_a, R.atol_needed(g32[..., 4:], g64[..., 4:], GPU_RTOL))
+                    for term in R.TERMS:
+                        e = abs(l32[term] - l64[term]) / max(1.0, abs(l64[term]))
+                        assert e <= 2e-5, (case, box, oname, term, e)
+                        worst_t = max(worst_t, (e, f'{term} {case} {box} {oname}'))
+        print(sweep, 'float32 build needs atol', worst_a, 'recorded', R.F32_ATOL_MEASURED, 'worst loss term', worst_t)
+        assert worst_a <= R.F32_ATOL_MEASURED
+
+
+def _shows(bit, common):
+    """Where a flipped OPT bit shows in the statement: (loss terms, slice of the gradient's last axis).  L_FOBJ and L_IOU: obj (L_FOBJ also
+    noobj) and entry 4; L_FCLS and L_SMOOTH: cls and entries 5..; L_POW: those of the focal bits beside it."""
+    obj, cls = (('obj', 'noobj'), slice(4, 5)), (('cls',), slice(5, None))
+    if bit == R.L_POW:
+        return [w for f, w in ((R.L_FOBJ, obj), (R.L_FCLS, cls)) if common & f]
+    return [obj if bit in (R.L_FOBJ, R.L_IOU) else cls]
+
+
+def _shown(a, b, where):
+    """The largest difference of two references over `where`, in units of what the GPU test allows there."""
+    (la, ga, _, _), (lb, gb, _, _) = a, b
+    worst = 0.0
+    for terms, sl in where:
+        for t in terms:
+            worst = max(worst, abs(la[t] - lb[t]) / (2e-5 * max(1.0, abs(la[t]), abs(lb[t]))))
+        worst = max(worst, float((np.abs(ga[..., sl] - gb[..., sl]) / (GPU_RTOL * np.maximum(np.abs(ga[..., sl]), np.abs(gb[..., sl])) + GPU_ATOL)).max()))
+    return worst
+
+
+@pytest.mark.parametrize('case', R.INSTANCE_CASES)
+def test_two_instances_one_bit_apart_differ_by_100_times_the_gpu_tolerance(case):
+    """(c) A wrong instance cannot pass: for every box mode and every two INSTANCE_SETS entries whose OPT differ in one bit, the float64
+    references differ, in a loss term or gradient entry of `_shows`, by at least 100 times what the GPU test allows there (2e-5 max(1, |ref|)
+    for a term, rtol |ref| + atol for an entry).  Every bit is observable on every case: each has object cells with classes.  On `geometry`
+    L_IOU alone shows at the disjoint cell, whose target falls from 1 to exactly 0."""
+    names = list(R.INSTANCE_SETS)
+    bits = {n: R.instance_bits(**R.INSTANCE_SETS[n]) for n in names}
+    disjoint = B.geometry_case()[3][0]
+    pairs, least = 0, {}
+    for box in R.ALL_BOX_MODES:
+        for i, u in enumerate(names):
+            for v in names[i + 1:]:
+                flip = bits[u] ^ bits[v]
+                if flip not in R.BIT_NAMES:
+                    continue
+                a, b = R.sweep_ref(case, box, u), R.sweep_ref(case, box, v)
+                d = _shown(a, b, _shows(flip, bits[u] & bits[v]))
+                assert d >= 100, (box, u, v, R.BIT_NAMES[flip], d)
+                least[R.BIT_NAMES[flip]] = min(least.get(R.BIT_NAMES[flip], np.inf), d)
+                if case == 'geometry' and flip == R.L_IOU:
+                    ga, gb = a[1][disjoint][4], b[1][disjoint][4]
+                    assert abs(ga - gb) >= 100 * (GPU_RTOL * max(abs(ga), abs(gb)) + GPU_ATOL), (box, u, v, ga, gb)
+                pairs += 1
+    print(case, pairs, 'pairs; least difference / allowance per bit:', least)
+    assert pairs == 4 * 60 and set(least) == set(R.BIT_NAMES.values())
+
+
+def test_iou_target_on_the_forced_geometries():
+    """(d) obj_target='iou' on `geometry`: the returned target is exactly 0.0 at the disjoint cell, strictly inside (0, 1) at the cells with
+    the prediction inside the label box, around it and across it, and the same array in all four box modes."""
+    cells = B.geometry_case()[3]
+    zo = [R.sweep_ref('geometry', box, 'iou')[3] for box in R.ALL_BOX_MODES]
+    assert zo[0][cells[0]] == 0.0
+    assert all(0.0 < zo[0][c] < 1.0 for c in cells[1:])
+    assert all(np.array_equal(z, zo[0]) for z in zo[1:])
+
+
+def test_corner_case_is_disjoint_in_both_axes_with_a_product_below_the_areas():
+    """What the GPU test of `corner_case` rests on: the target is exactly 0, an IoU of the unclamped overlaps would be about 0.02, and the
+    float32 build of the statement stays within the recorded figures on it."""
+    anc, y_true, y_pred, kw, cell = R.corner_case()
+    b, t = B.decode(y_pred, anc)[0][cell], y_true[cell][0:4].astype(np.float64)
+    assert B.geometry_of(b, t) == 'disjoint'
+    raw = np.minimum(b[0:2] + b[2:4] / 2, t[0:2] + t[2:4] / 2) - np.maximum(b[0:2] - b[2:4] / 2, t[0:2] - t[2:4] / 2)
+    assert (raw < 0).all() and 0.015 < raw.prod() / (b[2] * b[3] + t[2] * t[3] - raw.prod()) < 0.025
+    for box in R.ALL_BOX_MODES:
+        l64, g64, i64, zo = R.autograd(y_true, y_pred, anc, box_loss=box, **kw, obj_target='iou')
+        l32, g32, i32, _ = R.autograd(y_true, y_pred, anc, box_loss=box, dtype=torch.float32, **kw, obj_target='iou')
+        assert zo[cell] == 0.0 and np.array_equal(i64, i32)
+        assert R.atol_needed(g32[..., 4:], g64[..., 4:], GPU_RTOL) <= R.F32_ATOL_MEASURED
+        assert all(abs(l32[k] - l64[k]) <= 2e-5 * max(1.0, abs(l64[k])) for k in R.TERMS)
 
 
 def test_the_inputs_are_what_they_say():
