@@ -19,7 +19,12 @@
 //   mma(k)    A x B on v_mfma_f32_16x16x32_f16, three products per tile
 //
 // Single-buffered and phase-shifted (two s_barriers per step): the patch of step k+1 is requested when dw(k) is over and lands under
-// mma(k); the weight fragments of step k are requested before dw(k).  One stage of patch + A tile is 23 - 39 KB and the small tiles are
+// mma(k); the weight fragments are requested a PHASE AHEAD into the one set of registers there is - W(0) at the top of the kernel, right
+// behind the first patch request (in a fused-stem block: before the whole stem computation), W(k+1) when the last MFMA of step k has been
+// issued - so they fly under the wait for the patch, the barrier and dw(k+1).  The wait at the top of a step is COUNTED: the memory
+// counter retires in order and a wave's 2 * TNW fragment loads are its youngest requests, so `vmcnt(2 * TNW)` means "my patch pieces
+// have landed" and leaves the fragments in flight; the compiler is made to wait for them between the second barrier and the request of
+// patch(k+1), so that no vector-memory wait stands in the MFMA sweep.  One stage of patch + A tile is 23 - 39 KB and the small tiles are
 // held to 128 registers, so FOUR workgroups share a CU and their DMA, depthwise (VALU) and MFMA phases overlap - co-residency is what
 // these launches' time follows (round 5: 3 -> 4 workgroups = -8 ... -15 %; two stages, which halve it, never paid; removing the depthwise
 // pass's LDS reads in a pricing build changes nothing).  The output tile leaves through LDS in passes of IPP row blocks, or - fp32
@@ -190,7 +195,7 @@ __device__ __forceinline__ void xb_stem_patch(const xb_args &a, const void *winp
 // items are split into their two channel halves (512 half items), every deposit / copy-out loop strides by 512.  Two such workgroups
 // take the registers of a CU's SIMDs that two 4-wave workgroups of <= 256 took; each serial phase of a step sits on twice the waves.
 template <int TM, int TN, int SG, bool F32IN = false, int NW = 4>
-__global__ void __launch_bounds__(NW * 64, (NW == 8 || TM * TN > 8 ? 2 : 4)) xb_kernel(const xb_args a) {   // 2 (3) workgroups per CU: <= 256 (168) registers, <= 128 on 8 waves; the fused-stem block stays under 128 by itself (4 per CU)
+__global__ void __launch_bounds__(NW * 64, (NW == 4 && TM * TN > 8 ? 2 : 4)) xb_kernel(const xb_args a) {   // waves per SIMD -> 2 (3) workgroups per CU: <= 256 (168) registers; <= 128 on 8 waves (a BOUND since the fragments live across the loop edge: left to itself the scheduler reads all eight A fragments ahead of the MFMAs, 136); the fused-stem block stays under 128 by itself (4 per CU)
     typedef xb_cfg<TM, TN> C;
     constexpr int BM = C::BM, BN = C::BN;
     constexpr bool STEM = SG > 0;
@@ -286,7 +291,34 @@ __global__ void __launch_bounds__(NW * 64, (NW == 8 || TM * TN > 8 ? 2 : 4)) xb_
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rsp, (lds_ptr_t)(PARb + wid * 1024), 16, op, 0, 0, 0);
         }
     };
+    // The pointwise weights of a step.  Wave w multiplies ITS 16 * TN output channels and nobody else's, so a weight tile in LDS would be
+    // written once and read once by one wave: the fragments go from global memory straight into that wave's registers (host order =
+    // fragment order: one coalesced 1 KB load per 16-channel block and half).  No LDS stage for them: 6 - 24 KB less per workgroup, which
+    // is what lets a fourth workgroup onto a CU.  ONE set of fragments, requested a phase ahead: W(0) here, right behind the first patch
+    // request (the address needs blockIdx, wid, lane and rot only), W(k+1) when the last MFMA of step k has been issued and the registers
+    // are dead.  A wave whose channels all lie past N (`wave_live`) requests nothing.
+    const bool wave_live = n0 + wid * TNW * 16 < a.N;                 // wave-uniform
+    const bool wreq = wave_live && !X_DBG(a, 16);
+    // fragment offsets: rows of 64 bytes with the 16-byte pieces swizzled (weight tile; A tile of a stored-tensor block), rows of GL * 16
+    // bytes in a fused-stem block (48-byte rows of a 24-channel stem touch every bank once per 16 lanes without a swizzle)
+    const int foff = fr * 64 + ((fq ^ ((fr >> 1) & 3)) * 16);
+    half8 wh[TNW], wl[TNW];
+#pragma unroll
+    for (int j = 0; j < TNW; ++j) wh[j] = wl[j] = half8{0, 0, 0, 0, 0, 0, 0, 0};
+    auto load_w = [&](int it_) {                                  // the 2 * TNW fragment loads of loop step it_
+        const uint32_t ws = (uint32_t)(n0 >> 4) * 2048u + (uint32_t)kstep(it_) * wstep + (uint32_t)(wid * TNW) * 2048u + (uint32_t)foff;
+#pragma unroll
+        for (int j = 0; j < TNW; ++j) {
+            wh[j] = __builtin_bit_cast(half8, __builtin_amdgcn_raw_buffer_load_b128(rsw, ws + (uint32_t)j * 2048u, 0, 0));
+            wl[j] = __builtin_bit_cast(half8, __builtin_amdgcn_raw_buffer_load_b128(rsw, ws + (uint32_t)j * 2048u + 1024u, 0, 0));
+        }
+    };
     if (!X_DBG(a, 1)) dma_patch(0);
+    // (the fences keep the fragment loads the YOUNGEST vector-memory requests behind a patch request: the counted wait at the loop top
+    // stands on that order)
+    asm volatile("" ::: "memory");
+    if (wreq) load_w(0);
+    asm volatile("" ::: "memory");
     if constexpr (STEM) {
         // ---- the patch of the depthwise input = the stem conv's output on (PH x PW) positions, straight from the frames.
         // (1) the frame window those positions need, normalised (`img / np.max(img)`, tools/utils.py:405), as fp32 in LDS (the A tile's
@@ -394,11 +426,7 @@ __global__ void __launch_bounds__(NW * 64, (NW == 8 || TM * TN > 8 ? 2 : 4)) xb_
     for (int i = 0; i < TM; ++i)
 #pragma unroll
         for (int j = 0; j < TNW; ++j) acc[i][j] = floatx4{0.f, 0.f, 0.f, 0.f};
-    const bool wave_live = n0 + wid * TNW * 16 < a.N;                 // wave-uniform
-    // fragment offsets: rows of 64 bytes with the 16-byte pieces swizzled (weight tile; A tile of a stored-tensor block), rows of GL * 16
-    // bytes in a fused-stem block (48-byte rows of a 24-channel stem touch every bank once per 16 lanes without a swizzle)
-    const int foff = fr * 64 + ((fq ^ ((fr >> 1) & 3)) * 16);
-    // (a k group the stem does not have: the lane re-reads group 0 - finite values against weight rows that are zero)
+    // the A tile's fragment offset (a k group the stem does not have: the lane re-reads group 0 - finite values against weight rows that are zero)
     const int afoff = fr * (GL * 16) + (GL == 4 ? (fq ^ ((fr >> 1) & 3)) : (fq < GL ? fq : 0)) * 16;
     // ---- this thread's depthwise items.  item = (pixel p, group q of the step[, channel half hf of the group on 8 waves]); which
     // pixel, whether it is alive, where its taps start in the patch and where it goes in the A tile depend on tid, the tile and the
@@ -436,26 +464,16 @@ __global__ void __launch_bounds__(NW * 64, (NW == 8 || TM * TN > 8 ? 2 : 4)) xb_
     }
     const int nk = X_DBG(a, 1) ? 0 : a.nk;
     for (int ks = 0; ks < nk; ++ks) {
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // this wave's pieces of patch(ks) have landed
-        __builtin_amdgcn_s_barrier();                                 // everybody's have; mma(ks-1) is over: A and the weight tile are free
+        // this wave's pieces of patch(ks) have landed.  The memory counter retires in order and the 2 * TNW fragment loads of W(ks) are
+        // the youngest requests of a wave that made them (anything younger still - the prologue's frame window, per-image factors - only
+        // makes the wait stricter): such a wave leaves them in flight under the depthwise pass, the others wait for everything
+        if (wreq) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(2 * TNW) : "memory");
+        else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();                                 // everybody's have; mma(ks-1) is over: the A tile is free
         asm volatile("" ::: "memory");
         if (ks == 0) { XB_STAMP(3) }
         if (ks == 1) { XB_STAMP(13) }
-        // The pointwise weights of this step.  Wave w multiplies ITS 16 * TN output channels and nobody else's, so a weight tile in LDS
-        // would be written once and read once by one wave: the fragments go from global memory straight into that wave's registers
-        // (host order = fragment order: one coalesced 1 KB load per 16-channel block and half), requested here, used after the depthwise
-        // pass.  No LDS stage for them: 6 - 24 KB less per workgroup, which is what lets a fourth workgroup onto a CU.
-        half8 wh[TNW], wl[TNW];
-        if (wave_live && !X_DBG(a, 16)) {
-            const uint32_t ws = (uint32_t)(n0 >> 4) * 2048u + (uint32_t)kstep(ks) * wstep + (uint32_t)(wid * TNW) * 2048u + (uint32_t)foff;
-#pragma unroll
-            for (int j = 0; j < TNW; ++j) {
-                wh[j] = __builtin_bit_cast(half8, __builtin_amdgcn_raw_buffer_load_b128(rsw, ws + (uint32_t)j * 2048u, 0, 0));
-                wl[j] = __builtin_bit_cast(half8, __builtin_amdgcn_raw_buffer_load_b128(rsw, ws + (uint32_t)j * 2048u + 1024u, 0, 0));
-            }
-        }
-        // two stages: the other one is free - request the patch of step ks+1 now (AFTER the weight loads: the memory counter retires in
-        // order, and the weights are needed first)
+        // two stages: the other one is free - request the patch of step ks+1 now
         if (XB_DB && ks + 1 < nk) dma_patch(ks + 1);
         const unsigned char *HI = xsm + ((XB_DB & ks) & 1) * STG, *LO = HI + a.n16p * 16;
         // the parameter slice is read as DWORDS, like the patch: a float-typed LDS read makes the compiler wait for every LDS-DMA in
@@ -521,10 +539,10 @@ __global__ void __launch_bounds__(NW * 64, (NW == 8 || TM * TN > 8 ? 2 : 4)) xb_
                                     d2[c] = __builtin_elementwise_fma(x2, w2[c], d2[c]);
                                 }
                             }
-                            // the tiles held to 128 registers: one patch row's reads in flight at a time, on <3,2> one tap's (a row's
-                            // there, or all nine anywhere, spill two registers around the channel loop)
+                            // the tiles held to 128 registers: one patch row's reads in flight at a time, on <3,2> and <4,2> one tap's (a
+                            // row's there, or all nine anywhere, spill two registers around the channel loop)
                             if constexpr (TM * TN <= 8 && !STEM)
-                                if (t < 8 && (t % 3 == 2 || (TM == 3 && TN == 2))) __builtin_amdgcn_sched_barrier(0);
+                                if (t < 8 && (t % 3 == 2 || (TM >= 3 && TN == 2))) __builtin_amdgcn_sched_barrier(0);
                         }
                     };
                     if (f32patch) taps(std::true_type{});
@@ -602,6 +620,11 @@ __global__ void __launch_bounds__(NW * 64, (NW == 8 || TM * TN > 8 ? 2 : 4)) xb_
         asm volatile("" ::: "memory");
         if (ks == 0) { XB_STAMP(5) }
         if (ks == 1) { XB_STAMP(15) }
+        // W(ks) has had the whole depthwise pass to arrive.  The compiler cannot count the patch pieces requested below (they depend on
+        // runtime conditions) and would wait for ALL vector memory in front of the first MFMA - the patch of step ks+1 included, which is
+        // meant to land under the MFMAs: it is made to wait for the fragments HERE, while nothing else is in flight
+#pragma unroll
+        for (int j = 0; j < TNW; ++j) asm volatile("" : "+v"(wh[j]), "+v"(wl[j]));
         if (!XB_DB && ks + 1 < nk) dma_patch(ks + 1);
         // ---- pointwise: three products per tile (a wave whose 16*TN channels all lie past N - the last quarter of a 48- or 96-channel
         // layer in a 64- / 128-wide tile - has nothing to multiply nor, below, to stage)
@@ -626,6 +649,10 @@ __global__ void __launch_bounds__(NW * 64, (NW == 8 || TM * TN > 8 ? 2 : 4)) xb_
 #pragma unroll
                 for (int j = 0; j < TNW; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[j], xh[i], acc[i][j], 0, 0, 0);
         }
+        // W(ks+1): the fragment registers are dead from here to the next step's MFMAs
+        asm volatile("" ::: "memory");
+        if (wreq && ks + 1 < nk) load_w(ks + 1);
+        asm volatile("" ::: "memory");
     }
     XB_STAMP(6)
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
