@@ -27,6 +27,7 @@
 #                    [EMA=True EMADECAY=0.9999 EMATAU=2000]: an exponential moving average of the weights (decay ramped over EMATAU updates) is
 #                    validated and saved as yolo_ema_model.h5 beside the usual checkpoint; [CLIPNORM=10.0]: global-norm gradient clipping (0: off);
 #                    [LRSCHED=cosine|step|constant WARMUP=N LRFINAL=0.01]: linear warmup and a schedule over the whole run: DESIGN.md 3.21
+#                    [LABELS=gpu]: the label grids are built on the GPU from the boxes; [ASSIGN=multi ASSIGNIOU=0.213]: every anchor that fits a box better than ASSIGNIOU is trained on it: DESIGN.md 3.26
 #   make kmodel      CKPT=yolo_model.h5 OUT=yolo.kmodel|.kfpkg [SYNTHETIC=256 | CALIB=data/voc_img_ann.npy]: 8-bit K210 model, calibrated on the GPU
 #                    [RANGES=yolo_qat_ranges.npz]: the ranges a QAT run learned instead of a calibration
 #                    [CALIBMETHOD=minmax|percentile|mse CALIBPCT=99.99 CALIBBINS=2048]: minmax (default) takes each tensor's exact range; percentile
@@ -134,6 +135,9 @@ CLIPNORM      ?= 0
 LRSCHED       ?=
 WARMUP        ?= 0
 LRFINAL       ?= 0.01
+LABELS        ?= host
+ASSIGN        ?= best
+ASSIGNIOU     ?= 0.213
 # eval only
 PRECISION     ?= f16x2
 ANN           ?= data/$(DATASET)_img_ann.npy
@@ -196,6 +200,7 @@ TRAIN_ARGS = --pre_ckpt $(CKPT) --augmenter $(IAA) --batch_size $(BATCH) --rand_
              $(if $(TEACHERDEPTH),--teacher_depth $(TEACHERDEPTH))) \
              $(if $(filter True,$(EMA)),--ema True --ema_decay $(EMADECAY) --ema_tau $(EMATAU)) \
              $(if $(filter-out 0 0.0,$(CLIPNORM)),--clip_norm $(CLIPNORM)) \
+             $(if $(filter-out host,$(LABELS)),--labels $(LABELS)) $(if $(filter-out best,$(ASSIGN)),--assign $(ASSIGN) --assign_iou $(ASSIGNIOU)) \
              $(if $(LRSCHED),--lr_schedule $(LRSCHED) --warmup_steps $(WARMUP) --lr_final $(LRFINAL))$(if \
              $(filter-out off,$(FOCAL))$(filter-out 0 0.0,$(LABELSMOOTH))$(filter-out label,$(OBJTARGET)), --focal $(or $(FOCAL),off) \
              --focal_gamma $(FOCALGAMMA) --focal_alpha $(FOCALALPHA) --label_smooth $(LABELSMOOTH) --obj_target $(or $(OBJTARGET),label))

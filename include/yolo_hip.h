@@ -462,6 +462,43 @@ int yk_mosaic_ragged_u8(const uint8_t *d_src, size_t src_bytes, const yk_ragged_
  * no byte.  n == 0: YK_OK, nothing launched.  A NULL pointer with n > 0, n < 0, h <= 0, w <= 0 or 3*n*h*w beyond size_t: YK_ERR_ARG;
  * no device: YK_ERR_NO_DEVICE.  Can be recorded in a graph. */
 int yk_hsv_jitter_u8(uint8_t *d_frames, int n, int h, int w, const double *d_params, void *stream);
+/* ---- training labels from boxes (Helper.batch_box_to_label, k210_yolo_framework_amd/helper.py) ------
+ * The dense label grids of a batch, built on the device from its boxes: d_boxes [n_boxes][5] float64 rows (cls, x, y, w, h) relative to the
+ * network frame, sample i owning rows d_first[i] .. d_first[i + 1] - 1 (d_first [n + 1] int32).  d_labels is ONE flat fp32 buffer: layer 0's
+ * [n][out_h][out_w][A][5 + class_num], then layer 1's, and so on; every element of it is written (a buffer full of anything comes out
+ * defined).  The rule is Helper.batch_box_to_label's, in float64, numpy's operation order, contraction off:
+ *   fit[k][l][a] = o / (w h + aw ah - o),  o = max(min(w, aw), 0) max(min(h, ah), 0)                        (Helper._fake_iou)
+ *   primary slot of box k: the first argmax of fit[k] over the flattened (l, a); YK_ASSIGN_MULTI: secondary slots, every other (l, a) with
+ *   fit[k][l][a] > assign_iou; the cell of a slot in layer l is (floor(x out_w[l]), floor(y out_h[l]));
+ *   a slot's first five entries are (float)clip(x y w h, 1e-8, 1) and 1 of the candidate with the largest key is_primary * n_boxes + k among
+ *   those written there - the last primary box, else the last secondary box - and entry 5 + cls is 1 for every candidate written there.
+ * Bit-identical to the host statement for every box whose cells lie inside the grids of all the layers it is written to.  Where numpy raises
+ * (index out_w) or wraps (negative index) the kernel writes NOTHING of that box, in any layer, and records the smallest such row index of
+ * d_boxes in *d_status with an integer atomicMin; the call sets *d_status to INT32_MAX first, which is what a clean batch leaves.  A row
+ * whose class, truncated toward zero as numpy's astype(int) does, is not in [0, class_num), or with an x or y that is not finite, counts as such a box.  d_first is not trusted: rows outside
+ * [0, n_boxes) are not read.
+ * One launch (blockIdx.y the sample, chunked at 65535; blockIdx.x a chunk of YK_LABEL_CHUNK floats of one layer of that sample) after a
+ * 4-byte memset node: a workgroup builds its chunk in LDS from the sample's candidate table - YK_LABEL_LDS_BOXES boxes at a time, a sample
+ * with more is walked in tiles of that many, read from global memory again, by the same rule - and stores it once, 16 bytes per lane where
+ * the address allows.  No workgroup waits for another and no floating-point atomics: two calls give the same bits.  Can be recorded in a graph.
+ * n == 0: YK_OK, nothing launched.  NULL cfg, d_first, d_labels or d_status with n > 0, NULL d_boxes with n_boxes > 0, n < 0, n_boxes outside
+ * 0 .. 2^30 - 1, n_layers outside 1 .. YK_MAX_LAYERS, an anchor_num outside 1 .. YK_MAX_ANCHORS, out_h or out_w <= 0, class_num < 1, an
+ * unknown assign, an assign_iou outside (0, 1) with YK_ASSIGN_MULTI, sizes beyond size_t: YK_ERR_ARG, the message names the function and the
+ * argument, nothing launched; these checks come before the device is needed.  No device: YK_ERR_NO_DEVICE. */
+#define YK_LABEL_LDS_BOXES 512
+#define YK_LABEL_CHUNK 4096
+enum { YK_ASSIGN_BEST = 0, YK_ASSIGN_MULTI = 1 };
+typedef struct {
+    int32_t n_layers, class_num;
+    int32_t assign;                                     /* YK_ASSIGN_* */
+    int32_t reserved;                                   /* 0 */
+    int32_t out_h[YK_MAX_LAYERS], out_w[YK_MAX_LAYERS]; /* Helper.out_hw */
+    int32_t anchor_num[YK_MAX_LAYERS];
+    double anchors[YK_MAX_LAYERS][YK_MAX_ANCHORS][2];   /* np.asarray(Helper.anchors, float): (w, h), image-relative */
+    double assign_iou;                                  /* read with YK_ASSIGN_MULTI only */
+} yk_label_cfg_t;                                       /* 584 bytes, no padding */
+int yk_boxes_to_labels_f32(const yk_label_cfg_t *cfg, const double *d_boxes, int n_boxes, const int32_t *d_first, int n, float *d_labels,
+                           int32_t *d_status, void *stream);
 /* Draws detections INTO the pictures of a ragged batch, in place (inference.py's PIL loop plus keras_inference.py:137-174's label with
  * its filled background), by the painter's rule: for picture i and its rows k = 0 .. count_i - 1 in order, later paint over earlier:
  *   corners   t = max(0, floorf(top + 0.5f)), l likewise from left; b = min(h, floorf(bottom + 0.5f)), r = min(w, floorf(right + 0.5f))

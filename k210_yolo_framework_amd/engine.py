@@ -72,7 +72,15 @@ class LossCfgOpt(C.Structure):
                                      ('label_smooth', C.c_float), ('obj_target', C.c_int32)]
 
 
+class LabelCfg(C.Structure):
+    """yk_label_cfg_t"""
+    _fields_ = [('n_layers', C.c_int32), ('class_num', C.c_int32), ('assign', C.c_int32), ('reserved', C.c_int32),
+                ('out_h', C.c_int32 * YK_MAX_LAYERS), ('out_w', C.c_int32 * YK_MAX_LAYERS), ('anchor_num', C.c_int32 * YK_MAX_LAYERS),
+                ('anchors', (C.c_double * 2) * YK_MAX_ANCHORS * YK_MAX_LAYERS), ('assign_iou', C.c_double)]
+
+
 BOX_LOSSES = {'mse': 0, 'giou': 1, 'diou': 2, 'ciou': 3}      # YK_BOX_LOSS_* (include/yolo_hip.h)
+LABEL_STATUS_CLEAN = 2 ** 31 - 1                              # what yk_boxes_to_labels_f32 leaves in its status word for a clean batch
 
 
 def library_path() -> Path:
@@ -860,6 +868,69 @@ def hsv_jitter_u8(frames, params, stream=None):
     assert tuple(params.shape) == (n, 3), tuple(params.shape)
     call('yk_hsv_jitter_u8', frames, n, frames.shape[1], frames.shape[2], params, _stream(stream))
     return frames
+
+
+def make_label_cfg(helper, assign: str = 'best', assign_iou: float = 0.213) -> LabelCfg:
+    """yk_label_cfg_t of a Helper: its grids, its anchors as float64 and the positive assignment (Helper.box_to_label).  CPU only."""
+    from .helper import ASSIGN_MODES, Helper
+    try:
+        Helper.check_assign(assign, assign_iou)
+    except ValueError as e:
+        raise YkError(str(e)) from e
+    anchors = [np.asarray(a, float).reshape(-1, 2) for a in helper.anchors]
+    if not 1 <= len(anchors) <= YK_MAX_LAYERS or any(not 1 <= len(a) <= YK_MAX_ANCHORS for a in anchors):
+        raise YkError(f'labels: {len(anchors)} layers of {[len(a) for a in anchors]} anchors: at most {YK_MAX_LAYERS} of {YK_MAX_ANCHORS}')
+    cfg = LabelCfg()
+    cfg.n_layers, cfg.class_num, cfg.assign, cfg.assign_iou = len(anchors), int(helper.class_num), ASSIGN_MODES[assign], float(assign_iou)
+    for l, a in enumerate(anchors):
+        cfg.out_h[l], cfg.out_w[l], cfg.anchor_num[l] = int(helper.out_hw[l][0]), int(helper.out_hw[l][1]), len(a)
+        for k, (w, h) in enumerate(a):
+            cfg.anchors[l][k][0], cfg.anchors[l][k][1] = float(w), float(h)
+    return cfg
+
+
+def boxes_to_labels(boxes, first, helper, assign: str = 'best', assign_iou: float = 0.213, stream=None, out=None, status=None):
+    """The label grids of a batch, built on the device (yk_boxes_to_labels_f32; the rule is Helper.batch_box_to_label's, bit for bit):
+    `boxes` [N, 5] float64 rows (cls, x, y, w, h) and `first` [n + 1] int32, sample i owning rows first[i] .. first[i + 1] - 1 - both either
+    cuda tensors, or host arrays, which are checked here (rows that are not finite, offsets that do not ascend from 0 to N: refused) and
+    uploaded.  -> ([one contiguous view [n, h, w, A, 5 + C] float32 per layer of ONE flat buffer], status): status is a cuda int32 [1] that
+    holds INT32_MAX, or the smallest row of `boxes` that numpy could not have written (a cell outside its grid, a class outside
+    [0, C)) and of which nothing was written.  out / status: buffers to reuse (cuda float32 [n * floats per sample], int32 [1]).  Does
+    not synchronise."""
+    import torch
+    require_gpu()
+    cfg = helper if isinstance(helper, LabelCfg) else make_label_cfg(helper, assign, assign_iou)
+    with torch.cuda.stream(torch.cuda.current_stream() if stream is None else stream):
+        if not torch.is_tensor(first):
+            f = np.ascontiguousarray(first, np.int32).reshape(-1)
+            b = np.ascontiguousarray(boxes, np.float64).reshape(-1, 5) if not torch.is_tensor(boxes) else None
+            if len(f) < 1 or f[0] != 0 or (np.diff(f) < 0).any() or (b is not None and f[-1] != len(b)):
+                raise YkError(f'boxes_to_labels: first must ascend from 0 to the number of boxes, got {f.tolist()[:8]} ..')
+            first = torch.from_numpy(f).cuda()
+        if not torch.is_tensor(boxes):
+            b = np.ascontiguousarray(boxes, np.float64).reshape(-1, 5)
+            if not np.isfinite(b).all():
+                raise YkError(f'boxes_to_labels: box {int(np.nonzero(~np.isfinite(b).all(1))[0][0])} is not finite')
+            boxes = torch.from_numpy(b).cuda()
+        assert boxes.is_cuda and boxes.dtype == torch.float64 and boxes.is_contiguous() and boxes.dim() == 2 and boxes.shape[1] == 5, 'boxes: cuda float64 [N, 5]'
+        assert first.is_cuda and first.dtype == torch.int32 and first.is_contiguous() and first.dim() == 1 and first.numel() >= 1 and first.device == boxes.device
+        n = int(first.numel()) - 1
+        shapes = [(n, int(cfg.out_h[l]), int(cfg.out_w[l]), int(cfg.anchor_num[l]), 5 + int(cfg.class_num)) for l in range(cfg.n_layers)]
+        sizes = [int(np.prod(s, dtype=np.int64)) for s in shapes]
+        if out is None:
+            out = torch.empty((sum(sizes),), dtype=torch.float32, device=boxes.device)
+        if status is None:
+            status = torch.empty((1,), dtype=torch.int32, device=boxes.device)
+        if n == 0:                                                          # (the library launches nothing)
+            status.fill_(LABEL_STATUS_CLEAN)
+    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == sum(sizes) and out.device == boxes.device
+    assert status.is_cuda and status.dtype == torch.int32 and status.numel() == 1 and status.device == boxes.device
+    call('yk_boxes_to_labels_f32', C.byref(cfg), boxes if boxes.numel() else None, int(boxes.shape[0]), first, n, out, status, _stream(stream))
+    views, at = [], 0
+    for s, size in zip(shapes, sizes):
+        views.append(out[at:at + size].view(s))
+        at += size
+    return views, status
 
 
 def draw_detections_u8(packed, table, dets, counts, colormap, atlas, stream=None, max_pixels: Optional[int] = None):

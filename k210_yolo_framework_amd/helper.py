@@ -18,6 +18,7 @@ from typing import Iterator, List, Optional, Sequence, Tuple, Union
 import numpy as np
 
 INFO, ERROR, NOTE = '[ INFO  ]', '[ ERROR ]', '[ NOTE  ]'     # tools/utils.py:15-17 (uncoloured)
+ASSIGN_MODES = {'best': 0, 'multi': 1}                        # YK_ASSIGN_* (include/yolo_hip.h)
 
 # data/voc_anchor.npy of the reference == main.c:46-52 (w,h) relative to the whole image
 VOC_ANCHORS = np.array([[[0.76120044, 0.57155991], [0.6923348, 0.88535553], [0.47163042, 0.34163313]],
@@ -96,10 +97,24 @@ class Helper(object):
         table = Helper._fake_iou(wh, self.anchors)
         return np.unravel_index(int(table.argmax()), table.shape)
 
-    def box_to_label(self, true_box: np.ndarray, out: Optional[List[np.ndarray]] = None) -> List[np.ndarray]:
+    @staticmethod
+    def check_assign(assign: str, assign_iou: float) -> None:
+        """The positive-assignment options of `box_to_label`: assign 'best' | 'multi'; with 'multi' assign_iou inside (0, 1)."""
+        if assign not in ASSIGN_MODES:
+            raise ValueError(f'assign {assign!r}: choose one of ' + ', '.join(repr(k) for k in ASSIGN_MODES))
+        if assign == 'multi' and not 0.0 < float(assign_iou) < 1.0:          # (a NaN fails both comparisons)
+            raise ValueError(f'assign_iou {assign_iou!r}: a threshold inside (0, 1)')
+
+    def box_to_label(self, true_box: np.ndarray, out: Optional[List[np.ndarray]] = None, assign: str = 'best',
+                     assign_iou: float = 0.213) -> List[np.ndarray]:
         """[n,5] = [cls,x,y,w,h] (image-relative) -> one [h,w,A,5+C] float32 grid per layer (utils.py:207-230).
         A box lands in the cell of its centre, at the best-fitting anchor: xywh clipped to [1e-8, 1], conf 1, one-hot class.
-        Boxes are written in order, so a later box in the same slot replaces xywh and ADDS its class bit, like the reference."""
+        Boxes are written in order, so a later box in the same slot replaces xywh and ADDS its class bit, like the reference.
+        assign='multi' (not in the reference): besides that PRIMARY slot - the first argmax of the fit over all (layer,
+        anchor) - a box is also written to every other (layer, anchor) whose fit is above assign_iou (strictly), in the cell of its
+        centre in that layer: its SECONDARY slots.  All secondary writes come first, in box order, then all primary writes, in box order:
+        a slot's xywh is its last primary box's if it has one, else its last secondary box's; class bits add up over everything written."""
+        Helper.check_assign(assign, assign_iou)
         if out is None:
             grids = [np.zeros((*map(int, self.out_hw[l]), len(self.anchors[l]), 5 + self.class_num), np.float32)
                      for l in range(self.output_number)]
@@ -111,6 +126,15 @@ class Helper(object):
         if len(boxes):
             fit = Helper._fake_iou(boxes[:, None, None, 3:5], self.anchors[None])            # [n, L, A]
             layer, anchor = np.unravel_index(fit.reshape(len(boxes), -1).argmax(1), fit.shape[1:])
+            if assign == 'multi':
+                for k in range(len(boxes)):
+                    for l, a in zip(*np.nonzero(fit[k] > assign_iou)):
+                        if (l, a) != (layer[k], anchor[k]):
+                            cx, cy = self._xy_grid_index(boxes[k, 1:3], l)
+                            slot = grids[l][cy, cx, a]
+                            slot[:4] = np.clip(boxes[k, 1:5], 1e-8, 1.0)
+                            slot[4] = 1.0
+                            slot[5 + int(boxes[k, 0])] = 1.0
             for k, (l, a) in enumerate(zip(layer, anchor)):
                 cx, cy = self._xy_grid_index(boxes[k, 1:3], l)
                 slot = grids[l][cy, cx, a]
@@ -119,11 +143,13 @@ class Helper(object):
                 slot[5 + int(boxes[k, 0])] = 1.0
         return grids
 
-    def batch_box_to_label(self, boxes_per_sample: Sequence[np.ndarray]) -> List[np.ndarray]:
+    def batch_box_to_label(self, boxes_per_sample: Sequence[np.ndarray], assign: str = 'best', assign_iou: float = 0.213) -> List[np.ndarray]:
         """`box_to_label` of every sample of a batch in a handful of array operations -> one [n,h,w,A,5+C] float32 array per layer,
         bit-identical to stacking the per-sample results (boxes are scattered in order: a later box in the same slot replaces xywh
         and adds its class bit).  The input pipeline's host side is bound by the NUMBER of small numpy calls on a busy host, not by
-        their work: ~10 calls per batch here instead of ~12 per box."""
+        their work: ~10 calls per batch here instead of ~12 per box.  assign, assign_iou: as `box_to_label`; this is the statement
+        yk_boxes_to_labels_f32 is held to."""
+        Helper.check_assign(assign, assign_iou)
         n = len(boxes_per_sample)
         grids = [np.zeros((n, *map(int, self.out_hw[l]), len(self.anchors[l]), 5 + self.class_num), np.float32)
                  for l in range(self.output_number)]
@@ -137,6 +163,19 @@ class Helper(object):
         layer, anchor = np.unravel_index(fit.reshape(len(allb), -1).argmax(1), fit.shape[1:])
         xywh = np.clip(allb[:, 1:5], 1e-8, 1.0)
         cls = allb[:, 0].astype(int)
+        if assign == 'multi':                              # every secondary write of the batch, box by box, before any primary write
+            second = fit > assign_iou
+            second[np.arange(len(allb)), layer, anchor] = False
+            for l in range(self.output_number):
+                m, a = np.nonzero(second[:, l, :])         # row-major: in box order
+                if not len(m):
+                    continue
+                h, w = self.out_hw[l]
+                cell = np.floor(allb[m, 1:3] * (w, h)).astype(int)
+                s_, cy, cx = sid[m], cell[:, 1], cell[:, 0]
+                grids[l][s_, cy, cx, a, :4] = xywh[m]
+                grids[l][s_, cy, cx, a, 4] = 1.0
+                grids[l][s_, cy, cx, a, 5 + cls[m]] = 1.0
         for l in range(self.output_number):
             m = np.nonzero(layer == l)[0]
             if not len(m):

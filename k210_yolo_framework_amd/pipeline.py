@@ -37,9 +37,19 @@ the cache does not hold into its arena - decoded by the pool and copied (decode=
 pool and decoded there by ONE `yk_jpeg_decode_ragged_u8` (decode='gpu'; without a cache it runs on a staging ring of its own) - and ONE
 ragged launch over the arena writes the whole batch, plain, warped or mosaicked; hsv, normalise and labels follow as above.  The batches are
 those of the paths above, bit for bit.  Without cache and with decode='pil' the paths above run untouched.
+
+labels='gpu'  builds the label grids on the device: letterboxing, augmentation and mosaic of the BOXES stay on the host in
+float64 (a few hundred numbers), the batch's boxes [N, 5] and offsets [n + 1] travel through two pinned slots instead of the dense grids, and
+ONE `yk_boxes_to_labels_f32` launch writes every layer's grid into one flat buffer - `Helper.batch_box_to_label`'s bits.  Where numpy would
+raise or wrap (a centre cell outside its grid) the kernel writes nothing of the box and says so in a status word, which comes home to a
+pinned int32 and is read once the batch's `ready` event has completed, at the latest when the epoch ends: the producer then raises, naming
+the dataset row and the box; rows that are not finite are refused before upload.  assign='multi', assign_iou (Helper.box_to_label): a box
+is also written at every other (layer, anchor) that fits it better than assign_iou, under either value of `labels`.  With labels='host',
+assign='best' (the defaults) every path above runs untouched.
 """
 from __future__ import annotations
 
+import collections
 import io
 import os
 import queue
@@ -148,11 +158,18 @@ class InputPipeline:
     def __init__(self, h: Helper, items: Sequence, global_batch: int, rank: int = 0, world: int = 1, seed: int = 0, epoch: int = 0,
                  shuffle: bool = True, workers: int = 8, prefetch: int = 2, device: Optional[int] = None, augment: bool = False,
                  mosaic: Optional[mosaic_mod.MosaicConfig] = None, hsv: Optional[colour_mod.HsvConfig] = None, cache=None,
-                 decode: str = 'pil'):
+                 decode: str = 'pil', labels: str = 'host', assign: str = 'best', assign_iou: float = 0.213):
         import torch
         engine.require_gpu()
         if decode not in ('pil', 'gpu'):
             raise engine.YkError(f'InputPipeline: decode {decode!r}: expected pil or gpu')
+        if labels not in ('host', 'gpu'):
+            raise engine.YkError(f'InputPipeline: labels {labels!r}: expected host or gpu')
+        try:
+            Helper.check_assign(assign, assign_iou)
+        except ValueError as e:
+            raise engine.YkError(f'InputPipeline: {e}') from e
+        self.labels, self.assign, self.assign_iou = labels, assign, float(assign_iou)
         self.h, self.items = h, items
         self.hsv_table = colour_mod.param_table(seed, epoch, len(items), hsv) if hsv is not None else None       # [n_rows, 3], rank-independent
         self.mosaic = mosaic
@@ -168,6 +185,13 @@ class InputPipeline:
         self.seconds = 0.0
         self._thread = None
         self._stop = False
+        # labels='gpu': the grids are built on the device from the boxes (yk_boxes_to_labels_f32); every batch's status word comes home
+        # to its own pinned int32 and is read once the batch's `ready` event has completed, at the latest when the epoch ends
+        self._in_flight: "collections.deque" = collections.deque()
+        self._batches = 0
+        if labels == 'gpu':
+            self._label_cfg = engine.make_label_cfg(h, assign, assign_iou)
+            self._status_home = torch.full((max(1, len(self.rows)),), engine.LABEL_STATUS_CLEAN, dtype=torch.int32).pin_memory()
         # cache=PictureCache (cache.py) and / or decode='gpu': every batch is composed from the cache's arena by one launch
         self.decode = decode
         self._own_cache = None
@@ -219,10 +243,16 @@ class InputPipeline:
         import torch
         H, W = int(self.h.in_hw[0][0]), int(self.h.in_hw[0][1])
         self._tick = 0
+        self._batches = 0                                                       # (a second pass over the same pipeline starts its status words afresh)
+        self._in_flight.clear()
+        if self.labels == 'gpu':
+            self.stream.synchronize()                                           # no status word of an abandoned pass is still on its way home
+            self._status_home.fill_(engine.LABEL_STATUS_CLEAN)
         try:
             for rows in self.rows:
                 if self._stop:
                     break
+                self._check_labels(wait=False)
                 t0 = time.perf_counter()
                 if self.cache is not None or self.mosaic is not None:
                     batch = self._cached_batch(rows, H, W) if self.cache is not None else self._mosaic_batch(rows, H, W)
@@ -250,10 +280,7 @@ class InputPipeline:
                     # the inverse maps in size-group order: group g reads a contiguous run of rows
                     inv_slot = self._slot('inv', (n, 6), torch.float64)
                     inv_slot[0].numpy()[...] = M.reshape(n, 6)[np.concatenate(list(by_size.values()))]
-                labs = self.h.batch_box_to_label(boxes)
-                lab_slots = [self._slot(('lab', l), labs[l].shape, torch.float32) for l in range(len(labs))]
-                for (view, _), lab in zip(lab_slots, labs):
-                    view.numpy()[...] = lab
+                staged = self._stage_labels(boxes, rows)
                 with torch.cuda.stream(self.stream):
                     frames = torch.empty((n, H, W, 3), dtype=torch.uint8, device=self.dev)
                     if inv_slot is not None:
@@ -282,18 +309,13 @@ class InputPipeline:
                         engine.hsv_jitter_u8(frames, self._upload('hsv', self.hsv_table[rows], torch.float64), stream=self.stream)
                     x = torch.empty((n, H, W, 3), dtype=torch.float32, device=self.dev)
                     engine.call('yk_normalise_u8', frames, n, H * W * 3, x, engine._stream(self.stream))
-                    labels = []
-                    for view, slot in lab_slots:
-                        labels.append(view.to(self.dev, non_blocking=True))
-                        slot[1] = torch.cuda.Event()
-                        slot[1].record(self.stream)
-                    ready = torch.cuda.Event()
-                    ready.record(self.stream)
+                    labels, ready = self._send_labels(staged)
                 self.images += n
                 self.seconds += time.perf_counter() - t0
                 if not self._put(Batch(x, labels, ready, n)):
                     return
-        except BaseException as e:                                          # surface worker errors in the consumer
+            self._check_labels(wait=not self._stop)
+        except BaseException as e:                                         # surface worker errors in the consumer
             self._put(e)
             return
         self._put(None)
@@ -307,6 +329,72 @@ class InputPipeline:
         slot[1] = torch.cuda.Event()
         slot[1].record(self.stream)
         return dev
+
+    # ---- labels: the one place the three batch builders get them from ---------------------------------------------------------------
+    def _stage_labels(self, boxes, rows):
+        """The host half, before anything is queued.  labels='host': the dense grids (Helper.batch_box_to_label) written into pinned
+        slots, one per layer.  labels='gpu': the batch's boxes as one [N, 5] float64 array and its offsets [n + 1]; rows that are not
+        finite are refused here, naming the dataset row."""
+        import torch
+        if self.labels == 'host':
+            labs = self.h.batch_box_to_label(boxes, self.assign, self.assign_iou)
+            lab_slots = [self._slot(('lab', l), labs[l].shape, torch.float32) for l in range(len(labs))]
+            for (view, _), lab in zip(lab_slots, labs):
+                view.numpy()[...] = lab
+            return lab_slots
+        per = [np.asarray(b, np.float64).reshape(-1, 5) for b in boxes]
+        first = np.zeros(len(per) + 1, np.int32)
+        np.cumsum([len(b) for b in per], out=first[1:])
+        allb = np.concatenate(per) if first[-1] else np.zeros((0, 5), np.float64)
+        if not np.isfinite(allb).all():
+            raise engine.YkError(self._box_message(int(np.nonzero(~np.isfinite(allb).all(1))[0][0]), rows, first, allb, 'is not finite'))
+        return allb, first, np.array(rows, np.int64, copy=True)
+
+    def _send_labels(self, staged):
+        """The device half, inside `torch.cuda.stream(self.stream)`, last of the batch: -> (labels per layer, the batch's `ready` event).
+        labels='host': one copy per layer from the pinned slots.  labels='gpu': boxes and offsets through `_upload`, ONE
+        yk_boxes_to_labels_f32 launch, and the status word on its way to its pinned home - read once `ready` has completed."""
+        import torch
+        if self.labels == 'host':
+            labels = []
+            for view, slot in staged:
+                labels.append(view.to(self.dev, non_blocking=True))
+                slot[1] = torch.cuda.Event()
+                slot[1].record(self.stream)
+            ready = torch.cuda.Event()
+            ready.record(self.stream)
+            return labels, ready
+        allb, first, rows = staged
+        d_boxes = self._upload('lbox', allb, torch.float64)
+        d_first = self._upload('lfirst', first, torch.int32)
+        labels, status = engine.boxes_to_labels(d_boxes, d_first, self._label_cfg, stream=self.stream)
+        home = self._status_home[self._batches:self._batches + 1]
+        home.copy_(status, non_blocking=True)
+        self._batches += 1
+        ready = torch.cuda.Event()
+        ready.record(self.stream)
+        self._in_flight.append((ready, status, home, rows, first, allb))
+        return labels, ready
+
+    def _box_message(self, g: int, rows, first, allb, what: str) -> str:
+        s = int(np.searchsorted(first, g, side='right')) - 1
+        return (f'InputPipeline(labels=\'gpu\'): dataset row {int(rows[s])} (sample {s} of its batch), box {g - int(first[s])} of the sample, '
+                f'(cls, x, y, w, h) = {tuple(float(v) for v in allb[g])} {what}')
+
+    def _check_labels(self, wait: bool) -> None:
+        """Read the status words of the batches whose `ready` event has completed (wait: of all of them, waiting for each): a box that
+        numpy could not have written either - a centre cell outside a grid it is written to, a class outside [0, class_num) - raises."""
+        while self._in_flight:
+            ready, _, home, rows, first, allb = self._in_flight[0]
+            if wait:
+                ready.synchronize()
+            elif not ready.query():
+                return
+            self._in_flight.popleft()
+            g = int(home[0])
+            if g != engine.LABEL_STATUS_CLEAN:
+                raise engine.YkError(self._box_message(g, rows, first, allb, 'has a centre cell outside the label grid of a layer it is written '
+                                                       'to (or a class outside [0, class_num)): Helper.batch_box_to_label raises or wraps there'))
 
     def _mosaic_batch(self, rows, H: int, W: int) -> Batch:
         """One batch of mosaics (mosaic.py): decode each picture the batch names once, one packed pinned buffer, one launch."""
@@ -324,10 +412,7 @@ class InputPipeline:
         if self.table is not None:
             A, t, M = aug_mod.matrices(self.table[rows], (H, W))
             boxes = aug_mod.augment_boxes_batch(boxes, A, t, (H, W))
-        labs = self.h.batch_box_to_label(boxes)
-        lab_slots = [self._slot(('lab', l), labs[l].shape, torch.float32) for l in range(len(labs))]
-        for (view, _), lab in zip(lab_slots, labs):
-            view.numpy()[...] = lab
+        staged = self._stage_labels(boxes, rows)
         total = sum(im.size for im in imgs.values())
         view, slot = self._slot('mosaic', (total,), torch.uint8)
         _, ptable, _ = pack_ragged([imgs[i] for i in uniq], out=view)
@@ -345,13 +430,7 @@ class InputPipeline:
                 engine.hsv_jitter_u8(frames, self._upload('hsv', self.hsv_table[rows], torch.float64), stream=self.stream)
             x = torch.empty((n, H, W, 3), dtype=torch.float32, device=self.dev)
             engine.call('yk_normalise_u8', frames, n, H * W * 3, x, engine._stream(self.stream))
-            labels = []
-            for view, slot in lab_slots:
-                labels.append(view.to(self.dev, non_blocking=True))
-                slot[1] = torch.cuda.Event()
-                slot[1].record(self.stream)
-            ready = torch.cuda.Event()
-            ready.record(self.stream)
+            labels, ready = self._send_labels(staged)
         return Batch(x, labels, ready, n)
 
     # ---- cache= / decode='gpu': the batch is composed from the arena of cache.py -------------------------------------------------
@@ -459,10 +538,7 @@ class InputPipeline:
                     table[b]['offset'], table[b]['h'], table[b]['w'] = plan.table[int(i)]
                 engine.call('yk_letterbox_ragged_params', table, n, H, W)
             table = engine.check_ragged_rows(table, cache.arena_bytes)
-            labs = self.h.batch_box_to_label(boxes)
-            lab_slots = [self._slot(('lab', l), labs[l].shape, torch.float32) for l in range(len(labs))]
-            for (view, _), lab in zip(lab_slots, labs):
-                view.numpy()[...] = lab
+            staged = self._stage_labels(boxes, rows)
             with torch.cuda.stream(self.stream):
                 written = cache.last_write()
                 if written is not None:                                         # (a pipeline of an earlier epoch wrote on its own stream)
@@ -496,13 +572,7 @@ class InputPipeline:
                 engine.hsv_jitter_u8(frames, self._upload('hsv', self.hsv_table[rows], torch.float64), stream=self.stream)
             x = torch.empty((n, H, W, 3), dtype=torch.float32, device=self.dev)
             engine.call('yk_normalise_u8', frames, n, H * W * 3, x, engine._stream(self.stream))
-            labels = []
-            for view, slot in lab_slots:
-                labels.append(view.to(self.dev, non_blocking=True))
-                slot[1] = torch.cuda.Event()
-                slot[1].record(self.stream)
-            ready = torch.cuda.Event()
-            ready.record(self.stream)
+            labels, ready = self._send_labels(staged)
         return Batch(x, labels, ready, n)
 
     def _put(self, item) -> bool:

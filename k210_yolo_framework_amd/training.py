@@ -63,7 +63,13 @@ BatchNorm moving statistics, which validation scores (`(ema)` on the epoch line)
 `--is_prune True` `yolo_prune_ema_model.*`, as sparse as the live one) beside the usual checkpoint of the live weights; global-norm gradient
 clipping, the step line then shows `gnorm`, the norm before clipping; a learning-rate schedule with linear warmup over the run's
 `train_epoch_step x max_nrof_epochs` steps (capped by `--max_steps`), the step line then shows `lr`.  All off by default: then the update is
-the reference's Adam call and no line changes."""
+the reference's Adam call and no line changes.
+
+`--labels gpu`, `--assign multi`, `--assign_iou` (`make train LABELS=gpu ASSIGN=multi ASSIGNIOU=0.213`; not in the reference): the
+label grids are built on the GPU from the batch's boxes by one HIP launch (`InputPipeline(labels='gpu')`), the bits of the host's; with
+`--assign multi` a box is written not only at its best-fitting (layer, anchor) but at every other whose fit exceeds `--assign_iou`
+(`Helper.box_to_label`), under either `--labels` value, in training and validation alike.  One line at the start names a non-default
+value; with the defaults (host, best) nothing changes."""
 from __future__ import annotations
 
 import argparse
@@ -99,14 +105,17 @@ def synthetic_list(n: int, in_hw, class_num: int, seed: int):
     return out
 
 
-def batches(h: Helper, items, batch_size: int, rng, shuffle: bool, augment=None, with_boxes: bool = False, mosaic=None, hsv=None):
+def batches(h: Helper, items, batch_size: int, rng, shuffle: bool, augment=None, with_boxes: bool = False, mosaic=None, hsv=None,
+            assign: str = 'best', assign_iou: float = 0.213, make_labels: bool = True):
     """tools/utils.py:417-450: (normalised image [B,H,W,3] float32, labels per layer [B,h,w,A,5+C] float32).  augment=(seed, epoch):
     every sample augmented with its row of augment.param_table(seed, epoch, len(items)), like InputPipeline(augment=True).
     with_boxes: a third element, each sample's boxes [n,5] (class, cx, cy, w, h) relative to the letterboxed frame.
     mosaic=(seed, epoch, prob): every sample composed by mosaic.py from its row of mosaic.param_table(seed, epoch, len(items)) on the host
     (mosaic.compose_u8), like InputPipeline(mosaic=MosaicConfig(prob)); the augmentation, if any, then acts on the mosaic.
     hsv=(seed, epoch, HsvConfig): the finished u8 frame of every sample jittered on the host (colour.jitter_u8) with its row of
-    colour.param_table(seed, epoch, len(items), HsvConfig), like InputPipeline(hsv=HsvConfig); labels and boxes do not change."""
+    colour.param_table(seed, epoch, len(items), HsvConfig), like InputPipeline(hsv=HsvConfig); labels and boxes do not change.
+    assign, assign_iou: the positive assignment of Helper.box_to_label, like InputPipeline(assign=, assign_iou=).
+    make_labels=False: no label grid is built, the second element is None (for a caller that builds them from the boxes: with_boxes)."""
     from . import augment as aug_mod
     from . import colour as colour_mod
     from . import mosaic as mosaic_mod
@@ -141,12 +150,14 @@ def batches(h: Helper, items, batch_size: int, rng, shuffle: bool, augment=None,
                                         aug=None if table is None else table[i], hsv=None if ctable is None else ctable[i])
             xs.append(img.astype(np.float32))
             bs.append(boxes)
-            for l, lab in enumerate(h.box_to_label(boxes)):
-                ys[l].append(lab)
+            if make_labels:
+                for l, lab in enumerate(h.box_to_label(boxes, assign=assign, assign_iou=assign_iou)):
+                    ys[l].append(lab)
+        labs = [np.stack(y).astype(np.float32) for y in ys] if make_labels else None
         if with_boxes:
-            yield np.stack(xs), [np.stack(y).astype(np.float32) for y in ys], bs
+            yield np.stack(xs), labs, bs
         else:
-            yield np.stack(xs), [np.stack(y).astype(np.float32) for y in ys]
+            yield np.stack(xs), labs
 
 
 def main(args, train_set, class_num, pre_ckpt, model_def, depth_multiplier, is_augmenter, image_size, output_size, batch_size,
@@ -156,7 +167,8 @@ def main(args, train_set, class_num, pre_ckpt, model_def, depth_multiplier, is_a
          box_loss='mse', box_weight=1.0, is_mosaic='False', mosaic_prob=1.0, mosaic_off_epochs=0, is_hsv='False', hsv_hue=0.1, hsv_sat=1.5,
          hsv_exposure=1.5, hsv_prob=1.0, teacher_ckpt='', teacher_def=None, teacher_depth=None, distill_weight=1.0, cache='off',
          cache_gb=8.0, cache_stage_mb=256, decode='pil', is_ema='False', ema_decay=0.9999, ema_tau=2000.0, clip_norm=0.0, lr_schedule='none',
-         warmup_steps=0, lr_final=0.01, focal='off', focal_gamma=2.0, focal_alpha=0.0, label_smooth=0.0, obj_target='label'):
+         warmup_steps=0, lr_final=0.01, focal='off', focal_gamma=2.0, focal_alpha=0.0, label_smooth=0.0, obj_target='label',
+         labels='host', assign='best', assign_iou=0.213):
     import torch
     from . import lossopt
     from .train import Trainer
@@ -205,6 +217,13 @@ def main(args, train_set, class_num, pre_ckpt, model_def, depth_multiplier, is_a
     if scheduled and float(learning_rate_decay_factor) != 0.0:
         raise engine.YkError(f'--lr_schedule {lr_schedule} together with --learning_rate_decay_factor {learning_rate_decay_factor} would be two schedules')
     distill = teacher_ckpt not in (None, 'None', '', '""')
+    if labels not in ('host', 'gpu'):
+        raise engine.YkError(f'--labels {labels}: host or gpu')
+    try:
+        Helper.check_assign(assign, float(assign_iou))
+    except ValueError as e:
+        raise engine.YkError(f'--assign {assign} --assign_iou {assign_iou}: {e}') from e
+    label_opts = dict(labels=labels, assign=assign, assign_iou=float(assign_iou))
     if distill and not (np.isfinite(float(distill_weight)) and float(distill_weight) >= 0.0):
         raise engine.YkError(f'--distill_weight {distill_weight}: a finite weight, not negative')
     rank, world = int(os.environ.get('RANK', '0')), int(os.environ.get('WORLD_SIZE', '1'))
@@ -229,6 +248,8 @@ def main(args, train_set, class_num, pre_ckpt, model_def, depth_multiplier, is_a
             raise engine.YkError('--cache gpu (the picture cache, cache.py) keeps the decoded training pictures in device memory: no HIP device') from e
         if ema or scheduled or float(clip_norm):
             raise engine.YkError('--ema / --clip_norm / --lr_schedule (optim.py) run in HIP kernels on the training step: no HIP device') from e
+        if labels == 'gpu':
+            raise engine.YkError('--labels gpu (the label grids built by yk_boxes_to_labels_f32) runs in the GPU input pipeline: no HIP device') from e
         if decode == 'gpu':
             raise engine.YkError('--decode gpu (baseline JPEG files decoded by yk_jpeg_decode_ragged_u8) runs in the GPU input pipeline: no HIP device') from e
         raise
@@ -307,6 +328,8 @@ def main(args, train_set, class_num, pre_ckpt, model_def, depth_multiplier, is_a
         print(INFO, f'ema is {ema_cfg}, clip_norm {float(clip_norm)}, lr schedule {lr_cfg}')
     if rank == 0 and not lossopt.is_off(**loss_opts):
         print(INFO, f'loss options: {lossopt.describe(**loss_opts)}')
+    if rank == 0 and (labels != 'host' or assign != 'best'):
+        print(INFO, f'labels are built on the {labels}, assign is {assign}' + (f', assign_iou {float(assign_iou)}' if assign == 'multi' else ''))
     tr = Trainer(spec, weights, h.anchors, per_rank, obj_thresh=obj_thresh, iou_thresh=iou_thresh, obj_weight=obj_weight,
                  noobj_weight=noobj_weight, wh_weight=wh_weight, lr=init_learning_rate, decay=learning_rate_decay_factor, device=local,
                  world_size=world, prune=schedule, qat=qat_cfg, box_loss=box_loss, box_weight=box_weight, distill=distill_cfg,
@@ -337,7 +360,8 @@ def main(args, train_set, class_num, pre_ckpt, model_def, depth_multiplier, is_a
                              augment=augment,                                    # the last mosaic_off_epochs epochs train on plain samples
                              mosaic=MosaicConfig(float(mosaic_prob)) if mosaic and epoch < max_nrof_epochs - int(mosaic_off_epochs) else None,
                              hsv=hsv_cfg,                                       # ... the colour jitter stays on in them
-                             **({} if pic_cache is None else dict(cache=pic_cache, decode=decode)))
+                             **({} if pic_cache is None else dict(cache=pic_cache, decode=decode)),
+                             **({} if labels == 'host' and assign == 'best' else label_opts))
         try:                                                                    # an exception in the step must not leave the producer running
             for x, ys in pipe:
                 if qat and epoch == 0 and observed < int(qat_observe):           # the first batches of epoch 0 only set the activation ranges
@@ -366,9 +390,9 @@ def main(args, train_set, class_num, pre_ckpt, model_def, depth_multiplier, is_a
         val = vmap = None
         if rank == 0 and len(h.test_list) >= per_rank:
             if val_map == 'True':                                               # opt-in: the pass also scores its detections
-                val, vmap = validate(tr, h, spec, per_rank, rank, map_obj=val_map_obj, ema=ema)
+                val, vmap = validate(tr, h, spec, per_rank, rank, map_obj=val_map_obj, ema=ema, **label_opts)
             else:
-                val = validate(tr, h, spec, per_rank, rank, ema=ema)
+                val = validate(tr, h, spec, per_rank, rank, ema=ema, **label_opts)
         if rank == 0:
             print(f'epoch {epoch + 1}: {seen} steps, mean loss {run / max(seen, 1):.4f}, ' +
                   (f'mean {box_loss} {run_box / max(seen, 1):.4f}, ' if iou_box else '') +
@@ -443,14 +467,17 @@ def sparsity_line(tr, spec, epoch: int) -> str:
             ' '.join(f'{nm} {rep[nm + "/kernel"]["sparsity"]:.4f}' for nm in heads))
 
 
-def validate(tr, h: Helper, spec, batch: int, rank: int, map_obj=None, ema: bool = False):
+def validate(tr, h: Helper, spec, batch: int, rank: int, map_obj=None, ema: bool = False, labels: str = 'host', assign: str = 'best',
+             assign_iou: float = 0.213):
     """validation_data pass (keras_train.py:96-98): inference-mode forward on the engine (the f16x2 mode, the boundary default) + the same loss.
     map_obj (`--val_map True`): the plan's outputs are also decoded on the GPU at this objectness threshold (NMS and match IoU = the run's
     iou_thresh) and scored in device memory by map_gpu.MapEvaluator against the validation boxes in network-input pixels - the letterboxed
     frame is the image; -> (val_loss, val_mAP) instead of val_loss.
-    ema (`--ema True`): the plan is built from the averaged weights, tr.export_weights(ema=True), for the loss and the mAP alike."""
+    ema (`--ema True`): the plan is built from the averaged weights, tr.export_weights(ema=True), for the loss and the mAP alike.
+    labels, assign, assign_iou: the run's label options (InputPipeline's): the validation labels follow the same assignment and, with
+    labels='gpu', are built by the same kernel from the batch's boxes; a box it could not write raises, as in training."""
     import torch
-    tot, n = 0.0, 0
+    tot, n, statuses = 0.0, 0, []
     e = 5 + spec.class_num
     ev = cfg = None
     if map_obj is not None:
@@ -459,16 +486,24 @@ def validate(tr, h: Helper, spec, batch: int, rank: int, map_obj=None, ema: bool
         ev = MapEvaluator(spec.class_num, tr.hyper['iou_thresh'], device=tr.dev.index or 0)
         cfg = engine.make_decode_cfg(h.anchors, spec.class_num, spec.in_hw, spec.out_hw())
     with engine.Plan(spec, tr.export_weights(ema=True) if ema else tr.export_weights(), max_batch=batch, device=tr.dev.index or 0) as plan:   # freed on exit, every epoch
-        for x, ys, *boxes in batches(h, h.test_list, batch, np.random.default_rng(0), shuffle=False, with_boxes=ev is not None):
+        for x, ys, *boxes in batches(h, h.test_list, batch, np.random.default_rng(0), shuffle=False, with_boxes=ev is not None or labels == 'gpu',
+                                     assign=assign, assign_iou=assign_iou, make_labels=labels != 'gpu'):
             plan.run_f32(torch.from_numpy(x).cuda())
+            if labels == 'gpu':
+                first = np.concatenate([[0], np.cumsum([len(b) for b in boxes[0]])])
+                ys, status = engine.boxes_to_labels(np.concatenate([np.reshape(b, (-1, 5)) for b in boxes[0]]), first, h, assign, assign_iou)
+                statuses.append(status)                                         # read once, after the pass
             if ev is not None:
                 dets, counts = engine.decode_py(cfg, plan.outputs(), batch, None, float(map_obj), tr.hyper['iou_thresh'])
                 ev.add(dets, counts, [ground_truth_rows(b, spec.in_hw) for b in boxes[0]])
             for li, (o, yt) in enumerate(zip(plan.outputs(), ys)):
                 yp = o[:batch].reshape(batch, *spec.tensors[spec.outputs[li]][:2], spec.anchor_num, e).contiguous()
-                loss6, _, _ = engine.yolo_loss(torch.from_numpy(yt).cuda(), yp, tr.anchors[li], batch_size=batch, want_grad=False, **tr.hyper)
+                loss6, _, _ = engine.yolo_loss(yt if torch.is_tensor(yt) else torch.from_numpy(yt).cuda(), yp, tr.anchors[li], batch_size=batch, want_grad=False, **tr.hyper)
                 tot += float(loss6[0])
             n += 1
+    for b, status in enumerate(statuses):
+        if int(status.item()) != engine.LABEL_STATUS_CLEAN:
+            raise engine.YkError(f'validate: box {int(status.item())} of validation batch {b} has a centre cell outside a label grid it is written to')
     if ev is not None:
         return tot / max(n, 1), ev.result()['map']
     return tot / max(n, 1)
@@ -547,6 +582,11 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument('--label_smooth', type=float, default=0.0, help='class targets z -> z (1 - eps) + eps / 2, eps in [0, 1); 0 = off')
     p.add_argument('--obj_target', type=str, choices=['label', 'iou'], default='label',
                    help="iou: an object cell's objectness target is the IoU of its predicted box with the label box")
+    p.add_argument('--labels', type=str, choices=['host', 'gpu'], default='host',
+                   help='gpu: the label grids are built on the GPU from the boxes, only the boxes cross PCIe (DESIGN.md 3.26)')
+    p.add_argument('--assign', type=str, choices=['best', 'multi'], default='best',
+                   help='multi: a box also trains every other (layer, anchor) that fits it better than --assign_iou (DESIGN.md 3.26)')
+    p.add_argument('--assign_iou', type=float, default=0.213, help='with --assign multi: the fit above which an anchor is also trained on a box, inside (0, 1)')
     return p
 
 
@@ -559,7 +599,7 @@ def cli(argv=None):
                 a.qat, a.qat_momentum, a.qat_observe, a.val_map, a.val_map_obj, a.box_loss, a.box_weight, a.mosaic, a.mosaic_prob,
                 a.mosaic_off_epochs, a.hsv, a.hsv_hue, a.hsv_sat, a.hsv_exposure, a.hsv_prob, a.teacher_ckpt, a.teacher_def, a.teacher_depth,
                 a.distill_weight, a.cache, a.cache_gb, a.cache_stage_mb, a.decode, a.ema, a.ema_decay, a.ema_tau, a.clip_norm, a.lr_schedule,
-                a.warmup_steps, a.lr_final, a.focal, a.focal_gamma, a.focal_alpha, a.label_smooth, a.obj_target)
+                a.warmup_steps, a.lr_final, a.focal, a.focal_gamma, a.focal_alpha, a.label_smooth, a.obj_target, a.labels, a.assign, a.assign_iou)
 
 
 if __name__ == '__main__':
