@@ -79,7 +79,8 @@ Path = collections.namedtuple('Path', 'template branch detail selp')
 
 
 def nms_path(ntot_, n, max_out, all_tied):
-    """decode_impl's template choice and nms_py_kernel's branch.  detail: P of a sorted sweep, the number of LDS chunks a tied class has."""
+    """The template choice (nms_maxc) and the branch chain at the end of nms_py_kernel in csrc/yk_decode.hip, branch for branch: keep the two
+    together.  detail: P of a sorted sweep, the number of LDS chunks a tied class has."""
     maxc = 1088 if ntot_ <= 1088 else 2048
     sweep_ok = max_out <= 64 and ntot_ < (1 << 20)
     selp = 'selg' if max_out <= 256 else 'og'
