@@ -57,6 +57,9 @@
 #                    labels drawn on the GPU; ENCODE=gpu also JPEG-encodes them there at QUALITY, ENCODE=pil leaves that to PIL on the host;
 #                    DECODE=gpu decodes baseline JPEG files there too, by the project's own integer rule, every other file by PIL)
 #                    [TTA=flip|v5|1,0.83f,0.67 TTATHRESH=0.55]: test-time augmentation, every picture also mirrored / shrunk, the views' rows fused on the GPU
+#                    [TRACK=True TRACKTHRESH=0.5 TRACKLOW=0.1 TRACKMATCH=0.8 TRACKBUFFER=30 TRACKMAX=256]: the pictures of a folder are the frames of
+#                    a sequence; rows get ids that last across frames on the GPU (ByteTrack restated, k210_yolo_framework_amd/track.py), the labels
+#                    show them, and OUTDIR/tracks/<sequence>.txt holds them in the MOTChallenge text format
 #   make anchors     DATASET=voc ANCNUM=3 [LOW='0.0 0.0' HIGH='1.0 1.0']   (reference Makefile:78-87: k-means anchors from data/<set>_img_ann.npy)
 #                    [ANCDEVICE=gpu RESTARTS=256 ANCSEED=0]: RESTARTS random starts in one GPU call; the set with the highest mean IoU is
 #                    kept and that IoU printed (ANCDEVICE=cpu RESTARTS=N loops the same rule in numpy)
@@ -155,6 +158,13 @@ DRAW          ?= True
 ENCODE        ?= pil
 DECODE        ?= pil
 QUALITY       ?= 75
+# tracking across the frames of a folder (k210_yolo_framework_amd/track.py); the defaults are ByteTrack's, starting points only
+TRACK         ?= False
+TRACKTHRESH   ?= 0.5
+TRACKLOW      ?= 0.1
+TRACKMATCH    ?= 0.8
+TRACKBUFFER   ?= 30
+TRACKMAX      ?= 256
 # kmodel only
 OUT           ?= yolo.kmodel
 CALIB         ?= data/$(DATASET)_img_ann.npy
@@ -187,6 +197,7 @@ NET_ARGS   = --train_set $(DATASET) --class_num $(CLSNUM) --model_def $(MODEL) -
 NMS_ARGS   = $(if $(filter-out hard,$(NMS)),--nms $(NMS) --nms_sigma $(NMSSIGMA))
 TILE_ARGS  = $(if $(TILES),--tiles $(TILES) --tile_overlap $(TILEOVERLAP) --tile_full $(TILEFULL) --tile_match $(TILEMATCH) --tile_thresh $(TILETHRESH))
 TTA_ARGS   = $(if $(TTA),--tta $(TTA) --tta_thresh $(TTATHRESH))
+TRACK_ARGS = $(if $(filter True,$(TRACK)),--track True --track_thresh $(TRACKTHRESH) --track_low $(TRACKLOW) --track_match $(TRACKMATCH) --track_buffer $(TRACKBUFFER) --track_max $(TRACKMAX))
 TRAIN_ARGS = --pre_ckpt $(CKPT) --augmenter $(IAA) --batch_size $(BATCH) --rand_seed 3 --max_nrof_epochs $(MAXEP) \
              --init_learning_rate $(ILR) --learning_rate_decay_factor $(LRDECAYFACTOR) --obj_weight $(OBJWEIGHT) \
              --noobj_weight $(NOOBJWEIGHT) --wh_weight $(WHWEIGHT) --vaildation_split $(SPLITFACTOR) --log_dir log \
@@ -244,7 +255,7 @@ eval:
 
 # every picture of SRC (a folder or a text list) -> OUTDIR/detections.json + OUTDIR/<stem>_res.jpg; batches of BATCH pictures of any sizes
 detect:
-	$(PY) keras_detect.py $(CKPT) $(SRC) --out_dir $(OUTDIR) --draw $(DRAW) --decode $(DECODE) --encode $(ENCODE) --quality $(QUALITY) --batch $(BATCH) --precision $(PRECISION) $(NET_ARGS) $(NMS_ARGS) $(TILE_ARGS) $(TTA_ARGS)
+	$(PY) keras_detect.py $(CKPT) $(SRC) --out_dir $(OUTDIR) --draw $(DRAW) --decode $(DECODE) --encode $(ENCODE) --quality $(QUALITY) --batch $(BATCH) --precision $(PRECISION) $(NET_ARGS) $(NMS_ARGS) $(TILE_ARGS) $(TTA_ARGS) $(TRACK_ARGS)
 
 # reference Makefile:78-87 (same flags; --is_random True as there)
 anchors:

@@ -301,6 +301,51 @@ int yk_fuse_views(const float *d_dets, const int32_t *d_counts, const float *d_x
  * YK_ERR_ARG, no device: YK_ERR_NO_DEVICE. */
 int yk_fuse_views_lds_candidates(int max_out);
 
+/* ---- tracking: identities across the frames of a sequence for the decode's rows (k210_yolo_framework_amd/track.py states the rule,
+ * ByteTrack restated with a class-aware greedy association).  The state of n_seq sequences of at most max_tracks tracks each
+ * (1 .. YK_TRACK_MAX_TRACKS) is device memory of yk_track_state_bytes the caller allocates and yk_track_reset empties (a kernel, not a fill:
+ * it can be recorded in a graph); per sequence a header (live tracks, next id, frames seen, overflow) and 25 words per track.
+ * yk_track_update advances every sequence by its frames of this call: d_dets [n_frames][cap][6] and d_counts [n_frames] as yk_decode_py*
+ * leaves them (counts are clamped to [0, cap]); d_seq_first [n_seq + 1] int32: the frames of sequence s are d_seq_first[s] ..
+ * d_seq_first[s+1] - 1, in time order (it is DEVICE memory, so that nothing is read on the host: a value outside [0, n_frames] is clamped and
+ * a descending pair is a sequence without frames in this call; engine.TrackState refuses a descending host table by name.  The ranges of
+ * different sequences must be disjoint, which an ascending table gives: two sequences that shared a frame would both write its rows of
+ * d_out).  Per frame, in
+ * float32 with one rounding per operation and no contraction: every track predicted; the rows whose class is exactly one of
+ * 0 .. class_num - 1, whose score is >= low_thresh (a NaN is dropped) and whose height and width are positive and finite split into high
+ * (score >= track_thresh) and low; TRACKED and LOST tracks x high rows at IoU >= 1 - match_thresh, then the TRACKED tracks still unmatched x
+ * low rows at IoU >= 0.5, then NEW tracks x the high rows still free at IoU >= 0.3 - in each stage the pair of one class with the largest
+ * IoU first (the IoU of yk_decode_py's own NMS; ties: the lowest track index, then the lowest row index); a matched track updated and
+ * TRACKED, an unmatched TRACKED one LOST, an unmatched NEW one deleted, a LOST one deleted once its last match is more than track_buffer
+ * frames ago; every high row still free with score >= track_thresh + 0.1 opens a track with the next id (from 1; TRACKED on the sequence's
+ * first frame, NEW afterwards) while the sequence holds fewer than max_tracks - a row that finds it full opens nothing, takes no id and is
+ * counted in the sequence's overflow, everything else proceeding unchanged.
+ * d_out [n_frames][cap][6], d_out_ids [n_frames][cap] and d_out_counts [n_frames]: per frame one row per track that was matched (or, on
+ * the first frame, opened) in it, in ascending id order, at most cap: the filter's box as (top, left, bottom, right), the matched row's
+ * score, the class - the padded form again; rows past the count and frames outside every sequence are not written.  d_draw, unless NULL,
+ * receives d_out with the class column replaced by id mod 100, for yk_draw_dets_u8's label and colour.
+ * One wavefront per sequence, its tracks resident in LDS across the call's frames (128 bytes each) beside the current frame's rows (24
+ * bytes each), no atomics: two calls give the same bytes, and 8 frames in one call leave what 3 + 5 in two leave.  There is one path: cap
+ * must not exceed yk_track_max_cap(max_tracks), and more is refused, never truncated.  One launch on `stream`, no host read; can be recorded
+ * in a graph after an eager call of the same max_tracks and cap.  A NULL pointer other than d_draw, n_seq <= 0, max_tracks outside
+ * 1 .. YK_TRACK_MAX_TRACKS, cap <= 0, n_frames <= 0, class_num <= 0, a NaN threshold, track_buffer < 0, n_frames * cap >= 2^31 or cap above
+ * the capacity: YK_ERR_ARG with the argument named in yk_last_error, nothing launched.
+ * yk_track_read waits for the device and copies each sequence's live-track count, next id and overflow count to the host. */
+#define YK_TRACK_MAX_TRACKS 1024
+typedef struct {
+    float track_thresh, low_thresh, match_thresh;
+    int32_t track_buffer;
+} yk_track_cfg_t;
+int yk_track_state_bytes(int n_seq, int max_tracks, size_t *bytes);
+int yk_track_reset(void *d_state, int n_seq, int max_tracks, void *stream);
+int yk_track_max_cap(int max_tracks);      /* largest row capacity per frame one call takes on the current device */
+int yk_track_update(void *d_state, int n_seq, int max_tracks, const float *d_dets, const int32_t *d_counts, int cap,
+                    const int32_t *d_seq_first /* [n_seq+1]: the frames of sequence s are d_seq_first[s] .. d_seq_first[s+1]-1 */,
+                    int n_frames, int class_num, const yk_track_cfg_t *cfg,
+                    float *d_out, int32_t *d_out_ids, int32_t *d_out_counts,
+                    float *d_draw /* may be NULL: d_out with the class column replaced by id mod 100 */, void *stream);
+int yk_track_read(const void *d_state, int n_seq, int max_tracks, int32_t *h_live, int32_t *h_next_id, int32_t *h_overflow);
+
 /* ---- a step as one hipGraph (the kpu_run_kmodel(..., dma, ai_done_cb) shape of main.c:303-311: submit once, get called back) ----
  * Everything issued on `stream` (a created stream, not NULL) between yk_graph_begin and yk_graph_end - yk_run_*, yk_decode_py*,
  * yk_letterbox_u8, yk_memcpy_async - is recorded, not executed; yk_graph_launch replays the recording with ONE host call.

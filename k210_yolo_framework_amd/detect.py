@@ -3,6 +3,7 @@
     python keras_detect.py CKPT SRC --out_dir D [--draw True|False] [--decode pil|gpu] [--encode pil|gpu] [--quality 75] [--batch 32] [--depth 4]
                            [--tiles NXxNY --tile_overlap 0.2 --tile_full True --tile_match ios|iou --tile_thresh 0.5]
                            [--tta 1,1f|flip|v5 --tta_thresh 0.55]
+                           [--track True --track_thresh 0.5 --track_low 0.1 --track_match 0.8 --track_buffer 30 --track_max 256]
                            [network and threshold flags of keras_inference.py]
 
 SRC: a folder (its .jpg / .jpeg / .png / .bmp files, in sorted order), a text file with one picture path per line, or one picture.
@@ -33,6 +34,7 @@ from . import draw as dr
 from . import jpeg
 from . import softnms
 from . import tiles as tl
+from . import track as tk
 from . import tta as tt
 from .helper import INFO, NOTE, Helper, VOC_ANCHORS
 from .yolonet import MODEL_DEFS
@@ -68,6 +70,7 @@ def parse(argv=None):
     p.add_argument('--nms_sigma', type=float, default=0.5, help='sigma of --nms gaussian')
     tl.add_arguments(p)
     tt.add_arguments(p)
+    tk.add_arguments(p)
     a = p.parse_args(sys.argv[1:] if argv is None else argv)
     if (a.precision == 'kpu') != a.pre_ckpt.endswith(('.kmodel', '.kfpkg')):
         p.error('--precision kpu runs a .kmodel / .kfpkg checkpoint, and only it does (the float modes take .h5 / .npz)')
@@ -82,6 +85,7 @@ def parse(argv=None):
     try:
         tl.parse_arguments(a)
         tt.parse_arguments(a)
+        tk.parse_arguments(a)
     except ValueError as e:
         p.error(str(e))
     if a.tta is not None and len(a.tta) > a.batch:
@@ -120,10 +124,14 @@ def output_names(names: Sequence[str], out_dir) -> List[str]:
     return out
 
 
-def print_table(name: str, rows: np.ndarray) -> None:
-    """keras_inference.py:146,154 for one picture, its path above."""
+def print_table(name: str, rows: np.ndarray, ids=None) -> None:
+    """keras_inference.py:146,154 for one picture, its path above; with ids (tracking) an id column besides."""
     print(name)
-    if len(rows):
+    if len(rows) and ids is not None:
+        print('[top\tleft\tbottom\tright\tscore\tclass\tid]')
+        for (top, left, bottom, right, score, c), i in zip(rows, ids):
+            print(f'[{top:.1f}\t{left:.1f}\t{bottom:.1f}\t{right:.1f}\t{score:.2f}\t{int(c):2d}\t{int(i)}]')
+    elif len(rows):
         print('[top\tleft\tbottom\tright\tscore\tclass]')
         for top, left, bottom, right, score, c in rows:
             print(f'[{top:.1f}\t{left:.1f}\t{bottom:.1f}\t{right:.1f}\t{score:.2f}\t{int(c):2d}]')
@@ -145,13 +153,37 @@ class _Stage:
         self.d_work = self.d_scan = self.h_scan = self.d_off = self.h_off = None       # encode='gpu'
         self.d_stage = self.d_jwork = self.d_jstatus = self.h_jstatus = None           # decode='gpu'
         self.d_mdets = self.d_mcounts = None                                            # tiles, tta: the merged / fused rows per picture
+        self.d_track = self.h_ids = None                                                # track: (rows, ids, counts, rows for the draw)
+
+
+def sequences_of(sources, in_memory: bool):
+    """track=True: -> (sequence index per picture, sequence names).  The pictures of one parent folder are one sequence, sequences counted
+    in order of first appearance; in-memory sources are one sequence.  A folder whose pictures are not contiguous in the list is refused:
+    the frames of a sequence are tracked in the order given."""
+    if in_memory:
+        return np.zeros(len(sources), np.int64), ['sequence']
+    index, folders = [], []
+    for s in sources:
+        folder = str(Path(s).parent)
+        if folder not in folders:
+            folders.append(folder)
+        elif folders[-1] != folder:
+            raise ValueError(f'track: the pictures of {folder} are not contiguous in the list; a sequence is tracked in the order given')
+        index.append(len(folders) - 1)
+    seen, names = {}, []
+    for folder in folders:
+        stem = Path(folder).name or 'sequence'
+        seen[stem] = seen.get(stem, 0) + 1
+        names.append(stem if seen[stem] == 1 else f'{stem}_{seen[stem]}')
+    return np.asarray(index, np.int64), names
 
 
 def run(h: Helper, model, sources, out_dir=None, draw: bool = True, batch: int = 32, depth: int = 4, precision: str = 'f16x2',
         obj_thresh: float = 0.7, iou_thresh: float = 0.3, workers: int = 8, names: Optional[Sequence[str]] = None,
         return_arrays: bool = False, verbose: bool = True, max_out: int = 30, encode: str = 'pil', quality: int = 75, decode: str = 'pil',
         nms: str = 'hard', nms_sigma: float = 0.5, tiles=None, tile_overlap: float = 0.2, tile_full: bool = True, tile_match: str = 'ios',
-        tile_thresh: float = 0.5, tta=None, tta_thresh: float = 0.55):
+        tile_thresh: float = 0.5, tta=None, tta_thresh: float = 0.55, track: bool = False, track_thresh: float = 0.5, track_low: float = 0.1,
+        track_match: float = 0.8, track_buffer: int = 30, track_max: int = 256):
     """sources: picture paths, or [h, w, 3] uint8 arrays already in memory (then `names` names them); with decode='gpu' paths or the bytes of
     picture files: baseline JPEGs are decoded on the device by the rule of include/yolo_hip.h (not PIL's bytes: DESIGN.md 3.12), every other
     file by PIL on the pool as with decode='pil'; a stream the device cannot finish raises YkError naming the file.  -> {'names', 'detections': one
@@ -166,7 +198,12 @@ def run(h: Helper, model, sources, out_dir=None, draw: bool = True, batch: int =
     tta='1,0.83f,0.67' | 'flip' | 'v5' | ((gain, mirror), ...): test-time augmentation (tta.py) - every picture runs as one
     frame per view (yk_letterbox_views_u8 reads the shrunk and mirrored canvases out of the resident originals), each decoded at its canvas's
     size, and yk_fuse_views fuses their rows by Weighted Boxes Fusion at IoU > tta_thresh; a batch holds batch // views pictures (more views
-    than `batch` are refused), and tta together with tiles or with a soft nms is refused.  None (the default): everything as without it."""
+    than `batch` are refused), and tta together with tiles or with a soft nms is refused.  None (the default): everything as without it.
+    track=True: the rows get identities across frames (track.py; sequences_of says what a sequence is) - yk_track_update runs
+    when a batch is drained, in frame order whatever `depth` is, between the slot's decode and the draw; 'detections' are then the tracks'
+    rows, 'track_ids' their ids per picture and 'sequences' the sequences' names; the draw labels a box with its id (mod 100); with out_dir
+    detections.json's rows carry the id as a seventh column and tracks/<sequence>.txt is written in the MOTChallenge text format.  track together with tiles, tta or a soft nms is refused; a sequence
+    that needed more than track_max tracks raises YkError naming it at the end of the run.  False (the default): everything as without it."""
     import torch
     from . import engine
     engine.require_gpu()
@@ -194,6 +231,11 @@ def run(h: Helper, model, sources, out_dir=None, draw: bool = True, batch: int =
         T = len(tta_spec)
         if T > int(batch):
             raise engine.YkError(f'detect: tta {tt.text_of(tta_spec)}: a picture is {T} frames and a batch holds {int(batch)}')
+    if track:
+        try:
+            track_cfg = tk.check(track_thresh, track_low, track_match, track_buffer, track_max, nms, tiles, tta)
+        except ValueError as e:
+            raise engine.YkError(f'detect: {e}') from None
     gpu_decode = decode == 'gpu'
     in_memory = isinstance(sources[0], (np.ndarray, bytes))
     if gpu_decode and any(isinstance(s, np.ndarray) for s in sources):
@@ -209,6 +251,16 @@ def run(h: Helper, model, sources, out_dir=None, draw: bool = True, batch: int =
     gpu_jpeg = encode == 'gpu' and draw and out_dir is not None
     copy_pixels = want_pixels and (return_arrays or not gpu_jpeg)       # the uncompressed pictures cross PCIe only when someone reads them
     cap = h.class_num * max_out
+    if track:
+        try:
+            seq_of, seq_names = sequences_of(sources, in_memory)
+        except ValueError as e:
+            raise engine.YkError(f'detect: {e}') from None
+        tracks = engine.TrackState(len(seq_names), h.class_num, max_tracks=int(track_max), **track_cfg)
+        track_ids = [None] * n_all
+        if verbose and obj_thresh > track_low:
+            print(NOTE, f' obj_thresh {obj_thresh:g} is above track_low {track_low:g}: the decode drops the rows between the two, and the second '
+                        f'association sees nothing there')
     colormap = torch.from_numpy(np.asarray(h.colormap, np.uint8).reshape(-1, 3)).to(dev)
     atlas = torch.from_numpy(dr.glyph_atlas()).to(dev)
     if gpu_jpeg:
@@ -254,14 +306,49 @@ def run(h: Helper, model, sources, out_dir=None, draw: bool = True, batch: int =
         Pipeline.close() has destroyed them."""
         engine.call('yk_memcpy_async', dst, src, int(nbytes), stream.cuda_stream)
 
+    def finish(st, n, dets, counts, draw_dets, d_packed, table_d, table, shapes, total, stream):
+        """What follows a batch's rows on its stream: the draw (of draw_dets: the rows, or with track the rows labelled by id), the encode
+        and the copies back."""
+        if want_pixels:
+            max_px = int(max(s[0] * s[1] for s in shapes))
+            engine.draw_detections_u8(d_packed, table_d, draw_dets, counts, colormap, atlas, stream=stream, max_pixels=max_px)
+            if copy_pixels:
+                copy(st.pinned, d_packed, total, stream)                                    # only finished pictures come back
+            if gpu_jpeg:
+                sizes = engine.jpeg_workspace_bytes(table)
+                if st.d_work is None or st.d_work.numel() < sizes[0] or st.d_scan.numel() < sizes[1]:
+                    torch.cuda.synchronize()                                                # grown rarely; nothing in flight reads the old ones
+                    st.d_work = torch.empty(sizes[0] + sizes[0] // 4, dtype=torch.uint8, device=dev)
+                    st.d_scan = torch.empty(sizes[1] + sizes[1] // 4, dtype=torch.uint8, device=dev)
+                    st.h_scan = torch.empty(st.d_scan.numel(), dtype=torch.uint8).pin_memory()
+                    st.d_off = torch.empty(B + 1, dtype=torch.int64, device=dev)
+                    st.h_off = torch.empty(B + 1, dtype=torch.int64).pin_memory()
+                engine.jpeg_encode_ragged_u8(d_packed, table_d, d_qtab, stream=stream, sizes=sizes, work=st.d_work, out=st.d_scan,
+                                             out_off=st.d_off[:n + 1])
+                copy(st.h_off, st.d_off, (n + 1) * 8, stream)
+        copy(st.h_dets, dets, n * cap * 6 * 4, stream)
+        copy(st.h_counts, counts, n * 4, stream)
+
     def start_load(k):
         loading.append([pool.submit(load, s) for s in sources[starts[k]:starts[k] + B]])
 
     def drain():
-        first, n, st, table, keep, ev, slot, stream = pending.popleft()
+        first, n, st, table, keep, ev, slot, stream, late = pending.popleft()
         ev.synchronize()
         if pipe is not None:
             pipe.plans[slot].raise_if_failed()
+        if track:                                           # the batches are drained in order: the state advances in frame order
+            if st.d_track is None:
+                st.d_track = (torch.zeros((B, cap, 6), dtype=torch.float32, device=dev), torch.zeros((B, cap), dtype=torch.int32, device=dev),
+                              torch.zeros((B,), dtype=torch.int32, device=dev), torch.zeros((B, cap, 6), dtype=torch.float32, device=dev))
+                st.h_ids = torch.empty((B, cap), dtype=torch.int32).pin_memory()
+                torch.cuda.current_stream().synchronize()   # (filled on torch's stream, written on the slot's)
+            dets, counts, *rest = late
+            seq_first = np.searchsorted(seq_of[first:first + n], np.arange(len(seq_names) + 1))
+            rows, ids, tcounts, for_draw = tracks.update(dets, counts, seq_first, stream=stream, draw=True, out=tuple(t[:n] for t in st.d_track))
+            finish(st, n, rows, tcounts, for_draw, *rest, stream)
+            copy(st.h_ids, ids, n * cap * 4, stream)
+            stream.synchronize()
         if gpu_decode and keep[1]:
             for j, code in zip(keep[1], st.h_jstatus[:len(keep[1])].numpy().tolist()):
                 if code:
@@ -269,6 +356,8 @@ def run(h: Helper, model, sources, out_dir=None, draw: bool = True, batch: int =
         counts = st.h_counts[:n].numpy()
         for i in range(n):
             results[first + i] = st.h_dets[i, :int(counts[i])].numpy().copy()
+            if track:
+                track_ids[first + i] = st.h_ids[i, :int(counts[i])].numpy().copy()
         if copy_pixels:
             flat = st.pinned.numpy()
             for i, view in enumerate(dr.unpack_ragged(flat, table)):
@@ -290,7 +379,7 @@ def run(h: Helper, model, sources, out_dir=None, draw: bool = True, batch: int =
                 written.append(files[first + i])
         if verbose:
             for i in range(n):
-                print_table(names[first + i], results[first + i])
+                print_table(names[first + i], results[first + i], track_ids[first + i] if track else None)
 
     try:
         for k in range(min(ahead, len(starts))):
@@ -415,31 +504,22 @@ def run(h: Helper, model, sources, out_dir=None, draw: bool = True, batch: int =
             if tta_spec is not None:
                 dets, counts = engine.fuse_views(dets, counts, xform_d, T, h.class_num, max_out, tta_thresh, stream=stream, out=st.d_mdets[:n],
                                                  out_counts=st.d_mcounts[:n])
-            if want_pixels:
-                max_px = int(max(s[0] * s[1] for s in shapes))
-                engine.draw_detections_u8(d_packed, table_d, dets, counts, colormap, atlas, stream=stream, max_pixels=max_px)
-                if copy_pixels:
-                    copy(st.pinned, d_packed, total, stream)                                # only finished pictures come back
-                if gpu_jpeg:
-                    sizes = engine.jpeg_workspace_bytes(table)
-                    if st.d_work is None or st.d_work.numel() < sizes[0] or st.d_scan.numel() < sizes[1]:
-                        torch.cuda.synchronize()                                            # grown rarely; nothing in flight reads the old ones
-                        st.d_work = torch.empty(sizes[0] + sizes[0] // 4, dtype=torch.uint8, device=dev)
-                        st.d_scan = torch.empty(sizes[1] + sizes[1] // 4, dtype=torch.uint8, device=dev)
-                        st.h_scan = torch.empty(st.d_scan.numel(), dtype=torch.uint8).pin_memory()
-                        st.d_off = torch.empty(B + 1, dtype=torch.int64, device=dev)
-                        st.h_off = torch.empty(B + 1, dtype=torch.int64).pin_memory()
-                    engine.jpeg_encode_ragged_u8(d_packed, table_d, d_qtab, stream=stream, sizes=sizes, work=st.d_work, out=st.d_scan,
-                                                 out_off=st.d_off[:n + 1])
-                    copy(st.h_off, st.d_off, (n + 1) * 8, stream)
-            copy(st.h_dets, dets, n * cap * 6 * 4, stream)
-            copy(st.h_counts, counts, n * 4, stream)
+            late = None
+            if track:                                                                       # draw, encode and copies follow the tracker, in drain()
+                late = (dets, counts, d_packed, table_d, table, shapes, total)
+            else:
+                finish(st, n, dets, counts, dets, d_packed, table_d, table, shapes, total, stream)
             ev = torch.cuda.Event()
             ev.record(stream)
-            pending.append((first, n, st, table, keep, ev, slot, stream))                   # (keep: the device table, alive until the batch has run)
+            pending.append((first, n, st, table, keep, ev, slot, stream, late))             # (keep: the device table, alive until the batch has run)
         while pending:
             drain()
         written += [f.result() for f in saves]
+        if track:
+            _, _, overflow = tracks.read()
+            for s in np.flatnonzero(overflow):
+                raise engine.YkError(f'detect: track: sequence {seq_names[s]} needed more than track_max {int(track_max)} tracks at once: '
+                                     f'{int(overflow[s])} rows opened no track; raise track_max (at most {tk.MAX_TRACKS})')
     finally:
         pool.shutdown(wait=True)
         if pipe is not None:
@@ -452,8 +532,19 @@ def run(h: Helper, model, sources, out_dir=None, draw: bool = True, batch: int =
         if tta_spec is not None:
             rule.update(tt.rule_of(tta_spec, tta_thresh))
         doc = [{'path': names[i], **rule, 'detections': [[float(v) for v in row] for row in results[i]]} for i in range(n_all)]
+        if track:                                            # a row is a track's row with its id: [top, left, bottom, right, score, class, track_id]
+            rule.update(tracker='bytetrack-greedy', **track_cfg, track_max=int(track_max))
+            doc = [{'path': names[i], **rule, 'sequence': seq_names[seq_of[i]],
+                    'detections': [[*(float(v) for v in row), int(t)] for row, t in zip(results[i], track_ids[i])]} for i in range(n_all)]
+            (Path(out_dir) / 'tracks').mkdir(exist_ok=True)
+            for s, seq in enumerate(seq_names):
+                mine = np.flatnonzero(seq_of == s)
+                lines = [ln for frame, i in enumerate(mine, 1) for ln in tk.mot_lines(frame, results[i], track_ids[i])]
+                (Path(out_dir) / 'tracks' / f'{seq}.txt').write_text(''.join(ln + '\n' for ln in lines))
         (Path(out_dir) / 'detections.json').write_text(json.dumps(doc, indent=1))
     out = {'names': names, 'detections': results, 'files': written}
+    if track:
+        out.update(track_ids=track_ids, sequences=seq_names)
     if arrays is not None:
         out['arrays'] = arrays
     return out
@@ -478,13 +569,16 @@ def main(argv=None):
         raise engine.YkError(f'detect: no pictures ({", ".join(EXTENSIONS)}) in {a.src}')
     res = run(h, model, paths, out_dir=a.out_dir, draw=a.draw, batch=a.batch, depth=a.depth, precision=a.precision,
               obj_thresh=a.obj_thresh, iou_thresh=a.iou_thresh, workers=a.workers, encode=a.encode, quality=a.quality, decode=a.decode,
-              nms=a.nms, nms_sigma=a.nms_sigma, **tl.run_options(a), **tt.run_options(a))
+              nms=a.nms, nms_sigma=a.nms_sigma, **tl.run_options(a), **tt.run_options(a), **tk.run_options(a))
     if a.nms != 'hard':
         print(INFO, f' nms {a.nms}, sigma {a.nms_sigma:g}: scores are the decayed ones')
     if a.tiles is not None:
         print(INFO, f' tiles {a.tiles[0]}x{a.tiles[1]}, overlap {a.tile_overlap:g}, whole picture {a.tile_full}: merged by {a.tile_match} > {a.tile_thresh:g}')
     if a.tta is not None:
         print(INFO, f' tta {tt.text_of(a.tta)}: {len(a.tta)} views a picture, fused by IoU > {a.tta_thresh:g} (tta.py); scores are the fused ones')
+    if a.track:
+        print(INFO, f' track: {len(res["sequences"])} sequences, ids up to {max([int(t.max()) for t in res["track_ids"] if len(t)], default=0)} '
+                    f'(track.py: ByteTrack restated, class-aware and greedy) -> {Path(a.out_dir) / "tracks"}')
     print(INFO, f' {len(paths)} pictures, {sum(len(d) for d in res["detections"])} detections -> {Path(a.out_dir) / "detections.json"}'
           + (f', {len(res["files"])} annotated pictures' if a.draw else ''))
     return res

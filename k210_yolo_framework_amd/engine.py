@@ -816,6 +816,84 @@ def fuse_views(dets, counts, xforms, views: int, class_num: int, max_out: int, t
     return out, out_counts
 
 
+class TrackCfg(C.Structure):
+    """yk_track_cfg_t"""
+    _fields_ = [('track_thresh', C.c_float), ('low_thresh', C.c_float), ('match_thresh', C.c_float), ('track_buffer', C.c_int32)]
+
+
+def track_max_cap(max_tracks: int = 256) -> int:
+    """Rows of one frame that TrackState.update takes beside max_tracks tracks on the current device; more are refused."""
+    n = lib().yk_track_max_cap(int(max_tracks))
+    if n < 0:
+        _check(n, 'yk_track_max_cap')
+    return int(n)
+
+
+class TrackState:
+    """The tracks of n_seq sequences on the device (yk_track_update; the rule is track.Tracker's, bit for bit).  cfg: track_thresh,
+    low_thresh, match_thresh, track_buffer (track.check refuses bad ones by name)."""
+
+    def __init__(self, n_seq: int, class_num: int, max_tracks: int = 256, **cfg):
+        import torch
+        from . import track
+        require_gpu()
+        try:
+            opts = track.check(max_tracks=max_tracks, **cfg)
+        except (ValueError, TypeError) as e:
+            raise YkError(f'TrackState: {e}') from None
+        if int(n_seq) < 1 or int(class_num) < 1:
+            raise YkError(f'TrackState: n_seq {n_seq!r} and class_num {class_num!r} are at least 1')
+        self.n_seq, self.class_num, self.max_tracks = int(n_seq), int(class_num), int(max_tracks)
+        self.cfg = TrackCfg(opts['track_thresh'], opts['low_thresh'], opts['match_thresh'], opts['track_buffer'])
+        nbytes = C.c_size_t(0)
+        call('yk_track_state_bytes', self.n_seq, self.max_tracks, C.byref(nbytes))
+        self.state = torch.empty(nbytes.value // 4, dtype=torch.int32, device=torch.device('cuda', torch.cuda.current_device()))
+        self.reset()
+
+    def reset(self, stream=None) -> None:
+        """Every sequence back to no tracks, next id 1, no frames seen."""
+        call('yk_track_reset', self.state, self.n_seq, self.max_tracks, _stream(stream))
+
+    def update(self, dets, counts, seq_first, stream=None, draw: bool = False, out=None):
+        """dets cuda fp32 [n_frames, cap, 6] and counts cuda int32 [n_frames] as decode_py / Pipeline.submit leave them; seq_first a host
+        table [n_seq + 1] (the frames of sequence s are seq_first[s] .. seq_first[s+1] - 1, ascending from 0 to n_frames) or that table on
+        the device as cuda int32.  -> (rows cuda fp32 [n_frames, cap, 6], ids cuda int32 [n_frames, cap], counts cuda int32 [n_frames])
+        and, with draw, the rows with the class column replaced by id mod 100.  out: those tensors, to be written in place."""
+        import torch
+        assert dets.is_cuda and dets.dtype == torch.float32 and dets.is_contiguous() and dets.dim() == 3 and dets.shape[2] == 6, tuple(dets.shape)
+        n_frames, cap = int(dets.shape[0]), int(dets.shape[1])
+        assert counts.is_cuda and counts.dtype == torch.int32 and counts.is_contiguous() and tuple(counts.shape) == (n_frames,)
+        if not torch.is_tensor(seq_first):
+            sf = np.asarray(seq_first, np.int64).reshape(-1)
+            if len(sf) != self.n_seq + 1 or sf[0] != 0 or sf[-1] != n_frames or (np.diff(sf) < 0).any():
+                raise YkError(f'TrackState.update: seq_first {sf.tolist()}: expected {self.n_seq + 1} ascending values from 0 to n_frames {n_frames}')
+            with torch.cuda.stream(torch.cuda.current_stream() if stream is None else stream):
+                seq_first = torch.from_numpy(sf.astype(np.int32)).to(dets.device)
+        assert seq_first.is_cuda and seq_first.dtype == torch.int32 and seq_first.is_contiguous() and tuple(seq_first.shape) == (self.n_seq + 1,)
+        if out is None:
+            out = (torch.zeros((n_frames, cap, 6), dtype=torch.float32, device=dets.device),
+                   torch.zeros((n_frames, cap), dtype=torch.int32, device=dets.device),
+                   torch.zeros((n_frames,), dtype=torch.int32, device=dets.device)) + \
+                  ((torch.zeros((n_frames, cap, 6), dtype=torch.float32, device=dets.device),) if draw else ())
+            if stream is not None:
+                torch.cuda.current_stream().synchronize()                   # (filled on torch's stream, written on `stream`)
+        rows, ids, out_counts = out[:3]
+        d_draw = out[3] if draw else None
+        for t, shape, dt in ((rows, (n_frames, cap, 6), torch.float32), (ids, (n_frames, cap), torch.int32), (out_counts, (n_frames,), torch.int32)) + \
+                (((d_draw, (n_frames, cap, 6), torch.float32),) if draw else ()):
+            assert t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == shape, tuple(t.shape)
+        call('yk_track_update', self.state, self.n_seq, self.max_tracks, dets, counts, cap, seq_first, n_frames, self.class_num,
+             C.byref(self.cfg), rows, ids, out_counts, d_draw, _stream(stream))
+        self._keep = seq_first                                              # alive until the launch has read it
+        return (rows, ids, out_counts, d_draw) if draw else (rows, ids, out_counts)
+
+    def read(self):
+        """Waits for the device.  -> (live tracks, next id, overflow) per sequence, int32 [n_seq] each."""
+        live, next_id, overflow = (np.zeros(self.n_seq, np.int32) for _ in range(3))
+        call('yk_track_read', self.state, self.n_seq, self.max_tracks, live, next_id, overflow)
+        return live, next_id, overflow
+
+
 def mosaic_ragged_u8(packed, table, centres, dst_hw, inv=None, stream=None, out=None):
     """One training frame from four pictures per sample, the whole batch in one launch (yk_mosaic_ragged_u8; the rule is in mosaic.py):
     `packed` cuda uint8 [bytes], the pictures of draw.pack_ragged; `table` the samples' rows in quadrant order with scale / tx / ty filled
