@@ -60,6 +60,12 @@
 #                    [TRACK=True TRACKTHRESH=0.5 TRACKLOW=0.1 TRACKMATCH=0.8 TRACKBUFFER=30 TRACKMAX=256]: the pictures of a folder are the frames of
 #                    a sequence; rows get ids that last across frames on the GPU (ByteTrack restated, k210_yolo_framework_amd/track.py), the labels
 #                    show them, and OUTDIR/tracks/<sequence>.txt holds them in the MOTChallenge text format
+#   make trackeval   GT=folder RES=folder | SYNTHETIC=N [SEQFRAMES=60 SEQOBJECTS=8 SEED=0]: HOTA, MOTA and IDF1 (and DetA, AssA, LocA, MOTP, IDSW,
+#                    Frag, MT/PT/ML) of tracks files against ground truth, one line per sequence and a COMBINED line, trackeval.json beside RES.
+#                    GT and RES hold <sequence>.txt in the MOTChallenge text format (what `make detect TRACK=True` writes under OUTDIR/tracks);
+#                    GT may also hold <sequence>/gt/gt.txt.  Class-agnostic; the rule is k210_yolo_framework_amd/motmetrics.py, restated from
+#                    TrackEval from memory, parity unpinned.  [TRACKEVALDEVICE=gpu|cpu]: gpu (default) scores on the GPU (yk_mot_eval: similarity,
+#                    the linear assignment yk_lap_f64 and the three scores in HIP), cpu runs the numpy rule they are held to: DESIGN.md 3.28
 #   make anchors     DATASET=voc ANCNUM=3 [LOW='0.0 0.0' HIGH='1.0 1.0']   (reference Makefile:78-87: k-means anchors from data/<set>_img_ann.npy)
 #                    [ANCDEVICE=gpu RESTARTS=256 ANCSEED=0]: RESTARTS random starts in one GPU call; the set with the highest mean IoU is
 #                    kept and that IoU printed (ANCDEVICE=cpu RESTARTS=N loops the same rule in numpy)
@@ -165,6 +171,13 @@ TRACKLOW      ?= 0.1
 TRACKMATCH    ?= 0.8
 TRACKBUFFER   ?= 30
 TRACKMAX      ?= 256
+# trackeval only
+GT            ?=
+RES           ?=
+TRACKEVALDEVICE ?= gpu
+SEQFRAMES     ?= 60
+SEQOBJECTS    ?= 8
+SEED          ?= 0
 # kmodel only
 OUT           ?= yolo.kmodel
 CALIB         ?= data/$(DATASET)_img_ann.npy
@@ -221,9 +234,9 @@ else
 LAUNCH = $(PY) -m torch.distributed.run --nnodes=1 --nproc-per-node $(GPUS) --master-addr 127.0.0.1 --master-port 29533
 endif
 
-.PHONY: all build test bench inference train anchors kmodel eval detect
+.PHONY: all build test bench inference train anchors kmodel eval detect trackeval
 all:
-	@echo 'targets: build | test | bench | inference | train | kmodel | eval | detect   (see the header of this Makefile)'
+	@echo 'targets: build | test | bench | inference | train | kmodel | eval | detect | trackeval   (see the header of this Makefile)'
 
 build:
 	$(PY) -c "import __graft_entry__ as g; g.build()"
@@ -256,6 +269,10 @@ eval:
 # every picture of SRC (a folder or a text list) -> OUTDIR/detections.json + OUTDIR/<stem>_res.jpg; batches of BATCH pictures of any sizes
 detect:
 	$(PY) keras_detect.py $(CKPT) $(SRC) --out_dir $(OUTDIR) --draw $(DRAW) --decode $(DECODE) --encode $(ENCODE) --quality $(QUALITY) --batch $(BATCH) --precision $(PRECISION) $(NET_ARGS) $(NMS_ARGS) $(TILE_ARGS) $(TTA_ARGS) $(TRACK_ARGS)
+
+# scores of RES/<sequence>.txt against GT/<sequence>.txt (or GT/<sequence>/gt/gt.txt), or of SYNTHETIC=N generated sequences
+trackeval:
+	$(PY) keras_trackeval.py --device $(TRACKEVALDEVICE) $(if $(filter-out 0,$(SYNTHETIC)),--synthetic $(SYNTHETIC) --seq_frames $(SEQFRAMES) --seq_objects $(SEQOBJECTS) --seed $(SEED),--gt $(GT) --res $(RES))
 
 # reference Makefile:78-87 (same flags; --is_random True as there)
 anchors:

@@ -346,6 +346,70 @@ int yk_track_update(void *d_state, int n_seq, int max_tracks, const float *d_det
                     float *d_draw /* may be NULL: d_out with the class column replaced by id mod 100 */, void *stream);
 int yk_track_read(const void *d_state, int n_seq, int max_tracks, int32_t *h_live, int32_t *h_next_id, int32_t *h_overflow);
 
+/* ---- linear assignment: what the tracking scores (HOTA, CLEAR-MOT, identity) rest on (k210_yolo_framework_amd/motmetrics.py states the
+ * rule).  yk_lap_f64 solves n_problems rectangular minimum-cost assignment problems in one launch.  h_table, HOST memory,
+ * names them: problem k is rows x cols float64, row-major, at d_cost + cost_offset (in doubles), and leaves the column of every row, or -1
+ * (more rows than columns), in the rows int32 at d_out + out_offset (in words).  The rule is motmetrics.lap's, assignment for
+ * assignment: shortest augmenting paths with dual variables (Jonker-Volgenant in Crouse's form), the transpose solved when rows > cols,
+ * rows augmented in ascending order, r = ((minval + c) - u) - v relaxed with a strict <, the next column the FIRST argmin of the
+ * tentative distances among the unscanned columns, the duals moved by t = minval - dist; float64, one rounding per operation, no
+ * contraction.  Every entry must be finite (a forbidden pair carries 1e10): that is the caller's contract, the kernel does not look.
+ * One wavefront per problem, lanes own columns; the vectors live in LDS (YK_LAP_LDS_PER_COL bytes per column of the longer side,
+ * YK_LAP_LDS_PER_ROW per row of the shorter) and so does the cost matrix when rows * cols * 8 bytes fit beside them in
+ * YK_LAP_LDS_BYTES - otherwise it is read from global memory by the same code; which, is a function of the shape alone
+ * (yk_lap_lds_resident: 1 or 0).  No atomics: two calls give the same bytes.  The table is copied to the device on `stream` (the host
+ * copy is free again on return; not to be recorded in a graph), one launch on `stream`, no read back.  A NULL pointer, n_problems <= 0,
+ * rows or cols <= 0, the smaller side above YK_LAP_MAX or the larger above YK_LAP_MAX_LONG, a matrix that overruns n_cost doubles, an
+ * output that overruns n_out words or two outputs that overlap (matrices may be shared): YK_ERR_ARG with the argument named in
+ * yk_last_error, nothing launched. */
+#define YK_LAP_LDS_BYTES (160 * 1024)
+#define YK_LAP_LDS_PER_COL 28
+#define YK_LAP_LDS_PER_ROW 12
+#define YK_LAP_MAX 2048        /* the smaller side at the most */
+#define YK_LAP_MAX_LONG 4096   /* the larger side at the most: 28 * 4096 + 12 * 2048 = 139264 bytes of the 163840 */
+typedef struct {
+    int32_t rows, cols;
+    long long cost_offset, out_offset;
+} yk_lap_problem_t;
+int yk_lap_lds_resident(int rows, int cols);
+int yk_lap_limit(int which);   /* 0 YK_LAP_LDS_BYTES, 1 YK_LAP_LDS_PER_COL, 2 YK_LAP_LDS_PER_ROW, 3 YK_LAP_MAX, 4 YK_LAP_MAX_LONG; else YK_ERR_ARG */
+int yk_lap_f64(const double *d_cost, long long n_cost, const yk_lap_problem_t *h_table, int n_problems, int32_t *d_out, long long n_out,
+               void *stream);
+
+/* ---- the tracking scores on the GPU: HOTA, CLEAR-MOT and identity of packed sequences (motmetrics.hota / clear / identity state the
+ * rules; motmetrics_gpu.MotEvaluator builds the tables).  All sequences of a call are packed: ground-truth and result rows
+ * (left, top, width, height; float64) sorted by (sequence, frame), dense ids per sequence beside them; d_frame_tab [n_frames + 1][3] the
+ * first gt row, first result row and offset of the frame's similarity matrix; d_frame_seq [n_frames] a frame's sequence; d_seq_tab
+ * [n_seq + 1][5] per sequence the first frame, the gt ids and result ids before it, the G x T cells and the (G + T)^2 cells before it;
+ * d_csr_first / d_csr_rows the gt rows of every gt id in ascending frame order; d_gt_frame a gt row's frame; d_id_seq a gt id's
+ * sequence; d_gcount / d_tcount the frames an id appears in (float64); d_alpha_eps the 19 thresholds alpha - eps.  Six launches on `stream`
+ * after a kernel that clears the integer sums, no host read: similarity (one wavefront per frame, S and its ordered row / column sums
+ * written once into the ragged workspace), pmc / pm (one wavefront per gt id over its frames in ascending order, an LDS row of T
+ * accumulators: gas equals the rule's bit for bit), HOTA's matching (one wavefront per frame, every frame side by side, yk_lap_f64's device
+ * function on -(gas S); integer atomics for mc and TP / FN / FP), the Ass* folds (one wavefront per (sequence, alpha), an order the
+ * shape fixes), CLEAR (one wavefront per sequence walking its frames, prev / prev_t and the per-id counters in LDS), identity (one
+ * wavefront per sequence, the (G + T)^2 matrix in the workspace, one assignment).  No floating-point atomics: two calls give the same
+ * bytes.  d_out_i [n_seq][YK_MOT_OUT_INTS]: HOTA TP, FN, FP and the mc total per alpha (19 each), then CLR_TP, CLR_FN, CLR_FP, IDSW,
+ * Frag, MT, PT, ML.  d_out_d [n_seq][YK_MOT_OUT_DOUBLES]: sum mc A, sum mc mc / max(1, gcount), the same with tcount, and Loc per alpha (19
+ * each), then MOTPsum, sum fn and sum fp of the identity matches.  yk_mot_workspace_bytes sizes d_workspace from the shape.  Refused by
+ * name, never truncated, nothing launched: n_seq <= 0, a negative count, a sequence whose G x T exceeds YK_MOT_MAX_PAIR_CELLS (its 19 x
+ * G x T integers), whose G + T exceeds YK_LAP_MAX (its (G + T)^2 doubles), whose ids on one side exceed YK_MOT_MAX_IDS, a frame above
+ * YK_LAP_MAX x YK_LAP_MAX_LONG, CLEAR's LDS above YK_LAP_LDS_BYTES, a workspace that is too small, a NULL pointer. */
+#define YK_MOT_OUT_INTS 84
+#define YK_MOT_OUT_DOUBLES 80
+#define YK_MOT_MAX_PAIR_CELLS (1 << 22)
+#define YK_MOT_MAX_IDS 2048
+typedef struct {
+    int32_t n_seq, n_frames, n_gt_ids, n_res_ids;
+    int32_t max_seq_gt_ids, max_seq_res_ids, max_seq_ids, max_frame_gt, max_frame_res, reserved;
+    long long n_gt_rows, n_res_rows, s_cells, gt_cells, id_cells, max_seq_gt_cells;
+} yk_mot_shape_t;
+int yk_mot_workspace_bytes(const yk_mot_shape_t *shape, size_t *bytes);
+int yk_mot_eval(const yk_mot_shape_t *shape, const double *d_gt_box, const double *d_res_box, const int32_t *d_gt_id, const int32_t *d_res_id,
+                const long long *d_frame_tab, const int32_t *d_frame_seq, const long long *d_seq_tab, const int32_t *d_csr_first,
+                const int32_t *d_csr_rows, const int32_t *d_gt_frame, const int32_t *d_id_seq, const double *d_gcount, const double *d_tcount,
+                const double *d_alpha_eps, void *d_workspace, size_t workspace_bytes, int32_t *d_out_i, double *d_out_d, void *stream);
+
 /* ---- a step as one hipGraph (the kpu_run_kmodel(..., dma, ai_done_cb) shape of main.c:303-311: submit once, get called back) ----
  * Everything issued on `stream` (a created stream, not NULL) between yk_graph_begin and yk_graph_end - yk_run_*, yk_decode_py*,
  * yk_letterbox_u8, yk_memcpy_async - is recorded, not executed; yk_graph_launch replays the recording with ONE host call.

@@ -1,0 +1,611 @@
+// yk_mot.hip — the linear assignment that the tracking scores rest on (k210_yolo_framework_amd/motmetrics.py states the rule, the
+// Jonker-Volgenant shortest-augmenting-path algorithm in Crouse's form with stated tie rules).
+//
+// An assignment problem is a chain: row `cur` cannot be augmented before row cur - 1 has been, and inside an augmentation every step
+// needs the column the step before chose.  The parallelism there is lies across the columns of one step and across the problems of a
+// batch, and that is how the work is split:
+//   - one wavefront per problem, the problems of a call side by side on different CUs;
+//   - lanes own columns (lane, lane + 64, ...): a column's dual v, tentative distance, predecessor, scanned flag and holding row are only
+//     ever written by its own lane during the search, so the search needs no barrier: the wave reduction's shuffles publish the chosen column;
+//   - one step is ONE sweep: relax the unscanned columns against the current row and, in the same pass, keep the lane's smallest distance
+//     (strict <, ascending columns: the lane's first); a wave reduction over (distance, column) then gives the rule's first argmin;
+//   - the duals, distances, predecessors, the row <-> column maps and the flags live in LDS (28 bytes a column, 12 a row), and so does the
+//     cost matrix when it fits what is left of the 160 KB; if not it is read from global memory through the same device function - the
+//     switch is a function of the shape alone (yk_lap_resident);
+//   - a problem with more rows than columns is solved transposed by index: c(i, j) = cost[j * cols + i], nothing is copied.
+// No floating-point atomics (the assignment has no atomics at all; the scores below add integers only), so two calls give the same bytes.  Additions, subtractions and comparisons only: there is
+// no matrix product in it, hence no MFMA.  Compiled with -ffp-contract=off and without packed fp32: one rounding per operation, as
+// motmetrics.lap's float64 steps.
+#include <algorithm>
+#include <vector>
+
+#include "yk_common.h"
+
+struct lap_lds {
+    double *v, *dist, *u;                 // [n] column duals, [n] tentative distances, [m] row duals
+    int *pred, *row4col, *scanned;        // [n] each
+    int *col4row;                         // [m]
+};
+
+__host__ __device__ static inline size_t lap_vector_bytes(int m, int n) {
+    return (size_t)YK_LAP_LDS_PER_COL * n + (size_t)YK_LAP_LDS_PER_ROW * m;
+}
+
+// does the cost matrix of a rows x cols problem live in LDS beside the vectors?  A function of the shape alone.
+__host__ __device__ static inline bool yk_lap_resident(int rows, int cols) {
+    const int m = rows < cols ? rows : cols, n = rows < cols ? cols : rows;
+    return lap_vector_bytes(m, n) + (size_t)m * n * sizeof(double) <= (size_t)YK_LAP_LDS_BYTES;
+}
+
+__device__ __forceinline__ lap_lds lap_carve(void *base, int m, int n) {
+    lap_lds L;
+    L.v = reinterpret_cast<double *>(base);
+    L.dist = L.v + n;
+    L.u = L.dist + n;
+    L.pred = reinterpret_cast<int *>(L.u + m);
+    L.row4col = L.pred + n;
+    L.scanned = L.row4col + n;
+    L.col4row = L.scanned + n;
+    return L;
+}
+
+// arg-min over (value asc, column asc) across the wave; col < 0 means "no candidate"
+__device__ __forceinline__ void lap_wave_argmin(double &best, int &col) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const double ob = __shfl_xor(best, o, 64);
+        const int oc = __shfl_xor(col, o, 64);
+        if (oc >= 0 && (col < 0 || ob < best || (ob == best && oc < col))) {
+            best = ob;
+            col = oc;
+        }
+    }
+}
+
+// One problem by one wavefront.  c: the cost matrix, LDS or global (a generic pointer), indexed c[i * si + j * sj] for row i of the m the
+// wave augments and column j of the n it searches (m <= n).  Leaves col4row [m] and row4col [n] in L; the caller reads them after it.
+__device__ void yk_lap_wave(const double *c, long long si, long long sj, int m, int n, const lap_lds &L, int lane) {
+    for (int j = lane; j < n; j += 64) {
+        L.v[j] = 0.0;
+        L.row4col[j] = -1;
+    }
+    for (int i = lane; i < m; i += 64) {
+        L.u[i] = 0.0;
+        L.col4row[i] = -1;
+    }
+    __syncthreads();
+    for (int cur = 0; cur < m; ++cur) {
+        for (int j = lane; j < n; j += 64) {
+            L.dist[j] = INFINITY;
+            L.pred[j] = -1;
+            L.scanned[j] = 0;
+        }
+        double minval = 0.0;
+        int i = cur, sink = -1;
+        while (sink < 0) {
+            const double ui = L.u[i];
+            const double *ci = c + i * si;
+            double best = INFINITY;
+            int bcol = -1;
+            for (int j = lane; j < n; j += 64) {
+                if (L.scanned[j]) continue;
+                const double r = ((minval + ci[j * sj]) - ui) - L.v[j];
+                double d = L.dist[j];
+                if (r < d) {
+                    d = r;
+                    L.dist[j] = r;
+                    L.pred[j] = i;
+                }
+                if (bcol < 0 || d < best) {
+                    best = d;
+                    bcol = j;
+                }
+            }
+            lap_wave_argmin(best, bcol);                                 // (an unscanned column exists while no sink was found: m <= n)
+            minval = best;
+            if ((bcol & 63) == lane) L.scanned[bcol] = 1;
+            const int holder = L.row4col[bcol];
+            if (holder < 0) sink = bcol;
+            else i = holder;
+        }
+        __syncthreads();
+        // the duals: every scanned column but the sink is held by a row of its own, so no two lanes write one u
+        for (int j = lane; j < n; j += 64) {
+            if (!L.scanned[j]) continue;
+            const double t = minval - L.dist[j];
+            L.v[j] = L.v[j] - t;
+            if (j != sink) {
+                const int r = L.row4col[j];
+                L.u[r] = L.u[r] + t;
+            }
+        }
+        __syncthreads();
+        if (lane == 0) {
+            L.u[cur] = L.u[cur] + minval;
+            int j = sink;
+            for (;;) {
+                const int r = L.pred[j];
+                L.row4col[j] = r;
+                const int next = L.col4row[r];
+                L.col4row[r] = j;
+                j = next;
+                if (r == cur) break;
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// grid (n_problems), one wavefront; dynamic LDS: the largest problem's vectors and, where it is resident, its matrix
+__global__ void __launch_bounds__(64) lap_kernel(const double *__restrict__ cost, const yk_lap_problem_t *__restrict__ table,
+                                                 int32_t *__restrict__ out) {
+    extern __shared__ double lap_raw[];
+    const yk_lap_problem_t p = table[blockIdx.x];
+    const int lane = threadIdx.x, rows = p.rows, cols = p.cols;
+    const bool tall = rows > cols;
+    const int m = tall ? cols : rows, n = tall ? rows : cols;
+    const double *src = cost + p.cost_offset;
+    double *mat = lap_raw;
+    const bool resident = yk_lap_resident(rows, cols);
+    const lap_lds L = lap_carve(resident ? mat + (size_t)rows * cols : mat, m, n);
+    if (resident) {
+        for (int k = lane; k < rows * cols; k += 64) mat[k] = src[k];
+        src = mat;
+    }
+    // tall: the wave's row i is the problem's column i, its column j the problem's row j
+    yk_lap_wave(src, tall ? 1 : cols, tall ? cols : 1, m, n, L, lane);
+    int32_t *mine = out + p.out_offset;
+    const int *answer = tall ? L.row4col : L.col4row;
+    for (int r = lane; r < rows; r += 64) mine[r] = answer[r];
+}
+
+#define YK_LAP_REFUSE(cond, ...)                      \
+    if (cond) {                                       \
+        yk_set_error("yk_lap_f64: " __VA_ARGS__);     \
+        return YK_ERR_ARG;                            \
+    }
+
+extern "C" int yk_lap_lds_resident(int rows, int cols) {
+    if (rows <= 0 || cols <= 0) {
+        yk_set_error("yk_lap_lds_resident: rows %d, cols %d: expected at least 1 each", rows, cols);
+        return YK_ERR_ARG;
+    }
+    return yk_lap_resident(rows, cols) ? 1 : 0;
+}
+
+extern "C" int yk_lap_limit(int which) {
+    static const int v[5] = {YK_LAP_LDS_BYTES, YK_LAP_LDS_PER_COL, YK_LAP_LDS_PER_ROW, YK_LAP_MAX, YK_LAP_MAX_LONG};
+    if (which < 0 || which > 4) {
+        yk_set_error("yk_lap_limit: which %d: expected 0 .. 4", which);
+        return YK_ERR_ARG;
+    }
+    return v[which];
+}
+
+extern "C" int yk_lap_f64(const double *d_cost, long long n_cost, const yk_lap_problem_t *h_table, int n_problems, int32_t *d_out,
+                          long long n_out, void *stream) {
+    YK_LAP_REFUSE(!d_cost, "d_cost is NULL")
+    YK_LAP_REFUSE(!h_table, "h_table is NULL")
+    YK_LAP_REFUSE(!d_out, "d_out is NULL")
+    YK_LAP_REFUSE(n_problems <= 0, "n_problems %d: expected at least 1", n_problems)
+    YK_LAP_REFUSE(n_cost <= 0, "n_cost %lld: expected at least 1", n_cost)
+    YK_LAP_REFUSE(n_out <= 0, "n_out %lld: expected at least 1", n_out)
+    size_t lds = 0;
+    std::vector<std::pair<long long, long long>> spans((size_t)n_problems);
+    for (int k = 0; k < n_problems; ++k) {
+        const yk_lap_problem_t &p = h_table[k];
+        YK_LAP_REFUSE(p.rows <= 0, "h_table[%d].rows %d: expected at least 1", k, p.rows)
+        YK_LAP_REFUSE(p.cols <= 0, "h_table[%d].cols %d: expected at least 1", k, p.cols)
+        const int m = std::min(p.rows, p.cols), n = std::max(p.rows, p.cols);
+        YK_LAP_REFUSE(m > YK_LAP_MAX, "h_table[%d]: %d x %d, the smaller side is above YK_LAP_MAX %d (the row vectors live in LDS)", k, p.rows,
+                      p.cols, YK_LAP_MAX)
+        YK_LAP_REFUSE(n > YK_LAP_MAX_LONG, "h_table[%d]: %d x %d, the larger side is above YK_LAP_MAX_LONG %d (the column vectors live in LDS)", k,
+                      p.rows, p.cols, YK_LAP_MAX_LONG)
+        const long long cells = (long long)p.rows * p.cols;
+        YK_LAP_REFUSE(p.cost_offset < 0 || p.cost_offset > n_cost || cells > n_cost - p.cost_offset,
+                      "h_table[%d].cost_offset %lld: %d x %d doubles from there overrun the %lld of d_cost", k, p.cost_offset, p.rows, p.cols, n_cost)
+        YK_LAP_REFUSE(p.out_offset < 0 || p.out_offset > n_out || p.rows > n_out - p.out_offset,
+                      "h_table[%d].out_offset %lld: %d rows from there overrun the %lld of d_out", k, p.out_offset, p.rows, n_out)
+        spans[(size_t)k] = {p.out_offset, p.out_offset + p.rows};
+        lds = std::max(lds, lap_vector_bytes(m, n) + (yk_lap_resident(p.rows, p.cols) ? (size_t)cells * sizeof(double) : 0));
+    }
+    std::sort(spans.begin(), spans.end());
+    for (int k = 1; k < n_problems; ++k)
+        YK_LAP_REFUSE(spans[(size_t)k].first < spans[(size_t)k - 1].second, "two problems' outputs overlap at d_out[%lld]", spans[(size_t)k].first)
+    const int dev = yk_current_device();
+    if (dev < 0) {
+        yk_set_error("yk_lap_f64: no HIP device");
+        return YK_ERR_NO_DEVICE;
+    }
+    const size_t table_bytes = (size_t)n_problems * sizeof(yk_lap_problem_t);
+    void *d_table = yk_scratch(dev, stream, YK_SLOT_MOT, table_bytes);
+    if (!d_table) return YK_ERR_HIP;
+    // (pageable host memory: the runtime has taken its copy of the table when this returns, so the caller may free it)
+    YK_HIP(hipMemcpyAsync(d_table, h_table, table_bytes, hipMemcpyHostToDevice, (hipStream_t)stream));
+    yk_launch_lds(lap_kernel, dim3((unsigned)n_problems), dim3(64), lds, (hipStream_t)stream, d_cost, (const yk_lap_problem_t *)d_table, d_out);
+    YK_HIP(hipGetLastError());
+    return YK_OK;
+}
+
+// ---- the scores: HOTA, CLEAR-MOT and identity of packed sequences (motmetrics.hota / clear / identity state the rules) -----------------
+// How the work is split:
+//   - similarity: one wavefront per frame writes the frame's S (G_t x T_t) into a ragged workspace ONCE, and its row and column sums in
+//     the rule's order (ascending, one addition after the other); all three scores read them from there;
+//   - pmc and pm: one wavefront per ground-truth id walks that id's frames in ascending order from a host-built CSR list; lanes run over
+//     the frame's result rows and add into an LDS row of T accumulators (ids inside a frame are distinct: no collisions), so every
+//     (g, t) is summed in the rule's order and gas equals the rule's bit for bit;
+//   - HOTA's matching: one wavefront per frame, all frames of all sequences side by side (no chain over time): it builds
+//     -(gas * S) where S lay, calls yk_lap_wave on it and counts per alpha; mc[a] and TP / FN / FP are integer atomics, the localisation
+//     sum is left per frame and folded per sequence in frame order;
+//   - the Ass* folds: one wavefront per (sequence, alpha) over G x T, lane-strided and wave-reduced: an order the shape alone fixes;
+//   - CLEAR is a chain over frames: one wavefront per sequence walks its frames, prev / prev_t and the per-id counters in LDS;
+//   - identity: one wavefront per sequence builds the (G + T)^2 matrix in the workspace and makes one yk_lap_wave call.
+struct mot_args {
+    const double *g_box, *t_box;            // [NG][4], [NT][4] (left, top, width, height), rows sorted by (sequence, frame)
+    const int32_t *g_id, *t_id;             // dense ids inside their sequence
+    const long long *frame_tab;             // [F + 1][3]: first gt row, first result row, offset of S
+    const int32_t *frame_seq;               // [F]
+    const long long *seq_tab;               // [n_seq + 1][5]: first frame, ids before (gt, result), G x T cells before, (G + T)^2 cells before
+    const int32_t *csr_first, *csr_rows;    // [all gt ids + 1], [NG]: the gt rows of an id in ascending frame order
+    const int32_t *g_frame;                 // [NG] the frame of a gt row
+    const double *gcount, *tcount;          // per id: the frames it appears in
+    const double *alpha_eps;                // [19] alpha - eps
+    double *S, *M, *rowsum, *colsum, *gas, *idm, *locf;
+    int32_t *pm, *mc;
+    int32_t *out_i;                         // [n_seq][YK_MOT_OUT_INTS]
+    double *out_d;                          // [n_seq][YK_MOT_OUT_DOUBLES]
+    int n_seq, n_frames;
+};
+#define MOT_EPS 2.220446049250313e-16
+#define FT(f, k) A.frame_tab[(size_t)(f) * 3 + (k)]
+#define ST(s, k) A.seq_tab[(size_t)(s) * 5 + (k)]
+
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ int wave_sum_i(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+__global__ void __launch_bounds__(64) mot_clear_kernel(int32_t *__restrict__ a, long long na, int32_t *__restrict__ b, long long nb) {
+    const long long k = (long long)blockIdx.x * 64 + threadIdx.x;
+    if (k < na) a[k] = 0;
+    if (k < nb) b[k] = 0;
+}
+
+// grid (F)
+__global__ void __launch_bounds__(64) mot_similarity_kernel(mot_args A) {
+    const int f = blockIdx.x, lane = threadIdx.x;
+    const long long g0 = FT(f, 0), t0 = FT(f, 1), s0 = FT(f, 2);
+    const int G = (int)(FT(f + 1, 0) - g0), T = (int)(FT(f + 1, 1) - t0);
+    double *S = A.S + s0;
+    for (int k = lane; k < G * T; k += 64) {
+        const double *a = A.g_box + (g0 + k / T) * 4, *b = A.t_box + (t0 + k % T) * 4;
+        const double iw = fmax(fmin(a[0] + a[2], b[0] + b[2]) - fmax(a[0], b[0]), 0.0);
+        const double ih = fmax(fmin(a[1] + a[3], b[1] + b[3]) - fmax(a[1], b[1]), 0.0);
+        const double inter = iw * ih, uni = (a[2] * a[3] + b[2] * b[3]) - inter;
+        S[k] = uni > 0.0 ? inter / uni : 0.0;
+    }
+    __syncthreads();
+    for (int i = lane; i < G; i += 64) {
+        double r = 0.0;
+        for (int j = 0; j < T; ++j) r = j ? r + S[(size_t)i * T + j] : S[(size_t)i * T];
+        A.rowsum[g0 + i] = r;
+    }
+    for (int j = lane; j < T; j += 64) {
+        double c = 0.0;
+        for (int i = 0; i < G; ++i) c = i ? c + S[(size_t)i * T + j] : S[j];
+        A.colsum[t0 + j] = c;
+    }
+}
+
+// grid (all gt ids); dynamic LDS: 12 bytes per result id of the largest sequence.  id_seq: the sequence of a gt id
+__global__ void __launch_bounds__(64) mot_pair_kernel(mot_args A, const int32_t *__restrict__ id_seq) {
+    extern __shared__ double pair_raw[];
+    const int gi = blockIdx.x, lane = threadIdx.x, s = id_seq[gi];
+    const int G = (int)(ST(s + 1, 1) - ST(s, 1)), T = (int)(ST(s + 1, 2) - ST(s, 2)), g = gi - (int)ST(s, 1);
+    double *acc = pair_raw;
+    int *cnt = reinterpret_cast<int *>(acc + T);
+    for (int t = lane; t < T; t += 64) {
+        acc[t] = 0.0;
+        cnt[t] = 0;
+    }
+    __syncthreads();
+    for (int e = A.csr_first[gi]; e < A.csr_first[gi + 1]; ++e) {
+        const int r = A.csr_rows[e], f = A.g_frame[r];
+        const long long t0 = FT(f, 1);
+        const int Tt = (int)(FT(f + 1, 1) - t0), i = r - (int)FT(f, 0);
+        const double *row = A.S + FT(f, 2) + (size_t)i * Tt;
+        const double rs = A.rowsum[r];
+        for (int j = lane; j < Tt; j += 64) {
+            const double sv = row[j], d = (rs + A.colsum[t0 + j]) - sv;
+            const int t = A.t_id[t0 + j];
+            if (d > MOT_EPS) acc[t] += sv / d;
+            if (sv >= 0.5) cnt[t] += 1;
+        }
+        __syncthreads();
+    }
+    const size_t at = (size_t)ST(s, 3) + (size_t)g * T;
+    const double gc = A.gcount[gi];
+    for (int t = lane; t < T; t += 64) {
+        A.gas[at + t] = acc[t] / ((gc + A.tcount[ST(s, 2) + t]) - acc[t]);
+        A.pm[at + t] = cnt[t];
+    }
+    (void)G;
+}
+
+// one problem of rows x cols at c (global) by the calling wavefront -> the column of every row, or -1, in LDS
+__device__ __forceinline__ const int *lap_solve(const double *c, int rows, int cols, void *lds, int lane) {
+    const bool tall = rows > cols;
+    const int m = tall ? cols : rows, n = tall ? rows : cols;
+    const lap_lds L = lap_carve(lds, m, n);
+    yk_lap_wave(c, tall ? 1 : cols, tall ? cols : 1, m, n, L, lane);
+    return tall ? L.row4col : L.col4row;
+}
+
+// grid (F); dynamic LDS: the lap vectors of the largest frame
+__global__ void __launch_bounds__(64) mot_hota_match_kernel(mot_args A) {
+    extern __shared__ double hota_raw[];
+    const int f = blockIdx.x, lane = threadIdx.x, s = A.frame_seq[f];
+    const long long g0 = FT(f, 0), t0 = FT(f, 1), s0 = FT(f, 2);
+    const int G = (int)(FT(f + 1, 0) - g0), T = (int)(FT(f + 1, 1) - t0);
+    const int Ts = (int)(ST(s + 1, 2) - ST(s, 2));
+    const size_t GTs = (size_t)(ST(s + 1, 3) - ST(s, 3));
+    int32_t *oi = A.out_i + (size_t)s * YK_MOT_OUT_INTS;
+    double *loc = A.locf + (size_t)f * 19;
+    if (G == 0 || T == 0) {
+        for (int a = lane; a < 19; a += 64) {
+            loc[a] = 0.0;
+            if (T) atomicAdd(oi + 38 + a, T);
+            if (G) atomicAdd(oi + 19 + a, G);
+        }
+        return;
+    }
+    const double *S = A.S + s0, *gas = A.gas + ST(s, 3);
+    double *M = A.M + s0;
+    for (int k = lane; k < G * T; k += 64)
+        M[k] = -(gas[(size_t)A.g_id[g0 + k / T] * Ts + A.t_id[t0 + k % T]] * S[k]);
+    __syncthreads();
+    const int *col = lap_solve(M, G, T, hota_raw, lane);
+    for (int a = 0; a < 19; ++a) {
+        const double thr = A.alpha_eps[a];
+        int n = 0;
+        double sum = 0.0;
+        for (int i = lane; i < G; i += 64) {
+            const int j = col[i];
+            if (j < 0) continue;
+            const double sv = S[(size_t)i * T + j];
+            if (sv >= thr) {
+                ++n;
+                sum += sv;
+                atomicAdd(A.mc + (size_t)ST(s, 3) * 19 + (size_t)a * GTs + (size_t)A.g_id[g0 + i] * Ts + A.t_id[t0 + j], 1);
+            }
+        }
+        n = wave_sum_i(n);
+        sum = wave_sum(sum);
+        if (lane == 0) {
+            loc[a] = sum;
+            atomicAdd(oi + a, n);
+            atomicAdd(oi + 19 + a, G - n);
+            atomicAdd(oi + 38 + a, T - n);
+        }
+    }
+}
+
+// grid (n_seq, 19)
+__global__ void __launch_bounds__(64) mot_hota_fold_kernel(mot_args A) {
+    const int s = blockIdx.x, a = blockIdx.y, lane = threadIdx.x;
+    const int G = (int)(ST(s + 1, 1) - ST(s, 1)), T = (int)(ST(s + 1, 2) - ST(s, 2));
+    const size_t GT = (size_t)G * T;
+    const int32_t *mc = A.mc + (size_t)ST(s, 3) * 19 + (size_t)a * GT;
+    const double *gc = A.gcount + ST(s, 1), *tc = A.tcount + ST(s, 2);
+    double sa = 0.0, sr = 0.0, sp = 0.0, sl = 0.0;
+    int total = 0;
+    for (size_t k = lane; k < GT; k += 64) {
+        const int c = mc[k];
+        if (!c) continue;
+        const double m = (double)c, g = gc[k / T], t = tc[k % T];
+        sa += m * (m / fmax(1.0, (g + t) - m));
+        sr += m * (m / fmax(1.0, g));
+        sp += m * (m / fmax(1.0, t));
+        total += c;
+    }
+    for (long long f = ST(s, 0) + lane; f < ST(s + 1, 0); f += 64) sl += A.locf[(size_t)f * 19 + a];
+    sa = wave_sum(sa), sr = wave_sum(sr), sp = wave_sum(sp), sl = wave_sum(sl), total = wave_sum_i(total);
+    if (lane == 0) {
+        double *od = A.out_d + (size_t)s * YK_MOT_OUT_DOUBLES;
+        od[a] = sa, od[19 + a] = sr, od[38 + a] = sp, od[57 + a] = sl;
+        A.out_i[(size_t)s * YK_MOT_OUT_INTS + 57 + a] = total;
+    }
+}
+
+// grid (n_seq); dynamic LDS: the lap vectors of the largest frame, then 6 ints per gt id of the largest sequence
+__global__ void __launch_bounds__(64) mot_clear_mot_kernel(mot_args A, int lap_bytes) {
+    extern __shared__ double clear_raw[];
+    const int s = blockIdx.x, lane = threadIdx.x;
+    const int Gs = (int)(ST(s + 1, 1) - ST(s, 1));
+    int *prev = reinterpret_cast<int *>(reinterpret_cast<char *>(clear_raw) + lap_bytes);
+    int *prev_t = prev + Gs, *seen = prev_t + Gs, *matched = seen + Gs, *frags = matched + Gs, *now = frags + Gs;
+    for (int g = lane; g < Gs; g += 64) {
+        prev[g] = prev_t[g] = now[g] = -1;
+        seen[g] = matched[g] = frags[g] = 0;
+    }
+    __syncthreads();
+    int tp = 0, fn = 0, fp = 0, idsw = 0;
+    double motp = 0.0;
+    for (long long f = ST(s, 0); f < ST(s + 1, 0); ++f) {
+        const long long g0 = FT(f, 0), t0 = FT(f, 1);
+        const int G = (int)(FT(f + 1, 0) - g0), T = (int)(FT(f + 1, 1) - t0);
+        if (G == 0) {
+            if (lane == 0) fp += T;
+            continue;
+        }
+        for (int i = lane; i < G; i += 64) seen[A.g_id[g0 + i]] += 1;
+        if (T == 0) {
+            if (lane == 0) fn += G;
+            continue;
+        }
+        const double *S = A.S + FT(f, 2);
+        double *M = A.M + FT(f, 2);
+        for (int k = lane; k < G * T; k += 64) {
+            const double sv = S[k];
+            const double sc = (A.t_id[t0 + k % T] == prev_t[A.g_id[g0 + k / T]] ? 1000.0 : 0.0) + sv;
+            M[k] = sv < 0.5 - MOT_EPS ? -0.0 : -sc;
+        }
+        __syncthreads();
+        const int *col = lap_solve(M, G, T, clear_raw, lane);
+        int n = 0;
+        for (int i = lane; i < G; i += 64) {                              // (a frame's ids are distinct: every lane has ids of its own)
+            const int j = col[i];
+            if (j < 0 || !(-M[(size_t)i * T + j] > MOT_EPS)) continue;
+            const int g = A.g_id[g0 + i], t = A.t_id[t0 + j];
+            motp += S[(size_t)i * T + j];
+            if (prev[g] >= 0 && prev[g] != t) ++idsw;
+            if (prev_t[g] < 0) frags[g] += 1;
+            prev[g] = t;
+            now[g] = t;
+            matched[g] += 1;
+            ++n;
+        }
+        __syncthreads();
+        for (int g = lane; g < Gs; g += 64) {                             // prev_t: this frame's matches only
+            prev_t[g] = now[g];
+            now[g] = -1;
+        }
+        __syncthreads();
+        n = wave_sum_i(n);
+        if (lane == 0) tp += n, fn += G - n, fp += T - n;
+    }
+    idsw = wave_sum_i(idsw);
+    motp = wave_sum(motp);
+    int mt = 0, pt = 0, frag = 0;
+    for (int g = lane; g < Gs; g += 64) {
+        const double ratio = (double)matched[g] / fmax(1.0, (double)seen[g]);
+        if (ratio > 0.8) ++mt;
+        else if (ratio >= 0.2) ++pt;
+        if (frags[g] > 0) frag += frags[g] - 1;
+    }
+    mt = wave_sum_i(mt), pt = wave_sum_i(pt), frag = wave_sum_i(frag);
+    if (lane == 0) {
+        int32_t *oi = A.out_i + (size_t)s * YK_MOT_OUT_INTS + 76;
+        oi[0] = tp, oi[1] = fn, oi[2] = fp, oi[3] = idsw, oi[4] = frag, oi[5] = mt, oi[6] = pt, oi[7] = Gs - mt - pt;
+        A.out_d[(size_t)s * YK_MOT_OUT_DOUBLES + 76] = motp;
+    }
+}
+
+__device__ __forceinline__ void identity_cell(const mot_args &A, int s, int G, int T, int r, int c, double &fn, double &fp) {
+    const double gc = r < G ? A.gcount[ST(s, 1) + r] : 0.0, tc = c < T ? A.tcount[ST(s, 2) + c] : 0.0;
+    const double pm = r < G && c < T ? (double)A.pm[(size_t)ST(s, 3) + (size_t)r * T + c] : 0.0;
+    fn = r >= G ? 0.0 : c < T ? gc - pm : c - T == r ? gc : 1e10;
+    fp = c >= T ? 0.0 : r < G ? tc - pm : r - G == c ? tc : 1e10;
+}
+
+// grid (n_seq); dynamic LDS: the lap vectors of the largest G + T
+__global__ void __launch_bounds__(64) mot_identity_kernel(mot_args A) {
+    extern __shared__ double ident_raw[];
+    const int s = blockIdx.x, lane = threadIdx.x;
+    const int G = (int)(ST(s + 1, 1) - ST(s, 1)), T = (int)(ST(s + 1, 2) - ST(s, 2)), N = G + T;
+    double *od = A.out_d + (size_t)s * YK_MOT_OUT_DOUBLES;
+    if (N == 0) {
+        if (lane == 0) od[77] = od[78] = 0.0;
+        return;
+    }
+    double *M = A.idm + ST(s, 4);
+    for (size_t k = lane; k < (size_t)N * N; k += 64) {
+        double fn, fp;
+        identity_cell(A, s, G, T, (int)(k / N), (int)(k % N), fn, fp);
+        M[k] = fn + fp;
+    }
+    __syncthreads();
+    const int *col = lap_solve(M, N, N, ident_raw, lane);
+    double sfn = 0.0, sfp = 0.0;
+    for (int r = lane; r < N; r += 64) {
+        double fn, fp;
+        identity_cell(A, s, G, T, r, col[r], fn, fp);
+        sfn += fn, sfp += fp;
+    }
+    sfn = wave_sum(sfn), sfp = wave_sum(sfp);
+    if (lane == 0) od[77] = sfn, od[78] = sfp;
+}
+
+#define YK_MOT_REFUSE(fn, cond, ...)        \
+    if (cond) {                             \
+        yk_set_error(fn ": " __VA_ARGS__);  \
+        return YK_ERR_ARG;                  \
+    }
+#define YK_MOT_SHAPE_ARGS(fn)                                                                                                                  \
+    YK_MOT_REFUSE(fn, !sh, "shape is NULL")                                                                                                    \
+    YK_MOT_REFUSE(fn, sh->n_seq <= 0, "shape->n_seq %d: expected at least 1", sh->n_seq)                                                       \
+    YK_MOT_REFUSE(fn, sh->n_frames < 0 || sh->n_gt_rows < 0 || sh->n_res_rows < 0 || sh->n_gt_ids < 0 || sh->n_res_ids < 0 ||                  \
+                          sh->s_cells < 0 || sh->gt_cells < 0 || sh->id_cells < 0, "shape: a negative count")                                  \
+    YK_MOT_REFUSE(fn, sh->max_seq_gt_cells > YK_MOT_MAX_PAIR_CELLS, "shape->max_seq_gt_cells %lld: a sequence's 19 x G x T integers exceed 19 x %lld", \
+                  sh->max_seq_gt_cells, (long long)YK_MOT_MAX_PAIR_CELLS)                                                                      \
+    YK_MOT_REFUSE(fn, sh->max_seq_ids > YK_LAP_MAX, "shape->max_seq_ids %d: a sequence's (G + T)^2 doubles exceed %d^2 (YK_LAP_MAX)",          \
+                  sh->max_seq_ids, YK_LAP_MAX)                                                                                                 \
+    YK_MOT_REFUSE(fn, sh->max_seq_res_ids > YK_MOT_MAX_IDS || sh->max_seq_gt_ids > YK_MOT_MAX_IDS,                                             \
+                  "shape->max_seq_gt_ids %d, max_seq_res_ids %d: a sequence's ids per side exceed %d (their counters live in LDS)",            \
+                  sh->max_seq_gt_ids, sh->max_seq_res_ids, YK_MOT_MAX_IDS)                                                                     \
+    YK_MOT_REFUSE(fn, sh->max_frame_gt > YK_LAP_MAX_LONG || sh->max_frame_res > YK_LAP_MAX_LONG ||                                             \
+                          (sh->max_frame_gt > YK_LAP_MAX && sh->max_frame_res > YK_LAP_MAX),                                                   \
+                  "shape->max_frame_gt %d, max_frame_res %d: a frame's assignment exceeds %d x %d", sh->max_frame_gt, sh->max_frame_res,       \
+                  YK_LAP_MAX, YK_LAP_MAX_LONG)
+
+static size_t mot_up(size_t b) { return (b + 255) & ~(size_t)255; }
+
+extern "C" int yk_mot_workspace_bytes(const yk_mot_shape_t *sh, size_t *bytes) {
+    YK_MOT_SHAPE_ARGS("yk_mot_workspace_bytes")
+    YK_MOT_REFUSE("yk_mot_workspace_bytes", !bytes, "bytes is NULL")
+    *bytes = 2 * mot_up(8 * (size_t)sh->s_cells) + mot_up(8 * (size_t)sh->n_gt_rows) + mot_up(8 * (size_t)sh->n_res_rows) +
+             mot_up(8 * (size_t)sh->gt_cells) + mot_up(8 * (size_t)sh->id_cells) + mot_up(8 * 19 * (size_t)sh->n_frames) +
+             mot_up(4 * (size_t)sh->gt_cells) + mot_up(4 * 19 * (size_t)sh->gt_cells) + 256;
+    return YK_OK;
+}
+
+extern "C" int yk_mot_eval(const yk_mot_shape_t *sh, const double *d_gt_box, const double *d_res_box, const int32_t *d_gt_id,
+                           const int32_t *d_res_id, const long long *d_frame_tab, const int32_t *d_frame_seq, const long long *d_seq_tab,
+                           const int32_t *d_csr_first, const int32_t *d_csr_rows, const int32_t *d_gt_frame, const int32_t *d_id_seq,
+                           const double *d_gcount, const double *d_tcount, const double *d_alpha_eps, void *d_workspace, size_t workspace_bytes,
+                           int32_t *d_out_i, double *d_out_d, void *stream) {
+    YK_MOT_SHAPE_ARGS("yk_mot_eval")
+    size_t need = 0;
+    yk_mot_workspace_bytes(sh, &need);
+    YK_MOT_REFUSE("yk_mot_eval", !d_workspace || workspace_bytes < need, "d_workspace: %zu bytes, yk_mot_workspace_bytes asks for %zu", workspace_bytes, need)
+    YK_MOT_REFUSE("yk_mot_eval", !d_gt_box || !d_res_box || !d_gt_id || !d_res_id || !d_frame_tab || !d_frame_seq || !d_seq_tab || !d_csr_first ||
+                                     !d_csr_rows || !d_gt_frame || !d_id_seq || !d_gcount || !d_tcount || !d_alpha_eps || !d_out_i || !d_out_d,
+                  "a table or an output is NULL")
+    mot_args A;
+    A.g_box = d_gt_box, A.t_box = d_res_box, A.g_id = d_gt_id, A.t_id = d_res_id, A.frame_tab = d_frame_tab, A.frame_seq = d_frame_seq;
+    A.seq_tab = d_seq_tab, A.csr_first = d_csr_first, A.csr_rows = d_csr_rows, A.g_frame = d_gt_frame, A.gcount = d_gcount, A.tcount = d_tcount;
+    A.alpha_eps = d_alpha_eps, A.out_i = d_out_i, A.out_d = d_out_d, A.n_seq = sh->n_seq, A.n_frames = sh->n_frames;
+    char *w = (char *)(((uintptr_t)d_workspace + 255) & ~(uintptr_t)255);
+    auto take = [&w](size_t b) { char *p = w; w += mot_up(b); return p; };
+    A.S = (double *)take(8 * (size_t)sh->s_cells), A.M = (double *)take(8 * (size_t)sh->s_cells);
+    A.rowsum = (double *)take(8 * (size_t)sh->n_gt_rows), A.colsum = (double *)take(8 * (size_t)sh->n_res_rows);
+    A.gas = (double *)take(8 * (size_t)sh->gt_cells), A.idm = (double *)take(8 * (size_t)sh->id_cells);
+    A.locf = (double *)take(8 * 19 * (size_t)sh->n_frames);
+    A.pm = (int32_t *)take(4 * (size_t)sh->gt_cells), A.mc = (int32_t *)take(4 * 19 * (size_t)sh->gt_cells);
+    const int fm = std::min(sh->max_frame_gt, sh->max_frame_res), fn = std::max(sh->max_frame_gt, sh->max_frame_res);
+    const size_t frame_lap = (lap_vector_bytes(std::max(fm, 1), std::max(fn, 1)) + 15) & ~(size_t)15;
+    const size_t clear_lds = frame_lap + (size_t)24 * std::max(sh->max_seq_gt_ids, 1);
+    YK_MOT_REFUSE("yk_mot_eval", clear_lds > YK_LAP_LDS_BYTES, "CLEAR needs %zu bytes of LDS for max_frame %d x %d beside %d ids, above %d",
+                  clear_lds, sh->max_frame_gt, sh->max_frame_res, sh->max_seq_gt_ids, YK_LAP_LDS_BYTES)
+    hipStream_t st = (hipStream_t)stream;
+    const long long n_mc = 19 * sh->gt_cells, n_oi = (long long)sh->n_seq * YK_MOT_OUT_INTS, n_clr = std::max(n_mc, n_oi);
+    hipLaunchKernelGGL(mot_clear_kernel, dim3((unsigned)((n_clr + 63) / 64)), dim3(64), 0, st, A.mc, n_mc, d_out_i, n_oi);
+    if (sh->n_frames > 0) {
+        hipLaunchKernelGGL(mot_similarity_kernel, dim3((unsigned)sh->n_frames), dim3(64), 0, st, A);
+        if (sh->n_gt_ids > 0)
+            yk_launch_lds(mot_pair_kernel, dim3((unsigned)sh->n_gt_ids), dim3(64), (size_t)12 * std::max(sh->max_seq_res_ids, 1), st, A, d_id_seq);
+        yk_launch_lds(mot_hota_match_kernel, dim3((unsigned)sh->n_frames), dim3(64), frame_lap, st, A);
+    }
+    hipLaunchKernelGGL(mot_hota_fold_kernel, dim3((unsigned)sh->n_seq, 19), dim3(64), 0, st, A);
+    yk_launch_lds(mot_clear_mot_kernel, dim3((unsigned)sh->n_seq), dim3(64), clear_lds, st, A, (int)frame_lap);
+    const int N = std::max(sh->max_seq_ids, 1);
+    yk_launch_lds(mot_identity_kernel, dim3((unsigned)sh->n_seq), dim3(64), lap_vector_bytes(N, N), st, A);
+    YK_HIP(hipGetLastError());
+    return YK_OK;
+}

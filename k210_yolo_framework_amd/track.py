@@ -9,8 +9,8 @@ PARITY UNPINNED: the authors' code is not on hand and no number here is held to 
   - class-aware.  A track keeps the class of the row that opened it and pairs of different classes never match (ByteTrack is written for
     one class; this detector has twenty).
   - greedy, not Hungarian.  In each stage the pair with the largest IoU is taken, then the next (ties: the lowest track index, then the
-    lowest row index).  A linear assignment has no order of operations a kernel could be held to bit for bit; the greedy rule has, and is
-    what embedded ports do.
+    lowest row index).  An unspecified linear-assignment solver has no order of operations a kernel could be held to bit for bit; the
+    greedy rule has, and is what embedded ports do.  (motmetrics.lap states one that has, for the scores: DESIGN.md 3.28.)
   - the defaults (track_thresh 0.5, low_thresh 0.1, match_thresh 0.8, track_buffer 30) are ByteTrack's and are starting points, not
     findings; its `fuse_score` option is left out.
 What is pinned: the filter against the dense 8 x 8 filter in float64 and the rule on hand cases (tests/test_track.py), and the kernel
