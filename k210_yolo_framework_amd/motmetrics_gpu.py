@@ -133,6 +133,10 @@ class MotEvaluator:
             out_d = torch.zeros((len(self.seqs), OUT_DOUBLES), dtype=torch.float64, device=self.device)
             engine.call('yk_mot_eval', C.byref(sh), *dev, ws, nbytes.value, out_i, out_d, engine._stream(stream))
             oi, od = out_i.cpu().numpy().astype(np.int64), out_d.cpu().numpy()
+        return self._scores(oi, od)
+
+    def _scores(self, oi: np.ndarray, od: np.ndarray) -> dict:
+        """yk_mot_eval's two outputs on the host (int64 [n_seq, OUT_INTS], float64 [n_seq, OUT_DOUBLES]) -> what result() returns"""
         per = {}
         for k, s in enumerate(self.seqs):
             i, d = oi[k], od[k]
