@@ -608,6 +608,49 @@ typedef struct {
 } yk_label_cfg_t;                                       /* 584 bytes, no padding */
 int yk_boxes_to_labels_f32(const yk_label_cfg_t *cfg, const double *d_boxes, int n_boxes, const int32_t *d_first, int n, float *d_labels,
                            int32_t *d_status, void *stream);
+/* ---- SimOTA dynamic label assignment (k210_yolo_framework_amd/simota.py is the rule; csrc/yk_ota.hip) ------
+ * The same dense label grids, but which predictions train on which box is decided from the step's own predictions: d_pred is a HOST array
+ * of cfg->n_layers device pointers, layer l's raw outputs [n][out_h][out_w][A][5 + class_num] fp32; d_boxes, d_first and the flat layout of
+ * d_labels are yk_boxes_to_labels_f32's.  n_boxes is the CAPACITY of d_boxes: the counts are read from d_first on the device, clamped to
+ * [0, n_boxes) as there, so a captured call serves batches of any box count.  Per image, every (layer, row, col, anchor) is a candidate j in
+ * the flat order of the label buffer; a valid box g (the label kernel's test - class truncated toward zero in [0, class_num), centre finite
+ * and its cell inside EVERY layer's grid - and among the first cfg->max_boxes rows of its image) takes its k_g eligible candidates of
+ * smallest cost, ties to the lower j, and a candidate taken by several boxes goes to the one of smallest cost, ties to the lower g:
+ *   eligible  the candidate's cell centre lies inside the box or within radius cells of its centre
+ *   cost      (Z_j + L0(q_c)) - L1(q_c) + iou_weight (-log(IoU + 1e-8)) + 1e5 unless both of the above hold, q_k = sqrt(s(tc_k) s(to)),
+ *             Z_j = sum_k -L0(q_k) with k ascending, L0 / L1 the binary cross-entropy's two logarithms clamped at -100
+ *   k_g       min(E_g, max(1, floor(S))), S the sum of the min(topk, E_g) largest eligible IoUs added from the largest down
+ * all in float64, contraction off, in simota.py's operation order; the owner writes (float)clip(x y w h, 1e-8, 1), 1 and the class bit into
+ * slot j, every other element of d_labels is written 0.  d_npos [n]: the slots written per image.  *d_status: INT32_MAX, or the smallest
+ * row of d_boxes of which nothing was written (an invalid box, or the first row past max_boxes of an image).  Held to simota.assign decision
+ * for decision wherever that function's margin exceeds the few ulps by which exp, log and log1p differ between the host's libm and the device.
+ * Four launches (clear, per-candidate decode and Z_j, one workgroup per (image, box) for the two searches, one workgroup per image for the
+ * owners); no memset node, no floating-point atomics, no synchronisation: two calls give the same bytes, and the call can be recorded in a
+ * graph.  Up to YK_OTA_LDS_CANDS candidates per image a workgroup keeps its 8-byte-per-candidate strip in LDS, past that in d_work.
+ * yk_simota_workspace_bytes: the bytes of d_work for n images of up to max_boxes boxes (its own argument; cfg->max_boxes is not read).
+ * n == 0: YK_OK, nothing launched.  NULL cfg, d_first, d_pred or one of its entries, d_labels, d_npos, d_status or d_work with n > 0, NULL d_boxes
+ * with n_boxes > 0, n outside 0 .. 65535, n_boxes outside 0 .. 2^30 - 1, max_boxes outside 1 .. YK_OTA_MAX_BOXES, n_layers outside
+ * 1 .. YK_MAX_LAYERS, an anchor_num outside 1 .. YK_MAX_ANCHORS, out_h or out_w <= 0, class_num outside 1 .. YK_OTA_MAX_CLASSES, topk outside
+ * 1 .. YK_OTA_MAX_TOPK, radius outside 1 .. 16, iou_weight not positive and finite, more than 2^24 candidates per image, a misaligned pointer,
+ * work_bytes below the query's answer: YK_ERR_ARG, the message names the function and the argument, nothing launched; these checks come
+ * before the device is needed.  No device: YK_ERR_NO_DEVICE. */
+#define YK_OTA_LDS_CANDS 6144
+#define YK_OTA_MAX_TOPK 32
+#define YK_OTA_MAX_BOXES 256
+#define YK_OTA_MAX_CLASSES 4096
+typedef struct {
+    int32_t n_layers, class_num;
+    int32_t topk;                                       /* 1 .. YK_OTA_MAX_TOPK */
+    int32_t max_boxes;                                  /* boxes per image, 1 .. YK_OTA_MAX_BOXES */
+    int32_t out_h[YK_MAX_LAYERS], out_w[YK_MAX_LAYERS]; /* Helper.out_hw */
+    int32_t anchor_num[YK_MAX_LAYERS];
+    double anchors[YK_MAX_LAYERS][YK_MAX_ANCHORS][2];   /* np.asarray(Helper.anchors, float): (w, h), image-relative */
+    double radius, iou_weight;
+} yk_ota_cfg_t;                                         /* 592 bytes, no padding */
+int yk_simota_workspace_bytes(const yk_ota_cfg_t *cfg, int n, int max_boxes, size_t *bytes);
+int yk_assign_simota_f32(const yk_ota_cfg_t *cfg, const double *d_boxes, int n_boxes, const int32_t *d_first, int n,
+                         const float *const *d_pred /* [n_layers] raw outputs [n][h][w][A][5+C] */,
+                         float *d_labels, int32_t *d_npos, int32_t *d_status, void *d_work, size_t work_bytes, void *stream);
 /* Draws detections INTO the pictures of a ragged batch, in place (inference.py's PIL loop plus keras_inference.py:137-174's label with
  * its filled background), by the painter's rule: for picture i and its rows k = 0 .. count_i - 1 in order, later paint over earlier:
  *   corners   t = max(0, floorf(top + 0.5f)), l likewise from left; b = min(h, floorf(bottom + 0.5f)), r = min(w, floorf(right + 0.5f))

@@ -79,6 +79,20 @@ class LabelCfg(C.Structure):
                 ('anchors', (C.c_double * 2) * YK_MAX_ANCHORS * YK_MAX_LAYERS), ('assign_iou', C.c_double)]
 
 
+class OtaCfg(C.Structure):
+    """yk_ota_cfg_t"""
+    _fields_ = [('n_layers', C.c_int32), ('class_num', C.c_int32), ('topk', C.c_int32), ('max_boxes', C.c_int32),
+                ('out_h', C.c_int32 * YK_MAX_LAYERS), ('out_w', C.c_int32 * YK_MAX_LAYERS), ('anchor_num', C.c_int32 * YK_MAX_LAYERS),
+                ('anchors', (C.c_double * 2) * YK_MAX_ANCHORS * YK_MAX_LAYERS), ('radius', C.c_double), ('iou_weight', C.c_double)]
+
+
+class BoxBatch(NamedTuple):
+    """The boxes of a batch on the device, as assign_simota reads them: boxes cuda float64 [capacity, 5] rows (cls, x, y, w, h), first cuda
+    int32 [n + 1]; image i owns rows first[i] .. first[i + 1] - 1, rows past first[n] are not read."""
+    boxes: object
+    first: object
+
+
 BOX_LOSSES = {'mse': 0, 'giou': 1, 'diou': 2, 'ciou': 3}      # YK_BOX_LOSS_* (include/yolo_hip.h)
 LABEL_STATUS_CLEAN = 2 ** 31 - 1                              # what yk_boxes_to_labels_f32 leaves in its status word for a clean batch
 
@@ -1009,6 +1023,77 @@ def boxes_to_labels(boxes, first, helper, assign: str = 'best', assign_iou: floa
         views.append(out[at:at + size].view(s))
         at += size
     return views, status
+
+
+OTA_MAX_BOXES, OTA_MAX_TOPK = 256, 32                         # YK_OTA_MAX_BOXES, YK_OTA_MAX_TOPK
+_ota_work: dict = {}                                          # (device, stream handle) -> the workspace of assign_simota, grow-only
+
+
+def make_ota_cfg(helper, topk: int = 10, radius: float = 2.5, iou_weight: float = 3.0, max_boxes: int = 64) -> OtaCfg:
+    """yk_ota_cfg_t of a Helper (or of a dict with out_hw, anchors, class_num): its grids, its anchors as float64 and SimOTA's options
+    (simota.py).  CPU only; the ranges are checked by the library."""
+    from . import simota
+    out_hw, anchors, class_num = simota.grids(helper)
+    if not 1 <= len(anchors) <= YK_MAX_LAYERS or any(not 1 <= len(a) <= YK_MAX_ANCHORS for a in anchors) or len(out_hw) != len(anchors):
+        raise YkError(f'simota: {len(anchors)} layers of {[len(a) for a in anchors]} anchors: at most {YK_MAX_LAYERS} of {YK_MAX_ANCHORS}')
+    cfg = OtaCfg()
+    cfg.n_layers, cfg.class_num, cfg.topk, cfg.max_boxes = len(anchors), class_num, int(topk), int(max_boxes)
+    cfg.radius, cfg.iou_weight = float(radius), float(iou_weight)
+    for l, a in enumerate(anchors):
+        cfg.out_h[l], cfg.out_w[l], cfg.anchor_num[l] = out_hw[l][0], out_hw[l][1], len(a)
+        for k, (w, h) in enumerate(a):
+            cfg.anchors[l][k][0], cfg.anchors[l][k][1] = float(w), float(h)
+    return cfg
+
+
+def assign_simota(preds, boxes, first, cfg, max_boxes: Optional[int] = None, stream=None, out=None):
+    """SimOTA label grids of a batch from its boxes and the step's raw outputs (yk_assign_simota_f32; the rule is simota.assign's):
+    preds: per layer a contiguous cuda float32 [n, h, w, A, 5 + C]; boxes cuda float64 [capacity, 5], first cuda int32 [n + 1] (a BoxBatch's
+    fields; host arrays are uploaded); cfg: make_ota_cfg's, or a Helper (then the default options); max_boxes overrides cfg's.
+    -> ([one view [n, h, w, A, 5 + C] float32 per layer of ONE flat buffer], npos cuda int32 [n], status cuda int32 [1]); status holds
+    INT32_MAX or the smallest row of `boxes` of which nothing was written.  out: (flat labels, npos, status) to reuse.  The workspace is
+    kept per stream and only grows.  Does not synchronise; once it has run eagerly on a stream the call can be recorded in a graph there."""
+    import torch
+    require_gpu()
+    if not isinstance(cfg, OtaCfg):
+        cfg = make_ota_cfg(cfg)
+    if max_boxes is not None and int(max_boxes) != cfg.max_boxes:
+        cfg = OtaCfg.from_buffer_copy(cfg)
+        cfg.max_boxes = int(max_boxes)
+    with torch.cuda.stream(torch.cuda.current_stream() if stream is None else stream):
+        if not torch.is_tensor(boxes):
+            boxes = torch.from_numpy(np.ascontiguousarray(boxes, np.float64).reshape(-1, 5)).cuda()
+        if not torch.is_tensor(first):
+            first = torch.from_numpy(np.ascontiguousarray(first, np.int32).reshape(-1)).cuda()
+        assert boxes.is_cuda and boxes.dtype == torch.float64 and boxes.is_contiguous() and boxes.dim() == 2 and boxes.shape[1] == 5, 'boxes: cuda float64 [N, 5]'
+        assert first.is_cuda and first.dtype == torch.int32 and first.is_contiguous() and first.dim() == 1 and first.numel() >= 1 and first.device == boxes.device
+        n = int(first.numel()) - 1
+        shapes = [(n, int(cfg.out_h[l]), int(cfg.out_w[l]), int(cfg.anchor_num[l]), 5 + int(cfg.class_num)) for l in range(cfg.n_layers)]
+        sizes = [int(np.prod(s, dtype=np.int64)) for s in shapes]
+        assert len(preds) == cfg.n_layers, f'preds: {len(preds)} layers, cfg has {cfg.n_layers}'
+        for p, s in zip(preds, shapes):
+            assert p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() and tuple(p.shape) == s and p.device == boxes.device, (tuple(p.shape), s)
+        nbytes = C.c_size_t()
+        call('yk_simota_workspace_bytes', C.byref(cfg), n, int(cfg.max_boxes), C.byref(nbytes))
+        key = (boxes.device.index, _stream(stream).value)
+        work = _ota_work.get(key)
+        if work is None or work.numel() < max(nbytes.value, 8):
+            work = _ota_work[key] = torch.empty((max(nbytes.value, 8),), dtype=torch.uint8, device=boxes.device)
+        labels, npos, status = out if out is not None else (torch.empty((sum(sizes),), dtype=torch.float32, device=boxes.device),
+                                                             torch.zeros((n,), dtype=torch.int32, device=boxes.device),
+                                                             torch.empty((1,), dtype=torch.int32, device=boxes.device))
+        if n == 0:                                                          # (the library launches nothing)
+            status.fill_(LABEL_STATUS_CLEAN)
+    assert labels.is_cuda and labels.dtype == torch.float32 and labels.is_contiguous() and labels.numel() == sum(sizes) and labels.device == boxes.device
+    assert npos.dtype == torch.int32 and npos.numel() == n and status.dtype == torch.int32 and status.numel() == 1 and npos.is_cuda and status.is_cuda
+    ptrs = (C.c_void_p * YK_MAX_LAYERS)(*[p.data_ptr() for p in preds])
+    call('yk_assign_simota_f32', C.byref(cfg), boxes if boxes.numel() else None, int(boxes.shape[0]), first, n, ptrs, labels, npos, status, work,
+         int(work.numel()), _stream(stream))
+    views, at = [], 0
+    for s, size in zip(shapes, sizes):
+        views.append(labels[at:at + size].view(s))
+        at += size
+    return views, npos, status
 
 
 def draw_detections_u8(packed, table, dets, counts, colormap, atlas, stream=None, max_pixels: Optional[int] = None):

@@ -46,6 +46,12 @@ pinned int32 and is read once the batch's `ready` event has completed, at the la
 the dataset row and the box; rows that are not finite are refused before upload.  assign='multi', assign_iou (Helper.box_to_label): a box
 is also written at every other (layer, anchor) that fits it better than assign_iou, under either value of `labels`.  With labels='host',
 assign='best' (the defaults) every path above runs untouched.
+
+assign='simota' (needs labels='gpu') launches no label kernel at all: the grids are built inside the training step from its
+own predictions (`engine.assign_simota`), and the pipeline only uploads the batch's boxes and offsets, into a buffer of the fixed capacity
+batch x ota_max_boxes whose rows past the last offset are zero, and yields (x, engine.BoxBatch).  Boxes that are not finite, and an image
+with more than ota_max_boxes boxes, are refused on the host naming the dataset row; `box_message(batch, g, what)` names the row and the box
+behind a status word the step reports.
 """
 from __future__ import annotations
 
@@ -158,17 +164,26 @@ class InputPipeline:
     def __init__(self, h: Helper, items: Sequence, global_batch: int, rank: int = 0, world: int = 1, seed: int = 0, epoch: int = 0,
                  shuffle: bool = True, workers: int = 8, prefetch: int = 2, device: Optional[int] = None, augment: bool = False,
                  mosaic: Optional[mosaic_mod.MosaicConfig] = None, hsv: Optional[colour_mod.HsvConfig] = None, cache=None,
-                 decode: str = 'pil', labels: str = 'host', assign: str = 'best', assign_iou: float = 0.213):
+                 decode: str = 'pil', labels: str = 'host', assign: str = 'best', assign_iou: float = 0.213, ota_max_boxes: int = 64):
         import torch
         engine.require_gpu()
         if decode not in ('pil', 'gpu'):
             raise engine.YkError(f'InputPipeline: decode {decode!r}: expected pil or gpu')
         if labels not in ('host', 'gpu'):
             raise engine.YkError(f'InputPipeline: labels {labels!r}: expected host or gpu')
-        try:
-            Helper.check_assign(assign, assign_iou)
-        except ValueError as e:
-            raise engine.YkError(f'InputPipeline: {e}') from e
+        self.simota = assign == 'simota'
+        if self.simota:
+            if labels != 'gpu':
+                raise engine.YkError("InputPipeline: assign 'simota' needs labels='gpu': the boxes travel to the device, the step builds the grids")
+            if not 1 <= int(ota_max_boxes) <= engine.OTA_MAX_BOXES:
+                raise engine.YkError(f'InputPipeline: ota_max_boxes {ota_max_boxes}: must be in 1 .. {engine.OTA_MAX_BOXES}')
+            self.ota_max_boxes = int(ota_max_boxes)
+            self._ota_batches: list = []                                        # per batch of this pass: (rows, first, boxes), for box_message
+        else:
+            try:
+                Helper.check_assign(assign, assign_iou)
+            except ValueError as e:
+                raise engine.YkError(f'InputPipeline: {e}') from e
         self.labels, self.assign, self.assign_iou = labels, assign, float(assign_iou)
         self.h, self.items = h, items
         self.hsv_table = colour_mod.param_table(seed, epoch, len(items), hsv) if hsv is not None else None       # [n_rows, 3], rank-independent
@@ -189,7 +204,7 @@ class InputPipeline:
         # to its own pinned int32 and is read once the batch's `ready` event has completed, at the latest when the epoch ends
         self._in_flight: "collections.deque" = collections.deque()
         self._batches = 0
-        if labels == 'gpu':
+        if labels == 'gpu' and not self.simota:
             self._label_cfg = engine.make_label_cfg(h, assign, assign_iou)
             self._status_home = torch.full((max(1, len(self.rows)),), engine.LABEL_STATUS_CLEAN, dtype=torch.int32).pin_memory()
         # cache=PictureCache (cache.py) and / or decode='gpu': every batch is composed from the cache's arena by one launch
@@ -245,7 +260,9 @@ class InputPipeline:
         self._tick = 0
         self._batches = 0                                                       # (a second pass over the same pipeline starts its status words afresh)
         self._in_flight.clear()
-        if self.labels == 'gpu':
+        if self.simota:
+            self._ota_batches.clear()
+        elif self.labels == 'gpu':
             self.stream.synchronize()                                           # no status word of an abandoned pass is still on its way home
             self._status_home.fill_(engine.LABEL_STATUS_CLEAN)
         try:
@@ -348,6 +365,10 @@ class InputPipeline:
         allb = np.concatenate(per) if first[-1] else np.zeros((0, 5), np.float64)
         if not np.isfinite(allb).all():
             raise engine.YkError(self._box_message(int(np.nonzero(~np.isfinite(allb).all(1))[0][0]), rows, first, allb, 'is not finite'))
+        if self.simota and len(per) and max(len(b) for b in per) > self.ota_max_boxes:
+            s = int(np.argmax([len(b) > self.ota_max_boxes for b in per]))
+            raise engine.YkError(f"InputPipeline(assign='simota'): dataset row {int(rows[s])} (sample {s} of its batch) has {len(per[s])} boxes, "
+                                 f'ota_max_boxes is {self.ota_max_boxes}')
         return allb, first, np.array(rows, np.int64, copy=True)
 
     def _send_labels(self, staged):
@@ -365,6 +386,16 @@ class InputPipeline:
             ready.record(self.stream)
             return labels, ready
         allb, first, rows = staged
+        if self.simota:                                                         # no launch: the step assigns from its own predictions
+            padded = np.zeros((self.per * self.ota_max_boxes, 5), np.float64)
+            padded[:len(allb)] = allb
+            full = np.full(self.per + 1, first[-1], np.int32)                   # (a short last batch: its missing images own no box)
+            full[:len(first)] = first
+            batch = engine.BoxBatch(self._upload('obox', padded, torch.float64), self._upload('ofirst', full, torch.int32))
+            self._ota_batches.append((rows, first, allb))
+            ready = torch.cuda.Event()
+            ready.record(self.stream)
+            return batch, ready
         d_boxes = self._upload('lbox', allb, torch.float64)
         d_first = self._upload('lfirst', first, torch.int32)
         labels, status = engine.boxes_to_labels(d_boxes, d_first, self._label_cfg, stream=self.stream)
@@ -380,6 +411,15 @@ class InputPipeline:
         s = int(np.searchsorted(first, g, side='right')) - 1
         return (f'InputPipeline(labels=\'gpu\'): dataset row {int(rows[s])} (sample {s} of its batch), box {g - int(first[s])} of the sample, '
                 f'(cls, x, y, w, h) = {tuple(float(v) for v in allb[g])} {what}')
+
+    def box_message(self, batch: int, g: int, what: str) -> str:
+        """assign='simota': the dataset row and the box behind row g of batch `batch` (of this pass) of the uploaded boxes."""
+        rows, first, allb = self._ota_batches[batch]
+        return self._box_message(g, rows, first, allb, what)
+
+    def box_count(self, batch: int) -> int:
+        """assign='simota': the boxes of batch `batch` of this pass."""
+        return len(self._ota_batches[batch][2])
 
     def _check_labels(self, wait: bool) -> None:
         """Read the status words of the batches whose `ready` event has completed (wait: of all of them, waiting for each): a box that

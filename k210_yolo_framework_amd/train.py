@@ -38,6 +38,11 @@ LrSchedule(...))` replace the update's one yk_adam_f32 launch by yk_sumsq_f32 (c
 outside the captured graph like Adam; the average E of P and the average of the BatchNorm moving statistics are what `export_weights(ema=True)`
 returns.  With the defaults nothing is allocated and apply_update issues yk_adam_f32 as before.
 
+SimOTA dynamic label assignment (simota.py): `Trainer(assign='simota', ota_topk=, ota_radius=, ota_iou_weight=, ota_max_boxes=)`
+takes an engine.BoxBatch where the other modes take label grids: between the forward pass and the loss, inside the captured step, one
+engine.assign_simota call (csrc/yk_ota.hip) writes the grids from the step's own raw outputs, and the loss reads them unchanged.  The status
+word and the positives per image are read after the step with its losses.  With assign='best' nothing is allocated and nothing is launched.
+
 fp32 storage and fp32 MFMA throughout (TF1.14's default for this model)."""
 from __future__ import annotations
 
@@ -79,12 +84,18 @@ class Trainer:
                  wh_weight: float = 1.0, lr: float = 5e-4, decay: float = 0.0, device: int = 0, process_group=None,
                  world_size: int = 1, use_graph: bool = True, prune=None, qat=None, box_loss: str = 'mse', box_weight: float = 1.0,
                  distill=None, ema=None, clip_norm: float = 0.0, lr_schedule=None, focal: str = 'off', focal_gamma: float = 2.0,
-                 focal_alpha: float = 0.0, label_smooth: float = 0.0, obj_target: str = 'label'):
+                 focal_alpha: float = 0.0, label_smooth: float = 0.0, obj_target: str = 'label', assign: str = 'best', ota_topk: int = 10,
+                 ota_radius: float = 2.5, ota_iou_weight: float = 3.0, ota_max_boxes: int = 64):
         import torch
         from . import lossopt
         loss_opts = lossopt.validate(focal, focal_gamma, focal_alpha, label_smooth, obj_target)
         if box_loss not in engine.BOX_LOSSES:
             raise ValueError(f'box_loss {box_loss!r}: choose one of ' + ', '.join(repr(k) for k in engine.BOX_LOSSES))
+        if assign not in ('best', 'simota'):
+            raise ValueError(f"assign {assign!r}: 'best' (the label grids come with the batch) or 'simota'")
+        if assign == 'simota' and box_loss == 'mse':
+            raise engine.YkError("assign='simota' with box_loss='mse' is not supported: the in-cell offset target of the mse box loss is undefined "
+                                 "for a candidate outside the box's own centre cell; choose box_loss='giou', 'diou' or 'ciou'")
         if ema is not None and qat is not None:
             raise engine.YkError('ema= together with qat= is not supported: the learned activation ranges belong to the live weights, not to '
                                  'their average')
@@ -149,6 +160,18 @@ class Trainer:
             engine.call('yk_sumsq_workspace_bytes', self.n_params, C.byref(nbytes))
             self._sq_work = torch.zeros(nbytes.value // 8, dtype=torch.float64, device=self.dev)
             self._sumsq = torch.zeros(1, dtype=torch.float64, device=self.dev)
+        # SimOTA (simota.py): the grids are written inside the step.  'best': nothing is allocated and nothing is launched.
+        self.assign = assign
+        if assign == 'simota':
+            self.ota = dict(topk=int(ota_topk), radius=float(ota_radius), iou_weight=float(ota_iou_weight), max_boxes=int(ota_max_boxes))
+            self._ota_cfg = engine.make_ota_cfg(dict(out_hw=[spec.tensors[o][:2] for o in spec.outputs], anchors=np.asarray(anchors, np.float64),
+                                                     class_num=spec.class_num), **self.ota)
+            nbytes = C.c_size_t()                                    # the library's range checks, before the first step
+            engine.call('yk_simota_workspace_bytes', C.byref(self._ota_cfg), self.B, self.ota['max_boxes'], C.byref(nbytes))
+            floats = sum(int(np.prod(spec.tensors[o][:2])) * spec.anchor_num * (5 + spec.class_num) for o in spec.outputs)
+            # static: the eager step and the captured one write the same buffers, and step() reads them after either
+            self._ota_out = (torch.zeros(self.B * floats, dtype=torch.float32, device=self.dev),
+                             torch.zeros(self.B, dtype=torch.int32, device=self.dev), torch.full((1,), engine.LABEL_STATUS_CLEAN, dtype=torch.int32, device=self.dev))
         self.counts = [torch.zeros(3, dtype=torch.float32, device=self.dev) for _ in spec.outputs]
         self.saved: Dict[int, dict] = {}
         self.T: Dict[int, "torch.Tensor"] = {}
@@ -526,6 +549,8 @@ class Trainer:
         """forward + loss + backward (no all-reduce, no update).  -> dict of device scalars."""
         global_batch = self.B * self.world
         preds = self.forward(x_nhwc)
+        if self.assign == 'simota':                                  # y_true is an engine.BoxBatch: the grids from THESE outputs
+            y_true, _, _ = engine.assign_simota([yp.contiguous() for yp in preds], y_true.boxes, y_true.first, self._ota_cfg, out=self._ota_out)
         parts, grads = [], []
         for li, (yp, yt) in enumerate(zip(preds, y_true)):
             loss6, g, _ = engine.yolo_loss(yt, yp.contiguous(), self.anchors[li], batch_size=global_batch, counts=self.counts[li],
@@ -555,7 +580,8 @@ class Trainer:
     def _graph_key(self, x_nhwc, y_true):
         return (tuple(sorted(self.hyper.items())), tuple(x_nhwc.shape), tuple(tuple(y.shape) for y in y_true), self.world,
                 None if self.qat is None else self.qat.momentum,           # (a launch scalar of yk_qat_update_f32 inside the capture)
-                None if self.distill is None else self.distill_weight)      # (a launch scalar of yk_distill_loss_f32 inside the capture)
+                None if self.distill is None else self.distill_weight,      # (a launch scalar of yk_distill_loss_f32 inside the capture)
+                None if self.assign != 'simota' else tuple(sorted(self.ota.items())))
 
     def _loss_and_grads_replayed(self, x_nhwc, y_true):
         """loss_and_grads through a captured HIP graph (after one eager step that also warms allocator and scratch buffers).
@@ -580,7 +606,7 @@ class Trainer:
                 cur.wait_stream(side)
                 return r
             self._gx = x_nhwc.clone()
-            self._gy = [y.clone() for y in y_true]
+            self._gy = type(y_true)(*[y.clone() for y in y_true]) if self.assign == 'simota' else [y.clone() for y in y_true]
             side.wait_stream(cur)
             with torch.cuda.stream(side):
                 g = torch.cuda.CUDAGraph()
@@ -879,10 +905,15 @@ class Trainer:
         tail = [r['reg'].view(1)]
         if self.clip_norm:                                            # the float64 sum of squares rides along as two float32 words: one transfer
             tail.append(self._sumsq.view(torch.float32))
+        if self.assign == 'simota':                                   # the positives of the batch and the status word ride along as raw int32 words
+            tail.append(torch.cat([self._ota_out[1].sum(dtype=torch.int32).view(1), self._ota_out[2]]).view(torch.float32))
         vals = torch.cat([data] + tail).cpu().numpy()
         extra = {}
         if self.lr_schedule is not None:
             extra['lr'] = self.last_lr
+        if self.assign == 'simota':                                   # (the last tail entry)
+            extra['pos'], extra['ota_status'] = (int(v) for v in vals[-2:].copy().view(np.int32))
+            vals = vals[:-2]
         if self.clip_norm:
             extra['grad_norm'] = float(np.sqrt(vals[-2:].copy().view(np.float64)[0]))      # the norm BEFORE clipping
             vals = vals[:-2]

@@ -68,7 +68,9 @@ the reference's Adam call and no line changes.
 `--labels gpu`, `--assign multi`, `--assign_iou` (`make train LABELS=gpu ASSIGN=multi ASSIGNIOU=0.213`; not in the reference): the
 label grids are built on the GPU from the batch's boxes by one HIP launch (`InputPipeline(labels='gpu')`), the bits of the host's; with
 `--assign multi` a box is written not only at its best-fitting (layer, anchor) but at every other whose fit exceeds `--assign_iou`
-(`Helper.box_to_label`), under either `--labels` value, in training and validation alike.  One line at the start names a non-default
+(`Helper.box_to_label`), under either `--labels` value, in training and validation alike.  `--assign simota` (`ASSIGN=simota OTATOPK= OTARADIUS=
+OTAIOUW= OTAMAXBOXES=`; needs `--labels gpu` and an IoU `--box_loss`): the step assigns its labels from its own predictions
+(`engine.assign_simota`), validation does the same from its forward's outputs, and the epoch line gains `pos/box`.  One line at the start names a non-default
 value; with the defaults (host, best) nothing changes."""
 from __future__ import annotations
 
@@ -168,7 +170,7 @@ def main(args, train_set, class_num, pre_ckpt, model_def, depth_multiplier, is_a
          hsv_exposure=1.5, hsv_prob=1.0, teacher_ckpt='', teacher_def=None, teacher_depth=None, distill_weight=1.0, cache='off',
          cache_gb=8.0, cache_stage_mb=256, decode='pil', is_ema='False', ema_decay=0.9999, ema_tau=2000.0, clip_norm=0.0, lr_schedule='none',
          warmup_steps=0, lr_final=0.01, focal='off', focal_gamma=2.0, focal_alpha=0.0, label_smooth=0.0, obj_target='label',
-         labels='host', assign='best', assign_iou=0.213):
+         labels='host', assign='best', assign_iou=0.213, ota_topk=10, ota_radius=2.5, ota_iou_weight=3.0, ota_max_boxes=64):
     import torch
     from . import lossopt
     from .train import Trainer
@@ -219,11 +221,19 @@ def main(args, train_set, class_num, pre_ckpt, model_def, depth_multiplier, is_a
     distill = teacher_ckpt not in (None, 'None', '', '""')
     if labels not in ('host', 'gpu'):
         raise engine.YkError(f'--labels {labels}: host or gpu')
-    try:
-        Helper.check_assign(assign, float(assign_iou))
-    except ValueError as e:
-        raise engine.YkError(f'--assign {assign} --assign_iou {assign_iou}: {e}') from e
+    simota = assign == 'simota'
+    if simota and labels != 'gpu':
+        raise engine.YkError('--assign simota needs --labels gpu (make train: LABELS=gpu): the boxes travel to the device and the step builds the grids')
+    if simota and box_loss == 'mse':
+        raise engine.YkError('--assign simota needs an IoU box loss: add --box_loss ciou (make train: BOXLOSS=ciou); the mse offsets are undefined '
+                             "outside a box's own centre cell")
+    if not simota:
+        try:
+            Helper.check_assign(assign, float(assign_iou))
+        except ValueError as e:
+            raise engine.YkError(f'--assign {assign} --assign_iou {assign_iou}: {e}') from e
     label_opts = dict(labels=labels, assign=assign, assign_iou=float(assign_iou))
+    ota_opts = dict(ota_topk=int(ota_topk), ota_radius=float(ota_radius), ota_iou_weight=float(ota_iou_weight), ota_max_boxes=int(ota_max_boxes))
     if distill and not (np.isfinite(float(distill_weight)) and float(distill_weight) >= 0.0):
         raise engine.YkError(f'--distill_weight {distill_weight}: a finite weight, not negative')
     rank, world = int(os.environ.get('RANK', '0')), int(os.environ.get('WORLD_SIZE', '1'))
@@ -329,11 +339,12 @@ def main(args, train_set, class_num, pre_ckpt, model_def, depth_multiplier, is_a
     if rank == 0 and not lossopt.is_off(**loss_opts):
         print(INFO, f'loss options: {lossopt.describe(**loss_opts)}')
     if rank == 0 and (labels != 'host' or assign != 'best'):
-        print(INFO, f'labels are built on the {labels}, assign is {assign}' + (f', assign_iou {float(assign_iou)}' if assign == 'multi' else ''))
+        print(INFO, f'labels are built on the {labels}, assign is {assign}' + (f', assign_iou {float(assign_iou)}' if assign == 'multi' else '') +
+              (''.join(f', {k} {v}' for k, v in ota_opts.items()) if simota else ''))
     tr = Trainer(spec, weights, h.anchors, per_rank, obj_thresh=obj_thresh, iou_thresh=iou_thresh, obj_weight=obj_weight,
                  noobj_weight=noobj_weight, wh_weight=wh_weight, lr=init_learning_rate, decay=learning_rate_decay_factor, device=local,
                  world_size=world, prune=schedule, qat=qat_cfg, box_loss=box_loss, box_weight=box_weight, distill=distill_cfg,
-                 ema=ema_cfg, clip_norm=float(clip_norm), lr_schedule=lr_cfg, **loss_opts)
+                 ema=ema_cfg, clip_norm=float(clip_norm), lr_schedule=lr_cfg, **loss_opts, **(dict(assign='simota', **ota_opts) if simota else {}))
     from .mosaic import MosaicConfig
     from .pipeline import InputPipeline
     if rank == 0:
@@ -352,6 +363,7 @@ def main(args, train_set, class_num, pre_ckpt, model_def, depth_multiplier, is_a
     iou_box = box_loss != 'mse'
     for epoch in range(max_nrof_epochs):
         t0, seen, run, run_box, run_kd = time.time(), 0, 0.0, 0.0, 0.0
+        ota_pos = ota_boxes = 0
         if rank == 0 and mosaic and int(mosaic_off_epochs) > 0 and epoch == max(max_nrof_epochs - int(mosaic_off_epochs), 0):
             print(f'epoch {epoch + 1}: mosaic off from here on', flush=True)
         # tools/utils.py:417-450: each rank decodes only its rows of the global batch, on a thread pool, two batches ahead;
@@ -361,14 +373,20 @@ def main(args, train_set, class_num, pre_ckpt, model_def, depth_multiplier, is_a
                              mosaic=MosaicConfig(float(mosaic_prob)) if mosaic and epoch < max_nrof_epochs - int(mosaic_off_epochs) else None,
                              hsv=hsv_cfg,                                       # ... the colour jitter stays on in them
                              **({} if pic_cache is None else dict(cache=pic_cache, decode=decode)),
-                             **({} if labels == 'host' and assign == 'best' else label_opts))
+                             **({} if labels == 'host' and assign == 'best' else label_opts),
+                             **(dict(ota_max_boxes=int(ota_max_boxes)) if simota else {}))
         try:                                                                    # an exception in the step must not leave the producer running
-            for x, ys in pipe:
+            for bi, (x, ys) in enumerate(pipe):
                 if qat and epoch == 0 and observed < int(qat_observe):           # the first batches of epoch 0 only set the activation ranges
                     tr.qat_observe(x)
                     observed += 1
                     continue
                 out = tr.step(x, ys)
+                if simota:                                                      # the step's status word came home with its losses
+                    if out['ota_status'] != engine.LABEL_STATUS_CLEAN:
+                        raise engine.YkError(pipe.box_message(bi, out['ota_status'], 'has a centre cell outside a label grid (or a '
+                                                              'class outside [0, class_num)): nothing of it was assigned'))
+                    ota_pos, ota_boxes = ota_pos + out['pos'], ota_boxes + pipe.box_count(bi)
                 seen, run, steps = seen + 1, run + out['loss'], steps + 1
                 run_box += out.get('box', 0.0)
                 run_kd += out.get('distill', 0.0)
@@ -390,13 +408,13 @@ def main(args, train_set, class_num, pre_ckpt, model_def, depth_multiplier, is_a
         val = vmap = None
         if rank == 0 and len(h.test_list) >= per_rank:
             if val_map == 'True':                                               # opt-in: the pass also scores its detections
-                val, vmap = validate(tr, h, spec, per_rank, rank, map_obj=val_map_obj, ema=ema, **label_opts)
+                val, vmap = validate(tr, h, spec, per_rank, rank, map_obj=val_map_obj, ema=ema, **label_opts, **(dict(ota=tr._ota_cfg) if simota else {}))
             else:
-                val = validate(tr, h, spec, per_rank, rank, ema=ema, **label_opts)
+                val = validate(tr, h, spec, per_rank, rank, ema=ema, **label_opts, **(dict(ota=tr._ota_cfg) if simota else {}))
         if rank == 0:
             print(f'epoch {epoch + 1}: {seen} steps, mean loss {run / max(seen, 1):.4f}, ' +
                   (f'mean {box_loss} {run_box / max(seen, 1):.4f}, ' if iou_box else '') +
-                  (f'mean distill {run_kd / max(seen, 1):.4f}, ' if distill else '') +
+                  (f'mean distill {run_kd / max(seen, 1):.4f}, ' if distill else '') + (f'pos/box {ota_pos / max(ota_boxes, 1):.2f}, ' if simota else '') +
                   (f'val_loss {val:.4f}{" (ema)" if ema else ""}, ' if val is not None else '') + f'{time.time() - t0:.1f}s, input pipeline {pipe_rate:.0f} images/s/rank' +
                   (f', val_mAP {vmap:.4f}' if vmap is not None else '') + (cache_line(pic_cache) if cached else ''), flush=True)
         for c in tr.counts:
@@ -468,14 +486,15 @@ def sparsity_line(tr, spec, epoch: int) -> str:
 
 
 def validate(tr, h: Helper, spec, batch: int, rank: int, map_obj=None, ema: bool = False, labels: str = 'host', assign: str = 'best',
-             assign_iou: float = 0.213):
+             assign_iou: float = 0.213, ota=None):
     """validation_data pass (keras_train.py:96-98): inference-mode forward on the engine (the f16x2 mode, the boundary default) + the same loss.
     map_obj (`--val_map True`): the plan's outputs are also decoded on the GPU at this objectness threshold (NMS and match IoU = the run's
     iou_thresh) and scored in device memory by map_gpu.MapEvaluator against the validation boxes in network-input pixels - the letterboxed
     frame is the image; -> (val_loss, val_mAP) instead of val_loss.
     ema (`--ema True`): the plan is built from the averaged weights, tr.export_weights(ema=True), for the loss and the mAP alike.
     labels, assign, assign_iou: the run's label options (InputPipeline's): the validation labels follow the same assignment and, with
-    labels='gpu', are built by the same kernel from the batch's boxes; a box it could not write raises, as in training."""
+    labels='gpu', are built by the same kernel from the batch's boxes; a box it could not write raises, as in training.
+    ota (assign='simota': the Trainer's yk_ota_cfg_t): the grids are assigned by engine.assign_simota from the validation forward's outputs."""
     import torch
     tot, n, statuses = 0.0, 0, []
     e = 5 + spec.class_num
@@ -487,17 +506,22 @@ def validate(tr, h: Helper, spec, batch: int, rank: int, map_obj=None, ema: bool
         cfg = engine.make_decode_cfg(h.anchors, spec.class_num, spec.in_hw, spec.out_hw())
     with engine.Plan(spec, tr.export_weights(ema=True) if ema else tr.export_weights(), max_batch=batch, device=tr.dev.index or 0) as plan:   # freed on exit, every epoch
         for x, ys, *boxes in batches(h, h.test_list, batch, np.random.default_rng(0), shuffle=False, with_boxes=ev is not None or labels == 'gpu',
-                                     assign=assign, assign_iou=assign_iou, make_labels=labels != 'gpu'):
+                                     **({} if ota is not None else dict(assign=assign, assign_iou=assign_iou)), make_labels=labels != 'gpu'):
             plan.run_f32(torch.from_numpy(x).cuda())
-            if labels == 'gpu':
+            yps = [o[:batch].reshape(batch, *spec.tensors[spec.outputs[li]][:2], spec.anchor_num, e).contiguous() for li, o in enumerate(plan.outputs())]
+            if ota is not None:
+                first = np.concatenate([[0], np.cumsum([len(b) for b in boxes[0]])])
+                ys, _, status = engine.assign_simota(yps, np.concatenate([np.reshape(b, (-1, 5)) for b in boxes[0]]), first, ota,
+                                                     max_boxes=engine.OTA_MAX_BOXES)
+                statuses.append(status)
+            elif labels == 'gpu':
                 first = np.concatenate([[0], np.cumsum([len(b) for b in boxes[0]])])
                 ys, status = engine.boxes_to_labels(np.concatenate([np.reshape(b, (-1, 5)) for b in boxes[0]]), first, h, assign, assign_iou)
                 statuses.append(status)                                         # read once, after the pass
             if ev is not None:
                 dets, counts = engine.decode_py(cfg, plan.outputs(), batch, None, float(map_obj), tr.hyper['iou_thresh'])
                 ev.add(dets, counts, [ground_truth_rows(b, spec.in_hw) for b in boxes[0]])
-            for li, (o, yt) in enumerate(zip(plan.outputs(), ys)):
-                yp = o[:batch].reshape(batch, *spec.tensors[spec.outputs[li]][:2], spec.anchor_num, e).contiguous()
+            for li, (yp, yt) in enumerate(zip(yps, ys)):
                 loss6, _, _ = engine.yolo_loss(yt if torch.is_tensor(yt) else torch.from_numpy(yt).cuda(), yp, tr.anchors[li], batch_size=batch, want_grad=False, **tr.hyper)
                 tot += float(loss6[0])
             n += 1
@@ -584,8 +608,13 @@ def parser() -> argparse.ArgumentParser:
                    help="iou: an object cell's objectness target is the IoU of its predicted box with the label box")
     p.add_argument('--labels', type=str, choices=['host', 'gpu'], default='host',
                    help='gpu: the label grids are built on the GPU from the boxes, only the boxes cross PCIe (DESIGN.md 3.26)')
-    p.add_argument('--assign', type=str, choices=['best', 'multi'], default='best',
-                   help='multi: a box also trains every other (layer, anchor) that fits it better than --assign_iou (DESIGN.md 3.26)')
+    p.add_argument('--ota_topk', type=int, default=10, help='with --assign simota: the IoUs summed into the dynamic k, 1 to 32')
+    p.add_argument('--ota_radius', type=float, default=2.5, help='with --assign simota: the centre region, in cells of each layer, 1 to 16')
+    p.add_argument('--ota_iou_weight', type=float, default=3.0, help='with --assign simota: the weight of -log(IoU) in the cost')
+    p.add_argument('--ota_max_boxes', type=int, default=64, help='with --assign simota: the most boxes one image may have, 1 to 256')
+    p.add_argument('--assign', type=str, choices=['best', 'multi', 'simota'], default='best',
+                   help='simota: which predictions train on which box is decided per step from the predictions (needs --labels gpu and an IoU '
+                        '--box_loss; DESIGN.md 3.29); multi: a box also trains every other (layer, anchor) that fits it better than --assign_iou (DESIGN.md 3.26)')
     p.add_argument('--assign_iou', type=float, default=0.213, help='with --assign multi: the fit above which an anchor is also trained on a box, inside (0, 1)')
     return p
 
@@ -599,7 +628,7 @@ def cli(argv=None):
                 a.qat, a.qat_momentum, a.qat_observe, a.val_map, a.val_map_obj, a.box_loss, a.box_weight, a.mosaic, a.mosaic_prob,
                 a.mosaic_off_epochs, a.hsv, a.hsv_hue, a.hsv_sat, a.hsv_exposure, a.hsv_prob, a.teacher_ckpt, a.teacher_def, a.teacher_depth,
                 a.distill_weight, a.cache, a.cache_gb, a.cache_stage_mb, a.decode, a.ema, a.ema_decay, a.ema_tau, a.clip_norm, a.lr_schedule,
-                a.warmup_steps, a.lr_final, a.focal, a.focal_gamma, a.focal_alpha, a.label_smooth, a.obj_target, a.labels, a.assign, a.assign_iou)
+                a.warmup_steps, a.lr_final, a.focal, a.focal_gamma, a.focal_alpha, a.label_smooth, a.obj_target, a.labels, a.assign, a.assign_iou, a.ota_topk, a.ota_radius, a.ota_iou_weight, a.ota_max_boxes)
 
 
 if __name__ == '__main__':
