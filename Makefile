@@ -58,9 +58,10 @@
 #                    labels drawn on the GPU; ENCODE=gpu also JPEG-encodes them there at QUALITY, ENCODE=pil leaves that to PIL on the host;
 #                    DECODE=gpu decodes baseline JPEG files there too, by the project's own integer rule, every other file by PIL)
 #                    [TTA=flip|v5|1,0.83f,0.67 TTATHRESH=0.55]: test-time augmentation, every picture also mirrored / shrunk, the views' rows fused on the GPU
-#                    [TRACK=True TRACKTHRESH=0.5 TRACKLOW=0.1 TRACKMATCH=0.8 TRACKBUFFER=30 TRACKMAX=256]: the pictures of a folder are the frames of
+#                    [TRACK=True TRACKTHRESH=0.5 TRACKLOW=0.1 TRACKMATCH=0.8 TRACKBUFFER=30 TRACKMAX=256 TRACKASSIGN=greedy|lap TRACKFUSE=False]: the pictures of a folder are the frames of
 #                    a sequence; rows get ids that last across frames on the GPU (ByteTrack restated, k210_yolo_framework_amd/track.py), the labels
-#                    show them, and OUTDIR/tracks/<sequence>.txt holds them in the MOTChallenge text format
+#                    show them, and OUTDIR/tracks/<sequence>.txt holds them in the MOTChallenge text format; TRACKASSIGN=lap associates optimally
+#                    (the Hungarian assignment ByteTrack makes) instead of greedily, TRACKFUSE=True is its fuse_score
 #   make trackeval   GT=folder RES=folder | SYNTHETIC=N [SEQFRAMES=60 SEQOBJECTS=8 SEED=0]: HOTA, MOTA and IDF1 (and DetA, AssA, LocA, MOTP, IDSW,
 #                    Frag, MT/PT/ML) of tracks files against ground truth, one line per sequence and a COMBINED line, trackeval.json beside RES.
 #                    GT and RES hold <sequence>.txt in the MOTChallenge text format (what `make detect TRACK=True` writes under OUTDIR/tracks);
@@ -176,6 +177,8 @@ TRACKLOW      ?= 0.1
 TRACKMATCH    ?= 0.8
 TRACKBUFFER   ?= 30
 TRACKMAX      ?= 256
+TRACKASSIGN   ?= greedy
+TRACKFUSE     ?= False
 # trackeval only
 GT            ?=
 RES           ?=
@@ -215,7 +218,7 @@ NET_ARGS   = --train_set $(DATASET) --class_num $(CLSNUM) --model_def $(MODEL) -
 NMS_ARGS   = $(if $(filter-out hard,$(NMS)),--nms $(NMS) --nms_sigma $(NMSSIGMA))
 TILE_ARGS  = $(if $(TILES),--tiles $(TILES) --tile_overlap $(TILEOVERLAP) --tile_full $(TILEFULL) --tile_match $(TILEMATCH) --tile_thresh $(TILETHRESH))
 TTA_ARGS   = $(if $(TTA),--tta $(TTA) --tta_thresh $(TTATHRESH))
-TRACK_ARGS = $(if $(filter True,$(TRACK)),--track True --track_thresh $(TRACKTHRESH) --track_low $(TRACKLOW) --track_match $(TRACKMATCH) --track_buffer $(TRACKBUFFER) --track_max $(TRACKMAX))
+TRACK_ARGS = $(if $(filter True,$(TRACK)),--track True --track_thresh $(TRACKTHRESH) --track_low $(TRACKLOW) --track_match $(TRACKMATCH) --track_buffer $(TRACKBUFFER) --track_max $(TRACKMAX)$(if $(filter-out greedy,$(TRACKASSIGN)), --track_assign $(TRACKASSIGN))$(if $(filter True,$(TRACKFUSE)), --track_fuse True))
 TRAIN_ARGS = --pre_ckpt $(CKPT) --augmenter $(IAA) --batch_size $(BATCH) --rand_seed 3 --max_nrof_epochs $(MAXEP) \
              --init_learning_rate $(ILR) --learning_rate_decay_factor $(LRDECAYFACTOR) --obj_weight $(OBJWEIGHT) \
              --noobj_weight $(NOOBJWEIGHT) --wh_weight $(WHWEIGHT) --vaildation_split $(SPLITFACTOR) --log_dir log \

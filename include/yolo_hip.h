@@ -302,7 +302,7 @@ int yk_fuse_views(const float *d_dets, const int32_t *d_counts, const float *d_x
 int yk_fuse_views_lds_candidates(int max_out);
 
 /* ---- tracking: identities across the frames of a sequence for the decode's rows (k210_yolo_framework_amd/track.py states the rule,
- * ByteTrack restated with a class-aware greedy association).  The state of n_seq sequences of at most max_tracks tracks each
+ * ByteTrack restated with a class-aware association, greedy unless yk_track_update_ex is asked otherwise).  The state of n_seq sequences of at most max_tracks tracks each
  * (1 .. YK_TRACK_MAX_TRACKS) is device memory of yk_track_state_bytes the caller allocates and yk_track_reset empties (a kernel, not a fill:
  * it can be recorded in a graph); per sequence a header (live tracks, next id, frames seen, overflow) and 25 words per track.
  * yk_track_update advances every sequence by its frames of this call: d_dets [n_frames][cap][6] and d_counts [n_frames] as yk_decode_py*
@@ -330,8 +330,20 @@ int yk_fuse_views_lds_candidates(int max_out);
  * in a graph after an eager call of the same max_tracks and cap.  A NULL pointer other than d_draw, n_seq <= 0, max_tracks outside
  * 1 .. YK_TRACK_MAX_TRACKS, cap <= 0, n_frames <= 0, class_num <= 0, a NaN threshold, track_buffer < 0, n_frames * cap >= 2^31 or cap above
  * the capacity: YK_ERR_ARG with the argument named in yk_last_error, nothing launched.
- * yk_track_read waits for the device and copies each sequence's live-track count, next id and overflow count to the host. */
+ * yk_track_read waits for the device and copies each sequence's live-track count, next id and overflow count to the host.
+ * yk_track_update_ex is yk_track_update with two options of the association (track.py states both); with YK_TRACK_ASSIGN_GREEDY and
+ * fuse_score 0 it is yk_track_update itself, the same kernel and the same bytes.  fuse_score 1: the similarity of a pair in the FIRST
+ * stage is float32(IoU * the row's score), one rounding, and the stage's gate reads it; the other stages never.  YK_TRACK_ASSIGN_LAP: per
+ * stage and per class (ascending) the optimal assignment instead of the greedy one - motmetrics.lap's shortest augmenting paths, operation
+ * for operation in float64, on the eligible tracks (in track order) x the eligible free rows (in row order) of the class, the transpose
+ * when there are more tracks than rows; an allowed pair (gate met) costs 1 - (double)similarity, a forbidden one 2^20, and of the solver's
+ * pairs the allowed ones are kept: first as many matches as can be had, then the smallest total cost.  The costs are recomputed where they
+ * are read, no matrix is stored; the solver's vectors and the class's index lists take 28 more bytes of LDS per track and 32 per row, so
+ * the capacity of a call is smaller: yk_track_max_cap_ex(max_tracks, assign), and more is refused by name, never truncated.  An assign
+ * other than the two or a fuse_score other than 0 / 1: YK_ERR_ARG, named. */
 #define YK_TRACK_MAX_TRACKS 1024
+#define YK_TRACK_ASSIGN_GREEDY 0
+#define YK_TRACK_ASSIGN_LAP 1
 typedef struct {
     float track_thresh, low_thresh, match_thresh;
     int32_t track_buffer;
@@ -344,6 +356,11 @@ int yk_track_update(void *d_state, int n_seq, int max_tracks, const float *d_det
                     int n_frames, int class_num, const yk_track_cfg_t *cfg,
                     float *d_out, int32_t *d_out_ids, int32_t *d_out_counts,
                     float *d_draw /* may be NULL: d_out with the class column replaced by id mod 100 */, void *stream);
+int yk_track_max_cap_ex(int max_tracks, int assign /* YK_TRACK_ASSIGN_* */);
+int yk_track_update_ex(void *d_state, int n_seq, int max_tracks, const float *d_dets, const int32_t *d_counts, int cap,
+                       const int32_t *d_seq_first, int n_frames, int class_num, const yk_track_cfg_t *cfg,
+                       int assign /* YK_TRACK_ASSIGN_* */, int fuse_score /* 0 or 1 */,
+                       float *d_out, int32_t *d_out_ids, int32_t *d_out_counts, float *d_draw /* may be NULL */, void *stream);
 int yk_track_read(const void *d_state, int n_seq, int max_tracks, int32_t *h_live, int32_t *h_next_id, int32_t *h_overflow);
 
 /* ---- linear assignment: what the tracking scores (HOTA, CLEAR-MOT, identity) rest on (k210_yolo_framework_amd/motmetrics.py states the

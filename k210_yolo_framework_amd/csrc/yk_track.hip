@@ -1,5 +1,5 @@
 // yk_track.hip — identities across frames for the decode's rows (k210_yolo_framework_amd/track.py states the rule, ByteTrack restated with a
-// class-aware greedy association).
+// class-aware association, greedy or optimal).
 //
 // Tracking is a chain over time: frame t cannot start before frame t - 1 has ended.  The parallelism there is lies across sequences, across
 // the tracks of a sequence and across the rows of a frame, and that is how the work is split:
@@ -10,7 +10,14 @@
 //   - per frame the rows that take part are compacted by ballot into LDS (box, score, class and kind: 24 bytes a row);
 //   - lanes own tracks (lane, lane + 64, ...): predict, update, open and emit are one track (or one row) per lane;
 //   - matching: every track keeps its best free row in LDS, a wave reduction picks the stage's best pair (largest IoU, lowest track, lowest
-//     row), and only the tracks whose cached row was just taken look again.
+//     row), and only the tracks whose cached row was just taken look again;
+//   - matching, assign = lap (a second instantiation of the kernel; the greedy one carries none of it): per stage and class the eligible
+//     tracks and rows are compacted by ballot into two index lists in LDS and motmetrics.lap's shortest augmenting paths run on the dense
+//     nr x nc problem, the smaller side as the solver's rows.  MATRIX-FREE: 1024 x cap float64 costs do not fit beside the tracks, so a cost
+//     is recomputed where it is read - tf_iou of two LDS-resident boxes, the optional score multiply, the gate, 1.0 - (double)s or 2^20 -
+//     which is LDS reads and VALU only.  Lanes own columns (lane, lane + 64, ...): a column's dual, distance, predecessor, flag and holder
+//     are written by its own lane during the search, one sweep relaxes and keeps the lane's first smallest distance, a wave reduction over
+//     (distance, column) gives np.argmin's first minimum.  The solver row's box is held in registers across the sweep.
 // No atomics anywhere, so two calls give the same bytes.  A 2 x 2 filter and an arg-max have no matrix product in them: no MFMA.
 // Compiled with -ffp-contract=off: one rounding per operation, as track.py's float32 steps.
 #include <vector>
@@ -22,6 +29,13 @@
 #define YK_TRACK_HEADER 4                 // a sequence's header: live tracks, next id, frames seen, overflow
 #define YK_TRACK_LDS_PER_TRACK 128        // the 25 words + predicted box (16) + matched row, best IoU, best row (12)
 #define YK_TRACK_LDS_PER_ROW 24
+// assign = lap, on top of the two above: a share of the solver's vectors and, per row, an entry of the class's index list (4; the tracks'
+// list lies where the greedy path keeps its best IoU, which lap never reads).  The vectors of the longer side (v, dist: 8 each; pred,
+// row4col, scanned: 4 each = YK_LAP_LDS_PER_COL) are carved for max(M, cap) entries and those of the shorter (u: 8; col4row: 4 =
+// YK_LAP_LDS_PER_ROW) for min(M, cap), which 28 bytes per track and per row cover whichever side is longer.
+#define YK_TRACK_LAP_LDS_PER_TRACK YK_LAP_LDS_PER_COL
+#define YK_TRACK_LAP_LDS_PER_ROW (4 + YK_LAP_LDS_PER_COL)
+#define YK_TRACK_LAP_FORBIDDEN 1048576.0  // 2^20: above any sum of 1024 allowed costs, and a power of two (track.py says why)
 #define YK_TRACK_LDS_LIMIT (160 * 1024)
 
 enum { T_NEW = 0, T_TRACKED = 1, T_LOST = 2, T_DEAD = 3 };
@@ -39,6 +53,11 @@ struct track_lds {
     int *Tm;                              // [M] the row a track matched in this frame, or -1
     float *Tbest;                         // [M] the IoU of the track's best free row in the running stage
     int *Tbrow;                           // [M] that row, or -1
+    // assign = lap only
+    double *Sv, *Sdist, *Su;              // [max(M, cap)] column duals and tentative distances, [min(M, cap)] row duals
+    int *Spred, *Srow4col, *Sscanned;     // [max(M, cap)] each
+    int *Scol4row;                        // [min(M, cap)]
+    int *Tidx, *Ridx;                     // [M], [cap] the stage's eligible tracks and rows of the running class, ascending
 };
 
 __device__ __forceinline__ void measure(const float4 &b, float z[4]) {
@@ -63,7 +82,15 @@ __device__ __forceinline__ void noise(float h, float pos, float vel, float &p2, 
     v2 = sv * sv;
 }
 
-// the best free row of track i among the rows of `kind` and the track's class: the largest IoU >= thr, ties to the lowest row
+// the similarity of a pair: the decode's float32 IoU, in stage 1 with fuse_score times the row's score (one rounding)
+template <bool FUSE>
+__device__ __forceinline__ float pair_sim(const float4 &pb, const float4 &rb, float score) {
+    const float o = tf_iou(pb, rb);
+    return FUSE ? o * score : o;
+}
+
+// the best free row of track i among the rows of `kind` and the track's class: the largest similarity >= thr, ties to the lowest row
+template <bool FUSE>
 __device__ __forceinline__ void scan_rows(const track_lds &L, int M, int i, int n_rows, int kind, float thr) {
     const float4 pb = L.Pbox[i];
     const int want = L.Ti[1 * M + i] * 4 + kind;
@@ -71,7 +98,7 @@ __device__ __forceinline__ void scan_rows(const track_lds &L, int M, int i, int 
     int brow = -1;
     for (int r = 0; r < n_rows; ++r) {
         if (L.Ri[r] != want) continue;
-        const float o = tf_iou(pb, L.Rbox[r]);
+        const float o = pair_sim<FUSE>(pb, L.Rbox[r], FUSE ? L.Rs[r] : 0.f);
         if (o >= thr && (brow < 0 || o > best)) {
             best = o;
             brow = r;
@@ -82,10 +109,11 @@ __device__ __forceinline__ void scan_rows(const track_lds &L, int M, int i, int 
 }
 
 // one association stage: the tracks whose state is in `states` (a bit set) and that are unmatched against the free rows of `kind`
+template <bool FUSE>
 __device__ __forceinline__ void match_stage(const track_lds &L, int M, int lane, int n_live, int n_rows, unsigned states, int kind, float thr) {
     for (int i = lane; i < n_live; i += 64) {
         if (L.Tm[i] < 0 && ((states >> L.Ti[2 * M + i]) & 1u)) {
-            scan_rows(L, M, i, n_rows, kind, thr);
+            scan_rows<FUSE>(L, M, i, n_rows, kind, thr);
         } else {
             L.Tbest[i] = -INFINITY;
             L.Tbrow[i] = -1;
@@ -114,12 +142,162 @@ __device__ __forceinline__ void match_stage(const track_lds &L, int M, int lane,
         }
         __syncthreads();
         for (int i = lane; i < n_live; i += 64)
-            if (L.Tbrow[i] == r) scan_rows(L, M, i, n_rows, kind, thr);
+            if (L.Tbrow[i] == r) scan_rows<FUSE>(L, M, i, n_rows, kind, thr);
         __syncthreads();
     }
 }
 
-// grid (n_seq), one wavefront; dynamic LDS: 128 bytes per track of M and 24 per row of cap
+// ---- assign = lap: motmetrics.lap on the stage's pairs of one class, matrix-free ---------------------------------------------------------
+
+// arg-min over (value asc, column asc) across the wave; col < 0 means "no candidate"
+__device__ __forceinline__ void track_wave_argmin(double &best, int &col) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const double ob = __shfl_xor(best, o, 64);
+        const int oc = __shfl_xor(col, o, 64);
+        if (oc >= 0 && (col < 0 || ob < best || (ob == best && oc < col))) {
+            best = ob;
+            col = oc;
+        }
+    }
+}
+
+// the cost of a pair: an allowed one (gate met; a NaN meets none) 1 - s in float64, a forbidden one 2^20
+__device__ __forceinline__ double lap_cost(float s, float thr) { return s >= thr ? 1.0 - (double)s : YK_TRACK_LAP_FORBIDDEN; }
+
+// One class of one stage by the wavefront: nt tracks (L.Tidx) x nr rows (L.Ridx), both ascending.  The solver's rows are the smaller side
+// (`tall`: more tracks than rows, the transpose, as motmetrics.lap); its m rows and n columns are positions in the two lists.  Every step of
+// the rule in its order: r = ((minval + c) - u[i]) - v[j], strict <, the first argmin among the unscanned columns, t = minval - dist[j].
+// Leaves the allowed pairs in L.Tm and their rows R_TAKEN.
+template <bool FUSE>
+__device__ __forceinline__ void lap_solve_class(const track_lds &L, int lane, int nt, int nr, float thr) {
+    const bool tall = nt > nr;
+    const int m = tall ? nr : nt, n = tall ? nt : nr;
+    const int *rowlist = tall ? L.Ridx : L.Tidx, *collist = tall ? L.Tidx : L.Ridx;
+    for (int j = lane; j < n; j += 64) {
+        L.Sv[j] = 0.0;
+        L.Srow4col[j] = -1;
+    }
+    for (int i = lane; i < m; i += 64) {
+        L.Su[i] = 0.0;
+        L.Scol4row[i] = -1;
+    }
+    __syncthreads();
+    for (int cur = 0; cur < m; ++cur) {
+        for (int j = lane; j < n; j += 64) {
+            L.Sdist[j] = INFINITY;
+            L.Spred[j] = -1;
+            L.Sscanned[j] = 0;
+        }
+        double minval = 0.0;
+        int i = cur, sink = -1;
+        while (sink < 0) {
+            const double ui = L.Su[i];
+            const int own = rowlist[i];                                  // the solver row's box (and score) stay in registers for the sweep
+            const float4 ob = tall ? L.Rbox[own] : L.Pbox[own];
+            const float os = (FUSE && tall) ? L.Rs[own] : 0.f;
+            double best = INFINITY;
+            int bcol = -1;
+            for (int j = lane; j < n; j += 64) {
+                if (L.Sscanned[j]) continue;
+                const int other = collist[j];
+                const float s = tall ? pair_sim<FUSE>(L.Pbox[other], ob, os) : pair_sim<FUSE>(ob, L.Rbox[other], FUSE ? L.Rs[other] : 0.f);
+                const double r = ((minval + lap_cost(s, thr)) - ui) - L.Sv[j];
+                double d = L.Sdist[j];
+                if (r < d) {
+                    d = r;
+                    L.Sdist[j] = r;
+                    L.Spred[j] = i;
+                }
+                if (bcol < 0 || d < best) {
+                    best = d;
+                    bcol = j;
+                }
+            }
+            track_wave_argmin(best, bcol);                               // (an unscanned column exists while no sink was found: m <= n)
+            minval = best;
+            if ((bcol & 63) == lane) L.Sscanned[bcol] = 1;
+            const int holder = L.Srow4col[bcol];
+            if (holder < 0) sink = bcol;
+            else i = holder;
+        }
+        __syncthreads();
+        // the duals: every scanned column but the sink is held by a row of its own, so no two lanes write one u
+        for (int j = lane; j < n; j += 64) {
+            if (!L.Sscanned[j]) continue;
+            const double t = minval - L.Sdist[j];
+            L.Sv[j] = L.Sv[j] - t;
+            if (j != sink) {
+                const int r = L.Srow4col[j];
+                L.Su[r] = L.Su[r] + t;
+            }
+        }
+        __syncthreads();
+        if (lane == 0) {
+            L.Su[cur] = L.Su[cur] + minval;
+            int j = sink;
+            for (;;) {
+                const int r = L.Spred[j];
+                L.Srow4col[j] = r;
+                const int next = L.Scol4row[r];
+                L.Scol4row[r] = j;
+                j = next;
+                if (r == cur) break;
+            }
+        }
+        __syncthreads();
+    }
+    // every solver row holds a column (m <= n); the pair is kept where it is allowed.  Tracks and rows of distinct pairs are distinct.
+    for (int i = lane; i < m; i += 64) {
+        const int a = rowlist[i], b = collist[L.Scol4row[i]];
+        const int t = tall ? b : a, r = tall ? a : b;
+        if (pair_sim<FUSE>(L.Pbox[t], L.Rbox[r], FUSE ? L.Rs[r] : 0.f) >= thr) {
+            L.Tm[t] = r;
+            L.Ri[r] &= ~3;                                               // R_TAKEN
+        }
+    }
+    __syncthreads();
+}
+
+// one association stage under assign = lap: the classes that have an eligible track, ascending; one solve per class that has a row too
+template <bool FUSE>
+__device__ __forceinline__ void lap_stage(const track_lds &L, int M, int lane, unsigned long long below, int n_live, int n_rows, unsigned states,
+                                          int kind, float thr) {
+    int prev = -1;
+    for (;;) {
+        int c = 0x7fffffff;                                              // the lowest class above `prev` among the eligible tracks
+        for (int i = lane; i < n_live; i += 64) {
+            const int ci = L.Ti[1 * M + i];
+            if (L.Tm[i] < 0 && ((states >> L.Ti[2 * M + i]) & 1u) && ci > prev && ci < c) c = ci;
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) c = min(c, __shfl_xor(c, o, 64));
+        if (c == 0x7fffffff) break;
+        prev = c;
+        int nt = 0, nr = 0;
+        for (int base = 0; base < n_live; base += 64) {
+            const int i = base + lane;
+            const bool take = i < n_live && L.Tm[i] < 0 && ((states >> L.Ti[2 * M + i]) & 1u) && L.Ti[1 * M + i] == c;
+            const unsigned long long mask = __ballot(take);
+            if (take) L.Tidx[nt + __popcll(mask & below)] = i;
+            nt += __popcll(mask);
+        }
+        const int want = c * 4 + kind;
+        for (int base = 0; base < n_rows; base += 64) {
+            const int r = base + lane;
+            const bool take = r < n_rows && L.Ri[r] == want;
+            const unsigned long long mask = __ballot(take);
+            if (take) L.Ridx[nr + __popcll(mask & below)] = r;
+            nr += __popcll(mask);
+        }
+        __syncthreads();
+        if (nr > 0) lap_solve_class<FUSE>(L, lane, nt, nr, thr);
+    }
+}
+
+// grid (n_seq), one wavefront; dynamic LDS: 128 bytes per track of M and 24 per row of cap, with ASSIGN = lap 28 and 32 more.
+// ASSIGN (YK_TRACK_ASSIGN_*) and FUSE (stage 1's similarity is IoU * score) are compile-time: <GREEDY, false> is the kernel of before.
+template <int ASSIGN, bool FUSE>
 __global__ void __launch_bounds__(64) track_update_kernel(int32_t *__restrict__ state, int M, const float *__restrict__ dets,
                                                           const int32_t *__restrict__ counts, int cap, const int32_t *__restrict__ seq_first,
                                                           int n_frames, int class_num, float track_thresh, float low_thresh, float stage1,
@@ -137,6 +315,18 @@ __global__ void __launch_bounds__(64) track_update_kernel(int32_t *__restrict__ 
     L.Tm = reinterpret_cast<int *>(L.Tf + 21 * M);
     L.Tbest = reinterpret_cast<float *>(L.Tm + M);
     L.Tbrow = reinterpret_cast<int *>(L.Tbest + M);
+    if constexpr (ASSIGN == YK_TRACK_ASSIGN_LAP) {                       // (128 M + 24 cap bytes lie before: a multiple of 8)
+        const int longer = max(M, cap), shorter = min(M, cap);
+        L.Sv = reinterpret_cast<double *>(L.Tbrow + M);
+        L.Sdist = L.Sv + longer;
+        L.Su = L.Sdist + longer;
+        L.Spred = reinterpret_cast<int *>(L.Su + shorter);
+        L.Srow4col = L.Spred + longer;
+        L.Sscanned = L.Srow4col + longer;
+        L.Scol4row = L.Sscanned + longer;
+        L.Ridx = L.Scol4row + shorter;
+        L.Tidx = reinterpret_cast<int *>(L.Tbest);                       // (Tbest and Tbrow are the greedy path's alone)
+    }
     int *Ti = L.Ti;
     float *Tf = L.Tf;
     const int s = blockIdx.x, lane = threadIdx.x;
@@ -195,9 +385,15 @@ __global__ void __launch_bounds__(64) track_update_kernel(int32_t *__restrict__ 
         }
         __syncthreads();
         // 3  the three associations
-        match_stage(L, M, lane, n_live, n_rows, (1u << T_TRACKED) | (1u << T_LOST), R_HIGH, stage1);
-        match_stage(L, M, lane, n_live, n_rows, 1u << T_TRACKED, R_LOW, 0.5f);
-        match_stage(L, M, lane, n_live, n_rows, 1u << T_NEW, R_HIGH, 0.3f);
+        if constexpr (ASSIGN == YK_TRACK_ASSIGN_LAP) {
+            lap_stage<FUSE>(L, M, lane, below, n_live, n_rows, (1u << T_TRACKED) | (1u << T_LOST), R_HIGH, stage1);
+            lap_stage<false>(L, M, lane, below, n_live, n_rows, 1u << T_TRACKED, R_LOW, 0.5f);
+            lap_stage<false>(L, M, lane, below, n_live, n_rows, 1u << T_NEW, R_HIGH, 0.3f);
+        } else {
+            match_stage<FUSE>(L, M, lane, n_live, n_rows, (1u << T_TRACKED) | (1u << T_LOST), R_HIGH, stage1);
+            match_stage<false>(L, M, lane, n_live, n_rows, 1u << T_TRACKED, R_LOW, 0.5f);
+            match_stage<false>(L, M, lane, n_live, n_rows, 1u << T_NEW, R_HIGH, 0.3f);
+        }
         // 4  update the matched, retire the others
         for (int i = lane; i < n_live; i += 64) {
             const int r = L.Tm[i];
@@ -365,24 +561,43 @@ extern "C" int yk_track_reset(void *d_state, int n_seq, int max_tracks, void *st
     return YK_OK;
 }
 
-extern "C" int yk_track_max_cap(int max_tracks) {
-    YK_TRACK_REFUSE("yk_track_max_cap", max_tracks <= 0 || max_tracks > YK_TRACK_MAX_TRACKS, "max_tracks %d: expected 1 .. %d", max_tracks,
-                    YK_TRACK_MAX_TRACKS)
+// LDS bytes per track and per row of a call under `assign`
+static int track_per_track(int assign) { return YK_TRACK_LDS_PER_TRACK + (assign == YK_TRACK_ASSIGN_LAP ? YK_TRACK_LAP_LDS_PER_TRACK : 0); }
+static int track_per_row(int assign) { return YK_TRACK_LDS_PER_ROW + (assign == YK_TRACK_ASSIGN_LAP ? YK_TRACK_LAP_LDS_PER_ROW : 0); }
+
+// fn: the entry point the refusal names
+static int track_max_cap(const char *fn, int max_tracks, int assign) {
+    if (max_tracks <= 0 || max_tracks > YK_TRACK_MAX_TRACKS) {
+        yk_set_error("%s: max_tracks %d: expected 1 .. %d", fn, max_tracks, YK_TRACK_MAX_TRACKS);
+        return YK_ERR_ARG;
+    }
+    if (assign != YK_TRACK_ASSIGN_GREEDY && assign != YK_TRACK_ASSIGN_LAP) {
+        yk_set_error("%s: assign %d: expected YK_TRACK_ASSIGN_GREEDY (%d) or YK_TRACK_ASSIGN_LAP (%d)", fn, assign, YK_TRACK_ASSIGN_GREEDY,
+                     YK_TRACK_ASSIGN_LAP);
+        return YK_ERR_ARG;
+    }
     const int dev = yk_current_device();
     if (dev < 0) {
-        yk_set_error("yk_track_max_cap: no HIP device");
+        yk_set_error("%s: no HIP device", fn);
         return YK_ERR_NO_DEVICE;
     }
-    const long long room = track_lds_bytes(dev) - (long long)YK_TRACK_LDS_PER_TRACK * max_tracks;
-    return room <= 0 ? 0 : (int)(room / YK_TRACK_LDS_PER_ROW);
+    const long long room = track_lds_bytes(dev) - (long long)track_per_track(assign) * max_tracks;
+    return room <= 0 ? 0 : (int)(room / track_per_row(assign));
 }
 
-extern "C" int yk_track_update(void *d_state, int n_seq, int max_tracks, const float *d_dets, const int32_t *d_counts, int cap,
-                               const int32_t *d_seq_first, int n_frames, int class_num, const yk_track_cfg_t *cfg, float *d_out,
-                               int32_t *d_out_ids, int32_t *d_out_counts, float *d_draw, void *stream) {
+extern "C" int yk_track_max_cap(int max_tracks) { return track_max_cap("yk_track_max_cap", max_tracks, YK_TRACK_ASSIGN_GREEDY); }
+
+extern "C" int yk_track_max_cap_ex(int max_tracks, int assign) { return track_max_cap("yk_track_max_cap_ex", max_tracks, assign); }
+
+extern "C" int yk_track_update_ex(void *d_state, int n_seq, int max_tracks, const float *d_dets, const int32_t *d_counts, int cap,
+                                  const int32_t *d_seq_first, int n_frames, int class_num, const yk_track_cfg_t *cfg, int assign,
+                                  int fuse_score, float *d_out, int32_t *d_out_ids, int32_t *d_out_counts, float *d_draw, void *stream) {
 #define R(cond, ...) YK_TRACK_REFUSE("yk_track_update", cond, __VA_ARGS__)
     R(!d_state, "d_state is NULL")
     YK_TRACK_STATE_ARGS("yk_track_update")
+    R(assign != YK_TRACK_ASSIGN_GREEDY && assign != YK_TRACK_ASSIGN_LAP, "assign %d: expected YK_TRACK_ASSIGN_GREEDY (%d) or YK_TRACK_ASSIGN_LAP (%d)",
+      assign, YK_TRACK_ASSIGN_GREEDY, YK_TRACK_ASSIGN_LAP)
+    R(fuse_score != 0 && fuse_score != 1, "fuse_score %d: expected 0 or 1", fuse_score)
     R(!d_dets, "d_dets is NULL")
     R(!d_counts, "d_counts is NULL")
     R(!d_seq_first, "d_seq_first is NULL")
@@ -398,16 +613,33 @@ extern "C" int yk_track_update(void *d_state, int n_seq, int max_tracks, const f
     R(cfg->match_thresh != cfg->match_thresh, "cfg->match_thresh is NaN")
     R(cfg->track_buffer < 0, "cfg->track_buffer %d: expected a number of frames >= 0", cfg->track_buffer)
     R((long long)n_frames * cap > 0x7fffffffLL, "n_frames %d x cap %d: 2^31 rows or more", n_frames, cap)
-    const int max_cap = yk_track_max_cap(max_tracks);
+    const int max_cap = track_max_cap("yk_track_update", max_tracks, assign);
     if (max_cap < 0) return max_cap;
-    R(cap > max_cap, "cap %d: beside max_tracks %d the device holds %d rows of a frame in LDS (yk_track_max_cap)", cap, max_tracks, max_cap)
+    R(cap > max_cap, "cap %d: beside max_tracks %d the device holds %d rows of a frame in LDS (%s)", cap, max_tracks, max_cap,
+      assign == YK_TRACK_ASSIGN_LAP ? "yk_track_max_cap_ex, assign lap" : "yk_track_max_cap")
 #undef R
-    const size_t lds = (size_t)YK_TRACK_LDS_PER_TRACK * max_tracks + (size_t)YK_TRACK_LDS_PER_ROW * cap;
-    yk_launch_lds(track_update_kernel, dim3((unsigned)n_seq), dim3(64), lds, (hipStream_t)stream, (int32_t *)d_state, max_tracks, d_dets, d_counts, cap,
-                  d_seq_first, n_frames, class_num, cfg->track_thresh, cfg->low_thresh, 1.f - cfg->match_thresh, cfg->track_thresh + 0.1f,
-                  cfg->track_buffer, d_out, d_out_ids, d_out_counts, d_draw);
+    const size_t lds = (size_t)track_per_track(assign) * max_tracks + (size_t)track_per_row(assign) * cap;
+    auto go = [&](auto kern) {
+        yk_launch_lds(kern, dim3((unsigned)n_seq), dim3(64), lds, (hipStream_t)stream, (int32_t *)d_state, max_tracks, d_dets, d_counts, cap,
+                      d_seq_first, n_frames, class_num, cfg->track_thresh, cfg->low_thresh, 1.f - cfg->match_thresh, cfg->track_thresh + 0.1f,
+                      cfg->track_buffer, d_out, d_out_ids, d_out_counts, d_draw);
+    };
+    if (assign == YK_TRACK_ASSIGN_LAP) {
+        if (fuse_score) go(track_update_kernel<YK_TRACK_ASSIGN_LAP, true>);
+        else go(track_update_kernel<YK_TRACK_ASSIGN_LAP, false>);
+    } else {
+        if (fuse_score) go(track_update_kernel<YK_TRACK_ASSIGN_GREEDY, true>);
+        else go(track_update_kernel<YK_TRACK_ASSIGN_GREEDY, false>);
+    }
     YK_HIP(hipGetLastError());
     return YK_OK;
+}
+
+extern "C" int yk_track_update(void *d_state, int n_seq, int max_tracks, const float *d_dets, const int32_t *d_counts, int cap,
+                               const int32_t *d_seq_first, int n_frames, int class_num, const yk_track_cfg_t *cfg, float *d_out,
+                               int32_t *d_out_ids, int32_t *d_out_counts, float *d_draw, void *stream) {
+    return yk_track_update_ex(d_state, n_seq, max_tracks, d_dets, d_counts, cap, d_seq_first, n_frames, class_num, cfg, YK_TRACK_ASSIGN_GREEDY, 0,
+                              d_out, d_out_ids, d_out_counts, d_draw, stream);
 }
 
 extern "C" int yk_track_read(const void *d_state, int n_seq, int max_tracks, int32_t *h_live, int32_t *h_next_id, int32_t *h_overflow) {

@@ -3,7 +3,7 @@
     python keras_detect.py CKPT SRC --out_dir D [--draw True|False] [--decode pil|gpu] [--encode pil|gpu] [--quality 75] [--batch 32] [--depth 4]
                            [--tiles NXxNY --tile_overlap 0.2 --tile_full True --tile_match ios|iou --tile_thresh 0.5]
                            [--tta 1,1f|flip|v5 --tta_thresh 0.55]
-                           [--track True --track_thresh 0.5 --track_low 0.1 --track_match 0.8 --track_buffer 30 --track_max 256]
+                           [--track True --track_thresh 0.5 --track_low 0.1 --track_match 0.8 --track_buffer 30 --track_max 256 --track_assign greedy --track_fuse False]
                            [network and threshold flags of keras_inference.py]
 
 SRC: a folder (its .jpg / .jpeg / .png / .bmp files, in sorted order), a text file with one picture path per line, or one picture.
@@ -183,7 +183,7 @@ def run(h: Helper, model, sources, out_dir=None, draw: bool = True, batch: int =
         return_arrays: bool = False, verbose: bool = True, max_out: int = 30, encode: str = 'pil', quality: int = 75, decode: str = 'pil',
         nms: str = 'hard', nms_sigma: float = 0.5, tiles=None, tile_overlap: float = 0.2, tile_full: bool = True, tile_match: str = 'ios',
         tile_thresh: float = 0.5, tta=None, tta_thresh: float = 0.55, track: bool = False, track_thresh: float = 0.5, track_low: float = 0.1,
-        track_match: float = 0.8, track_buffer: int = 30, track_max: int = 256):
+        track_match: float = 0.8, track_buffer: int = 30, track_max: int = 256, track_assign: str = 'greedy', track_fuse: bool = False):
     """sources: picture paths, or [h, w, 3] uint8 arrays already in memory (then `names` names them); with decode='gpu' paths or the bytes of
     picture files: baseline JPEGs are decoded on the device by the rule of include/yolo_hip.h (not PIL's bytes: DESIGN.md 3.12), every other
     file by PIL on the pool as with decode='pil'; a stream the device cannot finish raises YkError naming the file.  -> {'names', 'detections': one
@@ -203,7 +203,10 @@ def run(h: Helper, model, sources, out_dir=None, draw: bool = True, batch: int =
     when a batch is drained, in frame order whatever `depth` is, between the slot's decode and the draw; 'detections' are then the tracks'
     rows, 'track_ids' their ids per picture and 'sequences' the sequences' names; the draw labels a box with its id (mod 100); with out_dir
     detections.json's rows carry the id as a seventh column and tracks/<sequence>.txt is written in the MOTChallenge text format.  track together with tiles, tta or a soft nms is refused; a sequence
-    that needed more than track_max tracks raises YkError naming it at the end of the run.  False (the default): everything as without it."""
+    that needed more than track_max tracks raises YkError naming it at the end of the run.  track_assign='lap': the optimal association per
+    stage and class instead of the greedy one; track_fuse=True: the first association compares IoU * score (both: track.py's header); either
+    is named in detections.json, and a frame of more rows than engine.track_max_cap(track_max, 'lap') is refused by name.  False (the
+    default): everything as without it."""
     import torch
     from . import engine
     engine.require_gpu()
@@ -233,7 +236,7 @@ def run(h: Helper, model, sources, out_dir=None, draw: bool = True, batch: int =
             raise engine.YkError(f'detect: tta {tt.text_of(tta_spec)}: a picture is {T} frames and a batch holds {int(batch)}')
     if track:
         try:
-            track_cfg = tk.check(track_thresh, track_low, track_match, track_buffer, track_max, nms, tiles, tta)
+            track_cfg = tk.check(track_thresh, track_low, track_match, track_buffer, track_max, nms, tiles, tta, track_assign, track_fuse)
         except ValueError as e:
             raise engine.YkError(f'detect: {e}') from None
     gpu_decode = decode == 'gpu'
@@ -258,6 +261,9 @@ def run(h: Helper, model, sources, out_dir=None, draw: bool = True, batch: int =
             raise engine.YkError(f'detect: {e}') from None
         tracks = engine.TrackState(len(seq_names), h.class_num, max_tracks=int(track_max), **track_cfg)
         track_ids = [None] * n_all
+        if track_assign != 'greedy' and cap > tracks.max_cap:
+            raise engine.YkError(f'detect: track_assign {track_assign}: a frame has up to {cap} rows and beside track_max {int(track_max)} tracks the '
+                                 f'device holds {tracks.max_cap} (engine.track_max_cap); lower track_max')
         if verbose and obj_thresh > track_low:
             print(NOTE, f' obj_thresh {obj_thresh:g} is above track_low {track_low:g}: the decode drops the rows between the two, and the second '
                         f'association sees nothing there')
@@ -533,7 +539,7 @@ def run(h: Helper, model, sources, out_dir=None, draw: bool = True, batch: int =
             rule.update(tt.rule_of(tta_spec, tta_thresh))
         doc = [{'path': names[i], **rule, 'detections': [[float(v) for v in row] for row in results[i]]} for i in range(n_all)]
         if track:                                            # a row is a track's row with its id: [top, left, bottom, right, score, class, track_id]
-            rule.update(tracker='bytetrack-greedy', **track_cfg, track_max=int(track_max))
+            rule.update(tracker=f'bytetrack-{track_assign}', **track_cfg, track_max=int(track_max))
             doc = [{'path': names[i], **rule, 'sequence': seq_names[seq_of[i]],
                     'detections': [[*(float(v) for v in row), int(t)] for row, t in zip(results[i], track_ids[i])]} for i in range(n_all)]
             (Path(out_dir) / 'tracks').mkdir(exist_ok=True)
@@ -578,7 +584,8 @@ def main(argv=None):
         print(INFO, f' tta {tt.text_of(a.tta)}: {len(a.tta)} views a picture, fused by IoU > {a.tta_thresh:g} (tta.py); scores are the fused ones')
     if a.track:
         print(INFO, f' track: {len(res["sequences"])} sequences, ids up to {max([int(t.max()) for t in res["track_ids"] if len(t)], default=0)} '
-                    f'(track.py: ByteTrack restated, class-aware and greedy) -> {Path(a.out_dir) / "tracks"}')
+                    f'(track.py: ByteTrack restated, class-aware and {"greedy" if a.track_assign == "greedy" else "optimal (lap)"}'
+                    f'{", fuse_score" if a.track_fuse else ""}) -> {Path(a.out_dir) / "tracks"}')
     print(INFO, f' {len(paths)} pictures, {sum(len(d) for d in res["detections"])} detections -> {Path(a.out_dir) / "detections.json"}'
           + (f', {len(res["files"])} annotated pictures' if a.draw else ''))
     return res

@@ -835,17 +835,28 @@ class TrackCfg(C.Structure):
     _fields_ = [('track_thresh', C.c_float), ('low_thresh', C.c_float), ('match_thresh', C.c_float), ('track_buffer', C.c_int32)]
 
 
-def track_max_cap(max_tracks: int = 256) -> int:
-    """Rows of one frame that TrackState.update takes beside max_tracks tracks on the current device; more are refused."""
-    n = lib().yk_track_max_cap(int(max_tracks))
+TRACK_ASSIGNS = {'greedy': 0, 'lap': 1}      # YK_TRACK_ASSIGN_GREEDY / YK_TRACK_ASSIGN_LAP
+
+
+def track_max_cap(max_tracks: int = 256, assign: str = 'greedy') -> int:
+    """Rows of one frame that TrackState.update takes beside max_tracks tracks on the current device; more are refused.  assign='lap'
+    (yk_track_max_cap_ex): fewer, the solver's vectors lie in LDS beside them."""
+    if assign == 'greedy':
+        n, fn = lib().yk_track_max_cap(int(max_tracks)), 'yk_track_max_cap'
+    else:
+        if assign not in TRACK_ASSIGNS:
+            raise YkError(f'track_max_cap: assign {assign!r}: expected one of {", ".join(TRACK_ASSIGNS)}')
+        n, fn = lib().yk_track_max_cap_ex(int(max_tracks), TRACK_ASSIGNS[assign]), 'yk_track_max_cap_ex'
     if n < 0:
-        _check(n, 'yk_track_max_cap')
+        _check(n, fn)
     return int(n)
 
 
 class TrackState:
     """The tracks of n_seq sequences on the device (yk_track_update; the rule is track.Tracker's, bit for bit).  cfg: track_thresh,
-    low_thresh, match_thresh, track_buffer (track.check refuses bad ones by name)."""
+    low_thresh, match_thresh, track_buffer, assign ('greedy' | 'lap') and fuse_score (track.check refuses bad ones by name).  With the
+    defaults of the last two every update is one yk_track_update call; otherwise yk_track_update_ex, and `max_cap` - the rows of a frame a
+    call takes - is yk_track_max_cap_ex's."""
 
     def __init__(self, n_seq: int, class_num: int, max_tracks: int = 256, **cfg):
         import torch
@@ -859,6 +870,8 @@ class TrackState:
             raise YkError(f'TrackState: n_seq {n_seq!r} and class_num {class_num!r} are at least 1')
         self.n_seq, self.class_num, self.max_tracks = int(n_seq), int(class_num), int(max_tracks)
         self.cfg = TrackCfg(opts['track_thresh'], opts['low_thresh'], opts['match_thresh'], opts['track_buffer'])
+        self.assign, self.fuse_score = opts.get('assign', 'greedy'), bool(opts.get('fuse_score', False))
+        self.max_cap = track_max_cap(self.max_tracks, self.assign)
         nbytes = C.c_size_t(0)
         call('yk_track_state_bytes', self.n_seq, self.max_tracks, C.byref(nbytes))
         self.state = torch.empty(nbytes.value // 4, dtype=torch.int32, device=torch.device('cuda', torch.cuda.current_device()))
@@ -896,8 +909,12 @@ class TrackState:
         for t, shape, dt in ((rows, (n_frames, cap, 6), torch.float32), (ids, (n_frames, cap), torch.int32), (out_counts, (n_frames,), torch.int32)) + \
                 (((d_draw, (n_frames, cap, 6), torch.float32),) if draw else ()):
             assert t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == shape, tuple(t.shape)
-        call('yk_track_update', self.state, self.n_seq, self.max_tracks, dets, counts, cap, seq_first, n_frames, self.class_num,
-             C.byref(self.cfg), rows, ids, out_counts, d_draw, _stream(stream))
+        if self.assign == 'greedy' and not self.fuse_score:
+            call('yk_track_update', self.state, self.n_seq, self.max_tracks, dets, counts, cap, seq_first, n_frames, self.class_num,
+                 C.byref(self.cfg), rows, ids, out_counts, d_draw, _stream(stream))
+        else:
+            call('yk_track_update_ex', self.state, self.n_seq, self.max_tracks, dets, counts, cap, seq_first, n_frames, self.class_num,
+                 C.byref(self.cfg), TRACK_ASSIGNS[self.assign], int(self.fuse_score), rows, ids, out_counts, d_draw, _stream(stream))
         self._keep = seq_first                                              # alive until the launch has read it
         return (rows, ids, out_counts, d_draw) if draw else (rows, ids, out_counts)
 

@@ -5,16 +5,31 @@ The rows the decode leaves per frame get identities that last from frame to fram
   Detection Box", ECCV 2022,
 restated from the paper: a constant-velocity Kalman filter per track (the 8-state filter of SORT), a first association of the tracks with
 the high-score boxes, a second association of the tracks still unmatched with the low-score boxes a detector normally throws away.
-PARITY UNPINNED: the authors' code is not on hand and no number here is held to it or to TrackEval.  Three deliberate deviations:
+PARITY UNPINNED: the authors' code is not on hand and no number here is held to it or to TrackEval.  Two deliberate deviations:
   - class-aware.  A track keeps the class of the row that opened it and pairs of different classes never match (ByteTrack is written for
     one class; this detector has twenty).
-  - greedy, not Hungarian.  In each stage the pair with the largest IoU is taken, then the next (ties: the lowest track index, then the
-    lowest row index).  An unspecified linear-assignment solver has no order of operations a kernel could be held to bit for bit; the
-    greedy rule has, and is what embedded ports do.  (motmetrics.lap states one that has, for the scores: DESIGN.md 3.28.)
-  - the defaults (track_thresh 0.5, low_thresh 0.1, match_thresh 0.8, track_buffer 30) are ByteTrack's and are starting points, not
-    findings; its `fuse_score` option is left out.
-What is pinned: the filter against the dense 8 x 8 filter in float64 and the rule on hand cases (tests/test_track.py), and the kernel
-against this module, bit for bit (tests/test_gpu_track.py).
+  - greedy by default, not Hungarian.  In each stage the pair with the largest similarity is taken, then the next (ties: the lowest track
+    index, then the lowest row index); it is what embedded ports do, and what every earlier run of this tracker did.  assign='lap' makes
+    the optimal assignment ByteTrack makes, by the one solver whose order of operations is stated: motmetrics.lap.
+The defaults (track_thresh 0.5, low_thresh 0.1, match_thresh 0.8, track_buffer 30) are ByteTrack's and are starting points, not findings;
+its `fuse_score` is an option here too, off by default.
+What is pinned: the filter against the dense 8 x 8 filter in float64 and the rule on hand cases (tests/test_track.py), the optimal
+association against a brute force (tests/test_track_assign.py), and the kernel against this module, bit for bit (tests/test_gpu_track.py,
+tests/test_gpu_track_assign.py).
+
+Similarity.  s of a (track, row) pair is the float32 IoU below; in stage 1 with fuse_score it is float32(IoU * the row's score), one
+rounding; stages 2 and 3 are never fused.  The gates read s: s >= 1 - match_thresh in stage 1, s >= 0.5 in stage 2, s >= 0.3 in stage 3;
+a NaN meets no gate.  Fusion applies under greedy too: the pair with the largest s is taken, with the same ties.
+
+assign='lap', per stage: for each class c in ascending order that has at least one eligible track and one eligible free row, a cost matrix
+over that class only - its rows the eligible tracks of class c in track-index order, its columns the eligible rows of class c in row
+order; an allowed pair (gate met) costs float64(1) - float64(s), a forbidden one LAP_FORBIDDEN = 2.0 ** 20; motmetrics.lap solves it
+exactly as it is written, its transpose when there are more tracks than rows included; of the assigned pairs the allowed ones are kept
+and their rows are taken before the next stage.  Why 2 ** 20: at most 1024 tracks and costs of at most 1 give any sum of allowed costs
+below it, so the solver first maximises the number of allowed matches and then minimises their total cost; and a power of two that size
+leaves the duals about 2e-10 of resolution, where the scores' 1e10 would leave 2e-6.  This is the "solve, then drop the pairs over the
+threshold" form that scipy-based ports of ByteTrack use, not lapjv's `cost_limit` extension (which solves an extended problem and can
+pick other pairs); parity with the authors' code stays unpinned.
 
 State per track: id (from 1, ascending in order of opening), class, state (NEW seen once and not confirmed, TRACKED, LOST), the frame of its
 last match, its last score, and the filter over (cx, cy, a, h), a = w / h, and their velocities.  Tracks are kept in ascending id order.
@@ -53,17 +68,25 @@ from typing import Optional, Tuple
 
 import numpy as np
 
+from .motmetrics import lap
+
 F = np.float32
 NEW, TRACKED, LOST = 0, 1, 2
 DEFAULTS = dict(track_thresh=0.5, low_thresh=0.1, match_thresh=0.8, track_buffer=30)
 DEFAULT_MAX_TRACKS = 256
 MAX_TRACKS = 1024                         # what yk_track_update holds of one sequence in LDS at the most
 STAGE2_IOU, STAGE3_IOU, OPEN_MARGIN = 0.5, 0.3, 0.1
+ASSIGNS = ('greedy', 'lap')               # YK_TRACK_ASSIGN_GREEDY, YK_TRACK_ASSIGN_LAP
+LAP_FORBIDDEN = 2.0 ** 20
 
 
 def check(track_thresh=0.5, low_thresh=0.1, match_thresh=0.8, track_buffer=30, max_tracks=DEFAULT_MAX_TRACKS, nms: str = 'hard',
-          tiles=None, tta=None) -> dict:
-    """The tracker's options, refused by name -> the four options as a dict."""
+          tiles=None, tta=None, assign: str = 'greedy', fuse_score: bool = False) -> dict:
+    """The tracker's options, refused by name -> the four options as a dict, and `assign` / `fuse_score` where they are not the defaults."""
+    if assign not in ASSIGNS:
+        raise ValueError(f'track_assign {assign!r}: expected one of {", ".join(ASSIGNS)}')
+    if not isinstance(fuse_score, (bool, np.bool_)):
+        raise ValueError(f'track_fuse {fuse_score!r}: expected True or False')
     num = lambda v: isinstance(v, (int, float, np.floating, np.integer)) and not isinstance(v, bool) and math.isfinite(v)
     if not (num(track_thresh) and 0.0 < track_thresh <= 1.0):
         raise ValueError(f'track_thresh {track_thresh!r}: expected a number in (0, 1]')
@@ -82,7 +105,12 @@ def check(track_thresh=0.5, low_thresh=0.1, match_thresh=0.8, track_buffer=30, m
         raise ValueError('track with tta: the fused scores are not the scores the two thresholds were set for; tracking takes one view')
     if nms != 'hard':
         raise ValueError(f"nms {nms!r} with track: the second association reads undecayed low scores; tracking needs nms 'hard'")
-    return dict(track_thresh=float(track_thresh), low_thresh=float(low_thresh), match_thresh=float(match_thresh), track_buffer=int(track_buffer))
+    out = dict(track_thresh=float(track_thresh), low_thresh=float(low_thresh), match_thresh=float(match_thresh), track_buffer=int(track_buffer))
+    if assign != 'greedy':
+        out['assign'] = assign
+    if fuse_score:
+        out['fuse_score'] = True
+    return out
 
 
 def add_arguments(p) -> None:
@@ -94,20 +122,25 @@ def add_arguments(p) -> None:
     p.add_argument('--track_match', type=float, default=DEFAULTS['match_thresh'], help='the first association matches at IoU >= 1 - this')
     p.add_argument('--track_buffer', type=int, default=DEFAULTS['track_buffer'], help='frames a lost track is kept')
     p.add_argument('--track_max', type=int, default=DEFAULT_MAX_TRACKS, help=f'tracks held per sequence (at most {MAX_TRACKS})')
+    p.add_argument('--track_assign', type=str, default='greedy',
+                   help='greedy: the best pair first; lap: the optimal assignment per stage and class (motmetrics.lap)')
+    p.add_argument('--track_fuse', type=str, choices=['True', 'False'], default='False',
+                   help="ByteTrack's fuse_score: the first association compares IoU * score instead of IoU")
 
 
 def parse_arguments(a) -> None:
-    """Checks what add_arguments read (ValueError by name) and leaves a.track as a bool."""
+    """Checks what add_arguments read (ValueError by name) and leaves a.track and a.track_fuse as bools."""
     a.track = a.track == 'True'
+    a.track_fuse = a.track_fuse == 'True'
     if a.track:
         check(a.track_thresh, a.track_low, a.track_match, a.track_buffer, a.track_max, getattr(a, 'nms', 'hard'), getattr(a, 'tiles', None),
-              getattr(a, 'tta', None))
+              getattr(a, 'tta', None), a.track_assign, a.track_fuse)
 
 
 def run_options(a) -> dict:
     """The keyword arguments detect.run takes, from parsed arguments."""
     return dict(track=a.track, track_thresh=a.track_thresh, track_low=a.track_low, track_match=a.track_match, track_buffer=a.track_buffer,
-                track_max=a.track_max)
+                track_max=a.track_max, track_assign=a.track_assign, track_fuse=a.track_fuse)
 
 
 # ---- the filter: the last axis holds the four coordinates; any leading axes are tracks --------------------------------------------------
@@ -199,11 +232,13 @@ def iou_matrix(a: np.ndarray, b: np.ndarray) -> np.ndarray:
 class Tracker:
     """The host form of one sequence: update(rows of a frame) -> (rows [k, 6] float32, ids [k] int32)."""
 
-    def __init__(self, class_num: int, track_thresh=0.5, low_thresh=0.1, match_thresh=0.8, track_buffer=30, max_tracks: Optional[int] = None):
-        cfg = check(track_thresh, low_thresh, match_thresh, track_buffer, max_tracks)
+    def __init__(self, class_num: int, track_thresh=0.5, low_thresh=0.1, match_thresh=0.8, track_buffer=30, max_tracks: Optional[int] = None,
+                 assign: str = 'greedy', fuse_score: bool = False):
+        cfg = check(track_thresh, low_thresh, match_thresh, track_buffer, max_tracks, assign=assign, fuse_score=fuse_score)
         if int(class_num) < 1:
             raise ValueError(f'class_num {class_num!r}: expected at least 1')
         self.class_num, self.max_tracks = int(class_num), max_tracks
+        self.assign, self.fuse_score = assign, bool(fuse_score)
         self.track_thresh, self.low_thresh = F(cfg['track_thresh']), F(cfg['low_thresh'])
         self.stage1 = F(1) - F(cfg['match_thresh'])
         self.open_thresh = self.track_thresh + F(OPEN_MARGIN)
@@ -242,9 +277,26 @@ class Tracker:
         same = self.cls[:, None] == classes[None, :]
         match = np.full(n_t, -1, np.int64)
         free = np.ones(n_r, bool)
-        for states, want_high, thr in (((TRACKED, LOST), True, self.stage1), ((TRACKED,), False, F(STAGE2_IOU)), ((NEW,), True, F(STAGE3_IOU))):
+        with np.errstate(all='ignore'):
+            fused = (iou * scores[None, :]).astype(F) if self.fuse_score else iou
+        for stage, (states, want_high, thr) in enumerate((((TRACKED, LOST), True, self.stage1), ((TRACKED,), False, F(STAGE2_IOU)),
+                                                          ((NEW,), True, F(STAGE3_IOU)))):
+            sim = fused if stage == 0 else iou
             t_ok = np.isin(self.state, states) & (match < 0)
-            m = np.where(same & t_ok[:, None] & (free & (high == want_high))[None, :] & (iou >= thr), iou, F(-1))
+            if self.assign == 'lap':
+                r_ok = free & (high == want_high)
+                for c in np.unique(self.cls[t_ok]):                       # ascending
+                    ts, rs = np.flatnonzero(t_ok & (self.cls == c)), np.flatnonzero(r_ok & (classes == c))
+                    if not len(rs):
+                        continue
+                    s = sim[np.ix_(ts, rs)]
+                    allowed = s >= thr                                    # (a NaN meets no gate)
+                    cost = np.where(allowed, np.float64(1) - s.astype(np.float64), LAP_FORBIDDEN)
+                    for i, j in enumerate(lap(cost)):
+                        if j >= 0 and allowed[i, j]:
+                            match[ts[i]], free[rs[j]] = rs[j], False
+                continue
+            m = np.where(same & t_ok[:, None] & (free & (high == want_high))[None, :] & (sim >= thr), sim, F(-1))
             while m.size:
                 k = int(np.argmax(m))                                     # the largest IoU; ties: the lowest track, then the lowest row
                 t, r = divmod(k, n_r)

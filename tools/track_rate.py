@@ -7,7 +7,10 @@
   (ii)  detect.run pictures/s on generated frames of moving rectangles (JPEG files in a folder, seeded random weights), track off and on;
   (iii) the same off run by the package of a second tree - a checkout of the parent commit, built, given with --parent.  Off has to agree
         with it within the spread of the repeats: the acceptance condition on speed;
-  (iv)  on against off, recorded and not judged.
+  (iv)  on against off, recorded and not judged;
+  (v)   the call of (i) under --track_assign: greedy by the parent commit's tree, greedy and lap by this tree, fresh processes in turns.  The
+        two greedy rows have to agree within the spread of their own repeats; the lap row is recorded and not judged.  --only_assign
+        measures (v) alone and replaces it in --out.
 (ii) - (iv): every measurement is a fresh child process of this file (--child) that imports the package of ONE tree, runs a warm-up and then
 --runs timed runs; the kinds (off, parent off, on) take turns, --rounds times, so each has rounds * runs repeats taken in one session.
 Medians and the spread (min .. max) of the repeats.  Needs an MI355X; there is no CPU path.
@@ -43,12 +46,75 @@ def spread(v):
     return f'median {np.median(v):.4g} (min {v.min():.4g} .. max {v.max():.4g}, {len(v)} repeats)'
 
 
+def case_rows():
+    return {'1 sequence x 32 frames, 10 tracks': [moving_rows(10, 32, 1)], '1 sequence x 32 frames, 200 tracks': [moving_rows(200, 32, 2)],
+            '8 sequences x 4 frames, 50 tracks each': [moving_rows(50, 4, 10 + s) for s in range(8)]}
+
+
+def assign_child(tree: str, assign: str, repeats: int):
+    """One process, one tree's package: the cases of (i) under `assign`, three warm-up calls and `repeats` timed ones each -> a JSON line of
+    ms per call.  The parent commit's tree has no `assign`, and is only asked for greedy."""
+    sys.path.insert(0, tree)
+    import torch
+    from k210_yolo_framework_amd import engine
+    assert Path(engine.__file__).resolve().is_relative_to(Path(tree).resolve()), engine.__file__
+    times = {}
+    for name, seqs in case_rows().items():
+        frames = [f for s in seqs for f in s]
+        dets, counts = np.zeros((len(frames), 600, 6), F), np.asarray([len(f) for f in frames], np.int32)
+        for i, f in enumerate(frames):
+            dets[i, :len(f)] = f
+        state = engine.TrackState(len(seqs), 20, **({} if assign == 'greedy' else {'assign': assign}))
+        first = torch.from_numpy(np.concatenate([[0], np.cumsum([len(s) for s in seqs])]).astype(np.int32)).cuda()
+        d, c = torch.from_numpy(dets).cuda(), torch.from_numpy(counts).cuda()
+        out = state.update(d, c, first)
+        times[name] = []
+        for rep in range(3 + repeats):
+            state.reset()
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            state.update(d, c, first, out=out)
+            b.record()
+            b.synchronize()
+            if rep >= 3:
+                times[name].append(a.elapsed_time(b))
+    print('TIMES ' + json.dumps(times))
+
+
+def assign_rates(parent: str, rounds: int, repeats: int, lines):
+    """(v): one yk_track_update call under greedy by the parent commit's tree, greedy by this tree and lap by this tree, fresh processes in
+    turns.  -> do the two greedy rows agree within the spread of their own repeats, in every case"""
+    kinds = {'greedy, parent commit': (str(Path(parent).resolve()), 'greedy'), 'greedy': (str(ROOT), 'greedy'), 'lap': (str(ROOT), 'lap')}
+    times = {k: {name: [] for name in case_rows()} for k in kinds}
+    for _ in range(rounds):
+        for kind, (tree, assign) in kinds.items():
+            r = subprocess.run([sys.executable, str(Path(__file__).resolve()), '--assign-child', tree, assign, str(repeats)], capture_output=True,
+                               text=True, timeout=CHILD_LIMIT, cwd=tree)
+            if r.returncode != 0:                                       # nothing more is started after a child that failed
+                raise SystemExit(f'track_rate: the {kind} child ended with {r.returncode}:\n{r.stderr[-2000:]}')
+            for name, ms in json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('TIMES ')][-1][6:]).items():
+                times[kind][name] += ms
+    lines.append(f'(v) yk_track_update, ms per call by --track_assign: {rounds} rounds of fresh processes in turns ({", ".join(kinds)}), '
+                 f'3 warm-up calls and {repeats} timed ones each')
+    agree = True
+    for name in case_rows():
+        lines.append(f'    {name}')
+        lines += [f'      {kind + ":":24s}{spread(times[kind][name])}' for kind in kinds]
+        old, new = times['greedy, parent commit'][name], times['greedy'][name]
+        inside = min(old) <= np.median(new) <= max(old) and min(new) <= np.median(old) <= max(new)
+        agree &= bool(inside)
+        lines.append(f'      greedy / parent = {np.median(new) / np.median(old):.3f}; each median lies {"INSIDE" if inside else "OUTSIDE"} the other\'s min .. max.  '
+                     f'lap / greedy = {np.median(times["lap"][name]) / np.median(new):.2f} (recorded, not judged)')
+    lines.append('    not measured: the solver\'s worst case (a stage of one class in which every augmentation walks every row: rows x rows x '
+                 'columns / 64 lane steps); these rows have twenty classes and boxes that stay apart')
+    return agree
+
+
 def kernel_cases(repeats: int, lines):
     import torch
     from k210_yolo_framework_amd import engine
     from k210_yolo_framework_amd import track as tk
-    cases = {'1 sequence x 32 frames, 10 tracks': [moving_rows(10, 32, 1)], '1 sequence x 32 frames, 200 tracks': [moving_rows(200, 32, 2)],
-             '8 sequences x 4 frames, 50 tracks each': [moving_rows(50, 4, 10 + s) for s in range(8)]}
+    cases = case_rows()
     prepared = {}
     for name, seqs in cases.items():
         cap = 600
@@ -149,6 +215,8 @@ def detect_rates(parent: str, n_frames: int, rounds: int, runs: int, lines):
 def main():
     if len(sys.argv) > 1 and sys.argv[1] == '--child':
         return child(sys.argv[2], sys.argv[3], sys.argv[4], sys.argv[5] == '1', int(sys.argv[6]))
+    if len(sys.argv) > 1 and sys.argv[1] == '--assign-child':
+        return assign_child(sys.argv[2], sys.argv[3], int(sys.argv[4]))
     sys.path.insert(0, str(ROOT))
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     p.add_argument('--parent', type=str, required=True, help='a built checkout of the parent commit: its track-off detect.run is measured beside this tree\'s')
@@ -157,15 +225,24 @@ def main():
     p.add_argument('--frames', type=int, default=96)
     p.add_argument('--rounds', type=int, default=4)
     p.add_argument('--runs', type=int, default=3)
+    p.add_argument('--only_assign', action='store_true', help='measure (v) alone and replace it in --out, whose other lines stay')
     a = p.parse_args()
     if not (Path(a.parent) / 'k210_yolo_framework_amd' / 'csrc' / 'libyolo_hip.so').exists():
         p.error(f'--parent {a.parent}: no built k210_yolo_framework_amd/csrc/libyolo_hip.so there')
+    if a.only_assign:
+        kept = Path(a.out).read_text().splitlines() if Path(a.out).exists() else []
+        lines = kept[:next((i for i, ln in enumerate(kept) if ln.startswith('(v) ')), len(kept))]
+        agrees = assign_rates(a.parent, a.rounds, a.repeats, lines)
+        Path(a.out).write_text('\n'.join(lines) + '\n')
+        print('\n'.join(lines))
+        return 0 if agrees else 1
     lines = ['tools/track_rate.py: tracking (DESIGN.md 3.27); times from device events, rates from a host clock around runs that end synchronised']
     agrees = detect_rates(a.parent, a.frames, a.rounds, a.runs, lines)   # first: the children run before this process opens the GPU
     from k210_yolo_framework_amd import engine
     engine.require_gpu()
     kernel_cases(a.repeats, lines)
     lines.append('not measured: tracking quality (MOTA, IDF1) - no annotated sequences; PRECISION=kpu with TRACK=True (it shares the padded-row path)')
+    agrees &= assign_rates(a.parent, a.rounds, a.repeats, lines)         # last: the section --only_assign replaces
     Path(a.out).parent.mkdir(parents=True, exist_ok=True)
     Path(a.out).write_text('\n'.join(lines) + '\n')
     print('\n'.join(lines))

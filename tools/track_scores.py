@@ -42,15 +42,17 @@ def main():
              'motmetrics_gpu.MotEvaluator; recorded, not judged' % (track.DEFAULTS,)]
     for label, miss, clutter in (('clean: no misses, no clutter', 0.0, 0.0), ('10 % missed rows, 0.5 clutter boxes a frame', 0.1, 0.5),
                                  ('30 % missed rows, 2 clutter boxes a frame', 0.3, 2.0)):
-        rng, ev, cap, n_frames = np.random.default_rng(0), mg.MotEvaluator(), 64, 120
-        for name, gt, _ in mm.synthetic_sequences(8, n_frames, 10, seed=7):
-            dets, counts = detections(gt, n_frames, rng, miss, clutter, cap)
-            state = engine.TrackState(1, 1)
-            rows, ids, n = (t.cpu().numpy() for t in state.update(torch.from_numpy(dets).cuda(), torch.from_numpy(counts).cuda(), [0, n_frames]))
-            res = [[f + 1, ids[f, k], r[1], r[0], r[3] - r[1], r[2] - r[0]] for f in range(n_frames) for k, r in enumerate(rows[f, :n[f]])]
-            ev.add_sequence(name, gt, np.asarray(res, np.float64).reshape(-1, 6))
-        lines += [label, '  ' + mm.line('COMBINED', ev.result()['combined'])]
-        print('\n'.join(lines[-2:]), flush=True)
+        lines.append(label)
+        for how, opts in (('greedy', {}), ('lap', dict(assign='lap')), ('lap + fuse', dict(assign='lap', fuse_score=True))):
+            rng, ev, cap, n_frames = np.random.default_rng(0), mg.MotEvaluator(), 64, 120      # (the same detections for every row)
+            for name, gt, _ in mm.synthetic_sequences(8, n_frames, 10, seed=7):
+                dets, counts = detections(gt, n_frames, rng, miss, clutter, cap)
+                state = engine.TrackState(1, 1, **opts)
+                rows, ids, n = (t.cpu().numpy() for t in state.update(torch.from_numpy(dets).cuda(), torch.from_numpy(counts).cuda(), [0, n_frames]))
+                res = [[f + 1, ids[f, k], r[1], r[0], r[3] - r[1], r[2] - r[0]] for f in range(n_frames) for k, r in enumerate(rows[f, :n[f]])]
+                ev.add_sequence(name, gt, np.asarray(res, np.float64).reshape(-1, 6))
+            lines.append(f'  {how + ":":12s}' + mm.line('COMBINED', ev.result()['combined']))
+            print('\n'.join(lines[-2 if how == 'greedy' else -1:]), flush=True)
     Path(a.out).write_text('\n'.join(lines) + '\n')
 
 
