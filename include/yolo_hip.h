@@ -637,7 +637,7 @@ int yk_boxes_to_labels_f32(const yk_label_cfg_t *cfg, const double *d_boxes, int
  *   cost      (Z_j + L0(q_c)) - L1(q_c) + iou_weight (-log(IoU + 1e-8)) + 1e5 unless both of the above hold, q_k = sqrt(s(tc_k) s(to)),
  *             Z_j = sum_k -L0(q_k) with k ascending, L0 / L1 the binary cross-entropy's two logarithms clamped at -100
  *   k_g       min(E_g, max(1, floor(S))), S the sum of the min(topk, E_g) largest eligible IoUs added from the largest down
- * all in float64, contraction off, in simota.py's operation order; the owner writes (float)clip(x y w h, 1e-8, 1), 1 and the class bit into
+ * all in float64, contraction off, in simota.py's operation order; the owner writes (float)fmin(fmax(x y w h, 1e-8), 1) (a NaN w or h: 1e-8), 1 and the class bit into
  * slot j, every other element of d_labels is written 0.  d_npos [n]: the slots written per image.  *d_status: INT32_MAX, or the smallest
  * row of d_boxes of which nothing was written (an invalid box, or the first row past max_boxes of an image).  Held to simota.assign decision
  * for decision wherever that function's margin exceeds the few ulps by which exp, log and log1p differ between the host's libm and the device.

@@ -21,7 +21,9 @@
 //   ota_write    one workgroup per image.  Owners by integer atomicMin on the cost key per contested candidate, then on g among the
 //                boxes that hold that key; the winners write their slots (no two share one) and the count goes to d_npos.
 // There is no contraction in this problem once Z_j is factored out of the class cost, so no matrix instruction is used.
-// Nothing is trusted: d_first is clamped to [0, n_boxes), an invalid box writes nothing, every candidate index comes from a loop bound.
+// Nothing is trusted: an image's rows are max(d_first[s], 0) .. min(d_first[s + 1], n_boxes) - 1, none where that is empty (a descending pair, a
+// start past the end), an invalid box writes nothing, every candidate index comes from a loop bound.  x y w h are clipped with fmax / fmin:
+// a NaN width or height becomes 1e-8 (validity looks at the class and the centre only), as simota.py states it.
 #include "yk_common.h"
 
 #pragma clang fp contract(off)

@@ -4,7 +4,9 @@ Restated from the YOLOX paper (Ge et al. 2021, section 2.2 "SimOTA") and adapted
 code base is not pinned.  Which predictions train on which box is decided per step from the predictions themselves:
 
   candidates  of an image: every (layer, row, col, anchor), numbered j in the flat order of the label buffer (layer, row, col, anchor).
-  boxes       of an image: its rows (cls, x, y, w, h), g in row order; x y w h clipped to [1e-8, 1] (Helper.box_to_label's clip).
+  boxes       of an image: its rows (cls, x, y, w, h), g in row order; x y w h clipped as min(max(v, 1e-8), 1) with C's fmax / fmin, which
+              return the other operand for a NaN: a NaN goes to 1e-8 (the kernel's and yk_boxes_to_labels_f32's clip; validity does not
+              look at w and h).
   validity    yk_boxes_to_labels_f32's test: the class truncated toward zero in [0, C), the centre finite, floor(x W) in [0, W) and
               floor(y H) in [0, H) in EVERY layer (on the unclipped centre); here also: the box is among the first `max_boxes` of its image.
               Nothing is written for an invalid box; status is the smallest such row of `boxes`, INT32_MAX for a clean batch.
@@ -36,6 +38,11 @@ import numpy as np
 
 STATUS_CLEAN = 2 ** 31 - 1
 PENALTY = 1e5
+
+
+def _clip(v):
+    """min(max(v, 1e-8), 1) as C's fmax / fmin compute it: a NaN goes to 1e-8."""
+    return np.fmin(np.fmax(np.asarray(v, np.float64), 1e-8), 1.0)
 
 
 def grids(helper_or_cfg):
@@ -74,9 +81,13 @@ def _l1(q):
 
 
 def assign(preds: Sequence[np.ndarray], boxes, first, helper_or_cfg, topk: int = 10, radius: float = 2.5, iou_weight: float = 3.0,
-           max_boxes=None):
+           max_boxes=None, detail=None):
     """-> (labels per layer [n, h, w, A, 5 + C] float32, npos [n] int32, status, margin).  preds: the raw outputs per layer,
-    [n, h, w, A, 5 + C] float32; boxes [N, 5] float64 rows (cls, x, y, w, h); first [n + 1]: image s owns rows first[s] .. first[s + 1] - 1."""
+    [n, h, w, A, 5 + C] float32; boxes [N, 5] float64 rows (cls, x, y, w, h); first [n + 1]: image s owns rows first[s] .. first[s + 1] - 1.
+    detail: a list that receives one dict per valid box, in (image, row) order, of what the rule did: image, g (the row of `boxes`), E, S, k,
+    el / iou / cost (every eligible j ascending, its IoU and its cost), j (the k chosen, in the order taken) with cost, in_box and in_ctr
+    beside it, and per chosen j rivals (the other rows that chose it, ascending; empty: uncontested) and owner (the row that got it).
+    It changes no result."""
     out_hw, anchors, C = grids(helper_or_cfg)
     boxes, first = np.asarray(boxes, np.float64).reshape(-1, 5), np.asarray(first, np.int64).reshape(-1)
     n = len(first) - 1
@@ -94,7 +105,7 @@ def assign(preds: Sequence[np.ndarray], boxes, first, helper_or_cfg, topk: int =
             Z = np.zeros(len(q))
             for k in range(C):                                      # k ascending
                 Z = Z + terms[:, k]
-        chosen = {}                                                 # j -> [(cost, g)]
+        chosen, records = {}, {}                                    # j -> [(cost, g)]; g -> its record
         for g in range(b0, b1):
             cls, x0, y0 = boxes[g, 0], boxes[g, 1], boxes[g, 2]
             ok = cls > -1.0 and cls < C and np.isfinite(x0) and np.isfinite(y0) and (max_boxes is None or g - b0 < max_boxes)
@@ -104,7 +115,7 @@ def assign(preds: Sequence[np.ndarray], boxes, first, helper_or_cfg, topk: int =
                 status = min(status, g)
                 continue
             c = int(cls)
-            x, y, w, h = np.clip(boxes[g, 1:], 1e-8, 1.0)
+            x, y, w, h = _clip(boxes[g, 1:])
             dx, dy = np.abs(px - x), np.abs(py - y)
             in_box, in_ctr = (dx < w / 2) & (dy < h / 2), (dx < radius / gw) & (dy < radius / gh)
             el = np.nonzero(in_box | in_ctr)[0]
@@ -129,18 +140,28 @@ def assign(preds: Sequence[np.ndarray], boxes, first, helper_or_cfg, topk: int =
                 margin = min(margin, float(cost[order[k]] - cost[order[k - 1]]))
             for o in order[:k]:
                 chosen.setdefault(int(el[o]), []).append((float(cost[o]), g))
+            if detail is not None:
+                took = order[:k]
+                records[g] = dict(image=s, g=g, E=len(el), S=S, k=k, el=el.copy(), iou=iou.copy(), cost=cost.copy(), j=[int(v) for v in el[took]],
+                                  j_cost=[float(v) for v in cost[took]], in_box=[bool(v) for v in in_box[el[took]]],
+                                  in_ctr=[bool(v) for v in in_ctr[el[took]]])
+                detail.append(records[g])
         for j, takers in chosen.items():
             takers.sort()                                           # smallest cost, ties to the lower g
             for (c0, g0), (c1, g1) in zip(takers, takers[1:]):
                 if not np.array_equal(boxes[g0], boxes[g1]):
                     margin = min(margin, c1 - c0)
             g = takers[0][1]
+            for _, g0 in takers if detail is not None else ():
+                rec = records[g0]
+                rec.setdefault('rivals', {})[j] = sorted(g1 for _, g1 in takers if g1 != g0)
+                rec.setdefault('owner', {})[j] = g
             l = 0
             while j >= sizes[l]:
                 j -= sizes[l]
                 l += 1
             slot = labels[l][s].reshape(-1, 5 + C)[j]
-            slot[:4] = np.clip(boxes[g, 1:], 1e-8, 1.0).astype(np.float32)
+            slot[:4] = _clip(boxes[g, 1:]).astype(np.float32)
             slot[4] = 1.0
             slot[5 + int(boxes[g, 0])] = 1.0
             npos[s] += 1
