@@ -62,6 +62,8 @@
 #                    a sequence; rows get ids that last across frames on the GPU (ByteTrack restated, k210_yolo_framework_amd/track.py), the labels
 #                    show them, and OUTDIR/tracks/<sequence>.txt holds them in the MOTChallenge text format; TRACKASSIGN=lap associates optimally
 #                    (the Hungarian assignment ByteTrack makes) instead of greedily, TRACKFUSE=True is its fuse_score
+#                    [TRACKGMC=True GMCSCALE=4 GMCBLOCK=16 GMCRANGE=8 GMCSTEP=16 GMCTEXTURE=16] with TRACK=True: camera-motion compensation - the
+#                    picture's translation between frames from block matching on the GPU (k210_yolo_framework_amd/gmc.py), applied to the tracks
 #   make trackeval   GT=folder RES=folder | SYNTHETIC=N [SEQFRAMES=60 SEQOBJECTS=8 SEED=0]: HOTA, MOTA and IDF1 (and DetA, AssA, LocA, MOTP, IDSW,
 #                    Frag, MT/PT/ML) of tracks files against ground truth, one line per sequence and a COMBINED line, trackeval.json beside RES.
 #                    GT and RES hold <sequence>.txt in the MOTChallenge text format (what `make detect TRACK=True` writes under OUTDIR/tracks);
@@ -179,6 +181,12 @@ TRACKBUFFER   ?= 30
 TRACKMAX      ?= 256
 TRACKASSIGN   ?= greedy
 TRACKFUSE     ?= False
+TRACKGMC      ?= False
+GMCSCALE      ?= 4
+GMCBLOCK      ?= 16
+GMCRANGE      ?= 8
+GMCSTEP       ?= 16
+GMCTEXTURE    ?= 16
 # trackeval only
 GT            ?=
 RES           ?=
@@ -219,6 +227,7 @@ NMS_ARGS   = $(if $(filter-out hard,$(NMS)),--nms $(NMS) --nms_sigma $(NMSSIGMA)
 TILE_ARGS  = $(if $(TILES),--tiles $(TILES) --tile_overlap $(TILEOVERLAP) --tile_full $(TILEFULL) --tile_match $(TILEMATCH) --tile_thresh $(TILETHRESH))
 TTA_ARGS   = $(if $(TTA),--tta $(TTA) --tta_thresh $(TTATHRESH))
 TRACK_ARGS = $(if $(filter True,$(TRACK)),--track True --track_thresh $(TRACKTHRESH) --track_low $(TRACKLOW) --track_match $(TRACKMATCH) --track_buffer $(TRACKBUFFER) --track_max $(TRACKMAX)$(if $(filter-out greedy,$(TRACKASSIGN)), --track_assign $(TRACKASSIGN))$(if $(filter True,$(TRACKFUSE)), --track_fuse True))
+GMC_ARGS = $(if $(filter True,$(TRACKGMC)),--track_gmc True --gmc_scale $(GMCSCALE) --gmc_block $(GMCBLOCK) --gmc_range $(GMCRANGE) --gmc_step $(GMCSTEP) --gmc_texture $(GMCTEXTURE))
 TRAIN_ARGS = --pre_ckpt $(CKPT) --augmenter $(IAA) --batch_size $(BATCH) --rand_seed 3 --max_nrof_epochs $(MAXEP) \
              --init_learning_rate $(ILR) --learning_rate_decay_factor $(LRDECAYFACTOR) --obj_weight $(OBJWEIGHT) \
              --noobj_weight $(NOOBJWEIGHT) --wh_weight $(WHWEIGHT) --vaildation_split $(SPLITFACTOR) --log_dir log \
@@ -277,7 +286,7 @@ eval:
 
 # every picture of SRC (a folder or a text list) -> OUTDIR/detections.json + OUTDIR/<stem>_res.jpg; batches of BATCH pictures of any sizes
 detect:
-	$(PY) keras_detect.py $(CKPT) $(SRC) --out_dir $(OUTDIR) --draw $(DRAW) --decode $(DECODE) --encode $(ENCODE) --quality $(QUALITY) --batch $(BATCH) --precision $(PRECISION) $(NET_ARGS) $(NMS_ARGS) $(TILE_ARGS) $(TTA_ARGS) $(TRACK_ARGS)
+	$(PY) keras_detect.py $(CKPT) $(SRC) --out_dir $(OUTDIR) --draw $(DRAW) --decode $(DECODE) --encode $(ENCODE) --quality $(QUALITY) --batch $(BATCH) --precision $(PRECISION) $(NET_ARGS) $(NMS_ARGS) $(TILE_ARGS) $(TTA_ARGS) $(TRACK_ARGS) $(GMC_ARGS)
 
 # scores of RES/<sequence>.txt against GT/<sequence>.txt (or GT/<sequence>/gt/gt.txt), or of SYNTHETIC=N generated sequences
 trackeval:

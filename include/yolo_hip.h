@@ -362,6 +362,14 @@ int yk_track_update_ex(void *d_state, int n_seq, int max_tracks, const float *d_
                        int assign /* YK_TRACK_ASSIGN_* */, int fuse_score /* 0 or 1 */,
                        float *d_out, int32_t *d_out_ids, int32_t *d_out_counts, float *d_draw /* may be NULL */, void *stream);
 int yk_track_read(const void *d_state, int n_seq, int max_tracks, int32_t *h_live, int32_t *h_next_id, int32_t *h_overflow);
+/* yk_track_update_ex with camera-motion compensation (track.py's step 0): d_motion [n_frames][2] float32, (mx, my) per frame as
+ * yk_gmc_motion_u8 leaves them.  Before a frame's predict step the centre (cx, cy) of every track of its sequence, live or lost, moves by
+ * the frame's (mx, my), one float32 add each; velocities and covariances stay.  Everything after is yk_track_update_ex, and with d_motion
+ * NULL it IS yk_track_update_ex: the same kernel without the adds, the same bytes. */
+int yk_track_update_gmc(void *d_state, int n_seq, int max_tracks, const float *d_dets, const int32_t *d_counts, int cap,
+                        const int32_t *d_seq_first, int n_frames, int class_num, const yk_track_cfg_t *cfg,
+                        int assign /* YK_TRACK_ASSIGN_* */, int fuse_score /* 0 or 1 */, const float *d_motion /* [n_frames][2]; may be NULL */,
+                        float *d_out, int32_t *d_out_ids, int32_t *d_out_counts, float *d_draw /* may be NULL */, void *stream);
 
 /* ---- linear assignment: what the tracking scores (HOTA, CLEAR-MOT, identity) rest on (k210_yolo_framework_amd/motmetrics.py states the
  * rule).  yk_lap_f64 solves n_problems rectangular minimum-cost assignment problems in one launch.  h_table, HOST memory,
@@ -514,6 +522,40 @@ int yk_letterbox_ragged_params(yk_ragged_row_t *h_table, int n, int dst_h, int d
  * zeros and nothing of d_src is read for it.  Can be recorded in a graph. */
 int yk_letterbox_ragged_u8(const uint8_t *d_src, size_t src_bytes, const yk_ragged_row_t *d_table, int n, uint8_t *d_dst, int dst_h,
                            int dst_w, void *stream);
+/* ---- camera-motion compensation: the translation of the picture between consecutive frames of a sequence, from block matching
+ * (k210_yolo_framework_amd/gmc.py states the rule - this project's own, integers only).  yk_gmc_motion_u8 reads the n_frames
+ * pictures of a ragged batch (d_buf, src_bytes and d_table as yk_letterbox_ragged_u8 and yk_draw_dets_u8 take them; d_buf 4-byte aligned)
+ * whose frames belong to sequences by d_seq_first [n_seq + 1] exactly as yk_track_update reads it, and writes d_motion [n_frames][2]
+ * float32: (mx, my) in source pixels, exact integers - where the content of frame i went against the frame before it in its sequence.
+ * Per picture: grey (77 R + 150 G + 29 B + 128) >> 8, shrunk by `scale` = f to h / f x w / f by the rounded average of f x f cells;
+ * block x block = B x B blocks of the PREVIOUS small picture at (R + i S, R + j S) wherever the block and its +-R window fit, R = range,
+ * S = step; per block the displacement in [-R, R]^2 of the least sum of absolute differences against the current small picture (ties: the
+ * smallest |dy| + |dx|, then dy, then dx); a block whose own pixels span less than `texture` is dropped; the lower median of the kept
+ * blocks' dx and of their dy, times f.  (0, 0) for: fewer than min_blocks kept blocks (a picture too small for one block is no error), a
+ * frame outside every sequence, a frame whose (h, w) differs from its predecessor's, and a sequence's first frame ever.  The first frame a
+ * sequence has in a call is matched against the last it had in the call before: d_state (yk_gmc_state_bytes(n_seq, max_frames,
+ * max_small_pixels) bytes the caller allocates, yk_gmc_reset empties - a kernel, not a fill) keeps every sequence's last small picture and
+ * holds the call's small pictures and answers; cfg names the same three sizes.  A table row without pixels, outside the buffer or of more
+ * than max_small_pixels small pixels is not read: its frame has motion (0, 0) and so has its successor.
+ * d_blocks, unless NULL: [n_frames][yk_gmc_max_blocks(cfg)][4] int32, (dy, dx, sad, kept) of every block matched, row-major over (i, j);
+ * rows past a frame's blocks, and all rows of a frame without a predecessor, are not written.
+ * Three launches on `stream` (shrink: a thread per small pixel; match: a wavefront per block, v_sad_u8 over an LDS-resident window; median:
+ * a wavefront per frame) and nothing else: no host read, no atomics - two calls give the same bytes - and it can be recorded in a graph.
+ * A NULL pointer other than d_blocks, a cfg value outside its range (block a multiple of 4 in 4 .. YK_GMC_MAX_BLOCK, range 1 ..
+ * YK_GMC_MAX_RANGE, scale 1 .. 64, step >= 1, texture 0 .. 256, min_blocks >= 1), n_frames outside 1 .. cfg->max_frames, or a
+ * max_small_pixels that allows more than YK_GMC_MAX_BLOCKS blocks a frame (refused, never truncated): YK_ERR_ARG, the argument named. */
+#define YK_GMC_MAX_BLOCK 32
+#define YK_GMC_MAX_RANGE 16
+#define YK_GMC_MAX_BLOCKS 8192
+typedef struct {
+    int32_t scale, block, range, step, texture, min_blocks;
+    int32_t n_seq, max_frames, max_small_pixels;   /* the state's sizes, as yk_gmc_state_bytes was given them */
+} yk_gmc_cfg_t;
+int yk_gmc_state_bytes(int n_seq, int max_frames, int max_small_pixels, size_t *bytes);
+int yk_gmc_reset(void *d_state, int n_seq, void *stream);
+int yk_gmc_max_blocks(const yk_gmc_cfg_t *cfg);   /* blocks a frame can have at the most: the stride of d_blocks; negative: an error */
+int yk_gmc_motion_u8(void *d_state, const uint8_t *d_buf, size_t src_bytes, const yk_ragged_row_t *d_table, const int32_t *d_seq_first,
+                     int n_frames, const yk_gmc_cfg_t *cfg, float *d_motion, int32_t *d_blocks /* may be NULL */, void *stream);
 /* ---- sliced inference: tiles of the pictures of a ragged batch as frames (k210_yolo_framework_amd/tiles.py) ------
  * A tile is a sub-rectangle of a packed picture: h rows of w pixels, the first at byte `offset` of the packed buffer, consecutive rows
  * `stride` bytes apart (3 * the parent picture's width; stride == 3*w is a whole picture). */

@@ -295,6 +295,7 @@ __device__ __forceinline__ void lap_stage(const track_lds &L, int M, int lane, u
     }
 }
 
+// motion: NULL, or [n_frames][2] (mx, my) per frame, added to every track's centre before the frame's predict step.
 // grid (n_seq), one wavefront; dynamic LDS: 128 bytes per track of M and 24 per row of cap, with ASSIGN = lap 28 and 32 more.
 // ASSIGN (YK_TRACK_ASSIGN_*) and FUSE (stage 1's similarity is IoU * score) are compile-time: <GREEDY, false> is the kernel of before.
 template <int ASSIGN, bool FUSE>
@@ -303,7 +304,7 @@ __global__ void __launch_bounds__(64) track_update_kernel(int32_t *__restrict__ 
                                                           int n_frames, int class_num, float track_thresh, float low_thresh, float stage1,
                                                           float open_thresh, int track_buffer, float *__restrict__ out,
                                                           int32_t *__restrict__ out_ids, int32_t *__restrict__ out_counts,
-                                                          float *__restrict__ draw) {
+                                                          float *__restrict__ draw, const float *__restrict__ motion) {
     extern __shared__ float4 lds_raw[];
     track_lds L;
     L.Pbox = lds_raw;
@@ -342,8 +343,14 @@ __global__ void __launch_bounds__(64) track_update_kernel(int32_t *__restrict__ 
     const int f0 = min(max(seq_first[s], 0), n_frames), f1 = min(max(seq_first[s + 1], 0), n_frames);
     for (int f = f0; f < f1; ++f) {
         ++frame;
+        // 0  camera-motion compensation (yk_track_update_gmc): every centre moves by the frame's (mx, my); v and P stay
+        const float mx = motion ? motion[2 * (size_t)f] : 0.f, my = motion ? motion[2 * (size_t)f + 1] : 0.f;
         // 1  predict
         for (int i = lane; i < n_live; i += 64) {
+            if (motion) {
+                TF(1, i) = TF(1, i) + mx;
+                TF(2, i) = TF(2, i) + my;
+            }
             if (TI(2, i) == T_LOST) TF(8, i) = 0.f;
             float qp, qv;
             noise(TF(4, i), 1.f, 1.f, qp, qv);
@@ -589,9 +596,10 @@ extern "C" int yk_track_max_cap(int max_tracks) { return track_max_cap("yk_track
 
 extern "C" int yk_track_max_cap_ex(int max_tracks, int assign) { return track_max_cap("yk_track_max_cap_ex", max_tracks, assign); }
 
-extern "C" int yk_track_update_ex(void *d_state, int n_seq, int max_tracks, const float *d_dets, const int32_t *d_counts, int cap,
-                                  const int32_t *d_seq_first, int n_frames, int class_num, const yk_track_cfg_t *cfg, int assign,
-                                  int fuse_score, float *d_out, int32_t *d_out_ids, int32_t *d_out_counts, float *d_draw, void *stream) {
+extern "C" int yk_track_update_gmc(void *d_state, int n_seq, int max_tracks, const float *d_dets, const int32_t *d_counts, int cap,
+                                   const int32_t *d_seq_first, int n_frames, int class_num, const yk_track_cfg_t *cfg, int assign,
+                                   int fuse_score, const float *d_motion, float *d_out, int32_t *d_out_ids, int32_t *d_out_counts, float *d_draw,
+                                   void *stream) {
 #define R(cond, ...) YK_TRACK_REFUSE("yk_track_update", cond, __VA_ARGS__)
     R(!d_state, "d_state is NULL")
     YK_TRACK_STATE_ARGS("yk_track_update")
@@ -622,7 +630,7 @@ extern "C" int yk_track_update_ex(void *d_state, int n_seq, int max_tracks, cons
     auto go = [&](auto kern) {
         yk_launch_lds(kern, dim3((unsigned)n_seq), dim3(64), lds, (hipStream_t)stream, (int32_t *)d_state, max_tracks, d_dets, d_counts, cap,
                       d_seq_first, n_frames, class_num, cfg->track_thresh, cfg->low_thresh, 1.f - cfg->match_thresh, cfg->track_thresh + 0.1f,
-                      cfg->track_buffer, d_out, d_out_ids, d_out_counts, d_draw);
+                      cfg->track_buffer, d_out, d_out_ids, d_out_counts, d_draw, d_motion);
     };
     if (assign == YK_TRACK_ASSIGN_LAP) {
         if (fuse_score) go(track_update_kernel<YK_TRACK_ASSIGN_LAP, true>);
@@ -633,6 +641,13 @@ extern "C" int yk_track_update_ex(void *d_state, int n_seq, int max_tracks, cons
     }
     YK_HIP(hipGetLastError());
     return YK_OK;
+}
+
+extern "C" int yk_track_update_ex(void *d_state, int n_seq, int max_tracks, const float *d_dets, const int32_t *d_counts, int cap,
+                                  const int32_t *d_seq_first, int n_frames, int class_num, const yk_track_cfg_t *cfg, int assign,
+                                  int fuse_score, float *d_out, int32_t *d_out_ids, int32_t *d_out_counts, float *d_draw, void *stream) {
+    return yk_track_update_gmc(d_state, n_seq, max_tracks, d_dets, d_counts, cap, d_seq_first, n_frames, class_num, cfg, assign, fuse_score, nullptr,
+                               d_out, d_out_ids, d_out_counts, d_draw, stream);
 }
 
 extern "C" int yk_track_update(void *d_state, int n_seq, int max_tracks, const float *d_dets, const int32_t *d_counts, int cap,

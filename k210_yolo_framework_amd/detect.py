@@ -4,6 +4,7 @@
                            [--tiles NXxNY --tile_overlap 0.2 --tile_full True --tile_match ios|iou --tile_thresh 0.5]
                            [--tta 1,1f|flip|v5 --tta_thresh 0.55]
                            [--track True --track_thresh 0.5 --track_low 0.1 --track_match 0.8 --track_buffer 30 --track_max 256 --track_assign greedy --track_fuse False]
+                           [--track_gmc True --gmc_scale 4 --gmc_block 16 --gmc_range 8 --gmc_step 16 --gmc_texture 16]
                            [network and threshold flags of keras_inference.py]
 
 SRC: a folder (its .jpg / .jpeg / .png / .bmp files, in sorted order), a text file with one picture path per line, or one picture.
@@ -31,6 +32,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import draw as dr
+from . import gmc as gm
 from . import jpeg
 from . import softnms
 from . import tiles as tl
@@ -71,6 +73,7 @@ def parse(argv=None):
     tl.add_arguments(p)
     tt.add_arguments(p)
     tk.add_arguments(p)
+    gm.add_arguments(p)
     a = p.parse_args(sys.argv[1:] if argv is None else argv)
     if (a.precision == 'kpu') != a.pre_ckpt.endswith(('.kmodel', '.kfpkg')):
         p.error('--precision kpu runs a .kmodel / .kfpkg checkpoint, and only it does (the float modes take .h5 / .npz)')
@@ -86,6 +89,7 @@ def parse(argv=None):
         tl.parse_arguments(a)
         tt.parse_arguments(a)
         tk.parse_arguments(a)
+        gm.parse_arguments(a)
     except ValueError as e:
         p.error(str(e))
     if a.tta is not None and len(a.tta) > a.batch:
@@ -154,6 +158,7 @@ class _Stage:
         self.d_stage = self.d_jwork = self.d_jstatus = self.h_jstatus = None           # decode='gpu'
         self.d_mdets = self.d_mcounts = None                                            # tiles, tta: the merged / fused rows per picture
         self.d_track = self.h_ids = None                                                # track: (rows, ids, counts, rows for the draw)
+        self.d_motion = self.h_motion = None                                            # gmc: (mx, my) per picture
 
 
 def sequences_of(sources, in_memory: bool):
@@ -178,12 +183,26 @@ def sequences_of(sources, in_memory: bool):
     return np.asarray(index, np.int64), names
 
 
+def picture_sizes(sources) -> List[tuple]:
+    """(h, w) per source - an array's shape, or a file's or a byte string's size as its header states it (nothing is decoded)."""
+    from PIL import Image
+    out = []
+    for s in sources:
+        if isinstance(s, np.ndarray):
+            out.append((int(s.shape[0]), int(s.shape[1])))
+        else:
+            with Image.open(io.BytesIO(s) if isinstance(s, bytes) else str(s)) as im:
+                out.append((int(im.size[1]), int(im.size[0])))
+    return out
+
+
 def run(h: Helper, model, sources, out_dir=None, draw: bool = True, batch: int = 32, depth: int = 4, precision: str = 'f16x2',
         obj_thresh: float = 0.7, iou_thresh: float = 0.3, workers: int = 8, names: Optional[Sequence[str]] = None,
         return_arrays: bool = False, verbose: bool = True, max_out: int = 30, encode: str = 'pil', quality: int = 75, decode: str = 'pil',
         nms: str = 'hard', nms_sigma: float = 0.5, tiles=None, tile_overlap: float = 0.2, tile_full: bool = True, tile_match: str = 'ios',
         tile_thresh: float = 0.5, tta=None, tta_thresh: float = 0.55, track: bool = False, track_thresh: float = 0.5, track_low: float = 0.1,
-        track_match: float = 0.8, track_buffer: int = 30, track_max: int = 256, track_assign: str = 'greedy', track_fuse: bool = False):
+        track_match: float = 0.8, track_buffer: int = 30, track_max: int = 256, track_assign: str = 'greedy', track_fuse: bool = False,
+        gmc: bool = False, gmc_scale: int = 4, gmc_block: int = 16, gmc_range: int = 8, gmc_step: int = 16, gmc_texture: int = 16):
     """sources: picture paths, or [h, w, 3] uint8 arrays already in memory (then `names` names them); with decode='gpu' paths or the bytes of
     picture files: baseline JPEGs are decoded on the device by the rule of include/yolo_hip.h (not PIL's bytes: DESIGN.md 3.12), every other
     file by PIL on the pool as with decode='pil'; a stream the device cannot finish raises YkError naming the file.  -> {'names', 'detections': one
@@ -206,7 +225,13 @@ def run(h: Helper, model, sources, out_dir=None, draw: bool = True, batch: int =
     that needed more than track_max tracks raises YkError naming it at the end of the run.  track_assign='lap': the optimal association per
     stage and class instead of the greedy one; track_fuse=True: the first association compares IoU * score (both: track.py's header); either
     is named in detections.json, and a frame of more rows than engine.track_max_cap(track_max, 'lap') is refused by name.  False (the
-    default): everything as without it."""
+    default): everything as without it.
+    gmc=True (with track=True; gmc.py): camera-motion compensation - yk_gmc_motion_u8 estimates every frame's translation
+    against the frame before it in its sequence from the still-resident originals (before the draw paints into them, so draw=False changes
+    nothing), and the tracker moves its tracks by it before predicting (yk_track_update_gmc); gmc_scale, gmc_block, gmc_range, gmc_step and
+    gmc_texture are the rule's parameters.  The result gains 'motion' ([mx, my] per picture), detections.json names the option and carries a
+    `motion` list per sequence, and a frame whose size differs from its predecessor's is named in one printed line (its motion is 0).  The
+    pictures' sizes are read from their headers before the run, to size the state.  gmc without track is refused."""
     import torch
     from . import engine
     engine.require_gpu()
@@ -239,6 +264,13 @@ def run(h: Helper, model, sources, out_dir=None, draw: bool = True, batch: int =
             track_cfg = tk.check(track_thresh, track_low, track_match, track_buffer, track_max, nms, tiles, tta, track_assign, track_fuse)
         except ValueError as e:
             raise engine.YkError(f'detect: {e}') from None
+    if gmc:
+        if not track:
+            raise engine.YkError('detect: gmc without track: the compensation moves the tracker\'s tracks; add track=True (make detect TRACK=True)')
+        try:
+            gmc_cfg = gm.check(gmc_scale, gmc_block, gmc_range, gmc_step, gmc_texture)
+        except ValueError as e:
+            raise engine.YkError(f'detect: {e}') from None
     gpu_decode = decode == 'gpu'
     in_memory = isinstance(sources[0], (np.ndarray, bytes))
     if gpu_decode and any(isinstance(s, np.ndarray) for s in sources):
@@ -264,6 +296,15 @@ def run(h: Helper, model, sources, out_dir=None, draw: bool = True, batch: int =
         if track_assign != 'greedy' and cap > tracks.max_cap:
             raise engine.YkError(f'detect: track_assign {track_assign}: a frame has up to {cap} rows and beside track_max {int(track_max)} tracks the '
                                  f'device holds {tracks.max_cap} (engine.track_max_cap); lower track_max')
+        if gmc:
+            sizes = picture_sizes(sources)
+            gmc_state = engine.GmcState(len(seq_names), B, max((sh // gmc_cfg['scale']) * (sw // gmc_cfg['scale']) for sh, sw in sizes) or 1,
+                                        **gmc_cfg)
+            motions = np.zeros((n_all, 2), np.float32)
+            for i in range(1, n_all):
+                if seq_of[i] == seq_of[i - 1] and sizes[i] != sizes[i - 1] and verbose:
+                    print(NOTE, f' {names[i]}: {sizes[i][0]} x {sizes[i][1]}, its predecessor {sizes[i - 1][0]} x {sizes[i - 1][1]}: no camera motion '
+                                f'is estimated across a change of size (gmc.py)')
         if verbose and obj_thresh > track_low:
             print(NOTE, f' obj_thresh {obj_thresh:g} is above track_low {track_low:g}: the decode drops the rows between the two, and the second '
                         f'association sees nothing there')
@@ -348,13 +389,23 @@ def run(h: Helper, model, sources, out_dir=None, draw: bool = True, batch: int =
                 st.d_track = (torch.zeros((B, cap, 6), dtype=torch.float32, device=dev), torch.zeros((B, cap), dtype=torch.int32, device=dev),
                               torch.zeros((B,), dtype=torch.int32, device=dev), torch.zeros((B, cap, 6), dtype=torch.float32, device=dev))
                 st.h_ids = torch.empty((B, cap), dtype=torch.int32).pin_memory()
+                if gmc:
+                    st.d_motion = torch.zeros((B, 2), dtype=torch.float32, device=dev)
+                    st.h_motion = torch.empty((B, 2), dtype=torch.float32).pin_memory()
                 torch.cuda.current_stream().synchronize()   # (filled on torch's stream, written on the slot's)
             dets, counts, *rest = late
             seq_first = np.searchsorted(seq_of[first:first + n], np.arange(len(seq_names) + 1))
-            rows, ids, tcounts, for_draw = tracks.update(dets, counts, seq_first, stream=stream, draw=True, out=tuple(t[:n] for t in st.d_track))
+            motion = None
+            if gmc:                                         # from the originals, before the draw paints into them
+                motion = engine.gmc_motion(gmc_state, rest[0], rest[1], seq_first, stream=stream, out=st.d_motion[:n])
+                copy(st.h_motion, motion, n * 2 * 4, stream)
+            rows, ids, tcounts, for_draw = tracks.update(dets, counts, seq_first, stream=stream, draw=True, out=tuple(t[:n] for t in st.d_track),
+                                                         motion=motion)
             finish(st, n, rows, tcounts, for_draw, *rest, stream)
             copy(st.h_ids, ids, n * cap * 4, stream)
             stream.synchronize()
+            if gmc:
+                motions[first:first + n] = st.h_motion[:n].numpy()
         if gpu_decode and keep[1]:
             for j, code in zip(keep[1], st.h_jstatus[:len(keep[1])].numpy().tolist()):
                 if code:
@@ -540,8 +591,14 @@ def run(h: Helper, model, sources, out_dir=None, draw: bool = True, batch: int =
         doc = [{'path': names[i], **rule, 'detections': [[float(v) for v in row] for row in results[i]]} for i in range(n_all)]
         if track:                                            # a row is a track's row with its id: [top, left, bottom, right, score, class, track_id]
             rule.update(tracker=f'bytetrack-{track_assign}', **track_cfg, track_max=int(track_max))
+            if gmc:                                          # every entry names the option; a sequence's first entry carries its motions
+                rule.update(gmc={f'gmc_{k}': v for k, v in gmc_cfg.items()})
             doc = [{'path': names[i], **rule, 'sequence': seq_names[seq_of[i]],
                     'detections': [[*(float(v) for v in row), int(t)] for row, t in zip(results[i], track_ids[i])]} for i in range(n_all)]
+            if gmc:
+                for s in range(len(seq_names)):
+                    mine = np.flatnonzero(seq_of == s)
+                    doc[mine[0]]['motion'] = [[float(v) for v in motions[i]] for i in mine]
             (Path(out_dir) / 'tracks').mkdir(exist_ok=True)
             for s, seq in enumerate(seq_names):
                 mine = np.flatnonzero(seq_of == s)
@@ -551,6 +608,8 @@ def run(h: Helper, model, sources, out_dir=None, draw: bool = True, batch: int =
     out = {'names': names, 'detections': results, 'files': written}
     if track:
         out.update(track_ids=track_ids, sequences=seq_names)
+        if gmc:
+            out['motion'] = motions
     if arrays is not None:
         out['arrays'] = arrays
     return out
@@ -575,7 +634,7 @@ def main(argv=None):
         raise engine.YkError(f'detect: no pictures ({", ".join(EXTENSIONS)}) in {a.src}')
     res = run(h, model, paths, out_dir=a.out_dir, draw=a.draw, batch=a.batch, depth=a.depth, precision=a.precision,
               obj_thresh=a.obj_thresh, iou_thresh=a.iou_thresh, workers=a.workers, encode=a.encode, quality=a.quality, decode=a.decode,
-              nms=a.nms, nms_sigma=a.nms_sigma, **tl.run_options(a), **tt.run_options(a), **tk.run_options(a))
+              nms=a.nms, nms_sigma=a.nms_sigma, **tl.run_options(a), **tt.run_options(a), **tk.run_options(a), **gm.run_options(a))
     if a.nms != 'hard':
         print(INFO, f' nms {a.nms}, sigma {a.nms_sigma:g}: scores are the decayed ones')
     if a.tiles is not None:
@@ -586,6 +645,10 @@ def main(argv=None):
         print(INFO, f' track: {len(res["sequences"])} sequences, ids up to {max([int(t.max()) for t in res["track_ids"] if len(t)], default=0)} '
                     f'(track.py: ByteTrack restated, class-aware and {"greedy" if a.track_assign == "greedy" else "optimal (lap)"}'
                     f'{", fuse_score" if a.track_fuse else ""}) -> {Path(a.out_dir) / "tracks"}')
+    if a.track_gmc:
+        moved = int((res['motion'] != 0).any(1).sum())
+        print(INFO, f' gmc: camera translation from block matching at 1/{a.gmc_scale} (gmc.py: this project\'s rule, translation only, no box mask); '
+                    f'{moved} of {len(paths)} frames moved')
     print(INFO, f' {len(paths)} pictures, {sum(len(d) for d in res["detections"])} detections -> {Path(a.out_dir) / "detections.json"}'
           + (f', {len(res["files"])} annotated pictures' if a.draw else ''))
     return res

@@ -881,11 +881,13 @@ class TrackState:
         """Every sequence back to no tracks, next id 1, no frames seen."""
         call('yk_track_reset', self.state, self.n_seq, self.max_tracks, _stream(stream))
 
-    def update(self, dets, counts, seq_first, stream=None, draw: bool = False, out=None):
+    def update(self, dets, counts, seq_first, stream=None, draw: bool = False, out=None, motion=None):
         """dets cuda fp32 [n_frames, cap, 6] and counts cuda int32 [n_frames] as decode_py / Pipeline.submit leave them; seq_first a host
         table [n_seq + 1] (the frames of sequence s are seq_first[s] .. seq_first[s+1] - 1, ascending from 0 to n_frames) or that table on
         the device as cuda int32.  -> (rows cuda fp32 [n_frames, cap, 6], ids cuda int32 [n_frames, cap], counts cuda int32 [n_frames])
-        and, with draw, the rows with the class column replaced by id mod 100.  out: those tensors, to be written in place."""
+        and, with draw, the rows with the class column replaced by id mod 100.  out: those tensors, to be written in place.
+        motion: cuda fp32 [n_frames, 2] as gmc_motion leaves it - camera-motion compensation (yk_track_update_gmc; track.Tracker(gmc=True)):
+        every track's centre moves by its frame's (mx, my) before the predict step.  None: the call of before."""
         import torch
         assert dets.is_cuda and dets.dtype == torch.float32 and dets.is_contiguous() and dets.dim() == 3 and dets.shape[2] == 6, tuple(dets.shape)
         n_frames, cap = int(dets.shape[0]), int(dets.shape[1])
@@ -909,7 +911,12 @@ class TrackState:
         for t, shape, dt in ((rows, (n_frames, cap, 6), torch.float32), (ids, (n_frames, cap), torch.int32), (out_counts, (n_frames,), torch.int32)) + \
                 (((d_draw, (n_frames, cap, 6), torch.float32),) if draw else ()):
             assert t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == shape, tuple(t.shape)
-        if self.assign == 'greedy' and not self.fuse_score:
+        if motion is not None:
+            assert motion.is_cuda and motion.dtype == torch.float32 and motion.is_contiguous() and tuple(motion.shape) == (n_frames, 2), \
+                tuple(motion.shape)
+            call('yk_track_update_gmc', self.state, self.n_seq, self.max_tracks, dets, counts, cap, seq_first, n_frames, self.class_num,
+                 C.byref(self.cfg), TRACK_ASSIGNS[self.assign], int(self.fuse_score), motion, rows, ids, out_counts, d_draw, _stream(stream))
+        elif self.assign == 'greedy' and not self.fuse_score:
             call('yk_track_update', self.state, self.n_seq, self.max_tracks, dets, counts, cap, seq_first, n_frames, self.class_num,
                  C.byref(self.cfg), rows, ids, out_counts, d_draw, _stream(stream))
         else:
@@ -923,6 +930,78 @@ class TrackState:
         live, next_id, overflow = (np.zeros(self.n_seq, np.int32) for _ in range(3))
         call('yk_track_read', self.state, self.n_seq, self.max_tracks, live, next_id, overflow)
         return live, next_id, overflow
+
+
+class GmcCfg(C.Structure):
+    """yk_gmc_cfg_t"""
+    _fields_ = [(n, C.c_int32) for n in ('scale', 'block', 'range', 'step', 'texture', 'min_blocks', 'n_seq', 'max_frames', 'max_small_pixels')]
+
+
+class GmcState:
+    """What camera-motion compensation keeps on the device for n_seq sequences (yk_gmc_motion_u8; the rule is gmc.py's, exactly): every
+    sequence's last small grey picture, and room for the small pictures and answers of a call of at most max_frames pictures of at most
+    max_small_pixels = (h // scale) * (w // scale) small pixels each.  cfg: scale, block, range, step, texture, min_blocks (gmc.check
+    refuses bad ones by name).  max_blocks: the blocks a frame can have, the stride of `blocks`."""
+
+    def __init__(self, n_seq: int, max_frames: int, max_small_pixels: int, **cfg):
+        import torch
+        from . import gmc
+        require_gpu()
+        try:
+            opts = gmc.check(**cfg)
+        except (ValueError, TypeError) as e:
+            raise YkError(f'GmcState: {e}') from None
+        self.n_seq, self.max_frames, self.max_small_pixels = int(n_seq), int(max_frames), int(max_small_pixels)
+        self.opts = opts
+        self.cfg = GmcCfg(*(opts[k] for k in ('scale', 'block', 'range', 'step', 'texture', 'min_blocks')), self.n_seq, self.max_frames,
+                          self.max_small_pixels)
+        nbytes = C.c_size_t(0)
+        call('yk_gmc_state_bytes', self.n_seq, self.max_frames, self.max_small_pixels, C.byref(nbytes))
+        self.max_blocks = lib().yk_gmc_max_blocks(C.byref(self.cfg))
+        if self.max_blocks < 0:
+            _check(self.max_blocks, 'yk_gmc_max_blocks')
+        self.state = torch.empty(nbytes.value, dtype=torch.uint8, device=torch.device('cuda', torch.cuda.current_device()))
+        self.reset()
+
+    def reset(self, stream=None) -> None:
+        """No sequence has a last picture."""
+        call('yk_gmc_reset', self.state, self.n_seq, _stream(stream))
+
+
+def gmc_motion(state: GmcState, packed, table, seq_first, stream=None, out=None, blocks=None):
+    """The camera's translation per picture of a ragged batch (yk_gmc_motion_u8): `packed` and `table` as for letterbox_ragged_u8 (a host
+    table is checked here: a row without pixels, one that leaves the buffer or one of more small pixels than the state holds is refused);
+    seq_first as TrackState.update takes it.  -> cuda fp32 [n, 2], (mx, my) per picture; `out`: that tensor, written in place.  blocks:
+    cuda int32 [n, state.max_blocks, 4] to receive (dy, dx, sad, kept) of every block matched (rows past a frame's blocks keep what they held)."""
+    import torch
+    require_gpu()
+    if not torch.is_tensor(table):
+        t = check_ragged_rows(table, packed.numel())
+        small = (t['h'] // state.opts['scale']).astype(np.int64) * (t['w'] // state.opts['scale'])
+        if len(t) and small.max() > state.max_small_pixels:
+            i = int(np.argmax(small))
+            raise YkError(f'gmc_motion: ragged table: row {i} is {int(t["h"][i])} x {int(t["w"][i])}, {int(small[i])} small pixels at scale '
+                          f'{state.opts["scale"]}, and the state holds {state.max_small_pixels}')
+    table = _device_table(_RAGGED, packed, table, None, stream)
+    n = int(table.shape[0])
+    if not torch.is_tensor(seq_first):
+        sf = np.asarray(seq_first, np.int64).reshape(-1)
+        if len(sf) != state.n_seq + 1 or sf[0] != 0 or sf[-1] != n or (np.diff(sf) < 0).any():
+            raise YkError(f'gmc_motion: seq_first {sf.tolist()}: expected {state.n_seq + 1} ascending values from 0 to n_frames {n}')
+        with torch.cuda.stream(torch.cuda.current_stream() if stream is None else stream):
+            seq_first = torch.from_numpy(sf.astype(np.int32)).to(packed.device)
+    assert seq_first.is_cuda and seq_first.dtype == torch.int32 and seq_first.is_contiguous() and tuple(seq_first.shape) == (state.n_seq + 1,)
+    if out is None:
+        out = torch.zeros((n, 2), dtype=torch.float32, device=packed.device)
+        if stream is not None:
+            torch.cuda.current_stream().synchronize()                       # (filled on torch's stream, written on `stream`)
+    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (n, 2), tuple(out.shape)
+    if blocks is not None:
+        assert blocks.is_cuda and blocks.dtype == torch.int32 and blocks.is_contiguous() and tuple(blocks.shape) == (n, state.max_blocks, 4), \
+            tuple(blocks.shape)
+    call('yk_gmc_motion_u8', state.state, packed, packed.numel(), table, seq_first, n, C.byref(state.cfg), out, blocks, _stream(stream))
+    state._keep = (seq_first, table)                                        # alive until the launches have read them
+    return out
 
 
 def mosaic_ragged_u8(packed, table, centres, dst_hw, inv=None, stream=None, out=None):

@@ -46,6 +46,9 @@ A row (top, left, bottom, right) is measured as w = right - left, h = bottom - t
 a = w / h; a mean is a box again by w = a * h, hw = w * 0.5, hh = h * 0.5, (cy - hh, cx - hw, cy + hh, cx + hw).
 
 One frame, in this order (frames count from 1 per sequence):
+  0  gmc=True only (camera-motion compensation, gmc.py states how the motion is found): the centre (cx, cy) of every
+     track's mean, live or lost, moves by the frame's motion (mx, my), one float32 add each - always, a motion of (0, 0) included.
+     Velocities and covariances stay: a translation's linear part is the identity, so BoT-SORT's R P R^T leaves P alone.
   1  predict every track; its box is rebuilt from the predicted mean.
   2  rows: dropped unless the class is exactly one of 0 .. class_num - 1, score >= low_thresh (a NaN is dropped), and 0 < h < inf and
      0 < w < inf.  high: score >= track_thresh; low: the others.
@@ -233,8 +236,11 @@ class Tracker:
     """The host form of one sequence: update(rows of a frame) -> (rows [k, 6] float32, ids [k] int32)."""
 
     def __init__(self, class_num: int, track_thresh=0.5, low_thresh=0.1, match_thresh=0.8, track_buffer=30, max_tracks: Optional[int] = None,
-                 assign: str = 'greedy', fuse_score: bool = False):
+                 assign: str = 'greedy', fuse_score: bool = False, gmc: bool = False):
         cfg = check(track_thresh, low_thresh, match_thresh, track_buffer, max_tracks, assign=assign, fuse_score=fuse_score)
+        if not isinstance(gmc, (bool, np.bool_)):
+            raise ValueError(f'track_gmc {gmc!r}: expected True or False')
+        self.gmc = bool(gmc)
         if int(class_num) < 1:
             raise ValueError(f'class_num {class_num!r}: expected at least 1')
         self.class_num, self.max_tracks = int(class_num), max_tracks
@@ -266,8 +272,14 @@ class Tracker:
         r, c = r[ok], c[ok]
         return r[:, :4], r[:, 4], c, r[:, 4] >= self.track_thresh
 
-    def update(self, rows, cap: Optional[int] = None):
+    def update(self, rows, cap: Optional[int] = None, motion=None):
+        if motion is not None and not self.gmc:
+            raise ValueError('motion given to a tracker opened without gmc=True')
         self.frame += 1
+        if self.gmc:                                                      # step 0: the camera's translation moves every centre; v and P stay
+            mx, my = (0, 0) if motion is None else motion
+            self.mean[:, 0] = (self.mean[:, 0] + F(mx)).astype(F)
+            self.mean[:, 1] = (self.mean[:, 1] + F(my)).astype(F)
         lost = self.state == LOST
         self.mean[lost, 7] = F(0)
         self.mean, self.cov = kf_predict(self.mean, self.cov)
