@@ -13,6 +13,8 @@
 //     cost matrix when it fits what is left of the 160 KB; if not it is read from global memory through the same device function - the
 //     switch is a function of the shape alone (yk_lap_resident);
 //   - a problem with more rows than columns is solved transposed by index: c(i, j) = cost[j * cols + i], nothing is copied.
+// The solver itself (yk_lap_wave, its LDS vectors and the wave arg-min) is yk_lap.h, shared with yk_track.hip's assign = lap; this unit
+// gives it costs read from a matrix (lap_matrix_cost).
 // No floating-point atomics (the assignment has no atomics at all; the scores below add integers only), so two calls give the same bytes.  Additions, subtractions and comparisons only: there is
 // no matrix product in it, hence no MFMA.  Compiled with -ffp-contract=off and without packed fp32: one rounding per operation, as
 // motmetrics.lap's float64 steps.
@@ -20,121 +22,19 @@
 #include <vector>
 
 #include "yk_common.h"
+#include "yk_lap.h"
 
-struct lap_lds {
-    double *v, *dist, *u;                 // [n] column duals, [n] tentative distances, [m] row duals
-    int *pred, *row4col, *scanned;        // [n] each
-    int *col4row;                         // [m]
+// a cost read from a matrix, LDS or global (a generic pointer): c[i * si + j * sj] for the wave's row i and column j
+struct lap_matrix_cost {
+    const double *c;
+    long long si, sj;
+    struct row_costs {
+        const double *ci;
+        long long sj;
+        __device__ __forceinline__ double operator()(int j) const { return ci[j * sj]; }
+    };
+    __device__ __forceinline__ row_costs row(int i) const { return {c + i * si, sj}; }
 };
-
-__host__ __device__ static inline size_t lap_vector_bytes(int m, int n) {
-    return (size_t)YK_LAP_LDS_PER_COL * n + (size_t)YK_LAP_LDS_PER_ROW * m;
-}
-
-// does the cost matrix of a rows x cols problem live in LDS beside the vectors?  A function of the shape alone.
-__host__ __device__ static inline bool yk_lap_resident(int rows, int cols) {
-    const int m = rows < cols ? rows : cols, n = rows < cols ? cols : rows;
-    return lap_vector_bytes(m, n) + (size_t)m * n * sizeof(double) <= (size_t)YK_LAP_LDS_BYTES;
-}
-
-__device__ __forceinline__ lap_lds lap_carve(void *base, int m, int n) {
-    lap_lds L;
-    L.v = reinterpret_cast<double *>(base);
-    L.dist = L.v + n;
-    L.u = L.dist + n;
-    L.pred = reinterpret_cast<int *>(L.u + m);
-    L.row4col = L.pred + n;
-    L.scanned = L.row4col + n;
-    L.col4row = L.scanned + n;
-    return L;
-}
-
-// arg-min over (value asc, column asc) across the wave; col < 0 means "no candidate"
-__device__ __forceinline__ void lap_wave_argmin(double &best, int &col) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const double ob = __shfl_xor(best, o, 64);
-        const int oc = __shfl_xor(col, o, 64);
-        if (oc >= 0 && (col < 0 || ob < best || (ob == best && oc < col))) {
-            best = ob;
-            col = oc;
-        }
-    }
-}
-
-// One problem by one wavefront.  c: the cost matrix, LDS or global (a generic pointer), indexed c[i * si + j * sj] for row i of the m the
-// wave augments and column j of the n it searches (m <= n).  Leaves col4row [m] and row4col [n] in L; the caller reads them after it.
-__device__ void yk_lap_wave(const double *c, long long si, long long sj, int m, int n, const lap_lds &L, int lane) {
-    for (int j = lane; j < n; j += 64) {
-        L.v[j] = 0.0;
-        L.row4col[j] = -1;
-    }
-    for (int i = lane; i < m; i += 64) {
-        L.u[i] = 0.0;
-        L.col4row[i] = -1;
-    }
-    __syncthreads();
-    for (int cur = 0; cur < m; ++cur) {
-        for (int j = lane; j < n; j += 64) {
-            L.dist[j] = INFINITY;
-            L.pred[j] = -1;
-            L.scanned[j] = 0;
-        }
-        double minval = 0.0;
-        int i = cur, sink = -1;
-        while (sink < 0) {
-            const double ui = L.u[i];
-            const double *ci = c + i * si;
-            double best = INFINITY;
-            int bcol = -1;
-            for (int j = lane; j < n; j += 64) {
-                if (L.scanned[j]) continue;
-                const double r = ((minval + ci[j * sj]) - ui) - L.v[j];
-                double d = L.dist[j];
-                if (r < d) {
-                    d = r;
-                    L.dist[j] = r;
-                    L.pred[j] = i;
-                }
-                if (bcol < 0 || d < best) {
-                    best = d;
-                    bcol = j;
-                }
-            }
-            lap_wave_argmin(best, bcol);                                 // (an unscanned column exists while no sink was found: m <= n)
-            minval = best;
-            if ((bcol & 63) == lane) L.scanned[bcol] = 1;
-            const int holder = L.row4col[bcol];
-            if (holder < 0) sink = bcol;
-            else i = holder;
-        }
-        __syncthreads();
-        // the duals: every scanned column but the sink is held by a row of its own, so no two lanes write one u
-        for (int j = lane; j < n; j += 64) {
-            if (!L.scanned[j]) continue;
-            const double t = minval - L.dist[j];
-            L.v[j] = L.v[j] - t;
-            if (j != sink) {
-                const int r = L.row4col[j];
-                L.u[r] = L.u[r] + t;
-            }
-        }
-        __syncthreads();
-        if (lane == 0) {
-            L.u[cur] = L.u[cur] + minval;
-            int j = sink;
-            for (;;) {
-                const int r = L.pred[j];
-                L.row4col[j] = r;
-                const int next = L.col4row[r];
-                L.col4row[r] = j;
-                j = next;
-                if (r == cur) break;
-            }
-        }
-        __syncthreads();
-    }
-}
 
 // grid (n_problems), one wavefront; dynamic LDS: the largest problem's vectors and, where it is resident, its matrix
 __global__ void __launch_bounds__(64) lap_kernel(const double *__restrict__ cost, const yk_lap_problem_t *__restrict__ table,
@@ -153,9 +53,9 @@ __global__ void __launch_bounds__(64) lap_kernel(const double *__restrict__ cost
         src = mat;
     }
     // tall: the wave's row i is the problem's column i, its column j the problem's row j
-    yk_lap_wave(src, tall ? 1 : cols, tall ? cols : 1, m, n, L, lane);
+    yk_lap_wave(lap_matrix_cost{src, tall ? 1 : cols, tall ? cols : 1}, m, n, L, lane);
     int32_t *mine = out + p.out_offset;
-    const int *answer = tall ? L.row4col : L.col4row;
+    const int *answer = lap_answer(L, tall);
     for (int r = lane; r < rows; r += 64) mine[r] = answer[r];
 }
 
@@ -344,8 +244,8 @@ __device__ __forceinline__ const int *lap_solve(const double *c, int rows, int c
     const bool tall = rows > cols;
     const int m = tall ? cols : rows, n = tall ? rows : cols;
     const lap_lds L = lap_carve(lds, m, n);
-    yk_lap_wave(c, tall ? 1 : cols, tall ? cols : 1, m, n, L, lane);
-    return tall ? L.row4col : L.col4row;
+    yk_lap_wave(lap_matrix_cost{c, tall ? 1 : cols, tall ? cols : 1}, m, n, L, lane);
+    return lap_answer(L, tall);
 }
 
 // grid (F); dynamic LDS: the lap vectors of the largest frame

@@ -13,16 +13,16 @@
 //     row), and only the tracks whose cached row was just taken look again;
 //   - matching, assign = lap (a second instantiation of the kernel; the greedy one carries none of it): per stage and class the eligible
 //     tracks and rows are compacted by ballot into two index lists in LDS and motmetrics.lap's shortest augmenting paths run on the dense
-//     nr x nc problem, the smaller side as the solver's rows.  MATRIX-FREE: 1024 x cap float64 costs do not fit beside the tracks, so a cost
-//     is recomputed where it is read - tf_iou of two LDS-resident boxes, the optional score multiply, the gate, 1.0 - (double)s or 2^20 -
-//     which is LDS reads and VALU only.  Lanes own columns (lane, lane + 64, ...): a column's dual, distance, predecessor, flag and holder
-//     are written by its own lane during the search, one sweep relaxes and keeps the lane's first smallest distance, a wave reduction over
-//     (distance, column) gives np.argmin's first minimum.  The solver row's box is held in registers across the sweep.
+//     nr x nc problem, the smaller side as the solver's rows.  The solver is yk_lap.h's yk_lap_wave, the one yk_mot.hip's scores call; this
+//     unit gives it its costs (track_pair_cost).  MATRIX-FREE: 1024 x cap float64 costs do not fit beside the tracks, so a cost is
+//     recomputed where the solver reads it - tf_iou of two LDS-resident boxes, the optional score multiply, the gate, 1.0 - (double)s or
+//     2^20 - which is LDS reads and VALU only.  The solver row's box is held in registers across the sweep.
 // No atomics anywhere, so two calls give the same bytes.  A 2 x 2 filter and an arg-max have no matrix product in them: no MFMA.
 // Compiled with -ffp-contract=off: one rounding per operation, as track.py's float32 steps.
 #include <vector>
 
 #include "yk_common.h"
+#include "yk_lap.h"
 #include "yk_nms.h"
 
 #define YK_TRACK_WORDS 25                 // a track in the state: id, class, state, last frame | score, mean[8], cov[12]
@@ -30,9 +30,9 @@
 #define YK_TRACK_LDS_PER_TRACK 128        // the 25 words + predicted box (16) + matched row, best IoU, best row (12)
 #define YK_TRACK_LDS_PER_ROW 24
 // assign = lap, on top of the two above: a share of the solver's vectors and, per row, an entry of the class's index list (4; the tracks'
-// list lies where the greedy path keeps its best IoU, which lap never reads).  The vectors of the longer side (v, dist: 8 each; pred,
-// row4col, scanned: 4 each = YK_LAP_LDS_PER_COL) are carved for max(M, cap) entries and those of the shorter (u: 8; col4row: 4 =
-// YK_LAP_LDS_PER_ROW) for min(M, cap), which 28 bytes per track and per row cover whichever side is longer.
+// list lies where the greedy path keeps its best IoU, which lap never reads).  lap_carve's vectors of the longer side (YK_LAP_LDS_PER_COL
+// bytes an entry) are carved for max(M, cap) entries and those of the shorter (YK_LAP_LDS_PER_ROW) for min(M, cap), which 28 bytes per track
+// and per row cover whichever side is longer.
 #define YK_TRACK_LAP_LDS_PER_TRACK YK_LAP_LDS_PER_COL
 #define YK_TRACK_LAP_LDS_PER_ROW (4 + YK_LAP_LDS_PER_COL)
 #define YK_TRACK_LAP_FORBIDDEN 1048576.0  // 2^20: above any sum of 1024 allowed costs, and a power of two (track.py says why)
@@ -54,9 +54,7 @@ struct track_lds {
     float *Tbest;                         // [M] the IoU of the track's best free row in the running stage
     int *Tbrow;                           // [M] that row, or -1
     // assign = lap only
-    double *Sv, *Sdist, *Su;              // [max(M, cap)] column duals and tentative distances, [min(M, cap)] row duals
-    int *Spred, *Srow4col, *Sscanned;     // [max(M, cap)] each
-    int *Scol4row;                        // [min(M, cap)]
+    lap_lds S;                            // the solver's vectors: min(M, cap) rows, max(M, cap) columns
     int *Tidx, *Ridx;                     // [M], [cap] the stage's eligible tracks and rows of the running class, ascending
 };
 
@@ -108,11 +106,24 @@ __device__ __forceinline__ void scan_rows(const track_lds &L, int M, int i, int 
     L.Tbrow[i] = brow;
 }
 
+// does track i take part in a stage: unmatched in this frame, and its state in `states` (a bit set)
+__device__ __forceinline__ bool eligible(const track_lds &L, int M, int i, unsigned states) {
+    return L.Tm[i] < 0 && ((states >> L.Ti[2 * M + i]) & 1u);
+}
+
+// one chunk of a ballot compaction: the slot of this lane's item (`count` + the takers in the lanes below); `count` moves past the chunk's takers
+__device__ __forceinline__ int ballot_slot(bool take, unsigned long long below, int &count) {
+    const unsigned long long m = __ballot(take);
+    const int pos = count + __popcll(m & below);
+    count += __popcll(m);
+    return pos;
+}
+
 // one association stage: the tracks whose state is in `states` (a bit set) and that are unmatched against the free rows of `kind`
 template <bool FUSE>
 __device__ __forceinline__ void match_stage(const track_lds &L, int M, int lane, int n_live, int n_rows, unsigned states, int kind, float thr) {
     for (int i = lane; i < n_live; i += 64) {
-        if (L.Tm[i] < 0 && ((states >> L.Ti[2 * M + i]) & 1u)) {
+        if (eligible(L, M, i, states)) {
             scan_rows<FUSE>(L, M, i, n_rows, kind, thr);
         } else {
             L.Tbest[i] = -INFINITY;
@@ -149,107 +160,45 @@ __device__ __forceinline__ void match_stage(const track_lds &L, int M, int lane,
 
 // ---- assign = lap: motmetrics.lap on the stage's pairs of one class, matrix-free ---------------------------------------------------------
 
-// arg-min over (value asc, column asc) across the wave; col < 0 means "no candidate"
-__device__ __forceinline__ void track_wave_argmin(double &best, int &col) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const double ob = __shfl_xor(best, o, 64);
-        const int oc = __shfl_xor(col, o, 64);
-        if (oc >= 0 && (col < 0 || ob < best || (ob == best && oc < col))) {
-            best = ob;
-            col = oc;
-        }
-    }
-}
-
 // the cost of a pair: an allowed one (gate met; a NaN meets none) 1 - s in float64, a forbidden one 2^20
 __device__ __forceinline__ double lap_cost(float s, float thr) { return s >= thr ? 1.0 - (double)s : YK_TRACK_LAP_FORBIDDEN; }
 
+// yk_lap_wave's cost source: solver row i and column j are positions in rowlist and collist; the pair's cost is recomputed from the two boxes.
+// The solver row's box (and its score, where the rows of the frame are the solver's rows) stay in registers for the sweep.
+template <bool FUSE>
+struct track_pair_cost {
+    const track_lds &L;
+    const int *rowlist, *collist;
+    bool tall;
+    float thr;
+    struct row_costs {
+        const track_pair_cost &P;
+        float4 ob;
+        float os;
+        __device__ __forceinline__ double operator()(int j) const {
+            const int other = P.collist[j];
+            const float s = P.tall ? pair_sim<FUSE>(P.L.Pbox[other], ob, os) : pair_sim<FUSE>(ob, P.L.Rbox[other], FUSE ? P.L.Rs[other] : 0.f);
+            return lap_cost(s, P.thr);
+        }
+    };
+    __device__ __forceinline__ row_costs row(int i) const {
+        const int own = rowlist[i];
+        return {*this, tall ? L.Rbox[own] : L.Pbox[own], (FUSE && tall) ? L.Rs[own] : 0.f};
+    }
+};
+
 // One class of one stage by the wavefront: nt tracks (L.Tidx) x nr rows (L.Ridx), both ascending.  The solver's rows are the smaller side
-// (`tall`: more tracks than rows, the transpose, as motmetrics.lap); its m rows and n columns are positions in the two lists.  Every step of
-// the rule in its order: r = ((minval + c) - u[i]) - v[j], strict <, the first argmin among the unscanned columns, t = minval - dist[j].
+// (`tall`: more tracks than rows, the transpose, as motmetrics.lap); its m rows and n columns are positions in the two lists.
 // Leaves the allowed pairs in L.Tm and their rows R_TAKEN.
 template <bool FUSE>
 __device__ __forceinline__ void lap_solve_class(const track_lds &L, int lane, int nt, int nr, float thr) {
     const bool tall = nt > nr;
     const int m = tall ? nr : nt, n = tall ? nt : nr;
     const int *rowlist = tall ? L.Ridx : L.Tidx, *collist = tall ? L.Tidx : L.Ridx;
-    for (int j = lane; j < n; j += 64) {
-        L.Sv[j] = 0.0;
-        L.Srow4col[j] = -1;
-    }
-    for (int i = lane; i < m; i += 64) {
-        L.Su[i] = 0.0;
-        L.Scol4row[i] = -1;
-    }
-    __syncthreads();
-    for (int cur = 0; cur < m; ++cur) {
-        for (int j = lane; j < n; j += 64) {
-            L.Sdist[j] = INFINITY;
-            L.Spred[j] = -1;
-            L.Sscanned[j] = 0;
-        }
-        double minval = 0.0;
-        int i = cur, sink = -1;
-        while (sink < 0) {
-            const double ui = L.Su[i];
-            const int own = rowlist[i];                                  // the solver row's box (and score) stay in registers for the sweep
-            const float4 ob = tall ? L.Rbox[own] : L.Pbox[own];
-            const float os = (FUSE && tall) ? L.Rs[own] : 0.f;
-            double best = INFINITY;
-            int bcol = -1;
-            for (int j = lane; j < n; j += 64) {
-                if (L.Sscanned[j]) continue;
-                const int other = collist[j];
-                const float s = tall ? pair_sim<FUSE>(L.Pbox[other], ob, os) : pair_sim<FUSE>(ob, L.Rbox[other], FUSE ? L.Rs[other] : 0.f);
-                const double r = ((minval + lap_cost(s, thr)) - ui) - L.Sv[j];
-                double d = L.Sdist[j];
-                if (r < d) {
-                    d = r;
-                    L.Sdist[j] = r;
-                    L.Spred[j] = i;
-                }
-                if (bcol < 0 || d < best) {
-                    best = d;
-                    bcol = j;
-                }
-            }
-            track_wave_argmin(best, bcol);                               // (an unscanned column exists while no sink was found: m <= n)
-            minval = best;
-            if ((bcol & 63) == lane) L.Sscanned[bcol] = 1;
-            const int holder = L.Srow4col[bcol];
-            if (holder < 0) sink = bcol;
-            else i = holder;
-        }
-        __syncthreads();
-        // the duals: every scanned column but the sink is held by a row of its own, so no two lanes write one u
-        for (int j = lane; j < n; j += 64) {
-            if (!L.Sscanned[j]) continue;
-            const double t = minval - L.Sdist[j];
-            L.Sv[j] = L.Sv[j] - t;
-            if (j != sink) {
-                const int r = L.Srow4col[j];
-                L.Su[r] = L.Su[r] + t;
-            }
-        }
-        __syncthreads();
-        if (lane == 0) {
-            L.Su[cur] = L.Su[cur] + minval;
-            int j = sink;
-            for (;;) {
-                const int r = L.Spred[j];
-                L.Srow4col[j] = r;
-                const int next = L.Scol4row[r];
-                L.Scol4row[r] = j;
-                j = next;
-                if (r == cur) break;
-            }
-        }
-        __syncthreads();
-    }
+    yk_lap_wave(track_pair_cost<FUSE>{L, rowlist, collist, tall, thr}, m, n, L.S, lane);
     // every solver row holds a column (m <= n); the pair is kept where it is allowed.  Tracks and rows of distinct pairs are distinct.
     for (int i = lane; i < m; i += 64) {
-        const int a = rowlist[i], b = collist[L.Scol4row[i]];
+        const int a = rowlist[i], b = collist[L.S.col4row[i]];
         const int t = tall ? b : a, r = tall ? a : b;
         if (pair_sim<FUSE>(L.Pbox[t], L.Rbox[r], FUSE ? L.Rs[r] : 0.f) >= thr) {
             L.Tm[t] = r;
@@ -268,7 +217,7 @@ __device__ __forceinline__ void lap_stage(const track_lds &L, int M, int lane, u
         int c = 0x7fffffff;                                              // the lowest class above `prev` among the eligible tracks
         for (int i = lane; i < n_live; i += 64) {
             const int ci = L.Ti[1 * M + i];
-            if (L.Tm[i] < 0 && ((states >> L.Ti[2 * M + i]) & 1u) && ci > prev && ci < c) c = ci;
+            if (eligible(L, M, i, states) && ci > prev && ci < c) c = ci;
         }
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) c = min(c, __shfl_xor(c, o, 64));
@@ -277,18 +226,16 @@ __device__ __forceinline__ void lap_stage(const track_lds &L, int M, int lane, u
         int nt = 0, nr = 0;
         for (int base = 0; base < n_live; base += 64) {
             const int i = base + lane;
-            const bool take = i < n_live && L.Tm[i] < 0 && ((states >> L.Ti[2 * M + i]) & 1u) && L.Ti[1 * M + i] == c;
-            const unsigned long long mask = __ballot(take);
-            if (take) L.Tidx[nt + __popcll(mask & below)] = i;
-            nt += __popcll(mask);
+            const bool take = i < n_live && eligible(L, M, i, states) && L.Ti[1 * M + i] == c;
+            const int pos = ballot_slot(take, below, nt);
+            if (take) L.Tidx[pos] = i;
         }
         const int want = c * 4 + kind;
         for (int base = 0; base < n_rows; base += 64) {
             const int r = base + lane;
             const bool take = r < n_rows && L.Ri[r] == want;
-            const unsigned long long mask = __ballot(take);
-            if (take) L.Ridx[nr + __popcll(mask & below)] = r;
-            nr += __popcll(mask);
+            const int pos = ballot_slot(take, below, nr);
+            if (take) L.Ridx[pos] = r;
         }
         __syncthreads();
         if (nr > 0) lap_solve_class<FUSE>(L, lane, nt, nr, thr);
@@ -317,15 +264,11 @@ __global__ void __launch_bounds__(64) track_update_kernel(int32_t *__restrict__ 
     L.Tbest = reinterpret_cast<float *>(L.Tm + M);
     L.Tbrow = reinterpret_cast<int *>(L.Tbest + M);
     if constexpr (ASSIGN == YK_TRACK_ASSIGN_LAP) {                       // (128 M + 24 cap bytes lie before: a multiple of 8)
-        const int longer = max(M, cap), shorter = min(M, cap);
-        L.Sv = reinterpret_cast<double *>(L.Tbrow + M);
-        L.Sdist = L.Sv + longer;
-        L.Su = L.Sdist + longer;
-        L.Spred = reinterpret_cast<int *>(L.Su + shorter);
-        L.Srow4col = L.Spred + longer;
-        L.Sscanned = L.Srow4col + longer;
-        L.Scol4row = L.Sscanned + longer;
-        L.Ridx = L.Scol4row + shorter;
+        // lap_carve's vectors end lap_vector_bytes(shorter, longer) = 28 longer + 12 shorter bytes behind Tbrow, col4row [shorter] last:
+        // with Ridx [cap] behind it that is the 28 M + 32 cap of YK_TRACK_LAP_LDS_PER_TRACK / _PER_ROW at the most
+        const int shorter = min(M, cap);
+        L.S = lap_carve(L.Tbrow + M, shorter, max(M, cap));
+        L.Ridx = L.S.col4row + shorter;
         L.Tidx = reinterpret_cast<int *>(L.Tbest);                       // (Tbest and Tbrow are the greedy path's alone)
     }
     int *Ti = L.Ti;
@@ -381,14 +324,12 @@ __global__ void __launch_bounds__(64) track_update_kernel(int32_t *__restrict__ 
             const float h = b.z - b.x, w = b.w - b.y;
             const bool take = r < k_rows && cf >= 0.f && cf < (float)class_num && cf == floorf(cf) && sc >= low_thresh && h > 0.f && h < INFINITY &&
                               w > 0.f && w < INFINITY;
-            const unsigned long long m = __ballot(take);
+            const int pos = ballot_slot(take, below, n_rows);
             if (take) {
-                const int pos = n_rows + __popcll(m & below);
                 L.Rbox[pos] = b;
                 L.Rs[pos] = sc;
                 L.Ri[pos] = (int)cf * 4 + (sc >= track_thresh ? R_HIGH : R_LOW);
             }
-            n_rows += __popcll(m);
         }
         __syncthreads();
         // 3  the three associations
@@ -483,8 +424,7 @@ __global__ void __launch_bounds__(64) track_update_kernel(int32_t *__restrict__ 
         for (int base = 0; base < n_live; base += 64) {
             const int i = base + lane;
             const bool emit = i < n_live && TI(2, i) == T_TRACKED && TI(3, i) == frame;
-            const unsigned long long m = __ballot(emit);
-            const int pos = n_out + __popcll(m & below);
+            const int pos = ballot_slot(emit, below, n_out);
             if (emit && pos < cap) {
                 const float4 b = box_of(TF(1, i), TF(2, i), TF(3, i), TF(4, i));
                 const size_t at = (size_t)f * cap + pos;
@@ -506,7 +446,6 @@ __global__ void __launch_bounds__(64) track_update_kernel(int32_t *__restrict__ 
                     g[5] = (float)(TI(0, i) % 100);
                 }
             }
-            n_out += __popcll(m);
         }
         if (lane == 0) out_counts[f] = min(n_out, cap);
         __syncthreads();

@@ -8,9 +8,9 @@
   (iii) the same off run by the package of a second tree - a checkout of the parent commit, built, given with --parent.  Off has to agree
         with it within the spread of the repeats: the acceptance condition on speed;
   (iv)  on against off, recorded and not judged;
-  (v)   the call of (i) under --track_assign: greedy by the parent commit's tree, greedy and lap by this tree, fresh processes in turns.  The
-        two greedy rows have to agree within the spread of their own repeats; the lap row is recorded and not judged.  --only_assign
-        measures (v) alone and replaces it in --out.
+  (v)   the call of (i) under --track_assign: greedy and lap by the parent commit's tree, greedy and lap by this tree, fresh processes in
+        turns.  The two greedy rows have to agree within the spread of their own repeats, and so have the two lap rows; lap against greedy
+        is recorded and not judged.  --only_assign measures (v) alone and replaces it in --out.
 (ii) - (iv): every measurement is a fresh child process of this file (--child) that imports the package of ONE tree, runs a warm-up and then
 --runs timed runs; the kinds (off, parent off, on) take turns, --rounds times, so each has rounds * runs repeats taken in one session.
 Medians and the spread (min .. max) of the repeats.  Needs an MI355X; there is no CPU path.
@@ -53,7 +53,7 @@ def case_rows():
 
 def assign_child(tree: str, assign: str, repeats: int):
     """One process, one tree's package: the cases of (i) under `assign`, three warm-up calls and `repeats` timed ones each -> a JSON line of
-    ms per call.  The parent commit's tree has no `assign`, and is only asked for greedy."""
+    ms per call."""
     sys.path.insert(0, tree)
     import torch
     from k210_yolo_framework_amd import engine
@@ -82,9 +82,10 @@ def assign_child(tree: str, assign: str, repeats: int):
 
 
 def assign_rates(parent: str, rounds: int, repeats: int, lines):
-    """(v): one yk_track_update call under greedy by the parent commit's tree, greedy by this tree and lap by this tree, fresh processes in
-    turns.  -> do the two greedy rows agree within the spread of their own repeats, in every case"""
-    kinds = {'greedy, parent commit': (str(Path(parent).resolve()), 'greedy'), 'greedy': (str(ROOT), 'greedy'), 'lap': (str(ROOT), 'lap')}
+    """(v): one yk_track_update call under greedy and under lap, each by the parent commit's tree and by this tree, fresh processes in
+    turns.  -> do the two rows of either kind agree within the spread of their own repeats, in every case"""
+    kinds = {f'{assign}{who}': (tree, assign) for assign in ('greedy', 'lap')
+             for who, tree in ((', parent commit', str(Path(parent).resolve())), ('', str(ROOT)))}
     times = {k: {name: [] for name in case_rows()} for k in kinds}
     for _ in range(rounds):
         for kind, (tree, assign) in kinds.items():
@@ -100,11 +101,12 @@ def assign_rates(parent: str, rounds: int, repeats: int, lines):
     for name in case_rows():
         lines.append(f'    {name}')
         lines += [f'      {kind + ":":24s}{spread(times[kind][name])}' for kind in kinds]
-        old, new = times['greedy, parent commit'][name], times['greedy'][name]
-        inside = min(old) <= np.median(new) <= max(old) and min(new) <= np.median(old) <= max(new)
-        agree &= bool(inside)
-        lines.append(f'      greedy / parent = {np.median(new) / np.median(old):.3f}; each median lies {"INSIDE" if inside else "OUTSIDE"} the other\'s min .. max.  '
-                     f'lap / greedy = {np.median(times["lap"][name]) / np.median(new):.2f} (recorded, not judged)')
+        for assign in ('greedy', 'lap'):
+            old, new = times[f'{assign}, parent commit'][name], times[assign][name]
+            inside = min(old) <= np.median(new) <= max(old) and min(new) <= np.median(old) <= max(new)
+            agree &= bool(inside)
+            lines.append(f'      {assign} / parent = {np.median(new) / np.median(old):.3f}; each median lies {"INSIDE" if inside else "OUTSIDE"} the other\'s min .. max')
+        lines.append(f'      lap / greedy = {np.median(times["lap"][name]) / np.median(times["greedy"][name]):.2f} (recorded, not judged)')
     lines.append('    not measured: the solver\'s worst case (a stage of one class in which every augmentation walks every row: rows x rows x '
                  'columns / 64 lane steps); these rows have twenty classes and boxes that stay apart')
     return agree
